@@ -20,6 +20,8 @@ ABI_SYMBOLS = (
     "bhw_sincos_to_host", "bhw_release_device", "bhw_apply_device", "bhw_atan2_device", "bhw_atan2_to_host",
     "bhw_prepare_device", "bhw_part_segments", "bhw_generate_part_device", "bhw_describe_plan",
     "bhw_coeffs_preset", "bhw_gather_parts_device", "bhw_workspace_bytes_ex",
+    "bhw_table_create", "bhw_table_destroy", "bhw_table_bytes", "bhw_table_describe", "bhw_generate_from_table",
+    "bhw_apply_from_table", "bhw_generate_part_from_table",
 )
 
 
@@ -109,6 +111,18 @@ def lib():
     L.bhw_part_segments.argtypes = [P, u32, u32, ctypes.POINTER(BhwSegment), u32, ctypes.POINTER(u32)]
     L.bhw_generate_part_device.argtypes = [P, ci, vp, u32, u32, i32p, ctypes.POINTER(BhwExec)]
     L.bhw_apply_device.argtypes = [P, ci, vp, u64, u64, i32p, i32p, u32]
+    T = ctypes.c_void_p                                     # bhw_table (opaque handle)
+    L.bhw_table_create.argtypes = [P, ci, vp, u32, ctypes.POINTER(T)]
+    L.bhw_table_destroy.argtypes = [T]
+    L.bhw_table_bytes.restype = u64
+    L.bhw_table_bytes.argtypes = [T]
+    L.bhw_table_describe.argtypes = [T, P, u64, u64, ctypes.c_char_p, u64]
+    L.bhw_generate_from_table.argtypes = [T, P, vp, u64, u64, i32p]
+    L.bhw_apply_from_table.argtypes = [T, P, vp, u64, u64, i32p, i32p, u32]
+    L.bhw_generate_part_from_table.argtypes = [T, P, vp, u32, u32, i32p]
+    L.bhw_dbg_table_key_matches.argtypes = [P, P]
+    L.bhw_dbg_describe_from_table.argtypes = [P, u32, P, u64, u64, ctypes.c_char_p, u64]
+    L.bhw_dbg_generate_from_table_generic.argtypes = [T, P, vp, u64, u64, i32p]
     PA = ctypes.POINTER(BhwAtan2Params)
     L.bhw_atan2_device.argtypes = [PA, ci, vp, u64, i32p, i32p, i32p]
     L.bhw_atan2_to_host.argtypes = [PA, ci, u64, i32p, i32p, i32p]
@@ -132,6 +146,14 @@ def describe_plan(params, n0, count, algo=ALGO_AUTO, table_format=TABLE_BEST):
     ex.table_format = table_format
     buf = ctypes.create_string_buffer(256)
     check(lib().bhw_describe_plan(ctypes.byref(params), int(n0), int(count), ctypes.byref(ex), buf, 256))
+    return buf.value.decode()
+
+
+def describe_table(table, params, n0, count):
+    """One line: the resident table's format, layout and bytes, and the kernels a from-table call of (params, n0, count) launches
+    (bhw_table_describe; `table` is the handle, e.g. ResidentTable.handle)."""
+    buf = ctypes.create_string_buffer(384)
+    check(lib().bhw_table_describe(table, ctypes.byref(params), int(n0), int(count), buf, 384))
     return buf.value.decode()
 
 

@@ -11,6 +11,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <new>
 #include <vector>
 
 #include "bhw_plan.h"
@@ -790,6 +791,213 @@ int bhw_prepare_device(const bhw_params *p, int device, void *hip_stream)
         if (rc) return rc;
     }
     return BHW_OK;
+}
+
+// ---- resident tables (include/bhw.h: bhw_table_create ...) -------------------------------------------------------------------------
+// One first-quadrant table of a configuration's CORDIC generics in one device allocation, immutable after create.  The calls that
+// read it take no lock, allocate nothing, neither synchronise nor read anything back and never touch the library scratch, so they
+// can be captured into a graph on any stream.  Decisions from parameters alone (key match, layout, format candidates, the kernel of
+// each piece) are bhw_plan.cpp's.
+
+} // extern "C"
+
+struct bhw_table_s {
+    int device;
+    bhw_params key;        // the generics the table was built from (only model / widths / precision matter)
+    BhwCordicCfg c;        // resolved, with the format and the pointers of the table's records / escape lists set
+    bool tiled;            // whole periods take the tile kernel (split packed layout at z_shr == 0)
+    void *buf;
+    uint64_t bytes;
+};
+
+namespace {
+
+void point_table(BhwCordicCfg &c, uint32_t dlog, void *buf)
+{
+    const BhwTableLayout lay = bhwp_table_layout(bhwp_table_entries(c), dlog);
+    c.tab_dlog = dlog;
+    c.tab_coarse = dlog ? (const void *)((const char *)buf + lay.coarse_off) : nullptr;
+    c.tab_esc = lay.esc_off ? (const void *)((const char *)buf + lay.esc_off) : nullptr;
+    c.esc_wg_log = lay.esc_wg_log;
+    c.tab_check = nullptr;
+}
+
+// Settles the verdict of packed format `dlog` for `p` by a trial build with the overflow check into a temporary buffer
+int trial_build(const bhw_params *p, const BhwLaunch &l, BhwCordicCfg c, uint32_t dlog)
+{
+    const BhwTableLayout lay = bhwp_table_layout(bhwp_table_entries(c), dlog);
+    void *tmp = nullptr;
+    hipError_t he = hipMalloc(&tmp, lay.bytes);
+    if (he != hipSuccess) return fail_hip(he, "hipMalloc(trial table)");
+    point_table(c, dlog, tmp);
+    c.tab_check = (uint32_t *)((char *)tmp + lay.check_off);
+    uint32_t flag = 1;
+    he = hipMemsetAsync(c.tab_check, 0, 8, (hipStream_t)l.stream);
+    int e = he == hipSuccess ? bhwk_table_build(l, c, (int32_t *)tmp) : (int)he;
+    if (!e) e = hipMemcpyAsync(&flag, c.tab_check, sizeof flag, hipMemcpyDeviceToHost, (hipStream_t)l.stream);
+    if (!e) e = hipStreamSynchronize((hipStream_t)l.stream);
+    (void)hipFree(tmp);
+    if (e) return fail_hip(e, "trial build of a packed table format");
+    bhwp_fmt_set_verdict(p, dlog, flag ? kFmtBad : kFmtOk);
+    return BHW_OK;
+}
+
+// the prologue of every from-table call: the handle, `p` validated and matched to the table's generics
+int table_call_checks(bhw_table t, const bhw_params *p)
+{
+    if (!t) return fail(BHW_ERR_BADARG, "table is NULL");
+    const int rc = bhwp_validate(p);
+    return rc ? rc : bhwp_table_key_check(&t->key, p);
+}
+
+int from_table(bhw_table t, const bhw_params *p, void *stream, uint64_t n0, uint64_t count, int32_t *d_out,
+               const int32_t *apply_x = nullptr, uint32_t apply_shift = 0, bool generic_ragged = false)
+{
+    int rc = table_call_checks(t, p);
+    if (rc) return rc;
+    if (count && !d_out) return fail(BHW_ERR_BADARG, "d_out is NULL");
+    if (!count) return BHW_OK;
+    if (count > (1ull << 34)) return fail(BHW_ERR_BADARG, "count %llu > 2^34 per call", (unsigned long long)count);
+    DeviceGuard guard(t->device);
+    if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
+    const BhwLaunch l{t->device, stream};
+    const BhwCordicCfg &c = t->c;
+    const int32_t *tab = (const int32_t *)t->buf;
+    BhwWinCfg w;
+    bhwp_resolve_window(p, w);
+    w.apply_x = apply_x;
+    w.apply_shift = apply_shift;
+    // head | whole periods | tail as generate_impl splits a table-strategy call, every piece over the one resident table
+    const BhwTableCall tc = bhwp_table_call(p, c, w, n0, count, apply_x != nullptr);
+    if (tc.images) {
+        const int e = bhwk_table_combine_tile_range(l, c, w, tab, d_out, 0, 0, tc.img_mask, tc.n0mod);
+        return e ? fail_hip(e, "tile launch (image subset)") : BHW_OK;
+    }
+    auto ragged = [&](uint64_t off, uint64_t len) -> int {
+        if (apply_x) w.apply_x = apply_x + off;
+        return generic_ragged ? bhwk_table_combine(l, c, w, tab, n0 + off, len, d_out + off)
+                              : bhwk_range_combine(l, c, w, tab, n0 + off, len, d_out + off);
+    };
+    auto period = [&](uint64_t off) -> int {
+        if (apply_x) w.apply_x = apply_x + off;
+        if (bhwk_runlength_applicable(c, w, d_out + off)) return bhwk_runlength_window(l, c, w, tab, d_out + off);
+        return t->tiled ? bhwk_table_combine_tile(l, c, w, tab, d_out + off) : bhwk_table_combine_fold(l, c, w, tab, d_out + off);
+    };
+    return run_split(l, n0, count, 1ull << p->phi_width, apply_x != nullptr, d_out, ragged, period);
+}
+
+} // namespace
+
+extern "C" {
+
+int bhw_table_create(const bhw_params *p, int device, void *hip_stream, uint32_t table_format, bhw_table *out)
+{
+    if (!out) return fail(BHW_ERR_BADARG, "out is NULL");
+    *out = nullptr;
+    int rc = bhwp_table_create_checks(p, table_format);
+    if (rc) return rc;
+    if (!device_ok(device)) return fail(BHW_ERR_HIP, "no usable HIP device %d (this library has no CPU path)", device);
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
+    const BhwLaunch l{device, hip_stream};
+    BhwCordicCfg c;
+    bool tiled;
+    bhwp_resident_layout(p, c, &tiled);
+    // the narrowest format under `table_format` that is exact for the configuration: open verdicts are settled by trial builds
+    uint32_t cand[kMaxFormats];
+    const int n_cand = bhwp_table_format_candidates(c, tiled, table_format, cand);
+    uint32_t keep = 0;
+    for (int i = 0; i < n_cand; ++i) {
+        if (!cand[i]) break;                                            // plain: always exact, the last candidate
+        if (bhwp_fmt_verdict(p, cand[i]) == kFmtUnknown) {
+            rc = trial_build(p, l, c, cand[i]);
+            if (rc) return rc;
+        }
+        if (bhwp_fmt_verdict(p, cand[i]) == kFmtOk) { keep = cand[i]; break; }
+    }
+    const uint64_t bytes = bhwp_table_layout(bhwp_table_entries(c), keep).bytes;
+    void *buf = nullptr;
+    hipError_t he = hipMalloc(&buf, bytes);
+    if (he != hipSuccess) return fail_hip(he, "hipMalloc(resident table)");
+    point_table(c, keep, buf);
+    int e = bhwk_table_build(l, c, (int32_t *)buf);
+    if (!e) e = hipStreamSynchronize((hipStream_t)hip_stream);
+    if (e) {
+        (void)hipFree(buf);
+        return fail_hip(e, "resident table build");
+    }
+    bhw_table t = new (std::nothrow) bhw_table_s{device, *p, c, tiled, buf, bytes};
+    if (!t) {
+        (void)hipFree(buf);
+        return fail(BHW_ERR_HIP, "out of host memory");
+    }
+    *out = t;
+    return BHW_OK;
+}
+
+int bhw_table_destroy(bhw_table t)
+{
+    if (!t) return BHW_OK;
+    {
+        DeviceGuard guard(t->device);
+        if (guard.err == hipSuccess) {
+            (void)hipDeviceSynchronize();                               // launches still reading it finish first
+            (void)hipFree(t->buf);
+        }
+    }
+    delete t;
+    return BHW_OK;
+}
+
+uint64_t bhw_table_bytes(bhw_table t) { return t ? t->bytes : 0; }
+
+int bhw_table_describe(bhw_table t, const bhw_params *p, uint64_t n0, uint64_t count, char *buf, uint64_t len)
+{
+    const int rc = table_call_checks(t, p);
+    return rc ? rc : bhwp_describe_from_table(p, t->c, t->tiled, n0, count, buf, len);
+}
+
+int bhw_generate_from_table(bhw_table t, const bhw_params *p, void *hip_stream, uint64_t n0, uint64_t count, int32_t *d_out)
+{
+    return from_table(t, p, hip_stream, n0, count, d_out);
+}
+
+int bhw_apply_from_table(bhw_table t, const bhw_params *p, void *hip_stream, uint64_t n0, uint64_t count,
+                         const int32_t *d_x, int32_t *d_y, uint32_t shift)
+{
+    if (count && (!d_x || !d_y)) return fail(BHW_ERR_BADARG, "d_x / d_y is NULL");
+    if (shift > 62) return fail(BHW_ERR_BADARG, "shift %u > 62", shift);
+    const uintptr_t xa = (uintptr_t)d_x, ya = (uintptr_t)d_y, nb = (uintptr_t)count * 4u;
+    if (count && xa < ya + nb && ya < xa + nb) return fail(BHW_ERR_BADARG, "d_y must not overlap d_x (tile seams recompute a few samples)");
+    return from_table(t, p, hip_stream, n0, count, d_y, d_x, shift);
+}
+
+int bhw_generate_part_from_table(bhw_table t, const bhw_params *p, void *hip_stream, uint32_t part, uint32_t n_parts, int32_t *d_window)
+{
+    if (!t) return fail(BHW_ERR_BADARG, "table is NULL");
+    int rc = bhwp_part_checks(p, part, n_parts);
+    if (!rc) rc = bhwp_table_key_check(&t->key, p);
+    if (rc) return rc;
+    if (!d_window) return fail(BHW_ERR_BADARG, "d_window is NULL");
+    if (!t->tiled)
+        return fail(BHW_ERR_UNSUPPORTED, "parts from a table need the tile layout (phi_width >= 22); shorter windows' parts are the fused kernel's");
+    BhwWinCfg w;
+    bhwp_resolve_window(p, w);
+    BhwFoldRun runs[32];
+    uint32_t tile0 = 0, tile_count = 0;
+    if (bhwk_part_runs(t->c, w, part, n_parts, runs, &tile0, &tile_count) == 0 || tile_count == 0) return BHW_OK;
+    DeviceGuard guard(t->device);
+    if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
+    const BhwLaunch l{t->device, hip_stream};
+    const int e = bhwk_table_combine_tile_range(l, t->c, w, (const int32_t *)t->buf, d_window, tile0, tile_count);
+    return e ? fail_hip(e, "tile part launch") : BHW_OK;
+}
+
+// Development hook (not part of the ABI in include/bhw.h): bhw_generate_from_table with every ragged piece on the general gather
+// kernel k_table_combine (format read at run time) instead of k_range_combine -- the A/B of tools/bench_resident_table.py.
+int bhw_dbg_generate_from_table_generic(bhw_table t, const bhw_params *p, void *hip_stream, uint64_t n0, uint64_t count, int32_t *d_out)
+{
+    return from_table(t, p, hip_stream, n0, count, d_out, nullptr, 0, true);
 }
 
 // Bytes the library-owned scratch of (device, hip_stream) holds right now (0: none yet) -- what bench.py reports beside the size of

@@ -84,6 +84,9 @@ int bhwk_replicate(const BhwLaunch &l, const int32_t *d_frame, uint64_t frame_le
 int bhwk_table_build(const BhwLaunch &l, const BhwCordicCfg &c, int32_t *d_table /* (c,s) pairs, 2^(PW-2) */);
 int bhwk_table_combine(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *d_table,
                        uint64_t n0, uint64_t count, int32_t *d_out);
+// any range [n0, n0 + count) over a resident table in any format (bhw_range.hip): k_range_combine, one gather per harmonic
+int bhwk_range_combine(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *d_table,
+                       uint64_t n0, uint64_t count, int32_t *d_out);
 // whole-period cordic() sweep through the shared-prefix chains of the table build (bhwk_sincos picks it for periods >= 2^16)
 int bhwk_sincos_sweep(const BhwLaunch &l, const BhwCordicCfg &c, uint64_t theta0, int32_t *d_sin, int32_t *d_cos);
 // Predicates and shapes below that take no BhwLaunch are host arithmetic only and live in the HIP-free bhw_plan.cpp.

@@ -633,6 +633,84 @@ void bhwk_describe_table(const BhwCordicCfg &c_in, const BhwWinCfg &w, bool tile
     else snprintf(combine, len, "k_table_combine_fold");
 }
 
+// ---- resident tables ------------------------------------------------------------------------------------------------------------
+
+int bhwp_table_create_checks(const bhw_params *p, uint32_t table_format)
+{
+    if (!p) return bhwp_fail(BHW_ERR_BADARG, "params is NULL");
+    const int rc = bhwp_validate(p);        // (cordic_dds48 / cordic_dds_scaled: UNSUPPORTED, they feed no window)
+    if (rc) return rc;
+    if (p->sin_type != BHW_SIN_CORDIC)
+        return bhwp_fail(BHW_ERR_UNSUPPORTED, "resident tables hold the CORDIC table; the Taylor ROM is cached by the library already");
+    if (table_format > BHW_TABLE_NIBBLE_ESC) return bhwp_fail(BHW_ERR_BADARG, "table_format %u", table_format);
+    return BHW_OK;
+}
+
+// The table depends on the CORDIC generics only -- the fields fmt_key() keys the format verdicts by.
+int bhwp_table_key_check(const bhw_params *pt, const bhw_params *p)
+{
+    if (!pt || !p) return bhwp_fail(BHW_ERR_BADARG, "params is NULL");
+    if (p->sin_type != BHW_SIN_CORDIC) return bhwp_fail(BHW_ERR_BADARG, "sin_type %u: a resident table serves the CORDIC source only", p->sin_type);
+    if (p->model != pt->model) return bhwp_fail(BHW_ERR_BADARG, "model %u differs from the table's %u", p->model, pt->model);
+    if (p->phi_width != pt->phi_width)
+        return bhwp_fail(BHW_ERR_BADARG, "phi_width %u differs from the table's %u", p->phi_width, pt->phi_width);
+    if (p->dat_width != pt->dat_width)
+        return bhwp_fail(BHW_ERR_BADARG, "dat_width %u differs from the table's %u", p->dat_width, pt->dat_width);
+    if (p->model == BHW_MODEL_VHDL && p->precision != pt->precision)
+        return bhwp_fail(BHW_ERR_BADARG, "precision %u differs from the table's %u", p->precision, pt->precision);
+    return BHW_OK;
+}
+
+void bhwp_resident_layout(const bhw_params *p, BhwCordicCfg &c, bool *tiled)
+{
+    bhwp_resolve_cordic(p, c);
+    BhwWinCfg w;
+    bhwp_resolve_window(p, w);
+    *tiled = bhwk_tile_applicable(c, w);                  // (a property of phi_width alone: the weights do not enter)
+    c.tab_split = (*tiled && c.z_shr == 0) ? 1u : 0u;
+}
+
+bool bhwp_range_form(const BhwCordicCfg &c, const BhwWinCfg &w, int *fmt, int *nt, int *mode)
+{
+    *fmt = fmt_of(c.tab_dlog);
+    *nt = w.n_terms <= 3 ? 3 : w.n_terms <= 5 ? 5 : 7;
+    *mode = mode_of(c, w);
+    return *fmt == 0 || *fmt == 1 || *fmt == 2 || *fmt == 3 || *fmt == 5;
+}
+
+int bhwp_describe_from_table(const bhw_params *p, const BhwCordicCfg &ct, bool tiled, uint64_t n0, uint64_t count, char *buf, uint64_t len)
+{
+    if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
+    const BhwCordicCfg c = table_layout(ct);
+    BhwWinCfg w;
+    bhwp_resolve_window(p, w);
+    const uint64_t N = 1ull << p->phi_width, E = bhwp_table_entries(c);
+    const char *fmt = c.tab_dlog == 0 ? "plain" : c.tab_dlog == kPackLog ? "delta16" : c.tab_dlog >= kEscFlag ? "nibble+esc" : c.tab_dlog >= kNibbleFlag ? "nibble" : "residual";
+    char ragged[64], period[128], build[64], combine[96];
+    int rf, rn, rm;
+    if (bhwp_range_form(c, w, &rf, &rn, &rm)) snprintf(ragged, sizeof ragged, "k_range_combine<%d,%d,%d>", rf, rn, rm);
+    else snprintf(ragged, sizeof ragged, "k_table_combine");
+    const BhwTableCall t = bhwp_table_call(p, c, w, n0, count, false);
+    bhwk_describe_table(c, w, tiled || t.images, t.images, build, combine, sizeof build);
+    if (bhwk_runlength_applicable(c, w, nullptr))
+        snprintf(period, sizeof period, "k_runlength_window<%u,%d,%s> (16-byte aligned output; else %s)", p->n_terms, mode_of(c, w),
+                 c.dat_width <= 16 ? "true" : "false", combine);
+    else snprintf(period, sizeof period, "%s", combine);
+    const uint64_t head = (N - n0 % N) % N;
+    const uint64_t periods = t.has_period ? (count - head) / N : 0, tail = t.has_period ? count - head - periods * N : 0;
+    char calls[320];
+    if (!count) snprintf(calls, sizeof calls, "nothing");
+    else if (t.images) snprintf(calls, sizeof calls, "%s (image subset)", combine);
+    else if (!t.has_period) snprintf(calls, sizeof calls, "%s", ragged);
+    else {
+        const std::string ends = head || tail ? std::string(" + ") + ragged + " on the ragged ends" : std::string();
+        snprintf(calls, sizeof calls, "%s%s%s", period, periods > 1 ? " + k_replicate" : "", ends.c_str());
+    }
+    snprintf(buf, len, "resident table[%s, %s, %llu bytes]: %s", fmt, c.tab_split ? "split" : "natural",
+             (unsigned long long)bhwp_table_layout(E, c.tab_dlog).bytes, calls);
+    return BHW_OK;
+}
+
 // ---- the pure entry points of the C ABI (include/bhw.h) -------------------------------------------------------------------------------
 extern "C" {
 
@@ -850,6 +928,31 @@ int bhw_dbg_table_format_verdict(const bhw_params *p, uint32_t dlog, int set)
     if (bhwp_validate(p)) return BHW_ERR_BADARG;
     if (set) bhwp_fmt_set_verdict(p, dlog, set);
     return bhwp_fmt_verdict(p, dlog);
+}
+
+// The key check of the resident tables on its own (no device): BHW_OK when a table built from p_table serves calls with p_call.
+int bhw_dbg_table_key_matches(const bhw_params *p_table, const bhw_params *p_call)
+{
+    int rc = bhwp_table_create_checks(p_table, BHW_TABLE_BEST);
+    if (!rc) rc = bhwp_validate(p_call);
+    return rc ? rc : bhwp_table_key_check(p_table, p_call);
+}
+
+// bhw_table_describe from parameters alone (no device, no table): the table of p_table as bhw_table_create would hold it if
+// every packed format under `table_format` were exact (the first candidate), and the kernels a call of (p_call, n0, count) launches.
+int bhw_dbg_describe_from_table(const bhw_params *p_table, uint32_t table_format, const bhw_params *p_call, uint64_t n0, uint64_t count,
+                                char *buf, uint64_t len)
+{
+    int rc = bhw_dbg_table_key_matches(p_table, p_call);
+    if (!rc && table_format > BHW_TABLE_NIBBLE_ESC) rc = bhwp_fail(BHW_ERR_BADARG, "table_format %u", table_format);
+    if (rc) return rc;
+    BhwCordicCfg c;
+    bool tiled;
+    bhwp_resident_layout(p_table, c, &tiled);
+    uint32_t cand[kMaxFormats];
+    bhwp_table_format_candidates(c, tiled, table_format, cand);
+    c.tab_dlog = cand[0];
+    return bhwp_describe_from_table(p_call, c, tiled, n0, count, buf, len);
 }
 
 // tab_dlog the residual format would use for `p` (0: not applicable) and whether delta16 applies

@@ -116,6 +116,23 @@ struct BhwTableCall {
 };
 BhwTableCall bhwp_table_call(const bhw_params *p, const BhwCordicCfg &c, const BhwWinCfg &w, uint64_t n0, uint64_t count, bool apply);
 
+// ---- resident tables (bhw_table_create and the *_from_table calls) ------------------------------------------------------------
+// Argument checks of bhw_table_create, before any HIP call: BADARG / UNSUPPORTED as documented in bhw.h.
+int  bhwp_table_create_checks(const bhw_params *p, uint32_t table_format);
+// `p` may be used with a table built from `pt`: same model, phi_width, dat_width (and precision, VHDL model), CORDIC source.
+// BHW_ERR_BADARG naming the first field that differs.  aa, n_terms, win_type and combine are free.
+int  bhwp_table_key_check(const bhw_params *pt, const bhw_params *p);
+// The layout a resident table of `p` is held in: resolves `c` and sets c.tab_split; *tiled = whole periods take the tile kernel
+// (split layout at z_shr == 0, the one-run tile form over the natural layout otherwise), else the fold / run-length kernels
+// over the natural plain table.
+void bhwp_resident_layout(const bhw_params *p, BhwCordicCfg &c, bool *tiled);
+// Kernel of a ragged piece over a resident table: k_range_combine<fmt, nt, mode> (nt: the term-count bound 3, 5 or 7 of the
+// instance).  Every table format a resident table can hold has instances, so this never declines today; false would send the
+// piece to k_table_combine (format read at run time).
+bool bhwp_range_form(const BhwCordicCfg &c, const BhwWinCfg &w, int *fmt, int *nt, int *mode);
+// bhw_table_describe: one line for a from-table call of (p, n0, count) over a table whose c.tab_dlog / c.tab_split are set
+int  bhwp_describe_from_table(const bhw_params *p, const BhwCordicCfg &ct, bool tiled, uint64_t n0, uint64_t count, char *buf, uint64_t len);
+
 // ownership parts
 int  bhwp_part_checks(const bhw_params *p, uint32_t part, uint32_t n_parts);
 // strategy of bhw_generate_part_device: true = fused kernel over the part's runs, false = full table + the part's tiles; rc != 0: neither applies

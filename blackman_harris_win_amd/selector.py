@@ -142,6 +142,95 @@ def apply(params, x, *, n0=0, shift=None, out=None):
     return out
 
 
+class ResidentTable:
+    """A first-quadrant CORDIC table built once and kept on the device (bhw_table_create): the elaboration of win_selector's
+    CORDIC from its generics (model, PHI_WIDTH, DAT_WIDTH, PRECISION).  Every call then takes the run-time ports -- the weights
+    aa, n_terms, combine -- from its own `params` and reads the same table: no rebuild, no allocation, no synchronisation, so
+    the calls can be captured into a graph.  `params` must match the table's generics (BhwError otherwise).  A context manager;
+    close() frees the table (after the device has finished with it; a captured graph must not replay it afterwards)."""
+
+    def __init__(self, params, *, device=None, table_format=B.TABLE_BEST):
+        torch = _torch()
+        self.device = _dev_index(torch, device)
+        self.params = B.BhwParams.from_buffer_copy(params)
+        h = ctypes.c_void_p()
+        B.check(B.lib().bhw_table_create(ctypes.byref(self.params), self.device, _stream_ptr(torch, self.device),
+                                         int(table_format), ctypes.byref(h)))
+        self.handle = h
+
+    def close(self):
+        if self.handle:
+            B.lib().bhw_table_destroy(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        import sys
+        if sys.is_finalizing():              # the HIP runtime may already be gone: the process exit frees the table
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _live(self):
+        if not self.handle:
+            raise ValueError("the resident table has been closed")
+        return self.handle
+
+    @property
+    def nbytes(self):
+        """Device bytes the table holds (bhw_table_bytes)."""
+        return int(B.lib().bhw_table_bytes(self._live()))
+
+    def describe(self, params, n0, count):
+        """The table's format / layout and the kernels generate(params, n0, count) launches (bhw_table_describe)."""
+        return B.describe_table(self._live(), params, n0, count)
+
+    def generate(self, params, n0, count, out=None):
+        """count coefficients from stream index n0 with params' weights (bhw_generate_from_table), on the current stream."""
+        torch = _torch()
+        h = self._live()
+        if out is None:
+            out = torch.empty(int(count), dtype=torch.int32, device=f"cuda:{self.device}")
+        elif _check_out(torch, out, int(count)) != self.device:
+            raise ValueError("out must live on the table's device")
+        B.check(B.lib().bhw_generate_from_table(h, ctypes.byref(params), _stream_ptr(torch, self.device), int(n0), int(count),
+                                                ctypes.c_void_p(out.data_ptr())))
+        return out
+
+    def apply(self, params, x, n0=0, shift=None, out=None):
+        """y[i] = (x[i] * w[n0+i]) >> shift (bhw_apply_from_table); shift defaults to dat_width - 1."""
+        torch = _torch()
+        h = self._live()
+        if x.dtype != torch.int32 or not x.is_cuda or not x.is_contiguous() or x.device.index != self.device:
+            raise ValueError("x must be a contiguous int32 CUDA tensor on the table's device")
+        if out is None:
+            out = torch.empty_like(x)
+        elif _check_out(torch, out, x.numel()) != self.device:
+            raise ValueError("out must live on the table's device")
+        if shift is None:
+            shift = params.dat_width - 1
+        B.check(B.lib().bhw_apply_from_table(h, ctypes.byref(params), _stream_ptr(torch, self.device), int(n0), x.numel(),
+                                             ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr()), int(shift)))
+        return out
+
+    def generate_part(self, params, part, n_parts, window):
+        """Interleaved ownership part `part` of `n_parts` into the full-length `window` (bhw_generate_part_from_table)."""
+        torch = _torch()
+        h = self._live()
+        if _check_out(torch, window, 1 << params.phi_width, "window") != self.device:
+            raise ValueError("window must live on the table's device")
+        B.check(B.lib().bhw_generate_part_from_table(h, ctypes.byref(params), _stream_ptr(torch, self.device), int(part),
+                                                     int(n_parts), ctypes.c_void_p(window.data_ptr())))
+        return window
+
+
 def generate_batched(params, frames, *, device=None, out=None):
     """frames x 2^phi_width coefficients: one period computed, then replicated (bhw_generate_batched_device)."""
     torch = _torch()
@@ -216,6 +305,7 @@ class WinSelector:
             sin_type=self._sin_type(SIN_TYPE, _WIN_TYPES[WIN_TYPE]),
             precision=precision, lut_size=LUT_SIZE, aa=aa)
         self._phase = 0  # the PHI_WIDTH-bit counter (RESET clears it: bh_win_7term.vhd:179-186)
+        self._table = None  # ResidentTable of the generics after elaborate()
 
     @staticmethod
     def _sin_type(SIN_TYPE, win_type):
@@ -235,20 +325,51 @@ class WinSelector:
     def reset(self):
         self._phase = 0
 
+    def elaborate(self, table_format=B.TABLE_BEST):
+        """Build the CORDIC table of the generics once (ResidentTable) -- what elaboration does for the entity.  Afterwards
+        enable / apply / window / shard(layout="interleaved") read it, and a change of self.params.aa between calls is a change
+        on the AA ports: it takes effect from the next call, with no rebuild.  Nothing to keep for the Taylor source (its ROM is
+        cached by the library): a no-op there."""
+        if self.params.sin_type != B.SIN_CORDIC or self._table is not None:
+            return self
+        self._table = ResidentTable(self.params, device=self.device, table_format=table_format)
+        return self
+
+    def release(self):
+        """Free the table elaborate() built (the calls go back to the per-call table)."""
+        if self._table is not None:
+            self._table.close()
+            self._table = None
+
+    @property
+    def table(self):
+        """The ResidentTable after elaborate(), else None."""
+        return self._table
+
     def enable(self, count, out=None, algo=B.ALGO_AUTO):
         """ENABLE high for `count` clocks: the next `count` values of DT_WIN; the counter advances and wraps."""
+        if self._table is not None and algo == B.ALGO_AUTO:
+            w = self._table.generate(self.params, self._phase, count, out=out)
+            self._phase = (self._phase + int(count)) % self.length
+            return w
         w = generate(self.params, self._phase, count, device=self.device, out=out, algo=algo)
         self._phase = (self._phase + int(count)) % self.length
         return w
 
     def apply(self, x, shift=None, out=None):
         """The multiplier stage behind DT_WIN for the next x.numel() clocks: y = (x * DT_WIN) >> shift."""
+        if self._table is not None:
+            y = self._table.apply(self.params, x, n0=self._phase, shift=shift, out=out)
+            self._phase = (self._phase + x.numel()) % self.length
+            return y
         y = apply(self.params, x, n0=self._phase, shift=shift, out=out)
         self._phase = (self._phase + x.numel()) % self.length
         return y
 
     def window(self, out=None, algo=B.ALGO_AUTO):
         """One full period from phase 0."""
+        if self._table is not None and algo == B.ALGO_AUTO:
+            return self._table.generate(self.params, 0, self.length, out=out)
         return generate(self.params, 0, self.length, device=self.device, out=out, algo=algo)
 
     def shard(self, rank, world_size, out=None, algo=B.ALGO_AUTO, layout="contiguous"):
@@ -265,7 +386,14 @@ class WinSelector:
         if out is None:
             torch = _torch()
             out = torch.empty(self.length, dtype=torch.int32, device=f"cuda:{_dev_index(torch, self.device)}")
+        if self._table is not None and self._table_parts_ok() and algo == B.ALGO_AUTO:
+            return self._table.generate_part(self.params, rank, world_size, out)
         return generate_part(self.params, rank, world_size, out, algo=algo)
+
+    def _table_parts_ok(self):
+        """Parts come from the table where it is in the tile layout (phi_width >= 22); shorter windows' parts are the fused
+        kernel's and need no table."""
+        return self.params.phi_width >= 22
 
     def segments(self, rank, world_size):
         """[(n0, count), ...] owned by `rank` in the interleaved layout (host arithmetic, no GPU needed)."""

@@ -259,6 +259,40 @@ int bhw_atan2_device(const bhw_atan2_params *p, int device, void *hip_stream, ui
 int bhw_atan2_to_host(const bhw_atan2_params *p, int device, uint64_t count,
                       const int32_t *h_x, const int32_t *h_y, int32_t *h_phi);
 
+/* Resident tables (win_selector elaborates its CORDIC from the generics; AA0..AA6 are run-time ports, src/win_selector.vhd:60-87).
+ * The first-quadrant (c, s) table of BHW_ALGO_TABLE depends on the CORDIC generics only: model, phi_width, dat_width and, for
+ * the VHDL model, precision.  A bhw_table is a caller-owned handle that holds one such table on one device, built once, with the
+ * lifetime of a hipFFT plan; every call below then generates or applies any weights over any range from it without rebuilding it.
+ *   - Create: any configuration bhw_generate_device_ex accepts with BHW_ALGO_TABLE.  sin_type other than BHW_SIN_CORDIC (the
+ *     Taylor ROM is cached by the library already) and the models DDS48 / SCALED are BHW_ERR_UNSUPPORTED; table_format
+ *     (BHW_TABLE_*, BEST = the narrowest exact format) limits the format as bhw_exec.table_format does.  All argument checks come
+ *     before any HIP call.  Synchronous: settles the packed-format verdicts of the configuration (trial builds, the check word read
+ *     back), then holds exactly one table in one allocation, in the layout the configuration's whole periods read -- split and
+ *     packed where the tile kernel applies (phi_width >= 22 at z_shr = 0), plain and natural otherwise.  bhw_table_bytes is what
+ *     bhw_workspace_bytes_ex gives for a whole-period BHW_ALGO_TABLE call with the same table_format once the formats are settled
+ *     (16.5 MiB for a 2^26-point window at 32 bits, model HLS).
+ *   - Calls from a table: `p` must match the table on model, phi_width, dat_width, precision (VHDL model only) and have sin_type
+ *     BHW_SIN_CORDIC, else BHW_ERR_BADARG and bhw_last_error() names the field; aa, n_terms, win_type and combine are free per call
+ *     and `p` is validated as usual.  Same results as bhw_generate_device / bhw_apply_device / bhw_generate_part_device of `p`.
+ *     They allocate nothing, neither synchronise nor read anything back, and do not touch the library scratch of any stream: they
+ *     can always be captured into a HIP graph, with no bhw_prepare_device.  They run on the table's device (the calling thread's
+ *     current device is restored).  The table is immutable after create: any number of streams and host threads may read one table
+ *     at the same time.
+ *   - bhw_generate_part_from_table needs a table in the tile layout (phi_width >= 22), else BHW_ERR_UNSUPPORTED.
+ *   - bhw_table_describe: one line -- the table's format, layout and bytes, and the kernels a from-table call of (p, n0, count) launches.
+ *   - Destroy synchronises the table's device and frees the table; NULL is accepted.  The caller must not destroy a table that a
+ *     captured graph may still replay (the graph holds its address).  bhw_release_device does not touch tables. */
+typedef struct bhw_table_s *bhw_table;
+int      bhw_table_create(const bhw_params *p, int device, void *hip_stream, uint32_t table_format, bhw_table *out);
+int      bhw_table_destroy(bhw_table t);
+uint64_t bhw_table_bytes(bhw_table t);
+int      bhw_table_describe(bhw_table t, const bhw_params *p, uint64_t n0, uint64_t count, char *buf, uint64_t len);
+int bhw_generate_from_table(bhw_table t, const bhw_params *p, void *hip_stream, uint64_t n0, uint64_t count, int32_t *d_out);
+int bhw_apply_from_table(bhw_table t, const bhw_params *p, void *hip_stream, uint64_t n0, uint64_t count,
+                         const int32_t *d_x, int32_t *d_y, uint32_t shift);
+int bhw_generate_part_from_table(bhw_table t, const bhw_params *p, void *hip_stream, uint32_t part, uint32_t n_parts,
+                                 int32_t *d_window);
+
 /* Threading: every entry point may be called from any host thread.  Calls that use the library-owned scratch of one
  * (device, stream) are serialised against each other for the duration of their launches (the table is rebuilt per call);
  * callers that pass their own bhw_exec.workspace must not share one workspace between concurrent calls.  The calling

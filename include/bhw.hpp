@@ -6,6 +6,7 @@
 //   bhw::cordic()       <->  cordic()                       cpp/cordic_sincos.cpp:10, hls/cordic/cordic.cpp:45;
 //                            entities cordic_dds / cordic_dds48 / cordic_dds_scaled (model BHW_MODEL_VHDL / _DDS48 / _SCALED)
 //   bhw::cordic_atan2() <->  entity cordic_atan2            src/cordic_atan2.vhd:64-76
+//   bhw::resident_table      the elaborated CORDIC of win_selector's generics (bhw_table_create), move-only, RAII
 // Same names, argument meaning and error behaviour (unknown win_type -> zeros, like win_empty,
 // hls/windows/win_function.cpp:159-165,417-419).  All arithmetic runs in the HIP kernels behind the ABI.
 #pragma once
@@ -165,5 +166,55 @@ inline std::vector<int32_t> cordic_atan2(unsigned PRECISION, unsigned INPUT_WIDT
     check(bhw_atan2_to_host(&p, device, VEC_DX.size(), VEC_DX.data(), VEC_DY.data(), phi.data()));
     return phi;
 }
+
+// The CORDIC table of a configuration's generics, built once on `device` (bhw_table_create) and freed by the destructor
+// (bhw_table_destroy: it synchronises the device first).  Move-only.  Every call takes its weights -- the AA ports -- from its own
+// bhw_params, which must match the table's generics; device pointers and streams as in the C calls.
+class resident_table {
+public:
+    resident_table() = default;
+    explicit resident_table(const bhw_params &p, int device = 0, void *hip_stream = nullptr, uint32_t table_format = BHW_TABLE_BEST)
+    {
+        check(bhw_table_create(&p, device, hip_stream, table_format, &t_));
+    }
+    ~resident_table() { bhw_table_destroy(t_); }
+    resident_table(const resident_table &) = delete;
+    resident_table &operator=(const resident_table &) = delete;
+    resident_table(resident_table &&o) noexcept : t_(o.t_) { o.t_ = nullptr; }
+    resident_table &operator=(resident_table &&o) noexcept
+    {
+        if (this != &o) {
+            bhw_table_destroy(t_);
+            t_ = o.t_;
+            o.t_ = nullptr;
+        }
+        return *this;
+    }
+
+    bhw_table get() const { return t_; }
+    explicit operator bool() const { return t_ != nullptr; }
+    uint64_t bytes() const { return bhw_table_bytes(t_); }
+    std::string describe(const bhw_params &p, uint64_t n0, uint64_t count) const
+    {
+        char buf[384];
+        check(bhw_table_describe(t_, &p, n0, count, buf, sizeof buf));
+        return buf;
+    }
+    void generate(const bhw_params &p, void *hip_stream, uint64_t n0, uint64_t count, int32_t *d_out) const
+    {
+        check(bhw_generate_from_table(t_, &p, hip_stream, n0, count, d_out));
+    }
+    void apply(const bhw_params &p, void *hip_stream, uint64_t n0, uint64_t count, const int32_t *d_x, int32_t *d_y, uint32_t shift) const
+    {
+        check(bhw_apply_from_table(t_, &p, hip_stream, n0, count, d_x, d_y, shift));
+    }
+    void generate_part(const bhw_params &p, void *hip_stream, uint32_t part, uint32_t n_parts, int32_t *d_window) const
+    {
+        check(bhw_generate_part_from_table(t_, &p, hip_stream, part, n_parts, d_window));
+    }
+
+private:
+    bhw_table t_ = nullptr;
+};
 
 } // namespace bhw
