@@ -22,6 +22,7 @@ ABI_SYMBOLS = (
     "bhw_coeffs_preset", "bhw_gather_parts_device", "bhw_workspace_bytes_ex",
     "bhw_table_create", "bhw_table_destroy", "bhw_table_bytes", "bhw_table_describe", "bhw_generate_from_table",
     "bhw_apply_from_table", "bhw_generate_part_from_table",
+    "bhw_apply_frames_device", "bhw_apply_frames_from_table", "bhw_apply_frames_describe",
 )
 
 
@@ -56,6 +57,19 @@ class BhwExec(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("algo", ctypes.c_uint32),
                 ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_uint64),
                 ("event_after_build", ctypes.c_void_p), ("table_format", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class BhwFrames(ctypes.Structure):
+    """struct bhw_frames of include/bhw.h (the overlapped-frame apply)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("channels", ctypes.c_uint32), ("frames", ctypes.c_uint64),
+                ("hop", ctypes.c_uint64), ("y_stride", ctypes.c_uint64), ("shift", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+def make_frames(frames, hop, *, channels=1, shift=0, y_stride=0):
+    f = BhwFrames()
+    f.struct_size = ctypes.sizeof(BhwFrames)
+    f.channels, f.frames, f.hop, f.y_stride, f.shift = int(channels), int(frames), int(hop), int(y_stride), int(shift)
+    return f
 
 
 _lib = None
@@ -123,6 +137,12 @@ def lib():
     L.bhw_dbg_table_key_matches.argtypes = [P, P]
     L.bhw_dbg_describe_from_table.argtypes = [P, u32, P, u64, u64, ctypes.c_char_p, u64]
     L.bhw_dbg_generate_from_table_generic.argtypes = [T, P, vp, u64, u64, i32p]
+    F = ctypes.POINTER(BhwFrames)
+    L.bhw_apply_frames_device.argtypes = [P, ci, vp, F, i32p, i32p]
+    L.bhw_apply_frames_from_table.argtypes = [T, P, vp, F, i32p, i32p]
+    L.bhw_apply_frames_describe.argtypes = [T, P, F, ctypes.c_char_p, u64]
+    L.bhw_dbg_apply_frames_route.argtypes = [P, ci, vp, F, i32p, i32p, ci]
+    L.bhw_dbg_describe_frames_from_table.argtypes = [P, u32, P, F, ctypes.c_char_p, u64]
     PA = ctypes.POINTER(BhwAtan2Params)
     L.bhw_atan2_device.argtypes = [PA, ci, vp, u64, i32p, i32p, i32p]
     L.bhw_atan2_to_host.argtypes = [PA, ci, u64, i32p, i32p, i32p]
@@ -154,6 +174,15 @@ def describe_table(table, params, n0, count):
     (bhw_table_describe; `table` is the handle, e.g. ResidentTable.handle)."""
     buf = ctypes.create_string_buffer(384)
     check(lib().bhw_table_describe(table, ctypes.byref(params), int(n0), int(count), buf, 384))
+    return buf.value.decode()
+
+
+def describe_frames(params, frames, hop, *, channels=1, y_stride=0, table=None):
+    """One line: the route, the frame-group size and the kernels an overlapped-frame apply would launch (bhw_apply_frames_describe;
+    `table` is a resident table handle or None for the library call).  Host arithmetic only."""
+    buf = ctypes.create_string_buffer(384)
+    f = make_frames(frames, hop, channels=channels, y_stride=y_stride)
+    check(lib().bhw_apply_frames_describe(table, ctypes.byref(params), ctypes.byref(f), buf, 384))
     return buf.value.decode()
 
 

@@ -384,6 +384,32 @@ int generate_impl(const bhw_params *p, int device, void *stream, uint64_t n0, ui
     return run_split(l, n0, count, N, apply_x != nullptr, d_out, ragged, period);
 }
 
+// bhw_apply_frames_device: the frames kernel with the direct CORDIC source (no table, no scratch), or one bhw_apply_device per
+// frame where the planner's route rule says so.  force_route >= 0: the route of an A/B run (bhw_dbg_apply_frames_route).
+int frames_impl(const bhw_params *p, int device, void *stream, const bhw_frames *f, const int32_t *d_x, int32_t *d_y, int force_route)
+{
+    int rc = bhwp_frames_checks(p, f, d_x, d_y);
+    if (rc || !f->frames) return rc;
+    const BhwFramesPlan pl = bhwp_frames_plan(p, f, false, force_route);
+    if (pl.route == BHWP_FRAMES_PER_FRAME) {
+        const uint64_t N = 1ull << p->phi_width;
+        for (uint64_t i = 0; i < f->frames; ++i) {
+            rc = generate_impl(p, device, stream, 0, N, d_y + i * pl.y_stride, nullptr, d_x + i * f->hop, f->shift);
+            if (rc) return rc;
+        }
+        return BHW_OK;
+    }
+    if (!device_ok(device)) return fail(BHW_ERR_HIP, "no usable HIP device %d (this library has no CPU path)", device);
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
+    BhwCordicCfg c;
+    bhwp_resolve_cordic(p, c);
+    BhwWinCfg w;
+    bhwp_resolve_window(p, w);
+    const int e = bhwk_frames(BhwLaunch{device, stream}, c, w, pl, f, d_x, d_y, nullptr);
+    return e ? fail_hip(e, "frames launch") : BHW_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -408,6 +434,19 @@ int bhw_apply_device(const bhw_params *p, int device, void *hip_stream, uint64_t
     if (count && xa < ya + bytes && ya < xa + bytes)
         return fail(BHW_ERR_BADARG, "d_y must not overlap d_x (tile seams recompute a few samples)");
     return generate_impl(p, device, hip_stream, n0, count, d_y, nullptr, d_x, shift);
+}
+
+int bhw_apply_frames_device(const bhw_params *p, int device, void *hip_stream, const bhw_frames *f, const int32_t *d_x, int32_t *d_y)
+{
+    return frames_impl(p, device, hip_stream, f, d_x, d_y, -1);
+}
+
+// Development hook (not part of the ABI in include/bhw.h): bhw_apply_frames_device on a forced route (BHWP_FRAMES_DIRECT or
+// BHWP_FRAMES_PER_FRAME; a route the call cannot take is ignored) -- the crossover runs of tools/bench_apply_frames.py and tests.
+int bhw_dbg_apply_frames_route(const bhw_params *p, int device, void *hip_stream, const bhw_frames *f, const int32_t *d_x, int32_t *d_y,
+                               int route)
+{
+    return frames_impl(p, device, hip_stream, f, d_x, d_y, route);
 }
 
 int bhw_generate_batched_device(const bhw_params *p, int device, void *hip_stream, uint32_t frames, int32_t *d_out)
@@ -991,6 +1030,27 @@ int bhw_generate_part_from_table(bhw_table t, const bhw_params *p, void *hip_str
     const BhwLaunch l{t->device, hip_stream};
     const int e = bhwk_table_combine_tile_range(l, t->c, w, (const int32_t *)t->buf, d_window, tile0, tile_count);
     return e ? fail_hip(e, "tile part launch") : BHW_OK;
+}
+
+int bhw_apply_frames_from_table(bhw_table t, const bhw_params *p, void *hip_stream, const bhw_frames *f, const int32_t *d_x, int32_t *d_y)
+{
+    int rc = table_call_checks(t, p);
+    if (!rc) rc = bhwp_frames_checks(p, f, d_x, d_y);
+    if (rc || !f->frames) return rc;
+    const BhwFramesPlan pl = bhwp_frames_plan(p, f, true);
+    DeviceGuard guard(t->device);
+    if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
+    BhwWinCfg w;
+    bhwp_resolve_window(p, w);
+    const int e = bhwk_frames(BhwLaunch{t->device, hip_stream}, t->c, w, pl, f, d_x, d_y, (const int32_t *)t->buf);
+    return e ? fail_hip(e, "frames launch (resident table)") : BHW_OK;
+}
+
+int bhw_apply_frames_describe(bhw_table t, const bhw_params *p, const bhw_frames *f, char *buf, uint64_t len)
+{
+    int rc = t ? table_call_checks(t, p) : BHW_OK;
+    if (!rc) rc = bhwp_frames_checks(p, f, nullptr, nullptr, false);
+    return rc ? rc : bhwp_describe_frames(p, t ? &t->c : nullptr, f, buf, len);
 }
 
 // Development hook (not part of the ABI in include/bhw.h): bhw_generate_from_table with every ragged piece on the general gather

@@ -724,6 +724,88 @@ __device__ __forceinline__ void rot_step_dyn(int64_t &x, int64_t &y, int32_t &z,
     else       z = (int32_t)((uint32_t)z - lutk + ((2u * lutk) & (uint32_t)m));
 }
 
+// Coefficient n (masked phase) by K-1 full CORDIC chains: the per-lane work of k_direct (bhw_direct.hip) and k_frames_direct
+// (bhw_frames.hip).  lut: the rescaled ROM staged by stage_lut<T>.
+template <typename T>
+__device__ __forceinline__ int32_t direct_coeff(const BhwCordicCfg &cfg, const BhwWinCfg &win, const T *lut, uint32_t n)
+{
+    const uint32_t mask = (cfg.phi_width >= 32) ? 0xFFFFFFFFu : ((1u << cfg.phi_width) - 1u);
+    int64_t acc = win.aa[0];
+    for (uint32_t k = 1; k < win.n_terms; ++k) {
+        const uint32_t theta = (k * n) & mask;                     // ph_ink += k: bh_win_7term.vhd:187-194 | cordic(k*i): win_function.cpp:361-366
+        int32_t c, s;
+        cordic_full<T>(cfg, lut, theta, c, s);
+        combine_term(acc, win.aa[k], c, k, cfg.dat_width, win.combine);
+    }
+    return combine_final(acc, cfg.dat_width, win.combine, win.n_terms);
+}
+
+// ---------------------------------------------------------------------------------------
+// Coefficient n (0 <= n < 2^PW) gathered from a resident table in any format: the per-lane work of k_range_combine
+// (bhw_range.hip) and k_frames_table (bhw_frames.hip).  FMT: the table format (fmt_of: 0 plain, 1 delta16, 2 residual, 3 nibble,
+// 5 nibble + escapes); NT: bound of the term count (3, 5, 7: the harmonics k < win.n_terms are taken, a wave-uniform test); MODE as
+// in k_table_combine_fold_t: 0 HLS rule, 1 HLS rule with the one's-complement quadrant map (cpp model), 2 VHDL rule.  The K - 1
+// gathers of a lane issue together, and the escape format costs one test per lane (the minimum of its low fields over the
+// harmonics) with the rare marked lane resolved on the scalar unit (esc_fix_wave): every lane of the wave must reach this call.
+// ---------------------------------------------------------------------------------------
+template <int FMT, int NT, int MODE>
+__device__ __forceinline__ int32_t range_coeff(const BhwCordicCfg &cfg, const BhwWinCfg &win, const void *__restrict__ table, uint32_t n)
+{
+    constexpr uint32_t COMBINE = MODE == 2 ? BHW_COMBINE_VHDL : BHW_COMBINE_HLS;
+    const uint32_t pw = cfg.phi_width, W = cfg.dat_width;
+    const uint32_t mask = (1u << pw) - 1u, tmask = (1u << (pw - 2u)) - 1u;
+    const uint32_t lq = pw - 2u - cfg.z_shr;                       // log2 of the table's entries
+    const uint32_t nt = win.n_terms;
+    int2 cs[NT];
+    uint32_t q[NT];
+    uint32_t ent[NT];                                              // FMT 5: entry index and stored byte, for the escape test
+    uint32_t byte[NT];
+    uint32_t low_min = 15u;
+#pragma unroll
+    for (int k = 1; k < NT; ++k) {
+        cs[k] = make_int2(0, 0);
+        q[k] = 0u;
+        ent[k] = byte[k] = 0u;
+        if ((uint32_t)k < nt) {
+            const uint32_t theta = ((uint32_t)k * n) & mask;
+            q[k] = theta >> (pw - 2u);
+            const uint32_t u = (theta & tmask) >> cfg.z_shr;
+            if constexpr (FMT == 5) {
+                // the nibble decode of tab_fetch, the marker left to the test below
+                const uint32_t d = fmt_cell_log(cfg.tab_dlog);
+                const int4 rec = ld_off<int4>(cfg.tab_coarse, (u >> d) << 4);
+                const uint32_t e = ld_off<uint8_t>(table, u);
+                const int2 p = tab_predict_nib(rec, u & ((1u << d) - 1u), d), f = nib_fields(e);
+                cs[k] = make_int2(p.x + f.x, p.y + f.y);
+                ent[k] = u;
+                byte[k] = e;
+                low_min = min(low_min, e & 15u);
+            } else {
+                cs[k] = tab_fetch<FMT>(cfg, table, u, tab_index<0, -1>(u, lq, cfg.tab_split));
+            }
+        }
+    }
+    if constexpr (FMT == 5) {
+        // one test per lane over all its harmonics; listed entries are a few per million, so the branch is almost never taken
+        if (__builtin_expect(low_min == kEscMarker, 0)) {
+#pragma unroll
+            for (int k = 1; k < NT; ++k)
+                if ((uint32_t)k < nt) esc_fix_wave(cfg.tab_esc, cfg.esc_wg_log, lq, ent[k], (byte[k] & 15u) == kEscMarker, cs[k]);
+        }
+    }
+    Sum32 acc = MODE == 2 ? sum32_first(win.aa[0]) : Sum32{win.aa[0], win.aa[0]};
+    const uint32_t ones_neg = MODE == 0 ? 0u : MODE == 1 ? 1u : cfg.ones_neg;
+#pragma unroll
+    for (int k = 1; k < NT; ++k) {
+        if ((uint32_t)k < nt) {
+            int32_t c, s;
+            quadrant_map(q[k], cs[k].x, cs[k].y, ones_neg, c, s);
+            w32_term<COMBINE>(acc, win.aa[k], c, (uint32_t)k, W);
+        }
+    }
+    return w32_final<COMBINE>(acc, W, nt);
+}
+
 inline unsigned grid_for(uint64_t count) { return (unsigned)((count + kBlock - 1) / kBlock); }
 
 // Launches go through hipLaunchKernel, which returns the launch status itself: the thread's hipGetLastError() state is

@@ -20,14 +20,7 @@ __global__ __launch_bounds__(kBlock) void k_direct(BhwCordicCfg cfg, BhwWinCfg w
     if (i >= count) return;
     const uint32_t mask = (cfg.phi_width >= 32) ? 0xFFFFFFFFu : ((1u << cfg.phi_width) - 1u);
     const uint32_t n = (uint32_t)(n0 + i) & mask;                   // phase counter wraps: bh_win_7term.vhd:92-97
-    int64_t acc = win.aa[0];
-    for (uint32_t k = 1; k < win.n_terms; ++k) {
-        const uint32_t theta = (k * n) & mask;                     // ph_ink += k: bh_win_7term.vhd:187-194 | cordic(k*i): win_function.cpp:361-366
-        int32_t c, s;
-        cordic_full<T>(cfg, lut_s, theta, c, s);
-        combine_term(acc, win.aa[k], c, k, cfg.dat_width, win.combine);
-    }
-    emit(win, out, i, combine_final(acc, cfg.dat_width, win.combine, win.n_terms));
+    emit(win, out, i, direct_coeff<T>(cfg, win, lut_s, n));
 }
 
 // sin/cos sweep: cordic() alone.

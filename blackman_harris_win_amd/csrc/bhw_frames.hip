@@ -1,0 +1,191 @@
+// bhw_frames.hip -- overlapped-frame apply (bhw_apply_frames_device / bhw_apply_frames_from_table): the window over many frames of
+// one signal at any hop in one launch, the front end of an STFT or a Welch estimate
+//
+// Part of the hand-written HIP kernels for gfx950 (MI355X, CDNA4) behind include/bhw.h.  Hot path of the reference: phase
+// accumulator -> CORDIC rotation chain (or Taylor LUT) -> weighted N-term cosine sum -> int32 coefficient (SURVEY section 8a
+// rows a1-a11), then the multiplier in front of the FFT (int_multNxN_dsp48, src/int_multNxN_dsp48.vhd:102).
+//
+// Coefficient k is the same in every frame, so a lane computes w[k] once -- by the direct CORDIC chains of k_direct
+// (direct_coeff) or by the gather of k_range_combine over a resident table (range_coeff) -- keeps it in a register and applies it to
+// a group of G frames:  y[f * y_stride + k * C + c] = low32((x[(f * hop + k) * C + c] * w[k]) >> shift).  The per-coefficient work
+// that bounds every other kernel of the library is spread over G frames, and what is left is the x read and the y write.
+//   - Workgroup: kFramesBlock lanes, min(N, 256) along k and the rest side by side over frames (windows shorter than 256).
+//   - Grid: (N / kx) x (frame groups); bhwp_frames_plan picks G so that about kFramesTargetWg workgroups fill the 256 CUs.
+//   - x is read up to ceil(N / hop) times (once per frame that covers it), so it takes default-policy loads -- the nontemporal load
+//     of the single-use emit() would push it past the caches -- and the frame groups are dispatched in signal order, so the frames
+//     that share an x are in flight together.
+//   - The frame loop issues four frames' loads before their stores; two channels move as one 8-byte access when both bases and the
+//     stride allow it (FramesArgs.io), else as two 4-byte ones.
+#include "bhw_device.h"
+
+namespace {
+
+struct FramesArgs {
+    const int32_t *x;
+    int32_t *y;
+    uint64_t frames, hop, y_stride;
+    uint64_t group;      // G: frame rows of one workgroup
+    uint32_t kx;         // lanes along k (a power of two)
+    uint32_t fy;         // frame rows side by side in a workgroup: kFramesBlock / kx
+    uint32_t shift;
+    uint32_t io;         // 0: one channel; 1: two channels, 4-byte accesses; 2: two channels, one 8-byte access
+};
+
+__device__ __forceinline__ int32_t apply1(int32_t x, int32_t w, uint32_t shift) { return (int32_t)(((int64_t)x * (int64_t)w) >> shift); }
+
+// The frames of this lane: rows [blockIdx.y * G, +G) of fy frames, frame f = row * fy + ty.  C = channels, VEC: one 8-byte access.
+template <int C, bool VEC>
+__device__ __forceinline__ void frames_loop(const FramesArgs &a, uint32_t k, uint32_t ty, int32_t w)
+{
+    constexpr int U = 4;
+    const uint64_t f_end0 = ((uint64_t)blockIdx.y + 1) * a.group * a.fy;
+    const uint64_t f_end = f_end0 < a.frames ? f_end0 : a.frames;
+    const uint64_t step = a.fy;
+    for (uint64_t f = (uint64_t)blockIdx.y * a.group * a.fy + ty; f < f_end; f += U * step) {
+        int32_t v[U][C];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint64_t fu = f + u * step;
+            if (fu < f_end) {
+                const uint64_t xi = (fu * a.hop + k) * C;
+                if constexpr (C == 1) {
+                    v[u][0] = a.x[xi];
+                } else if constexpr (VEC) {
+                    const int2 p = *(const int2 *)(a.x + xi);
+                    v[u][0] = p.x;
+                    v[u][1] = p.y;
+                } else {
+                    v[u][0] = a.x[xi];
+                    v[u][1] = a.x[xi + 1];
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint64_t fu = f + u * step;
+            if (fu < f_end) {
+                int32_t *yp = a.y + fu * a.y_stride + (uint64_t)k * C;
+                if constexpr (C == 1) {
+                    yp[0] = apply1(v[u][0], w, a.shift);
+                } else if constexpr (VEC) {
+                    *(int2 *)yp = make_int2(apply1(v[u][0], w, a.shift), apply1(v[u][1], w, a.shift));
+                } else {
+                    yp[0] = apply1(v[u][0], w, a.shift);
+                    yp[1] = apply1(v[u][1], w, a.shift);
+                }
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ void frames_apply(const FramesArgs &a, uint32_t k, uint32_t ty, int32_t w)
+{
+    if (a.io == 0)      frames_loop<1, false>(a, k, ty, w);
+    else if (a.io == 1) frames_loop<2, false>(a, k, ty, w);
+    else                frames_loop<2, true>(a, k, ty, w);
+}
+
+// Coefficient n by K-1 full CORDIC chains in the mad-form rotation of k_direct_fast (rot_step: |x| < 2^33, quarter circle <= 2^32),
+// with the chain as a rolled loop on a scalar counter (rot_step_dyn) instead of one unrolled instance per rotation count: the
+// coefficient is spread over G frames here, so the 26 NITER instances of k_direct_fast would buy little.
+__device__ __forceinline__ int32_t direct_coeff_mad(const BhwCordicCfg &cfg, const BhwWinCfg &win, const uint32_t *lut, uint32_t n)
+{
+    const uint32_t pw = cfg.phi_width;
+    const uint32_t mask = (pw >= 32) ? 0xFFFFFFFFu : ((1u << pw) - 1u);
+    const uint32_t tmask = (1u << (pw - 2)) - 1u;
+    int64_t acc = win.aa[0];
+    for (uint32_t k = 1; k < win.n_terms; ++k) {
+        const uint32_t theta = (k * n) & mask;
+        const uint32_t u = (theta & tmask) >> cfg.z_shr;
+        int64_t x = cfg.x0, y = cfg.x0;                                          // rotation 0 always adds (z0 >= 0)
+        int32_t z = (int32_t)((u << cfg.z_shl) - lut[0]);
+        const int n_iter = (int)cfg.n_iter;
+        for (int r = 1; r < n_iter; ++r) rot_step_dyn(x, y, z, r, lut[r], r >= kMad24From);
+        int32_t c, s;
+        quadrant_map(theta >> (pw - 2), (int32_t)(x >> cfg.out_shr), (int32_t)(y >> cfg.out_shr), cfg.ones_neg, c, s);
+        combine_term(acc, win.aa[k], c, k, cfg.dat_width, win.combine);
+    }
+    return combine_final(acc, cfg.dat_width, win.combine, win.n_terms);
+}
+
+// Coefficient by the direct CORDIC chains.  FORM 0 / 1: the cordic_full chain of k_direct (T = int32_t, or int64_t where the state
+// needs more than 32 bits); FORM 2: the mad-form rotation where it applies (bhwk_frames picks it as bhwk_direct picks k_direct_fast).
+template <int FORM>
+__global__ __launch_bounds__(kFramesBlock) void k_frames_direct(BhwCordicCfg cfg, BhwWinCfg win, FramesArgs a)
+{
+    using T = std::conditional_t<FORM == 0, int32_t, int64_t>;
+    using L = std::conditional_t<FORM == 2, uint32_t, T>;
+    __shared__ L lut_s[32];
+    if (threadIdx.x < 32) lut_s[threadIdx.x] = (L)cfg.lut[threadIdx.x];
+    __syncthreads();
+    const uint32_t k = blockIdx.x * a.kx + (threadIdx.x & (a.kx - 1u));        // < N: grid.x * kx = N
+    int32_t w;
+    if constexpr (FORM == 2) w = direct_coeff_mad(cfg, win, lut_s, k);
+    else                     w = direct_coeff<T>(cfg, win, lut_s, k);
+    frames_apply(a, k, threadIdx.x / a.kx, w);
+}
+
+// Coefficient gathered from a resident table in format FMT (range_coeff: NT the term-count bound, MODE the rule).  Every lane
+// reaches the gather (the escape format resolves marked lanes wave-wide).
+template <int FMT, int NT, int MODE>
+__global__ __launch_bounds__(kFramesBlock) void k_frames_table(BhwCordicCfg cfg, BhwWinCfg win, const void *__restrict__ table, FramesArgs a)
+{
+    const uint32_t k = blockIdx.x * a.kx + (threadIdx.x & (a.kx - 1u));
+    frames_apply(a, k, threadIdx.x / a.kx, range_coeff<FMT, NT, MODE>(cfg, win, table, k));
+}
+
+} // namespace
+
+int bhwk_frames(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinCfg &w, const BhwFramesPlan &pl, const bhw_frames *f,
+                const int32_t *d_x, int32_t *d_y, const int32_t *d_table)
+{
+    if (!f->frames) return 0;
+    BHW_SET_DEVICE(l);
+    hipStream_t st = (hipStream_t)l.stream;
+    FramesArgs a;
+    a.x = d_x;
+    a.y = d_y;
+    a.frames = f->frames;
+    a.hop = f->hop;
+    a.y_stride = pl.y_stride;
+    a.group = pl.group;
+    a.kx = pl.kx;
+    a.fy = pl.fy;
+    a.shift = f->shift;
+    a.io = f->channels == 1 ? 0u : ((((uintptr_t)d_x | (uintptr_t)d_y) % 8 == 0 && pl.y_stride % 2 == 0) ? 2u : 1u);
+    const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y), block(kFramesBlock);
+    if (!d_table) {
+        if (bhwp_frames_mad_form(c_in)) BHW_LAUNCH(k_frames_direct<2>, grid, block, 0, st, c_in, w, a);
+        else if (c_in.wide)             BHW_LAUNCH(k_frames_direct<1>, grid, block, 0, st, c_in, w, a);
+        else                            BHW_LAUNCH(k_frames_direct<0>, grid, block, 0, st, c_in, w, a);
+        return finish(hipSuccess);
+    }
+    const BhwCordicCfg c = table_layout(c_in);
+    int fmt, nt, mode;
+    if (!bhwp_range_form(c, w, &fmt, &nt, &mode)) return (int)hipErrorInvalidValue;   // every format a resident table holds has instances
+    const void *tab = (const void *)d_table;
+#define BHW_FRAMES_F(F, NT, M) BHW_LAUNCH((k_frames_table<F, NT, M>), grid, block, 0, st, c, w, tab, a)
+#define BHW_FRAMES_NT(F, M)                                                                                              \
+    do {                                                                                                                 \
+        if (nt == 3)      BHW_FRAMES_F(F, 3, M);                                                                         \
+        else if (nt == 5) BHW_FRAMES_F(F, 5, M);                                                                         \
+        else              BHW_FRAMES_F(F, 7, M);                                                                         \
+    } while (0)
+#define BHW_FRAMES_M(F)                                                                                                  \
+    do {                                                                                                                 \
+        if (mode == 0)      BHW_FRAMES_NT(F, 0);                                                                         \
+        else if (mode == 1) BHW_FRAMES_NT(F, 1);                                                                         \
+        else                BHW_FRAMES_NT(F, 2);                                                                         \
+    } while (0)
+    switch (fmt) {
+    case 0: BHW_FRAMES_M(0); break;
+    case 1: BHW_FRAMES_M(1); break;
+    case 2: BHW_FRAMES_M(2); break;
+    case 3: BHW_FRAMES_M(3); break;
+    default: BHW_FRAMES_M(5); break;
+    }
+#undef BHW_FRAMES_M
+#undef BHW_FRAMES_NT
+#undef BHW_FRAMES_F
+    return finish(hipSuccess);
+}

@@ -711,6 +711,105 @@ int bhwp_describe_from_table(const bhw_params *p, const BhwCordicCfg &ct, bool t
     return BHW_OK;
 }
 
+// ---- overlapped-frame apply --------------------------------------------------------------------------------------------------
+
+int bhwp_frames_checks(const bhw_params *p, const bhw_frames *f, const void *d_x, const void *d_y, bool pointers)
+{
+    if (!p) return bhwp_fail(BHW_ERR_BADARG, "params is NULL");
+    int rc = bhwp_validate(p);
+    if (rc) return rc;
+    if (!f) return bhwp_fail(BHW_ERR_BADARG, "frames descriptor is NULL");
+    if (f->struct_size != sizeof(bhw_frames)) return bhwp_fail(BHW_ERR_BADARG, "bhw_frames.struct_size %u != %zu", f->struct_size, sizeof(bhw_frames));
+    if (f->channels != 1 && f->channels != 2) return bhwp_fail(BHW_ERR_BADARG, "channels %u (1 or 2)", f->channels);
+    if (f->hop == 0) return bhwp_fail(BHW_ERR_BADARG, "hop is 0");
+    if (f->shift > 62) return bhwp_fail(BHW_ERR_BADARG, "shift %u > 62", f->shift);
+    if (f->reserved) return bhwp_fail(BHW_ERR_BADARG, "bhw_frames.reserved must be 0");
+    const uint64_t N = 1ull << p->phi_width, NC = N * f->channels;
+    if (f->y_stride && f->y_stride < NC)
+        return bhwp_fail(BHW_ERR_BADARG, "y_stride %llu < N * channels = %llu", (unsigned long long)f->y_stride, (unsigned long long)NC);
+    if (p->sin_type != BHW_SIN_CORDIC && f->channels == 2)
+        return bhwp_fail(BHW_ERR_UNSUPPORTED, "the Taylor sources take the per-frame route, which has no I/Q form (channels 2)");
+    if (!f->frames) return BHW_OK;
+    if (f->frames > (1ull << 34) / N)
+        return bhwp_fail(BHW_ERR_BADARG, "frames * N = %llu * %llu > 2^34 per call", (unsigned long long)f->frames, (unsigned long long)N);
+    if (!pointers) return BHW_OK;
+    if (!d_x || !d_y) return bhwp_fail(BHW_ERR_BADARG, "d_x / d_y is NULL");
+    // extents in int32 elements; hop and y_stride are free 64-bit values, so the products are taken in 128 bits
+    const unsigned __int128 xe = ((unsigned __int128)(f->frames - 1) * f->hop + N) * f->channels;
+    const unsigned __int128 ye = (unsigned __int128)(f->frames - 1) * (f->y_stride ? f->y_stride : NC) + NC;
+    if (xe > (1ull << 60) || ye > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "x or y extent beyond 2^60 elements");
+    const uint64_t xa = (uint64_t)(uintptr_t)d_x, ya = (uint64_t)(uintptr_t)d_y, xb = (uint64_t)xe * 4u, yb = (uint64_t)ye * 4u;
+    if (xa > UINT64_MAX - xb || ya > UINT64_MAX - yb) return bhwp_fail(BHW_ERR_BADARG, "x or y range wraps the address space");
+    if (xa < ya + yb && ya < xa + xb) return bhwp_fail(BHW_ERR_BADARG, "d_y must not overlap d_x");
+    return BHW_OK;
+}
+
+BhwFramesPlan bhwp_frames_plan(const bhw_params *p, const bhw_frames *f, bool from_table, int force_route)
+{
+    BhwFramesPlan pl{};
+    const uint64_t N = 1ull << p->phi_width;
+    pl.y_stride = f->y_stride ? f->y_stride : N * f->channels;
+    if (from_table) pl.route = BHWP_FRAMES_TABLE;
+    else if (f->channels == 2) pl.route = BHWP_FRAMES_DIRECT;                  // the existing apply has no I/Q form
+    else if (p->sin_type != BHW_SIN_CORDIC) pl.route = BHWP_FRAMES_PER_FRAME;  // no frames kernel for the Taylor sources
+    else {
+        BhwCordicCfg c;
+        bhwp_resolve_cordic(p, c);
+        const uint64_t work = (uint64_t)(p->n_terms - 1) * c.n_iter;       // direct CORDIC rotations per coefficient
+        const bool per_frame = f->frames * kFramesPerFrameRef < (uint64_t)bhwp_frames_crossover(p->phi_width) * work;
+        pl.route = per_frame ? BHWP_FRAMES_PER_FRAME : BHWP_FRAMES_DIRECT;
+    }
+    if (force_route >= 0 && !from_table && force_route != BHWP_FRAMES_TABLE &&
+        !(force_route == BHWP_FRAMES_PER_FRAME && f->channels == 2) && !(force_route == BHWP_FRAMES_DIRECT && p->sin_type != BHW_SIN_CORDIC))
+        pl.route = force_route;
+    pl.kx = N < kFramesBlock ? (uint32_t)N : kFramesBlock;
+    pl.fy = kFramesBlock / pl.kx;
+    pl.grid_x = N / pl.kx;
+    if (pl.route == BHWP_FRAMES_PER_FRAME || !f->frames) return pl;
+    // frame rows of fy frames; as many workgroups as kFramesTargetWg asks for, each lane then applies its coefficient to G rows
+    const uint64_t rows = (f->frames + pl.fy - 1) / pl.fy;
+    // (a long window fills the chip alone: cutting its frames into groups would only compute each coefficient again per group)
+    const uint64_t gy_target = pl.grid_x >= kFramesOnePassGx ? 1 : (kFramesTargetWg + pl.grid_x - 1) / pl.grid_x;
+    uint64_t G = (rows + gy_target - 1) / gy_target;
+    const uint64_t g_min = (rows + kFramesMaxGridY - 1) / kFramesMaxGridY;
+    if (G < g_min) G = g_min;
+    if (G < 1) G = 1;
+    pl.group = G;
+    pl.grid_y = (rows + G - 1) / G;
+    return pl;
+}
+
+int bhwp_describe_frames(const bhw_params *p, const BhwCordicCfg *ct, const bhw_frames *f, char *buf, uint64_t len)
+{
+    if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
+    const BhwFramesPlan pl = bhwp_frames_plan(p, f, ct != nullptr);
+    const uint64_t N = 1ull << p->phi_width;
+    if (pl.route == BHWP_FRAMES_PER_FRAME) {
+        char one[256];
+        const int rc = bhw_describe_plan(p, 0, N, nullptr, one, sizeof one);
+        if (rc) return rc;
+        snprintf(buf, len, "per-frame: %llu x bhw_apply_device [%s]", (unsigned long long)f->frames, one);
+        return BHW_OK;
+    }
+    char kern[64];
+    if (pl.route == BHWP_FRAMES_TABLE) {
+        const BhwCordicCfg c = table_layout(*ct);
+        BhwWinCfg w;
+        bhwp_resolve_window(p, w);
+        int fmt, nt, mode;
+        bhwp_range_form(c, w, &fmt, &nt, &mode);
+        snprintf(kern, sizeof kern, "k_frames_table<%d,%d,%d>", fmt, nt, mode);
+    } else {
+        BhwCordicCfg c;
+        bhwp_resolve_cordic(p, c);
+        snprintf(kern, sizeof kern, "k_frames_direct<%d>", bhwp_frames_mad_form(c) ? 2 : c.wide ? 1 : 0);
+    }
+    snprintf(buf, len, "frames kernel: %s, %u channel%s, G = %llu frames per lane, grid %llu x %llu x %u lanes (%u along k)", kern,
+             f->channels, f->channels == 2 ? "s" : "", (unsigned long long)pl.group, (unsigned long long)pl.grid_x,
+             (unsigned long long)pl.grid_y, kFramesBlock, pl.kx);
+    return BHW_OK;
+}
+
 // ---- the pure entry points of the C ABI (include/bhw.h) -------------------------------------------------------------------------------
 extern "C" {
 
@@ -953,6 +1052,24 @@ int bhw_dbg_describe_from_table(const bhw_params *p_table, uint32_t table_format
     bhwp_table_format_candidates(c, tiled, table_format, cand);
     c.tab_dlog = cand[0];
     return bhwp_describe_from_table(p_call, c, tiled, n0, count, buf, len);
+}
+
+// bhw_apply_frames_describe of a from-table call from parameters alone (no device, no table): the table of p_table as
+// bhw_table_create would hold it if every packed format under `table_format` were exact, and the call's checks before that
+int bhw_dbg_describe_frames_from_table(const bhw_params *p_table, uint32_t table_format, const bhw_params *p_call, const bhw_frames *f,
+                                       char *buf, uint64_t len)
+{
+    int rc = bhw_dbg_table_key_matches(p_table, p_call);
+    if (!rc && table_format > BHW_TABLE_NIBBLE_ESC) rc = bhwp_fail(BHW_ERR_BADARG, "table_format %u", table_format);
+    if (!rc) rc = bhwp_frames_checks(p_call, f, nullptr, nullptr, false);
+    if (rc) return rc;
+    BhwCordicCfg c;
+    bool tiled;
+    bhwp_resident_layout(p_table, c, &tiled);
+    uint32_t cand[kMaxFormats];
+    bhwp_table_format_candidates(c, tiled, table_format, cand);
+    c.tab_dlog = cand[0];
+    return bhwp_describe_frames(p_call, &c, f, buf, len);
 }
 
 // tab_dlog the residual format would use for `p` (0: not applicable) and whether delta16 applies

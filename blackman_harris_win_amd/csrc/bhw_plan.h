@@ -137,3 +137,38 @@ int  bhwp_describe_from_table(const bhw_params *p, const BhwCordicCfg &ct, bool 
 int  bhwp_part_checks(const bhw_params *p, uint32_t part, uint32_t n_parts);
 // strategy of bhw_generate_part_device: true = fused kernel over the part's runs, false = full table + the part's tiles; rc != 0: neither applies
 bool bhwp_part_fused(const bhw_params *p, const BhwCordicCfg &c, const BhwFoldRun *runs, int n_runs, uint32_t tile_count, uint32_t requested, int *rc);
+
+// ---- overlapped-frame apply (bhw_apply_frames_device / _from_table) -------------------------------------------------------------
+// Routes: the frames kernel with the direct CORDIC source, the frames kernel over a resident table, or one bhw_apply_device per frame.
+enum { BHWP_FRAMES_DIRECT = 0, BHWP_FRAMES_TABLE = 1, BHWP_FRAMES_PER_FRAME = 2 };
+constexpr uint32_t kFramesBlock = 256;          // lanes of a workgroup: min(N, 256) along k, the rest side by side over frames
+constexpr uint32_t kFramesTargetWg = 4096;      // workgroups the frame groups are cut for (16 per CU on 256 CUs) ...
+constexpr uint64_t kFramesOnePassGx = 1024;     // ... unless one pass over the window is this many already: then G = every frame
+constexpr uint32_t kFramesMaxGridY = 65535;
+// Per-frame route of a one-channel CORDIC call: below this many frames one bhw_apply_device per frame costs
+// less than the direct CORDIC of every coefficient in the frames kernel.  Measured with BH-7 / 32 bits (192 rotations per
+// coefficient: (n_terms - 1) * n_iter) at 2^18, 2^20 and 2^22 (profiles/r07_apply_frames.json: 22 / 65 / 230 us for the frames
+// kernel against 7.7 / 11.4 / 28 us per frame); other configurations scale it by their rotations per coefficient.
+constexpr uint32_t kFramesPerFrameRef = 192;
+inline uint32_t bhwp_frames_crossover(uint32_t phi_width) { return phi_width >= 22 ? 8u : phi_width >= 20 ? 6u : phi_width >= 18 ? 3u : 0u; }
+struct BhwFramesPlan {
+    int route;           // BHWP_FRAMES_*
+    uint32_t kx;         // lanes of a workgroup along k: min(N, kFramesBlock)
+    uint32_t fy;         // frames a workgroup runs side by side: kFramesBlock / kx
+    uint64_t group;      // G: frames one lane applies its coefficient to (in steps of fy)
+    uint64_t grid_x;     // N / kx
+    uint64_t grid_y;     // ceil(frames / (fy * G)) <= kFramesMaxGridY
+    uint64_t y_stride;   // resolved (0 -> N * channels)
+};
+// Every argument check of the two calls that needs no table handle, before any HIP call: BHW_OK, BADARG or UNSUPPORTED (Taylor with
+// two channels).  frames == 0 passes with the pointers unchecked (nothing to do); `pointers` false: the describe call, no pointers.
+int  bhwp_frames_checks(const bhw_params *p, const bhw_frames *f, const void *d_x, const void *d_y, bool pointers = true);
+// route, frame-group size and grid of a call that passed bhwp_frames_checks; force_route >= 0 overrides the route rule (A/B runs)
+BhwFramesPlan bhwp_frames_plan(const bhw_params *p, const bhw_frames *f, bool from_table, int force_route = -1);
+// bhw_apply_frames_describe: ct = the resident table's resolved configuration (format and layout set), or NULL for the library call
+int  bhwp_describe_frames(const bhw_params *p, const BhwCordicCfg *ct, const bhw_frames *f, char *buf, uint64_t len);
+// k_frames_direct in the mad-form rotation of k_direct_fast (the same condition as bhwk_direct's): form 2, else 1 (64-bit state) or 0
+inline bool bhwp_frames_mad_form(const BhwCordicCfg &c) { return c.dat_width + c.out_shr <= 34 && c.n_iter >= 7; }
+// the frames kernel of a plan (bhw_frames.hip): d_table NULL = k_frames_direct, else k_frames_table over the resident table of c
+int  bhwk_frames(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwFramesPlan &pl, const bhw_frames *f,
+                 const int32_t *d_x, int32_t *d_y, const int32_t *d_table);

@@ -142,6 +142,55 @@ def apply(params, x, *, n0=0, shift=None, out=None):
     return out
 
 
+def _frames_call(torch, params, x, hop, frames, channels, shift, out, y_stride, dev):
+    """Checks and shapes of apply_frames: (bhw_frames, out, the tensor returned)."""
+    if x.dtype != torch.int32 or not x.is_cuda or not x.is_contiguous() or x.device.index != dev:
+        raise ValueError("x must be a contiguous int32 CUDA tensor on the call's device")
+    if channels not in (1, 2):
+        raise ValueError("channels must be 1 or 2")
+    if hop < 1:
+        raise ValueError("hop must be >= 1")
+    N = 1 << params.phi_width
+    samples = x.numel() // channels
+    if x.numel() % channels:
+        raise ValueError("x must hold whole I/Q pairs")
+    if frames is None:
+        frames = 0 if samples < N else (samples - N) // hop + 1
+    if frames and ((frames - 1) * hop + N) > samples:
+        raise ValueError(f"x holds {samples} time indices, {frames} frames at hop {hop} need {(frames - 1) * hop + N}")
+    stride = N * channels if y_stride is None else int(y_stride)
+    if stride < N * channels:
+        raise ValueError(f"y_stride must be >= N * channels = {N * channels}")
+    if out is None:
+        out = torch.empty((frames, stride), dtype=torch.int32, device=x.device)
+    elif _check_out(torch, out, frames * stride if frames else 0) != dev:
+        raise ValueError("out must live on x's device")
+    if shift is None:
+        shift = params.dat_width - 1
+    f = B.make_frames(frames, hop, channels=channels, shift=shift, y_stride=stride)
+    flat = out.view(-1)[:frames * stride]
+    if y_stride is not None:
+        result = flat.view(frames, stride)
+    else:
+        result = flat.view((frames, N, 2) if channels == 2 else (frames, N))
+    return f, out, result
+
+
+def apply_frames(params, x, hop, *, frames=None, channels=1, shift=None, out=None, y_stride=None):
+    """Overlapped-frame apply (bhw_apply_frames_device): y[f, k, c] = (x[(f * hop + k) * C + c] * w[k]) >> shift for every frame f,
+    with one launch (the STFT / Welch front end).  x: contiguous int32 (time-major, I/Q interleaved for channels = 2); frames=None
+    takes as many as fit.  Returns a (frames, N) int32 tensor, (frames, N, 2) for I/Q, or a (frames, y_stride) view when y_stride
+    is given (the elements past N * channels of each row are not written).  shift defaults to dat_width - 1."""
+    torch = _torch()
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise ValueError("x must be a contiguous int32 CUDA tensor")
+    dev = x.device.index
+    f, out, result = _frames_call(torch, params, x, int(hop), frames, channels, shift, out, y_stride, dev)
+    B.check(B.lib().bhw_apply_frames_device(ctypes.byref(params), dev, _stream_ptr(torch, dev), ctypes.byref(f),
+                                            ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr())))
+    return result
+
+
 class ResidentTable:
     """A first-quadrant CORDIC table built once and kept on the device (bhw_table_create): the elaboration of win_selector's
     CORDIC from its generics (model, PHI_WIDTH, DAT_WIDTH, PRECISION).  Every call then takes the run-time ports -- the weights
@@ -219,6 +268,22 @@ class ResidentTable:
         B.check(B.lib().bhw_apply_from_table(h, ctypes.byref(params), _stream_ptr(torch, self.device), int(n0), x.numel(),
                                              ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr()), int(shift)))
         return out
+
+    def apply_frames(self, params, x, hop, *, frames=None, channels=1, shift=None, out=None, y_stride=None):
+        """apply_frames() with the coefficients gathered from this table (bhw_apply_frames_from_table): no allocation by the
+        library, no synchronisation, capturable into a graph."""
+        torch = _torch()
+        h = self._live()
+        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.device.index != self.device:
+            raise ValueError("x must be a contiguous int32 CUDA tensor on the table's device")
+        f, out, result = _frames_call(torch, params, x, int(hop), frames, channels, shift, out, y_stride, self.device)
+        B.check(B.lib().bhw_apply_frames_from_table(h, ctypes.byref(params), _stream_ptr(torch, self.device), ctypes.byref(f),
+                                                    ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr())))
+        return result
+
+    def describe_frames(self, params, frames, hop, *, channels=1, y_stride=0):
+        """The route and kernels apply_frames(params, ...) launches over this table (bhw_apply_frames_describe)."""
+        return B.describe_frames(params, frames, hop, channels=channels, y_stride=y_stride, table=self._live())
 
     def generate_part(self, params, part, n_parts, window):
         """Interleaved ownership part `part` of `n_parts` into the full-length `window` (bhw_generate_part_from_table)."""

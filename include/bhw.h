@@ -28,7 +28,8 @@
 extern "C" {
 #endif
 
-#define BHW_ABI_VERSION 4u   /* 3: bhw_coeffs_preset, bhw_gather_parts_device; 4: bhw_workspace_bytes_ex (nothing removed or changed) */
+#define BHW_ABI_VERSION 4u   /* 3: bhw_coeffs_preset, bhw_gather_parts_device; 4: bhw_workspace_bytes_ex (nothing removed or changed);
+                                the resident tables and the overlapped-frame apply were added without a bump (additions only) */
 
 /* CORDIC bit-model (the reference holds three that are not bit-identical). */
 enum {
@@ -292,6 +293,39 @@ int bhw_apply_from_table(bhw_table t, const bhw_params *p, void *hip_stream, uin
                          const int32_t *d_x, int32_t *d_y, uint32_t shift);
 int bhw_generate_part_from_table(bhw_table t, const bhw_params *p, void *hip_stream, uint32_t part, uint32_t n_parts,
                                  int32_t *d_window);
+
+/* Overlapped-frame apply (the STFT / Welch front end: the window multiplies overlapping frames of one signal in front of an FFT).
+ * With N = 2^phi_width, C = channels and w[k] the coefficient bhw_generate_device(p, n0 = 0) gives at index k, for f < frames,
+ * k < N, c < C:
+ *     d_y[f * y_stride + k * C + c] = low32((int64 d_x[(f * hop + k) * C + c] * w[k]) >> shift)
+ * the arithmetic of bhw_apply_device (exact 64-bit product, floor shift 0..62, low 32 bits stored).  Both channels of a time index
+ * share one coefficient; hop >= 1 is free (below N: overlap, N: back to back, above N: gaps); y_stride counts int32 elements between
+ * frame starts in d_y (0 = N * C; a larger stride lands the frames in a zero-padded FFT input, the elements between N * C and
+ * y_stride are never written).  d_x holds ((frames - 1) * hop + N) * C int32; d_y must not overlap d_x.
+ *   - All argument checks come before any HIP call: NULL pointers, struct_size, channels outside {1, 2}, hop 0, y_stride below N * C,
+ *     shift > 62, reserved != 0, overlap of d_x and d_y, frames * N above 2^34, and (from a table) the key match of the table calls.
+ *   - bhw_apply_frames_device accepts every configuration bhw_apply_device accepts.  Each coefficient is computed once per lane and
+ *     applied to a group of frames (k_frames_direct: direct CORDIC, no table, no scratch -- capturable with no bhw_prepare_device).
+ *     For one channel the planner may instead take the per-frame route, one bhw_apply_device call per frame: always for the Taylor
+ *     sources, and for long windows with few frames, where one apply per frame costs less than the direct CORDIC of every
+ *     coefficient (the crossover is measured).  The Taylor sources with channels = 2 are BHW_ERR_UNSUPPORTED.
+ *   - bhw_apply_frames_from_table accepts what bhw_apply_from_table accepts and keeps its contract: no allocation, no
+ *     synchronisation, always capturable; the coefficients are gathered from the resident table (k_frames_table).
+ *   - bhw_apply_frames_describe: one line -- the route, the frame-group size and the kernel names.  t may be NULL (the library
+ *     call).  Host arithmetic only. */
+typedef struct bhw_frames {
+    uint32_t struct_size;  /* sizeof(bhw_frames)                                     */
+    uint32_t channels;     /* 1 (real) or 2 (interleaved I/Q)                        */
+    uint64_t frames;       /* 0 = nothing to do                                      */
+    uint64_t hop;          /* time indices between frame starts, >= 1                */
+    uint64_t y_stride;     /* int32 elements between frames in d_y; 0 = N * channels  */
+    uint32_t shift;        /* 0..62                                                  */
+    uint32_t reserved;     /* must be 0                                              */
+} bhw_frames;
+int bhw_apply_frames_device(const bhw_params *p, int device, void *hip_stream, const bhw_frames *f, const int32_t *d_x, int32_t *d_y);
+int bhw_apply_frames_from_table(bhw_table t, const bhw_params *p, void *hip_stream, const bhw_frames *f, const int32_t *d_x,
+                                int32_t *d_y);
+int bhw_apply_frames_describe(bhw_table t, const bhw_params *p, const bhw_frames *f, char *buf, uint64_t len);
 
 /* Threading: every entry point may be called from any host thread.  Calls that use the library-owned scratch of one
  * (device, stream) are serialised against each other for the duration of their launches (the table is rebuilt per call);

@@ -7,6 +7,7 @@
 //                            entities cordic_dds / cordic_dds48 / cordic_dds_scaled (model BHW_MODEL_VHDL / _DDS48 / _SCALED)
 //   bhw::cordic_atan2() <->  entity cordic_atan2            src/cordic_atan2.vhd:64-76
 //   bhw::resident_table      the elaborated CORDIC of win_selector's generics (bhw_table_create), move-only, RAII
+//   bhw::apply_frames()      the window over overlapping frames of a signal in one launch (bhw_apply_frames_device)
 // Same names, argument meaning and error behaviour (unknown win_type -> zeros, like win_empty,
 // hls/windows/win_function.cpp:159-165,417-419).  All arithmetic runs in the HIP kernels behind the ABI.
 #pragma once
@@ -167,6 +168,19 @@ inline std::vector<int32_t> cordic_atan2(unsigned PRECISION, unsigned INPUT_WIDT
     return phi;
 }
 
+// The descriptor of an overlapped-frame apply: `frames` frames of `hop` time indices apart, `channels` 1 or 2 (I/Q), y_stride 0 = N * C.
+inline bhw_frames frames(uint64_t n_frames, uint64_t hop, uint32_t shift, uint32_t channels = 1, uint64_t y_stride = 0)
+{
+    return bhw_frames{(uint32_t)sizeof(bhw_frames), channels, n_frames, hop, y_stride, shift, 0u};
+}
+
+// Overlapped-frame apply (the STFT / Welch front end): the window of `p` over every frame of d_x in one launch
+// (bhw_apply_frames_device); device pointers and stream as in the C call.
+inline void apply_frames(const bhw_params &p, const bhw_frames &f, const int32_t *d_x, int32_t *d_y, int device = 0, void *hip_stream = nullptr)
+{
+    check(bhw_apply_frames_device(&p, device, hip_stream, &f, d_x, d_y));
+}
+
 // The CORDIC table of a configuration's generics, built once on `device` (bhw_table_create) and freed by the destructor
 // (bhw_table_destroy: it synchronises the device first).  Move-only.  Every call takes its weights -- the AA ports -- from its own
 // bhw_params, which must match the table's generics; device pointers and streams as in the C calls.
@@ -207,6 +221,16 @@ public:
     void apply(const bhw_params &p, void *hip_stream, uint64_t n0, uint64_t count, const int32_t *d_x, int32_t *d_y, uint32_t shift) const
     {
         check(bhw_apply_from_table(t_, &p, hip_stream, n0, count, d_x, d_y, shift));
+    }
+    void apply_frames(const bhw_params &p, void *hip_stream, const bhw_frames &f, const int32_t *d_x, int32_t *d_y) const
+    {
+        check(bhw_apply_frames_from_table(t_, &p, hip_stream, &f, d_x, d_y));
+    }
+    std::string describe_frames(const bhw_params &p, const bhw_frames &f) const
+    {
+        char buf[384];
+        check(bhw_apply_frames_describe(t_, &p, &f, buf, sizeof buf));
+        return buf;
     }
     void generate_part(const bhw_params &p, void *hip_stream, uint32_t part, uint32_t n_parts, int32_t *d_window) const
     {
