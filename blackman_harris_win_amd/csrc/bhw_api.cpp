@@ -28,13 +28,23 @@ int fail_hip(int hip_code, const char *what)
     return fail(BHW_ERR_HIP, "%s: %s (hipError %d)", what, hipGetErrorString((hipError_t)hip_code), hip_code);
 }
 
-// The calling thread's current device is switched for the duration of an entry point and put back afterwards.
+bool device_ok(int device)
+{
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) return false;
+    return device >= 0 && device < n;
+}
+
+// The calling thread's current device is switched for the duration of an entry point and put back afterwards.  status() is the
+// entry point's prologue: BHW_ERR_HIP, with bhw_last_error() set, when `device` cannot be made current or -- with `check_device` --
+// is no usable device at all (nothing is switched then).  The hooks that report neither do not ask.
 struct DeviceGuard {
-    int prev = -1;
-    bool switched = false;
+    int device, prev = -1;
+    bool usable, switched = false;
     hipError_t err = hipSuccess;
-    explicit DeviceGuard(int device)
+    explicit DeviceGuard(int dev, bool check_device = true) : device(dev), usable(!check_device || device_ok(dev))
     {
+        if (!usable) return;
         if (hipGetDevice(&prev) != hipSuccess) prev = -1;
         if (prev != device) {
             err = hipSetDevice(device);
@@ -44,6 +54,11 @@ struct DeviceGuard {
     ~DeviceGuard()
     {
         if (switched && prev >= 0) (void)hipSetDevice(prev);
+    }
+    int status() const
+    {
+        if (!usable) return fail(BHW_ERR_HIP, "no usable HIP device %d (this library has no CPU path)", device);
+        return err != hipSuccess ? fail_hip(err, "hipSetDevice") : BHW_OK;
     }
     DeviceGuard(const DeviceGuard &) = delete;
     DeviceGuard &operator=(const DeviceGuard &) = delete;
@@ -162,79 +177,95 @@ int resolve_taylor(const bhw_params *p, int device, void *stream, BhwTaylorCfg &
     return get_taylor_rom(device, stream, p->dat_width, p->lut_size, &t.rom);
 }
 
-bool device_ok(int device)
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return false;
-    return device >= 0 && device < n;
-}
-
-// Runs [n0, n0+count) as  head | whole periods | tail.  `ragged(off, len)` handles an arbitrary sub-range,
-// `period(off)` one whole period starting at a multiple of N.  Without the fused apply only the first period is
-// computed and the others are store-only replicas; with it every period has its own x.
+// Runs [n0, n0+count) as  head | whole periods | tail.  `ragged(w, off, len)` handles an arbitrary sub-range, `period(w, off)`
+// one whole period starting at a multiple of N; each gets `w` with the fused apply's input (w.apply_x, if any) advanced to its
+// piece.  Without the fused apply only the first period is computed and the others are store-only replicas; with it every
+// period has its own x.
 template <typename Ragged, typename Period>
-int run_split(const BhwLaunch &l, uint64_t n0, uint64_t count, uint64_t N, bool per_period_input, int32_t *d_out,
-              Ragged ragged, Period period)
+int run_split(const BhwLaunch &l, const BhwWinCfg &w, uint64_t n0, uint64_t count, uint64_t N, int32_t *d_out, Ragged ragged, Period period)
 {
+    BhwWinCfg piece = w;
+    auto at = [&](uint64_t off) -> const BhwWinCfg & {
+        if (w.apply_x) piece.apply_x = w.apply_x + off;
+        return piece;
+    };
     const uint64_t head_len = (N - n0 % N) % N;
     int e;
     if (count < head_len + N) {
-        e = ragged(0, count);
+        e = ragged(at(0), 0, count);
         return e ? fail_hip(e, "launch") : BHW_OK;
     }
     const uint64_t head = head_len, periods = (count - head) / N, tail = count - head - periods * N;
-    e = head ? ragged(0, head) : 0;
+    e = head ? ragged(at(0), 0, head) : 0;
     if (e) return fail_hip(e, "head launch");
-    const uint64_t computed = per_period_input ? periods : 1;
+    const uint64_t computed = w.apply_x ? periods : 1;
     for (uint64_t f = 0; f < computed; ++f) {
-        e = period(head + f * N);
+        e = period(at(head + f * N), head + f * N);
         if (e) return fail_hip(e, "whole-period launch");
     }
-    if (!per_period_input && periods > 1) {
+    if (!w.apply_x && periods > 1) {
         e = bhwk_replicate(l, d_out + head, N, (uint32_t)(periods - 1), d_out + head + N);
         if (e) return fail_hip(e, "replicate launch");
     }
-    e = tail ? ragged(head + periods * N, tail) : 0;
+    e = tail ? ragged(at(head + periods * N), head + periods * N, tail) : 0;
     return e ? fail_hip(e, "tail launch") : BHW_OK;
 }
 
-// Build the table in the narrowest format that is exact for this configuration.  A packed format whose exactness has not
-// been established yet for the configuration is built with the kernels' overflow check on and read back here (once per
-// process and configuration; during stream capture the plain format is used instead).  `ws` holds
-// bhwp_table_scratch_bytes(...) bytes, laid out per format by bhwp_table_layout.
-int build_table(const bhw_params *p, const BhwLaunch &l, BhwCordicCfg &c, bool tiled, uint32_t limit, void *ws)
+// Points `c` at a table in format `dlog` laid out in `buf` (bhwp_table_layout), with the overflow check off.
+void point_table(BhwCordicCfg &c, uint32_t dlog, const void *buf)
 {
-    uint32_t cand[kMaxFormats];
-    const int n_cand = bhwp_table_format_candidates(c, tiled, limit, cand);
-    const uint64_t E = bhwp_table_entries(c);
-    for (int i = 0; i < n_cand; ++i) {
-        const uint32_t dlog = cand[i];
-        int verdict = dlog ? bhwp_fmt_verdict(p, dlog) : (int)kFmtOk;
+    const BhwTableLayout lay = bhwp_table_layout(bhwp_table_entries(c), dlog);
+    c.tab_dlog = dlog;
+    c.tab_coarse = dlog ? (const void *)((const char *)buf + lay.coarse_off) : nullptr;
+    c.tab_esc = lay.esc_off ? (const void *)((const char *)buf + lay.esc_off) : nullptr;
+    c.esc_wg_log = lay.esc_wg_log;
+    c.tab_check = nullptr;
+}
+
+// Builds the packed table `c` points at in `buf` with the kernels' overflow check on, reads the check word back into *flag
+// (non-zero: the format overflowed) and synchronises.  Returns the raw HIP status; `stage` names the step that failed.
+int checked_build(const BhwLaunch &l, BhwCordicCfg c, void *buf, uint32_t *flag, const char **stage = nullptr)
+{
+    c.tab_check = (uint32_t *)((char *)buf + bhwp_table_layout(bhwp_table_entries(c), c.tab_dlog).check_off);
+    const char *what = "hipMemsetAsync(check word)";
+    int e = hipMemsetAsync(c.tab_check, 0, 8, (hipStream_t)l.stream);
+    if (!e) {
+        what = "table build launch";
+        e = bhwk_table_build(l, c, (int32_t *)buf);
+    }
+    if (!e) {
+        what = "read-back of the table format check";
+        e = hipMemcpyAsync(flag, c.tab_check, sizeof *flag, hipMemcpyDeviceToHost, (hipStream_t)l.stream);
+    }
+    if (!e) e = hipStreamSynchronize((hipStream_t)l.stream);
+    if (e && stage) *stage = what;
+    return e;
+}
+
+// Build the table in the narrowest format that is exact for this configuration: the walk's open formats first, each with the
+// kernels' overflow check on and read back (once per process and configuration; a capture walks none), then the one it kept.
+// Each open verdict is read again first: another call may have settled it since the walk.  `ws` holds fw.scratch_bytes bytes.
+int build_table(const bhw_params *p, const BhwLaunch &l, BhwCordicCfg &c, const BhwFormatWalk &fw, void *ws)
+{
+    uint32_t dlog = fw.kept;
+    for (int i = 0; i < fw.n_open; ++i) {
+        const int verdict = bhwp_fmt_verdict(p, fw.open[i]);
         if (verdict == kFmtBad) continue;
-        if (verdict == kFmtUnknown && stream_is_capturing(l.stream)) continue;   // no read-back inside a capture
-        const BhwTableLayout lay = bhwp_table_layout(E, dlog);
-        c.tab_dlog = dlog;
-        c.tab_coarse = dlog ? (const void *)((const char *)ws + lay.coarse_off) : nullptr;
-        c.tab_esc = lay.esc_off ? (const void *)((const char *)ws + lay.esc_off) : nullptr;
-        c.esc_wg_log = lay.esc_wg_log;
-        c.tab_check = nullptr;
-        if (verdict == kFmtUnknown) {
-            c.tab_check = (uint32_t *)((char *)ws + lay.check_off);
-            const hipError_t he = hipMemsetAsync(c.tab_check, 0, 8, (hipStream_t)l.stream);
-            if (he != hipSuccess) return fail_hip(he, "hipMemsetAsync(check word)");
+        if (verdict == kFmtOk) {
+            dlog = fw.open[i];
+            break;
         }
-        const int e = bhwk_table_build(l, c, (int32_t *)ws);
-        if (e) return fail_hip(e, "table build launch");
-        if (verdict == kFmtOk) return BHW_OK;
+        point_table(c, fw.open[i], ws);
         uint32_t flag = 1;
-        hipError_t he = hipMemcpyAsync(&flag, c.tab_check, sizeof flag, hipMemcpyDeviceToHost, (hipStream_t)l.stream);
-        if (he == hipSuccess) he = hipStreamSynchronize((hipStream_t)l.stream);
-        if (he != hipSuccess) return fail_hip(he, "read-back of the table format check");
-        c.tab_check = nullptr;
-        bhwp_fmt_set_verdict(p, dlog, flag ? kFmtBad : kFmtOk);
+        const char *stage = "";
+        const int e = checked_build(l, c, ws, &flag, &stage);
+        if (e) return fail_hip(e, stage);
+        bhwp_fmt_set_verdict(p, fw.open[i], flag ? kFmtBad : kFmtOk);
         if (!flag) return BHW_OK;                                                // exact: keep the table just built
     }
-    return fail(BHW_ERR_HIP, "no table format applies");                         // unreachable: plain is always a candidate
+    point_table(c, dlog, ws);
+    const int e = bhwk_table_build(l, c, (int32_t *)ws);
+    return e ? fail_hip(e, "table build launch") : BHW_OK;
 }
 
 // Scratch of a table-strategy call: the caller's workspace when it passed one, else the library-owned buffer of this stream
@@ -271,17 +302,54 @@ int acquire_scratch(const bhw_exec *ex, int device, void *stream, uint64_t need,
     return BHW_OK;
 }
 
-// true while some packed format this call may try has no verdict yet (its scratch is then sized for every candidate)
-bool verdicts_open(const bhw_params *p, const BhwCordicCfg &c, bool tiled, uint32_t limit)
+// The table of a table-strategy call, rebuilt: scratch for the formats the call may use (acquire_scratch; a slot stays locked in
+// `scratch` until every launch of the call is enqueued), the table built into it, then ex->event_after_build recorded.
+// Whole-period tile tables are stored packed when the widths allow it (formats in bhw_device.h): "nibble" = 1 byte per entry,
+// "residual" = 2 bytes + one int4 record per 2^d entries, else "delta16" = 4 bytes per entry + one int2 head per 64 entries, else
+// the plain 8 bytes per entry.
+int rebuild_table(const bhw_params *p, const BhwLaunch &l, BhwCordicCfg &c, bool tiled, const bhw_exec *ex, TableScratch &scratch)
 {
-    uint32_t cand[kMaxFormats];
-    const int n = bhwp_table_format_candidates(c, tiled, limit, cand);
-    for (int i = 0; i < n; ++i) {
-        const int v = cand[i] ? bhwp_fmt_verdict(p, cand[i]) : (int)kFmtOk;
-        if (v == kFmtOk) return false;
-        if (v == kFmtUnknown) return true;
+    const BhwFormatWalk fw = bhwp_format_walk(p, c, tiled, bhwp_exec_table_format(ex), stream_is_capturing(l.stream));
+    int rc = acquire_scratch(ex, l.device, l.stream, fw.scratch_bytes, fw.n_open != 0, scratch);
+    if (!rc) rc = build_table(p, l, c, fw, scratch.ws);
+    if (rc || !ex || !ex->event_after_build) return rc;
+    const hipError_t he = hipEventRecord((hipEvent_t)ex->event_after_build, (hipStream_t)l.stream);
+    return he != hipSuccess ? fail_hip(he, "hipEventRecord(event_after_build)") : BHW_OK;
+}
+
+// A built table: the configuration pointing at it, and whether whole periods take the tile kernel.
+struct TableView {
+    const BhwCordicCfg &c;
+    bool tiled;
+    const int32_t *tab;
+};
+// ragged pieces over a built table: bhwk_table_combine (the rebuilt path) or bhwk_range_combine (resident tables)
+using RaggedKernel = int (*)(const BhwLaunch &, const BhwCordicCfg &, const BhwWinCfg &, const int32_t *, uint64_t, uint64_t, int32_t *);
+
+// [n0, n0 + count) over a built table: the tile kernel over an image subset (a contiguous range of whole eighths of one window --
+// one device's contiguous shard of a window split over 2, 4 or 8), else head | whole periods | tail with the whole periods on the
+// run-length kernel (dropped phase bits: consecutive coefficients repeat table entries) or the tile / fold kernel of the layout.
+int table_pieces(const BhwLaunch &l, const TableView &t, const bhw_params *p, const BhwWinCfg &w, uint64_t n0, uint64_t count,
+                 int32_t *d_out, RaggedKernel ragged)
+{
+    const BhwTableCall tc = bhwp_table_call(p, t.c, w, n0, count, w.apply_x != nullptr);
+    if (tc.images) {
+        const int e = bhwk_table_combine_tile_range(l, t.c, w, t.tab, d_out, 0, 0, tc.img_mask, tc.n0mod);
+        return e ? fail_hip(e, "tile launch (image subset)") : BHW_OK;
     }
-    return false;
+    auto piece = [&](const BhwWinCfg &wp, uint64_t off, uint64_t len) { return ragged(l, t.c, wp, t.tab, n0 + off, len, d_out + off); };
+    auto period = [&](const BhwWinCfg &wp, uint64_t off) {
+        if (bhwk_runlength_applicable(t.c, wp, d_out + off)) return bhwk_runlength_window(l, t.c, wp, t.tab, d_out + off);
+        return t.tiled ? bhwk_table_combine_tile(l, t.c, wp, t.tab, d_out + off) : bhwk_table_combine_fold(l, t.c, wp, t.tab, d_out + off);
+    };
+    return run_split(l, w, n0, count, 1ull << p->phi_width, d_out, piece, period);
+}
+
+// the tiles [tile0, tile0 + tile_count) of an ownership part over a built table
+int part_tiles(const BhwLaunch &l, const TableView &t, const BhwWinCfg &w, uint32_t tile0, uint32_t tile_count, int32_t *d_window)
+{
+    const int e = bhwk_table_combine_tile_range(l, t.c, w, t.tab, d_window, tile0, tile_count);
+    return e ? fail_hip(e, "tile part launch") : BHW_OK;
 }
 
 int generate_impl(const bhw_params *p, int device, void *stream, uint64_t n0, uint64_t count, int32_t *d_out,
@@ -294,9 +362,8 @@ int generate_impl(const bhw_params *p, int device, void *stream, uint64_t n0, ui
     if (rc) return rc;
     if (!count) return BHW_OK;
     if (count > (1ull << 34)) return fail(BHW_ERR_BADARG, "count %llu > 2^34 per call", (unsigned long long)count);
-    if (!device_ok(device)) return fail(BHW_ERR_HIP, "no usable HIP device %d (this library has no CPU path)", device);
     DeviceGuard guard(device);
-    if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
+    if ((rc = guard.status())) return rc;
     BhwLaunch l{device, stream};
     BhwWinCfg w;
     bhwp_resolve_window(p, w);
@@ -306,20 +373,13 @@ int generate_impl(const bhw_params *p, int device, void *stream, uint64_t n0, ui
         BhwTaylorCfg t;
         rc = resolve_taylor(p, device, stream, t);
         if (rc) return rc;
-        const uint64_t NT = 1ull << p->phi_width;
-        auto ragged = [&](uint64_t off, uint64_t len) -> int {
-            if (apply_x) w.apply_x = apply_x + off;
-            return bhwk_taylor_window(l, t, w, n0 + off, len, d_out + off);
-        };
+        auto ragged = [&](const BhwWinCfg &wp, uint64_t off, uint64_t len) { return bhwk_taylor_window(l, t, wp, n0 + off, len, d_out + off); };
         if (p->phi_width < 5) {
-            int e = ragged(0, count);
+            int e = ragged(w, 0, count);
             return e ? fail_hip(e, "taylor window launch") : BHW_OK;
         }
-        auto period = [&](uint64_t off) -> int {
-            if (apply_x) w.apply_x = apply_x + off;
-            return bhwk_taylor_window_fold(l, t, w, d_out + off);
-        };
-        return run_split(l, n0, count, NT, apply_x != nullptr, d_out, ragged, period);
+        auto period = [&](const BhwWinCfg &wp, uint64_t off) { return bhwk_taylor_window_fold(l, t, wp, d_out + off); };
+        return run_split(l, w, n0, count, 1ull << p->phi_width, d_out, ragged, period);
     }
     BhwCordicCfg c;
     bhwp_resolve_cordic(p, c);
@@ -331,57 +391,18 @@ int generate_impl(const bhw_params *p, int device, void *stream, uint64_t n0, ui
     if (algo == BHW_ALGO_FUSED) {
         // head | whole periods | tail: each whole period is one launch of the fused kernel over the full ring, the ragged
         // ends take the direct kernel; nothing is allocated and no table exists
-        const uint64_t NF = 1ull << p->phi_width;
         const BhwFoldRun ring{0u, 1u << (p->phi_width - 3)};
-        auto ragged = [&](uint64_t off, uint64_t len) -> int {
-            if (apply_x) w.apply_x = apply_x + off;
-            return bhwk_direct(l, c, w, n0 + off, len, d_out + off);
-        };
-        auto period = [&](uint64_t off) -> int {
-            if (apply_x) w.apply_x = apply_x + off;
-            return bhwk_fold_direct(l, c, w, &ring, 1, d_out + off);
-        };
-        return run_split(l, n0, count, NF, apply_x != nullptr, d_out, ragged, period);
+        auto ragged = [&](const BhwWinCfg &wp, uint64_t off, uint64_t len) { return bhwk_direct(l, c, wp, n0 + off, len, d_out + off); };
+        auto period = [&](const BhwWinCfg &wp, uint64_t off) { return bhwk_fold_direct(l, c, wp, &ring, 1, d_out + off); };
+        return run_split(l, w, n0, count, 1ull << p->phi_width, d_out, ragged, period);
     }
-    // head | whole periods | tail over the one table built here: the whole periods take the fold / tile kernels (a contiguous
-    // range of whole eighths of one window -- one device's contiguous shard of a window split over 2, 4 or 8 -- the tile kernel
-    // over the images it covers), the ragged ends the general gather kernel
-    const uint64_t N = 1ull << p->phi_width;
+    // the one table built here, then its pieces; the ragged ends take the general gather kernel
     const BhwTableCall tc = bhwp_table_call(p, c, w, n0, count, apply_x != nullptr);
-    const bool tiled = tc.tiled, images = tc.images;
-    const uint32_t img_mask = tc.img_mask, n0mod = tc.n0mod;
-    c.tab_split = (tiled && c.z_shr == 0) ? 1u : 0u;
-    // whole-period tile tables are stored packed when the widths allow it (formats in bhw_device.h): "nibble" = 1 byte per entry,
-    // "residual" = 2 bytes + one int4 record per 2^d entries, else "delta16" = 4 bytes per entry + one int2 head per 64 entries, else
-    // the plain 8 bytes per entry.  The scratch is sized for the format(s) this call may use.
-    const uint32_t limit = bhwp_exec_table_format(ex);
+    c.tab_split = (tc.tiled && c.z_shr == 0) ? 1u : 0u;
     TableScratch scratch;
-    const bool capturing = stream_is_capturing(stream);
-    rc = acquire_scratch(ex, device, stream, bhwp_table_scratch_bytes(p, c, tiled, limit, capturing), !capturing && verdicts_open(p, c, tiled, limit), scratch);
+    rc = rebuild_table(p, l, c, tc.tiled, ex, scratch);
     if (rc) return rc;
-    void *ws = scratch.ws;
-    rc = build_table(p, l, c, tiled, limit, ws);
-    if (rc) return rc;
-    if (ex && ex->event_after_build) {
-        hipError_t he = hipEventRecord((hipEvent_t)ex->event_after_build, (hipStream_t)stream);
-        if (he != hipSuccess) return fail_hip(he, "hipEventRecord(event_after_build)");
-    }
-    auto ragged = [&](uint64_t off, uint64_t len) -> int {
-        if (apply_x) w.apply_x = apply_x + off;
-        return bhwk_table_combine(l, c, w, (const int32_t *)ws, n0 + off, len, d_out + off);
-    };
-    auto period = [&](uint64_t off) -> int {
-        if (apply_x) w.apply_x = apply_x + off;
-        // dropped phase bits: consecutive coefficients repeat table entries -- the run-length kernel works per breakpoint
-        if (bhwk_runlength_applicable(c, w, d_out + off)) return bhwk_runlength_window(l, c, w, (const int32_t *)ws, d_out + off);
-        return tiled ? bhwk_table_combine_tile(l, c, w, (const int32_t *)ws, d_out + off)
-                     : bhwk_table_combine_fold(l, c, w, (const int32_t *)ws, d_out + off);
-    };
-    if (images) {
-        const int e = bhwk_table_combine_tile_range(l, c, w, (const int32_t *)ws, d_out, 0, 0, img_mask, n0mod);
-        return e ? fail_hip(e, "tile launch (image subset)") : BHW_OK;
-    }
-    return run_split(l, n0, count, N, apply_x != nullptr, d_out, ragged, period);
+    return table_pieces(l, TableView{c, tc.tiled, (const int32_t *)scratch.ws}, p, w, n0, count, d_out, bhwk_table_combine);
 }
 
 // bhw_apply_frames_device: the frames kernel with the direct CORDIC source (no table, no scratch), or one bhw_apply_device per
@@ -399,9 +420,8 @@ int frames_impl(const bhw_params *p, int device, void *stream, const bhw_frames 
         }
         return BHW_OK;
     }
-    if (!device_ok(device)) return fail(BHW_ERR_HIP, "no usable HIP device %d (this library has no CPU path)", device);
     DeviceGuard guard(device);
-    if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
+    if ((rc = guard.status())) return rc;
     BhwCordicCfg c;
     bhwp_resolve_cordic(p, c);
     BhwWinCfg w;
@@ -428,12 +448,8 @@ int bhw_generate_device_ex(const bhw_params *p, int device, void *hip_stream, ui
 int bhw_apply_device(const bhw_params *p, int device, void *hip_stream, uint64_t n0, uint64_t count,
                      const int32_t *d_x, int32_t *d_y, uint32_t shift)
 {
-    if (count && (!d_x || !d_y)) return fail(BHW_ERR_BADARG, "d_x / d_y is NULL");
-    if (shift > 62) return fail(BHW_ERR_BADARG, "shift %u > 62", shift);
-    const uintptr_t xa = (uintptr_t)d_x, ya = (uintptr_t)d_y, bytes = (uintptr_t)count * 4u;
-    if (count && xa < ya + bytes && ya < xa + bytes)
-        return fail(BHW_ERR_BADARG, "d_y must not overlap d_x (tile seams recompute a few samples)");
-    return generate_impl(p, device, hip_stream, n0, count, d_y, nullptr, d_x, shift);
+    const int rc = bhwp_apply_checks(count, d_x, d_y, shift);
+    return rc ? rc : generate_impl(p, device, hip_stream, n0, count, d_y, nullptr, d_x, shift);
 }
 
 int bhw_apply_frames_device(const bhw_params *p, int device, void *hip_stream, const bhw_frames *f, const int32_t *d_x, int32_t *d_y)
@@ -466,9 +482,8 @@ int bhw_generate_batched_device(const bhw_params *p, int device, void *hip_strea
         BhwWinCfg w;
         bhwp_resolve_window(p, w);
         if (p->phi_width <= 19 && bhwp_pick_algo(p, c, w, 0, N, BHW_ALGO_AUTO) == BHW_ALGO_FUSED && bhwp_fold_form(c, w, N >> 3) != BHWP_FOLD_SPLIT) {
-            if (!device_ok(device)) return fail(BHW_ERR_HIP, "no usable HIP device %d (this library has no CPU path)", device);
             DeviceGuard guard(device);
-            if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
+            if ((rc = guard.status())) return rc;
             BhwLaunch l{device, hip_stream};
             const BhwFoldRun ring{0u, 1u << (p->phi_width - 3)};
             const int e = bhwk_fold_direct(l, c, w, &ring, 1, d_out, frames);
@@ -478,8 +493,8 @@ int bhw_generate_batched_device(const bhw_params *p, int device, void *hip_strea
     // frame 0 is generated in place, then replicated into frames 1..frames-1
     rc = generate_impl(p, device, hip_stream, 0, N, d_out, nullptr);
     if (rc || frames == 1) return rc;
-    DeviceGuard guard(device);
-    if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
+    DeviceGuard guard(device, false);
+    if ((rc = guard.status())) return rc;
     BhwLaunch l{device, hip_stream};
     int e = bhwk_replicate(l, d_out, N, frames - 1, d_out + N);
     return e ? fail_hip(e, "replicate launch") : BHW_OK;
@@ -492,9 +507,8 @@ int bhw_sincos_device(const bhw_params *p, int device, void *hip_stream, uint64_
     if (rc) return rc;
     if (!count) return BHW_OK;
     if (!d_sin && !d_cos) return fail(BHW_ERR_BADARG, "both outputs NULL");
-    if (!device_ok(device)) return fail(BHW_ERR_HIP, "no usable HIP device %d (this library has no CPU path)", device);
     DeviceGuard guard(device);
-    if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
+    if ((rc = guard.status())) return rc;
     BhwLaunch l{device, hip_stream};
     if (p->sin_type != BHW_SIN_CORDIC) {
         BhwTaylorCfg t;
@@ -521,9 +535,8 @@ int bhw_generate_to_host(const bhw_params *p, int device, uint64_t n0, uint64_t 
     if (rc) return rc;
     if (!count) return BHW_OK;
     if (!h_out) return fail(BHW_ERR_BADARG, "h_out is NULL");
-    if (!device_ok(device)) return fail(BHW_ERR_HIP, "no usable HIP device %d (this library has no CPU path)", device);
     DeviceGuard guard(device);
-    if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
+    if ((rc = guard.status())) return rc;
     int32_t *d = nullptr;
     hipError_t e = hipMalloc((void **)&d, count * sizeof(int32_t));
     if (e != hipSuccess) return fail_hip(e, "hipMalloc(out)");
@@ -542,9 +555,8 @@ int bhw_sincos_to_host(const bhw_params *p, int device, uint64_t theta0, uint64_
     if (rc) return rc;
     if (!count) return BHW_OK;
     if (!h_sin && !h_cos) return fail(BHW_ERR_BADARG, "both outputs NULL");
-    if (!device_ok(device)) return fail(BHW_ERR_HIP, "no usable HIP device %d (this library has no CPU path)", device);
     DeviceGuard guard(device);
-    if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
+    if ((rc = guard.status())) return rc;
     int32_t *d = nullptr;
     hipError_t e = hipMalloc((void **)&d, 2 * count * sizeof(int32_t));
     if (e != hipSuccess) return fail_hip(e, "hipMalloc(out)");
@@ -563,19 +575,10 @@ int bhw_sincos_to_host(const bhw_params *p, int device, uint64_t theta0, uint64_
 
 // Development hooks (not part of the ABI in include/bhw.h): the two passes of the table strategy on their own,
 // for overlap experiments (tools/overlap_probe.py).  They use the narrowest table format already verified for the
-// configuration (a bhw_generate_device call of the same parameters settles it), plain otherwise.
+// configuration (a bhw_generate_device call of the same parameters settles it: the walk's `kept`), plain otherwise.
 static void dbg_verified_format(const bhw_params *p, BhwCordicCfg &c, bool tiled, const void *ws)
 {
-    uint32_t cand[kMaxFormats];
-    const int n = bhwp_table_format_candidates(c, tiled, BHW_TABLE_BEST, cand);
-    c.tab_dlog = 0;
-    for (int i = 0; i < n; ++i)
-        if (cand[i] && bhwp_fmt_verdict(p, cand[i]) == kFmtOk) { c.tab_dlog = cand[i]; break; }
-    const BhwTableLayout lay = bhwp_table_layout(bhwp_table_entries(c), c.tab_dlog);
-    c.tab_coarse = c.tab_dlog ? (const void *)((const char *)ws + lay.coarse_off) : nullptr;
-    c.tab_esc = lay.esc_off ? (const void *)((const char *)ws + lay.esc_off) : nullptr;
-    c.esc_wg_log = lay.esc_wg_log;
-    c.tab_check = nullptr;
+    point_table(c, bhwp_format_walk(p, c, tiled, BHW_TABLE_BEST, false).kept, ws);
 }
 
 int bhw_dbg_table_build(const bhw_params *p, int device, void *stream, void *ws)
@@ -587,7 +590,7 @@ int bhw_dbg_table_build(const bhw_params *p, int device, void *stream, void *ws)
     bhwp_resolve_window(p, w);
     c.tab_split = (bhwk_tile_applicable(c, w) && c.z_shr == 0) ? 1u : 0u;
     dbg_verified_format(p, c, bhwk_tile_applicable(c, w), ws);
-    DeviceGuard guard(device);
+    DeviceGuard guard(device, false);
     BhwLaunch l{device, stream};
     return bhwk_table_build(l, c, (int32_t *)ws);
 }
@@ -599,7 +602,7 @@ int bhw_dbg_table_combine(const bhw_params *p, int device, void *stream, const v
     bhwp_resolve_cordic(p, c);
     BhwWinCfg w;
     bhwp_resolve_window(p, w);
-    DeviceGuard guard(device);
+    DeviceGuard guard(device, false);
     BhwLaunch l{device, stream};
     if (bhwk_tile_applicable(c, w)) {
         c.tab_split = c.z_shr == 0 ? 1u : 0u;
@@ -617,21 +620,10 @@ int bhw_dbg_check_table_format(const bhw_params *p, int device, void *stream, ui
     BhwCordicCfg c;
     bhwp_resolve_cordic(p, c);
     if (c.z_shr != 0 || c.n_iter < 21 || c.dat_width + c.out_shr > 34 || bhwp_table_entries(c) < (1ull << 20)) return BHW_ERR_UNSUPPORTED;   // packed tables exist for tiled windows (PW >= 22) only
-    DeviceGuard guard(device);
-    const BhwTableLayout lay = bhwp_table_layout(bhwp_table_entries(c), dlog);
+    DeviceGuard guard(device, false);
     c.tab_split = 1u;
-    c.tab_dlog = dlog;
-    c.tab_coarse = (const char *)ws + lay.coarse_off;
-    c.tab_esc = lay.esc_off ? (const void *)((const char *)ws + lay.esc_off) : nullptr;
-    c.esc_wg_log = lay.esc_wg_log;
-    c.tab_check = (uint32_t *)((char *)ws + lay.check_off);
-    hipError_t he = hipMemsetAsync(c.tab_check, 0, 8, (hipStream_t)stream);
-    if (he != hipSuccess) return BHW_ERR_HIP;
-    BhwLaunch l{device, stream};
-    if (bhwk_table_build(l, c, (int32_t *)ws)) return BHW_ERR_HIP;
-    he = hipMemcpyAsync(flag_out, c.tab_check, 4, hipMemcpyDeviceToHost, (hipStream_t)stream);
-    if (he == hipSuccess) he = hipStreamSynchronize((hipStream_t)stream);
-    return he == hipSuccess ? BHW_OK : BHW_ERR_HIP;
+    point_table(c, dlog, ws);
+    return checked_build(BhwLaunch{device, stream}, c, ws, flag_out) ? BHW_ERR_HIP : BHW_OK;
 }
 
 int bhw_atan2_device(const bhw_atan2_params *p, int device, void *hip_stream, uint64_t count,
@@ -641,9 +633,8 @@ int bhw_atan2_device(const bhw_atan2_params *p, int device, void *hip_stream, ui
     if (rc) return rc;
     if (!count) return BHW_OK;
     if (!d_x || !d_y || !d_phi) return fail(BHW_ERR_BADARG, "d_x / d_y / d_phi is NULL");
-    if (!device_ok(device)) return fail(BHW_ERR_HIP, "no usable HIP device %d (this library has no CPU path)", device);
     DeviceGuard guard(device);
-    if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
+    if ((rc = guard.status())) return rc;
     BhwAtan2Cfg c;
     bhwp_resolve_atan2(p, c);
     BhwLaunch l{device, hip_stream};
@@ -657,9 +648,8 @@ int bhw_atan2_to_host(const bhw_atan2_params *p, int device, uint64_t count, con
     if (rc) return rc;
     if (!count) return BHW_OK;
     if (!h_x || !h_y || !h_phi) return fail(BHW_ERR_BADARG, "h_x / h_y / h_phi is NULL");
-    if (!device_ok(device)) return fail(BHW_ERR_HIP, "no usable HIP device %d (this library has no CPU path)", device);
     DeviceGuard guard(device);
-    if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
+    if ((rc = guard.status())) return rc;
     int32_t *d = nullptr;
     hipError_t e = hipMalloc((void **)&d, 3 * count * sizeof(int32_t));
     if (e != hipSuccess) return fail_hip(e, "hipMalloc(atan2)");
@@ -684,9 +674,8 @@ int bhw_generate_part_device(const bhw_params *p, int device, void *hip_stream, 
     if (!d_window) return fail(BHW_ERR_BADARG, "d_window is NULL");
     rc = bhwp_check_exec(ex);
     if (rc) return rc;
-    if (!device_ok(device)) return fail(BHW_ERR_HIP, "no usable HIP device %d (this library has no CPU path)", device);
     DeviceGuard guard(device);
-    if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
+    if ((rc = guard.status())) return rc;
     BhwLaunch l{device, hip_stream};
     BhwCordicCfg c;
     bhwp_resolve_cordic(p, c);
@@ -703,20 +692,9 @@ int bhw_generate_part_device(const bhw_params *p, int device, void *hip_stream, 
         return e ? fail_hip(e, "fused part launch") : BHW_OK;
     }
     c.tab_split = c.z_shr == 0 ? 1u : 0u;
-    const uint32_t limit = bhwp_exec_table_format(ex);
     TableScratch scratch;
-    const bool capturing = stream_is_capturing(hip_stream);
-    rc = acquire_scratch(ex, device, hip_stream, bhwp_table_scratch_bytes(p, c, true, limit, capturing), !capturing && verdicts_open(p, c, true, limit), scratch);
-    if (rc) return rc;
-    void *ws = scratch.ws;
-    rc = build_table(p, l, c, true, limit, ws);
-    if (rc) return rc;
-    if (ex && ex->event_after_build) {
-        hipError_t he = hipEventRecord((hipEvent_t)ex->event_after_build, (hipStream_t)hip_stream);
-        if (he != hipSuccess) return fail_hip(he, "hipEventRecord(event_after_build)");
-    }
-    const int e = bhwk_table_combine_tile_range(l, c, w, (const int32_t *)ws, d_window, tile0, tile_count);
-    return e ? fail_hip(e, "tile part launch") : BHW_OK;
+    rc = rebuild_table(p, l, c, true, ex, scratch);
+    return rc ? rc : part_tiles(l, TableView{c, true, (const int32_t *)scratch.ws}, w, tile0, tile_count, d_window);
 }
 
 int bhw_gather_parts_device(const bhw_params *p, uint32_t n_parts, const int *src_devices, const int32_t *const *d_windows,
@@ -725,13 +703,13 @@ int bhw_gather_parts_device(const bhw_params *p, uint32_t n_parts, const int *sr
     int rc = bhwp_part_checks(p, 0, n_parts);
     if (rc) return rc;
     if (!src_devices || !d_windows || !d_dst) return fail(BHW_ERR_BADARG, "src_devices / d_windows / d_dst is NULL");
-    if (!device_ok(dst_device)) return fail(BHW_ERR_HIP, "no usable HIP device %d (this library has no CPU path)", dst_device);
+    DeviceGuard guard(dst_device);
+    if (!guard.usable) return guard.status();
     for (uint32_t g = 0; g < n_parts; ++g) {
         if (!d_windows[g]) return fail(BHW_ERR_BADARG, "d_windows[%u] is NULL", g);
         if (!device_ok(src_devices[g])) return fail(BHW_ERR_HIP, "no usable HIP device %d", src_devices[g]);
     }
-    DeviceGuard guard(dst_device);
-    if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
+    if ((rc = guard.status())) return rc;
     std::vector<bhw_segment> segs(256);
     for (uint32_t g = 0; g < n_parts; ++g) {
         if (d_windows[g] == d_dst) continue;                      // this part was generated in place
@@ -757,7 +735,7 @@ int bhw_release_device(int device)
         taken = std::move(it->second);
         g_scratch.erase(it);
     }
-    DeviceGuard guard(device);
+    DeviceGuard guard(device, false);
     if (guard.err == hipSuccess) {
         (void)hipDeviceSynchronize();
         for (auto &kv : taken.bufs) {
@@ -775,9 +753,8 @@ int bhw_prepare_device(const bhw_params *p, int device, void *hip_stream)
 {
     int rc = bhwp_validate(p, true);
     if (rc) return rc;
-    if (!device_ok(device)) return fail(BHW_ERR_HIP, "no usable HIP device %d (this library has no CPU path)", device);
     DeviceGuard guard(device);
-    if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
+    if ((rc = guard.status())) return rc;
     if (p->sin_type != BHW_SIN_CORDIC) {
         BhwTaylorCfg t;
         return resolve_taylor(p, device, hip_stream, t);        // uploads the ROM on first use
@@ -799,8 +776,8 @@ int bhw_prepare_device(const bhw_params *p, int device, void *hip_stream)
     if (tile) {
         c.tab_split = c.z_shr == 0 ? 1u : 0u;
         for (uint32_t limit : limits) {
-            const uint64_t first = bhwp_table_scratch_bytes(p, c, true, limit, false);   // while formats are unverified: the widest that may be tried
-            if ((limit == BHW_TABLE_BEST || verdicts_open(p, c, true, limit)) && first > need) need = first;
+            const BhwFormatWalk fw = bhwp_format_walk(p, c, true, limit, false);   // while formats are unverified: the widest that may be tried
+            if ((limit == BHW_TABLE_BEST || fw.n_open) && fw.scratch_bytes > need) need = fw.scratch_bytes;
         }
     }
     auto slot = slot_of(device, hip_stream);
@@ -812,9 +789,10 @@ int bhw_prepare_device(const bhw_params *p, int device, void *hip_stream)
     // must not meet an open verdict (it would fall back to the plain table, which the scratch below no longer holds).
     if (tile) {
         BhwLaunch l{device, hip_stream};
+        const bool capturing = stream_is_capturing(hip_stream);
         for (uint32_t limit : limits) {
-            if (limit != BHW_TABLE_BEST && !verdicts_open(p, c, true, limit)) continue;
-            rc = build_table(p, l, c, true, limit, slot->buf);
+            if (limit != BHW_TABLE_BEST && !bhwp_format_walk(p, c, true, limit, false).n_open) continue;
+            rc = build_table(p, l, c, bhwp_format_walk(p, c, true, limit, capturing), slot->buf);
             if (rc) return rc;
         }
     }
@@ -823,7 +801,7 @@ int bhw_prepare_device(const bhw_params *p, int device, void *hip_stream)
     // ... and with the verdicts known the scratch is what table_format BEST needs from now on (16.5 MiB instead of 128 MiB for a
     // 2^26-point window at 32 bits), plus the plain table of partial ranges where that was reserved above
     if (tile) {
-        const uint64_t settled = bhwp_table_scratch_bytes(p, c, true, BHW_TABLE_BEST, false);
+        const uint64_t settled = bhwp_format_walk(p, c, true, BHW_TABLE_BEST, false).scratch_bytes;
         const uint64_t keep = plain <= (64ull << 20) ? (plain > settled ? plain : settled) : settled;
         slot->oversized = false;
         rc = shrink_slot_to(*slot, hip_stream, keep);
@@ -847,34 +825,20 @@ struct bhw_table_s {
     bool tiled;            // whole periods take the tile kernel (split packed layout at z_shr == 0)
     void *buf;
     uint64_t bytes;
+    TableView view() const { return TableView{c, tiled, (const int32_t *)buf}; }
 };
 
 namespace {
 
-void point_table(BhwCordicCfg &c, uint32_t dlog, void *buf)
-{
-    const BhwTableLayout lay = bhwp_table_layout(bhwp_table_entries(c), dlog);
-    c.tab_dlog = dlog;
-    c.tab_coarse = dlog ? (const void *)((const char *)buf + lay.coarse_off) : nullptr;
-    c.tab_esc = lay.esc_off ? (const void *)((const char *)buf + lay.esc_off) : nullptr;
-    c.esc_wg_log = lay.esc_wg_log;
-    c.tab_check = nullptr;
-}
-
 // Settles the verdict of packed format `dlog` for `p` by a trial build with the overflow check into a temporary buffer
 int trial_build(const bhw_params *p, const BhwLaunch &l, BhwCordicCfg c, uint32_t dlog)
 {
-    const BhwTableLayout lay = bhwp_table_layout(bhwp_table_entries(c), dlog);
     void *tmp = nullptr;
-    hipError_t he = hipMalloc(&tmp, lay.bytes);
+    const hipError_t he = hipMalloc(&tmp, bhwp_table_layout(bhwp_table_entries(c), dlog).bytes);
     if (he != hipSuccess) return fail_hip(he, "hipMalloc(trial table)");
     point_table(c, dlog, tmp);
-    c.tab_check = (uint32_t *)((char *)tmp + lay.check_off);
     uint32_t flag = 1;
-    he = hipMemsetAsync(c.tab_check, 0, 8, (hipStream_t)l.stream);
-    int e = he == hipSuccess ? bhwk_table_build(l, c, (int32_t *)tmp) : (int)he;
-    if (!e) e = hipMemcpyAsync(&flag, c.tab_check, sizeof flag, hipMemcpyDeviceToHost, (hipStream_t)l.stream);
-    if (!e) e = hipStreamSynchronize((hipStream_t)l.stream);
+    const int e = checked_build(l, c, tmp, &flag);
     (void)hipFree(tmp);
     if (e) return fail_hip(e, "trial build of a packed table format");
     bhwp_fmt_set_verdict(p, dlog, flag ? kFmtBad : kFmtOk);
@@ -889,40 +853,22 @@ int table_call_checks(bhw_table t, const bhw_params *p)
     return rc ? rc : bhwp_table_key_check(&t->key, p);
 }
 
+// head | whole periods | tail as generate_impl splits a table-strategy call, every piece over the one resident table
 int from_table(bhw_table t, const bhw_params *p, void *stream, uint64_t n0, uint64_t count, int32_t *d_out,
-               const int32_t *apply_x = nullptr, uint32_t apply_shift = 0, bool generic_ragged = false)
+               const int32_t *apply_x = nullptr, uint32_t apply_shift = 0, RaggedKernel ragged = bhwk_range_combine)
 {
     int rc = table_call_checks(t, p);
     if (rc) return rc;
     if (count && !d_out) return fail(BHW_ERR_BADARG, "d_out is NULL");
     if (!count) return BHW_OK;
     if (count > (1ull << 34)) return fail(BHW_ERR_BADARG, "count %llu > 2^34 per call", (unsigned long long)count);
-    DeviceGuard guard(t->device);
-    if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
-    const BhwLaunch l{t->device, stream};
-    const BhwCordicCfg &c = t->c;
-    const int32_t *tab = (const int32_t *)t->buf;
+    DeviceGuard guard(t->device, false);
+    if ((rc = guard.status())) return rc;
     BhwWinCfg w;
     bhwp_resolve_window(p, w);
     w.apply_x = apply_x;
     w.apply_shift = apply_shift;
-    // head | whole periods | tail as generate_impl splits a table-strategy call, every piece over the one resident table
-    const BhwTableCall tc = bhwp_table_call(p, c, w, n0, count, apply_x != nullptr);
-    if (tc.images) {
-        const int e = bhwk_table_combine_tile_range(l, c, w, tab, d_out, 0, 0, tc.img_mask, tc.n0mod);
-        return e ? fail_hip(e, "tile launch (image subset)") : BHW_OK;
-    }
-    auto ragged = [&](uint64_t off, uint64_t len) -> int {
-        if (apply_x) w.apply_x = apply_x + off;
-        return generic_ragged ? bhwk_table_combine(l, c, w, tab, n0 + off, len, d_out + off)
-                              : bhwk_range_combine(l, c, w, tab, n0 + off, len, d_out + off);
-    };
-    auto period = [&](uint64_t off) -> int {
-        if (apply_x) w.apply_x = apply_x + off;
-        if (bhwk_runlength_applicable(c, w, d_out + off)) return bhwk_runlength_window(l, c, w, tab, d_out + off);
-        return t->tiled ? bhwk_table_combine_tile(l, c, w, tab, d_out + off) : bhwk_table_combine_fold(l, c, w, tab, d_out + off);
-    };
-    return run_split(l, n0, count, 1ull << p->phi_width, apply_x != nullptr, d_out, ragged, period);
+    return table_pieces(BhwLaunch{t->device, stream}, t->view(), p, w, n0, count, d_out, ragged);
 }
 
 } // namespace
@@ -935,24 +881,25 @@ int bhw_table_create(const bhw_params *p, int device, void *hip_stream, uint32_t
     *out = nullptr;
     int rc = bhwp_table_create_checks(p, table_format);
     if (rc) return rc;
-    if (!device_ok(device)) return fail(BHW_ERR_HIP, "no usable HIP device %d (this library has no CPU path)", device);
     DeviceGuard guard(device);
-    if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
+    if ((rc = guard.status())) return rc;
     const BhwLaunch l{device, hip_stream};
     BhwCordicCfg c;
     bool tiled;
     bhwp_resident_layout(p, c, &tiled);
-    // the narrowest format under `table_format` that is exact for the configuration: open verdicts are settled by trial builds
-    uint32_t cand[kMaxFormats];
-    const int n_cand = bhwp_table_format_candidates(c, tiled, table_format, cand);
-    uint32_t keep = 0;
-    for (int i = 0; i < n_cand; ++i) {
-        if (!cand[i]) break;                                            // plain: always exact, the last candidate
-        if (bhwp_fmt_verdict(p, cand[i]) == kFmtUnknown) {
-            rc = trial_build(p, l, c, cand[i]);
+    // the narrowest format under `table_format` that is exact for the configuration: the walk's open verdicts are settled by trial
+    // builds, narrowest first (each read again first: another thread may have settled it since the walk), else the walk's `kept`
+    const BhwFormatWalk fw = bhwp_format_walk(p, c, tiled, table_format, false);
+    uint32_t keep = fw.kept;
+    for (int i = 0; i < fw.n_open; ++i) {
+        if (bhwp_fmt_verdict(p, fw.open[i]) == kFmtUnknown) {
+            rc = trial_build(p, l, c, fw.open[i]);
             if (rc) return rc;
         }
-        if (bhwp_fmt_verdict(p, cand[i]) == kFmtOk) { keep = cand[i]; break; }
+        if (bhwp_fmt_verdict(p, fw.open[i]) == kFmtOk) {
+            keep = fw.open[i];
+            break;
+        }
     }
     const uint64_t bytes = bhwp_table_layout(bhwp_table_entries(c), keep).bytes;
     void *buf = nullptr;
@@ -978,7 +925,7 @@ int bhw_table_destroy(bhw_table t)
 {
     if (!t) return BHW_OK;
     {
-        DeviceGuard guard(t->device);
+        DeviceGuard guard(t->device, false);
         if (guard.err == hipSuccess) {
             (void)hipDeviceSynchronize();                               // launches still reading it finish first
             (void)hipFree(t->buf);
@@ -1004,11 +951,8 @@ int bhw_generate_from_table(bhw_table t, const bhw_params *p, void *hip_stream, 
 int bhw_apply_from_table(bhw_table t, const bhw_params *p, void *hip_stream, uint64_t n0, uint64_t count,
                          const int32_t *d_x, int32_t *d_y, uint32_t shift)
 {
-    if (count && (!d_x || !d_y)) return fail(BHW_ERR_BADARG, "d_x / d_y is NULL");
-    if (shift > 62) return fail(BHW_ERR_BADARG, "shift %u > 62", shift);
-    const uintptr_t xa = (uintptr_t)d_x, ya = (uintptr_t)d_y, nb = (uintptr_t)count * 4u;
-    if (count && xa < ya + nb && ya < xa + nb) return fail(BHW_ERR_BADARG, "d_y must not overlap d_x (tile seams recompute a few samples)");
-    return from_table(t, p, hip_stream, n0, count, d_y, d_x, shift);
+    const int rc = bhwp_apply_checks(count, d_x, d_y, shift);
+    return rc ? rc : from_table(t, p, hip_stream, n0, count, d_y, d_x, shift);
 }
 
 int bhw_generate_part_from_table(bhw_table t, const bhw_params *p, void *hip_stream, uint32_t part, uint32_t n_parts, int32_t *d_window)
@@ -1025,11 +969,9 @@ int bhw_generate_part_from_table(bhw_table t, const bhw_params *p, void *hip_str
     BhwFoldRun runs[32];
     uint32_t tile0 = 0, tile_count = 0;
     if (bhwk_part_runs(t->c, w, part, n_parts, runs, &tile0, &tile_count) == 0 || tile_count == 0) return BHW_OK;
-    DeviceGuard guard(t->device);
-    if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
-    const BhwLaunch l{t->device, hip_stream};
-    const int e = bhwk_table_combine_tile_range(l, t->c, w, (const int32_t *)t->buf, d_window, tile0, tile_count);
-    return e ? fail_hip(e, "tile part launch") : BHW_OK;
+    DeviceGuard guard(t->device, false);
+    if ((rc = guard.status())) return rc;
+    return part_tiles(BhwLaunch{t->device, hip_stream}, t->view(), w, tile0, tile_count, d_window);
 }
 
 int bhw_apply_frames_from_table(bhw_table t, const bhw_params *p, void *hip_stream, const bhw_frames *f, const int32_t *d_x, int32_t *d_y)
@@ -1038,8 +980,8 @@ int bhw_apply_frames_from_table(bhw_table t, const bhw_params *p, void *hip_stre
     if (!rc) rc = bhwp_frames_checks(p, f, d_x, d_y);
     if (rc || !f->frames) return rc;
     const BhwFramesPlan pl = bhwp_frames_plan(p, f, true);
-    DeviceGuard guard(t->device);
-    if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
+    DeviceGuard guard(t->device, false);
+    if ((rc = guard.status())) return rc;
     BhwWinCfg w;
     bhwp_resolve_window(p, w);
     const int e = bhwk_frames(BhwLaunch{t->device, hip_stream}, t->c, w, pl, f, d_x, d_y, (const int32_t *)t->buf);
@@ -1057,7 +999,7 @@ int bhw_apply_frames_describe(bhw_table t, const bhw_params *p, const bhw_frames
 // kernel k_table_combine (format read at run time) instead of k_range_combine -- the A/B of tools/bench_resident_table.py.
 int bhw_dbg_generate_from_table_generic(bhw_table t, const bhw_params *p, void *hip_stream, uint64_t n0, uint64_t count, int32_t *d_out)
 {
-    return from_table(t, p, hip_stream, n0, count, d_out, nullptr, 0, true);
+    return from_table(t, p, hip_stream, n0, count, d_out, nullptr, 0, bhwk_table_combine);
 }
 
 // Bytes the library-owned scratch of (device, hip_stream) holds right now (0: none yet) -- what bench.py reports beside the size of

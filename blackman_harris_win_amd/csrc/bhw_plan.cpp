@@ -215,6 +215,16 @@ bool bhwp_has_whole_period(const bhw_params *p, uint64_t n0, uint64_t count)
     return count >= (N - n0 % N) % N + N;
 }
 
+int bhwp_apply_checks(uint64_t count, const void *d_x, const void *d_y, uint32_t shift)
+{
+    if (count && (!d_x || !d_y)) return bhwp_fail(BHW_ERR_BADARG, "d_x / d_y is NULL");
+    if (shift > 62) return bhwp_fail(BHW_ERR_BADARG, "shift %u > 62", shift);
+    const uintptr_t xa = (uintptr_t)d_x, ya = (uintptr_t)d_y, bytes = (uintptr_t)count * 4u;
+    if (count && xa < ya + bytes && ya < xa + bytes)
+        return bhwp_fail(BHW_ERR_BADARG, "d_y must not overlap d_x (tile seams recompute a few samples)");
+    return BHW_OK;
+}
+
 // AUTO: the fused kernel for short whole periods; else build the shared table when it replaces clearly more CORDIC chains
 // than it costs; else one chain per harmonic per coefficient.
 uint32_t bhwp_pick_algo(const bhw_params *p, const BhwCordicCfg &c, const BhwWinCfg &w, uint64_t n0, uint64_t count, uint32_t requested)
@@ -352,20 +362,34 @@ void bhwp_fmt_set_verdict(const bhw_params *p, uint32_t dlog, int v)
     else g_fmt_verdict.erase(fmt_key(p, dlog));                  // anything else: forget it (unknown again)
 }
 
-uint64_t bhwp_table_scratch_bytes(const bhw_params *p, const BhwCordicCfg &c, bool tiled, uint32_t limit, bool capturing)
+BhwFormatWalk bhwp_format_walk(const bhw_params *p, const BhwCordicCfg &c, bool tiled, uint32_t limit, bool capturing)
 {
     uint32_t cand[kMaxFormats];
     const int n = bhwp_table_format_candidates(c, tiled, limit, cand);
     const uint64_t E = bhwp_table_entries(c);
-    uint64_t need = 0;
+    BhwFormatWalk fw{};
     for (int i = 0; i < n; ++i) {
         const int v = cand[i] ? bhwp_fmt_verdict(p, cand[i]) : (int)kFmtOk;
         if (v == kFmtBad || (v == kFmtUnknown && capturing)) continue;
         const uint64_t b = bhwp_table_layout(E, cand[i]).bytes;
-        if (b > need) need = b;
-        if (v == kFmtOk) break;
+        if (b > fw.scratch_bytes) fw.scratch_bytes = b;
+        if (v == kFmtOk) {
+            fw.kept = cand[i];
+            break;
+        }
+        fw.open[fw.n_open++] = cand[i];
     }
-    return need;
+    return fw;
+}
+
+uint64_t bhwp_table_scratch_bytes(const bhw_params *p, const BhwCordicCfg &c, bool tiled, uint32_t limit, bool capturing)
+{
+    return bhwp_format_walk(p, c, tiled, limit, capturing).scratch_bytes;
+}
+
+const char *bhwp_format_name(uint32_t tab_dlog)
+{
+    return tab_dlog == 0 ? "plain" : tab_dlog == kPackLog ? "delta16" : tab_dlog >= kEscFlag ? "nibble+esc" : tab_dlog >= kNibbleFlag ? "nibble" : "residual";
 }
 
 // ---- combine pass: tile plan ------------------------------------------------------------------------------------------------------
@@ -685,7 +709,6 @@ int bhwp_describe_from_table(const bhw_params *p, const BhwCordicCfg &ct, bool t
     BhwWinCfg w;
     bhwp_resolve_window(p, w);
     const uint64_t N = 1ull << p->phi_width, E = bhwp_table_entries(c);
-    const char *fmt = c.tab_dlog == 0 ? "plain" : c.tab_dlog == kPackLog ? "delta16" : c.tab_dlog >= kEscFlag ? "nibble+esc" : c.tab_dlog >= kNibbleFlag ? "nibble" : "residual";
     char ragged[64], period[128], build[64], combine[96];
     int rf, rn, rm;
     if (bhwp_range_form(c, w, &rf, &rn, &rm)) snprintf(ragged, sizeof ragged, "k_range_combine<%d,%d,%d>", rf, rn, rm);
@@ -706,7 +729,7 @@ int bhwp_describe_from_table(const bhw_params *p, const BhwCordicCfg &ct, bool t
         const std::string ends = head || tail ? std::string(" + ") + ragged + " on the ragged ends" : std::string();
         snprintf(calls, sizeof calls, "%s%s%s", period, periods > 1 ? " + k_replicate" : "", ends.c_str());
     }
-    snprintf(buf, len, "resident table[%s, %s, %llu bytes]: %s", fmt, c.tab_split ? "split" : "natural",
+    snprintf(buf, len, "resident table[%s, %s, %llu bytes]: %s", bhwp_format_name(c.tab_dlog), c.tab_split ? "split" : "natural",
              (unsigned long long)bhwp_table_layout(E, c.tab_dlog).bytes, calls);
     return BHW_OK;
 }
@@ -931,7 +954,7 @@ uint64_t bhw_workspace_bytes_ex(const bhw_params *p, uint64_t n0, uint64_t count
     bhwp_resolve_window(p, w);
     if (bhwp_pick_algo(p, c, w, n0, count, ex ? ex->algo : (uint32_t)BHW_ALGO_AUTO) != BHW_ALGO_TABLE) return 0;
     const BhwTableCall t = bhwp_table_call(p, c, w, n0, count, false);
-    return bhwp_table_scratch_bytes(p, c, t.tiled, bhwp_exec_table_format(ex), false);
+    return bhwp_format_walk(p, c, t.tiled, bhwp_exec_table_format(ex), false).scratch_bytes;
 }
 
 int bhw_describe_plan(const bhw_params *p, uint64_t n0, uint64_t count, const bhw_exec *ex, char *buf, uint64_t len)
@@ -964,24 +987,15 @@ int bhw_describe_plan(const bhw_params *p, uint64_t n0, uint64_t count, const bh
     }
     const BhwTableCall t = bhwp_table_call(p, c, w, n0, count, false);
     c.tab_split = (t.tiled && c.z_shr == 0) ? 1u : 0u;
-    uint32_t cand[kMaxFormats];
-    const int n_cand = bhwp_table_format_candidates(c, t.tiled, bhwp_exec_table_format(ex), cand);
-    const char *state = "";
-    c.tab_dlog = 0;
-    for (int i = 0; i < n_cand; ++i) {
-        const int v = cand[i] ? bhwp_fmt_verdict(p, cand[i]) : (int)kFmtOk;
-        if (v == kFmtBad) continue;
-        c.tab_dlog = cand[i];
-        if (v == kFmtUnknown) state = ", unverified";
-        break;
-    }
+    // the format the call builds first: the narrowest one still open (tried with the check word), else the one known exact
+    const BhwFormatWalk fw = bhwp_format_walk(p, c, t.tiled, bhwp_exec_table_format(ex), false);
+    c.tab_dlog = fw.n_open ? fw.open[0] : fw.kept;
     char build[64], combine[96];
     bhwk_describe_table(c, w, t.tiled, t.images, build, combine, sizeof build);
     if (period && c.tab_dlog == 0 && bhwk_runlength_applicable(c, w, nullptr))     // generate_impl's period(): dropped phase bits
         snprintf(combine, sizeof combine, "k_runlength_window<%u,%d,%s> (16-byte aligned output; else k_table_combine_fold_t)", p->n_terms,
                  mode_of(c, w), c.dat_width <= 16 ? "true" : "false");
-    const char *fmt = c.tab_dlog == 0 ? "plain" : c.tab_dlog == 6 ? "delta16" : c.tab_dlog >= kEscFlag ? "nibble+esc" : c.tab_dlog >= 16 ? "nibble" : "residual";
-    snprintf(buf, len, "table[%s%s]: %s + %s%s", fmt, state, build, (period || t.images) ? combine : "k_table_combine",
+    snprintf(buf, len, "table[%s%s]: %s + %s%s", bhwp_format_name(c.tab_dlog), fw.n_open ? ", unverified" : "", build, (period || t.images) ? combine : "k_table_combine",
              t.images ? " (image subset)" : period && count != (1ull << p->phi_width) ? " (+ k_table_combine / k_replicate on the rest)" : "");
     return BHW_OK;
 }
@@ -1037,39 +1051,39 @@ int bhw_dbg_table_key_matches(const bhw_params *p_table, const bhw_params *p_cal
     return rc ? rc : bhwp_table_key_check(p_table, p_call);
 }
 
-// bhw_table_describe from parameters alone (no device, no table): the table of p_table as bhw_table_create would hold it if
-// every packed format under `table_format` were exact (the first candidate), and the kernels a call of (p_call, n0, count) launches.
+// The describe hooks below: their checks, and the table of p_table as bhw_table_create would hold it if every packed format under
+// `table_format` were exact (the first candidate).
+static int dbg_resident_table(const bhw_params *p_table, uint32_t table_format, const bhw_params *p_call, BhwCordicCfg &c, bool *tiled)
+{
+    int rc = bhw_dbg_table_key_matches(p_table, p_call);
+    if (!rc && table_format > BHW_TABLE_NIBBLE_ESC) rc = bhwp_fail(BHW_ERR_BADARG, "table_format %u", table_format);
+    if (rc) return rc;
+    bhwp_resident_layout(p_table, c, tiled);
+    uint32_t cand[kMaxFormats];
+    bhwp_table_format_candidates(c, *tiled, table_format, cand);
+    c.tab_dlog = cand[0];
+    return BHW_OK;
+}
+
+// bhw_table_describe from parameters alone (no device, no table): the kernels a call of (p_call, n0, count) launches over that table.
 int bhw_dbg_describe_from_table(const bhw_params *p_table, uint32_t table_format, const bhw_params *p_call, uint64_t n0, uint64_t count,
                                 char *buf, uint64_t len)
 {
-    int rc = bhw_dbg_table_key_matches(p_table, p_call);
-    if (!rc && table_format > BHW_TABLE_NIBBLE_ESC) rc = bhwp_fail(BHW_ERR_BADARG, "table_format %u", table_format);
-    if (rc) return rc;
     BhwCordicCfg c;
     bool tiled;
-    bhwp_resident_layout(p_table, c, &tiled);
-    uint32_t cand[kMaxFormats];
-    bhwp_table_format_candidates(c, tiled, table_format, cand);
-    c.tab_dlog = cand[0];
-    return bhwp_describe_from_table(p_call, c, tiled, n0, count, buf, len);
+    const int rc = dbg_resident_table(p_table, table_format, p_call, c, &tiled);
+    return rc ? rc : bhwp_describe_from_table(p_call, c, tiled, n0, count, buf, len);
 }
 
-// bhw_apply_frames_describe of a from-table call from parameters alone (no device, no table): the table of p_table as
-// bhw_table_create would hold it if every packed format under `table_format` were exact, and the call's checks before that
+// bhw_apply_frames_describe of a from-table call from parameters alone (no device, no table), over that table.
 int bhw_dbg_describe_frames_from_table(const bhw_params *p_table, uint32_t table_format, const bhw_params *p_call, const bhw_frames *f,
                                        char *buf, uint64_t len)
 {
-    int rc = bhw_dbg_table_key_matches(p_table, p_call);
-    if (!rc && table_format > BHW_TABLE_NIBBLE_ESC) rc = bhwp_fail(BHW_ERR_BADARG, "table_format %u", table_format);
-    if (!rc) rc = bhwp_frames_checks(p_call, f, nullptr, nullptr, false);
-    if (rc) return rc;
     BhwCordicCfg c;
     bool tiled;
-    bhwp_resident_layout(p_table, c, &tiled);
-    uint32_t cand[kMaxFormats];
-    bhwp_table_format_candidates(c, tiled, table_format, cand);
-    c.tab_dlog = cand[0];
-    return bhwp_describe_frames(p_call, &c, f, buf, len);
+    int rc = dbg_resident_table(p_table, table_format, p_call, c, &tiled);
+    if (!rc) rc = bhwp_frames_checks(p_call, f, nullptr, nullptr, false);
+    return rc ? rc : bhwp_describe_frames(p_call, &c, f, buf, len);
 }
 
 // tab_dlog the residual format would use for `p` (0: not applicable) and whether delta16 applies

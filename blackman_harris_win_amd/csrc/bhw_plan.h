@@ -92,6 +92,8 @@ void bhwp_resolve_prerot(const bhw_params *p, BhwPrerotCfg &c);
 void bhwp_resolve_atan2(const bhw_atan2_params *p, BhwAtan2Cfg &c);
 inline uint64_t bhwp_table_entries(const BhwCordicCfg &c) { return 1ull << (c.phi_width - 2 - c.z_shr); }
 bool bhwp_has_whole_period(const bhw_params *p, uint64_t n0, uint64_t count);
+// Argument checks of bhw_apply_device / bhw_apply_from_table, before any other: BHW_OK or BADARG.
+int  bhwp_apply_checks(uint64_t count, const void *d_x, const void *d_y, uint32_t shift);
 uint32_t bhwp_pick_algo(const bhw_params *p, const BhwCordicCfg &c, const BhwWinCfg &w, uint64_t n0, uint64_t count, uint32_t requested);
 int  bhwp_check_exec(const bhw_exec *ex);
 uint32_t bhwp_exec_table_format(const bhw_exec *ex);
@@ -103,9 +105,19 @@ int bhwp_table_format_candidates(const BhwCordicCfg &c, bool tiled, uint32_t lim
 enum { kFmtUnknown = 0, kFmtOk = 1, kFmtBad = 2 };
 int  bhwp_fmt_verdict(const bhw_params *p, uint32_t dlog);
 void bhwp_fmt_set_verdict(const bhw_params *p, uint32_t dlog, int v);
-// scratch bytes a table-strategy call needs right now: the first candidate that is known to be exact, or -- while a narrower one is
-// still unverified and may fall back -- the largest of those that may be tried (`capturing`: unverified formats are skipped)
+// The candidates of a call read against the verdict cache, once: every format decision of the rebuilt and the resident tables
+// (scratch size, trial order, the format bhw_describe_plan names, the format a resident table keeps) is taken from it.
+struct BhwFormatWalk {
+    uint32_t kept;                  // the narrowest candidate known to be exact (0: plain, always exact)
+    uint32_t open[kMaxFormats];     // packed candidates narrower than `kept` with no verdict yet, narrowest first: the trial order
+    int n_open;                     // ... (none while `capturing`: a capture cannot read a check word back)
+    uint64_t scratch_bytes;         // what a table-strategy call needs right now: the largest of `kept` and the open formats
+};
+BhwFormatWalk bhwp_format_walk(const bhw_params *p, const BhwCordicCfg &c, bool tiled, uint32_t limit, bool capturing);
+// the walk's scratch_bytes alone
 uint64_t bhwp_table_scratch_bytes(const bhw_params *p, const BhwCordicCfg &c, bool tiled, uint32_t limit, bool capturing);
+// the name of a table format (tab_dlog) in the describe strings
+const char *bhwp_format_name(uint32_t tab_dlog);
 
 // What a table-strategy call over [n0, n0 + count) does with its whole periods.
 struct BhwTableCall {

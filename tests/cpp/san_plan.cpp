@@ -102,9 +102,27 @@ static void sweep_config(bhw_params &p, int parts)
             for (int state = 0; state < 3; ++state) {             // every packed format unknown / exact / overflowing
                 for (int i = 0; i + 1 < n; ++i) bhw_dbg_table_format_verdict(&p, cand[i], state == 0 ? 3 : state);   // 3: any value but 1 / 2 reads as "unknown"
                 for (int cap = 0; cap < 2; ++cap) {
-                    const uint64_t need = bhwp_table_scratch_bytes(&p, ct, tiled != 0, limit, cap != 0);
+                    const BhwFormatWalk fw = bhwp_format_walk(&p, ct, tiled != 0, limit, cap != 0);
+                    const uint64_t need = fw.scratch_bytes;
                     REQUIRE(need >= bhwp_table_layout(E, state == 1 ? cand[0] : 0).bytes || (state == 0 && !cap), "scratch %" PRIu64 " in state %d", need, state);
                     REQUIRE(need <= E * 8 || E < 64, "scratch beyond the bound");
+                    // the walk: `kept` is a candidate known exact (or plain), every open format is an unknown candidate narrower than it
+                    // (narrowest first), none while capturing, and the scratch is the widest of them
+                    int k = 0;
+                    while (k < n && cand[k] != fw.kept) ++k;
+                    REQUIRE(k < n && (fw.kept == 0 || bhwp_fmt_verdict(&p, fw.kept) == kFmtOk), "kept %u in state %d", fw.kept, state);
+                    REQUIRE(fw.n_open >= 0 && fw.n_open <= k && (!cap || fw.n_open == 0), "%d open formats (capturing %d)", fw.n_open, cap);
+                    uint64_t widest = bhwp_table_layout(E, fw.kept).bytes;
+                    for (int i = 0, j = 0; i < fw.n_open; ++i, ++j) {
+                        while (j < k && cand[j] != fw.open[i]) ++j;
+                        REQUIRE(j < k && fw.open[i] != 0 && bhwp_fmt_verdict(&p, fw.open[i]) == kFmtUnknown, "open format %u", fw.open[i]);
+                        const uint64_t b = bhwp_table_layout(E, fw.open[i]).bytes;
+                        if (b > widest) widest = b;
+                    }
+                    REQUIRE(need == widest, "scratch %" PRIu64 " != %" PRIu64, need, widest);
+                    // all unknown: every packed candidate open (outside a capture), plain kept; all exact: the first kept; all overflowing: plain
+                    REQUIRE(state == 1 ? fw.kept == cand[0] && fw.n_open == 0 : fw.kept == 0 && fw.n_open == (state == 0 && !cap ? n - 1 : 0),
+                            "walk in state %d: kept %u, %d open", state, fw.kept, fw.n_open);
                 }
             }
         }
