@@ -23,6 +23,7 @@ ABI_SYMBOLS = (
     "bhw_table_create", "bhw_table_destroy", "bhw_table_bytes", "bhw_table_describe", "bhw_generate_from_table",
     "bhw_apply_from_table", "bhw_generate_part_from_table",
     "bhw_apply_frames_device", "bhw_apply_frames_from_table", "bhw_apply_frames_describe",
+    "bhw_overlap_add_device", "bhw_overlap_add_from_table", "bhw_overlap_add_describe",
 )
 
 
@@ -70,6 +71,21 @@ def make_frames(frames, hop, *, channels=1, shift=0, y_stride=0):
     f.struct_size = ctypes.sizeof(BhwFrames)
     f.channels, f.frames, f.hop, f.y_stride, f.shift = int(channels), int(frames), int(hop), int(y_stride), int(shift)
     return f
+
+
+class BhwOla(ctypes.Structure):
+    """struct bhw_ola of include/bhw.h (the weighted overlap-add)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("channels", ctypes.c_uint32), ("frames", ctypes.c_uint64),
+                ("hop", ctypes.c_uint64), ("y_stride", ctypes.c_uint64), ("t0", ctypes.c_uint64), ("count", ctypes.c_uint64),
+                ("shift", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+def make_ola(frames, hop, count, *, t0=0, channels=1, shift=0, y_stride=0):
+    o = BhwOla()
+    o.struct_size = ctypes.sizeof(BhwOla)
+    o.channels, o.frames, o.hop, o.y_stride = int(channels), int(frames), int(hop), int(y_stride)
+    o.t0, o.count, o.shift = int(t0), int(count), int(shift)
+    return o
 
 
 _lib = None
@@ -143,6 +159,12 @@ def lib():
     L.bhw_apply_frames_describe.argtypes = [T, P, F, ctypes.c_char_p, u64]
     L.bhw_dbg_apply_frames_route.argtypes = [P, ci, vp, F, i32p, i32p, ci]
     L.bhw_dbg_describe_frames_from_table.argtypes = [P, u32, P, F, ctypes.c_char_p, u64]
+    O = ctypes.POINTER(BhwOla)
+    L.bhw_overlap_add_device.argtypes = [P, ci, vp, O, i32p, i32p]
+    L.bhw_overlap_add_from_table.argtypes = [T, P, vp, O, i32p, i32p]
+    L.bhw_overlap_add_describe.argtypes = [T, P, O, ctypes.c_char_p, u64]
+    L.bhw_dbg_overlap_add_shape.argtypes = [T, P, ci, vp, O, i32p, i32p, u32, u32]
+    L.bhw_dbg_describe_ola_from_table.argtypes = [P, u32, P, O, ctypes.c_char_p, u64]
     PA = ctypes.POINTER(BhwAtan2Params)
     L.bhw_atan2_device.argtypes = [PA, ci, vp, u64, i32p, i32p, i32p]
     L.bhw_atan2_to_host.argtypes = [PA, ci, u64, i32p, i32p, i32p]
@@ -183,6 +205,17 @@ def describe_frames(params, frames, hop, *, channels=1, y_stride=0, table=None):
     buf = ctypes.create_string_buffer(384)
     f = make_frames(frames, hop, channels=channels, y_stride=y_stride)
     check(lib().bhw_apply_frames_describe(table, ctypes.byref(params), ctypes.byref(f), buf, 384))
+    return buf.value.decode()
+
+
+def describe_ola(params, frames, hop, count=None, *, t0=0, channels=1, y_stride=0, table=None):
+    """One line: the route, Q, the lane layout, the grid and the kernel an overlap-add would launch (bhw_overlap_add_describe;
+    `table` is a resident table handle or None for the library call; count=None: the whole extent).  Host arithmetic only."""
+    if count is None:
+        count = max(0, (int(frames) - 1) * int(hop) + (1 << params.phi_width) - int(t0)) if frames else 0
+    buf = ctypes.create_string_buffer(384)
+    o = make_ola(frames, hop, count, t0=t0, channels=channels, y_stride=y_stride)
+    check(lib().bhw_overlap_add_describe(table, ctypes.byref(params), ctypes.byref(o), buf, 384))
     return buf.value.decode()
 
 

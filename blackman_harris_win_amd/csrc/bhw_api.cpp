@@ -430,6 +430,24 @@ int frames_impl(const bhw_params *p, int device, void *stream, const bhw_frames 
     return e ? fail_hip(e, "frames launch") : BHW_OK;
 }
 
+// bhw_overlap_add_device: the overlap-add kernel with the direct CORDIC source (no table, no scratch).  force_q / force_rx > 0: the
+// plan shape of a test or A/B run (bhw_dbg_overlap_add_shape).
+int ola_impl(const bhw_params *p, int device, void *stream, const bhw_ola *o, const int32_t *d_y, int32_t *d_x, uint32_t force_q,
+             uint32_t force_rx)
+{
+    int rc = bhwp_ola_checks(p, o, d_y, d_x);
+    if (rc || !o->count) return rc;
+    const BhwOlaPlan pl = bhwp_ola_plan(p, o, false, force_q, force_rx);
+    DeviceGuard guard(device);
+    if ((rc = guard.status())) return rc;
+    BhwCordicCfg c;
+    bhwp_resolve_cordic(p, c);
+    BhwWinCfg w;
+    bhwp_resolve_window(p, w);
+    const int e = bhwk_ola(BhwLaunch{device, stream}, c, w, pl, o, d_y, d_x, nullptr);
+    return e ? fail_hip(e, "overlap-add launch") : BHW_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -463,6 +481,11 @@ int bhw_dbg_apply_frames_route(const bhw_params *p, int device, void *hip_stream
                                int route)
 {
     return frames_impl(p, device, hip_stream, f, d_x, d_y, route);
+}
+
+int bhw_overlap_add_device(const bhw_params *p, int device, void *hip_stream, const bhw_ola *o, const int32_t *d_y, int32_t *d_x)
+{
+    return ola_impl(p, device, hip_stream, o, d_y, d_x, 0, 0);
 }
 
 int bhw_generate_batched_device(const bhw_params *p, int device, void *hip_stream, uint32_t frames, int32_t *d_out)
@@ -993,6 +1016,38 @@ int bhw_apply_frames_describe(bhw_table t, const bhw_params *p, const bhw_frames
     int rc = t ? table_call_checks(t, p) : BHW_OK;
     if (!rc) rc = bhwp_frames_checks(p, f, nullptr, nullptr, false);
     return rc ? rc : bhwp_describe_frames(p, t ? &t->c : nullptr, f, buf, len);
+}
+
+int bhw_overlap_add_describe(bhw_table t, const bhw_params *p, const bhw_ola *o, char *buf, uint64_t len)
+{
+    int rc = t ? table_call_checks(t, p) : BHW_OK;
+    if (!rc) rc = bhwp_ola_checks(p, o, nullptr, nullptr, false);
+    return rc ? rc : bhwp_describe_ola(p, t ? &t->c : nullptr, o, buf, len);
+}
+
+// Development hook (not part of the ABI in include/bhw.h): the overlap-add with a forced plan shape -- Q (1..16) and the lanes along
+// the residue rx (a power of two <= 256; 0 = the planner's) -- from table t, or with the direct source when t is NULL (on `device`).
+// The tests compare the shapes' outputs; tools/bench_overlap_add.py times them.
+int bhw_dbg_overlap_add_shape(bhw_table t, const bhw_params *p, int device, void *hip_stream, const bhw_ola *o, const int32_t *d_y,
+                              int32_t *d_x, uint32_t force_q, uint32_t force_rx)
+{
+    if (!t) return ola_impl(p, device, hip_stream, o, d_y, d_x, force_q, force_rx);
+    int rc = table_call_checks(t, p);
+    if (!rc) rc = bhwp_ola_checks(p, o, d_y, d_x);
+    if (rc || !o->count) return rc;
+    const BhwOlaPlan pl = bhwp_ola_plan(p, o, true, force_q, force_rx);
+    DeviceGuard guard(t->device, false);
+    if ((rc = guard.status())) return rc;
+    BhwWinCfg w;
+    bhwp_resolve_window(p, w);
+    const int e = bhwk_ola(BhwLaunch{t->device, hip_stream}, t->c, w, pl, o, d_y, d_x, (const int32_t *)t->buf);
+    return e ? fail_hip(e, "overlap-add launch (resident table)") : BHW_OK;
+}
+
+int bhw_overlap_add_from_table(bhw_table t, const bhw_params *p, void *hip_stream, const bhw_ola *o, const int32_t *d_y, int32_t *d_x)
+{
+    if (!t) return fail(BHW_ERR_BADARG, "table is NULL");
+    return bhw_dbg_overlap_add_shape(t, p, t->device, hip_stream, o, d_y, d_x, 0, 0);
 }
 
 // Development hook (not part of the ABI in include/bhw.h): bhw_generate_from_table with every ragged piece on the general gather

@@ -740,9 +740,33 @@ __device__ __forceinline__ int32_t direct_coeff(const BhwCordicCfg &cfg, const B
     return combine_final(acc, cfg.dat_width, win.combine, win.n_terms);
 }
 
+// Coefficient n by K-1 full CORDIC chains in the mad-form rotation of k_direct_fast (rot_step: |x| < 2^33, quarter circle <= 2^32),
+// with the chain as a rolled loop on a scalar counter (rot_step_dyn) instead of one unrolled instance per rotation count: the per-lane work
+// of k_frames_direct (bhw_frames.hip) and k_ola_direct (bhw_ola.hip), where the coefficient is spread over many frames or hops,
+// so the 26 NITER instances of k_direct_fast would buy little.
+__device__ __forceinline__ int32_t direct_coeff_mad(const BhwCordicCfg &cfg, const BhwWinCfg &win, const uint32_t *lut, uint32_t n)
+{
+    const uint32_t pw = cfg.phi_width;
+    const uint32_t mask = (pw >= 32) ? 0xFFFFFFFFu : ((1u << pw) - 1u);
+    const uint32_t tmask = (1u << (pw - 2)) - 1u;
+    int64_t acc = win.aa[0];
+    for (uint32_t k = 1; k < win.n_terms; ++k) {
+        const uint32_t theta = (k * n) & mask;
+        const uint32_t u = (theta & tmask) >> cfg.z_shr;
+        int64_t x = cfg.x0, y = cfg.x0;                                          // rotation 0 always adds (z0 >= 0)
+        int32_t z = (int32_t)((u << cfg.z_shl) - lut[0]);
+        const int n_iter = (int)cfg.n_iter;
+        for (int r = 1; r < n_iter; ++r) rot_step_dyn(x, y, z, r, lut[r], r >= kMad24From);
+        int32_t c, s;
+        quadrant_map(theta >> (pw - 2), (int32_t)(x >> cfg.out_shr), (int32_t)(y >> cfg.out_shr), cfg.ones_neg, c, s);
+        combine_term(acc, win.aa[k], c, k, cfg.dat_width, win.combine);
+    }
+    return combine_final(acc, cfg.dat_width, win.combine, win.n_terms);
+}
+
 // ---------------------------------------------------------------------------------------
 // Coefficient n (0 <= n < 2^PW) gathered from a resident table in any format: the per-lane work of k_range_combine
-// (bhw_range.hip) and k_frames_table (bhw_frames.hip).  FMT: the table format (fmt_of: 0 plain, 1 delta16, 2 residual, 3 nibble,
+// (bhw_range.hip), k_frames_table (bhw_frames.hip) and k_ola_table (bhw_ola.hip).  FMT: the table format (fmt_of: 0 plain, 1 delta16, 2 residual, 3 nibble,
 // 5 nibble + escapes); NT: bound of the term count (3, 5, 7: the harmonics k < win.n_terms are taken, a wave-uniform test); MODE as
 // in k_table_combine_fold_t: 0 HLS rule, 1 HLS rule with the one's-complement quadrant map (cpp model), 2 VHDL rule.  The K - 1
 // gathers of a lane issue together, and the escape format costs one test per lane (the minimum of its low fields over the

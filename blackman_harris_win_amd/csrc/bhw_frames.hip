@@ -85,29 +85,6 @@ __device__ __forceinline__ void frames_apply(const FramesArgs &a, uint32_t k, ui
     else                frames_loop<2, true>(a, k, ty, w);
 }
 
-// Coefficient n by K-1 full CORDIC chains in the mad-form rotation of k_direct_fast (rot_step: |x| < 2^33, quarter circle <= 2^32),
-// with the chain as a rolled loop on a scalar counter (rot_step_dyn) instead of one unrolled instance per rotation count: the
-// coefficient is spread over G frames here, so the 26 NITER instances of k_direct_fast would buy little.
-__device__ __forceinline__ int32_t direct_coeff_mad(const BhwCordicCfg &cfg, const BhwWinCfg &win, const uint32_t *lut, uint32_t n)
-{
-    const uint32_t pw = cfg.phi_width;
-    const uint32_t mask = (pw >= 32) ? 0xFFFFFFFFu : ((1u << pw) - 1u);
-    const uint32_t tmask = (1u << (pw - 2)) - 1u;
-    int64_t acc = win.aa[0];
-    for (uint32_t k = 1; k < win.n_terms; ++k) {
-        const uint32_t theta = (k * n) & mask;
-        const uint32_t u = (theta & tmask) >> cfg.z_shr;
-        int64_t x = cfg.x0, y = cfg.x0;                                          // rotation 0 always adds (z0 >= 0)
-        int32_t z = (int32_t)((u << cfg.z_shl) - lut[0]);
-        const int n_iter = (int)cfg.n_iter;
-        for (int r = 1; r < n_iter; ++r) rot_step_dyn(x, y, z, r, lut[r], r >= kMad24From);
-        int32_t c, s;
-        quadrant_map(theta >> (pw - 2), (int32_t)(x >> cfg.out_shr), (int32_t)(y >> cfg.out_shr), cfg.ones_neg, c, s);
-        combine_term(acc, win.aa[k], c, k, cfg.dat_width, win.combine);
-    }
-    return combine_final(acc, cfg.dat_width, win.combine, win.n_terms);
-}
-
 // Coefficient by the direct CORDIC chains.  FORM 0 / 1: the cordic_full chain of k_direct (T = int32_t, or int64_t where the state
 // needs more than 32 bits); FORM 2: the mad-form rotation where it applies (bhwk_frames picks it as bhwk_direct picks k_direct_fast).
 template <int FORM>

@@ -833,6 +833,108 @@ int bhwp_describe_frames(const bhw_params *p, const BhwCordicCfg *ct, const bhw_
     return BHW_OK;
 }
 
+// ---- weighted overlap-add ----------------------------------------------------------------------------------------------------
+
+int bhwp_ola_checks(const bhw_params *p, const bhw_ola *o, const void *d_y, const void *d_x, bool pointers)
+{
+    if (!p) return bhwp_fail(BHW_ERR_BADARG, "params is NULL");
+    int rc = bhwp_validate(p);
+    if (rc) return rc;
+    if (!o) return bhwp_fail(BHW_ERR_BADARG, "overlap-add descriptor is NULL");
+    if (o->struct_size != sizeof(bhw_ola)) return bhwp_fail(BHW_ERR_BADARG, "bhw_ola.struct_size %u != %zu", o->struct_size, sizeof(bhw_ola));
+    if (o->reserved) return bhwp_fail(BHW_ERR_BADARG, "bhw_ola.reserved must be 0");
+    if (o->channels != 1 && o->channels != 2) return bhwp_fail(BHW_ERR_BADARG, "channels %u (1 or 2)", o->channels);
+    if (o->hop == 0) return bhwp_fail(BHW_ERR_BADARG, "hop is 0");
+    if (o->shift > 62) return bhwp_fail(BHW_ERR_BADARG, "shift %u > 62", o->shift);
+    const uint64_t N = 1ull << p->phi_width, NC = N * o->channels;
+    if (o->y_stride && o->y_stride < NC)
+        return bhwp_fail(BHW_ERR_BADARG, "y_stride %llu < N * channels = %llu", (unsigned long long)o->y_stride, (unsigned long long)NC);
+    if (p->sin_type != BHW_SIN_CORDIC)
+        return bhwp_fail(BHW_ERR_UNSUPPORTED, "the Taylor sources (sin_type %u) have no per-coefficient form to sum frames with: generate the "
+                         "window and form the sums in the caller", p->sin_type);
+    if (!o->count) return BHW_OK;
+    if (!o->frames) return bhwp_fail(BHW_ERR_BADARG, "frames is 0 with count %llu > 0", (unsigned long long)o->count);
+    if (o->frames > (1ull << 34) / N)
+        return bhwp_fail(BHW_ERR_BADARG, "frames * N = %llu * %llu > 2^34 per call", (unsigned long long)o->frames, (unsigned long long)N);
+    // hop is a free 64-bit value: the extent is taken in 128 bits
+    const unsigned __int128 ext = (unsigned __int128)(o->frames - 1) * o->hop + N;
+    if (ext > (1ull << 34)) return bhwp_fail(BHW_ERR_BADARG, "extent (frames - 1) * hop + N above 2^34 per call");
+    if (o->t0 > (uint64_t)ext || o->count > (uint64_t)ext - o->t0)
+        return bhwp_fail(BHW_ERR_BADARG, "t0 + count = %llu + %llu beyond the extent (frames - 1) * hop + N = %llu", (unsigned long long)o->t0,
+                         (unsigned long long)o->count, (unsigned long long)ext);
+    if (!pointers) return BHW_OK;
+    if (!d_y || !d_x) return bhwp_fail(BHW_ERR_BADARG, "d_y / d_x is NULL");
+    // extents in int32 elements: the rows of d_y read, the outputs of d_x written
+    const unsigned __int128 ye = (unsigned __int128)(o->frames - 1) * (o->y_stride ? o->y_stride : NC) + NC;
+    if (ye > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "y extent beyond 2^60 elements");
+    const uint64_t ya = (uint64_t)(uintptr_t)d_y, xa = (uint64_t)(uintptr_t)d_x, yb = (uint64_t)ye * 4u, xb = o->count * o->channels * 4u;
+    if (ya > UINT64_MAX - yb || xa > UINT64_MAX - xb) return bhwp_fail(BHW_ERR_BADARG, "x or y range wraps the address space");
+    if (xa < ya + yb && ya < xa + xb) return bhwp_fail(BHW_ERR_BADARG, "d_x must not overlap d_y");
+    return BHW_OK;
+}
+
+BhwOlaPlan bhwp_ola_plan(const bhw_params *p, const bhw_ola *o, bool from_table, uint32_t force_q, uint32_t force_rx)
+{
+    BhwOlaPlan pl{};
+    const uint64_t N = 1ull << p->phi_width;
+    pl.route = from_table ? BHWP_OLA_TABLE : BHWP_OLA_DIRECT;
+    pl.y_stride = o->y_stride ? o->y_stride : N * o->channels;
+    pl.q0 = o->t0 / o->hop;
+    pl.r0 = o->t0 % o->hop;
+    pl.jmax = o->hop >= N ? 1 : (N + o->hop - 1) / o->hop;
+    if (!o->count) return pl;
+    pl.lanes = o->hop < o->count ? o->hop : o->count;
+    pl.rows = (o->count + o->hop - 1) / o->hop;
+    // lanes along the residue first (consecutive outputs and frame elements in a wave); short hops put the rest of the workgroup
+    // side by side over rows
+    pl.rx = 1;
+    while (pl.rx < kOlaBlock && pl.rx < pl.lanes) pl.rx *= 2;
+    if (force_rx && force_rx <= kOlaBlock && (force_rx & (force_rx - 1)) == 0) pl.rx = force_rx;
+    pl.fy = kOlaBlock / pl.rx;
+    pl.grid_x = (pl.lanes + pl.rx - 1) / pl.rx;
+    // Q: as many workgroups as kOlaTargetWg asks for (a wide residue range fills the chip alone), and at least the frames that reach
+    // one output, so that a lane computes no more coefficients than it writes outputs
+    const uint64_t row_groups = (pl.rows + pl.fy - 1) / pl.fy;
+    const uint64_t gy_target = pl.grid_x >= kOlaOnePassGx ? 1 : (kOlaTargetWg + pl.grid_x - 1) / pl.grid_x;
+    uint64_t Q = (row_groups + gy_target - 1) / gy_target;
+    if (Q < pl.jmax) Q = pl.jmax;
+    if (Q > row_groups) Q = row_groups;
+    if (Q > kOlaQMax) Q = kOlaQMax;
+    if (Q < 1) Q = 1;
+    if (force_q >= 1 && force_q <= kOlaQMax) Q = force_q;
+    pl.q = (uint32_t)Q;
+    pl.row_blocks = (pl.rows + (uint64_t)pl.fy * pl.q - 1) / ((uint64_t)pl.fy * pl.q);
+    pl.grid_y = pl.row_blocks < kOlaMaxGridY ? pl.row_blocks : kOlaMaxGridY;
+    return pl;
+}
+
+int bhwp_describe_ola(const bhw_params *p, const BhwCordicCfg *ct, const bhw_ola *o, char *buf, uint64_t len)
+{
+    if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
+    if (!o->count) {
+        snprintf(buf, len, "overlap-add: nothing (count 0)");
+        return BHW_OK;
+    }
+    const BhwOlaPlan pl = bhwp_ola_plan(p, o, ct != nullptr);
+    char kern[64];
+    if (pl.route == BHWP_OLA_TABLE) {
+        const BhwCordicCfg c = table_layout(*ct);
+        BhwWinCfg w;
+        bhwp_resolve_window(p, w);
+        int fmt, nt, mode;
+        bhwp_range_form(c, w, &fmt, &nt, &mode);
+        snprintf(kern, sizeof kern, "k_ola_table<%d,%d,%d>", fmt, nt, mode);
+    } else {
+        BhwCordicCfg c;
+        bhwp_resolve_cordic(p, c);
+        snprintf(kern, sizeof kern, "k_ola_direct<%d>", bhwp_frames_mad_form(c) ? 2 : c.wide ? 1 : 0);
+    }
+    snprintf(buf, len, "overlap-add %s: %s, %u channel%s, Q = %u hops per lane, up to %llu frames per output, grid %llu x %llu x %u lanes "
+             "(%u along r, %u along q)", pl.route == BHWP_OLA_TABLE ? "table" : "direct", kern, o->channels, o->channels == 2 ? "s" : "",
+             pl.q, (unsigned long long)pl.jmax, (unsigned long long)pl.grid_x, (unsigned long long)pl.grid_y, kOlaBlock, pl.rx, pl.fy);
+    return BHW_OK;
+}
+
 // ---- the pure entry points of the C ABI (include/bhw.h) -------------------------------------------------------------------------------
 extern "C" {
 
@@ -1084,6 +1186,17 @@ int bhw_dbg_describe_frames_from_table(const bhw_params *p_table, uint32_t table
     int rc = dbg_resident_table(p_table, table_format, p_call, c, &tiled);
     if (!rc) rc = bhwp_frames_checks(p_call, f, nullptr, nullptr, false);
     return rc ? rc : bhwp_describe_frames(p_call, &c, f, buf, len);
+}
+
+// bhw_overlap_add_describe of a from-table call from parameters alone (no device, no table), over that table.
+int bhw_dbg_describe_ola_from_table(const bhw_params *p_table, uint32_t table_format, const bhw_params *p_call, const bhw_ola *o,
+                                    char *buf, uint64_t len)
+{
+    BhwCordicCfg c;
+    bool tiled;
+    int rc = dbg_resident_table(p_table, table_format, p_call, c, &tiled);
+    if (!rc) rc = bhwp_ola_checks(p_call, o, nullptr, nullptr, false);
+    return rc ? rc : bhwp_describe_ola(p_call, &c, o, buf, len);
 }
 
 // tab_dlog the residual format would use for `p` (0: not applicable) and whether delta16 applies

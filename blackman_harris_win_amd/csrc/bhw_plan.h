@@ -184,3 +184,40 @@ inline bool bhwp_frames_mad_form(const BhwCordicCfg &c) { return c.dat_width + c
 // the frames kernel of a plan (bhw_frames.hip): d_table NULL = k_frames_direct, else k_frames_table over the resident table of c
 int  bhwk_frames(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwFramesPlan &pl, const bhw_frames *f,
                  const int32_t *d_x, int32_t *d_y, const int32_t *d_table);
+
+// ---- weighted overlap-add (bhw_overlap_add_device / _from_table) --------------------------------------------------------------
+// Output t = q * hop + r.  A lane owns one residue r and a block of Q consecutive hops q: it computes w[r + j * hop] once per j and
+// adds y[(q - j) * y_stride + (r + j * hop) * C + c] * w into Q * C int64 registers, so every element of y is read once and every
+// output written once.  Lanes are numbered relative to t0: lane s < min(hop, count) holds the residue of t0 + s, row i the output
+// u = i * hop + s (u < count).
+enum { BHWP_OLA_DIRECT = 0, BHWP_OLA_TABLE = 1 };
+constexpr uint32_t kOlaBlock = 256;           // lanes of a workgroup: rx along the residue, fy = kOlaBlock / rx side by side over rows
+constexpr uint32_t kOlaQMax = 16;             // Q: rows (hops) of one lane, the int64 accumulators it holds per channel
+constexpr uint32_t kOlaTargetWg = 4096;       // workgroups Q is cut for (16 per CU on 256 CUs) ...
+constexpr uint64_t kOlaOnePassGx = 1024;      // ... unless the residues alone give this many: then Q = kOlaQMax
+constexpr uint32_t kOlaMaxGridY = 65535;      // row blocks beyond it are taken by a grid-stride loop
+struct BhwOlaPlan {
+    int route;           // BHWP_OLA_*
+    uint32_t rx;         // lanes along the residue (a power of two <= kOlaBlock)
+    uint32_t fy;         // rows a workgroup runs side by side: kOlaBlock / rx
+    uint32_t q;          // Q: consecutive rows of one lane, 1..kOlaQMax
+    uint64_t lanes;      // residues in use: min(hop, count)
+    uint64_t rows;       // ceil(count / hop)
+    uint64_t row_blocks; // ceil(rows / (fy * Q)): workgroup rows
+    uint64_t grid_x;     // ceil(lanes / rx)
+    uint64_t grid_y;     // min(row_blocks, kOlaMaxGridY)
+    uint64_t jmax;       // ceil(N / hop): frames that reach the output of residue 0
+    uint64_t y_stride;   // resolved (0 -> N * channels)
+    uint64_t q0, r0;     // t0 = q0 * hop + r0
+};
+// Every argument check of the two calls that needs no table handle, before any HIP call: BHW_OK, BADARG or UNSUPPORTED (the Taylor
+// sources).  count == 0 passes with the pointers unchecked; `pointers` false: the describe call, no pointers.
+int  bhwp_ola_checks(const bhw_params *p, const bhw_ola *o, const void *d_y, const void *d_x, bool pointers = true);
+// route, Q, lane layout and grid of a call that passed bhwp_ola_checks with count > 0; force_q / force_rx > 0 override the rule
+// (bhw_dbg_overlap_add_shape: Q in 1..kOlaQMax, rx a power of two <= kOlaBlock; other values are ignored)
+BhwOlaPlan bhwp_ola_plan(const bhw_params *p, const bhw_ola *o, bool from_table, uint32_t force_q = 0, uint32_t force_rx = 0);
+// bhw_overlap_add_describe: ct = the resident table's resolved configuration (format and layout set), or NULL for the library call
+int  bhwp_describe_ola(const bhw_params *p, const BhwCordicCfg *ct, const bhw_ola *o, char *buf, uint64_t len);
+// the overlap-add kernel of a plan (bhw_ola.hip): d_table NULL = k_ola_direct, else k_ola_table over the resident table of c
+int  bhwk_ola(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwOlaPlan &pl, const bhw_ola *o,
+              const int32_t *d_y, int32_t *d_x, const int32_t *d_table);

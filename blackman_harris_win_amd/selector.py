@@ -191,6 +191,58 @@ def apply_frames(params, x, hop, *, frames=None, channels=1, shift=None, out=Non
     return result
 
 
+def _ola_call(torch, params, y, hop, frames, channels, shift, out, y_stride, t0, count, dev):
+    """Checks and shapes of overlap_add: (bhw_ola, out, the tensor returned)."""
+    if not isinstance(y, torch.Tensor) or y.dtype != torch.int32 or not y.is_cuda or not y.is_contiguous() or y.device.index != dev:
+        raise ValueError("y must be a contiguous int32 CUDA tensor on the call's device")
+    if channels not in (1, 2):
+        raise ValueError("channels must be 1 or 2")
+    if hop < 1:
+        raise ValueError("hop must be >= 1")
+    N = 1 << params.phi_width
+    if y.dim() < 1:
+        raise ValueError("y must be (frames, N), (frames, N, 2) or (frames, y_stride)")
+    rows = y.shape[0]
+    row_len = y.numel() // rows if rows else N * channels
+    stride = row_len if y_stride is None else int(y_stride)
+    if stride < N * channels:
+        raise ValueError(f"y_stride must be >= N * channels = {N * channels}")
+    if frames is None:
+        frames = rows
+    if frames and (frames - 1) * stride + N * channels > y.numel():
+        raise ValueError(f"y holds {y.numel()} int32, {frames} frames at stride {stride} need {(frames - 1) * stride + N * channels}")
+    extent = (frames - 1) * hop + N if frames else 0
+    t0 = int(t0)
+    if count is None:
+        count = max(0, extent - t0)
+    count = int(count)
+    if out is None:
+        out = torch.empty((count, 2) if channels == 2 else (count,), dtype=torch.int32, device=y.device)
+    elif _check_out(torch, out, count * channels) != dev:
+        raise ValueError("out must live on y's device")
+    if shift is None:
+        shift = params.dat_width - 1
+    o = B.make_ola(frames, hop, count, t0=t0, channels=channels, shift=shift, y_stride=stride)
+    result = out.view(-1)[:count * channels].view((count, 2) if channels == 2 else (count,))
+    return o, out, result
+
+
+def overlap_add(params, y, hop, *, frames=None, channels=1, shift=None, out=None, y_stride=None, t0=0, count=None):
+    """Weighted overlap-add (bhw_overlap_add_device), the STFT synthesis side in one launch:
+    x[t - t0, c] = (sum over frames f of y[f, t - f * hop, c] * w[t - f * hop]) >> shift for t in [t0, t0 + count), the sum in
+    int64 (wrapping), the low 32 bits stored.  y: contiguous int32 (frames, N), (frames, N, 2) for I/Q, or (frames, y_stride)
+    rows of which the first N * channels are read.  frames=None takes every row; count=None the whole extent
+    (frames - 1) * hop + N from t0; shift defaults to dat_width - 1.  Returns (count,) int32, or (count, 2) for I/Q."""
+    torch = _torch()
+    if not isinstance(y, torch.Tensor) or not y.is_cuda:
+        raise ValueError("y must be a contiguous int32 CUDA tensor")
+    dev = y.device.index
+    o, out, result = _ola_call(torch, params, y, int(hop), frames, channels, shift, out, y_stride, t0, count, dev)
+    B.check(B.lib().bhw_overlap_add_device(ctypes.byref(params), dev, _stream_ptr(torch, dev), ctypes.byref(o),
+                                           ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(out.data_ptr())))
+    return result
+
+
 class ResidentTable:
     """A first-quadrant CORDIC table built once and kept on the device (bhw_table_create): the elaboration of win_selector's
     CORDIC from its generics (model, PHI_WIDTH, DAT_WIDTH, PRECISION).  Every call then takes the run-time ports -- the weights
@@ -284,6 +336,22 @@ class ResidentTable:
     def describe_frames(self, params, frames, hop, *, channels=1, y_stride=0):
         """The route and kernels apply_frames(params, ...) launches over this table (bhw_apply_frames_describe)."""
         return B.describe_frames(params, frames, hop, channels=channels, y_stride=y_stride, table=self._live())
+
+    def overlap_add(self, params, y, hop, *, frames=None, channels=1, shift=None, out=None, y_stride=None, t0=0, count=None):
+        """overlap_add() with the coefficients gathered from this table (bhw_overlap_add_from_table): no allocation by the
+        library, no synchronisation, capturable into a graph."""
+        torch = _torch()
+        h = self._live()
+        if not isinstance(y, torch.Tensor) or not y.is_cuda or y.device.index != self.device:
+            raise ValueError("y must be a contiguous int32 CUDA tensor on the table's device")
+        o, out, result = _ola_call(torch, params, y, int(hop), frames, channels, shift, out, y_stride, t0, count, self.device)
+        B.check(B.lib().bhw_overlap_add_from_table(h, ctypes.byref(params), _stream_ptr(torch, self.device), ctypes.byref(o),
+                                                   ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(out.data_ptr())))
+        return result
+
+    def describe_overlap_add(self, params, frames, hop, count=None, *, t0=0, channels=1, y_stride=0):
+        """The route and kernel overlap_add(params, ...) launches over this table (bhw_overlap_add_describe)."""
+        return B.describe_ola(params, frames, hop, count, t0=t0, channels=channels, y_stride=y_stride, table=self._live())
 
     def generate_part(self, params, part, n_parts, window):
         """Interleaved ownership part `part` of `n_parts` into the full-length `window` (bhw_generate_part_from_table)."""

@@ -29,7 +29,8 @@ extern "C" {
 #endif
 
 #define BHW_ABI_VERSION 4u   /* 3: bhw_coeffs_preset, bhw_gather_parts_device; 4: bhw_workspace_bytes_ex (nothing removed or changed);
-                                the resident tables and the overlapped-frame apply were added without a bump (additions only) */
+                                the resident tables, the overlapped-frame apply and the overlap-add were added without a bump
+                                (additions only) */
 
 /* CORDIC bit-model (the reference holds three that are not bit-identical). */
 enum {
@@ -326,6 +327,45 @@ int bhw_apply_frames_device(const bhw_params *p, int device, void *hip_stream, c
 int bhw_apply_frames_from_table(bhw_table t, const bhw_params *p, void *hip_stream, const bhw_frames *f, const int32_t *d_x,
                                 int32_t *d_y);
 int bhw_apply_frames_describe(bhw_table t, const bhw_params *p, const bhw_frames *f, char *buf, uint64_t len);
+
+/* Weighted overlap-add (the synthesis side of an STFT: the window multiplies every frame again and the overlapping frames are summed
+ * back into one signal).  The transpose of bhw_apply_frames_device.  With N = 2^phi_width, C = channels and w[k] the coefficient
+ * bhw_generate_device(p, n0 = 0) gives at index k, for every output time index t in [t0, t0 + count) and every c < C:
+ *     S = sum over f < frames with f * hop <= t < f * hop + N of  int64 d_y[f * y_stride + (t - f * hop) * C + c] * int64 w[t - f * hop]
+ *     d_x[(t - t0) * C + c] = low32(S >> shift)       (arithmetic shift 0..62; an empty sum is 0 and is written)
+ * the arithmetic of bhw_apply_device summed before the shift.  The sum wraps mod 2^64, so the result is bit-exact whatever the
+ * order of summation.  Only the first N * C elements of each frame row of d_y are read; y_stride counts int32 elements between
+ * frame starts (0 = N * C; a larger stride reads the frames out of a zero-padded inverse-FFT output).  The signal's extent is
+ * (frames - 1) * hop + N time indices; t0 / count pick an output range inside it.  A streaming caller calls once per block and passes
+ * again the last ceil(N / hop) - 1 frames of the previous block: only the outputs every one of their frames reaches are complete.
+ * With hop > N the gaps between frames come out as 0.  d_x holds count * C int32 and must not overlap the rows of d_y read.
+ *   - All argument checks come before any HIP call: NULL pointers, struct_size, reserved != 0, channels outside {1, 2}, hop 0,
+ *     shift > 62, y_stride below N * C, frames 0 with count > 0, t0 + count beyond the extent, frames * N or the extent above 2^34,
+ *     overlap of d_x and d_y, and (from a table) the key match of the table calls.  count == 0 returns BHW_OK, pointers unchecked.
+ *   - The Taylor sources (BHW_SIN_TAYLOR*) are BHW_ERR_UNSUPPORTED: they have no per-coefficient form to sum frames with.  Generate
+ *     the window once (bhw_generate_device) and form the products and sums in the caller's framework instead.
+ *   - bhw_overlap_add_device accepts every CORDIC configuration bhw_apply_device accepts.  Each coefficient is computed once per
+ *     lane and applied to a block of Q consecutive hops (k_ola_direct: direct CORDIC); it allocates nothing and uses no scratch,
+ *     so it can be captured with no bhw_prepare_device.
+ *   - bhw_overlap_add_from_table keeps the contract of the from-table calls: no allocation, no synchronisation, always capturable,
+ *     any number of concurrent readers; the coefficients are gathered from the resident table (k_ola_table).
+ *   - bhw_overlap_add_describe: one line -- the route, Q, the lane layout, the grid and the kernel name.  t may be NULL (the library
+ *     call).  Host arithmetic only. */
+typedef struct bhw_ola {
+    uint32_t struct_size;  /* sizeof(bhw_ola) = 56                                    */
+    uint32_t channels;     /* 1 or 2 (interleaved I/Q, one coefficient per pair)       */
+    uint64_t frames;
+    uint64_t hop;          /* >= 1                                                     */
+    uint64_t y_stride;     /* int32 elements between frame starts in d_y; 0 = N * C   */
+    uint64_t t0;           /* first output time index                                  */
+    uint64_t count;        /* output time indices; 0 = nothing to do                   */
+    uint32_t shift;        /* 0..62                                                    */
+    uint32_t reserved;     /* must be 0                                                */
+} bhw_ola;
+int bhw_overlap_add_device(const bhw_params *p, int device, void *hip_stream, const bhw_ola *o, const int32_t *d_y, int32_t *d_x);
+int bhw_overlap_add_from_table(bhw_table t, const bhw_params *p, void *hip_stream, const bhw_ola *o, const int32_t *d_y,
+                               int32_t *d_x);
+int bhw_overlap_add_describe(bhw_table t, const bhw_params *p, const bhw_ola *o, char *buf, uint64_t len);
 
 /* Threading: every entry point may be called from any host thread.  Calls that use the library-owned scratch of one
  * (device, stream) are serialised against each other for the duration of their launches (the table is rebuilt per call);

@@ -8,6 +8,7 @@
 //   bhw::cordic_atan2() <->  entity cordic_atan2            src/cordic_atan2.vhd:64-76
 //   bhw::resident_table      the elaborated CORDIC of win_selector's generics (bhw_table_create), move-only, RAII
 //   bhw::apply_frames()      the window over overlapping frames of a signal in one launch (bhw_apply_frames_device)
+//   bhw::overlap_add()       the weighted overlap-add of frames back into one signal in one launch (bhw_overlap_add_device)
 // Same names, argument meaning and error behaviour (unknown win_type -> zeros, like win_empty,
 // hls/windows/win_function.cpp:159-165,417-419).  All arithmetic runs in the HIP kernels behind the ABI.
 #pragma once
@@ -181,6 +182,21 @@ inline void apply_frames(const bhw_params &p, const bhw_frames &f, const int32_t
     check(bhw_apply_frames_device(&p, device, hip_stream, &f, d_x, d_y));
 }
 
+// The descriptor of a weighted overlap-add: `frames` frames of `hop` time indices apart summed into the outputs [t0, t0 + count),
+// `channels` 1 or 2 (I/Q), y_stride 0 = N * C.
+inline bhw_ola ola(uint64_t n_frames, uint64_t hop, uint64_t count, uint32_t shift, uint64_t t0 = 0, uint32_t channels = 1,
+                   uint64_t y_stride = 0)
+{
+    return bhw_ola{(uint32_t)sizeof(bhw_ola), channels, n_frames, hop, y_stride, t0, count, shift, 0u};
+}
+
+// Weighted overlap-add (the STFT synthesis side): every frame of d_y windowed by `p` again and summed into d_x in one launch
+// (bhw_overlap_add_device); device pointers and stream as in the C call.
+inline void overlap_add(const bhw_params &p, const bhw_ola &o, const int32_t *d_y, int32_t *d_x, int device = 0, void *hip_stream = nullptr)
+{
+    check(bhw_overlap_add_device(&p, device, hip_stream, &o, d_y, d_x));
+}
+
 // The CORDIC table of a configuration's generics, built once on `device` (bhw_table_create) and freed by the destructor
 // (bhw_table_destroy: it synchronises the device first).  Move-only.  Every call takes its weights -- the AA ports -- from its own
 // bhw_params, which must match the table's generics; device pointers and streams as in the C calls.
@@ -230,6 +246,16 @@ public:
     {
         char buf[384];
         check(bhw_apply_frames_describe(t_, &p, &f, buf, sizeof buf));
+        return buf;
+    }
+    void overlap_add(const bhw_params &p, void *hip_stream, const bhw_ola &o, const int32_t *d_y, int32_t *d_x) const
+    {
+        check(bhw_overlap_add_from_table(t_, &p, hip_stream, &o, d_y, d_x));
+    }
+    std::string describe_overlap_add(const bhw_params &p, const bhw_ola &o) const
+    {
+        char buf[384];
+        check(bhw_overlap_add_describe(t_, &p, &o, buf, sizeof buf));
         return buf;
     }
     void generate_part(const bhw_params &p, void *hip_stream, uint32_t part, uint32_t n_parts, int32_t *d_window) const
