@@ -47,7 +47,8 @@ __global__ __launch_bounds__(kBlock) void k_table_build(BhwCordicCfg cfg, uint32
 // rotation 0 always adds (z0 >= 0), giving x1 = y1 = x0 and z1 = z0 - lut[0], which fits int32.
 // ---------------------------------------------------------------------------------------
 
-// FMT: table format as a template parameter (0 plain, 1 delta16, 2 residual): no format branches around the stores.
+// FMT: table format as a template parameter (0 plain, 1 delta16; 4 no table, the sin / cos sweep of bhwk_sincos): no format
+// branches around the stores.  Residual and nibble tables come only from k_table_build_mirror.
 template <int NITER, int FMT>
 __global__ __launch_bounds__(kBuildThreads) void k_table_build_shared(BhwBuildPlan plan, void *__restrict__ table)
 {
@@ -64,33 +65,6 @@ __global__ __launch_bounds__(kBuildThreads) void k_table_build_shared(BhwBuildPl
     const uint32_t gpw = plan.groups_per_wg;
     const uint32_t group0 = blockIdx.x * gpw;
     const uint32_t n_groups = plan.entries >> 6;
-
-    // Residual format: the records {c, s, dc, ds} of the cells this workgroup touches.  Lanes of the second wave run the full
-    // chain (the very rot_step of the leaves) at the cell starts -- heads cell_lo .. cell_lo + n_cell, plus head cell_lo - 1
-    // for the table's last cell, whose end point is not an entry and which reuses the slope of the cell before it -- while
-    // the first wave runs the group prefixes; cells that start inside this workgroup are also written out for the combine pass.
-    __shared__ int32_t hc[kHeadsMax], hs[kHeadsMax];
-    const uint32_t d = fmt_cell_log(plan.tab_dlog);
-    constexpr bool resid = (FMT == 2 || FMT == 3);            // (FMT 4: no table, see the store below)
-    const uint32_t cells_total = resid ? plan.entries >> d : 0u;
-    uint32_t cell_lo = 0, n_cell = 0;
-    if (resid) {
-        const uint32_t u_end = ((group0 + gpw) << 6) < plan.entries ? ((group0 + gpw) << 6) : plan.entries;
-        cell_lo = (group0 << 6) >> d;
-        n_cell = ((u_end - 1u) >> d) - cell_lo + 1u;
-    }
-    if (resid && threadIdx.x >= 64u && threadIdx.x < 64u + n_cell + 2u) {
-        const uint32_t t = threadIdx.x - 64u;
-        const int64_t cell = (t <= n_cell) ? (int64_t)cell_lo + t : (int64_t)cell_lo - 1;
-        if (cell >= 0 && cell < (int64_t)cells_total) {
-            int64_t x = plan.x0, y = plan.x0;
-            int32_t z = (int32_t)((((uint32_t)cell << d) << s) - lut_s[0]);
-#pragma unroll
-            for (int r = 1; r < n_iter; ++r) rot_step(x, y, z, r, plan.lut[r]);
-            hc[t] = (int32_t)(x >> plan.out_shr);
-            hs[t] = (int32_t)(y >> plan.out_shr);
-        }
-    }
 
     // ---- phase 1: shared prefix of each 64-leaf group ----
     if (threadIdx.x < gpw) {
@@ -121,21 +95,6 @@ __global__ __launch_bounds__(kBuildThreads) void k_table_build_shared(BhwBuildPl
         gk[threadIdx.x] = k;
     }
     __syncthreads();
-
-    auto record_of = [&](uint32_t cell) -> int4 {                  // cell in [cell_lo, cell_lo + n_cell)
-        const uint32_t t = cell - cell_lo;
-        if (cell + 1u < cells_total) return make_int4(hc[t], hs[t], hc[t + 1] - hc[t], hs[t + 1] - hs[t]);
-        const uint32_t tp = t ? t - 1u : n_cell + 1u;                // last cell of the table: slope of the cell before it
-        return make_int4(hc[t], hs[t], hc[t] - hc[tp], hs[t] - hs[tp]);
-    };
-    auto record = [&](uint32_t cell) -> int4 {                     // the same for a wave-uniform cell: scalar control flow
-        return record_of(__builtin_amdgcn_readfirstlane(cell));
-    };
-    if (resid && threadIdx.x < n_cell) {
-        const uint32_t cell = cell_lo + threadIdx.x;
-        if ((cell << d) >= (group0 << 6))                            // starts inside this workgroup's entries: this one writes it
-            reinterpret_cast<int4 *>(const_cast<void *>(plan.tab_coarse))[cell] = record_of(cell);
-    }
 
     // ---- phase 2: one wave per group, one lane per leaf, remaining rotations only ----
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;   // g and what derives from it stay scalar
@@ -179,24 +138,12 @@ __global__ __launch_bounds__(kBuildThreads) void k_table_build_shared(BhwBuildPl
             }
         } else if constexpr (FMT == 0) {
             reinterpret_cast<int2 *>(table)[idx] = make_int2(c, sn);
-        } else if constexpr (FMT == 1) {
+        } else {
+            static_assert(FMT == 1, "k_table_build_shared builds plain and delta16 tables (and the sin / cos sweep) only");
             const int32_t dc = c - head.x, ds = sn - head.y;
             if (plan.check_flag && !(fits_bits(dc, 16) && fits_bits(ds, 16))) atomicOr(plan.check_flag, 1u);   // scalar guard: verified configurations skip it
             reinterpret_cast<uint32_t *>(table)[idx] = ((uint32_t)dc & 0xFFFFu) | ((uint32_t)ds << 16);
             if (lane == 0u) reinterpret_cast<int2 *>(const_cast<void *>(plan.tab_coarse))[g] = head;   // block = group
-        } else {
-            const int4 rec = record((g << 6) >> d);                                                     // wave-uniform
-            const int2 p = tab_predict(rec, ((g << 6) & ((1u << d) - 1u)) + lane, d);
-            const int32_t dc = c - p.x, ds = sn - p.y;
-            // (byte-wide stores make this variant 2 % slower than the two-byte one at equal instruction counts, 72.3 against 70.7 us;
-            // staging a workgroup's entries in shared memory and writing them as 16-byte packets costs more than it saves, +1.5 us)
-            if constexpr (FMT == 3) {
-                if (plan.check_flag && !(fits_bits(dc, 4) && fits_bits(ds, 4))) atomicOr(plan.check_flag, 1u);
-                reinterpret_cast<uint8_t *>(table)[idx] = (uint8_t)(((uint32_t)dc & 0xFu) | (((uint32_t)ds & 0xFu) << 4));
-            } else {
-                if (plan.check_flag && !(fits_bits(dc, 8) && fits_bits(ds, 8))) atomicOr(plan.check_flag, 1u);
-                reinterpret_cast<uint16_t *>(table)[idx] = (uint16_t)(((uint32_t)dc & 0xFFu) | (((uint32_t)ds & 0xFFu) << 8));
-            }
         }
     }
 }
@@ -822,7 +769,6 @@ __global__ __launch_bounds__(kBlock) void k_table_build_plain(BhwCordicCfg cfg, 
 // straight out (k_table_build_shared<N, 4>).
 int bhwk_sincos_sweep(const BhwLaunch &l, const BhwCordicCfg &c, uint64_t theta0, int32_t *d_sin, int32_t *d_cos)
 {
-    BHW_SET_DEVICE(l);
     hipStream_t st = (hipStream_t)l.stream;
     BhwBuildPlan plan;
     for (uint32_t k = 0; k < 32; ++k) plan.lut[k] = (uint32_t)c.lut[k];
@@ -842,15 +788,8 @@ int bhwk_sincos_sweep(const BhwLaunch &l, const BhwCordicCfg &c, uint64_t theta0
     plan.groups_per_wg = groups >= 64u * 1024u ? 64u : groups >= 16u * 1024u ? 16u : 4u;
     plan.pad = (uint32_t)(theta0 & ((1ull << c.phi_width) - 1ull));
     const dim3 grid((groups + plan.groups_per_wg - 1) / plan.groups_per_wg), block(kBuildThreads);
-    switch (c.n_iter) {
-#define BHW_CASE(N) case N: BHW_LAUNCH((k_table_build_shared<N, 4>), grid, block, 0, st, plan, (void *)d_sin); break;
-        BHW_CASE(7) BHW_CASE(8) BHW_CASE(9) BHW_CASE(10) BHW_CASE(11) BHW_CASE(12) BHW_CASE(13) BHW_CASE(14)
-        BHW_CASE(15) BHW_CASE(16) BHW_CASE(17) BHW_CASE(18) BHW_CASE(19) BHW_CASE(20) BHW_CASE(21) BHW_CASE(22)
-        BHW_CASE(23) BHW_CASE(24) BHW_CASE(25) BHW_CASE(26) BHW_CASE(27) BHW_CASE(28) BHW_CASE(29) BHW_CASE(30)
-        BHW_CASE(31) BHW_CASE(32)
-#undef BHW_CASE
-    default: return (int)hipErrorInvalidValue;
-    }
+    if (!with_int_range<7, 32>(c.n_iter, [&](auto N) { launch(k_table_build_shared<N, 4>, grid, block, st, plan, (void *)d_sin); }))
+        return (int)hipErrorInvalidValue;
     return finish(hipSuccess);
 }
 
@@ -865,22 +804,14 @@ extern "C" int bhw_dbg_build_stamps(void *d_words)      // 8 x uint64 per workgr
 int bhwk_table_build(const BhwLaunch &l, const BhwCordicCfg &c_in, int32_t *d_table)
 {
     const BhwCordicCfg c = table_layout(c_in);
-    BHW_SET_DEVICE(l);
     hipStream_t st = (hipStream_t)l.stream;
     const uint32_t entries = 1u << (c.phi_width - 2 - c.z_shr);
     // shared-prefix kernel: needs whole 64-leaf groups, |x| < 2^33 and a quarter circle <= 2^32
     const bool fits = (c.dat_width + c.out_shr <= 34);
     if (fits && c.n_iter >= 7 && entries < (1u << 20) && c.tab_dlog == 0 && !c.tab_split) {
         const dim3 grid(grid_for(entries)), block(kBlock);
-        switch (c.n_iter) {
-#define BHW_CASE(N) case N: BHW_LAUNCH(k_table_build_plain<N>, grid, block, 0, st, c, entries, (int2 *)d_table); break;
-            BHW_CASE(7) BHW_CASE(8) BHW_CASE(9) BHW_CASE(10) BHW_CASE(11) BHW_CASE(12) BHW_CASE(13) BHW_CASE(14)
-            BHW_CASE(15) BHW_CASE(16) BHW_CASE(17) BHW_CASE(18) BHW_CASE(19) BHW_CASE(20) BHW_CASE(21) BHW_CASE(22)
-            BHW_CASE(23) BHW_CASE(24) BHW_CASE(25) BHW_CASE(26) BHW_CASE(27) BHW_CASE(28) BHW_CASE(29) BHW_CASE(30)
-            BHW_CASE(31) BHW_CASE(32)
-#undef BHW_CASE
-        default: return (int)hipErrorInvalidValue;
-        }
+        if (!with_int_range<7, 32>(c.n_iter, [&](auto N) { launch(k_table_build_plain<N>, grid, block, st, c, entries, (int2 *)d_table); }))
+            return (int)hipErrorInvalidValue;
         return finish(hipSuccess);
     }
     if (entries >= 64 && fits && c.n_iter >= 2) {
@@ -913,36 +844,25 @@ int bhwk_table_build(const BhwLaunch &l, const BhwCordicCfg &c_in, int32_t *d_ta
             const unsigned mgpw = (unsigned)mirror_gpw((int)threads);
             const dim3 mgrid((own_groups + mgpw - 1) / mgpw), mblock(threads);
             plan.groups_per_wg = mgpw;
-            switch (c.n_iter) {
-#define BHW_CASE_MT(N, F) do { if (threads == 1024u) BHW_LAUNCH((k_table_build_mirror<N, F, 1024>), mgrid, mblock, 0, st, plan, (void *)d_table); \
-                               else                  BHW_LAUNCH((k_table_build_mirror<N, F, 256>), mgrid, mblock, 0, st, plan, (void *)d_table); } while (0)
-#define BHW_CASE_M(N) case N: if (fmt == 2) BHW_CASE_MT(N, 2); else if (fmt == 3) BHW_CASE_MT(N, 3); else BHW_CASE_MT(N, 5); break;
-                BHW_CASE_M(21) BHW_CASE_M(22) BHW_CASE_M(23) BHW_CASE_M(24) BHW_CASE_M(25) BHW_CASE_M(26) BHW_CASE_M(27) BHW_CASE_M(28)
-                BHW_CASE_M(29) BHW_CASE_M(30) BHW_CASE_M(31) BHW_CASE_M(32)
-#undef BHW_CASE_M
-#undef BHW_CASE_MT
-            default: return (int)hipErrorInvalidValue;
-            }
-            return finish(hipSuccess);
+            const bool listed = with_int_range<21, 32>(c.n_iter, [&](auto N) {
+                with_int_or_last<2, 3, 5>(fmt, [&](auto F) {
+                    with_int_or_last<1024, 256>((int)threads, [&](auto T) {
+                        launch(k_table_build_mirror<N, F, T>, mgrid, mblock, st, plan, (void *)d_table);
+                    });
+                });
+            });
+            return listed ? finish(hipSuccess) : (int)hipErrorInvalidValue;
         }
-#define BHW_LAUNCH_BUILD(N, F) BHW_LAUNCH((k_table_build_shared<N, F>), grid, block, 0, st, plan, (void *)d_table)
-#define BHW_CASE(N) case N: BHW_LAUNCH_BUILD(N, 0); break;
-#define BHW_CASE_T(N) case N: if (fmt == 0) BHW_LAUNCH_BUILD(N, 0); else if (fmt == 1) BHW_LAUNCH_BUILD(N, 1); else return (int)hipErrorInvalidValue; break;   /* residual / nibble tables: the mirror kernel above (tables of 2^20 entries and more, the only ones that use them) */
-        switch (c.n_iter) {
-            BHW_CASE(7) BHW_CASE(8) BHW_CASE(9) BHW_CASE(10) BHW_CASE(11) BHW_CASE(12) BHW_CASE(13) BHW_CASE(14)
-            BHW_CASE(15) BHW_CASE(16) BHW_CASE(17) BHW_CASE(18) BHW_CASE(19) BHW_CASE(20)
-            BHW_CASE_T(21) BHW_CASE_T(22) BHW_CASE_T(23) BHW_CASE_T(24) BHW_CASE_T(25) BHW_CASE_T(26) BHW_CASE_T(27) BHW_CASE_T(28)
-            BHW_CASE_T(29) BHW_CASE_T(30) BHW_CASE_T(31) BHW_CASE_T(32)
-        default: return (int)hipErrorInvalidValue;
-        }
-#undef BHW_CASE
-#undef BHW_CASE_T
-#undef BHW_LAUNCH_BUILD
-        return finish(hipSuccess);
+        if (fmt > 1) return (int)hipErrorInvalidValue;   // residual / nibble tables: the mirror kernel above (tables of 2^20 entries and more, the only ones that use them)
+        const bool listed = with_int_range<7, 32>(c.n_iter, [&](auto N) {
+            if constexpr (N < 21) launch(k_table_build_shared<N, 0>, grid, block, st, plan, (void *)d_table);
+            else with_int_or_last<0, 1>(fmt, [&](auto F) { launch(k_table_build_shared<N, F>, grid, block, st, plan, (void *)d_table); });
+        });
+        return listed ? finish(hipSuccess) : (int)hipErrorInvalidValue;
     }
-    if (c.tab_dlog > kPackLog) return (int)hipErrorInvalidValue;        // residual records come from the shared-prefix kernel only
-    if (c.wide) BHW_LAUNCH(k_table_build<int64_t>, dim3(grid_for(entries)), dim3(kBlock), 0, st, c, entries, (void *)d_table);
-    else        BHW_LAUNCH(k_table_build<int32_t>, dim3(grid_for(entries)), dim3(kBlock), 0, st, c, entries, (void *)d_table);
+    if (c.tab_dlog > kPackLog) return (int)hipErrorInvalidValue;        // residual and nibble tables come from the mirror kernel only
+    if (c.wide) launch(k_table_build<int64_t>, dim3(grid_for(entries)), dim3(kBlock), st, c, entries, (void *)d_table);
+    else        launch(k_table_build<int32_t>, dim3(grid_for(entries)), dim3(kBlock), st, c, entries, (void *)d_table);
     return finish(hipSuccess);
 }
 

@@ -744,38 +744,26 @@ int bhwk_table_combine(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWi
 {
     const BhwCordicCfg c = table_layout(c_in);
     if (!count) return 0;
-    BHW_SET_DEVICE(l);
     hipStream_t st = (hipStream_t)l.stream;
-    BHW_LAUNCH(k_table_combine, dim3(grid_for(count)), dim3(kBlock), 0, st, c, w, (const void *)d_table, n0, count, d_out);
+    launch(k_table_combine, dim3(grid_for(count)), dim3(kBlock), st, c, w, (const void *)d_table, n0, count, d_out);
     return finish(hipSuccess);
 }
 
 int bhwk_table_combine_fold(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinCfg &w, const int32_t *d_table, int32_t *d_out)
 {
     const BhwCordicCfg c = table_layout(c_in);
-    BHW_SET_DEVICE(l);
     hipStream_t st = (hipStream_t)l.stream;
     const uint32_t quarter = 1u << (c.phi_width - 2);
     if (c.tab_dlog == 0 && !c.tab_split) {                          // the usual case: plain natural table
-        const int mode = (w.combine != BHW_COMBINE_HLS) ? 2 : (c.ones_neg ? 1 : 0);
         const dim3 grid(grid_for(quarter)), block(kBlock);
-#define BHW_FOLD_NT(NT)                                                                                                   \
-        do {                                                                                                              \
-            if (mode == 0)      BHW_LAUNCH((k_table_combine_fold_t<NT, 0>), grid, block, 0, st, c, w, (const void *)d_table, d_out); \
-            else if (mode == 1) BHW_LAUNCH((k_table_combine_fold_t<NT, 1>), grid, block, 0, st, c, w, (const void *)d_table, d_out); \
-            else                BHW_LAUNCH((k_table_combine_fold_t<NT, 2>), grid, block, 0, st, c, w, (const void *)d_table, d_out); \
-        } while (0)
-        switch (w.n_terms) {
-        case 2: BHW_FOLD_NT(2); return finish(hipSuccess);
-        case 3: BHW_FOLD_NT(3); return finish(hipSuccess);
-        case 4: BHW_FOLD_NT(4); return finish(hipSuccess);
-        case 5: BHW_FOLD_NT(5); return finish(hipSuccess);
-        case 7: BHW_FOLD_NT(7); return finish(hipSuccess);
-        default: break;
-        }
-#undef BHW_FOLD_NT
+        const bool listed = with_int<2, 3, 4, 5, 7>((int)w.n_terms, [&](auto NT) {
+            with_int_or_last<0, 1, 2>(mode_of(c, w), [&](auto M) {
+                launch(k_table_combine_fold_t<NT, M>, grid, block, st, c, w, (const void *)d_table, d_out);
+            });
+        });
+        if (listed) return finish(hipSuccess);
     }
-    BHW_LAUNCH(k_table_combine_fold, dim3(grid_for(quarter)), dim3(kBlock), 0, st, c, w, (const void *)d_table, d_out);
+    launch(k_table_combine_fold, dim3(grid_for(quarter)), dim3(kBlock), st, c, w, (const void *)d_table, d_out);
     return finish(hipSuccess);
 }
 
@@ -785,7 +773,6 @@ int bhwk_table_combine_tile_range(const BhwLaunch &l, const BhwCordicCfg &c_in, 
                                   uint32_t tile0, uint32_t tile_count, uint32_t img_mask, uint32_t n0mod)
 {
     const BhwCordicCfg c = table_layout(c_in);
-    BHW_SET_DEVICE(l);
     hipStream_t st = (hipStream_t)l.stream;
     BhwTilePlan tp;
     int nb;
@@ -798,42 +785,21 @@ int bhwk_table_combine_tile_range(const BhwLaunch &l, const BhwCordicCfg &c_in, 
     tp.n0mod = n0mod;
     const bool masked = tp.img_mask != 0xFFu;                       // some of the eight images only (bhwk_tile_images_applicable)
     if (masked && (nb != 15 || w.apply_x != nullptr || tp.img_mask == 0u)) return (int)hipErrorInvalidValue;
-    const int mode = (w.combine != BHW_COMBINE_HLS) ? 2 : (c.ones_neg ? 1 : 0);
     const uint32_t wg_threads = (uint32_t)tile_wg_of(nb);
     const dim3 grid(tile_count * ((uint32_t)kTileThreads / wg_threads)), block(wg_threads);
     const bool fast = bhwp_tile_fast(c, w, nb);                     // one-instruction products (and, VHDL rule, one-word sums)
     if (bhwk_tile9_applicable(c, w, nb, fast, masked)) return bhwk_tile9(l, c, w, tp, tile_count, d_table, d_out);   // bhw_tile9.hip
-#define BHW_LAUNCH_TILE_MFK(NB, M, F, K)                                                                                 \
-    do {                                                                                                                 \
-        if (c.tab_dlog == 0)             BHW_LAUNCH((k_table_combine_tile<NB, M, 0, F, K>), grid, block, 0, st, c, w, tp, (const void *)d_table, d_out); \
-        else if (c.tab_dlog == kPackLog) BHW_LAUNCH((k_table_combine_tile<NB, M, 1, F, K>), grid, block, 0, st, c, w, tp, (const void *)d_table, d_out); \
-        else if (c.tab_dlog < kNibbleFlag) BHW_LAUNCH((k_table_combine_tile<NB, M, 2, F, K>), grid, block, 0, st, c, w, tp, (const void *)d_table, d_out); \
-        else if (c.tab_dlog < kEscFlag)  BHW_LAUNCH((k_table_combine_tile<NB, M, 3, F, K>), grid, block, 0, st, c, w, tp, (const void *)d_table, d_out); \
-        else                             BHW_LAUNCH((k_table_combine_tile<NB, M, 5, F, K>), grid, block, 0, st, c, w, tp, (const void *)d_table, d_out); \
-    } while (0)
-#define BHW_LAUNCH_TILE_MF(NB, M, F)                                                                                     \
-    do {                                                                                                                 \
-        if (NB == 15 && masked) BHW_LAUNCH_TILE_MFK(NB, M, F, (NB == 15));                                               \
-        else                    BHW_LAUNCH_TILE_MFK(NB, M, F, false);                                                    \
-    } while (0)
-#define BHW_LAUNCH_TILE_M(NB, M)                                                                                         \
-    do {                                                                                                                 \
-        if (NB == 15 && fast) BHW_LAUNCH_TILE_MF(NB, M, (NB == 15));                                                    \
-        else                            BHW_LAUNCH_TILE_MF(NB, M, false);                                                \
-    } while (0)
-#define BHW_LAUNCH_TILE(NB)                                                                                              \
-    do {                                                                                                                 \
-        if (mode == 0)      BHW_LAUNCH_TILE_M(NB, 0);                                                                    \
-        else if (mode == 1) BHW_LAUNCH_TILE_M(NB, 1);                                                                    \
-        else                BHW_LAUNCH_TILE_M(NB, 2);                                                                    \
-    } while (0)
-    if (nb == 15) BHW_LAUNCH_TILE(15);
-    else if (nb == 3) BHW_LAUNCH_TILE(3);
-    else BHW_LAUNCH_TILE(1);
-#undef BHW_LAUNCH_TILE_M
-#undef BHW_LAUNCH_TILE_MF
-#undef BHW_LAUNCH_TILE_MFK
-#undef BHW_LAUNCH_TILE
+    auto tile = [&](auto NB, auto M, auto F, auto K) {
+        with_int_or_last<0, 1, 2, 3, 5>(fmt_of(c.tab_dlog), [&](auto FMT) {
+            launch(k_table_combine_tile<NB, M, FMT, F, K>, grid, block, st, c, w, tp, (const void *)d_table, d_out);
+        });
+    };
+    with_int_or_last<15, 3, 1>(nb, [&](auto NB) {
+        with_int_or_last<0, 1, 2>(mode_of(c, w), [&](auto M) {
+            if constexpr (NB == 15) with_bool(fast, [&](auto F) { with_bool(masked, [&](auto K) { tile(NB, M, F, K); }); });
+            else                    tile(NB, M, std::false_type(), std::false_type());
+        });
+    });
     return finish(hipSuccess);
 }
 
@@ -845,33 +811,16 @@ int bhwk_table_combine_tile(const BhwLaunch &l, const BhwCordicCfg &c, const Bhw
 int bhwk_runlength_window(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *d_table, int32_t *d_out)
 {
     if (!bhwk_runlength_applicable(c, w, d_out)) return (int)hipErrorInvalidValue;
-    BHW_SET_DEVICE(l);
     hipStream_t st = (hipStream_t)l.stream;
     const uint32_t H = 1u << (c.phi_width - 3);
     const dim3 grid(H / (kRlBlock * kRlRun)), block(kRlBlock);
-    const int mode = (w.combine != BHW_COMBINE_HLS) ? 2 : (c.ones_neg ? 1 : 0);
-    const bool narrow = c.dat_width <= 16;                       // coefficients fit int16: half-size LDS tile
-#define BHW_RL_NT_M(NT, M)                                                                                                     \
-    do {                                                                                                                       \
-        if (narrow) BHW_LAUNCH((k_runlength_window<NT, M, true>), grid, block, 0, st, c, w, (const int2 *)d_table, d_out);     \
-        else        BHW_LAUNCH((k_runlength_window<NT, M, false>), grid, block, 0, st, c, w, (const int2 *)d_table, d_out);    \
-    } while (0)
-#define BHW_RL_NT(NT)                                                                                                          \
-    do {                                                                                                                       \
-        if (mode == 0)      BHW_RL_NT_M(NT, 0);                                                                                \
-        else if (mode == 1) BHW_RL_NT_M(NT, 1);                                                                                \
-        else                BHW_RL_NT_M(NT, 2);                                                                                \
-    } while (0)
-    switch (w.n_terms) {
-    case 2: BHW_RL_NT(2); break;
-    case 3: BHW_RL_NT(3); break;
-    case 4: BHW_RL_NT(4); break;
-    case 5: BHW_RL_NT(5); break;
-    case 7: BHW_RL_NT(7); break;
-    default: return (int)hipErrorInvalidValue;
-    }
-#undef BHW_RL_NT
-#undef BHW_RL_NT_M
-    return finish(hipSuccess);
+    const bool listed = with_int<2, 3, 4, 5, 7>((int)w.n_terms, [&](auto NT) {
+        with_int_or_last<0, 1, 2>(mode_of(c, w), [&](auto M) {
+            with_bool(rl_narrow(c), [&](auto NARROW) {
+                launch(k_runlength_window<NT, M, NARROW>, grid, block, st, c, w, (const int2 *)d_table, d_out);
+            });
+        });
+    });
+    return listed ? finish(hipSuccess) : (int)hipErrorInvalidValue;
 }
 

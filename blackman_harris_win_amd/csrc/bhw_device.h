@@ -400,7 +400,6 @@ __device__ __forceinline__ void stage_lut(const BhwCordicCfg &cfg, T *lut_s)
 constexpr int kPrefixMax = 20;   // deepest rotation a 64-leaf group is followed to in phase 1
 constexpr int kGroupsPerWg = 64;    // phase 1: at most one group per lane of the first wave (plan.groups_per_wg <= 64)
 constexpr int kBuildThreads = 256;  // phase 2: four waves, 16 groups each
-constexpr int kHeadsMax = 40;       // residual format: cells of one workgroup (4096 entries >> 7 = 32) + 2
 
 struct BhwBuildPlan {
     uint32_t lut[32];    // the rescaled ROM as 32-bit words (entries fit: quarter circle <= 2^32)
@@ -846,7 +845,50 @@ inline void launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, hipStream_t 
     const hipError_t e = hipLaunchKernel(reinterpret_cast<const void *>(kernel), grid, block, ptrs, 0, st);
     if (e != hipSuccess && t_launch_err == hipSuccess) t_launch_err = e;
 }
-#define BHW_LAUNCH(kernel, grid, block, shmem, st, ...) launch(kernel, grid, block, st, __VA_ARGS__)
+
+// Instance choice at a launch: a run-time value becomes the compile-time constant of a listed template argument, so each kernel's
+// instances are listed once, where it is launched.  with_int<V0, V1, ...>(v, f) calls f(std::integral_constant<int, V>()) for the
+// listed V equal to v and returns true, or returns false if none is; with_int_or_last does the same with the last V taking every
+// value not listed; with_bool calls f(std::true_type()) or f(std::false_type()).  f is a lambda: inlined, this is the chain of
+// compares and branches the list spells, and instances are first used in list order.
+template <int V> using int_c = std::integral_constant<int, V>;
+
+template <int... Vs, typename F> inline bool with_int(int v, F &&f)
+{
+    return (... || (v == Vs && (f(int_c<Vs>()), true)));      // a left fold: clang instantiates a right fold's terms last to first
+}
+
+template <int V, int... Vs, typename F> inline void with_int_or_last(int v, F &&f)
+{
+    if constexpr (sizeof...(Vs) == 0) f(int_c<V>());
+    else if (v == V) f(int_c<V>());
+    else with_int_or_last<Vs...>(v, f);
+}
+
+template <typename F> inline void with_bool(bool b, F &&f)
+{
+    if (b) f(std::true_type());
+    else   f(std::false_type());
+}
+
+// CORDIC rotation counts and data widths the unrolled kernels are compiled for: with_int over [Lo, Hi]
+template <int Lo, int Hi, typename F> inline bool with_int_range(int v, F &&f)
+{
+    if constexpr (Lo > Hi) return false;
+    else if (v == Lo) { f(int_c<Lo>()); return true; }
+    else return with_int_range<Lo + 1, Hi>(v, f);
+}
+
+// The instances of a range_coeff kernel (k_range_combine, k_frames_table, k_ola_table): f(FMT, NT, MODE) for the form
+// bhwp_range_form chose -- FMT in 0, 1, 2, 3, 5, MODE in 0..2, NT in 3, 5, 7, chosen in that order (a value outside a list: its last)
+template <typename F> inline void with_range_form(int fmt, int nt, int mode, F &&f)
+{
+    with_int_or_last<0, 1, 2, 3, 5>(fmt, [&](auto FMT) {
+        with_int_or_last<0, 1, 2>(mode, [&](auto M) {
+            with_int_or_last<3, 5, 7>(nt, [&](auto NT) { f(FMT, NT, M); });
+        });
+    });
+}
 
 inline int finish(hipError_t e)
 {
@@ -857,5 +899,3 @@ inline int finish(hipError_t e)
 
 
 } // namespace
-
-#define BHW_SET_DEVICE(l) ((void)(l))

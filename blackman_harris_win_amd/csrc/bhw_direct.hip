@@ -123,60 +123,44 @@ __global__ __launch_bounds__(kBlock) void k_replicate4(const int32_t *__restrict
 int bhwk_direct(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, uint64_t n0, uint64_t count, int32_t *d_out)
 {
     if (!count) return 0;
-    BHW_SET_DEVICE(l);
     hipStream_t st = (hipStream_t)l.stream;
-    if (c.dat_width + c.out_shr <= 34 && c.n_iter >= 7) {   // |x| < 2^33, quarter circle <= 2^32: the mad-form rotation applies
+    const int form = direct_form(c);
+    if (form == 2) {
         const dim3 grid(grid_for(count)), block(kBlock);
-        switch (c.n_iter) {
-#define BHW_CASE(N) case N: BHW_LAUNCH(k_direct_fast<N>, grid, block, 0, st, c, w, n0, count, d_out); break;
-            BHW_CASE(7) BHW_CASE(8) BHW_CASE(9) BHW_CASE(10) BHW_CASE(11) BHW_CASE(12) BHW_CASE(13) BHW_CASE(14)
-            BHW_CASE(15) BHW_CASE(16) BHW_CASE(17) BHW_CASE(18) BHW_CASE(19) BHW_CASE(20) BHW_CASE(21) BHW_CASE(22)
-            BHW_CASE(23) BHW_CASE(24) BHW_CASE(25) BHW_CASE(26) BHW_CASE(27) BHW_CASE(28) BHW_CASE(29) BHW_CASE(30)
-            BHW_CASE(31) BHW_CASE(32)
-#undef BHW_CASE
-        default: return (int)hipErrorInvalidValue;
-        }
+        if (!with_int_range<7, 32>(c.n_iter, [&](auto N) { launch(k_direct_fast<N>, grid, block, st, c, w, n0, count, d_out); }))
+            return (int)hipErrorInvalidValue;
         return finish(hipSuccess);
     }
-    if (c.wide) BHW_LAUNCH(k_direct<int64_t>, dim3(grid_for(count)), dim3(kBlock), 0, st, c, w, n0, count, d_out);
-    else        BHW_LAUNCH(k_direct<int32_t>, dim3(grid_for(count)), dim3(kBlock), 0, st, c, w, n0, count, d_out);
+    if (form == 1) launch(k_direct<int64_t>, dim3(grid_for(count)), dim3(kBlock), st, c, w, n0, count, d_out);
+    else           launch(k_direct<int32_t>, dim3(grid_for(count)), dim3(kBlock), st, c, w, n0, count, d_out);
     return finish(hipSuccess);
 }
 
 int bhwk_sincos(const BhwLaunch &l, const BhwCordicCfg &c, uint64_t theta0, uint64_t count, int32_t *d_sin, int32_t *d_cos)
 {
     if (!count) return 0;
-    BHW_SET_DEVICE(l);
     hipStream_t st = (hipStream_t)l.stream;
+    const int form = direct_form(c);
     // One whole period from 2^16 phases on: the shared-prefix chains of the table build (one chain per first-quadrant angle, a
     // 64-leaf group's common rotations run once) with the four quadrant images written straight out -- a quarter of the chains of
     // the per-phase kernel and about half of their rotations.
-    if (c.dat_width + c.out_shr <= 34 && c.n_iter >= 7 && c.z_shr == 0 && c.phi_width >= 16 &&
-        count == (1ull << c.phi_width)) {
+    if (form == 2 && c.z_shr == 0 && c.phi_width >= 16 && count == (1ull << c.phi_width)) {
         return bhwk_sincos_sweep(l, c, theta0, d_sin, d_cos);
     }
-    if (c.dat_width + c.out_shr <= 34 && c.n_iter >= 7) {
+    if (form == 2) {
         const dim3 grid(grid_for(count)), block(kBlock);
-        switch (c.n_iter) {
-#define BHW_CASE(N) case N: BHW_LAUNCH(k_sincos_fast<N>, grid, block, 0, st, c, theta0, count, d_sin, d_cos); break;
-            BHW_CASE(7) BHW_CASE(8) BHW_CASE(9) BHW_CASE(10) BHW_CASE(11) BHW_CASE(12) BHW_CASE(13) BHW_CASE(14)
-            BHW_CASE(15) BHW_CASE(16) BHW_CASE(17) BHW_CASE(18) BHW_CASE(19) BHW_CASE(20) BHW_CASE(21) BHW_CASE(22)
-            BHW_CASE(23) BHW_CASE(24) BHW_CASE(25) BHW_CASE(26) BHW_CASE(27) BHW_CASE(28) BHW_CASE(29) BHW_CASE(30)
-            BHW_CASE(31) BHW_CASE(32)
-#undef BHW_CASE
-        default: return (int)hipErrorInvalidValue;
-        }
+        if (!with_int_range<7, 32>(c.n_iter, [&](auto N) { launch(k_sincos_fast<N>, grid, block, st, c, theta0, count, d_sin, d_cos); }))
+            return (int)hipErrorInvalidValue;
         return finish(hipSuccess);
     }
-    if (c.wide) BHW_LAUNCH(k_sincos<int64_t>, dim3(grid_for(count)), dim3(kBlock), 0, st, c, theta0, count, d_sin, d_cos);
-    else        BHW_LAUNCH(k_sincos<int32_t>, dim3(grid_for(count)), dim3(kBlock), 0, st, c, theta0, count, d_sin, d_cos);
+    if (form == 1) launch(k_sincos<int64_t>, dim3(grid_for(count)), dim3(kBlock), st, c, theta0, count, d_sin, d_cos);
+    else           launch(k_sincos<int32_t>, dim3(grid_for(count)), dim3(kBlock), st, c, theta0, count, d_sin, d_cos);
     return finish(hipSuccess);
 }
 
 int bhwk_replicate(const BhwLaunch &l, const int32_t *d_frame, uint64_t frame_len, uint32_t frames, int32_t *d_out)
 {
     if (!frames || !frame_len) return 0;
-    BHW_SET_DEVICE(l);
     hipStream_t st = (hipStream_t)l.stream;
     const bool vec = (frame_len % 4 == 0) && (((uintptr_t)d_frame | (uintptr_t)d_out) % 16 == 0);
     const uint64_t items = vec ? frame_len / 4 : frame_len;
@@ -187,8 +171,8 @@ int bhwk_replicate(const BhwLaunch &l, const int32_t *d_frame, uint64_t frame_le
     if (gy > frames) gy = frames;
     if (gy < 1) gy = 1;
     if (gy > 65535) gy = 65535;
-    if (vec) BHW_LAUNCH(k_replicate16, dim3(gx, gy), dim3(kBlock), 0, st, (const int4 *)d_frame, items, frames, (int4 *)d_out);
-    else     BHW_LAUNCH(k_replicate4, dim3(gx, gy), dim3(kBlock), 0, st, d_frame, items, frames, d_out);
+    if (vec) launch(k_replicate16, dim3(gx, gy), dim3(kBlock), st, (const int4 *)d_frame, items, frames, (int4 *)d_out);
+    else     launch(k_replicate4, dim3(gx, gy), dim3(kBlock), st, d_frame, items, frames, d_out);
     return finish(hipSuccess);
 }
 

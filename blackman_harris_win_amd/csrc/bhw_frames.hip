@@ -86,7 +86,7 @@ __device__ __forceinline__ void frames_apply(const FramesArgs &a, uint32_t k, ui
 }
 
 // Coefficient by the direct CORDIC chains.  FORM 0 / 1: the cordic_full chain of k_direct (T = int32_t, or int64_t where the state
-// needs more than 32 bits); FORM 2: the mad-form rotation where it applies (bhwk_frames picks it as bhwk_direct picks k_direct_fast).
+// needs more than 32 bits); FORM 2: the mad-form rotation where it applies (direct_form, the rule bhwk_direct picks k_direct_fast by).
 template <int FORM>
 __global__ __launch_bounds__(kFramesBlock) void k_frames_direct(BhwCordicCfg cfg, BhwWinCfg win, FramesArgs a)
 {
@@ -117,7 +117,6 @@ int bhwk_frames(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinCfg &w
                 const int32_t *d_x, int32_t *d_y, const int32_t *d_table)
 {
     if (!f->frames) return 0;
-    BHW_SET_DEVICE(l);
     hipStream_t st = (hipStream_t)l.stream;
     FramesArgs a;
     a.x = d_x;
@@ -132,37 +131,13 @@ int bhwk_frames(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinCfg &w
     a.io = f->channels == 1 ? 0u : ((((uintptr_t)d_x | (uintptr_t)d_y) % 8 == 0 && pl.y_stride % 2 == 0) ? 2u : 1u);
     const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y), block(kFramesBlock);
     if (!d_table) {
-        if (bhwp_frames_mad_form(c_in)) BHW_LAUNCH(k_frames_direct<2>, grid, block, 0, st, c_in, w, a);
-        else if (c_in.wide)             BHW_LAUNCH(k_frames_direct<1>, grid, block, 0, st, c_in, w, a);
-        else                            BHW_LAUNCH(k_frames_direct<0>, grid, block, 0, st, c_in, w, a);
+        with_int_or_last<2, 1, 0>(direct_form(c_in), [&](auto D) { launch(k_frames_direct<D>, grid, block, st, c_in, w, a); });
         return finish(hipSuccess);
     }
     const BhwCordicCfg c = table_layout(c_in);
     int fmt, nt, mode;
     if (!bhwp_range_form(c, w, &fmt, &nt, &mode)) return (int)hipErrorInvalidValue;   // every format a resident table holds has instances
     const void *tab = (const void *)d_table;
-#define BHW_FRAMES_F(F, NT, M) BHW_LAUNCH((k_frames_table<F, NT, M>), grid, block, 0, st, c, w, tab, a)
-#define BHW_FRAMES_NT(F, M)                                                                                              \
-    do {                                                                                                                 \
-        if (nt == 3)      BHW_FRAMES_F(F, 3, M);                                                                         \
-        else if (nt == 5) BHW_FRAMES_F(F, 5, M);                                                                         \
-        else              BHW_FRAMES_F(F, 7, M);                                                                         \
-    } while (0)
-#define BHW_FRAMES_M(F)                                                                                                  \
-    do {                                                                                                                 \
-        if (mode == 0)      BHW_FRAMES_NT(F, 0);                                                                         \
-        else if (mode == 1) BHW_FRAMES_NT(F, 1);                                                                         \
-        else                BHW_FRAMES_NT(F, 2);                                                                         \
-    } while (0)
-    switch (fmt) {
-    case 0: BHW_FRAMES_M(0); break;
-    case 1: BHW_FRAMES_M(1); break;
-    case 2: BHW_FRAMES_M(2); break;
-    case 3: BHW_FRAMES_M(3); break;
-    default: BHW_FRAMES_M(5); break;
-    }
-#undef BHW_FRAMES_M
-#undef BHW_FRAMES_NT
-#undef BHW_FRAMES_F
+    with_range_form(fmt, nt, mode, [&](auto F, auto NT, auto M) { launch(k_frames_table<F, NT, M>, grid, block, st, c, w, tab, a); });
     return finish(hipSuccess);
 }

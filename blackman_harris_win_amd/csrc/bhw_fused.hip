@@ -54,11 +54,6 @@ struct BhwFoldPlan {
     uint32_t wg_first[kFoldRunsMax + 1];     // first workgroup of each run; [n_runs] = grid size
 };
 
-__host__ __device__ constexpr int fold_chains(int n_terms)      // first-quadrant chains per ring lane
-{
-    return n_terms == 2 ? 2 : n_terms == 3 ? 3 : n_terms == 4 ? 5 : n_terms == 5 ? 6 : 9;
-}
-
 
 // lutv: the rescaled ROM spread over the lanes of the wave (lane k holds lut[k]); v_readlane_b32 with the scalar rotation
 // counter fetches a word in a few cycles.  (As a scalar load from the kernel arguments every rotation waited ~100+ cycles for
@@ -654,7 +649,6 @@ int bhwk_fold_direct(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg 
 {
     if (!n_runs) return 0;
     if (n_runs > (uint32_t)kFoldRunsMax || !bhwk_fold_direct_applicable(c)) return (int)hipErrorInvalidValue;
-    BHW_SET_DEVICE(l);
     hipStream_t st = (hipStream_t)l.stream;
     BhwFoldPlan plan;
     memset(&plan, 0, sizeof plan);
@@ -678,7 +672,7 @@ int bhwk_fold_direct(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg 
     for (uint32_t i = 0; i < n_runs; ++i) total += runs[i].r_end - runs[i].r0;
     // form of the kernel for this many lanes (bhwp_fold_form, bhw_plan.cpp: the measurements behind the thresholds are quoted there)
     const int form = bhwp_fold_form(c, w, total);
-    const bool split = form == BHWP_FOLD_SPLIT, narrow = form == BHWP_FOLD_NARROW, lockstep = form == BHWP_FOLD_LOCKSTEP;
+    const bool split = form == BHWP_FOLD_SPLIT;
     // short launches: one wave per workgroup spreads the few waves over more CUs
     // (one wave per workgroup for the longer launches of the barrier-free narrow form too: no gain, profiles/r04_short_windows_store_scope.txt)
     const uint32_t block = total <= 64u * 1024u ? 64u : (uint32_t)kFoldBlock;
@@ -694,7 +688,7 @@ int bhwk_fold_direct(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg 
     plan.run0_r0 = plan.r0[0];
     plan.run0_end = plan.r_end[0];
     if (!wg) return 0;
-    const int mode = (w.combine != BHW_COMBINE_HLS) ? 2 : (c.ones_neg ? 1 : 0);
+    const int mode = mode_of(c, w);
     // batched identical frames: the frames are divided over grid.y -- enough rows that the launch has ~4 waves per SIMD to keep
     // the store stream going (each row computes the period again: microseconds of latency, no traffic)
     uint32_t gy = 1u;
@@ -707,7 +701,7 @@ int bhwk_fold_direct(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg 
     }
     const dim3 grid(wg, gy), blk(block);
     plan.k24 = bhwp_fold_k24(c);
-    const uint32_t split_waves = (uint32_t)(w.n_terms == 2 ? 2 : w.n_terms == 3 ? 3 : w.n_terms == 4 ? 5 : w.n_terms == 5 ? 6 : 9);   // fold_chains(): one chain per wave
+    const uint32_t split_waves = (uint32_t)fold_chains((int)w.n_terms);   // one chain per wave
     dim3 grid_s(0), blk_s(64u * split_waves);
     if (split) {
         uint32_t wgs = 0;
@@ -718,29 +712,14 @@ int bhwk_fold_direct(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg 
         plan.wg_first[n_runs] = wgs;
         grid_s = dim3(wgs);
     }
-#define BHW_FD_NT_M(NT, M)                                                                                  \
-    do {                                                                                                    \
-        if (split) BHW_LAUNCH((k_fold_split<NT, M, fold_chains(NT)>), grid_s, blk_s, 0, st, w, plan, d_out); \
-        else if (narrow)   BHW_LAUNCH((k_fold_direct<NT, M, 2>), grid, blk, 0, st, w, plan, d_out);      \
-        else if (lockstep) BHW_LAUNCH((k_fold_direct<NT, M, 1>), grid, blk, 0, st, w, plan, d_out);      \
-        else               BHW_LAUNCH((k_fold_direct<NT, M, 0>), grid, blk, 0, st, w, plan, d_out);      \
-    } while (0)
-#define BHW_FD_NT(NT)                                                                                       \
-    do {                                                                                                    \
-        if (mode == 0)      BHW_FD_NT_M(NT, 0);                                                             \
-        else if (mode == 1) BHW_FD_NT_M(NT, 1);                                                             \
-        else                BHW_FD_NT_M(NT, 2);                                                             \
-    } while (0)
-    switch (w.n_terms) {
-    case 2: BHW_FD_NT(2); break;
-    case 3: BHW_FD_NT(3); break;
-    case 4: BHW_FD_NT(4); break;
-    case 5: BHW_FD_NT(5); break;
-    case 7: BHW_FD_NT(7); break;
-    default: return (int)hipErrorInvalidValue;
-    }
-#undef BHW_FD_NT
-#undef BHW_FD_NT_M
-    return finish(hipSuccess);
+    const bool listed = with_int<2, 3, 4, 5, 7>((int)w.n_terms, [&](auto NT) {
+        with_int_or_last<0, 1, 2>(mode, [&](auto M) {
+            with_int_or_last<BHWP_FOLD_SPLIT, BHWP_FOLD_NARROW, BHWP_FOLD_LOCKSTEP, BHWP_FOLD_SEQUENTIAL>(form, [&](auto F) {
+                if constexpr (F == BHWP_FOLD_SPLIT) launch(k_fold_split<NT, M, fold_chains(NT)>, grid_s, blk_s, st, w, plan, d_out);
+                else                                launch(k_fold_direct<NT, M, F>, grid, blk, st, w, plan, d_out);
+            });
+        });
+    });
+    return listed ? finish(hipSuccess) : (int)hipErrorInvalidValue;
 }
 

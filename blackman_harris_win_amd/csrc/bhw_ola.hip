@@ -139,7 +139,7 @@ __device__ __forceinline__ void ola_io(const OlaArgs &a, Coeff coeff)
 }
 
 // Coefficient by the direct CORDIC chains, as k_frames_direct: FORM 0 / 1 the cordic_full chain of k_direct (T = int32_t, or int64_t
-// where the state needs more than 32 bits), FORM 2 the mad-form rotation where it applies (bhwp_frames_mad_form).
+// where the state needs more than 32 bits), FORM 2 the mad-form rotation where it applies (direct_form).
 template <int FORM, int IO>
 __global__ __launch_bounds__(kOlaBlock) void k_ola_direct(BhwCordicCfg cfg, BhwWinCfg win, OlaArgs a)
 {
@@ -169,7 +169,6 @@ int bhwk_ola(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinCfg &w, c
              const int32_t *d_y, int32_t *d_x, const int32_t *d_table)
 {
     if (!o->count) return 0;
-    BHW_SET_DEVICE(l);
     hipStream_t st = (hipStream_t)l.stream;
     OlaArgs a;
     a.y = d_y;
@@ -192,56 +191,18 @@ int bhwk_ola(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinCfg &w, c
     a.shift = o->shift;
     a.io = o->channels == 1 ? 0u : ((((uintptr_t)d_y | (uintptr_t)d_x) % 8 == 0 && pl.y_stride % 2 == 0) ? 2u : 1u);
     const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y), block(kOlaBlock);
-#define BHW_OLA_IO(LAUNCH)                                                                                               \
-    do {                                                                                                                 \
-        if (a.io == 0)      LAUNCH(0);                                                                                   \
-        else if (a.io == 1) LAUNCH(1);                                                                                   \
-        else                LAUNCH(2);                                                                                   \
-    } while (0)
     if (!d_table) {
-        const int form = bhwp_frames_mad_form(c_in) ? 2 : c_in.wide ? 1 : 0;
-#define BHW_OLA_D(IO)                                                                                                    \
-    do {                                                                                                                 \
-        if (form == 2)      BHW_LAUNCH((k_ola_direct<2, IO>), grid, block, 0, st, c_in, w, a);                            \
-        else if (form == 1) BHW_LAUNCH((k_ola_direct<1, IO>), grid, block, 0, st, c_in, w, a);                            \
-        else                BHW_LAUNCH((k_ola_direct<0, IO>), grid, block, 0, st, c_in, w, a);                            \
-    } while (0)
-        BHW_OLA_IO(BHW_OLA_D);
-#undef BHW_OLA_D
+        with_int_or_last<0, 1, 2>(a.io, [&](auto IO) {
+            with_int_or_last<2, 1, 0>(direct_form(c_in), [&](auto D) { launch(k_ola_direct<D, IO>, grid, block, st, c_in, w, a); });
+        });
         return finish(hipSuccess);
     }
     const BhwCordicCfg c = table_layout(c_in);
     int fmt, nt, mode;
     if (!bhwp_range_form(c, w, &fmt, &nt, &mode)) return (int)hipErrorInvalidValue;   // every format a resident table holds has instances
     const void *tab = (const void *)d_table;
-#define BHW_OLA_F(F, NT, M)                                                                                              \
-    do {                                                                                                                 \
-        if (a.io == 0)      BHW_LAUNCH((k_ola_table<F, NT, M, 0>), grid, block, 0, st, c, w, tab, a);                     \
-        else if (a.io == 1) BHW_LAUNCH((k_ola_table<F, NT, M, 1>), grid, block, 0, st, c, w, tab, a);                     \
-        else                BHW_LAUNCH((k_ola_table<F, NT, M, 2>), grid, block, 0, st, c, w, tab, a);                     \
-    } while (0)
-#define BHW_OLA_NT(F, M)                                                                                                 \
-    do {                                                                                                                 \
-        if (nt == 3)      BHW_OLA_F(F, 3, M);                                                                            \
-        else if (nt == 5) BHW_OLA_F(F, 5, M);                                                                            \
-        else              BHW_OLA_F(F, 7, M);                                                                            \
-    } while (0)
-#define BHW_OLA_M(F)                                                                                                     \
-    do {                                                                                                                 \
-        if (mode == 0)      BHW_OLA_NT(F, 0);                                                                            \
-        else if (mode == 1) BHW_OLA_NT(F, 1);                                                                            \
-        else                BHW_OLA_NT(F, 2);                                                                            \
-    } while (0)
-    switch (fmt) {
-    case 0: BHW_OLA_M(0); break;
-    case 1: BHW_OLA_M(1); break;
-    case 2: BHW_OLA_M(2); break;
-    case 3: BHW_OLA_M(3); break;
-    default: BHW_OLA_M(5); break;
-    }
-#undef BHW_OLA_M
-#undef BHW_OLA_NT
-#undef BHW_OLA_F
-#undef BHW_OLA_IO
+    with_range_form(fmt, nt, mode, [&](auto F, auto NT, auto M) {
+        with_int_or_last<0, 1, 2>(a.io, [&](auto IO) { launch(k_ola_table<F, NT, M, IO>, grid, block, st, c, w, tab, a); });
+    });
     return finish(hipSuccess);
 }

@@ -55,8 +55,6 @@ uint32_t inv_mod_pow2(uint32_t a, uint32_t log2m)
     return log2m >= 32 ? x : (x & ((1u << log2m) - 1u));
 }
 
-int mode_of(const BhwCordicCfg &c, const BhwWinCfg &w) { return (w.combine != BHW_COMBINE_HLS) ? 2 : (c.ones_neg ? 1 : 0); }
-
 } // namespace
 
 int bhwp_fail(int code, const char *fmt, ...)
@@ -717,7 +715,7 @@ int bhwp_describe_from_table(const bhw_params *p, const BhwCordicCfg &ct, bool t
     bhwk_describe_table(c, w, tiled || t.images, t.images, build, combine, sizeof build);
     if (bhwk_runlength_applicable(c, w, nullptr))
         snprintf(period, sizeof period, "k_runlength_window<%u,%d,%s> (16-byte aligned output; else %s)", p->n_terms, mode_of(c, w),
-                 c.dat_width <= 16 ? "true" : "false", combine);
+                 rl_narrow(c) ? "true" : "false", combine);
     else snprintf(period, sizeof period, "%s", combine);
     const uint64_t head = (N - n0 % N) % N;
     const uint64_t periods = t.has_period ? (count - head) / N : 0, tail = t.has_period ? count - head - periods * N : 0;
@@ -825,7 +823,7 @@ int bhwp_describe_frames(const bhw_params *p, const BhwCordicCfg *ct, const bhw_
     } else {
         BhwCordicCfg c;
         bhwp_resolve_cordic(p, c);
-        snprintf(kern, sizeof kern, "k_frames_direct<%d>", bhwp_frames_mad_form(c) ? 2 : c.wide ? 1 : 0);
+        snprintf(kern, sizeof kern, "k_frames_direct<%d>", direct_form(c));
     }
     snprintf(buf, len, "frames kernel: %s, %u channel%s, G = %llu frames per lane, grid %llu x %llu x %u lanes (%u along k)", kern,
              f->channels, f->channels == 2 ? "s" : "", (unsigned long long)pl.group, (unsigned long long)pl.grid_x,
@@ -927,7 +925,7 @@ int bhwp_describe_ola(const bhw_params *p, const BhwCordicCfg *ct, const bhw_ola
     } else {
         BhwCordicCfg c;
         bhwp_resolve_cordic(p, c);
-        snprintf(kern, sizeof kern, "k_ola_direct<%d>", bhwp_frames_mad_form(c) ? 2 : c.wide ? 1 : 0);
+        snprintf(kern, sizeof kern, "k_ola_direct<%d>", direct_form(c));
     }
     snprintf(buf, len, "overlap-add %s: %s, %u channel%s, Q = %u hops per lane, up to %llu frames per output, grid %llu x %llu x %u lanes "
              "(%u along r, %u along q)", pl.route == BHWP_OLA_TABLE ? "table" : "direct", kern, o->channels, o->channels == 2 ? "s" : "",
@@ -1077,13 +1075,13 @@ int bhw_describe_plan(const bhw_params *p, uint64_t n0, uint64_t count, const bh
     bhwp_resolve_window(p, w);
     const uint32_t algo = bhwp_pick_algo(p, c, w, n0, count, ex ? ex->algo : (uint32_t)BHW_ALGO_AUTO);
     if (algo == BHW_ALGO_DIRECT) {
-        snprintf(buf, len, "direct: %s", (c.dat_width + c.out_shr <= 34 && c.n_iter >= 7) ? "k_direct_fast" : "k_direct");
+        snprintf(buf, len, "direct: %s", direct_form(c) == 2 ? "k_direct_fast" : "k_direct");
         return BHW_OK;
     }
     if (algo == BHW_ALGO_FUSED) {
         // one launch over the whole ring [0, N/8) per period: the form bhwk_fold_direct picks for that many lanes
         const int form = bhwp_fold_form(c, w, 1ull << (p->phi_width - 3));
-        if (form == BHWP_FOLD_SPLIT) snprintf(buf, len, "fused: k_fold_split<%u,%d,%u> (+ k_direct_fast on ragged ends)", p->n_terms, mode_of(c, w), p->n_terms == 2 ? 2u : p->n_terms == 3 ? 3u : p->n_terms == 4 ? 5u : p->n_terms == 5 ? 6u : 9u);
+        if (form == BHWP_FOLD_SPLIT) snprintf(buf, len, "fused: k_fold_split<%u,%d,%u> (+ k_direct_fast on ragged ends)", p->n_terms, mode_of(c, w), (unsigned)fold_chains((int)p->n_terms));
         else snprintf(buf, len, "fused: k_fold_direct<%u,%d,%d> (+ k_direct_fast on ragged ends)", p->n_terms, mode_of(c, w), form);
         return BHW_OK;
     }
@@ -1096,7 +1094,7 @@ int bhw_describe_plan(const bhw_params *p, uint64_t n0, uint64_t count, const bh
     bhwk_describe_table(c, w, t.tiled, t.images, build, combine, sizeof build);
     if (period && c.tab_dlog == 0 && bhwk_runlength_applicable(c, w, nullptr))     // generate_impl's period(): dropped phase bits
         snprintf(combine, sizeof combine, "k_runlength_window<%u,%d,%s> (16-byte aligned output; else k_table_combine_fold_t)", p->n_terms,
-                 mode_of(c, w), c.dat_width <= 16 ? "true" : "false");
+                 mode_of(c, w), rl_narrow(c) ? "true" : "false");
     snprintf(buf, len, "table[%s%s]: %s + %s%s", bhwp_format_name(c.tab_dlog), fw.n_open ? ", unverified" : "", build, (period || t.images) ? combine : "k_table_combine",
              t.images ? " (image subset)" : period && count != (1ull << p->phi_width) ? " (+ k_table_combine / k_replicate on the rest)" : "");
     return BHW_OK;

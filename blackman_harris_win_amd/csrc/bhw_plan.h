@@ -55,6 +55,17 @@ constexpr int kRlBlock = 64;
 constexpr int kFoldRunsMax = 32;    // fused kernel: runs per launch, threads per workgroup
 constexpr int kFoldBlock = 256;
 
+// Kernel forms: each rule is read by the launcher, as a template argument, and by the describe strings that name the instance.
+// cosine-sum rule of the combine kernels (MODE): 0 HLS rule, 1 HLS rule with the one's-complement quadrant map (cpp model), 2 VHDL rule
+inline int mode_of(const BhwCordicCfg &c, const BhwWinCfg &w) { return (w.combine != BHW_COMBINE_HLS) ? 2 : (c.ones_neg ? 1 : 0); }
+// direct CORDIC (k_direct, k_sincos, k_frames_direct, k_ola_direct): 2 the mad-form rotation (|x| < 2^33, quarter circle <= 2^32;
+// k_direct_fast, k_sincos_fast), else 1 the 64-bit state or 0 the 32-bit state
+inline int direct_form(const BhwCordicCfg &c) { return (c.dat_width + c.out_shr <= 34 && c.n_iter >= 7) ? 2 : c.wide ? 1 : 0; }
+// run-length kernel (k_runlength_window NARROW): coefficients fit int16, half-size LDS tile
+inline bool rl_narrow(const BhwCordicCfg &c) { return c.dat_width <= 16; }
+// fused kernel, split form (k_fold_split NCH): first-quadrant chains per ring lane, one wave each
+BHW_HD constexpr int fold_chains(int n_terms) { return n_terms == 2 ? 2 : n_terms == 3 ? 3 : n_terms == 4 ? 5 : n_terms == 5 ? 6 : 9; }
+
 struct BhwTilePlan {
     uint32_t offs[16];   // (i3*inv3 + i5*inv5) mod ring, index i3 + 3*i5; padded by repeating the last run
     uint32_t n_tiles;    // tiles that cover the ring once
@@ -179,8 +190,6 @@ int  bhwp_frames_checks(const bhw_params *p, const bhw_frames *f, const void *d_
 BhwFramesPlan bhwp_frames_plan(const bhw_params *p, const bhw_frames *f, bool from_table, int force_route = -1);
 // bhw_apply_frames_describe: ct = the resident table's resolved configuration (format and layout set), or NULL for the library call
 int  bhwp_describe_frames(const bhw_params *p, const BhwCordicCfg *ct, const bhw_frames *f, char *buf, uint64_t len);
-// k_frames_direct in the mad-form rotation of k_direct_fast (the same condition as bhwk_direct's): form 2, else 1 (64-bit state) or 0
-inline bool bhwp_frames_mad_form(const BhwCordicCfg &c) { return c.dat_width + c.out_shr <= 34 && c.n_iter >= 7; }
 // the frames kernel of a plan (bhw_frames.hip): d_table NULL = k_frames_direct, else k_frames_table over the resident table of c
 int  bhwk_frames(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwFramesPlan &pl, const bhw_frames *f,
                  const int32_t *d_x, int32_t *d_y, const int32_t *d_table);

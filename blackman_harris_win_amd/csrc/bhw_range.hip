@@ -35,32 +35,11 @@ int bhwk_range_combine(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWi
     if (!count) return 0;
     int fmt, nt, mode;
     if (!bhwp_range_form(c, w, &fmt, &nt, &mode)) return bhwk_table_combine(l, c, w, d_table, n0, count, d_out);
-    BHW_SET_DEVICE(l);
     hipStream_t st = (hipStream_t)l.stream;
     const dim3 grid(grid_for(count)), block(kBlock);
     const void *tab = (const void *)d_table;
-#define BHW_RANGE_F(F, NT, M) BHW_LAUNCH((k_range_combine<F, NT, M>), grid, block, 0, st, c, w, tab, n0, count, d_out)
-#define BHW_RANGE_NT(F, M)                                                                                               \
-    do {                                                                                                                 \
-        if (nt == 3)      BHW_RANGE_F(F, 3, M);                                                                          \
-        else if (nt == 5) BHW_RANGE_F(F, 5, M);                                                                          \
-        else              BHW_RANGE_F(F, 7, M);                                                                          \
-    } while (0)
-#define BHW_RANGE_M(F)                                                                                                   \
-    do {                                                                                                                 \
-        if (mode == 0)      BHW_RANGE_NT(F, 0);                                                                          \
-        else if (mode == 1) BHW_RANGE_NT(F, 1);                                                                          \
-        else                BHW_RANGE_NT(F, 2);                                                                          \
-    } while (0)
-    switch (fmt) {
-    case 0: BHW_RANGE_M(0); break;
-    case 1: BHW_RANGE_M(1); break;
-    case 2: BHW_RANGE_M(2); break;
-    case 3: BHW_RANGE_M(3); break;
-    default: BHW_RANGE_M(5); break;
-    }
-#undef BHW_RANGE_M
-#undef BHW_RANGE_NT
-#undef BHW_RANGE_F
+    with_range_form(fmt, nt, mode, [&](auto F, auto NT, auto M) {
+        launch(k_range_combine<F, NT, M>, grid, block, st, c, w, tab, n0, count, d_out);
+    });
     return finish(hipSuccess);
 }

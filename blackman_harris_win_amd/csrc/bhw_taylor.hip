@@ -302,14 +302,12 @@ __global__ __launch_bounds__(kBlock) void k_taylor_sincos(BhwTaylorCfg t, uint64
 int bhwk_taylor_window(const BhwLaunch &l, const BhwTaylorCfg &t, const BhwWinCfg &w, uint64_t n0, uint64_t count, int32_t *d_out)
 {
     if (!count) return 0;
-    BHW_SET_DEVICE(l);
-    BHW_LAUNCH(k_taylor_window, dim3(grid_for(count)), dim3(kBlock), 0, (hipStream_t)l.stream, t, w, n0, count, d_out);
+    launch(k_taylor_window, dim3(grid_for(count)), dim3(kBlock), (hipStream_t)l.stream, t, w, n0, count, d_out);
     return finish(hipSuccess);
 }
 
 int bhwk_taylor_window_fold(const BhwLaunch &l, const BhwTaylorCfg &t, const BhwWinCfg &w, int32_t *d_out)
 {
-    BHW_SET_DEVICE(l);
     const uint32_t E = 1u << (t.phi_width - 2);
     // dat_width <= 16 with weights inside the W-bit range: every product and sum fits int32
     bool narrow = t.dat_width <= 16;
@@ -320,43 +318,31 @@ int bhwk_taylor_window_fold(const BhwLaunch &l, const BhwTaylorCfg &t, const Bhw
     if (blocks > 4096u) blocks = 4096u;
     const dim3 grid(blocks);
     hipStream_t st = (hipStream_t)l.stream;
-#define BHW_TAYLOR_FOLD(ARITH, COMBINE, NT) BHW_LAUNCH((k_taylor_window_fold<ARITH, COMBINE, NT, true>), grid, dim3(kBlock), 0, st, t, w, d_out)
-    const bool vhdl = w.combine == BHW_COMBINE_VHDL;
     // every generator in use (PHASE_WIDTH - v, v <= vmax) on the 1st-order-correction path, ROM in LDS
     const int vmax = w.n_terms > 4 ? 2 : w.n_terms > 2 ? 1 : 0;
     const bool fast = (1u << t.lut_size) <= (uint32_t)kTaylorRomLds && (int)t.phi_width - vmax - (int)t.lut_size > 2;
     if (!fast) {
         // a quarter-wave ROM beyond LDS (LUT_SIZE > 12) or a generator without the correction stage (PHASE_WIDTH - LUT_SIZE <= 3):
         // the general one-lane-per-coefficient kernel over the period (the fold kernel is instantiated in its usual form only)
-        BHW_LAUNCH(k_taylor_window, dim3(grid_for(4ull * E)), dim3(kBlock), 0, st, t, w, (uint64_t)0, (uint64_t)(4ull * E), d_out);
+        launch(k_taylor_window, dim3(grid_for(4ull * E)), dim3(kBlock), st, t, w, (uint64_t)0, (uint64_t)(4ull * E), d_out);
         return finish(hipSuccess);
     }
     // 32-bit arithmetic: int16-sized operands (W <= 16), or the wide rounding variant with its shift inside one mul_hi
     const int arith = narrow ? 1 : (fast && t.dat_width >= 19 && t.xshift >= 24 && t.xshift <= 32) ? 2 : 0;
-#define BHW_TAYLOR_FOLD_NT(NT)                                                                                      \
-    do {                                                                                                            \
-        if (arith == 1)      { if (vhdl) BHW_TAYLOR_FOLD(1, BHW_COMBINE_VHDL, NT); else BHW_TAYLOR_FOLD(1, BHW_COMBINE_HLS, NT); } \
-        else if (arith == 2) { if (vhdl) BHW_TAYLOR_FOLD(2, BHW_COMBINE_VHDL, NT); else BHW_TAYLOR_FOLD(2, BHW_COMBINE_HLS, NT); } \
-        else                 { if (vhdl) BHW_TAYLOR_FOLD(0, BHW_COMBINE_VHDL, NT); else BHW_TAYLOR_FOLD(0, BHW_COMBINE_HLS, NT); } \
-    } while (0)
-    switch (w.n_terms) {
-    case 2: BHW_TAYLOR_FOLD_NT(2); break;
-    case 3: BHW_TAYLOR_FOLD_NT(3); break;
-    case 4: BHW_TAYLOR_FOLD_NT(4); break;
-    case 5: BHW_TAYLOR_FOLD_NT(5); break;
-    case 7: BHW_TAYLOR_FOLD_NT(7); break;
-    default: return (int)hipErrorInvalidValue;
-    }
-#undef BHW_TAYLOR_FOLD_NT
-#undef BHW_TAYLOR_FOLD
-    return finish(hipSuccess);
+    const bool listed = with_int<2, 3, 4, 5, 7>((int)w.n_terms, [&](auto NT) {
+        with_int_or_last<1, 2, 0>(arith, [&](auto A) {
+            with_int_or_last<BHW_COMBINE_VHDL, BHW_COMBINE_HLS>((int)w.combine, [&](auto C) {
+                launch(k_taylor_window_fold<A, C, NT, true>, grid, dim3(kBlock), st, t, w, d_out);
+            });
+        });
+    });
+    return listed ? finish(hipSuccess) : (int)hipErrorInvalidValue;
 }
 
 int bhwk_taylor_sincos(const BhwLaunch &l, const BhwTaylorCfg &t, uint64_t theta0, uint64_t count, int32_t *d_sin, int32_t *d_cos)
 {
     if (!count) return 0;
-    BHW_SET_DEVICE(l);
-    BHW_LAUNCH(k_taylor_sincos, dim3(grid_for(count)), dim3(kBlock), 0, (hipStream_t)l.stream, t, theta0, count, d_sin, d_cos);
+    launch(k_taylor_sincos, dim3(grid_for(count)), dim3(kBlock), (hipStream_t)l.stream, t, theta0, count, d_sin, d_cos);
     return finish(hipSuccess);
 }
 

@@ -587,28 +587,26 @@ static_assert(kT9D == kTile9CellLog, "the planner names the cell size");
 
 int bhwk_tile9(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwTilePlan &tp, uint32_t tile_count, const int32_t *d_table, int32_t *d_out)
 {
-    BHW_SET_DEVICE(l);
     hipStream_t st = (hipStream_t)l.stream;
-    const int mode = (w.combine != BHW_COMBINE_HLS) ? 2 : (c.ones_neg ? 1 : 0);
+    const int mode = mode_of(c, w);
     const dim3 grid(tile_count * (uint32_t)(kTileThreads / kT9Threads)), block(kT9Threads);
     const int fmt = fmt_of(c.tab_dlog);
     // instances: plain nibbles for every cosine-sum rule; nibble + escapes for the VHDL rule at 32 bits only (bhwk_tile9_applicable)
-#define BHW_T9(M, F, V)                                                                                                   \
-    do {                                                                                                                 \
-        if (w.apply_x) BHW_LAUNCH((k_tile9<M, F, true, V>), grid, block, 0, st, c, w, tp, (const void *)d_table, d_out);  \
-        else           BHW_LAUNCH((k_tile9<M, F, false, V>), grid, block, 0, st, c, w, tp, (const void *)d_table, d_out); \
-    } while (0)
+    auto t9 = [&](auto M, auto F, auto V) {
+        with_bool(w.apply_x != nullptr, [&](auto A) {
+            launch(k_tile9<M, F, A, V>, grid, block, st, c, w, tp, (const void *)d_table, d_out);
+        });
+    };
     const bool v32 = c.dat_width == 32u;
 #ifdef BHW_T9_ALLFMT5
-    if (fmt == 5 && mode == 0) BHW_T9(0, 5, false);
-    else if (fmt == 5 && mode == 1) BHW_T9(1, 5, false);
+    if (fmt == 5 && mode == 0) t9(int_c<0>(), int_c<5>(), std::false_type());
+    else if (fmt == 5 && mode == 1) t9(int_c<1>(), int_c<5>(), std::false_type());
     else
 #endif
-    if (fmt == 5) { if (mode == 2 && v32) BHW_T9(2, 5, true); else return (int)hipErrorInvalidValue; }
-    else if (mode == 0) BHW_T9(0, 3, false);
-    else if (mode == 1) BHW_T9(1, 3, false);
-    else if (v32) BHW_T9(2, 3, true);
-    else BHW_T9(2, 3, false);
-#undef BHW_T9
+    if (fmt == 5) { if (mode == 2 && v32) t9(int_c<2>(), int_c<5>(), std::true_type()); else return (int)hipErrorInvalidValue; }
+    else if (mode == 0) t9(int_c<0>(), int_c<3>(), std::false_type());
+    else if (mode == 1) t9(int_c<1>(), int_c<3>(), std::false_type());
+    else if (v32) t9(int_c<2>(), int_c<3>(), std::true_type());
+    else t9(int_c<2>(), int_c<3>(), std::false_type());
     return finish(hipSuccess);
 }

@@ -167,40 +167,27 @@ __global__ __launch_bounds__(kBlock) void k_atan2(BhwAtan2Cfg c, uint64_t count,
 int bhwk_sincos_prerot(const BhwLaunch &l, const BhwPrerotCfg &c, uint64_t theta0, uint64_t count, int32_t *d_sin, int32_t *d_cos)
 {
     if (!count) return 0;
-    BHW_SET_DEVICE(l);
     hipStream_t st = (hipStream_t)l.stream;
     if (c.phi_width >= 16 && c.phi_width <= 30 && count == (1ull << c.phi_width)) {      // one whole period: shared rotation prefixes
         const uint32_t groups = 1u << (c.phi_width - 6);
         const dim3 grid((groups + kGroupsPerWg - 1) / kGroupsPerWg), block(kBuildThreads);
         const uint32_t th0 = (uint32_t)(theta0 & ((1ull << c.phi_width) - 1ull));
-        switch (c.dat_width) {
-#define BHW_CASE(N) case N: BHW_LAUNCH(k_prerot_sweep<N>, grid, block, 0, st, c, th0, d_sin, d_cos); break;
-            BHW_CASE(8) BHW_CASE(9) BHW_CASE(10) BHW_CASE(11) BHW_CASE(12) BHW_CASE(13) BHW_CASE(14) BHW_CASE(15) BHW_CASE(16)
-            BHW_CASE(17) BHW_CASE(18) BHW_CASE(19) BHW_CASE(20) BHW_CASE(21) BHW_CASE(22) BHW_CASE(23) BHW_CASE(24)
-            BHW_CASE(25) BHW_CASE(26) BHW_CASE(27) BHW_CASE(28) BHW_CASE(29) BHW_CASE(30) BHW_CASE(31) BHW_CASE(32)
-#undef BHW_CASE
-        default: return (int)hipErrorInvalidValue;
-        }
+        if (!with_int_range<8, 32>(c.dat_width, [&](auto N) { launch(k_prerot_sweep<N>, grid, block, st, c, th0, d_sin, d_cos); }))
+            return (int)hipErrorInvalidValue;
         return finish(hipSuccess);
     }
     const dim3 grid(grid_for(count)), block(kBlock);
-    switch (c.dat_width) {                                              // DATA_WIDTH stages, unrolled
-#define BHW_CASE(N) case N: BHW_LAUNCH(k_sincos_prerot<N>, grid, block, 0, st, c, theta0, count, d_sin, d_cos); break;
-        BHW_CASE(8) BHW_CASE(9) BHW_CASE(10) BHW_CASE(11) BHW_CASE(12) BHW_CASE(13) BHW_CASE(14) BHW_CASE(15) BHW_CASE(16)
-        BHW_CASE(17) BHW_CASE(18) BHW_CASE(19) BHW_CASE(20) BHW_CASE(21) BHW_CASE(22) BHW_CASE(23) BHW_CASE(24)
-        BHW_CASE(25) BHW_CASE(26) BHW_CASE(27) BHW_CASE(28) BHW_CASE(29) BHW_CASE(30) BHW_CASE(31) BHW_CASE(32)
-#undef BHW_CASE
-    default: return (int)hipErrorInvalidValue;
-    }
+    // DATA_WIDTH stages, unrolled
+    if (!with_int_range<8, 32>(c.dat_width, [&](auto N) { launch(k_sincos_prerot<N>, grid, block, st, c, theta0, count, d_sin, d_cos); }))
+        return (int)hipErrorInvalidValue;
     return finish(hipSuccess);
 }
 
 int bhwk_atan2(const BhwLaunch &l, const BhwAtan2Cfg &c, uint64_t count, const int32_t *d_x, const int32_t *d_y, int32_t *d_phi)
 {
     if (!count) return 0;
-    BHW_SET_DEVICE(l);
-    if (c.angle_width + c.precision <= 32u) BHW_LAUNCH(k_atan2<uint32_t>, dim3(grid_for(count)), dim3(kBlock), 0, (hipStream_t)l.stream, c, count, d_x, d_y, d_phi);
-    else                                    BHW_LAUNCH(k_atan2<uint64_t>, dim3(grid_for(count)), dim3(kBlock), 0, (hipStream_t)l.stream, c, count, d_x, d_y, d_phi);
+    if (c.angle_width + c.precision <= 32u) launch(k_atan2<uint32_t>, dim3(grid_for(count)), dim3(kBlock), (hipStream_t)l.stream, c, count, d_x, d_y, d_phi);
+    else                                    launch(k_atan2<uint64_t>, dim3(grid_for(count)), dim3(kBlock), (hipStream_t)l.stream, c, count, d_x, d_y, d_phi);
     return finish(hipSuccess);
 }
 
