@@ -77,15 +77,16 @@ bool stream_is_capturing(void *stream)
 // (A.build, B.build, A.combine would combine A from B's table).  Calls on different streams get different
 // buffers; calls on one (device, stream) -- from any number of host threads, the *_to_host helpers on the
 // NULL stream included -- hold the slot's mutex from before the build launch until after the last launch,
-// and the stream then orders the kernels.  Growing a buffer happens under the same mutex.
+// and the stream then orders the kernels.  Growing a buffer happens under the same mutex; a buffer only grows.
 // Callers that want no allocation in the launch path (graph capture) pass their own workspace through
 // bhw_exec, or call bhw_prepare_device first.
 struct Slot {
     std::mutex mu;
     void *buf = nullptr;
     uint64_t bytes = 0;
-    bool oversized = false;   // sized while some packed-format verdict of the configuration was still open (the maximum over
-                              // every candidate up to plain): re-sized once the verdicts are known, see acquire_scratch
+    bool captured = false;              // buf was handed to a capturing stream: a graph may hold its address
+    std::vector<void *> retired;        // captured buffers the slot has grown out of, freed by bhw_release_device
+    uint64_t retired_bytes = 0;
 };
 struct DeviceScratch {
     std::map<void *, std::shared_ptr<Slot>> bufs;            // stream -> slot
@@ -109,29 +110,16 @@ int ensure_slot_bytes(Slot &slot, void *stream, uint64_t bytes)
     if (stream_is_capturing(stream))
         return fail(BHW_ERR_HIP, "library scratch of this stream must grow to %llu bytes during stream capture: call "
                     "bhw_prepare_device first or pass bhw_exec.workspace", (unsigned long long)bytes);
-    if (slot.buf) {
+    if (slot.buf && slot.captured) {                          // a graph may still replay with it: kept until bhw_release_device
+        slot.retired.push_back(slot.buf);
+        slot.retired_bytes += slot.bytes;
+    } else if (slot.buf) {
         (void)hipStreamSynchronize((hipStream_t)stream);      // earlier launches on this stream may still read it
         (void)hipFree(slot.buf);
-        slot.buf = nullptr;
-        slot.bytes = 0;
     }
-    void *b = nullptr;
-    const hipError_t e = hipMalloc(&b, bytes);
-    if (e != hipSuccess) return fail_hip(e, "hipMalloc(scratch)");
-    slot.buf = b;
-    slot.bytes = bytes;
-    return BHW_OK;
-}
-
-// slot.mu is held by the caller.  Gives back what a slot holds beyond `bytes` (never inside a capture: it synchronises).
-int shrink_slot_to(Slot &slot, void *stream, uint64_t bytes)
-{
-    if (slot.bytes <= bytes || stream_is_capturing(stream)) return BHW_OK;
-    (void)hipStreamSynchronize((hipStream_t)stream);          // earlier launches on this stream may still read it
-    (void)hipFree(slot.buf);
     slot.buf = nullptr;
     slot.bytes = 0;
-    if (!bytes) return BHW_OK;
+    slot.captured = false;
     void *b = nullptr;
     const hipError_t e = hipMalloc(&b, bytes);
     if (e != hipSuccess) return fail_hip(e, "hipMalloc(scratch)");
@@ -242,44 +230,44 @@ int checked_build(const BhwLaunch &l, BhwCordicCfg c, void *buf, uint32_t *flag,
     return e;
 }
 
-// Build the table in the narrowest format that is exact for this configuration: the walk's open formats first, each with the
-// kernels' overflow check on and read back (once per process and configuration; a capture walks none), then the one it kept.
-// Each open verdict is read again first: another call may have settled it since the walk.  `ws` holds fw.scratch_bytes bytes.
-int build_table(const bhw_params *p, const BhwLaunch &l, BhwCordicCfg &c, const BhwFormatWalk &fw, void *ws)
+// Settles the verdicts of the walk's open formats, narrowest first, up to the first exact one: each is read again first (another
+// call may have settled it since the walk), and each still unknown gets a build with the kernels' overflow check on -- into `spare`
+// when it holds spare_bytes >= the format's layout, else into a temporary allocation.  It reads the check word back, so never
+// during a capture (a capturing walk has no open formats), and it never sizes the library scratch.
+int settle_formats(const bhw_params *p, const BhwLaunch &l, BhwCordicCfg c, const BhwFormatWalk &fw, void *spare, uint64_t spare_bytes)
 {
-    uint32_t dlog = fw.kept;
     for (int i = 0; i < fw.n_open; ++i) {
-        const int verdict = bhwp_fmt_verdict(p, fw.open[i]);
-        if (verdict == kFmtBad) continue;
-        if (verdict == kFmtOk) {
-            dlog = fw.open[i];
-            break;
+        int verdict = bhwp_fmt_verdict(p, fw.open[i]);
+        if (verdict == kFmtUnknown) {
+            const uint64_t bytes = bhwp_table_layout(bhwp_table_entries(c), fw.open[i]).bytes;
+            void *buf = spare;
+            if (bytes > spare_bytes) {
+                const hipError_t he = hipMalloc(&buf, bytes);
+                if (he != hipSuccess) return fail_hip(he, "hipMalloc(trial table)");
+            }
+            point_table(c, fw.open[i], buf);
+            uint32_t flag = 1;
+            const char *stage = "";
+            const int e = checked_build(l, c, buf, &flag, &stage);
+            if (buf != spare) (void)hipFree(buf);
+            if (e) return fail_hip(e, stage);
+            verdict = flag ? kFmtBad : kFmtOk;
+            bhwp_fmt_set_verdict(p, fw.open[i], verdict);
         }
-        point_table(c, fw.open[i], ws);
-        uint32_t flag = 1;
-        const char *stage = "";
-        const int e = checked_build(l, c, ws, &flag, &stage);
-        if (e) return fail_hip(e, stage);
-        bhwp_fmt_set_verdict(p, fw.open[i], flag ? kFmtBad : kFmtOk);
-        if (!flag) return BHW_OK;                                                // exact: keep the table just built
+        if (verdict == kFmtOk) break;
     }
-    point_table(c, dlog, ws);
-    const int e = bhwk_table_build(l, c, (int32_t *)ws);
-    return e ? fail_hip(e, "table build launch") : BHW_OK;
+    return BHW_OK;
 }
 
 // Scratch of a table-strategy call: the caller's workspace when it passed one, else the library-owned buffer of this stream
-// (locked until every launch of the call is enqueued), holding at least `need` bytes.
+// (locked until every launch of the call is enqueued), holding at least `need` bytes.  A slot handed to a capturing stream is
+// marked `captured`, so that growing it later retires the buffer instead of freeing it.
 struct TableScratch {
     void *ws = nullptr;
     std::shared_ptr<Slot> slot;
     std::unique_lock<std::mutex> lock;
 };
-// `open_verdicts`: `need` is the maximum over formats whose verdict is not known yet (the first call of a configuration without
-// bhw_prepare_device).  The slot remembers that, and the next call that finds the verdicts settled gives the excess back once
-// (128 MiB -> 16.5 MiB for a 2^26-point window at 32 bits); a slot is never re-sized downwards otherwise, so streams that alternate
-// between configurations of different sizes do not re-allocate per call.
-int acquire_scratch(const bhw_exec *ex, int device, void *stream, uint64_t need, bool open_verdicts, TableScratch &t)
+int acquire_scratch(const bhw_exec *ex, int device, void *stream, uint64_t need, bool capturing, TableScratch &t)
 {
     if (ex && ex->workspace) {
         if (ex->workspace_bytes < need)
@@ -289,29 +277,42 @@ int acquire_scratch(const bhw_exec *ex, int device, void *stream, uint64_t need,
     }
     t.slot = slot_of(device, stream);
     t.lock = std::unique_lock<std::mutex>(t.slot->mu);
-    if (t.slot->oversized && !open_verdicts && t.slot->bytes > need && !stream_is_capturing(stream)) {   // (a capture keeps the excess for a later call)
-        t.slot->oversized = false;
-        const int rs = shrink_slot_to(*t.slot, stream, need);
-        if (rs) return rs;
-    }
-    const bool grows = t.slot->bytes < need;
     const int rc = ensure_slot_bytes(*t.slot, stream, need);
     if (rc) return rc;
-    if (grows && open_verdicts) t.slot->oversized = true;
+    if (capturing) t.slot->captured = true;
     t.ws = t.slot->buf;
     return BHW_OK;
 }
 
-// The table of a table-strategy call, rebuilt: scratch for the formats the call may use (acquire_scratch; a slot stays locked in
-// `scratch` until every launch of the call is enqueued), the table built into it, then ex->event_after_build recorded.
-// Whole-period tile tables are stored packed when the widths allow it (formats in bhw_device.h): "nibble" = 1 byte per entry,
-// "residual" = 2 bytes + one int4 record per 2^d entries, else "delta16" = 4 bytes per entry + one int2 head per 64 entries, else
-// the plain 8 bytes per entry.
+// The table of a table-strategy call, rebuilt: the open formats settled first (the first call of a configuration without
+// bhw_prepare_device; the trials use the call's workspace or the stream's current buffer where either holds them), then scratch
+// for the one format kept (acquire_scratch; a slot stays locked in `scratch` until every launch of the call is enqueued), the
+// table built into it, then ex->event_after_build recorded.  Whole-period tile tables are stored packed when the widths allow it
+// (formats in bhw_device.h): "nibble" = 1 byte per entry, "residual" = 2 bytes + one int4 record per 2^d entries, else "delta16"
+// = 4 bytes per entry + one int2 head per 64 entries, else the plain 8 bytes per entry.
 int rebuild_table(const bhw_params *p, const BhwLaunch &l, BhwCordicCfg &c, bool tiled, const bhw_exec *ex, TableScratch &scratch)
 {
-    const BhwFormatWalk fw = bhwp_format_walk(p, c, tiled, bhwp_exec_table_format(ex), stream_is_capturing(l.stream));
-    int rc = acquire_scratch(ex, l.device, l.stream, fw.scratch_bytes, fw.n_open != 0, scratch);
-    if (!rc) rc = build_table(p, l, c, fw, scratch.ws);
+    const uint32_t limit = bhwp_exec_table_format(ex);
+    const bool capturing = stream_is_capturing(l.stream);
+    BhwFormatWalk fw = bhwp_format_walk(p, c, tiled, limit, capturing);
+    int rc;
+    if (fw.n_open) {
+        if (ex && ex->workspace) {
+            rc = settle_formats(p, l, c, fw, ex->workspace, ex->workspace_bytes);
+        } else {
+            const std::shared_ptr<Slot> slot = slot_of(l.device, l.stream);
+            std::lock_guard<std::mutex> lk(slot->mu);
+            rc = settle_formats(p, l, c, fw, slot->buf, slot->bytes);
+        }
+        if (rc) return rc;
+        fw = bhwp_format_walk(p, c, tiled, limit, false);
+    }
+    rc = acquire_scratch(ex, l.device, l.stream, fw.scratch_bytes, capturing, scratch);
+    if (!rc) {
+        point_table(c, fw.kept, scratch.ws);
+        const int e = bhwk_table_build(l, c, (int32_t *)scratch.ws);
+        if (e) rc = fail_hip(e, "table build launch");
+    }
     if (rc || !ex || !ex->event_after_build) return rc;
     const hipError_t he = hipEventRecord((hipEvent_t)ex->event_after_build, (hipStream_t)l.stream);
     return he != hipSuccess ? fail_hip(he, "hipEventRecord(event_after_build)") : BHW_OK;
@@ -764,8 +765,11 @@ int bhw_release_device(int device)
         for (auto &kv : taken.bufs) {
             std::lock_guard<std::mutex> lk(kv.second->mu);   // a call still enqueueing on this slot finishes first
             if (kv.second->buf) (void)hipFree(kv.second->buf);
+            for (void *b : kv.second->retired) (void)hipFree(b);
             kv.second->buf = nullptr;
             kv.second->bytes = 0;
+            kv.second->retired.clear();
+            kv.second->retired_bytes = 0;
         }
         for (auto &kv : taken.roms) (void)hipFree(kv.second);
     }
@@ -787,50 +791,34 @@ int bhw_prepare_device(const bhw_params *p, int device, void *hip_stream)
     bhwp_resolve_cordic(p, c);
     BhwWinCfg w;
     bhwp_resolve_window(p, w);
-    // Reserve the scratch every later table-strategy call with these widths can need -- also for configurations AUTO sends to the
-    // fused kernel as whole periods: a partial range of such a window, or an explicit BHW_ALGO_TABLE, still builds a table, and
-    // must not allocate inside a stream capture.  Two shapes: the plain table of ranges without a whole period (8 bytes per entry;
-    // reserved up to 64 MiB -- beyond that a ragged call after prepare may still grow the scratch once, outside a capture) and the
-    // packed table of whole-period tile calls, whose format verdicts are settled here first.
+    // Settle the packed-format verdict of EVERY format a later call may name: the chain table_format BEST walks, and each explicit
+    // limit -- a captured call with an explicit bhw_exec.table_format must not meet an open verdict (it would fall back to the plain
+    // table, which the scratch may not hold).  Then reserve the scratch every later table-strategy call with these widths can need
+    // -- also for configurations AUTO sends to the fused kernel as whole periods: a partial range of such a window, or an explicit
+    // BHW_ALGO_TABLE, still builds a table, and must not allocate inside a stream capture.  Two shapes: the settled format of
+    // whole-period tile calls (16.5 MiB instead of 128 MiB for a 2^26-point window at 32 bits) and the plain table of ranges without
+    // a whole period (8 bytes per entry; reserved up to 64 MiB -- beyond that a ragged call after prepare may still grow the scratch
+    // once, outside a capture).  The slot only grows: what an earlier prepared configuration needs stays.
     const bool tile = bhwk_tile_applicable(c, w);
     const uint64_t plain = bhwp_table_layout(bhwp_table_entries(c), 0).bytes;
-    uint64_t need = plain <= (64ull << 20) || !tile ? plain : 0;
-    const uint32_t limits[] = {BHW_TABLE_BEST, BHW_TABLE_NIBBLE_ESC, BHW_TABLE_RESIDUAL, BHW_TABLE_DELTA16};
-    if (tile) {
-        c.tab_split = c.z_shr == 0 ? 1u : 0u;
-        for (uint32_t limit : limits) {
-            const BhwFormatWalk fw = bhwp_format_walk(p, c, true, limit, false);   // while formats are unverified: the widest that may be tried
-            if ((limit == BHW_TABLE_BEST || fw.n_open) && fw.scratch_bytes > need) need = fw.scratch_bytes;
-        }
-    }
+    uint64_t keep = plain <= (64ull << 20) || !tile ? plain : 0;
     auto slot = slot_of(device, hip_stream);
     std::unique_lock<std::mutex> lk(slot->mu);
-    rc = ensure_slot_bytes(*slot, hip_stream, need);
-    if (rc) return rc;
-    // Settle the packed-format verdict of EVERY format a later call may name (build_table reads the check word back when one is
-    // open): the chain table_format BEST walks, and each explicit limit -- a captured call with an explicit bhw_exec.table_format
-    // must not meet an open verdict (it would fall back to the plain table, which the scratch below no longer holds).
     if (tile) {
-        BhwLaunch l{device, hip_stream};
-        const bool capturing = stream_is_capturing(hip_stream);
-        for (uint32_t limit : limits) {
-            if (limit != BHW_TABLE_BEST && !bhwp_format_walk(p, c, true, limit, false).n_open) continue;
-            rc = build_table(p, l, c, bhwp_format_walk(p, c, true, limit, capturing), slot->buf);
-            if (rc) return rc;
+        c.tab_split = c.z_shr == 0 ? 1u : 0u;
+        if (!stream_is_capturing(hip_stream)) {
+            for (uint32_t limit : {BHW_TABLE_BEST, BHW_TABLE_NIBBLE_ESC, BHW_TABLE_RESIDUAL, BHW_TABLE_DELTA16}) {
+                rc = settle_formats(p, BhwLaunch{device, hip_stream}, c, bhwp_format_walk(p, c, true, limit, false), slot->buf, slot->bytes);
+                if (rc) return rc;
+            }
         }
-    }
-    hipError_t he = hipStreamSynchronize((hipStream_t)hip_stream);
-    if (he != hipSuccess) return fail_hip(he, "hipStreamSynchronize");
-    // ... and with the verdicts known the scratch is what table_format BEST needs from now on (16.5 MiB instead of 128 MiB for a
-    // 2^26-point window at 32 bits), plus the plain table of partial ranges where that was reserved above
-    if (tile) {
         const uint64_t settled = bhwp_format_walk(p, c, true, BHW_TABLE_BEST, false).scratch_bytes;
-        const uint64_t keep = plain <= (64ull << 20) ? (plain > settled ? plain : settled) : settled;
-        slot->oversized = false;
-        rc = shrink_slot_to(*slot, hip_stream, keep);
-        if (rc) return rc;
+        if (settled > keep) keep = settled;
     }
-    return BHW_OK;
+    rc = ensure_slot_bytes(*slot, hip_stream, keep);
+    if (rc) return rc;
+    const hipError_t he = hipStreamSynchronize((hipStream_t)hip_stream);
+    return he != hipSuccess ? fail_hip(he, "hipStreamSynchronize") : BHW_OK;
 }
 
 // ---- resident tables (include/bhw.h: bhw_table_create ...) -------------------------------------------------------------------------
@@ -852,21 +840,6 @@ struct bhw_table_s {
 };
 
 namespace {
-
-// Settles the verdict of packed format `dlog` for `p` by a trial build with the overflow check into a temporary buffer
-int trial_build(const bhw_params *p, const BhwLaunch &l, BhwCordicCfg c, uint32_t dlog)
-{
-    void *tmp = nullptr;
-    const hipError_t he = hipMalloc(&tmp, bhwp_table_layout(bhwp_table_entries(c), dlog).bytes);
-    if (he != hipSuccess) return fail_hip(he, "hipMalloc(trial table)");
-    point_table(c, dlog, tmp);
-    uint32_t flag = 1;
-    const int e = checked_build(l, c, tmp, &flag);
-    (void)hipFree(tmp);
-    if (e) return fail_hip(e, "trial build of a packed table format");
-    bhwp_fmt_set_verdict(p, dlog, flag ? kFmtBad : kFmtOk);
-    return BHW_OK;
-}
 
 // the prologue of every from-table call: the handle, `p` validated and matched to the table's generics
 int table_call_checks(bhw_table t, const bhw_params *p)
@@ -910,20 +883,11 @@ int bhw_table_create(const bhw_params *p, int device, void *hip_stream, uint32_t
     BhwCordicCfg c;
     bool tiled;
     bhwp_resident_layout(p, c, &tiled);
-    // the narrowest format under `table_format` that is exact for the configuration: the walk's open verdicts are settled by trial
-    // builds, narrowest first (each read again first: another thread may have settled it since the walk), else the walk's `kept`
-    const BhwFormatWalk fw = bhwp_format_walk(p, c, tiled, table_format, false);
-    uint32_t keep = fw.kept;
-    for (int i = 0; i < fw.n_open; ++i) {
-        if (bhwp_fmt_verdict(p, fw.open[i]) == kFmtUnknown) {
-            rc = trial_build(p, l, c, fw.open[i]);
-            if (rc) return rc;
-        }
-        if (bhwp_fmt_verdict(p, fw.open[i]) == kFmtOk) {
-            keep = fw.open[i];
-            break;
-        }
-    }
+    // the narrowest format under `table_format` that is exact for the configuration: the walk's open verdicts settled by trial
+    // builds into temporary buffers, then the walk's `kept`
+    rc = settle_formats(p, l, c, bhwp_format_walk(p, c, tiled, table_format, false), nullptr, 0);
+    if (rc) return rc;
+    const uint32_t keep = bhwp_format_walk(p, c, tiled, table_format, false).kept;
     const uint64_t bytes = bhwp_table_layout(bhwp_table_entries(c), keep).bytes;
     void *buf = nullptr;
     hipError_t he = hipMalloc(&buf, bytes);
@@ -1057,21 +1021,26 @@ int bhw_dbg_generate_from_table_generic(bhw_table t, const bhw_params *p, void *
     return from_table(t, p, hip_stream, n0, count, d_out, nullptr, 0, bhwk_table_combine);
 }
 
-// Bytes the library-owned scratch of (device, hip_stream) holds right now (0: none yet) -- what bench.py reports beside the size of
-// the workspace it passes itself.  Not part of the ABI in include/bhw.h.
-uint64_t bhw_dbg_library_scratch_bytes(int device, void *hip_stream)
+// the live (or, with `retired`, the retired) bytes of the library-owned scratch of (device, stream); 0 where it has none
+static uint64_t slot_bytes(int device, void *stream, bool retired)
 {
     std::shared_ptr<Slot> sp;
     {
         std::lock_guard<std::mutex> lk(g_mu);
         auto it = g_scratch.find(device);
         if (it == g_scratch.end()) return 0;
-        auto jt = it->second.bufs.find(hip_stream);
+        auto jt = it->second.bufs.find(stream);
         if (jt == it->second.bufs.end()) return 0;
         sp = jt->second;
     }
     std::lock_guard<std::mutex> lk(sp->mu);
-    return sp->bytes;
+    return retired ? sp->retired_bytes : sp->bytes;
 }
+
+// Bytes the library-owned scratch of (device, hip_stream) holds right now (0: none yet) -- what bench.py reports beside the size of
+// the workspace it passes itself -- and the bytes of the captured buffers it has grown out of (kept until bhw_release_device).  Not
+// part of the ABI in include/bhw.h.
+uint64_t bhw_dbg_library_scratch_bytes(int device, void *hip_stream) { return slot_bytes(device, hip_stream, false); }
+uint64_t bhw_dbg_library_retired_bytes(int device, void *hip_stream) { return slot_bytes(device, hip_stream, true); }
 
 } // extern "C"

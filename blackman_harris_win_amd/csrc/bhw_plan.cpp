@@ -380,11 +380,6 @@ BhwFormatWalk bhwp_format_walk(const bhw_params *p, const BhwCordicCfg &c, bool 
     return fw;
 }
 
-uint64_t bhwp_table_scratch_bytes(const bhw_params *p, const BhwCordicCfg &c, bool tiled, uint32_t limit, bool capturing)
-{
-    return bhwp_format_walk(p, c, tiled, limit, capturing).scratch_bytes;
-}
-
 const char *bhwp_format_name(uint32_t tab_dlog)
 {
     return tab_dlog == 0 ? "plain" : tab_dlog == kPackLog ? "delta16" : tab_dlog >= kEscFlag ? "nibble+esc" : tab_dlog >= kNibbleFlag ? "nibble" : "residual";

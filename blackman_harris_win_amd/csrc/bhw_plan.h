@@ -125,8 +125,6 @@ struct BhwFormatWalk {
     uint64_t scratch_bytes;         // what a table-strategy call needs right now: the largest of `kept` and the open formats
 };
 BhwFormatWalk bhwp_format_walk(const bhw_params *p, const BhwCordicCfg &c, bool tiled, uint32_t limit, bool capturing);
-// the walk's scratch_bytes alone
-uint64_t bhwp_table_scratch_bytes(const bhw_params *p, const BhwCordicCfg &c, bool tiled, uint32_t limit, bool capturing);
 // the name of a table format (tab_dlog) in the describe strings
 const char *bhwp_format_name(uint32_t tab_dlog);
 

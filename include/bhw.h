@@ -167,8 +167,7 @@ uint64_t bhw_workspace_bytes(const bhw_params *p, uint64_t n0, uint64_t count, u
  * format in use -- 16.5 MiB instead of 128 MiB for a 2^26-point window at 32 bits -- and it never grows afterwards.  A
  * workspace of at least this size is accepted by bhw_generate_device_ex / bhw_generate_part_device (bhw_apply_device takes no
  * bhw_exec: it always uses the library-owned scratch).  The library-owned scratch of a stream is sized by the same rule:
- * bhw_prepare_device leaves it at this size; a stream that was never prepared holds the 8-bytes-per-entry bound from its first
- * call (which has to try the formats) until the next call of that configuration, which gives the excess back once. */
+ * the formats are settled before it is sized, so a stream holds the settled format from its first call, prepared or not. */
 uint64_t bhw_workspace_bytes_ex(const bhw_params *p, uint64_t n0, uint64_t count, const bhw_exec *ex);
 
 /* What bhw_generate_device_ex(p, ..., n0, count, ..., ex) would launch right now, as one line of text into buf (NUL-terminated,
@@ -183,7 +182,8 @@ int bhw_describe_plan(const bhw_params *p, uint64_t n0, uint64_t count, const bh
  * these widths on this stream neither allocate nor synchronise, so they can be captured into a HIP graph -- whole periods,
  * partial ranges and explicit bhw_exec.algo alike (the scratch is reserved also for configurations whose whole periods take the
  * table-free fused kernel).  The verdict of every packed format is settled, so an explicit bhw_exec.table_format never meets
- * an open one; the scratch is sized for table_format BEST (the narrowest exact format).  Two exceptions, both answered by
+ * an open one; the scratch is sized for table_format BEST (the narrowest exact format) and never shrinks, so what an earlier
+ * prepare of this stream reserved for another configuration stays.  Two exceptions, both answered by
  * passing bhw_exec.workspace (bhw_workspace_bytes_ex bytes) inside a capture: a range WITHOUT a whole period of a window whose
  * plain table exceeds 64 MiB (phi_width >= 26 at z_shr = 0), and an explicit table_format wider than the one BEST resolves to --
  * either would have to grow the library scratch, which a capturing stream refuses (BHW_ERR_HIP).
@@ -373,7 +373,8 @@ int bhw_overlap_add_describe(bhw_table t, const bhw_params *p, const bhw_ola *o,
  * thread's current HIP device is restored before every entry point returns, and no entry point reads or clears the
  * thread's hipGetLastError() state.
  *
- * Releases the library-owned per-device scratch. */
+ * Releases the library-owned per-device scratch, including the buffers of graphs captured with it: a graph captured with
+ * library scratch on `device` must not be replayed after this call. */
 int bhw_release_device(int device);
 
 #ifdef __cplusplus

@@ -191,16 +191,14 @@ def test_library_scratch_is_sized_by_the_format_in_use(torch):
     assert ei.value.code == -4
 
 
-def test_library_scratch_gives_the_excess_back_once_the_formats_are_settled(torch):
-    """Round-4 advisor finding: the first call of a configuration has to size the stream's scratch for every format it may try (8 bytes
-    per entry: 128 MiB for the 2^26-point window at 32 bits) and the slot kept that size for good.  Now the next call of the
-    configuration re-sizes it to the format in use (16.5 MiB), bhw_prepare_device leaves it there directly, and every later call
-    produces the same window.  After prepare a captured call with an explicit, wider table_format is refused with a message that
-    names the remedy (the library scratch cannot grow inside a capture) and works with the caller's workspace."""
+def test_library_scratch_holds_the_settled_format_from_the_first_call(torch):
+    """Round-4 advisor finding: the first call of a configuration sized the stream's scratch for every format it might try (8 bytes
+    per entry: 128 MiB for the 2^26-point window at 32 bits).  Now the formats are settled before the scratch is sized, so the
+    first call leaves the format in use (16.5 MiB), the next call keeps it, bhw_prepare_device leaves it there directly, and every
+    later call produces the same window.  After prepare a captured call with an explicit, wider table_format is refused with a
+    message that names the remedy (the library scratch cannot grow inside a capture) and works with the caller's workspace."""
     import blackman_harris_win_amd as bhw
     L = _dbg()
-    L.bhw_dbg_library_scratch_bytes.restype = ctypes.c_uint64
-    L.bhw_dbg_library_scratch_bytes.argtypes = [ctypes.c_int, ctypes.c_void_p]
     p = B.make_params(7, 26, 32)
     n = 1 << 26
     d = ctypes.c_uint32()
@@ -214,14 +212,14 @@ def test_library_scratch_gives_the_excess_back_once_the_formats_are_settled(torc
     st = torch.cuda.Stream()
     with torch.cuda.stream(st):
         out = torch.zeros(n, dtype=torch.int32, device="cuda")
-        bhw.generate(p, 0, n, out=out)                                                   # unprepared: tries the formats
+        bhw.generate(p, 0, n, out=out)                                                   # unprepared: settles the formats first
         st.synchronize()
-        assert L.bhw_dbg_library_scratch_bytes(0, ctypes.c_void_p(st.cuda_stream)) == bound
-        first = out.clone()
         tight = B.lib().bhw_workspace_bytes_ex(ctypes.byref(p), 0, n, ctypes.byref(ex))
         assert tight < bound // 7
+        assert L.bhw_dbg_library_scratch_bytes(0, ctypes.c_void_p(st.cuda_stream)) == tight
+        first = out.clone()
         out.zero_()
-        bhw.generate(p, 0, n, out=out)                                                   # verdicts known: the excess goes back
+        bhw.generate(p, 0, n, out=out)
         st.synchronize()
         assert L.bhw_dbg_library_scratch_bytes(0, ctypes.c_void_p(st.cuda_stream)) == tight
         assert torch.equal(out, first)
@@ -248,30 +246,94 @@ def test_library_scratch_gives_the_excess_back_once_the_formats_are_settled(torc
         graph.replay()
         st2.synchronize()
         assert torch.equal(out2, first)
-    # an oversized slot met by a captured call: nothing is re-sized inside the capture (that would synchronise the stream), the graph
-    # uses the buffer as it is, and the next plain call gives the excess back
+    # Round-5 advisor finding: a graph captured after an unprepared warm-up call holds the slot's buffer, and a later plain call of
+    # the same configuration must not free it -- the graph replays after that call as well as before it
     for k in (16 + 9, 48 + 9, 9, 6):
         assert L.bhw_dbg_table_format_verdict(ctypes.byref(p), k, 3) == 0
     st3 = torch.cuda.Stream()
     with torch.cuda.stream(st3):
         out3 = torch.zeros(n, dtype=torch.int32, device="cuda")
-        bhw.generate(p, 0, n, out=out3)                                                  # unprepared again: the slot of st3 takes the bound
+        bhw.generate(p, 0, n, out=out3)                                                  # unprepared again: the slot of st3 takes tight
         st3.synchronize()
-        assert L.bhw_dbg_library_scratch_bytes(0, ctypes.c_void_p(st3.cuda_stream)) == bound
+        assert L.bhw_dbg_library_scratch_bytes(0, ctypes.c_void_p(st3.cuda_stream)) == tight
         out3.zero_()
         g3 = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g3, stream=st3):
             bhw.generate(p, 0, n, out=out3)
-        assert L.bhw_dbg_library_scratch_bytes(0, ctypes.c_void_p(st3.cuda_stream)) == bound
+        assert L.bhw_dbg_library_scratch_bytes(0, ctypes.c_void_p(st3.cuda_stream)) == tight
         g3.replay()
         st3.synchronize()
         assert torch.equal(out3, first)
-        del g3                                                                           # (the graph's kernels hold the buffer's address)
         out3.zero_()
         bhw.generate(p, 0, n, out=out3)
         st3.synchronize()
         assert L.bhw_dbg_library_scratch_bytes(0, ctypes.c_void_p(st3.cuda_stream)) == tight
         assert torch.equal(out3, first)
+        out3.zero_()
+        g3.replay()
+        st3.synchronize()
+        assert torch.equal(out3, first)
+
+
+def test_prepare_never_shrinks_what_an_earlier_prepare_reserved(torch):
+    """Round-5 advisor finding: bhw_prepare_device of a smaller configuration shrank the stream's scratch below what an earlier
+    prepared configuration needs, so a captured call of that one then failed.  The scratch only grows: after prepare(2^26) and
+    prepare(2^22) the slot still holds the 2^26 configuration's format, and a captured 2^26 call replays to the eager window."""
+    import blackman_harris_win_amd as bhw
+    L = _dbg()
+    big, small = B.make_params(7, 26, 32), B.make_params(7, 22, 32)
+    n = 1 << 26
+    ex = B.BhwExec()
+    ex.struct_size = ctypes.sizeof(B.BhwExec)
+    ex.algo = B.ALGO_TABLE
+    st = torch.cuda.Stream()
+    with torch.cuda.stream(st):
+        bhw.prepare(big)
+        tight = B.lib().bhw_workspace_bytes_ex(ctypes.byref(big), 0, n, ctypes.byref(ex))
+        assert L.bhw_dbg_library_scratch_bytes(0, ctypes.c_void_p(st.cuda_stream)) == tight
+        assert B.lib().bhw_workspace_bytes(ctypes.byref(small), 0, 1 << 22, B.ALGO_TABLE) < tight   # what prepare(small) reserves
+        bhw.prepare(small)
+        assert L.bhw_dbg_library_scratch_bytes(0, ctypes.c_void_p(st.cuda_stream)) == tight
+        want = bhw.generate(big, 0, n)
+        out = torch.zeros(n, dtype=torch.int32, device="cuda")
+        st.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=st):
+            bhw.generate(big, 0, n, out=out)
+        graph.replay()
+        st.synchronize()
+        assert torch.equal(out, want)
+
+
+def test_growing_a_captured_slot_retires_its_buffer(torch):
+    """A plain call that grows the library scratch of a stream whose buffer a captured graph holds moves that buffer to the slot's
+    retired list (freed by bhw_release_device) instead of freeing it: the graph still replays to the eager window.  The retired
+    bytes are checked before the replay, so a missing retire path fails here without the replay touching freed memory."""
+    import blackman_harris_win_amd as bhw
+    L = _dbg()
+    pa = B.make_params(7, 18, 32)                                                        # plain table, 512 KiB
+    pb = B.make_params(5, 20, 24, model=B.MODEL_CPP)                                     # plain table, 2 MiB
+    na, nb = 1 << 18, 1 << 20
+    a_bytes = B.lib().bhw_workspace_bytes(ctypes.byref(pa), 0, na, B.ALGO_TABLE)
+    assert a_bytes < B.lib().bhw_workspace_bytes(ctypes.byref(pb), 0, nb, B.ALGO_TABLE)
+    st = torch.cuda.Stream()
+    with torch.cuda.stream(st):
+        bhw.prepare(pa)
+        assert L.bhw_dbg_library_scratch_bytes(0, ctypes.c_void_p(st.cuda_stream)) == a_bytes
+        want = bhw.generate(pa, 0, na, algo=B.ALGO_TABLE)
+        out = torch.zeros(na, dtype=torch.int32, device="cuda")
+        st.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=st):
+            bhw.generate(pa, 0, na, out=out, algo=B.ALGO_TABLE)
+        assert L.bhw_dbg_library_retired_bytes(0, ctypes.c_void_p(st.cuda_stream)) == 0
+        bhw.generate(pb, 0, nb, algo=B.ALGO_TABLE)                                       # the slot grows
+        st.synchronize()
+        assert L.bhw_dbg_library_scratch_bytes(0, ctypes.c_void_p(st.cuda_stream)) > a_bytes
+        assert L.bhw_dbg_library_retired_bytes(0, ctypes.c_void_p(st.cuda_stream)) == a_bytes
+        graph.replay()
+        st.synchronize()
+        assert torch.equal(out, want)
 
 
 def _dbg():
@@ -281,6 +343,9 @@ def _dbg():
                                              ctypes.POINTER(ctypes.c_uint32)]
     L.bhw_dbg_table_format_verdict.argtypes = [P, ctypes.c_uint32, ctypes.c_int]
     L.bhw_dbg_table_format_info.argtypes = [P, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
+    for hook in (L.bhw_dbg_library_scratch_bytes, L.bhw_dbg_library_retired_bytes):
+        hook.restype = ctypes.c_uint64
+        hook.argtypes = [ctypes.c_int, ctypes.c_void_p]
     return L
 
 
