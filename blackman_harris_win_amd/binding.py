@@ -24,6 +24,8 @@ ABI_SYMBOLS = (
     "bhw_apply_from_table", "bhw_generate_part_from_table",
     "bhw_apply_frames_device", "bhw_apply_frames_from_table", "bhw_apply_frames_describe",
     "bhw_overlap_add_device", "bhw_overlap_add_from_table", "bhw_overlap_add_describe",
+    "bhw_generate_len_device", "bhw_generate_len_from_table", "bhw_apply_frames_len_device", "bhw_apply_frames_len_from_table",
+    "bhw_overlap_add_len_device", "bhw_overlap_add_len_from_table", "bhw_describe_len",
 )
 
 
@@ -165,6 +167,14 @@ def lib():
     L.bhw_overlap_add_describe.argtypes = [T, P, O, ctypes.c_char_p, u64]
     L.bhw_dbg_overlap_add_shape.argtypes = [T, P, ci, vp, O, i32p, i32p, u32, u32]
     L.bhw_dbg_describe_ola_from_table.argtypes = [P, u32, P, O, ctypes.c_char_p, u64]
+    L.bhw_generate_len_device.argtypes = [P, u64, ci, vp, u64, u64, i32p]
+    L.bhw_generate_len_from_table.argtypes = [T, P, u64, vp, u64, u64, i32p]
+    L.bhw_apply_frames_len_device.argtypes = [P, u64, ci, vp, F, i32p, i32p]
+    L.bhw_apply_frames_len_from_table.argtypes = [T, P, u64, vp, F, i32p, i32p]
+    L.bhw_overlap_add_len_device.argtypes = [P, u64, ci, vp, O, i32p, i32p]
+    L.bhw_overlap_add_len_from_table.argtypes = [T, P, u64, vp, O, i32p, i32p]
+    L.bhw_describe_len.argtypes = [T, P, u64, u64, u64, F, O, ctypes.c_char_p, u64]
+    L.bhw_dbg_len_force_kernels.argtypes = [ci]
     PA = ctypes.POINTER(BhwAtan2Params)
     L.bhw_atan2_device.argtypes = [PA, ci, vp, u64, i32p, i32p, i32p]
     L.bhw_atan2_to_host.argtypes = [PA, ci, u64, i32p, i32p, i32p]
@@ -216,6 +226,20 @@ def describe_ola(params, frames, hop, count=None, *, t0=0, channels=1, y_stride=
     buf = ctypes.create_string_buffer(384)
     o = make_ola(frames, hop, count, t0=t0, channels=channels, y_stride=y_stride)
     check(lib().bhw_overlap_add_describe(table, ctypes.byref(params), ctypes.byref(o), buf, 384))
+    return buf.value.decode()
+
+
+def describe_len(params, length, *, n0=0, count=None, frames=None, ola=None, table=None):
+    """One line: the route (power-of-two or any-length), kernel and grid a call for a window of `length` takes (bhw_describe_len).
+    frames: a BhwFrames (make_frames) for the frames call, ola: a BhwOla (make_ola) for the overlap-add, neither: generate
+    [n0, n0 + count) (count=None: one period).  `table` is a resident table handle or None for the library call.  Host arithmetic."""
+    if frames is not None and ola is not None:
+        raise ValueError("pass frames or ola, not both")
+    count = int(length) if count is None else int(count)
+    buf = ctypes.create_string_buffer(512)
+    check(lib().bhw_describe_len(table, ctypes.byref(params), int(length), int(n0), count,
+                                 ctypes.byref(frames) if frames is not None else None, ctypes.byref(ola) if ola is not None else None,
+                                 buf, 512))
     return buf.value.decode()
 
 

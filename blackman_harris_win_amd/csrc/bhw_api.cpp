@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <atomic>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -1042,5 +1043,149 @@ static uint64_t slot_bytes(int device, void *stream, bool retired)
 // part of the ABI in include/bhw.h.
 uint64_t bhw_dbg_library_scratch_bytes(int device, void *hip_stream) { return slot_bytes(device, hip_stream, false); }
 uint64_t bhw_dbg_library_retired_bytes(int device, void *hip_stream) { return slot_bytes(device, hip_stream, true); }
+
+} // extern "C"
+
+// ---- windows of any length (include/bhw.h: bhw_generate_len_device ...) -------------------------------------------------------------
+// At L = 2^phi_width every call takes the existing entry point of its kind, unchanged; otherwise the any-length kernels (bhw_len.hip,
+// k_frames_*_len, k_ola_*_len), which allocate nothing and use no scratch.  bhw_dbg_len_force_kernels sends L = 2^phi_width to the
+// any-length kernels too (the identity tests).
+
+namespace {
+
+std::atomic<bool> g_len_force{false};
+
+// the prologue of a library *_len call that takes the any-length kernels: a coefficient range [n0, n0 + count) into d_out
+int len_range_checks(uint64_t count, const int32_t *d_out)
+{
+    if (count && !d_out) return fail(BHW_ERR_BADARG, "d_out is NULL");
+    if (count > (1ull << 34)) return fail(BHW_ERR_BADARG, "count %llu > 2^34 per call", (unsigned long long)count);
+    return BHW_OK;
+}
+
+int frames_len(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_frames *f, const int32_t *d_x,
+               int32_t *d_y)
+{
+    int rc = t ? table_call_checks(t, p) : BHW_OK;
+    if (!rc) rc = bhwp_frames_checks(p, f, d_x, d_y, true, length);
+    if (rc || !f->frames) return rc;
+    const BhwFramesPlan pl = bhwp_frames_plan(p, f, t != nullptr, -1, length);
+    DeviceGuard guard(t ? t->device : device, !t);
+    if ((rc = guard.status())) return rc;
+    BhwCordicCfg c;
+    if (t) c = t->c;
+    else   bhwp_resolve_cordic(p, c);
+    BhwWinCfg w;
+    bhwp_resolve_window(p, w);
+    const BhwLenPhase lp = bhw_len_phase(p->phi_width, length);
+    const int e = bhwk_frames(BhwLaunch{t ? t->device : device, stream}, c, w, pl, f, d_x, d_y, t ? (const int32_t *)t->buf : nullptr, &lp);
+    return e ? fail_hip(e, "frames launch (any length)") : BHW_OK;
+}
+
+int ola_len(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_ola *o, const int32_t *d_y, int32_t *d_x)
+{
+    int rc = t ? table_call_checks(t, p) : BHW_OK;
+    if (!rc) rc = bhwp_ola_checks(p, o, d_y, d_x, true, length);
+    if (rc || !o->count) return rc;
+    const BhwOlaPlan pl = bhwp_ola_plan(p, o, t != nullptr, 0, 0, length);
+    DeviceGuard guard(t ? t->device : device, !t);
+    if ((rc = guard.status())) return rc;
+    BhwCordicCfg c;
+    if (t) c = t->c;
+    else   bhwp_resolve_cordic(p, c);
+    BhwWinCfg w;
+    bhwp_resolve_window(p, w);
+    const BhwLenPhase lp = bhw_len_phase(p->phi_width, length);
+    const int e = bhwk_ola(BhwLaunch{t ? t->device : device, stream}, c, w, pl, o, d_y, d_x, t ? (const int32_t *)t->buf : nullptr, &lp);
+    return e ? fail_hip(e, "overlap-add launch (any length)") : BHW_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int bhw_generate_len_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, uint64_t n0, uint64_t count, int32_t *d_out)
+{
+    int rc = bhwp_len_checks(p, length);
+    if (rc) return rc;
+    if (!bhwp_len_kernels(p, length, g_len_force)) return generate_impl(p, device, hip_stream, n0, count, d_out, nullptr);
+    if ((rc = len_range_checks(count, d_out)) || !count) return rc;
+    DeviceGuard guard(device);
+    if ((rc = guard.status())) return rc;
+    BhwCordicCfg c;
+    bhwp_resolve_cordic(p, c);
+    BhwWinCfg w;
+    bhwp_resolve_window(p, w);
+    const int e = bhwk_direct_len(BhwLaunch{device, hip_stream}, c, w, bhw_len_phase(p->phi_width, length), n0, count, d_out);
+    return e ? fail_hip(e, "generate launch (any length)") : BHW_OK;
+}
+
+int bhw_generate_len_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, uint64_t n0, uint64_t count,
+                                int32_t *d_out)
+{
+    int rc = bhwp_len_checks(p, length);
+    if (rc) return rc;
+    if (!bhwp_len_kernels(p, length, g_len_force)) return from_table(t, p, hip_stream, n0, count, d_out);
+    if ((rc = table_call_checks(t, p)) || (rc = len_range_checks(count, d_out)) || !count) return rc;
+    DeviceGuard guard(t->device, false);
+    if ((rc = guard.status())) return rc;
+    BhwWinCfg w;
+    bhwp_resolve_window(p, w);
+    const int e = bhwk_range_len(BhwLaunch{t->device, hip_stream}, t->c, w, (const int32_t *)t->buf, bhw_len_phase(p->phi_width, length), n0,
+                                 count, d_out);
+    return e ? fail_hip(e, "generate launch (any length, resident table)") : BHW_OK;
+}
+
+int bhw_apply_frames_len_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_frames *f, const int32_t *d_x,
+                                int32_t *d_y)
+{
+    const int rc = bhwp_len_checks(p, length);
+    if (rc) return rc;
+    if (!bhwp_len_kernels(p, length, g_len_force)) return frames_impl(p, device, hip_stream, f, d_x, d_y, -1);
+    return frames_len(nullptr, p, length, device, hip_stream, f, d_x, d_y);
+}
+
+int bhw_apply_frames_len_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_frames *f,
+                                    const int32_t *d_x, int32_t *d_y)
+{
+    int rc = bhwp_len_checks(p, length);
+    if (rc) return rc;
+    if (!bhwp_len_kernels(p, length, g_len_force)) return bhw_apply_frames_from_table(t, p, hip_stream, f, d_x, d_y);
+    if (!t) return fail(BHW_ERR_BADARG, "table is NULL");
+    return frames_len(t, p, length, t->device, hip_stream, f, d_x, d_y);
+}
+
+int bhw_overlap_add_len_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_ola *o, const int32_t *d_y,
+                               int32_t *d_x)
+{
+    const int rc = bhwp_len_checks(p, length);
+    if (rc) return rc;
+    if (!bhwp_len_kernels(p, length, g_len_force)) return ola_impl(p, device, hip_stream, o, d_y, d_x, 0, 0);
+    return ola_len(nullptr, p, length, device, hip_stream, o, d_y, d_x);
+}
+
+int bhw_overlap_add_len_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_ola *o, const int32_t *d_y,
+                                   int32_t *d_x)
+{
+    const int rc = bhwp_len_checks(p, length);
+    if (rc) return rc;
+    if (!bhwp_len_kernels(p, length, g_len_force)) return bhw_overlap_add_from_table(t, p, hip_stream, o, d_y, d_x);
+    if (!t) return fail(BHW_ERR_BADARG, "table is NULL");
+    return ola_len(t, p, length, t->device, hip_stream, o, d_y, d_x);
+}
+
+int bhw_describe_len(bhw_table t, const bhw_params *p, uint64_t length, uint64_t n0, uint64_t count, const bhw_frames *f, const bhw_ola *o,
+                     char *buf, uint64_t len)
+{
+    int rc = bhwp_len_checks(p, length);
+    if (!rc && t) rc = table_call_checks(t, p);
+    if (!rc && f) rc = bhwp_frames_checks(p, f, nullptr, nullptr, false, length);
+    if (!rc && o) rc = bhwp_ola_checks(p, o, nullptr, nullptr, false, length);
+    return rc ? rc : bhwp_describe_len(p, t ? &t->c : nullptr, t ? t->tiled : false, length, g_len_force, n0, count, f, o, buf, len);
+}
+
+// Development hook (not part of the ABI in include/bhw.h): on != 0 sends the *_len calls at L = 2^phi_width to the any-length kernels
+// as well (process-wide), so that tests can compare them with the power-of-two kernels.  Returns the previous setting.
+int bhw_dbg_len_force_kernels(int on) { return g_len_force.exchange(on != 0) ? 1 : 0; }
 
 } // extern "C"

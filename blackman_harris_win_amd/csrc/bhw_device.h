@@ -723,34 +723,54 @@ __device__ __forceinline__ void rot_step_dyn(int64_t &x, int64_t &y, int32_t &z,
     else       z = (int32_t)((uint32_t)z - lutk + ((2u * lutk) & (uint32_t)m));
 }
 
+// The phase maps of the coefficient functions below: theta_of(k) is the angle of harmonic k, called for k = 1, 2, ... in order.
+// A power-of-two window passes (k * n) & mask, which compiles to the code it always was; a window of any length passes LenTheta
+// (bhw_len.h), which keeps m_k = (k * m) mod L from call to call.
+struct LenTheta {
+    BhwLenPhase lp;
+    uint64_t m, mk;      // m = n mod L, m_k of the last call
+    __device__ __forceinline__ uint32_t operator()(uint32_t)
+    {
+        mk = bhw_len_step(mk, m, lp);
+        return bhw_len_theta(mk, lp);
+    }
+};
+__device__ __forceinline__ LenTheta len_theta_of(const BhwLenPhase &lp, uint64_t m) { return LenTheta{lp, m, 0u}; }
+
 // Coefficient n (masked phase) by K-1 full CORDIC chains: the per-lane work of k_direct (bhw_direct.hip) and k_frames_direct
 // (bhw_frames.hip).  lut: the rescaled ROM staged by stage_lut<T>.
-template <typename T>
-__device__ __forceinline__ int32_t direct_coeff(const BhwCordicCfg &cfg, const BhwWinCfg &win, const T *lut, uint32_t n)
+template <typename T, typename PH>
+__device__ __forceinline__ int32_t direct_coeff_ph(const BhwCordicCfg &cfg, const BhwWinCfg &win, const T *lut, PH theta_of)
 {
-    const uint32_t mask = (cfg.phi_width >= 32) ? 0xFFFFFFFFu : ((1u << cfg.phi_width) - 1u);
     int64_t acc = win.aa[0];
     for (uint32_t k = 1; k < win.n_terms; ++k) {
-        const uint32_t theta = (k * n) & mask;                     // ph_ink += k: bh_win_7term.vhd:187-194 | cordic(k*i): win_function.cpp:361-366
+        const uint32_t theta = theta_of(k);
         int32_t c, s;
         cordic_full<T>(cfg, lut, theta, c, s);
         combine_term(acc, win.aa[k], c, k, cfg.dat_width, win.combine);
     }
     return combine_final(acc, cfg.dat_width, win.combine, win.n_terms);
 }
+template <typename T>
+__device__ __forceinline__ int32_t direct_coeff(const BhwCordicCfg &cfg, const BhwWinCfg &win, const T *lut, uint32_t n)
+{
+    const uint32_t mask = (cfg.phi_width >= 32) ? 0xFFFFFFFFu : ((1u << cfg.phi_width) - 1u);
+    // ph_ink += k: bh_win_7term.vhd:187-194 | cordic(k*i): win_function.cpp:361-366
+    return direct_coeff_ph<T>(cfg, win, lut, [&](uint32_t k) { return (k * n) & mask; });
+}
 
 // Coefficient n by K-1 full CORDIC chains in the mad-form rotation of k_direct_fast (rot_step: |x| < 2^33, quarter circle <= 2^32),
 // with the chain as a rolled loop on a scalar counter (rot_step_dyn) instead of one unrolled instance per rotation count: the per-lane work
 // of k_frames_direct (bhw_frames.hip) and k_ola_direct (bhw_ola.hip), where the coefficient is spread over many frames or hops,
 // so the 26 NITER instances of k_direct_fast would buy little.
-__device__ __forceinline__ int32_t direct_coeff_mad(const BhwCordicCfg &cfg, const BhwWinCfg &win, const uint32_t *lut, uint32_t n)
+template <typename PH>
+__device__ __forceinline__ int32_t direct_coeff_mad_ph(const BhwCordicCfg &cfg, const BhwWinCfg &win, const uint32_t *lut, PH theta_of)
 {
     const uint32_t pw = cfg.phi_width;
-    const uint32_t mask = (pw >= 32) ? 0xFFFFFFFFu : ((1u << pw) - 1u);
     const uint32_t tmask = (1u << (pw - 2)) - 1u;
     int64_t acc = win.aa[0];
     for (uint32_t k = 1; k < win.n_terms; ++k) {
-        const uint32_t theta = (k * n) & mask;
+        const uint32_t theta = theta_of(k);
         const uint32_t u = (theta & tmask) >> cfg.z_shr;
         int64_t x = cfg.x0, y = cfg.x0;                                          // rotation 0 always adds (z0 >= 0)
         int32_t z = (int32_t)((u << cfg.z_shl) - lut[0]);
@@ -762,6 +782,12 @@ __device__ __forceinline__ int32_t direct_coeff_mad(const BhwCordicCfg &cfg, con
     }
     return combine_final(acc, cfg.dat_width, win.combine, win.n_terms);
 }
+__device__ __forceinline__ int32_t direct_coeff_mad(const BhwCordicCfg &cfg, const BhwWinCfg &win, const uint32_t *lut, uint32_t n)
+{
+    const uint32_t pw = cfg.phi_width;
+    const uint32_t mask = (pw >= 32) ? 0xFFFFFFFFu : ((1u << pw) - 1u);
+    return direct_coeff_mad_ph(cfg, win, lut, [&](uint32_t k) { return (k * n) & mask; });
+}
 
 // ---------------------------------------------------------------------------------------
 // Coefficient n (0 <= n < 2^PW) gathered from a resident table in any format: the per-lane work of k_range_combine
@@ -770,13 +796,14 @@ __device__ __forceinline__ int32_t direct_coeff_mad(const BhwCordicCfg &cfg, con
 // in k_table_combine_fold_t: 0 HLS rule, 1 HLS rule with the one's-complement quadrant map (cpp model), 2 VHDL rule.  The K - 1
 // gathers of a lane issue together, and the escape format costs one test per lane (the minimum of its low fields over the
 // harmonics) with the rare marked lane resolved on the scalar unit (esc_fix_wave): every lane of the wave must reach this call.
+// theta_of: the phase map (above); range_coeff is the power-of-two one.
 // ---------------------------------------------------------------------------------------
-template <int FMT, int NT, int MODE>
-__device__ __forceinline__ int32_t range_coeff(const BhwCordicCfg &cfg, const BhwWinCfg &win, const void *__restrict__ table, uint32_t n)
+template <int FMT, int NT, int MODE, typename PH>
+__device__ __forceinline__ int32_t range_coeff_ph(const BhwCordicCfg &cfg, const BhwWinCfg &win, const void *__restrict__ table, PH theta_of)
 {
     constexpr uint32_t COMBINE = MODE == 2 ? BHW_COMBINE_VHDL : BHW_COMBINE_HLS;
     const uint32_t pw = cfg.phi_width, W = cfg.dat_width;
-    const uint32_t mask = (1u << pw) - 1u, tmask = (1u << (pw - 2u)) - 1u;
+    const uint32_t tmask = (1u << (pw - 2u)) - 1u;
     const uint32_t lq = pw - 2u - cfg.z_shr;                       // log2 of the table's entries
     const uint32_t nt = win.n_terms;
     int2 cs[NT];
@@ -790,7 +817,7 @@ __device__ __forceinline__ int32_t range_coeff(const BhwCordicCfg &cfg, const Bh
         q[k] = 0u;
         ent[k] = byte[k] = 0u;
         if ((uint32_t)k < nt) {
-            const uint32_t theta = ((uint32_t)k * n) & mask;
+            const uint32_t theta = theta_of((uint32_t)k);
             q[k] = theta >> (pw - 2u);
             const uint32_t u = (theta & tmask) >> cfg.z_shr;
             if constexpr (FMT == 5) {
@@ -827,6 +854,12 @@ __device__ __forceinline__ int32_t range_coeff(const BhwCordicCfg &cfg, const Bh
         }
     }
     return w32_final<COMBINE>(acc, W, nt);
+}
+template <int FMT, int NT, int MODE>
+__device__ __forceinline__ int32_t range_coeff(const BhwCordicCfg &cfg, const BhwWinCfg &win, const void *__restrict__ table, uint32_t n)
+{
+    const uint32_t mask = (1u << cfg.phi_width) - 1u;
+    return range_coeff_ph<FMT, NT, MODE>(cfg, win, table, [&](uint32_t k) { return (k * n) & mask; });
 }
 
 inline unsigned grid_for(uint64_t count) { return (unsigned)((count + kBlock - 1) / kBlock); }

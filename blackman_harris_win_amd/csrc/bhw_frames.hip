@@ -111,10 +111,39 @@ __global__ __launch_bounds__(kFramesBlock) void k_frames_table(BhwCordicCfg cfg,
     frames_apply(a, k, threadIdx.x / a.kx, range_coeff<FMT, NT, MODE>(cfg, win, table, k));
 }
 
+// Windows of any length L (bhw_len.h): the same two sources with coefficient k read at the angles of the length-L phase map.  The
+// grid covers ceil(L / kx) * kx lanes along k; the lanes past L apply nothing (the table form still gathers, at k = 0, so that the
+// escape format's wave-wide fix is reached by every lane).
+template <int FORM>
+__global__ __launch_bounds__(kFramesBlock) void k_frames_direct_len(BhwCordicCfg cfg, BhwWinCfg win, FramesArgs a, BhwLenPhase lp)
+{
+    using T = std::conditional_t<FORM == 0, int32_t, int64_t>;
+    using L = std::conditional_t<FORM == 2, uint32_t, T>;
+    __shared__ L lut_s[32];
+    if (threadIdx.x < 32) lut_s[threadIdx.x] = (L)cfg.lut[threadIdx.x];
+    __syncthreads();
+    const uint32_t k = blockIdx.x * a.kx + (threadIdx.x & (a.kx - 1u));
+    if (k >= lp.len) return;
+    int32_t w;
+    if constexpr (FORM == 2) w = direct_coeff_mad_ph(cfg, win, lut_s, len_theta_of(lp, k));
+    else                     w = direct_coeff_ph<T>(cfg, win, lut_s, len_theta_of(lp, k));
+    frames_apply(a, k, threadIdx.x / a.kx, w);
+}
+
+template <int FMT, int NT, int MODE>
+__global__ __launch_bounds__(kFramesBlock) void k_frames_table_len(BhwCordicCfg cfg, BhwWinCfg win, const void *__restrict__ table, FramesArgs a,
+                                                                    BhwLenPhase lp)
+{
+    const uint32_t k = blockIdx.x * a.kx + (threadIdx.x & (a.kx - 1u));
+    const bool in = k < lp.len;
+    const int32_t w = range_coeff_ph<FMT, NT, MODE>(cfg, win, table, len_theta_of(lp, in ? k : 0u));
+    if (in) frames_apply(a, k, threadIdx.x / a.kx, w);
+}
+
 } // namespace
 
 int bhwk_frames(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinCfg &w, const BhwFramesPlan &pl, const bhw_frames *f,
-                const int32_t *d_x, int32_t *d_y, const int32_t *d_table)
+                const int32_t *d_x, int32_t *d_y, const int32_t *d_table, const BhwLenPhase *lp)
 {
     if (!f->frames) return 0;
     hipStream_t st = (hipStream_t)l.stream;
@@ -131,13 +160,19 @@ int bhwk_frames(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinCfg &w
     a.io = f->channels == 1 ? 0u : ((((uintptr_t)d_x | (uintptr_t)d_y) % 8 == 0 && pl.y_stride % 2 == 0) ? 2u : 1u);
     const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y), block(kFramesBlock);
     if (!d_table) {
-        with_int_or_last<2, 1, 0>(direct_form(c_in), [&](auto D) { launch(k_frames_direct<D>, grid, block, st, c_in, w, a); });
+        with_int_or_last<2, 1, 0>(direct_form(c_in), [&](auto D) {
+            if (lp) launch(k_frames_direct_len<D>, grid, block, st, c_in, w, a, *lp);
+            else    launch(k_frames_direct<D>, grid, block, st, c_in, w, a);
+        });
         return finish(hipSuccess);
     }
     const BhwCordicCfg c = table_layout(c_in);
     int fmt, nt, mode;
     if (!bhwp_range_form(c, w, &fmt, &nt, &mode)) return (int)hipErrorInvalidValue;   // every format a resident table holds has instances
     const void *tab = (const void *)d_table;
-    with_range_form(fmt, nt, mode, [&](auto F, auto NT, auto M) { launch(k_frames_table<F, NT, M>, grid, block, st, c, w, tab, a); });
+    with_range_form(fmt, nt, mode, [&](auto F, auto NT, auto M) {
+        if (lp) launch(k_frames_table_len<F, NT, M>, grid, block, st, c, w, tab, a, *lp);
+        else    launch(k_frames_table<F, NT, M>, grid, block, st, c, w, tab, a);
+    });
     return finish(hipSuccess);
 }

@@ -25,7 +25,7 @@ typedef int ola_v2i __attribute__((ext_vector_type(2)));      // one I/Q pair (t
 struct OlaArgs {
     const int32_t *y;
     int32_t *x;
-    uint64_t n;          // N = 2^phi_width
+    uint64_t n;          // N = 2^phi_width, or the length L of a window of any length
     uint64_t frames, hop, y_stride, count;
     uint64_t lanes;      // residues in use: min(hop, count)
     uint64_t rows;       // ceil(count / hop)
@@ -162,18 +162,40 @@ __global__ __launch_bounds__(kOlaBlock) void k_ola_table(BhwCordicCfg cfg, BhwWi
     ola_io<IO>(a, [&](uint32_t k) -> int32_t { return range_coeff<FMT, NT, MODE>(cfg, win, table, k); });
 }
 
+// Windows of any length L (bhw_len.h): the same two sources with coefficient k read at the angles of the length-L phase map (OlaArgs.n
+// is L, so the frames that reach a residue and the coefficients a lane takes are those of the length-L window).
+template <int FORM, int IO>
+__global__ __launch_bounds__(kOlaBlock) void k_ola_direct_len(BhwCordicCfg cfg, BhwWinCfg win, OlaArgs a, BhwLenPhase lp)
+{
+    using T = std::conditional_t<FORM == 0, int32_t, int64_t>;
+    using L = std::conditional_t<FORM == 2, uint32_t, T>;
+    __shared__ L lut_s[32];
+    if (threadIdx.x < 32) lut_s[threadIdx.x] = (L)cfg.lut[threadIdx.x];
+    __syncthreads();
+    ola_io<IO>(a, [&](uint32_t k) -> int32_t {
+        if constexpr (FORM == 2) return direct_coeff_mad_ph(cfg, win, lut_s, len_theta_of(lp, k));
+        else                     return direct_coeff_ph<T>(cfg, win, lut_s, len_theta_of(lp, k));
+    });
+}
+
+template <int FMT, int NT, int MODE, int IO>
+__global__ __launch_bounds__(kOlaBlock) void k_ola_table_len(BhwCordicCfg cfg, BhwWinCfg win, const void *__restrict__ table, OlaArgs a,
+                                                              BhwLenPhase lp)
+{
+    ola_io<IO>(a, [&](uint32_t k) -> int32_t { return range_coeff_ph<FMT, NT, MODE>(cfg, win, table, len_theta_of(lp, k)); });
+}
 
 } // namespace
 
 int bhwk_ola(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinCfg &w, const BhwOlaPlan &pl, const bhw_ola *o,
-             const int32_t *d_y, int32_t *d_x, const int32_t *d_table)
+             const int32_t *d_y, int32_t *d_x, const int32_t *d_table, const BhwLenPhase *lp)
 {
     if (!o->count) return 0;
     hipStream_t st = (hipStream_t)l.stream;
     OlaArgs a;
     a.y = d_y;
     a.x = d_x;
-    a.n = 1ull << c_in.phi_width;
+    a.n = pl.len;                                                  // N = 2^phi_width, or L
     a.frames = o->frames;
     a.hop = o->hop;
     a.y_stride = pl.y_stride;
@@ -184,7 +206,7 @@ int bhwk_ola(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinCfg &w, c
     a.q0 = pl.q0;
     a.r0 = pl.r0;
     a.jmax = (int64_t)pl.jmax;
-    a.rlim = a.n - (pl.jmax - 1) * o->hop;                         // (jmax - 1) * hop < N
+    a.rlim = a.n - (pl.jmax - 1) * o->hop;                         // (jmax - 1) * hop < N (or L)
     a.rx = pl.rx;
     a.fy = pl.fy;
     a.q = pl.q;
@@ -193,7 +215,10 @@ int bhwk_ola(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinCfg &w, c
     const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y), block(kOlaBlock);
     if (!d_table) {
         with_int_or_last<0, 1, 2>(a.io, [&](auto IO) {
-            with_int_or_last<2, 1, 0>(direct_form(c_in), [&](auto D) { launch(k_ola_direct<D, IO>, grid, block, st, c_in, w, a); });
+            with_int_or_last<2, 1, 0>(direct_form(c_in), [&](auto D) {
+                if (lp) launch(k_ola_direct_len<D, IO>, grid, block, st, c_in, w, a, *lp);
+                else    launch(k_ola_direct<D, IO>, grid, block, st, c_in, w, a);
+            });
         });
         return finish(hipSuccess);
     }
@@ -202,7 +227,10 @@ int bhwk_ola(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinCfg &w, c
     if (!bhwp_range_form(c, w, &fmt, &nt, &mode)) return (int)hipErrorInvalidValue;   // every format a resident table holds has instances
     const void *tab = (const void *)d_table;
     with_range_form(fmt, nt, mode, [&](auto F, auto NT, auto M) {
-        with_int_or_last<0, 1, 2>(a.io, [&](auto IO) { launch(k_ola_table<F, NT, M, IO>, grid, block, st, c, w, tab, a); });
+        with_int_or_last<0, 1, 2>(a.io, [&](auto IO) {
+            if (lp) launch(k_ola_table_len<F, NT, M, IO>, grid, block, st, c, w, tab, a, *lp);
+            else    launch(k_ola_table<F, NT, M, IO>, grid, block, st, c, w, tab, a);
+        });
     });
     return finish(hipSuccess);
 }

@@ -729,7 +729,7 @@ int bhwp_describe_from_table(const bhw_params *p, const BhwCordicCfg &ct, bool t
 
 // ---- overlapped-frame apply --------------------------------------------------------------------------------------------------
 
-int bhwp_frames_checks(const bhw_params *p, const bhw_frames *f, const void *d_x, const void *d_y, bool pointers)
+int bhwp_frames_checks(const bhw_params *p, const bhw_frames *f, const void *d_x, const void *d_y, bool pointers, uint64_t length)
 {
     if (!p) return bhwp_fail(BHW_ERR_BADARG, "params is NULL");
     int rc = bhwp_validate(p);
@@ -740,7 +740,7 @@ int bhwp_frames_checks(const bhw_params *p, const bhw_frames *f, const void *d_x
     if (f->hop == 0) return bhwp_fail(BHW_ERR_BADARG, "hop is 0");
     if (f->shift > 62) return bhwp_fail(BHW_ERR_BADARG, "shift %u > 62", f->shift);
     if (f->reserved) return bhwp_fail(BHW_ERR_BADARG, "bhw_frames.reserved must be 0");
-    const uint64_t N = 1ull << p->phi_width, NC = N * f->channels;
+    const uint64_t N = length ? length : 1ull << p->phi_width, NC = N * f->channels;
     if (f->y_stride && f->y_stride < NC)
         return bhwp_fail(BHW_ERR_BADARG, "y_stride %llu < N * channels = %llu", (unsigned long long)f->y_stride, (unsigned long long)NC);
     if (p->sin_type != BHW_SIN_CORDIC && f->channels == 2)
@@ -760,12 +760,14 @@ int bhwp_frames_checks(const bhw_params *p, const bhw_frames *f, const void *d_x
     return BHW_OK;
 }
 
-BhwFramesPlan bhwp_frames_plan(const bhw_params *p, const bhw_frames *f, bool from_table, int force_route)
+BhwFramesPlan bhwp_frames_plan(const bhw_params *p, const bhw_frames *f, bool from_table, int force_route, uint64_t length)
 {
     BhwFramesPlan pl{};
-    const uint64_t N = 1ull << p->phi_width;
+    const uint64_t N = length ? length : 1ull << p->phi_width;
+    pl.len = N;
     pl.y_stride = f->y_stride ? f->y_stride : N * f->channels;
     if (from_table) pl.route = BHWP_FRAMES_TABLE;
+    else if (length) pl.route = BHWP_FRAMES_DIRECT;                            // the any-length kernels have no per-frame route
     else if (f->channels == 2) pl.route = BHWP_FRAMES_DIRECT;                  // the existing apply has no I/Q form
     else if (p->sin_type != BHW_SIN_CORDIC) pl.route = BHWP_FRAMES_PER_FRAME;  // no frames kernel for the Taylor sources
     else {
@@ -778,9 +780,10 @@ BhwFramesPlan bhwp_frames_plan(const bhw_params *p, const bhw_frames *f, bool fr
     if (force_route >= 0 && !from_table && force_route != BHWP_FRAMES_TABLE &&
         !(force_route == BHWP_FRAMES_PER_FRAME && f->channels == 2) && !(force_route == BHWP_FRAMES_DIRECT && p->sin_type != BHW_SIN_CORDIC))
         pl.route = force_route;
-    pl.kx = N < kFramesBlock ? (uint32_t)N : kFramesBlock;
+    pl.kx = 1;                                                                 // N itself, or the power of two at or above L
+    while (pl.kx < kFramesBlock && pl.kx < N) pl.kx *= 2;
     pl.fy = kFramesBlock / pl.kx;
-    pl.grid_x = N / pl.kx;
+    pl.grid_x = (N + pl.kx - 1) / pl.kx;
     if (pl.route == BHWP_FRAMES_PER_FRAME || !f->frames) return pl;
     // frame rows of fy frames; as many workgroups as kFramesTargetWg asks for, each lane then applies its coefficient to G rows
     const uint64_t rows = (f->frames + pl.fy - 1) / pl.fy;
@@ -828,7 +831,7 @@ int bhwp_describe_frames(const bhw_params *p, const BhwCordicCfg *ct, const bhw_
 
 // ---- weighted overlap-add ----------------------------------------------------------------------------------------------------
 
-int bhwp_ola_checks(const bhw_params *p, const bhw_ola *o, const void *d_y, const void *d_x, bool pointers)
+int bhwp_ola_checks(const bhw_params *p, const bhw_ola *o, const void *d_y, const void *d_x, bool pointers, uint64_t length)
 {
     if (!p) return bhwp_fail(BHW_ERR_BADARG, "params is NULL");
     int rc = bhwp_validate(p);
@@ -839,7 +842,7 @@ int bhwp_ola_checks(const bhw_params *p, const bhw_ola *o, const void *d_y, cons
     if (o->channels != 1 && o->channels != 2) return bhwp_fail(BHW_ERR_BADARG, "channels %u (1 or 2)", o->channels);
     if (o->hop == 0) return bhwp_fail(BHW_ERR_BADARG, "hop is 0");
     if (o->shift > 62) return bhwp_fail(BHW_ERR_BADARG, "shift %u > 62", o->shift);
-    const uint64_t N = 1ull << p->phi_width, NC = N * o->channels;
+    const uint64_t N = length ? length : 1ull << p->phi_width, NC = N * o->channels;
     if (o->y_stride && o->y_stride < NC)
         return bhwp_fail(BHW_ERR_BADARG, "y_stride %llu < N * channels = %llu", (unsigned long long)o->y_stride, (unsigned long long)NC);
     if (p->sin_type != BHW_SIN_CORDIC)
@@ -866,10 +869,11 @@ int bhwp_ola_checks(const bhw_params *p, const bhw_ola *o, const void *d_y, cons
     return BHW_OK;
 }
 
-BhwOlaPlan bhwp_ola_plan(const bhw_params *p, const bhw_ola *o, bool from_table, uint32_t force_q, uint32_t force_rx)
+BhwOlaPlan bhwp_ola_plan(const bhw_params *p, const bhw_ola *o, bool from_table, uint32_t force_q, uint32_t force_rx, uint64_t length)
 {
     BhwOlaPlan pl{};
-    const uint64_t N = 1ull << p->phi_width;
+    const uint64_t N = length ? length : 1ull << p->phi_width;
+    pl.len = N;
     pl.route = from_table ? BHWP_OLA_TABLE : BHWP_OLA_DIRECT;
     pl.y_stride = o->y_stride ? o->y_stride : N * o->channels;
     pl.q0 = o->t0 / o->hop;
@@ -925,6 +929,72 @@ int bhwp_describe_ola(const bhw_params *p, const BhwCordicCfg *ct, const bhw_ola
     snprintf(buf, len, "overlap-add %s: %s, %u channel%s, Q = %u hops per lane, up to %llu frames per output, grid %llu x %llu x %u lanes "
              "(%u along r, %u along q)", pl.route == BHWP_OLA_TABLE ? "table" : "direct", kern, o->channels, o->channels == 2 ? "s" : "",
              pl.q, (unsigned long long)pl.jmax, (unsigned long long)pl.grid_x, (unsigned long long)pl.grid_y, kOlaBlock, pl.rx, pl.fy);
+    return BHW_OK;
+}
+
+// ---- windows of any length ------------------------------------------------------------------------------------------------------
+
+int bhwp_len_checks(const bhw_params *p, uint64_t length)
+{
+    if (!p) return bhwp_fail(BHW_ERR_BADARG, "params is NULL");
+    const int rc = bhwp_validate(p);
+    if (rc) return rc;
+    const uint64_t N = 1ull << p->phi_width;
+    if (length == 0 || length > N)
+        return bhwp_fail(BHW_ERR_BADARG, "length %llu outside 1..2^phi_width = %llu", (unsigned long long)length, (unsigned long long)N);
+    if (p->sin_type != BHW_SIN_CORDIC)
+        return bhwp_fail(BHW_ERR_UNSUPPORTED, "windows of any length take the CORDIC source only (sin_type %u)", p->sin_type);
+    return BHW_OK;
+}
+
+int bhwp_describe_len(const bhw_params *p, const BhwCordicCfg *ct, bool tiled, uint64_t length, bool force, uint64_t n0, uint64_t count,
+                      const bhw_frames *f, const bhw_ola *o, char *buf, uint64_t len)
+{
+    if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
+    if (f && o) return bhwp_fail(BHW_ERR_BADARG, "pass a frames or an overlap-add descriptor, not both");
+    char inner[384];
+    int rc = BHW_OK;
+    if (!bhwp_len_kernels(p, length, force)) {
+        if (f)       rc = bhwp_describe_frames(p, ct, f, inner, sizeof inner);
+        else if (o)  rc = bhwp_describe_ola(p, ct, o, inner, sizeof inner);
+        else if (ct) rc = bhwp_describe_from_table(p, *ct, tiled, n0, count, inner, sizeof inner);
+        else         rc = bhw_describe_plan(p, n0, count, nullptr, inner, sizeof inner);
+        if (rc) return rc;
+        snprintf(buf, len, "power-of-two route (L = 2^%u): %s", p->phi_width, inner);
+        return BHW_OK;
+    }
+    BhwCordicCfg c;
+    bhwp_resolve_cordic(p, c);
+    BhwWinCfg w;
+    bhwp_resolve_window(p, w);
+    char form[32];
+    if (ct) {
+        int fmt, nt, mode;
+        bhwp_range_form(table_layout(*ct), w, &fmt, &nt, &mode);
+        snprintf(form, sizeof form, "<%d,%d,%d>", fmt, nt, mode);
+    } else {
+        snprintf(form, sizeof form, "<%d>", direct_form(c));
+    }
+    const char *src = ct ? "table" : "direct";
+    if (f) {
+        const BhwFramesPlan pl = bhwp_frames_plan(p, f, ct != nullptr, -1, length);
+        snprintf(inner, sizeof inner, "k_frames_%s_len%s, %u channel%s, G = %llu frames per lane, grid %llu x %llu x %u lanes (%u along k)",
+                 src, form, f->channels, f->channels == 2 ? "s" : "", (unsigned long long)pl.group, (unsigned long long)pl.grid_x,
+                 (unsigned long long)pl.grid_y, kFramesBlock, pl.kx);
+    } else if (o) {
+        if (!o->count) {
+            snprintf(inner, sizeof inner, "overlap-add: nothing (count 0)");
+        } else {
+            const BhwOlaPlan pl = bhwp_ola_plan(p, o, ct != nullptr, 0, 0, length);
+            snprintf(inner, sizeof inner, "k_ola_%s_len%s, %u channel%s, Q = %u hops per lane, up to %llu frames per output, grid %llu x %llu x "
+                     "%u lanes (%u along r, %u along q)", src, form, o->channels, o->channels == 2 ? "s" : "", pl.q, (unsigned long long)pl.jmax,
+                     (unsigned long long)pl.grid_x, (unsigned long long)pl.grid_y, kOlaBlock, pl.rx, pl.fy);
+        }
+    } else {
+        snprintf(inner, sizeof inner, "%s%s, %llu coefficients from n0 mod L = %llu", ct ? "k_range_len" : "k_direct_len", form,
+                 (unsigned long long)count, (unsigned long long)(n0 % length));
+    }
+    snprintf(buf, len, "any-length route (L = %llu, phi_width %u): %s", (unsigned long long)length, p->phi_width, inner);
     return BHW_OK;
 }
 

@@ -16,6 +16,7 @@
 #else
 #define BHW_HD
 #endif
+#include "bhw_len.h"
 
 // ---- table formats (bhw_device.h documents the encodings) -----------------------------------------------------------------------
 constexpr uint32_t kPackLog = 6;                // cfg.tab_dlog = 6: delta16
@@ -180,17 +181,22 @@ struct BhwFramesPlan {
     uint64_t grid_x;     // N / kx
     uint64_t grid_y;     // ceil(frames / (fy * G)) <= kFramesMaxGridY
     uint64_t y_stride;   // resolved (0 -> N * channels)
+    uint64_t len;        // N = 2^phi_width, or the length L of the any-length kernels
 };
 // Every argument check of the two calls that needs no table handle, before any HIP call: BHW_OK, BADARG or UNSUPPORTED (Taylor with
 // two channels).  frames == 0 passes with the pointers unchecked (nothing to do); `pointers` false: the describe call, no pointers.
-int  bhwp_frames_checks(const bhw_params *p, const bhw_frames *f, const void *d_x, const void *d_y, bool pointers = true);
-// route, frame-group size and grid of a call that passed bhwp_frames_checks; force_route >= 0 overrides the route rule (A/B runs)
-BhwFramesPlan bhwp_frames_plan(const bhw_params *p, const bhw_frames *f, bool from_table, int force_route = -1);
+// length > 0: the checks of a window of that length (bhwp_len_checks passed), with L in place of N.
+int  bhwp_frames_checks(const bhw_params *p, const bhw_frames *f, const void *d_x, const void *d_y, bool pointers = true, uint64_t length = 0);
+// route, frame-group size and grid of a call that passed bhwp_frames_checks; force_route >= 0 overrides the route rule (A/B runs).
+// length > 0: the any-length kernels (k_frames_direct_len / k_frames_table_len) over a window of length L: kx the power of two at or
+// above min(L, kFramesBlock), grid_x = ceil(L / kx).  At a power-of-two L the shape is the one of length 0.
+BhwFramesPlan bhwp_frames_plan(const bhw_params *p, const bhw_frames *f, bool from_table, int force_route = -1, uint64_t length = 0);
 // bhw_apply_frames_describe: ct = the resident table's resolved configuration (format and layout set), or NULL for the library call
 int  bhwp_describe_frames(const bhw_params *p, const BhwCordicCfg *ct, const bhw_frames *f, char *buf, uint64_t len);
-// the frames kernel of a plan (bhw_frames.hip): d_table NULL = k_frames_direct, else k_frames_table over the resident table of c
+// the frames kernel of a plan (bhw_frames.hip): d_table NULL = k_frames_direct, else k_frames_table over the resident table of c;
+// lp != NULL: their any-length forms over the window of length lp->len
 int  bhwk_frames(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwFramesPlan &pl, const bhw_frames *f,
-                 const int32_t *d_x, int32_t *d_y, const int32_t *d_table);
+                 const int32_t *d_x, int32_t *d_y, const int32_t *d_table, const BhwLenPhase *lp = nullptr);
 
 // ---- weighted overlap-add (bhw_overlap_add_device / _from_table) --------------------------------------------------------------
 // Output t = q * hop + r.  A lane owns one residue r and a block of Q consecutive hops q: it computes w[r + j * hop] once per j and
@@ -216,15 +222,38 @@ struct BhwOlaPlan {
     uint64_t jmax;       // ceil(N / hop): frames that reach the output of residue 0
     uint64_t y_stride;   // resolved (0 -> N * channels)
     uint64_t q0, r0;     // t0 = q0 * hop + r0
+    uint64_t len;        // N = 2^phi_width, or the length L of the any-length kernels
 };
 // Every argument check of the two calls that needs no table handle, before any HIP call: BHW_OK, BADARG or UNSUPPORTED (the Taylor
 // sources).  count == 0 passes with the pointers unchecked; `pointers` false: the describe call, no pointers.
-int  bhwp_ola_checks(const bhw_params *p, const bhw_ola *o, const void *d_y, const void *d_x, bool pointers = true);
+// length > 0: the checks of a window of that length (bhwp_len_checks passed), with L in place of N.
+int  bhwp_ola_checks(const bhw_params *p, const bhw_ola *o, const void *d_y, const void *d_x, bool pointers = true, uint64_t length = 0);
 // route, Q, lane layout and grid of a call that passed bhwp_ola_checks with count > 0; force_q / force_rx > 0 override the rule
 // (bhw_dbg_overlap_add_shape: Q in 1..kOlaQMax, rx a power of two <= kOlaBlock; other values are ignored)
-BhwOlaPlan bhwp_ola_plan(const bhw_params *p, const bhw_ola *o, bool from_table, uint32_t force_q = 0, uint32_t force_rx = 0);
+// length > 0: the plan of the any-length kernels (k_ola_direct_len / k_ola_table_len) over a window of length L (jmax = ceil(L / hop));
+// at a power-of-two L it is the plan of length 0.
+BhwOlaPlan bhwp_ola_plan(const bhw_params *p, const bhw_ola *o, bool from_table, uint32_t force_q = 0, uint32_t force_rx = 0,
+                         uint64_t length = 0);
 // bhw_overlap_add_describe: ct = the resident table's resolved configuration (format and layout set), or NULL for the library call
 int  bhwp_describe_ola(const bhw_params *p, const BhwCordicCfg *ct, const bhw_ola *o, char *buf, uint64_t len);
 // the overlap-add kernel of a plan (bhw_ola.hip): d_table NULL = k_ola_direct, else k_ola_table over the resident table of c
+// lp != NULL: their any-length forms over the window of length lp->len (= pl.len)
 int  bhwk_ola(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwOlaPlan &pl, const bhw_ola *o,
-              const int32_t *d_y, int32_t *d_x, const int32_t *d_table);
+              const int32_t *d_y, int32_t *d_x, const int32_t *d_table, const BhwLenPhase *lp = nullptr);
+
+// ---- windows of any length (the *_len entry points; the phase map is bhw_len.h) -------------------------------------------------
+// Argument checks of every *_len call on (p, length), before any other and before any HIP call: p valid, 1 <= length <= 2^phi_width
+// (BADARG), CORDIC source (UNSUPPORTED, as for tables; the models DDS48 / SCALED are refused by bhwp_validate).
+int  bhwp_len_checks(const bhw_params *p, uint64_t length);
+// the call takes the any-length kernels: L != 2^phi_width, or `force` (bhw_dbg_len_force_kernels)
+inline bool bhwp_len_kernels(const bhw_params *p, uint64_t length, bool force) { return force || length != (1ull << p->phi_width); }
+// bhw_describe_len: one line naming the route, the kernel and whether the power-of-two route was taken.  Exactly one of: f (frames),
+// o (overlap-add), neither (generate [n0, n0 + count)).  ct / tiled: the resident table's resolved configuration and layout, or NULL
+// (library call).
+int  bhwp_describe_len(const bhw_params *p, const BhwCordicCfg *ct, bool tiled, uint64_t length, bool force, uint64_t n0, uint64_t count,
+                       const bhw_frames *f, const bhw_ola *o, char *buf, uint64_t len);
+// the generate kernels of a window of any length (bhw_len.hip): k_direct_len, or k_range_len over a resident table
+int  bhwk_direct_len(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwLenPhase &lp, uint64_t n0, uint64_t count,
+                     int32_t *d_out);
+int  bhwk_range_len(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *d_table, const BhwLenPhase &lp,
+                    uint64_t n0, uint64_t count, int32_t *d_out);

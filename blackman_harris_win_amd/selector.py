@@ -79,14 +79,20 @@ def prepare(params, *, device=None):
 
 
 def generate(params, n0, count, *, device=None, out=None, algo=B.ALGO_AUTO, workspace=None, event_after_build=None,
-             table_format=B.TABLE_BEST):
-    """count coefficients starting at stream index n0 as an int32 CUDA tensor (bhw_generate_device)."""
+             table_format=B.TABLE_BEST, length=None):
+    """count coefficients starting at stream index n0 as an int32 CUDA tensor (bhw_generate_device).  length: the window length L
+    (1..2^phi_width) of a window of any length (bhw_generate_len_device; algo, workspace, event_after_build and table_format do not
+    apply); None: the power-of-two window, N = 2^phi_width."""
     torch = _torch()
     dev = _dev_index(torch, device)
     if out is None:
         out = torch.empty(int(count), dtype=torch.int32, device=f"cuda:{dev}")
     else:
         dev = _check_out(torch, out, int(count))
+    if length is not None:
+        B.check(B.lib().bhw_generate_len_device(ctypes.byref(params), int(length), dev, _stream_ptr(torch, dev), int(n0), int(count),
+                                                ctypes.c_void_p(out.data_ptr())))
+        return out
     if workspace is not None and workspace.device.index != dev:
         raise ValueError("workspace must live on the output's device")
     ex = _exec(algo, workspace, event_after_build, table_format)
@@ -142,7 +148,24 @@ def apply(params, x, *, n0=0, shift=None, out=None):
     return out
 
 
-def _frames_call(torch, params, x, hop, frames, channels, shift, out, y_stride, dev):
+def _window_len(params, length):
+    """N: 2^phi_width, or the window length L of a call for a window of any length."""
+    return (1 << params.phi_width) if length is None else int(length)
+
+
+def window(params, length, *, sym=False, device=None, out=None):
+    """The int32 coefficients of the window of length `length` (1..2^phi_width): the periodic (DFT-even, spectral-analysis) window
+    bhw_generate_len_device(length, n0 = 0, count = length), or with sym=True the symmetric (filter-design) window: the periodic
+    window of length - 1 plus its first coefficient (length >= 2)."""
+    length = int(length)
+    if sym:
+        if length < 2:
+            raise ValueError("a symmetric window needs length >= 2")
+        return generate(params, 0, length, device=device, out=out, length=length - 1)
+    return generate(params, 0, length, device=device, out=out, length=length)
+
+
+def _frames_call(torch, params, x, hop, frames, channels, shift, out, y_stride, dev, length=None):
     """Checks and shapes of apply_frames: (bhw_frames, out, the tensor returned)."""
     if x.dtype != torch.int32 or not x.is_cuda or not x.is_contiguous() or x.device.index != dev:
         raise ValueError("x must be a contiguous int32 CUDA tensor on the call's device")
@@ -150,7 +173,7 @@ def _frames_call(torch, params, x, hop, frames, channels, shift, out, y_stride, 
         raise ValueError("channels must be 1 or 2")
     if hop < 1:
         raise ValueError("hop must be >= 1")
-    N = 1 << params.phi_width
+    N = _window_len(params, length)
     samples = x.numel() // channels
     if x.numel() % channels:
         raise ValueError("x must hold whole I/Q pairs")
@@ -176,22 +199,26 @@ def _frames_call(torch, params, x, hop, frames, channels, shift, out, y_stride, 
     return f, out, result
 
 
-def apply_frames(params, x, hop, *, frames=None, channels=1, shift=None, out=None, y_stride=None):
+def apply_frames(params, x, hop, *, frames=None, channels=1, shift=None, out=None, y_stride=None, length=None):
     """Overlapped-frame apply (bhw_apply_frames_device): y[f, k, c] = (x[(f * hop + k) * C + c] * w[k]) >> shift for every frame f,
     with one launch (the STFT / Welch front end).  x: contiguous int32 (time-major, I/Q interleaved for channels = 2); frames=None
     takes as many as fit.  Returns a (frames, N) int32 tensor, (frames, N, 2) for I/Q, or a (frames, y_stride) view when y_stride
-    is given (the elements past N * channels of each row are not written).  shift defaults to dat_width - 1."""
+    is given (the elements past N * channels of each row are not written).  shift defaults to dat_width - 1.  length: the window
+    length L of a window of any length (bhw_apply_frames_len_device; N is L in the shapes above); None: N = 2^phi_width."""
     torch = _torch()
     if not isinstance(x, torch.Tensor) or not x.is_cuda:
         raise ValueError("x must be a contiguous int32 CUDA tensor")
     dev = x.device.index
-    f, out, result = _frames_call(torch, params, x, int(hop), frames, channels, shift, out, y_stride, dev)
-    B.check(B.lib().bhw_apply_frames_device(ctypes.byref(params), dev, _stream_ptr(torch, dev), ctypes.byref(f),
-                                            ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr())))
+    f, out, result = _frames_call(torch, params, x, int(hop), frames, channels, shift, out, y_stride, dev, length)
+    args = (dev, _stream_ptr(torch, dev), ctypes.byref(f), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr()))
+    if length is None:
+        B.check(B.lib().bhw_apply_frames_device(ctypes.byref(params), *args))
+    else:
+        B.check(B.lib().bhw_apply_frames_len_device(ctypes.byref(params), int(length), *args))
     return result
 
 
-def _ola_call(torch, params, y, hop, frames, channels, shift, out, y_stride, t0, count, dev):
+def _ola_call(torch, params, y, hop, frames, channels, shift, out, y_stride, t0, count, dev, length=None):
     """Checks and shapes of overlap_add: (bhw_ola, out, the tensor returned)."""
     if not isinstance(y, torch.Tensor) or y.dtype != torch.int32 or not y.is_cuda or not y.is_contiguous() or y.device.index != dev:
         raise ValueError("y must be a contiguous int32 CUDA tensor on the call's device")
@@ -199,7 +226,7 @@ def _ola_call(torch, params, y, hop, frames, channels, shift, out, y_stride, t0,
         raise ValueError("channels must be 1 or 2")
     if hop < 1:
         raise ValueError("hop must be >= 1")
-    N = 1 << params.phi_width
+    N = _window_len(params, length)
     if y.dim() < 1:
         raise ValueError("y must be (frames, N), (frames, N, 2) or (frames, y_stride)")
     rows = y.shape[0]
@@ -227,19 +254,23 @@ def _ola_call(torch, params, y, hop, frames, channels, shift, out, y_stride, t0,
     return o, out, result
 
 
-def overlap_add(params, y, hop, *, frames=None, channels=1, shift=None, out=None, y_stride=None, t0=0, count=None):
+def overlap_add(params, y, hop, *, frames=None, channels=1, shift=None, out=None, y_stride=None, t0=0, count=None, length=None):
     """Weighted overlap-add (bhw_overlap_add_device), the STFT synthesis side in one launch:
     x[t - t0, c] = (sum over frames f of y[f, t - f * hop, c] * w[t - f * hop]) >> shift for t in [t0, t0 + count), the sum in
     int64 (wrapping), the low 32 bits stored.  y: contiguous int32 (frames, N), (frames, N, 2) for I/Q, or (frames, y_stride)
     rows of which the first N * channels are read.  frames=None takes every row; count=None the whole extent
-    (frames - 1) * hop + N from t0; shift defaults to dat_width - 1.  Returns (count,) int32, or (count, 2) for I/Q."""
+    (frames - 1) * hop + N from t0; shift defaults to dat_width - 1.  Returns (count,) int32, or (count, 2) for I/Q.  length: the
+    window length L of a window of any length (bhw_overlap_add_len_device; N is L above); None: N = 2^phi_width."""
     torch = _torch()
     if not isinstance(y, torch.Tensor) or not y.is_cuda:
         raise ValueError("y must be a contiguous int32 CUDA tensor")
     dev = y.device.index
-    o, out, result = _ola_call(torch, params, y, int(hop), frames, channels, shift, out, y_stride, t0, count, dev)
-    B.check(B.lib().bhw_overlap_add_device(ctypes.byref(params), dev, _stream_ptr(torch, dev), ctypes.byref(o),
-                                           ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(out.data_ptr())))
+    o, out, result = _ola_call(torch, params, y, int(hop), frames, channels, shift, out, y_stride, t0, count, dev, length)
+    args = (dev, _stream_ptr(torch, dev), ctypes.byref(o), ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(out.data_ptr()))
+    if length is None:
+        B.check(B.lib().bhw_overlap_add_device(ctypes.byref(params), *args))
+    else:
+        B.check(B.lib().bhw_overlap_add_len_device(ctypes.byref(params), int(length), *args))
     return result
 
 
@@ -293,17 +324,29 @@ class ResidentTable:
         """The table's format / layout and the kernels generate(params, n0, count) launches (bhw_table_describe)."""
         return B.describe_table(self._live(), params, n0, count)
 
-    def generate(self, params, n0, count, out=None):
-        """count coefficients from stream index n0 with params' weights (bhw_generate_from_table), on the current stream."""
+    def generate(self, params, n0, count, out=None, *, length=None):
+        """count coefficients from stream index n0 with params' weights (bhw_generate_from_table), on the current stream.  length:
+        the window length L of a window of any length (bhw_generate_len_from_table); None: N = 2^phi_width."""
         torch = _torch()
         h = self._live()
         if out is None:
             out = torch.empty(int(count), dtype=torch.int32, device=f"cuda:{self.device}")
         elif _check_out(torch, out, int(count)) != self.device:
             raise ValueError("out must live on the table's device")
-        B.check(B.lib().bhw_generate_from_table(h, ctypes.byref(params), _stream_ptr(torch, self.device), int(n0), int(count),
-                                                ctypes.c_void_p(out.data_ptr())))
+        if length is None:
+            B.check(B.lib().bhw_generate_from_table(h, ctypes.byref(params), _stream_ptr(torch, self.device), int(n0), int(count),
+                                                    ctypes.c_void_p(out.data_ptr())))
+        else:
+            B.check(B.lib().bhw_generate_len_from_table(h, ctypes.byref(params), int(length), _stream_ptr(torch, self.device), int(n0),
+                                                        int(count), ctypes.c_void_p(out.data_ptr())))
         return out
+
+    def window(self, params, length, *, sym=False, out=None):
+        """window() from this table: the periodic window of `length`, or with sym=True the symmetric one (length >= 2)."""
+        length = int(length)
+        if sym and length < 2:
+            raise ValueError("a symmetric window needs length >= 2")
+        return self.generate(params, 0, length, out=out, length=length - 1 if sym else length)
 
     def apply(self, params, x, n0=0, shift=None, out=None):
         """y[i] = (x[i] * w[n0+i]) >> shift (bhw_apply_from_table); shift defaults to dat_width - 1."""
@@ -321,32 +364,39 @@ class ResidentTable:
                                              ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr()), int(shift)))
         return out
 
-    def apply_frames(self, params, x, hop, *, frames=None, channels=1, shift=None, out=None, y_stride=None):
-        """apply_frames() with the coefficients gathered from this table (bhw_apply_frames_from_table): no allocation by the
-        library, no synchronisation, capturable into a graph."""
+    def apply_frames(self, params, x, hop, *, frames=None, channels=1, shift=None, out=None, y_stride=None, length=None):
+        """apply_frames() with the coefficients gathered from this table (bhw_apply_frames_from_table, or
+        bhw_apply_frames_len_from_table with a length): no allocation by the library, no synchronisation, capturable into a graph."""
         torch = _torch()
         h = self._live()
         if not isinstance(x, torch.Tensor) or not x.is_cuda or x.device.index != self.device:
             raise ValueError("x must be a contiguous int32 CUDA tensor on the table's device")
-        f, out, result = _frames_call(torch, params, x, int(hop), frames, channels, shift, out, y_stride, self.device)
-        B.check(B.lib().bhw_apply_frames_from_table(h, ctypes.byref(params), _stream_ptr(torch, self.device), ctypes.byref(f),
-                                                    ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr())))
+        f, out, result = _frames_call(torch, params, x, int(hop), frames, channels, shift, out, y_stride, self.device, length)
+        args = (_stream_ptr(torch, self.device), ctypes.byref(f), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr()))
+        if length is None:
+            B.check(B.lib().bhw_apply_frames_from_table(h, ctypes.byref(params), *args))
+        else:
+            B.check(B.lib().bhw_apply_frames_len_from_table(h, ctypes.byref(params), int(length), *args))
         return result
 
     def describe_frames(self, params, frames, hop, *, channels=1, y_stride=0):
         """The route and kernels apply_frames(params, ...) launches over this table (bhw_apply_frames_describe)."""
         return B.describe_frames(params, frames, hop, channels=channels, y_stride=y_stride, table=self._live())
 
-    def overlap_add(self, params, y, hop, *, frames=None, channels=1, shift=None, out=None, y_stride=None, t0=0, count=None):
-        """overlap_add() with the coefficients gathered from this table (bhw_overlap_add_from_table): no allocation by the
-        library, no synchronisation, capturable into a graph."""
+    def overlap_add(self, params, y, hop, *, frames=None, channels=1, shift=None, out=None, y_stride=None, t0=0, count=None,
+                    length=None):
+        """overlap_add() with the coefficients gathered from this table (bhw_overlap_add_from_table, or
+        bhw_overlap_add_len_from_table with a length): no allocation by the library, no synchronisation, capturable into a graph."""
         torch = _torch()
         h = self._live()
         if not isinstance(y, torch.Tensor) or not y.is_cuda or y.device.index != self.device:
             raise ValueError("y must be a contiguous int32 CUDA tensor on the table's device")
-        o, out, result = _ola_call(torch, params, y, int(hop), frames, channels, shift, out, y_stride, t0, count, self.device)
-        B.check(B.lib().bhw_overlap_add_from_table(h, ctypes.byref(params), _stream_ptr(torch, self.device), ctypes.byref(o),
-                                                   ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(out.data_ptr())))
+        o, out, result = _ola_call(torch, params, y, int(hop), frames, channels, shift, out, y_stride, t0, count, self.device, length)
+        args = (_stream_ptr(torch, self.device), ctypes.byref(o), ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(out.data_ptr()))
+        if length is None:
+            B.check(B.lib().bhw_overlap_add_from_table(h, ctypes.byref(params), *args))
+        else:
+            B.check(B.lib().bhw_overlap_add_len_from_table(h, ctypes.byref(params), int(length), *args))
         return result
 
     def describe_overlap_add(self, params, frames, hop, count=None, *, t0=0, channels=1, y_stride=0):

@@ -29,8 +29,8 @@ extern "C" {
 #endif
 
 #define BHW_ABI_VERSION 4u   /* 3: bhw_coeffs_preset, bhw_gather_parts_device; 4: bhw_workspace_bytes_ex (nothing removed or changed);
-                                the resident tables, the overlapped-frame apply and the overlap-add were added without a bump
-                                (additions only) */
+                                the resident tables, the overlapped-frame apply, the overlap-add and the windows of any length
+                                were added without a bump (additions only) */
 
 /* CORDIC bit-model (the reference holds three that are not bit-identical). */
 enum {
@@ -366,6 +366,49 @@ int bhw_overlap_add_device(const bhw_params *p, int device, void *hip_stream, co
 int bhw_overlap_add_from_table(bhw_table t, const bhw_params *p, void *hip_stream, const bhw_ola *o, const int32_t *d_y,
                                int32_t *d_x);
 int bhw_overlap_add_describe(bhw_table t, const bhw_params *p, const bhw_ola *o, char *buf, uint64_t len);
+
+/* Windows of any length L, 1 <= L <= 2^phi_width: torch.hann_window(400), a 25 ms frame at 16 kHz, a symmetric filter-design window.
+ * The phase accumulator counts modulo L instead of 2^phi_width, and each harmonic is read at the nearest phi_width-bit angle of the
+ * exact one.  For a coefficient index n (any uint64) let m = n mod L; for every harmonic k = 1 .. n_terms - 1
+ *     theta_k(n) = round(((k * m) mod L) * 2^phi_width / L)  mod 2^phi_width
+ * and the coefficient is the model's CORDIC at theta_k(n) combined with aa[] under the configured rule -- exactly what the
+ * power-of-two window does with theta_k = (k * n) mod 2^phi_width.
+ *   - L = 2^phi_width reproduces the power-of-two windows bit for bit (theta_k = (k * n) mod 2^phi_width, no rounding), and the calls
+ *     below then take the existing entry point of their kind unchanged: same kernels, same contracts.
+ *   - No rounding ties occur: with L = 2^a * b (b odd) a tie would need 2^(phi_width + 1 - a) * m = b (mod 2b), even against odd.  So
+ *     half up and half to even agree, and theta_k(L - m) = -theta_k(m) (mod 2^phi_width).
+ *   - The index stream is periodic in L, as the hardware counter is in 2^phi_width.  A symmetric window of length L is
+ *     bhw_generate_len_device(length = L - 1, n0 = 0, count = L).
+ *   - The rounding of the angle adds up to pi * 2^-phi_width rad of phase error per harmonic: choose phi_width above log2 L by enough
+ *     bits for the chosen dat_width (as a rule, phi_width >= dat_width).  The integer window is not promised to be mirror-symmetric
+ *     (the power-of-two windows are not either).
+ * Each call is its power-of-two counterpart with N replaced by L: the same formulas, limits and contracts (d_x extent
+ * (frames - 1) * hop + L, y_stride >= L * C, frames * L <= 2^34, the overlap-add extent (frames - 1) * hop + L, count <= 2^34).
+ *   - Argument checks come before any HIP call: those of the counterpart, and length 0 or above 2^phi_width (BHW_ERR_BADARG), a
+ *     sin_type other than BHW_SIN_CORDIC (BHW_ERR_UNSUPPORTED; the models DDS48 / SCALED are refused as for every window).
+ *   - At L != 2^phi_width the library calls run one lane per coefficient with the direct CORDIC chains (the frames and overlap-add
+ *     kernels spread each coefficient over frames or hops as their counterparts do); they allocate nothing and use no scratch, so they
+ *     can be captured with no bhw_prepare_device.  The whole-period kernels (fused, tile) need L = 2^phi_width and are not used.
+ *   - The from-table calls gather from the resident table (it holds every first-quadrant angle, so it serves any length) in any table
+ *     format and layout, and keep the from-table contract: no allocation, no synchronisation, always capturable, any number of
+ *     concurrent readers, the same key match.
+ *   - bhw_describe_len: one line naming the route ("power-of-two route" with the counterpart's describe text, or "any-length route"),
+ *     the kernel and its grid.  f non-NULL: the frames call; o non-NULL: the overlap-add call; both NULL: the generate call of
+ *     [n0, n0 + count) (n0, count are ignored otherwise).  t may be NULL (the library call).  Host arithmetic only. */
+int bhw_generate_len_device(const bhw_params *p, uint64_t length, int device, void *hip_stream,
+                            uint64_t n0, uint64_t count, int32_t *d_out);
+int bhw_generate_len_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream,
+                                uint64_t n0, uint64_t count, int32_t *d_out);
+int bhw_apply_frames_len_device(const bhw_params *p, uint64_t length, int device, void *hip_stream,
+                                const bhw_frames *f, const int32_t *d_x, int32_t *d_y);
+int bhw_apply_frames_len_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream,
+                                    const bhw_frames *f, const int32_t *d_x, int32_t *d_y);
+int bhw_overlap_add_len_device(const bhw_params *p, uint64_t length, int device, void *hip_stream,
+                               const bhw_ola *o, const int32_t *d_y, int32_t *d_x);
+int bhw_overlap_add_len_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream,
+                                   const bhw_ola *o, const int32_t *d_y, int32_t *d_x);
+int bhw_describe_len(bhw_table t, const bhw_params *p, uint64_t length, uint64_t n0, uint64_t count,
+                     const bhw_frames *f, const bhw_ola *o, char *buf, uint64_t len);
 
 /* Threading: every entry point may be called from any host thread.  Calls that use the library-owned scratch of one
  * (device, stream) are serialised against each other for the duration of their launches (the table is rebuilt per call);

@@ -9,6 +9,8 @@
 //   bhw::resident_table      the elaborated CORDIC of win_selector's generics (bhw_table_create), move-only, RAII
 //   bhw::apply_frames()      the window over overlapping frames of a signal in one launch (bhw_apply_frames_device)
 //   bhw::overlap_add()       the weighted overlap-add of frames back into one signal in one launch (bhw_overlap_add_device)
+//   bhw::generate_len(), bhw::apply_frames_len(), bhw::overlap_add_len()
+//                            the same for a window of any length L <= 2^phi_width (bhw_generate_len_device ...)
 // Same names, argument meaning and error behaviour (unknown win_type -> zeros, like win_empty,
 // hls/windows/win_function.cpp:159-165,417-419).  All arithmetic runs in the HIP kernels behind the ABI.
 #pragma once
@@ -197,6 +199,32 @@ inline void overlap_add(const bhw_params &p, const bhw_ola &o, const int32_t *d_
     check(bhw_overlap_add_device(&p, device, hip_stream, &o, d_y, d_x));
 }
 
+// Windows of any length L, 1 <= L <= 2^phi_width (the *_len calls of bhw.h): count coefficients of the length-L window from index n0
+// into device memory, the overlapped-frame apply and the overlap-add with L in place of N, and the one-line route description
+// (f / o NULL: the generate call).
+inline void generate_len(const bhw_params &p, uint64_t length, uint64_t n0, uint64_t count, int32_t *d_out, int device = 0,
+                         void *hip_stream = nullptr)
+{
+    check(bhw_generate_len_device(&p, length, device, hip_stream, n0, count, d_out));
+}
+inline void apply_frames_len(const bhw_params &p, uint64_t length, const bhw_frames &f, const int32_t *d_x, int32_t *d_y, int device = 0,
+                             void *hip_stream = nullptr)
+{
+    check(bhw_apply_frames_len_device(&p, length, device, hip_stream, &f, d_x, d_y));
+}
+inline void overlap_add_len(const bhw_params &p, uint64_t length, const bhw_ola &o, const int32_t *d_y, int32_t *d_x, int device = 0,
+                            void *hip_stream = nullptr)
+{
+    check(bhw_overlap_add_len_device(&p, length, device, hip_stream, &o, d_y, d_x));
+}
+inline std::string describe_len(const bhw_params &p, uint64_t length, uint64_t n0, uint64_t count, const bhw_frames *f = nullptr,
+                                const bhw_ola *o = nullptr, bhw_table t = nullptr)
+{
+    char buf[512];
+    check(bhw_describe_len(t, &p, length, n0, count, f, o, buf, sizeof buf));
+    return buf;
+}
+
 // The CORDIC table of a configuration's generics, built once on `device` (bhw_table_create) and freed by the destructor
 // (bhw_table_destroy: it synchronises the device first).  Move-only.  Every call takes its weights -- the AA ports -- from its own
 // bhw_params, which must match the table's generics; device pointers and streams as in the C calls.
@@ -257,6 +285,24 @@ public:
         char buf[384];
         check(bhw_overlap_add_describe(t_, &p, &o, buf, sizeof buf));
         return buf;
+    }
+    // windows of any length L from this table (bhw_generate_len_from_table ...)
+    void generate_len(const bhw_params &p, uint64_t length, void *hip_stream, uint64_t n0, uint64_t count, int32_t *d_out) const
+    {
+        check(bhw_generate_len_from_table(t_, &p, length, hip_stream, n0, count, d_out));
+    }
+    void apply_frames_len(const bhw_params &p, uint64_t length, void *hip_stream, const bhw_frames &f, const int32_t *d_x, int32_t *d_y) const
+    {
+        check(bhw_apply_frames_len_from_table(t_, &p, length, hip_stream, &f, d_x, d_y));
+    }
+    void overlap_add_len(const bhw_params &p, uint64_t length, void *hip_stream, const bhw_ola &o, const int32_t *d_y, int32_t *d_x) const
+    {
+        check(bhw_overlap_add_len_from_table(t_, &p, length, hip_stream, &o, d_y, d_x));
+    }
+    std::string describe_len(const bhw_params &p, uint64_t length, uint64_t n0, uint64_t count, const bhw_frames *f = nullptr,
+                             const bhw_ola *o = nullptr) const
+    {
+        return bhw::describe_len(p, length, n0, count, f, o, t_);
     }
     void generate_part(const bhw_params &p, void *hip_stream, uint32_t part, uint32_t n_parts, int32_t *d_window) const
     {
