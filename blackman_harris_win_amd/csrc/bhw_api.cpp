@@ -407,49 +407,6 @@ int generate_impl(const bhw_params *p, int device, void *stream, uint64_t n0, ui
     return table_pieces(l, TableView{c, tc.tiled, (const int32_t *)scratch.ws}, p, w, n0, count, d_out, bhwk_table_combine);
 }
 
-// bhw_apply_frames_device: the frames kernel with the direct CORDIC source (no table, no scratch), or one bhw_apply_device per
-// frame where the planner's route rule says so.  force_route >= 0: the route of an A/B run (bhw_dbg_apply_frames_route).
-int frames_impl(const bhw_params *p, int device, void *stream, const bhw_frames *f, const int32_t *d_x, int32_t *d_y, int force_route)
-{
-    int rc = bhwp_frames_checks(p, f, d_x, d_y);
-    if (rc || !f->frames) return rc;
-    const BhwFramesPlan pl = bhwp_frames_plan(p, f, false, force_route);
-    if (pl.route == BHWP_FRAMES_PER_FRAME) {
-        const uint64_t N = 1ull << p->phi_width;
-        for (uint64_t i = 0; i < f->frames; ++i) {
-            rc = generate_impl(p, device, stream, 0, N, d_y + i * pl.y_stride, nullptr, d_x + i * f->hop, f->shift);
-            if (rc) return rc;
-        }
-        return BHW_OK;
-    }
-    DeviceGuard guard(device);
-    if ((rc = guard.status())) return rc;
-    BhwCordicCfg c;
-    bhwp_resolve_cordic(p, c);
-    BhwWinCfg w;
-    bhwp_resolve_window(p, w);
-    const int e = bhwk_frames(BhwLaunch{device, stream}, c, w, pl, f, d_x, d_y, nullptr);
-    return e ? fail_hip(e, "frames launch") : BHW_OK;
-}
-
-// bhw_overlap_add_device: the overlap-add kernel with the direct CORDIC source (no table, no scratch).  force_q / force_rx > 0: the
-// plan shape of a test or A/B run (bhw_dbg_overlap_add_shape).
-int ola_impl(const bhw_params *p, int device, void *stream, const bhw_ola *o, const int32_t *d_y, int32_t *d_x, uint32_t force_q,
-             uint32_t force_rx)
-{
-    int rc = bhwp_ola_checks(p, o, d_y, d_x);
-    if (rc || !o->count) return rc;
-    const BhwOlaPlan pl = bhwp_ola_plan(p, o, false, force_q, force_rx);
-    DeviceGuard guard(device);
-    if ((rc = guard.status())) return rc;
-    BhwCordicCfg c;
-    bhwp_resolve_cordic(p, c);
-    BhwWinCfg w;
-    bhwp_resolve_window(p, w);
-    const int e = bhwk_ola(BhwLaunch{device, stream}, c, w, pl, o, d_y, d_x, nullptr);
-    return e ? fail_hip(e, "overlap-add launch") : BHW_OK;
-}
-
 } // namespace
 
 extern "C" {
@@ -470,24 +427,6 @@ int bhw_apply_device(const bhw_params *p, int device, void *hip_stream, uint64_t
 {
     const int rc = bhwp_apply_checks(count, d_x, d_y, shift);
     return rc ? rc : generate_impl(p, device, hip_stream, n0, count, d_y, nullptr, d_x, shift);
-}
-
-int bhw_apply_frames_device(const bhw_params *p, int device, void *hip_stream, const bhw_frames *f, const int32_t *d_x, int32_t *d_y)
-{
-    return frames_impl(p, device, hip_stream, f, d_x, d_y, -1);
-}
-
-// Development hook (not part of the ABI in include/bhw.h): bhw_apply_frames_device on a forced route (BHWP_FRAMES_DIRECT or
-// BHWP_FRAMES_PER_FRAME; a route the call cannot take is ignored) -- the crossover runs of tools/bench_apply_frames.py and tests.
-int bhw_dbg_apply_frames_route(const bhw_params *p, int device, void *hip_stream, const bhw_frames *f, const int32_t *d_x, int32_t *d_y,
-                               int route)
-{
-    return frames_impl(p, device, hip_stream, f, d_x, d_y, route);
-}
-
-int bhw_overlap_add_device(const bhw_params *p, int device, void *hip_stream, const bhw_ola *o, const int32_t *d_y, int32_t *d_x)
-{
-    return ola_impl(p, device, hip_stream, o, d_y, d_x, 0, 0);
 }
 
 int bhw_generate_batched_device(const bhw_params *p, int device, void *hip_stream, uint32_t frames, int32_t *d_out)
@@ -868,6 +807,58 @@ int from_table(bhw_table t, const bhw_params *p, void *stream, uint64_t n0, uint
     return table_pieces(BhwLaunch{t->device, stream}, t->view(), p, w, n0, count, d_out, ragged);
 }
 
+// The launch of a frames / overlap-add / any-length generate call that passed its checks, from table t (on its device) or, with t
+// NULL, by the direct CORDIC chains of p on `device` (checked to be a usable device).  length 0: L = 2^phi_width, no phase map.
+// launch(l, c, w, d_table, lp) returns the HIP status, reported as `what`.
+template <typename Launch>
+int run_source(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const char *what, Launch launch)
+{
+    const int dev = t ? t->device : device;
+    DeviceGuard guard(dev, !t);
+    if (const int rc = guard.status()) return rc;
+    BhwCordicCfg c;
+    if (t) c = t->c;
+    else   bhwp_resolve_cordic(p, c);
+    BhwWinCfg w;
+    bhwp_resolve_window(p, w);
+    const BhwLenPhase lp = length ? bhw_len_phase(p->phi_width, length) : BhwLenPhase{};
+    const int e = launch(BhwLaunch{dev, stream}, c, w, t ? (const int32_t *)t->buf : nullptr, length ? &lp : nullptr);
+    return e ? fail_hip(e, what) : BHW_OK;
+}
+
+// Every overlapped-frame apply: the frames kernel from table t or by the direct CORDIC chains (t NULL), over the window of length
+// `length` (0: 2^phi_width), or one bhw_apply_device per frame where the planner's route rule says so (library calls at
+// L = 2^phi_width).  force_route >= 0: the route of an A/B run (bhw_dbg_apply_frames_route).
+int frames_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_frames *f, const int32_t *d_x,
+               int32_t *d_y, int force_route = -1)
+{
+    int rc = t ? table_call_checks(t, p) : BHW_OK;
+    if (!rc) rc = bhwp_frames_checks(p, f, d_x, d_y, true, length);
+    if (rc || !f->frames) return rc;
+    const BhwFramesPlan pl = bhwp_frames_plan(p, f, t != nullptr, force_route, length);
+    if (pl.route == BHWP_FRAMES_PER_FRAME) {
+        for (uint64_t i = 0; i < f->frames; ++i)
+            if ((rc = generate_impl(p, device, stream, 0, pl.len, d_y + i * pl.y_stride, nullptr, d_x + i * f->hop, f->shift))) return rc;
+        return BHW_OK;
+    }
+    const char *what = length ? "frames launch (any length)" : t ? "frames launch (resident table)" : "frames launch";
+    return run_source(t, p, length, device, stream, what, [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *tab,
+                                                               const BhwLenPhase *lp) { return bhwk_frames(l, c, w, pl, f, d_x, d_y, tab, lp); });
+}
+
+// Every weighted overlap-add, as frames_run.  force_q / force_rx > 0: the plan shape of a test or A/B run (bhw_dbg_overlap_add_shape).
+int ola_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_ola *o, const int32_t *d_y, int32_t *d_x,
+            uint32_t force_q = 0, uint32_t force_rx = 0)
+{
+    int rc = t ? table_call_checks(t, p) : BHW_OK;
+    if (!rc) rc = bhwp_ola_checks(p, o, d_y, d_x, true, length);
+    if (rc || !o->count) return rc;
+    const BhwOlaPlan pl = bhwp_ola_plan(p, o, t != nullptr, force_q, force_rx, length);
+    const char *what = length ? "overlap-add launch (any length)" : t ? "overlap-add launch (resident table)" : "overlap-add launch";
+    return run_source(t, p, length, device, stream, what, [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *tab,
+                                                               const BhwLenPhase *lp) { return bhwk_ola(l, c, w, pl, o, d_y, d_x, tab, lp); });
+}
+
 } // namespace
 
 extern "C" {
@@ -962,18 +953,22 @@ int bhw_generate_part_from_table(bhw_table t, const bhw_params *p, void *hip_str
     return part_tiles(BhwLaunch{t->device, hip_stream}, t->view(), w, tile0, tile_count, d_window);
 }
 
+int bhw_apply_frames_device(const bhw_params *p, int device, void *hip_stream, const bhw_frames *f, const int32_t *d_x, int32_t *d_y)
+{
+    return frames_run(nullptr, p, 0, device, hip_stream, f, d_x, d_y);
+}
+
+// Development hook (not part of the ABI in include/bhw.h): bhw_apply_frames_device on a forced route (BHWP_FRAMES_DIRECT or
+// BHWP_FRAMES_PER_FRAME; a route the call cannot take is ignored) -- the crossover runs of tools/bench_apply_frames.py and tests.
+int bhw_dbg_apply_frames_route(const bhw_params *p, int device, void *hip_stream, const bhw_frames *f, const int32_t *d_x, int32_t *d_y,
+                               int route)
+{
+    return frames_run(nullptr, p, 0, device, hip_stream, f, d_x, d_y, route);
+}
+
 int bhw_apply_frames_from_table(bhw_table t, const bhw_params *p, void *hip_stream, const bhw_frames *f, const int32_t *d_x, int32_t *d_y)
 {
-    int rc = table_call_checks(t, p);
-    if (!rc) rc = bhwp_frames_checks(p, f, d_x, d_y);
-    if (rc || !f->frames) return rc;
-    const BhwFramesPlan pl = bhwp_frames_plan(p, f, true);
-    DeviceGuard guard(t->device, false);
-    if ((rc = guard.status())) return rc;
-    BhwWinCfg w;
-    bhwp_resolve_window(p, w);
-    const int e = bhwk_frames(BhwLaunch{t->device, hip_stream}, t->c, w, pl, f, d_x, d_y, (const int32_t *)t->buf);
-    return e ? fail_hip(e, "frames launch (resident table)") : BHW_OK;
+    return t ? frames_run(t, p, 0, t->device, hip_stream, f, d_x, d_y) : fail(BHW_ERR_BADARG, "table is NULL");
 }
 
 int bhw_apply_frames_describe(bhw_table t, const bhw_params *p, const bhw_frames *f, char *buf, uint64_t len)
@@ -996,23 +991,17 @@ int bhw_overlap_add_describe(bhw_table t, const bhw_params *p, const bhw_ola *o,
 int bhw_dbg_overlap_add_shape(bhw_table t, const bhw_params *p, int device, void *hip_stream, const bhw_ola *o, const int32_t *d_y,
                               int32_t *d_x, uint32_t force_q, uint32_t force_rx)
 {
-    if (!t) return ola_impl(p, device, hip_stream, o, d_y, d_x, force_q, force_rx);
-    int rc = table_call_checks(t, p);
-    if (!rc) rc = bhwp_ola_checks(p, o, d_y, d_x);
-    if (rc || !o->count) return rc;
-    const BhwOlaPlan pl = bhwp_ola_plan(p, o, true, force_q, force_rx);
-    DeviceGuard guard(t->device, false);
-    if ((rc = guard.status())) return rc;
-    BhwWinCfg w;
-    bhwp_resolve_window(p, w);
-    const int e = bhwk_ola(BhwLaunch{t->device, hip_stream}, t->c, w, pl, o, d_y, d_x, (const int32_t *)t->buf);
-    return e ? fail_hip(e, "overlap-add launch (resident table)") : BHW_OK;
+    return ola_run(t, p, 0, device, hip_stream, o, d_y, d_x, force_q, force_rx);
+}
+
+int bhw_overlap_add_device(const bhw_params *p, int device, void *hip_stream, const bhw_ola *o, const int32_t *d_y, int32_t *d_x)
+{
+    return ola_run(nullptr, p, 0, device, hip_stream, o, d_y, d_x);
 }
 
 int bhw_overlap_add_from_table(bhw_table t, const bhw_params *p, void *hip_stream, const bhw_ola *o, const int32_t *d_y, int32_t *d_x)
 {
-    if (!t) return fail(BHW_ERR_BADARG, "table is NULL");
-    return bhw_dbg_overlap_add_shape(t, p, t->device, hip_stream, o, d_y, d_x, 0, 0);
+    return t ? ola_run(t, p, 0, t->device, hip_stream, o, d_y, d_x) : fail(BHW_ERR_BADARG, "table is NULL");
 }
 
 // Development hook (not part of the ABI in include/bhw.h): bhw_generate_from_table with every ragged piece on the general gather
@@ -1055,123 +1044,73 @@ namespace {
 
 std::atomic<bool> g_len_force{false};
 
-// the prologue of a library *_len call that takes the any-length kernels: a coefficient range [n0, n0 + count) into d_out
-int len_range_checks(uint64_t count, const int32_t *d_out)
+// the length a run function takes after bhwp_len_checks: L on the any-length kernels, 0 on the power-of-two route
+uint64_t len_route(const bhw_params *p, uint64_t length) { return bhwp_len_kernels(p, length, g_len_force) ? length : 0; }
+
+// generate [n0, n0 + count) of the window of length L on the any-length kernels, from table t or by the direct chains (t NULL)
+int generate_len(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, uint64_t n0, uint64_t count, int32_t *d_out)
 {
+    int rc = t ? table_call_checks(t, p) : BHW_OK;
+    if (rc) return rc;
     if (count && !d_out) return fail(BHW_ERR_BADARG, "d_out is NULL");
     if (count > (1ull << 34)) return fail(BHW_ERR_BADARG, "count %llu > 2^34 per call", (unsigned long long)count);
-    return BHW_OK;
-}
-
-int frames_len(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_frames *f, const int32_t *d_x,
-               int32_t *d_y)
-{
-    int rc = t ? table_call_checks(t, p) : BHW_OK;
-    if (!rc) rc = bhwp_frames_checks(p, f, d_x, d_y, true, length);
-    if (rc || !f->frames) return rc;
-    const BhwFramesPlan pl = bhwp_frames_plan(p, f, t != nullptr, -1, length);
-    DeviceGuard guard(t ? t->device : device, !t);
-    if ((rc = guard.status())) return rc;
-    BhwCordicCfg c;
-    if (t) c = t->c;
-    else   bhwp_resolve_cordic(p, c);
-    BhwWinCfg w;
-    bhwp_resolve_window(p, w);
-    const BhwLenPhase lp = bhw_len_phase(p->phi_width, length);
-    const int e = bhwk_frames(BhwLaunch{t ? t->device : device, stream}, c, w, pl, f, d_x, d_y, t ? (const int32_t *)t->buf : nullptr, &lp);
-    return e ? fail_hip(e, "frames launch (any length)") : BHW_OK;
-}
-
-int ola_len(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_ola *o, const int32_t *d_y, int32_t *d_x)
-{
-    int rc = t ? table_call_checks(t, p) : BHW_OK;
-    if (!rc) rc = bhwp_ola_checks(p, o, d_y, d_x, true, length);
-    if (rc || !o->count) return rc;
-    const BhwOlaPlan pl = bhwp_ola_plan(p, o, t != nullptr, 0, 0, length);
-    DeviceGuard guard(t ? t->device : device, !t);
-    if ((rc = guard.status())) return rc;
-    BhwCordicCfg c;
-    if (t) c = t->c;
-    else   bhwp_resolve_cordic(p, c);
-    BhwWinCfg w;
-    bhwp_resolve_window(p, w);
-    const BhwLenPhase lp = bhw_len_phase(p->phi_width, length);
-    const int e = bhwk_ola(BhwLaunch{t ? t->device : device, stream}, c, w, pl, o, d_y, d_x, t ? (const int32_t *)t->buf : nullptr, &lp);
-    return e ? fail_hip(e, "overlap-add launch (any length)") : BHW_OK;
+    if (!count) return BHW_OK;
+    const char *what = t ? "generate launch (any length, resident table)" : "generate launch (any length)";
+    return run_source(t, p, length, device, stream, what, [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *tab,
+                                                               const BhwLenPhase *lp) { return bhwk_len_range(l, c, w, tab, *lp, n0, count, d_out); });
 }
 
 } // namespace
 
 extern "C" {
 
+// Each *_len call: bhwp_len_checks, then (from-table calls) the handle, then the route -- the existing calls at L = 2^phi_width.
 int bhw_generate_len_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, uint64_t n0, uint64_t count, int32_t *d_out)
 {
-    int rc = bhwp_len_checks(p, length);
+    const int rc = bhwp_len_checks(p, length);
     if (rc) return rc;
-    if (!bhwp_len_kernels(p, length, g_len_force)) return generate_impl(p, device, hip_stream, n0, count, d_out, nullptr);
-    if ((rc = len_range_checks(count, d_out)) || !count) return rc;
-    DeviceGuard guard(device);
-    if ((rc = guard.status())) return rc;
-    BhwCordicCfg c;
-    bhwp_resolve_cordic(p, c);
-    BhwWinCfg w;
-    bhwp_resolve_window(p, w);
-    const int e = bhwk_direct_len(BhwLaunch{device, hip_stream}, c, w, bhw_len_phase(p->phi_width, length), n0, count, d_out);
-    return e ? fail_hip(e, "generate launch (any length)") : BHW_OK;
+    if (!len_route(p, length)) return generate_impl(p, device, hip_stream, n0, count, d_out, nullptr);
+    return generate_len(nullptr, p, length, device, hip_stream, n0, count, d_out);
 }
 
 int bhw_generate_len_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, uint64_t n0, uint64_t count,
                                 int32_t *d_out)
 {
     int rc = bhwp_len_checks(p, length);
+    if (!rc && !t) rc = fail(BHW_ERR_BADARG, "table is NULL");
     if (rc) return rc;
-    if (!bhwp_len_kernels(p, length, g_len_force)) return from_table(t, p, hip_stream, n0, count, d_out);
-    if ((rc = table_call_checks(t, p)) || (rc = len_range_checks(count, d_out)) || !count) return rc;
-    DeviceGuard guard(t->device, false);
-    if ((rc = guard.status())) return rc;
-    BhwWinCfg w;
-    bhwp_resolve_window(p, w);
-    const int e = bhwk_range_len(BhwLaunch{t->device, hip_stream}, t->c, w, (const int32_t *)t->buf, bhw_len_phase(p->phi_width, length), n0,
-                                 count, d_out);
-    return e ? fail_hip(e, "generate launch (any length, resident table)") : BHW_OK;
+    if (!len_route(p, length)) return from_table(t, p, hip_stream, n0, count, d_out);
+    return generate_len(t, p, length, t->device, hip_stream, n0, count, d_out);
 }
 
 int bhw_apply_frames_len_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_frames *f, const int32_t *d_x,
                                 int32_t *d_y)
 {
     const int rc = bhwp_len_checks(p, length);
-    if (rc) return rc;
-    if (!bhwp_len_kernels(p, length, g_len_force)) return frames_impl(p, device, hip_stream, f, d_x, d_y, -1);
-    return frames_len(nullptr, p, length, device, hip_stream, f, d_x, d_y);
+    return rc ? rc : frames_run(nullptr, p, len_route(p, length), device, hip_stream, f, d_x, d_y);
 }
 
 int bhw_apply_frames_len_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_frames *f,
                                     const int32_t *d_x, int32_t *d_y)
 {
     int rc = bhwp_len_checks(p, length);
-    if (rc) return rc;
-    if (!bhwp_len_kernels(p, length, g_len_force)) return bhw_apply_frames_from_table(t, p, hip_stream, f, d_x, d_y);
-    if (!t) return fail(BHW_ERR_BADARG, "table is NULL");
-    return frames_len(t, p, length, t->device, hip_stream, f, d_x, d_y);
+    if (!rc && !t) rc = fail(BHW_ERR_BADARG, "table is NULL");
+    return rc ? rc : frames_run(t, p, len_route(p, length), t->device, hip_stream, f, d_x, d_y);
 }
 
 int bhw_overlap_add_len_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_ola *o, const int32_t *d_y,
                                int32_t *d_x)
 {
     const int rc = bhwp_len_checks(p, length);
-    if (rc) return rc;
-    if (!bhwp_len_kernels(p, length, g_len_force)) return ola_impl(p, device, hip_stream, o, d_y, d_x, 0, 0);
-    return ola_len(nullptr, p, length, device, hip_stream, o, d_y, d_x);
+    return rc ? rc : ola_run(nullptr, p, len_route(p, length), device, hip_stream, o, d_y, d_x);
 }
 
 int bhw_overlap_add_len_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_ola *o, const int32_t *d_y,
                                    int32_t *d_x)
 {
-    const int rc = bhwp_len_checks(p, length);
-    if (rc) return rc;
-    if (!bhwp_len_kernels(p, length, g_len_force)) return bhw_overlap_add_from_table(t, p, hip_stream, o, d_y, d_x);
-    if (!t) return fail(BHW_ERR_BADARG, "table is NULL");
-    return ola_len(t, p, length, t->device, hip_stream, o, d_y, d_x);
+    int rc = bhwp_len_checks(p, length);
+    if (!rc && !t) rc = fail(BHW_ERR_BADARG, "table is NULL");
+    return rc ? rc : ola_run(t, p, len_route(p, length), t->device, hip_stream, o, d_y, d_x);
 }
 
 int bhw_describe_len(bhw_table t, const bhw_params *p, uint64_t length, uint64_t n0, uint64_t count, const bhw_frames *f, const bhw_ola *o,

@@ -879,6 +879,15 @@ inline void launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, hipStream_t 
     if (e != hipSuccess && t_launch_err == hipSuccess) t_launch_err = e;
 }
 
+// The kernel of a front for its phase map: k at L = 2^phi_width or, with lp, k_len (the same parameters, the BhwLenPhase last).
+template <typename... KArgs>
+inline void launch_phase(void (*k_len)(KArgs..., BhwLenPhase), void (*k)(KArgs...), const BhwLenPhase *lp, dim3 grid, dim3 block,
+                         hipStream_t st, typename same_type<KArgs>::type... args)
+{
+    if (lp) launch(k_len, grid, block, st, args..., *lp);
+    else    launch(k, grid, block, st, args...);
+}
+
 // Instance choice at a launch: a run-time value becomes the compile-time constant of a listed template argument, so each kernel's
 // instances are listed once, where it is launched.  with_int<V0, V1, ...>(v, f) calls f(std::integral_constant<int, V>()) for the
 // listed V equal to v and returns true, or returns false if none is; with_int_or_last does the same with the last V taking every

@@ -160,10 +160,7 @@ int bhwk_frames(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinCfg &w
     a.io = f->channels == 1 ? 0u : ((((uintptr_t)d_x | (uintptr_t)d_y) % 8 == 0 && pl.y_stride % 2 == 0) ? 2u : 1u);
     const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y), block(kFramesBlock);
     if (!d_table) {
-        with_int_or_last<2, 1, 0>(direct_form(c_in), [&](auto D) {
-            if (lp) launch(k_frames_direct_len<D>, grid, block, st, c_in, w, a, *lp);
-            else    launch(k_frames_direct<D>, grid, block, st, c_in, w, a);
-        });
+        with_int_or_last<2, 1, 0>(direct_form(c_in), [&](auto D) { launch_phase(k_frames_direct_len<D>, k_frames_direct<D>, lp, grid, block, st, c_in, w, a); });
         return finish(hipSuccess);
     }
     const BhwCordicCfg c = table_layout(c_in);
@@ -171,8 +168,7 @@ int bhwk_frames(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinCfg &w
     if (!bhwp_range_form(c, w, &fmt, &nt, &mode)) return (int)hipErrorInvalidValue;   // every format a resident table holds has instances
     const void *tab = (const void *)d_table;
     with_range_form(fmt, nt, mode, [&](auto F, auto NT, auto M) {
-        if (lp) launch(k_frames_table_len<F, NT, M>, grid, block, st, c, w, tab, a, *lp);
-        else    launch(k_frames_table<F, NT, M>, grid, block, st, c, w, tab, a);
+        launch_phase(k_frames_table_len<F, NT, M>, k_frames_table<F, NT, M>, lp, grid, block, st, c, w, tab, a);
     });
     return finish(hipSuccess);
 }

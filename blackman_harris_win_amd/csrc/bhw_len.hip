@@ -48,27 +48,20 @@ __global__ __launch_bounds__(kBlock) void k_range_len(BhwCordicCfg cfg, BhwWinCf
 
 } // namespace
 
-int bhwk_direct_len(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwLenPhase &lp, uint64_t n0, uint64_t count,
-                    int32_t *d_out)
-{
-    if (!count) return 0;
-    hipStream_t st = (hipStream_t)l.stream;
-    const uint64_t m0 = bhw_len_mod(n0, lp);
-    const dim3 grid(grid_for(count)), block(kBlock);
-    with_int_or_last<2, 1, 0>(direct_form(c), [&](auto D) { launch(k_direct_len<D>, grid, block, st, c, w, lp, m0, count, d_out); });
-    return finish(hipSuccess);
-}
-
-int bhwk_range_len(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinCfg &w, const int32_t *d_table, const BhwLenPhase &lp,
+int bhwk_len_range(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinCfg &w, const int32_t *d_table, const BhwLenPhase &lp,
                    uint64_t n0, uint64_t count, int32_t *d_out)
 {
     if (!count) return 0;
-    const BhwCordicCfg c = table_layout(c_in);
-    int fmt, nt, mode;
-    if (!bhwp_range_form(c, w, &fmt, &nt, &mode)) return (int)hipErrorInvalidValue;   // every format a resident table holds has instances
     hipStream_t st = (hipStream_t)l.stream;
     const uint64_t m0 = bhw_len_mod(n0, lp);
     const dim3 grid(grid_for(count)), block(kBlock);
+    if (!d_table) {
+        with_int_or_last<2, 1, 0>(direct_form(c_in), [&](auto D) { launch(k_direct_len<D>, grid, block, st, c_in, w, lp, m0, count, d_out); });
+        return finish(hipSuccess);
+    }
+    const BhwCordicCfg c = table_layout(c_in);
+    int fmt, nt, mode;
+    if (!bhwp_range_form(c, w, &fmt, &nt, &mode)) return (int)hipErrorInvalidValue;   // every format a resident table holds has instances
     const void *tab = (const void *)d_table;
     with_range_form(fmt, nt, mode, [&](auto F, auto NT, auto M) {
         launch(k_range_len<F, NT, M>, grid, block, st, c, w, tab, lp, m0, count, d_out);

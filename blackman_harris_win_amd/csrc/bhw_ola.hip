@@ -216,8 +216,7 @@ int bhwk_ola(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinCfg &w, c
     if (!d_table) {
         with_int_or_last<0, 1, 2>(a.io, [&](auto IO) {
             with_int_or_last<2, 1, 0>(direct_form(c_in), [&](auto D) {
-                if (lp) launch(k_ola_direct_len<D, IO>, grid, block, st, c_in, w, a, *lp);
-                else    launch(k_ola_direct<D, IO>, grid, block, st, c_in, w, a);
+                launch_phase(k_ola_direct_len<D, IO>, k_ola_direct<D, IO>, lp, grid, block, st, c_in, w, a);
             });
         });
         return finish(hipSuccess);
@@ -227,10 +226,7 @@ int bhwk_ola(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinCfg &w, c
     if (!bhwp_range_form(c, w, &fmt, &nt, &mode)) return (int)hipErrorInvalidValue;   // every format a resident table holds has instances
     const void *tab = (const void *)d_table;
     with_range_form(fmt, nt, mode, [&](auto F, auto NT, auto M) {
-        with_int_or_last<0, 1, 2>(a.io, [&](auto IO) {
-            if (lp) launch(k_ola_table_len<F, NT, M, IO>, grid, block, st, c, w, tab, a, *lp);
-            else    launch(k_ola_table<F, NT, M, IO>, grid, block, st, c, w, tab, a);
-        });
+        with_int_or_last<0, 1, 2>(a.io, [&](auto IO) { launch_phase(k_ola_table_len<F, NT, M, IO>, k_ola_table<F, NT, M, IO>, lp, grid, block, st, c, w, tab, a); });
     });
     return finish(hipSuccess);
 }

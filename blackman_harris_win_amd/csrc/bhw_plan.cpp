@@ -729,6 +729,50 @@ int bhwp_describe_from_table(const bhw_params *p, const BhwCordicCfg &ct, bool t
 
 // ---- overlapped-frame apply --------------------------------------------------------------------------------------------------
 
+namespace {
+
+// The kernel a launch from the resident table ct takes (`table`<fmt,nt,mode>, bhwp_range_form) or, with ct NULL, the direct chains
+// (`direct`<direct_form>): the rules the launchers pick the instance by, with the _len suffix of the any-length kernels.
+void kernel_name(const bhw_params *p, const BhwCordicCfg *ct, const char *direct, const char *table, bool any_len, char *out, size_t len)
+{
+    const char *sfx = any_len ? "_len" : "";
+    if (ct) {
+        BhwWinCfg w;
+        bhwp_resolve_window(p, w);
+        int fmt, nt, mode;
+        bhwp_range_form(table_layout(*ct), w, &fmt, &nt, &mode);
+        snprintf(out, len, "%s%s<%d,%d,%d>", table, sfx, fmt, nt, mode);
+    } else {
+        BhwCordicCfg c;
+        bhwp_resolve_cordic(p, c);
+        snprintf(out, len, "%s%s<%d>", direct, sfx, direct_form(c));
+    }
+}
+
+// the describe line of a frames launch (bhwp_describe_frames, bhwp_describe_len): prefix, kernel, plan shape
+void frames_line(const char *prefix, const bhw_params *p, const BhwCordicCfg *ct, const bhw_frames *f, const BhwFramesPlan &pl, bool any_len,
+                 char *buf, uint64_t len)
+{
+    char kern[64];
+    kernel_name(p, ct, "k_frames_direct", "k_frames_table", any_len, kern, sizeof kern);
+    snprintf(buf, len, "%s%s, %u channel%s, G = %llu frames per lane, grid %llu x %llu x %u lanes (%u along k)", prefix, kern, f->channels,
+             f->channels == 2 ? "s" : "", (unsigned long long)pl.group, (unsigned long long)pl.grid_x, (unsigned long long)pl.grid_y,
+             kFramesBlock, pl.kx);
+}
+
+// the describe line of an overlap-add launch with count > 0 (bhwp_describe_ola, bhwp_describe_len): prefix, kernel, plan shape
+void ola_line(const char *prefix, const bhw_params *p, const BhwCordicCfg *ct, const bhw_ola *o, const BhwOlaPlan &pl, bool any_len, char *buf,
+              uint64_t len)
+{
+    char kern[64];
+    kernel_name(p, ct, "k_ola_direct", "k_ola_table", any_len, kern, sizeof kern);
+    snprintf(buf, len, "%s%s, %u channel%s, Q = %u hops per lane, up to %llu frames per output, grid %llu x %llu x %u lanes (%u along r, "
+             "%u along q)", prefix, kern, o->channels, o->channels == 2 ? "s" : "", pl.q, (unsigned long long)pl.jmax,
+             (unsigned long long)pl.grid_x, (unsigned long long)pl.grid_y, kOlaBlock, pl.rx, pl.fy);
+}
+
+} // namespace
+
 int bhwp_frames_checks(const bhw_params *p, const bhw_frames *f, const void *d_x, const void *d_y, bool pointers, uint64_t length)
 {
     if (!p) return bhwp_fail(BHW_ERR_BADARG, "params is NULL");
@@ -810,22 +854,7 @@ int bhwp_describe_frames(const bhw_params *p, const BhwCordicCfg *ct, const bhw_
         snprintf(buf, len, "per-frame: %llu x bhw_apply_device [%s]", (unsigned long long)f->frames, one);
         return BHW_OK;
     }
-    char kern[64];
-    if (pl.route == BHWP_FRAMES_TABLE) {
-        const BhwCordicCfg c = table_layout(*ct);
-        BhwWinCfg w;
-        bhwp_resolve_window(p, w);
-        int fmt, nt, mode;
-        bhwp_range_form(c, w, &fmt, &nt, &mode);
-        snprintf(kern, sizeof kern, "k_frames_table<%d,%d,%d>", fmt, nt, mode);
-    } else {
-        BhwCordicCfg c;
-        bhwp_resolve_cordic(p, c);
-        snprintf(kern, sizeof kern, "k_frames_direct<%d>", direct_form(c));
-    }
-    snprintf(buf, len, "frames kernel: %s, %u channel%s, G = %llu frames per lane, grid %llu x %llu x %u lanes (%u along k)", kern,
-             f->channels, f->channels == 2 ? "s" : "", (unsigned long long)pl.group, (unsigned long long)pl.grid_x,
-             (unsigned long long)pl.grid_y, kFramesBlock, pl.kx);
+    frames_line("frames kernel: ", p, ct, f, pl, false, buf, len);
     return BHW_OK;
 }
 
@@ -912,23 +941,7 @@ int bhwp_describe_ola(const bhw_params *p, const BhwCordicCfg *ct, const bhw_ola
         snprintf(buf, len, "overlap-add: nothing (count 0)");
         return BHW_OK;
     }
-    const BhwOlaPlan pl = bhwp_ola_plan(p, o, ct != nullptr);
-    char kern[64];
-    if (pl.route == BHWP_OLA_TABLE) {
-        const BhwCordicCfg c = table_layout(*ct);
-        BhwWinCfg w;
-        bhwp_resolve_window(p, w);
-        int fmt, nt, mode;
-        bhwp_range_form(c, w, &fmt, &nt, &mode);
-        snprintf(kern, sizeof kern, "k_ola_table<%d,%d,%d>", fmt, nt, mode);
-    } else {
-        BhwCordicCfg c;
-        bhwp_resolve_cordic(p, c);
-        snprintf(kern, sizeof kern, "k_ola_direct<%d>", direct_form(c));
-    }
-    snprintf(buf, len, "overlap-add %s: %s, %u channel%s, Q = %u hops per lane, up to %llu frames per output, grid %llu x %llu x %u lanes "
-             "(%u along r, %u along q)", pl.route == BHWP_OLA_TABLE ? "table" : "direct", kern, o->channels, o->channels == 2 ? "s" : "",
-             pl.q, (unsigned long long)pl.jmax, (unsigned long long)pl.grid_x, (unsigned long long)pl.grid_y, kOlaBlock, pl.rx, pl.fy);
+    ola_line(ct ? "overlap-add table: " : "overlap-add direct: ", p, ct, o, bhwp_ola_plan(p, o, ct != nullptr), false, buf, len);
     return BHW_OK;
 }
 
@@ -963,36 +976,16 @@ int bhwp_describe_len(const bhw_params *p, const BhwCordicCfg *ct, bool tiled, u
         snprintf(buf, len, "power-of-two route (L = 2^%u): %s", p->phi_width, inner);
         return BHW_OK;
     }
-    BhwCordicCfg c;
-    bhwp_resolve_cordic(p, c);
-    BhwWinCfg w;
-    bhwp_resolve_window(p, w);
-    char form[32];
-    if (ct) {
-        int fmt, nt, mode;
-        bhwp_range_form(table_layout(*ct), w, &fmt, &nt, &mode);
-        snprintf(form, sizeof form, "<%d,%d,%d>", fmt, nt, mode);
-    } else {
-        snprintf(form, sizeof form, "<%d>", direct_form(c));
-    }
-    const char *src = ct ? "table" : "direct";
     if (f) {
-        const BhwFramesPlan pl = bhwp_frames_plan(p, f, ct != nullptr, -1, length);
-        snprintf(inner, sizeof inner, "k_frames_%s_len%s, %u channel%s, G = %llu frames per lane, grid %llu x %llu x %u lanes (%u along k)",
-                 src, form, f->channels, f->channels == 2 ? "s" : "", (unsigned long long)pl.group, (unsigned long long)pl.grid_x,
-                 (unsigned long long)pl.grid_y, kFramesBlock, pl.kx);
+        frames_line("", p, ct, f, bhwp_frames_plan(p, f, ct != nullptr, -1, length), true, inner, sizeof inner);
     } else if (o) {
-        if (!o->count) {
-            snprintf(inner, sizeof inner, "overlap-add: nothing (count 0)");
-        } else {
-            const BhwOlaPlan pl = bhwp_ola_plan(p, o, ct != nullptr, 0, 0, length);
-            snprintf(inner, sizeof inner, "k_ola_%s_len%s, %u channel%s, Q = %u hops per lane, up to %llu frames per output, grid %llu x %llu x "
-                     "%u lanes (%u along r, %u along q)", src, form, o->channels, o->channels == 2 ? "s" : "", pl.q, (unsigned long long)pl.jmax,
-                     (unsigned long long)pl.grid_x, (unsigned long long)pl.grid_y, kOlaBlock, pl.rx, pl.fy);
-        }
+        if (!o->count) snprintf(inner, sizeof inner, "overlap-add: nothing (count 0)");
+        else           ola_line("", p, ct, o, bhwp_ola_plan(p, o, ct != nullptr, 0, 0, length), true, inner, sizeof inner);
     } else {
-        snprintf(inner, sizeof inner, "%s%s, %llu coefficients from n0 mod L = %llu", ct ? "k_range_len" : "k_direct_len", form,
-                 (unsigned long long)count, (unsigned long long)(n0 % length));
+        char kern[64];
+        kernel_name(p, ct, "k_direct", "k_range", true, kern, sizeof kern);
+        snprintf(inner, sizeof inner, "%s, %llu coefficients from n0 mod L = %llu", kern, (unsigned long long)count,
+                 (unsigned long long)(n0 % length));
     }
     snprintf(buf, len, "any-length route (L = %llu, phi_width %u): %s", (unsigned long long)length, p->phi_width, inner);
     return BHW_OK;

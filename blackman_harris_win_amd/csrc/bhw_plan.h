@@ -252,8 +252,6 @@ inline bool bhwp_len_kernels(const bhw_params *p, uint64_t length, bool force) {
 // (library call).
 int  bhwp_describe_len(const bhw_params *p, const BhwCordicCfg *ct, bool tiled, uint64_t length, bool force, uint64_t n0, uint64_t count,
                        const bhw_frames *f, const bhw_ola *o, char *buf, uint64_t len);
-// the generate kernels of a window of any length (bhw_len.hip): k_direct_len, or k_range_len over a resident table
-int  bhwk_direct_len(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwLenPhase &lp, uint64_t n0, uint64_t count,
-                     int32_t *d_out);
-int  bhwk_range_len(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *d_table, const BhwLenPhase &lp,
+// the generate kernel of a window of any length (bhw_len.hip): d_table NULL = k_direct_len, else k_range_len over the resident table of c
+int  bhwk_len_range(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *d_table, const BhwLenPhase &lp,
                     uint64_t n0, uint64_t count, int32_t *d_out);

@@ -89,15 +89,13 @@ def generate(params, n0, count, *, device=None, out=None, algo=B.ALGO_AUTO, work
         out = torch.empty(int(count), dtype=torch.int32, device=f"cuda:{dev}")
     else:
         dev = _check_out(torch, out, int(count))
-    if length is not None:
-        B.check(B.lib().bhw_generate_len_device(ctypes.byref(params), int(length), dev, _stream_ptr(torch, dev), int(n0), int(count),
-                                                ctypes.c_void_p(out.data_ptr())))
-        return out
-    if workspace is not None and workspace.device.index != dev:
-        raise ValueError("workspace must live on the output's device")
-    ex = _exec(algo, workspace, event_after_build, table_format)
-    B.check(B.lib().bhw_generate_device_ex(ctypes.byref(params), dev, _stream_ptr(torch, dev), int(n0), int(count),
-                                            ctypes.c_void_p(out.data_ptr()), ctypes.byref(ex)))
+    ex = ()
+    if length is None:
+        if workspace is not None and workspace.device.index != dev:
+            raise ValueError("workspace must live on the output's device")
+        ex = (ctypes.byref(_exec(algo, workspace, event_after_build, table_format)),)
+    _call("bhw_generate_device_ex", "bhw_generate_len_device", (), params, length,
+          (dev, _stream_ptr(torch, dev), int(n0), int(count), ctypes.c_void_p(out.data_ptr())), ex)
     return out
 
 
@@ -146,6 +144,15 @@ def apply(params, x, *, n0=0, shift=None, out=None):
     B.check(B.lib().bhw_apply_device(ctypes.byref(params), dev, _stream_ptr(torch, dev), int(n0), x.numel(),
                                       ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr()), int(shift)))
     return out
+
+
+def _call(pow2, any_len, lead, params, length, args, pow2_args=()):
+    """One C call of a front: pow2(*lead, params, *args, *pow2_args) for the power-of-two window (length None), else its
+    any-length entry point any_len(*lead, params, length, *args)."""
+    if length is None:
+        B.check(getattr(B.lib(), pow2)(*lead, ctypes.byref(params), *args, *pow2_args))
+    else:
+        B.check(getattr(B.lib(), any_len)(*lead, ctypes.byref(params), int(length), *args))
 
 
 def _window_len(params, length):
@@ -210,11 +217,8 @@ def apply_frames(params, x, hop, *, frames=None, channels=1, shift=None, out=Non
         raise ValueError("x must be a contiguous int32 CUDA tensor")
     dev = x.device.index
     f, out, result = _frames_call(torch, params, x, int(hop), frames, channels, shift, out, y_stride, dev, length)
-    args = (dev, _stream_ptr(torch, dev), ctypes.byref(f), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr()))
-    if length is None:
-        B.check(B.lib().bhw_apply_frames_device(ctypes.byref(params), *args))
-    else:
-        B.check(B.lib().bhw_apply_frames_len_device(ctypes.byref(params), int(length), *args))
+    _call("bhw_apply_frames_device", "bhw_apply_frames_len_device", (), params, length,
+          (dev, _stream_ptr(torch, dev), ctypes.byref(f), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr())))
     return result
 
 
@@ -266,11 +270,8 @@ def overlap_add(params, y, hop, *, frames=None, channels=1, shift=None, out=None
         raise ValueError("y must be a contiguous int32 CUDA tensor")
     dev = y.device.index
     o, out, result = _ola_call(torch, params, y, int(hop), frames, channels, shift, out, y_stride, t0, count, dev, length)
-    args = (dev, _stream_ptr(torch, dev), ctypes.byref(o), ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(out.data_ptr()))
-    if length is None:
-        B.check(B.lib().bhw_overlap_add_device(ctypes.byref(params), *args))
-    else:
-        B.check(B.lib().bhw_overlap_add_len_device(ctypes.byref(params), int(length), *args))
+    _call("bhw_overlap_add_device", "bhw_overlap_add_len_device", (), params, length,
+          (dev, _stream_ptr(torch, dev), ctypes.byref(o), ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(out.data_ptr())))
     return result
 
 
@@ -333,12 +334,8 @@ class ResidentTable:
             out = torch.empty(int(count), dtype=torch.int32, device=f"cuda:{self.device}")
         elif _check_out(torch, out, int(count)) != self.device:
             raise ValueError("out must live on the table's device")
-        if length is None:
-            B.check(B.lib().bhw_generate_from_table(h, ctypes.byref(params), _stream_ptr(torch, self.device), int(n0), int(count),
-                                                    ctypes.c_void_p(out.data_ptr())))
-        else:
-            B.check(B.lib().bhw_generate_len_from_table(h, ctypes.byref(params), int(length), _stream_ptr(torch, self.device), int(n0),
-                                                        int(count), ctypes.c_void_p(out.data_ptr())))
+        _call("bhw_generate_from_table", "bhw_generate_len_from_table", (h,), params, length,
+              (_stream_ptr(torch, self.device), int(n0), int(count), ctypes.c_void_p(out.data_ptr())))
         return out
 
     def window(self, params, length, *, sym=False, out=None):
@@ -372,11 +369,8 @@ class ResidentTable:
         if not isinstance(x, torch.Tensor) or not x.is_cuda or x.device.index != self.device:
             raise ValueError("x must be a contiguous int32 CUDA tensor on the table's device")
         f, out, result = _frames_call(torch, params, x, int(hop), frames, channels, shift, out, y_stride, self.device, length)
-        args = (_stream_ptr(torch, self.device), ctypes.byref(f), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr()))
-        if length is None:
-            B.check(B.lib().bhw_apply_frames_from_table(h, ctypes.byref(params), *args))
-        else:
-            B.check(B.lib().bhw_apply_frames_len_from_table(h, ctypes.byref(params), int(length), *args))
+        _call("bhw_apply_frames_from_table", "bhw_apply_frames_len_from_table", (h,), params, length,
+              (_stream_ptr(torch, self.device), ctypes.byref(f), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr())))
         return result
 
     def describe_frames(self, params, frames, hop, *, channels=1, y_stride=0):
@@ -392,11 +386,8 @@ class ResidentTable:
         if not isinstance(y, torch.Tensor) or not y.is_cuda or y.device.index != self.device:
             raise ValueError("y must be a contiguous int32 CUDA tensor on the table's device")
         o, out, result = _ola_call(torch, params, y, int(hop), frames, channels, shift, out, y_stride, t0, count, self.device, length)
-        args = (_stream_ptr(torch, self.device), ctypes.byref(o), ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(out.data_ptr()))
-        if length is None:
-            B.check(B.lib().bhw_overlap_add_from_table(h, ctypes.byref(params), *args))
-        else:
-            B.check(B.lib().bhw_overlap_add_len_from_table(h, ctypes.byref(params), int(length), *args))
+        _call("bhw_overlap_add_from_table", "bhw_overlap_add_len_from_table", (h,), params, length,
+              (_stream_ptr(torch, self.device), ctypes.byref(o), ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(out.data_ptr())))
         return result
 
     def describe_overlap_add(self, params, frames, hop, count=None, *, t0=0, channels=1, y_stride=0):
