@@ -11,6 +11,7 @@ WIN_HAMMING, WIN_HANN, WIN_BH3, WIN_BH4, WIN_BH5, WIN_BH7 = 1, 2, 3, 4, 5, 7
 ALGO_AUTO, ALGO_DIRECT, ALGO_TABLE, ALGO_FUSED = 0, 1, 2, 3
 TABLE_BEST, TABLE_PLAIN, TABLE_DELTA16, TABLE_RESIDUAL, TABLE_NIBBLE, TABLE_NIBBLE_ESC = 0, 1, 2, 3, 4, 5
 ABI_VERSION = 4
+OLA_NORMALIZE = 1
 
 # every symbol include/bhw.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = (
@@ -26,6 +27,8 @@ ABI_SYMBOLS = (
     "bhw_overlap_add_device", "bhw_overlap_add_from_table", "bhw_overlap_add_describe",
     "bhw_generate_len_device", "bhw_generate_len_from_table", "bhw_apply_frames_len_device", "bhw_apply_frames_len_from_table",
     "bhw_overlap_add_len_device", "bhw_overlap_add_len_from_table", "bhw_describe_len",
+    "bhw_apply_frames_f32_device", "bhw_apply_frames_f32_from_table", "bhw_overlap_add_f32_device", "bhw_overlap_add_f32_from_table",
+    "bhw_describe_f32",
 )
 
 
@@ -175,6 +178,12 @@ def lib():
     L.bhw_overlap_add_len_from_table.argtypes = [T, P, u64, vp, O, i32p, i32p]
     L.bhw_describe_len.argtypes = [T, P, u64, u64, u64, F, O, ctypes.c_char_p, u64]
     L.bhw_dbg_len_force_kernels.argtypes = [ci]
+    f32p = ctypes.c_void_p
+    L.bhw_apply_frames_f32_device.argtypes = [P, u64, ci, vp, F, f32p, f32p]
+    L.bhw_apply_frames_f32_from_table.argtypes = [T, P, u64, vp, F, f32p, f32p]
+    L.bhw_overlap_add_f32_device.argtypes = [P, u64, ci, vp, O, u32, f32p, f32p]
+    L.bhw_overlap_add_f32_from_table.argtypes = [T, P, u64, vp, O, u32, f32p, f32p]
+    L.bhw_describe_f32.argtypes = [T, P, u64, F, O, u32, ctypes.c_char_p, u64]
     PA = ctypes.POINTER(BhwAtan2Params)
     L.bhw_atan2_device.argtypes = [PA, ci, vp, u64, i32p, i32p, i32p]
     L.bhw_atan2_to_host.argtypes = [PA, ci, u64, i32p, i32p, i32p]
@@ -240,6 +249,20 @@ def describe_len(params, length, *, n0=0, count=None, frames=None, ola=None, tab
     check(lib().bhw_describe_len(table, ctypes.byref(params), int(length), int(n0), count,
                                  ctypes.byref(frames) if frames is not None else None, ctypes.byref(ola) if ola is not None else None,
                                  buf, 512))
+    return buf.value.decode()
+
+
+def describe_f32(params, length=None, *, frames=None, ola=None, normalize=False, table=None):
+    """One line: the route, the plan, the kernel and (overlap-add) whether it normalises, for a float32 call over the window of
+    `length` (None: 2^phi_width) (bhw_describe_f32).  Exactly one of frames (a BhwFrames, make_frames) and ola (a BhwOla,
+    make_ola).  `table` is a resident table handle or None for the library call.  Host arithmetic only."""
+    if (frames is None) == (ola is None):
+        raise ValueError("pass frames or ola (one of them)")
+    length = (1 << params.phi_width) if length is None else int(length)
+    buf = ctypes.create_string_buffer(512)
+    check(lib().bhw_describe_f32(table, ctypes.byref(params), length,
+                                 ctypes.byref(frames) if frames is not None else None, ctypes.byref(ola) if ola is not None else None,
+                                 OLA_NORMALIZE if normalize else 0, buf, 512))
     return buf.value.decode()
 
 

@@ -1060,6 +1060,38 @@ int generate_len(bhw_table t, const bhw_params *p, uint64_t length, int device, 
                                                                const BhwLenPhase *lp) { return bhwk_len_range(l, c, w, tab, *lp, n0, count, d_out); });
 }
 
+// Every float32 frame apply, from table t (checked non-NULL by the caller) or by the direct CORDIC chains (t NULL): the checks, then
+// the float32 frames kernel (no per-frame route).
+int frames_f32_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_frames *f, const float *d_x,
+                   float *d_y)
+{
+    int rc = bhwp_f32_checks(p, length, 0);
+    if (!rc && t) rc = table_call_checks(t, p);
+    if (!rc) rc = bhwp_frames_checks(p, f, d_x, d_y, true, length);
+    if (rc || !f->frames) return rc;
+    const uint64_t L = len_route(p, length);
+    const BhwFramesPlan pl = bhwp_frames_plan(p, f, t != nullptr, -1, L, true);
+    const char *what = t ? "f32 frames launch (resident table)" : "f32 frames launch";
+    return run_source(t, p, L, device, stream, what, [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *tab,
+                                                         const BhwLenPhase *lp) { return bhwk_frames_f32(l, c, w, pl, f, d_x, d_y, tab, lp); });
+}
+
+// Every float32 overlap-add, as frames_f32_run; flags: BHW_OLA_NORMALIZE or 0.
+int ola_f32_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_ola *o, uint32_t flags, const float *d_y,
+                float *d_x)
+{
+    int rc = bhwp_f32_checks(p, length, flags);
+    if (!rc && t) rc = table_call_checks(t, p);
+    if (!rc) rc = bhwp_ola_checks(p, o, d_y, d_x, true, length);
+    if (rc || !o->count) return rc;
+    const uint64_t L = len_route(p, length);
+    const bool norm = (flags & BHW_OLA_NORMALIZE) != 0;
+    const BhwOlaPlan pl = bhwp_ola_plan(p, o, t != nullptr, 0, 0, L, norm ? kOlaQMaxNorm : kOlaQMax);
+    const char *what = t ? "f32 overlap-add launch (resident table)" : "f32 overlap-add launch";
+    return run_source(t, p, L, device, stream, what, [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *tab,
+                                                         const BhwLenPhase *lp) { return bhwk_ola_f32(l, c, w, pl, o, norm, d_y, d_x, tab, lp); });
+}
+
 } // namespace
 
 extern "C" {
@@ -1121,6 +1153,49 @@ int bhw_describe_len(bhw_table t, const bhw_params *p, uint64_t length, uint64_t
     if (!rc && f) rc = bhwp_frames_checks(p, f, nullptr, nullptr, false, length);
     if (!rc && o) rc = bhwp_ola_checks(p, o, nullptr, nullptr, false, length);
     return rc ? rc : bhwp_describe_len(p, t ? &t->c : nullptr, t ? t->tiled : false, length, g_len_force, n0, count, f, o, buf, len);
+}
+
+// ---- float32 frame apply and overlap-add (include/bhw.h: bhw_apply_frames_f32_device ...) -----------------------------------------
+// Each *_f32 call: bhwp_f32_checks, then (from-table calls) the handle, then the checks of the int32 counterpart with L in place of N,
+// then the float32 kernels: at L = 2^phi_width those of the power-of-two window, else the any-length forms (len_route).  Every route
+// allocates nothing and uses no scratch.
+
+int bhw_apply_frames_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_frames *f, const float *d_x,
+                                float *d_y)
+{
+    return frames_f32_run(nullptr, p, length, device, hip_stream, f, d_x, d_y);
+}
+
+int bhw_apply_frames_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_frames *f,
+                                    const float *d_x, float *d_y)
+{
+    const int rc = bhwp_f32_checks(p, length, 0);
+    if (rc) return rc;
+    return t ? frames_f32_run(t, p, length, t->device, hip_stream, f, d_x, d_y) : fail(BHW_ERR_BADARG, "table is NULL");
+}
+
+int bhw_overlap_add_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_ola *o, uint32_t flags,
+                               const float *d_y, float *d_x)
+{
+    return ola_f32_run(nullptr, p, length, device, hip_stream, o, flags, d_y, d_x);
+}
+
+int bhw_overlap_add_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_ola *o, uint32_t flags,
+                                   const float *d_y, float *d_x)
+{
+    const int rc = bhwp_f32_checks(p, length, flags);
+    if (rc) return rc;
+    return t ? ola_f32_run(t, p, length, t->device, hip_stream, o, flags, d_y, d_x) : fail(BHW_ERR_BADARG, "table is NULL");
+}
+
+int bhw_describe_f32(bhw_table t, const bhw_params *p, uint64_t length, const bhw_frames *f, const bhw_ola *o, uint32_t flags, char *buf,
+                     uint64_t len)
+{
+    int rc = bhwp_f32_checks(p, length, flags);
+    if (!rc && t) rc = table_call_checks(t, p);
+    if (!rc && f) rc = bhwp_frames_checks(p, f, nullptr, nullptr, false, length);
+    if (!rc && o) rc = bhwp_ola_checks(p, o, nullptr, nullptr, false, length);
+    return rc ? rc : bhwp_describe_f32(p, t ? &t->c : nullptr, length, g_len_force, f, o, flags, buf, len);
 }
 
 // Development hook (not part of the ABI in include/bhw.h): on != 0 sends the *_len calls at L = 2^phi_width to the any-length kernels

@@ -932,6 +932,13 @@ template <typename F> inline void with_range_form(int fmt, int nt, int mode, F &
     });
 }
 
+// The I/Q access form of a frames or overlap-add launch (their `io` argument): 0 one channel; 2 two channels moved as one 8-byte
+// access, when both bases and the row stride are 8-byte aligned; 1 two channels, two 4-byte accesses.
+inline uint32_t pair_io(uint32_t channels, const void *a, const void *b, uint64_t stride)
+{
+    return channels == 1 ? 0u : (((((uintptr_t)a | (uintptr_t)b) % 8 == 0) && stride % 2 == 0) ? 2u : 1u);
+}
+
 inline int finish(hipError_t e)
 {
     if (e == hipSuccess) e = t_launch_err;

@@ -11,79 +11,16 @@
 // that bounds every other kernel of the library is spread over G frames, and what is left is the x read and the y write.
 //   - Workgroup: kFramesBlock lanes, min(N, 256) along k and the rest side by side over frames (windows shorter than 256).
 //   - Grid: (N / kx) x (frame groups); bhwp_frames_plan picks G so that about kFramesTargetWg workgroups fill the 256 CUs.
-//   - x is read up to ceil(N / hop) times (once per frame that covers it), so it takes default-policy loads -- the nontemporal load
-//     of the single-use emit() would push it past the caches -- and the frame groups are dispatched in signal order, so the frames
-//     that share an x are in flight together.
-//   - The frame loop issues four frames' loads before their stores; two channels move as one 8-byte access when both bases and the
-//     stride allow it (FramesArgs.io), else as two 4-byte ones.
-#include "bhw_device.h"
+//   - x is read up to ceil(N / hop) times (once per frame that covers it), so it takes default-policy loads, and the frame groups are
+//     dispatched in signal order, so the frames that share an x are in flight together.
+//   - The frame loop (bhw_frames.h, shared with the float32 kernels of bhw_frames_f32.hip) issues four frames' loads before their
+//     stores; two channels move as one 8-byte access when both bases and the stride allow it (FramesArgs.io), else as two 4-byte ones.
+#include "bhw_frames.h"
 
 namespace {
 
-struct FramesArgs {
-    const int32_t *x;
-    int32_t *y;
-    uint64_t frames, hop, y_stride;
-    uint64_t group;      // G: frame rows of one workgroup
-    uint32_t kx;         // lanes along k (a power of two)
-    uint32_t fy;         // frame rows side by side in a workgroup: kFramesBlock / kx
-    uint32_t shift;
-    uint32_t io;         // 0: one channel; 1: two channels, 4-byte accesses; 2: two channels, one 8-byte access
-};
-
-__device__ __forceinline__ int32_t apply1(int32_t x, int32_t w, uint32_t shift) { return (int32_t)(((int64_t)x * (int64_t)w) >> shift); }
-
-// The frames of this lane: rows [blockIdx.y * G, +G) of fy frames, frame f = row * fy + ty.  C = channels, VEC: one 8-byte access.
-template <int C, bool VEC>
-__device__ __forceinline__ void frames_loop(const FramesArgs &a, uint32_t k, uint32_t ty, int32_t w)
-{
-    constexpr int U = 4;
-    const uint64_t f_end0 = ((uint64_t)blockIdx.y + 1) * a.group * a.fy;
-    const uint64_t f_end = f_end0 < a.frames ? f_end0 : a.frames;
-    const uint64_t step = a.fy;
-    for (uint64_t f = (uint64_t)blockIdx.y * a.group * a.fy + ty; f < f_end; f += U * step) {
-        int32_t v[U][C];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const uint64_t fu = f + u * step;
-            if (fu < f_end) {
-                const uint64_t xi = (fu * a.hop + k) * C;
-                if constexpr (C == 1) {
-                    v[u][0] = a.x[xi];
-                } else if constexpr (VEC) {
-                    const int2 p = *(const int2 *)(a.x + xi);
-                    v[u][0] = p.x;
-                    v[u][1] = p.y;
-                } else {
-                    v[u][0] = a.x[xi];
-                    v[u][1] = a.x[xi + 1];
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const uint64_t fu = f + u * step;
-            if (fu < f_end) {
-                int32_t *yp = a.y + fu * a.y_stride + (uint64_t)k * C;
-                if constexpr (C == 1) {
-                    yp[0] = apply1(v[u][0], w, a.shift);
-                } else if constexpr (VEC) {
-                    *(int2 *)yp = make_int2(apply1(v[u][0], w, a.shift), apply1(v[u][1], w, a.shift));
-                } else {
-                    yp[0] = apply1(v[u][0], w, a.shift);
-                    yp[1] = apply1(v[u][1], w, a.shift);
-                }
-            }
-        }
-    }
-}
-
-__device__ __forceinline__ void frames_apply(const FramesArgs &a, uint32_t k, uint32_t ty, int32_t w)
-{
-    if (a.io == 0)      frames_loop<1, false>(a, k, ty, w);
-    else if (a.io == 1) frames_loop<2, false>(a, k, ty, w);
-    else                frames_loop<2, true>(a, k, ty, w);
-}
+// the int32 form of the frame loop's arguments (bhw_frames.h)
+struct FramesArgs : FramesIo<int32_t> {};
 
 // Coefficient by the direct CORDIC chains.  FORM 0 / 1: the cordic_full chain of k_direct (T = int32_t, or int64_t where the state
 // needs more than 32 bits); FORM 2: the mad-form rotation where it applies (direct_form, the rule bhwk_direct picks k_direct_fast by).
@@ -157,7 +94,7 @@ int bhwk_frames(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinCfg &w
     a.kx = pl.kx;
     a.fy = pl.fy;
     a.shift = f->shift;
-    a.io = f->channels == 1 ? 0u : ((((uintptr_t)d_x | (uintptr_t)d_y) % 8 == 0 && pl.y_stride % 2 == 0) ? 2u : 1u);
+    a.io = pair_io(f->channels, d_x, d_y, pl.y_stride);
     const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y), block(kFramesBlock);
     if (!d_table) {
         with_int_or_last<2, 1, 0>(direct_form(c_in), [&](auto D) { launch_phase(k_frames_direct_len<D>, k_frames_direct<D>, lp, grid, block, st, c_in, w, a); });

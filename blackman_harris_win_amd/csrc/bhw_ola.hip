@@ -16,36 +16,14 @@
 //     outputs); its trip count is the wave's largest, with the other lanes masked, so every lane reaches range_coeff together.
 //   - y and x are single-use streams: nontemporal loads and stores (the emit() policy); two channels move as one 8-byte access when
 //     both bases and the stride allow it (OlaArgs.io), else as two 4-byte ones.
-#include "bhw_device.h"
+#include "bhw_ola.h"
 
 namespace {
 
 typedef int ola_v2i __attribute__((ext_vector_type(2)));      // one I/Q pair (the nontemporal builtins take native vectors only)
 
-struct OlaArgs {
-    const int32_t *y;
-    int32_t *x;
-    uint64_t n;          // N = 2^phi_width, or the length L of a window of any length
-    uint64_t frames, hop, y_stride, count;
-    uint64_t lanes;      // residues in use: min(hop, count)
-    uint64_t rows;       // ceil(count / hop)
-    uint64_t row_blocks; // workgroup rows of fy * Q hops
-    uint64_t q0, r0;     // t0 = q0 * hop + r0
-    uint64_t rlim;       // residues r < rlim are reached by jmax frames, r in [rlim, N) by jmax - 1, r >= N by none
-    int64_t jmax;        // ceil(N / hop)
-    uint32_t rx;         // lanes along the residue (a power of two)
-    uint32_t fy;         // rows side by side in a workgroup: kOlaBlock / rx
-    uint32_t q;          // Q: hops of one lane, 1..kOlaQMax
-    uint32_t shift;
-    uint32_t io;         // 0: one channel; 1: two channels, 4-byte accesses; 2: two channels, one 8-byte access
-};
-
-__device__ __forceinline__ uint32_t wave_max(uint32_t v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, m));
-    return v;
-}
+// the int32 form of the overlap-add arguments (bhw_ola.h)
+struct OlaArgs : OlaIo<int32_t> {};
 
 // The outputs of this lane.  C = channels, VEC: one 8-byte access per I/Q pair; coeff(k) gives w[k] for k < N (and is called
 // with k = 0 on masked lanes).
@@ -193,25 +171,7 @@ int bhwk_ola(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinCfg &w, c
     if (!o->count) return 0;
     hipStream_t st = (hipStream_t)l.stream;
     OlaArgs a;
-    a.y = d_y;
-    a.x = d_x;
-    a.n = pl.len;                                                  // N = 2^phi_width, or L
-    a.frames = o->frames;
-    a.hop = o->hop;
-    a.y_stride = pl.y_stride;
-    a.count = o->count;
-    a.lanes = pl.lanes;
-    a.rows = pl.rows;
-    a.row_blocks = pl.row_blocks;
-    a.q0 = pl.q0;
-    a.r0 = pl.r0;
-    a.jmax = (int64_t)pl.jmax;
-    a.rlim = a.n - (pl.jmax - 1) * o->hop;                         // (jmax - 1) * hop < N (or L)
-    a.rx = pl.rx;
-    a.fy = pl.fy;
-    a.q = pl.q;
-    a.shift = o->shift;
-    a.io = o->channels == 1 ? 0u : ((((uintptr_t)d_y | (uintptr_t)d_x) % 8 == 0 && pl.y_stride % 2 == 0) ? 2u : 1u);
+    ola_args(a, pl, o, d_y, d_x);
     const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y), block(kOlaBlock);
     if (!d_table) {
         with_int_or_last<0, 1, 2>(a.io, [&](auto IO) {

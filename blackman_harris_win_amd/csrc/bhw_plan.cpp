@@ -750,11 +750,12 @@ void kernel_name(const bhw_params *p, const BhwCordicCfg *ct, const char *direct
 }
 
 // the describe line of a frames launch (bhwp_describe_frames, bhwp_describe_len): prefix, kernel, plan shape
+// (direct / table: the kernel names, those of the float32 kernels for bhwp_describe_f32)
 void frames_line(const char *prefix, const bhw_params *p, const BhwCordicCfg *ct, const bhw_frames *f, const BhwFramesPlan &pl, bool any_len,
-                 char *buf, uint64_t len)
+                 char *buf, uint64_t len, const char *direct = "k_frames_direct", const char *table = "k_frames_table")
 {
     char kern[64];
-    kernel_name(p, ct, "k_frames_direct", "k_frames_table", any_len, kern, sizeof kern);
+    kernel_name(p, ct, direct, table, any_len, kern, sizeof kern);
     snprintf(buf, len, "%s%s, %u channel%s, G = %llu frames per lane, grid %llu x %llu x %u lanes (%u along k)", prefix, kern, f->channels,
              f->channels == 2 ? "s" : "", (unsigned long long)pl.group, (unsigned long long)pl.grid_x, (unsigned long long)pl.grid_y,
              kFramesBlock, pl.kx);
@@ -762,10 +763,10 @@ void frames_line(const char *prefix, const bhw_params *p, const BhwCordicCfg *ct
 
 // the describe line of an overlap-add launch with count > 0 (bhwp_describe_ola, bhwp_describe_len): prefix, kernel, plan shape
 void ola_line(const char *prefix, const bhw_params *p, const BhwCordicCfg *ct, const bhw_ola *o, const BhwOlaPlan &pl, bool any_len, char *buf,
-              uint64_t len)
+              uint64_t len, const char *direct = "k_ola_direct", const char *table = "k_ola_table")
 {
     char kern[64];
-    kernel_name(p, ct, "k_ola_direct", "k_ola_table", any_len, kern, sizeof kern);
+    kernel_name(p, ct, direct, table, any_len, kern, sizeof kern);
     snprintf(buf, len, "%s%s, %u channel%s, Q = %u hops per lane, up to %llu frames per output, grid %llu x %llu x %u lanes (%u along r, "
              "%u along q)", prefix, kern, o->channels, o->channels == 2 ? "s" : "", pl.q, (unsigned long long)pl.jmax,
              (unsigned long long)pl.grid_x, (unsigned long long)pl.grid_y, kOlaBlock, pl.rx, pl.fy);
@@ -804,14 +805,14 @@ int bhwp_frames_checks(const bhw_params *p, const bhw_frames *f, const void *d_x
     return BHW_OK;
 }
 
-BhwFramesPlan bhwp_frames_plan(const bhw_params *p, const bhw_frames *f, bool from_table, int force_route, uint64_t length)
+BhwFramesPlan bhwp_frames_plan(const bhw_params *p, const bhw_frames *f, bool from_table, int force_route, uint64_t length, bool f32)
 {
     BhwFramesPlan pl{};
     const uint64_t N = length ? length : 1ull << p->phi_width;
     pl.len = N;
     pl.y_stride = f->y_stride ? f->y_stride : N * f->channels;
     if (from_table) pl.route = BHWP_FRAMES_TABLE;
-    else if (length) pl.route = BHWP_FRAMES_DIRECT;                            // the any-length kernels have no per-frame route
+    else if (length || f32) pl.route = BHWP_FRAMES_DIRECT;                     // the any-length and float32 kernels have no per-frame route
     else if (f->channels == 2) pl.route = BHWP_FRAMES_DIRECT;                  // the existing apply has no I/Q form
     else if (p->sin_type != BHW_SIN_CORDIC) pl.route = BHWP_FRAMES_PER_FRAME;  // no frames kernel for the Taylor sources
     else {
@@ -821,7 +822,7 @@ BhwFramesPlan bhwp_frames_plan(const bhw_params *p, const bhw_frames *f, bool fr
         const bool per_frame = f->frames * kFramesPerFrameRef < (uint64_t)bhwp_frames_crossover(p->phi_width) * work;
         pl.route = per_frame ? BHWP_FRAMES_PER_FRAME : BHWP_FRAMES_DIRECT;
     }
-    if (force_route >= 0 && !from_table && force_route != BHWP_FRAMES_TABLE &&
+    if (force_route >= 0 && !from_table && !f32 && force_route != BHWP_FRAMES_TABLE &&
         !(force_route == BHWP_FRAMES_PER_FRAME && f->channels == 2) && !(force_route == BHWP_FRAMES_DIRECT && p->sin_type != BHW_SIN_CORDIC))
         pl.route = force_route;
     pl.kx = 1;                                                                 // N itself, or the power of two at or above L
@@ -898,7 +899,8 @@ int bhwp_ola_checks(const bhw_params *p, const bhw_ola *o, const void *d_y, cons
     return BHW_OK;
 }
 
-BhwOlaPlan bhwp_ola_plan(const bhw_params *p, const bhw_ola *o, bool from_table, uint32_t force_q, uint32_t force_rx, uint64_t length)
+BhwOlaPlan bhwp_ola_plan(const bhw_params *p, const bhw_ola *o, bool from_table, uint32_t force_q, uint32_t force_rx, uint64_t length,
+                         uint32_t q_max)
 {
     BhwOlaPlan pl{};
     const uint64_t N = length ? length : 1ull << p->phi_width;
@@ -925,9 +927,9 @@ BhwOlaPlan bhwp_ola_plan(const bhw_params *p, const bhw_ola *o, bool from_table,
     uint64_t Q = (row_groups + gy_target - 1) / gy_target;
     if (Q < pl.jmax) Q = pl.jmax;
     if (Q > row_groups) Q = row_groups;
-    if (Q > kOlaQMax) Q = kOlaQMax;
+    if (Q > q_max) Q = q_max;
     if (Q < 1) Q = 1;
-    if (force_q >= 1 && force_q <= kOlaQMax) Q = force_q;
+    if (force_q >= 1 && force_q <= q_max) Q = force_q;
     pl.q = (uint32_t)Q;
     pl.row_blocks = (pl.rows + (uint64_t)pl.fy * pl.q - 1) / ((uint64_t)pl.fy * pl.q);
     pl.grid_y = pl.row_blocks < kOlaMaxGridY ? pl.row_blocks : kOlaMaxGridY;
@@ -988,6 +990,42 @@ int bhwp_describe_len(const bhw_params *p, const BhwCordicCfg *ct, bool tiled, u
                  (unsigned long long)(n0 % length));
     }
     snprintf(buf, len, "any-length route (L = %llu, phi_width %u): %s", (unsigned long long)length, p->phi_width, inner);
+    return BHW_OK;
+}
+
+// ---- float32 frame apply and overlap-add ----------------------------------------------------------------------------------------
+
+int bhwp_f32_checks(const bhw_params *p, uint64_t length, uint32_t flags)
+{
+    const int rc = bhwp_len_checks(p, length);
+    if (rc) return rc;
+    if (flags & ~BHW_OLA_NORMALIZE) return bhwp_fail(BHW_ERR_BADARG, "flags 0x%x (0 or BHW_OLA_NORMALIZE)", flags);
+    return BHW_OK;
+}
+
+int bhwp_describe_f32(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, bool force, const bhw_frames *f, const bhw_ola *o,
+                      uint32_t flags, char *buf, uint64_t len)
+{
+    if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
+    if (!f == !o) return bhwp_fail(BHW_ERR_BADARG, "pass a frames or an overlap-add descriptor (one of them)");
+    if (f && flags) return bhwp_fail(BHW_ERR_BADARG, "flags 0x%x: the frames call takes none", flags);
+    const bool any = bhwp_len_kernels(p, length, force);
+    char win[64], inner[384];
+    if (any) snprintf(win, sizeof win, "L = %llu", (unsigned long long)length);
+    else     snprintf(win, sizeof win, "L = 2^%u", p->phi_width);
+    const char *route = ct ? "table" : "direct";
+    if (f) {
+        frames_line("", p, ct, f, bhwp_frames_plan(p, f, ct != nullptr, -1, any ? length : 0, true), any, inner, sizeof inner,
+                    "k_frames_f32_direct", "k_frames_f32_table");
+        snprintf(buf, len, "f32 frames %s (%s): %s", route, win, inner);
+        return BHW_OK;
+    }
+    const char *norm = (flags & BHW_OLA_NORMALIZE) ? "normalised by the window envelope" : "not normalised";
+    if (!o->count) snprintf(inner, sizeof inner, "nothing (count 0)");
+    else           ola_line("", p, ct, o, bhwp_ola_plan(p, o, ct != nullptr, 0, 0, any ? length : 0,
+                                                 (flags & BHW_OLA_NORMALIZE) ? kOlaQMaxNorm : kOlaQMax), any, inner, sizeof inner,
+                            "k_ola_f32_direct", "k_ola_f32_table");
+    snprintf(buf, len, "f32 overlap-add %s (%s), %s: %s", route, win, norm, inner);
     return BHW_OK;
 }
 

@@ -190,7 +190,9 @@ int  bhwp_frames_checks(const bhw_params *p, const bhw_frames *f, const void *d_
 // route, frame-group size and grid of a call that passed bhwp_frames_checks; force_route >= 0 overrides the route rule (A/B runs).
 // length > 0: the any-length kernels (k_frames_direct_len / k_frames_table_len) over a window of length L: kx the power of two at or
 // above min(L, kFramesBlock), grid_x = ceil(L / kx).  At a power-of-two L the shape is the one of length 0.
-BhwFramesPlan bhwp_frames_plan(const bhw_params *p, const bhw_frames *f, bool from_table, int force_route = -1, uint64_t length = 0);
+// f32: the float32 kernels (bhw_frames_f32.hip), which have no per-frame route: the direct or the table route, same shape.
+BhwFramesPlan bhwp_frames_plan(const bhw_params *p, const bhw_frames *f, bool from_table, int force_route = -1, uint64_t length = 0,
+                               bool f32 = false);
 // bhw_apply_frames_describe: ct = the resident table's resolved configuration (format and layout set), or NULL for the library call
 int  bhwp_describe_frames(const bhw_params *p, const BhwCordicCfg *ct, const bhw_frames *f, char *buf, uint64_t len);
 // the frames kernel of a plan (bhw_frames.hip): d_table NULL = k_frames_direct, else k_frames_table over the resident table of c;
@@ -206,6 +208,7 @@ int  bhwk_frames(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, 
 enum { BHWP_OLA_DIRECT = 0, BHWP_OLA_TABLE = 1 };
 constexpr uint32_t kOlaBlock = 256;           // lanes of a workgroup: rx along the residue, fy = kOlaBlock / rx side by side over rows
 constexpr uint32_t kOlaQMax = 16;             // Q: rows (hops) of one lane, the int64 accumulators it holds per channel
+constexpr uint32_t kOlaQMaxNorm = 8;          // ... of the float32 overlap-add with the envelope division (Q more binary64 sums)
 constexpr uint32_t kOlaTargetWg = 4096;       // workgroups Q is cut for (16 per CU on 256 CUs) ...
 constexpr uint64_t kOlaOnePassGx = 1024;      // ... unless the residues alone give this many: then Q = kOlaQMax
 constexpr uint32_t kOlaMaxGridY = 65535;      // row blocks beyond it are taken by a grid-stride loop
@@ -232,8 +235,10 @@ int  bhwp_ola_checks(const bhw_params *p, const bhw_ola *o, const void *d_y, con
 // (bhw_dbg_overlap_add_shape: Q in 1..kOlaQMax, rx a power of two <= kOlaBlock; other values are ignored)
 // length > 0: the plan of the any-length kernels (k_ola_direct_len / k_ola_table_len) over a window of length L (jmax = ceil(L / hop));
 // at a power-of-two L it is the plan of length 0.
+// q_max: the Q bound of the kernel (kOlaQMax; kOlaQMaxNorm for the float32 overlap-add with BHW_OLA_NORMALIZE, which holds Q more
+// binary64 sums and is compiled for that many rows).
 BhwOlaPlan bhwp_ola_plan(const bhw_params *p, const bhw_ola *o, bool from_table, uint32_t force_q = 0, uint32_t force_rx = 0,
-                         uint64_t length = 0);
+                         uint64_t length = 0, uint32_t q_max = kOlaQMax);
 // bhw_overlap_add_describe: ct = the resident table's resolved configuration (format and layout set), or NULL for the library call
 int  bhwp_describe_ola(const bhw_params *p, const BhwCordicCfg *ct, const bhw_ola *o, char *buf, uint64_t len);
 // the overlap-add kernel of a plan (bhw_ola.hip): d_table NULL = k_ola_direct, else k_ola_table over the resident table of c
@@ -252,6 +257,22 @@ inline bool bhwp_len_kernels(const bhw_params *p, uint64_t length, bool force) {
 // (library call).
 int  bhwp_describe_len(const bhw_params *p, const BhwCordicCfg *ct, bool tiled, uint64_t length, bool force, uint64_t n0, uint64_t count,
                        const bhw_frames *f, const bhw_ola *o, char *buf, uint64_t len);
+// ---- float32 frame apply and overlap-add (the *_f32 entry points) ---------------------------------------------------------------
+// Argument checks of every *_f32 call on (p, length, flags), before any other and before any HIP call: bhwp_len_checks, then flags
+// outside {0, BHW_OLA_NORMALIZE} (BADARG).  The frames and overlap-add checks follow with L in place of N.
+int  bhwp_f32_checks(const bhw_params *p, uint64_t length, uint32_t flags);
+// bhw_describe_f32: one line naming the route, the plan, the kernel and whether the overlap-add normalises.  length: L (2^phi_width:
+// the power-of-two kernels unless `force`, as bhwp_len_kernels); exactly one of f and o; ct the resident table's resolved
+// configuration, or NULL (library call).
+int  bhwp_describe_f32(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, bool force, const bhw_frames *f, const bhw_ola *o,
+                       uint32_t flags, char *buf, uint64_t len);
+// the float32 kernels (bhw_frames_f32.hip, bhw_ola_f32.hip / bhw_ola_f32_norm.hip): d_table NULL = the direct CORDIC chains, else
+// the gather over the resident table of c; lp != NULL: the any-length forms over the window of length lp->len
+int  bhwk_frames_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwFramesPlan &pl, const bhw_frames *f,
+                     const float *d_x, float *d_y, const int32_t *d_table, const BhwLenPhase *lp);
+int  bhwk_ola_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwOlaPlan &pl, const bhw_ola *o, bool normalize,
+                  const float *d_y, float *d_x, const int32_t *d_table, const BhwLenPhase *lp);
+
 // the generate kernel of a window of any length (bhw_len.hip): d_table NULL = k_direct_len, else k_range_len over the resident table of c
 int  bhwk_len_range(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *d_table, const BhwLenPhase &lp,
                     uint64_t n0, uint64_t count, int32_t *d_out);

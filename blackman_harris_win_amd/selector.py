@@ -47,10 +47,11 @@ def shard_range(total, rank, world_size):
     return n0, base + (1 if rank < rem else 0)
 
 
-def _check_out(torch, out, need, what="out"):
-    """An output tensor handed to the kernels: int32, on a GPU, contiguous, large enough."""
-    if out.dtype != torch.int32 or not out.is_cuda or not out.is_contiguous() or out.numel() < need:
-        raise ValueError(f"{what} must be a contiguous int32 CUDA tensor with at least {need} elements")
+def _check_out(torch, out, need, what="out", dtype=None):
+    """An output tensor handed to the kernels: int32 (or `dtype`), on a GPU, contiguous, large enough."""
+    dtype = torch.int32 if dtype is None else dtype
+    if out.dtype != dtype or not out.is_cuda or not out.is_contiguous() or out.numel() < need:
+        raise ValueError(f"{what} must be a contiguous {str(dtype).replace('torch.', '')} CUDA tensor with at least {need} elements")
     return out.device.index
 
 
@@ -160,22 +161,39 @@ def _window_len(params, length):
     return (1 << params.phi_width) if length is None else int(length)
 
 
-def window(params, length, *, sym=False, device=None, out=None):
+def window(params, length, *, sym=False, device=None, out=None, dtype=None, shift=None):
     """The int32 coefficients of the window of length `length` (1..2^phi_width): the periodic (DFT-even, spectral-analysis) window
     bhw_generate_len_device(length, n0 = 0, count = length), or with sym=True the symmetric (filter-design) window: the periodic
-    window of length - 1 plus its first coefficient (length >= 2)."""
+    window of length - 1 plus its first coefficient (length >= 2).
+    dtype=torch.float32: the float coefficients v = fl32(w) * 2^-shift the float32 frames and overlap-add calls apply (shift
+    defaults to dat_width - 1), e.g. the window of torch.stft / torch.istft; `out` is then not taken."""
     length = int(length)
-    if sym:
-        if length < 2:
-            raise ValueError("a symmetric window needs length >= 2")
-        return generate(params, 0, length, device=device, out=out, length=length - 1)
-    return generate(params, 0, length, device=device, out=out, length=length)
+    if sym and length < 2:
+        raise ValueError("a symmetric window needs length >= 2")
+    torch = _torch() if dtype is not None else None
+    if dtype is not None and dtype not in (torch.int32, torch.float32):
+        raise ValueError("dtype must be torch.int32 or torch.float32")
+    if dtype is not None and dtype == torch.float32:
+        if out is not None:
+            raise ValueError("out is taken for the int32 window only")
+        return _float_window(torch, window(params, length, sym=sym, device=device), params, shift)
+    if shift is not None:
+        raise ValueError("shift applies to the float32 window only")
+    return generate(params, 0, length, device=device, out=out, length=length - 1 if sym else length)
+
+
+def _float_window(torch, w, params, shift):
+    """v = fl32(w) * 2^-shift: the int32 window to binary32 (round to nearest even), then an exact power-of-two scaling."""
+    shift = params.dat_width - 1 if shift is None else int(shift)
+    if not 0 <= shift <= 62:
+        raise ValueError("shift must be in 0..62")
+    return w.to(torch.float32) * 2.0 ** -shift                  # 2^-shift is a binary32 power of two: the product is exact
 
 
 def _frames_call(torch, params, x, hop, frames, channels, shift, out, y_stride, dev, length=None):
-    """Checks and shapes of apply_frames: (bhw_frames, out, the tensor returned)."""
-    if x.dtype != torch.int32 or not x.is_cuda or not x.is_contiguous() or x.device.index != dev:
-        raise ValueError("x must be a contiguous int32 CUDA tensor on the call's device")
+    """Checks and shapes of apply_frames: (bhw_frames, out, the tensor returned); y takes x's dtype (int32 or float32)."""
+    if x.dtype not in (torch.int32, torch.float32) or not x.is_cuda or not x.is_contiguous() or x.device.index != dev:
+        raise ValueError("x must be a contiguous int32 or float32 CUDA tensor on the call's device")
     if channels not in (1, 2):
         raise ValueError("channels must be 1 or 2")
     if hop < 1:
@@ -192,8 +210,8 @@ def _frames_call(torch, params, x, hop, frames, channels, shift, out, y_stride, 
     if stride < N * channels:
         raise ValueError(f"y_stride must be >= N * channels = {N * channels}")
     if out is None:
-        out = torch.empty((frames, stride), dtype=torch.int32, device=x.device)
-    elif _check_out(torch, out, frames * stride if frames else 0) != dev:
+        out = torch.empty((frames, stride), dtype=x.dtype, device=x.device)
+    elif _check_out(torch, out, frames * stride if frames else 0, dtype=x.dtype) != dev:
         raise ValueError("out must live on x's device")
     if shift is None:
         shift = params.dat_width - 1
@@ -211,21 +229,29 @@ def apply_frames(params, x, hop, *, frames=None, channels=1, shift=None, out=Non
     with one launch (the STFT / Welch front end).  x: contiguous int32 (time-major, I/Q interleaved for channels = 2); frames=None
     takes as many as fit.  Returns a (frames, N) int32 tensor, (frames, N, 2) for I/Q, or a (frames, y_stride) view when y_stride
     is given (the elements past N * channels of each row are not written).  shift defaults to dat_width - 1.  length: the window
-    length L of a window of any length (bhw_apply_frames_len_device; N is L in the shapes above); None: N = 2^phi_width."""
+    length L of a window of any length (bhw_apply_frames_len_device; N is L in the shapes above); None: N = 2^phi_width.
+    A float32 x takes bhw_apply_frames_f32_device: y = fl32(x * v[k]) with v = window(..., dtype=torch.float32, shift=shift), in
+    float32 tensors of the same shapes."""
     torch = _torch()
     if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise ValueError("x must be a contiguous int32 CUDA tensor")
+        raise ValueError("x must be a contiguous int32 or float32 CUDA tensor")
     dev = x.device.index
     f, out, result = _frames_call(torch, params, x, int(hop), frames, channels, shift, out, y_stride, dev, length)
-    _call("bhw_apply_frames_device", "bhw_apply_frames_len_device", (), params, length,
-          (dev, _stream_ptr(torch, dev), ctypes.byref(f), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr())))
+    args = (dev, _stream_ptr(torch, dev), ctypes.byref(f), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr()))
+    if x.dtype == torch.float32:
+        B.check(B.lib().bhw_apply_frames_f32_device(ctypes.byref(params), _window_len(params, length), *args))
+    else:
+        _call("bhw_apply_frames_device", "bhw_apply_frames_len_device", (), params, length, args)
     return result
 
 
-def _ola_call(torch, params, y, hop, frames, channels, shift, out, y_stride, t0, count, dev, length=None):
-    """Checks and shapes of overlap_add: (bhw_ola, out, the tensor returned)."""
-    if not isinstance(y, torch.Tensor) or y.dtype != torch.int32 or not y.is_cuda or not y.is_contiguous() or y.device.index != dev:
-        raise ValueError("y must be a contiguous int32 CUDA tensor on the call's device")
+def _ola_call(torch, params, y, hop, frames, channels, shift, out, y_stride, t0, count, dev, length=None, normalize=False):
+    """Checks and shapes of overlap_add: (bhw_ola, out, the tensor returned, flags); x takes y's dtype (int32 or float32)."""
+    if not isinstance(y, torch.Tensor) or y.dtype not in (torch.int32, torch.float32) or not y.is_cuda or not y.is_contiguous() \
+            or y.device.index != dev:
+        raise ValueError("y must be a contiguous int32 or float32 CUDA tensor on the call's device")
+    if normalize and y.dtype != torch.float32:
+        raise ValueError("normalize=True takes a float32 y (the int32 overlap-add has no envelope division)")
     if channels not in (1, 2):
         raise ValueError("channels must be 1 or 2")
     if hop < 1:
@@ -248,30 +274,38 @@ def _ola_call(torch, params, y, hop, frames, channels, shift, out, y_stride, t0,
         count = max(0, extent - t0)
     count = int(count)
     if out is None:
-        out = torch.empty((count, 2) if channels == 2 else (count,), dtype=torch.int32, device=y.device)
-    elif _check_out(torch, out, count * channels) != dev:
+        out = torch.empty((count, 2) if channels == 2 else (count,), dtype=y.dtype, device=y.device)
+    elif _check_out(torch, out, count * channels, dtype=y.dtype) != dev:
         raise ValueError("out must live on y's device")
     if shift is None:
         shift = params.dat_width - 1
     o = B.make_ola(frames, hop, count, t0=t0, channels=channels, shift=shift, y_stride=stride)
     result = out.view(-1)[:count * channels].view((count, 2) if channels == 2 else (count,))
-    return o, out, result
+    return o, out, result, (B.OLA_NORMALIZE if normalize else 0)
 
 
-def overlap_add(params, y, hop, *, frames=None, channels=1, shift=None, out=None, y_stride=None, t0=0, count=None, length=None):
+def overlap_add(params, y, hop, *, frames=None, channels=1, shift=None, out=None, y_stride=None, t0=0, count=None, length=None,
+                normalize=False):
     """Weighted overlap-add (bhw_overlap_add_device), the STFT synthesis side in one launch:
     x[t - t0, c] = (sum over frames f of y[f, t - f * hop, c] * w[t - f * hop]) >> shift for t in [t0, t0 + count), the sum in
     int64 (wrapping), the low 32 bits stored.  y: contiguous int32 (frames, N), (frames, N, 2) for I/Q, or (frames, y_stride)
     rows of which the first N * channels are read.  frames=None takes every row; count=None the whole extent
     (frames - 1) * hop + N from t0; shift defaults to dat_width - 1.  Returns (count,) int32, or (count, 2) for I/Q.  length: the
-    window length L of a window of any length (bhw_overlap_add_len_device; N is L above); None: N = 2^phi_width."""
+    window length L of a window of any length (bhw_overlap_add_len_device; N is L above); None: N = 2^phi_width.
+    A float32 y takes bhw_overlap_add_f32_device: the sum in binary64 over the frames in ascending order of (double) y * v[k]
+    (v = window(..., dtype=torch.float32, shift=shift)), rounded to float32; normalize=True (float32 only) divides it by the window
+    envelope, the sum of v[k]^2 over the same frames (+0.0 where no frame reaches t), as torch.istft does."""
     torch = _torch()
     if not isinstance(y, torch.Tensor) or not y.is_cuda:
-        raise ValueError("y must be a contiguous int32 CUDA tensor")
+        raise ValueError("y must be a contiguous int32 or float32 CUDA tensor")
     dev = y.device.index
-    o, out, result = _ola_call(torch, params, y, int(hop), frames, channels, shift, out, y_stride, t0, count, dev, length)
-    _call("bhw_overlap_add_device", "bhw_overlap_add_len_device", (), params, length,
-          (dev, _stream_ptr(torch, dev), ctypes.byref(o), ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(out.data_ptr())))
+    o, out, result, flags = _ola_call(torch, params, y, int(hop), frames, channels, shift, out, y_stride, t0, count, dev, length, normalize)
+    if y.dtype == torch.float32:
+        B.check(B.lib().bhw_overlap_add_f32_device(ctypes.byref(params), _window_len(params, length), dev, _stream_ptr(torch, dev),
+                                                   ctypes.byref(o), flags, ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(out.data_ptr())))
+    else:
+        _call("bhw_overlap_add_device", "bhw_overlap_add_len_device", (), params, length,
+              (dev, _stream_ptr(torch, dev), ctypes.byref(o), ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(out.data_ptr())))
     return result
 
 
@@ -367,10 +401,13 @@ class ResidentTable:
         torch = _torch()
         h = self._live()
         if not isinstance(x, torch.Tensor) or not x.is_cuda or x.device.index != self.device:
-            raise ValueError("x must be a contiguous int32 CUDA tensor on the table's device")
+            raise ValueError("x must be a contiguous int32 or float32 CUDA tensor on the table's device")
         f, out, result = _frames_call(torch, params, x, int(hop), frames, channels, shift, out, y_stride, self.device, length)
-        _call("bhw_apply_frames_from_table", "bhw_apply_frames_len_from_table", (h,), params, length,
-              (_stream_ptr(torch, self.device), ctypes.byref(f), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr())))
+        args = (_stream_ptr(torch, self.device), ctypes.byref(f), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr()))
+        if x.dtype == torch.float32:
+            B.check(B.lib().bhw_apply_frames_f32_from_table(h, ctypes.byref(params), _window_len(params, length), *args))
+        else:
+            _call("bhw_apply_frames_from_table", "bhw_apply_frames_len_from_table", (h,), params, length, args)
         return result
 
     def describe_frames(self, params, frames, hop, *, channels=1, y_stride=0):
@@ -378,16 +415,22 @@ class ResidentTable:
         return B.describe_frames(params, frames, hop, channels=channels, y_stride=y_stride, table=self._live())
 
     def overlap_add(self, params, y, hop, *, frames=None, channels=1, shift=None, out=None, y_stride=None, t0=0, count=None,
-                    length=None):
+                    length=None, normalize=False):
         """overlap_add() with the coefficients gathered from this table (bhw_overlap_add_from_table, or
         bhw_overlap_add_len_from_table with a length): no allocation by the library, no synchronisation, capturable into a graph."""
         torch = _torch()
         h = self._live()
         if not isinstance(y, torch.Tensor) or not y.is_cuda or y.device.index != self.device:
-            raise ValueError("y must be a contiguous int32 CUDA tensor on the table's device")
-        o, out, result = _ola_call(torch, params, y, int(hop), frames, channels, shift, out, y_stride, t0, count, self.device, length)
-        _call("bhw_overlap_add_from_table", "bhw_overlap_add_len_from_table", (h,), params, length,
-              (_stream_ptr(torch, self.device), ctypes.byref(o), ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(out.data_ptr())))
+            raise ValueError("y must be a contiguous int32 or float32 CUDA tensor on the table's device")
+        o, out, result, flags = _ola_call(torch, params, y, int(hop), frames, channels, shift, out, y_stride, t0, count, self.device, length,
+                                          normalize)
+        if y.dtype == torch.float32:
+            B.check(B.lib().bhw_overlap_add_f32_from_table(h, ctypes.byref(params), _window_len(params, length), _stream_ptr(torch, self.device),
+                                                           ctypes.byref(o), flags, ctypes.c_void_p(y.data_ptr()),
+                                                           ctypes.c_void_p(out.data_ptr())))
+        else:
+            _call("bhw_overlap_add_from_table", "bhw_overlap_add_len_from_table", (h,), params, length,
+                  (_stream_ptr(torch, self.device), ctypes.byref(o), ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(out.data_ptr())))
         return result
 
     def describe_overlap_add(self, params, frames, hop, count=None, *, t0=0, channels=1, y_stride=0):

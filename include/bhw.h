@@ -410,6 +410,48 @@ int bhw_overlap_add_len_from_table(bhw_table t, const bhw_params *p, uint64_t le
 int bhw_describe_len(bhw_table t, const bhw_params *p, uint64_t length, uint64_t n0, uint64_t count,
                      const bhw_frames *f, const bhw_ola *o, char *buf, uint64_t len);
 
+/* Float32 frame apply and overlap-add: the STFT front and back ends with the float samples an FFT reads and writes.  Let w[k] be the
+ * int32 coefficient the matching int32 call uses at index k -- bhw_generate_device(p, n0 = 0) for length = 2^phi_width, the phase
+ * map of the *_len calls otherwise -- and `shift` the descriptor's field (0..62).  The float coefficient is
+ *     v[k] = fl32(w[k]) * 2^-shift
+ * fl32: conversion to binary32, round to nearest even (exact for |w| < 2^24).  The scaling is exact: |w| >= 1 gives |v| >= 2^-62,
+ * a normal number.  N below is the window length `length` (1..2^phi_width; 2^phi_width is the power-of-two window).
+ *   - bhw_apply_frames_f32_*: the indexing of bhw_apply_frames_device, one IEEE binary32 multiply rounded to nearest even, subnormals
+ *     kept, inf and NaN as IEEE arithmetic has them:
+ *         d_y[f * y_stride + k * C + c] = fl32(d_x[(f * hop + k) * C + c] * v[k])
+ *   - bhw_overlap_add_f32_*: the indexing and extent of bhw_overlap_add_device.  For each output t in [t0, t0 + count) and c < C
+ *         S = sum over the frames f reaching t, in ASCENDING f, of  (double) d_y[f * y_stride + (t - f * hop) * C + c] * (double) v[t - f * hop]
+ *     accumulated in binary64 from +0.0.  Each product is exact in binary64 (24 x 24 significand bits), so a fused multiply-add and a
+ *     separate multiply and add give the same S.  The summation order is part of the contract: floating-point addition does not
+ *     associate (the int64 sums of the int32 call were exact in any order).
+ *       flags 0:                  d_x[(t - t0) * C + c] = fl32(S)                (binary64 -> binary32, nearest even; empty sum: +0.0)
+ *       flags BHW_OLA_NORMALIZE:  E = sum over the same frames, in the same order, of (double) v[t - f * hop]^2, and
+ *                                 d_x[(t - t0) * C + c] = E > 0 ? fl32(S / E) : +0.0    (S / E a correctly rounded binary64 division)
+ *     The normalised form is what torch.istft computes, save that torch.istft raises where the envelope E is tiny and a kernel
+ *     cannot: the outputs at the edges of the extent, covered only by small edge coefficients of the window, come out amplified.
+ *     The caller picks t0 / count to leave them out (the first and last N - hop outputs for a window whose envelope is flat inside).
+ *   - y_stride, the extents and every limit count float32 elements exactly as the int32 calls count int32 ones.
+ *   - Argument checks come before any HIP call: everything the int32 counterpart checks, flags outside {0, BHW_OLA_NORMALIZE}
+ *     (BHW_ERR_BADARG), length 0 or above 2^phi_width (BHW_ERR_BADARG), the Taylor sources (BHW_ERR_UNSUPPORTED: no per-lane
+ *     coefficient).  The structs are those of the int32 calls; reserved must be 0.
+ *   - The library forms compute the coefficients with the direct CORDIC chains: no allocation, no scratch, capturable with no
+ *     bhw_prepare_device.  The from-table forms keep the from-table contract: no allocation, no synchronisation, always capturable,
+ *     the same key match.  There is no per-frame route (no float fused apply exists; bhw_apply_device stays int32).
+ *   - bhw_describe_f32: one line naming the route, the plan (G, or Q and the lane layout), the kernel and whether the overlap-add
+ *     normalises.  Exactly one of f (frames call; flags must be 0) and o (overlap-add call).  t may be NULL (the library call).
+ *     Host arithmetic only. */
+#define BHW_OLA_NORMALIZE 1u
+int bhw_apply_frames_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream,
+                                const bhw_frames *f, const float *d_x, float *d_y);
+int bhw_apply_frames_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream,
+                                    const bhw_frames *f, const float *d_x, float *d_y);
+int bhw_overlap_add_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream,
+                               const bhw_ola *o, uint32_t flags, const float *d_y, float *d_x);
+int bhw_overlap_add_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream,
+                                   const bhw_ola *o, uint32_t flags, const float *d_y, float *d_x);
+int bhw_describe_f32(bhw_table t, const bhw_params *p, uint64_t length, const bhw_frames *f, const bhw_ola *o, uint32_t flags,
+                     char *buf, uint64_t len);
+
 /* Threading: every entry point may be called from any host thread.  Calls that use the library-owned scratch of one
  * (device, stream) are serialised against each other for the duration of their launches (the table is rebuilt per call);
  * callers that pass their own bhw_exec.workspace must not share one workspace between concurrent calls.  The calling

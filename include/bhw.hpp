@@ -11,6 +11,8 @@
 //   bhw::overlap_add()       the weighted overlap-add of frames back into one signal in one launch (bhw_overlap_add_device)
 //   bhw::generate_len(), bhw::apply_frames_len(), bhw::overlap_add_len()
 //                            the same for a window of any length L <= 2^phi_width (bhw_generate_len_device ...)
+//   bhw::apply_frames_f32(), bhw::overlap_add_f32()
+//                            float32 samples, with the envelope division of the overlap-add (bhw_apply_frames_f32_device ...)
 // Same names, argument meaning and error behaviour (unknown win_type -> zeros, like win_empty,
 // hls/windows/win_function.cpp:159-165,417-419).  All arithmetic runs in the HIP kernels behind the ABI.
 #pragma once
@@ -225,6 +227,27 @@ inline std::string describe_len(const bhw_params &p, uint64_t length, uint64_t n
     return buf;
 }
 
+// Float32 frame apply and overlap-add over the window of length L (2^phi_width: the power-of-two window): v[k] = fl32(w[k]) * 2^-shift
+// applied to float32 samples; flags BHW_OLA_NORMALIZE divides each output by the window envelope (bhw.h gives the arithmetic), and
+// the one-line description (exactly one of f and o).
+inline void apply_frames_f32(const bhw_params &p, uint64_t length, const bhw_frames &f, const float *d_x, float *d_y, int device = 0,
+                             void *hip_stream = nullptr)
+{
+    check(bhw_apply_frames_f32_device(&p, length, device, hip_stream, &f, d_x, d_y));
+}
+inline void overlap_add_f32(const bhw_params &p, uint64_t length, const bhw_ola &o, uint32_t flags, const float *d_y, float *d_x,
+                            int device = 0, void *hip_stream = nullptr)
+{
+    check(bhw_overlap_add_f32_device(&p, length, device, hip_stream, &o, flags, d_y, d_x));
+}
+inline std::string describe_f32(const bhw_params &p, uint64_t length, const bhw_frames *f, const bhw_ola *o, uint32_t flags = 0,
+                                bhw_table t = nullptr)
+{
+    char buf[512];
+    check(bhw_describe_f32(t, &p, length, f, o, flags, buf, sizeof buf));
+    return buf;
+}
+
 // The CORDIC table of a configuration's generics, built once on `device` (bhw_table_create) and freed by the destructor
 // (bhw_table_destroy: it synchronises the device first).  Move-only.  Every call takes its weights -- the AA ports -- from its own
 // bhw_params, which must match the table's generics; device pointers and streams as in the C calls.
@@ -303,6 +326,20 @@ public:
                              const bhw_ola *o = nullptr) const
     {
         return bhw::describe_len(p, length, n0, count, f, o, t_);
+    }
+    // float32 samples from this table (bhw_apply_frames_f32_from_table ...)
+    void apply_frames_f32(const bhw_params &p, uint64_t length, void *hip_stream, const bhw_frames &f, const float *d_x, float *d_y) const
+    {
+        check(bhw_apply_frames_f32_from_table(t_, &p, length, hip_stream, &f, d_x, d_y));
+    }
+    void overlap_add_f32(const bhw_params &p, uint64_t length, void *hip_stream, const bhw_ola &o, uint32_t flags, const float *d_y,
+                         float *d_x) const
+    {
+        check(bhw_overlap_add_f32_from_table(t_, &p, length, hip_stream, &o, flags, d_y, d_x));
+    }
+    std::string describe_f32(const bhw_params &p, uint64_t length, const bhw_frames *f, const bhw_ola *o, uint32_t flags = 0) const
+    {
+        return bhw::describe_f32(p, length, f, o, flags, t_);
     }
     void generate_part(const bhw_params &p, void *hip_stream, uint32_t part, uint32_t n_parts, int32_t *d_window) const
     {
