@@ -12,6 +12,7 @@ ALGO_AUTO, ALGO_DIRECT, ALGO_TABLE, ALGO_FUSED = 0, 1, 2, 3
 TABLE_BEST, TABLE_PLAIN, TABLE_DELTA16, TABLE_RESIDUAL, TABLE_NIBBLE, TABLE_NIBBLE_ESC = 0, 1, 2, 3, 4, 5
 ABI_VERSION = 4
 OLA_NORMALIZE = 1
+PAD_CONSTANT, PAD_REFLECT = 0, 1        # bhw_stft.pad_mode
 
 # every symbol include/bhw.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = (
@@ -29,6 +30,8 @@ ABI_SYMBOLS = (
     "bhw_overlap_add_len_device", "bhw_overlap_add_len_from_table", "bhw_describe_len",
     "bhw_apply_frames_f32_device", "bhw_apply_frames_f32_from_table", "bhw_overlap_add_f32_device", "bhw_overlap_add_f32_from_table",
     "bhw_describe_f32",
+    "bhw_stft_frames_f32_device", "bhw_stft_frames_f32_from_table", "bhw_istft_ola_f32_device", "bhw_istft_ola_f32_from_table",
+    "bhw_describe_stft",
 )
 
 
@@ -91,6 +94,24 @@ def make_ola(frames, hop, count, *, t0=0, channels=1, shift=0, y_stride=0):
     o.channels, o.frames, o.hop, o.y_stride = int(channels), int(frames), int(hop), int(y_stride)
     o.t0, o.count, o.shift = int(t0), int(count), int(shift)
     return o
+
+
+class BhwStft(ctypes.Structure):
+    """struct bhw_stft of include/bhw.h (the batched, centred STFT framing and overlap-add)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("channels", ctypes.c_uint32), ("batch", ctypes.c_uint64),
+                ("samples", ctypes.c_uint64), ("x_stride", ctypes.c_uint64), ("frames", ctypes.c_uint64), ("hop", ctypes.c_uint64),
+                ("n_fft", ctypes.c_uint64), ("col0", ctypes.c_uint64), ("pad", ctypes.c_uint64), ("y_stride", ctypes.c_uint64),
+                ("y_batch_stride", ctypes.c_uint64), ("pad_mode", ctypes.c_uint32), ("shift", ctypes.c_uint32)]
+
+
+def make_stft(batch, samples, frames, hop, n_fft, *, col0=0, pad=0, pad_mode=0, channels=1, shift=0, x_stride=0, y_stride=0,
+              y_batch_stride=0):
+    s = BhwStft()
+    s.struct_size = ctypes.sizeof(BhwStft)
+    s.channels, s.batch, s.samples, s.frames, s.hop, s.n_fft = int(channels), int(batch), int(samples), int(frames), int(hop), int(n_fft)
+    s.col0, s.pad, s.pad_mode, s.shift = int(col0), int(pad), int(pad_mode), int(shift)
+    s.x_stride, s.y_stride, s.y_batch_stride = int(x_stride), int(y_stride), int(y_batch_stride)
+    return s
 
 
 _lib = None
@@ -184,6 +205,12 @@ def lib():
     L.bhw_overlap_add_f32_device.argtypes = [P, u64, ci, vp, O, u32, f32p, f32p]
     L.bhw_overlap_add_f32_from_table.argtypes = [T, P, u64, vp, O, u32, f32p, f32p]
     L.bhw_describe_f32.argtypes = [T, P, u64, F, O, u32, ctypes.c_char_p, u64]
+    S = ctypes.POINTER(BhwStft)
+    L.bhw_stft_frames_f32_device.argtypes = [P, u64, ci, vp, S, f32p, f32p]
+    L.bhw_stft_frames_f32_from_table.argtypes = [T, P, u64, vp, S, f32p, f32p]
+    L.bhw_istft_ola_f32_device.argtypes = [P, u64, ci, vp, S, u32, f32p, f32p]
+    L.bhw_istft_ola_f32_from_table.argtypes = [T, P, u64, vp, S, u32, f32p, f32p]
+    L.bhw_describe_stft.argtypes = [T, P, u64, S, ci, u32, ctypes.c_char_p, u64]
     PA = ctypes.POINTER(BhwAtan2Params)
     L.bhw_atan2_device.argtypes = [PA, ci, vp, u64, i32p, i32p, i32p]
     L.bhw_atan2_to_host.argtypes = [PA, ci, u64, i32p, i32p, i32p]
@@ -263,6 +290,16 @@ def describe_f32(params, length=None, *, frames=None, ola=None, normalize=False,
     check(lib().bhw_describe_f32(table, ctypes.byref(params), length,
                                  ctypes.byref(frames) if frames is not None else None, ctypes.byref(ola) if ola is not None else None,
                                  OLA_NORMALIZE if normalize else 0, buf, 512))
+    return buf.value.decode()
+
+
+def describe_stft(params, length, stft, *, inverse=False, normalize=False, table=None):
+    """One line: the route, the plan and the kernel of a batched STFT frames call (inverse False) or overlap-add (inverse True) over
+    the window of `length`, for the descriptor `stft` (a BhwStft, make_stft) (bhw_describe_stft).  `table` is a resident table handle
+    or None for the library call.  Host arithmetic only."""
+    buf = ctypes.create_string_buffer(640)
+    check(lib().bhw_describe_stft(table, ctypes.byref(params), int(length), ctypes.byref(stft), 1 if inverse else 0,
+                                  OLA_NORMALIZE if normalize else 0, buf, 640))
     return buf.value.decode()
 
 

@@ -1092,6 +1092,42 @@ int ola_f32_run(bhw_table t, const bhw_params *p, uint64_t length, int device, v
                                                          const BhwLenPhase *lp) { return bhwk_ola_f32(l, c, w, pl, o, norm, d_y, d_x, tab, lp); });
 }
 
+// A batched STFT frames call (t NULL: the direct CORDIC chains): the checks, then the frames kernel at the angles of the length-L
+// phase map, for every L.
+int stft_frames_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *s, const float *d_x,
+                    float *d_y)
+{
+    int rc = bhwp_f32_checks(p, length, 0);
+    if (!rc && t) rc = table_call_checks(t, p);
+    if (!rc) rc = bhwp_stft_checks(p, length, s, false, 0, d_x, d_y);
+    if (rc || !s->frames) return rc;
+    const BhwStftPlan pl = bhwp_stft_plan(p, length, s, t != nullptr);
+    const char *what = t ? "stft frames launch (resident table)" : "stft frames launch";
+    return run_source(t, p, length, device, stream, what, [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *tab,
+                                                              const BhwLenPhase *lp) { return bhwk_stft_frames_f32(l, c, w, pl, s, d_x, d_y, tab, *lp); });
+}
+
+// A batched STFT overlap-add: the float32 overlap-add of every signal in one launch (bhwp_stft_ola maps the descriptor onto it; the
+// power-of-two kernels at L = 2^phi_width, the any-length ones otherwise).
+int istft_ola_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *s, uint32_t flags,
+                  const float *d_y, float *d_x)
+{
+    int rc = bhwp_f32_checks(p, length, flags);
+    if (!rc && t) rc = table_call_checks(t, p);
+    if (!rc) rc = bhwp_stft_checks(p, length, s, true, flags, d_x, d_y);
+    if (rc || !s->samples) return rc;
+    bhw_ola o;
+    BhwOlaBatch bt;
+    bhwp_stft_ola(s, o, bt);
+    const uint64_t L = bhwp_len_kernels(p, length, false) ? length : 0;
+    const bool norm = (flags & BHW_OLA_NORMALIZE) != 0;
+    const BhwOlaPlan pl = bhwp_ola_plan(p, &o, t != nullptr, 0, 0, L, norm ? kOlaQMaxNorm : kOlaQMax, bt.batch);
+    const float *rows = d_y + s->col0 * s->channels;             // the window columns of each row
+    const char *what = t ? "istft overlap-add launch (resident table)" : "istft overlap-add launch";
+    return run_source(t, p, L, device, stream, what, [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *tab,
+                                                         const BhwLenPhase *lp) { return bhwk_ola_f32(l, c, w, pl, &o, norm, rows, d_x, tab, lp, bt); });
+}
+
 } // namespace
 
 extern "C" {
@@ -1196,6 +1232,45 @@ int bhw_describe_f32(bhw_table t, const bhw_params *p, uint64_t length, const bh
     if (!rc && f) rc = bhwp_frames_checks(p, f, nullptr, nullptr, false, length);
     if (!rc && o) rc = bhwp_ola_checks(p, o, nullptr, nullptr, false, length);
     return rc ? rc : bhwp_describe_f32(p, t ? &t->c : nullptr, length, g_len_force, f, o, flags, buf, len);
+}
+
+// ---- batched, centred STFT framing and overlap-add (include/bhw.h: bhw_stft_frames_f32_device ...) ------------------------------------
+
+int bhw_stft_frames_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, const float *d_x,
+                               float *d_y)
+{
+    return stft_frames_run(nullptr, p, length, device, hip_stream, s, d_x, d_y);
+}
+
+int bhw_stft_frames_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, const float *d_x,
+                                   float *d_y)
+{
+    const int rc = bhwp_f32_checks(p, length, 0);
+    if (rc) return rc;
+    return t ? stft_frames_run(t, p, length, t->device, hip_stream, s, d_x, d_y) : fail(BHW_ERR_BADARG, "table is NULL");
+}
+
+int bhw_istft_ola_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                             const float *d_y, float *d_x)
+{
+    return istft_ola_run(nullptr, p, length, device, hip_stream, s, flags, d_y, d_x);
+}
+
+int bhw_istft_ola_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                 const float *d_y, float *d_x)
+{
+    const int rc = bhwp_f32_checks(p, length, flags);
+    if (rc) return rc;
+    return t ? istft_ola_run(t, p, length, t->device, hip_stream, s, flags, d_y, d_x) : fail(BHW_ERR_BADARG, "table is NULL");
+}
+
+int bhw_describe_stft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, int inverse, uint32_t flags, char *buf,
+                      uint64_t len)
+{
+    int rc = bhwp_f32_checks(p, length, flags);
+    if (!rc && t) rc = table_call_checks(t, p);
+    if (!rc) rc = bhwp_stft_checks(p, length, s, inverse != 0, flags, nullptr, nullptr, false);
+    return rc ? rc : bhwp_describe_stft(p, t ? &t->c : nullptr, length, s, inverse != 0, flags, buf, len);
 }
 
 // Development hook (not part of the ABI in include/bhw.h): on != 0 sends the *_len calls at L = 2^phi_width to the any-length kernels

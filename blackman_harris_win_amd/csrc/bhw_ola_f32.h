@@ -14,20 +14,26 @@
 //     at +0.0 is never -0.0 under round-to-nearest.
 //   - The trip count is the wave's largest, with the other lanes masked, so every lane reaches range_coeff together.
 //   - y and x keep the nontemporal emit() policy; two channels move as one 8-byte access when both bases and the stride allow it.
+//   - A batch of signals (bhw_istft_ola_f32_*) runs in grid z: each workgroup moves y and x once to its signal's rows and outputs
+//     (OlaArgsF32's strides); the lane structure does not see the batch, and the one-signal calls run with grid z = 1.
 //   - NORM is a template argument, not a run-time branch: the Q extra accumulators of E belong only to the instances that need them,
 //     which are compiled for Q <= kOlaQMaxNorm rows (the planner's bound for them) to keep their registers near the plain ones.
 #pragma once
 #include "bhw_ola.h"
 
 int bhwk_ola_f32_norm(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwOlaPlan &pl, const bhw_ola *o,
-                      const float *d_y, float *d_x, const int32_t *d_table, const BhwLenPhase *lp);
+                      const float *d_y, float *d_x, const int32_t *d_table, const BhwLenPhase *lp, const BhwOlaBatch &bt);
 
 namespace {
 
 typedef float ola_v2f __attribute__((ext_vector_type(2)));    // one I/Q pair (the nontemporal builtins take native vectors only)
 
-// the float32 form of the overlap-add arguments (bhw_ola.h)
-struct OlaArgsF32 : OlaIo<float> {};
+// the float32 form of the overlap-add arguments (bhw_ola.h), with the signals of a batch: the workgroups of grid z = b read the rows
+// of signal b from y + b * y_bstride and write its outputs to x + b * x_bstride (a batch beyond kOlaMaxGridZ signals takes several
+// launches)
+struct OlaArgsF32 : OlaIo<float> {
+    uint64_t y_bstride, x_bstride;
+};
 
 __device__ __forceinline__ float ola_out(double s, double e)
 {
@@ -44,6 +50,8 @@ __device__ __forceinline__ void ola_f32_loop(const OlaArgsF32 &a, Coeff coeff)
     const uint64_t r = ln.r;
     const int64_t frames = (int64_t)a.frames;
     constexpr uint32_t QM = NORM ? kOlaQMaxNorm : kOlaQMax;       // rows this instance holds (the plan's Q is at most that)
+    const float *ys = a.y + (uint64_t)blockIdx.z * a.y_bstride;     // signal blockIdx.z of the batch
+    float *xs = a.x + (uint64_t)blockIdx.z * a.x_bstride;
     for (uint64_t by = blockIdx.y; by < a.row_blocks; by += gridDim.y) {
         const OlaRows rw = ola_rows(a, ln, frames, by, ty);
         const uint64_t u0 = rw.u0;
@@ -75,14 +83,14 @@ __device__ __forceinline__ void ola_f32_loop(const OlaArgsF32 &a, Coeff coeff)
                 // masked afterwards: a load under the mask would take the conversion into its branch and wait for each load alone
                 const uint64_t yi = ok ? (uint64_t)f * a.y_stride + (uint64_t)k * C : 0;
                 if constexpr (C == 1) {
-                    e[i][0] = __builtin_nontemporal_load(a.y + yi);
+                    e[i][0] = __builtin_nontemporal_load(ys + yi);
                 } else if constexpr (VEC) {
-                    const ola_v2f pr = __builtin_nontemporal_load((const ola_v2f *)(a.y + yi));
+                    const ola_v2f pr = __builtin_nontemporal_load((const ola_v2f *)(ys + yi));
                     e[i][0] = pr.x;
                     e[i][1] = pr.y;
                 } else {
-                    e[i][0] = __builtin_nontemporal_load(a.y + yi);
-                    e[i][1] = __builtin_nontemporal_load(a.y + yi + 1);
+                    e[i][0] = __builtin_nontemporal_load(ys + yi);
+                    e[i][1] = __builtin_nontemporal_load(ys + yi + 1);
                 }
             }
 #pragma unroll
@@ -99,7 +107,7 @@ __device__ __forceinline__ void ola_f32_loop(const OlaArgsF32 &a, Coeff coeff)
 #pragma unroll
         for (uint32_t i = 0; i < QM; ++i) {
             if (i < nrow) {
-                float *xp = a.x + (u0 + (uint64_t)i * a.hop) * C;
+                float *xp = xs + (u0 + (uint64_t)i * a.hop) * C;
                 float o[C];
 #pragma unroll
                 for (int c = 0; c < C; ++c) {
@@ -172,30 +180,38 @@ __global__ __launch_bounds__(kOlaBlock) void k_ola_f32_table_len(BhwCordicCfg cf
 // The launch of one NORM half (each translation unit instantiates one).
 template <bool NORM>
 int ola_f32_launch(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinCfg &w, const BhwOlaPlan &pl, const bhw_ola *o,
-                   const float *d_y, float *d_x, const int32_t *d_table, const BhwLenPhase *lp)
+                   const float *d_y, float *d_x, const int32_t *d_table, const BhwLenPhase *lp, const BhwOlaBatch &bt)
 {
-    if (!o->count) return 0;
+    if (!o->count || !bt.batch) return 0;
     hipStream_t st = (hipStream_t)l.stream;
     OlaArgsF32 a;
     ola_args(a, pl, o, d_y, d_x);
-    const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y), block(kOlaBlock);
-    if (!d_table) {
-        with_int_or_last<0, 1, 2>(a.io, [&](auto IO) {
-            with_int_or_last<2, 1, 0>(direct_form(c_in), [&](auto D) {
-                launch_phase(k_ola_f32_direct_len<D, IO, NORM>, k_ola_f32_direct<D, IO, NORM>, lp, grid, block, st, c_in, w, a);
+    a.y_bstride = bt.y_bstride;
+    a.x_bstride = bt.x_bstride;
+    if (a.io == 2 && bt.batch > 1 && (bt.y_bstride % 2 || bt.x_bstride % 2)) a.io = 1;    // every signal start 8-byte aligned
+    const BhwCordicCfg c = d_table ? table_layout(c_in) : c_in;
+    int fmt = 0, nt = 0, mode = 0;
+    if (d_table && !bhwp_range_form(c, w, &fmt, &nt, &mode)) return (int)hipErrorInvalidValue;
+    const void *tab = (const void *)d_table;
+    for (uint64_t b0 = 0; b0 < bt.batch; b0 += kOlaMaxGridZ) {
+        const uint64_t nb = bt.batch - b0 < kOlaMaxGridZ ? bt.batch - b0 : kOlaMaxGridZ;
+        a.y = d_y + b0 * bt.y_bstride;
+        a.x = d_x + b0 * bt.x_bstride;
+        const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y, (unsigned)nb), block(kOlaBlock);
+        if (!d_table) {
+            with_int_or_last<0, 1, 2>(a.io, [&](auto IO) {
+                with_int_or_last<2, 1, 0>(direct_form(c_in), [&](auto D) {
+                    launch_phase(k_ola_f32_direct_len<D, IO, NORM>, k_ola_f32_direct<D, IO, NORM>, lp, grid, block, st, c_in, w, a);
+                });
+            });
+            continue;
+        }
+        with_range_form(fmt, nt, mode, [&](auto F, auto NT, auto M) {
+            with_int_or_last<0, 1, 2>(a.io, [&](auto IO) {
+                launch_phase(k_ola_f32_table_len<F, NT, M, IO, NORM>, k_ola_f32_table<F, NT, M, IO, NORM>, lp, grid, block, st, c, w, tab, a);
             });
         });
-        return finish(hipSuccess);
     }
-    const BhwCordicCfg c = table_layout(c_in);
-    int fmt, nt, mode;
-    if (!bhwp_range_form(c, w, &fmt, &nt, &mode)) return (int)hipErrorInvalidValue;
-    const void *tab = (const void *)d_table;
-    with_range_form(fmt, nt, mode, [&](auto F, auto NT, auto M) {
-        with_int_or_last<0, 1, 2>(a.io, [&](auto IO) {
-            launch_phase(k_ola_f32_table_len<F, NT, M, IO, NORM>, k_ola_f32_table<F, NT, M, IO, NORM>, lp, grid, block, st, c, w, tab, a);
-        });
-    });
     return finish(hipSuccess);
 }
 

@@ -3,7 +3,7 @@
 #include "bhw_ola_f32.h"
 
 int bhwk_ola_f32_norm(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwOlaPlan &pl, const bhw_ola *o,
-                      const float *d_y, float *d_x, const int32_t *d_table, const BhwLenPhase *lp)
+                      const float *d_y, float *d_x, const int32_t *d_table, const BhwLenPhase *lp, const BhwOlaBatch &bt)
 {
-    return ola_f32_launch<true>(l, c, w, pl, o, d_y, d_x, d_table, lp);
+    return ola_f32_launch<true>(l, c, w, pl, o, d_y, d_x, d_table, lp, bt);
 }

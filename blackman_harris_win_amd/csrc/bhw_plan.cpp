@@ -900,7 +900,7 @@ int bhwp_ola_checks(const bhw_params *p, const bhw_ola *o, const void *d_y, cons
 }
 
 BhwOlaPlan bhwp_ola_plan(const bhw_params *p, const bhw_ola *o, bool from_table, uint32_t force_q, uint32_t force_rx, uint64_t length,
-                         uint32_t q_max)
+                         uint32_t q_max, uint64_t batch)
 {
     BhwOlaPlan pl{};
     const uint64_t N = length ? length : 1ull << p->phi_width;
@@ -923,7 +923,8 @@ BhwOlaPlan bhwp_ola_plan(const bhw_params *p, const bhw_ola *o, bool from_table,
     // Q: as many workgroups as kOlaTargetWg asks for (a wide residue range fills the chip alone), and at least the frames that reach
     // one output, so that a lane computes no more coefficients than it writes outputs
     const uint64_t row_groups = (pl.rows + pl.fy - 1) / pl.fy;
-    const uint64_t gy_target = pl.grid_x >= kOlaOnePassGx ? 1 : (kOlaTargetWg + pl.grid_x - 1) / pl.grid_x;
+    const uint64_t gx = pl.grid_x * batch;                         // the signals of a batch share the target
+    const uint64_t gy_target = gx >= kOlaOnePassGx ? 1 : (kOlaTargetWg + gx - 1) / gx;
     uint64_t Q = (row_groups + gy_target - 1) / gy_target;
     if (Q < pl.jmax) Q = pl.jmax;
     if (Q > row_groups) Q = row_groups;
@@ -1026,6 +1027,158 @@ int bhwp_describe_f32(const bhw_params *p, const BhwCordicCfg *ct, uint64_t leng
                                                  (flags & BHW_OLA_NORMALIZE) ? kOlaQMaxNorm : kOlaQMax), any, inner, sizeof inner,
                             "k_ola_f32_direct", "k_ola_f32_table");
     snprintf(buf, len, "f32 overlap-add %s (%s), %s: %s", route, win, norm, inner);
+    return BHW_OK;
+}
+
+// ---- batched, centred STFT framing and overlap-add ---------------------------------------------------------------------------------
+
+int bhwp_stft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, bool inverse, uint32_t flags, const void *d_x,
+                     const void *d_y, bool pointers)
+{
+    int rc = bhwp_f32_checks(p, length, flags);
+    if (rc) return rc;
+    if (!inverse && flags) return bhwp_fail(BHW_ERR_BADARG, "flags 0x%x: the frames call takes none", flags);
+    if (!s) return bhwp_fail(BHW_ERR_BADARG, "stft descriptor is NULL");
+    if (s->struct_size != sizeof(bhw_stft)) return bhwp_fail(BHW_ERR_BADARG, "bhw_stft.struct_size %u != %zu", s->struct_size, sizeof(bhw_stft));
+    if (s->channels != 1 && s->channels != 2) return bhwp_fail(BHW_ERR_BADARG, "channels %u (1 or 2)", s->channels);
+    if (s->batch == 0) return bhwp_fail(BHW_ERR_BADARG, "batch is 0");
+    if (s->hop == 0) return bhwp_fail(BHW_ERR_BADARG, "hop is 0");
+    if (s->n_fft == 0 || s->n_fft > (1ull << 31)) return bhwp_fail(BHW_ERR_BADARG, "n_fft %llu outside 1..2^31", (unsigned long long)s->n_fft);
+    if (s->shift > 62) return bhwp_fail(BHW_ERR_BADARG, "shift %u > 62", s->shift);
+    if (s->col0 > s->n_fft || length > s->n_fft - s->col0)
+        return bhwp_fail(BHW_ERR_BADARG, "col0 + L = %llu + %llu > n_fft = %llu", (unsigned long long)s->col0, (unsigned long long)length,
+                         (unsigned long long)s->n_fft);
+    if (s->pad > (1ull << 40)) return bhwp_fail(BHW_ERR_BADARG, "pad %llu above 2^40", (unsigned long long)s->pad);
+    if (inverse ? s->pad_mode != 0 : (s->pad_mode != BHW_PAD_CONSTANT && s->pad_mode != BHW_PAD_REFLECT))
+        return bhwp_fail(BHW_ERR_BADARG, inverse ? "pad_mode %u: the overlap-add takes 0" : "pad_mode %u (BHW_PAD_CONSTANT or BHW_PAD_REFLECT)",
+                         s->pad_mode);
+    const uint64_t T = s->samples, C = s->channels, F = s->frames, NC = s->n_fft * C;
+    if (inverse) {
+        if (!T) return BHW_OK;
+        if (!F) return bhwp_fail(BHW_ERR_BADARG, "frames is 0 with samples %llu > 0", (unsigned long long)T);
+        if (s->pad < s->col0)
+            return bhwp_fail(BHW_ERR_BADARG, "pad %llu < col0 %llu: the first outputs have no window under them", (unsigned long long)s->pad,
+                             (unsigned long long)s->col0);
+        if (T > (1ull << 34)) return bhwp_fail(BHW_ERR_BADARG, "samples %llu above 2^34 per signal", (unsigned long long)T);
+    } else {
+        if (!F) return BHW_OK;
+        if (!T) return bhwp_fail(BHW_ERR_BADARG, "samples is 0 with frames %llu > 0", (unsigned long long)F);
+        // every frame inside the padded signal; hop is a free 64-bit value, so the products are taken in 128 bits
+        if ((unsigned __int128)(F - 1) * s->hop + s->n_fft > (unsigned __int128)T + 2 * s->pad)
+            return bhwp_fail(BHW_ERR_BADARG, "(frames - 1) * hop + n_fft > samples + 2 * pad: frame %llu leaves the padded signal",
+                             (unsigned long long)(F - 1));
+        if (s->pad_mode == BHW_PAD_REFLECT && s->pad > T - 1)
+            return bhwp_fail(BHW_ERR_BADARG, "reflect padding needs pad %llu <= samples - 1 = %llu", (unsigned long long)s->pad,
+                             (unsigned long long)(T - 1));
+    }
+    if ((unsigned __int128)s->batch * F * s->n_fft > (1ull << 34))
+        return bhwp_fail(BHW_ERR_BADARG, "batch * frames * n_fft above 2^34 per call");
+    if ((unsigned __int128)T * C > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "samples * channels beyond 2^60 elements");
+    if (s->x_stride && s->x_stride < T * C)
+        return bhwp_fail(BHW_ERR_BADARG, "x_stride %llu < samples * channels = %llu: signals overlap", (unsigned long long)s->x_stride,
+                         (unsigned long long)(T * C));
+    if (s->y_stride && s->y_stride < NC)
+        return bhwp_fail(BHW_ERR_BADARG, "y_stride %llu < n_fft * channels = %llu: rows overlap", (unsigned long long)s->y_stride,
+                         (unsigned long long)NC);
+    const uint64_t ys = s->y_stride ? s->y_stride : NC;
+    const unsigned __int128 ysig = (unsigned __int128)(F - 1) * ys + NC;           // the rows of one signal
+    if (ysig > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "y extent beyond 2^60 elements");
+    if (s->y_batch_stride && s->y_batch_stride < (uint64_t)ysig)
+        return bhwp_fail(BHW_ERR_BADARG, "y_batch_stride %llu < (frames - 1) * y_stride + n_fft * channels = %llu: signals overlap",
+                         (unsigned long long)s->y_batch_stride, (unsigned long long)ysig);
+    if (!pointers) return BHW_OK;
+    if (!d_x || !d_y) return bhwp_fail(BHW_ERR_BADARG, "d_x / d_y is NULL");
+    const uint64_t xs = s->x_stride ? s->x_stride : T * C, ybs = s->y_batch_stride ? s->y_batch_stride : F * ys;
+    const unsigned __int128 xe = (unsigned __int128)(s->batch - 1) * xs + T * C, ye = (unsigned __int128)(s->batch - 1) * ybs + ysig;
+    if (xe > (1ull << 60) || ye > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "x or y extent beyond 2^60 elements");
+    const uint64_t xa = (uint64_t)(uintptr_t)d_x, ya = (uint64_t)(uintptr_t)d_y, xb = (uint64_t)xe * 4u, yb = (uint64_t)ye * 4u;
+    if (xa > UINT64_MAX - xb || ya > UINT64_MAX - yb) return bhwp_fail(BHW_ERR_BADARG, "x or y range wraps the address space");
+    if (xa < ya + yb && ya < xa + xb) return bhwp_fail(BHW_ERR_BADARG, "d_x and d_y overlap");
+    return BHW_OK;
+}
+
+BhwStftPlan bhwp_stft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, bool from_table)
+{
+    (void)p;
+    BhwStftPlan pl{};
+    const uint64_t C = s->channels;
+    pl.route = from_table ? BHWP_FRAMES_TABLE : BHWP_FRAMES_DIRECT;
+    pl.len = length;
+    pl.x_stride = s->x_stride ? s->x_stride : s->samples * C;
+    pl.y_stride = s->y_stride ? s->y_stride : s->n_fft * C;
+    pl.y_bstride = s->y_batch_stride ? s->y_batch_stride : s->frames * pl.y_stride;
+    pl.kx = 1;
+    while (pl.kx < kFramesBlock && pl.kx < s->n_fft) pl.kx *= 2;
+    pl.fy = kFramesBlock / pl.kx;
+    pl.grid_x = (s->n_fft + pl.kx - 1) / pl.kx;
+    pl.rows = s->batch * s->frames;
+    if (!pl.rows) return pl;
+    pl.step_b = pl.fy / s->frames;
+    pl.step_f = pl.fy % s->frames;
+    // as bhwp_frames_plan, over the row pool of the whole batch: a lane applies its coefficient to G rows of any signals
+    const uint64_t groups = (pl.rows + pl.fy - 1) / pl.fy;
+    const uint64_t gy_target = pl.grid_x >= kFramesOnePassGx ? 1 : (kFramesTargetWg + pl.grid_x - 1) / pl.grid_x;
+    const uint64_t G = (groups + gy_target - 1) / gy_target;
+    pl.group = G < 1 ? 1 : G;
+    pl.row_blocks = (groups + pl.group - 1) / pl.group;
+    pl.grid_y = pl.row_blocks < kFramesMaxGridY ? pl.row_blocks : kFramesMaxGridY;
+    return pl;
+}
+
+void bhwp_stft_ola(const bhw_stft *s, bhw_ola &o, BhwOlaBatch &bt)
+{
+    memset(&o, 0, sizeof o);
+    o.struct_size = sizeof o;
+    o.channels = s->channels;
+    o.frames = s->frames;
+    o.hop = s->hop;
+    o.y_stride = s->y_stride ? s->y_stride : s->n_fft * s->channels;
+    o.t0 = s->pad - s->col0;                                       // output t of the signal is window-start time t + pad - col0
+    o.count = s->samples;
+    o.shift = s->shift;
+    bt.batch = s->batch;
+    bt.y_bstride = s->y_batch_stride ? s->y_batch_stride : s->frames * o.y_stride;
+    bt.x_bstride = s->x_stride ? s->x_stride : s->samples * s->channels;
+}
+
+int bhwp_describe_stft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, bool inverse, uint32_t flags,
+                       char *buf, uint64_t len)
+{
+    if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
+    const char *route = ct ? "table" : "direct";
+    char kern[64];
+    const char *pad = s->pad_mode == BHW_PAD_REFLECT ? "reflect" : "constant";
+    if (!inverse) {
+        if (!s->frames) {
+            snprintf(buf, len, "stft frames %s (L = %llu): nothing (frames 0)", route, (unsigned long long)length);
+            return BHW_OK;
+        }
+        const BhwStftPlan pl = bhwp_stft_plan(p, length, s, ct != nullptr);
+        kernel_name(p, ct, "k_stft_frames_direct", "k_stft_frames_table", false, kern, sizeof kern);
+        snprintf(buf, len, "stft frames %s (L = %llu, n_fft %llu, col0 %llu, pad %llu %s): %s, %u channel%s, %llu signals x %llu frames = "
+                 "%llu rows, G = %llu rows per lane, grid %llu x %llu x %u lanes (%u along the row)", route, (unsigned long long)length,
+                 (unsigned long long)s->n_fft, (unsigned long long)s->col0, (unsigned long long)s->pad, pad, kern, s->channels,
+                 s->channels == 2 ? "s" : "", (unsigned long long)s->batch, (unsigned long long)s->frames, (unsigned long long)pl.rows,
+                 (unsigned long long)pl.group, (unsigned long long)pl.grid_x, (unsigned long long)pl.grid_y, kFramesBlock, pl.kx);
+        return BHW_OK;
+    }
+    const char *norm = (flags & BHW_OLA_NORMALIZE) ? "normalised by the window envelope" : "not normalised";
+    if (!s->samples) {
+        snprintf(buf, len, "istft overlap-add %s (L = %llu), %s: nothing (samples 0)", route, (unsigned long long)length, norm);
+        return BHW_OK;
+    }
+    bhw_ola o;
+    BhwOlaBatch bt;
+    bhwp_stft_ola(s, o, bt);
+    const bool nm = (flags & BHW_OLA_NORMALIZE) != 0;
+    const bool any = bhwp_len_kernels(p, length, false);           // the overlap-add takes the power-of-two kernels at L = 2^phi_width
+    const BhwOlaPlan pl = bhwp_ola_plan(p, &o, ct != nullptr, 0, 0, any ? length : 0, nm ? kOlaQMaxNorm : kOlaQMax, bt.batch);
+    char inner[384];
+    ola_line("", p, ct, &o, pl, any, inner, sizeof inner, "k_ola_f32_direct", "k_ola_f32_table");
+    const uint64_t gz = bt.batch < kOlaMaxGridZ ? bt.batch : kOlaMaxGridZ;
+    snprintf(buf, len, "istft overlap-add %s (L = %llu, n_fft %llu, col0 %llu, pad %llu: t0 = %llu), %s, %llu signals (grid z %llu): %s", route,
+             (unsigned long long)length, (unsigned long long)s->n_fft, (unsigned long long)s->col0, (unsigned long long)s->pad,
+             (unsigned long long)o.t0, norm, (unsigned long long)bt.batch, (unsigned long long)gz, inner);
     return BHW_OK;
 }
 

@@ -237,8 +237,9 @@ int  bhwp_ola_checks(const bhw_params *p, const bhw_ola *o, const void *d_y, con
 // at a power-of-two L it is the plan of length 0.
 // q_max: the Q bound of the kernel (kOlaQMax; kOlaQMaxNorm for the float32 overlap-add with BHW_OLA_NORMALIZE, which holds Q more
 // binary64 sums and is compiled for that many rows).
+// batch: the signals of a batched launch (bhwp_stft_ola), which share the workgroup target: gy_target is cut for grid_x * batch.
 BhwOlaPlan bhwp_ola_plan(const bhw_params *p, const bhw_ola *o, bool from_table, uint32_t force_q = 0, uint32_t force_rx = 0,
-                         uint64_t length = 0, uint32_t q_max = kOlaQMax);
+                         uint64_t length = 0, uint32_t q_max = kOlaQMax, uint64_t batch = 1);
 // bhw_overlap_add_describe: ct = the resident table's resolved configuration (format and layout set), or NULL for the library call
 int  bhwp_describe_ola(const bhw_params *p, const BhwCordicCfg *ct, const bhw_ola *o, char *buf, uint64_t len);
 // the overlap-add kernel of a plan (bhw_ola.hip): d_table NULL = k_ola_direct, else k_ola_table over the resident table of c
@@ -266,12 +267,55 @@ int  bhwp_f32_checks(const bhw_params *p, uint64_t length, uint32_t flags);
 // configuration, or NULL (library call).
 int  bhwp_describe_f32(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, bool force, const bhw_frames *f, const bhw_ola *o,
                        uint32_t flags, char *buf, uint64_t len);
+// The signals of a batched float32 overlap-add: `batch` of them (a grid dimension), the rows of signal b at d_y + b * y_bstride and
+// its outputs at d_x + b * x_bstride (float elements).  {1, 0, 0}: the one signal of bhw_overlap_add_f32_*.
+struct BhwOlaBatch {
+    uint64_t batch, y_bstride, x_bstride;
+};
+constexpr uint32_t kOlaMaxGridZ = 65535;      // signals of one launch (grid z); a larger batch takes several launches
 // the float32 kernels (bhw_frames_f32.hip, bhw_ola_f32.hip / bhw_ola_f32_norm.hip): d_table NULL = the direct CORDIC chains, else
 // the gather over the resident table of c; lp != NULL: the any-length forms over the window of length lp->len
 int  bhwk_frames_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwFramesPlan &pl, const bhw_frames *f,
                      const float *d_x, float *d_y, const int32_t *d_table, const BhwLenPhase *lp);
 int  bhwk_ola_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwOlaPlan &pl, const bhw_ola *o, bool normalize,
-                  const float *d_y, float *d_x, const int32_t *d_table, const BhwLenPhase *lp);
+                  const float *d_y, float *d_x, const int32_t *d_table, const BhwLenPhase *lp, const BhwOlaBatch &bt = BhwOlaBatch{1, 0, 0});
+
+// ---- batched, centred STFT framing and overlap-add (bhw_stft_frames_f32_* / bhw_istft_ola_f32_*) ----------------------------------
+// Frames: the lanes of a workgroup run along the row columns j in [0, n_fft) (kx of them, a power of two), fy = kFramesBlock / kx rows
+// side by side.  The rows (b, f) of the whole batch form one pool, row r = b * frames + f, which is cut into groups of G * fy rows as
+// bhwp_frames_plan cuts frames: a lane computes v[j - col0] once and applies it to G rows of any signals.  Row blocks past
+// kFramesMaxGridY are taken by a grid-stride loop.
+struct BhwStftPlan {
+    int route;            // BHWP_FRAMES_DIRECT or BHWP_FRAMES_TABLE
+    uint32_t kx;          // lanes along the row: the power of two at or above min(n_fft, kFramesBlock)
+    uint32_t fy;          // rows a workgroup runs side by side: kFramesBlock / kx
+    uint64_t rows;        // B * frames: the row pool
+    uint64_t group;       // G: rows one lane applies its coefficient to (in steps of fy)
+    uint64_t row_blocks;  // ceil(rows / (fy * G))
+    uint64_t grid_x;      // ceil(n_fft / kx)
+    uint64_t grid_y;      // min(row_blocks, kFramesMaxGridY)
+    uint64_t step_b, step_f;        // fy = step_b * frames + step_f: the (b, f) step of a lane from one of its rows to the next
+    uint64_t x_stride, y_stride, y_bstride;   // resolved (0 -> T * C, n_fft * C, frames * y_stride)
+    uint64_t len;         // L
+};
+// Every argument check of the four calls (include/bhw.h) that needs no table handle, before any HIP call.  inverse: the overlap-add
+// (flags 0 or BHW_OLA_NORMALIZE), else the frames call (flags must be 0).  frames 0 (frames call) / samples 0 (overlap-add) pass with
+// the pointers unchecked; `pointers` false: the describe call.
+int  bhwp_stft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, bool inverse, uint32_t flags, const void *d_x,
+                      const void *d_y, bool pointers = true);
+// the plan of a frames call that passed bhwp_stft_checks with frames > 0
+BhwStftPlan bhwp_stft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, bool from_table);
+// The overlap-add of a call that passed bhwp_stft_checks with samples > 0, mapped onto the one-signal overlap-add: o (t0 = pad - col0,
+// count = samples, y_stride resolved) over rows that start col0 * C floats into each frame row, and the batch strides.  The extent
+// check of bhwp_ola_checks does not apply: outputs past the frames' extent are empty sums.
+void bhwp_stft_ola(const bhw_stft *s, bhw_ola &o, BhwOlaBatch &bt);
+// bhw_describe_stft: ct = the resident table's resolved configuration, or NULL (library call)
+int  bhwp_describe_stft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, bool inverse, uint32_t flags,
+                        char *buf, uint64_t len);
+// the frames kernel (bhw_stft_f32.hip): d_table NULL = the direct CORDIC chains, else the gather over the resident table of c, both
+// at the angles of the length-L phase map lp (every L, 2^phi_width included)
+int  bhwk_stft_frames_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwStftPlan &pl, const bhw_stft *s,
+                          const float *d_x, float *d_y, const int32_t *d_table, const BhwLenPhase &lp);
 
 // the generate kernel of a window of any length (bhw_len.hip): d_table NULL = k_direct_len, else k_range_len over the resident table of c
 int  bhwk_len_range(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *d_table, const BhwLenPhase &lp,

@@ -309,6 +309,147 @@ def overlap_add(params, y, hop, *, frames=None, channels=1, shift=None, out=None
     return result
 
 
+_PAD_MODES = {"constant": B.PAD_CONSTANT, "reflect": B.PAD_REFLECT}
+
+
+def _stft_window(params, n_fft, win_length):
+    """(n_fft, L, col0): the window of win_length (default n_fft) centred in an n_fft row as torch.stft centres it."""
+    n_fft = int(n_fft)
+    L = n_fft if win_length is None else int(win_length)
+    if n_fft < 1:
+        raise ValueError("n_fft must be >= 1")
+    if not 1 <= L <= n_fft:
+        raise ValueError(f"expected 0 < win_length <= n_fft, but got win_length={L}, n_fft={n_fft}")
+    if L > 1 << params.phi_width:
+        raise ValueError(f"win_length {L} above 2^phi_width = {1 << params.phi_width}")
+    return n_fft, L, (n_fft - L) // 2
+
+
+def _stft_float(torch, t, what, dev):
+    """C of a float32 (1) or complex64 (2, interleaved pairs) CUDA tensor on `dev`."""
+    if not isinstance(t, torch.Tensor) or t.dtype not in (torch.float32, torch.complex64) or not t.is_cuda or t.device.index != dev:
+        raise ValueError(f"{what} must be a float32 or complex64 CUDA tensor on the call's device")
+    return 2 if t.dtype == torch.complex64 else 1
+
+
+def _stft_input(t, packed):
+    """t as the kernels read it: its elements in memory (a lazy conjugate or negation resolved), contiguous along the last axis, and
+    every outer stride at least the packed size of what it steps over (`packed`: the minimum stride per leading axis, in elements).
+    Anything else -- a broadcast (stride 0), overlapping or transposed view -- is copied first: the descriptor takes 0 for packed
+    and the checks cannot tell such a view from a buffer that holds the data."""
+    t = t.resolve_conj().resolve_neg()
+    ok = t.shape[-1] <= 1 or t.stride(-1) == 1
+    for axis, need in enumerate(packed):
+        ok = ok and (t.shape[axis] <= 1 or t.stride(axis) >= need)
+    return t if ok else t.contiguous()
+
+
+def _stft_out(torch, out, shape, like, what):
+    """The output tensor: allocated, or the caller's `out` of the shape the call returns (contiguous, no lazy conjugate or negation)."""
+    if out is None:
+        return torch.empty(shape, dtype=like.dtype, device=like.device)
+    if not isinstance(out, torch.Tensor) or out.dtype != like.dtype or out.device != like.device or not out.is_contiguous() \
+            or out.is_conj() or out.is_neg() or tuple(out.shape) != tuple(shape):
+        raise ValueError(f"out must be a contiguous {str(like.dtype).replace('torch.', '')} tensor of shape {tuple(shape)} on {what}'s device")
+    return out
+
+
+def _stft_frames_call(torch, params, x, n_fft, hop, win_length, center, pad_mode, shift, out, dev):
+    """Checks and shapes of stft_frames: (bhw_stft, L, the x read, out)."""
+    C = _stft_float(torch, x, "x", dev)
+    if x.dim() not in (1, 2):
+        raise ValueError("x must be (T,) or (B, T)")
+    hop = int(hop)
+    if hop < 1:
+        raise ValueError("hop must be >= 1")
+    n_fft, L, col0 = _stft_window(params, n_fft, win_length)
+    if pad_mode not in _PAD_MODES:
+        raise ValueError(f"pad_mode must be 'reflect' or 'constant', got {pad_mode!r}")
+    xb = x if x.dim() == 2 else x.unsqueeze(0)
+    nb, T = xb.shape
+    pad = n_fft // 2 if center else 0
+    if pad and pad_mode == "reflect" and pad >= T:
+        raise ValueError(f"reflect padding needs pad {pad} < T = {T} (n_fft // 2 < the signal's length)")
+    if nb < 1 or T + 2 * pad < n_fft:
+        raise ValueError(f"zero frames: T + 2 * pad = {T + 2 * pad} < n_fft = {n_fft}" if nb else "zero signals")
+    frames = 1 + (T + 2 * pad - n_fft) // hop
+    xb = _stft_input(xb, (T,))
+    shape = (nb, frames, n_fft) if x.dim() == 2 else (frames, n_fft)
+    out = _stft_out(torch, out, shape, x, "x")
+    shift = params.dat_width - 1 if shift is None else int(shift)
+    s = B.make_stft(nb, T, frames, hop, n_fft, col0=col0, pad=pad, pad_mode=_PAD_MODES[pad_mode], channels=C, shift=shift,
+                    x_stride=xb.stride(0) * C if nb > 1 else 0)
+    return s, L, xb, out
+
+
+def _istft_call(torch, params, y, n_fft, hop, win_length, center, length, normalize, shift, out, dev):
+    """Checks and shapes of istft_overlap_add: (bhw_stft, L, the y read, out, flags)."""
+    C = _stft_float(torch, y, "y", dev)
+    if y.dim() not in (2, 3):
+        raise ValueError("y must be (frames, n_fft) or (B, frames, n_fft)")
+    hop = int(hop)
+    if hop < 1:
+        raise ValueError("hop must be >= 1")
+    n_fft, L, col0 = _stft_window(params, n_fft, win_length)
+    if not center and L < n_fft:
+        raise ValueError("center=False with win_length < n_fft: the first outputs have no window under them")
+    yb = y if y.dim() == 3 else y.unsqueeze(0)
+    nb, frames, cols = yb.shape
+    if cols != n_fft:
+        raise ValueError(f"y rows hold {cols} columns, n_fft is {n_fft}")
+    if frames < 1 or nb < 1:
+        raise ValueError("zero frames")
+    pad = n_fft // 2 if center else 0
+    length = n_fft + hop * (frames - 1) - 2 * pad if length is None else int(length)
+    if length < 0:
+        raise ValueError(f"length {length} < 0")
+    yb = _stft_input(yb, ((frames - 1) * max(yb.stride(1), n_fft) + n_fft, n_fft))
+    out = _stft_out(torch, out, (nb, length) if y.dim() == 3 else (length,), y, "y")
+    shift = params.dat_width - 1 if shift is None else int(shift)
+    s = B.make_stft(nb, length, frames, hop, n_fft, col0=col0, pad=pad, channels=C, shift=shift,
+                    y_stride=yb.stride(1) * C if frames > 1 else 0, y_batch_stride=yb.stride(0) * C if nb > 1 else 0)
+    return s, L, yb, out, (B.OLA_NORMALIZE if normalize else 0)
+
+
+def stft_frames(params, x, n_fft, hop, *, win_length=None, center=True, pad_mode="reflect", shift=None, out=None):
+    """The framing of torch.stft for a batch, in one launch (bhw_stft_frames_f32_device): x (T,) or (B, T), float32 or complex64,
+    padded by n_fft // 2 on both sides (center=True; pad_mode "reflect" or "constant"), cut into frames of n_fft
+    at `hop`, and the window of win_length (default n_fft; v = window(params, win_length, dtype=torch.float32, shift=shift)) applied
+    in the columns [(n_fft - win_length) // 2, +win_length) of each row; the other columns are +0.0.  Returns (B, frames, n_fft), or
+    (frames, n_fft) for 1-D x, in x's dtype, frames = 1 + (T + 2 * pad - n_fft) // hop.  torch.fft.rfft (fft for complex x) of the
+    result, transposed to (..., n_fft // 2 + 1, frames), is torch.stft(x, n_fft, hop, win_length, window=v, center=center,
+    pad_mode=pad_mode, return_complex=True).  The kernel reads x in place when its rows are contiguous and apart (x[1:, :T] of a
+    wider buffer, say); a view that is not -- a broadcast (expand), transposed or lazily conjugated x -- is copied first.  `out`: a
+    contiguous tensor of the returned shape."""
+    torch = _torch()
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise ValueError("x must be a float32 or complex64 CUDA tensor")
+    dev = x.device.index
+    s, L, xr, out = _stft_frames_call(torch, params, x, n_fft, hop, win_length, center, pad_mode, shift, out, dev)
+    B.check(B.lib().bhw_stft_frames_f32_device(ctypes.byref(params), L, dev, _stream_ptr(torch, dev), ctypes.byref(s),
+                                               ctypes.c_void_p(xr.data_ptr()), ctypes.c_void_p(out.data_ptr())))
+    return out
+
+
+def istft_overlap_add(params, y, n_fft, hop, *, win_length=None, center=True, length=None, normalize=True, shift=None, out=None):
+    """The overlap-add of torch.istft for a batch, in one launch (bhw_istft_ola_f32_device): y (B, frames, n_fft) or (frames, n_fft),
+    float32 or complex64 (e.g. torch.fft.irfft(spec.transpose(-1, -2), n=n_fft)).  Each output t < length sums,
+    in ascending frame order in binary64, the frame elements under the window at padded time t + n_fft // 2 (center=True) times v
+    (window(params, win_length, dtype=torch.float32, shift=shift)), and with normalize=True divides by the window envelope, the sum of
+    v^2 (+0.0 where no frame reaches t).  length defaults to torch.istft's n_fft + hop * (frames - 1) - 2 * pad; outputs past the frames'
+    extent are +0.0.  Returns (B, length), or (length,) for 2-D y, in y's dtype.  y is read in place when its rows and signals are
+    contiguous along n_fft and apart; a broadcast, overlapping, transposed or lazily conjugated y is copied first.  `out`: a contiguous
+    tensor of the returned shape."""
+    torch = _torch()
+    if not isinstance(y, torch.Tensor) or not y.is_cuda:
+        raise ValueError("y must be a float32 or complex64 CUDA tensor")
+    dev = y.device.index
+    s, L, yr, out, flags = _istft_call(torch, params, y, n_fft, hop, win_length, center, length, normalize, shift, out, dev)
+    B.check(B.lib().bhw_istft_ola_f32_device(ctypes.byref(params), L, dev, _stream_ptr(torch, dev), ctypes.byref(s), flags,
+                                             ctypes.c_void_p(yr.data_ptr()), ctypes.c_void_p(out.data_ptr())))
+    return out
+
+
 class ResidentTable:
     """A first-quadrant CORDIC table built once and kept on the device (bhw_table_create): the elaboration of win_selector's
     CORDIC from its generics (model, PHI_WIDTH, DAT_WIDTH, PRECISION).  Every call then takes the run-time ports -- the weights
@@ -436,6 +577,28 @@ class ResidentTable:
     def describe_overlap_add(self, params, frames, hop, count=None, *, t0=0, channels=1, y_stride=0):
         """The route and kernel overlap_add(params, ...) launches over this table (bhw_overlap_add_describe)."""
         return B.describe_ola(params, frames, hop, count, t0=t0, channels=channels, y_stride=y_stride, table=self._live())
+
+    def stft_frames(self, params, x, n_fft, hop, *, win_length=None, center=True, pad_mode="reflect", shift=None, out=None):
+        """stft_frames() with the coefficients gathered from this table (bhw_stft_frames_f32_from_table): no allocation by the
+        library, no synchronisation, capturable into a graph."""
+        torch = _torch()
+        h = self._live()
+        s, L, xr, out = _stft_frames_call(torch, params, x, n_fft, hop, win_length, center, pad_mode, shift, out, self.device)
+        B.check(B.lib().bhw_stft_frames_f32_from_table(h, ctypes.byref(params), L, _stream_ptr(torch, self.device), ctypes.byref(s),
+                                                       ctypes.c_void_p(xr.data_ptr()), ctypes.c_void_p(out.data_ptr())))
+        return out
+
+    def istft_overlap_add(self, params, y, n_fft, hop, *, win_length=None, center=True, length=None, normalize=True, shift=None,
+                          out=None):
+        """istft_overlap_add() with the coefficients gathered from this table (bhw_istft_ola_f32_from_table): no allocation by the
+        library, no synchronisation, capturable into a graph."""
+        torch = _torch()
+        h = self._live()
+        s, L, yr, out, flags = _istft_call(torch, params, y, n_fft, hop, win_length, center, length, normalize, shift, out,
+                                           self.device)
+        B.check(B.lib().bhw_istft_ola_f32_from_table(h, ctypes.byref(params), L, _stream_ptr(torch, self.device), ctypes.byref(s),
+                                                     flags, ctypes.c_void_p(yr.data_ptr()), ctypes.c_void_p(out.data_ptr())))
+        return out
 
     def generate_part(self, params, part, n_parts, window):
         """Interleaved ownership part `part` of `n_parts` into the full-length `window` (bhw_generate_part_from_table)."""

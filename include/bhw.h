@@ -452,6 +452,65 @@ int bhw_overlap_add_f32_from_table(bhw_table t, const bhw_params *p, uint64_t le
 int bhw_describe_f32(bhw_table t, const bhw_params *p, uint64_t length, const bhw_frames *f, const bhw_ola *o, uint32_t flags,
                      char *buf, uint64_t len);
 
+/* Batched, centred STFT framing and overlap-add: the framing of torch.stft / torch.istft (center, pad_mode, win_length < n_fft) for
+ * B signals in one launch per side.  One descriptor serves both directions.  L is the window length `length` (1..2^phi_width), v[k]
+ * the float coefficient of the *_f32 calls above, C = channels (2: interleaved pairs, complex64; both share a coefficient).
+ *   - bhw_stft_frames_f32_*: for b < batch, f < frames, j < n_fft, c < C, with t = f * hop + j - pad (signed),
+ *         d_y[b * y_batch_stride + f * y_stride + j * C + c] = col0 <= j < col0 + L ? fl32(X_b(t, c) * v[j - col0]) : +0.0
+ *         X_b(t, c) = d_x[b * x_stride + t' * C + c],  t' = t for 0 <= t < samples;
+ *                     BHW_PAD_REFLECT: t' = -t (t < 0), 2 * (samples - 1) - t (t >= samples);  BHW_PAD_CONSTANT: X = +0.0 outside
+ *     This is F.pad(x, [pad, pad], pad_mode).unfold(-1, n_fft, hop) * window_padded, what torch.stft forms before its FFT, bit for
+ *     bit inside the window columns (IEEE special values included).  The one difference: outside the window torch gets x * 0.0
+ *     (-0.0 or NaN for some x), these calls write +0.0.  Every element of [0, n_fft * C) of each row is written; the elements
+ *     between n_fft * C and y_stride, and the gaps of y_batch_stride, never are.
+ *   - bhw_istft_ola_f32_*: for b < batch, t < samples, c < C, with u = t + pad, over the frames f with 0 <= k = u - f * hop - col0
+ *     < L in ASCENDING f, in binary64 from +0.0:
+ *         S = sum (double) d_y[b * y_batch_stride + f * y_stride + (u - f * hop) * C + c] * (double) v[k],   E = sum (double) v[k]^2
+ *         d_x[b * x_stride + t * C + c] = flags ? (E > 0 ? fl32(S / E) : +0.0) : fl32(S)
+ *     bhw_overlap_add_f32_* per signal, with t0 = pad - col0 and count = samples, save that samples may reach past the frames'
+ *     extent (outputs no frame reaches are +0.0, as torch.istft zero-pads a long `length`).  pad_mode must be 0.
+ *   - Argument checks, all before any HIP call (BHW_ERR_BADARG unless noted): those of the *_f32 calls on (p, length, flags), the
+ *     frames call taking flags 0 only; NULL descriptor or pointers, struct_size, channels outside {1, 2}, batch 0, hop 0, n_fft 0 or
+ *     above 2^31, shift > 62, col0 + L > n_fft, pad above 2^40, an unknown pad_mode (frames) or a nonzero one (overlap-add);
+ *     frames: a frame outside the padded signal ((frames - 1) * hop + n_fft > samples + 2 * pad), samples 0 with frames > 0,
+ *     BHW_PAD_REFLECT with pad > samples - 1; overlap-add: frames 0 with samples > 0, pad < col0 (the first outputs would have no
+ *     window under them; torch.istft raises there too); strides that make signals or rows overlap (x_stride below samples * C,
+ *     y_stride below n_fft * C, y_batch_stride below (frames - 1) * y_stride + n_fft * C), batch * frames * n_fft above 2^34,
+ *     d_x and d_y overlapping, the Taylor sources (BHW_ERR_UNSUPPORTED), and (from a table) the key match of the from-table calls.
+ *     frames 0 (frames call) or samples 0 (overlap-add) return BHW_OK with the pointers unchecked.
+ *   - The library forms compute the coefficients by direct CORDIC: no allocation, no scratch, capturable with no
+ *     bhw_prepare_device.  The from-table forms keep the from-table contract: no allocation, no synchronisation, always capturable.
+ *   - bhw_describe_stft: one line naming the route, the plan and the kernel of the frames call (inverse 0) or of the overlap-add
+ *     (inverse 1, flags 0 or BHW_OLA_NORMALIZE).  t may be NULL (the library call).  Host arithmetic only. */
+#define BHW_PAD_CONSTANT 0u
+#define BHW_PAD_REFLECT 1u
+typedef struct bhw_stft {
+    uint32_t struct_size;     /* sizeof(bhw_stft) = 96                                              */
+    uint32_t channels;        /* 1 (float32) or 2 (interleaved pairs: complex64)                    */
+    uint64_t batch;           /* B >= 1 signals                                                      */
+    uint64_t samples;         /* T: time indices per signal (read by the frames, written by the OLA) */
+    uint64_t x_stride;        /* float elements between signal starts; 0 = T * C                     */
+    uint64_t frames;          /* frames per signal                                                   */
+    uint64_t hop;             /* >= 1                                                                */
+    uint64_t n_fft;           /* columns of a frame row                                              */
+    uint64_t col0;            /* first window column; torch: (n_fft - L) / 2                         */
+    uint64_t pad;             /* padding in front of the signal: center n_fft / 2, else 0            */
+    uint64_t y_stride;        /* float elements between rows; 0 = n_fft * C                          */
+    uint64_t y_batch_stride;  /* float elements between the first rows of two signals; 0 = frames * y_stride */
+    uint32_t pad_mode;        /* frames: BHW_PAD_CONSTANT or BHW_PAD_REFLECT; overlap-add: 0          */
+    uint32_t shift;           /* 0..62                                                               */
+} bhw_stft;
+int bhw_stft_frames_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s,
+                               const float *d_x, float *d_y);
+int bhw_stft_frames_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s,
+                                   const float *d_x, float *d_y);
+int bhw_istft_ola_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                             const float *d_y, float *d_x);
+int bhw_istft_ola_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s,
+                                 uint32_t flags, const float *d_y, float *d_x);
+int bhw_describe_stft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, int inverse, uint32_t flags, char *buf,
+                      uint64_t len);
+
 /* Threading: every entry point may be called from any host thread.  Calls that use the library-owned scratch of one
  * (device, stream) are serialised against each other for the duration of their launches (the table is rebuilt per call);
  * callers that pass their own bhw_exec.workspace must not share one workspace between concurrent calls.  The calling

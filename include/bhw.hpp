@@ -13,6 +13,8 @@
 //                            the same for a window of any length L <= 2^phi_width (bhw_generate_len_device ...)
 //   bhw::apply_frames_f32(), bhw::overlap_add_f32()
 //                            float32 samples, with the envelope division of the overlap-add (bhw_apply_frames_f32_device ...)
+//   bhw::stft_frames_f32(), bhw::istft_ola_f32()
+//                            the framing of torch.stft / torch.istft for a batch (centred, padded, win_length < n_fft)
 // Same names, argument meaning and error behaviour (unknown win_type -> zeros, like win_empty,
 // hls/windows/win_function.cpp:159-165,417-419).  All arithmetic runs in the HIP kernels behind the ABI.
 #pragma once
@@ -248,6 +250,26 @@ inline std::string describe_f32(const bhw_params &p, uint64_t length, const bhw_
     return buf;
 }
 
+// Batched, centred STFT framing and overlap-add over the window of length L (bhw.h gives the arithmetic): one launch per side for the
+// B signals of the descriptor, and the one-line description (inverse: the overlap-add).
+inline void stft_frames_f32(const bhw_params &p, uint64_t length, const bhw_stft &s, const float *d_x, float *d_y, int device = 0,
+                            void *hip_stream = nullptr)
+{
+    check(bhw_stft_frames_f32_device(&p, length, device, hip_stream, &s, d_x, d_y));
+}
+inline void istft_ola_f32(const bhw_params &p, uint64_t length, const bhw_stft &s, uint32_t flags, const float *d_y, float *d_x,
+                          int device = 0, void *hip_stream = nullptr)
+{
+    check(bhw_istft_ola_f32_device(&p, length, device, hip_stream, &s, flags, d_y, d_x));
+}
+inline std::string describe_stft(const bhw_params &p, uint64_t length, const bhw_stft &s, bool inverse, uint32_t flags = 0,
+                                 bhw_table t = nullptr)
+{
+    char buf[640];
+    check(bhw_describe_stft(t, &p, length, &s, inverse ? 1 : 0, flags, buf, sizeof buf));
+    return buf;
+}
+
 // The CORDIC table of a configuration's generics, built once on `device` (bhw_table_create) and freed by the destructor
 // (bhw_table_destroy: it synchronises the device first).  Move-only.  Every call takes its weights -- the AA ports -- from its own
 // bhw_params, which must match the table's generics; device pointers and streams as in the C calls.
@@ -340,6 +362,20 @@ public:
     std::string describe_f32(const bhw_params &p, uint64_t length, const bhw_frames *f, const bhw_ola *o, uint32_t flags = 0) const
     {
         return bhw::describe_f32(p, length, f, o, flags, t_);
+    }
+    // batched STFT framing and overlap-add from this table (bhw_stft_frames_f32_from_table ...)
+    void stft_frames_f32(const bhw_params &p, uint64_t length, void *hip_stream, const bhw_stft &s, const float *d_x, float *d_y) const
+    {
+        check(bhw_stft_frames_f32_from_table(t_, &p, length, hip_stream, &s, d_x, d_y));
+    }
+    void istft_ola_f32(const bhw_params &p, uint64_t length, void *hip_stream, const bhw_stft &s, uint32_t flags, const float *d_y,
+                       float *d_x) const
+    {
+        check(bhw_istft_ola_f32_from_table(t_, &p, length, hip_stream, &s, flags, d_y, d_x));
+    }
+    std::string describe_stft(const bhw_params &p, uint64_t length, const bhw_stft &s, bool inverse, uint32_t flags = 0) const
+    {
+        return bhw::describe_stft(p, length, s, inverse, flags, t_);
     }
     void generate_part(const bhw_params &p, void *hip_stream, uint32_t part, uint32_t n_parts, int32_t *d_window) const
     {
