@@ -13,6 +13,10 @@ TABLE_BEST, TABLE_PLAIN, TABLE_DELTA16, TABLE_RESIDUAL, TABLE_NIBBLE, TABLE_NIBB
 ABI_VERSION = 4
 OLA_NORMALIZE = 1
 PAD_CONSTANT, PAD_REFLECT = 0, 1        # bhw_stft.pad_mode
+SUMS_F32 = 1                            # bhw_window_sums_* flags
+WELCH_DETREND_CONSTANT = 1              # bhw_welch_frames_f32_* flags
+PSD_ONESIDED = 1                        # bhw_psd.flags
+WELCH_BLOCK = 256                       # BHW_WELCH_BLOCK: frames of one block of the periodogram sum
 
 # every symbol include/bhw.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = (
@@ -32,6 +36,8 @@ ABI_SYMBOLS = (
     "bhw_describe_f32",
     "bhw_stft_frames_f32_device", "bhw_stft_frames_f32_from_table", "bhw_istft_ola_f32_device", "bhw_istft_ola_f32_from_table",
     "bhw_describe_stft",
+    "bhw_window_sums_device", "bhw_window_sums_from_table", "bhw_welch_workspace_bytes", "bhw_welch_frames_f32_device",
+    "bhw_welch_frames_f32_from_table", "bhw_welch_psd_workspace_bytes", "bhw_welch_psd_f32", "bhw_describe_welch",
 )
 
 
@@ -112,6 +118,22 @@ def make_stft(batch, samples, frames, hop, n_fft, *, col0=0, pad=0, pad_mode=0, 
     s.col0, s.pad, s.pad_mode, s.shift = int(col0), int(pad), int(pad_mode), int(shift)
     s.x_stride, s.y_stride, s.y_batch_stride = int(x_stride), int(y_stride), int(y_batch_stride)
     return s
+
+
+class BhwPsd(ctypes.Structure):
+    """struct bhw_psd of include/bhw.h (the averaged periodogram)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("batch", ctypes.c_uint64), ("frames", ctypes.c_uint64),
+                ("bins", ctypes.c_uint64), ("n_fft", ctypes.c_uint64), ("y_stride", ctypes.c_uint64), ("y_batch_stride", ctypes.c_uint64),
+                ("p_stride", ctypes.c_uint64), ("scale", ctypes.c_double)]
+
+
+def make_psd(batch, frames, bins, n_fft, scale, *, onesided=False, y_stride=0, y_batch_stride=0, p_stride=0):
+    d = BhwPsd()
+    d.struct_size = ctypes.sizeof(BhwPsd)
+    d.flags = PSD_ONESIDED if onesided else 0
+    d.batch, d.frames, d.bins, d.n_fft = int(batch), int(frames), int(bins), int(n_fft)
+    d.y_stride, d.y_batch_stride, d.p_stride, d.scale = int(y_stride), int(y_batch_stride), int(p_stride), float(scale)
+    return d
 
 
 _lib = None
@@ -211,6 +233,17 @@ def lib():
     L.bhw_istft_ola_f32_device.argtypes = [P, u64, ci, vp, S, u32, f32p, f32p]
     L.bhw_istft_ola_f32_from_table.argtypes = [T, P, u64, vp, S, u32, f32p, f32p]
     L.bhw_describe_stft.argtypes = [T, P, u64, S, ci, u32, ctypes.c_char_p, u64]
+    D = ctypes.POINTER(BhwPsd)
+    L.bhw_window_sums_device.argtypes = [P, u64, ci, vp, u32, vp]
+    L.bhw_window_sums_from_table.argtypes = [T, P, u64, vp, u32, vp]
+    L.bhw_welch_workspace_bytes.restype = u64
+    L.bhw_welch_workspace_bytes.argtypes = [S, u32]
+    L.bhw_welch_frames_f32_device.argtypes = [P, u64, ci, vp, S, u32, f32p, f32p, vp, u64]
+    L.bhw_welch_frames_f32_from_table.argtypes = [T, P, u64, vp, S, u32, f32p, f32p, vp, u64]
+    L.bhw_welch_psd_workspace_bytes.restype = u64
+    L.bhw_welch_psd_workspace_bytes.argtypes = [D]
+    L.bhw_welch_psd_f32.argtypes = [ci, vp, D, f32p, f32p, vp, u64]
+    L.bhw_describe_welch.argtypes = [T, P, u64, S, u32, D, ctypes.c_char_p, u64]
     PA = ctypes.POINTER(BhwAtan2Params)
     L.bhw_atan2_device.argtypes = [PA, ci, vp, u64, i32p, i32p, i32p]
     L.bhw_atan2_to_host.argtypes = [PA, ci, u64, i32p, i32p, i32p]
@@ -301,6 +334,40 @@ def describe_stft(params, length, stft, *, inverse=False, normalize=False, table
     check(lib().bhw_describe_stft(table, ctypes.byref(params), int(length), ctypes.byref(stft), 1 if inverse else 0,
                                   OLA_NORMALIZE if normalize else 0, buf, 640))
     return buf.value.decode()
+
+
+def describe_welch(params=None, length=0, *, stft=None, detrend=False, psd=None, sums_f32=False, table=None):
+    """One line naming the route, the plan and the kernels of a Welch call (bhw_describe_welch): the segments call of the descriptor
+    `stft` (a BhwStft with pad 0, col0 0; detrend: BHW_WELCH_DETREND_CONSTANT), the periodogram of `psd` (a BhwPsd, make_psd), or,
+    with neither, the window sums of the window of `length` (sums_f32: BHW_SUMS_F32).  `table` is a resident table handle or None."""
+    buf = ctypes.create_string_buffer(1024)
+    flags = (WELCH_DETREND_CONSTANT if detrend else 0) if stft is not None else (SUMS_F32 if sums_f32 else 0)
+    check(lib().bhw_describe_welch(table, ctypes.byref(params) if params is not None else None, int(length),
+                                   ctypes.byref(stft) if stft is not None else None, flags,
+                                   ctypes.byref(psd) if psd is not None else None, buf, len(buf)))
+    return buf.value.decode()
+
+
+def sums_from_words(words, shift, length):
+    """The window sums from the four result words of bhw_window_sums_*: (s1, s2) as Python ints, S1 = s1 * 2^-shift and
+    S2 = s2 * 2^-2 shift each rounded once to a float, coherent_gain = S1 / L and enbw_bins = L * S2 / S1^2."""
+    from fractions import Fraction
+    s1 = int(words[0]) - (1 << 64) if int(words[0]) >> 63 else int(words[0])
+    s2 = int(words[1]) + (int(words[2]) << 32)
+    if int(words[3]) != int(length):
+        raise RuntimeError(f"window sums counted {int(words[3])} coefficients, expected {int(length)}")
+    S1, S2 = float(Fraction(s1, 1 << shift)), float(Fraction(s2, 1 << (2 * shift)))
+    return {"s1": s1, "s2": s2, "S1": S1, "S2": S2, "length": int(length), "shift": int(shift),
+            "coherent_gain": S1 / length, "enbw_bins": length * S2 / (S1 * S1) if s1 else float("inf")}
+
+
+def welch_scale(sums, frames, fs=1.0, scaling="density"):
+    """The periodogram scale of scipy.signal.welch from the window sums: 1 / (fs * S2 * F) (density) or 1 / (S1^2 * F) (spectrum)."""
+    if scaling == "density":
+        return 1.0 / (float(fs) * sums["S2"] * frames)
+    if scaling == "spectrum":
+        return 1.0 / (sums["S1"] * sums["S1"] * frames)
+    raise ValueError(f"scaling must be 'density' or 'spectrum', got {scaling!r}")
 
 
 def part_segments(params, part, n_parts):

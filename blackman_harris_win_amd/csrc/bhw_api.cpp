@@ -1128,6 +1128,38 @@ int istft_ola_run(bhw_table t, const bhw_params *p, uint64_t length, int device,
                                                          const BhwLenPhase *lp) { return bhwk_ola_f32(l, c, w, pl, &o, norm, rows, d_x, tab, lp, bt); });
 }
 
+// The window sums (t NULL: the direct CORDIC chains): the checks, then the memset of the four words and the reduction.
+int window_sums_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, uint32_t flags, uint64_t *d_sums)
+{
+    int rc = bhwp_sums_checks(p, length, flags, d_sums);
+    if (!rc && t) rc = table_call_checks(t, p);
+    if (rc) return rc;
+    const BhwSumsPlan pl = bhwp_sums_plan(length);
+    const char *what = t ? "window sums launch (resident table)" : "window sums launch";
+    return run_source(t, p, length, device, stream, what, [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *tab,
+                                                              const BhwLenPhase *lp) { return bhwk_window_sums(l, c, w, pl, flags, tab, *lp, d_sums); });
+}
+
+// The Welch segments: flags 0 is the stft frames kernel on the same descriptor; with detrending the mean pass and the frames loop.
+int welch_frames_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *s, uint32_t flags,
+                     const float *d_x, float *d_y, void *workspace, uint64_t workspace_bytes)
+{
+    int rc = bhwp_welch_checks(p, length, s, flags, d_x, d_y, workspace, workspace_bytes);
+    if (!rc && t) rc = table_call_checks(t, p);
+    if (rc || !s->frames) return rc;
+    const BhwWelchPlan pl = bhwp_welch_plan(p, length, s, flags, t != nullptr);
+    const char *what = t ? "welch segments launch (resident table)" : "welch segments launch";
+    if (!pl.detrend)                                               // the stft frames kernel itself, under the Welch extent rule
+        return run_source(t, p, length, device, stream, what,
+                          [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *tab, const BhwLenPhase *lp) {
+                              return bhwk_stft_frames_f32(l, c, w, pl.frames, s, d_x, d_y, tab, *lp);
+                          });
+    return run_source(t, p, length, device, stream, what,
+                      [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *tab, const BhwLenPhase *lp) {
+                          return bhwk_welch_frames_f32(l, c, w, pl, s, d_x, d_y, (float *)workspace, tab, *lp);
+                      });
+}
+
 } // namespace
 
 extern "C" {
@@ -1271,6 +1303,58 @@ int bhw_describe_stft(bhw_table t, const bhw_params *p, uint64_t length, const b
     if (!rc && t) rc = table_call_checks(t, p);
     if (!rc) rc = bhwp_stft_checks(p, length, s, inverse != 0, flags, nullptr, nullptr, false);
     return rc ? rc : bhwp_describe_stft(p, t ? &t->c : nullptr, length, s, inverse != 0, flags, buf, len);
+}
+
+// ---- Welch's method (include/bhw.h: bhw_window_sums_device ...) ------------------------------------------------------------------------
+
+int bhw_window_sums_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, uint32_t flags, uint64_t *d_sums)
+{
+    return window_sums_run(nullptr, p, length, device, hip_stream, flags, d_sums);
+}
+
+int bhw_window_sums_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, uint32_t flags, uint64_t *d_sums)
+{
+    const int rc = bhwp_sums_checks(p, length, flags, d_sums);
+    if (rc) return rc;
+    return t ? window_sums_run(t, p, length, t->device, hip_stream, flags, d_sums) : fail(BHW_ERR_BADARG, "table is NULL");
+}
+
+int bhw_welch_frames_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                const float *d_x, float *d_y, void *workspace, uint64_t workspace_bytes)
+{
+    return welch_frames_run(nullptr, p, length, device, hip_stream, s, flags, d_x, d_y, workspace, workspace_bytes);
+}
+
+int bhw_welch_frames_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                    const float *d_x, float *d_y, void *workspace, uint64_t workspace_bytes)
+{
+    const int rc = bhwp_welch_checks(p, length, s, flags, d_x, d_y, workspace, workspace_bytes);
+    if (rc) return rc;
+    return t ? welch_frames_run(t, p, length, t->device, hip_stream, s, flags, d_x, d_y, workspace, workspace_bytes)
+             : fail(BHW_ERR_BADARG, "table is NULL");
+}
+
+int bhw_welch_psd_f32(int device, void *hip_stream, const bhw_psd *d, const float *d_Y, float *d_P, void *workspace, uint64_t workspace_bytes)
+{
+    const int rc = bhwp_psd_checks(d, d_Y, d_P, workspace, workspace_bytes);
+    if (rc) return rc;
+    const BhwPsdPlan pl = bhwp_psd_plan(d);
+    DeviceGuard guard(device);
+    if (const int g = guard.status()) return g;
+    const int e = bhwk_welch_psd_f32(BhwLaunch{device, hip_stream}, pl, d, d_Y, d_P, (double *)workspace);
+    return e ? fail_hip(e, "welch psd launch") : BHW_OK;
+}
+
+int bhw_describe_welch(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const bhw_psd *d, char *buf,
+                       uint64_t len)
+{
+    if (s && d) return fail(BHW_ERR_BADARG, "pass the segments descriptor or the periodogram descriptor, not both");
+    int rc;
+    if (d) rc = bhwp_psd_checks(d, nullptr, nullptr, nullptr, 0, false);
+    else if (s) rc = bhwp_welch_checks(p, length, s, flags, nullptr, nullptr, nullptr, 0, false);
+    else rc = bhwp_sums_checks(p, length, flags, nullptr, false);
+    if (!rc && t && !d) rc = table_call_checks(t, p);
+    return rc ? rc : bhwp_describe_welch(p, t && !d ? &t->c : nullptr, length, s, flags, d, buf, len);
 }
 
 // Development hook (not part of the ABI in include/bhw.h): on != 0 sends the *_len calls at L = 2^phi_width to the any-length kernels

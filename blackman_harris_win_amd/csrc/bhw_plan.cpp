@@ -1033,7 +1033,7 @@ int bhwp_describe_f32(const bhw_params *p, const BhwCordicCfg *ct, uint64_t leng
 // ---- batched, centred STFT framing and overlap-add ---------------------------------------------------------------------------------
 
 int bhwp_stft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, bool inverse, uint32_t flags, const void *d_x,
-                     const void *d_y, bool pointers)
+                     const void *d_y, bool pointers, bool welch)
 {
     int rc = bhwp_f32_checks(p, length, flags);
     if (rc) return rc;
@@ -1064,7 +1064,10 @@ int bhwp_stft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, bo
         if (!F) return BHW_OK;
         if (!T) return bhwp_fail(BHW_ERR_BADARG, "samples is 0 with frames %llu > 0", (unsigned long long)F);
         // every frame inside the padded signal; hop is a free 64-bit value, so the products are taken in 128 bits
-        if ((unsigned __int128)(F - 1) * s->hop + s->n_fft > (unsigned __int128)T + 2 * s->pad)
+        // (a Welch segment reads its L window columns only: the columns up to n_fft are the zero padding at its end)
+        if (welch && (unsigned __int128)(F - 1) * s->hop + length > (unsigned __int128)T + 2 * s->pad)
+            return bhwp_fail(BHW_ERR_BADARG, "(frames - 1) * hop + L > samples: segment %llu leaves the signal", (unsigned long long)(F - 1));
+        if (!welch && (unsigned __int128)(F - 1) * s->hop + s->n_fft > (unsigned __int128)T + 2 * s->pad)
             return bhwp_fail(BHW_ERR_BADARG, "(frames - 1) * hop + n_fft > samples + 2 * pad: frame %llu leaves the padded signal",
                              (unsigned long long)(F - 1));
         if (s->pad_mode == BHW_PAD_REFLECT && s->pad > T - 1)
@@ -1182,10 +1185,211 @@ int bhwp_describe_stft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t len
     return BHW_OK;
 }
 
+// ---- Welch's method: window sums, detrended segments, averaged periodogram ----------------------------------------------------------
+
+int bhwp_sums_checks(const bhw_params *p, uint64_t length, uint32_t flags, const void *d_sums, bool pointers)
+{
+    const int rc = bhwp_len_checks(p, length);
+    if (rc) return rc;
+    if (flags & ~BHW_SUMS_F32) return bhwp_fail(BHW_ERR_BADARG, "flags 0x%x (0 or BHW_SUMS_F32)", flags);
+    if (!pointers) return BHW_OK;
+    if (!d_sums) return bhwp_fail(BHW_ERR_BADARG, "d_sums is NULL");
+    if ((uintptr_t)d_sums % 8) return bhwp_fail(BHW_ERR_BADARG, "d_sums is not 8-byte aligned");
+    return BHW_OK;
+}
+
+BhwSumsPlan bhwp_sums_plan(uint64_t length)
+{
+    BhwSumsPlan pl{};
+    pl.len = length;
+    const uint64_t per_wg = (uint64_t)kSumsBlock * kSumsPerLane;
+    const uint64_t g = (length + per_wg - 1) / per_wg;
+    pl.grid = (uint32_t)(g < 1 ? 1 : g > kSumsMaxGrid ? kSumsMaxGrid : g);
+    const uint64_t lanes = (uint64_t)pl.grid * kSumsBlock;
+    pl.trips = (uint32_t)((length + lanes - 1) / lanes);
+    return pl;
+}
+
+uint64_t bhwp_welch_workspace_bytes(const bhw_stft *s, uint32_t flags)
+{
+    if (!s || !(flags & BHW_WELCH_DETREND_CONSTANT)) return 0;
+    const unsigned __int128 n = (unsigned __int128)s->batch * s->frames * s->channels * 4u;
+    return n > (1ull << 62) ? 0 : (uint64_t)n;
+}
+
+int bhwp_welch_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const void *d_x, const void *d_y,
+                      const void *workspace, uint64_t workspace_bytes, bool pointers)
+{
+    int rc = bhwp_f32_checks(p, length, 0);
+    if (rc) return rc;
+    if (flags & ~BHW_WELCH_DETREND_CONSTANT) return bhwp_fail(BHW_ERR_BADARG, "flags 0x%x (0 or BHW_WELCH_DETREND_CONSTANT)", flags);
+    rc = bhwp_stft_checks(p, length, s, false, 0, d_x, d_y, pointers, true);
+    if (rc) return rc;
+    if (s->pad) return bhwp_fail(BHW_ERR_BADARG, "pad %llu: Welch segments take no padding", (unsigned long long)s->pad);
+    if (s->col0) return bhwp_fail(BHW_ERR_BADARG, "col0 %llu: Welch segments are zero-padded at the end (col0 0)", (unsigned long long)s->col0);
+    if (s->pad_mode) return bhwp_fail(BHW_ERR_BADARG, "pad_mode %u: Welch segments take 0", s->pad_mode);
+    if (!pointers || !s->frames || !(flags & BHW_WELCH_DETREND_CONSTANT)) return BHW_OK;
+    const uint64_t need = bhwp_welch_workspace_bytes(s, flags);
+    if (!workspace) return bhwp_fail(BHW_ERR_BADARG, "workspace is NULL: detrending needs %llu bytes", (unsigned long long)need);
+    if ((uintptr_t)workspace % 4) return bhwp_fail(BHW_ERR_BADARG, "workspace is not 4-byte aligned");
+    if (workspace_bytes < need)
+        return bhwp_fail(BHW_ERR_WORKSPACE, "workspace of %llu bytes, detrending needs %llu", (unsigned long long)workspace_bytes,
+                         (unsigned long long)need);
+    // the extents bhwp_stft_checks has bounded (2^60 elements each, no wrap)
+    const uint64_t T = s->samples, C = s->channels, F = s->frames, NC = s->n_fft * C;
+    const uint64_t xs = s->x_stride ? s->x_stride : T * C, ys = s->y_stride ? s->y_stride : NC;
+    const uint64_t ybs = s->y_batch_stride ? s->y_batch_stride : F * ys;
+    const uint64_t xb = ((s->batch - 1) * xs + T * C) * 4u, yb = ((s->batch - 1) * ybs + (F - 1) * ys + NC) * 4u;
+    const uint64_t xa = (uint64_t)(uintptr_t)d_x, ya = (uint64_t)(uintptr_t)d_y, wa = (uint64_t)(uintptr_t)workspace;
+    if (wa > UINT64_MAX - need) return bhwp_fail(BHW_ERR_BADARG, "workspace range wraps the address space");
+    if ((wa < xa + xb && xa < wa + need) || (wa < ya + yb && ya < wa + need))
+        return bhwp_fail(BHW_ERR_BADARG, "workspace overlaps d_x or d_y");
+    return BHW_OK;
+}
+
+BhwWelchPlan bhwp_welch_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, bool from_table)
+{
+    BhwWelchPlan pl{};
+    pl.frames = bhwp_stft_plan(p, length, s, from_table);
+    pl.detrend = (flags & BHW_WELCH_DETREND_CONSTANT) != 0;
+    if (pl.detrend && pl.frames.rows) {
+        const uint64_t per_wg = kWelchMeanBlock / 64u;
+        const uint64_t wg = (pl.frames.rows + per_wg - 1) / per_wg;
+        pl.mean_grid = wg < kWelchMeanMaxGrid ? wg : kWelchMeanMaxGrid;
+        pl.ws_bytes = bhwp_welch_workspace_bytes(s, flags);
+    }
+    return pl;
+}
+
+BhwPsdPlan bhwp_psd_plan(const bhw_psd *d)
+{
+    BhwPsdPlan pl{};
+    pl.blocks = (d->frames + BHW_WELCH_BLOCK - 1) / BHW_WELCH_BLOCK;
+    pl.tiles = (d->bins + kPsdLanes - 1) / kPsdLanes;
+    pl.grid = d->batch * pl.blocks * pl.tiles;
+    pl.unroll = pl.grid <= kPsdSmallGrid ? kPsdUnrollMax : kPsdUnrollMin;
+    pl.y_stride = d->y_stride ? d->y_stride : d->bins;
+    pl.y_bstride = d->y_batch_stride ? d->y_batch_stride : d->frames * pl.y_stride;
+    pl.p_stride = d->p_stride ? d->p_stride : d->bins;
+    if (pl.blocks > 1) {
+        pl.join_grid = (d->batch * d->bins + 255u) / 256u;
+        pl.ws_bytes = d->batch * pl.blocks * d->bins * 8u;
+    }
+    return pl;
+}
+
+int bhwp_psd_checks(const bhw_psd *d, const void *d_Y, const void *d_P, const void *workspace, uint64_t workspace_bytes, bool pointers)
+{
+    if (!d) return bhwp_fail(BHW_ERR_BADARG, "psd descriptor is NULL");
+    if (d->struct_size != sizeof(bhw_psd)) return bhwp_fail(BHW_ERR_BADARG, "bhw_psd.struct_size %u != %zu", d->struct_size, sizeof(bhw_psd));
+    if (d->flags & ~BHW_PSD_ONESIDED) return bhwp_fail(BHW_ERR_BADARG, "flags 0x%x (0 or BHW_PSD_ONESIDED)", d->flags);
+    if (!d->batch || !d->frames || !d->bins) return bhwp_fail(BHW_ERR_BADARG, "batch, frames or bins is 0");
+    if (!d->n_fft || d->n_fft > (1ull << 31)) return bhwp_fail(BHW_ERR_BADARG, "n_fft %llu outside 1..2^31", (unsigned long long)d->n_fft);
+    if (d->bins > d->n_fft) return bhwp_fail(BHW_ERR_BADARG, "bins %llu above n_fft %llu", (unsigned long long)d->bins, (unsigned long long)d->n_fft);
+    if ((d->flags & BHW_PSD_ONESIDED) && d->bins != d->n_fft / 2 + 1)
+        return bhwp_fail(BHW_ERR_BADARG, "BHW_PSD_ONESIDED needs bins = n_fft / 2 + 1 = %llu, got %llu", (unsigned long long)(d->n_fft / 2 + 1),
+                         (unsigned long long)d->bins);
+    if (!(d->scale - d->scale == 0.0)) return bhwp_fail(BHW_ERR_BADARG, "scale is not finite");
+    const uint64_t K = d->bins, F = d->frames;
+    if ((unsigned __int128)d->batch * F * K > (1ull << 34)) return bhwp_fail(BHW_ERR_BADARG, "batch * frames * bins above 2^34 per call");
+    if (d->y_stride && d->y_stride < K)
+        return bhwp_fail(BHW_ERR_BADARG, "y_stride %llu < bins %llu: rows overlap", (unsigned long long)d->y_stride, (unsigned long long)K);
+    const uint64_t ys = d->y_stride ? d->y_stride : K;
+    const unsigned __int128 ysig = (unsigned __int128)(F - 1) * ys + K;
+    if (ysig > (1ull << 58)) return bhwp_fail(BHW_ERR_BADARG, "Y extent beyond 2^58 elements");
+    if (d->y_batch_stride && d->y_batch_stride < (uint64_t)ysig)
+        return bhwp_fail(BHW_ERR_BADARG, "y_batch_stride %llu < (frames - 1) * y_stride + bins = %llu: signals overlap",
+                         (unsigned long long)d->y_batch_stride, (unsigned long long)ysig);
+    if (d->p_stride && d->p_stride < K)
+        return bhwp_fail(BHW_ERR_BADARG, "p_stride %llu < bins %llu: rows overlap", (unsigned long long)d->p_stride, (unsigned long long)K);
+    const uint64_t ybs = d->y_batch_stride ? d->y_batch_stride : F * ys, ps = d->p_stride ? d->p_stride : K;
+    const unsigned __int128 ye = (unsigned __int128)(d->batch - 1) * ybs + ysig, pe = (unsigned __int128)(d->batch - 1) * ps + K;
+    if (ye > (1ull << 58) || pe > (1ull << 58)) return bhwp_fail(BHW_ERR_BADARG, "Y or P extent beyond 2^58 elements");
+    const uint64_t blocks = (F + BHW_WELCH_BLOCK - 1) / BHW_WELCH_BLOCK, tiles = (K + kPsdLanes - 1) / kPsdLanes;
+    if ((unsigned __int128)d->batch * blocks * tiles > 0x7FFFFFFFull)
+        return bhwp_fail(BHW_ERR_BADARG, "batch * ceil(frames / %u) * ceil(bins / %u) above 2^31 - 1 workgroups", BHW_WELCH_BLOCK, kPsdLanes);
+    if (!pointers) return BHW_OK;
+    if (!d_Y || !d_P) return bhwp_fail(BHW_ERR_BADARG, "d_Y / d_P is NULL");
+    if ((uintptr_t)d_Y % 8) return bhwp_fail(BHW_ERR_BADARG, "d_Y is not 8-byte aligned");
+    if ((uintptr_t)d_P % 4) return bhwp_fail(BHW_ERR_BADARG, "d_P is not 4-byte aligned");
+    const uint64_t Ya = (uint64_t)(uintptr_t)d_Y, Pa = (uint64_t)(uintptr_t)d_P, Yb = (uint64_t)ye * 8u, Pb = (uint64_t)pe * 4u;
+    if (Ya > UINT64_MAX - Yb || Pa > UINT64_MAX - Pb) return bhwp_fail(BHW_ERR_BADARG, "Y or P range wraps the address space");
+    if (Ya < Pa + Pb && Pa < Ya + Yb) return bhwp_fail(BHW_ERR_BADARG, "d_Y and d_P overlap");
+    if (blocks > 1) {
+        const uint64_t need = d->batch * blocks * K * 8u;                       // below 2^34 / 256 * 8 + ... : no overflow
+        if (!workspace) return bhwp_fail(BHW_ERR_BADARG, "workspace is NULL: %llu frame blocks need %llu bytes", (unsigned long long)blocks,
+                                         (unsigned long long)need);
+        if ((uintptr_t)workspace % 8) return bhwp_fail(BHW_ERR_BADARG, "workspace is not 8-byte aligned");
+        if (workspace_bytes < need)
+            return bhwp_fail(BHW_ERR_WORKSPACE, "workspace of %llu bytes, the block sums need %llu", (unsigned long long)workspace_bytes,
+                             (unsigned long long)need);
+        const uint64_t Wa = (uint64_t)(uintptr_t)workspace;
+        if (Wa > UINT64_MAX - need) return bhwp_fail(BHW_ERR_BADARG, "workspace range wraps the address space");
+        if ((Wa < Ya + Yb && Ya < Wa + need) || (Wa < Pa + Pb && Pa < Wa + need))
+            return bhwp_fail(BHW_ERR_BADARG, "workspace overlaps d_Y or d_P");
+    }
+    return BHW_OK;
+}
+
+int bhwp_describe_welch(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags, const bhw_psd *d,
+                        char *buf, uint64_t len)
+{
+    if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
+    if (d) {
+        const BhwPsdPlan pl = bhwp_psd_plan(d);
+        snprintf(buf, len, "welch psd (%s, n_fft %llu): k_welch_psd<%d,%u>, %llu signals x %llu frames x %llu bins, %llu block%s of %u frames, "
+                 "grid %llu x %u lanes (%u along the bins x %u waves of %u frames a pass)%s, workspace %llu bytes", (d->flags & BHW_PSD_ONESIDED) ? "one-sided" : "two-sided",
+                 (unsigned long long)d->n_fft, pl.blocks > 1 ? 1 : 0, pl.unroll, (unsigned long long)d->batch, (unsigned long long)d->frames,
+                 (unsigned long long)d->bins, (unsigned long long)pl.blocks, pl.blocks == 1 ? "" : "s", BHW_WELCH_BLOCK,
+                 (unsigned long long)pl.grid, kPsdLanes * kPsdWaves, kPsdLanes, kPsdWaves, pl.unroll, pl.blocks > 1 ? ", then k_welch_psd_join in block order" : "",
+                 (unsigned long long)pl.ws_bytes);
+        return BHW_OK;
+    }
+    const char *route = ct ? "table" : "direct";
+    char kern[64];
+    if (!s) {
+        const BhwSumsPlan pl = bhwp_sums_plan(length);
+        kernel_name(p, ct, "k_window_sums_direct", "k_window_sums_table", false, kern, sizeof kern);
+        snprintf(buf, len, "window sums %s (L = %llu, %s): memset of 4 words, then %s, grid %u x %u lanes, %u coefficient%s per lane, "
+                 "3 integer atomics per workgroup", route, (unsigned long long)length, (flags & BHW_SUMS_F32) ? "u = fl32(w)" : "u = w", kern,
+                 pl.grid, kSumsBlock, pl.trips, pl.trips == 1 ? "" : "s");
+        return BHW_OK;
+    }
+    if (!(flags & BHW_WELCH_DETREND_CONSTANT)) {
+        char inner[512];
+        const int rc = bhwp_describe_stft(p, ct, length, s, false, 0, inner, sizeof inner);
+        if (rc) return rc;
+        snprintf(buf, len, "welch segments %s, no detrending: %s", route, inner);
+        return BHW_OK;
+    }
+    if (!s->frames) {
+        snprintf(buf, len, "welch segments %s (L = %llu): nothing (frames 0)", route, (unsigned long long)length);
+        return BHW_OK;
+    }
+    const BhwWelchPlan pl = bhwp_welch_plan(p, length, s, flags, ct != nullptr);
+    kernel_name(p, ct, "k_welch_frames_direct", "k_welch_frames_table", false, kern, sizeof kern);
+    snprintf(buf, len, "welch segments %s (L = %llu, n_fft %llu), constant detrend: mean pass %s (one wave per row, grid %llu x %u "
+             "lanes, workspace %llu bytes), then %s, %u channel%s, %llu signals x %llu frames = %llu rows, G = %llu rows per lane, "
+             "grid %llu x %llu x %u lanes (%u along the row)", route, (unsigned long long)length, (unsigned long long)s->n_fft,
+             s->channels == 1 ? "k_welch_mean<0>" : "k_welch_mean<2> (<1> where the pairs are not 8-byte aligned)",
+             (unsigned long long)pl.mean_grid, kWelchMeanBlock, (unsigned long long)pl.ws_bytes, kern, s->channels, s->channels == 2 ? "s" : "",
+             (unsigned long long)s->batch, (unsigned long long)s->frames, (unsigned long long)pl.frames.rows,
+             (unsigned long long)pl.frames.group, (unsigned long long)pl.frames.grid_x, (unsigned long long)pl.frames.grid_y, kFramesBlock,
+             pl.frames.kx);
+    return BHW_OK;
+}
+
 // ---- the pure entry points of the C ABI (include/bhw.h) -------------------------------------------------------------------------------
 extern "C" {
 
 uint32_t bhw_abi_version(void) { return BHW_ABI_VERSION; }
+
+uint64_t bhw_welch_workspace_bytes(const bhw_stft *s, uint32_t flags) { return bhwp_welch_workspace_bytes(s, flags); }
+
+uint64_t bhw_welch_psd_workspace_bytes(const bhw_psd *d)
+{
+    return bhwp_psd_checks(d, nullptr, nullptr, nullptr, 0, false) ? 0 : bhwp_psd_plan(d).ws_bytes;
+}
 
 const char *bhw_strerror(int code)
 {

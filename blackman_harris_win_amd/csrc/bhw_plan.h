@@ -301,8 +301,9 @@ struct BhwStftPlan {
 // Every argument check of the four calls (include/bhw.h) that needs no table handle, before any HIP call.  inverse: the overlap-add
 // (flags 0 or BHW_OLA_NORMALIZE), else the frames call (flags must be 0).  frames 0 (frames call) / samples 0 (overlap-add) pass with
 // the pointers unchecked; `pointers` false: the describe call.
+// welch: the frames call of bhw_welch_frames_f32_*, whose segments read L samples each, not n_fft (bhwp_welch_checks).
 int  bhwp_stft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, bool inverse, uint32_t flags, const void *d_x,
-                      const void *d_y, bool pointers = true);
+                      const void *d_y, bool pointers = true, bool welch = false);
 // the plan of a frames call that passed bhwp_stft_checks with frames > 0
 BhwStftPlan bhwp_stft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, bool from_table);
 // The overlap-add of a call that passed bhwp_stft_checks with samples > 0, mapped onto the one-signal overlap-add: o (t0 = pad - col0,
@@ -316,6 +317,74 @@ int  bhwp_describe_stft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t le
 // at the angles of the length-L phase map lp (every L, 2^phi_width included)
 int  bhwk_stft_frames_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwStftPlan &pl, const bhw_stft *s,
                           const float *d_x, float *d_y, const int32_t *d_table, const BhwLenPhase &lp);
+
+// ---- Welch's method: window sums, detrended segments, averaged periodogram (bhw_window_sums_* / bhw_welch_*) ----------------------
+// Window sums: one lane per coefficient in a grid-stride loop, a wave and workgroup reduction of (s1, low and high halves of u^2), then
+// three 64-bit integer atomics per workgroup (bhw_welch_sums.hip).
+constexpr uint32_t kSumsBlock = 256;            // lanes of a workgroup
+constexpr uint32_t kSumsPerLane = 8;            // coefficients a lane aims at before the grid stops growing
+constexpr uint32_t kSumsMaxGrid = 4096;         // workgroups at most (each ends in three atomics)
+struct BhwSumsPlan {
+    uint64_t len;         // L
+    uint32_t grid;        // workgroups of kSumsBlock lanes; lane g takes k = g, g + grid * kSumsBlock, ...
+    uint32_t trips;       // ceil(L / (grid * kSumsBlock)): the loop count of every lane (uniform: the table gather is wave-wide)
+};
+int  bhwp_sums_checks(const bhw_params *p, uint64_t length, uint32_t flags, const void *d_sums, bool pointers = true);
+BhwSumsPlan bhwp_sums_plan(uint64_t length);
+// the 128-bit sum of squares from the two counters of the result: lo + hi * 2^32
+inline unsigned __int128 bhwp_sums_join(uint64_t lo, uint64_t hi) { return (unsigned __int128)lo + ((unsigned __int128)hi << 32); }
+
+// Segments with BHW_WELCH_DETREND_CONSTANT: a mean pass, one wave per (row, both channels), kWelchMeanBlock / 64 rows per workgroup and
+// a grid-stride loop over the row pool past kWelchMeanMaxGrid workgroups; then the frames loop of bhwp_stft_plan with the row's mean.
+constexpr uint32_t kWelchMeanBlock = 256;
+constexpr uint32_t kWelchMeanMaxGrid = 1u << 20;
+struct BhwWelchPlan {
+    BhwStftPlan frames;   // the plan of the frames launch (flags 0: the stft kernel itself)
+    bool detrend;
+    uint64_t mean_grid;   // workgroups of the mean pass (0 without detrending)
+    uint64_t ws_bytes;    // workspace the call needs: rows * C floats (0 without detrending)
+};
+// bhwp_stft_checks of the frames call, then the Welch restrictions and the workspace (pointers false: the describe call)
+int  bhwp_welch_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const void *d_x, const void *d_y,
+                       const void *workspace, uint64_t workspace_bytes, bool pointers = true);
+uint64_t bhwp_welch_workspace_bytes(const bhw_stft *s, uint32_t flags);
+BhwWelchPlan bhwp_welch_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, bool from_table);
+
+// Periodogram: one workgroup per (signal, frame block, bin tile), kPsdLanes lanes along the bins and kPsdWaves waves over the frames of a
+// pass (each loads `unroll` of them; wave 0 adds the pass in ascending order); a frame block is BHW_WELCH_BLOCK frames (part of the
+// contract, include/bhw.h).  One block: the first launch writes P.  More: it writes the block sums to the workspace,
+// [(b * blocks + blk) * K + k], and k_welch_psd_join adds them in block order.
+constexpr uint32_t kPsdLanes = 64;
+constexpr uint32_t kPsdWaves = 4;
+constexpr uint32_t kPsdUnrollMax = 16;          // frames one wave loads per pass, all in flight: 16 (a pass of 64 frames, 32 KiB of binary64
+constexpr uint32_t kPsdUnrollMin = 8;           // squares in LDS) up to kPsdSmallGrid workgroups, 8 (32 frames, 16 KiB) above
+constexpr uint32_t kPsdSmallGrid = 1024;
+struct BhwPsdPlan {
+    uint64_t blocks;      // ceil(F / BHW_WELCH_BLOCK)
+    uint64_t tiles;       // ceil(K / kPsdLanes)
+    uint64_t grid;        // B * blocks * tiles workgroups
+    uint32_t unroll;      // kPsdUnrollMax or kPsdUnrollMin
+    uint64_t join_grid;   // workgroups of the second launch (0 for one block)
+    uint64_t y_stride, y_bstride, p_stride;   // resolved
+    uint64_t ws_bytes;
+};
+int  bhwp_psd_checks(const bhw_psd *d, const void *d_Y, const void *d_P, const void *workspace, uint64_t workspace_bytes,
+                     bool pointers = true);
+BhwPsdPlan bhwp_psd_plan(const bhw_psd *d);
+// s_k's factor: 2 for the bins scipy doubles under BHW_PSD_ONESIDED
+BHW_HD inline bool bhw_psd_doubled(uint32_t flags, uint64_t k, uint64_t bins, uint64_t n_fft)
+{
+    return (flags & BHW_PSD_ONESIDED) && k != 0 && !(n_fft % 2 == 0 && k == bins - 1);
+}
+// bhw_describe_welch: s: the segments; d: the periodogram; neither: the window sums.  ct as bhwp_describe_stft.
+int  bhwp_describe_welch(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags, const bhw_psd *d,
+                         char *buf, uint64_t len);
+// the kernels (bhw_welch_sums.hip, bhw_welch_f32.hip): d_table NULL = the direct CORDIC chains, else the gather over the resident table
+int  bhwk_window_sums(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwSumsPlan &pl, uint32_t flags,
+                      const int32_t *d_table, const BhwLenPhase &lp, uint64_t *d_sums);
+int  bhwk_welch_frames_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwWelchPlan &pl, const bhw_stft *s,
+                           const float *d_x, float *d_y, float *d_mean, const int32_t *d_table, const BhwLenPhase &lp);
+int  bhwk_welch_psd_f32(const BhwLaunch &l, const BhwPsdPlan &pl, const bhw_psd *d, const float *d_Y, float *d_P, double *d_ws);
 
 // the generate kernel of a window of any length (bhw_len.hip): d_table NULL = k_direct_len, else k_range_len over the resident table of c
 int  bhwk_len_range(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *d_table, const BhwLenPhase &lp,

@@ -450,6 +450,193 @@ def istft_overlap_add(params, y, n_fft, hop, *, win_length=None, center=True, le
     return out
 
 
+# ---- Welch's method around the FFT: window sums, detrended segments, averaged periodogram ----------------------------------------------
+
+_SUMS_CACHE = {}        # (params bytes, length, shift, f32) -> the numbers of window_sums (library form; a ResidentTable keeps its own)
+
+
+def _sums_key(params, length, shift, f32):
+    return (bytes(params), int(length), int(shift), bool(f32))
+
+
+def _window_sums(torch, params, length, f32, shift, dev, table, cache):
+    """The numbers of window_sums, read back once per (params, length, shift, f32) and cached in `cache`."""
+    length = int(length)
+    shift = params.dat_width - 1 if shift is None else int(shift)
+    if not 0 <= shift <= 62:
+        raise ValueError("shift must be in 0..62")
+    key = _sums_key(params, length, shift, f32)
+    hit = cache.get(key)
+    if hit is not None:
+        return hit
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("the window sums of this (params, length, shift) have not been read yet: call once outside the capture")
+    words = torch.empty(4, dtype=torch.int64, device=f"cuda:{dev}")
+    flags = B.SUMS_F32 if f32 else 0
+    if table is None:
+        B.check(B.lib().bhw_window_sums_device(ctypes.byref(params), length, dev, _stream_ptr(torch, dev), flags,
+                                               ctypes.c_void_p(words.data_ptr())))
+    else:
+        B.check(B.lib().bhw_window_sums_from_table(table, ctypes.byref(params), length, _stream_ptr(torch, dev), flags,
+                                                   ctypes.c_void_p(words.data_ptr())))
+    w = [int(v) & ((1 << 64) - 1) for v in words.cpu().tolist()]
+    res = B.sums_from_words(w, shift, length)
+    cache[key] = res
+    return res
+
+
+def window_sums(params, length, *, f32=False, shift=None, device=None):
+    """The exact sums of the window of `length` (1..2^phi_width), computed on the device without storing the window
+    (bhw_window_sums_device): a dict with the Python ints s1 = sum u[k] and s2 = sum u[k]^2 (u = w, or with f32=True the integer
+    fl32(w) the float calls multiply by), S1 = s1 * 2^-shift and S2 = s2 * 2^-2 shift (each rounded once to a float; shift defaults
+    to dat_width - 1), coherent_gain = S1 / length and enbw_bins = length * S2 / S1^2.  Reads the four result words back (one
+    synchronisation) the first time; the numbers of a (params, length, shift, f32) are cached."""
+    torch = _torch()
+    dev = _dev_index(torch, device)
+    return _window_sums(torch, params, length, f32, shift, dev, None, _SUMS_CACHE)
+
+
+def _welch_frames_call(torch, params, x, length, hop, nfft, detrend, shift, out, workspace, dev):
+    """Checks and shapes of welch_frames: (bhw_stft, L, flags, the x read, out, workspace)."""
+    C = _stft_float(torch, x, "x", dev)
+    if x.dim() not in (1, 2):
+        raise ValueError("x must be (T,) or (B, T)")
+    L, hop = int(length), int(hop)
+    nfft = L if nfft is None else int(nfft)
+    if hop < 1:
+        raise ValueError("hop must be >= 1 (noverlap < length)")
+    if not 1 <= L <= 1 << params.phi_width:
+        raise ValueError(f"length {L} outside 1..2^phi_width = {1 << params.phi_width}")
+    if nfft < L:
+        raise ValueError(f"nfft {nfft} must be at least the window length {L}")
+    if detrend not in ("constant", False, None):
+        raise ValueError(f"detrend must be 'constant' or False, got {detrend!r}")
+    xb = x if x.dim() == 2 else x.unsqueeze(0)
+    nb, T = xb.shape
+    if nb < 1 or T < L:
+        raise ValueError(f"zero segments: T = {T} < length = {L}" if nb else "zero signals")
+    frames = 1 + (T - L) // hop                  # scipy: (T - noverlap) // (L - noverlap) with hop = L - noverlap
+    xb = _stft_input(xb, (T,))
+    out = _stft_out(torch, out, (nb, frames, nfft) if x.dim() == 2 else (frames, nfft), x, "x")
+    shift = params.dat_width - 1 if shift is None else int(shift)
+    flags = B.WELCH_DETREND_CONSTANT if detrend == "constant" else 0
+    s = B.make_stft(nb, T, frames, hop, nfft, channels=C, shift=shift, x_stride=xb.stride(0) * C if nb > 1 else 0)
+    need = nb * frames * C if flags else 0
+    if need and workspace is None:
+        workspace = torch.empty(need, dtype=torch.float32, device=x.device)
+    elif need:
+        _check_out(torch, workspace, need, "workspace", torch.float32)
+    return s, L, flags, xb, out, (workspace if need else None)
+
+
+def _welch_frames(torch, params, x, length, hop, nfft, detrend, shift, out, workspace, dev, table):
+    s, L, flags, xr, out, ws = _welch_frames_call(torch, params, x, length, hop, nfft, detrend, shift, out, workspace, dev)
+    tail = (ctypes.byref(s), flags, ctypes.c_void_p(xr.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+            ctypes.c_void_p(ws.data_ptr() if ws is not None else None), ws.numel() * 4 if ws is not None else 0)
+    if table is None:
+        B.check(B.lib().bhw_welch_frames_f32_device(ctypes.byref(params), L, dev, _stream_ptr(torch, dev), *tail))
+    else:
+        B.check(B.lib().bhw_welch_frames_f32_from_table(table, ctypes.byref(params), L, _stream_ptr(torch, dev), *tail))
+    return out
+
+
+def welch_frames(params, x, length, hop, *, nfft=None, detrend="constant", shift=None, out=None, workspace=None):
+    """The segments scipy.signal.welch hands its FFT (bhw_welch_frames_f32_device): x (T,) or (B, T), float32 or complex64, cut into
+    frames = 1 + (T - length) // hop segments at `hop` with no padding, each with its mean removed (detrend="constant"; the mean is a
+    binary64 sum in the fixed order include/bhw.h writes down, rounded to float32) or not (detrend=False: bit for bit
+    stft_frames(center=False) for nfft = length), multiplied by the window of `length` and zero-padded at the end to `nfft` (default
+    length).  Returns (B, frames, nfft) or (frames, nfft) in x's dtype.  `workspace`: B * frames * C float32 for the means (allocated
+    when not given; detrending only)."""
+    torch = _torch()
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise ValueError("x must be a float32 or complex64 CUDA tensor")
+    return _welch_frames(torch, params, x, length, hop, nfft, detrend, shift, out, workspace, x.device.index, None)
+
+
+def welch_psd(Y, scale, *, nfft, onesided=True, out=None, workspace=None):
+    """The averaged periodogram (bhw_welch_psd_f32): Y complex64 (F, K) or (B, F, K), the FFT of the segments; returns float32 (K,) or
+    (B, K) with P[b, k] = fl32(sum over f of |Y[b, f, k]|^2 * scale * (2 for the doubled bins of a one-sided spectrum)), the sum in
+    binary64 in ascending f inside blocks of 256 frames and then over the blocks in order.  onesided: K = nfft // 2 + 1 and every bin
+    but 0 (and nfft / 2 for even nfft) doubled.  Y is read in place when its bins are contiguous and its rows apart, else copied.
+    `out`: float32, last axis contiguous (its gaps are left alone); `workspace`: float64, B * ceil(F / 256) * K elements when F > 256
+    (allocated when not given)."""
+    torch = _torch()
+    if not isinstance(Y, torch.Tensor) or not Y.is_cuda or Y.dtype != torch.complex64:
+        raise ValueError("Y must be a complex64 CUDA tensor")
+    if Y.dim() not in (2, 3):
+        raise ValueError("Y must be (frames, bins) or (B, frames, bins)")
+    dev = Y.device.index
+    Yb = Y if Y.dim() == 3 else Y.unsqueeze(0)
+    nb, F, K = Yb.shape
+    if nb < 1 or F < 1 or K < 1:
+        raise ValueError("Y has no signals, frames or bins")
+    nfft = int(nfft)
+    if onesided and K != nfft // 2 + 1:
+        raise ValueError(f"a one-sided spectrum of nfft {nfft} has {nfft // 2 + 1} bins, Y has {K}")
+    if K > nfft:
+        raise ValueError(f"Y has {K} bins, more than nfft {nfft}")
+    Yb = _stft_input(Yb, ((F - 1) * max(Yb.stride(1), K) + K, K))
+    shape = (nb, K) if Y.dim() == 3 else (K,)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=Y.device)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != Y.device or tuple(out.shape) != shape \
+            or (K > 1 and out.stride(-1) != 1) or (out.dim() == 2 and nb > 1 and out.stride(0) < K):
+        raise ValueError(f"out must be a float32 tensor of shape {shape} on Y's device, contiguous along the bins, rows apart")
+    d = B.make_psd(nb, F, K, nfft, scale, onesided=onesided, y_stride=Yb.stride(1) if F > 1 else 0,
+                   y_batch_stride=Yb.stride(0) if nb > 1 else 0, p_stride=out.stride(0) if (out.dim() == 2 and nb > 1) else 0)
+    need = int(B.lib().bhw_welch_psd_workspace_bytes(ctypes.byref(d))) // 8
+    if need and workspace is None:
+        workspace = torch.empty(need, dtype=torch.float64, device=Y.device)
+    elif need:
+        _check_out(torch, workspace, need, "workspace", torch.float64)
+    B.check(B.lib().bhw_welch_psd_f32(dev, _stream_ptr(torch, dev), ctypes.byref(d), ctypes.c_void_p(Yb.data_ptr()),
+                                      ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(workspace.data_ptr() if need else None),
+                                      need * 8))
+    return out
+
+
+def _welch(torch, params, x, fs, length, noverlap, nfft, detrend, return_onesided, scaling, shift, average, dev, table, cache):
+    if average != "mean":
+        raise ValueError("only average='mean' is built (the median needs the periodograms kept)")
+    if detrend not in ("constant", False, None):
+        raise ValueError(f"detrend must be 'constant' or False, got {detrend!r}")
+    if scaling not in ("density", "spectrum"):
+        raise ValueError(f"scaling must be 'density' or 'spectrum', got {scaling!r}")
+    L = int(length)
+    noverlap = L // 2 if noverlap is None else int(noverlap)
+    if not 0 <= noverlap < L:
+        raise ValueError("noverlap must be less than length")
+    nfft = L if nfft is None else int(nfft)
+    seg = _welch_frames(torch, params, x, L, L - noverlap, nfft, detrend, shift, None, None, dev, table)
+    frames = seg.shape[-2]
+    sums = _window_sums(torch, params, L, True, shift, dev, table, cache)
+    scale = B.welch_scale(sums, frames, fs, scaling)
+    onesided = bool(return_onesided) and not seg.is_complex()
+    Y = torch.fft.rfft(seg, dim=-1) if onesided else torch.fft.fft(seg, dim=-1)
+    P = welch_psd(Y, scale, nfft=nfft, onesided=onesided)
+    mk = torch.fft.rfftfreq if onesided else torch.fft.fftfreq
+    return mk(nfft, d=1.0 / float(fs), dtype=torch.float64, device=seg.device), P
+
+
+def welch(params, x, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", return_onesided=True, scaling="density",
+          shift=None, average="mean"):
+    """Welch's power spectral density with one of this library's windows, scipy.signal.welch's defaults as the model: x (T,) or
+    (B, T), float32 (one-sided spectrum, rfft) or complex64 (two-sided, fft; return_onesided is then ignored, as scipy does), cut
+    into segments of `length` overlapping by noverlap (default length // 2), detrended ("constant" or False), windowed, zero-padded
+    to nfft (default length), transformed by torch.fft, and the periodograms averaged: window_sums -> welch_frames -> torch.fft ->
+    welch_psd.  scaling "density": 1 / (fs * sum v^2), "spectrum": 1 / (sum v)^2, from the exact sums of the float coefficients.
+    Returns (freqs float64, Pxx float32 (..., K)).  The sums of a (params, length, shift) are read from the device once and cached;
+    after that one call the whole chain neither synchronises nor reads back (capturable with ResidentTable.welch, whose segments
+    call needs no bhw_prepare_device).  Not built (ValueError): detrend="linear", average="median", cross spectra, scipy's boundary
+    and padded."""
+    torch = _torch()
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise ValueError("x must be a float32 or complex64 CUDA tensor")
+    dev = x.device.index
+    return _welch(torch, params, x, fs, length, noverlap, nfft, detrend, return_onesided, scaling, shift, average, dev, None,
+                  _SUMS_CACHE)
+
+
 class ResidentTable:
     """A first-quadrant CORDIC table built once and kept on the device (bhw_table_create): the elaboration of win_selector's
     CORDIC from its generics (model, PHI_WIDTH, DAT_WIDTH, PRECISION).  Every call then takes the run-time ports -- the weights
@@ -465,6 +652,7 @@ class ResidentTable:
         B.check(B.lib().bhw_table_create(ctypes.byref(self.params), self.device, _stream_ptr(torch, self.device),
                                          int(table_format), ctypes.byref(h)))
         self.handle = h
+        self._sums = {}                      # window sums read back so far (welch)
 
     def close(self):
         if self.handle:
@@ -599,6 +787,23 @@ class ResidentTable:
         B.check(B.lib().bhw_istft_ola_f32_from_table(h, ctypes.byref(params), L, _stream_ptr(torch, self.device), ctypes.byref(s),
                                                      flags, ctypes.c_void_p(yr.data_ptr()), ctypes.c_void_p(out.data_ptr())))
         return out
+
+    def window_sums(self, params, length, *, f32=False, shift=None):
+        """window_sums() with the coefficients gathered from this table (bhw_window_sums_from_table); the numbers are cached on the
+        table per (params, length, shift, f32)."""
+        return _window_sums(_torch(), params, length, f32, shift, self.device, self._live(), self._sums)
+
+    def welch_frames(self, params, x, length, hop, *, nfft=None, detrend="constant", shift=None, out=None, workspace=None):
+        """welch_frames() with the coefficients gathered from this table (bhw_welch_frames_f32_from_table): no allocation by the
+        library, no synchronisation, capturable into a graph."""
+        return _welch_frames(_torch(), params, x, length, hop, nfft, detrend, shift, out, workspace, self.device, self._live())
+
+    def welch(self, params, x, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", return_onesided=True,
+              scaling="density", shift=None, average="mean"):
+        """welch() from this table.  The window sums are read back once per (params, length, shift) and kept on the table; after that
+        one call the whole chain can be captured into a graph."""
+        return _welch(_torch(), params, x, fs, length, noverlap, nfft, detrend, return_onesided, scaling, shift, average, self.device,
+                      self._live(), self._sums)
 
     def generate_part(self, params, part, n_parts, window):
         """Interleaved ownership part `part` of `n_parts` into the full-length `window` (bhw_generate_part_from_table)."""

@@ -30,7 +30,7 @@ extern "C" {
 
 #define BHW_ABI_VERSION 4u   /* 3: bhw_coeffs_preset, bhw_gather_parts_device; 4: bhw_workspace_bytes_ex (nothing removed or changed);
                                 the resident tables, the overlapped-frame apply, the overlap-add and the windows of any length
-                                were added without a bump (additions only) */
+                                were added without a bump (additions only), as were the float32, STFT and Welch calls */
 
 /* CORDIC bit-model (the reference holds three that are not bit-identical). */
 enum {
@@ -510,6 +510,99 @@ int bhw_istft_ola_f32_from_table(bhw_table t, const bhw_params *p, uint64_t leng
                                  uint32_t flags, const float *d_y, float *d_x);
 int bhw_describe_stft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, int inverse, uint32_t flags, char *buf,
                       uint64_t len);
+
+/* Welch's method around the FFT (scipy.signal.welch's defaults as the model): the window sums every spectrum scaling needs, the
+ * detrended windowed segments in front of the FFT, and the averaged periodogram behind it.  The FFT itself is the caller's (hipFFT,
+ * torch.fft).  L is the window length `length` (1..2^phi_width), w[k] the int32 coefficient of the length-L phase map (the *_len
+ * calls; the power-of-two window at L = 2^phi_width) and v[k] = fl32(w[k]) * 2^-shift the float coefficient of the *_f32 calls.
+ *
+ * 1. Window sums.  Exact integer sums of the window, computed on the device without storing it:
+ *        s1 = sum over k < L of u[k]   (int64),        s2 = sum over k < L of u[k]^2   (below 2^92)
+ *    with u[k] = w[k], or under BHW_SUMS_F32 u[k] = (int64) fl32(w[k]), the integer the float calls multiply by (it differs from
+ *    w[k] only for |w[k]| >= 2^24; |u| <= 2^31 either way).  d_sums receives four 64-bit words:
+ *        d_sums[0] = s1 (two's complement)          d_sums[1] = sum of the low 32 bits of u[k]^2
+ *        d_sums[2] = sum of u[k]^2 >> 32            d_sums[3] = L (the number of coefficients summed)
+ *    so that s2 = d_sums[1] + d_sums[2] * 2^32, joined by the host in 128 bits (L <= 2^30 keeps each word below 2^62 and |s1| <= 2^61).
+ *    The sums are integers: the result does not depend on the order of the reduction, which uses 64-bit integer atomics.
+ *    The caller zeroes nothing: the call first clears the four words with a memset on the stream (a memset node under capture), then
+ *    launches the reduction -- asynchronous, no synchronisation, capturable.  The library form computes the coefficients by the direct
+ *    CORDIC chains (no scratch, no bhw_prepare_device); the from-table form gathers them and keeps the from-table contract.
+ *    Checks before any HIP call: those of the *_len calls on (p, length) (the Taylor sources: BHW_ERR_UNSUPPORTED), flags outside
+ *    {0, BHW_SUMS_F32}, d_sums NULL or not 8-byte aligned (BHW_ERR_BADARG), and (from a table) the key match.
+ *
+ * 2. Welch segments.  scipy.signal.welch cuts frames = (T - noverlap) / (L - noverlap) segments at hop = L - noverlap with no padding,
+ *    detrends each, multiplies by the window and zero-pads at the END to n_fft.  The descriptor is bhw_stft with pad 0, col0 0,
+ *    pad_mode 0 and n_fft >= L (batch, strides, one or two channels as there), plus a flags word:
+ *    A segment reads its L window columns only, so the extent rule is (frames - 1) * hop + L <= samples (scipy's segment count), not
+ *    the n_fft one of bhw_stft_frames_f32_*: the columns L..n_fft of a row are written, never read.
+ *      flags 0:  exactly bhw_stft_frames_f32_* of the same descriptor (the same kernel).  No workspace is needed or read.
+ *      BHW_WELCH_DETREND_CONSTANT:  for each row (b, f) and channel c, with x_j = X_b(f * hop + j, c) for j < L:
+ *            S = sum over j < L of (double) x_j, in the FIXED order below, binary64 from +0.0
+ *            m = fl32(S / (double) L)                                   (a correctly rounded binary64 division, then one rounding)
+ *            d_y[b * y_batch_stride + f * y_stride + j * C + c] = j < L ? fl32(fl32(x_j - m) * v[j]) : +0.0      (no fused operation)
+ *        Binary64 addition of float32 values is not exact, so the ORDER of S is part of the contract.  It is a function of L alone --
+ *        not of the plan, the batch, the lane layout, or library versus table:
+ *            P[i] = sum of x_j over j = i, i + 64, i + 128, ... < L, in ascending j, binary64 from +0.0         (i = 0..63)
+ *            for s = 32, 16, 8, 4, 2, 1:  P[i] = P[i] + P[i + s]  for every i < s (all i of a step read before any is written)
+ *            S = P[0]
+ *        IEEE special values propagate: a NaN or an infinity in a segment poisons that row (and channel) and no other.
+ *        The means go through a caller workspace of bhw_welch_workspace_bytes bytes (batch * frames * C floats, row (b, f) at
+ *        (b * frames + f) * C + c): a first launch computes them, one wave per row, a second one is the stft frames loop with one more
+ *        load and a subtraction per row.  No call allocates.
+ *    Checks before any HIP call (BHW_ERR_BADARG unless noted): those of bhw_stft_frames_f32_* (with the extent rule above), plus pad != 0,
+ *    col0 != 0, pad_mode != 0,
+ *    flags outside {0, BHW_WELCH_DETREND_CONSTANT}, and with detrending and frames > 0 a NULL, misaligned (4 bytes) or short workspace
+ *    (short: BHW_ERR_WORKSPACE) or one that overlaps d_x or d_y.
+ *
+ * 3. Averaged periodogram.  d_Y: complex64 (B, F, K) as interleaved float pairs, 8-byte aligned, row (b, f) at
+ *    (b * y_batch_stride + f * y_stride) complex elements, bins contiguous; d_P: float32, row b at b * p_stride floats.
+ *        q_f   = (double) re * (double) re + (double) im * (double) im      (both squares are exact in binary64: one rounding, and a
+ *                                                                            fused multiply-add gives the same value)
+ *        A_blk = sum of q_f over the frames of one block, in ascending f, binary64 from +0.0
+ *        A     = sum of A_blk over the blocks, in ascending order, binary64 from +0.0
+ *        d_P[b * p_stride + k] = fl32(A * s_k),    s_k = scale * (doubled(k) ? 2 : 1)          (binary64 products, one final rounding)
+ *    A block is BHW_WELCH_BLOCK consecutive frames (the last one shorter), so every F <= BHW_WELCH_BLOCK is one plain ascending sum.
+ *    Under BHW_PSD_ONESIDED doubled(k) is true for every k except 0 and, for even n_fft, K - 1 (scipy's rule); otherwise never.
+ *    With more than one block the block sums go through a caller workspace of bhw_welch_psd_workspace_bytes bytes
+ *    (B * ceil(F / BLOCK) * K doubles; 0 for one block) and a second launch adds them in block order: no float atomics.  Only the
+ *    K floats of each output row are written.  Y is read exactly once, with nontemporal loads.
+ *    Checks before any HIP call (BHW_ERR_BADARG unless noted): NULL descriptor or pointers, struct_size, reserved != 0, unknown flags,
+ *    batch, frames or bins 0, n_fft 0, bins above n_fft, BHW_PSD_ONESIDED with bins != n_fft / 2 + 1, a scale that is not finite,
+ *    strides that make rows overlap (y_stride < K, y_batch_stride < (F - 1) * y_stride + K, p_stride < K), B * F * K above 2^34,
+ *    B * ceil(F / BLOCK) * ceil(K / 64) above 2^31 - 1, d_Y not 8-byte aligned, d_P overlapping d_Y, a missing or misaligned
+ *    workspace when one is needed, a short one (BHW_ERR_WORKSPACE).
+ *
+ *  - bhw_describe_welch: one line naming the route, the plan and the kernels.  s non-NULL: the segments call (flags: its flags);
+ *    d non-NULL: the periodogram (p, length may then be NULL / 0); both NULL: the window sums (flags: BHW_SUMS_F32 or 0).  t may be NULL
+ *    (the library call).  Host arithmetic only. */
+#define BHW_SUMS_F32 1u
+#define BHW_WELCH_DETREND_CONSTANT 1u
+#define BHW_PSD_ONESIDED 1u
+#define BHW_WELCH_BLOCK 256u
+typedef struct bhw_psd {
+    uint32_t struct_size;     /* sizeof(bhw_psd) = 72                                            */
+    uint32_t flags;           /* 0 or BHW_PSD_ONESIDED                                            */
+    uint64_t batch;           /* B >= 1                                                           */
+    uint64_t frames;          /* F >= 1: the rows averaged                                        */
+    uint64_t bins;            /* K >= 1: n_fft / 2 + 1 (rfft) or n_fft (fft)                      */
+    uint64_t n_fft;           /* for doubled(k)                                                   */
+    uint64_t y_stride;        /* complex elements between frames; 0 = K                           */
+    uint64_t y_batch_stride;  /* complex elements between signals; 0 = frames * y_stride          */
+    uint64_t p_stride;        /* float elements between output rows; 0 = K                        */
+    double   scale;           /* density: 1 / (fs * sum v^2 * F); spectrum: 1 / ((sum v)^2 * F)   */
+} bhw_psd;
+int bhw_window_sums_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, uint32_t flags, uint64_t *d_sums);
+int bhw_window_sums_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, uint32_t flags, uint64_t *d_sums);
+uint64_t bhw_welch_workspace_bytes(const bhw_stft *s, uint32_t flags);
+int bhw_welch_frames_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                const float *d_x, float *d_y, void *workspace, uint64_t workspace_bytes);
+int bhw_welch_frames_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s,
+                                    uint32_t flags, const float *d_x, float *d_y, void *workspace, uint64_t workspace_bytes);
+uint64_t bhw_welch_psd_workspace_bytes(const bhw_psd *d);
+int bhw_welch_psd_f32(int device, void *hip_stream, const bhw_psd *d, const float *d_Y, float *d_P, void *workspace,
+                      uint64_t workspace_bytes);
+int bhw_describe_welch(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const bhw_psd *d,
+                       char *buf, uint64_t len);
 
 /* Threading: every entry point may be called from any host thread.  Calls that use the library-owned scratch of one
  * (device, stream) are serialised against each other for the duration of their launches (the table is rebuilt per call);
