@@ -17,6 +17,11 @@ SUMS_F32 = 1                            # bhw_window_sums_* flags
 WELCH_DETREND_CONSTANT = 1              # bhw_welch_frames_f32_* flags
 PSD_ONESIDED = 1                        # bhw_psd.flags
 WELCH_BLOCK = 256                       # BHW_WELCH_BLOCK: frames of one block of the periodogram sum
+CSD_ONESIDED, CSD_BROADCAST_X = 1, 2    # bhw_csd.flags
+CSD_PXY, CSD_PXX, CSD_PYY, CSD_COHERENCE, CSD_H1 = 0x10, 0x20, 0x40, 0x80, 0x100
+# output name -> (flag, complex); the order of the pointers of bhw_welch_csd_f32
+CSD_OUTPUTS = {"pxy": (CSD_PXY, True), "pxx": (CSD_PXX, False), "pyy": (CSD_PYY, False), "coherence": (CSD_COHERENCE, False),
+               "h1": (CSD_H1, True)}
 
 # every symbol include/bhw.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = (
@@ -38,6 +43,7 @@ ABI_SYMBOLS = (
     "bhw_describe_stft",
     "bhw_window_sums_device", "bhw_window_sums_from_table", "bhw_welch_workspace_bytes", "bhw_welch_frames_f32_device",
     "bhw_welch_frames_f32_from_table", "bhw_welch_psd_workspace_bytes", "bhw_welch_psd_f32", "bhw_describe_welch",
+    "bhw_welch_csd_workspace_bytes", "bhw_welch_csd_f32", "bhw_describe_csd",
 )
 
 
@@ -133,6 +139,38 @@ def make_psd(batch, frames, bins, n_fft, scale, *, onesided=False, y_stride=0, y
     d.flags = PSD_ONESIDED if onesided else 0
     d.batch, d.frames, d.bins, d.n_fft = int(batch), int(frames), int(bins), int(n_fft)
     d.y_stride, d.y_batch_stride, d.p_stride, d.scale = int(y_stride), int(y_batch_stride), int(p_stride), float(scale)
+    return d
+
+
+class BhwCsd(ctypes.Structure):
+    """struct bhw_csd of include/bhw.h (the Welch cross spectra)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("batch", ctypes.c_uint64), ("frames", ctypes.c_uint64),
+                ("bins", ctypes.c_uint64), ("n_fft", ctypes.c_uint64), ("x_stride", ctypes.c_uint64), ("x_batch_stride", ctypes.c_uint64),
+                ("y_stride", ctypes.c_uint64), ("y_batch_stride", ctypes.c_uint64), ("o_stride", ctypes.c_uint64),
+                ("scale", ctypes.c_double), ("reserved", ctypes.c_uint64)]
+
+
+def csd_mask(outputs):
+    """The output mask of bhw_csd.flags from output names (CSD_OUTPUTS)."""
+    if isinstance(outputs, str):
+        outputs = (outputs,)
+    outputs = tuple(outputs)
+    if not outputs or len(set(outputs)) != len(outputs) or any(o not in CSD_OUTPUTS for o in outputs):
+        raise ValueError(f"outputs must be a non-empty selection, without repeats, of {tuple(CSD_OUTPUTS)}, got {outputs!r}")
+    mask = 0
+    for o in outputs:
+        mask |= CSD_OUTPUTS[o][0]
+    return mask
+
+
+def make_csd(batch, frames, bins, n_fft, scale, *, outputs=("pxy",), onesided=False, broadcast_x=False, x_stride=0, x_batch_stride=0,
+             y_stride=0, y_batch_stride=0, o_stride=0):
+    d = BhwCsd()
+    d.struct_size = ctypes.sizeof(BhwCsd)
+    d.flags = csd_mask(outputs) | (CSD_ONESIDED if onesided else 0) | (CSD_BROADCAST_X if broadcast_x else 0)
+    d.batch, d.frames, d.bins, d.n_fft = int(batch), int(frames), int(bins), int(n_fft)
+    d.x_stride, d.x_batch_stride, d.y_stride, d.y_batch_stride = int(x_stride), int(x_batch_stride), int(y_stride), int(y_batch_stride)
+    d.o_stride, d.scale = int(o_stride), float(scale)
     return d
 
 
@@ -244,6 +282,11 @@ def lib():
     L.bhw_welch_psd_workspace_bytes.argtypes = [D]
     L.bhw_welch_psd_f32.argtypes = [ci, vp, D, f32p, f32p, vp, u64]
     L.bhw_describe_welch.argtypes = [T, P, u64, S, u32, D, ctypes.c_char_p, u64]
+    X = ctypes.POINTER(BhwCsd)
+    L.bhw_welch_csd_workspace_bytes.restype = u64
+    L.bhw_welch_csd_workspace_bytes.argtypes = [X]
+    L.bhw_welch_csd_f32.argtypes = [ci, vp, X, f32p, f32p, f32p, f32p, f32p, f32p, f32p, vp, u64]
+    L.bhw_describe_csd.argtypes = [X, ctypes.c_char_p, u64]
     PA = ctypes.POINTER(BhwAtan2Params)
     L.bhw_atan2_device.argtypes = [PA, ci, vp, u64, i32p, i32p, i32p]
     L.bhw_atan2_to_host.argtypes = [PA, ci, u64, i32p, i32p, i32p]
@@ -345,6 +388,14 @@ def describe_welch(params=None, length=0, *, stft=None, detrend=False, psd=None,
     check(lib().bhw_describe_welch(table, ctypes.byref(params) if params is not None else None, int(length),
                                    ctypes.byref(stft) if stft is not None else None, flags,
                                    ctypes.byref(psd) if psd is not None else None, buf, len(buf)))
+    return buf.value.decode()
+
+
+def describe_csd(csd):
+    """One line naming the form (two or four chains), the plan and the kernels of a cross-spectra call (bhw_describe_csd) for the
+    descriptor `csd` (a BhwCsd, make_csd).  Host arithmetic only."""
+    buf = ctypes.create_string_buffer(1024)
+    check(lib().bhw_describe_csd(ctypes.byref(csd), buf, len(buf)))
     return buf.value.decode()
 
 

@@ -1357,6 +1357,19 @@ int bhw_describe_welch(bhw_table t, const bhw_params *p, uint64_t length, const 
     return rc ? rc : bhwp_describe_welch(p, t && !d ? &t->c : nullptr, length, s, flags, d, buf, len);
 }
 
+int bhw_welch_csd_f32(int device, void *hip_stream, const bhw_csd *d, const float *d_X, const float *d_Y, float *d_Pxy, float *d_Pxx,
+                      float *d_Pyy, float *d_Cxy, float *d_H1, void *workspace, uint64_t workspace_bytes)
+{
+    float *const outs[kCsdOutputs] = {d_Pxy, d_Pxx, d_Pyy, d_Cxy, d_H1};
+    const int rc = bhwp_csd_checks(d, d_X, d_Y, (const void *const *)outs, workspace, workspace_bytes);
+    if (rc) return rc;
+    const BhwCsdPlan pl = bhwp_csd_plan(d);
+    DeviceGuard guard(device);
+    if (const int g = guard.status()) return g;
+    const int e = bhwk_welch_csd_f32(BhwLaunch{device, hip_stream}, pl, d, d_X, d_Y, outs, (double *)workspace);
+    return e ? fail_hip(e, "welch csd launch") : BHW_OK;
+}
+
 // Development hook (not part of the ABI in include/bhw.h): on != 0 sends the *_len calls at L = 2^phi_width to the any-length kernels
 // as well (process-wide), so that tests can compare them with the power-of-two kernels.  Returns the previous setting.
 int bhw_dbg_len_force_kernels(int on) { return g_len_force.exchange(on != 0) ? 1 : 0; }

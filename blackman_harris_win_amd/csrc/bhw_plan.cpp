@@ -1379,8 +1379,155 @@ int bhwp_describe_welch(const bhw_params *p, const BhwCordicCfg *ct, uint64_t le
     return BHW_OK;
 }
 
+// ---- cross spectra -----------------------------------------------------------------------------------------------------------------------
+BhwCsdPlan bhwp_csd_plan(const bhw_csd *d)
+{
+    BhwCsdPlan pl{};
+    pl.blocks = (d->frames + BHW_WELCH_BLOCK - 1) / BHW_WELCH_BLOCK;
+    pl.tiles = (d->bins + kPsdLanes - 1) / kPsdLanes;
+    pl.grid = d->batch * pl.blocks * pl.tiles;
+    pl.chains = (d->flags & kCsdOutputMask) == BHW_CSD_PXY ? 2u : 4u;
+    pl.unroll = kCsdPassBytes / (kPsdWaves * kPsdLanes * pl.chains * 8u);
+    pl.lds_bytes = kPsdWaves * pl.unroll * kPsdLanes * pl.chains * 8u;
+    pl.x_stride = d->x_stride ? d->x_stride : d->bins;
+    pl.x_bstride = (d->flags & BHW_CSD_BROADCAST_X) ? 0 : d->x_batch_stride ? d->x_batch_stride : d->frames * pl.x_stride;
+    pl.y_stride = d->y_stride ? d->y_stride : d->bins;
+    pl.y_bstride = d->y_batch_stride ? d->y_batch_stride : d->frames * pl.y_stride;
+    pl.o_stride = d->o_stride ? d->o_stride : d->bins;
+    if (pl.blocks > 1) {
+        pl.join_grid = (d->batch * d->bins + 255u) / 256u;
+        pl.ws_bytes = d->batch * pl.blocks * d->bins * pl.chains * 8u;
+    }
+    return pl;
+}
+
+// one operand's strides: rows and signals apart; *ext = its extent in complex elements
+static int csd_operand(const char *name, uint64_t B, uint64_t F, uint64_t K, uint64_t stride, uint64_t bstride, uint64_t *ext)
+{
+    if (stride && stride < K)
+        return bhwp_fail(BHW_ERR_BADARG, "%s_stride %llu < bins %llu: rows overlap", name, (unsigned long long)stride, (unsigned long long)K);
+    const uint64_t s = stride ? stride : K;
+    const unsigned __int128 sig = (unsigned __int128)(F - 1) * s + K;
+    if (sig > (1ull << 58)) return bhwp_fail(BHW_ERR_BADARG, "%s extent beyond 2^58 elements", name);
+    if (bstride && bstride < (uint64_t)sig)
+        return bhwp_fail(BHW_ERR_BADARG, "%s_batch_stride %llu < (frames - 1) * %s_stride + bins = %llu: signals overlap", name,
+                         (unsigned long long)bstride, name, (unsigned long long)sig);
+    const uint64_t bs = bstride ? bstride : F * s;
+    const unsigned __int128 e = (unsigned __int128)(B - 1) * bs + sig;
+    if (e > (1ull << 58)) return bhwp_fail(BHW_ERR_BADARG, "%s extent beyond 2^58 elements", name);
+    *ext = (uint64_t)e;
+    return BHW_OK;
+}
+
+int bhwp_csd_checks(const bhw_csd *d, const void *d_X, const void *d_Y, const void *const *outs, const void *workspace,
+                    uint64_t workspace_bytes, bool pointers)
+{
+    static const char *const names[kCsdOutputs] = {"d_Pxy", "d_Pxx", "d_Pyy", "d_Cxy", "d_H1"};
+    static const uint32_t bits[kCsdOutputs] = {BHW_CSD_PXY, BHW_CSD_PXX, BHW_CSD_PYY, BHW_CSD_COHERENCE, BHW_CSD_H1};
+    static const uint32_t width[kCsdOutputs] = {8, 4, 4, 4, 8};
+    if (!d) return bhwp_fail(BHW_ERR_BADARG, "csd descriptor is NULL");
+    if (d->struct_size != sizeof(bhw_csd)) return bhwp_fail(BHW_ERR_BADARG, "bhw_csd.struct_size %u != %zu", d->struct_size, sizeof(bhw_csd));
+    if (d->reserved) return bhwp_fail(BHW_ERR_BADARG, "bhw_csd.reserved is not 0");
+    if (d->flags & ~(BHW_CSD_ONESIDED | BHW_CSD_BROADCAST_X | kCsdOutputMask))
+        return bhwp_fail(BHW_ERR_BADARG, "flags 0x%x (BHW_CSD_ONESIDED, BHW_CSD_BROADCAST_X and the output mask 0x%x)", d->flags, kCsdOutputMask);
+    if (!(d->flags & kCsdOutputMask)) return bhwp_fail(BHW_ERR_BADARG, "flags 0x%x: the output mask is empty", d->flags);
+    if (!d->batch || !d->frames || !d->bins) return bhwp_fail(BHW_ERR_BADARG, "batch, frames or bins is 0");
+    if (!d->n_fft || d->n_fft > (1ull << 31)) return bhwp_fail(BHW_ERR_BADARG, "n_fft %llu outside 1..2^31", (unsigned long long)d->n_fft);
+    if (d->bins > d->n_fft) return bhwp_fail(BHW_ERR_BADARG, "bins %llu above n_fft %llu", (unsigned long long)d->bins, (unsigned long long)d->n_fft);
+    if ((d->flags & BHW_CSD_ONESIDED) && d->bins != d->n_fft / 2 + 1)
+        return bhwp_fail(BHW_ERR_BADARG, "BHW_CSD_ONESIDED needs bins = n_fft / 2 + 1 = %llu, got %llu", (unsigned long long)(d->n_fft / 2 + 1),
+                         (unsigned long long)d->bins);
+    if (!(d->scale - d->scale == 0.0)) return bhwp_fail(BHW_ERR_BADARG, "scale is not finite");
+    const uint64_t K = d->bins, F = d->frames, B = d->batch;
+    const bool bcast = (d->flags & BHW_CSD_BROADCAST_X) != 0;
+    if ((unsigned __int128)B * F * K > (1ull << 34)) return bhwp_fail(BHW_ERR_BADARG, "batch * frames * bins above 2^34 per call");
+    if (bcast && d->x_batch_stride)
+        return bhwp_fail(BHW_ERR_BADARG, "x_batch_stride %llu under BHW_CSD_BROADCAST_X: X is one signal", (unsigned long long)d->x_batch_stride);
+    uint64_t xe, ye;
+    if (int rc = csd_operand("x", bcast ? 1 : B, F, K, d->x_stride, d->x_batch_stride, &xe)) return rc;
+    if (int rc = csd_operand("y", B, F, K, d->y_stride, d->y_batch_stride, &ye)) return rc;
+    if (d->o_stride && d->o_stride < K)
+        return bhwp_fail(BHW_ERR_BADARG, "o_stride %llu < bins %llu: rows overlap", (unsigned long long)d->o_stride, (unsigned long long)K);
+    const unsigned __int128 oe = (unsigned __int128)(B - 1) * (d->o_stride ? d->o_stride : K) + K;
+    if (oe > (1ull << 58)) return bhwp_fail(BHW_ERR_BADARG, "output extent beyond 2^58 elements");
+    const uint64_t blocks = (F + BHW_WELCH_BLOCK - 1) / BHW_WELCH_BLOCK, tiles = (K + kPsdLanes - 1) / kPsdLanes;
+    if ((unsigned __int128)B * blocks * tiles > 0x7FFFFFFFull)
+        return bhwp_fail(BHW_ERR_BADARG, "batch * ceil(frames / %u) * ceil(bins / %u) above 2^31 - 1 workgroups", BHW_WELCH_BLOCK, kPsdLanes);
+    if (!pointers) return BHW_OK;
+    if (!d_X || !d_Y) return bhwp_fail(BHW_ERR_BADARG, "d_X / d_Y is NULL");
+    if ((uintptr_t)d_X % 8 || (uintptr_t)d_Y % 8) return bhwp_fail(BHW_ERR_BADARG, "d_X / d_Y is not 8-byte aligned");
+    // the byte ranges the call touches: X, Y, the requested outputs, the workspace
+    uint64_t lo[kCsdOutputs + 3], nb[kCsdOutputs + 3];
+    const char *what[kCsdOutputs + 3];
+    uint32_t n = 0;
+    lo[n] = (uint64_t)(uintptr_t)d_X, nb[n] = xe * 8u, what[n++] = "d_X";
+    lo[n] = (uint64_t)(uintptr_t)d_Y, nb[n] = ye * 8u, what[n++] = "d_Y";
+    for (uint32_t i = 0; i < kCsdOutputs; ++i) {
+        if (!(d->flags & bits[i])) continue;
+        const void *o = outs ? outs[i] : nullptr;
+        if (!o) return bhwp_fail(BHW_ERR_BADARG, "%s is NULL and its output is requested", names[i]);
+        if ((uintptr_t)o % width[i]) return bhwp_fail(BHW_ERR_BADARG, "%s is not %u-byte aligned", names[i], width[i]);
+        lo[n] = (uint64_t)(uintptr_t)o, nb[n] = (uint64_t)oe * width[i], what[n++] = names[i];
+    }
+    const uint32_t chains = (d->flags & kCsdOutputMask) == BHW_CSD_PXY ? 2u : 4u;
+    const uint64_t need = blocks > 1 ? B * blocks * K * chains * 8u : 0;             // below 2^34 / 256 * 32 + ...: no overflow
+    if (need) {
+        if (!workspace) return bhwp_fail(BHW_ERR_BADARG, "workspace is NULL: %llu frame blocks need %llu bytes", (unsigned long long)blocks,
+                                         (unsigned long long)need);
+        if ((uintptr_t)workspace % 8) return bhwp_fail(BHW_ERR_BADARG, "workspace is not 8-byte aligned");
+        if (workspace_bytes < need)
+            return bhwp_fail(BHW_ERR_WORKSPACE, "workspace of %llu bytes, the block sums need %llu", (unsigned long long)workspace_bytes,
+                             (unsigned long long)need);
+        lo[n] = (uint64_t)(uintptr_t)workspace, nb[n] = need, what[n++] = "workspace";
+    }
+    for (uint32_t i = 0; i < n; ++i)
+        if (lo[i] > UINT64_MAX - nb[i]) return bhwp_fail(BHW_ERR_BADARG, "%s range wraps the address space", what[i]);
+    for (uint32_t i = 2; i < n; ++i)                                                  // X and Y are only read: they may coincide
+        for (uint32_t j = 0; j < i; ++j)
+            if (lo[i] < lo[j] + nb[j] && lo[j] < lo[i] + nb[i]) {
+                if (i == n - 1 && need) return bhwp_fail(BHW_ERR_BADARG, "workspace overlaps %s", what[j]);
+                return bhwp_fail(BHW_ERR_BADARG, "%s and %s overlap", what[j], what[i]);
+            }
+    return BHW_OK;
+}
+
+int bhwp_describe_csd(const bhw_csd *d, char *buf, uint64_t len)
+{
+    if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
+    const BhwCsdPlan pl = bhwp_csd_plan(d);
+    char outs[64] = "";
+    static const char *const names[kCsdOutputs] = {"pxy", "pxx", "pyy", "coherence", "h1"};
+    static const uint32_t bits[kCsdOutputs] = {BHW_CSD_PXY, BHW_CSD_PXX, BHW_CSD_PYY, BHW_CSD_COHERENCE, BHW_CSD_H1};
+    for (uint32_t i = 0; i < kCsdOutputs; ++i)
+        if (d->flags & bits[i]) {
+            if (outs[0]) strncat(outs, "+", sizeof outs - strlen(outs) - 1);
+            strncat(outs, names[i], sizeof outs - strlen(outs) - 1);
+        }
+    snprintf(buf, len, "welch csd (%s, n_fft %llu, %s%s): k_welch_csd<%u,%d>, %u chains (%s), %llu signals x %llu frames x %llu bins, "
+             "%llu block%s of %u frames, grid %llu x %u lanes (%u along the bins x %u waves of %u frames a pass, %u bytes of LDS)%s, "
+             "workspace %llu bytes", (d->flags & BHW_CSD_ONESIDED) ? "one-sided" : "two-sided", (unsigned long long)d->n_fft, outs,
+             (d->flags & BHW_CSD_BROADCAST_X) ? ", X broadcast" : "", pl.chains, pl.blocks > 1 ? 1 : 0, pl.chains,
+             pl.chains == 2 ? "C_re, C_im" : "S_xx, S_yy, C_re, C_im", (unsigned long long)d->batch, (unsigned long long)d->frames,
+             (unsigned long long)d->bins, (unsigned long long)pl.blocks, pl.blocks == 1 ? "" : "s", BHW_WELCH_BLOCK, (unsigned long long)pl.grid,
+             kPsdLanes * kPsdWaves, kPsdLanes, kPsdWaves, pl.unroll, pl.lds_bytes,
+             pl.blocks > 1 ? (pl.chains == 2 ? ", then k_welch_csd_join<2> in block order" : ", then k_welch_csd_join<4> in block order") : "",
+             (unsigned long long)pl.ws_bytes);
+    return BHW_OK;
+}
+
 // ---- the pure entry points of the C ABI (include/bhw.h) -------------------------------------------------------------------------------
 extern "C" {
+
+uint64_t bhw_welch_csd_workspace_bytes(const bhw_csd *d)
+{
+    return bhwp_csd_checks(d, nullptr, nullptr, nullptr, nullptr, 0, false) ? 0 : bhwp_csd_plan(d).ws_bytes;
+}
+
+int bhw_describe_csd(const bhw_csd *d, char *buf, uint64_t len)
+{
+    const int rc = bhwp_csd_checks(d, nullptr, nullptr, nullptr, nullptr, 0, false);
+    return rc ? rc : bhwp_describe_csd(d, buf, len);
+}
 
 uint32_t bhw_abi_version(void) { return BHW_ABI_VERSION; }
 

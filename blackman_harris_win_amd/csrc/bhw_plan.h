@@ -386,6 +386,35 @@ int  bhwk_welch_frames_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwW
                            const float *d_x, float *d_y, float *d_mean, const int32_t *d_table, const BhwLenPhase &lp);
 int  bhwk_welch_psd_f32(const BhwLaunch &l, const BhwPsdPlan &pl, const bhw_psd *d, const float *d_Y, float *d_P, double *d_ws);
 
+// Cross spectra (bhw_welch_csd.hip): the periodogram's grid -- one workgroup per (signal of Y, frame block, bin tile), kPsdLanes lanes
+// along the bins, kPsdWaves waves over the frames of a pass -- with two operands and `chains` ordered sums per bin: 2 (C_re, C_im) when
+// P_xy is the only output, else 4 (S_xx, S_yy, C_re, C_im).  Wave w loads `unroll` frames of X and of Y per pass and puts their `chains`
+// binary64 terms in LDS; then wave c < chains adds chain c of the pass in ascending order.  unroll = kCsdPassBytes / (waves * lanes *
+// chains * 8): a pass always fills kCsdPassBytes = 32 KiB of LDS (16 frames of four terms, 32 frames of two), so four workgroups fit the
+// CU's 160 KiB.  One block: the first launch writes the outputs.  More: the block sums go to the workspace,
+// [((b * blocks + blk) * chains + c) * K + k], and k_welch_csd_join adds them in block order and writes the outputs.
+constexpr uint32_t kCsdPassBytes = 32u * 1024u;
+constexpr uint32_t kCsdOutputs = 5;              // d_Pxy, d_Pxx, d_Pyy, d_Cxy, d_H1: the order of the output mask's bits
+constexpr uint32_t kCsdOutputMask = BHW_CSD_PXY | BHW_CSD_PXX | BHW_CSD_PYY | BHW_CSD_COHERENCE | BHW_CSD_H1;
+struct BhwCsdPlan {
+    uint64_t blocks;      // ceil(F / BHW_WELCH_BLOCK)
+    uint64_t tiles;       // ceil(K / kPsdLanes)
+    uint64_t grid;        // B * blocks * tiles workgroups
+    uint32_t chains;      // 2 or 4
+    uint32_t unroll;      // frames one wave loads per pass: 8 (two chains) or 4 (four)
+    uint32_t lds_bytes;   // waves * unroll * lanes * chains * 8
+    uint64_t join_grid;   // workgroups of the second launch (0 for one block)
+    uint64_t x_stride, x_bstride, y_stride, y_bstride, o_stride;   // resolved; x_bstride 0 under BHW_CSD_BROADCAST_X
+    uint64_t ws_bytes;
+};
+// outs: the five output pointers in the order of kCsdOutputs (pointers false: the describe / workspace-size calls, outs may be NULL)
+int  bhwp_csd_checks(const bhw_csd *d, const void *d_X, const void *d_Y, const void *const *outs, const void *workspace,
+                     uint64_t workspace_bytes, bool pointers = true);
+BhwCsdPlan bhwp_csd_plan(const bhw_csd *d);
+int  bhwp_describe_csd(const bhw_csd *d, char *buf, uint64_t len);
+int  bhwk_welch_csd_f32(const BhwLaunch &l, const BhwCsdPlan &pl, const bhw_csd *d, const float *d_X, const float *d_Y, float *const *outs,
+                        double *d_ws);
+
 // the generate kernel of a window of any length (bhw_len.hip): d_table NULL = k_direct_len, else k_range_len over the resident table of c
 int  bhwk_len_range(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *d_table, const BhwLenPhase &lp,
                     uint64_t n0, uint64_t count, int32_t *d_out);

@@ -627,14 +627,185 @@ def welch(params, x, fs=1.0, *, length, noverlap=None, nfft=None, detrend="const
     welch_psd.  scaling "density": 1 / (fs * sum v^2), "spectrum": 1 / (sum v)^2, from the exact sums of the float coefficients.
     Returns (freqs float64, Pxx float32 (..., K)).  The sums of a (params, length, shift) are read from the device once and cached;
     after that one call the whole chain neither synchronises nor reads back (capturable with ResidentTable.welch, whose segments
-    call needs no bhw_prepare_device).  Not built (ValueError): detrend="linear", average="median", cross spectra, scipy's boundary
-    and padded."""
+    call needs no bhw_prepare_device).  Not built (ValueError): detrend="linear", average="median", scipy's boundary and padded.
+    Cross spectra: csd(), coherence(), transfer_function(), cross_spectra()."""
     torch = _torch()
     if not isinstance(x, torch.Tensor) or not x.is_cuda:
         raise ValueError("x must be a float32 or complex64 CUDA tensor")
     dev = x.device.index
     return _welch(torch, params, x, fs, length, noverlap, nfft, detrend, return_onesided, scaling, shift, average, dev, None,
                   _SUMS_CACHE)
+
+
+# ---- Welch cross spectra: the pass behind the FFT for two signals -------------------------------------------------------------------------
+
+def _csd_operand(torch, t, what, dev):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.complex64 or t.device.index != dev:
+        raise ValueError(f"{what} must be a complex64 CUDA tensor on the call's device")
+    if t.dim() not in (2, 3):
+        raise ValueError(f"{what} must be (frames, bins) or (B, frames, bins)")
+    tb = t if t.dim() == 3 else t.unsqueeze(0)
+    nb, F, K = tb.shape
+    if nb < 1 or F < 1 or K < 1:
+        raise ValueError(f"{what} has no signals, frames or bins")
+    return _stft_input(tb, ((F - 1) * max(tb.stride(1), K) + K, K))
+
+
+def welch_csd(X, Y, scale, *, nfft, onesided=True, outputs=("pxy",), out=None, workspace=None):
+    """Welch cross spectra behind the FFT (bhw_welch_csd_f32): X, Y complex64 (F, K) or (B, F, K), the FFTs of the segments of x and
+    of y.  One pass reads X and Y once and returns a dict with the `outputs` asked for, each (K,) or (B, K) as Y is: "pxy" complex64,
+    the averaged conj(X) * Y times scale (scipy.signal.csd's convention); "pxx", "pyy" float32, bit for bit welch_psd of X and of Y;
+    "coherence" float32, |sum conj(X) Y|^2 / (sum |X|^2 * sum |Y|^2); "h1" complex64, the transfer-function estimate P_xy / P_xx.
+    All come from the same four binary64 sums, in ascending f inside blocks of 256 frames and then over the blocks in order
+    (include/bhw.h writes the arithmetic down).  X of one signal -- (F, K) or (1, F, K) -- against Y of B signals is paired with
+    each of them.  onesided as welch_psd.  X and Y are read in place when their bins are contiguous and their rows apart, else
+    copied.  `out`: a dict by output name of tensors of the returned shape and dtype, last axis contiguous, all with the same row
+    stride (their gaps are left alone); `workspace`: float64, B * ceil(F / 256) * K * chains elements when F > 256 (chains = 2 for
+    "pxy" alone, else 4; allocated when not given)."""
+    torch = _torch()
+    if not isinstance(Y, torch.Tensor) or not Y.is_cuda:
+        raise ValueError("Y must be a complex64 CUDA tensor on the call's device")
+    dev = Y.device.index
+    mask = B.csd_mask(outputs)
+    names = [n for n in B.CSD_OUTPUTS if B.CSD_OUTPUTS[n][0] & mask]
+    Xb, Yb = _csd_operand(torch, X, "X", dev), _csd_operand(torch, Y, "Y", dev)
+    nb, F, K = Yb.shape
+    if X.dim() == 3 and Y.dim() == 2:
+        raise ValueError("a batched X (B, frames, bins) needs a batched Y")
+    if tuple(Xb.shape[1:]) != (F, K) or Xb.shape[0] not in (1, nb):
+        raise ValueError(f"X {tuple(X.shape)} and Y {tuple(Y.shape)} must have the same frames and bins, and X one signal or Y's {nb}")
+    bcast = Xb.shape[0] == 1 and nb > 1
+    nfft = int(nfft)
+    if onesided and K != nfft // 2 + 1:
+        raise ValueError(f"a one-sided spectrum of nfft {nfft} has {nfft // 2 + 1} bins, X and Y have {K}")
+    if K > nfft:
+        raise ValueError(f"X and Y have {K} bins, more than nfft {nfft}")
+    shape = (nb, K) if Y.dim() == 3 else (K,)
+    out = {} if out is None else out
+    if not isinstance(out, dict) or any(n not in names for n in out):
+        raise ValueError(f"out must be a dict of tensors by output name, within the outputs asked for {tuple(names)}")
+    res, o_stride = {}, None
+    for n in names:
+        dt = torch.complex64 if B.CSD_OUTPUTS[n][1] else torch.float32
+        t = out.get(n)
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.device != Y.device or tuple(t.shape) != shape or t.is_conj() or t.is_neg() \
+                or (K > 1 and t.stride(-1) != 1) or (t.dim() == 2 and nb > 1 and t.stride(0) < K):
+            raise ValueError(f"out[{n!r}] must be a {str(dt).replace('torch.', '')} tensor of shape {shape} on Y's device, contiguous along "
+                             "the bins, rows apart")
+        if t.dim() == 2 and nb > 1:
+            if o_stride not in (None, t.stride(0)):
+                raise ValueError("the tensors of out must have the same row stride (bhw_csd.o_stride is one number)")
+            o_stride = t.stride(0)
+        res[n] = t
+    for n in names:
+        if n not in res:
+            dt = torch.complex64 if B.CSD_OUTPUTS[n][1] else torch.float32
+            if o_stride in (None, K):
+                res[n] = torch.empty(shape, dtype=dt, device=Y.device)
+            else:
+                res[n] = torch.empty((nb, o_stride), dtype=dt, device=Y.device)[:, :K]
+    d = B.make_csd(nb, F, K, nfft, scale, outputs=names, onesided=onesided, broadcast_x=bcast,
+                   x_stride=Xb.stride(1) if F > 1 else 0, x_batch_stride=Xb.stride(0) if (nb > 1 and not bcast) else 0,
+                   y_stride=Yb.stride(1) if F > 1 else 0, y_batch_stride=Yb.stride(0) if nb > 1 else 0, o_stride=o_stride or 0)
+    need = int(B.lib().bhw_welch_csd_workspace_bytes(ctypes.byref(d))) // 8
+    if need and workspace is None:
+        workspace = torch.empty(need, dtype=torch.float64, device=Y.device)
+    elif need:
+        _check_out(torch, workspace, need, "workspace", torch.float64)
+    ptrs = [ctypes.c_void_p(res[n].data_ptr() if n in res else None) for n in B.CSD_OUTPUTS]
+    B.check(B.lib().bhw_welch_csd_f32(dev, _stream_ptr(torch, dev), ctypes.byref(d), ctypes.c_void_p(Xb.data_ptr()),
+                                      ctypes.c_void_p(Yb.data_ptr()), *ptrs, ctypes.c_void_p(workspace.data_ptr() if need else None),
+                                      need * 8))
+    return res
+
+
+def _cross(torch, params, x, y, fs, length, noverlap, nfft, detrend, return_onesided, scaling, shift, outputs, table, cache):
+    """The chain of csd / coherence / transfer_function / cross_spectra: (freqs, dict by output name)."""
+    for t, what in ((x, "x"), (y, "y")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"{what} must be a float32 or complex64 CUDA tensor")
+    dev = x.device.index if table is None else table.device
+    _stft_float(torch, x, "x", dev)
+    _stft_float(torch, y, "y", dev)
+    if x.dtype != y.dtype:
+        raise ValueError(f"x and y must have the same dtype, got {x.dtype} and {y.dtype}")
+    if x.dim() not in (1, 2) or y.dim() not in (1, 2):
+        raise ValueError("x and y must be (T,) or (B, T)")
+    if x.shape[-1] != y.shape[-1]:
+        raise ValueError(f"x and y must have the same length, got {x.shape[-1]} and {y.shape[-1]} (scipy zero-pads the shorter one; "
+                         "that is not built: pad or cut it yourself)")
+    if x.dim() == 2 and (y.dim() == 1 or x.shape[0] != y.shape[0]):
+        raise ValueError(f"x {tuple(x.shape)} against y {tuple(y.shape)}: x must be (T,) (paired with every signal of y) or have y's batch")
+    B.csd_mask(outputs)
+    if detrend not in ("constant", False, None):
+        raise ValueError(f"detrend must be 'constant' or False, got {detrend!r}")
+    if scaling not in ("density", "spectrum"):
+        raise ValueError(f"scaling must be 'density' or 'spectrum', got {scaling!r}")
+    L, T = int(length), x.shape[-1]
+    noverlap = L // 2 if noverlap is None else int(noverlap)
+    if not 0 <= noverlap < L:
+        raise ValueError("noverlap must be less than length")
+    nfft = L if nfft is None else int(nfft)
+    if nfft < L:
+        raise ValueError(f"nfft {nfft} must be at least the window length {L}")
+    if T < L or (y.dim() == 2 and y.shape[0] < 1):
+        raise ValueError(f"zero segments: T = {T} < length = {L}" if T < L else "zero signals")
+    hop = L - noverlap
+    frames = 1 + (T - L) // hop
+    sums = _window_sums(torch, params, L, True, shift, dev, None if table is None else table._live(), cache)
+    scale = B.welch_scale(sums, frames, fs, scaling)
+    # the segments of x and of y in one buffer, so that one FFT call transforms both
+    nx = x.shape[0] if x.dim() == 2 else 1
+    ny = y.shape[0] if y.dim() == 2 else 1
+    seg = torch.empty((nx + ny, frames, nfft), dtype=x.dtype, device=x.device)
+    handle = None if table is None else table._live()
+    _welch_frames(torch, params, x, L, hop, nfft, detrend, shift, seg[:nx] if x.dim() == 2 else seg[0], None, dev, handle)
+    _welch_frames(torch, params, y, L, hop, nfft, detrend, shift, seg[nx:] if y.dim() == 2 else seg[nx], None, dev, handle)
+    onesided = bool(return_onesided) and not seg.is_complex()
+    S = torch.fft.rfft(seg, dim=-1) if onesided else torch.fft.fft(seg, dim=-1)
+    res = welch_csd(S[:nx] if x.dim() == 2 else S[0], S[nx:] if y.dim() == 2 else S[nx], scale, nfft=nfft, onesided=onesided,
+                    outputs=outputs)
+    mk = torch.fft.rfftfreq if onesided else torch.fft.fftfreq
+    return mk(nfft, d=1.0 / float(fs), dtype=torch.float64, device=seg.device), res
+
+
+def cross_spectra(params, x, y, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", return_onesided=True, scaling="density",
+                  shift=None, outputs=("pxy", "pxx", "pyy", "coherence", "h1")):
+    """Every Welch cross-spectral estimate of (x, y) from one pass, scipy.signal.csd / coherence as the model: x and y (T,) or (B, T)
+    of the same length and dtype, float32 (one-sided, rfft) or complex64 (two-sided, fft); x (T,) against y (B, T) is paired with
+    every signal of y.  Both are cut, detrended, windowed and zero-padded as welch() does, into ONE buffer that one torch.fft call
+    transforms, and welch_csd reads the two spectra once: window_sums -> welch_frames(x), welch_frames(y) -> torch.fft -> welch_csd.
+    Returns (freqs float64, dict by output name: "pxy" = scipy's csd(x, y), "pxx" / "pyy" = welch(x) / welch(y), "coherence" =
+    scipy's coherence(x, y), "h1" = P_xy / P_xx).  The sums cache and the capture rule are welch()'s.  Signals of unequal length are a
+    ValueError (scipy zero-pads the shorter one)."""
+    return _cross(_torch(), params, x, y, fs, length, noverlap, nfft, detrend, return_onesided, scaling, shift, outputs, None, _SUMS_CACHE)
+
+
+def csd(params, x, y, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", return_onesided=True, scaling="density",
+        shift=None):
+    """Welch's cross power spectral density P_xy (scipy.signal.csd's convention, conj(X) * Y): cross_spectra() with outputs=("pxy",),
+    the two-chain kernel.  Returns (freqs float64, Pxy complex64 (..., K))."""
+    f, r = _cross(_torch(), params, x, y, fs, length, noverlap, nfft, detrend, return_onesided, scaling, shift, ("pxy",), None, _SUMS_CACHE)
+    return f, r["pxy"]
+
+
+def coherence(params, x, y, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", return_onesided=True, scaling="density",
+              shift=None):
+    """The magnitude-squared coherence |P_xy|^2 / (P_xx P_yy) of scipy.signal.coherence, from one pass over both spectra.  Returns
+    (freqs float64, Cxy float32 (..., K)); NaN in a bin where x or y has no power at all."""
+    f, r = _cross(_torch(), params, x, y, fs, length, noverlap, nfft, detrend, return_onesided, scaling, shift, ("coherence",), None,
+                  _SUMS_CACHE)
+    return f, r["coherence"]
+
+
+def transfer_function(params, x, y, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", return_onesided=True,
+                      scaling="density", shift=None):
+    """The H1 estimate P_xy / P_xx of the transfer function from x (the excitation) to y (the response).  Returns (freqs float64,
+    H1 complex64 (..., K))."""
+    f, r = _cross(_torch(), params, x, y, fs, length, noverlap, nfft, detrend, return_onesided, scaling, shift, ("h1",), None, _SUMS_CACHE)
+    return f, r["h1"]
 
 
 class ResidentTable:
@@ -804,6 +975,34 @@ class ResidentTable:
         one call the whole chain can be captured into a graph."""
         return _welch(_torch(), params, x, fs, length, noverlap, nfft, detrend, return_onesided, scaling, shift, average, self.device,
                       self._live(), self._sums)
+
+    def cross_spectra(self, params, x, y, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", return_onesided=True,
+                      scaling="density", shift=None, outputs=("pxy", "pxx", "pyy", "coherence", "h1")):
+        """cross_spectra() from this table.  The sums cache and the capture rule are welch()'s: after one warm call the chain can be
+        captured into a graph, a first call inside a capture raises."""
+        return _cross(_torch(), params, x, y, fs, length, noverlap, nfft, detrend, return_onesided, scaling, shift, outputs, self,
+                      self._sums)
+
+    def csd(self, params, x, y, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", return_onesided=True,
+            scaling="density", shift=None):
+        """csd() from this table."""
+        f, r = _cross(_torch(), params, x, y, fs, length, noverlap, nfft, detrend, return_onesided, scaling, shift, ("pxy",), self,
+                      self._sums)
+        return f, r["pxy"]
+
+    def coherence(self, params, x, y, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", return_onesided=True,
+                  scaling="density", shift=None):
+        """coherence() from this table."""
+        f, r = _cross(_torch(), params, x, y, fs, length, noverlap, nfft, detrend, return_onesided, scaling, shift, ("coherence",), self,
+                      self._sums)
+        return f, r["coherence"]
+
+    def transfer_function(self, params, x, y, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", return_onesided=True,
+                          scaling="density", shift=None):
+        """transfer_function() from this table."""
+        f, r = _cross(_torch(), params, x, y, fs, length, noverlap, nfft, detrend, return_onesided, scaling, shift, ("h1",), self,
+                      self._sums)
+        return f, r["h1"]
 
     def generate_part(self, params, part, n_parts, window):
         """Interleaved ownership part `part` of `n_parts` into the full-length `window` (bhw_generate_part_from_table)."""

@@ -604,6 +604,70 @@ int bhw_welch_psd_f32(int device, void *hip_stream, const bhw_psd *d, const floa
 int bhw_describe_welch(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const bhw_psd *d,
                        char *buf, uint64_t len);
 
+/* Welch cross spectra (scipy.signal.csd / coherence as the model): the pass behind the FFT for TWO signals.  d_X, d_Y: complex64
+ * (B, F, K) as interleaved float pairs, 8-byte aligned, the FFTs of the segments of x and of y (bhw_welch_frames_f32_* of each);
+ * same B, F, K, each with its own frame and batch strides in complex elements (0 = packed).  X and Y are each read exactly once, with
+ * nontemporal loads, and every requested output comes from the same four binary64 sums.  Per signal b and bin k, over the frames f,
+ * with (xr, xi) = X[b, f, k] and (yr, yi) = Y[b, f, k] converted to binary64:
+ *        xx_f = xr * xr + xi * xi          yy_f = yr * yr + yi * yi                (the q_f of the periodogram, for X and for Y)
+ *        re_f = xr * yr + xi * yi          im_f = xr * yi - xi * yr                (conj(X) * Y: scipy's convention)
+ *    Every product of two float32 values is exact in binary64, so each of the four is ONE rounding, and a fused multiply-add gives
+ *    the same value.  Each of the four is summed exactly as the periodogram sums q_f: ascending f inside blocks of BHW_WELCH_BLOCK
+ *    frames from +0.0, then the block sums in ascending block order from +0.0.  Call the sums S_xx, S_yy, C_re, C_im, and let
+ *    s_k = scale * (doubled(k) ? 2 : 1) with the periodogram's doubled(k) under BHW_CSD_ONESIDED.  rn() is one binary64 rounding:
+ *        BHW_CSD_PXY         d_Pxy, complex64 (B, K):  (fl32(C_re * s_k), fl32(C_im * s_k))
+ *        BHW_CSD_PXX / PYY   d_Pxx / d_Pyy, float32 (B, K):  fl32(S_xx * s_k) / fl32(S_yy * s_k) -- bit for bit what bhw_welch_psd_f32
+ *                            gives for X (for Y) with the same descriptor fields
+ *        BHW_CSD_COHERENCE   d_Cxy, float32 (B, K):  n = rn(C_re * C_re), m = rn(C_im * C_im), num = rn(n + m), den = rn(S_xx * S_yy),
+ *                            fl32(rn(num / den)): a correctly rounded division and NO fused operation (n + m is never contracted into
+ *                            a multiply-add); the scale cancels and is not applied
+ *        BHW_CSD_H1          d_H1, complex64 (B, K):  (fl32(rn(C_re / S_xx)), fl32(rn(C_im / S_xx))): the H1 estimate P_xy / P_xx
+ *    IEEE throughout, no special cases: an all-zero bin gives the coherence 0 / 0 = NaN (as scipy does), a NaN or an infinity in a frame
+ *    poisons that (signal, bin) and no other.  For finite float32 spectra den neither overflows nor underflows to zero (every q_f is
+ *    below 2^257, a sum of at most 2^34 of them below 2^291, the product below 2^582; a non-zero sum is at least 2^-298), so a NaN
+ *    coherence means a zero or a non-finite bin.
+ *    Any non-empty subset of the five outputs may be asked for in one call; a pointer whose flag is not set is neither read nor written.
+ *    Output row b is at b * o_stride elements of the output's own type (one stride for all outputs); only the K elements of a row are
+ *    written.  BHW_CSD_BROADCAST_X: X holds ONE signal (F, K), paired with each of Y's B signals (one excitation, many responses); the
+ *    X side of every output is then the same in every row and is still written per row.  X is only read.
+ *    With more than one block the block sums go through a caller workspace of bhw_welch_csd_workspace_bytes bytes
+ *    (B * ceil(F / BLOCK) * K * chains doubles, chains = 2 when BHW_CSD_PXY is the only output and 4 otherwise; 0 for one block) and a
+ *    second launch adds them in block order: no float atomics.  The call allocates nothing, neither synchronises nor reads back, and can
+ *    be captured.
+ *    Checks before any HIP call (BHW_ERR_BADARG unless noted): for X and for Y everything bhw_welch_psd_f32 checks for its operand
+ *    (descriptor, struct_size, reserved, sizes, BHW_CSD_ONESIDED with bins != n_fft / 2 + 1, scale, strides that make rows overlap,
+ *    B * F * K above 2^34, the workgroup bound, alignment), plus: unknown flags, an empty output mask, a NULL or misaligned pointer of
+ *    a requested output (8 bytes for the complex ones, 4 for the others), o_stride < K, an output that overlaps an input, another
+ *    requested output or the workspace, x_batch_stride != 0 under BHW_CSD_BROADCAST_X, a missing or misaligned workspace when one is
+ *    needed, a short one (BHW_ERR_WORKSPACE).
+ *  - bhw_describe_csd: one line naming the form, the plan and the kernels.  Host arithmetic only. */
+#define BHW_CSD_ONESIDED 1u
+#define BHW_CSD_BROADCAST_X 2u
+#define BHW_CSD_PXY 0x10u
+#define BHW_CSD_PXX 0x20u
+#define BHW_CSD_PYY 0x40u
+#define BHW_CSD_COHERENCE 0x80u
+#define BHW_CSD_H1 0x100u
+typedef struct bhw_csd {
+    uint32_t struct_size;     /* sizeof(bhw_csd) = 96                                             */
+    uint32_t flags;           /* BHW_CSD_ONESIDED, BHW_CSD_BROADCAST_X, and the output mask       */
+    uint64_t batch;           /* B >= 1: the signals of Y (and of X without BHW_CSD_BROADCAST_X)  */
+    uint64_t frames;          /* F >= 1: the rows averaged                                        */
+    uint64_t bins;            /* K >= 1: n_fft / 2 + 1 (rfft) or n_fft (fft)                      */
+    uint64_t n_fft;           /* for doubled(k)                                                   */
+    uint64_t x_stride;        /* complex elements between frames of X; 0 = K                      */
+    uint64_t x_batch_stride;  /* between signals of X; 0 = frames * x_stride (broadcast: must be 0) */
+    uint64_t y_stride;        /* complex elements between frames of Y; 0 = K                      */
+    uint64_t y_batch_stride;  /* between signals of Y; 0 = frames * y_stride                      */
+    uint64_t o_stride;        /* elements between the rows of every output; 0 = K                 */
+    double   scale;           /* as bhw_psd.scale                                                 */
+    uint64_t reserved;        /* 0                                                                */
+} bhw_csd;
+uint64_t bhw_welch_csd_workspace_bytes(const bhw_csd *d);
+int bhw_welch_csd_f32(int device, void *hip_stream, const bhw_csd *d, const float *d_X, const float *d_Y, float *d_Pxy, float *d_Pxx,
+                      float *d_Pyy, float *d_Cxy, float *d_H1, void *workspace, uint64_t workspace_bytes);
+int bhw_describe_csd(const bhw_csd *d, char *buf, uint64_t len);
+
 /* Threading: every entry point may be called from any host thread.  Calls that use the library-owned scratch of one
  * (device, stream) are serialised against each other for the duration of their launches (the table is rebuilt per call);
  * callers that pass their own bhw_exec.workspace must not share one workspace between concurrent calls.  The calling
