@@ -44,6 +44,7 @@ ABI_SYMBOLS = (
     "bhw_window_sums_device", "bhw_window_sums_from_table", "bhw_welch_workspace_bytes", "bhw_welch_frames_f32_device",
     "bhw_welch_frames_f32_from_table", "bhw_welch_psd_workspace_bytes", "bhw_welch_psd_f32", "bhw_describe_welch",
     "bhw_welch_csd_workspace_bytes", "bhw_welch_csd_f32", "bhw_describe_csd",
+    "bhw_stft_fft_f32_device", "bhw_stft_fft_f32_from_table", "bhw_describe_stft_fft",
 )
 
 
@@ -287,6 +288,9 @@ def lib():
     L.bhw_welch_csd_workspace_bytes.argtypes = [X]
     L.bhw_welch_csd_f32.argtypes = [ci, vp, X, f32p, f32p, f32p, f32p, f32p, f32p, f32p, vp, u64]
     L.bhw_describe_csd.argtypes = [X, ctypes.c_char_p, u64]
+    L.bhw_stft_fft_f32_device.argtypes = [P, u64, ci, vp, S, u32, f32p, f32p]
+    L.bhw_stft_fft_f32_from_table.argtypes = [T, P, u64, vp, S, u32, f32p, f32p]
+    L.bhw_describe_stft_fft.argtypes = [T, P, u64, S, u32, ctypes.c_char_p, u64]
     PA = ctypes.POINTER(BhwAtan2Params)
     L.bhw_atan2_device.argtypes = [PA, ci, vp, u64, i32p, i32p, i32p]
     L.bhw_atan2_to_host.argtypes = [PA, ci, u64, i32p, i32p, i32p]
@@ -396,6 +400,25 @@ def describe_csd(csd):
     descriptor `csd` (a BhwCsd, make_csd).  Host arithmetic only."""
     buf = ctypes.create_string_buffer(1024)
     check(lib().bhw_describe_csd(ctypes.byref(csd), buf, len(buf)))
+    return buf.value.decode()
+
+
+FFT_MIN_N, FFT_MAX_N = 16, 4096          # n_fft of the fused window + FFT calls: a power of two in this range
+
+
+def fft_supported(n_fft):
+    """True where bhw_stft_fft_f32_* take n_fft: a power of two in 16..4096."""
+    n_fft = int(n_fft)
+    return FFT_MIN_N <= n_fft <= FFT_MAX_N and n_fft & (n_fft - 1) == 0
+
+
+def describe_stft_fft(params, length, stft, *, detrend=False, table=None):
+    """One line: the route, the plan (lanes per row, rows per workgroup, radix schedule, LDS, grid) and the kernel of a fused window +
+    FFT call over the window of `length`, for the descriptor `stft` (a BhwStft, make_stft; its y strides count floats of spectrum
+    rows) (bhw_describe_stft_fft).  `table` is a resident table handle or None for the library call.  Host arithmetic only."""
+    buf = ctypes.create_string_buffer(768)
+    check(lib().bhw_describe_stft_fft(table, ctypes.byref(params), int(length), ctypes.byref(stft),
+                                      WELCH_DETREND_CONSTANT if detrend else 0, buf, len(buf)))
     return buf.value.decode()
 
 

@@ -1128,6 +1128,19 @@ int istft_ola_run(bhw_table t, const bhw_params *p, uint64_t length, int device,
                                                          const BhwLenPhase *lp) { return bhwk_ola_f32(l, c, w, pl, &o, norm, rows, d_x, tab, lp, bt); });
 }
 
+// The fused window + FFT (t NULL: the direct CORDIC chains): the checks, then the one kernel.
+int stft_fft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *s, uint32_t flags,
+                 const float *d_x, float *d_Y)
+{
+    int rc = bhwp_stft_fft_checks(p, length, s, flags, d_x, d_Y);
+    if (!rc && t) rc = table_call_checks(t, p);
+    if (rc || !s->frames) return rc;
+    const BhwStftFftPlan pl = bhwp_stft_fft_plan(p, length, s, flags, t != nullptr);
+    const char *what = t ? "stft fft launch (resident table)" : "stft fft launch";
+    return run_source(t, p, length, device, stream, what, [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *tab,
+                                                              const BhwLenPhase *lp) { return bhwk_stft_fft_f32(l, c, w, pl, s, d_x, d_Y, tab, *lp); });
+}
+
 // The window sums (t NULL: the direct CORDIC chains): the checks, then the memset of the four words and the reduction.
 int window_sums_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, uint32_t flags, uint64_t *d_sums)
 {
@@ -1303,6 +1316,29 @@ int bhw_describe_stft(bhw_table t, const bhw_params *p, uint64_t length, const b
     if (!rc && t) rc = table_call_checks(t, p);
     if (!rc) rc = bhwp_stft_checks(p, length, s, inverse != 0, flags, nullptr, nullptr, false);
     return rc ? rc : bhwp_describe_stft(p, t ? &t->c : nullptr, length, s, inverse != 0, flags, buf, len);
+}
+
+// ---- fused window and real FFT (include/bhw.h: bhw_stft_fft_f32_device ...) ------------------------------------------------------------
+
+int bhw_stft_fft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                            const float *d_x, float *d_Y)
+{
+    return stft_fft_run(nullptr, p, length, device, hip_stream, s, flags, d_x, d_Y);
+}
+
+int bhw_stft_fft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                const float *d_x, float *d_Y)
+{
+    const int rc = bhwp_stft_fft_checks(p, length, s, flags, d_x, d_Y);
+    if (rc) return rc;
+    return t ? stft_fft_run(t, p, length, t->device, hip_stream, s, flags, d_x, d_Y) : fail(BHW_ERR_BADARG, "table is NULL");
+}
+
+int bhw_describe_stft_fft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf, uint64_t len)
+{
+    int rc = bhwp_stft_fft_checks(p, length, s, flags, nullptr, nullptr, false);
+    if (!rc && t) rc = table_call_checks(t, p);
+    return rc ? rc : bhwp_describe_stft_fft(p, t ? &t->c : nullptr, length, s, flags, buf, len);
 }
 
 // ---- Welch's method (include/bhw.h: bhw_window_sums_device ...) ------------------------------------------------------------------------

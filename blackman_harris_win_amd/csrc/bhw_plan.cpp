@@ -1515,6 +1515,113 @@ int bhwp_describe_csd(const bhw_csd *d, char *buf, uint64_t len)
     return BHW_OK;
 }
 
+// ---- fused window and real FFT -------------------------------------------------------------------------------------------------------------
+
+int bhwp_stft_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const void *d_x, const void *d_Y,
+                         bool pointers)
+{
+    int rc = bhwp_f32_checks(p, length, 0);
+    if (rc) return rc;
+    if (flags & ~BHW_WELCH_DETREND_CONSTANT) return bhwp_fail(BHW_ERR_BADARG, "flags 0x%x (0 or BHW_WELCH_DETREND_CONSTANT)", flags);
+    if (!s) return bhwp_fail(BHW_ERR_BADARG, "stft descriptor is NULL");
+    if (s->struct_size != sizeof(bhw_stft)) return bhwp_fail(BHW_ERR_BADARG, "bhw_stft.struct_size %u != %zu", s->struct_size, sizeof(bhw_stft));
+    // what the frames or the segments call checks, for the same descriptor with packed rows (the output strides mean something else
+    // here and are checked below)
+    bhw_stft t = *s;
+    t.y_stride = t.y_batch_stride = 0;
+    const bool segments = (flags & BHW_WELCH_DETREND_CONSTANT) || (!s->pad && !s->col0 && !s->pad_mode);
+    if (segments) rc = bhwp_welch_checks(p, length, &t, flags, nullptr, nullptr, nullptr, 0, false);
+    else          rc = bhwp_stft_checks(p, length, &t, false, 0, nullptr, nullptr, false);
+    if (rc) return rc;
+    if (s->channels != 1) return bhwp_fail(BHW_ERR_UNSUPPORTED, "channels %u: the fused FFT takes real input (1)", s->channels);
+    if ((s->n_fft & (s->n_fft - 1)) || s->n_fft < (1ull << kFftMinLog) || s->n_fft > (1ull << kFftMaxLog))
+        return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu: the fused FFT takes a power of two in %u..%u", (unsigned long long)s->n_fft,
+                         1u << kFftMinLog, 1u << kFftMaxLog);
+    const uint64_t T = s->samples, F = s->frames, K2 = s->n_fft + 2;          // 2K floats of a spectrum row
+    if (!F) return BHW_OK;
+    if ((unsigned __int128)s->batch * F * (K2 / 2) > (1ull << 34)) return bhwp_fail(BHW_ERR_BADARG, "batch * frames * K above 2^34 per call");
+    if (s->y_stride && (s->y_stride < K2 || s->y_stride % 2))
+        return bhwp_fail(BHW_ERR_BADARG, "y_stride %llu: at least 2 * K = %llu floats, and even", (unsigned long long)s->y_stride,
+                         (unsigned long long)K2);
+    const uint64_t ys = s->y_stride ? s->y_stride : K2;
+    const unsigned __int128 ysig = (unsigned __int128)(F - 1) * ys + K2;
+    if (ysig > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "Y extent beyond 2^60 elements");
+    if (s->y_batch_stride && (s->y_batch_stride < (uint64_t)ysig || s->y_batch_stride % 2))
+        return bhwp_fail(BHW_ERR_BADARG, "y_batch_stride %llu: at least (frames - 1) * y_stride + 2 * K = %llu floats, and even",
+                         (unsigned long long)s->y_batch_stride, (unsigned long long)ysig);
+    if (!pointers) return BHW_OK;
+    if (!d_x || !d_Y) return bhwp_fail(BHW_ERR_BADARG, "d_x / d_Y is NULL");
+    if ((uintptr_t)d_Y % 8) return bhwp_fail(BHW_ERR_BADARG, "d_Y is not 8-byte aligned");
+    if ((uintptr_t)d_x % 4) return bhwp_fail(BHW_ERR_BADARG, "d_x is not 4-byte aligned");
+    const uint64_t xs = s->x_stride ? s->x_stride : T, ybs = s->y_batch_stride ? s->y_batch_stride : F * ys;
+    const unsigned __int128 xe = (unsigned __int128)(s->batch - 1) * xs + T, ye = (unsigned __int128)(s->batch - 1) * ybs + ysig;
+    if (xe > (1ull << 60) || ye > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "x or Y extent beyond 2^60 elements");
+    const uint64_t xa = (uint64_t)(uintptr_t)d_x, ya = (uint64_t)(uintptr_t)d_Y, xb = (uint64_t)xe * 4u, yb = (uint64_t)ye * 4u;
+    if (xa > UINT64_MAX - xb || ya > UINT64_MAX - yb) return bhwp_fail(BHW_ERR_BADARG, "x or Y range wraps the address space");
+    if (xa < ya + yb && ya < xa + xb) return bhwp_fail(BHW_ERR_BADARG, "d_x and d_Y overlap");
+    return BHW_OK;
+}
+
+BhwStftFftPlan bhwp_stft_fft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, bool from_table)
+{
+    (void)p;
+    BhwStftFftPlan pl{};
+    pl.route = from_table ? BHWP_FRAMES_TABLE : BHWP_FRAMES_DIRECT;
+    pl.detrend = (flags & BHW_WELCH_DETREND_CONSTANT) != 0;
+    pl.len = length;
+    while ((1ull << pl.log2n) < s->n_fft) ++pl.log2n;
+    pl.m = (uint32_t)(s->n_fft / 2);
+    const uint32_t quarter = pl.m / 4 < 4 ? 4 : pl.m / 4;
+    pl.lpf = quarter < kFftBlock ? quarter : kFftBlock;
+    pl.fy = kFftBlock / pl.lpf;
+    pl.cpl = (uint32_t)(s->n_fft / pl.lpf);
+    pl.radix4 = (pl.log2n - 1) / 2;
+    pl.radix2 = (pl.log2n - 1) % 2;
+    pl.lds_bytes = 2u * pl.fy * pl.m * 8u + pl.m * 8u + pl.fy * 4u;
+    pl.x_stride = s->x_stride ? s->x_stride : s->samples;
+    pl.y_stride = s->y_stride ? s->y_stride : s->n_fft + 2;
+    pl.y_bstride = s->y_batch_stride ? s->y_batch_stride : s->frames * pl.y_stride;
+    pl.rows = s->batch * s->frames;
+    pl.groups = (pl.rows + pl.fy - 1) / pl.fy;
+    pl.grid = pl.groups < kFftMaxGrid ? pl.groups : kFftMaxGrid;
+    return pl;
+}
+
+void bhwp_stft_fft_schedule(const BhwStftFftPlan &pl, char *buf, uint64_t len)
+{
+    if (!buf || !len) return;
+    buf[0] = 0;
+    for (uint32_t i = 0; i < pl.radix4 + pl.radix2; ++i) {
+        const size_t at = strlen(buf);
+        snprintf(buf + at, len - at, "%s%d", i ? "x" : "", i < pl.radix4 ? 4 : 2);
+    }
+}
+
+int bhwp_describe_stft_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf,
+                           uint64_t len)
+{
+    if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
+    const char *route = ct ? "table" : "direct";
+    const BhwStftFftPlan pl = bhwp_stft_fft_plan(p, length, s, flags, ct != nullptr);
+    const char *pad = s->pad_mode == BHW_PAD_REFLECT ? "reflect" : "constant";
+    const char *det = pl.detrend ? "constant detrend" : "no detrending";
+    if (!s->frames) {
+        snprintf(buf, len, "stft fft %s (L = %llu, n_fft %llu, %s): nothing (frames 0)", route, (unsigned long long)length,
+                 (unsigned long long)s->n_fft, det);
+        return BHW_OK;
+    }
+    char kern[64], sched[48];
+    kernel_name(p, ct, "k_stft_fft_direct", "k_stft_fft_table", false, kern, sizeof kern);
+    bhwp_stft_fft_schedule(pl, sched, sizeof sched);
+    snprintf(buf, len, "stft fft %s (L = %llu, n_fft %llu, col0 %llu, pad %llu %s, %s): %s, %llu signals x %llu frames = %llu rows, "
+             "complex FFT of %u points in passes %s + split, %u lanes per row x %u rows per workgroup, %u columns per lane, %llu groups, "
+             "grid %llu x %u lanes, %u bytes of LDS", route, (unsigned long long)length, (unsigned long long)s->n_fft,
+             (unsigned long long)s->col0, (unsigned long long)s->pad, pad, det, kern, (unsigned long long)s->batch,
+             (unsigned long long)s->frames, (unsigned long long)pl.rows, pl.m, sched, pl.lpf, pl.fy, pl.cpl, (unsigned long long)pl.groups,
+             (unsigned long long)pl.grid, kFftBlock, pl.lds_bytes);
+    return BHW_OK;
+}
+
 // ---- the pure entry points of the C ABI (include/bhw.h) -------------------------------------------------------------------------------
 extern "C" {
 

@@ -415,6 +415,47 @@ int  bhwp_describe_csd(const bhw_csd *d, char *buf, uint64_t len);
 int  bhwk_welch_csd_f32(const BhwLaunch &l, const BhwCsdPlan &pl, const bhw_csd *d, const float *d_X, const float *d_Y, float *const *outs,
                         double *d_ws);
 
+// ---- fused window and real FFT (bhw_stft_fft_f32_*; bhw_stft_fft.hip) ---------------------------------------------------------------
+// A workgroup of kFftBlock lanes owns whole rows.  M = n_fft / 2 complex points per row (the real row taken as pairs); lpf lanes work
+// on a row (one radix-4 butterfly per lane and pass up to M = 1024), fy = kFftBlock / lpf rows side by side; a lane holds cpl =
+// n_fft / lpf columns of its row (column c * lpf + lane) and their window coefficients in registers.  The rows (b, f) of the batch are
+// one pool cut into groups of fy consecutive rows; workgroup w takes the groups w, w + grid, ... (the last group may be ragged).
+// LDS: two buffers of fy * M complex64 (Stockham ping-pong; the first also stages the window and the raw row of the detrend mean), the
+// n_fft / 2 twiddles exp(-2 pi i k / n_fft) and fy means.
+constexpr uint32_t kFftBlock = 256;
+constexpr uint32_t kFftMinLog = 4, kFftMaxLog = 12;   // n_fft = 2^4 .. 2^12
+constexpr uint32_t kFftMaxCpl = 16;                   // columns of one lane at most (n_fft 4096 on 256 lanes)
+constexpr uint32_t kFftMaxGrid = 2048;                // workgroups at most: the window and the twiddles are computed once per workgroup
+struct BhwStftFftPlan {
+    int route;            // BHWP_FRAMES_DIRECT or BHWP_FRAMES_TABLE
+    bool detrend;
+    uint32_t log2n;       // n_fft = 2^log2n
+    uint32_t m;           // M = n_fft / 2
+    uint32_t lpf;         // lanes per row: min(kFftBlock, max(4, M / 4))
+    uint32_t fy;          // rows side by side: kFftBlock / lpf
+    uint32_t cpl;         // columns per lane: n_fft / lpf (4, 8 or 16)
+    uint32_t radix4;      // radix-4 passes: floor(log2(M) / 2)
+    uint32_t radix2;      // 1: a last radix-2 pass (log2(M) odd)
+    uint32_t lds_bytes;   // 2 * fy * M * 8 + M * 8 + fy * 4  (<= 64 KiB)
+    uint64_t rows;        // B * frames
+    uint64_t groups;      // ceil(rows / fy)
+    uint64_t grid;        // min(groups, kFftMaxGrid)
+    uint64_t x_stride, y_stride, y_bstride;   // resolved (0 -> T, 2K, frames * y_stride)
+    uint64_t len;         // L
+};
+// Every check of the two calls that needs no table handle, before any HIP call (include/bhw.h).  frames 0 passes with the pointers
+// unchecked; `pointers` false: the describe call.
+int  bhwp_stft_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const void *d_x, const void *d_Y,
+                          bool pointers = true);
+// the plan of a call that passed the checks (frames 0: rows, groups and grid are 0)
+BhwStftFftPlan bhwp_stft_fft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, bool from_table);
+// the radix schedule as text, "4x4x4x2"
+void bhwp_stft_fft_schedule(const BhwStftFftPlan &pl, char *buf, uint64_t len);
+int  bhwp_describe_stft_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf,
+                            uint64_t len);
+int  bhwk_stft_fft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwStftFftPlan &pl, const bhw_stft *s,
+                       const float *d_x, float *d_Y, const int32_t *d_table, const BhwLenPhase &lp);
+
 // the generate kernel of a window of any length (bhw_len.hip): d_table NULL = k_direct_len, else k_range_len over the resident table of c
 int  bhwk_len_range(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *d_table, const BhwLenPhase &lp,
                     uint64_t n0, uint64_t count, int32_t *d_out);

@@ -450,6 +450,127 @@ def istft_overlap_add(params, y, n_fft, hop, *, win_length=None, center=True, le
     return out
 
 
+# ---- fused window and real FFT: the spectrum rows in one launch ---------------------------------------------------------------------------
+
+def _fft_check(fft, what="fft"):
+    if fft not in ("torch", "fused"):
+        raise ValueError(f"{what} must be 'torch' or 'fused', got {fft!r}")
+    return fft == "fused"
+
+
+def _fft_input(torch, x, n_fft, dev):
+    """The checks every fused call makes on (x, n_fft): real float32 (T,) or (B, T) on `dev`, n_fft a supported power of two."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.device.index != dev:
+        raise ValueError("x must be a float32 CUDA tensor on the call's device")
+    if x.dtype != torch.float32:
+        raise ValueError(f"the fused FFT takes real float32 input, got {x.dtype} (complex input: fft='torch' / stft_frames + torch.fft)")
+    if x.dim() not in (1, 2):
+        raise ValueError("x must be (T,) or (B, T)")
+    if not B.fft_supported(n_fft):
+        raise ValueError(f"the fused FFT takes n_fft a power of two in {B.FFT_MIN_N}..{B.FFT_MAX_N}, got {int(n_fft)}")
+
+
+def _fft_out(torch, out, shape, x):
+    """The spectrum tensor and its strides in floats: allocated packed, or the caller's complex64 `out` of `shape` (bins contiguous,
+    rows and signals apart; the gaps of a wider buffer are left alone)."""
+    nb, F, K = shape[-3] if len(shape) == 3 else 1, shape[-2], shape[-1]
+    if out is None:
+        return torch.empty(shape, dtype=torch.complex64, device=x.device), 0, 0
+    ok = isinstance(out, torch.Tensor) and out.dtype == torch.complex64 and out.device == x.device and tuple(out.shape) == tuple(shape) \
+        and not out.is_conj() and not out.is_neg() and out.stride(-1) == 1
+    if ok and F > 1:
+        ok = out.stride(-2) >= K
+    if ok and len(shape) == 3 and nb > 1:
+        ok = out.stride(0) >= (F - 1) * (out.stride(-2) if F > 1 else K) + K
+    if not ok:
+        raise ValueError(f"out must be a complex64 tensor of shape {tuple(shape)} on x's device, contiguous along the bins, rows and signals apart")
+    return out, (out.stride(-2) * 2 if F > 1 else 0), (out.stride(0) * 2 if len(shape) == 3 and nb > 1 else 0)
+
+
+def _fft_launch(torch, params, L, s, flags, xr, out, dev, table):
+    tail = (ctypes.byref(s), flags, ctypes.c_void_p(xr.data_ptr()), ctypes.c_void_p(out.data_ptr()))
+    if table is None:
+        B.check(B.lib().bhw_stft_fft_f32_device(ctypes.byref(params), L, dev, _stream_ptr(torch, dev), *tail))
+    else:
+        B.check(B.lib().bhw_stft_fft_f32_from_table(table, ctypes.byref(params), L, _stream_ptr(torch, dev), *tail))
+    return out
+
+
+def _stft(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, shift, out, dev, table):
+    n_fft, L, col0 = _stft_window(params, n_fft, win_length)
+    _fft_input(torch, x, n_fft, dev)
+    hop = int(hop)
+    if hop < 1:
+        raise ValueError("hop must be >= 1")
+    if pad_mode not in _PAD_MODES:
+        raise ValueError(f"pad_mode must be 'reflect' or 'constant', got {pad_mode!r}")
+    xb = x if x.dim() == 2 else x.unsqueeze(0)
+    nb, T = xb.shape
+    if detrend:
+        if center:
+            raise ValueError("detrend=True forms Welch segments (no padding, the window at column 0): pass center=False")
+        pad, col0, mode, reach = 0, 0, 0, L
+    else:
+        pad, mode = (n_fft // 2 if center else 0), _PAD_MODES[pad_mode]
+        reach = n_fft
+        if pad and pad_mode == "reflect" and pad >= T:
+            raise ValueError(f"reflect padding needs pad {pad} < T = {T} (n_fft // 2 < the signal's length)")
+    if nb < 1 or T + 2 * pad < reach:
+        raise ValueError(f"zero frames: T + 2 * pad = {T + 2 * pad} < {reach}" if nb else "zero signals")
+    frames = 1 + (T + 2 * pad - reach) // hop
+    xb = _stft_input(xb, (T,))
+    K = n_fft // 2 + 1
+    out, ys, ybs = _fft_out(torch, out, (nb, frames, K) if x.dim() == 2 else (frames, K), x)
+    shift = params.dat_width - 1 if shift is None else int(shift)
+    s = B.make_stft(nb, T, frames, hop, n_fft, col0=col0, pad=pad, pad_mode=mode, shift=shift,
+                    x_stride=xb.stride(0) if nb > 1 else 0, y_stride=ys, y_batch_stride=ybs)
+    return _fft_launch(torch, params, L, s, B.WELCH_DETREND_CONSTANT if detrend else 0, xb, out, dev, table)
+
+
+def stft(params, x, n_fft, hop, *, win_length=None, center=True, pad_mode="reflect", detrend=False, shift=None, out=None):
+    """The short-time Fourier transform of a batch in ONE launch (bhw_stft_fft_f32_device): x (T,) or (B, T), real float32, framed
+    and windowed exactly as stft_frames() does (center, pad_mode, the window of win_length centred in an n_fft row) and transformed
+    in the same kernel by a float32 FFT in LDS, so neither the windowed frames nor a second pass over x ever reach memory.  Returns
+    complex64 (B, F, K) or (F, K) for 1-D x, K = n_fft // 2 + 1, with torch.fft.rfft's sign and no scaling; `.transpose(-1, -2)` of
+    it is the layout of torch.stft(x, n_fft, hop, win_length, window=v, center=center, pad_mode=pad_mode, return_complex=True).
+    detrend=True (needs center=False) forms scipy's Welch segments instead: no padding, frames = 1 + (T - win_length) // hop, each
+    frame's mean removed (the fixed-order binary64 sum of welch_frames), the window at column 0 and zeros up to n_fft.  n_fft: a
+    power of two in 16..4096 (ValueError otherwise; complex x too).  The rows the FFT sees are bit for bit those of stft_frames /
+    welch_frames; the FFT itself is accurate to a float32 FFT's error, not pinned bit for bit.  `out`: complex64 of the returned
+    shape, bins contiguous, rows and signals apart (its gaps are left alone)."""
+    torch = _torch()
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise ValueError("x must be a float32 CUDA tensor")
+    return _stft(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, shift, out, x.device.index, None)
+
+
+def _welch_fft(torch, params, x, length, hop, nfft, detrend, shift, out, dev, table):
+    """The one-sided spectra of the Welch segments of x by the fused kernel: (B, frames, K) or (frames, K) complex64, into `out`
+    (a packed complex64 tensor of that shape) when given."""
+    L, hop = int(length), int(hop)
+    nfft = L if nfft is None else int(nfft)
+    _fft_input(torch, x, nfft, dev)
+    if hop < 1:
+        raise ValueError("hop must be >= 1 (noverlap < length)")
+    if not 1 <= L <= 1 << params.phi_width:
+        raise ValueError(f"length {L} outside 1..2^phi_width = {1 << params.phi_width}")
+    if nfft < L:
+        raise ValueError(f"nfft {nfft} must be at least the window length {L}")
+    if detrend not in ("constant", False, None):
+        raise ValueError(f"detrend must be 'constant' or False, got {detrend!r}")
+    xb = x if x.dim() == 2 else x.unsqueeze(0)
+    nb, T = xb.shape
+    if nb < 1 or T < L:
+        raise ValueError(f"zero segments: T = {T} < length = {L}" if nb else "zero signals")
+    frames = 1 + (T - L) // hop
+    xb = _stft_input(xb, (T,))
+    K = nfft // 2 + 1
+    out, ys, ybs = _fft_out(torch, out, (nb, frames, K) if x.dim() == 2 else (frames, K), x)
+    shift = params.dat_width - 1 if shift is None else int(shift)
+    s = B.make_stft(nb, T, frames, hop, nfft, shift=shift, x_stride=xb.stride(0) if nb > 1 else 0, y_stride=ys, y_batch_stride=ybs)
+    return _fft_launch(torch, params, L, s, B.WELCH_DETREND_CONSTANT if detrend == "constant" else 0, xb, out, dev, table)
+
+
 # ---- Welch's method around the FFT: window sums, detrended segments, averaged periodogram ----------------------------------------------
 
 _SUMS_CACHE = {}        # (params bytes, length, shift, f32) -> the numbers of window_sums (library form; a ResidentTable keeps its own)
@@ -595,7 +716,9 @@ def welch_psd(Y, scale, *, nfft, onesided=True, out=None, workspace=None):
     return out
 
 
-def _welch(torch, params, x, fs, length, noverlap, nfft, detrend, return_onesided, scaling, shift, average, dev, table, cache):
+def _welch(torch, params, x, fs, length, noverlap, nfft, detrend, return_onesided, scaling, shift, average, dev, table, cache,
+           fft="torch"):
+    fused = _fft_check(fft)
     if average != "mean":
         raise ValueError("only average='mean' is built (the median needs the periodograms kept)")
     if detrend not in ("constant", False, None):
@@ -607,6 +730,13 @@ def _welch(torch, params, x, fs, length, noverlap, nfft, detrend, return_oneside
     if not 0 <= noverlap < L:
         raise ValueError("noverlap must be less than length")
     nfft = L if nfft is None else int(nfft)
+    if fused:
+        if not return_onesided:
+            raise ValueError("fft='fused' gives the one-sided spectrum only (return_onesided=False: fft='torch')")
+        Y = _welch_fft(torch, params, x, L, L - noverlap, nfft, detrend, shift, None, dev, table)
+        sums = _window_sums(torch, params, L, True, shift, dev, table, cache)
+        P = welch_psd(Y, B.welch_scale(sums, Y.shape[-2], fs, scaling), nfft=nfft, onesided=True)
+        return torch.fft.rfftfreq(nfft, d=1.0 / float(fs), dtype=torch.float64, device=Y.device), P
     seg = _welch_frames(torch, params, x, L, L - noverlap, nfft, detrend, shift, None, None, dev, table)
     frames = seg.shape[-2]
     sums = _window_sums(torch, params, L, True, shift, dev, table, cache)
@@ -619,7 +749,7 @@ def _welch(torch, params, x, fs, length, noverlap, nfft, detrend, return_oneside
 
 
 def welch(params, x, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", return_onesided=True, scaling="density",
-          shift=None, average="mean"):
+          shift=None, average="mean", fft="torch"):
     """Welch's power spectral density with one of this library's windows, scipy.signal.welch's defaults as the model: x (T,) or
     (B, T), float32 (one-sided spectrum, rfft) or complex64 (two-sided, fft; return_onesided is then ignored, as scipy does), cut
     into segments of `length` overlapping by noverlap (default length // 2), detrended ("constant" or False), windowed, zero-padded
@@ -628,13 +758,17 @@ def welch(params, x, fs=1.0, *, length, noverlap=None, nfft=None, detrend="const
     Returns (freqs float64, Pxx float32 (..., K)).  The sums of a (params, length, shift) are read from the device once and cached;
     after that one call the whole chain neither synchronises nor reads back (capturable with ResidentTable.welch, whose segments
     call needs no bhw_prepare_device).  Not built (ValueError): detrend="linear", average="median", scipy's boundary and padded.
+    fft="fused": the segments and their FFT come from ONE kernel (bhw_stft_fft_f32_*, see stft()) in place of welch_frames ->
+    torch.fft; welch_psd then reads the same kind of Y and keeps its bit-for-bit contract given Y.  It takes real x and nfft a power
+    of two in 16..4096 (ValueError otherwise) and gives the one-sided spectrum; its FFT is accurate to a float32 FFT's error, so P
+    agrees with the default route to that error, not bit for bit.  The default "torch" is the chain above, unchanged.
     Cross spectra: csd(), coherence(), transfer_function(), cross_spectra()."""
     torch = _torch()
     if not isinstance(x, torch.Tensor) or not x.is_cuda:
         raise ValueError("x must be a float32 or complex64 CUDA tensor")
     dev = x.device.index
     return _welch(torch, params, x, fs, length, noverlap, nfft, detrend, return_onesided, scaling, shift, average, dev, None,
-                  _SUMS_CACHE)
+                  _SUMS_CACHE, fft)
 
 
 # ---- Welch cross spectra: the pass behind the FFT for two signals -------------------------------------------------------------------------
@@ -721,8 +855,9 @@ def welch_csd(X, Y, scale, *, nfft, onesided=True, outputs=("pxy",), out=None, w
     return res
 
 
-def _cross(torch, params, x, y, fs, length, noverlap, nfft, detrend, return_onesided, scaling, shift, outputs, table, cache):
+def _cross(torch, params, x, y, fs, length, noverlap, nfft, detrend, return_onesided, scaling, shift, outputs, table, cache, fft="torch"):
     """The chain of csd / coherence / transfer_function / cross_spectra: (freqs, dict by output name)."""
+    fused = _fft_check(fft)
     for t, what in ((x, "x"), (y, "y")):
         if not isinstance(t, torch.Tensor) or not t.is_cuda:
             raise ValueError(f"{what} must be a float32 or complex64 CUDA tensor")
@@ -750,6 +885,11 @@ def _cross(torch, params, x, y, fs, length, noverlap, nfft, detrend, return_ones
     nfft = L if nfft is None else int(nfft)
     if nfft < L:
         raise ValueError(f"nfft {nfft} must be at least the window length {L}")
+    if fused:                                                      # every refusal of the fused route before anything is launched or read
+        if x.is_complex() or not return_onesided:
+            raise ValueError("fft='fused' takes real x and y and gives the one-sided spectra only (otherwise: fft='torch')")
+        _fft_input(torch, x, nfft, dev)
+        _fft_input(torch, y, nfft, dev)
     if T < L or (y.dim() == 2 and y.shape[0] < 1):
         raise ValueError(f"zero segments: T = {T} < length = {L}" if T < L else "zero signals")
     hop = L - noverlap
@@ -759,6 +899,15 @@ def _cross(torch, params, x, y, fs, length, noverlap, nfft, detrend, return_ones
     # the segments of x and of y in one buffer, so that one FFT call transforms both
     nx = x.shape[0] if x.dim() == 2 else 1
     ny = y.shape[0] if y.dim() == 2 else 1
+    if fused:
+        # the spectra of x and of y by the fused kernel, two calls into the two halves of one buffer
+        handle = None if table is None else table._live()
+        S = torch.empty((nx + ny, frames, nfft // 2 + 1), dtype=torch.complex64, device=x.device)
+        _welch_fft(torch, params, x, L, hop, nfft, detrend, shift, S[:nx] if x.dim() == 2 else S[0], dev, handle)
+        _welch_fft(torch, params, y, L, hop, nfft, detrend, shift, S[nx:] if y.dim() == 2 else S[nx], dev, handle)
+        res = welch_csd(S[:nx] if x.dim() == 2 else S[0], S[nx:] if y.dim() == 2 else S[nx], scale, nfft=nfft, onesided=True,
+                        outputs=outputs)
+        return torch.fft.rfftfreq(nfft, d=1.0 / float(fs), dtype=torch.float64, device=S.device), res
     seg = torch.empty((nx + ny, frames, nfft), dtype=x.dtype, device=x.device)
     handle = None if table is None else table._live()
     _welch_frames(torch, params, x, L, hop, nfft, detrend, shift, seg[:nx] if x.dim() == 2 else seg[0], None, dev, handle)
@@ -772,39 +921,43 @@ def _cross(torch, params, x, y, fs, length, noverlap, nfft, detrend, return_ones
 
 
 def cross_spectra(params, x, y, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", return_onesided=True, scaling="density",
-                  shift=None, outputs=("pxy", "pxx", "pyy", "coherence", "h1")):
+                  shift=None, outputs=("pxy", "pxx", "pyy", "coherence", "h1"), fft="torch"):
     """Every Welch cross-spectral estimate of (x, y) from one pass, scipy.signal.csd / coherence as the model: x and y (T,) or (B, T)
     of the same length and dtype, float32 (one-sided, rfft) or complex64 (two-sided, fft); x (T,) against y (B, T) is paired with
     every signal of y.  Both are cut, detrended, windowed and zero-padded as welch() does, into ONE buffer that one torch.fft call
     transforms, and welch_csd reads the two spectra once: window_sums -> welch_frames(x), welch_frames(y) -> torch.fft -> welch_csd.
     Returns (freqs float64, dict by output name: "pxy" = scipy's csd(x, y), "pxx" / "pyy" = welch(x) / welch(y), "coherence" =
     scipy's coherence(x, y), "h1" = P_xy / P_xx).  The sums cache and the capture rule are welch()'s.  Signals of unequal length are a
-    ValueError (scipy zero-pads the shorter one)."""
-    return _cross(_torch(), params, x, y, fs, length, noverlap, nfft, detrend, return_onesided, scaling, shift, outputs, None, _SUMS_CACHE)
+    ValueError (scipy zero-pads the shorter one).  fft="fused": the segments and spectra of x and of y come from the fused window +
+    FFT kernel (two calls into the two halves of one buffer; see welch() for what it takes and what it changes)."""
+    return _cross(_torch(), params, x, y, fs, length, noverlap, nfft, detrend, return_onesided, scaling, shift, outputs, None, _SUMS_CACHE,
+                  fft)
 
 
 def csd(params, x, y, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", return_onesided=True, scaling="density",
-        shift=None):
+        shift=None, fft="torch"):
     """Welch's cross power spectral density P_xy (scipy.signal.csd's convention, conj(X) * Y): cross_spectra() with outputs=("pxy",),
     the two-chain kernel.  Returns (freqs float64, Pxy complex64 (..., K))."""
-    f, r = _cross(_torch(), params, x, y, fs, length, noverlap, nfft, detrend, return_onesided, scaling, shift, ("pxy",), None, _SUMS_CACHE)
+    f, r = _cross(_torch(), params, x, y, fs, length, noverlap, nfft, detrend, return_onesided, scaling, shift, ("pxy",), None, _SUMS_CACHE,
+                  fft)
     return f, r["pxy"]
 
 
 def coherence(params, x, y, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", return_onesided=True, scaling="density",
-              shift=None):
+              shift=None, fft="torch"):
     """The magnitude-squared coherence |P_xy|^2 / (P_xx P_yy) of scipy.signal.coherence, from one pass over both spectra.  Returns
     (freqs float64, Cxy float32 (..., K)); NaN in a bin where x or y has no power at all."""
     f, r = _cross(_torch(), params, x, y, fs, length, noverlap, nfft, detrend, return_onesided, scaling, shift, ("coherence",), None,
-                  _SUMS_CACHE)
+                  _SUMS_CACHE, fft)
     return f, r["coherence"]
 
 
 def transfer_function(params, x, y, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", return_onesided=True,
-                      scaling="density", shift=None):
+                      scaling="density", shift=None, fft="torch"):
     """The H1 estimate P_xy / P_xx of the transfer function from x (the excitation) to y (the response).  Returns (freqs float64,
     H1 complex64 (..., K))."""
-    f, r = _cross(_torch(), params, x, y, fs, length, noverlap, nfft, detrend, return_onesided, scaling, shift, ("h1",), None, _SUMS_CACHE)
+    f, r = _cross(_torch(), params, x, y, fs, length, noverlap, nfft, detrend, return_onesided, scaling, shift, ("h1",), None, _SUMS_CACHE,
+                  fft)
     return f, r["h1"]
 
 
@@ -947,6 +1100,11 @@ class ResidentTable:
                                                        ctypes.c_void_p(xr.data_ptr()), ctypes.c_void_p(out.data_ptr())))
         return out
 
+    def stft(self, params, x, n_fft, hop, *, win_length=None, center=True, pad_mode="reflect", detrend=False, shift=None, out=None):
+        """stft() with the coefficients gathered from this table (bhw_stft_fft_f32_from_table): no allocation by the library, no
+        synchronisation, capturable into a graph on its first call."""
+        return _stft(_torch(), params, x, n_fft, hop, win_length, center, pad_mode, detrend, shift, out, self.device, self._live())
+
     def istft_overlap_add(self, params, y, n_fft, hop, *, win_length=None, center=True, length=None, normalize=True, shift=None,
                           out=None):
         """istft_overlap_add() with the coefficients gathered from this table (bhw_istft_ola_f32_from_table): no allocation by the
@@ -970,38 +1128,38 @@ class ResidentTable:
         return _welch_frames(_torch(), params, x, length, hop, nfft, detrend, shift, out, workspace, self.device, self._live())
 
     def welch(self, params, x, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", return_onesided=True,
-              scaling="density", shift=None, average="mean"):
+              scaling="density", shift=None, average="mean", fft="torch"):
         """welch() from this table.  The window sums are read back once per (params, length, shift) and kept on the table; after that
         one call the whole chain can be captured into a graph."""
         return _welch(_torch(), params, x, fs, length, noverlap, nfft, detrend, return_onesided, scaling, shift, average, self.device,
-                      self._live(), self._sums)
+                      self._live(), self._sums, fft)
 
     def cross_spectra(self, params, x, y, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", return_onesided=True,
-                      scaling="density", shift=None, outputs=("pxy", "pxx", "pyy", "coherence", "h1")):
+                      scaling="density", shift=None, outputs=("pxy", "pxx", "pyy", "coherence", "h1"), fft="torch"):
         """cross_spectra() from this table.  The sums cache and the capture rule are welch()'s: after one warm call the chain can be
         captured into a graph, a first call inside a capture raises."""
         return _cross(_torch(), params, x, y, fs, length, noverlap, nfft, detrend, return_onesided, scaling, shift, outputs, self,
-                      self._sums)
+                      self._sums, fft)
 
     def csd(self, params, x, y, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", return_onesided=True,
-            scaling="density", shift=None):
+            scaling="density", shift=None, fft="torch"):
         """csd() from this table."""
         f, r = _cross(_torch(), params, x, y, fs, length, noverlap, nfft, detrend, return_onesided, scaling, shift, ("pxy",), self,
-                      self._sums)
+                      self._sums, fft)
         return f, r["pxy"]
 
     def coherence(self, params, x, y, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", return_onesided=True,
-                  scaling="density", shift=None):
+                  scaling="density", shift=None, fft="torch"):
         """coherence() from this table."""
         f, r = _cross(_torch(), params, x, y, fs, length, noverlap, nfft, detrend, return_onesided, scaling, shift, ("coherence",), self,
-                      self._sums)
+                      self._sums, fft)
         return f, r["coherence"]
 
     def transfer_function(self, params, x, y, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", return_onesided=True,
-                          scaling="density", shift=None):
+                          scaling="density", shift=None, fft="torch"):
         """transfer_function() from this table."""
         f, r = _cross(_torch(), params, x, y, fs, length, noverlap, nfft, detrend, return_onesided, scaling, shift, ("h1",), self,
-                      self._sums)
+                      self._sums, fft)
         return f, r["h1"]
 
     def generate_part(self, params, part, n_parts, window):

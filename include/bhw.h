@@ -30,7 +30,8 @@ extern "C" {
 
 #define BHW_ABI_VERSION 4u   /* 3: bhw_coeffs_preset, bhw_gather_parts_device; 4: bhw_workspace_bytes_ex (nothing removed or changed);
                                 the resident tables, the overlapped-frame apply, the overlap-add and the windows of any length
-                                were added without a bump (additions only), as were the float32, STFT and Welch calls */
+                                were added without a bump (additions only), as were the float32, STFT and Welch calls and the fused
+                                window + FFT calls (bhw_stft_fft_f32_*) */
 
 /* CORDIC bit-model (the reference holds three that are not bit-identical). */
 enum {
@@ -667,6 +668,48 @@ uint64_t bhw_welch_csd_workspace_bytes(const bhw_csd *d);
 int bhw_welch_csd_f32(int device, void *hip_stream, const bhw_csd *d, const float *d_X, const float *d_Y, float *d_Pxy, float *d_Pxx,
                       float *d_Pyy, float *d_Cxy, float *d_H1, void *workspace, uint64_t workspace_bytes);
 int bhw_describe_csd(const bhw_csd *d, char *buf, uint64_t len);
+
+/* Fused window and real FFT: the rows of bhw_stft_frames_f32_* (flags 0) or of bhw_welch_frames_f32_* (BHW_WELCH_DETREND_CONSTANT)
+ * formed, transformed and written as their one-sided spectrum by ONE launch.  A workgroup owns whole rows: it reads the samples of a
+ * row once, removes the mean (with the flag), applies the window, runs a float32 FFT of n_fft points in LDS and writes only the
+ * K = n_fft / 2 + 1 bins.  Neither the windowed rows nor the means ever reach memory, so the call takes no workspace.
+ *   - The row.  The n_fft values the transform sees are bit for bit the row (b, f) those calls would have written for the same
+ *     descriptor: flags 0: col0 <= j < col0 + L ? fl32(X_b(t, 0) * v[j - col0]) : +0.0 with the padding of bhw_stft_frames_f32_*;
+ *     BHW_WELCH_DETREND_CONSTANT: j < L ? fl32(fl32(x_j - m) * v[j]) : +0.0 with m = fl32(S / L) and S summed in the FIXED order of
+ *     bhw_welch_frames_f32_* (64 binary64 partial sums by j mod 64 in ascending j, then the butterfly 32 ... 1), no fused operation.
+ *     A row reads its L window columns only, so the extent rule is the Welch one, (frames - 1) * hop + L <= samples, whenever pad,
+ *     col0 and pad_mode are all 0, and that of bhw_stft_frames_f32_* otherwise.
+ *   - The transform.  d_Y[b * y_batch_stride + f * y_stride + 2 * k + {0, 1}] = (re, im) of sum over j of row[j] * exp(-2 pi i j k / n_fft)
+ *     for k < K: the sign convention of torch.fft.rfft, no scaling; complex64 as interleaved float pairs.  The FFT is NOT pinned bit
+ *     for bit: it is a float32 Stockham transform of n_fft / 2 complex points (the row taken as pairs) in radix-4 passes, one radix-2
+ *     pass at the end when log2(n_fft / 2) is odd, and a split pass; every twiddle factor is the float32 rounding of a binary64
+ *     cosine or sine.  Its error against an exact transform of the float32 row is that of a float32 FFT (relative l2 error of a row
+ *     of the order of 2^-24 * log2(n_fft) at most); the tests hold it to twice the error of rocFFT on the same rows.
+ *   - Supported: channels 1 and n_fft a power of two in 16..4096.  Everything else -- complex input, other lengths, an inverse --
+ *     is BHW_ERR_UNSUPPORTED.
+ *   - Descriptor: bhw_stft, where for these calls y_stride and y_batch_stride count FLOAT elements between spectrum rows and between
+ *     signals; 0 means 2 * K and frames * y_stride.  Both must be even (rows of complex64 stay 8-byte aligned).  flags: 0 or
+ *     BHW_WELCH_DETREND_CONSTANT; with the flag pad, col0 and pad_mode must be 0, as for the segments call.
+ *   - Determinism: the bits of spectrum row (b, f) depend only on the window, n_fft, flags and that row's samples -- not on the
+ *     batch, the plan, the row's place in a workgroup, the strides, or library versus table.
+ *   - Purely real bins: the imaginary parts of bin 0 and of bin n_fft / 2 are written as +0.0.
+ *   - IEEE: a NaN or an infinity in x reaches only the rows whose window covers it; every other row keeps its bits.
+ *   - Only the 2 * K floats of each row are written: the elements between 2 * K and y_stride and the gaps of y_batch_stride never are.
+ *   - Checks before any HIP call (BHW_ERR_BADARG unless noted): everything the frames call (flags 0) or the segments call (with the
+ *     flag) checks for the descriptor with packed output strides, unknown flags, the unsupported n_fft or channels
+ *     (BHW_ERR_UNSUPPORTED), y_stride below 2 * K or odd, y_batch_stride below (frames - 1) * y_stride + 2 * K or odd,
+ *     batch * frames * K above 2^34, NULL pointers, d_Y not 8-byte aligned, d_x not 4-byte aligned, d_Y overlapping d_x, and (from a
+ *     table) the key match.  frames 0 returns BHW_OK with the pointers unchecked.
+ *   - The library form computes the coefficients by direct CORDIC and the twiddle factors in the kernel: no allocation, no scratch,
+ *     capturable with no bhw_prepare_device.  The from-table form keeps the from-table contract: no allocation, no synchronisation,
+ *     capturable on its first call.
+ *   - bhw_describe_stft_fft: one line naming the route, the plan (lanes per row, rows side by side in a workgroup, radix schedule,
+ *     LDS bytes, grid) and the kernel.  t may be NULL (the library call).  Host arithmetic only. */
+int bhw_stft_fft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                            const float *d_x, float *d_Y);
+int bhw_stft_fft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                const float *d_x, float *d_Y);
+int bhw_describe_stft_fft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf, uint64_t len);
 
 /* Threading: every entry point may be called from any host thread.  Calls that use the library-owned scratch of one
  * (device, stream) are serialised against each other for the duration of their launches (the table is rebuilt per call);
