@@ -45,6 +45,7 @@ ABI_SYMBOLS = (
     "bhw_welch_frames_f32_from_table", "bhw_welch_psd_workspace_bytes", "bhw_welch_psd_f32", "bhw_describe_welch",
     "bhw_welch_csd_workspace_bytes", "bhw_welch_csd_f32", "bhw_describe_csd",
     "bhw_stft_fft_f32_device", "bhw_stft_fft_f32_from_table", "bhw_describe_stft_fft",
+    "bhw_istft_fft_f32_device", "bhw_istft_fft_f32_from_table", "bhw_describe_istft_fft",
 )
 
 
@@ -291,6 +292,9 @@ def lib():
     L.bhw_stft_fft_f32_device.argtypes = [P, u64, ci, vp, S, u32, f32p, f32p]
     L.bhw_stft_fft_f32_from_table.argtypes = [T, P, u64, vp, S, u32, f32p, f32p]
     L.bhw_describe_stft_fft.argtypes = [T, P, u64, S, u32, ctypes.c_char_p, u64]
+    L.bhw_istft_fft_f32_device.argtypes = [P, u64, ci, vp, S, u32, f32p, f32p]
+    L.bhw_istft_fft_f32_from_table.argtypes = [T, P, u64, vp, S, u32, f32p, f32p]
+    L.bhw_describe_istft_fft.argtypes = [T, P, u64, S, u32, ctypes.c_char_p, u64]
     PA = ctypes.POINTER(BhwAtan2Params)
     L.bhw_atan2_device.argtypes = [PA, ci, vp, u64, i32p, i32p, i32p]
     L.bhw_atan2_to_host.argtypes = [PA, ci, u64, i32p, i32p, i32p]
@@ -419,6 +423,17 @@ def describe_stft_fft(params, length, stft, *, detrend=False, table=None):
     buf = ctypes.create_string_buffer(768)
     check(lib().bhw_describe_stft_fft(table, ctypes.byref(params), int(length), ctypes.byref(stft),
                                       WELCH_DETREND_CONSTANT if detrend else 0, buf, len(buf)))
+    return buf.value.decode()
+
+
+def describe_istft_fft(params, length, stft, *, normalize=False, table=None):
+    """One line: the route, the kernel and the plan (radix schedule, lanes per row, spans per workgroup, span length S, halo, share of
+    repeated transforms, grid, LDS) of a fused inverse FFT + overlap-add over the window of `length`, for the descriptor `stft` (a
+    BhwStft, make_stft; its y strides count floats of spectrum rows) (bhw_describe_istft_fft).  `table` is a resident table handle or
+    None for the library call.  Host arithmetic only."""
+    buf = ctypes.create_string_buffer(1024)
+    check(lib().bhw_describe_istft_fft(table, ctypes.byref(params), int(length), ctypes.byref(stft),
+                                       OLA_NORMALIZE if normalize else 0, buf, len(buf)))
     return buf.value.decode()
 
 

@@ -1,0 +1,289 @@
+// bhw_istft_fft.hip -- inverse real FFT, window and overlap-add in one kernel (bhw_istft_fft_f32_device / _from_table; contract:
+// include/bhw.h, plan: BhwIstftFftPlan in bhw_plan.h, reasons and measurements: DESIGN.md section 19).
+//
+// The forward kernel (bhw_stft_fft.hip) mirrored.  A slot of lpf lanes owns one span of a signal's window-start axis w = t + pad -
+// col0 and walks, in ascending f, the frames that reach the span's outputs (bhwp_istft_span).  Prologue, once per workgroup: the
+// window coefficients v[0..L) by the direct CORDIC chains or the gather over a resident table, and the twiddle table
+// W[k] = exp(+2 pi i k / n_fft), k < n_fft / 2, each component the float32 rounding of a binary64 sincospi; both stay in LDS.
+// Then, per frame of the slot:
+//   1. the pre-split: a lane loads the bins Y[k] and Y[M - k], k <= M / 2 (consecutive lanes, consecutive complex64 values), and
+//      forms Z[k] = (Y[k] + conj Y[M - k]) + i (Y[k] - conj Y[M - k]) W[k] and its partner Z[M - k]; Z[0] = (Y[0].re + Y[M].re,
+//      Y[0].re - Y[M].re): the imaginary parts of bins 0 and M are never read into the arithmetic;
+//   2. an inverse Stockham FFT of M points, out of place between two LDS buffers: the forward's passes with the conjugated table
+//      and +i in the radix-4 butterfly.  The result z[i] = (row[2 i], row[2 i + 1]) is n_fft times the row;
+//   3. the ring: position w mod n_fft belongs to lane (w mod n_fft) mod lpf, cpl positions a lane.  With base = f * hop, ring
+//      position q holds w = base + k, k = (q - base) mod n_fft, which frame f reaches at window index k < L and row column col0 + k:
+//      S[q] += (double) fl32(row[col0 + k] / n_fft) * (double) v[k], E[q] += (double) v[k]^2, in binary64 registers.  Consecutive
+//      lanes read consecutive floats of the row and of v;
+//   4. the flush: after frame f every w < (f + 1) * hop of the span (after its last frame: every w) is complete; the lane stores
+//      fl32(S) or fl32(S / E) (consecutive lanes, consecutive samples) and clears the position.  Outputs no frame reaches are
+//      stored as +0.0 directly.
+// The fy slots of a workgroup hold different spans (of any signals) and pass the same barriers: every slot makes `trips` rounds,
+// idle once its frames are done.  A row's arithmetic does not depend on its slot, span or grid, and an output's sum takes its rows in
+// ascending f whatever the spans are: the bits of an output are a function of the window and the rows that reach it.
+//
+// Kept in step by hand: icmul, itwiddle and launch_lds restate cmul, twiddle and the launch helper of bhw_stft_fft.hip (that file
+// and its code objects stay the parent's), and tests/cpp/san_istft_fft.cpp replays this file's index arithmetic -- the pre-split
+// pairs, the pass indices, the ring's (q - base) mod n_fft and the flush bound `end` -- from a copy of its own, since only
+// bhwp_istft_span is shared through bhw_plan.h.  An edit of any of these here is an edit of the replay too.
+#include "bhw_device.h"
+
+namespace {
+
+typedef float ifft_v2f __attribute__((ext_vector_type(2)));
+
+struct IfftIo {
+    const float *Y;
+    float *x;
+    uint64_t batch, frames, hop, samples, t0;
+    uint64_t x_stride, y_stride, y_bstride;
+    uint64_t span, spans, groups, trips;
+    uint32_t n_fft, m, col0, len;
+    uint32_t lpf, fy, cpl, radix4, radix2;
+    uint32_t shift, normalize;
+};
+
+extern __shared__ __attribute__((aligned(16))) unsigned char ifft_lds[];
+
+__device__ __forceinline__ float ifft_coeff(int32_t w, uint32_t shift) { return ldexpf((float)w, -(int)shift); }
+
+__device__ __forceinline__ ifft_v2f icmul(ifft_v2f a, ifft_v2f w) { return ifft_v2f{a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x}; }
+
+// W at index idx < n_fft (table of n_fft / 2 entries, W[idx + n_fft / 2] = -W[idx])
+__device__ __forceinline__ ifft_v2f itwiddle(const ifft_v2f *tw, uint32_t idx, uint32_t m)
+{
+    const ifft_v2f w = tw[idx & (m - 1u)];
+    return (idx & m) ? ifft_v2f{-w.x, -w.y} : w;
+}
+
+__device__ __forceinline__ float ifft_out(double s, double e, uint32_t normalize)
+{
+    if (!normalize) return (float)s;
+    return e > 0.0 ? (float)(s / e) : 0.0f;
+}
+
+// Everything after the prologue's coefficients: vS (behind the twiddles) holds v[0..L).
+__device__ __forceinline__ void istft_fft_spans(const IfftIo &a)
+{
+    const uint32_t M = a.m, n = a.n_fft, lpf = a.lpf, fy = a.fy, L = a.len;
+    ifft_v2f *bufA = (ifft_v2f *)ifft_lds;
+    ifft_v2f *bufB = bufA + (size_t)fy * M;
+    ifft_v2f *tw = bufB + (size_t)fy * M;
+    const float *vS = (const float *)(tw + M);
+    const uint32_t tid = threadIdx.x;
+    const uint32_t slot = tid / lpf, l = tid - slot * lpf;
+    for (uint32_t k = tid; k < M; k += kFftBlock) {
+        double sn, cs;
+        sincospi((double)k * 2.0 / (double)n, &sn, &cs);
+        tw[k] = ifft_v2f{(float)cs, (float)sn};
+    }
+    __syncthreads();
+    const float scale = 1.0f / (float)n;                                 // a power of two: exact
+    const uint64_t pool = a.batch * a.spans, hop = a.hop;
+    const uint32_t H = M >> 1, Q = M >> 2;
+    double acc[kFftMaxCpl], env[kFftMaxCpl];
+#pragma unroll
+    for (uint32_t c = 0; c < kFftMaxCpl; ++c) acc[c] = env[c] = 0.0;
+    for (uint64_t g = blockIdx.x; g < a.groups; g += gridDim.x) {
+        const uint64_t sp = g * fy + slot;
+        const bool live = sp < pool;
+        const uint64_t b = live ? sp / a.spans : 0, s = live ? sp - b * a.spans : 0;
+        BhwIstftSpan r = bhwp_istft_span(s, a.span, hop, L, a.t0, a.samples, a.frames);
+        if (!live) r.wlo = r.whi = r.f_lo = r.f_hi = 0;
+        const float *yb = a.Y + b * a.y_bstride;
+        float *xb = a.x + b * a.x_stride;                                // output t = w - t0 (every w formed below is >= wlo >= t0)
+        uint64_t cur = r.wlo;                                            // the span's outputs below cur are stored
+        for (uint64_t it = 0; it < a.trips; ++it) {
+            const uint64_t f = r.f_lo + it;
+            const bool act = f < r.f_hi;
+            // 1. the pre-split, into the slot's half of buffer A
+            ifft_v2f *src = bufA + (size_t)slot * M, *dst = bufB + (size_t)slot * M;
+            if (act) {
+                const ifft_v2f *yp = (const ifft_v2f *)(yb + f * a.y_stride);
+                for (uint32_t k = l; k <= H; k += lpf) {
+                    const ifft_v2f A = yp[k], B = yp[M - k];
+                    if (k == 0u) {
+                        src[0] = ifft_v2f{A.x + B.x, A.x - B.x};
+                    } else {
+                        const ifft_v2f w = tw[k];
+                        const ifft_v2f e0 = ifft_v2f{A.x + B.x, A.y - B.y}, d0 = ifft_v2f{A.x - B.x, A.y + B.y};
+                        const ifft_v2f o0 = icmul(d0, w);
+                        src[k] = ifft_v2f{e0.x - o0.y, e0.y + o0.x};
+                        if (k != H) {                                    // the partner M - k: W[M - k] = -conj W[k]
+                            const ifft_v2f e1 = ifft_v2f{e0.x, -e0.y}, d1 = ifft_v2f{-d0.x, d0.y};
+                            const ifft_v2f o1 = icmul(d1, ifft_v2f{-w.x, w.y});
+                            src[M - k] = ifft_v2f{e1.x - o1.y, e1.y + o1.x};
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+            // 2. the passes (every slot, idle ones on stale data: their result is not read)
+            uint32_t Ns = 1;
+            for (uint32_t p = 0; p < a.radix4; ++p) {
+                const uint32_t ts = M / (2u * Ns);                       // n_fft / (4 Ns)
+                for (uint32_t i = l; i < Q; i += lpf) {
+                    const uint32_t k = i & (Ns - 1u);
+                    ifft_v2f a0 = src[i], a1 = src[i + Q], a2 = src[i + 2u * Q], a3 = src[i + 3u * Q];
+                    if (Ns > 1u) {
+                        const uint32_t kt = k * ts;
+                        a1 = icmul(a1, itwiddle(tw, kt, M));
+                        a2 = icmul(a2, itwiddle(tw, 2u * kt, M));
+                        a3 = icmul(a3, itwiddle(tw, 3u * kt, M));
+                    }
+                    const ifft_v2f t0 = a0 + a2, t1 = a0 - a2, t2 = a1 + a3;
+                    const ifft_v2f t3 = ifft_v2f{a3.y - a1.y, a1.x - a3.x};   // +i (a1 - a3)
+                    const uint32_t o = ((i - k) << 2) + k;
+                    dst[o] = t0 + t2;
+                    dst[o + Ns] = t1 + t3;
+                    dst[o + 2u * Ns] = t0 - t2;
+                    dst[o + 3u * Ns] = t1 - t3;
+                }
+                __syncthreads();
+                ifft_v2f *sw = src;
+                src = dst;
+                dst = sw;
+                Ns <<= 2;
+            }
+            if (a.radix2) {                                              // Ns = M / 2: k = i, twiddle W[2 i]
+                for (uint32_t i = l; i < H; i += lpf) {
+                    const ifft_v2f a0 = src[i], a1 = icmul(src[i + H], tw[2u * i]);
+                    dst[i] = a0 + a1;
+                    dst[i + H] = a0 - a1;
+                }
+                __syncthreads();
+                ifft_v2f *sw = src;
+                src = dst;
+                dst = sw;
+            }
+            // 3. and 4.: the ring
+            if (act) {
+                const float *row = (const float *)src + a.col0;
+                const uint64_t base = f * hop;
+                if (cur < base) {                                        // a gap no frame reaches (hop > L, or the span's start)
+                    for (uint64_t w = cur + l; w < base; w += lpf) xb[w - a.t0] = 0.0f;
+                    cur = base;
+                }
+                uint64_t end = (f + 1 == r.f_hi || base + hop > r.whi) ? r.whi : base + hop;
+                if (end < cur) end = cur;                                // a halo frame whose own hop lies before the span
+                const uint32_t bm = (uint32_t)(base & (uint64_t)(n - 1u));
+#pragma unroll
+                for (uint32_t c = 0; c < kFftMaxCpl; ++c) {
+                    if (c < a.cpl) {
+                        const uint32_t k = (c * lpf + l - bm) & (n - 1u);
+                        const uint64_t w = base + k;
+                        if (k < L && w >= cur && w < r.whi) {
+                            const double v = (double)vS[k];
+                            acc[c] += (double)(row[k] * scale) * v;
+                            env[c] += v * v;
+                            if (w < end) {
+                                xb[w - a.t0] = ifft_out(acc[c], env[c], a.normalize);
+                                acc[c] = env[c] = 0.0;
+                            }
+                        }
+                    }
+                }
+                const uint64_t reach = base + L;                         // the frame's extent: beyond it up to `end` nothing is summed
+                if (reach < end)
+                    for (uint64_t w = (reach > cur ? reach : cur) + l; w < end; w += lpf) xb[w - a.t0] = 0.0f;
+                cur = end;
+            }
+            __syncthreads();                                             // the next round overwrites both buffers
+        }
+        if (live)
+            for (uint64_t w = cur + l; w < r.whi; w += lpf) xb[w - a.t0] = 0.0f;   // a span with no frame, or outputs past the last one
+    }
+}
+
+// Four workgroups per CU (128 registers a lane): the compiler's own choice is 129 and three.
+// Coefficient by the direct CORDIC chains (FORM: direct_form, as k_stft_fft_direct).
+template <int FORM>
+__global__ __launch_bounds__(kFftBlock, 4) void k_istft_fft_direct(BhwCordicCfg cfg, BhwWinCfg win, IfftIo a, BhwLenPhase lp)
+{
+    using T = std::conditional_t<FORM == 0, int32_t, int64_t>;
+    using L = std::conditional_t<FORM == 2, uint32_t, T>;
+    __shared__ L lut_s[32];
+    if (threadIdx.x < 32) lut_s[threadIdx.x] = (L)cfg.lut[threadIdx.x];
+    __syncthreads();
+    float *vS = (float *)(ifft_lds + (size_t)(2u * a.fy + 1u) * a.m * sizeof(ifft_v2f));
+    for (uint32_t k = threadIdx.x; k < a.len; k += kFftBlock) {
+        int32_t w;
+        if constexpr (FORM == 2) w = direct_coeff_mad_ph(cfg, win, lut_s, len_theta_of(lp, k));
+        else                     w = direct_coeff_ph<T>(cfg, win, lut_s, len_theta_of(lp, k));
+        vS[k] = ifft_coeff(w, a.shift);
+    }
+    istft_fft_spans(a);
+}
+
+// Coefficient gathered from a resident table in format FMT; every lane reaches the gather (at k = 0 past the window) for the escape
+// format's wave-wide fix.
+template <int FMT, int NT, int MODE>
+__global__ __launch_bounds__(kFftBlock, 4) void k_istft_fft_table(BhwCordicCfg cfg, BhwWinCfg win, const void *__restrict__ table, IfftIo a,
+                                                                BhwLenPhase lp)
+{
+    float *vS = (float *)(ifft_lds + (size_t)(2u * a.fy + 1u) * a.m * sizeof(ifft_v2f));
+    for (uint32_t k0 = 0; k0 < a.len; k0 += kFftBlock) {
+        const uint32_t k = k0 + threadIdx.x;
+        const bool in = k < a.len;
+        const int32_t w = range_coeff_ph<FMT, NT, MODE>(cfg, win, table, len_theta_of(lp, in ? k : 0u));
+        if (in) vS[k] = ifft_coeff(w, a.shift);
+    }
+    istft_fft_spans(a);
+}
+
+// launch() of bhw_device.h with the plan's dynamic LDS
+template <typename... KArgs>
+inline void launch_lds(void (*kernel)(KArgs...), dim3 grid, dim3 block, uint32_t lds, hipStream_t st, typename same_type<KArgs>::type... args)
+{
+    void *ptrs[] = {(void *)&args...};
+    const hipError_t e = hipLaunchKernel(reinterpret_cast<const void *>(kernel), grid, block, ptrs, lds, st);
+    if (e != hipSuccess && t_launch_err == hipSuccess) t_launch_err = e;
+}
+
+} // namespace
+
+int bhwk_istft_fft_f32(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinCfg &w, const BhwIstftFftPlan &pl, const bhw_stft *s,
+                       const float *d_Y, float *d_x, const int32_t *d_table, const BhwLenPhase &lp)
+{
+    if (!s->samples) return 0;
+    hipStream_t st = (hipStream_t)l.stream;
+    IfftIo a;
+    a.Y = d_Y;
+    a.x = d_x;
+    a.batch = s->batch;
+    a.frames = s->frames;
+    a.hop = pl.hop;
+    a.samples = s->samples;
+    a.t0 = pl.t0;
+    a.x_stride = pl.x_stride;
+    a.y_stride = pl.y_stride;
+    a.y_bstride = pl.y_bstride;
+    a.span = pl.span;
+    a.spans = pl.spans;
+    a.groups = pl.groups;
+    a.trips = pl.trips;
+    a.n_fft = (uint32_t)s->n_fft;
+    a.m = pl.m;
+    a.col0 = (uint32_t)s->col0;
+    a.len = (uint32_t)pl.len;
+    a.lpf = pl.lpf;
+    a.fy = pl.fy;
+    a.cpl = pl.cpl;
+    a.radix4 = pl.radix4;
+    a.radix2 = pl.radix2;
+    a.shift = s->shift;
+    a.normalize = pl.normalize ? 1u : 0u;
+    const dim3 grid((unsigned)pl.grid), block(kFftBlock);
+    if (!d_table) {
+        with_int_or_last<2, 1, 0>(direct_form(c_in), [&](auto D) { launch_lds(k_istft_fft_direct<D>, grid, block, pl.lds_bytes, st, c_in, w, a, lp); });
+        return finish(hipSuccess);
+    }
+    const BhwCordicCfg c = table_layout(c_in);
+    int fmt, nt, mode;
+    if (!bhwp_range_form(c, w, &fmt, &nt, &mode)) return (int)hipErrorInvalidValue;
+    const void *tab = (const void *)d_table;
+    with_range_form(fmt, nt, mode, [&](auto F, auto NT, auto M) {
+        launch_lds(k_istft_fft_table<F, NT, M>, grid, block, pl.lds_bytes, st, c, w, tab, a, lp);
+    });
+    return finish(hipSuccess);
+}

@@ -456,6 +456,68 @@ int  bhwp_describe_stft_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64_
 int  bhwk_stft_fft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwStftFftPlan &pl, const bhw_stft *s,
                        const float *d_x, float *d_Y, const int32_t *d_table, const BhwLenPhase &lp);
 
+// ---- fused inverse real FFT, window and overlap-add (bhw_istft_fft_f32_*; bhw_istft_fft.hip) ------------------------------------------
+// The lane layout of the forward kernel (lpf lanes along a row, fy slots side by side, cpl columns per lane).  The window-start axis
+// w = t + pad - col0 of every signal (frame f covers w in [f * hop, f * hop + L)) is cut into spans of S * hop positions; the spans
+// (b, s) of the batch are one pool cut into groups of fy consecutive spans, one per slot; workgroup g takes the groups g, g + grid, ...
+// A slot walks, in ascending f, every frame that reaches its span's outputs -- at most S of its own and halo = ceil(L / hop) - 1
+// before them, which the previous span transforms too -- and adds (double) r * (double) v into a ring of n_fft binary64 accumulators
+// per slot, cpl of them (and cpl of the envelope) in the registers of each lane: ring position w mod n_fft belongs to lane
+// (w mod n_fft) mod lpf.  After frame f every w < (f + 1) * hop is complete, is stored and cleared.
+// S: the largest span that still leaves kIfftTargetGroups groups, but at least kIfftHaloFactor * halo frames, so that at most one
+// transform in kIfftHaloFactor + 1 is a repeat.  LDS: the two Stockham buffers of fy * M complex64, the n_fft / 2 conjugated
+// twiddles and the n_fft floats of the window (a function of n_fft alone, 64 KiB at 4096).
+constexpr uint32_t kIfftTargetGroups = 1024;          // span groups the planner asks for before spans grow (four per CU)
+constexpr uint32_t kIfftHaloFactor = 4;               // S >= 4 * halo
+struct BhwIstftFftPlan {
+    int route;            // BHWP_FRAMES_DIRECT or BHWP_FRAMES_TABLE
+    bool normalize;
+    uint32_t log2n, m, lpf, fy, cpl, radix4, radix2;   // as BhwStftFftPlan
+    uint32_t lds_bytes;   // 2 * fy * M * 8 + M * 8 + n_fft * 4  (<= 64 KiB)
+    uint64_t t0;          // pad - col0: output t is position w = t + t0
+    uint64_t hop;         // min(hop, t0 + samples): a larger hop leaves frame 0 alone under the outputs either way
+    uint64_t halo;        // ceil(L / hop) - 1
+    uint64_t span;        // S
+    uint64_t spans;       // spans per signal: ceil((t0 + samples) / (S * hop))
+    uint64_t groups;      // ceil(batch * spans / fy)
+    uint64_t grid;        // min(groups, kFftMaxGrid)
+    uint64_t trips;       // frames one slot walks at most: min(S + halo, frames)
+    bool halo_bound;      // S was set by the halo, not by the grid target: few workgroups under heavy overlap
+    uint64_t x_stride, y_stride, y_bstride;   // resolved (0 -> samples, 2K, frames * y_stride)
+    uint64_t len;         // L
+};
+// Span s of a signal: its outputs [wlo, whi) on the w axis and the frames [f_lo, f_hi) that reach them (both may be empty).
+struct BhwIstftSpan {
+    uint64_t wlo, whi, f_lo, f_hi;
+};
+BHW_HD inline BhwIstftSpan bhwp_istft_span(uint64_t s, uint64_t span, uint64_t hop, uint64_t len, uint64_t t0, uint64_t samples, uint64_t frames)
+{
+    BhwIstftSpan r;
+    const uint64_t a = s * span * hop, b = a + span * hop, end = t0 + samples;
+    r.wlo = a > t0 ? a : t0;
+    r.whi = b < end ? b : end;
+    if (r.whi <= r.wlo) {
+        r.whi = r.wlo;
+        r.f_lo = r.f_hi = 0;
+        return r;
+    }
+    r.f_lo = r.wlo >= len ? (r.wlo - len) / hop + 1 : 0;                  // f * hop + L > wlo
+    r.f_hi = (r.whi - 1) / hop + 1;                                       // f * hop < whi
+    if (r.f_hi > frames) r.f_hi = frames;
+    if (r.f_lo > r.f_hi) r.f_lo = r.f_hi;
+    return r;
+}
+// Every check of the two calls that needs no table handle, before any HIP call (include/bhw.h).  samples 0 passes with the pointers
+// unchecked; `pointers` false: the describe call.
+int  bhwp_istft_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const void *d_Y, const void *d_x,
+                           bool pointers = true);
+// the plan of a call that passed the checks with samples > 0
+BhwIstftFftPlan bhwp_istft_fft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, bool from_table);
+int  bhwp_describe_istft_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf,
+                             uint64_t len);
+int  bhwk_istft_fft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwIstftFftPlan &pl, const bhw_stft *s,
+                        const float *d_Y, float *d_x, const int32_t *d_table, const BhwLenPhase &lp);
+
 // the generate kernel of a window of any length (bhw_len.hip): d_table NULL = k_direct_len, else k_range_len over the resident table of c
 int  bhwk_len_range(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *d_table, const BhwLenPhase &lp,
                     uint64_t n0, uint64_t count, int32_t *d_out);

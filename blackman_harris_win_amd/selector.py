@@ -544,6 +544,68 @@ def stft(params, x, n_fft, hop, *, win_length=None, center=True, pad_mode="refle
     return _stft(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, shift, out, x.device.index, None)
 
 
+def _istft(torch, params, Y, n_fft, hop, win_length, center, length, normalize, shift, out, dev, table):
+    if not isinstance(Y, torch.Tensor) or not Y.is_cuda or Y.device.index != dev:
+        raise ValueError("Y must be a complex64 CUDA tensor on the call's device")
+    if Y.dtype != torch.complex64:
+        raise ValueError(f"the fused inverse FFT takes one-sided complex64 spectra, got {Y.dtype}")
+    if Y.dim() not in (2, 3):
+        raise ValueError("Y must be (frames, K) or (B, frames, K)")
+    n_fft, L, col0 = _stft_window(params, n_fft, win_length)
+    if not B.fft_supported(n_fft):
+        raise ValueError(f"the fused inverse FFT takes n_fft a power of two in {B.FFT_MIN_N}..{B.FFT_MAX_N}, got {n_fft}")
+    hop = int(hop)
+    if hop < 1:
+        raise ValueError("hop must be >= 1")
+    if not center and L < n_fft:
+        raise ValueError("center=False with win_length < n_fft: the first outputs have no window under them")
+    Yb = Y if Y.dim() == 3 else Y.unsqueeze(0)
+    nb, frames, K = Yb.shape
+    if K != n_fft // 2 + 1:
+        raise ValueError(f"Y rows hold {K} bins, n_fft // 2 + 1 is {n_fft // 2 + 1}")
+    if frames < 1 or nb < 1:
+        raise ValueError("zero frames")
+    pad = n_fft // 2 if center else 0
+    length = n_fft + hop * (frames - 1) - 2 * pad if length is None else int(length)
+    if length < 0:
+        raise ValueError(f"length {length} < 0")
+    Yb = _stft_input(Yb, ((frames - 1) * max(Yb.stride(1), K) + K, K))
+    shape = (nb, length) if Y.dim() == 3 else (length,)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=Y.device)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != Y.device or not out.is_contiguous() \
+            or out.is_neg() or tuple(out.shape) != shape:
+        raise ValueError(f"out must be a contiguous float32 tensor of shape {shape} on Y's device")
+    shift = params.dat_width - 1 if shift is None else int(shift)
+    s = B.make_stft(nb, length, frames, hop, n_fft, col0=col0, pad=pad, shift=shift,
+                    y_stride=Yb.stride(1) * 2 if frames > 1 else 0, y_batch_stride=Yb.stride(0) * 2 if nb > 1 else 0)
+    tail = (ctypes.byref(s), B.OLA_NORMALIZE if normalize else 0, ctypes.c_void_p(Yb.data_ptr()), ctypes.c_void_p(out.data_ptr()))
+    if table is None:
+        B.check(B.lib().bhw_istft_fft_f32_device(ctypes.byref(params), L, dev, _stream_ptr(torch, dev), *tail))
+    else:
+        B.check(B.lib().bhw_istft_fft_f32_from_table(table, ctypes.byref(params), L, _stream_ptr(torch, dev), *tail))
+    return out
+
+
+def istft(params, Y, n_fft, hop, *, win_length=None, center=True, length=None, normalize=True, shift=None, out=None):
+    """The inverse short-time Fourier transform of a batch in ONE launch (bhw_istft_fft_f32_device): Y (B, F, K) or (F, K), complex64,
+    K = n_fft // 2 + 1 -- the layout stft() returns.  Every row is transformed as torch.fft.irfft(Y, n=n_fft) does (same sign and
+    1 / n_fft scaling; the imaginary parts of bins 0 and n_fft / 2 are ignored) by a float32 FFT in LDS, and summed exactly as
+    istft_overlap_add() sums time rows: in ascending frame order in binary64, times v (window(params, win_length,
+    dtype=torch.float32, shift=shift)), and with normalize=True divided by the window envelope (+0.0 where no frame reaches).  The time
+    rows never reach memory.  length defaults to torch.istft's n_fft + hop * (frames - 1) - 2 * pad; outputs past the frames' extent are
+    +0.0.  Returns float32 (B, length), or (length,) for 2-D Y.  istft(params, S.transpose(-1, -2), ...) is torch.istft(S, n_fft, hop,
+    win_length, window=v, center=center, length=length) to a float32 FFT's error.  n_fft: a power of two in 16..4096 (ValueError
+    otherwise; a real or complex128 Y too).  Y is read in place when its bins are contiguous and its rows and signals apart; a
+    transposed view (of a torch.stft result, say), a broadcast or a lazy conjugate is copied first.  `out`: a contiguous float32 tensor
+    of the returned shape.  With heavy overlap and little work (see describe_istft_fft) few workgroups run; torch.fft.irfft +
+    istft_overlap_add remains for that case, and this call does not reroute to it."""
+    torch = _torch()
+    if not isinstance(Y, torch.Tensor) or not Y.is_cuda:
+        raise ValueError("Y must be a complex64 CUDA tensor")
+    return _istft(torch, params, Y, n_fft, hop, win_length, center, length, normalize, shift, out, Y.device.index, None)
+
+
 def _welch_fft(torch, params, x, length, hop, nfft, detrend, shift, out, dev, table):
     """The one-sided spectra of the Welch segments of x by the fused kernel: (B, frames, K) or (frames, K) complex64, into `out`
     (a packed complex64 tensor of that shape) when given."""
@@ -1104,6 +1166,11 @@ class ResidentTable:
         """stft() with the coefficients gathered from this table (bhw_stft_fft_f32_from_table): no allocation by the library, no
         synchronisation, capturable into a graph on its first call."""
         return _stft(_torch(), params, x, n_fft, hop, win_length, center, pad_mode, detrend, shift, out, self.device, self._live())
+
+    def istft(self, params, Y, n_fft, hop, *, win_length=None, center=True, length=None, normalize=True, shift=None, out=None):
+        """istft() with the coefficients gathered from this table (bhw_istft_fft_f32_from_table): no allocation by the library, no
+        synchronisation, capturable into a graph on its first call."""
+        return _istft(_torch(), params, Y, n_fft, hop, win_length, center, length, normalize, shift, out, self.device, self._live())
 
     def istft_overlap_add(self, params, y, n_fft, hop, *, win_length=None, center=True, length=None, normalize=True, shift=None,
                           out=None):

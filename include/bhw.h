@@ -685,8 +685,8 @@ int bhw_describe_csd(const bhw_csd *d, char *buf, uint64_t len);
  *     pass at the end when log2(n_fft / 2) is odd, and a split pass; every twiddle factor is the float32 rounding of a binary64
  *     cosine or sine.  Its error against an exact transform of the float32 row is that of a float32 FFT (relative l2 error of a row
  *     of the order of 2^-24 * log2(n_fft) at most); the tests hold it to twice the error of rocFFT on the same rows.
- *   - Supported: channels 1 and n_fft a power of two in 16..4096.  Everything else -- complex input, other lengths, an inverse --
- *     is BHW_ERR_UNSUPPORTED.
+ *   - Supported: channels 1 and n_fft a power of two in 16..4096.  Everything else -- complex input, other lengths -- is
+ *     BHW_ERR_UNSUPPORTED.  The inverse is bhw_istft_fft_f32_* below.
  *   - Descriptor: bhw_stft, where for these calls y_stride and y_batch_stride count FLOAT elements between spectrum rows and between
  *     signals; 0 means 2 * K and frames * y_stride.  Both must be even (rows of complex64 stay 8-byte aligned).  flags: 0 or
  *     BHW_WELCH_DETREND_CONSTANT; with the flag pad, col0 and pad_mode must be 0, as for the segments call.
@@ -710,6 +710,52 @@ int bhw_stft_fft_f32_device(const bhw_params *p, uint64_t length, int device, vo
 int bhw_stft_fft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
                                 const float *d_x, float *d_Y);
 int bhw_describe_stft_fft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf, uint64_t len);
+
+/* Fused inverse real FFT, window and overlap-add: torch.fft.irfft in front of bhw_istft_ola_f32_*, by ONE launch.  A group of lanes
+ * owns a span of a signal's time axis, reads the K = n_fft / 2 + 1 bins of every frame that reaches it, transforms them in LDS, and
+ * adds the windowed row into binary64 accumulators that it stores once.  The time rows never reach memory, so the call takes no
+ * workspace.
+ *   - The row.  For b < batch, f < frames, r[j], j < n_fft, is the float32 inverse real transform of the bins
+ *     Y[k] = d_Y[b * y_batch_stride + f * y_stride + 2 * k + {0, 1}]: r[j] ~ (1 / n_fft) * sum over k' < n_fft of Y[k'] exp(+2 pi i j k' /
+ *     n_fft) over the Hermitian extension Y[n_fft - k] = conj Y[k]: the convention and the scaling of torch.fft.irfft(Y, n=n_fft).  The
+ *     1 / n_fft is one exact power-of-two scaling of the float32 result.  The imaginary parts of bins 0 and n_fft / 2 never enter the
+ *     arithmetic.  The transform is NOT pinned bit for bit: it mirrors the forward's structure, a pre-split pass and an inverse float32
+ *     Stockham transform of n_fft / 2 complex points in radix-4 passes with one radix-2 pass at the end when log2(n_fft / 2) is odd;
+ *     every twiddle factor is the float32 rounding of a binary64 cosine or sine.  The bits of a row depend on its K bins and n_fft
+ *     only -- not on its place in a workgroup, the span that reads it, the grid, the strides or the route.
+ *   - The sum.  Given those rows every output is exactly what bhw_istft_ola_f32_* defines on them: for t < samples, u = t + pad, over
+ *     the frames f with 0 <= k = u - f * hop - col0 < L in ASCENDING f, in binary64 from +0.0:
+ *         S = sum (double) r_f[u - f * hop] * (double) v[k],   E = sum (double) v[k]^2
+ *         d_x[b * x_stride + t] = flags ? (E > 0 ? fl32(S / E) : +0.0) : fl32(S)
+ *     Outputs no frame reaches are +0.0: samples past the frames' extent, and the gaps when hop > L.
+ *   - Supported: channels 1 and n_fft a power of two in 16..4096; everything else -- complex output, other lengths -- is
+ *     BHW_ERR_UNSUPPORTED.
+ *   - Descriptor: bhw_stft, where (as for bhw_stft_fft_f32_*) y_stride and y_batch_stride count FLOAT elements between spectrum rows
+ *     and between signals; 0 means 2 * K and frames * y_stride; both must be even.  x_stride: floats between output signals.  flags:
+ *     0 or BHW_OLA_NORMALIZE.  pad_mode must be 0, as for bhw_istft_ola_f32_*.
+ *   - Determinism: the bits of output (b, t) depend only on the window, n_fft, hop, col0, pad, flags and the spectrum rows whose
+ *     window covers t -- not on the batch, the plan, how a signal is cut into spans, the strides, or library versus table.
+ *   - IEEE: a NaN or an infinity in spectrum row (b, f) makes exactly the outputs under that row's window non-finite; every other
+ *     output keeps its bits.
+ *   - Only the `samples` floats of each signal are written: the gaps of x_stride never are.
+ *   - Checks before any HIP call (BHW_ERR_BADARG unless noted): everything bhw_istft_ola_f32_* checks for the descriptor with packed
+ *     row strides (unknown flags, pad < col0, frames 0 with samples > 0, col0 + L > n_fft, shift, a nonzero pad_mode, the Taylor sources
+ *     (BHW_ERR_UNSUPPORTED), ...), the unsupported n_fft or channels (BHW_ERR_UNSUPPORTED), y_stride below 2 * K or odd, y_batch_stride
+ *     below (frames - 1) * y_stride + 2 * K or odd, batch * frames * n_fft above 2^34 (the overlap-add's cap, which keeps
+ *     batch * frames * K below it), NULL pointers, d_Y not 8-byte aligned, d_x not 4-byte aligned, d_Y overlapping d_x, and (from a
+ *     table) the key match.  samples 0 returns BHW_OK with the pointers unchecked.
+ *   - The library form computes the coefficients by direct CORDIC and the twiddle factors in the kernel: no allocation, no scratch,
+ *     capturable with no bhw_prepare_device.  The from-table form keeps the from-table contract: no allocation, no synchronisation,
+ *     capturable on its first call.
+ *   - bhw_describe_istft_fft: one line naming the route, the kernel and the plan: the radix schedule, the lanes per row, the spans a
+ *     workgroup runs side by side, the span length S in frames, the halo (frames before a span that it transforms again), the share
+ *     of transforms that are such repeats, the grid and the LDS bytes; under heavy overlap with little work (the halo sets S and few
+ *     workgroups run) it says so.  t may be NULL (the library call).  Host arithmetic only. */
+int bhw_istft_fft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                             const float *d_Y, float *d_x);
+int bhw_istft_fft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                 const float *d_Y, float *d_x);
+int bhw_describe_istft_fft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf, uint64_t len);
 
 /* Threading: every entry point may be called from any host thread.  Calls that use the library-owned scratch of one
  * (device, stream) are serialised against each other for the duration of their launches (the table is rebuilt per call);
