@@ -46,6 +46,7 @@ ABI_SYMBOLS = (
     "bhw_welch_csd_workspace_bytes", "bhw_welch_csd_f32", "bhw_describe_csd",
     "bhw_stft_fft_f32_device", "bhw_stft_fft_f32_from_table", "bhw_describe_stft_fft",
     "bhw_istft_fft_f32_device", "bhw_istft_fft_f32_from_table", "bhw_describe_istft_fft",
+    "bhw_spectrogram_f32_device", "bhw_spectrogram_f32_from_table", "bhw_describe_spectrogram",
 )
 
 
@@ -126,6 +127,22 @@ def make_stft(batch, samples, frames, hop, n_fft, *, col0=0, pad=0, pad_mode=0, 
     s.col0, s.pad, s.pad_mode, s.shift = int(col0), int(pad), int(pad_mode), int(shift)
     s.x_stride, s.y_stride, s.y_batch_stride = int(x_stride), int(y_stride), int(y_batch_stride)
     return s
+
+
+class BhwFbank(ctypes.Structure):
+    """struct bhw_fbank of include/bhw.h (the sparse filter bank of the fused spectrogram)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("filters", ctypes.c_uint32), ("bins", ctypes.c_uint32), ("weights", ctypes.c_uint32),
+                ("d_first", ctypes.c_void_p), ("d_offset", ctypes.c_void_p), ("d_weight", ctypes.c_void_p), ("reserved", ctypes.c_uint64)]
+
+
+def make_fbank(filters, bins, weights, d_first, d_offset, d_weight):
+    """A bhw_fbank over three device arrays given as addresses (ints or None): d_first (filters uint32), d_offset (filters + 1
+    uint32) and d_weight (weights float32)."""
+    fb = BhwFbank()
+    fb.struct_size = ctypes.sizeof(BhwFbank)
+    fb.filters, fb.bins, fb.weights = int(filters), int(bins), int(weights)
+    fb.d_first, fb.d_offset, fb.d_weight = d_first, d_offset, d_weight
+    return fb
 
 
 class BhwPsd(ctypes.Structure):
@@ -295,6 +312,10 @@ def lib():
     L.bhw_istft_fft_f32_device.argtypes = [P, u64, ci, vp, S, u32, f32p, f32p]
     L.bhw_istft_fft_f32_from_table.argtypes = [T, P, u64, vp, S, u32, f32p, f32p]
     L.bhw_describe_istft_fft.argtypes = [T, P, u64, S, u32, ctypes.c_char_p, u64]
+    FB = ctypes.POINTER(BhwFbank)
+    L.bhw_spectrogram_f32_device.argtypes = [P, u64, ci, vp, S, u32, FB, f32p, f32p]
+    L.bhw_spectrogram_f32_from_table.argtypes = [T, P, u64, vp, S, u32, FB, f32p, f32p]
+    L.bhw_describe_spectrogram.argtypes = [T, P, u64, S, u32, FB, ctypes.c_char_p, u64]
     PA = ctypes.POINTER(BhwAtan2Params)
     L.bhw_atan2_device.argtypes = [PA, ci, vp, u64, i32p, i32p, i32p]
     L.bhw_atan2_to_host.argtypes = [PA, ci, u64, i32p, i32p, i32p]
@@ -434,6 +455,18 @@ def describe_istft_fft(params, length, stft, *, normalize=False, table=None):
     buf = ctypes.create_string_buffer(1024)
     check(lib().bhw_describe_istft_fft(table, ctypes.byref(params), int(length), ctypes.byref(stft),
                                        OLA_NORMALIZE if normalize else 0, buf, len(buf)))
+    return buf.value.decode()
+
+
+def describe_spectrogram(params, length, stft, *, detrend=False, fbank=None, table=None):
+    """One line: the plan fields of describe_stft_fft in the same words, the mode (power or bank), W, and for a bank its filters,
+    weights and filters per lane, for a fused spectrogram call over the window of `length` with the descriptor `stft` (a BhwStft,
+    make_stft; its y strides count floats of output rows) and `fbank` (a BhwFbank, make_fbank, or None) (bhw_describe_spectrogram).
+    `table` is a resident table handle or None for the library call.  Host arithmetic only."""
+    buf = ctypes.create_string_buffer(1024)
+    check(lib().bhw_describe_spectrogram(table, ctypes.byref(params), int(length), ctypes.byref(stft),
+                                         WELCH_DETREND_CONSTANT if detrend else 0, ctypes.byref(fbank) if fbank is not None else None,
+                                         buf, len(buf)))
     return buf.value.decode()
 
 

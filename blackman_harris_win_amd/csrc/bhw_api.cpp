@@ -1141,6 +1141,19 @@ int stft_fft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, 
                                                               const BhwLenPhase *lp) { return bhwk_stft_fft_f32(l, c, w, pl, s, d_x, d_Y, tab, *lp); });
 }
 
+// The fused spectrogram (t NULL: the direct CORDIC chains): the checks, then the one kernel.
+int spectrogram_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *s, uint32_t flags,
+                    const bhw_fbank *fb, const float *d_x, float *d_P)
+{
+    int rc = bhwp_spectrogram_checks(p, length, s, flags, fb, d_x, d_P);
+    if (!rc && t) rc = table_call_checks(t, p);
+    if (rc || !s->frames) return rc;
+    const BhwStftFftPlan pl = bhwp_spectrogram_plan(p, length, s, flags, fb, t != nullptr);
+    const char *what = t ? "spectrogram launch (resident table)" : "spectrogram launch";
+    return run_source(t, p, length, device, stream, what, [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *tab,
+                                                              const BhwLenPhase *lp) { return bhwk_spectrogram_f32(l, c, w, pl, s, fb, d_x, d_P, tab, *lp); });
+}
+
 // The fused inverse FFT + overlap-add (t NULL: the direct CORDIC chains): the checks, then the one kernel.
 int istft_fft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *s, uint32_t flags,
                   const float *d_Y, float *d_x)
@@ -1352,6 +1365,30 @@ int bhw_describe_stft_fft(bhw_table t, const bhw_params *p, uint64_t length, con
     int rc = bhwp_stft_fft_checks(p, length, s, flags, nullptr, nullptr, false);
     if (!rc && t) rc = table_call_checks(t, p);
     return rc ? rc : bhwp_describe_stft_fft(p, t ? &t->c : nullptr, length, s, flags, buf, len);
+}
+
+// ---- fused power and filter-bank spectrogram (include/bhw.h: bhw_spectrogram_f32_device ...) -------------------------------------------
+
+int bhw_spectrogram_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                               const bhw_fbank *fb, const float *d_x, float *d_P)
+{
+    return spectrogram_run(nullptr, p, length, device, hip_stream, s, flags, fb, d_x, d_P);
+}
+
+int bhw_spectrogram_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                   const bhw_fbank *fb, const float *d_x, float *d_P)
+{
+    const int rc = bhwp_spectrogram_checks(p, length, s, flags, fb, d_x, d_P);
+    if (rc) return rc;
+    return t ? spectrogram_run(t, p, length, t->device, hip_stream, s, flags, fb, d_x, d_P) : fail(BHW_ERR_BADARG, "table is NULL");
+}
+
+int bhw_describe_spectrogram(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const bhw_fbank *fb,
+                             char *buf, uint64_t len)
+{
+    int rc = bhwp_spectrogram_checks(p, length, s, flags, fb, nullptr, nullptr, false);
+    if (!rc && t) rc = table_call_checks(t, p);
+    return rc ? rc : bhwp_describe_spectrogram(p, t ? &t->c : nullptr, length, s, flags, fb, buf, len);
 }
 
 // ---- fused inverse real FFT, window and overlap-add (include/bhw.h: bhw_istft_fft_f32_device ...) --------------------------------------

@@ -1622,6 +1622,107 @@ int bhwp_describe_stft_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t
     return BHW_OK;
 }
 
+// ---- fused power and filter-bank spectrogram ---------------------------------------------------------------------------------------------
+
+int bhwp_spectrogram_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const bhw_fbank *fb, const void *d_x,
+                            const void *d_P, bool pointers)
+{
+    // the input side: the forward call's checks for the descriptor with packed output strides (they count other rows here)
+    bhw_stft t{};
+    if (s && s->struct_size == sizeof(bhw_stft)) {
+        t = *s;
+        t.y_stride = t.y_batch_stride = 0;
+    }
+    int rc = bhwp_stft_fft_checks(p, length, s && s->struct_size == sizeof(bhw_stft) ? &t : s, flags, nullptr, nullptr, false);
+    if (rc) return rc;
+    const uint64_t T = s->samples, F = s->frames, K = s->n_fft / 2 + 1;
+    if (fb) {
+        if (fb->struct_size != sizeof(bhw_fbank))
+            return bhwp_fail(BHW_ERR_BADARG, "bhw_fbank.struct_size %u != %zu", fb->struct_size, sizeof(bhw_fbank));
+        if (fb->reserved) return bhwp_fail(BHW_ERR_BADARG, "bhw_fbank.reserved is not 0");
+        if (fb->filters < 1 || fb->filters > kSpecMaxFilters)
+            return bhwp_fail(BHW_ERR_BADARG, "bhw_fbank.filters %u outside 1..%u", fb->filters, kSpecMaxFilters);
+        if (fb->bins != K)
+            return bhwp_fail(BHW_ERR_BADARG, "bhw_fbank.bins %u: the call has n_fft / 2 + 1 = %llu bins", fb->bins, (unsigned long long)K);
+        if (fb->weights > kSpecMaxWeights) return bhwp_fail(BHW_ERR_BADARG, "bhw_fbank.weights %u above 2^24", fb->weights);
+    }
+    if (!F) return BHW_OK;
+    const uint64_t W = fb ? fb->filters : K;
+    if ((unsigned __int128)s->batch * F * W > (1ull << 34)) return bhwp_fail(BHW_ERR_BADARG, "batch * frames * W above 2^34 per call");
+    if (s->y_stride && s->y_stride < W)
+        return bhwp_fail(BHW_ERR_BADARG, "y_stride %llu: at least W = %llu floats", (unsigned long long)s->y_stride, (unsigned long long)W);
+    const uint64_t ys = s->y_stride ? s->y_stride : W;
+    const unsigned __int128 ysig = (unsigned __int128)(F - 1) * ys + W;
+    if (ysig > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "P extent beyond 2^60 elements");
+    if (s->y_batch_stride && s->y_batch_stride < (uint64_t)ysig)
+        return bhwp_fail(BHW_ERR_BADARG, "y_batch_stride %llu: at least (frames - 1) * y_stride + W = %llu floats",
+                         (unsigned long long)s->y_batch_stride, (unsigned long long)ysig);
+    if (!pointers) return BHW_OK;
+    if (!d_x || !d_P) return bhwp_fail(BHW_ERR_BADARG, "d_x / d_P is NULL");
+    if ((uintptr_t)d_P % 4) return bhwp_fail(BHW_ERR_BADARG, "d_P is not 4-byte aligned");
+    if ((uintptr_t)d_x % 4) return bhwp_fail(BHW_ERR_BADARG, "d_x is not 4-byte aligned");
+    const uint64_t xs = s->x_stride ? s->x_stride : T, ybs = s->y_batch_stride ? s->y_batch_stride : F * ys;
+    const unsigned __int128 xe = (unsigned __int128)(s->batch - 1) * xs + T, ye = (unsigned __int128)(s->batch - 1) * ybs + ysig;
+    if (xe > (1ull << 60) || ye > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "x or P extent beyond 2^60 elements");
+    const uint64_t xa = (uint64_t)(uintptr_t)d_x, ya = (uint64_t)(uintptr_t)d_P, xb = (uint64_t)xe * 4u, yb = (uint64_t)ye * 4u;
+    if (xa > UINT64_MAX - xb || ya > UINT64_MAX - yb) return bhwp_fail(BHW_ERR_BADARG, "x or P range wraps the address space");
+    if (xa < ya + yb && ya < xa + xb) return bhwp_fail(BHW_ERR_BADARG, "d_x and d_P overlap");
+    if (fb) {
+        if (!fb->d_first || !fb->d_offset) return bhwp_fail(BHW_ERR_BADARG, "bhw_fbank.d_first / d_offset is NULL");
+        if (!fb->d_weight && fb->weights) return bhwp_fail(BHW_ERR_BADARG, "bhw_fbank.d_weight is NULL with %u weights", fb->weights);
+        const void *ptr[3] = {fb->d_first, fb->d_offset, fb->d_weight};
+        const uint64_t nb[3] = {(uint64_t)fb->filters * 4u, ((uint64_t)fb->filters + 1u) * 4u, (uint64_t)fb->weights * 4u};
+        static const char *const what[3] = {"d_first", "d_offset", "d_weight"};
+        for (int i = 0; i < 3; ++i) {
+            const uint64_t a = (uint64_t)(uintptr_t)ptr[i];
+            if (a % 4) return bhwp_fail(BHW_ERR_BADARG, "bhw_fbank.%s is not 4-byte aligned", what[i]);
+            if (a > UINT64_MAX - nb[i]) return bhwp_fail(BHW_ERR_BADARG, "bhw_fbank.%s range wraps the address space", what[i]);
+            if (nb[i] && a < ya + yb && ya < a + nb[i]) return bhwp_fail(BHW_ERR_BADARG, "bhw_fbank.%s and d_P overlap", what[i]);
+        }
+    }
+    return BHW_OK;
+}
+
+BhwStftFftPlan bhwp_spectrogram_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const bhw_fbank *fb,
+                                     bool from_table)
+{
+    BhwStftFftPlan pl = bhwp_stft_fft_plan(p, length, s, flags, from_table);
+    const uint64_t W = fb ? fb->filters : s->n_fft / 2 + 1;
+    pl.y_stride = s->y_stride ? s->y_stride : W;
+    pl.y_bstride = s->y_batch_stride ? s->y_batch_stride : s->frames * pl.y_stride;
+    return pl;
+}
+
+int bhwp_describe_spectrogram(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags,
+                              const bhw_fbank *fb, char *buf, uint64_t len)
+{
+    if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
+    const char *route = ct ? "table" : "direct";
+    const BhwStftFftPlan pl = bhwp_spectrogram_plan(p, length, s, flags, fb, ct != nullptr);
+    const char *pad = s->pad_mode == BHW_PAD_REFLECT ? "reflect" : "constant";
+    const char *det = pl.detrend ? "constant detrend" : "no detrending";
+    const uint64_t W = fb ? fb->filters : s->n_fft / 2 + 1;
+    char mode[96];
+    if (fb) snprintf(mode, sizeof mode, "bank mode, W = %llu (%u filters, %u weights, %u filters per lane)", (unsigned long long)W, fb->filters,
+                     fb->weights, (fb->filters + pl.lpf - 1) / pl.lpf);
+    else    snprintf(mode, sizeof mode, "power mode, W = %llu", (unsigned long long)W);
+    if (!s->frames) {
+        snprintf(buf, len, "spectrogram %s (L = %llu, n_fft %llu, %s), %s: nothing (frames 0)", route, (unsigned long long)length,
+                 (unsigned long long)s->n_fft, det, mode);
+        return BHW_OK;
+    }
+    char kern[64], sched[48];
+    kernel_name(p, ct, "k_spectrogram_direct", "k_spectrogram_table", false, kern, sizeof kern);
+    bhwp_stft_fft_schedule(pl, sched, sizeof sched);
+    snprintf(buf, len, "spectrogram %s (L = %llu, n_fft %llu, col0 %llu, pad %llu %s, %s), %s: %s, %llu signals x %llu frames = %llu rows, "
+             "complex FFT of %u points in passes %s + split, %u lanes per row x %u rows per workgroup, %u columns per lane, %llu groups, "
+             "grid %llu x %u lanes, %u bytes of LDS", route, (unsigned long long)length, (unsigned long long)s->n_fft,
+             (unsigned long long)s->col0, (unsigned long long)s->pad, pad, det, mode, kern, (unsigned long long)s->batch,
+             (unsigned long long)s->frames, (unsigned long long)pl.rows, pl.m, sched, pl.lpf, pl.fy, pl.cpl, (unsigned long long)pl.groups,
+             (unsigned long long)pl.grid, kFftBlock, pl.lds_bytes);
+    return BHW_OK;
+}
+
 // ---- fused inverse real FFT, window and overlap-add -----------------------------------------------------------------------------------------
 
 int bhwp_istft_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const void *d_Y, const void *d_x,

@@ -456,6 +456,23 @@ int  bhwp_describe_stft_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64_
 int  bhwk_stft_fft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwStftFftPlan &pl, const bhw_stft *s,
                        const float *d_x, float *d_Y, const int32_t *d_table, const BhwLenPhase &lp);
 
+// ---- fused power and filter-bank spectrogram (bhw_spectrogram_f32_*; bhw_spectrogram.hip) ----------------------------------------------
+// The forward kernel with another epilogue: the plan is bhwp_stft_fft_plan's (lanes per row, rows per workgroup, columns per lane,
+// schedule, groups, grid, LDS bytes) with y_stride / y_bstride resolved in floats of the output rows of W = K (power) or filters (bank).
+constexpr uint32_t kSpecMaxFilters = 4096;
+constexpr uint32_t kSpecMaxWeights = 1u << 24;
+// Every check of the two calls that needs no table handle, before any HIP call (include/bhw.h): the input side by
+// bhwp_stft_fft_checks, the bank's fields, the output rules with W in place of 2K, the pointers.  frames 0 passes with the pointers
+// unchecked; `pointers` false: the describe call.
+int  bhwp_spectrogram_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const bhw_fbank *fb, const void *d_x,
+                             const void *d_P, bool pointers = true);
+BhwStftFftPlan bhwp_spectrogram_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const bhw_fbank *fb,
+                                     bool from_table);
+int  bhwp_describe_spectrogram(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags,
+                               const bhw_fbank *fb, char *buf, uint64_t len);
+int  bhwk_spectrogram_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwStftFftPlan &pl, const bhw_stft *s,
+                          const bhw_fbank *fb, const float *d_x, float *d_P, const int32_t *d_table, const BhwLenPhase &lp);
+
 // ---- fused inverse real FFT, window and overlap-add (bhw_istft_fft_f32_*; bhw_istft_fft.hip) ------------------------------------------
 // The lane layout of the forward kernel (lpf lanes along a row, fy slots side by side, cpl columns per lane).  The window-start axis
 // w = t + pad - col0 of every signal (frame f covers w in [f * hop, f * hop + L)) is cut into spans of S * hop positions; the spans

@@ -470,21 +470,26 @@ def _fft_input(torch, x, n_fft, dev):
         raise ValueError(f"the fused FFT takes n_fft a power of two in {B.FFT_MIN_N}..{B.FFT_MAX_N}, got {int(n_fft)}")
 
 
-def _fft_out(torch, out, shape, x):
-    """The spectrum tensor and its strides in floats: allocated packed, or the caller's complex64 `out` of `shape` (bins contiguous,
-    rows and signals apart; the gaps of a wider buffer are left alone)."""
+def _fft_out(torch, out, shape, x, dtype=None):
+    """The output tensor and its strides in floats: allocated packed, or the caller's `out` of `shape` and `dtype` (complex64 spectrum
+    rows by default, float32 for the spectrogram), the last axis contiguous, rows and signals apart; the gaps of a wider buffer are
+    left alone."""
+    dtype = torch.complex64 if dtype is None else dtype
+    floats = 2 if dtype == torch.complex64 else 1
     nb, F, K = shape[-3] if len(shape) == 3 else 1, shape[-2], shape[-1]
     if out is None:
-        return torch.empty(shape, dtype=torch.complex64, device=x.device), 0, 0
-    ok = isinstance(out, torch.Tensor) and out.dtype == torch.complex64 and out.device == x.device and tuple(out.shape) == tuple(shape) \
+        return torch.empty(shape, dtype=dtype, device=x.device), 0, 0
+    ok = isinstance(out, torch.Tensor) and out.dtype == dtype and out.device == x.device and tuple(out.shape) == tuple(shape) \
         and not out.is_conj() and not out.is_neg() and out.stride(-1) == 1
     if ok and F > 1:
         ok = out.stride(-2) >= K
     if ok and len(shape) == 3 and nb > 1:
         ok = out.stride(0) >= (F - 1) * (out.stride(-2) if F > 1 else K) + K
     if not ok:
-        raise ValueError(f"out must be a complex64 tensor of shape {tuple(shape)} on x's device, contiguous along the bins, rows and signals apart")
-    return out, (out.stride(-2) * 2 if F > 1 else 0), (out.stride(0) * 2 if len(shape) == 3 and nb > 1 else 0)
+        name = str(dtype).replace("torch.", "")
+        last = "bins" if floats == 2 else "columns"
+        raise ValueError(f"out must be a {name} tensor of shape {tuple(shape)} on x's device, contiguous along the {last}, rows and signals apart")
+    return out, (out.stride(-2) * floats if F > 1 else 0), (out.stride(0) * floats if len(shape) == 3 and nb > 1 else 0)
 
 
 def _fft_launch(torch, params, L, s, flags, xr, out, dev, table):
@@ -496,7 +501,9 @@ def _fft_launch(torch, params, L, s, flags, xr, out, dev, table):
     return out
 
 
-def _stft(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, shift, out, dev, table):
+def _stft_front(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, dev):
+    """The input checks and the framing every fused forward call shares (stft, spectrogram): (n_fft, L, the x read, its (nb, T),
+    frames, and the descriptor's hop, col0, pad, pad_mode)."""
     n_fft, L, col0 = _stft_window(params, n_fft, win_length)
     _fft_input(torch, x, n_fft, dev)
     hop = int(hop)
@@ -519,10 +526,15 @@ def _stft(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, s
         raise ValueError(f"zero frames: T + 2 * pad = {T + 2 * pad} < {reach}" if nb else "zero signals")
     frames = 1 + (T + 2 * pad - reach) // hop
     xb = _stft_input(xb, (T,))
+    return n_fft, L, xb, nb, T, frames, dict(hop=hop, col0=col0, pad=pad, pad_mode=mode)
+
+
+def _stft(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, shift, out, dev, table):
+    n_fft, L, xb, nb, T, frames, d = _stft_front(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, dev)
     K = n_fft // 2 + 1
     out, ys, ybs = _fft_out(torch, out, (nb, frames, K) if x.dim() == 2 else (frames, K), x)
     shift = params.dat_width - 1 if shift is None else int(shift)
-    s = B.make_stft(nb, T, frames, hop, n_fft, col0=col0, pad=pad, pad_mode=mode, shift=shift,
+    s = B.make_stft(nb, T, frames, d["hop"], n_fft, col0=d["col0"], pad=d["pad"], pad_mode=d["pad_mode"], shift=shift,
                     x_stride=xb.stride(0) if nb > 1 else 0, y_stride=ys, y_batch_stride=ybs)
     return _fft_launch(torch, params, L, s, B.WELCH_DETREND_CONSTANT if detrend else 0, xb, out, dev, table)
 
@@ -604,6 +616,181 @@ def istft(params, Y, n_fft, hop, *, win_length=None, center=True, length=None, n
     if not isinstance(Y, torch.Tensor) or not Y.is_cuda:
         raise ValueError("Y must be a complex64 CUDA tensor")
     return _istft(torch, params, Y, n_fft, hop, win_length, center, length, normalize, shift, out, Y.device.index, None)
+
+
+# ---- fused power and filter-bank spectrogram ---------------------------------------------------------------------------------------------
+
+def fbank_bands(weights):
+    """The sparse form of a dense (K, filters) bank, on the host: (first, offset, weight) as numpy uint32, uint32 and float32 arrays.
+    Filter m's band runs from its first to its last nonzero weight (interior zeros are kept as weights) and owns
+    weight[offset[m] : offset[m + 1]], which multiplies the bins first[m], first[m] + 1, ...; an all-zero filter has an empty band
+    (first 0).  -0.0 counts as zero."""
+    import numpy as np
+    w = np.asarray(weights)
+    if w.ndim != 2 or w.shape[0] < 1 or w.shape[1] < 1:
+        raise ValueError("a filter bank is a dense (bins, filters) array")
+    if w.dtype.kind not in "fiu":
+        raise ValueError(f"a filter bank holds real weights, got {w.dtype}")
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    if not np.isfinite(w).all():
+        raise ValueError("a filter bank's weights must be finite")
+    K, M = w.shape
+    first = np.zeros(M, dtype=np.uint32)
+    offset = np.zeros(M + 1, dtype=np.uint32)
+    parts = []
+    for m in range(M):
+        nz = np.flatnonzero(w[:, m])
+        if nz.size:
+            first[m] = nz[0]
+            parts.append(w[nz[0]:nz[-1] + 1, m])
+            offset[m + 1] = offset[m] + (nz[-1] + 1 - nz[0])
+        else:
+            offset[m + 1] = offset[m]
+    weight = np.concatenate(parts) if parts else np.zeros(0, dtype=np.float32)
+    return first, offset, np.ascontiguousarray(weight, dtype=np.float32)
+
+
+def fbank_dense(first, offset, weight, bins):
+    """The dense (bins, filters) float32 array of a sparse bank (the inverse of fbank_bands), on the host."""
+    import numpy as np
+    M = len(first)
+    w = np.zeros((int(bins), M), dtype=np.float32)
+    for m in range(M):
+        c = int(offset[m + 1]) - int(offset[m])
+        w[int(first[m]):int(first[m]) + c, m] = weight[int(offset[m]):int(offset[m + 1])]
+    return w
+
+
+class FilterBank:
+    """A filter bank for spectrogram(), built ONCE from a dense (K, filters) float array or tensor -- the layout of
+    torchaudio.functional.melscale_fbanks and of mel_weights() -- and kept on `device` in the sparse form of bhw_fbank: per filter
+    the band from its first to its last nonzero weight (interior zeros kept, an all-zero filter empty).  The contents are validated
+    here, so a call never hands the kernel an inconsistent bank; the upload (and its one synchronisation, when the weights come from
+    a device tensor) happens here and never in spectrogram().  filters, bins, weights: the counts; dense(): the (K, filters) float32
+    numpy array the bank stands for."""
+
+    MAX_FILTERS, MAX_WEIGHTS = 4096, 1 << 24
+
+    def __init__(self, weights, device=None):
+        import numpy as np
+        torch = _torch()
+        if isinstance(weights, torch.Tensor):
+            if device is None and weights.is_cuda:
+                device = weights.device
+            weights = weights.detach().cpu().numpy()
+        first, offset, weight = fbank_bands(weights)
+        K, M = np.asarray(weights).shape
+        if M > self.MAX_FILTERS:
+            raise ValueError(f"{M} filters: a bank holds 1..{self.MAX_FILTERS}")
+        if weight.size > self.MAX_WEIGHTS:
+            raise ValueError(f"{weight.size} weights: a bank holds 2^24 at most")
+        assert offset[0] == 0 and offset[-1] == weight.size and (np.diff(offset.astype(np.int64)) >= 0).all()
+        assert ((first.astype(np.int64) + np.diff(offset.astype(np.int64))) <= K).all()
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise ValueError("a FilterBank lives on a CUDA device")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.device = dev
+        self.filters, self.bins, self.weights = int(M), int(K), int(weight.size)
+        self._host = (first, offset, weight)
+        # uint32 words travel as int32 tensors of the same bits
+        self._first = torch.from_numpy(first.view(np.int32)).to(dev)
+        self._offset = torch.from_numpy(offset.view(np.int32)).to(dev)
+        self._weight = torch.from_numpy(weight if weight.size else np.zeros(1, dtype=np.float32)).to(dev)
+        self.descriptor = B.make_fbank(M, K, weight.size, self._first.data_ptr(), self._offset.data_ptr(), self._weight.data_ptr())
+
+    def dense(self):
+        return fbank_dense(*self._host, self.bins)
+
+    def __repr__(self):
+        return f"FilterBank(filters={self.filters}, bins={self.bins}, weights={self.weights}, device={self.device})"
+
+
+def mel_weights(n_fft, n_mels, sample_rate, *, f_min=0.0, f_max=None, norm=None, mel_scale="htk"):
+    """The mel filter bank of torchaudio.functional.melscale_fbanks(n_fft // 2 + 1, f_min, f_max, n_mels, sample_rate, norm,
+    mel_scale), restated: a host numpy float32 array (K, n_mels), K = n_fft // 2 + 1, computed in float64 and rounded once.
+    all_freqs = linspace(0, sample_rate // 2, K); n_mels + 2 points equally spaced in mel between f_min and f_max (default
+    sample_rate / 2); filter m is the triangle max(0, min(up, down)) over points m, m + 1, m + 2; norm="slaney" scales filter m by
+    2 / (f[m + 2] - f[m]).  mel_scale: "htk" (2595 log10(1 + f / 700)) or "slaney" (linear below 1 kHz, logarithmic above).
+    FilterBank(mel_weights(...), device=...) is the mel bank of spectrogram()."""
+    import numpy as np
+    n_fft, n_mels = int(n_fft), int(n_mels)
+    if n_fft < 2 or n_mels < 1:
+        raise ValueError("n_fft must be >= 2 and n_mels >= 1")
+    if mel_scale not in ("htk", "slaney"):
+        raise ValueError(f"mel_scale must be 'htk' or 'slaney', got {mel_scale!r}")
+    if norm not in (None, "slaney"):
+        raise ValueError(f"norm must be None or 'slaney', got {norm!r}")
+    f_max = float(sample_rate) / 2 if f_max is None else float(f_max)
+    f_min = float(f_min)
+    if not 0.0 <= f_min < f_max:
+        raise ValueError(f"need 0 <= f_min < f_max, got {f_min}, {f_max}")
+    f_sp, min_log_hz, logstep = 200.0 / 3, 1000.0, np.log(6.4) / 27.0
+    min_log_mel = min_log_hz / f_sp
+
+    def to_mel(f):
+        if mel_scale == "htk":
+            return 2595.0 * np.log10(1.0 + f / 700.0)
+        return f / f_sp if f < min_log_hz else min_log_mel + np.log(f / min_log_hz) / logstep
+
+    def to_hz(m):
+        if mel_scale == "htk":
+            return 700.0 * (10.0 ** (m / 2595.0) - 1.0)
+        return np.where(m >= min_log_mel, min_log_hz * np.exp(logstep * (m - min_log_mel)), f_sp * m)
+
+    K = n_fft // 2 + 1
+    all_freqs = np.linspace(0.0, float(int(sample_rate) // 2), K)
+    f_pts = to_hz(np.linspace(to_mel(f_min), to_mel(f_max), n_mels + 2))
+    f_diff = f_pts[1:] - f_pts[:-1]
+    slopes = f_pts[None, :] - all_freqs[:, None]
+    down = -slopes[:, :-2] / f_diff[:-1]
+    up = slopes[:, 2:] / f_diff[1:]
+    fb = np.maximum(0.0, np.minimum(down, up))
+    if norm == "slaney":
+        fb = fb * (2.0 / (f_pts[2:n_mels + 2] - f_pts[:n_mels]))[None, :]
+    return np.ascontiguousarray(fb, dtype=np.float32)
+
+
+def _spectrogram(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, fbank, shift, out, dev, table):
+    n_fft, L, xb, nb, T, frames, d = _stft_front(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, dev)
+    K = n_fft // 2 + 1
+    if fbank is not None:
+        if not isinstance(fbank, FilterBank):
+            raise ValueError("fbank must be a FilterBank (FilterBank(dense_weights, device=...)) or None")
+        if fbank.bins != K:
+            raise ValueError(f"the filter bank has {fbank.bins} bins, n_fft // 2 + 1 is {K}")
+        if fbank.device != x.device:
+            raise ValueError(f"the filter bank is on {fbank.device}, x on {x.device}")
+    W = K if fbank is None else fbank.filters
+    out, ys, ybs = _fft_out(torch, out, (nb, frames, W) if x.dim() == 2 else (frames, W), x, torch.float32)
+    shift = params.dat_width - 1 if shift is None else int(shift)
+    s = B.make_stft(nb, T, frames, d["hop"], n_fft, col0=d["col0"], pad=d["pad"], pad_mode=d["pad_mode"], shift=shift,
+                    x_stride=xb.stride(0) if nb > 1 else 0, y_stride=ys, y_batch_stride=ybs)
+    tail = (ctypes.byref(s), B.WELCH_DETREND_CONSTANT if detrend else 0, ctypes.byref(fbank.descriptor) if fbank is not None else None,
+            ctypes.c_void_p(xb.data_ptr()), ctypes.c_void_p(out.data_ptr()))
+    if table is None:
+        B.check(B.lib().bhw_spectrogram_f32_device(ctypes.byref(params), L, dev, _stream_ptr(torch, dev), *tail))
+    else:
+        B.check(B.lib().bhw_spectrogram_f32_from_table(table, ctypes.byref(params), L, _stream_ptr(torch, dev), *tail))
+    return out
+
+
+def spectrogram(params, x, n_fft, hop, *, win_length=None, center=True, pad_mode="reflect", detrend=False, fbank=None, shift=None,
+                out=None):
+    """The power spectrogram of a batch, or its filter-bank (mel) spectrogram, in ONE launch (bhw_spectrogram_f32_device): x (T,) or
+    (B, T), real float32, framed, windowed and transformed exactly as stft() does (same arguments), and each bin written as
+    fl32(re^2 + im^2) of the float32 pair stft() would have written -- bit for bit -- so the complex spectrum never reaches memory.
+    With fbank (a FilterBank, e.g. FilterBank(mel_weights(n_fft, 80, 16000), device=x.device)) the powers stay in the kernel too
+    and each row is folded through the bank: column m is the binary64 sum, in ascending bin order, of power * weight over filter
+    m's band, rounded once to float32.  Returns float32 (B, F, W) or (F, W) for 1-D x, W = n_fft // 2 + 1 or fbank.filters;
+    `.transpose(-1, -2)` gives torchaudio's (..., freq, time) layout.  log, magnitude and a complex output next to the power are
+    not built: apply torch.log to the small result.  n_fft: a power of two in 16..4096 (ValueError otherwise; complex x too).
+    `out`: float32 of the returned shape, columns contiguous, rows and signals apart (its gaps are left alone)."""
+    torch = _torch()
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise ValueError("x must be a float32 CUDA tensor")
+    return _spectrogram(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, fbank, shift, out, x.device.index, None)
 
 
 def _welch_fft(torch, params, x, length, hop, nfft, detrend, shift, out, dev, table):
@@ -1166,6 +1353,13 @@ class ResidentTable:
         """stft() with the coefficients gathered from this table (bhw_stft_fft_f32_from_table): no allocation by the library, no
         synchronisation, capturable into a graph on its first call."""
         return _stft(_torch(), params, x, n_fft, hop, win_length, center, pad_mode, detrend, shift, out, self.device, self._live())
+
+    def spectrogram(self, params, x, n_fft, hop, *, win_length=None, center=True, pad_mode="reflect", detrend=False, fbank=None,
+                    shift=None, out=None):
+        """spectrogram() with the coefficients gathered from this table (bhw_spectrogram_f32_from_table): no allocation by the
+        library, no synchronisation, capturable into a graph on its first call."""
+        return _spectrogram(_torch(), params, x, n_fft, hop, win_length, center, pad_mode, detrend, fbank, shift, out, self.device,
+                            self._live())
 
     def istft(self, params, Y, n_fft, hop, *, win_length=None, center=True, length=None, normalize=True, shift=None, out=None):
         """istft() with the coefficients gathered from this table (bhw_istft_fft_f32_from_table): no allocation by the library, no

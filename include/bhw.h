@@ -757,6 +757,54 @@ int bhw_istft_fft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t leng
                                  const float *d_Y, float *d_x);
 int bhw_describe_istft_fft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf, uint64_t len);
 
+/* Fused power and filter-bank spectrogram: the rows of bhw_stft_fft_f32_* formed and transformed by the same kernel body, and
+ * written as |Y|^2 per bin or as those powers folded through a sparse filter bank (a mel bank, say), by ONE launch.  The spectrum
+ * never reaches memory, so the call takes no workspace.
+ *   - Row and transform: exactly those of bhw_stft_fft_f32_* for the same (p, length, s, flags); flags is 0 or
+ *     BHW_WELCH_DETREND_CONSTANT.  Let (re, im) be the float32 pair that call writes for bin k of row (b, f), bit for bit.
+ *   - Power, fb == NULL, W = K = n_fft / 2 + 1:
+ *         d_P[b * y_batch_stride + f * y_stride + k] = fl32((double) re * (double) re + (double) im * (double) im)
+ *     Both squares are exact in binary64 and the sum is one rounding (a fused multiply-add gives the same value), then one rounding
+ *     to float32: the periodogram's q_f, rounded.
+ *   - Filter bank, fb != NULL, W = filters.  With c_m = offset[m + 1] - offset[m] and P the float32 power above:
+ *         d_P[... + m] = fl32(sum over i < c_m of (double) P[first[m] + i] * (double) weight[offset[m] + i])
+ *     in ASCENDING i, in binary64, from +0.0 (each product is exact, so a fused multiply-add gives the same value).  c_m = 0 gives +0.0.
+ *   - Strides: y_stride and y_batch_stride count FLOATS between output rows and between signals; 0 means W and frames * y_stride.
+ *     No evenness rule applies; d_P is 4-byte aligned.  Only the W floats of each row are written.
+ *   - Determinism: the bits of an output row depend on the window, n_fft, flags, the bank and that row's samples only -- not on the
+ *     batch, the plan, the slot, the strides, or library versus table.
+ *   - IEEE: a NaN or an infinity in x reaches only the rows whose window covers it.
+ *   - Memory safety of the bank: the host cannot read the device arrays, so the kernel is safe whatever they hold: offset[m] and
+ *     offset[m + 1] are clamped to [0, weights] with end >= begin, and a band stops at bin K.  A wrong bank gives wrong numbers and
+ *     never an access outside d_weight or the power row.  (d_first holds `filters` and d_offset `filters + 1` readable entries.)
+ *   - Checks before any HIP call (BHW_ERR_BADARG unless noted): everything bhw_stft_fft_f32_* checks on the input side (channels 2
+ *     and an unsupported n_fft stay BHW_ERR_UNSUPPORTED), its output-stride and overlap rules with W in place of 2 * K (and no
+ *     evenness), batch * frames * W above 2^34, and for fb: struct_size, reserved != 0, filters outside 1..4096, bins != K, weights
+ *     above 2^24, a NULL d_first or d_offset, a NULL d_weight with weights > 0, any of the three not 4-byte aligned or overlapping
+ *     d_P; and (from a table) the key match.  frames 0 returns BHW_OK with the pointers unchecked.
+ *   - Capture: as bhw_stft_fft_f32_*.  The library form makes no allocation, uses no scratch and is capturable with no
+ *     bhw_prepare_device; the from-table form is capturable on its first call.
+ *   - Not built: magnitude (power 1); log (the caller applies it to the small result); a complex output next to the power;
+ *     accumulating over frames in the kernel (Welch); complex input; other n_fft.
+ *   - bhw_describe_spectrogram: the plan fields of bhw_describe_stft_fft's line in the same words, plus the mode, W, and for a bank
+ *     filters, weights and filters per lane.  t may be NULL (the library call).  Host arithmetic only. */
+typedef struct bhw_fbank {
+    uint32_t struct_size;      /* sizeof(bhw_fbank) = 48                                                              */
+    uint32_t filters;          /* 1..4096 output columns                                                              */
+    uint32_t bins;             /* must equal n_fft / 2 + 1 of the call                                                */
+    uint32_t weights;          /* total weights, <= 2^24: the value d_offset[filters] must hold                       */
+    const uint32_t *d_first;   /* device, filters entries: first bin of filter m                                      */
+    const uint32_t *d_offset;  /* device, filters + 1 entries, ascending from 0: filter m owns d_weight[offset[m] .. offset[m+1]) */
+    const float *d_weight;     /* device, `weights` floats                                                            */
+    uint64_t reserved;         /* 0                                                                                   */
+} bhw_fbank;
+int bhw_spectrogram_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                               const bhw_fbank *fb, const float *d_x, float *d_P);
+int bhw_spectrogram_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                   const bhw_fbank *fb, const float *d_x, float *d_P);
+int bhw_describe_spectrogram(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const bhw_fbank *fb,
+                             char *buf, uint64_t len);
+
 /* Threading: every entry point may be called from any host thread.  Calls that use the library-owned scratch of one
  * (device, stream) are serialised against each other for the duration of their launches (the table is rebuilt per call);
  * callers that pass their own bhw_exec.workspace must not share one workspace between concurrent calls.  The calling
