@@ -47,6 +47,7 @@ ABI_SYMBOLS = (
     "bhw_stft_fft_f32_device", "bhw_stft_fft_f32_from_table", "bhw_describe_stft_fft",
     "bhw_istft_fft_f32_device", "bhw_istft_fft_f32_from_table", "bhw_describe_istft_fft",
     "bhw_spectrogram_f32_device", "bhw_spectrogram_f32_from_table", "bhw_describe_spectrogram",
+    "bhw_stft_cfft_f32_device", "bhw_stft_cfft_f32_from_table", "bhw_describe_stft_cfft",
 )
 
 
@@ -316,6 +317,9 @@ def lib():
     L.bhw_spectrogram_f32_device.argtypes = [P, u64, ci, vp, S, u32, FB, f32p, f32p]
     L.bhw_spectrogram_f32_from_table.argtypes = [T, P, u64, vp, S, u32, FB, f32p, f32p]
     L.bhw_describe_spectrogram.argtypes = [T, P, u64, S, u32, FB, ctypes.c_char_p, u64]
+    L.bhw_stft_cfft_f32_device.argtypes = [P, u64, ci, vp, S, u32, vp, vp]
+    L.bhw_stft_cfft_f32_from_table.argtypes = [T, P, u64, vp, S, u32, vp, vp]
+    L.bhw_describe_stft_cfft.argtypes = [T, P, u64, S, u32, ctypes.c_char_p, u64]
     PA = ctypes.POINTER(BhwAtan2Params)
     L.bhw_atan2_device.argtypes = [PA, ci, vp, u64, i32p, i32p, i32p]
     L.bhw_atan2_to_host.argtypes = [PA, ci, u64, i32p, i32p, i32p]
@@ -467,6 +471,27 @@ def describe_spectrogram(params, length, stft, *, detrend=False, fbank=None, tab
     check(lib().bhw_describe_spectrogram(table, ctypes.byref(params), int(length), ctypes.byref(stft),
                                          WELCH_DETREND_CONSTANT if detrend else 0, ctypes.byref(fbank) if fbank is not None else None,
                                          buf, len(buf)))
+    return buf.value.decode()
+
+
+CFFT_MIN_N, CFFT_MAX_N = 16, 2048        # n_fft of the fused window + complex FFT calls (I/Q input): a power of two in this range
+CFFT_POWER, CFFT_SHIFT = 2, 4            # BHW_CFFT_POWER, BHW_CFFT_SHIFT
+
+
+def cfft_supported(n_fft):
+    """True where bhw_stft_cfft_f32_* take n_fft: a power of two in 16..2048."""
+    n_fft = int(n_fft)
+    return CFFT_MIN_N <= n_fft <= CFFT_MAX_N and n_fft & (n_fft - 1) == 0
+
+
+def describe_stft_cfft(params, length, stft, *, detrend=False, power=False, fftshift=False, table=None):
+    """One line: the plan fields of describe_stft_fft in the same words for the complex transform of I/Q rows (no split pass), the
+    output form (spectrum or power rows), whether the bins are shifted, and the kernel, for a fused window + complex FFT call over
+    the window of `length` with the descriptor `stft` (a BhwStft with channels 2; its y strides count floats of output rows)
+    (bhw_describe_stft_cfft).  `table` is a resident table handle or None for the library call.  Host arithmetic only."""
+    buf = ctypes.create_string_buffer(1024)
+    flags = (WELCH_DETREND_CONSTANT if detrend else 0) | (CFFT_POWER if power else 0) | (CFFT_SHIFT if fftshift else 0)
+    check(lib().bhw_describe_stft_cfft(table, ctypes.byref(params), int(length), ctypes.byref(stft), flags, buf, len(buf)))
     return buf.value.decode()
 
 

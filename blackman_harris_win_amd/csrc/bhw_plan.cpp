@@ -1723,6 +1723,119 @@ int bhwp_describe_spectrogram(const bhw_params *p, const BhwCordicCfg *ct, uint6
     return BHW_OK;
 }
 
+// ---- fused window and complex FFT for I/Q input ----------------------------------------------------------------------------------------------
+
+int bhwp_stft_cfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const void *d_x, const void *d_Y,
+                          bool pointers)
+{
+    int rc = bhwp_f32_checks(p, length, 0);
+    if (rc) return rc;
+    if (!s) return bhwp_fail(BHW_ERR_BADARG, "stft descriptor is NULL");
+    if (s->struct_size != sizeof(bhw_stft)) return bhwp_fail(BHW_ERR_BADARG, "bhw_stft.struct_size %u != %zu", s->struct_size, sizeof(bhw_stft));
+    // 1. what the frames or the segments call checks, for the same descriptor with packed rows (the output strides mean something
+    //    else here and are checked below); this holds batch * frames * n_fft to 2^34 and the extents of x to 2^60 floats
+    bhw_stft t = *s;
+    t.y_stride = t.y_batch_stride = 0;
+    const uint32_t detrend = flags & BHW_WELCH_DETREND_CONSTANT;
+    const bool segments = detrend || (!s->pad && !s->col0 && !s->pad_mode);
+    if (segments) rc = bhwp_welch_checks(p, length, &t, detrend, nullptr, nullptr, nullptr, 0, false);
+    else          rc = bhwp_stft_checks(p, length, &t, false, 0, nullptr, nullptr, false);
+    if (rc) return rc;
+    // 2., 3.
+    if (flags & ~kCfftFlags)
+        return bhwp_fail(BHW_ERR_BADARG, "flags 0x%x (BHW_WELCH_DETREND_CONSTANT, BHW_CFFT_POWER, BHW_CFFT_SHIFT)", flags);
+    if (s->channels != 2)
+        return bhwp_fail(BHW_ERR_UNSUPPORTED, "channels %u: the fused complex FFT takes interleaved I/Q input (2); real input: bhw_stft_fft_f32_*",
+                         s->channels);
+    if ((s->n_fft & (s->n_fft - 1)) || s->n_fft < (1ull << kCfftMinLog) || s->n_fft > (1ull << kCfftMaxLog))
+        return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu: the fused complex FFT takes a power of two in %u..%u", (unsigned long long)s->n_fft,
+                         1u << kCfftMinLog, 1u << kCfftMaxLog);
+    // 4., 5.
+    const uint64_t T = s->samples, F = s->frames;
+    if (!F) return BHW_OK;
+    const bool power = (flags & BHW_CFFT_POWER) != 0;
+    const uint64_t W = power ? s->n_fft : 2 * s->n_fft;                       // floats of an output row
+    const char *wname = power ? "n_fft" : "2 * n_fft";
+    if (s->y_stride && (s->y_stride < W || (!power && s->y_stride % 2)))
+        return bhwp_fail(BHW_ERR_BADARG, power ? "y_stride %llu: at least %s = %llu floats" : "y_stride %llu: at least %s = %llu floats, and even",
+                         (unsigned long long)s->y_stride, wname, (unsigned long long)W);
+    const uint64_t ys = s->y_stride ? s->y_stride : W;
+    const unsigned __int128 ysig = (unsigned __int128)(F - 1) * ys + W;
+    if (ysig > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "Y extent beyond 2^60 elements");
+    if (s->y_batch_stride && (s->y_batch_stride < (uint64_t)ysig || (!power && s->y_batch_stride % 2)))
+        return bhwp_fail(BHW_ERR_BADARG, power ? "y_batch_stride %llu: at least (frames - 1) * y_stride + %s = %llu floats"
+                                               : "y_batch_stride %llu: at least (frames - 1) * y_stride + %s = %llu floats, and even",
+                         (unsigned long long)s->y_batch_stride, wname, (unsigned long long)ysig);
+    if (!pointers) return BHW_OK;
+    if (!d_x || !d_Y) return bhwp_fail(BHW_ERR_BADARG, "d_x / d_Y is NULL");
+    if ((uintptr_t)d_Y % (power ? 4 : 8)) return bhwp_fail(BHW_ERR_BADARG, "d_Y is not %d-byte aligned", power ? 4 : 8);
+    if ((uintptr_t)d_x % 4) return bhwp_fail(BHW_ERR_BADARG, "d_x is not 4-byte aligned");
+    const uint64_t xs = s->x_stride ? s->x_stride : 2 * T, ybs = s->y_batch_stride ? s->y_batch_stride : F * ys;
+    const unsigned __int128 xe = (unsigned __int128)(s->batch - 1) * xs + 2 * T, ye = (unsigned __int128)(s->batch - 1) * ybs + ysig;
+    if (xe > (1ull << 60) || ye > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "x or Y extent beyond 2^60 elements");
+    const uint64_t xa = (uint64_t)(uintptr_t)d_x, ya = (uint64_t)(uintptr_t)d_Y, xb = (uint64_t)xe * 4u, yb = (uint64_t)ye * 4u;
+    if (xa > UINT64_MAX - xb || ya > UINT64_MAX - yb) return bhwp_fail(BHW_ERR_BADARG, "x or Y range wraps the address space");
+    if (xa < ya + yb && ya < xa + xb) return bhwp_fail(BHW_ERR_BADARG, "d_x and d_Y overlap");
+    return BHW_OK;
+}
+
+BhwStftCfftPlan bhwp_stft_cfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, bool from_table)
+{
+    (void)p;
+    BhwStftCfftPlan pl{};
+    pl.route = from_table ? BHWP_FRAMES_TABLE : BHWP_FRAMES_DIRECT;
+    pl.detrend = (flags & BHW_WELCH_DETREND_CONSTANT) != 0;
+    pl.power = (flags & BHW_CFFT_POWER) != 0;
+    pl.shifted = (flags & BHW_CFFT_SHIFT) != 0;
+    pl.len = length;
+    while ((1ull << pl.log2n) < s->n_fft) ++pl.log2n;
+    pl.n = (uint32_t)s->n_fft;
+    const uint32_t quarter = pl.n / 4 < 4 ? 4 : pl.n / 4;
+    pl.lpf = quarter < kFftBlock ? quarter : kFftBlock;
+    pl.fy = kFftBlock / pl.lpf;
+    pl.cpl = pl.n / pl.lpf;
+    pl.radix4 = pl.log2n / 2;
+    pl.radix2 = pl.log2n % 2;
+    pl.lds_bytes = 2u * pl.fy * pl.n * 8u + pl.n / 2u * 8u + pl.fy * 8u;
+    pl.x_stride = s->x_stride ? s->x_stride : 2 * s->samples;
+    pl.y_stride = s->y_stride ? s->y_stride : (pl.power ? s->n_fft : 2 * s->n_fft);
+    pl.y_bstride = s->y_batch_stride ? s->y_batch_stride : s->frames * pl.y_stride;
+    pl.rows = s->batch * s->frames;
+    pl.groups = (pl.rows + pl.fy - 1) / pl.fy;
+    pl.grid = pl.groups < kFftMaxGrid ? pl.groups : kFftMaxGrid;
+    return pl;
+}
+
+int bhwp_describe_stft_cfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf,
+                            uint64_t len)
+{
+    if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
+    const char *route = ct ? "table" : "direct";
+    const BhwStftCfftPlan pl = bhwp_stft_cfft_plan(p, length, s, flags, ct != nullptr);
+    const char *pad = s->pad_mode == BHW_PAD_REFLECT ? "reflect" : "constant";
+    const char *det = pl.detrend ? "constant detrend" : "no detrending";
+    const char *form = pl.power ? "power rows" : "spectrum rows";
+    const char *bins = pl.shifted ? "bins shifted" : "bins in order";
+    if (!s->frames) {
+        snprintf(buf, len, "stft cfft %s (L = %llu, n_fft %llu, %s), %s, %s: nothing (frames 0)", route, (unsigned long long)length,
+                 (unsigned long long)s->n_fft, det, form, bins);
+        return BHW_OK;
+    }
+    char kern[64], sched[48];
+    kernel_name(p, ct, "k_stft_cfft_direct", "k_stft_cfft_table", false, kern, sizeof kern);
+    BhwStftFftPlan f{};
+    f.radix4 = pl.radix4;
+    f.radix2 = pl.radix2;
+    bhwp_stft_fft_schedule(f, sched, sizeof sched);
+    snprintf(buf, len, "stft cfft %s (L = %llu, n_fft %llu, col0 %llu, pad %llu %s, %s), %s, %s: %s, %llu signals x %llu frames = %llu rows, "
+             "complex FFT of %u points in passes %s (no split), %u lanes per row x %u rows per workgroup, %u columns per lane, %llu groups, "
+             "grid %llu x %u lanes, %u bytes of LDS", route, (unsigned long long)length, (unsigned long long)s->n_fft,
+             (unsigned long long)s->col0, (unsigned long long)s->pad, pad, det, form, bins, kern, (unsigned long long)s->batch,
+             (unsigned long long)s->frames, (unsigned long long)pl.rows, pl.n, sched, pl.lpf, pl.fy, pl.cpl, (unsigned long long)pl.groups,
+             (unsigned long long)pl.grid, kFftBlock, pl.lds_bytes);
+    return BHW_OK;
+}
+
 // ---- fused inverse real FFT, window and overlap-add -----------------------------------------------------------------------------------------
 
 int bhwp_istft_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const void *d_Y, const void *d_x,

@@ -473,6 +473,43 @@ int  bhwp_describe_spectrogram(const bhw_params *p, const BhwCordicCfg *ct, uint
 int  bhwk_spectrogram_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwStftFftPlan &pl, const bhw_stft *s,
                           const bhw_fbank *fb, const float *d_x, float *d_P, const int32_t *d_table, const BhwLenPhase &lp);
 
+// ---- fused window and complex FFT for I/Q input (bhw_stft_cfft_f32_*; bhw_stft_cfft.hip) ----------------------------------------------
+// The lane layout of the real forward kernel for rows of n = n_fft COMPLEX points: lpf lanes work on a row (one radix-4 butterfly per
+// lane and pass up to n = 1024, two at 2048), fy = kFftBlock / lpf rows side by side, a lane holds cpl = n / lpf complex columns of its
+// row and their coefficients in registers.  The passes are those bhwp_stft_fft_plan gives for 2n real points, without the split pass.
+// LDS: two buffers of fy * n complex64 (the first also stages the window and the raw row of the detrend means), the n / 2 twiddles
+// exp(-2 pi i k / n) and 2 * fy means.  n_fft 4096 would need 80 KiB of LDS and 16 complex columns per lane: not built.
+constexpr uint32_t kCfftMinLog = 4, kCfftMaxLog = 11;  // n_fft = 2^4 .. 2^11
+constexpr uint32_t kCfftMaxCpl = 8;                    // complex columns of one lane at most (n_fft 2048 on 256 lanes)
+constexpr uint32_t kCfftFlags = BHW_WELCH_DETREND_CONSTANT | BHW_CFFT_POWER | BHW_CFFT_SHIFT;
+struct BhwStftCfftPlan {
+    int route;            // BHWP_FRAMES_DIRECT or BHWP_FRAMES_TABLE
+    bool detrend, power, shifted;
+    uint32_t log2n;       // n_fft = 2^log2n
+    uint32_t n;           // the points of a row: n_fft
+    uint32_t lpf;         // lanes per row: min(kFftBlock, max(4, n / 4))
+    uint32_t fy;          // rows side by side: kFftBlock / lpf
+    uint32_t cpl;         // complex columns per lane: n / lpf (4 or 8)
+    uint32_t radix4;      // radix-4 passes: floor(log2(n) / 2)
+    uint32_t radix2;      // 1: a last radix-2 pass (log2(n) odd)
+    uint32_t lds_bytes;   // 2 * fy * n * 8 + n / 2 * 8 + fy * 8  (<= 40 KiB + 8)
+    uint64_t rows;        // B * frames
+    uint64_t groups;      // ceil(rows / fy)
+    uint64_t grid;        // min(groups, kFftMaxGrid)
+    uint64_t x_stride, y_stride, y_bstride;   // resolved, in floats (0 -> 2T; 2n or n; frames * y_stride)
+    uint64_t len;         // L
+};
+// Every check of the two calls that needs no table handle, before any HIP call and in the order of include/bhw.h.  frames 0 passes
+// with the pointers unchecked; `pointers` false: the describe call.
+int  bhwp_stft_cfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const void *d_x, const void *d_Y,
+                           bool pointers = true);
+// the plan of a call that passed the checks (frames 0: rows, groups and grid are 0)
+BhwStftCfftPlan bhwp_stft_cfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, bool from_table);
+int  bhwp_describe_stft_cfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf,
+                             uint64_t len);
+int  bhwk_stft_cfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwStftCfftPlan &pl, const bhw_stft *s,
+                        const float *d_x, float *d_Y, const int32_t *d_table, const BhwLenPhase &lp);
+
 // ---- fused inverse real FFT, window and overlap-add (bhw_istft_fft_f32_*; bhw_istft_fft.hip) ------------------------------------------
 // The lane layout of the forward kernel (lpf lanes along a row, fy slots side by side, cpl columns per lane).  The window-start axis
 // w = t + pad - col0 of every signal (frame f covers w in [f * hop, f * hop + L)) is cut into spans of S * hop positions; the spans

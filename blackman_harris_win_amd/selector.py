@@ -470,6 +470,18 @@ def _fft_input(torch, x, n_fft, dev):
         raise ValueError(f"the fused FFT takes n_fft a power of two in {B.FFT_MIN_N}..{B.FFT_MAX_N}, got {int(n_fft)}")
 
 
+def _cfft_input(torch, x, n_fft, dev):
+    """_fft_input for the I/Q calls: complex64 (T,) or (B, T), n_fft a power of two the complex kernel takes.  The device is checked
+    at the launch (_cfft_launch), after every check that needs none."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.complex64:
+        got = x.dtype if isinstance(x, torch.Tensor) else type(x).__name__
+        raise ValueError(f"the fused complex FFT takes complex64 input, got {got} (real input: stft / spectrogram)")
+    if x.dim() not in (1, 2):
+        raise ValueError("x must be (T,) or (B, T)")
+    if not B.cfft_supported(n_fft):
+        raise ValueError(f"the fused complex FFT takes n_fft a power of two in {B.CFFT_MIN_N}..{B.CFFT_MAX_N}, got {int(n_fft)}")
+
+
 def _fft_out(torch, out, shape, x, dtype=None):
     """The output tensor and its strides in floats: allocated packed, or the caller's `out` of `shape` and `dtype` (complex64 spectrum
     rows by default, float32 for the spectrogram), the last axis contiguous, rows and signals apart; the gaps of a wider buffer are
@@ -501,11 +513,11 @@ def _fft_launch(torch, params, L, s, flags, xr, out, dev, table):
     return out
 
 
-def _stft_front(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, dev):
-    """The input checks and the framing every fused forward call shares (stft, spectrogram): (n_fft, L, the x read, its (nb, T),
-    frames, and the descriptor's hop, col0, pad, pad_mode)."""
+def _stft_front(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, dev, check=_fft_input):
+    """The input checks and the framing every fused forward call shares (stft, spectrogram, stft_iq, spectrogram_iq): (n_fft, L, the
+    x read, its (nb, T), frames, and the descriptor's hop, col0, pad, pad_mode).  check: _fft_input, or _cfft_input for I/Q input."""
     n_fft, L, col0 = _stft_window(params, n_fft, win_length)
-    _fft_input(torch, x, n_fft, dev)
+    check(torch, x, n_fft, dev)
     hop = int(hop)
     if hop < 1:
         raise ValueError("hop must be >= 1")
@@ -554,6 +566,59 @@ def stft(params, x, n_fft, hop, *, win_length=None, center=True, pad_mode="refle
     if not isinstance(x, torch.Tensor) or not x.is_cuda:
         raise ValueError("x must be a float32 CUDA tensor")
     return _stft(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, shift, out, x.device.index, None)
+
+
+# ---- fused window and complex FFT for I/Q input ---------------------------------------------------------------------------------------------
+
+def _stft_iq(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, shift, fftshift, out, dev, table, power):
+    n_fft, L, xb, nb, T, frames, d = _stft_front(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, dev, _cfft_input)
+    shape = (nb, frames, n_fft) if x.dim() == 2 else (frames, n_fft)
+    out, ys, ybs = _fft_out(torch, out, shape, x, torch.float32 if power else torch.complex64)
+    if not x.is_cuda or x.device.index != dev:
+        raise ValueError("x must be a complex64 CUDA tensor on the call's device")
+    shift = params.dat_width - 1 if shift is None else int(shift)
+    s = B.make_stft(nb, T, frames, d["hop"], n_fft, col0=d["col0"], pad=d["pad"], pad_mode=d["pad_mode"], channels=2, shift=shift,
+                    x_stride=xb.stride(0) * 2 if nb > 1 else 0, y_stride=ys, y_batch_stride=ybs)
+    flags = (B.WELCH_DETREND_CONSTANT if detrend else 0) | (B.CFFT_POWER if power else 0) | (B.CFFT_SHIFT if fftshift else 0)
+    tail = (ctypes.byref(s), flags, ctypes.c_void_p(xb.data_ptr()), ctypes.c_void_p(out.data_ptr()))
+    if table is None:
+        B.check(B.lib().bhw_stft_cfft_f32_device(ctypes.byref(params), L, dev, _stream_ptr(torch, dev), *tail))
+    else:
+        B.check(B.lib().bhw_stft_cfft_f32_from_table(table, ctypes.byref(params), L, _stream_ptr(torch, dev), *tail))
+    return out
+
+
+def stft_iq(params, x, n_fft, hop, *, win_length=None, center=True, pad_mode="reflect", detrend=False, shift=None, fftshift=False,
+            out=None):
+    """The short-time Fourier transform of a batch of complex (I/Q) signals in ONE launch (bhw_stft_cfft_f32_device): x (T,) or
+    (B, T), complex64, framed and windowed exactly as stft_frames() does for complex input (center, pad_mode, the window of
+    win_length centred in an n_fft row, one coefficient for both parts of a sample) and transformed in the same kernel by a float32
+    complex FFT in LDS, so neither the windowed frames nor a second pass over x ever reach memory.  Returns complex64 (B, F, n_fft)
+    or (F, n_fft) for 1-D x: all n_fft bins, torch.fft.fft's sign and no scaling; `.transpose(-1, -2)` of it is
+    torch.stft(x, n_fft, hop, win_length, window=v, center=center, pad_mode=pad_mode, onesided=False, return_complex=True).
+    detrend=True (needs center=False) forms scipy's Welch segments instead: no padding, frames = 1 + (T - win_length) // hop, the
+    mean of each part removed (the fixed-order binary64 sums of welch_frames), the window at column 0 and zeros up to n_fft;
+    welch_psd(stft_iq(..., detrend=True, center=False), scale, nfft=n_fft, onesided=False) is the fused two-sided Welch estimate.
+    fftshift=True writes bin (j + n_fft // 2) % n_fft to column j: torch.fft.fftshift along the bins, the same values.  n_fft: a
+    power of two in 16..2048 (ValueError otherwise; a real or complex128 x too: stft() takes real input).  The rows the FFT sees are
+    bit for bit those of stft_frames / welch_frames; the FFT itself is accurate to a float32 FFT's error, not pinned bit for bit.
+    `out`: complex64 of the returned shape, bins contiguous, rows and signals apart (its gaps are left alone)."""
+    torch = _torch()
+    dev = x.device.index if isinstance(x, torch.Tensor) and x.is_cuda else None
+    return _stft_iq(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, shift, fftshift, out, dev, None, False)
+
+
+def spectrogram_iq(params, x, n_fft, hop, *, win_length=None, center=True, pad_mode="reflect", detrend=False, shift=None,
+                   fftshift=False, out=None):
+    """The two-sided power spectrogram of a batch of complex (I/Q) signals in ONE launch (bhw_stft_cfft_f32_device with
+    BHW_CFFT_POWER): the arguments, rows and transform of stft_iq(), and each bin written as fl32(re^2 + im^2), taken in binary64, of
+    the float32 pair stft_iq() would have written -- bit for bit -- so the complex spectrum never reaches memory.  Returns float32
+    (B, F, n_fft) or (F, n_fft) for 1-D x; `.transpose(-1, -2)` gives the (..., freq, time) layout; fftshift=True puts the zero
+    frequency at column n_fft // 2.  A filter bank on these rows is not built.  `out`: float32 of the returned shape, columns
+    contiguous, rows and signals apart (its gaps are left alone)."""
+    torch = _torch()
+    dev = x.device.index if isinstance(x, torch.Tensor) and x.is_cuda else None
+    return _stft_iq(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, shift, fftshift, out, dev, None, True)
 
 
 def _istft(torch, params, Y, n_fft, hop, win_length, center, length, normalize, shift, out, dev, table):
@@ -1360,6 +1425,20 @@ class ResidentTable:
         library, no synchronisation, capturable into a graph on its first call."""
         return _spectrogram(_torch(), params, x, n_fft, hop, win_length, center, pad_mode, detrend, fbank, shift, out, self.device,
                             self._live())
+
+    def stft_iq(self, params, x, n_fft, hop, *, win_length=None, center=True, pad_mode="reflect", detrend=False, shift=None,
+                fftshift=False, out=None):
+        """stft_iq() with the coefficients gathered from this table (bhw_stft_cfft_f32_from_table): no allocation by the library, no
+        synchronisation, capturable into a graph on its first call."""
+        return _stft_iq(_torch(), params, x, n_fft, hop, win_length, center, pad_mode, detrend, shift, fftshift, out, self.device,
+                        self._live(), False)
+
+    def spectrogram_iq(self, params, x, n_fft, hop, *, win_length=None, center=True, pad_mode="reflect", detrend=False, shift=None,
+                       fftshift=False, out=None):
+        """spectrogram_iq() with the coefficients gathered from this table (bhw_stft_cfft_f32_from_table with BHW_CFFT_POWER): no
+        allocation by the library, no synchronisation, capturable into a graph on its first call."""
+        return _stft_iq(_torch(), params, x, n_fft, hop, win_length, center, pad_mode, detrend, shift, fftshift, out, self.device,
+                        self._live(), True)
 
     def istft(self, params, Y, n_fft, hop, *, win_length=None, center=True, length=None, normalize=True, shift=None, out=None):
         """istft() with the coefficients gathered from this table (bhw_istft_fft_f32_from_table): no allocation by the library, no

@@ -686,7 +686,7 @@ int bhw_describe_csd(const bhw_csd *d, char *buf, uint64_t len);
  *     cosine or sine.  Its error against an exact transform of the float32 row is that of a float32 FFT (relative l2 error of a row
  *     of the order of 2^-24 * log2(n_fft) at most); the tests hold it to twice the error of rocFFT on the same rows.
  *   - Supported: channels 1 and n_fft a power of two in 16..4096.  Everything else -- complex input, other lengths -- is
- *     BHW_ERR_UNSUPPORTED.  The inverse is bhw_istft_fft_f32_* below.
+ *     BHW_ERR_UNSUPPORTED.  The inverse is bhw_istft_fft_f32_* below.  Complex input has calls of its own: bhw_stft_cfft_f32_*.
  *   - Descriptor: bhw_stft, where for these calls y_stride and y_batch_stride count FLOAT elements between spectrum rows and between
  *     signals; 0 means 2 * K and frames * y_stride.  Both must be even (rows of complex64 stay 8-byte aligned).  flags: 0 or
  *     BHW_WELCH_DETREND_CONSTANT; with the flag pad, col0 and pad_mode must be 0, as for the segments call.
@@ -785,7 +785,8 @@ int bhw_describe_istft_fft(bhw_table t, const bhw_params *p, uint64_t length, co
  *   - Capture: as bhw_stft_fft_f32_*.  The library form makes no allocation, uses no scratch and is capturable with no
  *     bhw_prepare_device; the from-table form is capturable on its first call.
  *   - Not built: magnitude (power 1); log (the caller applies it to the small result); a complex output next to the power;
- *     accumulating over frames in the kernel (Welch); complex input; other n_fft.
+ *     accumulating over frames in the kernel (Welch); complex input (bhw_stft_cfft_f32_* with BHW_CFFT_POWER is its power form);
+ *     other n_fft.
  *   - bhw_describe_spectrogram: the plan fields of bhw_describe_stft_fft's line in the same words, plus the mode, W, and for a bank
  *     filters, weights and filters per lane.  t may be NULL (the library call).  Host arithmetic only. */
 typedef struct bhw_fbank {
@@ -804,6 +805,57 @@ int bhw_spectrogram_f32_from_table(bhw_table t, const bhw_params *p, uint64_t le
                                    const bhw_fbank *fb, const float *d_x, float *d_P);
 int bhw_describe_spectrogram(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const bhw_fbank *fb,
                              char *buf, uint64_t len);
+
+/* Fused window and complex FFT for interleaved I/Q input: the two-channel rows of bhw_stft_frames_f32_* (no detrend flag) or of
+ * bhw_welch_frames_f32_* (BHW_WELCH_DETREND_CONSTANT) formed, transformed and written as their two-sided spectrum, or as its powers,
+ * by ONE launch.  These are entry points of their own: bhw_stft_fft_f32_*, bhw_istft_fft_f32_* and bhw_spectrogram_f32_* keep
+ * refusing channels 2.  Neither the windowed rows nor the means reach memory, so the call takes no workspace.
+ *   - Supported: channels 2 (channels 1 is BHW_ERR_UNSUPPORTED: real input goes to bhw_stft_fft_f32_*) and n_fft a power of two in
+ *     16..2048; everything else is BHW_ERR_UNSUPPORTED.  n_fft 4096 is out: a workgroup would need 80 KiB of dynamic LDS and 16
+ *     complex columns (32 sample registers) per lane.  x is read exactly as bhw_stft_frames_f32_* / bhw_welch_frames_f32_* read it
+ *     for channels 2: interleaved (re, im) float pairs, x_stride in floats (0 = 2 * samples), 4-byte aligned.
+ *   - flags: any combination of BHW_WELCH_DETREND_CONSTANT, BHW_CFFT_POWER and BHW_CFFT_SHIFT.  With the detrend flag pad, col0 and
+ *     pad_mode must be 0, as for the segments call.
+ *   - The row is pinned bit for bit: n_fft complex points, the interleaved float pairs those calls would have written for the same
+ *     descriptor -- the padding rule, col0, +0.0 around a window with L < n_fft, ONE coefficient v[k] for both parts of a pair.  With
+ *     the detrend flag each channel has its own mean m_c = fl32(S_c / L), S_c summed in the FIXED order of bhw_welch_frames_f32_* (64
+ *     binary64 partial sums by j mod 64 in ascending j, then the butterfly 32 ... 1), and the product is fl32(fl32(x - m_c) * v),
+ *     unfused.  A row reads its L window columns only, so without padding (pad, col0 and pad_mode all 0) the extent rule is the
+ *     segments' one, (frames - 1) * hop + L <= samples, with or without the detrend flag.
+ *   - The transform is NOT pinned bit for bit.  Y[k] = sum over j of row[j] * exp(-2 pi i j k / n_fft) for k < n_fft: the sign of
+ *     torch.fft.fft, no scaling.  It is a float32 Stockham transform of n_fft complex points in radix-4 passes (the first without
+ *     twiddles) and one radix-2 pass at the end when log2(n_fft) is odd -- the passes bhw_stft_fft_f32_* runs for 2 * n_fft real
+ *     points, without the split pass; every twiddle factor is the float32 rounding of a binary64 cosine or sine, read from one table
+ *     and never a product.  Its error is that of a float32 FFT (relative l2 error of a row of the order of 2^-24 * log2(n_fft) at
+ *     most); the tests hold it to twice the error of rocFFT on the same rows.
+ *   - Outputs.  No BHW_CFFT_POWER: d_Y[b * y_batch_stride + f * y_stride + 2 * j + {0, 1}] = (re, im) of the bin of column j,
+ *     complex64 as interleaved float pairs; y_stride and y_batch_stride count FLOATS, 0 means 2 * n_fft and frames * y_stride, both
+ *     must be even and d_Y 8-byte aligned.  BHW_CFFT_POWER: float32 rows of n_fft values,
+ *         d_Y[b * y_batch_stride + f * y_stride + j] = fl32((double) re * (double) re + (double) im * (double) im)
+ *     of the very pair the spectrum form writes (the power contract of bhw_spectrogram_f32_*); the strides count floats, 0 means n_fft
+ *     and frames * y_stride, no evenness rule applies and d_Y is 4-byte aligned.  Column j holds bin j, or with BHW_CFFT_SHIFT bin
+ *     (j + n_fft / 2) mod n_fft (torch.fft.fftshift along the bins: the same values, permuted), in both forms.
+ *   - Determinism: the bits of an output row depend only on the window, n_fft, the flags and the row's samples -- not on the batch,
+ *     the slot, the group, the grid, the strides, or library versus table.
+ *   - IEEE: a NaN or an infinity in x reaches only the rows whose window covers it; every other row keeps its bits.
+ *   - Only the row's floats are written: the elements up to y_stride and the gaps of y_batch_stride never are.
+ *   - Checks before any HIP call, in this order (BHW_ERR_BADARG unless noted): everything the frames call (no detrend flag) or the
+ *     segments call (with it) checks for the descriptor with packed output strides; unknown flag bits; the unsupported n_fft or
+ *     channels (BHW_ERR_UNSUPPORTED); frames 0 returns BHW_OK here with the pointers unchecked; the stride rules of the output form,
+ *     batch * frames * n_fft above 2^34, NULL pointers, alignment, d_Y overlapping d_x; and (from a table) the key match.
+ *   - Capture: as bhw_stft_fft_f32_*.  The library form makes no allocation, uses no scratch and is capturable with no
+ *     bhw_prepare_device; the from-table form allocates nothing, never synchronises and is capturable on its first call.
+ *   - Not built: n_fft 4096 and other lengths; the inverse (complex output); a filter bank on the I/Q power rows; accumulating over
+ *     frames in the kernel.
+ *   - bhw_describe_stft_cfft: bhw_describe_stft_fft's line in the same words for the complex transform (no split), the output form,
+ *     whether the bins are shifted, and the kernel.  t may be NULL (the library call).  Host arithmetic only. */
+#define BHW_CFFT_POWER 2u
+#define BHW_CFFT_SHIFT 4u
+int bhw_stft_cfft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                             const void *d_x, void *d_Y);
+int bhw_stft_cfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                 const void *d_x, void *d_Y);
+int bhw_describe_stft_cfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf, uint64_t len);
 
 /* Threading: every entry point may be called from any host thread.  Calls that use the library-owned scratch of one
  * (device, stream) are serialised against each other for the duration of their launches (the table is rebuilt per call);
