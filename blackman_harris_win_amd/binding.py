@@ -48,6 +48,7 @@ ABI_SYMBOLS = (
     "bhw_istft_fft_f32_device", "bhw_istft_fft_f32_from_table", "bhw_describe_istft_fft",
     "bhw_spectrogram_f32_device", "bhw_spectrogram_f32_from_table", "bhw_describe_spectrogram",
     "bhw_stft_cfft_f32_device", "bhw_stft_cfft_f32_from_table", "bhw_describe_stft_cfft",
+    "bhw_istft_cfft_f32_device", "bhw_istft_cfft_f32_from_table", "bhw_describe_istft_cfft",
 )
 
 
@@ -320,6 +321,9 @@ def lib():
     L.bhw_stft_cfft_f32_device.argtypes = [P, u64, ci, vp, S, u32, vp, vp]
     L.bhw_stft_cfft_f32_from_table.argtypes = [T, P, u64, vp, S, u32, vp, vp]
     L.bhw_describe_stft_cfft.argtypes = [T, P, u64, S, u32, ctypes.c_char_p, u64]
+    L.bhw_istft_cfft_f32_device.argtypes = [P, u64, ci, vp, S, u32, f32p, f32p]
+    L.bhw_istft_cfft_f32_from_table.argtypes = [T, P, u64, vp, S, u32, f32p, f32p]
+    L.bhw_describe_istft_cfft.argtypes = [T, P, u64, S, u32, ctypes.c_char_p, u64]
     PA = ctypes.POINTER(BhwAtan2Params)
     L.bhw_atan2_device.argtypes = [PA, ci, vp, u64, i32p, i32p, i32p]
     L.bhw_atan2_to_host.argtypes = [PA, ci, u64, i32p, i32p, i32p]
@@ -492,6 +496,17 @@ def describe_stft_cfft(params, length, stft, *, detrend=False, power=False, ffts
     buf = ctypes.create_string_buffer(1024)
     flags = (WELCH_DETREND_CONSTANT if detrend else 0) | (CFFT_POWER if power else 0) | (CFFT_SHIFT if fftshift else 0)
     check(lib().bhw_describe_stft_cfft(table, ctypes.byref(params), int(length), ctypes.byref(stft), flags, buf, len(buf)))
+    return buf.value.decode()
+
+
+def describe_istft_cfft(params, length, stft, *, normalize=False, fftshift=False, table=None):
+    """One line: the plan fields of describe_istft_fft in the same words for the inverse complex transform of I/Q rows (no split
+    pass), whether the bins are shifted, and the kernel, for a fused inverse complex FFT + overlap-add over the window of `length`
+    with the descriptor `stft` (a BhwStft with channels 2; its y strides count floats of spectrum rows) (bhw_describe_istft_cfft).
+    `table` is a resident table handle or None for the library call.  Host arithmetic only."""
+    buf = ctypes.create_string_buffer(1024)
+    flags = (OLA_NORMALIZE if normalize else 0) | (CFFT_SHIFT if fftshift else 0)
+    check(lib().bhw_describe_istft_cfft(table, ctypes.byref(params), int(length), ctypes.byref(stft), flags, buf, len(buf)))
     return buf.value.decode()
 
 

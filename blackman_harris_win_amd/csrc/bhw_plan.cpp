@@ -1879,6 +1879,35 @@ int bhwp_istft_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *
     return BHW_OK;
 }
 
+// The spans of a fused inverse call with fy slots per workgroup (BhwIstftFftPlan's fields of the same names): one function for the
+// real and the I/Q front.
+struct IstftSpans {
+    uint64_t t0, hop, halo, span, spans, groups, grid, trips;
+    bool halo_bound;
+};
+static IstftSpans istft_spans(uint64_t length, const bhw_stft *s, uint32_t fy)
+{
+    IstftSpans pl{};
+    pl.t0 = s->pad - s->col0;
+    const uint64_t end = pl.t0 + s->samples;                         // <= 2^40 + 2^34
+    pl.hop = s->hop < end ? s->hop : end;
+    pl.halo = (length + pl.hop - 1) / pl.hop - 1;
+    uint64_t fw_count = (end + pl.hop - 1) / pl.hop;                  // frames that start below the last output
+    if (fw_count > s->frames) fw_count = s->frames;
+    const uint64_t s_grid = (uint64_t)((unsigned __int128)s->batch * fw_count / ((uint64_t)kIfftTargetGroups * fy));
+    const uint64_t s_halo = kIfftHaloFactor * pl.halo;
+    uint64_t S = s_grid > s_halo ? s_grid : s_halo;
+    if (S < 1) S = 1;
+    if (S > fw_count) S = fw_count;
+    pl.halo_bound = S > s_grid && s_grid >= 1;                       // enough rows for the grid target, were it not for the halo
+    pl.span = S;
+    pl.spans = (end + S * pl.hop - 1) / (S * pl.hop);
+    pl.groups = (s->batch * pl.spans + fy - 1) / fy;
+    pl.grid = pl.groups < kFftMaxGrid ? pl.groups : kFftMaxGrid;
+    pl.trips = S + pl.halo < s->frames ? S + pl.halo : s->frames;
+    return pl;
+}
+
 BhwIstftFftPlan bhwp_istft_fft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, bool from_table)
 {
     // the lane layout and the radix schedule are the forward's
@@ -1900,23 +1929,16 @@ BhwIstftFftPlan bhwp_istft_fft_plan(const bhw_params *p, uint64_t length, const 
     pl.x_stride = s->x_stride ? s->x_stride : s->samples;
     pl.y_stride = s->y_stride ? s->y_stride : s->n_fft + 2;
     pl.y_bstride = s->y_batch_stride ? s->y_batch_stride : s->frames * pl.y_stride;
-    pl.t0 = s->pad - s->col0;
-    const uint64_t end = pl.t0 + s->samples;                         // <= 2^40 + 2^34
-    pl.hop = s->hop < end ? s->hop : end;
-    pl.halo = (length + pl.hop - 1) / pl.hop - 1;
-    uint64_t fw_count = (end + pl.hop - 1) / pl.hop;                  // frames that start below the last output
-    if (fw_count > s->frames) fw_count = s->frames;
-    const uint64_t s_grid = (uint64_t)((unsigned __int128)s->batch * fw_count / ((uint64_t)kIfftTargetGroups * pl.fy));
-    const uint64_t s_halo = kIfftHaloFactor * pl.halo;
-    uint64_t S = s_grid > s_halo ? s_grid : s_halo;
-    if (S < 1) S = 1;
-    if (S > fw_count) S = fw_count;
-    pl.halo_bound = S > s_grid && s_grid >= 1;                       // enough rows for the grid target, were it not for the halo
-    pl.span = S;
-    pl.spans = (end + S * pl.hop - 1) / (S * pl.hop);
-    pl.groups = (s->batch * pl.spans + pl.fy - 1) / pl.fy;
-    pl.grid = pl.groups < kFftMaxGrid ? pl.groups : kFftMaxGrid;
-    pl.trips = S + pl.halo < s->frames ? S + pl.halo : s->frames;
+    const IstftSpans sp = istft_spans(length, s, pl.fy);
+    pl.t0 = sp.t0;
+    pl.hop = sp.hop;
+    pl.halo = sp.halo;
+    pl.halo_bound = sp.halo_bound;
+    pl.span = sp.span;
+    pl.spans = sp.spans;
+    pl.groups = sp.groups;
+    pl.grid = sp.grid;
+    pl.trips = sp.trips;
     return pl;
 }
 
@@ -1950,6 +1972,124 @@ int bhwp_describe_istft_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64_
              (unsigned long long)pl.span, (unsigned long long)pl.halo, (unsigned long long)pl.spans, (unsigned long long)pl.trips,
              (unsigned long long)repeat, (unsigned long long)pl.groups, (unsigned long long)pl.grid, kFftBlock, pl.lds_bytes,
              few ? "; heavy overlap: the halo sets S and few workgroups run (irfft + istft overlap-add may be faster)" : "");
+    return BHW_OK;
+}
+
+// ---- fused inverse complex FFT, window and overlap-add for I/Q output ----------------------------------------------------------------------
+
+int bhwp_istft_cfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const void *d_Y, const void *d_x,
+                           bool pointers)
+{
+    // 1. what the overlap-add checks, for the same descriptor with packed rows (the input strides are checked below; the shift bit is
+    //    this call's own)
+    const uint32_t ola_flags = flags & BHW_OLA_NORMALIZE;
+    int rc = bhwp_f32_checks(p, length, ola_flags);
+    if (rc) return rc;
+    if (!s) return bhwp_fail(BHW_ERR_BADARG, "stft descriptor is NULL");
+    if (s->struct_size != sizeof(bhw_stft)) return bhwp_fail(BHW_ERR_BADARG, "bhw_stft.struct_size %u != %zu", s->struct_size, sizeof(bhw_stft));
+    bhw_stft t = *s;
+    t.y_stride = t.y_batch_stride = 0;
+    rc = bhwp_stft_checks(p, length, &t, true, ola_flags, nullptr, nullptr, false);
+    if (rc) return rc;
+    // 2., 3.
+    if (flags & ~kIcfftFlags) return bhwp_fail(BHW_ERR_BADARG, "flags 0x%x (BHW_OLA_NORMALIZE, BHW_CFFT_SHIFT)", flags);
+    if (s->channels != 2)
+        return bhwp_fail(BHW_ERR_UNSUPPORTED, "channels %u: the fused inverse complex FFT gives interleaved I/Q output (2); real output: "
+                                              "bhw_istft_fft_f32_*", s->channels);
+    if ((s->n_fft & (s->n_fft - 1)) || s->n_fft < (1ull << kCfftMinLog) || s->n_fft > (1ull << kCfftMaxLog))
+        return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu: the fused inverse complex FFT takes a power of two in %u..%u",
+                         (unsigned long long)s->n_fft, 1u << kCfftMinLog, 1u << kCfftMaxLog);
+    // 4., 5.
+    const uint64_t T = s->samples, F = s->frames, W = 2 * s->n_fft;           // floats of a spectrum row
+    if (!T) return BHW_OK;
+    if (s->y_stride && (s->y_stride < W || s->y_stride % 2))
+        return bhwp_fail(BHW_ERR_BADARG, "y_stride %llu: at least 2 * n_fft = %llu floats, and even", (unsigned long long)s->y_stride,
+                         (unsigned long long)W);
+    const uint64_t ys = s->y_stride ? s->y_stride : W;
+    const unsigned __int128 ysig = (unsigned __int128)(F - 1) * ys + W;
+    if (ysig > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "Y extent beyond 2^60 elements");
+    if (s->y_batch_stride && (s->y_batch_stride < (uint64_t)ysig || s->y_batch_stride % 2))
+        return bhwp_fail(BHW_ERR_BADARG, "y_batch_stride %llu: at least (frames - 1) * y_stride + 2 * n_fft = %llu floats, and even",
+                         (unsigned long long)s->y_batch_stride, (unsigned long long)ysig);
+    if (!pointers) return BHW_OK;
+    if (!d_x || !d_Y) return bhwp_fail(BHW_ERR_BADARG, "d_Y / d_x is NULL");
+    if ((uintptr_t)d_Y % 8) return bhwp_fail(BHW_ERR_BADARG, "d_Y is not 8-byte aligned");
+    if ((uintptr_t)d_x % 4) return bhwp_fail(BHW_ERR_BADARG, "d_x is not 4-byte aligned");
+    const uint64_t xs = s->x_stride ? s->x_stride : 2 * T, ybs = s->y_batch_stride ? s->y_batch_stride : F * ys;
+    const unsigned __int128 xe = (unsigned __int128)(s->batch - 1) * xs + 2 * T, ye = (unsigned __int128)(s->batch - 1) * ybs + ysig;
+    if (xe > (1ull << 60) || ye > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "x or Y extent beyond 2^60 elements");
+    const uint64_t xa = (uint64_t)(uintptr_t)d_x, ya = (uint64_t)(uintptr_t)d_Y, xb = (uint64_t)xe * 4u, yb = (uint64_t)ye * 4u;
+    if (xa > UINT64_MAX - xb || ya > UINT64_MAX - yb) return bhwp_fail(BHW_ERR_BADARG, "x or Y range wraps the address space");
+    if (xa < ya + yb && ya < xa + xb) return bhwp_fail(BHW_ERR_BADARG, "d_Y and d_x overlap");
+    return BHW_OK;
+}
+
+BhwIstftCfftPlan bhwp_istft_cfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, bool from_table)
+{
+    // the lane layout and the radix schedule are the forward's
+    bhw_stft fw = *s;
+    fw.frames = 0;
+    const BhwStftCfftPlan f = bhwp_stft_cfft_plan(p, length, &fw, 0, from_table);
+    BhwIstftCfftPlan pl{};
+    pl.route = f.route;
+    pl.normalize = (flags & BHW_OLA_NORMALIZE) != 0;
+    pl.shifted = (flags & BHW_CFFT_SHIFT) != 0;
+    pl.log2n = f.log2n;
+    pl.n = f.n;
+    pl.lpf = f.lpf;
+    pl.fy = f.fy;
+    pl.cpl = f.cpl;
+    pl.radix4 = f.radix4;
+    pl.radix2 = f.radix2;
+    pl.lds_bytes = 2u * pl.fy * pl.n * 8u + pl.n / 2u * 8u + pl.n * 4u;
+    pl.len = length;
+    pl.x_stride = s->x_stride ? s->x_stride : 2 * s->samples;
+    pl.y_stride = s->y_stride ? s->y_stride : 2 * s->n_fft;
+    pl.y_bstride = s->y_batch_stride ? s->y_batch_stride : s->frames * pl.y_stride;
+    const IstftSpans sp = istft_spans(length, s, pl.fy);
+    pl.t0 = sp.t0;
+    pl.hop = sp.hop;
+    pl.halo = sp.halo;
+    pl.halo_bound = sp.halo_bound;
+    pl.span = sp.span;
+    pl.spans = sp.spans;
+    pl.groups = sp.groups;
+    pl.grid = sp.grid;
+    pl.trips = sp.trips;
+    return pl;
+}
+
+int bhwp_describe_istft_cfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf,
+                             uint64_t len)
+{
+    if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
+    const char *route = ct ? "table" : "direct";
+    const char *norm = (flags & BHW_OLA_NORMALIZE) ? "normalised by the window envelope" : "not normalised";
+    const char *bins = (flags & BHW_CFFT_SHIFT) ? "bins shifted" : "bins in order";
+    if (!s->samples) {
+        snprintf(buf, len, "istft cfft %s (L = %llu, n_fft %llu), %s, %s: nothing (samples 0)", route, (unsigned long long)length,
+                 (unsigned long long)s->n_fft, norm, bins);
+        return BHW_OK;
+    }
+    const BhwIstftCfftPlan pl = bhwp_istft_cfft_plan(p, length, s, flags, ct != nullptr);
+    BhwStftFftPlan f{};
+    f.radix4 = pl.radix4;
+    f.radix2 = pl.radix2;
+    char kern[64], sched[48];
+    kernel_name(p, ct, "k_istft_cfft_direct", "k_istft_cfft_table", false, kern, sizeof kern);
+    bhwp_stft_fft_schedule(f, sched, sizeof sched);
+    // the repeats: every span but a signal's first transforms up to `halo` frames that the span before it transforms too
+    const uint64_t repeat = pl.spans > 1 ? 100 * pl.halo / (pl.span + pl.halo) : 0;
+    const bool few = pl.halo_bound && pl.groups < kIfftTargetGroups / 4;
+    snprintf(buf, len, "istft cfft %s (L = %llu, n_fft %llu, col0 %llu, pad %llu: t0 = %llu), %s, %s: %s, %llu signals x %llu frames = %llu rows, "
+             "inverse complex FFT of %u points in passes %s (no split), %u lanes per row x %u spans per workgroup, %u columns per lane, "
+             "spans of S = %llu frames + halo %llu (%llu spans per signal, up to %llu frames a span, %llu%% of the transforms repeated), "
+             "%llu groups, grid %llu x %u lanes, %u bytes of LDS%s", route, (unsigned long long)length, (unsigned long long)s->n_fft,
+             (unsigned long long)s->col0, (unsigned long long)s->pad, (unsigned long long)pl.t0, norm, bins, kern, (unsigned long long)s->batch,
+             (unsigned long long)s->frames, (unsigned long long)(s->batch * s->frames), pl.n, sched, pl.lpf, pl.fy, pl.cpl,
+             (unsigned long long)pl.span, (unsigned long long)pl.halo, (unsigned long long)pl.spans, (unsigned long long)pl.trips,
+             (unsigned long long)repeat, (unsigned long long)pl.groups, (unsigned long long)pl.grid, kFftBlock, pl.lds_bytes,
+             few ? "; heavy overlap: the halo sets S and few workgroups run (ifft + istft overlap-add may be faster)" : "");
     return BHW_OK;
 }
 

@@ -572,6 +572,34 @@ int  bhwp_describe_istft_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64
 int  bhwk_istft_fft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwIstftFftPlan &pl, const bhw_stft *s,
                         const float *d_Y, float *d_x, const int32_t *d_table, const BhwLenPhase &lp);
 
+// ---- fused inverse complex FFT, window and overlap-add for I/Q output (bhw_istft_cfft_f32_*; bhw_istft_cfft.hip) ----------------------
+// The lane layout and the passes of bhwp_stft_cfft_plan (lpf lanes along a row of n = n_fft complex points, fy slots side by side,
+// cpl complex columns per lane) under the spans of bhwp_istft_fft_plan: the same S, halo, trips, halo_bound, grid cap and hop clamp,
+// from one function (istft_spans in bhw_plan.cpp), and bhwp_istft_span as it is.  A lane keeps cpl ring positions of two binary64
+// sums (re, im) and one envelope sum.  LDS: the two Stockham buffers of fy * n complex64, the n / 2 conjugated twiddles and the n
+// floats of the window: 48 KiB at 2048, three workgroups on a CU.
+constexpr uint32_t kIcfftFlags = BHW_OLA_NORMALIZE | BHW_CFFT_SHIFT;
+struct BhwIstftCfftPlan {
+    int route;            // BHWP_FRAMES_DIRECT or BHWP_FRAMES_TABLE
+    bool normalize, shifted;
+    uint32_t log2n, n, lpf, fy, cpl, radix4, radix2;   // as BhwStftCfftPlan
+    uint32_t lds_bytes;   // 2 * fy * n * 8 + n / 2 * 8 + n * 4  (<= 48 KiB)
+    uint64_t t0, hop, halo, span, spans, groups, grid, trips;   // as BhwIstftFftPlan
+    bool halo_bound;
+    uint64_t x_stride, y_stride, y_bstride;   // resolved, in floats (0 -> 2 * samples, 2 * n_fft, frames * y_stride)
+    uint64_t len;         // L
+};
+// Every check of the two calls that needs no table handle, before any HIP call and in the order of include/bhw.h.  samples 0 passes
+// with the strides and the pointers unchecked; `pointers` false: the describe call.
+int  bhwp_istft_cfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const void *d_Y, const void *d_x,
+                            bool pointers = true);
+// the plan of a call that passed the checks with samples > 0
+BhwIstftCfftPlan bhwp_istft_cfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, bool from_table);
+int  bhwp_describe_istft_cfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf,
+                              uint64_t len);
+int  bhwk_istft_cfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwIstftCfftPlan &pl, const bhw_stft *s,
+                         const float *d_Y, float *d_x, const int32_t *d_table, const BhwLenPhase &lp);
+
 // the generate kernel of a window of any length (bhw_len.hip): d_table NULL = k_direct_len, else k_range_len over the resident table of c
 int  bhwk_len_range(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *d_table, const BhwLenPhase &lp,
                     uint64_t n0, uint64_t count, int32_t *d_out);

@@ -621,15 +621,37 @@ def spectrogram_iq(params, x, n_fft, hop, *, win_length=None, center=True, pad_m
     return _stft_iq(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, shift, fftshift, out, dev, None, True)
 
 
-def _istft(torch, params, Y, n_fft, hop, win_length, center, length, normalize, shift, out, dev, table):
+def _ifft_input(torch, Y, dev):
+    """The input check of istft(): one-sided complex64 spectra (frames, K) or (B, frames, K) on the call's device."""
     if not isinstance(Y, torch.Tensor) or not Y.is_cuda or Y.device.index != dev:
         raise ValueError("Y must be a complex64 CUDA tensor on the call's device")
     if Y.dtype != torch.complex64:
         raise ValueError(f"the fused inverse FFT takes one-sided complex64 spectra, got {Y.dtype}")
     if Y.dim() not in (2, 3):
         raise ValueError("Y must be (frames, K) or (B, frames, K)")
+
+
+def _icfft_input(torch, Y, dev):
+    """_ifft_input for istft_iq(): two-sided complex64 spectra (frames, n_fft) or (B, frames, n_fft).  The device is checked at the
+    launch (_istft), after every check that needs none."""
+    if not isinstance(Y, torch.Tensor) or Y.dtype != torch.complex64:
+        got = Y.dtype if isinstance(Y, torch.Tensor) else type(Y).__name__
+        raise ValueError(f"the fused inverse complex FFT takes two-sided complex64 spectra, got {got} (one-sided spectra: istft)")
+    if Y.dim() not in (2, 3):
+        raise ValueError("Y must be (frames, n_fft) or (B, frames, n_fft)")
+
+
+def _istft(torch, params, Y, n_fft, hop, win_length, center, length, normalize, shift, out, dev, table, check=_ifft_input,
+           dtype=None, fftshift=False):
+    """The body istft() and istft_iq() share.  check: _ifft_input, or _icfft_input for I/Q output; dtype: the output's, float32 (the
+    one-sided spectra of istft) by default, complex64 for the two-sided spectra of istft_iq."""
+    dtype = torch.float32 if dtype is None else dtype
+    iq = dtype == torch.complex64
+    check(torch, Y, dev)
     n_fft, L, col0 = _stft_window(params, n_fft, win_length)
-    if not B.fft_supported(n_fft):
+    if iq and not B.cfft_supported(n_fft):
+        raise ValueError(f"the fused inverse complex FFT takes n_fft a power of two in {B.CFFT_MIN_N}..{B.CFFT_MAX_N}, got {n_fft}")
+    if not iq and not B.fft_supported(n_fft):
         raise ValueError(f"the fused inverse FFT takes n_fft a power of two in {B.FFT_MIN_N}..{B.FFT_MAX_N}, got {n_fft}")
     hop = int(hop)
     if hop < 1:
@@ -638,7 +660,9 @@ def _istft(torch, params, Y, n_fft, hop, win_length, center, length, normalize, 
         raise ValueError("center=False with win_length < n_fft: the first outputs have no window under them")
     Yb = Y if Y.dim() == 3 else Y.unsqueeze(0)
     nb, frames, K = Yb.shape
-    if K != n_fft // 2 + 1:
+    if iq and K != n_fft:
+        raise ValueError(f"Y rows hold {K} bins, the two-sided spectrum of n_fft {n_fft} has {n_fft} (one-sided spectra: istft)")
+    if not iq and K != n_fft // 2 + 1:
         raise ValueError(f"Y rows hold {K} bins, n_fft // 2 + 1 is {n_fft // 2 + 1}")
     if frames < 1 or nb < 1:
         raise ValueError("zero frames")
@@ -649,18 +673,24 @@ def _istft(torch, params, Y, n_fft, hop, win_length, center, length, normalize, 
     Yb = _stft_input(Yb, ((frames - 1) * max(Yb.stride(1), K) + K, K))
     shape = (nb, length) if Y.dim() == 3 else (length,)
     if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=Y.device)
-    elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != Y.device or not out.is_contiguous() \
-            or out.is_neg() or tuple(out.shape) != shape:
-        raise ValueError(f"out must be a contiguous float32 tensor of shape {shape} on Y's device")
+        out = torch.empty(shape, dtype=dtype, device=Y.device)
+    elif not isinstance(out, torch.Tensor) or out.dtype != dtype or out.device != Y.device or not out.is_contiguous() \
+            or out.is_neg() or out.is_conj() or tuple(out.shape) != shape:
+        raise ValueError(f"out must be a contiguous {str(dtype).replace('torch.', '')} tensor of shape {shape} on Y's device")
+    if iq and (not Y.is_cuda or Y.device.index != dev):
+        raise ValueError("Y must be a complex64 CUDA tensor on the call's device")
     shift = params.dat_width - 1 if shift is None else int(shift)
-    s = B.make_stft(nb, length, frames, hop, n_fft, col0=col0, pad=pad, shift=shift,
+    s = B.make_stft(nb, length, frames, hop, n_fft, col0=col0, pad=pad, shift=shift, channels=2 if iq else 1,
                     y_stride=Yb.stride(1) * 2 if frames > 1 else 0, y_batch_stride=Yb.stride(0) * 2 if nb > 1 else 0)
-    tail = (ctypes.byref(s), B.OLA_NORMALIZE if normalize else 0, ctypes.c_void_p(Yb.data_ptr()), ctypes.c_void_p(out.data_ptr()))
+    flags = (B.OLA_NORMALIZE if normalize else 0) | (B.CFFT_SHIFT if fftshift else 0)
+    tail = (ctypes.byref(s), flags, ctypes.c_void_p(Yb.data_ptr()), ctypes.c_void_p(out.data_ptr()))
+    L_ = B.lib()
+    device_call, table_call = (L_.bhw_istft_cfft_f32_device, L_.bhw_istft_cfft_f32_from_table) if iq else \
+        (L_.bhw_istft_fft_f32_device, L_.bhw_istft_fft_f32_from_table)
     if table is None:
-        B.check(B.lib().bhw_istft_fft_f32_device(ctypes.byref(params), L, dev, _stream_ptr(torch, dev), *tail))
+        B.check(device_call(ctypes.byref(params), L, dev, _stream_ptr(torch, dev), *tail))
     else:
-        B.check(B.lib().bhw_istft_fft_f32_from_table(table, ctypes.byref(params), L, _stream_ptr(torch, dev), *tail))
+        B.check(table_call(table, ctypes.byref(params), L, _stream_ptr(torch, dev), *tail))
     return out
 
 
@@ -681,6 +711,26 @@ def istft(params, Y, n_fft, hop, *, win_length=None, center=True, length=None, n
     if not isinstance(Y, torch.Tensor) or not Y.is_cuda:
         raise ValueError("Y must be a complex64 CUDA tensor")
     return _istft(torch, params, Y, n_fft, hop, win_length, center, length, normalize, shift, out, Y.device.index, None)
+
+
+def istft_iq(params, Y, n_fft, hop, *, win_length=None, center=True, length=None, normalize=True, shift=None, fftshift=False, out=None):
+    """The inverse short-time Fourier transform of a batch of complex (I/Q) signals in ONE launch (bhw_istft_cfft_f32_device): Y
+    (B, F, n_fft) or (F, n_fft), complex64, all n_fft bins -- the layout stft_iq() returns.  Every row is transformed as
+    torch.fft.ifft does (same sign and 1 / n_fft scaling) by a float32 complex FFT in LDS, and summed exactly as istft_overlap_add()
+    sums complex time rows: in ascending frame order in binary64 per part, times v (window(params, win_length, dtype=torch.float32,
+    shift=shift)), and with normalize=True divided by the window envelope (+0.0 where no frame reaches).  The time rows never reach
+    memory.  fftshift=True reads rows whose column j holds bin (j + n_fft // 2) % n_fft, what stft_iq(fftshift=True) writes.  length
+    defaults to torch.istft's n_fft + hop * (frames - 1) - 2 * pad; outputs past the frames' extent are +0.0.  Returns complex64
+    (B, length), or (length,) for 2-D Y.  istft_iq(params, S.transpose(-1, -2), ...) is torch.istft(S, n_fft, hop, win_length,
+    window=v, center=center, length=length, onesided=False, return_complex=True) to a float32 FFT's error.  n_fft: a power of two in
+    16..2048 (ValueError otherwise; a real, complex128 or one-sided Y too: istft() takes one-sided spectra).  Y is read in place when
+    its bins are contiguous and its rows and signals apart; a transposed view, a broadcast or a lazy conjugate is copied first.
+    `out`: a contiguous complex64 tensor of the returned shape.  With heavy overlap and little work (see describe_istft_cfft) few
+    workgroups run; torch.fft.ifft + istft_overlap_add remains for that case, and this call does not reroute to it."""
+    torch = _torch()
+    dev = Y.device.index if isinstance(Y, torch.Tensor) and Y.is_cuda else None
+    return _istft(torch, params, Y, n_fft, hop, win_length, center, length, normalize, shift, out, dev, None, _icfft_input,
+                  torch.complex64, fftshift)
 
 
 # ---- fused power and filter-bank spectrogram ---------------------------------------------------------------------------------------------
@@ -1444,6 +1494,14 @@ class ResidentTable:
         """istft() with the coefficients gathered from this table (bhw_istft_fft_f32_from_table): no allocation by the library, no
         synchronisation, capturable into a graph on its first call."""
         return _istft(_torch(), params, Y, n_fft, hop, win_length, center, length, normalize, shift, out, self.device, self._live())
+
+    def istft_iq(self, params, Y, n_fft, hop, *, win_length=None, center=True, length=None, normalize=True, shift=None, fftshift=False,
+                 out=None):
+        """istft_iq() with the coefficients gathered from this table (bhw_istft_cfft_f32_from_table): no allocation by the library, no
+        synchronisation, capturable into a graph on its first call."""
+        torch = _torch()
+        return _istft(torch, params, Y, n_fft, hop, win_length, center, length, normalize, shift, out, self.device, self._live(),
+                      _icfft_input, torch.complex64, fftshift)
 
     def istft_overlap_add(self, params, y, n_fft, hop, *, win_length=None, center=True, length=None, normalize=True, shift=None,
                           out=None):

@@ -845,8 +845,8 @@ int bhw_describe_spectrogram(bhw_table t, const bhw_params *p, uint64_t length, 
  *     batch * frames * n_fft above 2^34, NULL pointers, alignment, d_Y overlapping d_x; and (from a table) the key match.
  *   - Capture: as bhw_stft_fft_f32_*.  The library form makes no allocation, uses no scratch and is capturable with no
  *     bhw_prepare_device; the from-table form allocates nothing, never synchronises and is capturable on its first call.
- *   - Not built: n_fft 4096 and other lengths; the inverse (complex output); a filter bank on the I/Q power rows; accumulating over
- *     frames in the kernel.
+ *   - Not built: n_fft 4096 and other lengths; a filter bank on the I/Q power rows; accumulating over frames in the kernel.  The
+ *     inverse is bhw_istft_cfft_f32_* below.
  *   - bhw_describe_stft_cfft: bhw_describe_stft_fft's line in the same words for the complex transform (no split), the output form,
  *     whether the bins are shifted, and the kernel.  t may be NULL (the library call).  Host arithmetic only. */
 #define BHW_CFFT_POWER 2u
@@ -856,6 +856,57 @@ int bhw_stft_cfft_f32_device(const bhw_params *p, uint64_t length, int device, v
 int bhw_stft_cfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
                                  const void *d_x, void *d_Y);
 int bhw_describe_stft_cfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf, uint64_t len);
+
+/* Fused inverse complex FFT, window and overlap-add for I/Q output: torch.fft.ifft in front of bhw_istft_ola_f32_* with channels 2,
+ * by ONE launch -- the inverse of bhw_stft_cfft_f32_*.  A group of lanes owns a span of a signal's time axis, reads the n_fft bins of
+ * every frame that reaches it, transforms them in LDS, and adds the windowed row into binary64 accumulators that it stores once.
+ * The time rows never reach memory, so the call takes no workspace.  These are entry points of their own: bhw_istft_fft_f32_* keeps
+ * refusing channels 2.
+ *   - The row.  For b < batch, f < frames, r[j], j < n_fft, is the float32 inverse transform of the n_fft bins
+ *     Y[k] = d_Y[b * y_batch_stride + f * y_stride + 2 * k + {0, 1}]: r[j] ~ (1 / n_fft) * sum over k < n_fft of Y[k] exp(+2 pi i j k /
+ *     n_fft), complex: the sign and the scaling of torch.fft.ifft.  The 1 / n_fft is one exact power-of-two scaling of the float32
+ *     result.  The transform is NOT pinned bit for bit: it is an inverse float32 Stockham transform of n_fft complex points with the
+ *     passes of bhw_stft_cfft_f32_* (radix 4, the first without twiddles, one radix-2 pass at the end when log2(n_fft) is odd); every
+ *     twiddle factor is the float32 rounding of a binary64 cosine or sine, conjugated, read from one table and never a product; the
+ *     butterflies use +i.  The bits of a row depend on its bins, n_fft and the shift flag only -- not on its place in a workgroup, the
+ *     span that reads it, the grid, the strides or the route.
+ *   - The sum.  Given those rows every output is exactly what bhw_istft_ola_f32_* defines on them for channels 2: for t < samples,
+ *     u = t + pad, over the frames f with 0 <= k = u - f * hop - col0 < L in ASCENDING f, in binary64 from +0.0, per part c of {0, 1}:
+ *         S_c = sum (double) r_f[u - f * hop].c * (double) v[k],   E = sum (double) v[k]^2   (one E for both parts)
+ *         d_x[b * x_stride + 2 * t + c] = BHW_OLA_NORMALIZE ? (E > 0 ? fl32(S_c / E) : +0.0) : fl32(S_c)
+ *     Outputs no frame reaches are +0.0 in both parts: samples past the frames' extent, and the gaps when hop > L.
+ *   - flags: any combination of BHW_OLA_NORMALIZE and BHW_CFFT_SHIFT.  With BHW_CFFT_SHIFT column j of a spectrum row holds bin
+ *     (j + n_fft / 2) mod n_fft -- what bhw_stft_cfft_f32_* writes under the same flag; the kernel changes its load index and runs
+ *     no extra pass.
+ *   - Supported: channels 2 and n_fft a power of two in 16..2048.  channels 1 is BHW_ERR_UNSUPPORTED (real output goes to
+ *     bhw_istft_fft_f32_*); n_fft 4096 and every other length is BHW_ERR_UNSUPPORTED.
+ *   - Descriptor: bhw_stft, where y_stride and y_batch_stride count FLOAT elements between spectrum rows and between signals; 0
+ *     means 2 * n_fft and frames * y_stride; both must be even and d_Y 8-byte aligned.  x_stride: floats between output signals, 0
+ *     means 2 * samples, any value from 2 * samples; d_x is 4-byte aligned (a sample is stored as one 8-byte word where d_x and
+ *     x_stride are on the 8-byte grid, as two 4-byte words otherwise: the same bits).  pad_mode must be 0.
+ *   - Determinism: the bits of output (b, t) depend only on the window, n_fft, hop, col0, pad, flags and the spectrum rows whose
+ *     window covers t -- not on the batch, the plan, how a signal is cut into spans, the strides, or library versus table.
+ *   - IEEE: a bin of row (b, f) that is NaN in both parts makes both parts of exactly the outputs under that row's window
+ *     non-finite; every other output keeps its bits.
+ *   - Only the 2 * samples floats of each signal are written: the gaps of x_stride never are.
+ *   - Checks before any HIP call, in this order (BHW_ERR_BADARG unless noted): everything bhw_istft_ola_f32_* checks for the
+ *     descriptor with packed row strides (pad < col0, frames 0 with samples > 0, col0 + L > n_fft, shift, a nonzero pad_mode, x_stride
+ *     below 2 * samples, batch * frames * n_fft above 2^34, the Taylor sources (BHW_ERR_UNSUPPORTED), ...); unknown flag bits; the
+ *     unsupported channels, then the unsupported n_fft (BHW_ERR_UNSUPPORTED); samples 0 returns BHW_OK here with the strides and the
+ *     pointers unchecked; y_stride below 2 * n_fft or odd, y_batch_stride below (frames - 1) * y_stride + 2 * n_fft or odd; NULL
+ *     pointers, d_Y not 8-byte aligned, d_x not 4-byte aligned, d_Y overlapping d_x; and (from a table) the key match.
+ *   - The library form computes the coefficients by direct CORDIC and the twiddle factors in the kernel: no allocation, no scratch,
+ *     capturable with no warm call and no bhw_prepare_device.  The from-table form keeps the from-table contract: no allocation, no
+ *     synchronisation, capturable on its first call.
+ *   - Not built: n_fft 4096 and other lengths; a fast path under heavy overlap (the halo sets S and few workgroups run); complex
+ *     data through the real entry points.
+ *   - bhw_describe_istft_cfft: bhw_describe_istft_fft's line in the same words for the complex transform (no split), whether the bins
+ *     are shifted, and the kernel.  t may be NULL (the library call).  Host arithmetic only. */
+int bhw_istft_cfft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                              const float *d_Y, float *d_x);
+int bhw_istft_cfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                  const float *d_Y, float *d_x);
+int bhw_describe_istft_cfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf, uint64_t len);
 
 /* Threading: every entry point may be called from any host thread.  Calls that use the library-owned scratch of one
  * (device, stream) are serialised against each other for the duration of their launches (the table is rebuilt per call);
