@@ -47,6 +47,7 @@ ABI_SYMBOLS = (
     "bhw_stft_fft_f32_device", "bhw_stft_fft_f32_from_table", "bhw_describe_stft_fft",
     "bhw_istft_fft_f32_device", "bhw_istft_fft_f32_from_table", "bhw_describe_istft_fft",
     "bhw_spectrogram_f32_device", "bhw_spectrogram_f32_from_table", "bhw_describe_spectrogram",
+    "bhw_stft_mfft_f32_device", "bhw_stft_mfft_f32_from_table", "bhw_describe_stft_mfft",
     "bhw_stft_cfft_f32_device", "bhw_stft_cfft_f32_from_table", "bhw_describe_stft_cfft",
     "bhw_istft_cfft_f32_device", "bhw_istft_cfft_f32_from_table", "bhw_describe_istft_cfft",
 )
@@ -318,6 +319,9 @@ def lib():
     L.bhw_spectrogram_f32_device.argtypes = [P, u64, ci, vp, S, u32, FB, f32p, f32p]
     L.bhw_spectrogram_f32_from_table.argtypes = [T, P, u64, vp, S, u32, FB, f32p, f32p]
     L.bhw_describe_spectrogram.argtypes = [T, P, u64, S, u32, FB, ctypes.c_char_p, u64]
+    L.bhw_stft_mfft_f32_device.argtypes = [P, u64, ci, vp, S, u32, FB, f32p, f32p]
+    L.bhw_stft_mfft_f32_from_table.argtypes = [T, P, u64, vp, S, u32, FB, f32p, f32p]
+    L.bhw_describe_stft_mfft.argtypes = [T, P, u64, S, u32, FB, ctypes.c_char_p, u64]
     L.bhw_stft_cfft_f32_device.argtypes = [P, u64, ci, vp, S, u32, vp, vp]
     L.bhw_stft_cfft_f32_from_table.argtypes = [T, P, u64, vp, S, u32, vp, vp]
     L.bhw_describe_stft_cfft.argtypes = [T, P, u64, S, u32, ctypes.c_char_p, u64]
@@ -475,6 +479,35 @@ def describe_spectrogram(params, length, stft, *, detrend=False, fbank=None, tab
     check(lib().bhw_describe_spectrogram(table, ctypes.byref(params), int(length), ctypes.byref(stft),
                                          WELCH_DETREND_CONSTANT if detrend else 0, ctypes.byref(fbank) if fbank is not None else None,
                                          buf, len(buf)))
+    return buf.value.decode()
+
+
+MFFT_MIN_N, MFFT_MAX_N = 16, 4095         # n_fft of the mixed-radix fused calls: even 2^a 3^b 5^c in this range, no power of two
+MFFT_POWER = 2                           # BHW_MFFT_POWER
+
+
+def mfft_supported(n_fft):
+    """True where bhw_stft_mfft_f32_* take n_fft: even, 2^a * 3^b * 5^c, in 16..4095, and not a power of two (those go to
+    bhw_stft_fft_f32_*: fft_supported)."""
+    n = int(n_fft)
+    if not MFFT_MIN_N <= n <= MFFT_MAX_N or n % 2 or n & (n - 1) == 0:
+        return False
+    for r in (2, 3, 5):
+        while n % r == 0:
+            n //= r
+    return n == 1
+
+
+def describe_stft_mfft(params, length, stft, *, detrend=False, power=False, fbank=None, table=None):
+    """One line: the plan fields of describe_stft_fft in the same words for the mixed-radix transform (the schedule of radix-5, -3, -4
+    and -2 passes), the output form (spectrum rows, power rows, or bank rows with the filters, weights and filters per lane) and the
+    kernel, for a call over the window of `length` with the descriptor `stft` (a BhwStft, make_stft; its y strides count floats of
+    output rows) and `fbank` (a BhwFbank, make_fbank, or None; it needs power=True) (bhw_describe_stft_mfft).  `table` is a resident
+    table handle or None for the library call.  Host arithmetic only."""
+    buf = ctypes.create_string_buffer(1024)
+    flags = (WELCH_DETREND_CONSTANT if detrend else 0) | (MFFT_POWER if power else 0)
+    check(lib().bhw_describe_stft_mfft(table, ctypes.byref(params), int(length), ctypes.byref(stft), flags,
+                                       ctypes.byref(fbank) if fbank is not None else None, buf, len(buf)))
     return buf.value.decode()
 
 

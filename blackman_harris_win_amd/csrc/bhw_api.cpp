@@ -1167,6 +1167,19 @@ int spectrogram_run(bhw_table t, const bhw_params *p, uint64_t length, int devic
                                                               const BhwLenPhase *lp) { return bhwk_spectrogram_f32(l, c, w, pl, s, fb, d_x, d_P, tab, *lp); });
 }
 
+// The mixed-radix fused window + FFT in its three output forms (t NULL: the direct CORDIC chains): the checks, then the one kernel.
+int stft_mfft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *s, uint32_t flags,
+                  const bhw_fbank *fb, const float *d_x, float *d_out)
+{
+    int rc = bhwp_stft_mfft_checks(p, length, s, flags, fb, d_x, d_out);
+    if (!rc && t) rc = table_call_checks(t, p);
+    if (rc || !s->frames) return rc;
+    const BhwStftMfftPlan pl = bhwp_stft_mfft_plan(p, length, s, flags, fb, t != nullptr);
+    const char *what = t ? "stft mfft launch (resident table)" : "stft mfft launch";
+    return run_source(t, p, length, device, stream, what, [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *tab,
+                                                              const BhwLenPhase *lp) { return bhwk_stft_mfft_f32(l, c, w, pl, s, fb, d_x, d_out, tab, *lp); });
+}
+
 // The fused inverse FFT + overlap-add (t NULL: the direct CORDIC chains): the checks, then the one kernel.
 int istft_fft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *s, uint32_t flags,
                   const float *d_Y, float *d_x)
@@ -1415,6 +1428,30 @@ int bhw_describe_spectrogram(bhw_table t, const bhw_params *p, uint64_t length, 
     int rc = bhwp_spectrogram_checks(p, length, s, flags, fb, nullptr, nullptr, false);
     if (!rc && t) rc = table_call_checks(t, p);
     return rc ? rc : bhwp_describe_spectrogram(p, t ? &t->c : nullptr, length, s, flags, fb, buf, len);
+}
+
+// ---- mixed-radix fused window and real FFT (include/bhw.h: bhw_stft_mfft_f32_device ...) -----------------------------------------------
+
+int bhw_stft_mfft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                             const bhw_fbank *fb, const float *d_x, float *d_out)
+{
+    return stft_mfft_run(nullptr, p, length, device, hip_stream, s, flags, fb, d_x, d_out);
+}
+
+int bhw_stft_mfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                 const bhw_fbank *fb, const float *d_x, float *d_out)
+{
+    const int rc = bhwp_stft_mfft_checks(p, length, s, flags, fb, d_x, d_out);
+    if (rc) return rc;
+    return t ? stft_mfft_run(t, p, length, t->device, hip_stream, s, flags, fb, d_x, d_out) : fail(BHW_ERR_BADARG, "table is NULL");
+}
+
+int bhw_describe_stft_mfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const bhw_fbank *fb,
+                           char *buf, uint64_t len)
+{
+    int rc = bhwp_stft_mfft_checks(p, length, s, flags, fb, nullptr, nullptr, false);
+    if (!rc && t) rc = table_call_checks(t, p);
+    return rc ? rc : bhwp_describe_stft_mfft(p, t ? &t->c : nullptr, length, s, flags, fb, buf, len);
 }
 
 // ---- fused window and complex FFT for I/Q input (include/bhw.h: bhw_stft_cfft_f32_device ...) ------------------------------------------

@@ -1723,6 +1723,173 @@ int bhwp_describe_spectrogram(const bhw_params *p, const BhwCordicCfg *ct, uint6
     return BHW_OK;
 }
 
+// ---- mixed-radix fused window and real FFT -------------------------------------------------------------------------------------------------
+
+bool bhwp_mfft_supported(uint64_t n)
+{
+    if (n < kMfftMinN || n > kMfftMaxN || (n & 1u) || !(n & (n - 1))) return false;
+    for (const uint64_t r : {2ull, 3ull, 5ull})
+        while (n % r == 0) n /= r;
+    return n == 1;
+}
+
+int bhwp_stft_mfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const bhw_fbank *fb, const void *d_x,
+                          const void *d_out, bool pointers)
+{
+    int rc = bhwp_f32_checks(p, length, 0);
+    if (rc) return rc;
+    if (flags & ~(BHW_WELCH_DETREND_CONSTANT | BHW_MFFT_POWER))
+        return bhwp_fail(BHW_ERR_BADARG, "flags 0x%x (any of BHW_WELCH_DETREND_CONSTANT, BHW_MFFT_POWER)", flags);
+    if (!s) return bhwp_fail(BHW_ERR_BADARG, "stft descriptor is NULL");
+    if (s->struct_size != sizeof(bhw_stft)) return bhwp_fail(BHW_ERR_BADARG, "bhw_stft.struct_size %u != %zu", s->struct_size, sizeof(bhw_stft));
+    if (fb && !(flags & BHW_MFFT_POWER)) return bhwp_fail(BHW_ERR_BADARG, "a filter bank folds powers: fb needs BHW_MFFT_POWER in flags");
+    // what the frames or the segments call checks, for the same descriptor with packed rows (the output strides mean something else
+    // here and are checked below)
+    bhw_stft t = *s;
+    t.y_stride = t.y_batch_stride = 0;
+    const uint32_t det = flags & BHW_WELCH_DETREND_CONSTANT;
+    const bool segments = det || (!s->pad && !s->col0 && !s->pad_mode);
+    if (segments) rc = bhwp_welch_checks(p, length, &t, det, nullptr, nullptr, nullptr, 0, false);
+    else          rc = bhwp_stft_checks(p, length, &t, false, 0, nullptr, nullptr, false);
+    if (rc) return rc;
+    if (s->channels != 1)
+        return bhwp_fail(BHW_ERR_UNSUPPORTED, "channels %u: the mixed-radix fused FFT takes real input (1)", s->channels);
+    if (!(s->n_fft & (s->n_fft - 1)))
+        return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu is a power of two: bhw_stft_fft_f32_* and bhw_spectrogram_f32_* transform it "
+                         "(one transform per n_fft)", (unsigned long long)s->n_fft);
+    if (!bhwp_mfft_supported(s->n_fft))
+        return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu: the mixed-radix fused FFT takes an even 2^a 3^b 5^c in %u..%u", (unsigned long long)s->n_fft,
+                         kMfftMinN, kMfftMaxN);
+    const uint64_t T = s->samples, F = s->frames, K = s->n_fft / 2 + 1;
+    if (fb) {
+        if (fb->struct_size != sizeof(bhw_fbank))
+            return bhwp_fail(BHW_ERR_BADARG, "bhw_fbank.struct_size %u != %zu", fb->struct_size, sizeof(bhw_fbank));
+        if (fb->reserved) return bhwp_fail(BHW_ERR_BADARG, "bhw_fbank.reserved is not 0");
+        if (fb->filters < 1 || fb->filters > kSpecMaxFilters)
+            return bhwp_fail(BHW_ERR_BADARG, "bhw_fbank.filters %u outside 1..%u", fb->filters, kSpecMaxFilters);
+        if (fb->bins != K)
+            return bhwp_fail(BHW_ERR_BADARG, "bhw_fbank.bins %u: the call has n_fft / 2 + 1 = %llu bins", fb->bins, (unsigned long long)K);
+        if (fb->weights > kSpecMaxWeights) return bhwp_fail(BHW_ERR_BADARG, "bhw_fbank.weights %u above 2^24", fb->weights);
+    }
+    if (!F) return BHW_OK;
+    // the output rows: W floats each; spectrum rows are complex64 pairs (even strides, 8-byte alignment)
+    const bool spectrum = !(flags & BHW_MFFT_POWER);
+    const uint64_t W = spectrum ? 2 * K : fb ? fb->filters : K;
+    const char *wname = spectrum ? "2 * K" : "W";
+    if ((unsigned __int128)s->batch * F * (spectrum ? K : W) > (1ull << 34))
+        return bhwp_fail(BHW_ERR_BADARG, "batch * frames * %s above 2^34 per call", spectrum ? "K" : "W");
+    if (s->y_stride && (s->y_stride < W || (spectrum && s->y_stride % 2)))
+        return bhwp_fail(BHW_ERR_BADARG, "y_stride %llu: at least %s = %llu floats%s", (unsigned long long)s->y_stride, wname,
+                         (unsigned long long)W, spectrum ? ", and even" : "");
+    const uint64_t ys = s->y_stride ? s->y_stride : W;
+    const unsigned __int128 ysig = (unsigned __int128)(F - 1) * ys + W;
+    if (ysig > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "output extent beyond 2^60 elements");
+    if (s->y_batch_stride && (s->y_batch_stride < (uint64_t)ysig || (spectrum && s->y_batch_stride % 2)))
+        return bhwp_fail(BHW_ERR_BADARG, "y_batch_stride %llu: at least (frames - 1) * y_stride + %s = %llu floats%s",
+                         (unsigned long long)s->y_batch_stride, wname, (unsigned long long)ysig, spectrum ? ", and even" : "");
+    if (!pointers) return BHW_OK;
+    if (!d_x || !d_out) return bhwp_fail(BHW_ERR_BADARG, "d_x / d_out is NULL");
+    if ((uintptr_t)d_out % (spectrum ? 8 : 4)) return bhwp_fail(BHW_ERR_BADARG, "d_out is not %d-byte aligned", spectrum ? 8 : 4);
+    if ((uintptr_t)d_x % 4) return bhwp_fail(BHW_ERR_BADARG, "d_x is not 4-byte aligned");
+    const uint64_t xs = s->x_stride ? s->x_stride : T, ybs = s->y_batch_stride ? s->y_batch_stride : F * ys;
+    const unsigned __int128 xe = (unsigned __int128)(s->batch - 1) * xs + T, ye = (unsigned __int128)(s->batch - 1) * ybs + ysig;
+    if (xe > (1ull << 60) || ye > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "x or output extent beyond 2^60 elements");
+    const uint64_t xa = (uint64_t)(uintptr_t)d_x, ya = (uint64_t)(uintptr_t)d_out, xb = (uint64_t)xe * 4u, yb = (uint64_t)ye * 4u;
+    if (xa > UINT64_MAX - xb || ya > UINT64_MAX - yb) return bhwp_fail(BHW_ERR_BADARG, "x or output range wraps the address space");
+    if (xa < ya + yb && ya < xa + xb) return bhwp_fail(BHW_ERR_BADARG, "d_x and d_out overlap");
+    if (fb) {
+        if (!fb->d_first || !fb->d_offset) return bhwp_fail(BHW_ERR_BADARG, "bhw_fbank.d_first / d_offset is NULL");
+        if (!fb->d_weight && fb->weights) return bhwp_fail(BHW_ERR_BADARG, "bhw_fbank.d_weight is NULL with %u weights", fb->weights);
+        const void *ptr[3] = {fb->d_first, fb->d_offset, fb->d_weight};
+        const uint64_t nb[3] = {(uint64_t)fb->filters * 4u, ((uint64_t)fb->filters + 1u) * 4u, (uint64_t)fb->weights * 4u};
+        static const char *const what[3] = {"d_first", "d_offset", "d_weight"};
+        for (int i = 0; i < 3; ++i) {
+            const uint64_t a = (uint64_t)(uintptr_t)ptr[i];
+            if (a % 4) return bhwp_fail(BHW_ERR_BADARG, "bhw_fbank.%s is not 4-byte aligned", what[i]);
+            if (a > UINT64_MAX - nb[i]) return bhwp_fail(BHW_ERR_BADARG, "bhw_fbank.%s range wraps the address space", what[i]);
+            if (nb[i] && a < ya + yb && ya < a + nb[i]) return bhwp_fail(BHW_ERR_BADARG, "bhw_fbank.%s and d_out overlap", what[i]);
+        }
+    }
+    return BHW_OK;
+}
+
+BhwStftMfftPlan bhwp_stft_mfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const bhw_fbank *fb,
+                                    bool from_table)
+{
+    (void)p;
+    BhwStftMfftPlan pl{};
+    pl.route = from_table ? BHWP_FRAMES_TABLE : BHWP_FRAMES_DIRECT;
+    pl.detrend = (flags & BHW_WELCH_DETREND_CONSTANT) != 0;
+    pl.form = !(flags & BHW_MFFT_POWER) ? BHWP_MFFT_SPECTRUM : fb ? BHWP_MFFT_BANK : BHWP_MFFT_POWER;
+    pl.len = length;
+    const uint32_t n = (uint32_t)s->n_fft;
+    pl.m = n / 2;
+    pl.lpf = 4;
+    while (pl.lpf < kFftBlock && 4u * pl.lpf < pl.m) pl.lpf *= 2;       // the smallest power of two >= M / 4
+    pl.fy = kFftBlock / pl.lpf;
+    pl.cpl = (n + pl.lpf - 1) / pl.lpf;
+    // the schedule: 5s, 3s, 4s, a last 2
+    uint32_t rest = pl.m;
+    for (const uint32_t r : {5u, 3u, 4u, 2u})
+        while (rest % r == 0 && pl.passes < kMfftMaxPasses) {
+            pl.radix[pl.passes++] = (uint8_t)r;
+            rest /= r;
+        }
+    pl.lds_bytes = 2u * pl.fy * pl.m * 8u + pl.m * 8u + pl.fy * 4u;
+    const uint64_t K = s->n_fft / 2 + 1;
+    const uint64_t W = pl.form == BHWP_MFFT_SPECTRUM ? 2 * K : pl.form == BHWP_MFFT_BANK ? fb->filters : K;
+    pl.x_stride = s->x_stride ? s->x_stride : s->samples;
+    pl.y_stride = s->y_stride ? s->y_stride : W;
+    pl.y_bstride = s->y_batch_stride ? s->y_batch_stride : s->frames * pl.y_stride;
+    pl.rows = s->batch * s->frames;
+    pl.groups = (pl.rows + pl.fy - 1) / pl.fy;
+    pl.grid = pl.groups < kFftMaxGrid ? pl.groups : kFftMaxGrid;
+    return pl;
+}
+
+void bhwp_stft_mfft_schedule(const BhwStftMfftPlan &pl, char *buf, uint64_t len)
+{
+    if (!buf || !len) return;
+    buf[0] = 0;
+    for (uint32_t i = 0; i < pl.passes; ++i) {
+        const size_t at = strlen(buf);
+        if (at + 1 >= len) break;
+        snprintf(buf + at, len - at, "%s%u", i ? "x" : "", (unsigned)pl.radix[i]);
+    }
+}
+
+int bhwp_describe_stft_mfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags,
+                            const bhw_fbank *fb, char *buf, uint64_t len)
+{
+    if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
+    const char *route = ct ? "table" : "direct";
+    const BhwStftMfftPlan pl = bhwp_stft_mfft_plan(p, length, s, flags, fb, ct != nullptr);
+    const char *pad = s->pad_mode == BHW_PAD_REFLECT ? "reflect" : "constant";
+    const char *det = pl.detrend ? "constant detrend" : "no detrending";
+    const uint64_t K = s->n_fft / 2 + 1;
+    char form[112];
+    if (pl.form == BHWP_MFFT_BANK)
+        snprintf(form, sizeof form, "bank rows, W = %u (%u filters, %u weights, %u filters per lane)", fb->filters, fb->filters, fb->weights,
+                 (fb->filters + pl.lpf - 1) / pl.lpf);
+    else if (pl.form == BHWP_MFFT_POWER) snprintf(form, sizeof form, "power rows, W = %llu", (unsigned long long)K);
+    else                                 snprintf(form, sizeof form, "spectrum rows, K = %llu", (unsigned long long)K);
+    if (!s->frames) {
+        snprintf(buf, len, "stft mfft %s (L = %llu, n_fft %llu, %s), %s: nothing (frames 0)", route, (unsigned long long)length,
+                 (unsigned long long)s->n_fft, det, form);
+        return BHW_OK;
+    }
+    char kern[64], sched[48];
+    kernel_name(p, ct, "k_stft_mfft_direct", "k_stft_mfft_table", false, kern, sizeof kern);
+    bhwp_stft_mfft_schedule(pl, sched, sizeof sched);
+    snprintf(buf, len, "stft mfft %s (L = %llu, n_fft %llu, col0 %llu, pad %llu %s, %s), %s: %s, %llu signals x %llu frames = %llu rows, "
+             "complex FFT of %u points in passes %s + split, %u lanes per row x %u rows per workgroup, %u columns per lane, %llu groups, "
+             "grid %llu x %u lanes, %u bytes of LDS", route, (unsigned long long)length, (unsigned long long)s->n_fft,
+             (unsigned long long)s->col0, (unsigned long long)s->pad, pad, det, form, kern, (unsigned long long)s->batch,
+             (unsigned long long)s->frames, (unsigned long long)pl.rows, pl.m, sched, pl.lpf, pl.fy, pl.cpl, (unsigned long long)pl.groups,
+             (unsigned long long)pl.grid, kFftBlock, pl.lds_bytes);
+    return BHW_OK;
+}
+
 // ---- fused window and complex FFT for I/Q input ----------------------------------------------------------------------------------------------
 
 int bhwp_stft_cfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const void *d_x, const void *d_Y,

@@ -473,6 +473,48 @@ int  bhwp_describe_spectrogram(const bhw_params *p, const BhwCordicCfg *ct, uint
 int  bhwk_spectrogram_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwStftFftPlan &pl, const bhw_stft *s,
                           const bhw_fbank *fb, const float *d_x, float *d_P, const int32_t *d_table, const BhwLenPhase &lp);
 
+// ---- mixed-radix fused window and real FFT (bhw_stft_mfft_f32_*; bhw_stft_mfft.hip) -----------------------------------------------------
+// The forward kernel's layout for n_fft = 2^a 3^b 5^c that is even and NOT a power of two, 16 <= n_fft < 4096: M = n_fft / 2 complex
+// points per row, lpf = the smallest power of two >= M / 4 (clamped to 4 .. kFftBlock, so the slot of a lane stays a shift) lanes on a
+// row, fy = kFftBlock / lpf rows side by side, cpl = ceil(n_fft / lpf) <= kFftMaxCpl columns per lane; the last column of a lane need
+// not exist.  The schedule is a function of n_fft alone: the radix-5 passes of M, then its radix-3 passes, then floor(a' / 2) radix-4
+// passes for M = 2^a' ..., then one radix-2 pass when a' is odd.  LDS, groups, grid and the stride resolution are BhwStftFftPlan's.
+// Three output forms: spectrum rows of K = M + 1 complex64, their powers (BHW_MFFT_POWER), the powers folded through a filter bank.
+constexpr uint32_t kMfftMinN = 16, kMfftMaxN = 4095;
+constexpr uint32_t kMfftMaxPasses = 8;                // 2916 = 2^2 3^6 runs 3x3x3x3x3x3x2: seven
+enum { BHWP_MFFT_SPECTRUM = 0, BHWP_MFFT_POWER = 1, BHWP_MFFT_BANK = 2 };
+struct BhwStftMfftPlan {
+    int route;            // BHWP_FRAMES_DIRECT or BHWP_FRAMES_TABLE
+    bool detrend;
+    uint32_t form;        // BHWP_MFFT_SPECTRUM, _POWER or _BANK
+    uint32_t m;           // M = n_fft / 2
+    uint32_t lpf;         // lanes per row
+    uint32_t fy;          // rows side by side: kFftBlock / lpf
+    uint32_t cpl;         // columns per lane: ceil(n_fft / lpf)
+    uint32_t passes;      // radix passes before the split pass
+    uint8_t radix[kMfftMaxPasses];
+    uint32_t lds_bytes;   // 2 * fy * M * 8 + M * 8 + fy * 4  (<= 64 KiB)
+    uint64_t rows;        // B * frames
+    uint64_t groups;      // ceil(rows / fy)
+    uint64_t grid;        // min(groups, kFftMaxGrid)
+    uint64_t x_stride, y_stride, y_bstride;   // resolved (0 -> T, W, frames * y_stride; W = 2K, K or filters floats)
+    uint64_t len;         // L
+};
+// n_fft the mixed-radix calls take
+bool bhwp_mfft_supported(uint64_t n_fft);
+// Every check of the two calls that needs no table handle, before any HIP call (include/bhw.h).  frames 0 passes with the pointers
+// unchecked; `pointers` false: the describe call.
+int  bhwp_stft_mfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const bhw_fbank *fb, const void *d_x,
+                           const void *d_out, bool pointers = true);
+BhwStftMfftPlan bhwp_stft_mfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const bhw_fbank *fb,
+                                    bool from_table);
+// the radix schedule as text, "5x5x4x2"
+void bhwp_stft_mfft_schedule(const BhwStftMfftPlan &pl, char *buf, uint64_t len);
+int  bhwp_describe_stft_mfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags,
+                             const bhw_fbank *fb, char *buf, uint64_t len);
+int  bhwk_stft_mfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwStftMfftPlan &pl, const bhw_stft *s,
+                        const bhw_fbank *fb, const float *d_x, float *d_out, const int32_t *d_table, const BhwLenPhase &lp);
+
 // ---- fused window and complex FFT for I/Q input (bhw_stft_cfft_f32_*; bhw_stft_cfft.hip) ----------------------------------------------
 // The lane layout of the real forward kernel for rows of n = n_fft COMPLEX points: lpf lanes work on a row (one radix-4 butterfly per
 // lane and pass up to n = 1024, two at 2048), fy = kFftBlock / lpf rows side by side, a lane holds cpl = n / lpf complex columns of its

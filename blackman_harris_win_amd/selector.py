@@ -908,6 +908,79 @@ def spectrogram(params, x, n_fft, hop, *, win_length=None, center=True, pad_mode
     return _spectrogram(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, fbank, shift, out, x.device.index, None)
 
 
+# ---- mixed-radix fused window and real FFT: n_fft like 400, 480, 960, 1000 -----------------------------------------------------------------
+
+def _mfft_input(torch, x, n_fft, dev):
+    """_fft_input for the mixed-radix calls: real float32 (T,) or (B, T) on `dev`, n_fft one the mixed-radix kernel takes."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.device.index != dev:
+        raise ValueError("x must be a float32 CUDA tensor on the call's device")
+    if x.dtype != torch.float32:
+        raise ValueError(f"the fused FFT takes real float32 input, got {x.dtype} (complex input: stft_frames + torch.fft)")
+    if x.dim() not in (1, 2):
+        raise ValueError("x must be (T,) or (B, T)")
+    n = int(n_fft)
+    if n > 0 and n & (n - 1) == 0:
+        raise ValueError(f"n_fft {n} is a power of two: bhw.stft / bhw.spectrogram transform it (one transform per n_fft)")
+    if not B.mfft_supported(n):
+        raise ValueError(f"the mixed-radix fused FFT takes n_fft even 2^a·3^b·5^c in {B.MFFT_MIN_N}..{B.MFFT_MAX_N}, got {n}")
+
+
+def _stft_mixed(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, power, fbank, shift, out, dev, table):
+    n_fft, L, xb, nb, T, frames, d = _stft_front(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, dev, _mfft_input)
+    K = n_fft // 2 + 1
+    if fbank is not None:
+        if not isinstance(fbank, FilterBank):
+            raise ValueError("fbank must be a FilterBank (FilterBank(dense_weights, device=...)) or None")
+        if fbank.bins != K:
+            raise ValueError(f"the filter bank has {fbank.bins} bins, n_fft // 2 + 1 is {K}")
+        if fbank.device != x.device:
+            raise ValueError(f"the filter bank is on {fbank.device}, x on {x.device}")
+    W = K if fbank is None else fbank.filters
+    out, ys, ybs = _fft_out(torch, out, (nb, frames, W) if x.dim() == 2 else (frames, W), x, torch.float32 if power else torch.complex64)
+    shift = params.dat_width - 1 if shift is None else int(shift)
+    s = B.make_stft(nb, T, frames, d["hop"], n_fft, col0=d["col0"], pad=d["pad"], pad_mode=d["pad_mode"], shift=shift,
+                    x_stride=xb.stride(0) if nb > 1 else 0, y_stride=ys, y_batch_stride=ybs)
+    flags = (B.WELCH_DETREND_CONSTANT if detrend else 0) | (B.MFFT_POWER if power else 0)
+    tail = (ctypes.byref(s), flags, ctypes.byref(fbank.descriptor) if fbank is not None else None, ctypes.c_void_p(xb.data_ptr()),
+            ctypes.c_void_p(out.data_ptr()))
+    if table is None:
+        B.check(B.lib().bhw_stft_mfft_f32_device(ctypes.byref(params), L, dev, _stream_ptr(torch, dev), *tail))
+    else:
+        B.check(B.lib().bhw_stft_mfft_f32_from_table(table, ctypes.byref(params), L, _stream_ptr(torch, dev), *tail))
+    return out
+
+
+def stft_mixed(params, x, n_fft, hop, *, win_length=None, center=True, pad_mode="reflect", detrend=False, shift=None, out=None):
+    """stft() for the row lengths speech and audio code uses and a power-of-two transform refuses, in ONE launch
+    (bhw_stft_mfft_f32_device): n_fft even, 2^a·3^b·5^c, in 16..4095 and not a power of two -- 400 (torchaudio's and Whisper's
+    default), 480, 960, 1000, 1200, 1920.  The arguments, the shapes, the `out` rules and the errors are stft()'s: x (T,) or (B, T),
+    real float32, framed and windowed exactly as stft_frames() / welch_frames() do (their rows bit for bit) and transformed in the
+    same kernel by a float32 mixed-radix FFT in LDS (radix-5, -3, -4 and -2 Stockham passes).  Returns complex64 (B, F, K) or (F, K),
+    K = n_fft // 2 + 1; `stft_mixed(p, x, 400, 160).transpose(-1, -2)` is the layout of torch.stft(x, 400, 160, window=v,
+    return_complex=True).  detrend=True (needs center=False) forms scipy's Welch segments, and
+    welch_psd(stft_mixed(..., detrend=True, center=False), scale, nfft=n_fft) is the fused Welch estimate at such an nfft.  A
+    power-of-two n_fft raises ValueError (bhw.stft transforms it: one transform per n_fft); any other unsupported n_fft raises
+    ValueError too.  The FFT is accurate to a float32 FFT's error, not pinned bit for bit."""
+    torch = _torch()
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise ValueError("x must be a float32 CUDA tensor")
+    return _stft_mixed(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, False, None, shift, out, x.device.index, None)
+
+
+def spectrogram_mixed(params, x, n_fft, hop, *, win_length=None, center=True, pad_mode="reflect", detrend=False, fbank=None, shift=None,
+                      out=None):
+    """spectrogram() at the n_fft of stft_mixed() (bhw_stft_mfft_f32_device with BHW_MFFT_POWER): each bin fl32(re^2 + im^2), taken in
+    binary64, of the float32 pair stft_mixed() would have written -- bit for bit -- or, with fbank (a FilterBank of n_fft // 2 + 1
+    bins, e.g. FilterBank(mel_weights(400, 80, 16000), device=x.device): Whisper's 400 / 160 / 80 mel front end), those powers folded
+    through the bank exactly as spectrogram() folds them.  Returns float32 (B, F, W) or (F, W), W = n_fft // 2 + 1 or fbank.filters.
+    The arguments, `out` rules and errors are spectrogram()'s; a power-of-two n_fft raises ValueError (bhw.spectrogram transforms
+    it)."""
+    torch = _torch()
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise ValueError("x must be a float32 CUDA tensor")
+    return _stft_mixed(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, True, fbank, shift, out, x.device.index, None)
+
+
 def _welch_fft(torch, params, x, length, hop, nfft, detrend, shift, out, dev, table):
     """The one-sided spectra of the Welch segments of x by the fused kernel: (B, frames, K) or (frames, K) complex64, into `out`
     (a packed complex64 tensor of that shape) when given."""
@@ -1475,6 +1548,19 @@ class ResidentTable:
         library, no synchronisation, capturable into a graph on its first call."""
         return _spectrogram(_torch(), params, x, n_fft, hop, win_length, center, pad_mode, detrend, fbank, shift, out, self.device,
                             self._live())
+
+    def stft_mixed(self, params, x, n_fft, hop, *, win_length=None, center=True, pad_mode="reflect", detrend=False, shift=None, out=None):
+        """stft_mixed() with the coefficients gathered from this table (bhw_stft_mfft_f32_from_table): no allocation by the library, no
+        synchronisation, capturable into a graph on its first call."""
+        return _stft_mixed(_torch(), params, x, n_fft, hop, win_length, center, pad_mode, detrend, False, None, shift, out, self.device,
+                           self._live())
+
+    def spectrogram_mixed(self, params, x, n_fft, hop, *, win_length=None, center=True, pad_mode="reflect", detrend=False, fbank=None,
+                          shift=None, out=None):
+        """spectrogram_mixed() with the coefficients gathered from this table (bhw_stft_mfft_f32_from_table with BHW_MFFT_POWER): no
+        allocation by the library, no synchronisation, capturable into a graph on its first call."""
+        return _stft_mixed(_torch(), params, x, n_fft, hop, win_length, center, pad_mode, detrend, True, fbank, shift, out, self.device,
+                           self._live())
 
     def stft_iq(self, params, x, n_fft, hop, *, win_length=None, center=True, pad_mode="reflect", detrend=False, shift=None,
                 fftshift=False, out=None):

@@ -686,7 +686,8 @@ int bhw_describe_csd(const bhw_csd *d, char *buf, uint64_t len);
  *     cosine or sine.  Its error against an exact transform of the float32 row is that of a float32 FFT (relative l2 error of a row
  *     of the order of 2^-24 * log2(n_fft) at most); the tests hold it to twice the error of rocFFT on the same rows.
  *   - Supported: channels 1 and n_fft a power of two in 16..4096.  Everything else -- complex input, other lengths -- is
- *     BHW_ERR_UNSUPPORTED.  The inverse is bhw_istft_fft_f32_* below.  Complex input has calls of its own: bhw_stft_cfft_f32_*.
+ *     BHW_ERR_UNSUPPORTED.  The inverse is bhw_istft_fft_f32_* below.  Complex input has calls of its own: bhw_stft_cfft_f32_*; so
+ *     has an even n_fft = 2^a 3^b 5^c that is no power of two (400, 480, 960, 1000, ...): bhw_stft_mfft_f32_*.
  *   - Descriptor: bhw_stft, where for these calls y_stride and y_batch_stride count FLOAT elements between spectrum rows and between
  *     signals; 0 means 2 * K and frames * y_stride.  Both must be even (rows of complex64 stay 8-byte aligned).  flags: 0 or
  *     BHW_WELCH_DETREND_CONSTANT; with the flag pad, col0 and pad_mode must be 0, as for the segments call.
@@ -785,8 +786,8 @@ int bhw_describe_istft_fft(bhw_table t, const bhw_params *p, uint64_t length, co
  *   - Capture: as bhw_stft_fft_f32_*.  The library form makes no allocation, uses no scratch and is capturable with no
  *     bhw_prepare_device; the from-table form is capturable on its first call.
  *   - Not built: magnitude (power 1); log (the caller applies it to the small result); a complex output next to the power;
- *     accumulating over frames in the kernel (Welch); complex input (bhw_stft_cfft_f32_* with BHW_CFFT_POWER is its power form);
- *     other n_fft.
+ *     accumulating over frames in the kernel (Welch); complex input (bhw_stft_cfft_f32_* with BHW_CFFT_POWER is its power form).
+ *     Other n_fft: bhw_stft_mfft_f32_* with BHW_MFFT_POWER writes these rows for an even n_fft = 2^a 3^b 5^c that is no power of two.
  *   - bhw_describe_spectrogram: the plan fields of bhw_describe_stft_fft's line in the same words, plus the mode, W, and for a bank
  *     filters, weights and filters per lane.  t may be NULL (the library call).  Host arithmetic only. */
 typedef struct bhw_fbank {
@@ -805,6 +806,59 @@ int bhw_spectrogram_f32_from_table(bhw_table t, const bhw_params *p, uint64_t le
                                    const bhw_fbank *fb, const float *d_x, float *d_P);
 int bhw_describe_spectrogram(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const bhw_fbank *fb,
                              char *buf, uint64_t len);
+
+/* Mixed-radix fused window and real FFT: the calls above for the row lengths speech and audio code uses and a power-of-two transform
+ * refuses -- n_fft 400 (25 ms at 16 kHz), 480 and 960 (10 and 20 ms at 48 kHz), 1000, 1200, 1920 -- by ONE launch, in the three
+ * output forms of bhw_stft_fft_f32_* and bhw_spectrogram_f32_*.  These are entry points of their own: bhw_stft_fft_f32_* and
+ * bhw_spectrogram_f32_* keep refusing such n_fft, and these refuse a power of two, so there is one transform per n_fft and the bits of
+ * a row never depend on which entry point was used.
+ *   - Supported: channels 1 and n_fft EVEN, of the form 2^a 3^b 5^c, 16 <= n_fft < 4096, and not a power of two.  A power of two is
+ *     BHW_ERR_UNSUPPORTED with a message that names bhw_stft_fft_f32_*; an odd n_fft, another prime factor, a value out of range and
+ *     channels 2 are BHW_ERR_UNSUPPORTED.
+ *   - flags: any combination of BHW_WELCH_DETREND_CONSTANT and BHW_MFFT_POWER.  fb non-NULL requires BHW_MFFT_POWER.  With the detrend
+ *     flag pad, col0 and pad_mode must be 0, as for the segments call.
+ *   - The row is pinned bit for bit: the float32 row bhw_stft_frames_f32_* (no detrend flag) or bhw_welch_frames_f32_* (with it) writes
+ *     for the same descriptor -- those calls take any n_fft -- under the whole row contract of bhw_stft_fft_f32_*: the padding modes,
+ *     col0, +0.0 around a window with L < n_fft, the mean in the header's fixed order, fl32(fl32(x - m) * v) unfused, and the Welch
+ *     extent rule (frames - 1) * hop + L <= samples whenever pad, col0 and pad_mode are all 0.
+ *   - The transform is NOT pinned bit for bit.  Sign and scaling of torch.fft.rfft.  A float32 Stockham transform of M = n_fft / 2
+ *     complex points (the row taken as pairs): the radix-5 passes of M, then its radix-3 passes, then floor(a' / 2) radix-4 passes for
+ *     M = 2^a' ..., then one radix-2 pass when a' is odd, the first pass without twiddles, and a split pass.  The schedule is a
+ *     function of n_fft alone.  Every twiddle factor is an entry (or the negative of an entry) of ONE table W[k] = exp(-2 pi i k /
+ *     n_fft), k < n_fft / 2, each component the float32 rounding of a binary64 value, read at an exact index and never a product;
+ *     the radix-3 and radix-5 butterfly constants are float32 roundings of binary64 values.  Its error is that of a float32 FFT
+ *     (relative l2 error of a row of the order of 2^-24 * log2(n_fft) at most); the tests hold it to twice the error of rocFFT on the
+ *     same rows.
+ *   - Spectrum form (no BHW_MFFT_POWER): rows of K = n_fft / 2 + 1 complex64 values as interleaved float pairs; y_stride and
+ *     y_batch_stride count FLOATS, must be even, 0 means 2 * K and frames * y_stride; d_out is 8-byte aligned.  The imaginary parts
+ *     of bins 0 and n_fft / 2 are written as +0.0.
+ *   - Power form (BHW_MFFT_POWER, fb NULL): rows of W = K floats, fl32((double) re * (double) re + (double) im * (double) im) of the
+ *     very pair the spectrum form writes; the strides count floats, 0 means W and frames * y_stride, no evenness rule applies and
+ *     d_out is 4-byte aligned.
+ *   - Bank form (BHW_MFFT_POWER, fb non-NULL): rows of W = filters floats, the powers folded through fb exactly as
+ *     bhw_spectrogram_f32_* does: fb->bins = K, a binary64 fma sum in ascending bin order from +0.0 rounded once, and the same
+ *     clamping (offsets into [0, weights] with end >= begin, a band stops at bin K), so a wrong bank never reads outside its arrays.
+ *   - Determinism: the bits of an output row depend only on the window, n_fft, flags, the bank and that row's samples -- not on the
+ *     batch, the slot, the group, the grid, the strides, or library versus table.
+ *   - IEEE: a NaN or an infinity in x reaches only the rows whose window covers it.  Only the W floats of each row are written.
+ *   - Checks before any HIP call (BHW_ERR_BADARG unless noted): unknown flag bits, fb without BHW_MFFT_POWER, everything the frames
+ *     call or the segments call checks for the descriptor with packed output strides, the unsupported channels or n_fft
+ *     (BHW_ERR_UNSUPPORTED), the fields of fb as bhw_spectrogram_f32_* checks them; frames 0 returns BHW_OK here with the pointers
+ *     unchecked; the stride rules of the output form, batch * frames * K (spectrum) or batch * frames * W above 2^34, NULL pointers,
+ *     alignment, d_out overlapping d_x or an array of fb; and (from a table) the key match.
+ *   - Capture: the library form computes the coefficients by direct CORDIC and the twiddle factors in the kernel: no allocation, no
+ *     scratch, capturable with no bhw_prepare_device.  The from-table form allocates nothing, never synchronises and is capturable
+ *     on its first call.
+ *   - Not built: the inverse at these lengths; I/Q input at these lengths; odd n_fft and prime factors of 7 and above.
+ *   - bhw_describe_stft_mfft: bhw_describe_stft_fft's line in the same words, plus the output form and, for a bank, its filters,
+ *     weights and filters per lane.  t may be NULL (the library call).  Host arithmetic only. */
+#define BHW_MFFT_POWER 2u
+int bhw_stft_mfft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                             const bhw_fbank *fb, const float *d_x, float *d_out);
+int bhw_stft_mfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                 const bhw_fbank *fb, const float *d_x, float *d_out);
+int bhw_describe_stft_mfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const bhw_fbank *fb,
+                           char *buf, uint64_t len);
 
 /* Fused window and complex FFT for interleaved I/Q input: the two-channel rows of bhw_stft_frames_f32_* (no detrend flag) or of
  * bhw_welch_frames_f32_* (BHW_WELCH_DETREND_CONSTANT) formed, transformed and written as their two-sided spectrum, or as its powers,
