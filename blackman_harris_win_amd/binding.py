@@ -48,6 +48,7 @@ ABI_SYMBOLS = (
     "bhw_istft_fft_f32_device", "bhw_istft_fft_f32_from_table", "bhw_describe_istft_fft",
     "bhw_spectrogram_f32_device", "bhw_spectrogram_f32_from_table", "bhw_describe_spectrogram",
     "bhw_stft_mfft_f32_device", "bhw_stft_mfft_f32_from_table", "bhw_describe_stft_mfft",
+    "bhw_istft_mfft_f32_device", "bhw_istft_mfft_f32_from_table", "bhw_describe_istft_mfft",
     "bhw_stft_cfft_f32_device", "bhw_stft_cfft_f32_from_table", "bhw_describe_stft_cfft",
     "bhw_istft_cfft_f32_device", "bhw_istft_cfft_f32_from_table", "bhw_describe_istft_cfft",
 )
@@ -322,6 +323,9 @@ def lib():
     L.bhw_stft_mfft_f32_device.argtypes = [P, u64, ci, vp, S, u32, FB, f32p, f32p]
     L.bhw_stft_mfft_f32_from_table.argtypes = [T, P, u64, vp, S, u32, FB, f32p, f32p]
     L.bhw_describe_stft_mfft.argtypes = [T, P, u64, S, u32, FB, ctypes.c_char_p, u64]
+    L.bhw_istft_mfft_f32_device.argtypes = [P, u64, ci, vp, S, u32, f32p, f32p]
+    L.bhw_istft_mfft_f32_from_table.argtypes = [T, P, u64, vp, S, u32, f32p, f32p]
+    L.bhw_describe_istft_mfft.argtypes = [T, P, u64, S, u32, ctypes.c_char_p, u64]
     L.bhw_stft_cfft_f32_device.argtypes = [P, u64, ci, vp, S, u32, vp, vp]
     L.bhw_stft_cfft_f32_from_table.argtypes = [T, P, u64, vp, S, u32, vp, vp]
     L.bhw_describe_stft_cfft.argtypes = [T, P, u64, S, u32, ctypes.c_char_p, u64]
@@ -508,6 +512,17 @@ def describe_stft_mfft(params, length, stft, *, detrend=False, power=False, fban
     flags = (WELCH_DETREND_CONSTANT if detrend else 0) | (MFFT_POWER if power else 0)
     check(lib().bhw_describe_stft_mfft(table, ctypes.byref(params), int(length), ctypes.byref(stft), flags,
                                        ctypes.byref(fbank) if fbank is not None else None, buf, len(buf)))
+    return buf.value.decode()
+
+
+def describe_istft_mfft(params, length, stft, *, normalize=False, table=None):
+    """One line: the plan fields of describe_istft_fft in the same words for the inverse mixed-radix transform (the schedule of
+    radix-5, -3, -4 and -2 passes behind the pre-split), for a fused inverse FFT + overlap-add over the window of `length` with the
+    descriptor `stft` (a BhwStft, make_stft; its y strides count floats of spectrum rows) (bhw_describe_istft_mfft).  `table` is a
+    resident table handle or None for the library call.  Host arithmetic only."""
+    buf = ctypes.create_string_buffer(1024)
+    check(lib().bhw_describe_istft_mfft(table, ctypes.byref(params), int(length), ctypes.byref(stft),
+                                        OLA_NORMALIZE if normalize else 0, buf, len(buf)))
     return buf.value.decode()
 
 

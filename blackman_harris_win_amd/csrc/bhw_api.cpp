@@ -1193,6 +1193,19 @@ int istft_fft_run(bhw_table t, const bhw_params *p, uint64_t length, int device,
                                                               const BhwLenPhase *lp) { return bhwk_istft_fft_f32(l, c, w, pl, s, d_Y, d_x, tab, *lp); });
 }
 
+// The mixed-radix fused inverse FFT + overlap-add (t NULL: the direct CORDIC chains): the checks, then the one kernel.
+int istft_mfft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *s, uint32_t flags,
+                   const float *d_Y, float *d_x)
+{
+    int rc = bhwp_istft_mfft_checks(p, length, s, flags, d_Y, d_x);
+    if (!rc && t) rc = table_call_checks(t, p);
+    if (rc || !s->samples) return rc;
+    const BhwIstftMfftPlan pl = bhwp_istft_mfft_plan(p, length, s, flags, t != nullptr);
+    const char *what = t ? "istft mfft launch (resident table)" : "istft mfft launch";
+    return run_source(t, p, length, device, stream, what, [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *tab,
+                                                              const BhwLenPhase *lp) { return bhwk_istft_mfft_f32(l, c, w, pl, s, d_Y, d_x, tab, *lp); });
+}
+
 // The fused inverse complex FFT + overlap-add for I/Q output (t NULL: the direct CORDIC chains): the checks, then the one kernel.
 int istft_cfft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *s, uint32_t flags,
                    const float *d_Y, float *d_x)
@@ -1499,6 +1512,29 @@ int bhw_describe_istft_fft(bhw_table t, const bhw_params *p, uint64_t length, co
     int rc = bhwp_istft_fft_checks(p, length, s, flags, nullptr, nullptr, false);
     if (!rc && t) rc = table_call_checks(t, p);
     return rc ? rc : bhwp_describe_istft_fft(p, t ? &t->c : nullptr, length, s, flags, buf, len);
+}
+
+// ---- fused inverse mixed-radix FFT, window and overlap-add (include/bhw.h: bhw_istft_mfft_f32_device ...) ------------------------------
+
+int bhw_istft_mfft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                              const float *d_Y, float *d_x)
+{
+    return istft_mfft_run(nullptr, p, length, device, hip_stream, s, flags, d_Y, d_x);
+}
+
+int bhw_istft_mfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                  const float *d_Y, float *d_x)
+{
+    const int rc = bhwp_istft_mfft_checks(p, length, s, flags, d_Y, d_x);
+    if (rc) return rc;
+    return t ? istft_mfft_run(t, p, length, t->device, hip_stream, s, flags, d_Y, d_x) : fail(BHW_ERR_BADARG, "table is NULL");
+}
+
+int bhw_describe_istft_mfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf, uint64_t len)
+{
+    int rc = bhwp_istft_mfft_checks(p, length, s, flags, nullptr, nullptr, false);
+    if (!rc && t) rc = table_call_checks(t, p);
+    return rc ? rc : bhwp_describe_istft_mfft(p, t ? &t->c : nullptr, length, s, flags, buf, len);
 }
 
 // ---- fused inverse complex FFT, window and overlap-add for I/Q output (include/bhw.h: bhw_istft_cfft_f32_device ...) --------------------

@@ -2142,6 +2142,119 @@ int bhwp_describe_istft_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64_
     return BHW_OK;
 }
 
+// ---- fused inverse mixed-radix FFT, window and overlap-add ----------------------------------------------------------------------------------
+
+int bhwp_istft_mfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const void *d_Y, const void *d_x,
+                           bool pointers)
+{
+    int rc = bhwp_f32_checks(p, length, flags);
+    if (rc) return rc;
+    if (!s) return bhwp_fail(BHW_ERR_BADARG, "stft descriptor is NULL");
+    if (s->struct_size != sizeof(bhw_stft)) return bhwp_fail(BHW_ERR_BADARG, "bhw_stft.struct_size %u != %zu", s->struct_size, sizeof(bhw_stft));
+    // what the overlap-add checks, for the same descriptor with packed rows (the input strides mean something else here and are
+    // checked below)
+    bhw_stft t = *s;
+    t.y_stride = t.y_batch_stride = 0;
+    rc = bhwp_stft_checks(p, length, &t, true, flags, nullptr, nullptr, false);
+    if (rc) return rc;
+    if (s->channels != 1)
+        return bhwp_fail(BHW_ERR_UNSUPPORTED, "channels %u: the mixed-radix fused inverse FFT gives real output (1)", s->channels);
+    if (!(s->n_fft & (s->n_fft - 1)))
+        return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu is a power of two: bhw_istft_fft_f32_* transforms it (one transform per n_fft)",
+                         (unsigned long long)s->n_fft);
+    if (!bhwp_mfft_supported(s->n_fft))
+        return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu: the mixed-radix fused inverse FFT takes an even 2^a 3^b 5^c in %u..%u",
+                         (unsigned long long)s->n_fft, kMfftMinN, kMfftMaxN);
+    const uint64_t T = s->samples, F = s->frames, K2 = s->n_fft + 2;          // 2K floats of a spectrum row
+    if (!T) return BHW_OK;                                           // (batch * frames * K is below the overlap-add's cap on n_fft)
+    if (s->y_stride && (s->y_stride < K2 || s->y_stride % 2))
+        return bhwp_fail(BHW_ERR_BADARG, "y_stride %llu: at least 2 * K = %llu floats, and even", (unsigned long long)s->y_stride,
+                         (unsigned long long)K2);
+    const uint64_t ys = s->y_stride ? s->y_stride : K2;
+    const unsigned __int128 ysig = (unsigned __int128)(F - 1) * ys + K2;
+    if (ysig > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "Y extent beyond 2^60 elements");
+    if (s->y_batch_stride && (s->y_batch_stride < (uint64_t)ysig || s->y_batch_stride % 2))
+        return bhwp_fail(BHW_ERR_BADARG, "y_batch_stride %llu: at least (frames - 1) * y_stride + 2 * K = %llu floats, and even",
+                         (unsigned long long)s->y_batch_stride, (unsigned long long)ysig);
+    if (!pointers) return BHW_OK;
+    if (!d_x || !d_Y) return bhwp_fail(BHW_ERR_BADARG, "d_Y / d_x is NULL");
+    if ((uintptr_t)d_Y % 8) return bhwp_fail(BHW_ERR_BADARG, "d_Y is not 8-byte aligned");
+    if ((uintptr_t)d_x % 4) return bhwp_fail(BHW_ERR_BADARG, "d_x is not 4-byte aligned");
+    const uint64_t xs = s->x_stride ? s->x_stride : T, ybs = s->y_batch_stride ? s->y_batch_stride : F * ys;
+    const unsigned __int128 xe = (unsigned __int128)(s->batch - 1) * xs + T, ye = (unsigned __int128)(s->batch - 1) * ybs + ysig;
+    if (xe > (1ull << 60) || ye > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "x or Y extent beyond 2^60 elements");
+    const uint64_t xa = (uint64_t)(uintptr_t)d_x, ya = (uint64_t)(uintptr_t)d_Y, xb = (uint64_t)xe * 4u, yb = (uint64_t)ye * 4u;
+    if (xa > UINT64_MAX - xb || ya > UINT64_MAX - yb) return bhwp_fail(BHW_ERR_BADARG, "x or Y range wraps the address space");
+    if (xa < ya + yb && ya < xa + xb) return bhwp_fail(BHW_ERR_BADARG, "d_Y and d_x overlap");
+    return BHW_OK;
+}
+
+BhwIstftMfftPlan bhwp_istft_mfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, bool from_table)
+{
+    // the lane layout and the radix schedule are the forward's
+    bhw_stft fw = *s;
+    fw.frames = 0;
+    const BhwStftMfftPlan f = bhwp_stft_mfft_plan(p, length, &fw, 0, nullptr, from_table);
+    BhwIstftMfftPlan pl{};
+    pl.route = f.route;
+    pl.normalize = (flags & BHW_OLA_NORMALIZE) != 0;
+    pl.m = f.m;
+    pl.lpf = f.lpf;
+    pl.fy = f.fy;
+    pl.cpl = f.cpl;
+    pl.passes = f.passes;
+    for (uint32_t i = 0; i < f.passes; ++i) pl.radix[i] = f.radix[i];
+    pl.lds_bytes = 2u * pl.fy * pl.m * 8u + pl.m * 8u + (uint32_t)s->n_fft * 4u;
+    pl.len = length;
+    pl.x_stride = s->x_stride ? s->x_stride : s->samples;
+    pl.y_stride = s->y_stride ? s->y_stride : s->n_fft + 2;
+    pl.y_bstride = s->y_batch_stride ? s->y_batch_stride : s->frames * pl.y_stride;
+    const IstftSpans sp = istft_spans(length, s, pl.fy);
+    pl.t0 = sp.t0;
+    pl.hop = sp.hop;
+    pl.halo = sp.halo;
+    pl.halo_bound = sp.halo_bound;
+    pl.span = sp.span;
+    pl.spans = sp.spans;
+    pl.groups = sp.groups;
+    pl.grid = sp.grid;
+    pl.trips = sp.trips;
+    return pl;
+}
+
+int bhwp_describe_istft_mfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf,
+                             uint64_t len)
+{
+    if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
+    const char *route = ct ? "table" : "direct";
+    const char *norm = (flags & BHW_OLA_NORMALIZE) ? "normalised by the window envelope" : "not normalised";
+    if (!s->samples) {
+        snprintf(buf, len, "istft mfft %s (L = %llu, n_fft %llu), %s: nothing (samples 0)", route, (unsigned long long)length,
+                 (unsigned long long)s->n_fft, norm);
+        return BHW_OK;
+    }
+    const BhwIstftMfftPlan pl = bhwp_istft_mfft_plan(p, length, s, flags, ct != nullptr);
+    BhwStftMfftPlan f{};
+    f.passes = pl.passes;
+    for (uint32_t i = 0; i < pl.passes; ++i) f.radix[i] = pl.radix[i];
+    char kern[64], sched[48];
+    kernel_name(p, ct, "k_istft_mfft_direct", "k_istft_mfft_table", false, kern, sizeof kern);
+    bhwp_stft_mfft_schedule(f, sched, sizeof sched);
+    // the repeats: every span but a signal's first transforms up to `halo` frames that the span before it transforms too
+    const uint64_t repeat = pl.spans > 1 ? (pl.halo < pl.span + pl.halo ? 100 * pl.halo / (pl.span + pl.halo) : 0) : 0;
+    const bool few = pl.halo_bound && pl.groups < kIfftTargetGroups / 4;
+    snprintf(buf, len, "istft mfft %s (L = %llu, n_fft %llu, col0 %llu, pad %llu: t0 = %llu), %s: %s, %llu signals x %llu frames = %llu rows, "
+             "inverse complex FFT of %u points in pre-split + passes %s, %u lanes per row x %u spans per workgroup, %u columns per lane, "
+             "spans of S = %llu frames + halo %llu (%llu spans per signal, up to %llu frames a span, %llu%% of the transforms repeated), "
+             "%llu groups, grid %llu x %u lanes, %u bytes of LDS%s", route, (unsigned long long)length, (unsigned long long)s->n_fft,
+             (unsigned long long)s->col0, (unsigned long long)s->pad, (unsigned long long)pl.t0, norm, kern, (unsigned long long)s->batch,
+             (unsigned long long)s->frames, (unsigned long long)(s->batch * s->frames), pl.m, sched, pl.lpf, pl.fy, pl.cpl,
+             (unsigned long long)pl.span, (unsigned long long)pl.halo, (unsigned long long)pl.spans, (unsigned long long)pl.trips,
+             (unsigned long long)repeat, (unsigned long long)pl.groups, (unsigned long long)pl.grid, kFftBlock, pl.lds_bytes,
+             few ? "; heavy overlap: the halo sets S and few workgroups run (irfft + istft overlap-add may be faster)" : "");
+    return BHW_OK;
+}
+
 // ---- fused inverse complex FFT, window and overlap-add for I/Q output ----------------------------------------------------------------------
 
 int bhwp_istft_cfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const void *d_Y, const void *d_x,

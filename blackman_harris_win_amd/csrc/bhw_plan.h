@@ -614,6 +614,33 @@ int  bhwp_describe_istft_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64
 int  bhwk_istft_fft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwIstftFftPlan &pl, const bhw_stft *s,
                         const float *d_Y, float *d_x, const int32_t *d_table, const BhwLenPhase &lp);
 
+// ---- fused inverse mixed-radix FFT, window and overlap-add (bhw_istft_mfft_f32_*; bhw_istft_mfft.hip) ---------------------------------
+// The lane layout and the radix schedule of bhwp_stft_mfft_plan (lpf lanes along a row of M = n_fft / 2 complex points, fy slots side
+// by side, cpl = ceil(n_fft / lpf) ring positions per lane, the last of which need not exist) under the spans of bhwp_istft_fft_plan:
+// the same S, halo, trips, halo_bound, grid cap and hop clamp, from one function (istft_spans in bhw_plan.cpp), and bhwp_istft_span as
+// it is.  LDS is BhwIstftFftPlan's formula: 16 000 bytes at n_fft 400, 64 800 at 4050, the largest.
+struct BhwIstftMfftPlan {
+    int route;            // BHWP_FRAMES_DIRECT or BHWP_FRAMES_TABLE
+    bool normalize;
+    uint32_t m, lpf, fy, cpl, passes;                  // as BhwStftMfftPlan
+    uint8_t radix[kMfftMaxPasses];
+    uint32_t lds_bytes;   // 2 * fy * M * 8 + M * 8 + n_fft * 4  (<= 64 800)
+    uint64_t t0, hop, halo, span, spans, groups, grid, trips;   // as BhwIstftFftPlan
+    bool halo_bound;
+    uint64_t x_stride, y_stride, y_bstride;   // resolved (0 -> samples, 2K, frames * y_stride)
+    uint64_t len;         // L
+};
+// Every check of the two calls that needs no table handle, before any HIP call (include/bhw.h).  samples 0 passes with the pointers
+// unchecked; `pointers` false: the describe call.
+int  bhwp_istft_mfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const void *d_Y, const void *d_x,
+                            bool pointers = true);
+// the plan of a call that passed the checks with samples > 0
+BhwIstftMfftPlan bhwp_istft_mfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, bool from_table);
+int  bhwp_describe_istft_mfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf,
+                              uint64_t len);
+int  bhwk_istft_mfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwIstftMfftPlan &pl, const bhw_stft *s,
+                         const float *d_Y, float *d_x, const int32_t *d_table, const BhwLenPhase &lp);
+
 // ---- fused inverse complex FFT, window and overlap-add for I/Q output (bhw_istft_cfft_f32_*; bhw_istft_cfft.hip) ----------------------
 // The lane layout and the passes of bhwp_stft_cfft_plan (lpf lanes along a row of n = n_fft complex points, fy slots side by side,
 // cpl complex columns per lane) under the spans of bhwp_istft_fft_plan: the same S, halo, trips, halo_bound, grid cap and hop clamp,

@@ -641,17 +641,34 @@ def _icfft_input(torch, Y, dev):
         raise ValueError("Y must be (frames, n_fft) or (B, frames, n_fft)")
 
 
+def _imfft_input(torch, Y, dev):
+    """_ifft_input for istft_mixed(): one-sided complex64 spectra (frames, K) or (B, frames, K).  The device is checked at the launch
+    (_istft), after every check that needs none."""
+    if not isinstance(Y, torch.Tensor) or Y.dtype != torch.complex64:
+        got = Y.dtype if isinstance(Y, torch.Tensor) else type(Y).__name__
+        raise ValueError(f"the mixed-radix fused inverse FFT takes one-sided complex64 spectra, got {got}")
+    if Y.dim() not in (2, 3):
+        raise ValueError("Y must be (frames, K) or (B, frames, K)")
+
+
 def _istft(torch, params, Y, n_fft, hop, win_length, center, length, normalize, shift, out, dev, table, check=_ifft_input,
            dtype=None, fftshift=False):
-    """The body istft() and istft_iq() share.  check: _ifft_input, or _icfft_input for I/Q output; dtype: the output's, float32 (the
-    one-sided spectra of istft) by default, complex64 for the two-sided spectra of istft_iq."""
+    """The body istft(), istft_mixed() and istft_iq() share.  check: _ifft_input, _imfft_input for the mixed-radix lengths, or
+    _icfft_input for I/Q output; dtype: the output's, float32 (the one-sided spectra of istft) by default, complex64 for the two-sided
+    spectra of istft_iq."""
     dtype = torch.float32 if dtype is None else dtype
     iq = dtype == torch.complex64
+    mixed = check is _imfft_input
     check(torch, Y, dev)
     n_fft, L, col0 = _stft_window(params, n_fft, win_length)
     if iq and not B.cfft_supported(n_fft):
         raise ValueError(f"the fused inverse complex FFT takes n_fft a power of two in {B.CFFT_MIN_N}..{B.CFFT_MAX_N}, got {n_fft}")
-    if not iq and not B.fft_supported(n_fft):
+    if mixed and B.fft_supported(n_fft):
+        raise ValueError(f"n_fft {n_fft} is a power of two: bhw.istft transforms it (one transform per n_fft)")
+    if mixed and not B.mfft_supported(n_fft):
+        raise ValueError(f"the mixed-radix fused inverse FFT takes an even n_fft = 2^a 3^b 5^c in {B.MFFT_MIN_N}..{B.MFFT_MAX_N} that is "
+                         f"no power of two, got {n_fft}")
+    if not iq and not mixed and not B.fft_supported(n_fft):
         raise ValueError(f"the fused inverse FFT takes n_fft a power of two in {B.FFT_MIN_N}..{B.FFT_MAX_N}, got {n_fft}")
     hop = int(hop)
     if hop < 1:
@@ -677,7 +694,7 @@ def _istft(torch, params, Y, n_fft, hop, win_length, center, length, normalize, 
     elif not isinstance(out, torch.Tensor) or out.dtype != dtype or out.device != Y.device or not out.is_contiguous() \
             or out.is_neg() or out.is_conj() or tuple(out.shape) != shape:
         raise ValueError(f"out must be a contiguous {str(dtype).replace('torch.', '')} tensor of shape {shape} on Y's device")
-    if iq and (not Y.is_cuda or Y.device.index != dev):
+    if (iq or mixed) and (not Y.is_cuda or Y.device.index != dev):
         raise ValueError("Y must be a complex64 CUDA tensor on the call's device")
     shift = params.dat_width - 1 if shift is None else int(shift)
     s = B.make_stft(nb, length, frames, hop, n_fft, col0=col0, pad=pad, shift=shift, channels=2 if iq else 1,
@@ -686,6 +703,7 @@ def _istft(torch, params, Y, n_fft, hop, win_length, center, length, normalize, 
     tail = (ctypes.byref(s), flags, ctypes.c_void_p(Yb.data_ptr()), ctypes.c_void_p(out.data_ptr()))
     L_ = B.lib()
     device_call, table_call = (L_.bhw_istft_cfft_f32_device, L_.bhw_istft_cfft_f32_from_table) if iq else \
+        (L_.bhw_istft_mfft_f32_device, L_.bhw_istft_mfft_f32_from_table) if mixed else \
         (L_.bhw_istft_fft_f32_device, L_.bhw_istft_fft_f32_from_table)
     if table is None:
         B.check(device_call(ctypes.byref(params), L, dev, _stream_ptr(torch, dev), *tail))
@@ -711,6 +729,22 @@ def istft(params, Y, n_fft, hop, *, win_length=None, center=True, length=None, n
     if not isinstance(Y, torch.Tensor) or not Y.is_cuda:
         raise ValueError("Y must be a complex64 CUDA tensor")
     return _istft(torch, params, Y, n_fft, hop, win_length, center, length, normalize, shift, out, Y.device.index, None)
+
+
+def istft_mixed(params, Y, n_fft, hop, *, win_length=None, center=True, length=None, normalize=True, shift=None, out=None):
+    """istft() at the n_fft of stft_mixed() in ONE launch (bhw_istft_mfft_f32_device): Y (B, F, K) or (F, K), complex64,
+    K = n_fft // 2 + 1 -- the layout stft_mixed() returns -- for n_fft even, 2^a·3^b·5^c, in 16..4095 and not a power of two (400, 480,
+    960, 1000, 1200, 1920, ...; ValueError otherwise, and a power of two names istft()).  Every row is transformed as
+    torch.fft.irfft(Y, n=n_fft) does by a float32 mixed-radix FFT in LDS (the 1 / n_fft scaling is one float32 multiply by
+    fl32(1 / n_fft); the imaginary parts of bins 0 and n_fft / 2 are ignored) and summed exactly as istft_overlap_add() sums time rows:
+    in ascending frame order in binary64, times v (window(params, win_length, dtype=torch.float32, shift=shift)), and with
+    normalize=True divided by the window envelope (+0.0 where no frame reaches).  The time rows never reach memory.  Keywords, the
+    default length, the treatment of views and `out` are istft()'s.  istft_mixed(params, S.transpose(-1, -2), 400, 160) is
+    torch.istft(S, 400, 160, window=v) to a float32 FFT's error.  With heavy overlap and little work (see describe_istft_mfft) few
+    workgroups run; torch.fft.irfft + istft_overlap_add remains for that case, and this call does not reroute to it."""
+    torch = _torch()
+    dev = Y.device.index if isinstance(Y, torch.Tensor) and Y.is_cuda else None
+    return _istft(torch, params, Y, n_fft, hop, win_length, center, length, normalize, shift, out, dev, None, _imfft_input)
 
 
 def istft_iq(params, Y, n_fft, hop, *, win_length=None, center=True, length=None, normalize=True, shift=None, fftshift=False, out=None):
@@ -1580,6 +1614,12 @@ class ResidentTable:
         """istft() with the coefficients gathered from this table (bhw_istft_fft_f32_from_table): no allocation by the library, no
         synchronisation, capturable into a graph on its first call."""
         return _istft(_torch(), params, Y, n_fft, hop, win_length, center, length, normalize, shift, out, self.device, self._live())
+
+    def istft_mixed(self, params, Y, n_fft, hop, *, win_length=None, center=True, length=None, normalize=True, shift=None, out=None):
+        """istft_mixed() with the coefficients gathered from this table (bhw_istft_mfft_f32_from_table): no allocation by the library,
+        no synchronisation, capturable into a graph on its first call."""
+        return _istft(_torch(), params, Y, n_fft, hop, win_length, center, length, normalize, shift, out, self.device, self._live(),
+                      _imfft_input)
 
     def istft_iq(self, params, Y, n_fft, hop, *, win_length=None, center=True, length=None, normalize=True, shift=None, fftshift=False,
                  out=None):

@@ -730,7 +730,8 @@ int bhw_describe_stft_fft(bhw_table t, const bhw_params *p, uint64_t length, con
  *         d_x[b * x_stride + t] = flags ? (E > 0 ? fl32(S / E) : +0.0) : fl32(S)
  *     Outputs no frame reaches are +0.0: samples past the frames' extent, and the gaps when hop > L.
  *   - Supported: channels 1 and n_fft a power of two in 16..4096; everything else -- complex output, other lengths -- is
- *     BHW_ERR_UNSUPPORTED.
+ *     BHW_ERR_UNSUPPORTED.  An even n_fft = 2^a 3^b 5^c that is no power of two (400, 480, 960, ...) has calls of its own:
+ *     bhw_istft_mfft_f32_*.
  *   - Descriptor: bhw_stft, where (as for bhw_stft_fft_f32_*) y_stride and y_batch_stride count FLOAT elements between spectrum rows
  *     and between signals; 0 means 2 * K and frames * y_stride; both must be even.  x_stride: floats between output signals.  flags:
  *     0 or BHW_OLA_NORMALIZE.  pad_mode must be 0, as for bhw_istft_ola_f32_*.
@@ -849,7 +850,8 @@ int bhw_describe_spectrogram(bhw_table t, const bhw_params *p, uint64_t length, 
  *   - Capture: the library form computes the coefficients by direct CORDIC and the twiddle factors in the kernel: no allocation, no
  *     scratch, capturable with no bhw_prepare_device.  The from-table form allocates nothing, never synchronises and is capturable
  *     on its first call.
- *   - Not built: the inverse at these lengths; I/Q input at these lengths; odd n_fft and prime factors of 7 and above.
+ *   - The inverse at these lengths is bhw_istft_mfft_f32_* below.  Not built: I/Q input at these lengths; odd n_fft and prime factors
+ *     of 7 and above.
  *   - bhw_describe_stft_mfft: bhw_describe_stft_fft's line in the same words, plus the output form and, for a bank, its filters,
  *     weights and filters per lane.  t may be NULL (the library call).  Host arithmetic only. */
 #define BHW_MFFT_POWER 2u
@@ -859,6 +861,58 @@ int bhw_stft_mfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t leng
                                  const bhw_fbank *fb, const float *d_x, float *d_out);
 int bhw_describe_stft_mfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const bhw_fbank *fb,
                            char *buf, uint64_t len);
+
+/* Fused inverse mixed-radix real FFT, window and overlap-add: bhw_istft_fft_f32_* for the row lengths of bhw_stft_mfft_f32_* --
+ * torch.fft.irfft(Y, n=n_fft) in front of bhw_istft_ola_f32_*, by ONE launch, for n_fft 400, 480, 960, 1000, 1200, 1920, ...  The time
+ * rows never reach memory, so the call takes no workspace.  These are entry points of their own: bhw_istft_fft_f32_* keeps refusing
+ * such n_fft, and these refuse a power of two, so there is one transform per n_fft.
+ *   - Supported: channels 1 and exactly the n_fft bhw_stft_mfft_f32_* take: EVEN, of the form 2^a 3^b 5^c, 16 <= n_fft < 4096, and not a
+ *     power of two.  A power of two is BHW_ERR_UNSUPPORTED with a message that names bhw_istft_fft_f32_*; an odd n_fft, another prime
+ *     factor, a value out of range and channels 2 are BHW_ERR_UNSUPPORTED.
+ *   - The row.  For b < batch, f < frames, r[j], j < n_fft, is the float32 inverse real transform of the K = n_fft / 2 + 1 bins
+ *     Y[k] = d_Y[b * y_batch_stride + f * y_stride + 2 * k + {0, 1}], with the convention and the scaling of
+ *     torch.fft.irfft(Y, n=n_fft).  1 / n_fft is no power of two here: the scaling is ONE float32 multiply of the transform's float32
+ *     result by c = (float)(1.0 / (double) n_fft) -- a multiply, not a division, so that a plain C replay reproduces it on any IEEE
+ *     machine whatever its division flags.  This is one rounding more than bhw_istft_fft_f32_* makes, whose scaling is exact.  The
+ *     imaginary parts of bins 0 and n_fft / 2 never enter the arithmetic.  The transform is NOT pinned bit for bit.  The bits of a row
+ *     depend on its K bins and n_fft only -- not on its place in a workgroup, the span that reads it, the grid, the strides or the
+ *     route.
+ *   - The transform.  A pre-split pass, then an inverse float32 Stockham transform of M = n_fft / 2 complex points in the schedule of
+ *     bhw_stft_mfft_f32_*: the radix-5 passes of M, then its radix-3 passes, then the radix-4 passes, then one radix-2 pass when
+ *     needed (5x5x4x2 at 400).  Every twiddle factor is an entry, or the negative of an entry, of ONE table W[k] = exp(+2 pi i k /
+ *     n_fft), k < M, each component the float32 rounding of a binary64 sincospi, read at the exact index q * k * (n_fft / (r * Ns));
+ *     indices >= M fold by a compare (W[i + M] = -W[i]), never a mask and never a product.  The radix-3 and radix-5 constants are the
+ *     forward's float32 roundings of binary64 values; the butterflies are the forward's, conjugated.  Its error is that of a float32
+ *     FFT (relative l2 error of a row of the order of 2^-24 * log2(n_fft) at most).
+ *   - The sum.  Given those rows every output is exactly what bhw_istft_ola_f32_* defines on them: for t < samples, u = t + pad, over
+ *     the frames f with 0 <= k = u - f * hop - col0 < L in ASCENDING f, in binary64 from +0.0:
+ *         S = sum (double) r_f[u - f * hop] * (double) v[k],   E = sum (double) v[k]^2
+ *         d_x[b * x_stride + t] = flags ? (E > 0 ? fl32(S / E) : +0.0) : fl32(S)
+ *     Outputs no frame reaches are +0.0: samples past the frames' extent, and the gaps when hop > L.
+ *   - Descriptor: bhw_stft, where y_stride and y_batch_stride count FLOAT elements between spectrum rows and between signals; 0 means
+ *     2 * K and frames * y_stride; both must be even.  x_stride: floats between output signals.  flags: 0 or BHW_OLA_NORMALIZE.
+ *     pad_mode must be 0, as for bhw_istft_ola_f32_*.
+ *   - Determinism: the bits of output (b, t) depend only on the window, n_fft, hop, col0, pad, flags and the spectrum rows whose
+ *     window covers t -- not on the batch, the plan, how a signal is cut into spans, the strides, or library versus table.
+ *   - IEEE: a NaN or an infinity in spectrum row (b, f) makes exactly the outputs under that row's window non-finite; every other
+ *     output keeps its bits.
+ *   - Only the `samples` floats of each signal are written: the gaps of x_stride never are.
+ *   - Checks before any HIP call (BHW_ERR_BADARG unless noted): everything bhw_istft_ola_f32_* checks for the descriptor with packed
+ *     row strides (unknown flags, pad < col0, frames 0 with samples > 0, col0 + L > n_fft, shift, a nonzero pad_mode, the Taylor sources
+ *     (BHW_ERR_UNSUPPORTED), ...), channels other than 1 and the unsupported n_fft (BHW_ERR_UNSUPPORTED), y_stride below 2 * K or odd,
+ *     y_batch_stride below (frames - 1) * y_stride + 2 * K or odd, NULL pointers, d_Y not 8-byte aligned, d_x not 4-byte aligned, d_Y
+ *     overlapping d_x, and (from a table) the key match.  samples 0 returns BHW_OK with the pointers unchecked.
+ *   - The library form computes the coefficients by direct CORDIC and the twiddle factors in the kernel: no allocation, no scratch,
+ *     capturable with no bhw_prepare_device.  The from-table form keeps the from-table contract: no allocation, no synchronisation,
+ *     capturable on its first call.
+ *   - Not built: I/Q output at these lengths; odd n_fft and prime factors of 7 and above; a fast path for heavy overlap.
+ *   - bhw_describe_istft_mfft: bhw_describe_istft_fft's line in the same words and fields, with the mixed-radix schedule ("5x5x4x2").
+ *     t may be NULL (the library call).  Host arithmetic only. */
+int bhw_istft_mfft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                              const float *d_Y, float *d_x);
+int bhw_istft_mfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                  const float *d_Y, float *d_x);
+int bhw_describe_istft_mfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf, uint64_t len);
 
 /* Fused window and complex FFT for interleaved I/Q input: the two-channel rows of bhw_stft_frames_f32_* (no detrend flag) or of
  * bhw_welch_frames_f32_* (BHW_WELCH_DETREND_CONSTANT) formed, transformed and written as their two-sided spectrum, or as its powers,
