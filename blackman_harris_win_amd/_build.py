@@ -150,16 +150,25 @@ def _write_resources(compiler_output):
         json.dump(res, f, indent=0, sort_keys=True)
 
 
+ORACLE_SOURCES = ("bhw_oracle.c", "bhw_oracle.h", "cpu_baseline.c", "Makefile")
+# these go into oracle/_ref's HLS binaries only (oracle/Makefile rebuilds those when either is newer).  A tree that carries the
+# built oracle without them is not an error: nothing can be rebuilt from an absent file, so it enters the digest as absent.
+ORACLE_REF_SOURCES = ("ref_hls_wrap.cpp", os.path.join("shim", "ap_int.h"))
+
+
+def _oracle_digest():
+    present = [f for f in ORACLE_REF_SOURCES if os.path.exists(os.path.join(ORACLE_DIR, f))]
+    return _digest([os.path.join(ORACLE_DIR, f) for f in ORACLE_SOURCES + tuple(present)], extra=" ".join(present))
+
+
 def oracle_stale():
-    srcs = [os.path.join(ORACLE_DIR, f) for f in ("bhw_oracle.c", "bhw_oracle.h", "cpu_baseline.c", "Makefile")]
-    return not _stamp_ok(os.path.join(ORACLE_DIR, "liboracle.so"), _digest(srcs))
+    return not _stamp_ok(os.path.join(ORACLE_DIR, "liboracle.so"), _oracle_digest())
 
 
 def build_oracle(force=False):
     """Compile oracle/liboracle.so (test infrastructure) and, when the upstream checkout is present,
-    oracle/_ref from the reference's own cordic() source.  Building the checker is not using it."""
+    oracle/_ref from the reference's own cordic() and HLS win_function() sources.  Building the checker is not using it."""
     args = ["make", "-C", ORACLE_DIR, "REF=" + REFERENCE]
-    srcs = [os.path.join(ORACLE_DIR, f) for f in ("bhw_oracle.c", "bhw_oracle.h", "cpu_baseline.c", "Makefile")]
     if force:
         _run(["make", "-C", ORACLE_DIR, "clean"])
     else:   # make compares mtimes; a changed source with an older timestamp must still rebuild
@@ -167,7 +176,7 @@ def build_oracle(force=False):
             if oracle_stale() and os.path.exists(os.path.join(ORACLE_DIR, lib)):
                 os.remove(os.path.join(ORACLE_DIR, lib))
     out = _run(args)
-    _write_stamp(os.path.join(ORACLE_DIR, "liboracle.so"), _digest(srcs))
+    _write_stamp(os.path.join(ORACLE_DIR, "liboracle.so"), _oracle_digest())
     return out
 
 

@@ -224,3 +224,72 @@ class RefCordic:
             self.fn(int(th), self.lut, ctypes.byref(si), ctypes.byref(ci))
             s[i], c[i] = si.value, ci.value
         return s, c
+
+
+# ---- oracle/_ref: the reference's HLS win_function() / cordic(), compiled from hls/windows/win_function.cpp and
+# ---- hls/cordic/cordic.cpp against oracle/shim/ap_int.h, built per (NPHASE, NWIDTH) (oracle/Makefile) ----
+def ref_hls_pairs(kind="win"):
+    """(NPHASE, NWIDTH, path) of every built libref_hls_<kind>_<PW>_<W>.so; kind is "win" (win_function.cpp) or "cordic"."""
+    out = []
+    for f in glob.glob(os.path.join(REF_DIR, f"libref_hls_{kind}_*.so")):
+        m = re.search(r"_(\d+)_(\d+)\.so$", f)
+        out.append((int(m.group(1)), int(m.group(2)), f))
+    return sorted(out)
+
+
+_hls = {}
+
+
+def _ref_hls(kind, pw, w):
+    key = (kind, int(pw), int(w))
+    if key not in _hls:
+        path = os.path.join(REF_DIR, f"libref_hls_{kind}_{key[1]}_{key[2]}.so")
+        if not os.path.exists(path):
+            raise FileNotFoundError(path)
+        lib = ctypes.CDLL(path)
+        u64, vp = ctypes.c_uint64, ctypes.c_void_p
+        lib.ref_hls_widths.restype = None
+        lib.ref_hls_widths.argtypes = [ctypes.POINTER(ctypes.c_int)] * 2
+        lib.ref_hls_sincos.restype = None
+        lib.ref_hls_sincos.argtypes = [u64, u64, vp, vp]
+        if kind == "win":
+            lib.ref_hls_window.restype = None
+            lib.ref_hls_window.argtypes = [ctypes.c_int, u64, u64, vp]
+        _hls[key] = lib
+    return _hls[key]
+
+
+def ref_hls_widths(kind, pw, w):
+    """The (NPHASE, NWIDTH) a binary of oracle/_ref was compiled at, as the binary itself reports them."""
+    a, b = ctypes.c_int(), ctypes.c_int()
+    _ref_hls(kind, pw, w).ref_hls_widths(ctypes.byref(a), ctypes.byref(b))
+    return a.value, b.value
+
+
+def reference_hls_window_type(win_type, pw, w, n0, count):
+    """win_function(win_type, n mod 2^NPHASE) of the compiled hls/windows/win_function.cpp for n = n0 .. n0 + count - 1."""
+    out = np.empty(int(count), np.int32)
+    _ref_hls("win", pw, w).ref_hls_window(int(win_type), int(n0), int(count), out.ctypes.data)
+    return out
+
+
+def reference_hls_window(p, n0, count):
+    """The window of parameter set p (HLS model, HLS rule, the built-in weights) as the reference's own compiled win_function()
+    evaluates it: CORDIC, weights, products, sum and the win_t store all run from the reference's text (oracle/_ref).  In-process,
+    one thread.  Raises FileNotFoundError when that width pair was not built, ValueError when p is not one of the six built-in
+    windows (the reference has no caller-supplied weights)."""
+    if (p.model, p.combine, p.sin_type) != (MODEL_HLS, COMBINE_HLS, SIN_CORDIC):
+        raise ValueError("the compiled win_function() is the HLS model in the HLS rule")
+    aa = list(p.aa)
+    wins = [wt for wt in (1, 2, 3, 4, 5, 7) if TERMS[wt] == p.n_terms and coeffs(wt, p.dat_width) == aa]
+    if not wins:
+        raise ValueError("not a built-in window of the reference")
+    return reference_hls_window_type(wins[0], p.phi_width, p.dat_width, n0, count)
+
+
+def reference_hls_sincos(p, theta0, count, kind="win"):
+    """(sin, cos) from cordic() of the compiled win_function.cpp (kind "win") or hls/cordic/cordic.cpp (kind "cordic")."""
+    s = np.empty(int(count), np.int32)
+    c = np.empty(int(count), np.int32)
+    _ref_hls(kind, p.phi_width, p.dat_width).ref_hls_sincos(int(theta0), int(count), s.ctypes.data, c.ctypes.data)
+    return s, c

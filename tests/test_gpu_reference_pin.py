@@ -3,12 +3,18 @@
 (1) whole windows from the HIP path vs the same windows evaluated by the REFERENCE'S OWN COMPILED cordic() (oracle/_ref:
     cpp/cordic_sincos.cpp compiled from its source at the test's widths, oracle/Makefile) inside the reference's cosine-sum
     (hls/windows/win_function.cpp:361-375, restated in oracle/cpu_baseline.c::ref_worker) -- model CPP, the one model of
-    the reference that builds with a stock compiler here;
+    the reference that builds with a stock compiler as it stands;
 (2) the reference's own pass criteria applied to the HIP output: hls/windows/window_test.cpp:93-216
     (sqrt(sum err^2) / NSAMPLES < 10 against round((2^(NWIDTH-shift) - 1) * w_float), shift 1 for 2/3/4 terms, 2 for 5/7) and
     hls/cordic/cordic_test.cpp:66-93 (mean |err| per channel < 10 against round(2^(NWIDTH-2) * sin/cos)).  For the models
-    no stock compiler or simulator here can run (HLS: needs ap_int.h; VHDL cordic_dds and the Taylor feeder: no simulator)
-    these criteria are the only reference-held checks there are; they run at the BASELINE sizes C1, C2, C3 (and C4's frame).
+    no simulator is at hand for (VHDL cordic_dds and the Taylor feeder) these criteria are the only reference-held checks there
+    are; they run at the BASELINE sizes C1, C2, C3 (and C4's frame);
+(3) the HLS model in the HLS rule -- the benchmarked default -- against the reference's own compiled win_function() and cordic()
+    (oracle/_ref/libref_hls_*: hls/windows/win_function.cpp and hls/cordic/cordic.cpp compiled unchanged against the project's
+    stand-in oracle/shim/ap_int.h): CORDIC, weights, products, sum and the win_t store all run from the reference's text.  Stored
+    as md5s by tests/golden/make_reference_pins.py (keys hls_windows, hls_sincos), so the tests need neither the upstream
+    checkout nor oracle/_ref; where oracle/_ref is there the arrays themselves are compared too.  Every data width 8..32, the
+    BASELINE sizes, the edges of the init_z branch (PW = W, W + 1, W + 2).
 """
 import hashlib
 import os
@@ -201,3 +207,101 @@ def test_reference_cordic_rule_on_gpu_output_taylor(torch, pw, w, L):
         es, ec = torch.where(bad, torch.zeros_like(es), es), torch.where(bad, torch.zeros_like(ec), ec)
     assert float(es.sum()) / n < max(10, tol) and float(ec.sum()) / n < max(10, tol)
     assert float(es.max()) <= tol and float(ec.max()) <= tol
+
+
+# ---- (3) reference-compiled win_function() / cordic(): the HLS model, bit for bit ------------------------------------------
+HLS_KEYS = ["10_%d" % w for w in range(8, 33)] + ["12_16", "16_24", "4_16", "16_16", "17_16", "6_8", "4_32", "13_31",
+                                                  "20_24", "18_32", "24_30", "26_32", "30_28"]
+
+
+def _hls_live(kind, pw, w):
+    return any((a, b) == (pw, w) for a, b, _ in O.ref_hls_pairs(kind))
+
+
+def _first_bad_block(got, we):
+    """Index of the first block of the pin's block size whose md5 differs (None: the pin has no block md5s)."""
+    if "block_md5" not in we:
+        return None
+    b = we["block"]
+    return next((i for i, m in enumerate(we["block_md5"]) if _md5(got[i * b:(i + 1) * b]) != m), None)
+
+
+def _check_hls_window(torch, make, we, p, pw, w, win, algos):
+    """One window of an hls_windows entry: `make(p, n0, count, algo)` returns the device tensor.  The whole period through every
+    algo (one copy and one md5: the algos are compared with each other on the device), then the ragged ranges."""
+    n = 1 << pw
+    live = _hls_live("win", pw, w)
+    if "md5" in we:
+        outs = [make(p, 0, n, algo) for algo in algos]
+        for algo, o in zip(algos[1:], outs[1:]):
+            assert torch.equal(o, outs[0]), (pw, w, win, "algo", algo, "differs from algo", algos[0])
+        got = outs[0].cpu().numpy()
+        del outs
+        if _md5(got) != we["md5"]:
+            raise AssertionError((pw, w, win, "md5 differs from the compiled reference; first bad block", _first_bad_block(got, we)))
+        if live and pw <= 16:
+            assert np.array_equal(got, O.reference_hls_window(O.from_bhw(p), 0, n)), (pw, w, win)
+    assert we["ranges"] or pw < 10
+    for r in we["ranges"]:
+        got_r = make(p, r["n0"], r["count"], B.ALGO_AUTO).cpu().numpy()
+        assert _md5(got_r) == r["md5"], (pw, w, win, r["n0"])
+        if live:
+            assert np.array_equal(got_r, O.reference_hls_window(O.from_bhw(p), r["n0"], r["count"])), (pw, w, win, r["n0"])
+
+
+@pytest.mark.parametrize("key", HLS_KEYS)
+def test_hls_window_vs_reference_compiled_win_function(torch, reference_pins, key):
+    """bhw.generate (HLS model, HLS rule, built-in weights) == win_function() of the compiled reference: whole periods through
+    ALGO_AUTO, ALGO_TABLE and, up to 2^20, ALGO_DIRECT and ALGO_FUSED; ranges that wrap the period (at 30/28: ranges alone, across
+    every quadrant boundary).  The 10_W cases are the every-width family: six windows each."""
+    import blackman_harris_win_amd as bhw
+    assert sorted(reference_pins["hls_windows"]) == sorted(HLS_KEYS)
+    pin = reference_pins["hls_windows"][key]
+    pw, w = pin["phi_width"], pin["dat_width"]
+    assert key == "%d_%d" % (pw, w) and (pin["model"], pin["combine"]) == ("hls", "hls")
+    assert len(pin["windows"]) == (6 if pw <= 17 or pw == 30 else 1)
+    algos = [B.ALGO_AUTO, B.ALGO_TABLE] + ([B.ALGO_DIRECT, B.ALGO_FUSED] if pw <= 20 else [])
+    for win, we in sorted(pin["windows"].items()):
+        assert ("md5" in we) == (pw != 30) and ("block_md5" in we) == (pw > 17 and pw != 30)
+        p = B.make_params(int(win), pw, w, model=B.MODEL_HLS, combine=B.COMBINE_HLS)
+        _check_hls_window(torch, lambda p, n0, cnt, algo: bhw.generate(p, n0, cnt, algo=algo), we, p, pw, w, int(win), algos)
+
+
+@pytest.mark.parametrize("key", ["12_16", "20_24", "10_32"])
+def test_hls_window_from_resident_table_vs_reference_compiled_win_function(torch, reference_pins, key):
+    """The same pins through a resident table: one table per width pair, every pinned window of that pair from it."""
+    import blackman_harris_win_amd as bhw
+    pin = reference_pins["hls_windows"][key]
+    pw, w = pin["phi_width"], pin["dat_width"]
+    first = B.make_params(int(min(pin["windows"])), pw, w, model=B.MODEL_HLS, combine=B.COMBINE_HLS)
+    with bhw.ResidentTable(first) as rt:
+        for win, we in sorted(pin["windows"].items()):
+            p = B.make_params(int(win), pw, w, model=B.MODEL_HLS, combine=B.COMBINE_HLS)
+            _check_hls_window(torch, lambda p, n0, cnt, algo: rt.generate(p, n0, cnt), we, p, pw, w, int(win), [B.ALGO_AUTO])
+
+
+@pytest.mark.parametrize("key", HLS_KEYS)
+def test_hls_sincos_vs_reference_compiled_cordic(torch, reference_pins, key):
+    """bhw.cordic (HLS model) == cordic() of the compiled hls/windows/win_function.cpp and hls/cordic/cordic.cpp (one md5 stands for
+    both: make_reference_pins.py stores it only after they agree): the full circle up to 2^20, and ranges that wrap the period
+    (above 2^20 also across every quadrant boundary)."""
+    import blackman_harris_win_amd as bhw
+    assert sorted(reference_pins["hls_sincos"]) == sorted(HLS_KEYS)
+    pin = reference_pins["hls_sincos"][key]
+    pw, w = pin["phi_width"], pin["dat_width"]
+    assert key == "%d_%d" % (pw, w) and pin["model"] == "hls"
+    p = B.make_params(1, pw, w, model=B.MODEL_HLS)
+    kinds = [k for k in pin["sources"] if _hls_live(k, pw, w)]
+    n = 1 << pw
+    assert ("sin_md5" in pin) == (pw <= 20) and (pin["ranges"] or pw < 10) and len(pin["ranges"]) == (0 if pw < 10 else 1 if pw <= 20 else 4)
+    spans = [(r["theta0"], r["count"], r["sin_md5"], r["cos_md5"]) for r in pin["ranges"]]
+    if pw <= 20:
+        spans.append((0, n, pin["sin_md5"], pin["cos_md5"]))
+    for t0, cnt, sin_md5, cos_md5 in spans:
+        s, c = bhw.cordic(p, t0, cnt)
+        s, c = s.cpu().numpy(), c.cpu().numpy()
+        assert (_md5(s), _md5(c)) == (sin_md5, cos_md5), (key, t0)
+        if cnt <= 1 << 16:
+            for k in kinds:
+                rs, rc = O.reference_hls_sincos(O.from_bhw(p), t0, cnt, k)
+                assert np.array_equal(s, rs) and np.array_equal(c, rc), (key, k, t0)

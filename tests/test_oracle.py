@@ -403,3 +403,133 @@ def test_oracle_rejects_bad_params():
     with pytest.raises(ValueError):
         O.generate(O.oparams(5, 10, 16, sin_type=O.SIN_TAYLOR), 0, 4)   # reference wiring: 2-/3-term only
     assert len(O.generate(O.oparams(5, 10, 16, sin_type=O.SIN_TAYLOR_ALL), 0, 4)) == 4
+
+
+# ---- model B (HLS) pinned by the reference's own compiled win_function() / cordic() -------------------------------------
+# oracle/_ref/libref_hls_*: hls/windows/win_function.cpp and hls/cordic/cordic.cpp compiled as they stand against oracle/shim/ap_int.h
+# (oracle/Makefile).  CORDIC, weights (round(coe * (pow(2.0, NWIDTH - s) - 1.0)) in double), the 2 NWIDTH + 1 bit products, the sum and
+# the (win_t) store all run from the reference's text.  Every comparison below is equality.
+_WINS = (1, 2, 3, 4, 5, 7)
+# REF_HLS_PAIRS / REF_HLS_CORDIC_PAIRS of oracle/Makefile
+HLS_PAIRS = [(10, w) for w in range(8, 33)] + [(12, 16), (20, 24), (16, 24), (26, 32), (4, 16), (16, 16), (17, 16), (6, 8), (30, 28),
+                                               (4, 32), (13, 31), (18, 32), (24, 30)]
+HLS_CORDIC_PAIRS = [(10, 16), (12, 16), (20, 24), (26, 32), (10, 8), (17, 16), (30, 28)]
+
+
+def _hls_built(kind="win"):
+    return {(pw, w) for pw, w, _ in O.ref_hls_pairs(kind)}
+
+
+def _sample_blocks(pw, seed):
+    """Where the period is too long to compare whole: the first and last 4096 points of each quadrant and 16 random blocks of 4096."""
+    n, q, b = 1 << pw, 1 << (pw - 2), 4096
+    rng = np.random.default_rng(seed)
+    starts = [j * q for j in range(4)] + [(j + 1) * q - b for j in range(4)] + [int(v) for v in rng.integers(0, n - b, 16)]
+    return [(s, b) for s in starts]
+
+
+def test_hls_reference_binaries_are_the_listed_pairs():
+    """Where oracle/_ref has HLS binaries at all, it has every listed pair and no other (so the parametrised tests below cover every
+    built pair), and each binary reports the widths in its file name."""
+    if not O.ref_hls_pairs() and not O.ref_hls_pairs("cordic"):
+        return
+    assert _hls_built() == set(HLS_PAIRS) and _hls_built("cordic") == set(HLS_CORDIC_PAIRS)
+    for kind, pairs in (("win", HLS_PAIRS), ("cordic", HLS_CORDIC_PAIRS)):
+        for pw, w in pairs:
+            assert O.ref_hls_widths(kind, pw, w) == (pw, w)
+
+
+@pytest.mark.parametrize("pw,w", HLS_PAIRS)
+def test_model_b_window_equals_compiled_win_function(reference_pins, pw, w):
+    """The oracle's model-B window == win_function() of the compiled reference: the whole period of all six windows at PW <= 17,
+    elsewhere the quadrant edges and 16 random blocks of 4096; and both reproduce the md5s stored under hls_windows.  Where
+    oracle/_ref was not built the stored md5s (made from the compiled reference) are held against the oracle alone.
+    This is also the check of O.coeffs(win, W) at every W in 8..32 against the weights the reference's round(...) produces: the
+    10_W pairs compare whole windows of every type, and a weight off by one LSB changes a whole window."""
+    pin = reference_pins["hls_windows"]["%d_%d" % (pw, w)]
+    assert (pin["phi_width"], pin["dat_width"], pin["model"], pin["combine"]) == (pw, w, "hls", "hls")
+    n = 1 << pw
+    live = (pw, w) in _hls_built()
+    seen = 0
+    for win in _WINS:
+        p = O.oparams(win, pw, w)
+        we = pin["windows"].get(str(win))
+        if we is not None:
+            seen += 1
+            if "md5" in we and pw <= 20:
+                full = O.generate_mt(p, 0, n) if pw > 17 else O.generate(p, 0, n)
+                assert _md5(full) == we["md5"], (pw, w, win)
+                if live and pw <= 17:
+                    assert np.array_equal(O.reference_hls_window(p, 0, n), full), (pw, w, win)
+            elif "md5" in we:       # 2^24 and 2^26: the first, the last and one inner block of 2^20 (the GPU test hashes them all)
+                blocks = we["block_md5"]
+                assert we["block"] == 1 << 20 and len(blocks) == n >> 20
+                for b in (0, len(blocks) // 3, len(blocks) - 1):
+                    assert _md5(O.generate_mt(p, b << 20, 1 << 20)) == blocks[b], (pw, w, win, b)
+            for r in we["ranges"]:
+                got = O.generate(p, r["n0"], r["count"])
+                assert _md5(got) == r["md5"], (pw, w, win, r["n0"])
+                if live:
+                    assert np.array_equal(O.reference_hls_window(p, r["n0"], r["count"]), got), (pw, w, win, r["n0"])
+        if live and pw > 17:
+            for n0, cnt in _sample_blocks(pw, 1000 * pw + w):
+                assert np.array_equal(O.reference_hls_window(p, n0, cnt), O.generate(p, n0, cnt)), (pw, w, win, n0)
+    assert seen == (6 if pw <= 17 or pw == 30 else 1)
+    if live:     # an unknown win_type is the reference's win_empty
+        for bad in (0, 6, 8, 100, -1):
+            assert not O.reference_hls_window_type(bad, pw, w, 0, min(n, 64)).any()
+
+
+@pytest.mark.parametrize("pw,w", HLS_PAIRS)
+def test_model_b_sincos_equals_compiled_cordic(reference_pins, pw, w):
+    """The oracle's model-B (sin, cos) == cordic() of the compiled hls/windows/win_function.cpp and, where built, of the compiled
+    hls/cordic/cordic.cpp (which therefore agree with each other): the full circle at PW <= 17, elsewhere the sampled blocks; and
+    the md5s stored under hls_sincos, which the oracle alone holds where oracle/_ref was not built."""
+    pin = reference_pins["hls_sincos"]["%d_%d" % (pw, w)]
+    assert (pin["phi_width"], pin["dat_width"], pin["model"]) == (pw, w, "hls")
+    assert pin["sources"] == ["win"] + (["cordic"] if (pw, w) in HLS_CORDIC_PAIRS else [])
+    n = 1 << pw
+    p = O.oparams(1, pw, w)
+    kinds = [k for k in pin["sources"] if (pw, w) in _hls_built(k)]
+    spans = [(r["theta0"], r["count"], r["sin_md5"], r["cos_md5"]) for r in pin["ranges"]]
+    assert ("sin_md5" in pin) == (pw <= 20) and (spans or pw < 10)
+    if pw <= 20:
+        spans.append((0, n, pin["sin_md5"], pin["cos_md5"]))
+    spans += [(t0, cnt, None, None) for t0, cnt in (_sample_blocks(pw, 2000 * pw + w) if pw > 17 and kinds else [])]
+    for t0, cnt, sin_md5, cos_md5 in spans:
+        s, c = (O.sincos_mt if cnt >= 1 << 18 else O.sincos)(p, t0, cnt)
+        if sin_md5 is not None:
+            assert (_md5(s), _md5(c)) == (sin_md5, cos_md5), (pw, w, t0)
+        if cnt > 1 << 17:
+            continue
+        got = {k: O.reference_hls_sincos(p, t0, cnt, k) for k in kinds}
+        for k, (rs, rc) in got.items():
+            assert np.array_equal(rs, s) and np.array_equal(rc, c), (pw, w, k, t0)
+        if len(got) == 2:
+            assert np.array_equal(got["win"][0], got["cordic"][0]) and np.array_equal(got["win"][1], got["cordic"][1])
+
+
+def test_model_b_goldens_equal_compiled_win_function(golden, golden_dir):
+    """The model-B entries of tests/golden/golden.json (SURVEY App. B known answers) against the compiled win_function().  Without
+    oracle/_ref there is nothing to run here; test_model_b_known_answers and the md5 pins above hold the same windows."""
+    if not set(HLS_PAIRS) <= _hls_built():
+        return
+    for name, win in [("C1_hamming_12_16", 1), ("C2_bh4_20_24", 4), ("C4_bh4_16_24_frame", 4), ("bh5_10_24", 5), ("bh7_4_16", 7)]:
+        e = golden[name]
+        pr = e["params"]
+        assert O.coeffs(win, pr["dat_width"]) == pr["aa"] and O.TERMS[win] == pr["n_terms"]
+        a = O.reference_hls_window_type(win, pr["phi_width"], pr["dat_width"], e["n0"], e["count"])
+        assert _md5(a) == e["md5"], name
+        assert int(a.astype(np.int64).sum()) == e["sum"] and int(a.min()) == e["min"] and int(a.max()) == e["max"]
+        if "file" in e:
+            assert np.array_equal(a, np.load(os.path.join(golden_dir, e["file"])))
+        for n, v in e.get("sparse", {}).items():
+            assert int(a[int(n)]) == v
+    e = golden["C3_bh7_26_32"]
+    assert O.coeffs(7, 32) == e["params"]["aa"]
+    for n, v in e["sparse"].items():
+        assert int(O.reference_hls_window_type(7, 26, 32, int(n), 1)[0]) == v
+    step = (1 << 23) // 1024
+    for g, shard in enumerate(e["shards"]):
+        got = [int(O.reference_hls_window_type(7, 26, 32, (g << 23) + i * step, 1)[0]) for i in range(1024)]
+        assert got == shard["strided_1024"], g
