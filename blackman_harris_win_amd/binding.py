@@ -51,6 +51,7 @@ ABI_SYMBOLS = (
     "bhw_istft_mfft_f32_device", "bhw_istft_mfft_f32_from_table", "bhw_describe_istft_mfft",
     "bhw_stft_cfft_f32_device", "bhw_stft_cfft_f32_from_table", "bhw_describe_stft_cfft",
     "bhw_istft_cfft_f32_device", "bhw_istft_cfft_f32_from_table", "bhw_describe_istft_cfft",
+    "bhw_welch_fft_workspace_bytes", "bhw_welch_fft_f32_device", "bhw_welch_fft_f32_from_table", "bhw_describe_welch_fft",
 )
 
 
@@ -332,6 +333,12 @@ def lib():
     L.bhw_istft_cfft_f32_device.argtypes = [P, u64, ci, vp, S, u32, f32p, f32p]
     L.bhw_istft_cfft_f32_from_table.argtypes = [T, P, u64, vp, S, u32, f32p, f32p]
     L.bhw_describe_istft_cfft.argtypes = [T, P, u64, S, u32, ctypes.c_char_p, u64]
+    f64 = ctypes.c_double
+    L.bhw_welch_fft_workspace_bytes.restype = u64
+    L.bhw_welch_fft_workspace_bytes.argtypes = [S]
+    L.bhw_welch_fft_f32_device.argtypes = [P, u64, ci, vp, S, u32, f64, u32, f32p, f32p, u64, vp, u64]
+    L.bhw_welch_fft_f32_from_table.argtypes = [T, P, u64, vp, S, u32, f64, u32, f32p, f32p, u64, vp, u64]
+    L.bhw_describe_welch_fft.argtypes = [T, P, u64, S, u32, ctypes.c_char_p, u64]
     PA = ctypes.POINTER(BhwAtan2Params)
     L.bhw_atan2_device.argtypes = [PA, ci, vp, u64, i32p, i32p, i32p]
     L.bhw_atan2_to_host.argtypes = [PA, ci, u64, i32p, i32p, i32p]
@@ -483,6 +490,26 @@ def describe_spectrogram(params, length, stft, *, detrend=False, fbank=None, tab
     check(lib().bhw_describe_spectrogram(table, ctypes.byref(params), int(length), ctypes.byref(stft),
                                          WELCH_DETREND_CONSTANT if detrend else 0, ctypes.byref(fbank) if fbank is not None else None,
                                          buf, len(buf)))
+    return buf.value.decode()
+
+
+WELCH_FFT_CHUNK = 16                     # BHW_WELCH_FFT_CHUNK: the frames of one chunk sum of the fused Welch PSD
+
+
+def welch_fft_workspace_bytes(stft):
+    """The bytes of workspace a fused Welch PSD call of the descriptor `stft` (a BhwStft, make_stft, y strides 0) needs: B *
+    ceil(F / 16) * K chunk sums and, for F > 256, B * ceil(F / 256) * K block sums, as doubles (bhw_welch_fft_workspace_bytes)."""
+    return int(lib().bhw_welch_fft_workspace_bytes(ctypes.byref(stft)))
+
+
+def describe_welch_fft(params, length, stft, *, detrend=False, table=None):
+    """One line: the plan fields of describe_stft_fft in the same words, plus the chunk, the runs, the groups per run, the
+    accumulators per lane and the workspace bytes of a fused Welch PSD call over the window of `length` with the descriptor `stft`
+    (a BhwStft, make_stft, y strides 0) (bhw_describe_welch_fft).  `table` is a resident table handle or None for the library
+    call.  Host arithmetic only."""
+    buf = ctypes.create_string_buffer(1280)
+    check(lib().bhw_describe_welch_fft(table, ctypes.byref(params), int(length), ctypes.byref(stft),
+                                       WELCH_DETREND_CONSTANT if detrend else 0, buf, len(buf)))
     return buf.value.decode()
 
 

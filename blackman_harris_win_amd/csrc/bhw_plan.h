@@ -473,6 +473,44 @@ int  bhwp_describe_spectrogram(const bhw_params *p, const BhwCordicCfg *ct, uint
 int  bhwk_spectrogram_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwStftFftPlan &pl, const bhw_stft *s,
                           const bhw_fbank *fb, const float *d_x, float *d_P, const int32_t *d_table, const BhwLenPhase &lp);
 
+// ---- fused Welch PSD (bhw_welch_fft_f32_*; bhw_welch_fft.hip) ----------------------------------------------------------------------------
+// The forward kernel's lanes, LDS, schedule and row steps (fft: bhwp_stft_fft_plan's, with groups and grid recounted) under another
+// ownership: a workgroup owns RUNS.  A run is max(BHW_WELCH_FFT_CHUNK, fy) consecutive frames of one signal on the frame axis padded to
+// fpad = whole runs, so it is a whole number of chunks and never crosses a signal; gpr = max(1, 16 / fy) groups make a run; workgroup
+// w takes the runs w, w + grid, ...; grid = min(runs, kFftMaxGrid).  acc: the binary64 accumulators a lane carries over a run
+// (fy < 16: ceil(K / kFftBlock), at most kWelchFftMaxAcc; fy >= 16: none is carried, a lane sums one (chunk, bin) at a time).
+// Workspace: B * chunks * K chunk sums, then (blocks > 1) B * blocks * K block sums.
+constexpr uint32_t kWelchFftMaxAcc = 9;               // ceil(2049 / 256)
+struct BhwWelchFftPlan {
+    BhwStftFftPlan fft;   // groups = B * fpad / fy, grid = min(runs, kFftMaxGrid); rows = B * frames; the y strides are 0
+    uint64_t bins;        // K = n_fft / 2 + 1
+    uint64_t run;         // frames of a run: max(BHW_WELCH_FFT_CHUNK, fy)
+    uint32_t gpr;         // groups per run: run / fy
+    uint32_t acc;         // accumulators a lane carries (0 for fy >= 16)
+    uint64_t fpad;        // frames of a signal padded to whole runs
+    uint64_t chunks;      // ceil(F / BHW_WELCH_FFT_CHUNK) per signal
+    uint64_t blocks;      // ceil(F / BHW_WELCH_BLOCK) per signal
+    uint64_t runs;        // B * fpad / run
+    uint64_t blocks_grid; // workgroups of the launch that adds the chunks of a block
+    uint64_t join_grid;   // workgroups of the launch that adds the blocks (0 for one block)
+    uint64_t p_stride;    // resolved
+    uint64_t ws_bytes;
+};
+// Every check of the two calls that needs no table handle, before any HIP call (include/bhw.h).  frames 0 passes with the pointers
+// unchecked; `pointers` false: the describe call.
+int  bhwp_welch_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, double scale, uint32_t psd_flags,
+                           uint64_t p_stride, const void *d_x, const void *d_P, const void *workspace, uint64_t workspace_bytes,
+                           bool pointers = true);
+// bhw_welch_fft_workspace_bytes: from batch, frames and n_fft alone (0 for a NULL descriptor, frames 0 or a product beyond 2^60)
+uint64_t bhwp_welch_fft_workspace_bytes(const bhw_stft *s);
+BhwWelchFftPlan bhwp_welch_fft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, uint64_t p_stride,
+                                    bool from_table);
+int  bhwp_describe_welch_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf,
+                             uint64_t len);
+int  bhwk_welch_fft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwWelchFftPlan &pl, const bhw_stft *s,
+                        double scale, uint32_t psd_flags, const float *d_x, float *d_P, double *d_ws, const int32_t *d_table,
+                        const BhwLenPhase &lp);
+
 // ---- mixed-radix fused window and real FFT (bhw_stft_mfft_f32_*; bhw_stft_mfft.hip) -----------------------------------------------------
 // The forward kernel's layout for n_fft = 2^a 3^b 5^c that is even and NOT a power of two, 16 <= n_fft < 4096: M = n_fft / 2 complex
 // points per row, lpf = the smallest power of two >= M / 4 (clamped to 4 .. kFftBlock, so the slot of a lane stays a shift) lanes on a

@@ -1,5 +1,6 @@
 // bhw_stft_fft.h -- the body shared by the kernels that form a windowed row and transform it in LDS: bhw_stft_fft.hip (stores the
-// spectrum row) and bhw_spectrogram.hip (stores its powers, or those folded through a filter bank).  The row function is a template
+// spectrum row), bhw_spectrogram.hip (stores its powers, or those folded through a filter bank) and bhw_welch_fft.hip (adds the
+// powers over the frames of a run: DESIGN.md section 26).  The row function is a template
 // on the epilogue -- what happens to the transformed row -- and everything before it is one text for both units.  Moving the body
 // here left the instruction streams of k_stft_fft_direct<*> and k_stft_fft_table<*> unchanged.
 //
@@ -86,6 +87,33 @@ struct FftStoreSpectrum {
     static constexpr bool kSpectrum = true;
 };
 
+// An epilogue with a member kRuns owns RUNS instead of strided groups of the flat row pool (bhw_welch_fft.hip):
+// the frame axis of every signal is padded to epilogue.fpad frames, a run is epilogue.gpr (a power of two) consecutive groups of one
+// signal, workgroup w takes the runs w, w + grid, ... and a run's groups in ascending order; a row with f >= frames is not live.  It
+// is called once per group by every lane as epilogue(a, M, g, b, f0, base, tw): the group, its signal, the frame of slot 0 and the
+// transformed points of slot 0 (slot s at base + s * M).  Such an epilogue MAY CARRY STATE from group to group: the object handed to
+// stft_fft_rows lives for the whole group loop, one per lane, and is taken by const reference like every epilogue, so what it carries
+// (the sums of a run) stands in `mutable` members; the calls of a run's groups come in ascending order with nothing of another run
+// between them.  Every other epilogue keeps the flat pool, under `if constexpr`, and is stateless.
+template <class E, class = void>
+struct fft_owns_runs : std::false_type {};
+template <class E>
+struct fft_owns_runs<E, std::void_t<decltype(E::kRuns)>> : std::true_type {};
+
+template <class E>
+__device__ __forceinline__ uint64_t fft_first_group(const E &e)
+{
+    if constexpr (fft_owns_runs<E>::value) return (uint64_t)blockIdx.x * e.gpr;
+    else                                   return blockIdx.x;
+}
+
+template <class E>
+__device__ __forceinline__ uint64_t fft_next_group(const E &e, uint64_t g)
+{
+    if constexpr (fft_owns_runs<E>::value) return ((g + 1u) & (e.gpr - 1u)) ? g + 1u : g + 1u + (uint64_t)(gridDim.x - 1u) * e.gpr;
+    else                                   return g + gridDim.x;
+}
+
 // Everything after the prologue's coefficients: vbuf = buffer A viewed as floats holds v[0..n_fft).
 template <class Epilogue>
 __device__ __forceinline__ void stft_fft_rows(const FftIo &a, const Epilogue &epilogue)
@@ -125,10 +153,22 @@ __device__ __forceinline__ void stft_fft_rows(const FftIo &a, const Epilogue &ep
         }
     }
     float *rowA = (float *)bufA + (size_t)slot * n;               // the slot's row as floats = its M complex points
-    for (uint64_t g = blockIdx.x; g < a.groups; g += gridDim.x) {
-        const uint64_t r = g * fy + slot;
-        const bool live = r < a.rows;
-        const uint64_t b = live ? r / a.frames : 0, f = live ? r - b * a.frames : 0;
+    for (uint64_t g = fft_first_group(epilogue); g < a.groups; g = fft_next_group(epilogue, g)) {
+        bool live;
+        uint64_t b, f;
+        [[maybe_unused]] uint64_t f0 = 0;
+        if constexpr (fft_owns_runs<Epilogue>::value) {
+            const uint64_t r0 = g * fy;                                  // fpad is a multiple of fy: a group never crosses a signal
+            b = r0 / epilogue.fpad;
+            f0 = r0 - b * epilogue.fpad;
+            live = f0 + slot < a.frames;
+            f = live ? f0 + slot : 0;
+        } else {
+            const uint64_t r = g * fy + slot;
+            live = r < a.rows;
+            b = live ? r / a.frames : 0;
+            f = live ? r - b * a.frames : 0;
+        }
         const float *xb = a.x + b * a.x_stride;
         const uint64_t t0 = f * a.hop + l - a.pad;                     // the (wrapped) time of column l
         asm volatile("" : "+v"(cols), "+v"(wins));
@@ -241,6 +281,8 @@ __device__ __forceinline__ void stft_fft_rows(const FftIo &a, const Epilogue &ep
                     yp[k] = y;
                 }
             }
+        } else if constexpr (fft_owns_runs<Epilogue>::value) {
+            epilogue(a, M, g, b, f0, src - (size_t)slot * M, tw);
         } else {
             epilogue(a, M, lpf, live, b, f, l, src, tw);
         }

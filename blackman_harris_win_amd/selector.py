@@ -1242,6 +1242,131 @@ def welch(params, x, fs=1.0, *, length, noverlap=None, nfft=None, detrend="const
                   _SUMS_CACHE, fft)
 
 
+# ---- fused Welch PSD: window, FFT and the frame average in one kernel --------------------------------------------------------------------
+
+def _welch_fft_call(torch, params, L, s, flags, xb, nb, K, scale, onesided, out, workspace, dev, table, one_d):
+    """The output and workspace rules of the fused Welch PSD and its launch: P float32 (K,) or (B, K)."""
+    shape = (K,) if one_d else (nb, K)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=xb.device)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != xb.device or tuple(out.shape) != shape \
+            or out.stride(-1) != 1 or (out.dim() == 2 and nb > 1 and out.stride(0) < K):
+        raise ValueError(f"out must be a float32 tensor of shape {shape} on x's device, contiguous along the bins, rows apart")
+    need = B.welch_fft_workspace_bytes(s) // 8
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float64, device=xb.device)
+    else:
+        _check_out(torch, workspace, need, "workspace", torch.float64)
+    tail = (ctypes.byref(s), flags, float(scale), B.PSD_ONESIDED if onesided else 0, ctypes.c_void_p(xb.data_ptr()),
+            ctypes.c_void_p(out.data_ptr()), out.stride(0) if (out.dim() == 2 and nb > 1) else 0, ctypes.c_void_p(workspace.data_ptr()),
+            workspace.numel() * 8)
+    if table is None:
+        B.check(B.lib().bhw_welch_fft_f32_device(ctypes.byref(params), L, dev, _stream_ptr(torch, dev), *tail))
+    else:
+        B.check(B.lib().bhw_welch_fft_f32_from_table(table, ctypes.byref(params), L, _stream_ptr(torch, dev), *tail))
+    return out
+
+
+def _welch_fft_psd(torch, params, x, n_fft, hop, scale, win_length, center, pad_mode, detrend, onesided_doubling, shift, out, workspace,
+                   dev, table):
+    n_fft, L, xb, nb, T, frames, d = _stft_front(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, dev)
+    shift = params.dat_width - 1 if shift is None else int(shift)
+    s = B.make_stft(nb, T, frames, d["hop"], n_fft, col0=d["col0"], pad=d["pad"], pad_mode=d["pad_mode"], shift=shift,
+                    x_stride=xb.stride(0) if nb > 1 else 0)
+    return _welch_fft_call(torch, params, L, s, B.WELCH_DETREND_CONSTANT if detrend else 0, xb, nb, n_fft // 2 + 1, scale,
+                           onesided_doubling, out, workspace, dev, table, x.dim() == 1)
+
+
+def welch_fft(params, x, n_fft, hop, scale, *, win_length=None, center=False, pad_mode="reflect", detrend=False,
+              onesided_doubling=True, shift=None, out=None, workspace=None):
+    """The averaged periodogram of the rows of stft() WITHOUT the spectrum ever reaching memory (bhw_welch_fft_f32_device): x (T,) or
+    (B, T), real float32, framed, windowed and transformed exactly as stft(params, x, n_fft, hop, win_length=..., center=...,
+    pad_mode=..., detrend=...) does -- the (re, im) of every bin are the same words -- and |Y|^2 summed over the frames in the same
+    kernel.  Returns float32 (K,) or (B, K), K = n_fft // 2 + 1: P[b, k] = fl32(A * scale * (2 for the doubled bins under
+    onesided_doubling: every bin but 0 and n_fft / 2)), A the binary64 sum of re^2 + im^2 in the fixed order of include/bhw.h:
+    ascending frames inside chunks of 16, the chunks of a block of 256 frames in order, then the blocks in order.  So P does not
+    depend on B or the plan; for F <= 16 frames it is welch_psd(stft(...), scale, nfft=n_fft) bit for bit, for more frames within one
+    float32 ulp of it.  center=True averages a centred (reflect- or zero-padded) spectrogram over time.  n_fft: a power of two in
+    16..4096 (ValueError otherwise; complex x too).  `out`: float32 of the returned shape, bins contiguous, rows apart (its gaps are
+    left alone); `workspace`: float64, B.welch_fft_workspace_bytes(...) // 8 elements (allocated when not given).  With both given
+    the call neither allocates nor synchronises and can be captured with no warm call."""
+    torch = _torch()
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise ValueError("x must be a float32 CUDA tensor")
+    return _welch_fft_psd(torch, params, x, n_fft, hop, scale, win_length, center, pad_mode, detrend, onesided_doubling, shift, out,
+                          workspace, x.device.index, None)
+
+
+def _welch_fused(torch, params, x, fs, length, noverlap, nfft, detrend, scaling, shift, out, workspace, dev, table, cache):
+    if detrend not in ("constant", False, None):
+        raise ValueError(f"detrend must be 'constant' or False, got {detrend!r}")
+    if scaling not in ("density", "spectrum"):
+        raise ValueError(f"scaling must be 'density' or 'spectrum', got {scaling!r}")
+    L = int(length)
+    noverlap = L // 2 if noverlap is None else int(noverlap)
+    if not 0 <= noverlap < L:
+        raise ValueError("noverlap must be less than length")
+    nfft = L if nfft is None else int(nfft)
+    hop = L - noverlap
+    _fft_input(torch, x, nfft, dev)
+    if not 1 <= L <= 1 << params.phi_width:
+        raise ValueError(f"length {L} outside 1..2^phi_width = {1 << params.phi_width}")
+    if nfft < L:
+        raise ValueError(f"nfft {nfft} must be at least the window length {L}")
+    xb = x if x.dim() == 2 else x.unsqueeze(0)
+    nb, T = xb.shape
+    if nb < 1 or T < L:
+        raise ValueError(f"zero segments: T = {T} < length = {L}" if nb else "zero signals")
+    frames = 1 + (T - L) // hop
+    xb = _stft_input(xb, (T,))
+    sums = _window_sums(torch, params, L, True, shift, dev, table, cache)
+    scale = B.welch_scale(sums, frames, fs, scaling)
+    sh = params.dat_width - 1 if shift is None else int(shift)
+    s = B.make_stft(nb, T, frames, hop, nfft, shift=sh, x_stride=xb.stride(0) if nb > 1 else 0)
+    freqs = _freq_axis(torch, cache, nfft, fs, dev)                  # before the launch: it refuses inside a capture when missing
+    P = _welch_fft_call(torch, params, L, s, B.WELCH_DETREND_CONSTANT if detrend == "constant" else 0, xb, nb, nfft // 2 + 1, scale,
+                        True, out, workspace, dev, table, x.dim() == 1)
+    return freqs, P
+
+
+_FREQS_KEPT = 8         # frequency axes a sums cache keeps (the oldest goes first)
+
+
+def _freq_axis(torch, cache, nfft, fs, dev):
+    """The float64 frequency axis welch_fused returns, built once per (nfft, fs) and kept beside the window sums in `cache` (the
+    library's, or the table's own), so that a warm call allocates nothing.  Like the sums it is never made inside a capture: a tensor
+    allocated there belongs to the graph's pool and holds nothing until the graph is replayed."""
+    key = ("freqs", int(nfft), float(fs), int(dev))
+    hit = cache.get(key)
+    if hit is not None:
+        return hit
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("the frequency axis of this (nfft, fs) has not been built yet: call once outside the capture")
+    kept = [k for k in cache if isinstance(k, tuple) and k and k[0] == "freqs"]
+    for k in kept[:max(0, len(kept) - _FREQS_KEPT + 1)]:
+        del cache[k]
+    axis = cache[key] = torch.fft.rfftfreq(int(nfft), d=1.0 / float(fs), dtype=torch.float64, device=f"cuda:{dev}")
+    return axis
+
+
+def welch_fused(params, x, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", scaling="density", shift=None, out=None,
+                workspace=None):
+    """welch(..., fft="fused") in ONE kernel and a small join (bhw_welch_fft_f32_device): the segments, their FFT and the average
+    over them come from the same kernel, so the (B, F, K) spectrum that route writes and reads back never exists.  The arguments,
+    their checks, the window sums (read once per (params, length, shift) and cached) and the scale are welch()'s for fft="fused";
+    the result is the one-sided estimate (freqs float64, Pxx float32 (..., K)) -- the two-sided one is welch(return_onesided=False),
+    and only the mean is averaged.  The sum over the frames has the order of welch_fft(), so Pxx equals welch(fft="fused") bit for
+    bit up to 16 segments and within one float32 ulp beyond.  After one warm call, with `out` and `workspace` given, it neither
+    synchronises nor allocates and can be captured (ResidentTable.welch_fused); a first call inside a capture -- the first for its
+    window sums, or for its (nfft, fs) -- raises, as welch does.  `freqs` is SHARED and read-only: the same tensor is returned to
+    every call with that (nfft, fs) (welch builds a new one each time), so copy it before changing it in place."""
+    torch = _torch()
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise ValueError("x must be a float32 CUDA tensor")
+    return _welch_fused(torch, params, x, fs, length, noverlap, nfft, detrend, scaling, shift, out, workspace, x.device.index, None,
+                        _SUMS_CACHE)
+
+
 # ---- Welch cross spectra: the pass behind the FFT for two signals -------------------------------------------------------------------------
 
 def _csd_operand(torch, t, what, dev):
@@ -1657,6 +1782,20 @@ class ResidentTable:
         one call the whole chain can be captured into a graph."""
         return _welch(_torch(), params, x, fs, length, noverlap, nfft, detrend, return_onesided, scaling, shift, average, self.device,
                       self._live(), self._sums, fft)
+
+    def welch_fft(self, params, x, n_fft, hop, scale, *, win_length=None, center=False, pad_mode="reflect", detrend=False,
+                  onesided_doubling=True, shift=None, out=None, workspace=None):
+        """welch_fft() with the coefficients gathered from this table (bhw_welch_fft_f32_from_table): no allocation by the library,
+        no synchronisation, capturable on its first call; the bits are those of the library form."""
+        return _welch_fft_psd(_torch(), params, x, n_fft, hop, scale, win_length, center, pad_mode, detrend, onesided_doubling, shift,
+                              out, workspace, self.device, self._live())
+
+    def welch_fused(self, params, x, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", scaling="density", shift=None,
+                    out=None, workspace=None):
+        """welch_fused() from this table.  The sums cache and the capture rule are welch()'s: after one warm call the call can be
+        captured into a graph, a first call inside a capture raises."""
+        return _welch_fused(_torch(), params, x, fs, length, noverlap, nfft, detrend, scaling, shift, out, workspace, self.device,
+                            self._live(), self._sums)
 
     def cross_spectra(self, params, x, y, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", return_onesided=True,
                       scaling="density", shift=None, outputs=("pxy", "pxx", "pyy", "coherence", "h1"), fft="torch"):

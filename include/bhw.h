@@ -787,7 +787,8 @@ int bhw_describe_istft_fft(bhw_table t, const bhw_params *p, uint64_t length, co
  *   - Capture: as bhw_stft_fft_f32_*.  The library form makes no allocation, uses no scratch and is capturable with no
  *     bhw_prepare_device; the from-table form is capturable on its first call.
  *   - Not built: magnitude (power 1); log (the caller applies it to the small result); a complex output next to the power;
- *     accumulating over frames in the kernel (Welch); complex input (bhw_stft_cfft_f32_* with BHW_CFFT_POWER is its power form).
+ *     accumulating over frames in the kernel (Welch: bhw_welch_fft_f32_* is that call); complex input (bhw_stft_cfft_f32_* with
+ *     BHW_CFFT_POWER is its power form).
  *     Other n_fft: bhw_stft_mfft_f32_* with BHW_MFFT_POWER writes these rows for an even n_fft = 2^a 3^b 5^c that is no power of two.
  *   - bhw_describe_spectrogram: the plan fields of bhw_describe_stft_fft's line in the same words, plus the mode, W, and for a bank
  *     filters, weights and filters per lane.  t may be NULL (the library call).  Host arithmetic only. */
@@ -1015,6 +1016,58 @@ int bhw_istft_cfft_f32_device(const bhw_params *p, uint64_t length, int device, 
 int bhw_istft_cfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
                                   const float *d_Y, float *d_x);
 int bhw_describe_istft_cfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf, uint64_t len);
+
+/* Fused Welch PSD: window, real FFT and the average over the frames by ONE kernel and a small join.  The rows of bhw_stft_fft_f32_*
+ * are formed and transformed by the same kernel body, and |Y|^2 is accumulated over the frames where the transform ends, so the
+ * (B, F, K) spectrum that bhw_stft_fft_f32_* + bhw_welch_psd_f32 write and read back never exists.
+ *   - Inputs: (p, length, s, flags) exactly as bhw_stft_fft_f32_* takes them (flags 0 or BHW_WELCH_DETREND_CONSTANT; the padding
+ *     fields of s as that call accepts them, so the time average of a centred spectrogram comes free), except that s->y_stride and
+ *     s->y_batch_stride must be 0: no spectrum is written.  scale and psd_flags (0 or BHW_PSD_ONESIDED) are bhw_psd's; d_P is float32
+ *     (B, K), K = n_fft / 2 + 1, row b at b * p_stride floats (0 = K).
+ *   - Row and transform: those of bhw_stft_fft_f32_* for the same (p, length, s, flags).  Let (re, im) be the float32 pair that call
+ *     writes for bin k of row (b, f): the same words, from the same row function and the same split expression.
+ *   - The sums, with q_f = (double) re * (double) re + (double) im * (double) im (both squares exact, one rounding: the q_f of
+ *     bhw_welch_psd_f32):
+ *        A_chunk = sum of q_f over the frames of one chunk, in ascending f, binary64 from +0.0
+ *        A_blk   = sum of A_chunk over the chunks of one block, ascending, binary64 from +0.0
+ *        A       = sum of A_blk over the blocks, ascending, binary64 from +0.0
+ *        d_P[b * p_stride + k] = fl32(A * s_k),    s_k = scale * (doubled(k) ? 2 : 1)      (doubled: bhw_welch_psd_f32's rule)
+ *     A chunk is BHW_WELCH_FFT_CHUNK = 16 consecutive frames (the last may be shorter), a block BHW_WELCH_BLOCK = 256 frames = 16
+ *     chunks.  Both constants belong to this header and not to a plan: they ARE the order.
+ *   - Consequences: the bits of P depend on the window, n_fft, the flags, scale and the signal's samples only -- not on B, the grid,
+ *     or library versus table.  For F <= 16 the order is bhw_welch_psd_f32's plain ascending sum, so P equals bhw_welch_psd_f32 of
+ *     bhw_stft_fft_f32_*'s rows bit for bit.  For larger F the two orders associate differently and P may differ from that route by
+ *     at most one float32 ulp: both are roundings of binary64 sums of non-negative terms whose relative difference is below
+ *     2 F * 2^-53.
+ *   - Workspace: caller-provided, 8-byte aligned, bhw_welch_fft_workspace_bytes(s) bytes: the chunk sums, B * ceil(F / 16) * K
+ *     doubles, followed, when F > 256, by the block sums, B * ceil(F / 256) * K doubles.  A short one is BHW_ERR_WORKSPACE.  No call
+ *     allocates, and there are no float atomics: every chunk sum is stored plainly once and two small kernels join them in order.
+ *   - Supported: exactly the set of bhw_stft_fft_f32_* (real input, channels 1, n_fft a power of two in 16..4096) with the same codes
+ *     and words for refusals.
+ *   - IEEE: a NaN or an infinity in x reaches only the bins of its own signal.  Zeros in give +0.0 out (for a scale >= 0).
+ *   - Checks before any HIP call, in this order (BHW_ERR_BADARG unless noted): everything bhw_stft_fft_f32_* checks on the descriptor
+ *     (with the y strides taken as packed), non-zero y strides, unknown psd_flags, a scale that is not finite; frames 0 returns BHW_OK
+ *     here with the pointers unchecked; p_stride below K, B * ceil(F / 16) * K above 2^34; NULL d_x or d_P, either not 4-byte aligned,
+ *     a NULL or misaligned workspace, a short one (BHW_ERR_WORKSPACE), d_P or the workspace overlapping d_x or each other; and (from a
+ *     table) the key match.
+ *   - Capture: as bhw_stft_fft_f32_*.  The library form needs no bhw_prepare_device; the from-table form is capturable on its first
+ *     call.
+ *   - Not built: cross spectra accumulated in the kernel; the mixed-radix and I/Q kernels with this epilogue; max-hold or median
+ *     averaging; a filter bank on the averaged powers.
+ *   - bhw_describe_welch_fft: bhw_describe_stft_fft's line in the same words, plus the chunk, the runs, the groups per run, the
+ *     accumulators per lane and the workspace bytes.  t may be NULL (the library call).  Host arithmetic only. */
+/* Why 16: the frames of ONE signal are the only parallelism a long record has.  16 381 frames of one signal (2^24 samples, n_fft 4096,
+ * hop 1024) are 1 024 independent chunk chains; chains of BHW_WELCH_BLOCK frames would be 64 on 256 compute units.  16 is also the
+ * largest run that needs no carried sum for n_fft <= 128, where a workgroup holds 16 or more frames side by side. */
+#define BHW_WELCH_FFT_CHUNK 16u
+uint64_t bhw_welch_fft_workspace_bytes(const bhw_stft *s);
+int bhw_welch_fft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                             double scale, uint32_t psd_flags, const float *d_x, float *d_P, uint64_t p_stride, void *workspace,
+                             uint64_t workspace_bytes);
+int bhw_welch_fft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                 double scale, uint32_t psd_flags, const float *d_x, float *d_P, uint64_t p_stride, void *workspace,
+                                 uint64_t workspace_bytes);
+int bhw_describe_welch_fft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf, uint64_t len);
 
 /* Threading: every entry point may be called from any host thread.  Calls that use the library-owned scratch of one
  * (device, stream) are serialised against each other for the duration of their launches (the table is rebuilt per call);
