@@ -52,6 +52,7 @@ ABI_SYMBOLS = (
     "bhw_stft_cfft_f32_device", "bhw_stft_cfft_f32_from_table", "bhw_describe_stft_cfft",
     "bhw_istft_cfft_f32_device", "bhw_istft_cfft_f32_from_table", "bhw_describe_istft_cfft",
     "bhw_welch_fft_workspace_bytes", "bhw_welch_fft_f32_device", "bhw_welch_fft_f32_from_table", "bhw_describe_welch_fft",
+    "bhw_welch_cfft_workspace_bytes", "bhw_welch_cfft_f32_device", "bhw_welch_cfft_f32_from_table", "bhw_describe_welch_cfft",
 )
 
 
@@ -339,6 +340,11 @@ def lib():
     L.bhw_welch_fft_f32_device.argtypes = [P, u64, ci, vp, S, u32, f64, u32, f32p, f32p, u64, vp, u64]
     L.bhw_welch_fft_f32_from_table.argtypes = [T, P, u64, vp, S, u32, f64, u32, f32p, f32p, u64, vp, u64]
     L.bhw_describe_welch_fft.argtypes = [T, P, u64, S, u32, ctypes.c_char_p, u64]
+    L.bhw_welch_cfft_workspace_bytes.restype = u64
+    L.bhw_welch_cfft_workspace_bytes.argtypes = [S]
+    L.bhw_welch_cfft_f32_device.argtypes = [P, u64, ci, vp, S, u32, f64, f32p, f32p, u64, vp, u64]
+    L.bhw_welch_cfft_f32_from_table.argtypes = [T, P, u64, vp, S, u32, f64, f32p, f32p, u64, vp, u64]
+    L.bhw_describe_welch_cfft.argtypes = [T, P, u64, S, u32, ctypes.c_char_p, u64]
     PA = ctypes.POINTER(BhwAtan2Params)
     L.bhw_atan2_device.argtypes = [PA, ci, vp, u64, i32p, i32p, i32p]
     L.bhw_atan2_to_host.argtypes = [PA, ci, u64, i32p, i32p, i32p]
@@ -582,6 +588,24 @@ def describe_istft_cfft(params, length, stft, *, normalize=False, fftshift=False
     buf = ctypes.create_string_buffer(1024)
     flags = (OLA_NORMALIZE if normalize else 0) | (CFFT_SHIFT if fftshift else 0)
     check(lib().bhw_describe_istft_cfft(table, ctypes.byref(params), int(length), ctypes.byref(stft), flags, buf, len(buf)))
+    return buf.value.decode()
+
+
+def welch_cfft_workspace_bytes(stft):
+    """The bytes of workspace a fused Welch PSD call for I/Q input of the descriptor `stft` (a BhwStft with channels 2, y strides 0)
+    needs: B * ceil(F / 16) * n_fft chunk sums and, for F > 256, B * ceil(F / 256) * n_fft block sums, as doubles
+    (bhw_welch_cfft_workspace_bytes)."""
+    return int(lib().bhw_welch_cfft_workspace_bytes(ctypes.byref(stft)))
+
+
+def describe_welch_cfft(params, length, stft, *, detrend=False, fftshift=False, table=None):
+    """One line: the plan fields of describe_stft_cfft in the same words (without the output form), plus the chunk, the runs, the
+    groups per run, the accumulators per lane and the workspace bytes of a fused Welch PSD call for I/Q input over the window of
+    `length` with the descriptor `stft` (a BhwStft with channels 2, y strides 0) (bhw_describe_welch_cfft).  `table` is a resident
+    table handle or None for the library call.  Host arithmetic only."""
+    buf = ctypes.create_string_buffer(1280)
+    flags = (WELCH_DETREND_CONSTANT if detrend else 0) | (CFFT_SHIFT if fftshift else 0)
+    check(lib().bhw_describe_welch_cfft(table, ctypes.byref(params), int(length), ctypes.byref(stft), flags, buf, len(buf)))
     return buf.value.decode()
 
 

@@ -1725,13 +1725,29 @@ int bhwp_describe_spectrogram(const bhw_params *p, const BhwCordicCfg *ct, uint6
 
 // ---- fused Welch PSD ------------------------------------------------------------------------------------------------------------------------
 
+BhwWelchRuns bhwp_welch_runs(uint64_t batch, uint64_t F, uint32_t fy, uint64_t bins)
+{
+    BhwWelchRuns r{};
+    r.run = fy > BHW_WELCH_FFT_CHUNK ? fy : BHW_WELCH_FFT_CHUNK;
+    r.gpr = (uint32_t)(r.run / fy);
+    if (!F || !batch) return r;
+    r.fpad = ((F - 1) / r.run + 1) * r.run;
+    r.chunks = (F - 1) / BHW_WELCH_FFT_CHUNK + 1;
+    r.blocks = (F - 1) / BHW_WELCH_BLOCK + 1;
+    r.runs = batch * (r.fpad / r.run);
+    r.groups = r.runs * r.gpr;
+    r.grid = r.runs < kFftMaxGrid ? r.runs : kFftMaxGrid;
+    r.blocks_grid = (batch * r.blocks * bins + 255u) / 256u;
+    r.join_grid = r.blocks > 1 ? (batch * bins + 255u) / 256u : 0;
+    const unsigned __int128 n = (unsigned __int128)batch * (r.chunks + (r.blocks > 1 ? r.blocks : 0)) * bins;
+    r.ws_bytes = n > (1ull << 57) ? 0 : (uint64_t)n * 8u;
+    return r;
+}
+
 uint64_t bhwp_welch_fft_workspace_bytes(const bhw_stft *s)
 {
     if (!s || !s->frames || !s->batch) return 0;
-    const uint64_t K = s->n_fft / 2 + 1, F = s->frames;
-    const uint64_t chunks = (F - 1) / BHW_WELCH_FFT_CHUNK + 1, blocks = (F - 1) / BHW_WELCH_BLOCK + 1;
-    const unsigned __int128 n = (unsigned __int128)s->batch * (chunks + (blocks > 1 ? blocks : 0)) * K;
-    return n > (1ull << 57) ? 0 : (uint64_t)n * 8u;
+    return bhwp_welch_runs(s->batch, s->frames, 1, s->n_fft / 2 + 1).ws_bytes;        // the bytes do not depend on fy
 }
 
 int bhwp_welch_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, double scale, uint32_t psd_flags,
@@ -1790,25 +1806,21 @@ BhwWelchFftPlan bhwp_welch_fft_plan(const bhw_params *p, uint64_t length, const 
     t.y_stride = t.y_batch_stride = 0;
     pl.fft = bhwp_stft_fft_plan(p, length, &t, flags, from_table);
     pl.fft.y_stride = pl.fft.y_bstride = 0;
-    const uint64_t F = s->frames, fy = pl.fft.fy;
     pl.bins = s->n_fft / 2 + 1;
-    pl.run = fy > BHW_WELCH_FFT_CHUNK ? fy : BHW_WELCH_FFT_CHUNK;
-    pl.gpr = (uint32_t)(pl.run / fy);
-    pl.acc = fy >= BHW_WELCH_FFT_CHUNK ? 0u : (uint32_t)((pl.bins + kFftBlock - 1) / kFftBlock);
+    const BhwWelchRuns r = bhwp_welch_runs(s->batch, s->frames, pl.fft.fy, pl.bins);
+    pl.run = r.run;
+    pl.gpr = r.gpr;
+    pl.acc = pl.fft.fy >= BHW_WELCH_FFT_CHUNK ? 0u : (uint32_t)((pl.bins + kFftBlock - 1) / kFftBlock);
     pl.p_stride = p_stride ? p_stride : pl.bins;
-    if (!F) {
-        pl.fft.groups = pl.fft.grid = 0;
-        return pl;
-    }
-    pl.fpad = ((F - 1) / pl.run + 1) * pl.run;
-    pl.chunks = (F - 1) / BHW_WELCH_FFT_CHUNK + 1;
-    pl.blocks = (F - 1) / BHW_WELCH_BLOCK + 1;
-    pl.runs = s->batch * (pl.fpad / pl.run);
-    pl.fft.groups = pl.runs * pl.gpr;
-    pl.fft.grid = pl.runs < kFftMaxGrid ? pl.runs : kFftMaxGrid;
-    pl.blocks_grid = (s->batch * pl.blocks * pl.bins + 255u) / 256u;
-    pl.join_grid = pl.blocks > 1 ? (s->batch * pl.bins + 255u) / 256u : 0;
-    pl.ws_bytes = bhwp_welch_fft_workspace_bytes(s);
+    pl.fpad = r.fpad;
+    pl.chunks = r.chunks;
+    pl.blocks = r.blocks;
+    pl.runs = r.runs;
+    pl.fft.groups = r.groups;
+    pl.fft.grid = r.grid;
+    pl.blocks_grid = r.blocks_grid;
+    pl.join_grid = r.join_grid;
+    pl.ws_bytes = r.ws_bytes;
     return pl;
 }
 
@@ -2119,6 +2131,126 @@ int bhwp_describe_stft_cfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_
              (unsigned long long)s->col0, (unsigned long long)s->pad, pad, det, form, bins, kern, (unsigned long long)s->batch,
              (unsigned long long)s->frames, (unsigned long long)pl.rows, pl.n, sched, pl.lpf, pl.fy, pl.cpl, (unsigned long long)pl.groups,
              (unsigned long long)pl.grid, kFftBlock, pl.lds_bytes);
+    return BHW_OK;
+}
+
+// ---- fused Welch PSD for I/Q input --------------------------------------------------------------------------------------------------------------
+
+uint64_t bhwp_welch_cfft_workspace_bytes(const bhw_stft *s)
+{
+    if (!s || !s->frames || !s->batch) return 0;
+    return bhwp_welch_runs(s->batch, s->frames, 1, s->n_fft).ws_bytes;                // the bytes do not depend on fy
+}
+
+int bhwp_welch_cfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, double scale, uint64_t p_stride,
+                           const void *d_x, const void *d_P, const void *workspace, uint64_t workspace_bytes, bool pointers)
+{
+    // 1. the input side: the forward call's checks for the descriptor with packed output strides (no spectrum is written here)
+    bhw_stft t{};
+    const bool sized = s && s->struct_size == sizeof(bhw_stft);
+    if (sized) {
+        t = *s;
+        t.y_stride = t.y_batch_stride = 0;
+    }
+    int rc = bhwp_stft_cfft_checks(p, length, sized ? &t : s, flags, nullptr, nullptr, false);
+    if (rc) return rc;
+    // 2.
+    if (flags & BHW_CFFT_POWER)
+        return bhwp_fail(BHW_ERR_BADARG, "flags 0x%x: BHW_CFFT_POWER has no meaning here (BHW_WELCH_DETREND_CONSTANT, BHW_CFFT_SHIFT)", flags);
+    if (s->y_stride || s->y_batch_stride)
+        return bhwp_fail(BHW_ERR_BADARG, "y_stride %llu, y_batch_stride %llu: no spectrum is written, both must be 0",
+                         (unsigned long long)s->y_stride, (unsigned long long)s->y_batch_stride);
+    if (!(scale - scale == 0.0)) return bhwp_fail(BHW_ERR_BADARG, "scale is not finite");
+    // 3., 4.
+    const uint64_t T = s->samples, F = s->frames, N = s->n_fft;
+    if (!F) return BHW_OK;
+    if (p_stride && p_stride < N)
+        return bhwp_fail(BHW_ERR_BADARG, "p_stride %llu < n_fft %llu: rows overlap", (unsigned long long)p_stride, (unsigned long long)N);
+    const uint64_t chunks = (F - 1) / BHW_WELCH_FFT_CHUNK + 1;
+    if ((unsigned __int128)s->batch * chunks * N > (1ull << 34))
+        return bhwp_fail(BHW_ERR_BADARG, "batch * ceil(frames / %u) * n_fft above 2^34 per call", BHW_WELCH_FFT_CHUNK);
+    if (!pointers) return BHW_OK;
+    // 5., 6.
+    if (!d_x || !d_P) return bhwp_fail(BHW_ERR_BADARG, "d_x / d_P is NULL");
+    if ((uintptr_t)d_P % 4) return bhwp_fail(BHW_ERR_BADARG, "d_P is not 4-byte aligned");
+    if ((uintptr_t)d_x % 4) return bhwp_fail(BHW_ERR_BADARG, "d_x is not 4-byte aligned");
+    const uint64_t need = bhwp_welch_cfft_workspace_bytes(s);
+    if (!workspace) return bhwp_fail(BHW_ERR_BADARG, "workspace is NULL: the chunk sums need %llu bytes", (unsigned long long)need);
+    if ((uintptr_t)workspace % 8) return bhwp_fail(BHW_ERR_BADARG, "workspace is not 8-byte aligned");
+    if (workspace_bytes < need)
+        return bhwp_fail(BHW_ERR_WORKSPACE, "workspace of %llu bytes, the chunk and block sums need %llu", (unsigned long long)workspace_bytes,
+                         (unsigned long long)need);
+    // 7. (x counts floats: 2 T of a signal)
+    const uint64_t xs = s->x_stride ? s->x_stride : 2 * T, ps = p_stride ? p_stride : N;
+    const unsigned __int128 xe = (unsigned __int128)(s->batch - 1) * xs + 2 * T, pe = (unsigned __int128)(s->batch - 1) * ps + N;
+    if (xe > (1ull << 60) || pe > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "x or P extent beyond 2^60 elements");
+    const uint64_t xa = (uint64_t)(uintptr_t)d_x, pa = (uint64_t)(uintptr_t)d_P, wa = (uint64_t)(uintptr_t)workspace;
+    const uint64_t xb = (uint64_t)xe * 4u, pb = (uint64_t)pe * 4u;
+    if (xa > UINT64_MAX - xb || pa > UINT64_MAX - pb || wa > UINT64_MAX - need)
+        return bhwp_fail(BHW_ERR_BADARG, "x, P or workspace range wraps the address space");
+    if (xa < pa + pb && pa < xa + xb) return bhwp_fail(BHW_ERR_BADARG, "d_x and d_P overlap");
+    if ((wa < xa + xb && xa < wa + need) || (wa < pa + pb && pa < wa + need))
+        return bhwp_fail(BHW_ERR_BADARG, "workspace overlaps d_x or d_P");
+    return BHW_OK;
+}
+
+BhwWelchCfftPlan bhwp_welch_cfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, uint64_t p_stride,
+                                      bool from_table)
+{
+    BhwWelchCfftPlan pl{};
+    bhw_stft t = *s;
+    t.y_stride = t.y_batch_stride = 0;
+    pl.fft = bhwp_stft_cfft_plan(p, length, &t, flags & kWelchCfftFlags, from_table);
+    pl.fft.y_stride = pl.fft.y_bstride = 0;
+    pl.bins = s->n_fft;
+    const BhwWelchRuns r = bhwp_welch_runs(s->batch, s->frames, pl.fft.fy, pl.bins);
+    pl.run = r.run;
+    pl.gpr = r.gpr;
+    pl.acc = pl.fft.fy >= BHW_WELCH_FFT_CHUNK ? 0u : (uint32_t)((pl.bins + kFftBlock - 1) / kFftBlock);
+    pl.p_stride = p_stride ? p_stride : pl.bins;
+    pl.fpad = r.fpad;
+    pl.chunks = r.chunks;
+    pl.blocks = r.blocks;
+    pl.runs = r.runs;
+    pl.fft.groups = r.groups;
+    pl.fft.grid = r.grid;
+    pl.blocks_grid = r.blocks_grid;
+    pl.join_grid = r.join_grid;
+    pl.ws_bytes = r.ws_bytes;
+    return pl;
+}
+
+int bhwp_describe_welch_cfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf,
+                             uint64_t len)
+{
+    if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
+    const char *route = ct ? "table" : "direct";
+    const BhwWelchCfftPlan wp = bhwp_welch_cfft_plan(p, length, s, flags, 0, ct != nullptr);
+    const BhwStftCfftPlan &pl = wp.fft;
+    const char *pad = s->pad_mode == BHW_PAD_REFLECT ? "reflect" : "constant";
+    const char *det = pl.detrend ? "constant detrend" : "no detrending";
+    const char *bins = pl.shifted ? "bins shifted" : "bins in order";
+    if (!s->frames) {
+        snprintf(buf, len, "welch cfft %s (L = %llu, n_fft %llu, %s), %s: nothing (frames 0)", route, (unsigned long long)length,
+                 (unsigned long long)s->n_fft, det, bins);
+        return BHW_OK;
+    }
+    char kern[64], sched[48];
+    kernel_name(p, ct, "k_welch_cfft_direct", "k_welch_cfft_table", false, kern, sizeof kern);
+    BhwStftFftPlan f{};
+    f.radix4 = pl.radix4;
+    f.radix2 = pl.radix2;
+    bhwp_stft_fft_schedule(f, sched, sizeof sched);
+    snprintf(buf, len, "welch cfft %s (L = %llu, n_fft %llu, col0 %llu, pad %llu %s, %s), %s: %s, %llu signals x %llu frames = %llu rows, "
+             "complex FFT of %u points in passes %s (no split), %u lanes per row x %u rows per workgroup, %u columns per lane, %llu groups, "
+             "grid %llu x %u lanes, %u bytes of LDS; chunk %u frames, %llu runs of %llu frames (%u group%s per run), %u accumulator%s "
+             "per lane, %llu chunks and %llu block%s per signal, then k_welch_fft_join %s, workspace %llu bytes",
+             route, (unsigned long long)length, (unsigned long long)s->n_fft, (unsigned long long)s->col0, (unsigned long long)s->pad, pad,
+             det, bins, kern, (unsigned long long)s->batch, (unsigned long long)s->frames, (unsigned long long)pl.rows, pl.n, sched, pl.lpf,
+             pl.fy, pl.cpl, (unsigned long long)pl.groups, (unsigned long long)pl.grid, kFftBlock, pl.lds_bytes, BHW_WELCH_FFT_CHUNK,
+             (unsigned long long)wp.runs, (unsigned long long)wp.run, wp.gpr, wp.gpr == 1 ? "" : "s", wp.acc, wp.acc == 1 ? "" : "s",
+             (unsigned long long)wp.chunks, (unsigned long long)wp.blocks, wp.blocks == 1 ? "" : "s",
+             wp.blocks == 1 ? "once (chunks)" : "twice (chunks, blocks)", (unsigned long long)wp.ws_bytes);
     return BHW_OK;
 }
 

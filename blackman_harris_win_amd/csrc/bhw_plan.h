@@ -481,6 +481,22 @@ int  bhwk_spectrogram_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWi
 // (fy < 16: ceil(K / kFftBlock), at most kWelchFftMaxAcc; fy >= 16: none is carried, a lane sums one (chunk, bin) at a time).
 // Workspace: B * chunks * K chunk sums, then (blocks > 1) B * blocks * K block sums.
 constexpr uint32_t kWelchFftMaxAcc = 9;               // ceil(2049 / 256)
+// The run arithmetic of both fused Welch plans (real and I/Q input), from the batch, the frames, the rows side by side and the bins
+// of an output row: one text for bhwp_welch_fft_plan and bhwp_welch_cfft_plan.  frames 0: everything but run and gpr is 0.
+struct BhwWelchRuns {
+    uint64_t run;         // frames of a run: max(BHW_WELCH_FFT_CHUNK, fy)
+    uint32_t gpr;         // groups per run: run / fy
+    uint64_t fpad;        // frames of a signal padded to whole runs
+    uint64_t chunks;      // ceil(F / BHW_WELCH_FFT_CHUNK) per signal
+    uint64_t blocks;      // ceil(F / BHW_WELCH_BLOCK) per signal
+    uint64_t runs;        // B * fpad / run
+    uint64_t groups;      // runs * gpr = B * fpad / fy
+    uint64_t grid;        // min(runs, kFftMaxGrid)
+    uint64_t blocks_grid; // workgroups of the launch that adds the chunks of a block
+    uint64_t join_grid;   // workgroups of the launch that adds the blocks (0 for one block)
+    uint64_t ws_bytes;    // 8 * B * bins * (chunks + (blocks > 1 ? blocks : 0)); 0 beyond 2^60
+};
+BhwWelchRuns bhwp_welch_runs(uint64_t batch, uint64_t frames, uint32_t fy, uint64_t bins);
 struct BhwWelchFftPlan {
     BhwStftFftPlan fft;   // groups = B * fpad / fy, grid = min(runs, kFftMaxGrid); rows = B * frames; the y strides are 0
     uint64_t bins;        // K = n_fft / 2 + 1
@@ -589,6 +605,36 @@ int  bhwp_describe_stft_cfft(const bhw_params *p, const BhwCordicCfg *ct, uint64
                              uint64_t len);
 int  bhwk_stft_cfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwStftCfftPlan &pl, const bhw_stft *s,
                         const float *d_x, float *d_Y, const int32_t *d_table, const BhwLenPhase &lp);
+
+// ---- fused Welch PSD for I/Q input (bhw_welch_cfft_f32_*; bhw_welch_cfft.hip) ---------------------------------------------------------------
+// BhwWelchCfftPlan wraps BhwStftCfftPlan as BhwWelchFftPlan wraps BhwStftFftPlan: the lanes, LDS, schedule and row steps are
+// bhwp_stft_cfft_plan's field for field (fft, with groups and grid recounted), the ownership is bhwp_welch_runs' with bins = n_fft.
+// acc: the binary64 accumulators a lane carries over a run (fy < 16: ceil(n_fft / kFftBlock), at most kWelchCfftMaxAcc; fy >= 16:
+// none).  Workspace: B * chunks * n_fft chunk sums, then (blocks > 1) B * blocks * n_fft block sums.
+constexpr uint32_t kWelchCfftMaxAcc = 8;              // 2048 / 256
+constexpr uint32_t kWelchCfftFlags = BHW_WELCH_DETREND_CONSTANT | BHW_CFFT_SHIFT;
+struct BhwWelchCfftPlan {
+    BhwStftCfftPlan fft;  // groups = B * fpad / fy, grid = min(runs, kFftMaxGrid); rows = B * frames; the y strides are 0; power false
+    uint64_t bins;        // n_fft: the estimate is two-sided
+    uint64_t run;
+    uint32_t gpr;
+    uint32_t acc;         // accumulators a lane carries (0 for fy >= 16)
+    uint64_t fpad, chunks, blocks, runs, blocks_grid, join_grid;   // bhwp_welch_runs'
+    uint64_t p_stride;    // resolved
+    uint64_t ws_bytes;
+};
+// Every check of the two calls that needs no table handle, before any HIP call and in the order of include/bhw.h.  frames 0 passes
+// with the pointers unchecked; `pointers` false: the describe call.
+int  bhwp_welch_cfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, double scale, uint64_t p_stride,
+                            const void *d_x, const void *d_P, const void *workspace, uint64_t workspace_bytes, bool pointers = true);
+// bhw_welch_cfft_workspace_bytes: from batch, frames and n_fft alone (0 for a NULL descriptor, frames 0 or a product beyond 2^60)
+uint64_t bhwp_welch_cfft_workspace_bytes(const bhw_stft *s);
+BhwWelchCfftPlan bhwp_welch_cfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, uint64_t p_stride,
+                                      bool from_table);
+int  bhwp_describe_welch_cfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf,
+                              uint64_t len);
+int  bhwk_welch_cfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwWelchCfftPlan &pl, const bhw_stft *s,
+                         double scale, const float *d_x, float *d_P, double *d_ws, const int32_t *d_table, const BhwLenPhase &lp);
 
 // ---- fused inverse real FFT, window and overlap-add (bhw_istft_fft_f32_*; bhw_istft_fft.hip) ------------------------------------------
 // The lane layout of the forward kernel (lpf lanes along a row, fy slots side by side, cpl columns per lane).  The window-start axis

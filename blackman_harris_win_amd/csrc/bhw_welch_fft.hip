@@ -237,25 +237,36 @@ int bhwk_welch_fft_f32(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWi
             launch_lds(k_welch_fft_table<F, NT, M>, grid, block, pl.lds_bytes, st, c, w, tab, a, lp, wa);
         });
     }
+    const int e = finish(hipSuccess);
+    if (e) return e;
+    return bhwk_welch_join(l, d_ws, d_P, s->batch, wp.bins, s->n_fft, wp.chunks, wp.blocks, wp.blocks_grid, wp.join_grid, wp.p_stride, scale,
+                           psd_flags);
+}
+
+// The join of the chunk sums at d_ws (the block sums follow them), for this unit and bhw_welch_cfft.hip: bhw_internal.h.
+int bhwk_welch_join(const BhwLaunch &l, double *d_ws, float *d_P, uint64_t batch, uint64_t bins, uint64_t n_fft, uint64_t chunks,
+                    uint64_t blocks, uint64_t blocks_grid, uint64_t join_grid, uint64_t p_stride, double scale, uint32_t psd_flags)
+{
+    hipStream_t st = (hipStream_t)l.stream;
     WelchFftJoin j{};
     j.in = d_ws;
-    j.out = d_ws + s->batch * wp.chunks * wp.bins;                      // the block sums follow the chunk sums
+    j.out = d_ws + batch * chunks * bins;                               // the block sums follow the chunk sums
     j.P = d_P;
-    j.batch = s->batch;
-    j.bins = wp.bins;
-    j.n_fft = s->n_fft;
-    j.n_in = wp.chunks;
-    j.n_out = wp.blocks;
-    j.p_stride = wp.p_stride;
+    j.batch = batch;
+    j.bins = bins;
+    j.n_fft = n_fft;
+    j.n_in = chunks;
+    j.n_out = blocks;
+    j.p_stride = p_stride;
     j.scale = scale;
     j.flags = psd_flags;
-    const dim3 g1((unsigned)wp.blocks_grid), g2((unsigned)wp.join_grid);
-    if (wp.blocks == 1) {
+    const dim3 g1((unsigned)blocks_grid), g2((unsigned)join_grid);
+    if (blocks == 1) {
         launch(k_welch_fft_join<true, true>, g1, dim3(256), st, j);
     } else {
         launch(k_welch_fft_join<true, false>, g1, dim3(256), st, j);
         j.in = j.out;
-        j.n_in = wp.blocks;
+        j.n_in = blocks;
         j.n_out = 1;
         launch(k_welch_fft_join<false, true>, g2, dim3(256), st, j);
     }

@@ -1367,6 +1367,130 @@ def welch_fused(params, x, fs=1.0, *, length, noverlap=None, nfft=None, detrend=
                         _SUMS_CACHE)
 
 
+# ---- fused Welch PSD for I/Q input: window, complex FFT and the frame average in one kernel ------------------------------------------------
+
+def _welch_cfft_call(torch, params, L, s, flags, xb, nb, n_fft, scale, out, workspace, dev, table, one_d):
+    """The output and workspace rules of the fused Welch PSD for I/Q input and its launch: P float32 (n_fft,) or (B, n_fft)."""
+    shape = (n_fft,) if one_d else (nb, n_fft)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=xb.device)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != xb.device or tuple(out.shape) != shape \
+            or out.stride(-1) != 1 or (out.dim() == 2 and nb > 1 and out.stride(0) < n_fft):
+        raise ValueError(f"out must be a float32 tensor of shape {shape} on x's device, contiguous along the bins, rows apart")
+    need = B.welch_cfft_workspace_bytes(s) // 8
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float64, device=xb.device)
+    else:
+        _check_out(torch, workspace, need, "workspace", torch.float64)
+    tail = (ctypes.byref(s), flags, float(scale), ctypes.c_void_p(xb.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+            out.stride(0) if (out.dim() == 2 and nb > 1) else 0, ctypes.c_void_p(workspace.data_ptr()), workspace.numel() * 8)
+    if table is None:
+        B.check(B.lib().bhw_welch_cfft_f32_device(ctypes.byref(params), L, dev, _stream_ptr(torch, dev), *tail))
+    else:
+        B.check(B.lib().bhw_welch_cfft_f32_from_table(table, ctypes.byref(params), L, _stream_ptr(torch, dev), *tail))
+    return out
+
+
+def _welch_cfft_psd(torch, params, x, n_fft, hop, scale, win_length, center, pad_mode, detrend, shift, fftshift, out, workspace, dev,
+                    table):
+    n_fft, L, xb, nb, T, frames, d = _stft_front(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, dev, _cfft_input)
+    if not x.is_cuda or x.device.index != dev:
+        raise ValueError("x must be a complex64 CUDA tensor on the call's device")
+    shift = params.dat_width - 1 if shift is None else int(shift)
+    s = B.make_stft(nb, T, frames, d["hop"], n_fft, col0=d["col0"], pad=d["pad"], pad_mode=d["pad_mode"], channels=2, shift=shift,
+                    x_stride=xb.stride(0) * 2 if nb > 1 else 0)
+    flags = (B.WELCH_DETREND_CONSTANT if detrend else 0) | (B.CFFT_SHIFT if fftshift else 0)
+    return _welch_cfft_call(torch, params, L, s, flags, xb, nb, n_fft, scale, out, workspace, dev, table, x.dim() == 1)
+
+
+def welch_fft_iq(params, x, n_fft, hop, scale, *, win_length=None, center=False, pad_mode="reflect", detrend=False, shift=None,
+                 fftshift=False, out=None, workspace=None):
+    """The two-sided averaged periodogram of the rows of stft_iq() WITHOUT the spectrum ever reaching memory
+    (bhw_welch_cfft_f32_device): x (T,) or (B, T), complex64, framed, windowed and transformed exactly as stft_iq(params, x, n_fft,
+    hop, win_length=..., center=..., pad_mode=..., detrend=...) does -- the (re, im) of every bin are the same words -- and |Y|^2
+    summed over the frames in the same kernel.  Returns float32 (n_fft,) or (B, n_fft): P[b, j] = fl32(A * scale), A the binary64
+    sum of re^2 + im^2 in the fixed order of include/bhw.h (welch_fft's: ascending frames inside chunks of 16, the chunks of a block
+    of 256 frames in order, then the blocks in order); nothing is doubled.  So P does not depend on B or the plan; for F <= 16 frames
+    it is welch_psd(stft_iq(...), scale, nfft=n_fft, onesided=False) bit for bit, for more frames within one float32 ulp of it.
+    fftshift=True writes bin (j + n_fft // 2) % n_fft to column j: torch.fft.fftshift of the same values.  n_fft: a power of two in
+    16..2048 (ValueError otherwise; a real or complex128 x too: welch_fft() takes real input).  `out`: float32 of the returned shape,
+    bins contiguous, rows apart (its gaps are left alone); `workspace`: float64, B.welch_cfft_workspace_bytes(...) // 8 elements
+    (allocated when not given).  With both given the call neither allocates nor synchronises and can be captured with no warm
+    call."""
+    torch = _torch()
+    dev = x.device.index if isinstance(x, torch.Tensor) and x.is_cuda else None
+    return _welch_cfft_psd(torch, params, x, n_fft, hop, scale, win_length, center, pad_mode, detrend, shift, fftshift, out, workspace,
+                           dev, None)
+
+
+def _freq_axis_iq(torch, cache, nfft, fs, fftshift, dev):
+    """_freq_axis for welch_fused_iq: the two-sided axis fftfreq(nfft, 1 / fs), or its fftshift, kept beside the window sums under a
+    key of its own kind ("freqs_iq"), so that it never meets welch_fused's one-sided axes or their count."""
+    key = ("freqs_iq", int(nfft), float(fs), int(dev), bool(fftshift))
+    hit = cache.get(key)
+    if hit is not None:
+        return hit
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("the frequency axis of this (nfft, fs) has not been built yet: call once outside the capture")
+    kept = [k for k in cache if isinstance(k, tuple) and k and k[0] == "freqs_iq"]
+    for k in kept[:max(0, len(kept) - _FREQS_KEPT + 1)]:
+        del cache[k]
+    axis = torch.fft.fftfreq(int(nfft), d=1.0 / float(fs), dtype=torch.float64, device=f"cuda:{dev}")
+    cache[key] = torch.fft.fftshift(axis) if fftshift else axis
+    return cache[key]
+
+
+def _welch_fused_iq(torch, params, x, fs, length, noverlap, nfft, detrend, scaling, shift, fftshift, out, workspace, dev, table, cache):
+    if detrend not in ("constant", False, None):
+        raise ValueError(f"detrend must be 'constant' or False, got {detrend!r}")
+    if scaling not in ("density", "spectrum"):
+        raise ValueError(f"scaling must be 'density' or 'spectrum', got {scaling!r}")
+    L = int(length)
+    noverlap = L // 2 if noverlap is None else int(noverlap)
+    if not 0 <= noverlap < L:
+        raise ValueError("noverlap must be less than length")
+    nfft = L if nfft is None else int(nfft)
+    hop = L - noverlap
+    _cfft_input(torch, x, nfft, dev)
+    if not x.is_cuda or x.device.index != dev:
+        raise ValueError("x must be a complex64 CUDA tensor on the call's device")
+    if not 1 <= L <= 1 << params.phi_width:
+        raise ValueError(f"length {L} outside 1..2^phi_width = {1 << params.phi_width}")
+    if nfft < L:
+        raise ValueError(f"nfft {nfft} must be at least the window length {L}")
+    xb = x if x.dim() == 2 else x.unsqueeze(0)
+    nb, T = xb.shape
+    if nb < 1 or T < L:
+        raise ValueError(f"zero segments: T = {T} < length = {L}" if nb else "zero signals")
+    frames = 1 + (T - L) // hop
+    xb = _stft_input(xb, (T,))
+    sums = _window_sums(torch, params, L, True, shift, dev, table, cache)
+    scale = B.welch_scale(sums, frames, fs, scaling)
+    sh = params.dat_width - 1 if shift is None else int(shift)
+    s = B.make_stft(nb, T, frames, hop, nfft, channels=2, shift=sh, x_stride=xb.stride(0) * 2 if nb > 1 else 0)
+    freqs = _freq_axis_iq(torch, cache, nfft, fs, fftshift, dev)     # before the launch: it refuses inside a capture when missing
+    flags = (B.WELCH_DETREND_CONSTANT if detrend == "constant" else 0) | (B.CFFT_SHIFT if fftshift else 0)
+    P = _welch_cfft_call(torch, params, L, s, flags, xb, nb, nfft, scale, out, workspace, dev, table, x.dim() == 1)
+    return freqs, P
+
+
+def welch_fused_iq(params, x, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", scaling="density", shift=None,
+                   fftshift=False, out=None, workspace=None):
+    """welch() of a complex64 (I/Q) x in ONE kernel and a small join (bhw_welch_cfft_f32_device): the segments, their complex FFT and
+    the average over them come from the same kernel, so the (B, F, nfft) spectrum never exists.  The arguments, their checks, the
+    window sums (read once per (params, length, shift) and cached) and the scale are welch()'s for complex input; the result is the
+    two-sided estimate (freqs float64, Pxx float32 (..., nfft)), freqs = fftfreq(nfft, 1 / fs), or with fftshift=True both freqs and
+    Pxx in ascending frequency (torch.fft.fftshift of the same values).  Only the mean is averaged.  nfft: a power of two in 16..2048
+    (ValueError otherwise; a real or complex128 x too).  The sum over the frames has the order of welch_fft_iq().  After one warm
+    call, with `out` and `workspace` given, it neither synchronises nor allocates and can be captured
+    (ResidentTable.welch_fused_iq); a first call inside a capture -- the first for its window sums, or for its (nfft, fs, fftshift)
+    -- raises, as welch_fused does.  `freqs` is SHARED and read-only, as welch_fused's."""
+    torch = _torch()
+    dev = x.device.index if isinstance(x, torch.Tensor) and x.is_cuda else None
+    return _welch_fused_iq(torch, params, x, fs, length, noverlap, nfft, detrend, scaling, shift, fftshift, out, workspace, dev, None,
+                           _SUMS_CACHE)
+
+
 # ---- Welch cross spectra: the pass behind the FFT for two signals -------------------------------------------------------------------------
 
 def _csd_operand(torch, t, what, dev):
@@ -1796,6 +1920,20 @@ class ResidentTable:
         captured into a graph, a first call inside a capture raises."""
         return _welch_fused(_torch(), params, x, fs, length, noverlap, nfft, detrend, scaling, shift, out, workspace, self.device,
                             self._live(), self._sums)
+
+    def welch_fft_iq(self, params, x, n_fft, hop, scale, *, win_length=None, center=False, pad_mode="reflect", detrend=False,
+                     shift=None, fftshift=False, out=None, workspace=None):
+        """welch_fft_iq() with the coefficients gathered from this table (bhw_welch_cfft_f32_from_table): no allocation by the
+        library, no synchronisation, capturable on its first call; the bits are those of the library form."""
+        return _welch_cfft_psd(_torch(), params, x, n_fft, hop, scale, win_length, center, pad_mode, detrend, shift, fftshift, out,
+                               workspace, self.device, self._live())
+
+    def welch_fused_iq(self, params, x, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", scaling="density",
+                       shift=None, fftshift=False, out=None, workspace=None):
+        """welch_fused_iq() from this table.  The sums cache and the capture rule are welch()'s: after one warm call the call can be
+        captured into a graph, a first call inside a capture raises."""
+        return _welch_fused_iq(_torch(), params, x, fs, length, noverlap, nfft, detrend, scaling, shift, fftshift, out, workspace,
+                               self.device, self._live(), self._sums)
 
     def cross_spectra(self, params, x, y, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", return_onesided=True,
                       scaling="density", shift=None, outputs=("pxy", "pxx", "pyy", "coherence", "h1"), fft="torch"):

@@ -1052,8 +1052,8 @@ int bhw_describe_istft_cfft(bhw_table t, const bhw_params *p, uint64_t length, c
  *     table) the key match.
  *   - Capture: as bhw_stft_fft_f32_*.  The library form needs no bhw_prepare_device; the from-table form is capturable on its first
  *     call.
- *   - Not built: cross spectra accumulated in the kernel; the mixed-radix and I/Q kernels with this epilogue; max-hold or median
- *     averaging; a filter bank on the averaged powers.
+ *   - Not built: cross spectra accumulated in the kernel; the mixed-radix kernel with this epilogue (I/Q input has it:
+ *     bhw_welch_cfft_f32_* below); max-hold or median averaging; a filter bank on the averaged powers.
  *   - bhw_describe_welch_fft: bhw_describe_stft_fft's line in the same words, plus the chunk, the runs, the groups per run, the
  *     accumulators per lane and the workspace bytes.  t may be NULL (the library call).  Host arithmetic only. */
 /* Why 16: the frames of ONE signal are the only parallelism a long record has.  16 381 frames of one signal (2^24 samples, n_fft 4096,
@@ -1068,6 +1068,51 @@ int bhw_welch_fft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t leng
                                  double scale, uint32_t psd_flags, const float *d_x, float *d_P, uint64_t p_stride, void *workspace,
                                  uint64_t workspace_bytes);
 int bhw_describe_welch_fft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf, uint64_t len);
+
+/* Fused Welch PSD for complex (I/Q) input: window, complex FFT and the average over the frames by ONE kernel and the join of
+ * bhw_welch_fft_f32_*.  The rows of bhw_stft_cfft_f32_* are formed and transformed by the same kernel body, and |Y|^2 is accumulated
+ * over the frames where the transform ends, so the (B, F, n_fft) spectrum that bhw_stft_cfft_f32_* + bhw_welch_psd_f32 write and read
+ * back never exists.  The estimate is two-sided: n_fft bins, nothing is doubled, and there is no psd_flags.
+ *   - Inputs: (p, length, s, flags) exactly as bhw_stft_cfft_f32_* takes them (channels 2, interleaved I/Q; the padding fields of s
+ *     as that call accepts them), except that flags is any combination of BHW_WELCH_DETREND_CONSTANT and BHW_CFFT_SHIFT --
+ *     BHW_CFFT_POWER is refused -- and s->y_stride and s->y_batch_stride must be 0: no spectrum is written.  scale is bhw_psd's; d_P
+ *     is float32 (B, n_fft), row b at b * p_stride floats (0 = n_fft).
+ *   - Row and transform: those of bhw_stft_cfft_f32_* for the same (p, length, s) and the detrend flag.  Let (re, im) be the float32
+ *     pair that call writes for bin k of row (b, f), bit for bit: the same words, from the same row function.
+ *   - The sums, with q_f = (double) re * (double) re + (double) im * (double) im, are those of bhw_welch_fft_f32_* above:
+ *        A_chunk = sum of q_f over the frames of one chunk of BHW_WELCH_FFT_CHUNK = 16, in ascending f, binary64 from +0.0
+ *        A_blk   = sum of A_chunk over the 16 chunks of one block of BHW_WELCH_BLOCK = 256 frames, ascending, binary64 from +0.0
+ *        A       = sum of A_blk over the blocks, ascending, binary64 from +0.0
+ *        d_P[b * p_stride + j] = fl32(A * scale)
+ *     (the last chunk and the last block may be shorter).  Column j holds bin j, or with BHW_CFFT_SHIFT bin (j + n_fft / 2) mod
+ *     n_fft, the column rule of bhw_stft_cfft_f32_*.
+ *   - Consequences: the bits of P depend on the window, n_fft, the flags, scale and the signal's samples only -- not on B, the grid,
+ *     or library versus table.  For F <= 16 P equals bhw_welch_psd_f32 (flags 0) of bhw_stft_cfft_f32_*'s rows bit for bit; beyond 16
+ *     frames it lies within one float32 ulp of that route, by the argument given for bhw_welch_fft_f32_*.  There are no float
+ *     atomics: every chunk sum is stored plainly once.
+ *   - Workspace: caller-provided, 8-byte aligned, bhw_welch_cfft_workspace_bytes(s) bytes: the chunk sums, B * ceil(F / 16) * n_fft
+ *     doubles, followed, when F > 256, by the block sums, B * ceil(F / 256) * n_fft doubles.  A short one is BHW_ERR_WORKSPACE.  No
+ *     call allocates.
+ *   - Supported: exactly the set of bhw_stft_cfft_f32_* (channels 2, n_fft a power of two in 16..2048); channels 1 and every other
+ *     n_fft are BHW_ERR_UNSUPPORTED with that call's words.
+ *   - IEEE: a NaN or an infinity in x reaches only the bins of its own signal.  Zeros in give +0.0 out (for a scale >= 0).
+ *   - Checks before any HIP call, in this order (BHW_ERR_BADARG unless noted): everything bhw_stft_cfft_f32_* checks on the
+ *     descriptor (with the y strides taken as packed); BHW_CFFT_POWER set, non-zero y strides, a scale that is not finite; frames 0
+ *     returns BHW_OK here with the pointers unchecked; p_stride below n_fft, B * ceil(F / 16) * n_fft above 2^34; NULL d_x or d_P,
+ *     either not 4-byte aligned; a NULL or misaligned workspace, a short one (BHW_ERR_WORKSPACE); d_P or the workspace overlapping
+ *     d_x or each other; and (from a table) the key match.
+ *   - Capture: as bhw_stft_cfft_f32_*.  The library form needs no bhw_prepare_device; the from-table form is capturable on its first
+ *     call.
+ *   - Not built: the mixed-radix kernel under this epilogue; max-hold or median traces; n_fft 4096; cross spectra accumulated in the
+ *     kernel; a filter bank on the averaged powers.
+ *   - bhw_describe_welch_cfft: bhw_describe_stft_cfft's line in the same words (without the output form), plus the fields
+ *     bhw_describe_welch_fft adds.  t may be NULL (the library call).  Host arithmetic only. */
+uint64_t bhw_welch_cfft_workspace_bytes(const bhw_stft *s);
+int bhw_welch_cfft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                              double scale, const float *d_x, float *d_P, uint64_t p_stride, void *workspace, uint64_t workspace_bytes);
+int bhw_welch_cfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                  double scale, const float *d_x, float *d_P, uint64_t p_stride, void *workspace, uint64_t workspace_bytes);
+int bhw_describe_welch_cfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf, uint64_t len);
 
 /* Threading: every entry point may be called from any host thread.  Calls that use the library-owned scratch of one
  * (device, stream) are serialised against each other for the duration of their launches (the table is rebuilt per call);
