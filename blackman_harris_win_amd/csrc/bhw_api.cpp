@@ -1197,6 +1197,21 @@ int welch_cfft_run(bhw_table t, const bhw_params *p, uint64_t length, int device
     });
 }
 
+// The fused Welch PSD at a mixed-radix n_fft (t NULL: the direct CORDIC chains): the checks, then the accumulating kernel and the join.
+int welch_mfft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *s, uint32_t flags,
+                   double scale, uint32_t psd_flags, const float *d_x, float *d_P, uint64_t p_stride, void *workspace, uint64_t workspace_bytes)
+{
+    int rc = bhwp_welch_mfft_checks(p, length, s, flags, scale, psd_flags, p_stride, d_x, d_P, workspace, workspace_bytes);
+    if (!rc && t) rc = table_call_checks(t, p);
+    if (rc || !s->frames) return rc;
+    const BhwWelchMfftPlan pl = bhwp_welch_mfft_plan(p, length, s, flags, p_stride, t != nullptr);
+    const char *what = t ? "welch mfft launch (resident table)" : "welch mfft launch";
+    return run_source(t, p, length, device, stream, what, [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *tab,
+                                                              const BhwLenPhase *lp) {
+        return bhwk_welch_mfft_f32(l, c, w, pl, s, scale, psd_flags, d_x, d_P, (double *)workspace, tab, *lp);
+    });
+}
+
 // The mixed-radix fused window + FFT in its three output forms (t NULL: the direct CORDIC chains): the checks, then the one kernel.
 int stft_mfft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *s, uint32_t flags,
                   const bhw_fbank *fb, const float *d_x, float *d_out)
@@ -1531,6 +1546,37 @@ int bhw_describe_welch_cfft(bhw_table t, const bhw_params *p, uint64_t length, c
     int rc = bhwp_welch_cfft_checks(p, length, s, flags, 0.0, 0, nullptr, nullptr, nullptr, 0, false);
     if (!rc && t) rc = table_call_checks(t, p);
     return rc ? rc : bhwp_describe_welch_cfft(p, t ? &t->c : nullptr, length, s, flags, buf, len);
+}
+
+// ---- fused Welch PSD at mixed-radix n_fft (include/bhw.h: bhw_welch_mfft_f32_device ...) ---------------------------------------------------
+
+uint64_t bhw_welch_mfft_workspace_bytes(const bhw_stft *s)
+{
+    return s && s->struct_size == sizeof(bhw_stft) ? bhwp_welch_mfft_workspace_bytes(s) : 0;
+}
+
+int bhw_welch_mfft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                              double scale, uint32_t psd_flags, const float *d_x, float *d_P, uint64_t p_stride, void *workspace,
+                              uint64_t workspace_bytes)
+{
+    return welch_mfft_run(nullptr, p, length, device, hip_stream, s, flags, scale, psd_flags, d_x, d_P, p_stride, workspace, workspace_bytes);
+}
+
+int bhw_welch_mfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                  double scale, uint32_t psd_flags, const float *d_x, float *d_P, uint64_t p_stride, void *workspace,
+                                  uint64_t workspace_bytes)
+{
+    const int rc = bhwp_welch_mfft_checks(p, length, s, flags, scale, psd_flags, p_stride, d_x, d_P, workspace, workspace_bytes);
+    if (rc) return rc;
+    return t ? welch_mfft_run(t, p, length, t->device, hip_stream, s, flags, scale, psd_flags, d_x, d_P, p_stride, workspace, workspace_bytes)
+             : fail(BHW_ERR_BADARG, "table is NULL");
+}
+
+int bhw_describe_welch_mfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf, uint64_t len)
+{
+    int rc = bhwp_welch_mfft_checks(p, length, s, flags, 0.0, 0, 0, nullptr, nullptr, nullptr, 0, false);
+    if (!rc && t) rc = table_call_checks(t, p);
+    return rc ? rc : bhwp_describe_welch_mfft(p, t ? &t->c : nullptr, length, s, flags, buf, len);
 }
 
 // ---- mixed-radix fused window and real FFT (include/bhw.h: bhw_stft_mfft_f32_device ...) -----------------------------------------------

@@ -123,7 +123,8 @@ int bhwk_taylor_window(const BhwLaunch &l, const BhwTaylorCfg &t, const BhwWinCf
 int bhwk_taylor_window_fold(const BhwLaunch &l, const BhwTaylorCfg &t, const BhwWinCfg &w, int32_t *d_out);
 int bhwk_taylor_sincos(const BhwLaunch &l, const BhwTaylorCfg &t, uint64_t theta0, uint64_t count,
                        int32_t *d_sin, int32_t *d_cos);
-// The join of the fused Welch calls (bhw_welch_fft.hip; also launched by bhw_welch_cfft.hip): the chunk sums [(b * chunks + c) * bins + k]
+// The join of the fused Welch calls (bhw_welch_fft.hip; also launched by bhw_welch_cfft.hip and bhw_welch_mfft.hip): the chunk sums
+// [(b * chunks + c) * bins + k]
 // at d_ws, followed (blocks > 1) by the block sums, into d_P by k_welch_fft_join in one launch (one block) or two, in the order of
 // include/bhw.h.  psd_flags: bhw_psd's, for the doubling of a one-sided row of bins = n_fft / 2 + 1; 0 for bins = n_fft.
 int bhwk_welch_join(const BhwLaunch &l, double *d_ws, float *d_P, uint64_t batch, uint64_t bins, uint64_t n_fft, uint64_t chunks,

@@ -2254,6 +2254,125 @@ int bhwp_describe_welch_cfft(const bhw_params *p, const BhwCordicCfg *ct, uint64
     return BHW_OK;
 }
 
+// ---- fused Welch PSD at mixed-radix n_fft -------------------------------------------------------------------------------------------------------
+
+uint64_t bhwp_welch_mfft_workspace_bytes(const bhw_stft *s)
+{
+    if (!s || !s->frames || !s->batch) return 0;
+    return bhwp_welch_runs(s->batch, s->frames, 1, s->n_fft / 2 + 1).ws_bytes;        // the bytes do not depend on fy
+}
+
+int bhwp_welch_mfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, double scale, uint32_t psd_flags,
+                           uint64_t p_stride, const void *d_x, const void *d_P, const void *workspace, uint64_t workspace_bytes,
+                           bool pointers)
+{
+    // 1. the input side: the forward call's checks for the descriptor with packed output strides (no spectrum is written here) and no
+    //    bank.  BHW_MFFT_POWER is a flag that call knows: it passes here and is refused below.
+    bhw_stft t{};
+    const bool sized = s && s->struct_size == sizeof(bhw_stft);
+    if (sized) {
+        t = *s;
+        t.y_stride = t.y_batch_stride = 0;
+    }
+    int rc = bhwp_stft_mfft_checks(p, length, sized ? &t : s, flags, nullptr, nullptr, nullptr, false);
+    if (rc) return rc;
+    // 2.
+    if (flags & BHW_MFFT_POWER)
+        return bhwp_fail(BHW_ERR_BADARG, "flags 0x%x: BHW_MFFT_POWER has no meaning here (BHW_WELCH_DETREND_CONSTANT)", flags);
+    if (s->y_stride || s->y_batch_stride)
+        return bhwp_fail(BHW_ERR_BADARG, "y_stride %llu, y_batch_stride %llu: no spectrum is written, both must be 0",
+                         (unsigned long long)s->y_stride, (unsigned long long)s->y_batch_stride);
+    if (psd_flags & ~BHW_PSD_ONESIDED) return bhwp_fail(BHW_ERR_BADARG, "psd_flags 0x%x (0 or BHW_PSD_ONESIDED)", psd_flags);
+    if (!(scale - scale == 0.0)) return bhwp_fail(BHW_ERR_BADARG, "scale is not finite");
+    // 3., 4., 5.
+    const uint64_t T = s->samples, F = s->frames, K = s->n_fft / 2 + 1;
+    if (!F) return BHW_OK;
+    if (p_stride && p_stride < K)
+        return bhwp_fail(BHW_ERR_BADARG, "p_stride %llu < bins %llu: rows overlap", (unsigned long long)p_stride, (unsigned long long)K);
+    const uint64_t chunks = (F - 1) / BHW_WELCH_FFT_CHUNK + 1;
+    if ((unsigned __int128)s->batch * chunks * K > (1ull << 34))
+        return bhwp_fail(BHW_ERR_BADARG, "batch * ceil(frames / %u) * K above 2^34 per call", BHW_WELCH_FFT_CHUNK);
+    if (!pointers) return BHW_OK;
+    // 6., 7.
+    if (!d_x || !d_P) return bhwp_fail(BHW_ERR_BADARG, "d_x / d_P is NULL");
+    if ((uintptr_t)d_P % 4) return bhwp_fail(BHW_ERR_BADARG, "d_P is not 4-byte aligned");
+    if ((uintptr_t)d_x % 4) return bhwp_fail(BHW_ERR_BADARG, "d_x is not 4-byte aligned");
+    const uint64_t need = bhwp_welch_mfft_workspace_bytes(s);
+    if (!workspace) return bhwp_fail(BHW_ERR_BADARG, "workspace is NULL: the chunk sums need %llu bytes", (unsigned long long)need);
+    if ((uintptr_t)workspace % 8) return bhwp_fail(BHW_ERR_BADARG, "workspace is not 8-byte aligned");
+    if (workspace_bytes < need)
+        return bhwp_fail(BHW_ERR_WORKSPACE, "workspace of %llu bytes, the chunk and block sums need %llu", (unsigned long long)workspace_bytes,
+                         (unsigned long long)need);
+    // 8.
+    const uint64_t xs = s->x_stride ? s->x_stride : T, ps = p_stride ? p_stride : K;
+    const unsigned __int128 xe = (unsigned __int128)(s->batch - 1) * xs + T, pe = (unsigned __int128)(s->batch - 1) * ps + K;
+    if (xe > (1ull << 60) || pe > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "x or P extent beyond 2^60 elements");
+    const uint64_t xa = (uint64_t)(uintptr_t)d_x, pa = (uint64_t)(uintptr_t)d_P, wa = (uint64_t)(uintptr_t)workspace;
+    const uint64_t xb = (uint64_t)xe * 4u, pb = (uint64_t)pe * 4u;
+    if (xa > UINT64_MAX - xb || pa > UINT64_MAX - pb || wa > UINT64_MAX - need)
+        return bhwp_fail(BHW_ERR_BADARG, "x, P or workspace range wraps the address space");
+    if (xa < pa + pb && pa < xa + xb) return bhwp_fail(BHW_ERR_BADARG, "d_x and d_P overlap");
+    if ((wa < xa + xb && xa < wa + need) || (wa < pa + pb && pa < wa + need))
+        return bhwp_fail(BHW_ERR_BADARG, "workspace overlaps d_x or d_P");
+    return BHW_OK;
+}
+
+BhwWelchMfftPlan bhwp_welch_mfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, uint64_t p_stride,
+                                      bool from_table)
+{
+    BhwWelchMfftPlan pl{};
+    bhw_stft t = *s;
+    t.y_stride = t.y_batch_stride = 0;
+    pl.fft = bhwp_stft_mfft_plan(p, length, &t, flags & BHW_WELCH_DETREND_CONSTANT, nullptr, from_table);
+    pl.fft.y_stride = pl.fft.y_bstride = 0;
+    pl.bins = s->n_fft / 2 + 1;
+    const BhwWelchRuns r = bhwp_welch_runs(s->batch, s->frames, pl.fft.fy, pl.bins);
+    pl.run = r.run;
+    pl.gpr = r.gpr;
+    pl.acc = pl.fft.fy >= BHW_WELCH_FFT_CHUNK ? 0u : (uint32_t)((pl.bins + kFftBlock - 1) / kFftBlock);
+    pl.p_stride = p_stride ? p_stride : pl.bins;
+    pl.fpad = r.fpad;
+    pl.chunks = r.chunks;
+    pl.blocks = r.blocks;
+    pl.runs = r.runs;
+    pl.fft.groups = r.groups;
+    pl.fft.grid = r.grid;
+    pl.blocks_grid = r.blocks_grid;
+    pl.join_grid = r.join_grid;
+    pl.ws_bytes = r.ws_bytes;
+    return pl;
+}
+
+int bhwp_describe_welch_mfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf,
+                             uint64_t len)
+{
+    if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
+    const char *route = ct ? "table" : "direct";
+    const BhwWelchMfftPlan wp = bhwp_welch_mfft_plan(p, length, s, flags, 0, ct != nullptr);
+    const BhwStftMfftPlan &pl = wp.fft;
+    const char *pad = s->pad_mode == BHW_PAD_REFLECT ? "reflect" : "constant";
+    const char *det = pl.detrend ? "constant detrend" : "no detrending";
+    if (!s->frames) {
+        snprintf(buf, len, "welch mfft %s (L = %llu, n_fft %llu, %s): nothing (frames 0)", route, (unsigned long long)length,
+                 (unsigned long long)s->n_fft, det);
+        return BHW_OK;
+    }
+    char kern[64], sched[48];
+    kernel_name(p, ct, "k_welch_mfft_direct", "k_welch_mfft_table", false, kern, sizeof kern);
+    bhwp_stft_mfft_schedule(pl, sched, sizeof sched);
+    snprintf(buf, len, "welch mfft %s (L = %llu, n_fft %llu, col0 %llu, pad %llu %s, %s): %s, %llu signals x %llu frames = %llu rows, "
+             "complex FFT of %u points in passes %s + split, %u lanes per row x %u rows per workgroup, %u columns per lane, %llu groups, "
+             "grid %llu x %u lanes, %u bytes of LDS; chunk %u frames, %llu runs of %llu frames (%u group%s per run), %u accumulator%s "
+             "per lane, %llu chunks and %llu block%s per signal, then k_welch_fft_join %s, workspace %llu bytes",
+             route, (unsigned long long)length, (unsigned long long)s->n_fft, (unsigned long long)s->col0, (unsigned long long)s->pad, pad,
+             det, kern, (unsigned long long)s->batch, (unsigned long long)s->frames, (unsigned long long)pl.rows, pl.m, sched, pl.lpf, pl.fy,
+             pl.cpl, (unsigned long long)pl.groups, (unsigned long long)pl.grid, kFftBlock, pl.lds_bytes, BHW_WELCH_FFT_CHUNK,
+             (unsigned long long)wp.runs, (unsigned long long)wp.run, wp.gpr, wp.gpr == 1 ? "" : "s", wp.acc, wp.acc == 1 ? "" : "s",
+             (unsigned long long)wp.chunks, (unsigned long long)wp.blocks, wp.blocks == 1 ? "" : "s",
+             wp.blocks == 1 ? "once (chunks)" : "twice (chunks, blocks)", (unsigned long long)wp.ws_bytes);
+    return BHW_OK;
+}
+
 // ---- fused inverse real FFT, window and overlap-add -----------------------------------------------------------------------------------------
 
 int bhwp_istft_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const void *d_Y, const void *d_x,

@@ -1244,15 +1244,16 @@ def welch(params, x, fs=1.0, *, length, noverlap=None, nfft=None, detrend="const
 
 # ---- fused Welch PSD: window, FFT and the frame average in one kernel --------------------------------------------------------------------
 
-def _welch_fft_call(torch, params, L, s, flags, xb, nb, K, scale, onesided, out, workspace, dev, table, one_d):
-    """The output and workspace rules of the fused Welch PSD and its launch: P float32 (K,) or (B, K)."""
+def _welch_fft_call(torch, params, L, s, flags, xb, nb, K, scale, onesided, out, workspace, dev, table, one_d, family="fft"):
+    """The output and workspace rules of the fused Welch PSD and its launch: P float32 (K,) or (B, K).  family: "fft" (a power-of-two
+    n_fft, bhw_welch_fft_f32_*) or "mfft" (a mixed-radix one, bhw_welch_mfft_f32_*): the two argument lists are one."""
     shape = (K,) if one_d else (nb, K)
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=xb.device)
     elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != xb.device or tuple(out.shape) != shape \
             or out.stride(-1) != 1 or (out.dim() == 2 and nb > 1 and out.stride(0) < K):
         raise ValueError(f"out must be a float32 tensor of shape {shape} on x's device, contiguous along the bins, rows apart")
-    need = B.welch_fft_workspace_bytes(s) // 8
+    need = getattr(B, f"welch_{family}_workspace_bytes")(s) // 8
     if workspace is None:
         workspace = torch.empty(need, dtype=torch.float64, device=xb.device)
     else:
@@ -1261,20 +1262,21 @@ def _welch_fft_call(torch, params, L, s, flags, xb, nb, K, scale, onesided, out,
             ctypes.c_void_p(out.data_ptr()), out.stride(0) if (out.dim() == 2 and nb > 1) else 0, ctypes.c_void_p(workspace.data_ptr()),
             workspace.numel() * 8)
     if table is None:
-        B.check(B.lib().bhw_welch_fft_f32_device(ctypes.byref(params), L, dev, _stream_ptr(torch, dev), *tail))
+        B.check(getattr(B.lib(), f"bhw_welch_{family}_f32_device")(ctypes.byref(params), L, dev, _stream_ptr(torch, dev), *tail))
     else:
-        B.check(B.lib().bhw_welch_fft_f32_from_table(table, ctypes.byref(params), L, _stream_ptr(torch, dev), *tail))
+        B.check(getattr(B.lib(), f"bhw_welch_{family}_f32_from_table")(table, ctypes.byref(params), L, _stream_ptr(torch, dev), *tail))
     return out
 
 
 def _welch_fft_psd(torch, params, x, n_fft, hop, scale, win_length, center, pad_mode, detrend, onesided_doubling, shift, out, workspace,
-                   dev, table):
-    n_fft, L, xb, nb, T, frames, d = _stft_front(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, dev)
+                   dev, table, family="fft"):
+    check = _fft_input if family == "fft" else _welch_mfft_input
+    n_fft, L, xb, nb, T, frames, d = _stft_front(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, dev, check)
     shift = params.dat_width - 1 if shift is None else int(shift)
     s = B.make_stft(nb, T, frames, d["hop"], n_fft, col0=d["col0"], pad=d["pad"], pad_mode=d["pad_mode"], shift=shift,
                     x_stride=xb.stride(0) if nb > 1 else 0)
     return _welch_fft_call(torch, params, L, s, B.WELCH_DETREND_CONSTANT if detrend else 0, xb, nb, n_fft // 2 + 1, scale,
-                           onesided_doubling, out, workspace, dev, table, x.dim() == 1)
+                           onesided_doubling, out, workspace, dev, table, x.dim() == 1, family)
 
 
 def welch_fft(params, x, n_fft, hop, scale, *, win_length=None, center=False, pad_mode="reflect", detrend=False,
@@ -1297,7 +1299,7 @@ def welch_fft(params, x, n_fft, hop, scale, *, win_length=None, center=False, pa
                           workspace, x.device.index, None)
 
 
-def _welch_fused(torch, params, x, fs, length, noverlap, nfft, detrend, scaling, shift, out, workspace, dev, table, cache):
+def _welch_fused(torch, params, x, fs, length, noverlap, nfft, detrend, scaling, shift, out, workspace, dev, table, cache, family="fft"):
     if detrend not in ("constant", False, None):
         raise ValueError(f"detrend must be 'constant' or False, got {detrend!r}")
     if scaling not in ("density", "spectrum"):
@@ -1308,7 +1310,7 @@ def _welch_fused(torch, params, x, fs, length, noverlap, nfft, detrend, scaling,
         raise ValueError("noverlap must be less than length")
     nfft = L if nfft is None else int(nfft)
     hop = L - noverlap
-    _fft_input(torch, x, nfft, dev)
+    (_fft_input if family == "fft" else _welch_mfft_input)(torch, x, nfft, dev)
     if not 1 <= L <= 1 << params.phi_width:
         raise ValueError(f"length {L} outside 1..2^phi_width = {1 << params.phi_width}")
     if nfft < L:
@@ -1323,26 +1325,28 @@ def _welch_fused(torch, params, x, fs, length, noverlap, nfft, detrend, scaling,
     scale = B.welch_scale(sums, frames, fs, scaling)
     sh = params.dat_width - 1 if shift is None else int(shift)
     s = B.make_stft(nb, T, frames, hop, nfft, shift=sh, x_stride=xb.stride(0) if nb > 1 else 0)
-    freqs = _freq_axis(torch, cache, nfft, fs, dev)                  # before the launch: it refuses inside a capture when missing
+    # before the launch: it refuses inside a capture when missing
+    freqs = _freq_axis(torch, cache, nfft, fs, dev, "freqs" if family == "fft" else "freqs_mixed")
     P = _welch_fft_call(torch, params, L, s, B.WELCH_DETREND_CONSTANT if detrend == "constant" else 0, xb, nb, nfft // 2 + 1, scale,
-                        True, out, workspace, dev, table, x.dim() == 1)
+                        True, out, workspace, dev, table, x.dim() == 1, family)
     return freqs, P
 
 
 _FREQS_KEPT = 8         # frequency axes a sums cache keeps (the oldest goes first)
 
 
-def _freq_axis(torch, cache, nfft, fs, dev):
+def _freq_axis(torch, cache, nfft, fs, dev, kind="freqs"):
     """The float64 frequency axis welch_fused returns, built once per (nfft, fs) and kept beside the window sums in `cache` (the
     library's, or the table's own), so that a warm call allocates nothing.  Like the sums it is never made inside a capture: a tensor
-    allocated there belongs to the graph's pool and holds nothing until the graph is replayed."""
-    key = ("freqs", int(nfft), float(fs), int(dev))
+    allocated there belongs to the graph's pool and holds nothing until the graph is replayed.  kind: the first word of the key,
+    "freqs" for welch_fused and "freqs_mixed" for welch_fused_mixed, so that neither meets the other's axes or counts against them."""
+    key = (kind, int(nfft), float(fs), int(dev))
     hit = cache.get(key)
     if hit is not None:
         return hit
     if torch.cuda.is_current_stream_capturing():
         raise RuntimeError("the frequency axis of this (nfft, fs) has not been built yet: call once outside the capture")
-    kept = [k for k in cache if isinstance(k, tuple) and k and k[0] == "freqs"]
+    kept = [k for k in cache if isinstance(k, tuple) and k and k[0] == kind]
     for k in kept[:max(0, len(kept) - _FREQS_KEPT + 1)]:
         del cache[k]
     axis = cache[key] = torch.fft.rfftfreq(int(nfft), d=1.0 / float(fs), dtype=torch.float64, device=f"cuda:{dev}")
@@ -1365,6 +1369,59 @@ def welch_fused(params, x, fs=1.0, *, length, noverlap=None, nfft=None, detrend=
         raise ValueError("x must be a float32 CUDA tensor")
     return _welch_fused(torch, params, x, fs, length, noverlap, nfft, detrend, scaling, shift, out, workspace, x.device.index, None,
                         _SUMS_CACHE)
+
+
+# ---- fused Welch PSD at a mixed-radix n_fft: window, mixed-radix FFT and the frame average in one kernel -----------------------------------
+
+def _welch_mfft_input(torch, x, n_fft, dev):
+    """_mfft_input for the fused Welch calls: the refusals name the Welch call that takes what this one does not."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.device.index != dev:
+        raise ValueError("x must be a float32 CUDA tensor on the call's device")
+    if x.dtype != torch.float32:
+        raise ValueError(f"the mixed-radix fused Welch PSD takes real float32 input, got {x.dtype} (complex64 I/Q input at a "
+                         "power-of-two n_fft: welch_fft_iq / welch_fused_iq)")
+    if x.dim() not in (1, 2):
+        raise ValueError("x must be (T,) or (B, T)")
+    n = int(n_fft)
+    if n > 0 and n & (n - 1) == 0:
+        raise ValueError(f"n_fft {n} is a power of two: welch_fft / welch_fused transform it (one transform per n_fft)")
+    if not B.mfft_supported(n):
+        raise ValueError(f"the mixed-radix fused FFT takes n_fft even 2^a·3^b·5^c in {B.MFFT_MIN_N}..{B.MFFT_MAX_N}, got {n}")
+
+
+def welch_fft_mixed(params, x, n_fft, hop, scale, *, win_length=None, center=False, pad_mode="reflect", detrend=False,
+                    onesided_doubling=True, shift=None, out=None, workspace=None):
+    """welch_fft() at the n_fft of stft_mixed() (bhw_welch_mfft_f32_device): even, 2^a·3^b·5^c, in 16..4095 and not a power of two
+    -- 400, 480, 960, 1000, 4000, the lengths that make the bin spacing a round number of hertz.  x (T,) or (B, T), real float32,
+    framed, windowed and transformed exactly as stft_mixed(params, x, n_fft, hop, win_length=..., center=..., pad_mode=...,
+    detrend=...) does -- the (re, im) of every bin are the same words -- and |Y|^2 summed over the frames in the same kernel, so the
+    (B, F, K) spectrum never reaches memory.  Returns float32 (K,) or (B, K), K = n_fft // 2 + 1, with welch_fft()'s scale, doubling
+    rule and order of the sums (chunks of 16 frames, blocks of 256, the blocks): P does not depend on B or the plan; for F <= 16
+    frames it is welch_psd(stft_mixed(...), scale, nfft=n_fft) bit for bit, for more frames within one float32 ulp of it.  A
+    power-of-two n_fft raises ValueError (welch_fft transforms it), complex x too (welch_fft_iq).  `out` and `workspace`
+    (B.welch_mfft_workspace_bytes(...) // 8 float64 elements) as welch_fft(): with both given the call neither allocates nor
+    synchronises and can be captured with no warm call."""
+    torch = _torch()
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise ValueError("x must be a float32 CUDA tensor")
+    return _welch_fft_psd(torch, params, x, n_fft, hop, scale, win_length, center, pad_mode, detrend, onesided_doubling, shift, out,
+                          workspace, x.device.index, None, "mfft")
+
+
+def welch_fused_mixed(params, x, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", scaling="density", shift=None,
+                      out=None, workspace=None):
+    """welch_fused() at a mixed-radix nfft (bhw_welch_mfft_f32_device): scipy.signal.welch's segments, their FFT at nfft = 400, 1000,
+    4000 ... unpadded, and the average over them in ONE kernel and a small join.  The arguments, their checks, the window sums
+    cache, the scale and the SHARED read-only `freqs` are welch_fused()'s (the axes are kept under keys of their own kind, so neither
+    call evicts the other's); the result is the one-sided estimate (freqs float64, Pxx float32 (..., K)).  The sum over the frames
+    has the order of welch_fft_mixed().  A power-of-two nfft raises ValueError (welch_fused), complex x too (welch_fused_iq).  After
+    one warm call, with `out` and `workspace` given, it neither synchronises nor allocates and can be captured
+    (ResidentTable.welch_fused_mixed); a first call inside a capture raises."""
+    torch = _torch()
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise ValueError("x must be a float32 CUDA tensor")
+    return _welch_fused(torch, params, x, fs, length, noverlap, nfft, detrend, scaling, shift, out, workspace, x.device.index, None,
+                        _SUMS_CACHE, "mfft")
 
 
 # ---- fused Welch PSD for I/Q input: window, complex FFT and the frame average in one kernel ------------------------------------------------
@@ -1920,6 +1977,20 @@ class ResidentTable:
         captured into a graph, a first call inside a capture raises."""
         return _welch_fused(_torch(), params, x, fs, length, noverlap, nfft, detrend, scaling, shift, out, workspace, self.device,
                             self._live(), self._sums)
+
+    def welch_fft_mixed(self, params, x, n_fft, hop, scale, *, win_length=None, center=False, pad_mode="reflect", detrend=False,
+                        onesided_doubling=True, shift=None, out=None, workspace=None):
+        """welch_fft_mixed() with the coefficients gathered from this table (bhw_welch_mfft_f32_from_table): no allocation by the
+        library, no synchronisation, capturable on its first call; the bits are those of the library form."""
+        return _welch_fft_psd(_torch(), params, x, n_fft, hop, scale, win_length, center, pad_mode, detrend, onesided_doubling, shift,
+                              out, workspace, self.device, self._live(), "mfft")
+
+    def welch_fused_mixed(self, params, x, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", scaling="density",
+                          shift=None, out=None, workspace=None):
+        """welch_fused_mixed() from this table.  The sums cache and the capture rule are welch()'s: after one warm call the call can
+        be captured into a graph, a first call inside a capture raises."""
+        return _welch_fused(_torch(), params, x, fs, length, noverlap, nfft, detrend, scaling, shift, out, workspace, self.device,
+                            self._live(), self._sums, "mfft")
 
     def welch_fft_iq(self, params, x, n_fft, hop, scale, *, win_length=None, center=False, pad_mode="reflect", detrend=False,
                      shift=None, fftshift=False, out=None, workspace=None):

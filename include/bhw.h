@@ -1052,8 +1052,8 @@ int bhw_describe_istft_cfft(bhw_table t, const bhw_params *p, uint64_t length, c
  *     table) the key match.
  *   - Capture: as bhw_stft_fft_f32_*.  The library form needs no bhw_prepare_device; the from-table form is capturable on its first
  *     call.
- *   - Not built: cross spectra accumulated in the kernel; the mixed-radix kernel with this epilogue (I/Q input has it:
- *     bhw_welch_cfft_f32_* below); max-hold or median averaging; a filter bank on the averaged powers.
+ *   - Not built: cross spectra accumulated in the kernel; max-hold or median averaging; a filter bank on the averaged powers.  (I/Q
+ *     input and the mixed-radix n_fft have this epilogue: bhw_welch_cfft_f32_* and bhw_welch_mfft_f32_* below.)
  *   - bhw_describe_welch_fft: bhw_describe_stft_fft's line in the same words, plus the chunk, the runs, the groups per run, the
  *     accumulators per lane and the workspace bytes.  t may be NULL (the library call).  Host arithmetic only. */
 /* Why 16: the frames of ONE signal are the only parallelism a long record has.  16 381 frames of one signal (2^24 samples, n_fft 4096,
@@ -1103,7 +1103,7 @@ int bhw_describe_welch_fft(bhw_table t, const bhw_params *p, uint64_t length, co
  *     d_x or each other; and (from a table) the key match.
  *   - Capture: as bhw_stft_cfft_f32_*.  The library form needs no bhw_prepare_device; the from-table form is capturable on its first
  *     call.
- *   - Not built: the mixed-radix kernel under this epilogue; max-hold or median traces; n_fft 4096; cross spectra accumulated in the
+ *   - Not built: I/Q input at the mixed-radix lengths; max-hold or median traces; n_fft 4096; cross spectra accumulated in the
  *     kernel; a filter bank on the averaged powers.
  *   - bhw_describe_welch_cfft: bhw_describe_stft_cfft's line in the same words (without the output form), plus the fields
  *     bhw_describe_welch_fft adds.  t may be NULL (the library call).  Host arithmetic only. */
@@ -1113,6 +1113,55 @@ int bhw_welch_cfft_f32_device(const bhw_params *p, uint64_t length, int device, 
 int bhw_welch_cfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
                                   double scale, const float *d_x, float *d_P, uint64_t p_stride, void *workspace, uint64_t workspace_bytes);
 int bhw_describe_welch_cfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf, uint64_t len);
+
+/* Fused Welch PSD at a mixed-radix n_fft (400, 480, 1000, 4000 ...): window, mixed-radix real FFT and the average over the frames by
+ * ONE kernel and the join of bhw_welch_fft_f32_*.  The rows of bhw_stft_mfft_f32_* are formed and transformed by the same kernel body,
+ * and |Y|^2 is accumulated over the frames where the transform ends, so the (B, F, K) spectrum that bhw_stft_mfft_f32_* +
+ * bhw_welch_psd_f32 write and read back never exists.  The argument list is bhw_welch_fft_f32_*'s, word for word; the estimate is
+ * one-sided, so psd_flags and the doubling rule are that call's.
+ *   - Inputs: (p, length, s, flags) exactly as bhw_stft_mfft_f32_* takes them (channels 1; the padding fields of s as that call
+ *     accepts them), except that flags is 0 or BHW_WELCH_DETREND_CONSTANT -- BHW_MFFT_POWER is refused, and there is no filter-bank
+ *     argument -- and s->y_stride and s->y_batch_stride must be 0: no spectrum is written.  scale and psd_flags (0 or
+ *     BHW_PSD_ONESIDED) are bhw_psd's; d_P is float32 (B, K), K = n_fft / 2 + 1, row b at b * p_stride floats (0 = K).
+ *   - Row and transform: those of bhw_stft_mfft_f32_* for the same (p, length, s) and the detrend flag.  Let (re, im) be the float32
+ *     pair that call writes for bin k <= M = n_fft / 2 of row (b, f), bit for bit: the same words, from the same row function and
+ *     the same split expression.
+ *   - The sums, with q_f = (double) re * (double) re + (double) im * (double) im, are those of bhw_welch_fft_f32_* above:
+ *        A_chunk = sum of q_f over the frames of one chunk of BHW_WELCH_FFT_CHUNK = 16, in ascending f, binary64 from +0.0
+ *        A_blk   = sum of A_chunk over the 16 chunks of one block of BHW_WELCH_BLOCK = 256 frames, ascending, binary64 from +0.0
+ *        A       = sum of A_blk over the blocks, ascending, binary64 from +0.0
+ *        d_P[b * p_stride + k] = fl32(A * s_k),    s_k = scale * (doubled(k) ? 2 : 1)      (doubled: bhw_welch_psd_f32's rule)
+ *     (the last chunk and the last block may be shorter).
+ *   - Consequences: the bits of P depend on the window, n_fft, the flags, scale and the signal's samples only -- not on B, the grid,
+ *     or library versus table.  For F <= 16 P equals bhw_welch_psd_f32 of bhw_stft_mfft_f32_*'s rows bit for bit; beyond 16 frames it
+ *     lies within one float32 ulp of that route, by the argument given for bhw_welch_fft_f32_*.  There are no float atomics: every
+ *     chunk sum is stored plainly once.
+ *   - Workspace: caller-provided, 8-byte aligned, bhw_welch_mfft_workspace_bytes(s) bytes: the chunk sums, B * ceil(F / 16) * K
+ *     doubles, followed, when F > 256, by the block sums, B * ceil(F / 256) * K doubles.  A short one is BHW_ERR_WORKSPACE.  No call
+ *     allocates.
+ *   - Supported: exactly the set of bhw_stft_mfft_f32_* (channels 1, n_fft an even 2^a 3^b 5^c in 16..4095 that is no power of two);
+ *     channels 2, a power of two and every other n_fft are BHW_ERR_UNSUPPORTED with that call's words.
+ *   - IEEE: a NaN or an infinity in x reaches only the bins of its own signal.  Zeros in give +0.0 out (for a scale >= 0).
+ *   - Checks before any HIP call, in this order (BHW_ERR_BADARG unless noted): everything bhw_stft_mfft_f32_* checks on the
+ *     descriptor (with the y strides taken as packed and no bank), an unknown flag among them, with that call's code and words;
+ *     BHW_MFFT_POWER set, non-zero y strides, unknown psd_flags, a scale that is not finite; frames 0 returns BHW_OK here with the
+ *     pointers unchecked; p_stride below K; B * ceil(F / 16) * K above 2^34; NULL d_x or d_P, either not 4-byte aligned, a NULL or
+ *     misaligned workspace; a short one (BHW_ERR_WORKSPACE); d_P or the workspace overlapping d_x or each other; and (from a table)
+ *     the key match.
+ *   - Capture: as bhw_stft_mfft_f32_*.  The library form needs no bhw_prepare_device; the from-table form is capturable on its first
+ *     call.
+ *   - Not built: I/Q input at these lengths; odd n_fft and factors >= 7; cross spectra accumulated in the kernel; max-hold or median
+ *     traces.
+ *   - bhw_describe_welch_mfft: bhw_describe_stft_mfft's line in the same words (without the output form), plus the fields
+ *     bhw_describe_welch_fft adds.  t may be NULL (the library call).  Host arithmetic only. */
+uint64_t bhw_welch_mfft_workspace_bytes(const bhw_stft *s);
+int bhw_welch_mfft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                              double scale, uint32_t psd_flags, const float *d_x, float *d_P, uint64_t p_stride, void *workspace,
+                              uint64_t workspace_bytes);
+int bhw_welch_mfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                  double scale, uint32_t psd_flags, const float *d_x, float *d_P, uint64_t p_stride, void *workspace,
+                                  uint64_t workspace_bytes);
+int bhw_describe_welch_mfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf, uint64_t len);
 
 /* Threading: every entry point may be called from any host thread.  Calls that use the library-owned scratch of one
  * (device, stream) are serialised against each other for the duration of their launches (the table is rebuilt per call);
