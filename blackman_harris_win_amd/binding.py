@@ -52,6 +52,7 @@ ABI_SYMBOLS = (
     "bhw_stft_cfft_f32_device", "bhw_stft_cfft_f32_from_table", "bhw_describe_stft_cfft",
     "bhw_istft_cfft_f32_device", "bhw_istft_cfft_f32_from_table", "bhw_describe_istft_cfft",
     "bhw_welch_fft_workspace_bytes", "bhw_welch_fft_f32_device", "bhw_welch_fft_f32_from_table", "bhw_describe_welch_fft",
+    "bhw_csd_fft_workspace_bytes", "bhw_csd_fft_f32_device", "bhw_csd_fft_f32_from_table", "bhw_describe_csd_fft",
     "bhw_welch_cfft_workspace_bytes", "bhw_welch_cfft_f32_device", "bhw_welch_cfft_f32_from_table", "bhw_describe_welch_cfft",
     "bhw_welch_mfft_workspace_bytes", "bhw_welch_mfft_f32_device", "bhw_welch_mfft_f32_from_table", "bhw_describe_welch_mfft",
 )
@@ -341,6 +342,11 @@ def lib():
     L.bhw_welch_fft_f32_device.argtypes = [P, u64, ci, vp, S, u32, f64, u32, f32p, f32p, u64, vp, u64]
     L.bhw_welch_fft_f32_from_table.argtypes = [T, P, u64, vp, S, u32, f64, u32, f32p, f32p, u64, vp, u64]
     L.bhw_describe_welch_fft.argtypes = [T, P, u64, S, u32, ctypes.c_char_p, u64]
+    L.bhw_csd_fft_workspace_bytes.restype = u64
+    L.bhw_csd_fft_workspace_bytes.argtypes = [S]
+    L.bhw_csd_fft_f32_device.argtypes = [P, u64, ci, vp, S, u32, f64, u32, f32p, f32p, f32p, f32p, f32p, f32p, f32p, u64, vp, u64]
+    L.bhw_csd_fft_f32_from_table.argtypes = [T, P, u64, vp, S, u32, f64, u32, f32p, f32p, f32p, f32p, f32p, f32p, f32p, u64, vp, u64]
+    L.bhw_describe_csd_fft.argtypes = [T, P, u64, S, u32, u32, ctypes.c_char_p, u64]
     L.bhw_welch_cfft_workspace_bytes.restype = u64
     L.bhw_welch_cfft_workspace_bytes.argtypes = [S]
     L.bhw_welch_cfft_f32_device.argtypes = [P, u64, ci, vp, S, u32, f64, f32p, f32p, u64, vp, u64]
@@ -522,6 +528,24 @@ def describe_welch_fft(params, length, stft, *, detrend=False, table=None):
     buf = ctypes.create_string_buffer(1280)
     check(lib().bhw_describe_welch_fft(table, ctypes.byref(params), int(length), ctypes.byref(stft),
                                        WELCH_DETREND_CONSTANT if detrend else 0, buf, len(buf)))
+    return buf.value.decode()
+
+
+def csd_fft_workspace_bytes(stft):
+    """The bytes of workspace a fused cross-spectra call of the descriptor `stft` (a BhwStft, make_stft, y strides 0) needs: four times
+    welch_fft_workspace_bytes(stft), the chunk and block sums of the four chains (bhw_csd_fft_workspace_bytes)."""
+    return int(lib().bhw_csd_fft_workspace_bytes(ctypes.byref(stft)))
+
+
+def describe_csd_fft(params, length, stft, *, detrend=False, outputs=("pxy",), onesided=True, broadcast_x=False, table=None):
+    """One line: the plan fields of describe_welch_fft in the same words for the pair plan of a fused cross-spectra call (frames of x
+    and of y side by side, at most 128 lanes per row), plus the frame pairs per group, the outputs and the chains, over the window of
+    `length` with the descriptor `stft` (a BhwStft, make_stft, y strides 0) (bhw_describe_csd_fft).  `table` is a resident table
+    handle or None for the library call.  Host arithmetic only."""
+    buf = ctypes.create_string_buffer(1536)
+    flags = csd_mask(outputs) | (CSD_ONESIDED if onesided else 0) | (CSD_BROADCAST_X if broadcast_x else 0)
+    check(lib().bhw_describe_csd_fft(table, ctypes.byref(params), int(length), ctypes.byref(stft),
+                                     WELCH_DETREND_CONSTANT if detrend else 0, flags, buf, len(buf)))
     return buf.value.decode()
 
 

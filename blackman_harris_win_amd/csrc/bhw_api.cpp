@@ -1182,6 +1182,23 @@ int welch_fft_run(bhw_table t, const bhw_params *p, uint64_t length, int device,
     });
 }
 
+// The fused Welch cross spectra (t NULL: the direct CORDIC chains): the checks, then the accumulating kernel and its join.
+int csd_fft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *s, uint32_t flags, double scale,
+                uint32_t csd_flags, const float *d_x, const float *d_y, float *const *outs, uint64_t o_stride, void *workspace,
+                uint64_t workspace_bytes)
+{
+    int rc = bhwp_csd_fft_checks(p, length, s, flags, scale, csd_flags, o_stride, d_x, d_y, (const void *const *)outs, workspace,
+                                 workspace_bytes);
+    if (!rc && t) rc = table_call_checks(t, p);
+    if (rc || !s->frames) return rc;
+    const BhwCsdFftPlan pl = bhwp_csd_fft_plan(p, length, s, flags, csd_flags, o_stride, t != nullptr);
+    const char *what = t ? "csd fft launch (resident table)" : "csd fft launch";
+    return run_source(t, p, length, device, stream, what, [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *tab,
+                                                              const BhwLenPhase *lp) {
+        return bhwk_csd_fft_f32(l, c, w, pl, s, scale, d_x, d_y, outs, (double *)workspace, tab, *lp);
+    });
+}
+
 // The fused Welch PSD for I/Q input (t NULL: the direct CORDIC chains): the checks, then the accumulating kernel and the join.
 int welch_cfft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *s, uint32_t flags,
                    double scale, const float *d_x, float *d_P, uint64_t p_stride, void *workspace, uint64_t workspace_bytes)
@@ -1517,6 +1534,41 @@ int bhw_describe_welch_fft(bhw_table t, const bhw_params *p, uint64_t length, co
     int rc = bhwp_welch_fft_checks(p, length, s, flags, 0.0, 0, 0, nullptr, nullptr, nullptr, 0, false);
     if (!rc && t) rc = table_call_checks(t, p);
     return rc ? rc : bhwp_describe_welch_fft(p, t ? &t->c : nullptr, length, s, flags, buf, len);
+}
+
+// ---- fused Welch cross spectra (include/bhw.h: bhw_csd_fft_f32_device ...) ------------------------------------------------------------------
+
+uint64_t bhw_csd_fft_workspace_bytes(const bhw_stft *s)
+{
+    return s && s->struct_size == sizeof(bhw_stft) ? bhwp_csd_fft_workspace_bytes(s) : 0;
+}
+
+int bhw_csd_fft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                           double scale, uint32_t csd_flags, const float *d_x, const float *d_y, float *d_Pxy, float *d_Pxx, float *d_Pyy,
+                           float *d_Cxy, float *d_H1, uint64_t o_stride, void *workspace, uint64_t workspace_bytes)
+{
+    float *const outs[kCsdOutputs] = {d_Pxy, d_Pxx, d_Pyy, d_Cxy, d_H1};
+    return csd_fft_run(nullptr, p, length, device, hip_stream, s, flags, scale, csd_flags, d_x, d_y, outs, o_stride, workspace, workspace_bytes);
+}
+
+int bhw_csd_fft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                               double scale, uint32_t csd_flags, const float *d_x, const float *d_y, float *d_Pxy, float *d_Pxx,
+                               float *d_Pyy, float *d_Cxy, float *d_H1, uint64_t o_stride, void *workspace, uint64_t workspace_bytes)
+{
+    float *const outs[kCsdOutputs] = {d_Pxy, d_Pxx, d_Pyy, d_Cxy, d_H1};
+    const int rc = bhwp_csd_fft_checks(p, length, s, flags, scale, csd_flags, o_stride, d_x, d_y, (const void *const *)outs, workspace,
+                                       workspace_bytes);
+    if (rc) return rc;
+    return t ? csd_fft_run(t, p, length, t->device, hip_stream, s, flags, scale, csd_flags, d_x, d_y, outs, o_stride, workspace, workspace_bytes)
+             : fail(BHW_ERR_BADARG, "table is NULL");
+}
+
+int bhw_describe_csd_fft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, uint32_t csd_flags, char *buf,
+                         uint64_t len)
+{
+    int rc = bhwp_csd_fft_checks(p, length, s, flags, 0.0, csd_flags, 0, nullptr, nullptr, nullptr, nullptr, 0, false);
+    if (!rc && t) rc = table_call_checks(t, p);
+    return rc ? rc : bhwp_describe_csd_fft(p, t ? &t->c : nullptr, length, s, flags, csd_flags, buf, len);
 }
 
 // ---- fused Welch PSD for I/Q input (include/bhw.h: bhw_welch_cfft_f32_device ...) -----------------------------------------------------------

@@ -129,3 +129,7 @@ int bhwk_taylor_sincos(const BhwLaunch &l, const BhwTaylorCfg &t, uint64_t theta
 // include/bhw.h.  psd_flags: bhw_psd's, for the doubling of a one-sided row of bins = n_fft / 2 + 1; 0 for bins = n_fft.
 int bhwk_welch_join(const BhwLaunch &l, double *d_ws, float *d_P, uint64_t batch, uint64_t bins, uint64_t n_fft, uint64_t chunks,
                     uint64_t blocks, uint64_t blocks_grid, uint64_t join_grid, uint64_t p_stride, double scale, uint32_t psd_flags);
+// The first stage of that join alone, for bhw_csd_fft.hip: the chunk sums of every block of BHW_WELCH_BLOCK frames, blocks > 1, added by
+// k_welch_fft_join<true, false> into the block sums behind them.  The four chains of a cross spectrum are part of the bin axis there.
+int bhwk_welch_join_blocks(const BhwLaunch &l, double *d_ws, uint64_t batch, uint64_t bins, uint64_t chunks, uint64_t blocks,
+                           uint64_t blocks_grid);

@@ -1419,12 +1419,48 @@ static int csd_operand(const char *name, uint64_t B, uint64_t F, uint64_t K, uin
     return BHW_OK;
 }
 
-int bhwp_csd_checks(const bhw_csd *d, const void *d_X, const void *d_Y, const void *const *outs, const void *workspace,
-                    uint64_t workspace_bytes, bool pointers)
+// The byte ranges a cross-spectra call touches (bhwp_csd_checks, bhwp_csd_fft_checks): the two operands first, then the requested
+// outputs, then the workspace.
+struct CsdRanges {
+    uint64_t lo[kCsdOutputs + 3], nb[kCsdOutputs + 3];
+    const char *what[kCsdOutputs + 3];
+    uint32_t n = 0;
+    void add(uint64_t a, uint64_t bytes, const char *name) { lo[n] = a, nb[n] = bytes, what[n++] = name; }
+};
+
+// the requested outputs of the mask: each present and aligned to its element; oe = the extent of an output in elements
+static int csd_output_ranges(uint32_t flags, const void *const *outs, uint64_t oe, CsdRanges &r)
 {
     static const char *const names[kCsdOutputs] = {"d_Pxy", "d_Pxx", "d_Pyy", "d_Cxy", "d_H1"};
     static const uint32_t bits[kCsdOutputs] = {BHW_CSD_PXY, BHW_CSD_PXX, BHW_CSD_PYY, BHW_CSD_COHERENCE, BHW_CSD_H1};
     static const uint32_t width[kCsdOutputs] = {8, 4, 4, 4, 8};
+    for (uint32_t i = 0; i < kCsdOutputs; ++i) {
+        if (!(flags & bits[i])) continue;
+        const void *o = outs ? outs[i] : nullptr;
+        if (!o) return bhwp_fail(BHW_ERR_BADARG, "%s is NULL and its output is requested", names[i]);
+        if ((uintptr_t)o % width[i]) return bhwp_fail(BHW_ERR_BADARG, "%s is not %u-byte aligned", names[i], width[i]);
+        r.add((uint64_t)(uintptr_t)o, oe * width[i], names[i]);
+    }
+    return BHW_OK;
+}
+
+// no range wraps; nothing written overlaps anything (the two operands are only read: they may coincide)
+static int csd_overlaps(const CsdRanges &r, bool has_ws)
+{
+    for (uint32_t i = 0; i < r.n; ++i)
+        if (r.lo[i] > UINT64_MAX - r.nb[i]) return bhwp_fail(BHW_ERR_BADARG, "%s range wraps the address space", r.what[i]);
+    for (uint32_t i = 2; i < r.n; ++i)
+        for (uint32_t j = 0; j < i; ++j)
+            if (r.lo[i] < r.lo[j] + r.nb[j] && r.lo[j] < r.lo[i] + r.nb[i]) {
+                if (i == r.n - 1 && has_ws) return bhwp_fail(BHW_ERR_BADARG, "workspace overlaps %s", r.what[j]);
+                return bhwp_fail(BHW_ERR_BADARG, "%s and %s overlap", r.what[j], r.what[i]);
+            }
+    return BHW_OK;
+}
+
+int bhwp_csd_checks(const bhw_csd *d, const void *d_X, const void *d_Y, const void *const *outs, const void *workspace,
+                    uint64_t workspace_bytes, bool pointers)
+{
     if (!d) return bhwp_fail(BHW_ERR_BADARG, "csd descriptor is NULL");
     if (d->struct_size != sizeof(bhw_csd)) return bhwp_fail(BHW_ERR_BADARG, "bhw_csd.struct_size %u != %zu", d->struct_size, sizeof(bhw_csd));
     if (d->reserved) return bhwp_fail(BHW_ERR_BADARG, "bhw_csd.reserved is not 0");
@@ -1457,18 +1493,10 @@ int bhwp_csd_checks(const bhw_csd *d, const void *d_X, const void *d_Y, const vo
     if (!d_X || !d_Y) return bhwp_fail(BHW_ERR_BADARG, "d_X / d_Y is NULL");
     if ((uintptr_t)d_X % 8 || (uintptr_t)d_Y % 8) return bhwp_fail(BHW_ERR_BADARG, "d_X / d_Y is not 8-byte aligned");
     // the byte ranges the call touches: X, Y, the requested outputs, the workspace
-    uint64_t lo[kCsdOutputs + 3], nb[kCsdOutputs + 3];
-    const char *what[kCsdOutputs + 3];
-    uint32_t n = 0;
-    lo[n] = (uint64_t)(uintptr_t)d_X, nb[n] = xe * 8u, what[n++] = "d_X";
-    lo[n] = (uint64_t)(uintptr_t)d_Y, nb[n] = ye * 8u, what[n++] = "d_Y";
-    for (uint32_t i = 0; i < kCsdOutputs; ++i) {
-        if (!(d->flags & bits[i])) continue;
-        const void *o = outs ? outs[i] : nullptr;
-        if (!o) return bhwp_fail(BHW_ERR_BADARG, "%s is NULL and its output is requested", names[i]);
-        if ((uintptr_t)o % width[i]) return bhwp_fail(BHW_ERR_BADARG, "%s is not %u-byte aligned", names[i], width[i]);
-        lo[n] = (uint64_t)(uintptr_t)o, nb[n] = (uint64_t)oe * width[i], what[n++] = names[i];
-    }
+    CsdRanges r;
+    r.add((uint64_t)(uintptr_t)d_X, xe * 8u, "d_X");
+    r.add((uint64_t)(uintptr_t)d_Y, ye * 8u, "d_Y");
+    if (int rc = csd_output_ranges(d->flags, outs, (uint64_t)oe, r)) return rc;
     const uint32_t chains = (d->flags & kCsdOutputMask) == BHW_CSD_PXY ? 2u : 4u;
     const uint64_t need = blocks > 1 ? B * blocks * K * chains * 8u : 0;             // below 2^34 / 256 * 32 + ...: no overflow
     if (need) {
@@ -1478,17 +1506,9 @@ int bhwp_csd_checks(const bhw_csd *d, const void *d_X, const void *d_Y, const vo
         if (workspace_bytes < need)
             return bhwp_fail(BHW_ERR_WORKSPACE, "workspace of %llu bytes, the block sums need %llu", (unsigned long long)workspace_bytes,
                              (unsigned long long)need);
-        lo[n] = (uint64_t)(uintptr_t)workspace, nb[n] = need, what[n++] = "workspace";
+        r.add((uint64_t)(uintptr_t)workspace, need, "workspace");
     }
-    for (uint32_t i = 0; i < n; ++i)
-        if (lo[i] > UINT64_MAX - nb[i]) return bhwp_fail(BHW_ERR_BADARG, "%s range wraps the address space", what[i]);
-    for (uint32_t i = 2; i < n; ++i)                                                  // X and Y are only read: they may coincide
-        for (uint32_t j = 0; j < i; ++j)
-            if (lo[i] < lo[j] + nb[j] && lo[j] < lo[i] + nb[i]) {
-                if (i == n - 1 && need) return bhwp_fail(BHW_ERR_BADARG, "workspace overlaps %s", what[j]);
-                return bhwp_fail(BHW_ERR_BADARG, "%s and %s overlap", what[j], what[i]);
-            }
-    return BHW_OK;
+    return csd_overlaps(r, need != 0);
 }
 
 int bhwp_describe_csd(const bhw_csd *d, char *buf, uint64_t len)
@@ -1851,6 +1871,158 @@ int bhwp_describe_welch_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64_
              (unsigned long long)wp.runs, (unsigned long long)wp.run, wp.gpr, wp.gpr == 1 ? "" : "s", wp.acc, wp.acc == 1 ? "" : "s",
              (unsigned long long)wp.chunks, (unsigned long long)wp.blocks, wp.blocks == 1 ? "" : "s",
              wp.blocks == 1 ? "once (chunks)" : "twice (chunks, blocks)", (unsigned long long)wp.ws_bytes);
+    return BHW_OK;
+}
+
+// ---- fused Welch cross spectra ----------------------------------------------------------------------------------------------------------------
+
+uint64_t bhwp_csd_fft_workspace_bytes(const bhw_stft *s)
+{
+    if (!s || !s->frames || !s->batch) return 0;
+    return bhwp_welch_runs(s->batch, s->frames, 1, kCsdFftChains * (s->n_fft / 2 + 1)).ws_bytes;   // four chains on the bin axis
+}
+
+int bhwp_csd_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, double scale, uint32_t csd_flags,
+                        uint64_t o_stride, const void *d_x, const void *d_y, const void *const *outs, const void *workspace,
+                        uint64_t workspace_bytes, bool pointers)
+{
+    // the descriptor: bhwp_welch_fft_checks' in its order, with the routes that take what this call refuses named
+    bhw_stft t{};
+    const bool sized = s && s->struct_size == sizeof(bhw_stft);
+    if (sized) {
+        t = *s;
+        t.y_stride = t.y_batch_stride = 0;
+    }
+    // the params first, as every fused call has them first: their refusals (the source, the model, phi_width) keep their words
+    int rc = bhwp_f32_checks(p, length, 0);
+    if (rc) return rc;
+    rc = bhwp_stft_fft_checks(p, length, sized ? &t : s, flags, nullptr, nullptr, false);
+    const bool pow2 = sized && s->n_fft && !(s->n_fft & (s->n_fft - 1)) && s->n_fft >= (1ull << kFftMinLog) && s->n_fft <= (1ull << kFftMaxLog);
+    if (rc == BHW_ERR_UNSUPPORTED && sized && (s->channels != 1 || !pow2)) {           // the two refusals this call renames
+        if (s->channels != 1)
+            return bhwp_fail(BHW_ERR_UNSUPPORTED, "channels %u: the fused cross spectra take real input (1); for I/Q input use "
+                             "bhw_stft_cfft_f32_* + bhw_welch_csd_f32", s->channels);
+        if (bhwp_mfft_supported(s->n_fft))
+            return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu: the fused cross spectra take a power of two in %u..%u; for a mixed-radix "
+                             "n_fft use bhw_stft_mfft_f32_* + bhw_welch_csd_f32", (unsigned long long)s->n_fft, 1u << kFftMinLog,
+                             1u << kCsdFftMaxLog);
+        return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu: the fused cross spectra take a power of two in %u..%u",
+                         (unsigned long long)s->n_fft, 1u << kFftMinLog, 1u << kCsdFftMaxLog);
+    }
+    if (rc) return rc;
+    if (s->n_fft > (1ull << kCsdFftMaxLog))
+        return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu: the fused cross spectra take a power of two in %u..%u (two operands side by "
+                         "side); use bhw_stft_fft_f32_* + bhw_welch_csd_f32", (unsigned long long)s->n_fft, 1u << kFftMinLog,
+                         1u << kCsdFftMaxLog);
+    if (s->y_stride || s->y_batch_stride)
+        return bhwp_fail(BHW_ERR_BADARG, "y_stride %llu, y_batch_stride %llu: no spectrum is written, both must be 0",
+                         (unsigned long long)s->y_stride, (unsigned long long)s->y_batch_stride);
+    if (csd_flags & ~(BHW_CSD_ONESIDED | BHW_CSD_BROADCAST_X | kCsdOutputMask))
+        return bhwp_fail(BHW_ERR_BADARG, "flags 0x%x (BHW_CSD_ONESIDED, BHW_CSD_BROADCAST_X and the output mask 0x%x)", csd_flags, kCsdOutputMask);
+    if (!(csd_flags & kCsdOutputMask)) return bhwp_fail(BHW_ERR_BADARG, "flags 0x%x: the output mask is empty", csd_flags);
+    if (!(scale - scale == 0.0)) return bhwp_fail(BHW_ERR_BADARG, "scale is not finite");
+    const uint64_t T = s->samples, F = s->frames, K = s->n_fft / 2 + 1, B = s->batch;
+    if (!F) return BHW_OK;
+    if (o_stride && o_stride < K)
+        return bhwp_fail(BHW_ERR_BADARG, "o_stride %llu < bins %llu: rows overlap", (unsigned long long)o_stride, (unsigned long long)K);
+    const uint64_t chunks = (F - 1) / BHW_WELCH_FFT_CHUNK + 1;
+    if ((unsigned __int128)B * chunks * K * kCsdFftChains > (1ull << 34))
+        return bhwp_fail(BHW_ERR_BADARG, "batch * ceil(frames / %u) * 4 K above 2^34 per call", BHW_WELCH_FFT_CHUNK);
+    if (!pointers) return BHW_OK;
+    if (!d_x || !d_y) return bhwp_fail(BHW_ERR_BADARG, "d_x / d_y is NULL");
+    if ((uintptr_t)d_x % 4 || (uintptr_t)d_y % 4) return bhwp_fail(BHW_ERR_BADARG, "d_x / d_y is not 4-byte aligned");
+    const bool bcast = (csd_flags & BHW_CSD_BROADCAST_X) != 0;
+    const uint64_t xs = s->x_stride ? s->x_stride : T;
+    const unsigned __int128 ye = (unsigned __int128)(B - 1) * xs + T, xe = bcast ? (unsigned __int128)T : ye;
+    const unsigned __int128 oe = (unsigned __int128)(B - 1) * (o_stride ? o_stride : K) + K;
+    if (ye > (1ull << 58) || oe > (1ull << 58)) return bhwp_fail(BHW_ERR_BADARG, "x, y or output extent beyond 2^58 elements");
+    CsdRanges r;
+    r.add((uint64_t)(uintptr_t)d_x, (uint64_t)xe * 4u, "d_x");
+    r.add((uint64_t)(uintptr_t)d_y, (uint64_t)ye * 4u, "d_y");
+    if ((rc = csd_output_ranges(csd_flags, outs, (uint64_t)oe, r))) return rc;
+    const uint64_t need = bhwp_csd_fft_workspace_bytes(s);
+    if (!workspace) return bhwp_fail(BHW_ERR_BADARG, "workspace is NULL: the chunk sums need %llu bytes", (unsigned long long)need);
+    if ((uintptr_t)workspace % 8) return bhwp_fail(BHW_ERR_BADARG, "workspace is not 8-byte aligned");
+    if (workspace_bytes < need)
+        return bhwp_fail(BHW_ERR_WORKSPACE, "workspace of %llu bytes, the chunk and block sums need %llu", (unsigned long long)workspace_bytes,
+                         (unsigned long long)need);
+    r.add((uint64_t)(uintptr_t)workspace, need, "workspace");
+    return csd_overlaps(r, true);
+}
+
+BhwCsdFftPlan bhwp_csd_fft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, uint32_t csd_flags,
+                                uint64_t o_stride, bool from_table)
+{
+    BhwCsdFftPlan pl{};
+    bhw_stft t = *s;
+    t.y_stride = t.y_batch_stride = 0;
+    BhwStftFftPlan &f = pl.fft;
+    f = bhwp_stft_fft_plan(p, length, &t, flags, from_table);
+    f.y_stride = f.y_bstride = 0;
+    if (f.lpf > kCsdFftMaxLpf) {                                        // n_fft 2048: two slots of 128 lanes
+        f.lpf = kCsdFftMaxLpf;
+        f.fy = kFftBlock / f.lpf;
+        f.cpl = (uint32_t)(s->n_fft / f.lpf);
+        f.lds_bytes = 2u * f.fy * f.m * 8u + f.m * 8u + f.fy * 4u;
+    }
+    pl.bins = s->n_fft / 2 + 1;
+    pl.pairs = f.fy / 2u;
+    pl.flags = csd_flags;
+    const BhwWelchRuns r = bhwp_welch_runs(s->batch, s->frames, pl.pairs, kCsdFftChains * pl.bins);
+    pl.run = r.run;
+    pl.gpr = r.gpr;
+    pl.acc = pl.pairs >= BHW_WELCH_FFT_CHUNK ? 0u : (uint32_t)((pl.bins + kFftBlock - 1) / kFftBlock);
+    pl.fpad = r.fpad;
+    pl.chunks = r.chunks;
+    pl.blocks = r.blocks;
+    pl.runs = r.runs;
+    f.groups = r.groups;
+    f.grid = r.grid;
+    pl.blocks_grid = r.blocks > 1 ? r.blocks_grid : 0;
+    pl.out_grid = s->frames ? (s->batch * pl.bins + 255u) / 256u : 0;
+    pl.o_stride = o_stride ? o_stride : pl.bins;
+    pl.ws_bytes = r.ws_bytes;
+    return pl;
+}
+
+int bhwp_describe_csd_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags,
+                          uint32_t csd_flags, char *buf, uint64_t len)
+{
+    if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
+    const char *route = ct ? "table" : "direct";
+    const BhwCsdFftPlan cp = bhwp_csd_fft_plan(p, length, s, flags, csd_flags, 0, ct != nullptr);
+    const BhwStftFftPlan &pl = cp.fft;
+    const char *pad = s->pad_mode == BHW_PAD_REFLECT ? "reflect" : "constant";
+    const char *det = pl.detrend ? "constant detrend" : "no detrending";
+    if (!s->frames) {
+        snprintf(buf, len, "csd fft %s (L = %llu, n_fft %llu, %s): nothing (frames 0)", route, (unsigned long long)length,
+                 (unsigned long long)s->n_fft, det);
+        return BHW_OK;
+    }
+    char outs[64] = "";
+    static const char *const names[kCsdOutputs] = {"pxy", "pxx", "pyy", "coherence", "h1"};
+    static const uint32_t bits[kCsdOutputs] = {BHW_CSD_PXY, BHW_CSD_PXX, BHW_CSD_PYY, BHW_CSD_COHERENCE, BHW_CSD_H1};
+    for (uint32_t i = 0; i < kCsdOutputs; ++i)
+        if (csd_flags & bits[i]) {
+            if (outs[0]) strncat(outs, "+", sizeof outs - strlen(outs) - 1);
+            strncat(outs, names[i], sizeof outs - strlen(outs) - 1);
+        }
+    char kern[64], sched[48];
+    kernel_name(p, ct, "k_csd_fft_direct", "k_csd_fft_table", false, kern, sizeof kern);
+    bhwp_stft_fft_schedule(pl, sched, sizeof sched);
+    snprintf(buf, len, "csd fft %s (L = %llu, n_fft %llu, col0 %llu, pad %llu %s, %s): %s, %llu signals x %llu frames = %llu rows, "
+             "complex FFT of %u points in passes %s + split, %u lanes per row x %u rows per workgroup, %u columns per lane, %llu groups, "
+             "grid %llu x %u lanes, %u bytes of LDS; %u frame pair%s per group (x and y side by side%s), %s, %s; chunk %u frames, %llu runs "
+             "of %llu frames (%u group%s per run), %u accumulator%s per lane and chain, %u chains, %llu chunks and %llu block%s per "
+             "signal, then %s, workspace %llu bytes",
+             route, (unsigned long long)length, (unsigned long long)s->n_fft, (unsigned long long)s->col0, (unsigned long long)s->pad, pad,
+             det, kern, (unsigned long long)s->batch, (unsigned long long)s->frames, (unsigned long long)pl.rows, pl.m, sched, pl.lpf, pl.fy,
+             pl.cpl, (unsigned long long)pl.groups, (unsigned long long)pl.grid, kFftBlock, pl.lds_bytes, cp.pairs, cp.pairs == 1 ? "" : "s",
+             (csd_flags & BHW_CSD_BROADCAST_X) ? ", x broadcast" : "", (csd_flags & BHW_CSD_ONESIDED) ? "one-sided" : "two-sided", outs,
+             BHW_WELCH_FFT_CHUNK, (unsigned long long)cp.runs, (unsigned long long)cp.run, cp.gpr, cp.gpr == 1 ? "" : "s", cp.acc,
+             cp.acc == 1 ? "" : "s", kCsdFftChains, (unsigned long long)cp.chunks, (unsigned long long)cp.blocks, cp.blocks == 1 ? "" : "s",
+             cp.blocks == 1 ? "k_csd_fft_out once (chunks)" : "k_welch_fft_join (chunks) and k_csd_fft_out (blocks), twice",
+             (unsigned long long)cp.ws_bytes);
     return BHW_OK;
 }
 

@@ -527,6 +527,46 @@ int  bhwk_welch_fft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinC
                         double scale, uint32_t psd_flags, const float *d_x, float *d_P, double *d_ws, const int32_t *d_table,
                         const BhwLenPhase &lp);
 
+// ---- fused Welch cross spectra (bhw_csd_fft_f32_*; bhw_csd_fft.hip) -------------------------------------------------------------------
+// The forward kernel's row function with frames of x and of y side by side: of the fy slots of a group the first pairs = fy / 2 carry
+// the frames f0 .. f0 + pairs - 1 of x and the others the same frames of y, so fy >= 2: lpf = min(kCsdFftMaxLpf, max(4, M / 4)), and
+// n_fft 2048 runs as n_fft 4096 runs in the forward kernel (two butterflies per lane and pass, cpl 16, 40 KB of LDS).  Ownership is
+// bhwp_welch_runs' with `pairs` in place of fy: a run is max(16, pairs) frames of one pair of signals.  acc: the binary64
+// accumulators a lane carries over a run PER CHAIN (pairs < 16: ceil(K / kFftBlock), at most kCsdFftMaxAcc; else none); there are
+// always kCsdFftChains chains.  Workspace: the chain index is part of the bin axis, [(b * chunks + c) * 4 K + chain * K + k], then
+// (blocks > 1) the block sums likewise, so stage 1 of the join is k_welch_fft_join over 4 K bins.
+constexpr uint32_t kCsdFftMaxLpf = 128;
+constexpr uint32_t kCsdFftMaxLog = 11;                // n_fft <= 2048
+constexpr uint32_t kCsdFftChains = 4;                 // S_xx, S_yy, C_re, C_im
+constexpr uint32_t kCsdFftMaxAcc = 5;                 // ceil(1025 / 256)
+struct BhwCsdFftPlan {
+    BhwStftFftPlan fft;   // lpf, fy, cpl, lds_bytes as above; groups = B * fpad / pairs, grid = min(runs, kFftMaxGrid); rows = B * frames
+    uint64_t bins;        // K = n_fft / 2 + 1
+    uint32_t pairs;       // frame pairs side by side: fy / 2
+    uint32_t gpr;         // groups per run: run / pairs
+    uint64_t run;         // frames of a run: max(BHW_WELCH_FFT_CHUNK, pairs)
+    uint32_t acc;         // accumulators a lane carries per chain (0 for pairs >= 16)
+    uint32_t flags;       // the csd_flags
+    uint64_t fpad, chunks, blocks, runs;   // bhwp_welch_runs'
+    uint64_t blocks_grid; // workgroups of the launch that adds the chunks of a block, over 4 K bins (blocks > 1 only)
+    uint64_t out_grid;    // workgroups of the launch that adds the last level and writes the outputs
+    uint64_t o_stride;    // resolved
+    uint64_t ws_bytes;
+};
+// Every check of the two calls that needs no table handle, before any HIP call (include/bhw.h).  frames 0 passes with the pointers
+// unchecked; `pointers` false: the describe call.  outs: the five output pointers in the order of kCsdOutputs.
+int  bhwp_csd_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, double scale, uint32_t csd_flags,
+                         uint64_t o_stride, const void *d_x, const void *d_y, const void *const *outs, const void *workspace,
+                         uint64_t workspace_bytes, bool pointers = true);
+uint64_t bhwp_csd_fft_workspace_bytes(const bhw_stft *s);
+BhwCsdFftPlan bhwp_csd_fft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, uint32_t csd_flags,
+                                uint64_t o_stride, bool from_table);
+int  bhwp_describe_csd_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags,
+                           uint32_t csd_flags, char *buf, uint64_t len);
+int  bhwk_csd_fft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwCsdFftPlan &pl, const bhw_stft *s,
+                      double scale, const float *d_x, const float *d_y, float *const *outs, double *d_ws, const int32_t *d_table,
+                      const BhwLenPhase &lp);
+
 // ---- mixed-radix fused window and real FFT (bhw_stft_mfft_f32_*; bhw_stft_mfft.hip) -----------------------------------------------------
 // The forward kernel's layout for n_fft = 2^a 3^b 5^c that is even and NOT a power of two, 16 <= n_fft < 4096: M = n_fft / 2 complex
 // points per row, lpf = the smallest power of two >= M / 4 (clamped to 4 .. kFftBlock, so the slot of a lane stays a shift) lanes on a

@@ -1,7 +1,7 @@
 // bhw_stft_fft.h -- the body shared by the kernels that form a windowed row and transform it in LDS: bhw_stft_fft.hip (stores the
-// spectrum row), bhw_spectrogram.hip (stores its powers, or those folded through a filter bank) and bhw_welch_fft.hip (adds the
-// powers over the frames of a run: DESIGN.md section 26).  The row function is a template
-// on the epilogue -- what happens to the transformed row -- and everything before it is one text for both units.  Moving the body
+// spectrum row), bhw_spectrogram.hip (stores its powers, or those folded through a filter bank), bhw_welch_fft.hip (adds the
+// powers over the frames of a run: DESIGN.md section 26) and bhw_csd_fft.hip (two signals side by side: section 29).  The row
+// function is a template on the epilogue -- what happens to the transformed row -- and everything before it is one text for all.  Moving the body
 // here left the instruction streams of k_stft_fft_direct<*> and k_stft_fft_table<*> unchanged.
 //
 // A workgroup owns whole rows.  Prologue, once per workgroup: the window coefficients v[0..n_fft) (+0.0 outside the window) by the
@@ -100,6 +100,16 @@ struct fft_owns_runs : std::false_type {};
 template <class E>
 struct fft_owns_runs<E, std::void_t<decltype(E::kRuns)>> : std::true_type {};
 
+// An epilogue that owns runs and has a member kPairs as well takes frames of TWO signals side by side (bhw_csd_fft.hip, DESIGN.md
+// section 29): of the fy slots of a group the first pairs = fy / 2 carry the frames f0 .. f0 + pairs - 1 of signal b of a.x (signal 0
+// under epilogue.bcast: one x is paired with every y) and the others the same frames of signal b of epilogue.y, both at b *
+// a.x_stride.  fpad and gpr count frame PAIRS: group g begins at pair g * pairs of the padded axis.  The epilogue's call is the run
+// owner's; slot s of x is at base + s * M, of y at base + (pairs + s) * M.
+template <class E, class = void>
+struct fft_has_pairs : std::false_type {};
+template <class E>
+struct fft_has_pairs<E, std::void_t<decltype(E::kPairs)>> : std::true_type {};
+
 template <class E>
 __device__ __forceinline__ uint64_t fft_first_group(const E &e)
 {
@@ -157,7 +167,17 @@ __device__ __forceinline__ void stft_fft_rows(const FftIo &a, const Epilogue &ep
         bool live;
         uint64_t b, f;
         [[maybe_unused]] uint64_t f0 = 0;
-        if constexpr (fft_owns_runs<Epilogue>::value) {
+        [[maybe_unused]] bool second = false;
+        if constexpr (fft_has_pairs<Epilogue>::value) {
+            const uint32_t pairs = fy >> 1;
+            const uint64_t r0 = g * pairs;                               // fpad is a multiple of pairs: a group never crosses a signal
+            b = r0 / epilogue.fpad;
+            f0 = r0 - b * epilogue.fpad;
+            second = slot >= pairs;
+            const uint32_t fs = second ? slot - pairs : slot;
+            live = f0 + fs < a.frames;
+            f = live ? f0 + fs : 0;
+        } else if constexpr (fft_owns_runs<Epilogue>::value) {
             const uint64_t r0 = g * fy;                                  // fpad is a multiple of fy: a group never crosses a signal
             b = r0 / epilogue.fpad;
             f0 = r0 - b * epilogue.fpad;
@@ -169,7 +189,9 @@ __device__ __forceinline__ void stft_fft_rows(const FftIo &a, const Epilogue &ep
             b = live ? r / a.frames : 0;
             f = live ? r - b * a.frames : 0;
         }
-        const float *xb = a.x + b * a.x_stride;
+        const float *xb;
+        if constexpr (fft_has_pairs<Epilogue>::value) xb = second ? epilogue.y + b * a.x_stride : a.x + (epilogue.bcast ? 0u : b) * a.x_stride;
+        else                                          xb = a.x + b * a.x_stride;
         const uint64_t t0 = f * a.hop + l - a.pad;                     // the (wrapped) time of column l
         asm volatile("" : "+v"(cols), "+v"(wins));
         const uint32_t take = live ? wins : 0u;

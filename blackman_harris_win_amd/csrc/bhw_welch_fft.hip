@@ -272,3 +272,17 @@ int bhwk_welch_join(const BhwLaunch &l, double *d_ws, float *d_P, uint64_t batch
     }
     return finish(hipSuccess);
 }
+
+int bhwk_welch_join_blocks(const BhwLaunch &l, double *d_ws, uint64_t batch, uint64_t bins, uint64_t chunks, uint64_t blocks,
+                           uint64_t blocks_grid)
+{
+    WelchFftJoin j{};
+    j.in = d_ws;
+    j.out = d_ws + batch * chunks * bins;
+    j.batch = batch;
+    j.bins = bins;
+    j.n_in = chunks;
+    j.n_out = blocks;
+    launch(k_welch_fft_join<true, false>, dim3((unsigned)blocks_grid), dim3(256), (hipStream_t)l.stream, j);
+    return finish(hipSuccess);
+}

@@ -1738,6 +1738,201 @@ def transfer_function(params, x, y, fs=1.0, *, length, noverlap=None, nfft=None,
     return f, r["h1"]
 
 
+# ---- fused Welch cross spectra: window, FFT of x and of y and the four frame averages in one kernel ---------------------------------------
+
+CSD_FFT_MAX_N = 2048
+
+
+def _csd_fft_input(torch, x, y, n_fft, dev):
+    """The checks of the fused cross spectra on (x, y, n_fft); the refusals name the route that takes what this one does not."""
+    for t, what in ((x, "x"), (y, "y")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != dev:
+            raise ValueError(f"{what} must be a float32 CUDA tensor on the call's device")
+        if t.dtype != torch.float32:
+            raise ValueError(f"the fused cross spectra take real float32 input, got {t.dtype} for {what} (complex input: "
+                             "cross_spectra(fft='torch'), or stft_iq of x and of y + welch_csd)")
+    if x.dim() not in (1, 2) or y.dim() not in (1, 2):
+        raise ValueError("x and y must be (T,) or (B, T)")
+    if x.shape[-1] != y.shape[-1]:
+        raise ValueError(f"x and y must have the same length, got {x.shape[-1]} and {y.shape[-1]} (scipy zero-pads the shorter one; "
+                         "that is not built: pad or cut it yourself)")
+    if x.dim() == 2 and (y.dim() == 1 or x.shape[0] != y.shape[0]):
+        raise ValueError(f"x {tuple(x.shape)} against y {tuple(y.shape)}: x must be (T,) (paired with every signal of y) or have y's batch")
+    n = int(n_fft)
+    if B.mfft_supported(n):
+        raise ValueError(f"n_fft {n} is mixed-radix: the fused cross spectra take a power of two in {B.FFT_MIN_N}..{CSD_FFT_MAX_N} "
+                         "(stft_mixed of x and of y + welch_csd take it)")
+    if B.fft_supported(n) and n > CSD_FFT_MAX_N:
+        raise ValueError(f"n_fft {n}: the fused cross spectra take a power of two in {B.FFT_MIN_N}..{CSD_FFT_MAX_N}, two operands side "
+                         "by side (cross_spectra(fft='fused'), or stft of x and of y + welch_csd, take it)")
+    if not B.fft_supported(n):
+        raise ValueError(f"the fused cross spectra take n_fft a power of two in {B.FFT_MIN_N}..{CSD_FFT_MAX_N}, got {n}")
+
+
+def _csd_fft_call(torch, params, L, s, flags, xb, yb, nb, K, scale, onesided, bcast, outputs, out, workspace, dev, table, one_d):
+    """The output and workspace rules of the fused cross spectra (welch_csd's for `out`) and the launch: a dict by output name."""
+    mask = B.csd_mask(outputs)
+    names = [n for n in B.CSD_OUTPUTS if B.CSD_OUTPUTS[n][0] & mask]
+    shape = (K,) if one_d else (nb, K)
+    out = {} if out is None else out
+    if not isinstance(out, dict) or any(n not in names for n in out):
+        raise ValueError(f"out must be a dict of tensors by output name, within the outputs asked for {tuple(names)}")
+    res, o_stride = {}, None
+    for n in names:
+        t = out.get(n)
+        if t is None:
+            continue
+        dt = torch.complex64 if B.CSD_OUTPUTS[n][1] else torch.float32
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.device != yb.device or tuple(t.shape) != shape or t.is_conj() or t.is_neg() \
+                or t.stride(-1) != 1 or (t.dim() == 2 and nb > 1 and t.stride(0) < K):
+            raise ValueError(f"out[{n!r}] must be a {str(dt).replace('torch.', '')} tensor of shape {shape} on y's device, contiguous along "
+                             "the bins, rows apart")
+        if t.dim() == 2 and nb > 1:
+            if o_stride not in (None, t.stride(0)):
+                raise ValueError("the tensors of out must have the same row stride (o_stride is one number)")
+            o_stride = t.stride(0)
+        res[n] = t
+    for n in names:
+        if n not in res:
+            dt = torch.complex64 if B.CSD_OUTPUTS[n][1] else torch.float32
+            if o_stride in (None, K):
+                res[n] = torch.empty(shape, dtype=dt, device=yb.device)
+            else:
+                res[n] = torch.empty((nb, o_stride), dtype=dt, device=yb.device)[:, :K]
+    need = B.csd_fft_workspace_bytes(s) // 8
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float64, device=yb.device)
+    else:
+        _check_out(torch, workspace, need, "workspace", torch.float64)
+    cflags = mask | (B.CSD_ONESIDED if onesided else 0) | (B.CSD_BROADCAST_X if bcast else 0)
+    ptrs = [ctypes.c_void_p(res[n].data_ptr() if n in res else None) for n in B.CSD_OUTPUTS]
+    tail = (ctypes.byref(s), flags, float(scale), cflags, ctypes.c_void_p(xb.data_ptr()), ctypes.c_void_p(yb.data_ptr()), *ptrs,
+            o_stride or 0, ctypes.c_void_p(workspace.data_ptr()), workspace.numel() * 8)
+    if table is None:
+        B.check(B.lib().bhw_csd_fft_f32_device(ctypes.byref(params), L, dev, _stream_ptr(torch, dev), *tail))
+    else:
+        B.check(B.lib().bhw_csd_fft_f32_from_table(table, ctypes.byref(params), L, _stream_ptr(torch, dev), *tail))
+    return res
+
+
+def _csd_fft_operands(x, y):
+    """(x read, y read, nb, bcast, batch stride) for x (T,) or (B, T) against y: one batch stride serves both operands."""
+    yb = _stft_input(y if y.dim() == 2 else y.unsqueeze(0), (y.shape[-1],))
+    xb = _stft_input(x if x.dim() == 2 else x.unsqueeze(0), (x.shape[-1],))
+    nb, T = yb.shape
+    bcast = xb.shape[0] == 1 and nb > 1
+    if nb > 1 and not bcast and xb.stride(0) != yb.stride(0):           # one bhw_stft describes both: the same batch stride
+        xb, yb = xb.contiguous(), yb.contiguous()
+    return xb, yb, nb, bcast, (yb.stride(0) if nb > 1 else 0)
+
+
+def _csd_fft(torch, params, x, y, n_fft, hop, scale, outputs, win_length, center, pad_mode, detrend, onesided_doubling, shift, out,
+             workspace, dev, table):
+    check = lambda torch, t, n, dev: _csd_fft_input(torch, x, y, n, dev)
+    n_fft, L, _, _, T, frames, d = _stft_front(torch, params, y, n_fft, hop, win_length, center, pad_mode, detrend, dev, check)
+    xb, yb, nb, bcast, bs = _csd_fft_operands(x, y)
+    shift = params.dat_width - 1 if shift is None else int(shift)
+    s = B.make_stft(nb, T, frames, d["hop"], n_fft, col0=d["col0"], pad=d["pad"], pad_mode=d["pad_mode"], shift=shift, x_stride=bs)
+    return _csd_fft_call(torch, params, L, s, B.WELCH_DETREND_CONSTANT if detrend else 0, xb, yb, nb, n_fft // 2 + 1, scale,
+                         onesided_doubling, bcast, outputs, out, workspace, dev, table, y.dim() == 1)
+
+
+def csd_fft(params, x, y, n_fft, hop, scale, *, outputs=("pxy",), win_length=None, center=False, pad_mode="reflect", detrend=False,
+            onesided_doubling=True, shift=None, out=None, workspace=None):
+    """welch_csd(stft(x), stft(y)) WITHOUT either spectrum ever reaching memory (bhw_csd_fft_f32_device): x and y real float32 of the
+    same length, (T,) or (B, T) -- x (T,) against y (B, T) is paired with every signal of y --, framed, windowed and transformed
+    exactly as stft(params, ., n_fft, hop, win_length=..., center=..., pad_mode=..., detrend=...) does, frames of x and of y side by
+    side in one workgroup, and the four sums of welch_csd taken over the frames in the same kernel.  Returns a dict with the `outputs`
+    asked for ("pxy", "pxx", "pyy", "coherence", "h1": welch_csd's), each (K,) or (B, K) as y is.  The sums have welch_fft()'s order
+    (ascending frames inside chunks of 16, the chunks of a block of 256, then the blocks), so "pxx" / "pyy" are welch_fft of x / of y
+    bit for bit, and up to 16 frames every output is welch_csd's bit for bit.  n_fft: a power of two in 16..2048 (ValueError
+    otherwise, naming the route that takes 4096, a mixed-radix n_fft or complex input).  `out`: a dict by output name as welch_csd
+    takes it; `workspace`: float64, B.csd_fft_workspace_bytes(...) // 8 elements.  With both given the call neither allocates nor
+    synchronises and can be captured with no warm call."""
+    torch = _torch()
+    if not isinstance(y, torch.Tensor) or not y.is_cuda:
+        raise ValueError("y must be a float32 CUDA tensor")
+    return _csd_fft(torch, params, x, y, n_fft, hop, scale, outputs, win_length, center, pad_mode, detrend, onesided_doubling, shift, out,
+                    workspace, y.device.index, None)
+
+
+def _cross_fused(torch, params, x, y, fs, length, noverlap, nfft, detrend, scaling, shift, outputs, out, workspace, dev, table, cache):
+    B.csd_mask(outputs)
+    if detrend not in ("constant", False, None):
+        raise ValueError(f"detrend must be 'constant' or False, got {detrend!r}")
+    if scaling not in ("density", "spectrum"):
+        raise ValueError(f"scaling must be 'density' or 'spectrum', got {scaling!r}")
+    L = int(length)
+    noverlap = L // 2 if noverlap is None else int(noverlap)
+    if not 0 <= noverlap < L:
+        raise ValueError("noverlap must be less than length")
+    nfft = L if nfft is None else int(nfft)
+    hop = L - noverlap
+    _csd_fft_input(torch, x, y, nfft, dev)
+    if not 1 <= L <= 1 << params.phi_width:
+        raise ValueError(f"length {L} outside 1..2^phi_width = {1 << params.phi_width}")
+    if nfft < L:
+        raise ValueError(f"nfft {nfft} must be at least the window length {L}")
+    T = y.shape[-1]
+    if T < L or (y.dim() == 2 and y.shape[0] < 1):
+        raise ValueError(f"zero segments: T = {T} < length = {L}" if T < L else "zero signals")
+    frames = 1 + (T - L) // hop
+    xb, yb, nb, bcast, bs = _csd_fft_operands(x, y)
+    sums = _window_sums(torch, params, L, True, shift, dev, table, cache)
+    scale = B.welch_scale(sums, frames, fs, scaling)
+    sh = params.dat_width - 1 if shift is None else int(shift)
+    s = B.make_stft(nb, T, frames, hop, nfft, shift=sh, x_stride=bs)
+    freqs = _freq_axis(torch, cache, nfft, fs, dev)                    # before the launch: it refuses inside a capture when missing
+    res = _csd_fft_call(torch, params, L, s, B.WELCH_DETREND_CONSTANT if detrend == "constant" else 0, xb, yb, nb, nfft // 2 + 1, scale,
+                        True, bcast, outputs, out, workspace, dev, table, y.dim() == 1)
+    return freqs, res
+
+
+def cross_spectra_fused(params, x, y, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", scaling="density", shift=None,
+                        outputs=("pxy", "pxx", "pyy", "coherence", "h1"), out=None, workspace=None):
+    """cross_spectra(..., fft="fused") in ONE kernel and a small join (bhw_csd_fft_f32_device): the segments of x and of y, their FFTs
+    and the four averages come from the same kernel, so the two (B, F, K) spectra that route writes and reads back never exist.  The
+    argument checks, the window sums (cached) and the scale are cross_spectra's for fft="fused"; the estimates are one-sided and only
+    the mean is averaged.  Returns (freqs float64, dict by output name); `freqs` is welch_fused's shared, read-only axis.  The sums
+    have csd_fft()'s order: equal to cross_spectra(fft="fused") bit for bit up to 16 segments, "pxx" / "pyy" equal to welch_fused of x
+    / of y at any length.  Real float32 x and y of the same length, nfft a power of two in 16..2048; anything else is a ValueError
+    that names the route that takes it.  After one warm call, with `out` and `workspace` given, it neither synchronises nor allocates
+    and can be captured (ResidentTable.cross_spectra_fused); a first call inside a capture raises, as welch_fused does."""
+    torch = _torch()
+    if not isinstance(y, torch.Tensor) or not y.is_cuda:
+        raise ValueError("y must be a float32 CUDA tensor")
+    return _cross_fused(torch, params, x, y, fs, length, noverlap, nfft, detrend, scaling, shift, outputs, out, workspace, y.device.index,
+                        None, _SUMS_CACHE)
+
+
+def _one_fused(name, f_r):
+    return f_r[0], f_r[1][name]
+
+
+def csd_fused(params, x, y, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", scaling="density", shift=None, out=None,
+              workspace=None):
+    """cross_spectra_fused() with outputs=("pxy",): (freqs, Pxy complex64 (..., K)).  `out`: the tensor itself."""
+    return _one_fused("pxy", cross_spectra_fused(params, x, y, fs, length=length, noverlap=noverlap, nfft=nfft, detrend=detrend,
+                                                 scaling=scaling, shift=shift, outputs=("pxy",),
+                                                 out=None if out is None else {"pxy": out}, workspace=workspace))
+
+
+def coherence_fused(params, x, y, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", scaling="density", shift=None,
+                    out=None, workspace=None):
+    """cross_spectra_fused() with outputs=("coherence",): (freqs, Cxy float32 (..., K)).  `out`: the tensor itself."""
+    return _one_fused("coherence", cross_spectra_fused(params, x, y, fs, length=length, noverlap=noverlap, nfft=nfft, detrend=detrend,
+                                                       scaling=scaling, shift=shift, outputs=("coherence",),
+                                                       out=None if out is None else {"coherence": out}, workspace=workspace))
+
+
+def transfer_function_fused(params, x, y, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", scaling="density",
+                            shift=None, out=None, workspace=None):
+    """cross_spectra_fused() with outputs=("h1",): (freqs, H1 complex64 (..., K)).  `out`: the tensor itself."""
+    return _one_fused("h1", cross_spectra_fused(params, x, y, fs, length=length, noverlap=noverlap, nfft=nfft, detrend=detrend,
+                                                scaling=scaling, shift=shift, outputs=("h1",), out=None if out is None else {"h1": out},
+                                                workspace=workspace))
+
+
 class ResidentTable:
     """A first-quadrant CORDIC table built once and kept on the device (bhw_table_create): the elaboration of win_selector's
     CORDIC from its generics (model, PHI_WIDTH, DAT_WIDTH, PRECISION).  Every call then takes the run-time ports -- the weights
@@ -2033,6 +2228,40 @@ class ResidentTable:
         f, r = _cross(_torch(), params, x, y, fs, length, noverlap, nfft, detrend, return_onesided, scaling, shift, ("h1",), self,
                       self._sums, fft)
         return f, r["h1"]
+
+    def csd_fft(self, params, x, y, n_fft, hop, scale, *, outputs=("pxy",), win_length=None, center=False, pad_mode="reflect",
+                detrend=False, onesided_doubling=True, shift=None, out=None, workspace=None):
+        """csd_fft() with the coefficients gathered from this table (bhw_csd_fft_f32_from_table): no allocation by the library, no
+        synchronisation, capturable on its first call; the bits are those of the library form."""
+        return _csd_fft(_torch(), params, x, y, n_fft, hop, scale, outputs, win_length, center, pad_mode, detrend, onesided_doubling,
+                        shift, out, workspace, self.device, self._live())
+
+    def cross_spectra_fused(self, params, x, y, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", scaling="density",
+                            shift=None, outputs=("pxy", "pxx", "pyy", "coherence", "h1"), out=None, workspace=None):
+        """cross_spectra_fused() from this table.  The sums cache and the capture rule are welch()'s: after one warm call the call can
+        be captured into a graph, a first call inside a capture raises."""
+        return _cross_fused(_torch(), params, x, y, fs, length, noverlap, nfft, detrend, scaling, shift, outputs, out, workspace,
+                            self.device, self._live(), self._sums)
+
+    def _one_fused(self, name, params, x, y, fs, length, noverlap, nfft, detrend, scaling, shift, out, workspace):
+        f, r = self.cross_spectra_fused(params, x, y, fs, length=length, noverlap=noverlap, nfft=nfft, detrend=detrend, scaling=scaling,
+                                        shift=shift, outputs=(name,), out=None if out is None else {name: out}, workspace=workspace)
+        return f, r[name]
+
+    def csd_fused(self, params, x, y, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", scaling="density", shift=None,
+                  out=None, workspace=None):
+        """csd_fused() from this table."""
+        return self._one_fused("pxy", params, x, y, fs, length, noverlap, nfft, detrend, scaling, shift, out, workspace)
+
+    def coherence_fused(self, params, x, y, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", scaling="density",
+                        shift=None, out=None, workspace=None):
+        """coherence_fused() from this table."""
+        return self._one_fused("coherence", params, x, y, fs, length, noverlap, nfft, detrend, scaling, shift, out, workspace)
+
+    def transfer_function_fused(self, params, x, y, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", scaling="density",
+                                shift=None, out=None, workspace=None):
+        """transfer_function_fused() from this table."""
+        return self._one_fused("h1", params, x, y, fs, length, noverlap, nfft, detrend, scaling, shift, out, workspace)
 
     def generate_part(self, params, part, n_parts, window):
         """Interleaved ownership part `part` of `n_parts` into the full-length `window` (bhw_generate_part_from_table)."""

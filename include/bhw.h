@@ -1052,8 +1052,9 @@ int bhw_describe_istft_cfft(bhw_table t, const bhw_params *p, uint64_t length, c
  *     table) the key match.
  *   - Capture: as bhw_stft_fft_f32_*.  The library form needs no bhw_prepare_device; the from-table form is capturable on its first
  *     call.
- *   - Not built: cross spectra accumulated in the kernel; max-hold or median averaging; a filter bank on the averaged powers.  (I/Q
- *     input and the mixed-radix n_fft have this epilogue: bhw_welch_cfft_f32_* and bhw_welch_mfft_f32_* below.)
+ *   - Not built: max-hold or median averaging; a filter bank on the averaged powers.  (I/Q input and the mixed-radix n_fft have this
+ *     epilogue, bhw_welch_cfft_f32_* and bhw_welch_mfft_f32_* below; cross spectra have it for two signals side by side,
+ *     bhw_csd_fft_f32_* below.)
  *   - bhw_describe_welch_fft: bhw_describe_stft_fft's line in the same words, plus the chunk, the runs, the groups per run, the
  *     accumulators per lane and the workspace bytes.  t may be NULL (the library call).  Host arithmetic only. */
 /* Why 16: the frames of ONE signal are the only parallelism a long record has.  16 381 frames of one signal (2^24 samples, n_fft 4096,
@@ -1103,8 +1104,8 @@ int bhw_describe_welch_fft(bhw_table t, const bhw_params *p, uint64_t length, co
  *     d_x or each other; and (from a table) the key match.
  *   - Capture: as bhw_stft_cfft_f32_*.  The library form needs no bhw_prepare_device; the from-table form is capturable on its first
  *     call.
- *   - Not built: I/Q input at the mixed-radix lengths; max-hold or median traces; n_fft 4096; cross spectra accumulated in the
- *     kernel; a filter bank on the averaged powers.
+ *   - Not built: I/Q input at the mixed-radix lengths; max-hold or median traces; n_fft 4096; I/Q cross spectra accumulated in
+ *     the kernel (real input: bhw_csd_fft_f32_*); a filter bank on the averaged powers.
  *   - bhw_describe_welch_cfft: bhw_describe_stft_cfft's line in the same words (without the output form), plus the fields
  *     bhw_describe_welch_fft adds.  t may be NULL (the library call).  Host arithmetic only. */
 uint64_t bhw_welch_cfft_workspace_bytes(const bhw_stft *s);
@@ -1150,8 +1151,8 @@ int bhw_describe_welch_cfft(bhw_table t, const bhw_params *p, uint64_t length, c
  *     the key match.
  *   - Capture: as bhw_stft_mfft_f32_*.  The library form needs no bhw_prepare_device; the from-table form is capturable on its first
  *     call.
- *   - Not built: I/Q input at these lengths; odd n_fft and factors >= 7; cross spectra accumulated in the kernel; max-hold or median
- *     traces.
+ *   - Not built: I/Q input at these lengths; odd n_fft and factors >= 7; cross spectra at these lengths in one kernel; max-hold or
+ *     median traces.
  *   - bhw_describe_welch_mfft: bhw_describe_stft_mfft's line in the same words (without the output form), plus the fields
  *     bhw_describe_welch_fft adds.  t may be NULL (the library call).  Host arithmetic only. */
 uint64_t bhw_welch_mfft_workspace_bytes(const bhw_stft *s);
@@ -1162,6 +1163,58 @@ int bhw_welch_mfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t len
                                   double scale, uint32_t psd_flags, const float *d_x, float *d_P, uint64_t p_stride, void *workspace,
                                   uint64_t workspace_bytes);
 int bhw_describe_welch_mfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf, uint64_t len);
+
+/* Fused Welch cross spectra: window, real FFT of TWO signals and the four averages over the frames by ONE kernel and a small join.  The
+ * rows of bhw_stft_fft_f32_* of x and of y are formed and transformed side by side by the same kernel body, and the terms of
+ * bhw_welch_csd_f32 are accumulated where the transforms end, so the two (B, F, K) spectra that 2 x bhw_stft_fft_f32_* +
+ * bhw_welch_csd_f32 write and read back never exist.
+ *   - Inputs: (p, length, s, flags, scale) as bhw_welch_fft_f32_* takes them; ONE bhw_stft describes both operands (the same samples,
+ *     frames, hop, n_fft, padding and batch stride), and its y strides must be 0.  csd_flags is bhw_csd.flags: BHW_CSD_ONESIDED,
+ *     BHW_CSD_BROADCAST_X and the output mask BHW_CSD_PXY ... BHW_CSD_H1 (any non-empty subset).  d_x and d_y are float32 signals,
+ *     signal b at b * x_stride floats; under BHW_CSD_BROADCAST_X d_x holds ONE signal, paired with each of the B signals of d_y.  The
+ *     five output pointers and o_stride are bhw_welch_csd_f32's (d_Pxy and d_H1 complex64, the others float32, row b at b * o_stride
+ *     elements, 0 = K = n_fft / 2 + 1); a pointer is read only where its bit is set.
+ *   - Rows and transforms: those of bhw_stft_fft_f32_* for the same (p, length, s, flags).  Let (xr, xi) and (yr, yi) be the float32
+ *     pairs that call writes for bin k of row (b, f) of x and of y: the same words, from the same row function and split expression.
+ *   - The terms, in binary64 from the float32 parts, each one rounding (the products are exact), as bhw_welch_csd_f32 forms them:
+ *        xx = xr^2 + xi^2,  yy = yr^2 + yi^2,  re = xr * yr + xi * yi,  im = xr * yi - xi * yr
+ *   - The sums S_xx, S_yy, C_re, C_im, each in the order of bhw_welch_fft_f32_*:
+ *        chunk sums over the frames of a chunk of BHW_WELCH_FFT_CHUNK = 16, ascending f, binary64 from +0.0;
+ *        block sums over the 16 chunks of a block of BHW_WELCH_BLOCK = 256 frames, ascending, from +0.0; then the blocks, ascending.
+ *   - The outputs: from the four sums by the output formulas of bhw_welch_csd_f32, the unfused coherence expression and IEEE
+ *     0 / 0 = NaN included.
+ *   - Consequences: the bits depend on the window, n_fft, the flags, scale and the samples only -- not on B, the grid, or library
+ *     versus table.  P_xx is bit for bit bhw_welch_fft_f32_* of x and P_yy that of y, at any F (the same term, order and scale).  For
+ *     F <= 16 every output equals bhw_welch_csd_f32 of bhw_stft_fft_f32_*'s rows bit for bit.  Beyond 16 frames the cross terms are
+ *     signed, so the one-ulp statement of bhw_welch_fft_f32_* does not carry over: both orders add F products that are exact in
+ *     binary64, so C_re (and C_im) of the two routes differ by at most 2 F * 2^-53 * sum |term| <= 2 F * 2^-53 * sqrt(S_xx * S_yy)
+ *     (Cauchy-Schwarz), and each part of P_xy by that times s_k plus one float32 ulp of the larger result.
+ *   - Workspace: caller-provided, 8-byte aligned, bhw_csd_fft_workspace_bytes(s) = 4 * bhw_welch_fft_workspace_bytes(s) bytes: the
+ *     chunk sums of the four chains, [(b * chunks + c) * 4 K + chain * K + k], then, when F > 256, the block sums in the same layout.
+ *     A short one is BHW_ERR_WORKSPACE.  No call allocates, and there are no float atomics.
+ *   - Supported: real input (channels 1), n_fft a power of two in 16..2048.  n_fft 4096 is BHW_ERR_UNSUPPORTED (the two operands side
+ *     by side would need 80 KB of LDS): use bhw_stft_fft_f32_* + bhw_welch_csd_f32.  A mixed-radix n_fft and complex input are
+ *     BHW_ERR_UNSUPPORTED naming bhw_stft_mfft_f32_* / bhw_stft_cfft_f32_* + bhw_welch_csd_f32.
+ *   - IEEE: a NaN or an infinity in x or y reaches only the bins of its own pair.  Zeros in give P_xy = +0.0 and coherence NaN.
+ *   - Checks before any HIP call, in this order (BHW_ERR_BADARG unless noted): everything bhw_welch_fft_f32_* checks on the descriptor,
+ *     with the refusals named above and n_fft above 2048 (BHW_ERR_UNSUPPORTED); non-zero y strides; unknown csd_flags, an empty output
+ *     mask, a scale that is not finite; frames 0 returns BHW_OK here with the pointers unchecked; o_stride below K; B * ceil(F / 16) *
+ *     4 K above 2^34; NULL d_x or d_y, either not 4-byte aligned; a requested output that is NULL or misaligned (bhw_welch_csd_f32's
+ *     rules); a NULL or misaligned workspace, a short one (BHW_ERR_WORKSPACE); any output or the workspace overlapping anything else
+ *     (d_x and d_y may coincide: both are only read); and (from a table) the key match.
+ *   - Capture: as bhw_welch_fft_f32_*.
+ *   - Not built: n_fft 4096; mixed-radix and I/Q cross spectra; a two-chain kernel family for P_xy alone (four chains always run).
+ *   - bhw_describe_csd_fft: bhw_describe_welch_fft's line in the same words for the pair plan (lanes per row is min(128, ...): n_fft
+ *     2048 runs two butterflies per lane), plus the pairs per group and the outputs.  Host arithmetic only. */
+uint64_t bhw_csd_fft_workspace_bytes(const bhw_stft *s);
+int bhw_csd_fft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                           double scale, uint32_t csd_flags, const float *d_x, const float *d_y, float *d_Pxy, float *d_Pxx, float *d_Pyy,
+                           float *d_Cxy, float *d_H1, uint64_t o_stride, void *workspace, uint64_t workspace_bytes);
+int bhw_csd_fft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                               double scale, uint32_t csd_flags, const float *d_x, const float *d_y, float *d_Pxy, float *d_Pxx,
+                               float *d_Pyy, float *d_Cxy, float *d_H1, uint64_t o_stride, void *workspace, uint64_t workspace_bytes);
+int bhw_describe_csd_fft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, uint32_t csd_flags,
+                         char *buf, uint64_t len);
 
 /* Threading: every entry point may be called from any host thread.  Calls that use the library-owned scratch of one
  * (device, stream) are serialised against each other for the duration of their launches (the table is rebuilt per call);
