@@ -51,6 +51,7 @@ ABI_SYMBOLS = (
     "bhw_istft_mfft_f32_device", "bhw_istft_mfft_f32_from_table", "bhw_describe_istft_mfft",
     "bhw_stft_cfft_f32_device", "bhw_stft_cfft_f32_from_table", "bhw_describe_stft_cfft",
     "bhw_istft_cfft_f32_device", "bhw_istft_cfft_f32_from_table", "bhw_describe_istft_cfft",
+    "bhw_stft_cmfft_f32_device", "bhw_stft_cmfft_f32_from_table", "bhw_describe_stft_cmfft",
     "bhw_welch_fft_workspace_bytes", "bhw_welch_fft_f32_device", "bhw_welch_fft_f32_from_table", "bhw_describe_welch_fft",
     "bhw_csd_fft_workspace_bytes", "bhw_csd_fft_f32_device", "bhw_csd_fft_f32_from_table", "bhw_describe_csd_fft",
     "bhw_welch_cfft_workspace_bytes", "bhw_welch_cfft_f32_device", "bhw_welch_cfft_f32_from_table", "bhw_describe_welch_cfft",
@@ -333,6 +334,9 @@ def lib():
     L.bhw_stft_cfft_f32_device.argtypes = [P, u64, ci, vp, S, u32, vp, vp]
     L.bhw_stft_cfft_f32_from_table.argtypes = [T, P, u64, vp, S, u32, vp, vp]
     L.bhw_describe_stft_cfft.argtypes = [T, P, u64, S, u32, ctypes.c_char_p, u64]
+    L.bhw_stft_cmfft_f32_device.argtypes = [P, u64, ci, vp, S, u32, vp, vp]
+    L.bhw_stft_cmfft_f32_from_table.argtypes = [T, P, u64, vp, S, u32, vp, vp]
+    L.bhw_describe_stft_cmfft.argtypes = [T, P, u64, S, u32, ctypes.c_char_p, u64]
     L.bhw_istft_cfft_f32_device.argtypes = [P, u64, ci, vp, S, u32, f32p, f32p]
     L.bhw_istft_cfft_f32_from_table.argtypes = [T, P, u64, vp, S, u32, f32p, f32p]
     L.bhw_describe_istft_cfft.argtypes = [T, P, u64, S, u32, ctypes.c_char_p, u64]
@@ -607,6 +611,31 @@ def describe_stft_cfft(params, length, stft, *, detrend=False, power=False, ffts
     buf = ctypes.create_string_buffer(1024)
     flags = (WELCH_DETREND_CONSTANT if detrend else 0) | (CFFT_POWER if power else 0) | (CFFT_SHIFT if fftshift else 0)
     check(lib().bhw_describe_stft_cfft(table, ctypes.byref(params), int(length), ctypes.byref(stft), flags, buf, len(buf)))
+    return buf.value.decode()
+
+
+CMFFT_MIN_N, CMFFT_MAX_N = 16, 2047      # n_fft of the mixed-radix I/Q calls: 2^a 3^b 5^c in this range, odd or even, no power of two
+
+
+def cmfft_supported(n_fft):
+    """True where bhw_stft_cmfft_f32_* take n_fft: 2^a 3^b 5^c in 16..2047 that is no power of two (91 sizes, 18 of them odd)."""
+    n = int(n_fft)
+    if not CMFFT_MIN_N <= n <= CMFFT_MAX_N or n & (n - 1) == 0:
+        return False
+    for r in (2, 3, 5):
+        while n % r == 0:
+            n //= r
+    return n == 1
+
+
+def describe_stft_cmfft(params, length, stft, *, detrend=False, power=False, fftshift=False, table=None):
+    """One line: the plan fields of describe_stft_cfft in the same words for the mixed-radix complex transform of I/Q rows (the
+    schedule of radix-5, -3, -4 and -2 passes over n_fft points, no split pass), the entries of the twiddle table, the output form,
+    whether the bins are shifted, and the kernel (bhw_describe_stft_cmfft).  `stft` is a BhwStft with channels 2; `table` is a
+    resident table handle or None for the library call.  Host arithmetic only."""
+    buf = ctypes.create_string_buffer(1024)
+    flags = (WELCH_DETREND_CONSTANT if detrend else 0) | (CFFT_POWER if power else 0) | (CFFT_SHIFT if fftshift else 0)
+    check(lib().bhw_describe_stft_cmfft(table, ctypes.byref(params), int(length), ctypes.byref(stft), flags, buf, len(buf)))
     return buf.value.decode()
 
 

@@ -1154,6 +1154,19 @@ int stft_cfft_run(bhw_table t, const bhw_params *p, uint64_t length, int device,
                                                               const BhwLenPhase *lp) { return bhwk_stft_cfft_f32(l, c, w, pl, s, d_x, d_Y, tab, *lp); });
 }
 
+// The mixed-radix fused window + complex FFT for I/Q input (t NULL: the direct CORDIC chains): the checks, then the one kernel.
+int stft_cmfft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *s, uint32_t flags,
+                   const float *d_x, float *d_Y)
+{
+    int rc = bhwp_stft_cmfft_checks(p, length, s, flags, d_x, d_Y);
+    if (!rc && t) rc = table_call_checks(t, p);
+    if (rc || !s->frames) return rc;
+    const BhwStftCmfftPlan pl = bhwp_stft_cmfft_plan(p, length, s, flags, t != nullptr);
+    const char *what = t ? "stft cmfft launch (resident table)" : "stft cmfft launch";
+    return run_source(t, p, length, device, stream, what, [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *tab,
+                                                              const BhwLenPhase *lp) { return bhwk_stft_cmfft_f32(l, c, w, pl, s, d_x, d_Y, tab, *lp); });
+}
+
 // The fused spectrogram (t NULL: the direct CORDIC chains): the checks, then the one kernel.
 int spectrogram_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *s, uint32_t flags,
                     const bhw_fbank *fb, const float *d_x, float *d_P)
@@ -1677,6 +1690,30 @@ int bhw_describe_stft_cfft(bhw_table t, const bhw_params *p, uint64_t length, co
     int rc = bhwp_stft_cfft_checks(p, length, s, flags, nullptr, nullptr, false);
     if (!rc && t) rc = table_call_checks(t, p);
     return rc ? rc : bhwp_describe_stft_cfft(p, t ? &t->c : nullptr, length, s, flags, buf, len);
+}
+
+// ---- mixed-radix fused window and complex FFT for I/Q input (include/bhw.h: bhw_stft_cmfft_f32_device ...) ----------------------------
+
+int bhw_stft_cmfft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                              const void *d_x, void *d_Y)
+{
+    return stft_cmfft_run(nullptr, p, length, device, hip_stream, s, flags, (const float *)d_x, (float *)d_Y);
+}
+
+int bhw_stft_cmfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                  const void *d_x, void *d_Y)
+{
+    const int rc = bhwp_stft_cmfft_checks(p, length, s, flags, d_x, d_Y);
+    if (rc) return rc;
+    return t ? stft_cmfft_run(t, p, length, t->device, hip_stream, s, flags, (const float *)d_x, (float *)d_Y)
+             : fail(BHW_ERR_BADARG, "table is NULL");
+}
+
+int bhw_describe_stft_cmfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf, uint64_t len)
+{
+    int rc = bhwp_stft_cmfft_checks(p, length, s, flags, nullptr, nullptr, false);
+    if (!rc && t) rc = table_call_checks(t, p);
+    return rc ? rc : bhwp_describe_stft_cmfft(p, t ? &t->c : nullptr, length, s, flags, buf, len);
 }
 
 // ---- fused inverse real FFT, window and overlap-add (include/bhw.h: bhw_istft_fft_f32_device ...) --------------------------------------

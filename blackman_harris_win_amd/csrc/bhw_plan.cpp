@@ -2195,32 +2195,10 @@ int bhwp_describe_stft_mfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_
 
 // ---- fused window and complex FFT for I/Q input ----------------------------------------------------------------------------------------------
 
-int bhwp_stft_cfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const void *d_x, const void *d_Y,
-                          bool pointers)
+// Steps 4 and 5 of the I/Q forward calls (bhw_stft_cfft_f32_*, bhw_stft_cmfft_f32_*): frames 0, the stride rules of the output form,
+// the pointers.
+static int iq_output_checks(const bhw_stft *s, uint32_t flags, const void *d_x, const void *d_Y, bool pointers)
 {
-    int rc = bhwp_f32_checks(p, length, 0);
-    if (rc) return rc;
-    if (!s) return bhwp_fail(BHW_ERR_BADARG, "stft descriptor is NULL");
-    if (s->struct_size != sizeof(bhw_stft)) return bhwp_fail(BHW_ERR_BADARG, "bhw_stft.struct_size %u != %zu", s->struct_size, sizeof(bhw_stft));
-    // 1. what the frames or the segments call checks, for the same descriptor with packed rows (the output strides mean something
-    //    else here and are checked below); this holds batch * frames * n_fft to 2^34 and the extents of x to 2^60 floats
-    bhw_stft t = *s;
-    t.y_stride = t.y_batch_stride = 0;
-    const uint32_t detrend = flags & BHW_WELCH_DETREND_CONSTANT;
-    const bool segments = detrend || (!s->pad && !s->col0 && !s->pad_mode);
-    if (segments) rc = bhwp_welch_checks(p, length, &t, detrend, nullptr, nullptr, nullptr, 0, false);
-    else          rc = bhwp_stft_checks(p, length, &t, false, 0, nullptr, nullptr, false);
-    if (rc) return rc;
-    // 2., 3.
-    if (flags & ~kCfftFlags)
-        return bhwp_fail(BHW_ERR_BADARG, "flags 0x%x (BHW_WELCH_DETREND_CONSTANT, BHW_CFFT_POWER, BHW_CFFT_SHIFT)", flags);
-    if (s->channels != 2)
-        return bhwp_fail(BHW_ERR_UNSUPPORTED, "channels %u: the fused complex FFT takes interleaved I/Q input (2); real input: bhw_stft_fft_f32_*",
-                         s->channels);
-    if ((s->n_fft & (s->n_fft - 1)) || s->n_fft < (1ull << kCfftMinLog) || s->n_fft > (1ull << kCfftMaxLog))
-        return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu: the fused complex FFT takes a power of two in %u..%u", (unsigned long long)s->n_fft,
-                         1u << kCfftMinLog, 1u << kCfftMaxLog);
-    // 4., 5.
     const uint64_t T = s->samples, F = s->frames;
     if (!F) return BHW_OK;
     const bool power = (flags & BHW_CFFT_POWER) != 0;
@@ -2247,6 +2225,44 @@ int bhwp_stft_cfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *
     if (xa > UINT64_MAX - xb || ya > UINT64_MAX - yb) return bhwp_fail(BHW_ERR_BADARG, "x or Y range wraps the address space");
     if (xa < ya + yb && ya < xa + xb) return bhwp_fail(BHW_ERR_BADARG, "d_x and d_Y overlap");
     return BHW_OK;
+}
+
+// Steps 1 and 2 of the same calls: the descriptor as the frames or the segments call checks it, then the flag bits.
+static int iq_descriptor_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags)
+{
+    int rc = bhwp_f32_checks(p, length, 0);
+    if (rc) return rc;
+    if (!s) return bhwp_fail(BHW_ERR_BADARG, "stft descriptor is NULL");
+    if (s->struct_size != sizeof(bhw_stft)) return bhwp_fail(BHW_ERR_BADARG, "bhw_stft.struct_size %u != %zu", s->struct_size, sizeof(bhw_stft));
+    // 1. what the frames or the segments call checks, for the same descriptor with packed rows (the output strides mean something
+    //    else here and are checked below); this holds batch * frames * n_fft to 2^34 and the extents of x to 2^60 floats
+    bhw_stft t = *s;
+    t.y_stride = t.y_batch_stride = 0;
+    const uint32_t detrend = flags & BHW_WELCH_DETREND_CONSTANT;
+    const bool segments = detrend || (!s->pad && !s->col0 && !s->pad_mode);
+    if (segments) rc = bhwp_welch_checks(p, length, &t, detrend, nullptr, nullptr, nullptr, 0, false);
+    else          rc = bhwp_stft_checks(p, length, &t, false, 0, nullptr, nullptr, false);
+    if (rc) return rc;
+    // 2.
+    if (flags & ~kCfftFlags)
+        return bhwp_fail(BHW_ERR_BADARG, "flags 0x%x (BHW_WELCH_DETREND_CONSTANT, BHW_CFFT_POWER, BHW_CFFT_SHIFT)", flags);
+    return BHW_OK;
+}
+
+int bhwp_stft_cfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const void *d_x, const void *d_Y,
+                          bool pointers)
+{
+    const int rc = iq_descriptor_checks(p, length, s, flags);
+    if (rc) return rc;
+    // 3.
+    if (s->channels != 2)
+        return bhwp_fail(BHW_ERR_UNSUPPORTED, "channels %u: the fused complex FFT takes interleaved I/Q input (2); real input: bhw_stft_fft_f32_*",
+                         s->channels);
+    if ((s->n_fft & (s->n_fft - 1)) || s->n_fft < (1ull << kCfftMinLog) || s->n_fft > (1ull << kCfftMaxLog))
+        return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu: the fused complex FFT takes a power of two in %u..%u", (unsigned long long)s->n_fft,
+                         1u << kCfftMinLog, 1u << kCfftMaxLog);
+    // 4., 5.
+    return iq_output_checks(s, flags, d_x, d_Y, pointers);
 }
 
 BhwStftCfftPlan bhwp_stft_cfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, bool from_table)
@@ -2303,6 +2319,98 @@ int bhwp_describe_stft_cfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_
              (unsigned long long)s->col0, (unsigned long long)s->pad, pad, det, form, bins, kern, (unsigned long long)s->batch,
              (unsigned long long)s->frames, (unsigned long long)pl.rows, pl.n, sched, pl.lpf, pl.fy, pl.cpl, (unsigned long long)pl.groups,
              (unsigned long long)pl.grid, kFftBlock, pl.lds_bytes);
+    return BHW_OK;
+}
+
+// ---- mixed-radix fused window and complex FFT for I/Q input -------------------------------------------------------------------------------
+
+bool bhwp_cmfft_supported(uint64_t n)
+{
+    if (n < kCmfftMinN || n > kCmfftMaxN || !(n & (n - 1))) return false;
+    for (const uint64_t r : {2ull, 3ull, 5ull})
+        while (n % r == 0) n /= r;
+    return n == 1;
+}
+
+int bhwp_stft_cmfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const void *d_x, const void *d_Y,
+                           bool pointers)
+{
+    const int rc = iq_descriptor_checks(p, length, s, flags);
+    if (rc) return rc;
+    // 3.: each refusal names the route that takes the call
+    if (s->channels != 2)
+        return bhwp_fail(BHW_ERR_UNSUPPORTED, "channels %u: the mixed-radix fused complex FFT takes interleaved I/Q input (2); real input: "
+                         "bhw_stft_mfft_f32_*", s->channels);
+    if (!(s->n_fft & (s->n_fft - 1)))
+        return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu is a power of two: bhw_stft_cfft_f32_* transforms it (one transform per n_fft)",
+                         (unsigned long long)s->n_fft);
+    if (!bhwp_cmfft_supported(s->n_fft))
+        return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu: the mixed-radix fused complex FFT takes 2^a 3^b 5^c in %u..%u", (unsigned long long)s->n_fft,
+                         kCmfftMinN, kCmfftMaxN);
+    // 4., 5.
+    return iq_output_checks(s, flags, d_x, d_Y, pointers);
+}
+
+BhwStftCmfftPlan bhwp_stft_cmfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, bool from_table)
+{
+    (void)p;
+    BhwStftCmfftPlan pl{};
+    pl.route = from_table ? BHWP_FRAMES_TABLE : BHWP_FRAMES_DIRECT;
+    pl.detrend = (flags & BHW_WELCH_DETREND_CONSTANT) != 0;
+    pl.power = (flags & BHW_CFFT_POWER) != 0;
+    pl.shifted = (flags & BHW_CFFT_SHIFT) != 0;
+    pl.len = length;
+    const uint32_t n = (uint32_t)s->n_fft;
+    pl.n = n;
+    pl.fold = (n & 1u) ? n : n / 2;
+    pl.lpf = 4;
+    while (pl.lpf < kFftBlock && 4u * pl.lpf < n) pl.lpf *= 2;         // the smallest power of two >= n / 4
+    pl.fy = kFftBlock / pl.lpf;
+    pl.cpl = (n + pl.lpf - 1) / pl.lpf;
+    // the schedule: 5s, 3s, 4s, a last 2
+    uint32_t rest = n;
+    for (const uint32_t r : {5u, 3u, 4u, 2u})
+        while (rest % r == 0 && pl.passes < kMfftMaxPasses) {
+            pl.radix[pl.passes++] = (uint8_t)r;
+            rest /= r;
+        }
+    pl.lds_bytes = 2u * pl.fy * n * 8u + pl.fold * 8u + pl.fy * 8u;
+    pl.x_stride = s->x_stride ? s->x_stride : 2 * s->samples;
+    pl.y_stride = s->y_stride ? s->y_stride : (pl.power ? s->n_fft : 2 * s->n_fft);
+    pl.y_bstride = s->y_batch_stride ? s->y_batch_stride : s->frames * pl.y_stride;
+    pl.rows = s->batch * s->frames;
+    pl.groups = (pl.rows + pl.fy - 1) / pl.fy;
+    pl.grid = pl.groups < kFftMaxGrid ? pl.groups : kFftMaxGrid;
+    return pl;
+}
+
+int bhwp_describe_stft_cmfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf,
+                             uint64_t len)
+{
+    if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
+    const char *route = ct ? "table" : "direct";
+    const BhwStftCmfftPlan pl = bhwp_stft_cmfft_plan(p, length, s, flags, ct != nullptr);
+    const char *pad = s->pad_mode == BHW_PAD_REFLECT ? "reflect" : "constant";
+    const char *det = pl.detrend ? "constant detrend" : "no detrending";
+    const char *form = pl.power ? "power rows" : "spectrum rows";
+    const char *bins = pl.shifted ? "bins shifted" : "bins in order";
+    if (!s->frames) {
+        snprintf(buf, len, "stft cmfft %s (L = %llu, n_fft %llu, %s), %s, %s: nothing (frames 0)", route, (unsigned long long)length,
+                 (unsigned long long)s->n_fft, det, form, bins);
+        return BHW_OK;
+    }
+    char kern[64], sched[48];
+    kernel_name(p, ct, "k_stft_cmfft_direct", "k_stft_cmfft_table", false, kern, sizeof kern);
+    BhwStftMfftPlan f{};
+    f.passes = pl.passes;
+    memcpy(f.radix, pl.radix, sizeof f.radix);
+    bhwp_stft_mfft_schedule(f, sched, sizeof sched);
+    snprintf(buf, len, "stft cmfft %s (L = %llu, n_fft %llu, col0 %llu, pad %llu %s, %s), %s, %s: %s, %llu signals x %llu frames = %llu rows, "
+             "complex FFT of %u points in passes %s (no split), %u lanes per row x %u rows per workgroup, %u columns per lane, %llu groups, "
+             "grid %llu x %u lanes, %u bytes of LDS, %u twiddles", route, (unsigned long long)length, (unsigned long long)s->n_fft,
+             (unsigned long long)s->col0, (unsigned long long)s->pad, pad, det, form, bins, kern, (unsigned long long)s->batch,
+             (unsigned long long)s->frames, (unsigned long long)pl.rows, pl.n, sched, pl.lpf, pl.fy, pl.cpl, (unsigned long long)pl.groups,
+             (unsigned long long)pl.grid, kFftBlock, pl.lds_bytes, pl.fold);
     return BHW_OK;
 }
 

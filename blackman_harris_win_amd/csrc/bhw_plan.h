@@ -646,6 +646,45 @@ int  bhwp_describe_stft_cfft(const bhw_params *p, const BhwCordicCfg *ct, uint64
 int  bhwk_stft_cfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwStftCfftPlan &pl, const bhw_stft *s,
                         const float *d_x, float *d_Y, const int32_t *d_table, const BhwLenPhase &lp);
 
+// ---- mixed-radix fused window and complex FFT for I/Q input (bhw_stft_cmfft_f32_*; bhw_stft_cmfft.hip) --------------------------------
+// The complex kernel's layout for n = n_fft = 2^a 3^b 5^c that is NOT a power of two, odd lengths included, 16 <= n < 2048: lpf = the
+// smallest power of two >= n / 4 (clamped to 4 .. kFftBlock) lanes on a row of n complex points, fy = kFftBlock / lpf rows side by
+// side, cpl = ceil(n / lpf) <= kCfftMaxCpl complex columns per lane; the last column of a lane need not exist.  The schedule is
+// bhwp_stft_mfft_plan's rule applied to n itself: the radix-5 passes, the radix-3 passes, the radix-4 passes, then one radix-2 pass;
+// seven at most (1458 = 2 3^6).  fold: the entries of the twiddle table exp(-2 pi i k / n): n / 2 for an even n (the upper half is
+// the negated lower one), n for an odd n.  LDS: two buffers of fy * n complex64 (the first also stages the window and the raw row of
+// the detrend means), the fold twiddles and 2 * fy means.  Rows, groups, grid and the stride resolution are BhwStftCfftPlan's.
+constexpr uint32_t kCmfftMinN = 16, kCmfftMaxN = 2047;
+struct BhwStftCmfftPlan {
+    int route;            // BHWP_FRAMES_DIRECT or BHWP_FRAMES_TABLE
+    bool detrend, power, shifted;
+    uint32_t n;           // the points of a row: n_fft
+    uint32_t fold;        // twiddle table entries: n / 2 (n even) or n (n odd)
+    uint32_t lpf;         // lanes per row
+    uint32_t fy;          // rows side by side: kFftBlock / lpf
+    uint32_t cpl;         // complex columns per lane: ceil(n / lpf) (3 .. 8)
+    uint32_t passes;
+    uint8_t radix[kMfftMaxPasses];
+    uint32_t lds_bytes;   // 2 * fy * n * 8 + fold * 8 + fy * 8  (<= 48 608: n = 2025)
+    uint64_t rows;        // B * frames
+    uint64_t groups;      // ceil(rows / fy)
+    uint64_t grid;        // min(groups, kFftMaxGrid)
+    uint64_t x_stride, y_stride, y_bstride;   // resolved, in floats (0 -> 2T; 2n or n; frames * y_stride)
+    uint64_t len;         // L
+};
+// n_fft the mixed-radix I/Q calls take
+bool bhwp_cmfft_supported(uint64_t n_fft);
+// Every check of the two calls that needs no table handle, before any HIP call and in the order of bhwp_stft_cfft_checks.  frames 0
+// passes with the pointers unchecked; `pointers` false: the describe call.
+int  bhwp_stft_cmfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const void *d_x, const void *d_Y,
+                            bool pointers = true);
+// the plan of a call that passed the checks (frames 0: rows, groups and grid are 0)
+BhwStftCmfftPlan bhwp_stft_cmfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, bool from_table);
+int  bhwp_describe_stft_cmfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf,
+                              uint64_t len);
+int  bhwk_stft_cmfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwStftCmfftPlan &pl, const bhw_stft *s,
+                         const float *d_x, float *d_Y, const int32_t *d_table, const BhwLenPhase &lp);
+
 // ---- fused Welch PSD for I/Q input (bhw_welch_cfft_f32_*; bhw_welch_cfft.hip) ---------------------------------------------------------------
 // BhwWelchCfftPlan wraps BhwStftCfftPlan as BhwWelchFftPlan wraps BhwStftFftPlan: the lanes, LDS, schedule and row steps are
 // bhwp_stft_cfft_plan's field for field (fft, with groups and grid recounted), the ownership is bhwp_welch_runs' with bins = n_fft.

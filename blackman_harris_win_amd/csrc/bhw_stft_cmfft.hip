@@ -1,0 +1,101 @@
+// bhw_stft_cmfft.hip -- window and mixed-radix complex FFT in one kernel for interleaved I/Q input at n_fft = 2^a 3^b 5^c that is no
+// power of two, odd lengths included (bhw_stft_cmfft_f32_device / _from_table; contract: include/bhw.h, plan: BhwStftCmfftPlan in
+// bhw_plan.h, reasons and measurements: DESIGN.md section 30).  The row function and the account of what a workgroup does are in
+// bhw_stft_cmfft.h; the epilogue here is CmfftStore: lane l writes bins l, l + lpf, ... as complex64 or as fl32(re^2 + im^2) in
+// binary64, to column k or, shifted, to column (k + n / 2) mod n.
+#include "bhw_stft_cmfft.h"
+
+namespace {
+
+// Coefficient by the direct CORDIC chains (FORM: direct_form, as k_stft_cfft_direct).
+template <int FORM>
+__global__ __launch_bounds__(kFftBlock) void k_stft_cmfft_direct(BhwCordicCfg cfg, BhwWinCfg win, CmfftIo a, BhwLenPhase lp)
+{
+    using T = std::conditional_t<FORM == 0, int32_t, int64_t>;
+    using L = std::conditional_t<FORM == 2, uint32_t, T>;
+    __shared__ L lut_s[32];
+    if (threadIdx.x < 32) lut_s[threadIdx.x] = (L)cfg.lut[threadIdx.x];
+    __syncthreads();
+    float *vbuf = (float *)fft_lds;
+    for (uint32_t j = threadIdx.x; j < a.n; j += kFftBlock) {
+        const uint32_t k = j - a.col0;                             // unsigned: k < L is the window test
+        float v = 0.0f;
+        if (k < a.len) {
+            int32_t w;
+            if constexpr (FORM == 2) w = direct_coeff_mad_ph(cfg, win, lut_s, len_theta_of(lp, k));
+            else                     w = direct_coeff_ph<T>(cfg, win, lut_s, len_theta_of(lp, k));
+            v = fft_coeff(w, a.shift);
+        }
+        vbuf[j] = v;
+    }
+    __syncthreads();
+    stft_cmfft_rows(a, CmfftStore{});
+}
+
+// Coefficient gathered from a resident table in format FMT; every lane reaches the gather (at k = 0 outside the window) for the
+// escape format's wave-wide fix.
+template <int FMT, int NT, int MODE>
+__global__ __launch_bounds__(kFftBlock) void k_stft_cmfft_table(BhwCordicCfg cfg, BhwWinCfg win, const void *__restrict__ table, CmfftIo a,
+                                                                 BhwLenPhase lp)
+{
+    float *vbuf = (float *)fft_lds;
+    for (uint32_t j0 = 0; j0 < a.n; j0 += kFftBlock) {
+        const uint32_t j = j0 + threadIdx.x;
+        const uint32_t k = j - a.col0;
+        const bool in = j < a.n && k < a.len;
+        const int32_t w = range_coeff_ph<FMT, NT, MODE>(cfg, win, table, len_theta_of(lp, in ? k : 0u));
+        if (j < a.n) vbuf[j] = in ? fft_coeff(w, a.shift) : 0.0f;
+    }
+    __syncthreads();
+    stft_cmfft_rows(a, CmfftStore{});
+}
+
+} // namespace
+
+int bhwk_stft_cmfft_f32(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinCfg &w, const BhwStftCmfftPlan &pl, const bhw_stft *s,
+                        const float *d_x, float *d_Y, const int32_t *d_table, const BhwLenPhase &lp)
+{
+    if (!pl.rows) return 0;
+    hipStream_t st = (hipStream_t)l.stream;
+    CmfftIo a{};
+    a.x = d_x;
+    a.Y = d_Y;
+    a.rows = pl.rows;
+    a.frames = s->frames;
+    a.hop = s->hop;
+    a.samples = s->samples;
+    a.pad = s->pad;
+    a.x_stride = pl.x_stride;
+    a.y_stride = pl.y_stride;
+    a.y_bstride = pl.y_bstride;
+    a.groups = pl.groups;
+    a.n = pl.n;
+    a.fold = pl.fold;
+    a.col0 = (uint32_t)s->col0;
+    a.len = (uint32_t)pl.len;
+    a.lpf = pl.lpf;
+    a.fy = pl.fy;
+    a.cpl = pl.cpl;
+    a.passes = pl.passes;
+    for (uint32_t p = 0; p < pl.passes; ++p) a.sched |= (uint32_t)pl.radix[p] << (4u * p);
+    a.shift = s->shift;
+    a.reflect = s->pad_mode == BHW_PAD_REFLECT ? 1u : 0u;
+    a.detrend = pl.detrend ? 1u : 0u;
+    a.power = pl.power ? 1u : 0u;
+    a.binshift = pl.shifted ? 1u : 0u;
+    // one 8-byte load per complex sample where every sample is 8-byte aligned, as the power-of-two kernel's
+    a.vec = ((uintptr_t)d_x % 8 == 0 && (s->batch == 1 || pl.x_stride % 2 == 0)) ? 1u : 0u;
+    const dim3 grid((unsigned)pl.grid), block(kFftBlock);
+    if (!d_table) {
+        with_int_or_last<2, 1, 0>(direct_form(c_in), [&](auto D) { launch_lds(k_stft_cmfft_direct<D>, grid, block, pl.lds_bytes, st, c_in, w, a, lp); });
+        return finish(hipSuccess);
+    }
+    const BhwCordicCfg c = table_layout(c_in);
+    int fmt, nt, mode;
+    if (!bhwp_range_form(c, w, &fmt, &nt, &mode)) return (int)hipErrorInvalidValue;
+    const void *tab = (const void *)d_table;
+    with_range_form(fmt, nt, mode, [&](auto F, auto NT, auto M) {
+        launch_lds(k_stft_cmfft_table<F, NT, M>, grid, block, pl.lds_bytes, st, c, w, tab, a, lp);
+    });
+    return finish(hipSuccess);
+}

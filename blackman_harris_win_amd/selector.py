@@ -482,6 +482,20 @@ def _cfft_input(torch, x, n_fft, dev):
         raise ValueError(f"the fused complex FFT takes n_fft a power of two in {B.CFFT_MIN_N}..{B.CFFT_MAX_N}, got {int(n_fft)}")
 
 
+def _cmfft_input(torch, x, n_fft, dev):
+    """_cfft_input for the mixed-radix I/Q calls: complex64 (T,) or (B, T), n_fft one the mixed-radix complex kernel takes."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.complex64:
+        got = x.dtype if isinstance(x, torch.Tensor) else type(x).__name__
+        raise ValueError(f"the mixed-radix fused complex FFT takes complex64 input, got {got} (real input: stft_mixed / spectrogram_mixed)")
+    if x.dim() not in (1, 2):
+        raise ValueError("x must be (T,) or (B, T)")
+    n = int(n_fft)
+    if n > 0 and n & (n - 1) == 0:
+        raise ValueError(f"n_fft {n} is a power of two: bhw.stft_iq / bhw.spectrogram_iq transform it (one transform per n_fft)")
+    if not B.cmfft_supported(n):
+        raise ValueError(f"the mixed-radix fused complex FFT takes n_fft 2^a·3^b·5^c in {B.CMFFT_MIN_N}..{B.CMFFT_MAX_N}, got {n}")
+
+
 def _fft_out(torch, out, shape, x, dtype=None):
     """The output tensor and its strides in floats: allocated packed, or the caller's `out` of `shape` and `dtype` (complex64 spectrum
     rows by default, float32 for the spectrogram), the last axis contiguous, rows and signals apart; the gaps of a wider buffer are
@@ -515,7 +529,8 @@ def _fft_launch(torch, params, L, s, flags, xr, out, dev, table):
 
 def _stft_front(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, dev, check=_fft_input):
     """The input checks and the framing every fused forward call shares (stft, spectrogram, stft_iq, spectrogram_iq): (n_fft, L, the
-    x read, its (nb, T), frames, and the descriptor's hop, col0, pad, pad_mode).  check: _fft_input, or _cfft_input for I/Q input."""
+    x read, its (nb, T), frames, and the descriptor's hop, col0, pad, pad_mode).  check: _fft_input, _cfft_input for I/Q input, or the
+    mixed-radix ones (_mfft_input, _cmfft_input)."""
     n_fft, L, col0 = _stft_window(params, n_fft, win_length)
     check(torch, x, n_fft, dev)
     hop = int(hop)
@@ -570,8 +585,10 @@ def stft(params, x, n_fft, hop, *, win_length=None, center=True, pad_mode="refle
 
 # ---- fused window and complex FFT for I/Q input ---------------------------------------------------------------------------------------------
 
-def _stft_iq(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, shift, fftshift, out, dev, table, power):
-    n_fft, L, xb, nb, T, frames, d = _stft_front(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, dev, _cfft_input)
+def _stft_iq(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, shift, fftshift, out, dev, table, power, mixed=False):
+    """stft_iq / spectrogram_iq (power), or with `mixed` stft_iq_mixed / spectrogram_iq_mixed: the same front, the other kernel."""
+    n_fft, L, xb, nb, T, frames, d = _stft_front(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, dev,
+                                                 _cmfft_input if mixed else _cfft_input)
     shape = (nb, frames, n_fft) if x.dim() == 2 else (frames, n_fft)
     out, ys, ybs = _fft_out(torch, out, shape, x, torch.float32 if power else torch.complex64)
     if not x.is_cuda or x.device.index != dev:
@@ -581,10 +598,13 @@ def _stft_iq(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend
                     x_stride=xb.stride(0) * 2 if nb > 1 else 0, y_stride=ys, y_batch_stride=ybs)
     flags = (B.WELCH_DETREND_CONSTANT if detrend else 0) | (B.CFFT_POWER if power else 0) | (B.CFFT_SHIFT if fftshift else 0)
     tail = (ctypes.byref(s), flags, ctypes.c_void_p(xb.data_ptr()), ctypes.c_void_p(out.data_ptr()))
+    L_ = B.lib()
+    device_call, table_call = (L_.bhw_stft_cmfft_f32_device, L_.bhw_stft_cmfft_f32_from_table) if mixed else \
+        (L_.bhw_stft_cfft_f32_device, L_.bhw_stft_cfft_f32_from_table)
     if table is None:
-        B.check(B.lib().bhw_stft_cfft_f32_device(ctypes.byref(params), L, dev, _stream_ptr(torch, dev), *tail))
+        B.check(device_call(ctypes.byref(params), L, dev, _stream_ptr(torch, dev), *tail))
     else:
-        B.check(B.lib().bhw_stft_cfft_f32_from_table(table, ctypes.byref(params), L, _stream_ptr(torch, dev), *tail))
+        B.check(table_call(table, ctypes.byref(params), L, _stream_ptr(torch, dev), *tail))
     return out
 
 
@@ -619,6 +639,36 @@ def spectrogram_iq(params, x, n_fft, hop, *, win_length=None, center=True, pad_m
     torch = _torch()
     dev = x.device.index if isinstance(x, torch.Tensor) and x.is_cuda else None
     return _stft_iq(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, shift, fftshift, out, dev, None, True)
+
+
+def stft_iq_mixed(params, x, n_fft, hop, *, win_length=None, center=True, pad_mode="reflect", detrend=False, shift=None, fftshift=False,
+                  out=None):
+    """stft_iq() for the row lengths complex baseband uses and a power-of-two transform refuses, in ONE launch
+    (bhw_stft_cmfft_f32_device): n_fft 2^a·3^b·5^c in 16..2047 and not a power of two, odd lengths included -- 1536, 1200, 600, 300,
+    180, 1000, 2000, 480, 960, 75.  The arguments, the shapes, the `out` rules and the errors are stft_iq()'s: x (T,) or (B, T),
+    complex64, framed and windowed exactly as stft_frames() / welch_frames() do for complex input (their rows bit for bit) and
+    transformed in the same kernel by a float32 mixed-radix complex FFT in LDS (radix-5, -3, -4 and -2 Stockham passes over n_fft
+    points).  Returns complex64 (B, F, n_fft) or (F, n_fft); `stft_iq_mixed(p, x, n, hop).transpose(-1, -2)` is
+    torch.stft(x, n, hop, window=v, onesided=False, return_complex=True).  detrend=True (needs center=False) forms scipy's Welch
+    segments, and welch_psd(stft_iq_mixed(..., detrend=True, center=False), scale, nfft=n_fft, onesided=False) is the two-sided Welch
+    estimate at such an nfft.  fftshift=True writes bin k to column (k + n_fft // 2) % n_fft: torch.fft.fftshift along the bins, for
+    an odd n_fft too.  A power-of-two n_fft raises ValueError (bhw.stft_iq transforms it: one transform per n_fft); any other
+    unsupported n_fft and a real or complex128 x raise ValueError too.  The FFT is accurate to a float32 FFT's error, not pinned bit
+    for bit."""
+    torch = _torch()
+    dev = x.device.index if isinstance(x, torch.Tensor) and x.is_cuda else None
+    return _stft_iq(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, shift, fftshift, out, dev, None, False, True)
+
+
+def spectrogram_iq_mixed(params, x, n_fft, hop, *, win_length=None, center=True, pad_mode="reflect", detrend=False, shift=None,
+                         fftshift=False, out=None):
+    """spectrogram_iq() at the n_fft of stft_iq_mixed() (bhw_stft_cmfft_f32_device with BHW_CFFT_POWER): each bin fl32(re^2 + im^2),
+    taken in binary64, of the float32 pair stft_iq_mixed() would have written -- bit for bit.  Returns float32 (B, F, n_fft) or
+    (F, n_fft); fftshift=True puts the zero frequency at column n_fft // 2.  The arguments, `out` rules and errors are
+    spectrogram_iq()'s; a power-of-two n_fft raises ValueError (bhw.spectrogram_iq transforms it)."""
+    torch = _torch()
+    dev = x.device.index if isinstance(x, torch.Tensor) and x.is_cuda else None
+    return _stft_iq(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, shift, fftshift, out, dev, None, True, True)
 
 
 def _ifft_input(torch, Y, dev):
@@ -2110,6 +2160,20 @@ class ResidentTable:
         allocation by the library, no synchronisation, capturable into a graph on its first call."""
         return _stft_iq(_torch(), params, x, n_fft, hop, win_length, center, pad_mode, detrend, shift, fftshift, out, self.device,
                         self._live(), True)
+
+    def stft_iq_mixed(self, params, x, n_fft, hop, *, win_length=None, center=True, pad_mode="reflect", detrend=False, shift=None,
+                      fftshift=False, out=None):
+        """stft_iq_mixed() with the coefficients gathered from this table (bhw_stft_cmfft_f32_from_table): no allocation by the
+        library, no synchronisation, capturable into a graph on its first call."""
+        return _stft_iq(_torch(), params, x, n_fft, hop, win_length, center, pad_mode, detrend, shift, fftshift, out, self.device,
+                        self._live(), False, True)
+
+    def spectrogram_iq_mixed(self, params, x, n_fft, hop, *, win_length=None, center=True, pad_mode="reflect", detrend=False, shift=None,
+                             fftshift=False, out=None):
+        """spectrogram_iq_mixed() with the coefficients gathered from this table (bhw_stft_cmfft_f32_from_table with BHW_CFFT_POWER):
+        no allocation by the library, no synchronisation, capturable into a graph on its first call."""
+        return _stft_iq(_torch(), params, x, n_fft, hop, win_length, center, pad_mode, detrend, shift, fftshift, out, self.device,
+                        self._live(), True, True)
 
     def istft(self, params, Y, n_fft, hop, *, win_length=None, center=True, length=None, normalize=True, shift=None, out=None):
         """istft() with the coefficients gathered from this table (bhw_istft_fft_f32_from_table): no allocation by the library, no

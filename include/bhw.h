@@ -966,6 +966,32 @@ int bhw_stft_cfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t leng
                                  const void *d_x, void *d_Y);
 int bhw_describe_stft_cfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf, uint64_t len);
 
+/* Mixed-radix fused window and complex FFT for interleaved I/Q input: bhw_stft_cfft_f32_* at n_fft = 2^a 3^b 5^c that is NOT a power
+ * of two, 16 <= n_fft <= 2047, odd lengths included (91 sizes: 18, 20, 24, 25, 27, ... 2000, 2025).  The arguments, the flags
+ * (BHW_WELCH_DETREND_CONSTANT | BHW_CFFT_POWER | BHW_CFFT_SHIFT), the row contract, the output forms, the strides, determinism, the
+ * IEEE rule, capture and the order of the checks are those of bhw_stft_cfft_f32_* word for word; what differs:
+ *   - Supported: channels 2 and the n_fft above.  Three refusals are BHW_ERR_UNSUPPORTED and each names the route that takes the
+ *     call: a power of two (bhw_stft_cfft_f32_*: one transform per n_fft), channels 1 (bhw_stft_mfft_f32_*), any other n_fft (the
+ *     set).  The upper end is the I/Q kernel's: 8 complex columns per lane on 256 lanes.
+ *   - The transform is NOT pinned bit for bit.  Y[k] = sum over j of row[j] * exp(-2 pi i j k / n_fft), k < n_fft.  It is a float32
+ *     Stockham transform of n_fft complex points in the passes of bhw_stft_mfft_f32_* applied to n_fft itself (radix 5, then 3, then
+ *     4, then one radix-2 pass; seven passes at most), without a split pass; every twiddle factor is the float32 rounding of a
+ *     binary64 cosine or sine, read from one table at an exact index and never a product.  Its error is that of a float32 FFT
+ *     (relative l2 error of a row of the order of 2^-24 * log2(n_fft) at most); the tests hold it to twice the error of rocFFT on
+ *     the same rows.
+ *   - BHW_CFFT_SHIFT: column j holds bin (j + n_fft - n_fft / 2) mod n_fft, that is bin k goes to column (k + n_fft / 2) mod n_fft
+ *     with integer division: torch.fft.fftshift along the bins, for an odd n_fft too.
+ *   - Not built: accumulating over frames in the kernel (Welch) and the inverse at these lengths; a filter bank on the I/Q power
+ *     rows; prime factors of 7 and above; n_fft >= 2048.
+ *   - bhw_describe_stft_cmfft: bhw_describe_stft_cfft's line in the same words ("stft cmfft ..."), with the mixed-radix schedule
+ *     ("5x5x4x4") and the entries of the twiddle table (n_fft / 2 for an even n_fft, n_fft for an odd one).  t may be NULL (the
+ *     library call).  Host arithmetic only. */
+int bhw_stft_cmfft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                              const void *d_x, void *d_Y);
+int bhw_stft_cmfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                  const void *d_x, void *d_Y);
+int bhw_describe_stft_cmfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf, uint64_t len);
+
 /* Fused inverse complex FFT, window and overlap-add for I/Q output: torch.fft.ifft in front of bhw_istft_ola_f32_* with channels 2,
  * by ONE launch -- the inverse of bhw_stft_cfft_f32_*.  A group of lanes owns a span of a signal's time axis, reads the n_fft bins of
  * every frame that reaches it, transforms them in LDS, and adds the windowed row into binary64 accumulators that it stores once.
