@@ -52,6 +52,7 @@ ABI_SYMBOLS = (
     "bhw_stft_cfft_f32_device", "bhw_stft_cfft_f32_from_table", "bhw_describe_stft_cfft",
     "bhw_istft_cfft_f32_device", "bhw_istft_cfft_f32_from_table", "bhw_describe_istft_cfft",
     "bhw_stft_cmfft_f32_device", "bhw_stft_cmfft_f32_from_table", "bhw_describe_stft_cmfft",
+    "bhw_istft_cmfft_f32_device", "bhw_istft_cmfft_f32_from_table", "bhw_describe_istft_cmfft",
     "bhw_welch_fft_workspace_bytes", "bhw_welch_fft_f32_device", "bhw_welch_fft_f32_from_table", "bhw_describe_welch_fft",
     "bhw_csd_fft_workspace_bytes", "bhw_csd_fft_f32_device", "bhw_csd_fft_f32_from_table", "bhw_describe_csd_fft",
     "bhw_welch_cfft_workspace_bytes", "bhw_welch_cfft_f32_device", "bhw_welch_cfft_f32_from_table", "bhw_describe_welch_cfft",
@@ -340,6 +341,9 @@ def lib():
     L.bhw_istft_cfft_f32_device.argtypes = [P, u64, ci, vp, S, u32, f32p, f32p]
     L.bhw_istft_cfft_f32_from_table.argtypes = [T, P, u64, vp, S, u32, f32p, f32p]
     L.bhw_describe_istft_cfft.argtypes = [T, P, u64, S, u32, ctypes.c_char_p, u64]
+    L.bhw_istft_cmfft_f32_device.argtypes = [P, u64, ci, vp, S, u32, f32p, f32p]
+    L.bhw_istft_cmfft_f32_from_table.argtypes = [T, P, u64, vp, S, u32, f32p, f32p]
+    L.bhw_describe_istft_cmfft.argtypes = [T, P, u64, S, u32, ctypes.c_char_p, u64]
     f64 = ctypes.c_double
     L.bhw_welch_fft_workspace_bytes.restype = u64
     L.bhw_welch_fft_workspace_bytes.argtypes = [S]
@@ -647,6 +651,17 @@ def describe_istft_cfft(params, length, stft, *, normalize=False, fftshift=False
     buf = ctypes.create_string_buffer(1024)
     flags = (OLA_NORMALIZE if normalize else 0) | (CFFT_SHIFT if fftshift else 0)
     check(lib().bhw_describe_istft_cfft(table, ctypes.byref(params), int(length), ctypes.byref(stft), flags, buf, len(buf)))
+    return buf.value.decode()
+
+
+def describe_istft_cmfft(params, length, stft, *, normalize=False, fftshift=False, table=None):
+    """One line: the plan fields of describe_istft_cfft in the same words for the inverse mixed-radix complex transform of I/Q rows
+    (the schedule of radix-5, -3, -4 and -2 passes over n_fft points, no split pass), the entries of the twiddle table, whether the
+    bins are shifted, and the kernel (bhw_describe_istft_cmfft).  `stft` is a BhwStft with channels 2 whose y strides count floats of
+    spectrum rows; `table` is a resident table handle or None for the library call.  Host arithmetic only."""
+    buf = ctypes.create_string_buffer(1024)
+    flags = (OLA_NORMALIZE if normalize else 0) | (CFFT_SHIFT if fftshift else 0)
+    check(lib().bhw_describe_istft_cmfft(table, ctypes.byref(params), int(length), ctypes.byref(stft), flags, buf, len(buf)))
     return buf.value.decode()
 
 

@@ -1294,6 +1294,20 @@ int istft_cfft_run(bhw_table t, const bhw_params *p, uint64_t length, int device
                                                               const BhwLenPhase *lp) { return bhwk_istft_cfft_f32(l, c, w, pl, s, d_Y, d_x, tab, *lp); });
 }
 
+// The mixed-radix fused inverse complex FFT + overlap-add for I/Q output (t NULL: the direct CORDIC chains): the checks, then the one
+// kernel.
+int istft_cmfft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *s, uint32_t flags,
+                    const float *d_Y, float *d_x)
+{
+    int rc = bhwp_istft_cmfft_checks(p, length, s, flags, d_Y, d_x);
+    if (!rc && t) rc = table_call_checks(t, p);
+    if (rc || !s->samples) return rc;
+    const BhwIstftCmfftPlan pl = bhwp_istft_cmfft_plan(p, length, s, flags, t != nullptr);
+    const char *what = t ? "istft cmfft launch (resident table)" : "istft cmfft launch";
+    return run_source(t, p, length, device, stream, what, [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *tab,
+                                                              const BhwLenPhase *lp) { return bhwk_istft_cmfft_f32(l, c, w, pl, s, d_Y, d_x, tab, *lp); });
+}
+
 // The window sums (t NULL: the direct CORDIC chains): the checks, then the memset of the four words and the reduction.
 int window_sums_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, uint32_t flags, uint64_t *d_sums)
 {
@@ -1783,6 +1797,29 @@ int bhw_describe_istft_cfft(bhw_table t, const bhw_params *p, uint64_t length, c
     int rc = bhwp_istft_cfft_checks(p, length, s, flags, nullptr, nullptr, false);
     if (!rc && t) rc = table_call_checks(t, p);
     return rc ? rc : bhwp_describe_istft_cfft(p, t ? &t->c : nullptr, length, s, flags, buf, len);
+}
+
+// ---- fused inverse mixed-radix complex FFT, window and overlap-add for I/Q output (include/bhw.h: bhw_istft_cmfft_f32_device ...) -------
+
+int bhw_istft_cmfft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                               const float *d_Y, float *d_x)
+{
+    return istft_cmfft_run(nullptr, p, length, device, hip_stream, s, flags, d_Y, d_x);
+}
+
+int bhw_istft_cmfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                   const float *d_Y, float *d_x)
+{
+    const int rc = bhwp_istft_cmfft_checks(p, length, s, flags, d_Y, d_x);
+    if (rc) return rc;
+    return t ? istft_cmfft_run(t, p, length, t->device, hip_stream, s, flags, d_Y, d_x) : fail(BHW_ERR_BADARG, "table is NULL");
+}
+
+int bhw_describe_istft_cmfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf, uint64_t len)
+{
+    int rc = bhwp_istft_cmfft_checks(p, length, s, flags, nullptr, nullptr, false);
+    if (!rc && t) rc = table_call_checks(t, p);
+    return rc ? rc : bhwp_describe_istft_cmfft(p, t ? &t->c : nullptr, length, s, flags, buf, len);
 }
 
 // ---- Welch's method (include/bhw.h: bhw_window_sums_device ...) ------------------------------------------------------------------------

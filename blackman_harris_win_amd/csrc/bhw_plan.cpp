@@ -2907,8 +2907,9 @@ int bhwp_describe_istft_mfft(const bhw_params *p, const BhwCordicCfg *ct, uint64
 
 // ---- fused inverse complex FFT, window and overlap-add for I/Q output ----------------------------------------------------------------------
 
-int bhwp_istft_cfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const void *d_Y, const void *d_x,
-                           bool pointers)
+// Steps 1 and 2 of the I/Q inverse calls (bhw_istft_cfft_f32_*, bhw_istft_cmfft_f32_*): the descriptor as the overlap-add checks it,
+// then the flag bits.
+static int iq_inverse_descriptor_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags)
 {
     // 1. what the overlap-add checks, for the same descriptor with packed rows (the input strides are checked below; the shift bit is
     //    this call's own)
@@ -2921,15 +2922,14 @@ int bhwp_istft_cfft_checks(const bhw_params *p, uint64_t length, const bhw_stft 
     t.y_stride = t.y_batch_stride = 0;
     rc = bhwp_stft_checks(p, length, &t, true, ola_flags, nullptr, nullptr, false);
     if (rc) return rc;
-    // 2., 3.
+    // 2.
     if (flags & ~kIcfftFlags) return bhwp_fail(BHW_ERR_BADARG, "flags 0x%x (BHW_OLA_NORMALIZE, BHW_CFFT_SHIFT)", flags);
-    if (s->channels != 2)
-        return bhwp_fail(BHW_ERR_UNSUPPORTED, "channels %u: the fused inverse complex FFT gives interleaved I/Q output (2); real output: "
-                                              "bhw_istft_fft_f32_*", s->channels);
-    if ((s->n_fft & (s->n_fft - 1)) || s->n_fft < (1ull << kCfftMinLog) || s->n_fft > (1ull << kCfftMaxLog))
-        return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu: the fused inverse complex FFT takes a power of two in %u..%u",
-                         (unsigned long long)s->n_fft, 1u << kCfftMinLog, 1u << kCfftMaxLog);
-    // 4., 5.
+    return BHW_OK;
+}
+
+// Steps 4 and 5 of the same calls: samples 0, the stride rules of the spectrum rows, the pointers.
+static int iq_inverse_io_checks(const bhw_stft *s, const void *d_Y, const void *d_x, bool pointers)
+{
     const uint64_t T = s->samples, F = s->frames, W = 2 * s->n_fft;           // floats of a spectrum row
     if (!T) return BHW_OK;
     if (s->y_stride && (s->y_stride < W || s->y_stride % 2))
@@ -2952,6 +2952,22 @@ int bhwp_istft_cfft_checks(const bhw_params *p, uint64_t length, const bhw_stft 
     if (xa > UINT64_MAX - xb || ya > UINT64_MAX - yb) return bhwp_fail(BHW_ERR_BADARG, "x or Y range wraps the address space");
     if (xa < ya + yb && ya < xa + xb) return bhwp_fail(BHW_ERR_BADARG, "d_Y and d_x overlap");
     return BHW_OK;
+}
+
+int bhwp_istft_cfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const void *d_Y, const void *d_x,
+                           bool pointers)
+{
+    const int rc = iq_inverse_descriptor_checks(p, length, s, flags);
+    if (rc) return rc;
+    // 3.
+    if (s->channels != 2)
+        return bhwp_fail(BHW_ERR_UNSUPPORTED, "channels %u: the fused inverse complex FFT gives interleaved I/Q output (2); real output: "
+                                              "bhw_istft_fft_f32_*", s->channels);
+    if ((s->n_fft & (s->n_fft - 1)) || s->n_fft < (1ull << kCfftMinLog) || s->n_fft > (1ull << kCfftMaxLog))
+        return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu: the fused inverse complex FFT takes a power of two in %u..%u",
+                         (unsigned long long)s->n_fft, 1u << kCfftMinLog, 1u << kCfftMaxLog);
+    // 4., 5.
+    return iq_inverse_io_checks(s, d_Y, d_x, pointers);
 }
 
 BhwIstftCfftPlan bhwp_istft_cfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, bool from_table)
@@ -3019,6 +3035,96 @@ int bhwp_describe_istft_cfft(const bhw_params *p, const BhwCordicCfg *ct, uint64
              (unsigned long long)s->frames, (unsigned long long)(s->batch * s->frames), pl.n, sched, pl.lpf, pl.fy, pl.cpl,
              (unsigned long long)pl.span, (unsigned long long)pl.halo, (unsigned long long)pl.spans, (unsigned long long)pl.trips,
              (unsigned long long)repeat, (unsigned long long)pl.groups, (unsigned long long)pl.grid, kFftBlock, pl.lds_bytes,
+             few ? "; heavy overlap: the halo sets S and few workgroups run (ifft + istft overlap-add may be faster)" : "");
+    return BHW_OK;
+}
+
+// ---- fused inverse mixed-radix complex FFT, window and overlap-add for I/Q output ----------------------------------------------------------
+
+int bhwp_istft_cmfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const void *d_Y, const void *d_x,
+                            bool pointers)
+{
+    const int rc = iq_inverse_descriptor_checks(p, length, s, flags);
+    if (rc) return rc;
+    // 3.: each refusal names the route that takes the call
+    if (s->channels != 2)
+        return bhwp_fail(BHW_ERR_UNSUPPORTED, "channels %u: the mixed-radix fused inverse complex FFT gives interleaved I/Q output (2); real "
+                                              "output: bhw_istft_mfft_f32_*", s->channels);
+    if (!(s->n_fft & (s->n_fft - 1)))
+        return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu is a power of two: bhw_istft_cfft_f32_* transforms it (one transform per n_fft)",
+                         (unsigned long long)s->n_fft);
+    if (!bhwp_cmfft_supported(s->n_fft))
+        return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu: the mixed-radix fused inverse complex FFT takes 2^a 3^b 5^c in %u..%u",
+                         (unsigned long long)s->n_fft, kCmfftMinN, kCmfftMaxN);
+    // 4., 5.
+    return iq_inverse_io_checks(s, d_Y, d_x, pointers);
+}
+
+BhwIstftCmfftPlan bhwp_istft_cmfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, bool from_table)
+{
+    // the lane layout, the radix schedule and the twiddle-table form are the forward's
+    bhw_stft fw = *s;
+    fw.frames = 0;
+    const BhwStftCmfftPlan f = bhwp_stft_cmfft_plan(p, length, &fw, 0, from_table);
+    BhwIstftCmfftPlan pl{};
+    pl.route = f.route;
+    pl.normalize = (flags & BHW_OLA_NORMALIZE) != 0;
+    pl.shifted = (flags & BHW_CFFT_SHIFT) != 0;
+    pl.n = f.n;
+    pl.fold = f.fold;
+    pl.lpf = f.lpf;
+    pl.fy = f.fy;
+    pl.cpl = f.cpl;
+    pl.passes = f.passes;
+    for (uint32_t i = 0; i < f.passes; ++i) pl.radix[i] = f.radix[i];
+    pl.lds_bytes = 2u * pl.fy * pl.n * 8u + pl.fold * 8u + pl.n * 4u;
+    pl.len = length;
+    pl.x_stride = s->x_stride ? s->x_stride : 2 * s->samples;
+    pl.y_stride = s->y_stride ? s->y_stride : 2 * s->n_fft;
+    pl.y_bstride = s->y_batch_stride ? s->y_batch_stride : s->frames * pl.y_stride;
+    const IstftSpans sp = istft_spans(length, s, pl.fy);
+    pl.t0 = sp.t0;
+    pl.hop = sp.hop;
+    pl.halo = sp.halo;
+    pl.halo_bound = sp.halo_bound;
+    pl.span = sp.span;
+    pl.spans = sp.spans;
+    pl.groups = sp.groups;
+    pl.grid = sp.grid;
+    pl.trips = sp.trips;
+    return pl;
+}
+
+int bhwp_describe_istft_cmfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf,
+                              uint64_t len)
+{
+    if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
+    const char *route = ct ? "table" : "direct";
+    const char *norm = (flags & BHW_OLA_NORMALIZE) ? "normalised by the window envelope" : "not normalised";
+    const char *bins = (flags & BHW_CFFT_SHIFT) ? "bins shifted" : "bins in order";
+    if (!s->samples) {
+        snprintf(buf, len, "istft cmfft %s (L = %llu, n_fft %llu), %s, %s: nothing (samples 0)", route, (unsigned long long)length,
+                 (unsigned long long)s->n_fft, norm, bins);
+        return BHW_OK;
+    }
+    const BhwIstftCmfftPlan pl = bhwp_istft_cmfft_plan(p, length, s, flags, ct != nullptr);
+    BhwStftMfftPlan f{};
+    f.passes = pl.passes;
+    for (uint32_t i = 0; i < pl.passes; ++i) f.radix[i] = pl.radix[i];
+    char kern[64], sched[48];
+    kernel_name(p, ct, "k_istft_cmfft_direct", "k_istft_cmfft_table", false, kern, sizeof kern);
+    bhwp_stft_mfft_schedule(f, sched, sizeof sched);
+    // the repeats: every span but a signal's first transforms up to `halo` frames that the span before it transforms too
+    const uint64_t repeat = pl.spans > 1 ? 100 * pl.halo / (pl.span + pl.halo) : 0;
+    const bool few = pl.halo_bound && pl.groups < kIfftTargetGroups / 4;
+    snprintf(buf, len, "istft cmfft %s (L = %llu, n_fft %llu, col0 %llu, pad %llu: t0 = %llu), %s, %s: %s, %llu signals x %llu frames = %llu rows, "
+             "inverse complex FFT of %u points in passes %s (no split), %u lanes per row x %u spans per workgroup, %u columns per lane, "
+             "spans of S = %llu frames + halo %llu (%llu spans per signal, up to %llu frames a span, %llu%% of the transforms repeated), "
+             "%llu groups, grid %llu x %u lanes, %u bytes of LDS, %u twiddles%s", route, (unsigned long long)length,
+             (unsigned long long)s->n_fft, (unsigned long long)s->col0, (unsigned long long)s->pad, (unsigned long long)pl.t0, norm, bins, kern,
+             (unsigned long long)s->batch, (unsigned long long)s->frames, (unsigned long long)(s->batch * s->frames), pl.n, sched, pl.lpf, pl.fy,
+             pl.cpl, (unsigned long long)pl.span, (unsigned long long)pl.halo, (unsigned long long)pl.spans, (unsigned long long)pl.trips,
+             (unsigned long long)repeat, (unsigned long long)pl.groups, (unsigned long long)pl.grid, kFftBlock, pl.lds_bytes, pl.fold,
              few ? "; heavy overlap: the halo sets S and few workgroups run (ifft + istft overlap-add may be faster)" : "");
     return BHW_OK;
 }

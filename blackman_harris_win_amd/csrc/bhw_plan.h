@@ -865,6 +865,36 @@ int  bhwp_describe_istft_cfft(const bhw_params *p, const BhwCordicCfg *ct, uint6
 int  bhwk_istft_cfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwIstftCfftPlan &pl, const bhw_stft *s,
                          const float *d_Y, float *d_x, const int32_t *d_table, const BhwLenPhase &lp);
 
+// ---- fused inverse mixed-radix complex FFT, window and overlap-add for I/Q output (bhw_istft_cmfft_f32_*; bhw_istft_cmfft.hip) --------
+// The lane layout, the radix schedule and the twiddle-table form of bhwp_stft_cmfft_plan (lpf lanes along a row of n = n_fft complex
+// points, fy slots side by side, cpl = ceil(n / lpf) <= kCfftMaxCpl ring positions per lane, the last of which need not exist; fold
+// entries of the FORWARD table exp(-2 pi i k / n): the kernel swaps the parts of its input and of its result instead of conjugating
+// the transform) under the spans of bhwp_istft_fft_plan: the same S, halo, trips, halo_bound, grid cap and hop clamp, from one
+// function (istft_spans in bhw_plan.cpp), and bhwp_istft_span as it is.  A lane keeps cpl ring positions of two binary64 sums
+// (re, im) and one envelope sum.  LDS: the two Stockham buffers of fy * n complex64, the fold twiddles and the n floats of the
+// window: 48 000 bytes at 2000, 56 700 at 2025, the largest.
+struct BhwIstftCmfftPlan {
+    int route;            // BHWP_FRAMES_DIRECT or BHWP_FRAMES_TABLE
+    bool normalize, shifted;
+    uint32_t n, fold, lpf, fy, cpl, passes;            // as BhwStftCmfftPlan
+    uint8_t radix[kMfftMaxPasses];
+    uint32_t lds_bytes;   // 2 * fy * n * 8 + fold * 8 + n * 4  (<= 56 700)
+    uint64_t t0, hop, halo, span, spans, groups, grid, trips;   // as BhwIstftFftPlan
+    bool halo_bound;
+    uint64_t x_stride, y_stride, y_bstride;   // resolved, in floats (0 -> 2 * samples, 2 * n_fft, frames * y_stride)
+    uint64_t len;         // L
+};
+// Every check of the two calls that needs no table handle, before any HIP call and in the order of bhwp_istft_cfft_checks.  samples 0
+// passes with the strides and the pointers unchecked; `pointers` false: the describe call.
+int  bhwp_istft_cmfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const void *d_Y, const void *d_x,
+                             bool pointers = true);
+// the plan of a call that passed the checks with samples > 0
+BhwIstftCmfftPlan bhwp_istft_cmfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, bool from_table);
+int  bhwp_describe_istft_cmfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf,
+                               uint64_t len);
+int  bhwk_istft_cmfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwIstftCmfftPlan &pl, const bhw_stft *s,
+                          const float *d_Y, float *d_x, const int32_t *d_table, const BhwLenPhase &lp);
+
 // the generate kernel of a window of any length (bhw_len.hip): d_table NULL = k_direct_len, else k_range_len over the resident table of c
 int  bhwk_len_range(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *d_table, const BhwLenPhase &lp,
                     uint64_t n0, uint64_t count, int32_t *d_out);

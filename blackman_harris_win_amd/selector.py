@@ -701,17 +701,34 @@ def _imfft_input(torch, Y, dev):
         raise ValueError("Y must be (frames, K) or (B, frames, K)")
 
 
+def _icmfft_input(torch, Y, dev):
+    """_icfft_input for istft_iq_mixed(): two-sided complex64 spectra (frames, n_fft) or (B, frames, n_fft).  The device is checked at
+    the launch (_istft), after every check that needs none."""
+    if not isinstance(Y, torch.Tensor) or Y.dtype != torch.complex64:
+        got = Y.dtype if isinstance(Y, torch.Tensor) else type(Y).__name__
+        raise ValueError(f"the mixed-radix fused inverse complex FFT takes two-sided complex64 spectra, got {got} (one-sided spectra: "
+                         f"istft_mixed)")
+    if Y.dim() not in (2, 3):
+        raise ValueError("Y must be (frames, n_fft) or (B, frames, n_fft)")
+
+
 def _istft(torch, params, Y, n_fft, hop, win_length, center, length, normalize, shift, out, dev, table, check=_ifft_input,
            dtype=None, fftshift=False):
-    """The body istft(), istft_mixed() and istft_iq() share.  check: _ifft_input, _imfft_input for the mixed-radix lengths, or
-    _icfft_input for I/Q output; dtype: the output's, float32 (the one-sided spectra of istft) by default, complex64 for the two-sided
-    spectra of istft_iq."""
+    """The body istft(), istft_mixed(), istft_iq() and istft_iq_mixed() share.  check: _ifft_input, _imfft_input for the mixed-radix
+    lengths, _icfft_input for I/Q output or _icmfft_input for I/Q output at the mixed-radix lengths; dtype: the output's, float32 (the
+    one-sided spectra of istft) by default, complex64 for the two-sided spectra of istft_iq and istft_iq_mixed."""
     dtype = torch.float32 if dtype is None else dtype
     iq = dtype == torch.complex64
     mixed = check is _imfft_input
+    cmixed = check is _icmfft_input
     check(torch, Y, dev)
     n_fft, L, col0 = _stft_window(params, n_fft, win_length)
-    if iq and not B.cfft_supported(n_fft):
+    if cmixed and B.cfft_supported(n_fft):
+        raise ValueError(f"n_fft {n_fft} is a power of two: bhw.istft_iq transforms it (one transform per n_fft)")
+    if cmixed and not B.cmfft_supported(n_fft):
+        raise ValueError(f"the mixed-radix fused inverse complex FFT takes n_fft = 2^a 3^b 5^c in {B.CMFFT_MIN_N}..{B.CMFFT_MAX_N} that is "
+                         f"no power of two, got {n_fft}")
+    if iq and not cmixed and not B.cfft_supported(n_fft):
         raise ValueError(f"the fused inverse complex FFT takes n_fft a power of two in {B.CFFT_MIN_N}..{B.CFFT_MAX_N}, got {n_fft}")
     if mixed and B.fft_supported(n_fft):
         raise ValueError(f"n_fft {n_fft} is a power of two: bhw.istft transforms it (one transform per n_fft)")
@@ -728,7 +745,8 @@ def _istft(torch, params, Y, n_fft, hop, win_length, center, length, normalize, 
     Yb = Y if Y.dim() == 3 else Y.unsqueeze(0)
     nb, frames, K = Yb.shape
     if iq and K != n_fft:
-        raise ValueError(f"Y rows hold {K} bins, the two-sided spectrum of n_fft {n_fft} has {n_fft} (one-sided spectra: istft)")
+        raise ValueError(f"Y rows hold {K} bins, the two-sided spectrum of n_fft {n_fft} has {n_fft} (one-sided spectra: "
+                         f"{'istft_mixed' if cmixed else 'istft'})")
     if not iq and K != n_fft // 2 + 1:
         raise ValueError(f"Y rows hold {K} bins, n_fft // 2 + 1 is {n_fft // 2 + 1}")
     if frames < 1 or nb < 1:
@@ -752,7 +770,8 @@ def _istft(torch, params, Y, n_fft, hop, win_length, center, length, normalize, 
     flags = (B.OLA_NORMALIZE if normalize else 0) | (B.CFFT_SHIFT if fftshift else 0)
     tail = (ctypes.byref(s), flags, ctypes.c_void_p(Yb.data_ptr()), ctypes.c_void_p(out.data_ptr()))
     L_ = B.lib()
-    device_call, table_call = (L_.bhw_istft_cfft_f32_device, L_.bhw_istft_cfft_f32_from_table) if iq else \
+    device_call, table_call = (L_.bhw_istft_cmfft_f32_device, L_.bhw_istft_cmfft_f32_from_table) if cmixed else \
+        (L_.bhw_istft_cfft_f32_device, L_.bhw_istft_cfft_f32_from_table) if iq else \
         (L_.bhw_istft_mfft_f32_device, L_.bhw_istft_mfft_f32_from_table) if mixed else \
         (L_.bhw_istft_fft_f32_device, L_.bhw_istft_fft_f32_from_table)
     if table is None:
@@ -814,6 +833,25 @@ def istft_iq(params, Y, n_fft, hop, *, win_length=None, center=True, length=None
     torch = _torch()
     dev = Y.device.index if isinstance(Y, torch.Tensor) and Y.is_cuda else None
     return _istft(torch, params, Y, n_fft, hop, win_length, center, length, normalize, shift, out, dev, None, _icfft_input,
+                  torch.complex64, fftshift)
+
+
+def istft_iq_mixed(params, Y, n_fft, hop, *, win_length=None, center=True, length=None, normalize=True, shift=None, fftshift=False,
+                   out=None):
+    """istft_iq() at the n_fft of stft_iq_mixed() in ONE launch (bhw_istft_cmfft_f32_device): Y (B, F, n_fft) or (F, n_fft), complex64,
+    all n_fft bins -- the layout stft_iq_mixed() returns -- for n_fft 2^a·3^b·5^c in 16..2047 and not a power of two, odd lengths
+    included (1536, 1200, 600, 300, 1000, 2000, 480, 960, 75, ...; ValueError otherwise, and a power of two names istft_iq()).  Every
+    row is transformed as torch.fft.ifft does by a float32 mixed-radix complex FFT in LDS (the 1 / n_fft scaling is one float32
+    multiply of each part by fl32(1 / n_fft)) and summed exactly as istft_overlap_add() sums complex time rows: in ascending frame
+    order in binary64 per part, times v (window(params, win_length, dtype=torch.float32, shift=shift)), and with normalize=True divided
+    by the window envelope (+0.0 where no frame reaches).  The time rows never reach memory.  fftshift=True reads rows whose column
+    (k + n_fft // 2) % n_fft holds bin k, what stft_iq_mixed(fftshift=True) writes (torch.fft.fftshift along the bins, for an odd
+    n_fft too).  Keywords, the default length, the treatment of views and `out` are istft_iq()'s.  With heavy overlap and little work
+    (see describe_istft_cmfft) few workgroups run; torch.fft.ifft + istft_overlap_add remains for that case, and this call does not
+    reroute to it."""
+    torch = _torch()
+    dev = Y.device.index if isinstance(Y, torch.Tensor) and Y.is_cuda else None
+    return _istft(torch, params, Y, n_fft, hop, win_length, center, length, normalize, shift, out, dev, None, _icmfft_input,
                   torch.complex64, fftshift)
 
 
@@ -2193,6 +2231,14 @@ class ResidentTable:
         torch = _torch()
         return _istft(torch, params, Y, n_fft, hop, win_length, center, length, normalize, shift, out, self.device, self._live(),
                       _icfft_input, torch.complex64, fftshift)
+
+    def istft_iq_mixed(self, params, Y, n_fft, hop, *, win_length=None, center=True, length=None, normalize=True, shift=None,
+                       fftshift=False, out=None):
+        """istft_iq_mixed() with the coefficients gathered from this table (bhw_istft_cmfft_f32_from_table): no allocation by the
+        library, no synchronisation, capturable into a graph on its first call."""
+        torch = _torch()
+        return _istft(torch, params, Y, n_fft, hop, win_length, center, length, normalize, shift, out, self.device, self._live(),
+                      _icmfft_input, torch.complex64, fftshift)
 
     def istft_overlap_add(self, params, y, n_fft, hop, *, win_length=None, center=True, length=None, normalize=True, shift=None,
                           out=None):

@@ -981,8 +981,8 @@ int bhw_describe_stft_cfft(bhw_table t, const bhw_params *p, uint64_t length, co
  *     the same rows.
  *   - BHW_CFFT_SHIFT: column j holds bin (j + n_fft - n_fft / 2) mod n_fft, that is bin k goes to column (k + n_fft / 2) mod n_fft
  *     with integer division: torch.fft.fftshift along the bins, for an odd n_fft too.
- *   - Not built: accumulating over frames in the kernel (Welch) and the inverse at these lengths; a filter bank on the I/Q power
- *     rows; prime factors of 7 and above; n_fft >= 2048.
+ *   - Not built: accumulating over frames in the kernel (Welch) at these lengths; a filter bank on the I/Q power rows; prime
+ *     factors of 7 and above; n_fft >= 2048.  The inverse is bhw_istft_cmfft_f32_* below.
  *   - bhw_describe_stft_cmfft: bhw_describe_stft_cfft's line in the same words ("stft cmfft ..."), with the mixed-radix schedule
  *     ("5x5x4x4") and the entries of the twiddle table (n_fft / 2 for an even n_fft, n_fft for an odd one).  t may be NULL (the
  *     library call).  Host arithmetic only. */
@@ -1042,6 +1042,37 @@ int bhw_istft_cfft_f32_device(const bhw_params *p, uint64_t length, int device, 
 int bhw_istft_cfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
                                   const float *d_Y, float *d_x);
 int bhw_describe_istft_cfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf, uint64_t len);
+
+/* Fused inverse mixed-radix complex FFT, window and overlap-add for I/Q output: bhw_istft_cfft_f32_* at the n_fft of
+ * bhw_stft_cmfft_f32_* -- the inverse of that call, by ONE launch.  The arguments, the two flags (BHW_OLA_NORMALIZE |
+ * BHW_CFFT_SHIFT; any other bit is BHW_ERR_BADARG), the sum (ascending f, binary64 from +0.0, S_c per part and one E, fl32(S_c / E)
+ * where E > 0 under normalisation, +0.0 where no frame reaches), the descriptor and stride rules (y_stride in floats, even, default
+ * 2 * n_fft; any x_stride from 2 * samples, odd ones included; d_x 4-byte aligned), determinism, the IEEE rule, the order of the
+ * checks and the capture statement (no allocation, no workspace, no bhw_prepare_device; both forms capturable on their first call)
+ * are those of bhw_istft_cfft_f32_* word for word; what differs:
+ *   - Supported: channels 2 and exactly the n_fft of bhw_stft_cmfft_f32_*: 2^a 3^b 5^c in 16..2047 that is NOT a power of two (91
+ *     sizes, 18 of them odd).  One transform per n_fft.  Three refusals are BHW_ERR_UNSUPPORTED and each names the route that takes
+ *     the call: channels 1 (bhw_istft_mfft_f32_*), a power of two (bhw_istft_cfft_f32_*), any other n_fft (the set).
+ *   - The row.  r[j], j < n_fft, is the float32 inverse transform of the n_fft bins of (b, f) with the sign and the scaling of
+ *     torch.fft.ifft.  1 / n_fft is no power of two here: as in bhw_istft_mfft_f32_* the scaling is ONE float32 multiply of the
+ *     transform's float32 result by c = (float)(1.0 / (double) n_fft), applied to each part -- one rounding more than
+ *     bhw_istft_cfft_f32_*.  The transform is NOT pinned bit for bit: it is the forward float32 Stockham transform of
+ *     bhw_stft_cmfft_f32_* (radix 5, then 3, then 4, then one radix-2 pass; every twiddle factor the float32 rounding of a binary64
+ *     cosine or sine, read from one table at an exact index) applied to the bins with their parts swapped, and its result read with
+ *     the parts swapped again: n_fft * IDFT(Y) = swap(DFT(swap(Y))).  The bits of a row depend on its bins, n_fft and the shift flag
+ *     only.
+ *   - BHW_CFFT_SHIFT: bin k is read from column (k + n_fft / 2) mod n_fft with integer division, that is column j holds bin
+ *     (j + n_fft - n_fft / 2) mod n_fft -- what bhw_stft_cmfft_f32_* writes under the same flag (torch.fft.fftshift along the bins),
+ *     for an odd n_fft too.  A load index (a compare and a subtract), not a pass.
+ *   - Not built: n_fft >= 2048; prime factors of 7 and above; a fast path under heavy overlap; rerouting by n_fft inside
+ *     bhw_istft_cfft_f32_*.
+ *   - bhw_describe_istft_cmfft: bhw_describe_istft_cfft's line in the same words ("istft cmfft ..."), with the mixed-radix schedule
+ *     and the entries of the twiddle table.  t may be NULL (the library call).  Host arithmetic only. */
+int bhw_istft_cmfft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                               const float *d_Y, float *d_x);
+int bhw_istft_cmfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                   const float *d_Y, float *d_x);
+int bhw_describe_istft_cmfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf, uint64_t len);
 
 /* Fused Welch PSD: window, real FFT and the average over the frames by ONE kernel and a small join.  The rows of bhw_stft_fft_f32_*
  * are formed and transformed by the same kernel body, and |Y|^2 is accumulated over the frames where the transform ends, so the
