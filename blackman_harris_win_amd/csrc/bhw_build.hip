@@ -261,7 +261,7 @@ __device__ __forceinline__ void rot_narrow(uint32_t &x, uint32_t &y, int32_t &z,
 // in the first four workgroups; on the 64-bit path they kept the whole pass waiting 6 us for those four,
 // profiles/r04_build_timeline.txt.)
 template <int KA, int NITER>
-__device__ __forceinline__ void rot_narrow_block(uint32_t &x, uint32_t &y, int32_t &z, uint32_t &zacc, const uint32_t *lut, int e, uint32_t hi)
+__device__ __forceinline__ void rot_narrow_block(uint32_t &x, uint32_t &y, int32_t &z, uint32_t &zacc, const uint32_t (&l)[10], int e, uint32_t hi)
 {
     // Both forms in ONE statement behind a scalar branch on `hi` (labels 0 .. 10 plain, 20 .. 30 biased): as two statements in an
     // if / else the register allocator gave them different registers and joined them with four v_mov per group.
@@ -308,8 +308,8 @@ __device__ __forceinline__ void rot_narrow_block(uint32_t &x, uint32_t &y, int32
                  BHW_ROT_HI(0) BHW_ROT_HI(1) BHW_ROT_HI(2) BHW_ROT_HI(3) BHW_ROT_HI(4) BHW_ROT_HI(5) BHW_ROT_HI(6) BHW_ROT_HI(7) BHW_ROT_HI(8) BHW_ROT_HI(9)
                  "200:"
                  : [x] "+v"(x), [y] "+v"(y), [z] "+v"(z), [za] "+v"(zacc), [a] "=&v"(a), [b] "=&v"(b)
-                 : [e] "s"(e), [hi] "s"(hi), [l0] "s"(lut[KA]), [l1] "s"(lut[KA + 1]), [l2] "s"(lut[KA + 2]), [l3] "s"(lut[KA + 3]), [l4] "s"(lut[KA + 4]),
-                   [l5] "s"(lut[KA + 5]), [l6] "s"(lut[KA + 6]), [l7] "s"(lut[KA + 7]), [l8] "s"(lut[KA + 8]), [l9] "s"(lut[KA + 9]),
+                 : [e] "s"(e), [hi] "s"(hi), [l0] "s"(l[0]), [l1] "s"(l[1]), [l2] "s"(l[2]), [l3] "s"(l[3]), [l4] "s"(l[4]),
+                   [l5] "s"(l[5]), [l6] "s"(l[6]), [l7] "s"(l[7]), [l8] "s"(l[8]), [l9] "s"(l[9]),
                    [k0] "n"(KA), [k1] "n"(KA + 1), [k2] "n"(KA + 2), [k3] "n"(KA + 3), [k4] "n"(KA + 4), [k5] "n"(KA + 5), [k6] "n"(KA + 6),
                    [k7] "n"(KA + 7), [k8] "n"(KA + 8), [k9] "n"(KA + 9),
                    [c0] "n"(1 << S), [c1] "n"(1 << (S - 1)), [c2] "n"(1 << (S - 2)), [c3] "n"(1 << (S - 3)), [c4] "n"(1 << (S - 4)),
@@ -365,11 +365,11 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(8, 8)))
     constexpr uint32_t gpw = mirror_gpw(THREADS);               // own groups per workgroup
     constexpr uint32_t kHeads = mirror_heads_max(THREADS), kHeadsPad = mirror_heads_pad(THREADS);
     static_assert(gpw + 2 * kHeadsPad + 64 <= THREADS, "prefix lanes, two ranges of head chains, the tail-table wave");
-    __shared__ int64_t gx[gpw];
-    __shared__ int64_t gy[gpw];
-    __shared__ int32_t gz[gpw];
-    __shared__ int32_t gk[gpw];
-    __shared__ uint32_t gflag[gpw];                             // bit 0: leaf 0 met z == 0 inside the shared prefix; bit 1: narrow state; bit 2: ... with x biased
+    // parked group state, one 16-byte read per group in phase 2: {x, y (low words), z, k | flags << 8}; the high words of x and y apart
+    // (wide groups only).  flags bit 0: leaf 0 met z == 0 inside the shared prefix; bit 1: narrow state; bit 2: ... with x biased;
+    // bit 3: the table's group 0, whose leaf 0 has no image
+    __shared__ int4 gst[gpw];
+    __shared__ int2 ghi[gpw];
     __shared__ uint32_t lut_s[32];
     __shared__ uint8_t tail_p[2 * kTailZ];                      // z_KS + kTailZ -> decision pattern of the tail
     __shared__ __attribute__((aligned(16))) int8_t tail_d[kTailRows * 64 + 16];   // 65 rows of 64 patterns (+ padding to whole 16-byte packets)
@@ -494,11 +494,10 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(8, 8)))
         constexpr int64_t kBias = (int64_t)1 << (NITER - 1);
         const bool hi = !narrow && k >= KS - 10 && y >= drift && y + drift < lim && x - kBias >= drift && x - kBias + drift < ((int64_t)1 << 32) &&
                         x + drift < lim + ((int64_t)1 << KS);
-        gx[threadIdx.x] = hi ? x - kBias : x;
-        gy[threadIdx.x] = y;
-        gz[threadIdx.x] = zf;
-        gk[threadIdx.x] = k;
-        gflag[threadIdx.x] = zero0 | (narrow || hi ? 2u : 0u) | (hi ? 4u : 0u);
+        const int64_t xp = hi ? x - kBias : x;
+        const uint32_t flags = zero0 | (narrow || hi ? 2u : 0u) | (hi ? 4u : 0u) | (g == 0u ? 8u : 0u);
+        gst[threadIdx.x] = make_int4((int32_t)xp, (int32_t)y, zf, (int32_t)((uint32_t)k | (flags << 8)));
+        ghi[threadIdx.x] = make_int2((int32_t)(xp >> 32), (int32_t)(y >> 32));
         BHW_STAMP(11);                                               // prefixes done
     }
     BHW_STAMP(1);                                                    // last wave to reach the first barrier
@@ -529,12 +528,11 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(8, 8)))
     __syncthreads();
     BHW_STAMP_MIN(2);
     auto record_of = [&](int w, uint32_t cell) -> int4 { return hrec[w][cell - cell_lo[w]]; };   // cell in [cell_lo[w], cell_lo[w] + n_cell[w])
-    auto record = [&](int w, uint32_t cell) -> int4 {              // the same for a wave-uniform cell (a broadcast read)
-        return record_of(w, __builtin_amdgcn_readfirstlane(cell));
-    };
 
-    // one entry: deviation from the record's straight line, checked and packed
-    auto store_entry = [&](uint32_t idx, int32_t c, int32_t sn, const int4 rec, uint32_t pos) {
+    // one entry: deviation from the record's straight line, checked and packed.  CHECKED (std::true_type / std::false_type): whether
+    // the fields are tested against their width -- only while the format is not settled (plan.check_flag); a settled format's
+    // store carries no compare, no mask and no branch.  (The escape list of FMT 5 is data, not a check: it is filled either way.)
+    auto store_entry = [&](auto CHECKED, uint32_t idx, int32_t c, int32_t sn, const int4 rec, uint32_t pos) {
         if constexpr (FMT == 5) {
             // the deviation that does not fit (or collides with the marker) goes to this workgroup's list, the marker into the table
             const int2 p = tab_predict(rec, pos, d);                                            // (hrec: plain slopes)
@@ -550,18 +548,22 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(8, 8)))
         } else if constexpr (FMT == 3) {
             const int2 p = tab_predict(rec, pos, d);                                            // (hrec: plain slopes)
             const uint32_t nc = (uint32_t)(c - p.x), ns = (uint32_t)(sn - p.y);
-            if (plan.check_flag && (nc | ns) > 15u) atomicOr(plan.check_flag, 1u);
+            if constexpr (decltype(CHECKED)::value) {
+                if (plan.check_flag && (nc | ns) > 15u) atomicOr(plan.check_flag, 1u);
+            }
             table_store<1>(table, idx, nc | (ns << 4));                                           // bits 8.. are not stored
         } else {
             const int2 p = tab_predict(rec, pos, d);
             const int32_t dc = c - p.x, ds = sn - p.y;
-            if (plan.check_flag && !(fits_bits(dc, 8) && fits_bits(ds, 8))) atomicOr(plan.check_flag, 1u);
+            if constexpr (decltype(CHECKED)::value) {
+                if (plan.check_flag && !(fits_bits(dc, 8) && fits_bits(ds, 8))) atomicOr(plan.check_flag, 1u);
+            }
             table_store<2>(table, idx, ((uint32_t)dc & 0xFFu) | ((uint32_t)ds << 8));           // bits 16.. are not stored
         }
     };
 
     // ---- phase 2: one wave per group, one lane per leaf (and its image) ----
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;   // g and the cell arithmetic below stay scalar
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;   // the wave number and the loop control stay scalar
     // index of leaf (g, lane) = idx_a + g * idx_m; index of its image E - u = idx_i - (that) -- split layout per residue class of the lane
     uint32_t idx_a, idx_m, idx_i;
     if (lane & 1u)      { idx_a = (E >> 1) + (lane >> 1); idx_m = 32u; idx_i = E + (E >> 1) - 1u; }
@@ -569,142 +571,191 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(8, 8)))
     else                { idx_a = lane >> 2;              idx_m = 16u; idx_i = E >> 2; }
     if (!plan.tab_split) { idx_a = lane; idx_m = 64u; idx_i = E; }  // natural layout (nibble tables): index u, image E - u
     const uint32_t fmask = (1u << d) - 1u;
+    // A wave walks the groups wave, wave + kWaves, ..: 16 of them, THREADS entries apart.  What moves from one group to the next is
+    // carried and stepped by its fixed increment, one vector add each, instead of being derived from the group number with scalar
+    // shifts and a v_mov per use (the pass is bound by instruction issue, and a scalar instruction costs more of it than a VOP2:
+    // profiles/r28_build_loop.txt):
+    //   u            the lane's entry (its image is E - u);
+    //   st_off       where the group's parked state lies in gst;
+    //   off1, pos1   the own cell's record in hrec[0] and the entry's place in the cell;
+    //   off2, pos2   the same for the image, PER LANE: the images of a group descend with the lane inside one cell, except that
+    //                lane 0's opens the next cell in one group of 2^(d-6) -- as a lane's own address that case needs no branch.
+    // A step of THREADS entries is whole cells wherever THREADS is a multiple of 2^9 (d <= 9: bhwk_resid_dlog), and then the places
+    // in the cell never change; the 256-thread shape derives the four from u.
+    constexpr uint32_t kWaves = THREADS / 64;
+    static_assert(gpw == 16u * kWaves, "a wave walks 16 groups: four at each priority");
+    constexpr bool kWholeCells = THREADS % (1 << 9) == 0;
+    const uint32_t gi_end = group0 >= n_groups ? 0u : n_groups - group0 < gpw ? n_groups - group0 : gpw;   // own groups that exist
+    const uint32_t zlane = lane << s;
+    const uint32_t cell_step = ((uint32_t)THREADS >> d) << 4;       // records (bytes of hrec) per step, kWholeCells
+    // the ROM words of the ten-rotation block, held in scalar registers across the groups: as kernel arguments the compiler fetched
+    // twelve of them again for every group (two s_load and a wait).  Read from the LDS copy, so that they are not the values the
+    // deferred chains below fetch as arguments, which would then be kept alive across the walk as well (in spilled registers).
+    constexpr int KA = KS - 10;
+    static_assert(KA >= 5 && KA < kcap && KS - KA == 10, "ten-rotation block");
+    uint32_t rom[10];
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        rom[i] = __builtin_amdgcn_readfirstlane(lut_s[KA + i]);
+        asm volatile("" : "+s"(rom[i]));
+    }
     // (groups handed out dynamically -- an LDS counter, the next index requested a group ahead -- instead of this fixed interleave:
     // 0.0966 -> 0.0988 ms, profiles/HISTORY.md)
-    for (uint32_t gi = wave; gi < gpw; gi += THREADS / 64) {
-        const uint32_t g = __builtin_amdgcn_readfirstlane(group0 + gi);   // (kept in a vector register otherwise, and the cell arithmetic with it)
-        if (g >= n_groups) break;
-        // Issue priority by progress.  The SIMD's arbiter serves the oldest wave first, so of the two workgroups of a CU the one
-        // that was started first runs ahead, finishes its 16 rounds of groups ~12 us before the other (profiles/r04_build_timeline.txt:
-        // 21 against 33 us) and leaves the CU half empty for the rest of the pass -- and there is no second round of workgroups to
-        // refill it.  A wave lowers its own priority every four groups: whoever is behind is served first, the waves of both
-        // workgroups stay within four groups of each other and the CU stays full until the end (0.1076 -> 0.1047 ms per window,
-        // profiles/r04_ab_prio.txt).
-        {
-            const uint32_t it = (gi - wave) / (uint32_t)(THREADS / 64);
-            if (it == 0u) __builtin_amdgcn_s_setprio(3);
-            else if (it == 4u) __builtin_amdgcn_s_setprio(2);
-            else if (it == 8u) __builtin_amdgcn_s_setprio(1);
-            else if (it == 12u) __builtin_amdgcn_s_setprio(0);
-        }
-        const int k0 = __builtin_amdgcn_readfirstlane(gk[gi]);
-        const uint32_t gf = __builtin_amdgcn_readfirstlane(gflag[gi]);
-        int32_t z = (int32_t)((uint32_t)gz[gi] + (lane << s));
-        uint64_t zmask = 0ull;                                       // lanes whose z_k was exactly 0 at a rotation before KS
-        int32_t c1, s1, c2, s2;                                      // the entry and its image
-        bool replay = false;                                         // a lane whose image cannot come from the hand-over state
-        if (gf & 2u) {
-            // ---- narrow state: 32-bit words, EXEC-masked add / sub, table tail ----
-            uint32_t x = (uint32_t)gx[gi], y = (uint32_t)gy[gi];
-            uint32_t zacc = ~0u;                                      // min over the rotations of (unsigned)z_k: 0 = a zero event
-            // entry at the group's split rotation k0 (17 or 18 at 2^26 / 32 bits): rotations below KA = KS - 10 behind one scalar guard
-            // each (rare: a group that splits that early), the last ten as one block entered at k0 (a switch with fall-through is
-            // lowered to a flag machine that costs 10 us of the pass)
-            constexpr int KA = KS - 10;
-            static_assert(KA >= 5 && KA < kcap && KS - KA == 10, "ten-rotation block");
-            if (k0 < KA) {
-#define BHW_NARROW(K) if constexpr (K < KA) { if (K >= k0) rot_narrow<K, true>(x, y, z, zacc, plan.lut[K]); }
-                BHW_NARROW(1) BHW_NARROW(2) BHW_NARROW(3) BHW_NARROW(4) BHW_NARROW(5) BHW_NARROW(6) BHW_NARROW(7) BHW_NARROW(8)
-                BHW_NARROW(9) BHW_NARROW(10) BHW_NARROW(11) BHW_NARROW(12) BHW_NARROW(13) BHW_NARROW(14) BHW_NARROW(15)
-#undef BHW_NARROW
-            }
-            const bool hi = (gf & 4u) != 0u;                          // scalar: x holds x - 2^(NITER-1)
-            rot_narrow_block<KA, NITER>(x, y, z, zacc, plan.lut, k0 - KA, hi ? 1u : 0u);
-            zmask = __builtin_amdgcn_ballot_w64(zacc == 0u);
-            const uint32_t xrow6 = hi ? (1u << (NITER - 1 - KS + 6)) : 0u;   // (B >> KS) << 6: the bias in the tail table's row index
-            const uint32_t bias_out = hi ? ((1u << (NITER - 1)) >> plan.out_shr) : 0u;   // B >> out_shr
-            static_assert(KS <= 26, "unrolled to rotation 25");
-            constexpr uint32_t lowm = (1u << KS) - 1u;
-            const uint32_t zi = (uint32_t)(z + kTailZ);              // own pattern at zi, the image's (z -> -z) at 2 kTailZ - zi
-            const uint32_t mx = (x + 128u) & lowm, my = (y + 128u) & lowm;      // margin of 128 to both ends of the low KS bits
-            const uint32_t unsafe = (uint32_t)((mx < my ? mx : my) < 256u) | (uint32_t)((zi - 1u) >= (uint32_t)(2 * kTailZ - 1));
-            if (__builtin_amdgcn_ballot_w64(unsafe != 0u) == 0ull) {
-                const uint32_t xx = ((x >> KS) << 6) + xrow6, yy = (y >> KS) << 6;   // row of D: y < 2^NITER, so y >> KS < 64; x >> KS <= 64
-                const uint32_t p1 = tail_p[zi], p2 = tail_p[2u * kTailZ - zi];
-                const int32_t dx1 = tail_d[p1 + yy], dy1 = tail_d[p1 + xx], dx2 = tail_d[p2 + xx], dy2 = tail_d[p2 + yy];
-                c1 = (int32_t)(((x - (uint32_t)dx1) >> plan.out_shr) + bias_out);
-                s1 = (int32_t)((y + (uint32_t)dy1) >> plan.out_shr);
-                c2 = (int32_t)((y - (uint32_t)dx2) >> plan.out_shr);
-                s2 = (int32_t)(((x + (uint32_t)dy2) >> plan.out_shr) + bias_out);
-            } else if (hi) {
-                // (rare: a lane outside the tail table's margins in a biased group) the six rotations on the 64-bit state
-                int64_t xw = (int64_t)x + ((int64_t)1 << (NITER - 1)), yw = (int64_t)y;
-                int64_t x2 = yw, y2 = xw;
-                int32_t z2 = -z;
-#pragma unroll 1
-                for (int k = KS; k < NITER; ++k) {
-                    rot_step_dyn(xw, yw, z, k, lut_s[k], true);
-                    rot_step_dyn(x2, y2, z2, k, lut_s[k], true);
-                }
-                c1 = (int32_t)(xw >> plan.out_shr); s1 = (int32_t)(yw >> plan.out_shr);
-                c2 = (int32_t)(x2 >> plan.out_shr); s2 = (int32_t)(y2 >> plan.out_shr);
-            } else {
-                uint32_t x2 = y, y2 = x;
-                int32_t z2 = -z;
-                uint32_t unused = 0u;
-#define BHW_NARROW(K) if constexpr (K >= KS && K < NITER) { rot_narrow<K, false>(x, y, z, unused, plan.lut[K]); rot_narrow<K, false>(x2, y2, z2, unused, plan.lut[K]); }
-                BHW_NARROW(15) BHW_NARROW(16) BHW_NARROW(17) BHW_NARROW(18) BHW_NARROW(19) BHW_NARROW(20) BHW_NARROW(21) BHW_NARROW(22)
-                BHW_NARROW(23) BHW_NARROW(24) BHW_NARROW(25) BHW_NARROW(26) BHW_NARROW(27) BHW_NARROW(28) BHW_NARROW(29) BHW_NARROW(30)
-                BHW_NARROW(31)
-#undef BHW_NARROW
-                c1 = (int32_t)(x >> plan.out_shr); s1 = (int32_t)(y >> plan.out_shr);
-                c2 = (int32_t)(x2 >> plan.out_shr); s2 = (int32_t)(y2 >> plan.out_shr);
-            }
-        } else {
-            // ---- wide state (the first degree of the octant, groups that split early): the 64-bit rotation, rolled ----
-            int64_t x = gx[gi], y = gy[gi];
-#pragma unroll 1
-            for (int k = k0; k < KS; ++k) {
-                zmask |= __builtin_amdgcn_ballot_w64(z == 0);
-                rot_step_dyn(x, y, z, k, lut_s[k], k >= kMad24From);
-            }
-            int64_t x2 = y, y2 = x;
-            int32_t z2 = -z;
-#pragma unroll 1
-            for (int k = KS; k < NITER; ++k) {
-                rot_step_dyn(x, y, z, k, lut_s[k], true);
-                rot_step_dyn(x2, y2, z2, k, lut_s[k], true);
-            }
-            c1 = (int32_t)(x >> plan.out_shr); s1 = (int32_t)(y >> plan.out_shr);
-            c2 = (int32_t)(x2 >> plan.out_shr); s2 = (int32_t)(y2 >> plan.out_shr);
-        }
-        const uint32_t g6 = __builtin_amdgcn_readfirstlane(g << 6);   // back in a scalar register (merged with the branches' copies it
-                                                                      // lands in a vector one, and the wave-uniform cell arithmetic below with it)
-        const uint32_t u = g6 + lane;
-        const bool has_image = u >= 1u && u <= m_last;
-        bool deferred = false;                                       // this lane's image goes to the worklist
-        if (zmask != 0ull || gf & 1u) {                              // scalar
-            // z_k == 0 before the hand-over (or, leaf 0, inside the shared prefix): the image is a chain of its own
-            replay = has_image && ((((zmask >> lane) & 1ull) != 0ull) || ((gf & 1u) && lane == 0u));
-            if (replay) {
-                const uint32_t slot = atomicAdd(&work_n, 1u);
-                if (slot < kWorkMax) { work_u[slot] = u; deferred = true; }
-                else {                                               // list full (never seen): the image chain from scratch, in place
-                    int64_t xf = plan.x0, yf = plan.x0;
-                    int32_t zf = (int32_t)(((E - u) << s) - lut_s[0]);
-#pragma unroll 1
-                    for (int r = 1; r < n_iter; ++r) rot_step_dyn(xf, yf, zf, r, lut_s[r], r >= kMad24From);
-                    c2 = (int32_t)(xf >> plan.out_shr);
-                    s2 = (int32_t)(yf >> plan.out_shr);
-                }
-            }
-        }
-        // (nibble tables are always in the natural order: scalar shift + one add instead of the 64-bit multiply-add of the general form)
-        const uint32_t idx = fmt_is_nibble(FMT) ? (g << 6) + lane : idx_a + g * idx_m;
-        store_entry(idx, c1, s1, record(0, g6 >> d), (g6 & fmask) + lane);
-        if (has_image && !deferred) {
-            // images E - 64g - 63 .. E - 64g, descending with the lane: one cell, or two when lane 0's image opens the next one
+    auto build_groups = [&](auto CHECKED) {
+        uint32_t u = ((group0 + wave) << 6) + lane;
+        uint32_t st_off = wave * (uint32_t)sizeof(int4);
+        asm volatile("" : "+v"(st_off));                            // (a vector register from the start: it is only ever an LDS address)
+        uint32_t idx = idx_a + (group0 + wave) * idx_m;              // split layout (FMT 2): the entry's index, stepped like u
+        uint32_t off1, pos1, off2, pos2;
+        auto cells_of = [&]() {
             const uint32_t um = E - u;
-            const uint32_t top = E - g6, cell_a = (top - 63u) >> d, cell_b = top >> d;             // wave-uniform
-            const uint32_t cell_c = cell_a >= cell_lo[1] ? cell_a : cell_lo[1];                      // (sources above m_last are masked off)
-            int4 rec2 = record(1, cell_c);
-            if (__builtin_amdgcn_readfirstlane(cell_b) != __builtin_amdgcn_readfirstlane(cell_c)) { // scalar branch, 1 group in 2^(d-6)
-                const int4 rb = record(1, cell_b);
-                if (lane == 0u) rec2 = rb;
+            pos1 = u & fmask;
+            off1 = ((u >> d) - cell_lo[0]) << 4;
+            pos2 = um & fmask;
+            off2 = ((um >> d) - cell_lo[1]) << 4;
+        };
+        cells_of();
+        uint32_t gi = wave;
+#pragma unroll 1
+        for (uint32_t quarter = 0; quarter < 4u; ++quarter) {
+            // Issue priority by progress.  The SIMD's arbiter serves the oldest wave first, so of the two workgroups of a CU the one
+            // that was started first runs ahead, finishes its 16 rounds of groups ~12 us before the other (profiles/r04_build_timeline.txt:
+            // 21 against 33 us) and leaves the CU half empty for the rest of the pass -- and there is no second round of workgroups to
+            // refill it.  A wave lowers its own priority every four groups: whoever is behind is served first, the waves of both
+            // workgroups stay within four groups of each other and the CU stays full until the end (0.1076 -> 0.1047 ms per window,
+            // profiles/r04_ab_prio.txt).  One s_setprio per quarter of the walk, outside the loop over its groups (as a test of the
+            // iteration count inside it, the ladder was walked by every group: ~20 scalar instructions and 7 branches each).
+            if (quarter == 0u) __builtin_amdgcn_s_setprio(3);
+            else if (quarter == 1u) __builtin_amdgcn_s_setprio(2);
+            else if (quarter == 2u) __builtin_amdgcn_s_setprio(1);
+            else __builtin_amdgcn_s_setprio(0);
+            const uint32_t q_end = (quarter + 1u) * 4u * kWaves < gi_end ? (quarter + 1u) * 4u * kWaves : gi_end;
+#pragma unroll 1
+            for (; gi < q_end; gi += kWaves) {
+                const int4 st = *reinterpret_cast<const int4 *>(reinterpret_cast<const char *>(gst) + st_off);
+                const uint32_t kf = __builtin_amdgcn_readfirstlane((uint32_t)st.w);
+                const int k0 = (int)(kf & 0xFFu);
+                const uint32_t gf = kf >> 8;
+                int32_t z = (int32_t)((uint32_t)st.z + zlane);
+                uint64_t zmask = 0ull;                                       // lanes whose z_k was exactly 0 at a rotation before KS
+                int32_t c1, s1, c2, s2;                                      // the entry and its image
+                if (gf & 2u) {
+                    // ---- narrow state: 32-bit words, EXEC-masked add / sub, table tail ----
+                    uint32_t x = (uint32_t)st.x, y = (uint32_t)st.y;
+                    uint32_t zacc = ~0u;                                      // min over the rotations of (unsigned)z_k: 0 = a zero event
+                    // entry at the group's split rotation k0 (17 or 18 at 2^26 / 32 bits): rotations below KA = KS - 10 behind one scalar guard
+                    // each (rare: a group that splits that early), the last ten as one block entered at k0 (a switch with fall-through is
+                    // lowered to a flag machine that costs 10 us of the pass)
+                    if (k0 < KA) {
+                        // (the ROM words of rotations 1 .. 8 from the LDS copy: one group in a thousand splits that early, and as kernel
+                        // arguments they occupied eight scalar registers for the whole walk)
+#define BHW_NARROW(K) if constexpr (K < KA) { if (K >= k0) rot_narrow<K, true>(x, y, z, zacc, K < 9 ? (uint32_t)__builtin_amdgcn_readfirstlane(lut_s[K]) : plan.lut[K]); }
+                        BHW_NARROW(1) BHW_NARROW(2) BHW_NARROW(3) BHW_NARROW(4) BHW_NARROW(5) BHW_NARROW(6) BHW_NARROW(7) BHW_NARROW(8)
+                        BHW_NARROW(9) BHW_NARROW(10) BHW_NARROW(11) BHW_NARROW(12) BHW_NARROW(13) BHW_NARROW(14) BHW_NARROW(15)
+#undef BHW_NARROW
+                    }
+                    const uint32_t hi = (gf >> 2) & 1u;                       // scalar, 0 / 1: x holds x - 2^(NITER-1) (what follows from it by shifts, not selects)
+                    rot_narrow_block<KA, NITER>(x, y, z, zacc, rom, k0 - KA, hi);
+                    zmask = __builtin_amdgcn_ballot_w64(zacc == 0u);
+                    const uint32_t xrow6 = hi << (NITER - 1 - KS + 6);       // (B >> KS) << 6: the bias in the tail table's row index
+                    const uint32_t bias_out = (hi << (NITER - 1)) >> plan.out_shr;   // B >> out_shr
+                    static_assert(KS <= 26, "unrolled to rotation 25");
+                    constexpr uint32_t lowm = (1u << KS) - 1u;
+                    const uint32_t zi = (uint32_t)(z + kTailZ);              // own pattern at zi, the image's (z -> -z) at 2 kTailZ - zi
+                    const uint32_t mx = (x + 128u) & lowm, my = (y + 128u) & lowm;      // margin of 128 to both ends of the low KS bits
+                    const uint32_t unsafe = (uint32_t)((mx < my ? mx : my) < 256u) | (uint32_t)((zi - 1u) >= (uint32_t)(2 * kTailZ - 1));
+                    if (__builtin_expect(__builtin_amdgcn_ballot_w64(unsafe != 0u) == 0ull, 1)) {
+                        const uint32_t xx = ((x >> KS) << 6) + xrow6, yy = (y >> KS) << 6;   // row of D: y < 2^NITER, so y >> KS < 64; x >> KS <= 64
+                        const uint32_t p1 = tail_p[zi], p2 = tail_p[2u * kTailZ - zi];
+                        const int32_t dx1 = tail_d[p1 + yy], dy1 = tail_d[p1 + xx], dx2 = tail_d[p2 + xx], dy2 = tail_d[p2 + yy];
+                        c1 = (int32_t)(((x - (uint32_t)dx1) >> plan.out_shr) + bias_out);
+                        s1 = (int32_t)((y + (uint32_t)dy1) >> plan.out_shr);
+                        c2 = (int32_t)((y - (uint32_t)dx2) >> plan.out_shr);
+                        s2 = (int32_t)(((x + (uint32_t)dy2) >> plan.out_shr) + bias_out);
+                    } else if (hi) {
+                        // (rare: a lane outside the tail table's margins in a biased group) the six rotations on the 64-bit state
+                        int64_t xw = (int64_t)x + ((int64_t)1 << (NITER - 1)), yw = (int64_t)y;
+                        int64_t x2 = yw, y2 = xw;
+                        int32_t z2 = -z;
+#pragma unroll 1
+                        for (int k = KS; k < NITER; ++k) {
+                            rot_step_dyn(xw, yw, z, k, lut_s[k], true);
+                            rot_step_dyn(x2, y2, z2, k, lut_s[k], true);
+                        }
+                        c1 = (int32_t)(xw >> plan.out_shr); s1 = (int32_t)(yw >> plan.out_shr);
+                        c2 = (int32_t)(x2 >> plan.out_shr); s2 = (int32_t)(y2 >> plan.out_shr);
+                    } else {
+                        uint32_t x2 = y, y2 = x;
+                        int32_t z2 = -z;
+                        uint32_t unused = 0u;
+#define BHW_NARROW(K) if constexpr (K >= KS && K < NITER) { rot_narrow<K, false>(x, y, z, unused, plan.lut[K]); rot_narrow<K, false>(x2, y2, z2, unused, plan.lut[K]); }
+                        BHW_NARROW(15) BHW_NARROW(16) BHW_NARROW(17) BHW_NARROW(18) BHW_NARROW(19) BHW_NARROW(20) BHW_NARROW(21) BHW_NARROW(22)
+                        BHW_NARROW(23) BHW_NARROW(24) BHW_NARROW(25) BHW_NARROW(26) BHW_NARROW(27) BHW_NARROW(28) BHW_NARROW(29) BHW_NARROW(30)
+                        BHW_NARROW(31)
+#undef BHW_NARROW
+                        c1 = (int32_t)(x >> plan.out_shr); s1 = (int32_t)(y >> plan.out_shr);
+                        c2 = (int32_t)(x2 >> plan.out_shr); s2 = (int32_t)(y2 >> plan.out_shr);
+                    }
+                } else {
+                    // ---- wide state (the first degree of the octant, groups that split early): the 64-bit rotation, rolled ----
+                    const int2 high = ghi[gi];
+                    int64_t x = (int64_t)(((uint64_t)(uint32_t)high.x << 32) | (uint32_t)st.x), y = (int64_t)(((uint64_t)(uint32_t)high.y << 32) | (uint32_t)st.y);
+#pragma unroll 1
+                    for (int k = k0; k < KS; ++k) {
+                        zmask |= __builtin_amdgcn_ballot_w64(z == 0);
+                        rot_step_dyn(x, y, z, k, lut_s[k], k >= kMad24From);
+                    }
+                    int64_t x2 = y, y2 = x;
+                    int32_t z2 = -z;
+#pragma unroll 1
+                    for (int k = KS; k < NITER; ++k) {
+                        rot_step_dyn(x, y, z, k, lut_s[k], true);
+                        rot_step_dyn(x2, y2, z2, k, lut_s[k], true);
+                    }
+                    c1 = (int32_t)(x >> plan.out_shr); s1 = (int32_t)(y >> plan.out_shr);
+                    c2 = (int32_t)(x2 >> plan.out_shr); s2 = (int32_t)(y2 >> plan.out_shr);
+                }
+                // (nibble tables are always in the natural order: the entry's index is u itself)
+                const uint32_t own_idx = fmt_is_nibble(FMT) ? u : idx;
+                store_entry(CHECKED, own_idx, c1, s1, *reinterpret_cast<const int4 *>(reinterpret_cast<const char *>(hrec[0]) + off1), pos1);
+                // the image E - u.  Own entries end below E / 2 (g < n_groups), so every one of them has an image but entry 0.
+                auto store_image = [&]() {
+                    store_entry(CHECKED, fmt_is_nibble(FMT) ? E - u : idx_i - idx, c2, s2,
+                                *reinterpret_cast<const int4 *>(reinterpret_cast<const char *>(hrec[1]) + off2), pos2);
+                };
+                const uint32_t events = (uint32_t)zmask | (uint32_t)(zmask >> 32) | (gf & 9u);   // scalar, one 32-bit word to test
+                if (events == 0u) {                                          // no zero event and not the table's group 0: every image as it stands
+                    store_image();
+                } else {
+                    // z_k == 0 before the hand-over (or, leaf 0, inside the shared prefix): the image is a chain of its own
+                    const bool replay = u != 0u && ((((zmask >> lane) & 1ull) != 0ull) || ((gf & 1u) && lane == 0u));
+                    bool deferred = false;                                   // this lane's image goes to the worklist
+                    if (replay) {
+                        const uint32_t slot = atomicAdd(&work_n, 1u);
+                        if (slot < kWorkMax) { work_u[slot] = u; deferred = true; }
+                        else {                                               // list full (never seen): the image chain from scratch, in place
+                            int64_t xf = plan.x0, yf = plan.x0;
+                            int32_t zf = (int32_t)(((E - u) << s) - lut_s[0]);
+#pragma unroll 1
+                            for (int r = 1; r < n_iter; ++r) rot_step_dyn(xf, yf, zf, r, lut_s[r], r >= kMad24From);
+                            c2 = (int32_t)(xf >> plan.out_shr);
+                            s2 = (int32_t)(yf >> plan.out_shr);
+                        }
+                    }
+                    if (u != 0u && !deferred) store_image();
+                }
+                u += (uint32_t)THREADS;
+                st_off += kWaves * (uint32_t)sizeof(int4);
+                idx += kWaves * idx_m;
+                if constexpr (kWholeCells) { off1 += cell_step; off2 -= cell_step; }
+                else cells_of();
             }
-            store_entry(fmt_is_nibble(FMT) ? E - idx : idx_i - idx, c2, s2, rec2, um & fmask);
         }
-    }
+    };
+    // two copies of the walk behind one scalar test: with and without the format check (FMT 5 has none in the walk)
+    if constexpr (FMT == 5) build_groups(std::false_type{});
+    else if (plan.check_flag) build_groups(std::true_type{});
+    else build_groups(std::false_type{});
     BHW_STAMP_MIN(3);                                                // first wave done with its groups
     BHW_STAMP(4);                                                    // last wave done
     // ---- the deferred images: one lane each.  The chain is unrolled on the scalar ROM words (the rolled loop on the LDS copy kept
@@ -717,7 +768,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(8, 8)))
         int32_t zf = (int32_t)((um << s) - plan.lut[0]);
 #pragma unroll
         for (int r = 1; r < n_iter; ++r) rot_step(xf, yf, zf, r, plan.lut[r]);     // (restarting from the group's parked state, per-lane start rotation: +0.3 us)
-        store_entry(tab_index(um, plan.log2_entries, plan.tab_split), (int32_t)(xf >> plan.out_shr), (int32_t)(yf >> plan.out_shr), record_of(1, um >> d), um & fmask);
+        store_entry(std::true_type{}, tab_index(um, plan.log2_entries, plan.tab_split), (int32_t)(xf >> plan.out_shr), (int32_t)(yf >> plan.out_shr), record_of(1, um >> d), um & fmask);
     }
     if constexpr (FMT == 5) {                                        // the list's length; a list that overflowed fails the format
         __syncthreads();
