@@ -164,8 +164,11 @@ __global__ __launch_bounds__(kBuildThreads) void k_table_build_shared(BhwBuildPl
 //   * a group whose shared prefix itself met z == 0 (only its leaf 0 can) recomputes that one image from scratch;
 //   * the records of the image cells come from chains of their own (third wave), never from the symmetry.
 //
-// Round 3: two exact short cuts inside a group, both established on the host by tools/sim_build.cpp (every entry of the tables
-// of the BASELINE configurations against the plain chain) and covered on the device by the parity tests:
+// Round 3: two exact short cuts inside a group, both established on the host by tools/sim_build.cpp -- every entry of the table
+// against the plain chain, for EVERY configuration the planner sends to this kernel at PW 22..26 (176 of them: the three models
+// at every width, the VHDL model also at PW == W and at precisions 2 and 7; tests/test_build_mirror_host.py), not only the
+// BASELINE ones -- and covered on the device at the same 176 configurations, every bit of every table word, by
+// tests/test_gpu_build_mirror_sweep.py:
 //   NARROW STATE.  From its split rotation k0 on a group's leaves move x and y by less than D = 2^(NITER - k0 + 1) + 2 in total,
 //     so when the parked group state satisfies D <= X, Y and X + D, Y + D < 2^NITER (a scalar test in phase 1; 99 % of the
 //     groups: all but the first degree of the octant) every x_k, y_k of every leaf lies in [0, 2^NITER), NITER <= 32: the
@@ -733,7 +736,10 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(8, 8)))
                     if (replay) {
                         const uint32_t slot = atomicAdd(&work_n, 1u);
                         if (slot < kWorkMax) { work_u[slot] = u; deferred = true; }
-                        else {                                               // list full (never seen): the image chain from scratch, in place
+                        else {                                               // list full: the image chain from scratch, in place.
+                            // Unreached at PW <= 26: over all 176 mirror configurations the fullest workgroup defers 72 images of
+                            // kWorkMax = 512 (64 groups) and 250 of 2 048 (256 groups), the middle entry included -- a factor of
+                            // seven to spare (tools/sim_build.cpp, tests/test_build_mirror_host.py)
                             int64_t xf = plan.x0, yf = plan.x0;
                             int32_t zf = (int32_t)(((E - u) << s) - lut_s[0]);
 #pragma unroll 1

@@ -12,6 +12,9 @@
 // Every entry of the first-quadrant table is compared with the plain chain (the rotation loop of
 // hls/windows/win_function.cpp:110-125 | cpp/cordic_sincos.cpp:49-63 | src/cordic_dds.vhd:197-213).
 // Test infrastructure / design evidence only: nothing here is linked into the product.
+// Besides the comparison it prints what the rare paths of the kernel see in this configuration: the deferred images of the fullest
+// workgroup (the kernel's worklist bound) and the entries that leave the four-bit fields of the nibble formats (the format the
+// device settles on).
 //   usage: sim_build <model 0 hls | 1 cpp | 2 vhdl> <PW> <W> [precision [tail rotations 6 | 7]]     (exit code 0 = every entry identical)
 #include <quadmath.h>
 
@@ -60,7 +63,8 @@ int main(int argc, char **argv)
     if (model == 0)      { for (int i = 0; i + 1 < W; ++i) c.lut[i] = T4[i] >> (47 - W); c.x0 = G46 >> (46 - W); c.n_iter = W; c.z_shl = W - PW + 2; c.out_shr = 2; }
     else if (model == 1) { for (int i = 0; i + 1 < W; ++i) c.lut[i] = T2[i] >> (47 - W); c.x0 = G46 >> (46 - W); c.n_iter = W; c.z_shl = W - PW + 1; c.out_shr = 2; }
     else { const int Wi = W + P; for (int i = 0; i + 1 < W; ++i) c.lut[i] = T4[i] >> (49 - Wi); c.x0 = G47 >> (49 - Wi); c.n_iter = W - 1; c.z_shl = W - PW + P; c.out_shr = P; }
-    if (c.z_shl < 0 || (model == 0 ? PW - 1 >= W : model == 1 ? PW - 1 >= W : PW >= W)) { fprintf(stderr, "z_shr != 0: not a mirror-kernel configuration\n"); return 2; }
+    // z_shr == 0 as bhwp_resolve_cordic has it: hls / cpp at PW - 1 < W; vhdl up to PW == W (z_shl = P there: the 21-rotation tables at 22 / 22)
+    if (c.z_shl < 0 || (model == 0 ? PW - 1 >= W : model == 1 ? PW - 1 >= W : PW > W)) { fprintf(stderr, "z_shr != 0: not a mirror-kernel configuration\n"); return 2; }
     c.E = 1u << (PW - 2);
     const int N = c.n_iter, TAIL = argc > 5 ? atoi(argv[5]) : 6, KS = N - TAIL, PREFIX_MAX = 20;
     if (TAIL != 6 && TAIL != 7) { fprintf(stderr, "tail of 6 or 7 rotations\n"); return 2; }
@@ -105,6 +109,9 @@ int main(int argc, char **argv)
     const int64_t BX = (int64_t)1 << (N - 1);                                // bias of the biased narrow state
     uint64_t n_groups = E >> 7, wide_groups = 0, unsafe_waves = 0, unsafe_lanes = 0, zero_lanes = 0, zero_prefix = 0;
     const int64_t LIM = (int64_t)1 << N;
+    // deferred images per workgroup of the kernel, for both of its shapes (64 and 256 own groups): what its worklist (kWorkMax = 8 x
+    // groups per workgroup) has to hold
+    std::vector<uint32_t> def64((n_groups + 63) / 64, 0u), def256((n_groups + 255) / 256, 0u);
     auto full_chain = [&](uint32_t u, int32_t &oc, int32_t &os) {           // the kernel's deferred / fallback chain
         int64_t x = c.x0, y = c.x0, z = ((int64_t)u << s) - c.lut[0];
         for (int k = 1; k < N; ++k) step(x, y, z, k, c.lut[k]);
@@ -184,18 +191,56 @@ int main(int argc, char **argv)
             }
             gc[u] = oc; gs[u] = os;
             if (u >= 1 && u <= (E >> 1) - 1) {
-                if (L[lane].zero || (zero0 && lane == 0)) { ++zero_lanes; full_chain(E - u, oc2, os2); }   // worklist / leaf-0 replay
+                if (L[lane].zero || (zero0 && lane == 0)) { ++zero_lanes; ++def64[g >> 6]; ++def256[g >> 8]; full_chain(E - u, oc2, os2); }   // worklist / leaf-0 replay
                 gc[E - u] = oc2; gs[E - u] = os2;
             }
         }
     }
     full_chain(E >> 1, gc[E >> 1], gs[E >> 1]);                                 // the middle entry: a deferred chain
+    ++def64.back(); ++def256.back();                                            // ... of the last workgroup (the kernel's work_n starts at 1 there)
+    uint32_t def64_max = 0, def256_max = 0;
+    for (uint32_t v : def64) def64_max = v > def64_max ? v : def64_max;
+    for (uint32_t v : def256) def256_max = v > def256_max ? v : def256_max;
+
+    // Nibble formats, restated from the kernel's store_entry and its records: cells of 2^d entries (d as bhwk_resid_dlog has it), record
+    // = the cell's first entry (c, s) and the step to the next cell's (the table's last cell: the step from the cell before it), line
+    // = head + ((step * place) >> d), field = value - line + 8 stored in four bits.  "nibble": no field may leave 0 .. 15.  "nibble +
+    // escapes": the line lies one higher (kEscBias), the c field 0 is the marker, and what does not fit goes to the list of the
+    // workgroup that stores the entry (an own entry u < E/2, the image E - u of one, the middle entry with the last workgroup): a list
+    // beyond kEscFill = 96 entries refuses the format.  The workgroup has 256 own groups from 2^24 entries on, 64 below.
+    int dlog = (2 * PW - W - 2) / 2;
+    if (dlog > 9) dlog = 9;
+    if (dlog < 7 || W + c.out_shr > 34) dlog = 0;                                // no residual cell: not a configuration of the packed formats
+    uint64_t nib_out = 0, esc_all = 0;
+    uint32_t esc_wg_max = 0;
+    const uint32_t wg_groups = E >= (1u << 24) ? 256u : 64u;
+    if (dlog) {
+        std::vector<uint32_t> esc_wg((n_groups + wg_groups - 1) / wg_groups, 0u);
+        const uint32_t cells = E >> dlog, fm = (1u << dlog) - 1u;
+        for (uint32_t u = 0; u < E; ++u) {
+            const uint32_t cell = u >> dlog, h = cell << dlog, pos = u & fm;
+            const int32_t dc = cell + 1 < cells ? rc[h + fm + 1] - rc[h] : rc[h] - rc[h - fm - 1];
+            const int32_t ds = cell + 1 < cells ? rs[h + fm + 1] - rs[h] : rs[h] - rs[h - fm - 1];
+            const int32_t pc = rc[h] - 8 + ((dc * (int32_t)pos) >> dlog), ps = rs[h] - 8 + ((ds * (int32_t)pos) >> dlog);
+            const uint32_t nc = (uint32_t)(rc[u] - pc), ns = (uint32_t)(rs[u] - ps);
+            nib_out += (nc | ns) > 15u;
+            const uint32_t ec = nc - 1u, es = ns - 1u;                           // the same fields against the line one higher
+            if (ec - 1u > 14u || es > 15u) {
+                const uint32_t src = u < (E >> 1) ? u : u == (E >> 1) ? (E >> 1) - 1u : E - u;   // the own entry whose workgroup stores it
+                ++esc_all;
+                ++esc_wg[(src >> 6) / wg_groups];
+            }
+        }
+        for (uint32_t v : esc_wg) esc_wg_max = v > esc_wg_max ? v : esc_wg_max;
+    }
     uint64_t bad = 0;
     for (uint32_t u = 0; u < E; ++u)
         if (gc[u] != rc[u] || gs[u] != rs[u]) { if (bad < 5) fprintf(stderr, "mismatch u=%u got (%d,%d) want (%d,%d)\n", u, gc[u], gs[u], rc[u], rs[u]); ++bad; }
     printf("model %d PW %d W %d P %d: entries %u, groups %llu, wide-state groups %llu (%.2f %%), waves with an unsafe tail lane %llu (lanes %llu), "
-           "deferred images %llu (prefix zeros %llu), biased-narrow groups %llu, mismatches %llu\n", model, PW, W, P, E, (unsigned long long)n_groups,
+           "deferred images %llu (prefix zeros %llu), biased-narrow groups %llu, mismatches %llu, deferred per workgroup max %u of 64 groups | %u of 256 groups, "
+           "cell log %d, outside nibble fields %llu, escape lists %llu (max %u in one workgroup of %u groups)\n", model, PW, W, P, E, (unsigned long long)n_groups,
            (unsigned long long)wide_groups, 100.0 * wide_groups / n_groups, (unsigned long long)unsafe_waves, (unsigned long long)unsafe_lanes,
-           (unsigned long long)zero_lanes, (unsigned long long)zero_prefix, (unsigned long long)hi_groups, (unsigned long long)bad);
+           (unsigned long long)zero_lanes, (unsigned long long)zero_prefix, (unsigned long long)hi_groups, (unsigned long long)bad, def64_max, def256_max,
+           dlog, (unsigned long long)nib_out, (unsigned long long)esc_all, esc_wg_max, wg_groups);
     return bad ? 1 : 0;
 }
