@@ -57,6 +57,7 @@ ABI_SYMBOLS = (
     "bhw_csd_fft_workspace_bytes", "bhw_csd_fft_f32_device", "bhw_csd_fft_f32_from_table", "bhw_describe_csd_fft",
     "bhw_welch_cfft_workspace_bytes", "bhw_welch_cfft_f32_device", "bhw_welch_cfft_f32_from_table", "bhw_describe_welch_cfft",
     "bhw_welch_mfft_workspace_bytes", "bhw_welch_mfft_f32_device", "bhw_welch_mfft_f32_from_table", "bhw_describe_welch_mfft",
+    "bhw_welch_cmfft_workspace_bytes", "bhw_welch_cmfft_f32_device", "bhw_welch_cmfft_f32_from_table", "bhw_describe_welch_cmfft",
 )
 
 
@@ -365,6 +366,11 @@ def lib():
     L.bhw_welch_mfft_f32_device.argtypes = [P, u64, ci, vp, S, u32, f64, u32, f32p, f32p, u64, vp, u64]
     L.bhw_welch_mfft_f32_from_table.argtypes = [T, P, u64, vp, S, u32, f64, u32, f32p, f32p, u64, vp, u64]
     L.bhw_describe_welch_mfft.argtypes = [T, P, u64, S, u32, ctypes.c_char_p, u64]
+    L.bhw_welch_cmfft_workspace_bytes.restype = u64
+    L.bhw_welch_cmfft_workspace_bytes.argtypes = [S]
+    L.bhw_welch_cmfft_f32_device.argtypes = [P, u64, ci, vp, S, u32, f64, f32p, f32p, u64, vp, u64]
+    L.bhw_welch_cmfft_f32_from_table.argtypes = [T, P, u64, vp, S, u32, f64, f32p, f32p, u64, vp, u64]
+    L.bhw_describe_welch_cmfft.argtypes = [T, P, u64, S, u32, ctypes.c_char_p, u64]
     PA = ctypes.POINTER(BhwAtan2Params)
     L.bhw_atan2_device.argtypes = [PA, ci, vp, u64, i32p, i32p, i32p]
     L.bhw_atan2_to_host.argtypes = [PA, ci, u64, i32p, i32p, i32p]
@@ -698,6 +704,24 @@ def describe_welch_mfft(params, length, stft, *, detrend=False, table=None):
     buf = ctypes.create_string_buffer(1280)
     flags = WELCH_DETREND_CONSTANT if detrend else 0
     check(lib().bhw_describe_welch_mfft(table, ctypes.byref(params), int(length), ctypes.byref(stft), flags, buf, len(buf)))
+    return buf.value.decode()
+
+
+def welch_cmfft_workspace_bytes(stft):
+    """The bytes of workspace a fused Welch PSD call for I/Q input at a mixed-radix n_fft of the descriptor `stft` (a BhwStft with
+    channels 2, y strides 0) needs: B * ceil(F / 16) * n_fft chunk sums and, for F > 256, B * ceil(F / 256) * n_fft block sums, as
+    doubles (bhw_welch_cmfft_workspace_bytes)."""
+    return int(lib().bhw_welch_cmfft_workspace_bytes(ctypes.byref(stft)))
+
+
+def describe_welch_cmfft(params, length, stft, *, detrend=False, fftshift=False, table=None):
+    """One line: the plan fields of describe_stft_cmfft in the same words (without the output form), plus the chunk, the runs, the
+    groups per run, the accumulators per lane and the workspace bytes of a fused Welch PSD call for I/Q input at a mixed-radix n_fft
+    over the window of `length` with the descriptor `stft` (a BhwStft with channels 2, y strides 0) (bhw_describe_welch_cmfft).
+    `table` is a resident table handle or None for the library call.  Host arithmetic only."""
+    buf = ctypes.create_string_buffer(1280)
+    flags = (WELCH_DETREND_CONSTANT if detrend else 0) | (CFFT_SHIFT if fftshift else 0)
+    check(lib().bhw_describe_welch_cmfft(table, ctypes.byref(params), int(length), ctypes.byref(stft), flags, buf, len(buf)))
     return buf.value.decode()
 
 

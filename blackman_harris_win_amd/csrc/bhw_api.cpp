@@ -1227,6 +1227,22 @@ int welch_cfft_run(bhw_table t, const bhw_params *p, uint64_t length, int device
     });
 }
 
+// The fused Welch PSD for I/Q input at a mixed-radix n_fft (t NULL: the direct CORDIC chains): the checks, then the accumulating kernel
+// and the join.
+int welch_cmfft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *s, uint32_t flags,
+                    double scale, const float *d_x, float *d_P, uint64_t p_stride, void *workspace, uint64_t workspace_bytes)
+{
+    int rc = bhwp_welch_cmfft_checks(p, length, s, flags, scale, p_stride, d_x, d_P, workspace, workspace_bytes);
+    if (!rc && t) rc = table_call_checks(t, p);
+    if (rc || !s->frames) return rc;
+    const BhwWelchCmfftPlan pl = bhwp_welch_cmfft_plan(p, length, s, flags, p_stride, t != nullptr);
+    const char *what = t ? "welch cmfft launch (resident table)" : "welch cmfft launch";
+    return run_source(t, p, length, device, stream, what, [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *tab,
+                                                              const BhwLenPhase *lp) {
+        return bhwk_welch_cmfft_f32(l, c, w, pl, s, scale, d_x, d_P, (double *)workspace, tab, *lp);
+    });
+}
+
 // The fused Welch PSD at a mixed-radix n_fft (t NULL: the direct CORDIC chains): the checks, then the accumulating kernel and the join.
 int welch_mfft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *s, uint32_t flags,
                    double scale, uint32_t psd_flags, const float *d_x, float *d_P, uint64_t p_stride, void *workspace, uint64_t workspace_bytes)
@@ -1625,6 +1641,35 @@ int bhw_describe_welch_cfft(bhw_table t, const bhw_params *p, uint64_t length, c
     int rc = bhwp_welch_cfft_checks(p, length, s, flags, 0.0, 0, nullptr, nullptr, nullptr, 0, false);
     if (!rc && t) rc = table_call_checks(t, p);
     return rc ? rc : bhwp_describe_welch_cfft(p, t ? &t->c : nullptr, length, s, flags, buf, len);
+}
+
+// ---- fused Welch PSD for I/Q input at mixed-radix n_fft (include/bhw.h: bhw_welch_cmfft_f32_device ...) ----------------------------------
+
+uint64_t bhw_welch_cmfft_workspace_bytes(const bhw_stft *s)
+{
+    return s && s->struct_size == sizeof(bhw_stft) ? bhwp_welch_cmfft_workspace_bytes(s) : 0;
+}
+
+int bhw_welch_cmfft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                               double scale, const float *d_x, float *d_P, uint64_t p_stride, void *workspace, uint64_t workspace_bytes)
+{
+    return welch_cmfft_run(nullptr, p, length, device, hip_stream, s, flags, scale, d_x, d_P, p_stride, workspace, workspace_bytes);
+}
+
+int bhw_welch_cmfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                   double scale, const float *d_x, float *d_P, uint64_t p_stride, void *workspace, uint64_t workspace_bytes)
+{
+    const int rc = bhwp_welch_cmfft_checks(p, length, s, flags, scale, p_stride, d_x, d_P, workspace, workspace_bytes);
+    if (rc) return rc;
+    return t ? welch_cmfft_run(t, p, length, t->device, hip_stream, s, flags, scale, d_x, d_P, p_stride, workspace, workspace_bytes)
+             : fail(BHW_ERR_BADARG, "table is NULL");
+}
+
+int bhw_describe_welch_cmfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf, uint64_t len)
+{
+    int rc = bhwp_welch_cmfft_checks(p, length, s, flags, 0.0, 0, nullptr, nullptr, nullptr, 0, false);
+    if (!rc && t) rc = table_call_checks(t, p);
+    return rc ? rc : bhwp_describe_welch_cmfft(p, t ? &t->c : nullptr, length, s, flags, buf, len);
 }
 
 // ---- fused Welch PSD at mixed-radix n_fft (include/bhw.h: bhw_welch_mfft_f32_device ...) ---------------------------------------------------

@@ -2422,18 +2422,11 @@ uint64_t bhwp_welch_cfft_workspace_bytes(const bhw_stft *s)
     return bhwp_welch_runs(s->batch, s->frames, 1, s->n_fft).ws_bytes;                // the bytes do not depend on fy
 }
 
-int bhwp_welch_cfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, double scale, uint64_t p_stride,
-                           const void *d_x, const void *d_P, const void *workspace, uint64_t workspace_bytes, bool pointers)
+// The output side of both fused I/Q Welch calls (bhw_welch_cfft_f32_*, bhw_welch_cmfft_f32_*), after the forward call's checks passed:
+// steps 2 to 7 of include/bhw.h.  The workspace is bhwp_welch_runs' with bins = n_fft in both.
+static int welch_iq_output_checks(const bhw_stft *s, uint32_t flags, double scale, uint64_t p_stride, const void *d_x, const void *d_P,
+                                  const void *workspace, uint64_t workspace_bytes, bool pointers)
 {
-    // 1. the input side: the forward call's checks for the descriptor with packed output strides (no spectrum is written here)
-    bhw_stft t{};
-    const bool sized = s && s->struct_size == sizeof(bhw_stft);
-    if (sized) {
-        t = *s;
-        t.y_stride = t.y_batch_stride = 0;
-    }
-    int rc = bhwp_stft_cfft_checks(p, length, sized ? &t : s, flags, nullptr, nullptr, false);
-    if (rc) return rc;
     // 2.
     if (flags & BHW_CFFT_POWER)
         return bhwp_fail(BHW_ERR_BADARG, "flags 0x%x: BHW_CFFT_POWER has no meaning here (BHW_WELCH_DETREND_CONSTANT, BHW_CFFT_SHIFT)", flags);
@@ -2472,6 +2465,21 @@ int bhwp_welch_cfft_checks(const bhw_params *p, uint64_t length, const bhw_stft 
     if ((wa < xa + xb && xa < wa + need) || (wa < pa + pb && pa < wa + need))
         return bhwp_fail(BHW_ERR_BADARG, "workspace overlaps d_x or d_P");
     return BHW_OK;
+}
+
+int bhwp_welch_cfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, double scale, uint64_t p_stride,
+                           const void *d_x, const void *d_P, const void *workspace, uint64_t workspace_bytes, bool pointers)
+{
+    // 1. the input side: the forward call's checks for the descriptor with packed output strides (no spectrum is written here)
+    bhw_stft t{};
+    const bool sized = s && s->struct_size == sizeof(bhw_stft);
+    if (sized) {
+        t = *s;
+        t.y_stride = t.y_batch_stride = 0;
+    }
+    const int rc = bhwp_stft_cfft_checks(p, length, sized ? &t : s, flags, nullptr, nullptr, false);
+    if (rc) return rc;
+    return welch_iq_output_checks(s, flags, scale, p_stride, d_x, d_P, workspace, workspace_bytes, pointers);
 }
 
 BhwWelchCfftPlan bhwp_welch_cfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, uint64_t p_stride,
@@ -2530,6 +2538,89 @@ int bhwp_describe_welch_cfft(const bhw_params *p, const BhwCordicCfg *ct, uint64
              pl.fy, pl.cpl, (unsigned long long)pl.groups, (unsigned long long)pl.grid, kFftBlock, pl.lds_bytes, BHW_WELCH_FFT_CHUNK,
              (unsigned long long)wp.runs, (unsigned long long)wp.run, wp.gpr, wp.gpr == 1 ? "" : "s", wp.acc, wp.acc == 1 ? "" : "s",
              (unsigned long long)wp.chunks, (unsigned long long)wp.blocks, wp.blocks == 1 ? "" : "s",
+             wp.blocks == 1 ? "once (chunks)" : "twice (chunks, blocks)", (unsigned long long)wp.ws_bytes);
+    return BHW_OK;
+}
+
+// ---- fused Welch PSD for I/Q input at mixed-radix n_fft -----------------------------------------------------------------------------------------
+
+uint64_t bhwp_welch_cmfft_workspace_bytes(const bhw_stft *s)
+{
+    if (!s || !s->frames || !s->batch) return 0;
+    return bhwp_welch_runs(s->batch, s->frames, 1, s->n_fft).ws_bytes;                // the bytes do not depend on fy
+}
+
+int bhwp_welch_cmfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, double scale, uint64_t p_stride,
+                            const void *d_x, const void *d_P, const void *workspace, uint64_t workspace_bytes, bool pointers)
+{
+    // 1. the input side: the mixed-radix forward call's checks for the descriptor with packed output strides
+    bhw_stft t{};
+    const bool sized = s && s->struct_size == sizeof(bhw_stft);
+    if (sized) {
+        t = *s;
+        t.y_stride = t.y_batch_stride = 0;
+    }
+    const int rc = bhwp_stft_cmfft_checks(p, length, sized ? &t : s, flags, nullptr, nullptr, false);
+    if (rc) return rc;
+    return welch_iq_output_checks(s, flags, scale, p_stride, d_x, d_P, workspace, workspace_bytes, pointers);
+}
+
+BhwWelchCmfftPlan bhwp_welch_cmfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, uint64_t p_stride,
+                                        bool from_table)
+{
+    BhwWelchCmfftPlan pl{};
+    bhw_stft t = *s;
+    t.y_stride = t.y_batch_stride = 0;
+    pl.fft = bhwp_stft_cmfft_plan(p, length, &t, flags & kWelchCfftFlags, from_table);
+    pl.fft.y_stride = pl.fft.y_bstride = 0;
+    pl.bins = s->n_fft;
+    const BhwWelchRuns r = bhwp_welch_runs(s->batch, s->frames, pl.fft.fy, pl.bins);
+    pl.run = r.run;
+    pl.gpr = r.gpr;
+    pl.acc = pl.fft.fy >= BHW_WELCH_FFT_CHUNK ? 0u : (uint32_t)((pl.bins + kFftBlock - 1) / kFftBlock);
+    pl.p_stride = p_stride ? p_stride : pl.bins;
+    pl.fpad = r.fpad;
+    pl.chunks = r.chunks;
+    pl.blocks = r.blocks;
+    pl.runs = r.runs;
+    pl.fft.groups = r.groups;
+    pl.fft.grid = r.grid;
+    pl.blocks_grid = r.blocks_grid;
+    pl.join_grid = r.join_grid;
+    pl.ws_bytes = r.ws_bytes;
+    return pl;
+}
+
+int bhwp_describe_welch_cmfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf,
+                              uint64_t len)
+{
+    if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
+    const char *route = ct ? "table" : "direct";
+    const BhwWelchCmfftPlan wp = bhwp_welch_cmfft_plan(p, length, s, flags, 0, ct != nullptr);
+    const BhwStftCmfftPlan &pl = wp.fft;
+    const char *pad = s->pad_mode == BHW_PAD_REFLECT ? "reflect" : "constant";
+    const char *det = pl.detrend ? "constant detrend" : "no detrending";
+    const char *bins = pl.shifted ? "bins shifted" : "bins in order";
+    if (!s->frames) {
+        snprintf(buf, len, "welch cmfft %s (L = %llu, n_fft %llu, %s), %s: nothing (frames 0)", route, (unsigned long long)length,
+                 (unsigned long long)s->n_fft, det, bins);
+        return BHW_OK;
+    }
+    char kern[64], sched[48];
+    kernel_name(p, ct, "k_welch_cmfft_direct", "k_welch_cmfft_table", false, kern, sizeof kern);
+    BhwStftMfftPlan f{};
+    f.passes = pl.passes;
+    memcpy(f.radix, pl.radix, sizeof f.radix);
+    bhwp_stft_mfft_schedule(f, sched, sizeof sched);
+    snprintf(buf, len, "welch cmfft %s (L = %llu, n_fft %llu, col0 %llu, pad %llu %s, %s), %s: %s, %llu signals x %llu frames = %llu rows, "
+             "complex FFT of %u points in passes %s (no split), %u lanes per row x %u rows per workgroup, %u columns per lane, %llu groups, "
+             "grid %llu x %u lanes, %u bytes of LDS, %u twiddles; chunk %u frames, %llu runs of %llu frames (%u group%s per run), "
+             "%u accumulator%s per lane, %llu chunks and %llu block%s per signal, then k_welch_fft_join %s, workspace %llu bytes",
+             route, (unsigned long long)length, (unsigned long long)s->n_fft, (unsigned long long)s->col0, (unsigned long long)s->pad, pad,
+             det, bins, kern, (unsigned long long)s->batch, (unsigned long long)s->frames, (unsigned long long)pl.rows, pl.n, sched, pl.lpf,
+             pl.fy, pl.cpl, (unsigned long long)pl.groups, (unsigned long long)pl.grid, kFftBlock, pl.lds_bytes, pl.fold,
+             BHW_WELCH_FFT_CHUNK, (unsigned long long)wp.runs, (unsigned long long)wp.run, wp.gpr, wp.gpr == 1 ? "" : "s", wp.acc,
+             wp.acc == 1 ? "" : "s", (unsigned long long)wp.chunks, (unsigned long long)wp.blocks, wp.blocks == 1 ? "" : "s",
              wp.blocks == 1 ? "once (chunks)" : "twice (chunks, blocks)", (unsigned long long)wp.ws_bytes);
     return BHW_OK;
 }

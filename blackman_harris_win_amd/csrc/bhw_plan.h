@@ -715,6 +715,38 @@ int  bhwp_describe_welch_cfft(const bhw_params *p, const BhwCordicCfg *ct, uint6
 int  bhwk_welch_cfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwWelchCfftPlan &pl, const bhw_stft *s,
                          double scale, const float *d_x, float *d_P, double *d_ws, const int32_t *d_table, const BhwLenPhase &lp);
 
+// ---- fused Welch PSD for I/Q input at mixed-radix n_fft (bhw_welch_cmfft_f32_*; bhw_welch_cmfft.hip) ---------------------------------------
+// BhwWelchCmfftPlan wraps BhwStftCmfftPlan as BhwWelchCfftPlan wraps BhwStftCfftPlan: the lanes, LDS, schedule and row steps are
+// bhwp_stft_cmfft_plan's field for field (fft, with groups and grid recounted), the ownership is bhwp_welch_runs' with bins = n_fft.
+// fy is a power of two from 1 to 32 at these sizes (lpf is a power of two: 32 at n_fft 18 .. 32, 1 from 513 on), so run = max(16, fy)
+// and gpr = max(1, 16 / fy) hold unchanged.  acc: the binary64 accumulators a lane carries over a run (fy < 16: ceil(n_fft /
+// kFftBlock), at most kWelchCmfftMaxAcc; fy >= 16: none).  Workspace: B * chunks * n_fft chunk sums, then (blocks > 1) B * blocks *
+// n_fft block sums.  The flags are kWelchCfftFlags.
+constexpr uint32_t kWelchCmfftMaxAcc = 8;             // ceil(2025 / 256)
+struct BhwWelchCmfftPlan {
+    BhwStftCmfftPlan fft; // groups = B * fpad / fy, grid = min(runs, kFftMaxGrid); rows = B * frames; the y strides are 0; power false
+    uint64_t bins;        // n_fft: the estimate is two-sided
+    uint64_t run;
+    uint32_t gpr;
+    uint32_t acc;         // accumulators a lane carries (0 for fy >= 16)
+    uint64_t fpad, chunks, blocks, runs, blocks_grid, join_grid;   // bhwp_welch_runs'
+    uint64_t p_stride;    // resolved
+    uint64_t ws_bytes;
+};
+// Every check of the two calls that needs no table handle, before any HIP call and in the order of include/bhw.h: the checks of
+// bhwp_stft_cmfft_checks, then the output side of bhwp_welch_cfft_checks (one text for both).  frames 0 passes with the pointers
+// unchecked; `pointers` false: the describe call.
+int  bhwp_welch_cmfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, double scale, uint64_t p_stride,
+                             const void *d_x, const void *d_P, const void *workspace, uint64_t workspace_bytes, bool pointers = true);
+// bhw_welch_cmfft_workspace_bytes: from batch, frames and n_fft alone (0 for a NULL descriptor, frames 0 or a product beyond 2^60)
+uint64_t bhwp_welch_cmfft_workspace_bytes(const bhw_stft *s);
+BhwWelchCmfftPlan bhwp_welch_cmfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, uint64_t p_stride,
+                                        bool from_table);
+int  bhwp_describe_welch_cmfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf,
+                               uint64_t len);
+int  bhwk_welch_cmfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwWelchCmfftPlan &pl, const bhw_stft *s,
+                          double scale, const float *d_x, float *d_P, double *d_ws, const int32_t *d_table, const BhwLenPhase &lp);
+
 // ---- fused Welch PSD at mixed-radix n_fft (bhw_welch_mfft_f32_*; bhw_welch_mfft.hip) --------------------------------------------------------
 // BhwWelchMfftPlan wraps BhwStftMfftPlan as BhwWelchCfftPlan wraps BhwStftCfftPlan: the lanes, LDS, schedule and row steps are
 // bhwp_stft_mfft_plan's field for field (fft, form BHWP_MFFT_SPECTRUM, with groups and grid recounted), the ownership is

@@ -1514,15 +1514,21 @@ def welch_fused_mixed(params, x, fs=1.0, *, length, noverlap=None, nfft=None, de
 
 # ---- fused Welch PSD for I/Q input: window, complex FFT and the frame average in one kernel ------------------------------------------------
 
-def _welch_cfft_call(torch, params, L, s, flags, xb, nb, n_fft, scale, out, workspace, dev, table, one_d):
-    """The output and workspace rules of the fused Welch PSD for I/Q input and its launch: P float32 (n_fft,) or (B, n_fft)."""
+def _welch_cfft_call(torch, params, L, s, flags, xb, nb, n_fft, scale, out, workspace, dev, table, one_d, family="cfft"):
+    """The output and workspace rules of the fused Welch PSD for I/Q input and its launch: P float32 (n_fft,) or (B, n_fft).
+    family: "cfft" (a power-of-two n_fft) or "cmfft" (a mixed-radix one): the two calls take the same arguments."""
+    lib = B.lib()
+    if family == "cfft":
+        ws_bytes, device_call, table_call = B.welch_cfft_workspace_bytes, lib.bhw_welch_cfft_f32_device, lib.bhw_welch_cfft_f32_from_table
+    else:
+        ws_bytes, device_call, table_call = B.welch_cmfft_workspace_bytes, lib.bhw_welch_cmfft_f32_device, lib.bhw_welch_cmfft_f32_from_table
     shape = (n_fft,) if one_d else (nb, n_fft)
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=xb.device)
     elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != xb.device or tuple(out.shape) != shape \
             or out.stride(-1) != 1 or (out.dim() == 2 and nb > 1 and out.stride(0) < n_fft):
         raise ValueError(f"out must be a float32 tensor of shape {shape} on x's device, contiguous along the bins, rows apart")
-    need = B.welch_cfft_workspace_bytes(s) // 8
+    need = ws_bytes(s) // 8
     if workspace is None:
         workspace = torch.empty(need, dtype=torch.float64, device=xb.device)
     else:
@@ -1530,22 +1536,23 @@ def _welch_cfft_call(torch, params, L, s, flags, xb, nb, n_fft, scale, out, work
     tail = (ctypes.byref(s), flags, float(scale), ctypes.c_void_p(xb.data_ptr()), ctypes.c_void_p(out.data_ptr()),
             out.stride(0) if (out.dim() == 2 and nb > 1) else 0, ctypes.c_void_p(workspace.data_ptr()), workspace.numel() * 8)
     if table is None:
-        B.check(B.lib().bhw_welch_cfft_f32_device(ctypes.byref(params), L, dev, _stream_ptr(torch, dev), *tail))
+        B.check(device_call(ctypes.byref(params), L, dev, _stream_ptr(torch, dev), *tail))
     else:
-        B.check(B.lib().bhw_welch_cfft_f32_from_table(table, ctypes.byref(params), L, _stream_ptr(torch, dev), *tail))
+        B.check(table_call(table, ctypes.byref(params), L, _stream_ptr(torch, dev), *tail))
     return out
 
 
 def _welch_cfft_psd(torch, params, x, n_fft, hop, scale, win_length, center, pad_mode, detrend, shift, fftshift, out, workspace, dev,
-                    table):
-    n_fft, L, xb, nb, T, frames, d = _stft_front(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, dev, _cfft_input)
+                    table, family="cfft"):
+    check = _cfft_input if family == "cfft" else _welch_cmfft_input
+    n_fft, L, xb, nb, T, frames, d = _stft_front(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, dev, check)
     if not x.is_cuda or x.device.index != dev:
         raise ValueError("x must be a complex64 CUDA tensor on the call's device")
     shift = params.dat_width - 1 if shift is None else int(shift)
     s = B.make_stft(nb, T, frames, d["hop"], n_fft, col0=d["col0"], pad=d["pad"], pad_mode=d["pad_mode"], channels=2, shift=shift,
                     x_stride=xb.stride(0) * 2 if nb > 1 else 0)
     flags = (B.WELCH_DETREND_CONSTANT if detrend else 0) | (B.CFFT_SHIFT if fftshift else 0)
-    return _welch_cfft_call(torch, params, L, s, flags, xb, nb, n_fft, scale, out, workspace, dev, table, x.dim() == 1)
+    return _welch_cfft_call(torch, params, L, s, flags, xb, nb, n_fft, scale, out, workspace, dev, table, x.dim() == 1, family)
 
 
 def welch_fft_iq(params, x, n_fft, hop, scale, *, win_length=None, center=False, pad_mode="reflect", detrend=False, shift=None,
@@ -1568,16 +1575,17 @@ def welch_fft_iq(params, x, n_fft, hop, scale, *, win_length=None, center=False,
                            dev, None)
 
 
-def _freq_axis_iq(torch, cache, nfft, fs, fftshift, dev):
+def _freq_axis_iq(torch, cache, nfft, fs, fftshift, dev, kind="freqs_iq"):
     """_freq_axis for welch_fused_iq: the two-sided axis fftfreq(nfft, 1 / fs), or its fftshift, kept beside the window sums under a
-    key of its own kind ("freqs_iq"), so that it never meets welch_fused's one-sided axes or their count."""
-    key = ("freqs_iq", int(nfft), float(fs), int(dev), bool(fftshift))
+    key of its own kind ("freqs_iq"; welch_fused_iq_mixed: "freqs_iq_mixed"), so that it never meets welch_fused's one-sided axes,
+    the other I/Q call's axes, or their counts."""
+    key = (kind, int(nfft), float(fs), int(dev), bool(fftshift))
     hit = cache.get(key)
     if hit is not None:
         return hit
     if torch.cuda.is_current_stream_capturing():
         raise RuntimeError("the frequency axis of this (nfft, fs) has not been built yet: call once outside the capture")
-    kept = [k for k in cache if isinstance(k, tuple) and k and k[0] == "freqs_iq"]
+    kept = [k for k in cache if isinstance(k, tuple) and k and k[0] == kind]
     for k in kept[:max(0, len(kept) - _FREQS_KEPT + 1)]:
         del cache[k]
     axis = torch.fft.fftfreq(int(nfft), d=1.0 / float(fs), dtype=torch.float64, device=f"cuda:{dev}")
@@ -1585,7 +1593,8 @@ def _freq_axis_iq(torch, cache, nfft, fs, fftshift, dev):
     return cache[key]
 
 
-def _welch_fused_iq(torch, params, x, fs, length, noverlap, nfft, detrend, scaling, shift, fftshift, out, workspace, dev, table, cache):
+def _welch_fused_iq(torch, params, x, fs, length, noverlap, nfft, detrend, scaling, shift, fftshift, out, workspace, dev, table, cache,
+                    family="cfft"):
     if detrend not in ("constant", False, None):
         raise ValueError(f"detrend must be 'constant' or False, got {detrend!r}")
     if scaling not in ("density", "spectrum"):
@@ -1596,7 +1605,7 @@ def _welch_fused_iq(torch, params, x, fs, length, noverlap, nfft, detrend, scali
         raise ValueError("noverlap must be less than length")
     nfft = L if nfft is None else int(nfft)
     hop = L - noverlap
-    _cfft_input(torch, x, nfft, dev)
+    (_cfft_input if family == "cfft" else _welch_cmfft_input)(torch, x, nfft, dev)
     if not x.is_cuda or x.device.index != dev:
         raise ValueError("x must be a complex64 CUDA tensor on the call's device")
     if not 1 <= L <= 1 << params.phi_width:
@@ -1613,9 +1622,10 @@ def _welch_fused_iq(torch, params, x, fs, length, noverlap, nfft, detrend, scali
     scale = B.welch_scale(sums, frames, fs, scaling)
     sh = params.dat_width - 1 if shift is None else int(shift)
     s = B.make_stft(nb, T, frames, hop, nfft, channels=2, shift=sh, x_stride=xb.stride(0) * 2 if nb > 1 else 0)
-    freqs = _freq_axis_iq(torch, cache, nfft, fs, fftshift, dev)     # before the launch: it refuses inside a capture when missing
+    # before the launch: it refuses inside a capture when missing
+    freqs = _freq_axis_iq(torch, cache, nfft, fs, fftshift, dev, "freqs_iq" if family == "cfft" else "freqs_iq_mixed")
     flags = (B.WELCH_DETREND_CONSTANT if detrend == "constant" else 0) | (B.CFFT_SHIFT if fftshift else 0)
-    P = _welch_cfft_call(torch, params, L, s, flags, xb, nb, nfft, scale, out, workspace, dev, table, x.dim() == 1)
+    P = _welch_cfft_call(torch, params, L, s, flags, xb, nb, nfft, scale, out, workspace, dev, table, x.dim() == 1, family)
     return freqs, P
 
 
@@ -1634,6 +1644,56 @@ def welch_fused_iq(params, x, fs=1.0, *, length, noverlap=None, nfft=None, detre
     dev = x.device.index if isinstance(x, torch.Tensor) and x.is_cuda else None
     return _welch_fused_iq(torch, params, x, fs, length, noverlap, nfft, detrend, scaling, shift, fftshift, out, workspace, dev, None,
                            _SUMS_CACHE)
+
+
+# ---- fused Welch PSD for I/Q input at a mixed-radix n_fft: window, mixed-radix complex FFT and the frame average in one kernel ------------
+
+def _welch_cmfft_input(torch, x, n_fft, dev):
+    """_cmfft_input for the fused Welch calls: the refusals name the Welch call that takes what this one does not."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.complex64:
+        got = x.dtype if isinstance(x, torch.Tensor) else type(x).__name__
+        raise ValueError(f"the mixed-radix fused Welch PSD for I/Q input takes complex64 input, got {got} (real input at a "
+                         "mixed-radix n_fft: welch_fft_mixed / welch_fused_mixed)")
+    n = int(n_fft)
+    if x.dim() in (1, 2) and n > 0 and n & (n - 1) == 0:
+        raise ValueError(f"n_fft {n} is a power of two: welch_fft_iq / welch_fused_iq transform it (one transform per n_fft)")
+    _cmfft_input(torch, x, n_fft, dev)
+
+
+def welch_fft_iq_mixed(params, x, n_fft, hop, scale, *, win_length=None, center=False, pad_mode="reflect", detrend=False, shift=None,
+                       fftshift=False, out=None, workspace=None):
+    """welch_fft_iq() at the n_fft of stft_iq_mixed() (bhw_welch_cmfft_f32_device): 2^a·3^b·5^c in 16..2047 that is no power of two,
+    odd lengths included -- 400, 1000, 1200, 1536, 2000, 2025.  x (T,) or (B, T), complex64, framed, windowed and transformed exactly
+    as stft_iq_mixed(params, x, n_fft, hop, win_length=..., center=..., pad_mode=..., detrend=...) does -- the (re, im) of every bin
+    are the same words -- and |Y|^2 summed over the frames in the same kernel, so the (B, F, n_fft) spectrum never reaches memory.
+    Returns float32 (n_fft,) or (B, n_fft) with welch_fft_iq()'s scale and order of the sums (chunks of 16 frames, blocks of 256, the
+    blocks); nothing is doubled.  P does not depend on B or the plan; for F <= 16 frames it is welch_psd(stft_iq_mixed(...), scale,
+    nfft=n_fft, onesided=False) bit for bit, for more frames within one float32 ulp of it.  fftshift=True writes bin
+    (j + n_fft - n_fft // 2) % n_fft to column j: torch.fft.fftshift of the same values, for an odd n_fft too.  A power-of-two n_fft
+    raises ValueError (welch_fft_iq transforms it), real x too (welch_fft_mixed), complex128 and every other n_fft too.  `out` and
+    `workspace` (B.welch_cmfft_workspace_bytes(...) // 8 float64 elements) as welch_fft_iq(): with both given the call neither
+    allocates nor synchronises and can be captured with no warm call."""
+    torch = _torch()
+    dev = x.device.index if isinstance(x, torch.Tensor) and x.is_cuda else None
+    return _welch_cfft_psd(torch, params, x, n_fft, hop, scale, win_length, center, pad_mode, detrend, shift, fftshift, out, workspace,
+                           dev, None, "cmfft")
+
+
+def welch_fused_iq_mixed(params, x, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", scaling="density", shift=None,
+                         fftshift=False, out=None, workspace=None):
+    """welch_fused_iq() at a mixed-radix nfft (bhw_welch_cmfft_f32_device): scipy.signal.welch's segments of a complex64 x, their
+    complex FFT at nfft = 400, 1000, 1536, 2025 ... unpadded, and the average over them in ONE kernel and a small join.  The
+    arguments, their checks, the window sums cache and the scale are welch_fused_iq()'s; the result is the two-sided estimate (freqs
+    float64, Pxx float32 (..., nfft)), freqs = fftfreq(nfft, 1 / fs), or with fftshift=True both freqs and Pxx in ascending frequency
+    (torch.fft.fftshift of the same values).  The SHARED read-only `freqs` are kept under keys of their own kind, so neither I/Q call
+    evicts the other's.  Only the mean is averaged.  The sum over the frames has the order of welch_fft_iq_mixed().  A power-of-two
+    nfft raises ValueError (welch_fused_iq), real x too (welch_fused_mixed).  After one warm call, with `out` and `workspace` given,
+    it neither synchronises nor allocates and can be captured (ResidentTable.welch_fused_iq_mixed); a first call inside a capture
+    raises."""
+    torch = _torch()
+    dev = x.device.index if isinstance(x, torch.Tensor) and x.is_cuda else None
+    return _welch_fused_iq(torch, params, x, fs, length, noverlap, nfft, detrend, scaling, shift, fftshift, out, workspace, dev, None,
+                           _SUMS_CACHE, "cmfft")
 
 
 # ---- Welch cross spectra: the pass behind the FFT for two signals -------------------------------------------------------------------------
@@ -2310,6 +2370,20 @@ class ResidentTable:
         captured into a graph, a first call inside a capture raises."""
         return _welch_fused_iq(_torch(), params, x, fs, length, noverlap, nfft, detrend, scaling, shift, fftshift, out, workspace,
                                self.device, self._live(), self._sums)
+
+    def welch_fft_iq_mixed(self, params, x, n_fft, hop, scale, *, win_length=None, center=False, pad_mode="reflect", detrend=False,
+                           shift=None, fftshift=False, out=None, workspace=None):
+        """welch_fft_iq_mixed() with the coefficients gathered from this table (bhw_welch_cmfft_f32_from_table): no allocation by the
+        library, no synchronisation, capturable on its first call; the bits are those of the library form."""
+        return _welch_cfft_psd(_torch(), params, x, n_fft, hop, scale, win_length, center, pad_mode, detrend, shift, fftshift, out,
+                               workspace, self.device, self._live(), "cmfft")
+
+    def welch_fused_iq_mixed(self, params, x, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", scaling="density",
+                             shift=None, fftshift=False, out=None, workspace=None):
+        """welch_fused_iq_mixed() from this table.  The sums cache and the capture rule are welch()'s: after one warm call the call
+        can be captured into a graph, a first call inside a capture raises."""
+        return _welch_fused_iq(_torch(), params, x, fs, length, noverlap, nfft, detrend, scaling, shift, fftshift, out, workspace,
+                               self.device, self._live(), self._sums, "cmfft")
 
     def cross_spectra(self, params, x, y, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", return_onesided=True,
                       scaling="density", shift=None, outputs=("pxy", "pxx", "pyy", "coherence", "h1"), fft="torch"):

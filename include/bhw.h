@@ -1161,8 +1161,8 @@ int bhw_describe_welch_fft(bhw_table t, const bhw_params *p, uint64_t length, co
  *     d_x or each other; and (from a table) the key match.
  *   - Capture: as bhw_stft_cfft_f32_*.  The library form needs no bhw_prepare_device; the from-table form is capturable on its first
  *     call.
- *   - Not built: I/Q input at the mixed-radix lengths; max-hold or median traces; n_fft 4096; I/Q cross spectra accumulated in
- *     the kernel (real input: bhw_csd_fft_f32_*); a filter bank on the averaged powers.
+ *   - Not built: max-hold or median traces; n_fft 4096; I/Q cross spectra accumulated in the kernel (real input:
+ *     bhw_csd_fft_f32_*); a filter bank on the averaged powers.  (I/Q input at the mixed-radix lengths: bhw_welch_cmfft_f32_* below.)
  *   - bhw_describe_welch_cfft: bhw_describe_stft_cfft's line in the same words (without the output form), plus the fields
  *     bhw_describe_welch_fft adds.  t may be NULL (the library call).  Host arithmetic only. */
 uint64_t bhw_welch_cfft_workspace_bytes(const bhw_stft *s);
@@ -1208,8 +1208,8 @@ int bhw_describe_welch_cfft(bhw_table t, const bhw_params *p, uint64_t length, c
  *     the key match.
  *   - Capture: as bhw_stft_mfft_f32_*.  The library form needs no bhw_prepare_device; the from-table form is capturable on its first
  *     call.
- *   - Not built: I/Q input at these lengths; odd n_fft and factors >= 7; cross spectra at these lengths in one kernel; max-hold or
- *     median traces.
+ *   - Not built: odd n_fft and factors >= 7; cross spectra at these lengths in one kernel; max-hold or median traces.  (I/Q input
+ *     at these lengths, odd ones included: bhw_welch_cmfft_f32_* below.)
  *   - bhw_describe_welch_mfft: bhw_describe_stft_mfft's line in the same words (without the output form), plus the fields
  *     bhw_describe_welch_fft adds.  t may be NULL (the library call).  Host arithmetic only. */
 uint64_t bhw_welch_mfft_workspace_bytes(const bhw_stft *s);
@@ -1220,6 +1220,59 @@ int bhw_welch_mfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t len
                                   double scale, uint32_t psd_flags, const float *d_x, float *d_P, uint64_t p_stride, void *workspace,
                                   uint64_t workspace_bytes);
 int bhw_describe_welch_mfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf, uint64_t len);
+
+/* Fused Welch PSD for complex (I/Q) input at a mixed-radix n_fft (400, 1000, 1200, 1536, odd lengths included): window, mixed-radix
+ * complex FFT and the average over the frames by ONE kernel and the join of bhw_welch_fft_f32_*.  The rows of bhw_stft_cmfft_f32_* are
+ * formed and transformed by the same kernel body, and |Y|^2 is accumulated over the frames where the transform ends, so the
+ * (B, F, n_fft) spectrum that bhw_stft_cmfft_f32_* + bhw_welch_psd_f32 write and read back never exists.  The argument list is
+ * bhw_welch_cfft_f32_*'s, word for word: the estimate is two-sided, n_fft bins, nothing is doubled, and there is no psd_flags.
+ *   - Inputs: (p, length, s, flags) exactly as bhw_stft_cmfft_f32_* takes them (channels 2, interleaved I/Q; the padding fields of s
+ *     as that call accepts them), except that flags is any combination of BHW_WELCH_DETREND_CONSTANT and BHW_CFFT_SHIFT --
+ *     BHW_CFFT_POWER is refused -- and s->y_stride and s->y_batch_stride must be 0: no spectrum is written.  scale is bhw_psd's; d_P
+ *     is float32 (B, n_fft), row b at b * p_stride floats (0 = n_fft).
+ *   - Row and transform: those of bhw_stft_cmfft_f32_* for the same (p, length, s) and the detrend flag.  Let (re, im) be the float32
+ *     pair that call writes for bin k of row (b, f), bit for bit: the same words, from the same row function.
+ *   - The sums, with q_f = (double) re * (double) re + (double) im * (double) im, are those of bhw_welch_fft_f32_* above:
+ *        A_chunk = sum of q_f over the frames of one chunk of BHW_WELCH_FFT_CHUNK = 16, in ascending f, binary64 from +0.0
+ *        A_blk   = sum of A_chunk over the 16 chunks of one block of BHW_WELCH_BLOCK = 256 frames, ascending, binary64 from +0.0
+ *        A       = sum of A_blk over the blocks, ascending, binary64 from +0.0
+ *        d_P[b * p_stride + j] = fl32(A * scale)
+ *     (the last chunk and the last block may be shorter).  Column j holds bin j, or with BHW_CFFT_SHIFT bin (j + n_fft - n_fft / 2)
+ *     mod n_fft: bin k goes to column (k + n_fft / 2) mod n_fft, the column rule of bhw_stft_cmfft_f32_*.  n_fft / 2 is integer
+ *     division, so for an odd n_fft the row is torch.fft.fftshift of the unshifted one (bin (n_fft + 1) / 2 comes first).
+ *   - Consequences: the bits of P depend on the window, n_fft, the flags, scale and the signal's samples only -- not on B, the grid,
+ *     or library versus table.  For F <= 16 P equals bhw_welch_psd_f32 (flags 0) of bhw_stft_cmfft_f32_*'s rows bit for bit; beyond
+ *     16 frames it lies within one float32 ulp of that route, by the argument given for bhw_welch_fft_f32_*.  There are no float
+ *     atomics: every chunk sum is stored plainly once.
+ *   - Workspace: caller-provided, 8-byte aligned, bhw_welch_cmfft_workspace_bytes(s) bytes: the chunk sums, B * ceil(F / 16) * n_fft
+ *     doubles, followed, when F > 256, by the block sums, B * ceil(F / 256) * n_fft doubles.  A short one is BHW_ERR_WORKSPACE.  No
+ *     call allocates.
+ *   - Supported: exactly the set of bhw_stft_cmfft_f32_* (channels 2, n_fft = 2^a 3^b 5^c in 16..2047 that is no power of two: 91
+ *     sizes, 18 of them odd); channels 1, a power of two and every other n_fft are BHW_ERR_UNSUPPORTED with that call's words, which
+ *     name the call that takes them.
+ *   - IEEE: a NaN or an infinity in x reaches only the bins of its own signal.  Zeros in give +0.0 out (for a scale >= 0).
+ *   - Checks before any HIP call, in this order (BHW_ERR_BADARG unless noted):
+ *       1. everything bhw_stft_cmfft_f32_* checks on the descriptor (with the y strides taken as packed), with that call's codes and
+ *          words: the descriptor and an unknown flag, channels 1, a power of two, an unsupported n_fft (BHW_ERR_UNSUPPORTED);
+ *       2. BHW_CFFT_POWER set, then non-zero y strides, then a scale that is not finite;
+ *       3. frames 0 returns BHW_OK here with the pointers unchecked;
+ *       4. p_stride below n_fft, B * ceil(F / 16) * n_fft above 2^34;
+ *       5. NULL d_x or d_P, either not 4-byte aligned;
+ *       6. a NULL or misaligned workspace, a short one (BHW_ERR_WORKSPACE);
+ *       7. d_P or the workspace overlapping d_x or each other;
+ *       8. (from a table) the key match.
+ *     Steps 2 to 7 are those of bhw_welch_cfft_f32_*, in its words.
+ *   - Capture: as bhw_stft_cmfft_f32_*.  The library form needs no bhw_prepare_device; the from-table form is capturable on its
+ *     first call.
+ *   - Not built: n_fft >= 2048; factors of 7 and above; I/Q cross spectra accumulated in the kernel; max-hold or median traces.
+ *   - bhw_describe_welch_cmfft: bhw_describe_stft_cmfft's line in the same words ("welch cmfft ...", without the output form), plus
+ *     the fields bhw_describe_welch_fft adds.  t may be NULL (the library call).  Host arithmetic only. */
+uint64_t bhw_welch_cmfft_workspace_bytes(const bhw_stft *s);
+int bhw_welch_cmfft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                               double scale, const float *d_x, float *d_P, uint64_t p_stride, void *workspace, uint64_t workspace_bytes);
+int bhw_welch_cmfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                   double scale, const float *d_x, float *d_P, uint64_t p_stride, void *workspace, uint64_t workspace_bytes);
+int bhw_describe_welch_cmfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf, uint64_t len);
 
 /* Fused Welch cross spectra: window, real FFT of TWO signals and the four averages over the frames by ONE kernel and a small join.  The
  * rows of bhw_stft_fft_f32_* of x and of y are formed and transformed side by side by the same kernel body, and the terms of
