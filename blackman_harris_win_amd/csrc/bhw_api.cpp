@@ -1243,6 +1243,39 @@ int welch_cmfft_run(bhw_table t, const bhw_params *p, uint64_t length, int devic
     });
 }
 
+// The fused max-hold / min-hold traces for I/Q input (t NULL: the direct CORDIC chains): the checks, then the reducing kernel and the
+// join.  A NULL output is a trace that is not stored.
+int hold_cfft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *s, uint32_t flags,
+                  double scale, const float *d_x, float *d_max, float *d_min, uint64_t p_stride, void *workspace, uint64_t workspace_bytes)
+{
+    int rc = bhwp_hold_cfft_checks(p, length, s, flags, scale, p_stride, d_x, d_max, d_min, workspace, workspace_bytes);
+    if (!rc && t) rc = table_call_checks(t, p);
+    if (rc || !s->frames) return rc;
+    const uint32_t traces = (d_max ? BHW_HOLD_MAX : 0u) | (d_min ? BHW_HOLD_MIN : 0u);
+    const BhwHoldCfftPlan pl = bhwp_hold_cfft_plan(p, length, s, flags, p_stride, traces, t != nullptr);
+    const char *what = t ? "hold cfft launch (resident table)" : "hold cfft launch";
+    return run_source(t, p, length, device, stream, what, [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *tab,
+                                                              const BhwLenPhase *lp) {
+        return bhwk_hold_cfft_f32(l, c, w, pl, s, scale, d_x, d_max, d_min, workspace, tab, *lp);
+    });
+}
+
+// The same at a mixed-radix n_fft.
+int hold_cmfft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *s, uint32_t flags,
+                   double scale, const float *d_x, float *d_max, float *d_min, uint64_t p_stride, void *workspace, uint64_t workspace_bytes)
+{
+    int rc = bhwp_hold_cmfft_checks(p, length, s, flags, scale, p_stride, d_x, d_max, d_min, workspace, workspace_bytes);
+    if (!rc && t) rc = table_call_checks(t, p);
+    if (rc || !s->frames) return rc;
+    const uint32_t traces = (d_max ? BHW_HOLD_MAX : 0u) | (d_min ? BHW_HOLD_MIN : 0u);
+    const BhwHoldCmfftPlan pl = bhwp_hold_cmfft_plan(p, length, s, flags, p_stride, traces, t != nullptr);
+    const char *what = t ? "hold cmfft launch (resident table)" : "hold cmfft launch";
+    return run_source(t, p, length, device, stream, what, [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *tab,
+                                                              const BhwLenPhase *lp) {
+        return bhwk_hold_cmfft_f32(l, c, w, pl, s, scale, d_x, d_max, d_min, workspace, tab, *lp);
+    });
+}
+
 // The fused Welch PSD at a mixed-radix n_fft (t NULL: the direct CORDIC chains): the checks, then the accumulating kernel and the join.
 int welch_mfft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *s, uint32_t flags,
                    double scale, uint32_t psd_flags, const float *d_x, float *d_P, uint64_t p_stride, void *workspace, uint64_t workspace_bytes)
@@ -1670,6 +1703,70 @@ int bhw_describe_welch_cmfft(bhw_table t, const bhw_params *p, uint64_t length, 
     int rc = bhwp_welch_cmfft_checks(p, length, s, flags, 0.0, 0, nullptr, nullptr, nullptr, 0, false);
     if (!rc && t) rc = table_call_checks(t, p);
     return rc ? rc : bhwp_describe_welch_cmfft(p, t ? &t->c : nullptr, length, s, flags, buf, len);
+}
+
+// ---- fused max-hold / min-hold traces for I/Q input (include/bhw.h: bhw_hold_cfft_f32_device ..., bhw_hold_cmfft_f32_device ...) ----------
+
+uint64_t bhw_hold_cfft_workspace_bytes(const bhw_stft *s)
+{
+    return s && s->struct_size == sizeof(bhw_stft) ? bhwp_hold_cfft_workspace_bytes(s) : 0;
+}
+
+int bhw_hold_cfft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                             double scale, const float *d_x, float *d_max, float *d_min, uint64_t p_stride, void *workspace,
+                             uint64_t workspace_bytes)
+{
+    return hold_cfft_run(nullptr, p, length, device, hip_stream, s, flags, scale, d_x, d_max, d_min, p_stride, workspace, workspace_bytes);
+}
+
+int bhw_hold_cfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                 double scale, const float *d_x, float *d_max, float *d_min, uint64_t p_stride, void *workspace,
+                                 uint64_t workspace_bytes)
+{
+    const int rc = bhwp_hold_cfft_checks(p, length, s, flags, scale, p_stride, d_x, d_max, d_min, workspace, workspace_bytes);
+    if (rc) return rc;
+    return t ? hold_cfft_run(t, p, length, t->device, hip_stream, s, flags, scale, d_x, d_max, d_min, p_stride, workspace, workspace_bytes)
+             : fail(BHW_ERR_BADARG, "table is NULL");
+}
+
+int bhw_describe_hold_cfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, uint32_t traces, char *buf,
+                           uint64_t len)
+{
+    int rc = bhwp_hold_cfft_checks(p, length, s, flags, 0.0, 0, nullptr, nullptr, nullptr, nullptr, 0, false);
+    if (!rc) rc = bhwp_hold_traces_check(traces);
+    if (!rc && t) rc = table_call_checks(t, p);
+    return rc ? rc : bhwp_describe_hold_cfft(p, t ? &t->c : nullptr, length, s, flags, traces, buf, len);
+}
+
+uint64_t bhw_hold_cmfft_workspace_bytes(const bhw_stft *s)
+{
+    return s && s->struct_size == sizeof(bhw_stft) ? bhwp_hold_cmfft_workspace_bytes(s) : 0;
+}
+
+int bhw_hold_cmfft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                              double scale, const float *d_x, float *d_max, float *d_min, uint64_t p_stride, void *workspace,
+                              uint64_t workspace_bytes)
+{
+    return hold_cmfft_run(nullptr, p, length, device, hip_stream, s, flags, scale, d_x, d_max, d_min, p_stride, workspace, workspace_bytes);
+}
+
+int bhw_hold_cmfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                  double scale, const float *d_x, float *d_max, float *d_min, uint64_t p_stride, void *workspace,
+                                  uint64_t workspace_bytes)
+{
+    const int rc = bhwp_hold_cmfft_checks(p, length, s, flags, scale, p_stride, d_x, d_max, d_min, workspace, workspace_bytes);
+    if (rc) return rc;
+    return t ? hold_cmfft_run(t, p, length, t->device, hip_stream, s, flags, scale, d_x, d_max, d_min, p_stride, workspace, workspace_bytes)
+             : fail(BHW_ERR_BADARG, "table is NULL");
+}
+
+int bhw_describe_hold_cmfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, uint32_t traces, char *buf,
+                            uint64_t len)
+{
+    int rc = bhwp_hold_cmfft_checks(p, length, s, flags, 0.0, 0, nullptr, nullptr, nullptr, nullptr, 0, false);
+    if (!rc) rc = bhwp_hold_traces_check(traces);
+    if (!rc && t) rc = table_call_checks(t, p);
+    return rc ? rc : bhwp_describe_hold_cmfft(p, t ? &t->c : nullptr, length, s, flags, traces, buf, len);
 }
 
 // ---- fused Welch PSD at mixed-radix n_fft (include/bhw.h: bhw_welch_mfft_f32_device ...) ---------------------------------------------------

@@ -133,3 +133,8 @@ int bhwk_welch_join(const BhwLaunch &l, double *d_ws, float *d_P, uint64_t batch
 // k_welch_fft_join<true, false> into the block sums behind them.  The four chains of a cross spectrum are part of the bin axis there.
 int bhwk_welch_join_blocks(const BhwLaunch &l, double *d_ws, uint64_t batch, uint64_t bins, uint64_t chunks, uint64_t blocks,
                            uint64_t blocks_grid);
+// The join of the fused hold calls (bhw_hold_cfft.hip; also launched by bhw_hold_cmfft.hip): the chunk pairs (the words of the
+// maximum and of the minimum, 8 bytes) [(b * chunks + c) * bins + j] at d_ws, followed (blocks > 1) by the block pairs, reduced by
+// k_hold_join in one launch (one block) or two; the traces are scaled and written to d_max and d_min, either of which may be NULL.
+int bhwk_hold_join(const BhwLaunch &l, void *d_ws, float *d_max, float *d_min, uint64_t batch, uint64_t bins, uint64_t chunks,
+                   uint64_t blocks, uint64_t blocks_grid, uint64_t join_grid, uint64_t p_stride, double scale);

@@ -2508,8 +2508,11 @@ BhwWelchCfftPlan bhwp_welch_cfft_plan(const bhw_params *p, uint64_t length, cons
     return pl;
 }
 
-int bhwp_describe_welch_cfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf,
-                             uint64_t len)
+// The describe line of the calls that put stft_cfft_rows under an epilogue that owns runs: bhw_describe_welch_cfft (what "welch", the
+// join k_welch_fft_join, no tail) and bhw_describe_hold_cfft (what "hold", its kernels, its join and the traces as the tail).
+static int describe_cfft_runs(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags,
+                              const char *what, const char *k_direct, const char *k_table, const char *join, const char *tail, char *buf,
+                              uint64_t len)
 {
     if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
     const char *route = ct ? "table" : "direct";
@@ -2519,27 +2522,33 @@ int bhwp_describe_welch_cfft(const bhw_params *p, const BhwCordicCfg *ct, uint64
     const char *det = pl.detrend ? "constant detrend" : "no detrending";
     const char *bins = pl.shifted ? "bins shifted" : "bins in order";
     if (!s->frames) {
-        snprintf(buf, len, "welch cfft %s (L = %llu, n_fft %llu, %s), %s: nothing (frames 0)", route, (unsigned long long)length,
-                 (unsigned long long)s->n_fft, det, bins);
+        snprintf(buf, len, "%s cfft %s (L = %llu, n_fft %llu, %s), %s: nothing (frames 0)%s", what, route, (unsigned long long)length,
+                 (unsigned long long)s->n_fft, det, bins, tail);
         return BHW_OK;
     }
     char kern[64], sched[48];
-    kernel_name(p, ct, "k_welch_cfft_direct", "k_welch_cfft_table", false, kern, sizeof kern);
+    kernel_name(p, ct, k_direct, k_table, false, kern, sizeof kern);
     BhwStftFftPlan f{};
     f.radix4 = pl.radix4;
     f.radix2 = pl.radix2;
     bhwp_stft_fft_schedule(f, sched, sizeof sched);
-    snprintf(buf, len, "welch cfft %s (L = %llu, n_fft %llu, col0 %llu, pad %llu %s, %s), %s: %s, %llu signals x %llu frames = %llu rows, "
+    snprintf(buf, len, "%s cfft %s (L = %llu, n_fft %llu, col0 %llu, pad %llu %s, %s), %s: %s, %llu signals x %llu frames = %llu rows, "
              "complex FFT of %u points in passes %s (no split), %u lanes per row x %u rows per workgroup, %u columns per lane, %llu groups, "
              "grid %llu x %u lanes, %u bytes of LDS; chunk %u frames, %llu runs of %llu frames (%u group%s per run), %u accumulator%s "
-             "per lane, %llu chunks and %llu block%s per signal, then k_welch_fft_join %s, workspace %llu bytes",
-             route, (unsigned long long)length, (unsigned long long)s->n_fft, (unsigned long long)s->col0, (unsigned long long)s->pad, pad,
+             "per lane, %llu chunks and %llu block%s per signal, then %s %s, workspace %llu bytes%s",
+             what, route, (unsigned long long)length, (unsigned long long)s->n_fft, (unsigned long long)s->col0, (unsigned long long)s->pad, pad,
              det, bins, kern, (unsigned long long)s->batch, (unsigned long long)s->frames, (unsigned long long)pl.rows, pl.n, sched, pl.lpf,
              pl.fy, pl.cpl, (unsigned long long)pl.groups, (unsigned long long)pl.grid, kFftBlock, pl.lds_bytes, BHW_WELCH_FFT_CHUNK,
              (unsigned long long)wp.runs, (unsigned long long)wp.run, wp.gpr, wp.gpr == 1 ? "" : "s", wp.acc, wp.acc == 1 ? "" : "s",
-             (unsigned long long)wp.chunks, (unsigned long long)wp.blocks, wp.blocks == 1 ? "" : "s",
-             wp.blocks == 1 ? "once (chunks)" : "twice (chunks, blocks)", (unsigned long long)wp.ws_bytes);
+             (unsigned long long)wp.chunks, (unsigned long long)wp.blocks, wp.blocks == 1 ? "" : "s", join,
+             wp.blocks == 1 ? "once (chunks)" : "twice (chunks, blocks)", (unsigned long long)wp.ws_bytes, tail);
     return BHW_OK;
+}
+
+int bhwp_describe_welch_cfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf,
+                             uint64_t len)
+{
+    return describe_cfft_runs(p, ct, length, s, flags, "welch", "k_welch_cfft_direct", "k_welch_cfft_table", "k_welch_fft_join", "", buf, len);
 }
 
 // ---- fused Welch PSD for I/Q input at mixed-radix n_fft -----------------------------------------------------------------------------------------
@@ -2591,8 +2600,10 @@ BhwWelchCmfftPlan bhwp_welch_cmfft_plan(const bhw_params *p, uint64_t length, co
     return pl;
 }
 
-int bhwp_describe_welch_cmfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf,
-                              uint64_t len)
+// describe_cfft_runs for stft_cmfft_rows: bhw_describe_welch_cmfft and bhw_describe_hold_cmfft.
+static int describe_cmfft_runs(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags,
+                               const char *what, const char *k_direct, const char *k_table, const char *join, const char *tail, char *buf,
+                               uint64_t len)
 {
     if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
     const char *route = ct ? "table" : "direct";
@@ -2602,27 +2613,135 @@ int bhwp_describe_welch_cmfft(const bhw_params *p, const BhwCordicCfg *ct, uint6
     const char *det = pl.detrend ? "constant detrend" : "no detrending";
     const char *bins = pl.shifted ? "bins shifted" : "bins in order";
     if (!s->frames) {
-        snprintf(buf, len, "welch cmfft %s (L = %llu, n_fft %llu, %s), %s: nothing (frames 0)", route, (unsigned long long)length,
-                 (unsigned long long)s->n_fft, det, bins);
+        snprintf(buf, len, "%s cmfft %s (L = %llu, n_fft %llu, %s), %s: nothing (frames 0)%s", what, route, (unsigned long long)length,
+                 (unsigned long long)s->n_fft, det, bins, tail);
         return BHW_OK;
     }
     char kern[64], sched[48];
-    kernel_name(p, ct, "k_welch_cmfft_direct", "k_welch_cmfft_table", false, kern, sizeof kern);
+    kernel_name(p, ct, k_direct, k_table, false, kern, sizeof kern);
     BhwStftMfftPlan f{};
     f.passes = pl.passes;
     memcpy(f.radix, pl.radix, sizeof f.radix);
     bhwp_stft_mfft_schedule(f, sched, sizeof sched);
-    snprintf(buf, len, "welch cmfft %s (L = %llu, n_fft %llu, col0 %llu, pad %llu %s, %s), %s: %s, %llu signals x %llu frames = %llu rows, "
+    snprintf(buf, len, "%s cmfft %s (L = %llu, n_fft %llu, col0 %llu, pad %llu %s, %s), %s: %s, %llu signals x %llu frames = %llu rows, "
              "complex FFT of %u points in passes %s (no split), %u lanes per row x %u rows per workgroup, %u columns per lane, %llu groups, "
              "grid %llu x %u lanes, %u bytes of LDS, %u twiddles; chunk %u frames, %llu runs of %llu frames (%u group%s per run), "
-             "%u accumulator%s per lane, %llu chunks and %llu block%s per signal, then k_welch_fft_join %s, workspace %llu bytes",
-             route, (unsigned long long)length, (unsigned long long)s->n_fft, (unsigned long long)s->col0, (unsigned long long)s->pad, pad,
+             "%u accumulator%s per lane, %llu chunks and %llu block%s per signal, then %s %s, workspace %llu bytes%s",
+             what, route, (unsigned long long)length, (unsigned long long)s->n_fft, (unsigned long long)s->col0, (unsigned long long)s->pad, pad,
              det, bins, kern, (unsigned long long)s->batch, (unsigned long long)s->frames, (unsigned long long)pl.rows, pl.n, sched, pl.lpf,
              pl.fy, pl.cpl, (unsigned long long)pl.groups, (unsigned long long)pl.grid, kFftBlock, pl.lds_bytes, pl.fold,
              BHW_WELCH_FFT_CHUNK, (unsigned long long)wp.runs, (unsigned long long)wp.run, wp.gpr, wp.gpr == 1 ? "" : "s", wp.acc,
-             wp.acc == 1 ? "" : "s", (unsigned long long)wp.chunks, (unsigned long long)wp.blocks, wp.blocks == 1 ? "" : "s",
-             wp.blocks == 1 ? "once (chunks)" : "twice (chunks, blocks)", (unsigned long long)wp.ws_bytes);
+             wp.acc == 1 ? "" : "s", (unsigned long long)wp.chunks, (unsigned long long)wp.blocks, wp.blocks == 1 ? "" : "s", join,
+             wp.blocks == 1 ? "once (chunks)" : "twice (chunks, blocks)", (unsigned long long)wp.ws_bytes, tail);
     return BHW_OK;
+}
+
+int bhwp_describe_welch_cmfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf,
+                              uint64_t len)
+{
+    return describe_cmfft_runs(p, ct, length, s, flags, "welch", "k_welch_cmfft_direct", "k_welch_cmfft_table", "k_welch_fft_join", "", buf,
+                               len);
+}
+
+// ---- fused max-hold / min-hold traces for I/Q input -------------------------------------------------------------------------------------------
+
+uint64_t bhwp_hold_cfft_workspace_bytes(const bhw_stft *s) { return bhwp_welch_cfft_workspace_bytes(s); }
+uint64_t bhwp_hold_cmfft_workspace_bytes(const bhw_stft *s) { return bhwp_welch_cmfft_workspace_bytes(s); }
+
+int bhwp_hold_traces_check(uint32_t traces)
+{
+    if (!traces || (traces & ~(BHW_HOLD_MAX | BHW_HOLD_MIN)))
+        return bhwp_fail(BHW_ERR_BADARG, "traces 0x%x: a non-empty subset of BHW_HOLD_MAX | BHW_HOLD_MIN", traces);
+    return BHW_OK;
+}
+
+// The pointers of both hold calls, after the Welch sibling's check function passed everything else (the descriptor, the flags, the
+// y strides, scale, p_stride and the 2^34 bound: steps 1 to 4 of include/bhw.h): steps 5 to 7.  d_P's rules hold for each output
+// and between the two.
+static int hold_pointer_checks(const bhw_stft *s, uint64_t p_stride, const void *d_x, const void *d_max, const void *d_min,
+                               const void *workspace, uint64_t workspace_bytes)
+{
+    const uint64_t T = s->samples, N = s->n_fft;
+    if (!s->frames) return BHW_OK;
+    // 5.
+    if (!d_x) return bhwp_fail(BHW_ERR_BADARG, "d_x is NULL");
+    if (!d_max && !d_min) return bhwp_fail(BHW_ERR_BADARG, "d_max and d_min are both NULL: no trace is asked for");
+    if ((uintptr_t)d_max % 4) return bhwp_fail(BHW_ERR_BADARG, "d_max is not 4-byte aligned");
+    if ((uintptr_t)d_min % 4) return bhwp_fail(BHW_ERR_BADARG, "d_min is not 4-byte aligned");
+    if ((uintptr_t)d_x % 4) return bhwp_fail(BHW_ERR_BADARG, "d_x is not 4-byte aligned");
+    // 6.
+    const uint64_t need = bhwp_welch_cfft_workspace_bytes(s);
+    if (!workspace) return bhwp_fail(BHW_ERR_BADARG, "workspace is NULL: the chunk pairs need %llu bytes", (unsigned long long)need);
+    if ((uintptr_t)workspace % 8) return bhwp_fail(BHW_ERR_BADARG, "workspace is not 8-byte aligned");
+    if (workspace_bytes < need)
+        return bhwp_fail(BHW_ERR_WORKSPACE, "workspace of %llu bytes, the chunk and block pairs need %llu", (unsigned long long)workspace_bytes,
+                         (unsigned long long)need);
+    // 7. (x counts floats: 2 T of a signal)
+    const uint64_t xs = s->x_stride ? s->x_stride : 2 * T, ps = p_stride ? p_stride : N;
+    const unsigned __int128 xe = (unsigned __int128)(s->batch - 1) * xs + 2 * T, pe = (unsigned __int128)(s->batch - 1) * ps + N;
+    if (xe > (1ull << 60) || pe > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "x or trace extent beyond 2^60 elements");
+    const uint64_t xa = (uint64_t)(uintptr_t)d_x, wa = (uint64_t)(uintptr_t)workspace;
+    const uint64_t xb = (uint64_t)xe * 4u, pb = (uint64_t)pe * 4u;
+    const uint64_t oa[2] = {(uint64_t)(uintptr_t)d_max, (uint64_t)(uintptr_t)d_min};
+    const char *const name[2] = {"d_max", "d_min"};
+    if (xa > UINT64_MAX - xb || wa > UINT64_MAX - need || (d_max && oa[0] > UINT64_MAX - pb) || (d_min && oa[1] > UINT64_MAX - pb))
+        return bhwp_fail(BHW_ERR_BADARG, "x, trace or workspace range wraps the address space");
+    for (int i = 0; i < 2; ++i)
+        if (oa[i] && xa < oa[i] + pb && oa[i] < xa + xb) return bhwp_fail(BHW_ERR_BADARG, "d_x and %s overlap", name[i]);
+    if (d_max && d_min && oa[0] < oa[1] + pb && oa[1] < oa[0] + pb) return bhwp_fail(BHW_ERR_BADARG, "d_max and d_min overlap");
+    if (wa < xa + xb && xa < wa + need) return bhwp_fail(BHW_ERR_BADARG, "workspace overlaps d_x");
+    for (int i = 0; i < 2; ++i)
+        if (oa[i] && wa < oa[i] + pb && oa[i] < wa + need) return bhwp_fail(BHW_ERR_BADARG, "workspace overlaps %s", name[i]);
+    return BHW_OK;
+}
+
+int bhwp_hold_cfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, double scale, uint64_t p_stride,
+                          const void *d_x, const void *d_max, const void *d_min, const void *workspace, uint64_t workspace_bytes,
+                          bool pointers)
+{
+    const int rc = bhwp_welch_cfft_checks(p, length, s, flags, scale, p_stride, nullptr, nullptr, nullptr, 0, false);
+    if (rc || !pointers) return rc;
+    return hold_pointer_checks(s, p_stride, d_x, d_max, d_min, workspace, workspace_bytes);
+}
+
+int bhwp_hold_cmfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, double scale, uint64_t p_stride,
+                           const void *d_x, const void *d_max, const void *d_min, const void *workspace, uint64_t workspace_bytes,
+                           bool pointers)
+{
+    const int rc = bhwp_welch_cmfft_checks(p, length, s, flags, scale, p_stride, nullptr, nullptr, nullptr, 0, false);
+    if (rc || !pointers) return rc;
+    return hold_pointer_checks(s, p_stride, d_x, d_max, d_min, workspace, workspace_bytes);
+}
+
+BhwHoldCfftPlan bhwp_hold_cfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, uint64_t p_stride,
+                                    uint32_t traces, bool from_table)
+{
+    return BhwHoldCfftPlan{bhwp_welch_cfft_plan(p, length, s, flags, p_stride, from_table), traces};
+}
+
+BhwHoldCmfftPlan bhwp_hold_cmfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, uint64_t p_stride,
+                                      uint32_t traces, bool from_table)
+{
+    return BhwHoldCmfftPlan{bhwp_welch_cmfft_plan(p, length, s, flags, p_stride, from_table), traces};
+}
+
+static const char *hold_traces_tail(uint32_t traces)
+{
+    return traces == BHW_HOLD_MAX ? "; traces: max" : traces == BHW_HOLD_MIN ? "; traces: min" : "; traces: max, min";
+}
+
+int bhwp_describe_hold_cfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags,
+                            uint32_t traces, char *buf, uint64_t len)
+{
+    return describe_cfft_runs(p, ct, length, s, flags, "hold", "k_hold_cfft_direct", "k_hold_cfft_table", "k_hold_join",
+                              hold_traces_tail(traces), buf, len);
+}
+
+int bhwp_describe_hold_cmfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags,
+                             uint32_t traces, char *buf, uint64_t len)
+{
+    return describe_cmfft_runs(p, ct, length, s, flags, "hold", "k_hold_cmfft_direct", "k_hold_cmfft_table", "k_hold_join",
+                               hold_traces_tail(traces), buf, len);
 }
 
 // ---- fused Welch PSD at mixed-radix n_fft -------------------------------------------------------------------------------------------------------

@@ -747,6 +747,49 @@ int  bhwp_describe_welch_cmfft(const bhw_params *p, const BhwCordicCfg *ct, uint
 int  bhwk_welch_cmfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwWelchCmfftPlan &pl, const bhw_stft *s,
                           double scale, const float *d_x, float *d_P, double *d_ws, const int32_t *d_table, const BhwLenPhase &lp);
 
+// ---- fused max-hold / min-hold traces for I/Q input (bhw_hold_cfft_f32_*, bhw_hold_cmfft_f32_*; bhw_hold_cfft.hip, bhw_hold_cmfft.hip) -----
+// The plan of a hold call IS the plan of its Welch sibling (welch: the lanes, LDS, schedule, runs, chunks, blocks, grids and the
+// workspace bytes, field for field) plus the traces that are stored.  A (max, min) pair of float32 words is the 8 bytes of a chunk sum,
+// so bhwp_welch_runs' figures hold unchanged; welch.acc counts the PAIRS a lane carries over a run here (at most kHoldMaxAcc).
+constexpr uint32_t kHoldMaxAcc = 8;                   // kWelchCfftMaxAcc, kWelchCmfftMaxAcc
+struct BhwHoldCfftPlan {
+    BhwWelchCfftPlan welch;
+    uint32_t traces;      // BHW_HOLD_MAX | BHW_HOLD_MIN: what is stored (both are always computed)
+};
+struct BhwHoldCmfftPlan {
+    BhwWelchCmfftPlan welch;
+    uint32_t traces;
+};
+// Every check of the calls that needs no table handle, before any HIP call and in the order of include/bhw.h: the Welch sibling's
+// check function for everything but the pointers (bhwp_welch_cfft_checks / bhwp_welch_cmfft_checks, `pointers` false), then the two
+// outputs and the workspace (one text for both families).  frames 0 passes with the pointers unchecked; `pointers` false: the
+// describe call.
+int  bhwp_hold_cfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, double scale, uint64_t p_stride,
+                           const void *d_x, const void *d_max, const void *d_min, const void *workspace, uint64_t workspace_bytes,
+                           bool pointers = true);
+int  bhwp_hold_cmfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, double scale, uint64_t p_stride,
+                            const void *d_x, const void *d_max, const void *d_min, const void *workspace, uint64_t workspace_bytes,
+                            bool pointers = true);
+// bhw_hold_c(m)fft_workspace_bytes: the Welch sibling's figure
+uint64_t bhwp_hold_cfft_workspace_bytes(const bhw_stft *s);
+uint64_t bhwp_hold_cmfft_workspace_bytes(const bhw_stft *s);
+BhwHoldCfftPlan  bhwp_hold_cfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, uint64_t p_stride,
+                                     uint32_t traces, bool from_table);
+BhwHoldCmfftPlan bhwp_hold_cmfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, uint64_t p_stride,
+                                      uint32_t traces, bool from_table);
+// traces: a non-empty subset of BHW_HOLD_MAX | BHW_HOLD_MIN (checked by the caller)
+int  bhwp_describe_hold_cfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags,
+                             uint32_t traces, char *buf, uint64_t len);
+int  bhwp_describe_hold_cmfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags,
+                              uint32_t traces, char *buf, uint64_t len);
+int  bhwp_hold_traces_check(uint32_t traces);
+int  bhwk_hold_cfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwHoldCfftPlan &pl, const bhw_stft *s,
+                        double scale, const float *d_x, float *d_max, float *d_min, void *d_ws, const int32_t *d_table,
+                        const BhwLenPhase &lp);
+int  bhwk_hold_cmfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwHoldCmfftPlan &pl, const bhw_stft *s,
+                         double scale, const float *d_x, float *d_max, float *d_min, void *d_ws, const int32_t *d_table,
+                         const BhwLenPhase &lp);
+
 // ---- fused Welch PSD at mixed-radix n_fft (bhw_welch_mfft_f32_*; bhw_welch_mfft.hip) --------------------------------------------------------
 // BhwWelchMfftPlan wraps BhwStftMfftPlan as BhwWelchCfftPlan wraps BhwStftCfftPlan: the lanes, LDS, schedule and row steps are
 // bhwp_stft_mfft_plan's field for field (fft, form BHWP_MFFT_SPECTRUM, with groups and grid recounted), the ownership is

@@ -1543,7 +1543,11 @@ def _welch_cfft_call(torch, params, L, s, flags, xb, nb, n_fft, scale, out, work
 
 
 def _welch_cfft_psd(torch, params, x, n_fft, hop, scale, win_length, center, pad_mode, detrend, shift, fftshift, out, workspace, dev,
-                    table, family="cfft"):
+                    table, family="cfft", hold=None):
+    """hold: None (the mean: welch_fft_iq*), or (traces, out_max, out_min) for the max-hold / min-hold traces of the same call
+    (hold_fft_iq*): the same checks of the input, the same descriptor and flags, _hold_call in place of _welch_cfft_call."""
+    if hold is not None:
+        B.hold_traces(hold[0])
     check = _cfft_input if family == "cfft" else _welch_cmfft_input
     n_fft, L, xb, nb, T, frames, d = _stft_front(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, dev, check)
     if not x.is_cuda or x.device.index != dev:
@@ -1552,6 +1556,8 @@ def _welch_cfft_psd(torch, params, x, n_fft, hop, scale, win_length, center, pad
     s = B.make_stft(nb, T, frames, d["hop"], n_fft, col0=d["col0"], pad=d["pad"], pad_mode=d["pad_mode"], channels=2, shift=shift,
                     x_stride=xb.stride(0) * 2 if nb > 1 else 0)
     flags = (B.WELCH_DETREND_CONSTANT if detrend else 0) | (B.CFFT_SHIFT if fftshift else 0)
+    if hold is not None:
+        return _hold_call(torch, params, L, s, flags, xb, nb, n_fft, scale, hold, workspace, dev, table, x.dim() == 1, family)
     return _welch_cfft_call(torch, params, L, s, flags, xb, nb, n_fft, scale, out, workspace, dev, table, x.dim() == 1, family)
 
 
@@ -1594,7 +1600,11 @@ def _freq_axis_iq(torch, cache, nfft, fs, fftshift, dev, kind="freqs_iq"):
 
 
 def _welch_fused_iq(torch, params, x, fs, length, noverlap, nfft, detrend, scaling, shift, fftshift, out, workspace, dev, table, cache,
-                    family="cfft"):
+                    family="cfft", hold=None):
+    """hold: None (the mean: welch_fused_iq*), or (traces, out_max, out_min) for hold_fused_iq*: the same checks, window sums and
+    frequency axis (the same cache keys), the scale of ONE frame's periodogram, and _hold_call in place of _welch_cfft_call."""
+    if hold is not None:
+        B.hold_traces(hold[0])
     if detrend not in ("constant", False, None):
         raise ValueError(f"detrend must be 'constant' or False, got {detrend!r}")
     if scaling not in ("density", "spectrum"):
@@ -1619,12 +1629,14 @@ def _welch_fused_iq(torch, params, x, fs, length, noverlap, nfft, detrend, scali
     frames = 1 + (T - L) // hop
     xb = _stft_input(xb, (T,))
     sums = _window_sums(torch, params, L, True, shift, dev, table, cache)
-    scale = B.welch_scale(sums, frames, fs, scaling)
+    scale = B.welch_scale(sums, frames if hold is None else 1, fs, scaling)
     sh = params.dat_width - 1 if shift is None else int(shift)
     s = B.make_stft(nb, T, frames, hop, nfft, channels=2, shift=sh, x_stride=xb.stride(0) * 2 if nb > 1 else 0)
     # before the launch: it refuses inside a capture when missing
     freqs = _freq_axis_iq(torch, cache, nfft, fs, fftshift, dev, "freqs_iq" if family == "cfft" else "freqs_iq_mixed")
     flags = (B.WELCH_DETREND_CONSTANT if detrend == "constant" else 0) | (B.CFFT_SHIFT if fftshift else 0)
+    if hold is not None:
+        return (freqs,) + _hold_call(torch, params, L, s, flags, xb, nb, nfft, scale, hold, workspace, dev, table, x.dim() == 1, family)
     P = _welch_cfft_call(torch, params, L, s, flags, xb, nb, nfft, scale, out, workspace, dev, table, x.dim() == 1, family)
     return freqs, P
 
@@ -1694,6 +1706,107 @@ def welch_fused_iq_mixed(params, x, fs=1.0, *, length, noverlap=None, nfft=None,
     dev = x.device.index if isinstance(x, torch.Tensor) and x.is_cuda else None
     return _welch_fused_iq(torch, params, x, fs, length, noverlap, nfft, detrend, scaling, shift, fftshift, out, workspace, dev, None,
                            _SUMS_CACHE, "cmfft")
+
+
+# ---- fused max-hold / min-hold traces for I/Q input: window, complex FFT and the extrema over the frames in one kernel -------------------
+
+def _hold_call(torch, params, L, s, flags, xb, nb, n_fft, scale, hold, workspace, dev, table, one_d, family):
+    """The output and workspace rules of the fused hold calls and their launch: (pmax, pmin), each float32 (n_fft,) or (B, n_fft)
+    or None for the trace not asked for.  The rules of each output are those of welch_fft_iq's `out`; both given share one row
+    stride (the C call has one p_stride)."""
+    traces, out_max, out_min = hold
+    mask = B.hold_traces(traces)
+    lib = B.lib()
+    if family == "cfft":
+        ws_bytes, device_call, table_call = B.hold_cfft_workspace_bytes, lib.bhw_hold_cfft_f32_device, lib.bhw_hold_cfft_f32_from_table
+    else:
+        ws_bytes, device_call, table_call = B.hold_cmfft_workspace_bytes, lib.bhw_hold_cmfft_f32_device, lib.bhw_hold_cmfft_f32_from_table
+    shape = (n_fft,) if one_d else (nb, n_fft)
+    outs = []
+    for bit, name, out in ((B.HOLD_MAX, "out_max", out_max), (B.HOLD_MIN, "out_min", out_min)):
+        if not mask & bit:
+            if out is not None:
+                raise ValueError(f"{name} is given but traces={traces!r} does not ask for that trace")
+        elif out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=xb.device)
+        elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != xb.device or tuple(out.shape) != shape \
+                or out.stride(-1) != 1 or (out.dim() == 2 and nb > 1 and out.stride(0) < n_fft):
+            raise ValueError(f"{name} must be a float32 tensor of shape {shape} on x's device, contiguous along the bins, rows apart")
+        outs.append(out)
+    pmax, pmin = outs
+    strides = {o.stride(0) for o in outs if o is not None and o.dim() == 2 and nb > 1}
+    if len(strides) > 1:
+        raise ValueError("out_max and out_min must have the same row stride")
+    need = ws_bytes(s) // 8
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float64, device=xb.device)
+    else:
+        _check_out(torch, workspace, need, "workspace", torch.float64)
+    ptr = lambda o: ctypes.c_void_p(o.data_ptr()) if o is not None else None   # noqa: E731
+    tail = (ctypes.byref(s), flags, float(scale), ctypes.c_void_p(xb.data_ptr()), ptr(pmax), ptr(pmin),
+            strides.pop() if strides else 0, ctypes.c_void_p(workspace.data_ptr()), workspace.numel() * 8)
+    if table is None:
+        B.check(device_call(ctypes.byref(params), L, dev, _stream_ptr(torch, dev), *tail))
+    else:
+        B.check(table_call(table, ctypes.byref(params), L, _stream_ptr(torch, dev), *tail))
+    return pmax, pmin
+
+
+def hold_fft_iq(params, x, n_fft, hop, scale=1.0, *, win_length=None, center=False, pad_mode="reflect", detrend=False, shift=None,
+                fftshift=False, traces="both", out_max=None, out_min=None, workspace=None):
+    """The max-hold and min-hold traces of the rows of spectrogram_iq() WITHOUT the powers ever reaching memory
+    (bhw_hold_cfft_f32_device): x (T,) or (B, T), complex64, framed, windowed and transformed exactly as spectrogram_iq(params, x,
+    n_fft, hop, win_length=..., center=..., pad_mode=..., detrend=..., fftshift=...) does -- the float32 power of every bin is the
+    same word -- and reduced over the frames in the same kernel.  Returns (pmax, pmin), each float32 (n_fft,) or (B, n_fft):
+    pmax = (S.amax(-2).double() * scale).float() and pmin the same with amin, S that spectrogram, BIT FOR BIT at every number of
+    frames (a maximum has no order of summation), a NaN in any frame of a bin making both traces of it NaN as amax / amin do.  So
+    the traces do not depend on B or the plan.  traces: "both" | "max" | "min"; the trace not asked for is None and is not
+    written.  n_fft: a power of two in 16..2048; the arguments, their checks and ValueErrors are welch_fft_iq()'s.  `out_max`,
+    `out_min`: float32 of the returned shape, bins contiguous, rows apart by the same stride (gaps are left alone); `workspace`:
+    float64, B.hold_cfft_workspace_bytes(...) // 8 elements (allocated when not given).  With the outputs and the workspace given
+    the call neither allocates nor synchronises and can be captured with no warm call.  The mean of the same frames is
+    welch_fft_iq(); a median is not built."""
+    torch = _torch()
+    dev = x.device.index if isinstance(x, torch.Tensor) and x.is_cuda else None
+    return _welch_cfft_psd(torch, params, x, n_fft, hop, scale, win_length, center, pad_mode, detrend, shift, fftshift, None, workspace,
+                           dev, None, "cfft", (traces, out_max, out_min))
+
+
+def hold_fft_iq_mixed(params, x, n_fft, hop, scale=1.0, *, win_length=None, center=False, pad_mode="reflect", detrend=False, shift=None,
+                      fftshift=False, traces="both", out_max=None, out_min=None, workspace=None):
+    """hold_fft_iq() at the n_fft of stft_iq_mixed() (bhw_hold_cmfft_f32_device): 2^a·3^b·5^c in 16..2047 that is no power of two,
+    odd lengths included.  The traces are those of spectrogram_iq_mixed()'s rows, bit for bit; with fftshift=True an odd n_fft follows
+    torch.fft.fftshift.  The arguments, their checks and ValueErrors are welch_fft_iq_mixed()'s: a power-of-two n_fft raises
+    (hold_fft_iq transforms it), real x too.  `workspace`: B.hold_cmfft_workspace_bytes(...) // 8 float64 elements."""
+    torch = _torch()
+    dev = x.device.index if isinstance(x, torch.Tensor) and x.is_cuda else None
+    return _welch_cfft_psd(torch, params, x, n_fft, hop, scale, win_length, center, pad_mode, detrend, shift, fftshift, None, workspace,
+                           dev, None, "cmfft", (traces, out_max, out_min))
+
+
+def hold_fused_iq(params, x, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", scaling="density", shift=None,
+                  fftshift=False, traces="both", out_max=None, out_min=None, workspace=None):
+    """The max-hold and min-hold traces beside welch_fused_iq()'s mean (bhw_hold_cfft_f32_device): scipy.signal.welch's segments of
+    a complex64 x, their complex FFT, and the largest and the smallest periodogram value of every bin over the segments, in ONE
+    kernel and a small join.  The arguments, their checks, the window sums cache and the SHARED read-only `freqs` are
+    welch_fused_iq()'s (the same tensors under the same keys); the scale is that of ONE segment's periodogram, so the traces are in
+    the units of welch_fused_iq()'s Pxx and bracket it.  Returns (freqs, pmax, pmin); traces, out_max, out_min and workspace as
+    hold_fft_iq(), whose traces at that scale these are bit for bit.  After one warm call it can be captured
+    (ResidentTable.hold_fused_iq); a first call inside a capture raises, as welch_fused_iq does."""
+    torch = _torch()
+    dev = x.device.index if isinstance(x, torch.Tensor) and x.is_cuda else None
+    return _welch_fused_iq(torch, params, x, fs, length, noverlap, nfft, detrend, scaling, shift, fftshift, None, workspace, dev, None,
+                           _SUMS_CACHE, "cfft", (traces, out_max, out_min))
+
+
+def hold_fused_iq_mixed(params, x, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", scaling="density", shift=None,
+                        fftshift=False, traces="both", out_max=None, out_min=None, workspace=None):
+    """hold_fused_iq() at a mixed-radix nfft (bhw_hold_cmfft_f32_device): the checks, the caches and `freqs` are
+    welch_fused_iq_mixed()'s."""
+    torch = _torch()
+    dev = x.device.index if isinstance(x, torch.Tensor) and x.is_cuda else None
+    return _welch_fused_iq(torch, params, x, fs, length, noverlap, nfft, detrend, scaling, shift, fftshift, None, workspace, dev, None,
+                           _SUMS_CACHE, "cmfft", (traces, out_max, out_min))
 
 
 # ---- Welch cross spectra: the pass behind the FFT for two signals -------------------------------------------------------------------------
@@ -2384,6 +2497,34 @@ class ResidentTable:
         can be captured into a graph, a first call inside a capture raises."""
         return _welch_fused_iq(_torch(), params, x, fs, length, noverlap, nfft, detrend, scaling, shift, fftshift, out, workspace,
                                self.device, self._live(), self._sums, "cmfft")
+
+    def hold_fft_iq(self, params, x, n_fft, hop, scale=1.0, *, win_length=None, center=False, pad_mode="reflect", detrend=False,
+                    shift=None, fftshift=False, traces="both", out_max=None, out_min=None, workspace=None):
+        """hold_fft_iq() with the coefficients gathered from this table (bhw_hold_cfft_f32_from_table): no allocation by the library,
+        no synchronisation, capturable on its first call; the bits are those of the library form."""
+        return _welch_cfft_psd(_torch(), params, x, n_fft, hop, scale, win_length, center, pad_mode, detrend, shift, fftshift, None,
+                               workspace, self.device, self._live(), "cfft", (traces, out_max, out_min))
+
+    def hold_fused_iq(self, params, x, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", scaling="density", shift=None,
+                      fftshift=False, traces="both", out_max=None, out_min=None, workspace=None):
+        """hold_fused_iq() from this table.  The sums cache and the capture rule are welch()'s: after one warm call the call can be
+        captured into a graph, a first call inside a capture raises."""
+        return _welch_fused_iq(_torch(), params, x, fs, length, noverlap, nfft, detrend, scaling, shift, fftshift, None, workspace,
+                               self.device, self._live(), self._sums, "cfft", (traces, out_max, out_min))
+
+    def hold_fft_iq_mixed(self, params, x, n_fft, hop, scale=1.0, *, win_length=None, center=False, pad_mode="reflect", detrend=False,
+                          shift=None, fftshift=False, traces="both", out_max=None, out_min=None, workspace=None):
+        """hold_fft_iq_mixed() with the coefficients gathered from this table (bhw_hold_cmfft_f32_from_table): no allocation by the
+        library, no synchronisation, capturable on its first call; the bits are those of the library form."""
+        return _welch_cfft_psd(_torch(), params, x, n_fft, hop, scale, win_length, center, pad_mode, detrend, shift, fftshift, None,
+                               workspace, self.device, self._live(), "cmfft", (traces, out_max, out_min))
+
+    def hold_fused_iq_mixed(self, params, x, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", scaling="density",
+                            shift=None, fftshift=False, traces="both", out_max=None, out_min=None, workspace=None):
+        """hold_fused_iq_mixed() from this table.  The sums cache and the capture rule are welch()'s: after one warm call the call
+        can be captured into a graph, a first call inside a capture raises."""
+        return _welch_fused_iq(_torch(), params, x, fs, length, noverlap, nfft, detrend, scaling, shift, fftshift, None, workspace,
+                               self.device, self._live(), self._sums, "cmfft", (traces, out_max, out_min))
 
     def cross_spectra(self, params, x, y, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", return_onesided=True,
                       scaling="density", shift=None, outputs=("pxy", "pxx", "pyy", "coherence", "h1"), fft="torch"):

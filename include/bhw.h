@@ -1111,7 +1111,7 @@ int bhw_describe_istft_cmfft(bhw_table t, const bhw_params *p, uint64_t length, 
  *     call.
  *   - Not built: max-hold or median averaging; a filter bank on the averaged powers.  (I/Q input and the mixed-radix n_fft have this
  *     epilogue, bhw_welch_cfft_f32_* and bhw_welch_mfft_f32_* below; cross spectra have it for two signals side by side,
- *     bhw_csd_fft_f32_* below.)
+ *     bhw_csd_fft_f32_* below.  Max-hold and min-hold traces exist for I/Q input: bhw_hold_cfft_f32_* and bhw_hold_cmfft_f32_* below.)
  *   - bhw_describe_welch_fft: bhw_describe_stft_fft's line in the same words, plus the chunk, the runs, the groups per run, the
  *     accumulators per lane and the workspace bytes.  t may be NULL (the library call).  Host arithmetic only. */
 /* Why 16: the frames of ONE signal are the only parallelism a long record has.  16 381 frames of one signal (2^24 samples, n_fft 4096,
@@ -1163,6 +1163,7 @@ int bhw_describe_welch_fft(bhw_table t, const bhw_params *p, uint64_t length, co
  *     call.
  *   - Not built: max-hold or median traces; n_fft 4096; I/Q cross spectra accumulated in the kernel (real input:
  *     bhw_csd_fft_f32_*); a filter bank on the averaged powers.  (I/Q input at the mixed-radix lengths: bhw_welch_cmfft_f32_* below.)
+ *     (Max-hold and min-hold traces of the same rows: bhw_hold_cfft_f32_* below; a median is not built.)
  *   - bhw_describe_welch_cfft: bhw_describe_stft_cfft's line in the same words (without the output form), plus the fields
  *     bhw_describe_welch_fft adds.  t may be NULL (the library call).  Host arithmetic only. */
 uint64_t bhw_welch_cfft_workspace_bytes(const bhw_stft *s);
@@ -1209,7 +1210,8 @@ int bhw_describe_welch_cfft(bhw_table t, const bhw_params *p, uint64_t length, c
  *   - Capture: as bhw_stft_mfft_f32_*.  The library form needs no bhw_prepare_device; the from-table form is capturable on its first
  *     call.
  *   - Not built: odd n_fft and factors >= 7; cross spectra at these lengths in one kernel; max-hold or median traces.  (I/Q input
- *     at these lengths, odd ones included: bhw_welch_cmfft_f32_* below.)
+ *     at these lengths, odd ones included: bhw_welch_cmfft_f32_* below.  Max-hold and min-hold traces exist for I/Q input only:
+ *     bhw_hold_cmfft_f32_* below.)
  *   - bhw_describe_welch_mfft: bhw_describe_stft_mfft's line in the same words (without the output form), plus the fields
  *     bhw_describe_welch_fft adds.  t may be NULL (the library call).  Host arithmetic only. */
 uint64_t bhw_welch_mfft_workspace_bytes(const bhw_stft *s);
@@ -1265,6 +1267,7 @@ int bhw_describe_welch_mfft(bhw_table t, const bhw_params *p, uint64_t length, c
  *   - Capture: as bhw_stft_cmfft_f32_*.  The library form needs no bhw_prepare_device; the from-table form is capturable on its
  *     first call.
  *   - Not built: n_fft >= 2048; factors of 7 and above; I/Q cross spectra accumulated in the kernel; max-hold or median traces.
+ *     (Max-hold and min-hold traces of the same rows: bhw_hold_cmfft_f32_* below; a median is not built.)
  *   - bhw_describe_welch_cmfft: bhw_describe_stft_cmfft's line in the same words ("welch cmfft ...", without the output form), plus
  *     the fields bhw_describe_welch_fft adds.  t may be NULL (the library call).  Host arithmetic only. */
 uint64_t bhw_welch_cmfft_workspace_bytes(const bhw_stft *s);
@@ -1273,6 +1276,83 @@ int bhw_welch_cmfft_f32_device(const bhw_params *p, uint64_t length, int device,
 int bhw_welch_cmfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
                                    double scale, const float *d_x, float *d_P, uint64_t p_stride, void *workspace, uint64_t workspace_bytes);
 int bhw_describe_welch_cmfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf, uint64_t len);
+
+/* Fused max-hold and min-hold traces for complex (I/Q) input: window, complex FFT and the maximum and the minimum of |Y|^2 over the
+ * frames by ONE kernel and a small join -- the two traces a spectrum analyser keeps beside the average, for occupancy, intermittent
+ * emitters and the noise floor.  The rows of bhw_stft_cfft_f32_* are formed and transformed by the same kernel body, and the powers
+ * are reduced over the frames where the transform ends, so the (B, F, n_fft) powers that bhw_stft_cfft_f32_* with BHW_CFFT_POWER
+ * writes for an amax / amin to read back never exist.
+ *   - Inputs: (p, length, s, flags) exactly as bhw_welch_cfft_f32_* takes them: channels 2, any combination of
+ *     BHW_WELCH_DETREND_CONSTANT and BHW_CFFT_SHIFT -- BHW_CFFT_POWER is refused -- s->y_stride and s->y_batch_stride 0, and a
+ *     finite scale.
+ *   - Outputs: d_max and d_min are float32 (B, n_fft), row b at b * p_stride floats (0 = n_fft).  Either may be NULL: that trace is
+ *     not written.  Both NULL is BHW_ERR_BADARG.  Both traces are always computed; the pointers only select what is stored, so there
+ *     is one kernel family, not one per trace.  The alignment, p_stride and overlap rules are d_P's of bhw_welch_cfft_f32_*, applied
+ *     to each output and between the two.
+ *   - Values: let h_f be the float32 word that bhw_stft_cfft_f32_* with BHW_CFFT_POWER writes for bin k of row (b, f): fl32(re^2 +
+ *     im^2), the binary64 sum of the two exact products rounded to float32, from the same row function.  Then
+ *        d_max[b * p_stride + j] = fl32((double) max_f h_f * scale)         d_min[b * p_stride + j] = fl32((double) min_f h_f * scale)
+ *     over the live frames f < F only.  Column j holds bin j, or with BHW_CFFT_SHIFT bin (j + n_fft / 2) mod n_fft, the column rule
+ *     of bhw_stft_cfft_f32_* (integer division, a compare and a subtract).
+ *   - NaN: if any h_f of a bin is a NaN, both traces of that bin are NaN (some quiet NaN), as an amax / amin over the frames gives.
+ *     h_f is never negative, so the kernels reduce the float32 WORDS as unsigned integers: they order as the values do, and a NaN's
+ *     word lies above +inf's and is carried up where a float maximum would drop it.  Infinities behave as IEEE says; an infinite
+ *     maximum times a zero scale is a NaN.  A NaN or an infinity in x reaches only the bins of its own signal.  Zeros in give +0.0
+ *     out (for a scale >= 0).
+ *   - Consequences: the bits of both traces depend on the window, n_fft, the flags, scale and the signal's samples only -- not on B,
+ *     the grid, the order of the reduction (a maximum has none), or library versus table.  At EVERY F the result equals the
+ *     reduction of bhw_stft_cfft_f32_*'s power rows bit for bit; there is no ulp clause.
+ *   - Workspace: caller-provided, 8-byte aligned, bhw_hold_cfft_workspace_bytes(s) = bhw_welch_cfft_workspace_bytes(s) bytes: a
+ *     (max, min) pair of words is the 8 bytes of a chunk sum, per chunk of BHW_WELCH_FFT_CHUNK = 16 frames and, when F > 256, per
+ *     block of BHW_WELCH_BLOCK frames.  The layout inside is not part of the contract.  Partial results are stored plainly, once
+ *     each, and joined by small kernels: there are no float atomics.  A short workspace is BHW_ERR_WORKSPACE.  No call allocates.
+ *   - Supported: exactly the set of bhw_welch_cfft_f32_* (channels 2, n_fft a power of two in 16..2048), with that call's codes and
+ *     words for every refusal on the input side: both calls run the same check function.
+ *   - Checks before any HIP call, in this order (BHW_ERR_BADARG unless noted):
+ *       1. to 4. those of bhw_welch_cfft_f32_*, in its words (frames 0 returns BHW_OK at 3. with the pointers unchecked);
+ *       5. NULL d_x; d_max and d_min both NULL; d_max, d_min or d_x not 4-byte aligned;
+ *       6. a NULL or misaligned workspace, a short one (BHW_ERR_WORKSPACE);
+ *       7. d_max or d_min overlapping d_x, d_max overlapping d_min, the workspace overlapping d_x, d_max or d_min;
+ *       8. (from a table) the key match.
+ *   - Capture: as bhw_welch_cfft_f32_*.  The library form needs no bhw_prepare_device; the from-table form is capturable on its
+ *     first call.
+ *   - Not built: median or percentile traces; the mean in the same launch (call bhw_welch_cfft_f32_* beside this one); real input;
+ *     n_fft >= 2048 for I/Q input (2048 itself is taken here, 4096 is not).
+ *   - bhw_describe_hold_cfft: bhw_describe_welch_cfft's line field for field ("hold cfft ...", its own kernels and k_hold_join),
+ *     plus the traces asked for: traces is a non-empty subset of BHW_HOLD_MAX | BHW_HOLD_MIN.  t may be NULL (the library call).
+ *     Host arithmetic only. */
+#define BHW_HOLD_MAX 1u
+#define BHW_HOLD_MIN 2u
+uint64_t bhw_hold_cfft_workspace_bytes(const bhw_stft *s);
+int bhw_hold_cfft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                             double scale, const float *d_x, float *d_max, float *d_min, uint64_t p_stride,
+                             void *workspace, uint64_t workspace_bytes);
+int bhw_hold_cfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                 double scale, const float *d_x, float *d_max, float *d_min, uint64_t p_stride,
+                                 void *workspace, uint64_t workspace_bytes);
+int bhw_describe_hold_cfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, uint32_t traces,
+                           char *buf, uint64_t len);
+
+/* The same traces at a mixed-radix n_fft (400, 1000, 1200, 1536, odd lengths included): the rows of bhw_stft_cmfft_f32_* under the
+ * same epilogue.  The argument list is bhw_hold_cfft_f32_*'s, word for word, and so is the contract, with bhw_stft_cmfft_f32_* and
+ * bhw_welch_cmfft_f32_* read for bhw_stft_cfft_f32_* and bhw_welch_cfft_f32_*:
+ *   - Inputs, and every refusal on the input side, are bhw_welch_cmfft_f32_*'s (the same check function): channels 2, the 91 n_fft =
+ *     2^a 3^b 5^c in 18..2025 that are no power of two, 18 of them odd; a power of two, real input and every other n_fft are
+ *     BHW_ERR_UNSUPPORTED in that call's words.
+ *   - Values: h_f is the float32 word bhw_stft_cmfft_f32_* writes under BHW_CFFT_POWER; the traces, the NaN rule, the consequences
+ *     (bit for bit at every F) and the checks 5. to 8. are those above.  With BHW_CFFT_SHIFT bin k goes to column (k + n_fft / 2) mod
+ *     n_fft, integer division: an odd n_fft follows torch.fft.fftshift.
+ *   - Workspace: bhw_hold_cmfft_workspace_bytes(s) = bhw_welch_cmfft_workspace_bytes(s) bytes.
+ *   - Not built: as above; factors of 7 and above. */
+uint64_t bhw_hold_cmfft_workspace_bytes(const bhw_stft *s);
+int bhw_hold_cmfft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                              double scale, const float *d_x, float *d_max, float *d_min, uint64_t p_stride,
+                              void *workspace, uint64_t workspace_bytes);
+int bhw_hold_cmfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                  double scale, const float *d_x, float *d_max, float *d_min, uint64_t p_stride,
+                                  void *workspace, uint64_t workspace_bytes);
+int bhw_describe_hold_cmfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, uint32_t traces,
+                            char *buf, uint64_t len);
 
 /* Fused Welch cross spectra: window, real FFT of TWO signals and the four averages over the frames by ONE kernel and a small join.  The
  * rows of bhw_stft_fft_f32_* of x and of y are formed and transformed side by side by the same kernel body, and the terms of

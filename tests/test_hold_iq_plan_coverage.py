@@ -1,0 +1,106 @@
+"""The case table of tests/hold_iq_cases.py reaches every plan class of the fused max-hold / min-hold traces for I/Q input, both
+families: every class has a case, every claim holds on the describe line of its case (host arithmetic, no GPU), a sweep of the planner
+over all 8 + 91 supported n_fft and over frame counts at the edges of a chunk, a run, a block and the grid emits no regime the table's
+cases do not hold, and the line is the Welch sibling's field for field, with the traces behind it."""
+import pytest
+
+from blackman_harris_win_amd import binding as B
+
+import hold_iq_cases as H
+
+CLAIMS = [(c["id"], name) for c in H.CASES for name in c["classes"]]
+CLASS_IDS = [(fam, name) for fam in H.FAMILIES for name in H.CLASSES[fam]]
+
+
+@pytest.mark.parametrize("family,name", CLASS_IDS, ids=[f"{f}: {n}" for f, n in CLASS_IDS])
+def test_every_class_has_a_case(family, name):
+    claimed = [c for c in H.CASES if c["family"] == family and name in c["classes"]]
+    assert claimed, f"no {family} case claims the class {name!r}"
+    for c in claimed:
+        line = H.line(family, c, traces=c["traces"])
+        assert H.CLASSES[family][name](c, H.parse(family, line)), f"case {c['id']} is not of the class {name!r}: {line}"
+
+
+@pytest.mark.parametrize("cid,name", CLAIMS, ids=[f"{c}: {n}" for c, n in CLAIMS])
+def test_every_claim_names_a_class_and_holds(cid, name):
+    c = H.case(cid)
+    assert name in H.CLASSES[c["family"]], f"case {cid} claims {name!r}, which is no class"
+    line = H.line(c["family"], c, traces=c["traces"])
+    assert H.CLASSES[c["family"]][name](c, H.parse(c["family"], line)), f"case {cid} is not of the class {name!r}: {line}"
+
+
+def test_the_table_is_the_siblings_and_every_selection_meets_both_regimes():
+    ids = H.case_ids()
+    assert len(set(ids)) == len(ids), ids
+    assert len(H.case_ids("cfft")) == len(H.WC.CASES) and len(H.case_ids("cmfft")) == len(H.WM.CASES)
+    assert set(H.SHIFTED) <= set(ids)
+    for fam in H.FAMILIES:
+        for t in H.TRACES:
+            fys = [H.parse(fam, H.line(fam, c))["fy"] for c in H.CASES if c["family"] == fam and c["traces"] == t]
+            assert any(fy >= H.CHUNK for fy in fys) and any(fy < H.CHUNK for fy in fys), (fam, t, fys)
+    assert H.SIZES["cfft"] == [16, 32, 64, 128, 256, 512, 1024, 2048]
+    assert len(H.SIZES["cmfft"]) == 91 and H.SIZES["cmfft"][0] == 18 and H.SIZES["cmfft"][-1] == 2025
+
+
+@pytest.mark.parametrize("family", H.FAMILIES)
+def test_the_planner_emits_no_regime_without_a_case(family):
+    """Every n_fft the checks accept, at frame counts around a chunk, a run, a block and the grid cap, every selection of traces: the
+    regime (fy, groups per run, pairs carried per lane) is one a case has, the line is the Welch sibling's in the hold call's names,
+    and the workspace is the sibling's figure."""
+    p = H.params(4)
+    welch = {"cfft": B.describe_welch_cfft, "cmfft": B.describe_welch_cmfft}[family]
+    hold = {"cfft": B.describe_hold_cfft, "cmfft": B.describe_hold_cmfft}[family]
+    ws_hold = {"cfft": B.hold_cfft_workspace_bytes, "cmfft": B.hold_cmfft_workspace_bytes}[family]
+    ws_welch = {"cfft": B.welch_cfft_workspace_bytes, "cmfft": B.welch_cmfft_workspace_bytes}[family]
+    covered = {H.regime(H.parse(family, H.line(family, c))) for c in H.CASES if c["family"] == family}
+    seen = set()
+    for n in H.SIZES[family]:
+        for F in (1, 2, 15, 16, 17, 31, 32, 33, 63, 64, 65, 255, 256, 257, 513, 4097, 16 * 2048 + 1, 64 * 2048 + 1, 140000):
+            if F * n > 1 << 33:
+                continue
+            for nb in (1, 3):
+                if nb * F * n > 1 << 34:
+                    continue
+                for i, (det, sh) in enumerate(((False, False), (True, True), (False, True))):
+                    t = H.TRACES[(i + F) % 3]
+                    s = B.make_stft(nb, (F - 1) * 3 + n, F, 3, n, channels=2, shift=31)
+                    line = hold(p, min(n, 16), s, detrend=det, fftshift=sh, traces=t)
+                    d = H.parse(family, line)
+                    assert H.regime(d) in covered, line
+                    assert d["traces"] == t and d["shifted"] == sh and d["detrend"] == det
+                    assert H.to_welch(family, line) == welch(p, min(n, 16), s, detrend=det, fftshift=sh)
+                    assert d["acc"] == (0 if d["fy"] >= H.CHUNK else -(-n // 256)) <= 8
+                    assert d["chunks"] == -(-F // H.CHUNK) and d["blocks"] == -(-F // H.BLOCK)
+                    assert d["workspace"] == ws_hold(s) == ws_welch(s) == 8 * H.WC.workspace_doubles(nb, F, n)
+                    seen.add(H.regime(d))
+    assert seen == covered                          # and no case is of a regime the planner would not emit
+
+
+@pytest.mark.parametrize("shifted", [False, True])
+@pytest.mark.parametrize("cid", H.case_ids())
+def test_the_shared_fields_are_the_welch_siblings(cid, shifted):
+    c = H.case(cid)
+    fam = c["family"]
+    for table in (None,):
+        for t in H.TRACES:
+            h = H.line(fam, c, table=table, fftshift=shifted, traces=t)
+            w = H.welch_line(fam, c, table=table, fftshift=shifted)
+            assert h.startswith(f"hold {fam} direct (") and f"k_hold_{fam}_direct<" in h and "k_hold_join" in h and "welch" not in h
+            assert H.to_welch(fam, h) == w, (h, w)
+            assert h.endswith({"both": "; traces: max, min", "max": "; traces: max", "min": "; traces: min"}[t])
+            dh, dw = H.parse(fam, h), {"cfft": H.WC, "cmfft": H.WM}[fam].parse(w)
+            for name in dw:
+                if name not in ("line", "kernels"):
+                    assert dh[name] == dw[name], (cid, name, h, w)
+
+
+def test_unsupported_sizes_have_no_plan():
+    p = H.params(4)
+    for fam, sizes in (("cfft", (8, 18, 400, 4096)), ("cmfft", (8, 14, 15, 16, 17, 21, 64, 448, 512, 2048, 2160, 4050))):
+        hold = {"cfft": B.describe_hold_cfft, "cmfft": B.describe_hold_cmfft}[fam]
+        for n in sizes:
+            with pytest.raises(B.BhwError) as e:
+                hold(p, min(n, 8), B.make_stft(1, 100000, 3, 7, n, channels=2, shift=31))
+            assert e.value.code in (-1, -2), e.value           # n_fft 8 is below the window rule of some checks; the rest are UNSUPPORTED
+            if n >= 14:
+                assert e.value.code == -2, e.value
