@@ -212,6 +212,41 @@ constexpr TailD make_tail_d()
 }
 __device__ const TailD kTailD = make_tail_d();
 
+// RANK ENTRY.  From its split rotation k0 on, a narrow group's first kRankSkip rotations are not run lane by lane.  The angle is affine
+// in the lane, z_k0(lane) = zf + (lane << z_shl), so a leaf's first J = kRankSkip decisions are its rank among the 2^J - 1 sign-change
+// thresholds of the decision tree -- the partial sums +- lut[k0] +- .. +- lut[k0 + J - 2], which depend on k0 alone and lie in order
+// (z < 0 is the left child).  Phase 1, one lane per group: the 2^J states the group can reach (the same shifts and adds as
+// rot_narrow, every decision known in advance) go to cand_s, and the first lane at or above each threshold into a 64-bit mask;
+// phase 2: rank = thresholds at or below lane 0 + v_mbcnt of the mask, one ds_read_b64 for (x, y), one for {z offset, threshold
+// just below}: z_(k0+i) == 0 for some i < J exactly when z_k0 equals that threshold.  Groups that are not narrow, split before KA or
+// after KS - J, or whose thresholds crowd two to a lane keep the rotations.  tools/sim_build.cpp walks every leaf both ways.
+constexpr int kRankSkip = 4;
+constexpr int kRankCand = (1 << kRankSkip) + 1;   // uint2 per group in cand_s: 136 bytes, so that the groups' lanes write to different banks
+// in-order position p (1 .. 2^J - 1) of the tree's inner nodes = the rank whose lower neighbour the threshold is; its value from the
+// ROM words l[0 .. J-2] of the group's rotations: the node's depth is J - 1 - ctz(p), its path the bits of p above the lowest set one
+template <typename L>
+__device__ __forceinline__ int32_t rank_threshold(uint32_t p, const L &l)
+{
+    int32_t t = 0;
+#pragma unroll
+    for (int m = 0; m + 1 < kRankSkip; ++m) {
+        const uint32_t bit = 1u << (kRankSkip - 1 - m);
+        if (p & (bit - 1u)) t += (p & bit) ? (int32_t)l[m] : -(int32_t)l[m];
+    }
+    return t;
+}
+// the 2^J leaf states below (x, y) at rotation k (per lane), depth first, each stored as it is reached; bk = the bias's share of x >> k
+template <int M, int R>
+__device__ __forceinline__ void rank_candidates(uint32_t x, uint32_t y, uint32_t k, uint32_t bk, uint2 *out)
+{
+    if constexpr (M == kRankSkip) out[R] = make_uint2(x, y);
+    else {
+        const uint32_t a = y >> k, b = (x >> k) + bk;
+        rank_candidates<M + 1, 2 * R>(x + a, y - b, k + 1u, bk >> 1, out);          // z < 0
+        rank_candidates<M + 1, 2 * R + 1>(x - a, y + b, k + 1u, bk >> 1, out);      // z >= 0
+    }
+}
+
 // One rotation on the narrow state (see above); K is an immediate, lutk a scalar.  Every lane of the wave is active on entry and
 // on exit (phase 2 runs whole groups: EXEC is all ones), so the decision is: v_cmpx (EXEC = lanes with z < 0), three updates,
 // s_not EXEC, three updates, EXEC = -1.  ZERO: zacc = min(zacc, (unsigned)z) -- zero exactly when some z_k was 0 (one VOP2
@@ -286,12 +321,15 @@ __device__ __forceinline__ void rot_narrow_block(uint32_t &x, uint32_t &y, int32
     "s_mov_b64 exec, -1\n"
 #define BHW_ROT_PLAIN(i) BHW_ROT_I(i, i, "")
 #define BHW_ROT_HI(i) BHW_ROT_I(2##i, i, "v_add_u32 %[b], %[c" #i "], %[b]\n\t")
-#define BHW_ROT_DISPATCH(P)                                                                                            \
+// (entries 5 .. 9 behind one test: a rank group enters four rotations after its split rotation, and the ladder was walked to there)
+#define BHW_ROT_DISPATCH(P, H)                                                                                         \
+                 "s_cmp_gt_i32 %[e], 4\n\ts_cbranch_scc1 " #H "f\n\t"                                                 \
                  "s_cmp_lt_i32 %[e], 1\n\ts_cbranch_scc1 " #P "0f\n\t"                                                 \
                  "s_cmp_eq_u32 %[e], 1\n\ts_cbranch_scc1 " #P "1f\n\t"                                                 \
                  "s_cmp_eq_u32 %[e], 2\n\ts_cbranch_scc1 " #P "2f\n\t"                                                 \
                  "s_cmp_eq_u32 %[e], 3\n\ts_cbranch_scc1 " #P "3f\n\t"                                                 \
-                 "s_cmp_eq_u32 %[e], 4\n\ts_cbranch_scc1 " #P "4f\n\t"                                                 \
+                 "s_branch " #P "4f\n"                                                                                  \
+                 #H ":\n\t"                                                                                            \
                  "s_cmp_eq_u32 %[e], 5\n\ts_cbranch_scc1 " #P "5f\n\t"                                                 \
                  "s_cmp_eq_u32 %[e], 6\n\ts_cbranch_scc1 " #P "6f\n\t"                                                 \
                  "s_cmp_eq_u32 %[e], 7\n\ts_cbranch_scc1 " #P "7f\n\t"                                                 \
@@ -300,13 +338,13 @@ __device__ __forceinline__ void rot_narrow_block(uint32_t &x, uint32_t &y, int32
     constexpr int S = NITER - 1 - KA;                      // B >> (KA + i) = 2^(S - i)
     static_assert(S >= 9 && S <= 30, "bias shifts");
     asm volatile("s_cmp_lg_u32 %[hi], 0\n\ts_cbranch_scc1 100f\n\t"
-                 BHW_ROT_DISPATCH()
+                 BHW_ROT_DISPATCH(, 40)
                  "s_branch 10f\n"
                  BHW_ROT_PLAIN(0) BHW_ROT_PLAIN(1) BHW_ROT_PLAIN(2) BHW_ROT_PLAIN(3) BHW_ROT_PLAIN(4) BHW_ROT_PLAIN(5) BHW_ROT_PLAIN(6) BHW_ROT_PLAIN(7)
                  BHW_ROT_PLAIN(8) BHW_ROT_PLAIN(9)
                  "10:\n\ts_branch 200f\n"
                  "100:\n\t"
-                 BHW_ROT_DISPATCH(2)
+                 BHW_ROT_DISPATCH(2, 41)
                  "s_branch 200f\n"
                  BHW_ROT_HI(0) BHW_ROT_HI(1) BHW_ROT_HI(2) BHW_ROT_HI(3) BHW_ROT_HI(4) BHW_ROT_HI(5) BHW_ROT_HI(6) BHW_ROT_HI(7) BHW_ROT_HI(8) BHW_ROT_HI(9)
                  "200:"
@@ -376,6 +414,11 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(8, 8)))
     __shared__ uint32_t lut_s[32];
     __shared__ uint8_t tail_p[2 * kTailZ];                      // z_KS + kTailZ -> decision pattern of the tail
     __shared__ __attribute__((aligned(16))) int8_t tail_d[kTailRows * 64 + 16];   // 65 rows of 64 patterns (+ padding to whole 16-byte packets)
+    // (not in the 256-thread instances of nibble + escapes: with the escape list and table their eight workgroups per CU have no
+    // 9 KiB each to spare; their groups keep the rotations)
+    constexpr bool kRank = THREADS == 1024 || FMT != 5;
+    __shared__ uint2 cand_s[kRank ? gpw * kRankCand : 1];       // rank entry: the 2^J states of each group
+    __shared__ int2 rank_tab[kRank ? 8 << kRankSkip : 1];                   // ... and per split rotation KA + row, per rank: {z offset, threshold just below}
     constexpr uint32_t kWorkMax = 8 * gpw;           // images to run as chains of their own (expected ~0.6 per group)
     __shared__ uint32_t work_n;
     __shared__ uint32_t work_u[kWorkMax];
@@ -393,6 +436,9 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(8, 8)))
 #endif
     constexpr int n_iter = NITER;
     constexpr int KS = NITER - kMirrorTail;                     // image state taken at this rotation
+    constexpr int KA = KS - 10;                                 // the ten-rotation block of phase 2 starts here
+    constexpr int kRankTop = KS - kRankSkip < kPrefixMax ? KS - kRankSkip : kPrefixMax;   // rank entry: split rotations KA .. kRankTop
+    static_assert(kRankTop - KA < 8 && kRankTop + kRankSkip <= 31, "rank_tab rows; ROM words");
     const uint32_t s = plan.z_shl;
     const uint32_t group0 = blockIdx.x * gpw;
     const uint32_t E = plan.entries;
@@ -425,6 +471,17 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(8, 8)))
                 if (z < 0) { p |= 1u << j; z += (int32_t)plan.lut[KS + j]; } else z -= (int32_t)plan.lut[KS + j];
             }
             tail_p[zi] = (uint8_t)p;
+        }
+        // rank entry: rows of the split rotations KA .. kRankTop, lane = rank
+        if (kRank && t3 < (1u << kRankSkip)) {
+#pragma unroll
+            for (int row = 0; row <= kRankTop - KA; ++row) {
+                const uint32_t l[kRankSkip] = {plan.lut[KA + row], plan.lut[KA + row + 1], plan.lut[KA + row + 2], plan.lut[KA + row + 3]};
+                int32_t off = 0;
+#pragma unroll
+                for (int m = 0; m < kRankSkip; ++m) off += (t3 >> (kRankSkip - 1 - m)) & 1u ? (int32_t)l[m] : -(int32_t)l[m];
+                rank_tab[(row << kRankSkip) + t3] = make_int2(off, t3 ? rank_threshold(t3, l) : INT32_MIN);
+            }
         }
         BHW_STAMP(9);                                                // tail tables filled
     }
@@ -498,8 +555,42 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(8, 8)))
         const bool hi = !narrow && k >= KS - 10 && y >= drift && y + drift < lim && x - kBias >= drift && x - kBias + drift < ((int64_t)1 << 32) &&
                         x + drift < lim + ((int64_t)1 << KS);
         const int64_t xp = hi ? x - kBias : x;
-        const uint32_t flags = zero0 | (narrow || hi ? 2u : 0u) | (hi ? 4u : 0u) | (g == 0u ? 8u : 0u);
-        gst[threadIdx.x] = make_int4((int32_t)xp, (int32_t)y, zf, (int32_t)((uint32_t)k | (flags << 8)));
+        uint32_t flags = zero0 | (narrow || hi ? 2u : 0u) | (hi ? 4u : 0u) | (g == 0u ? 8u : 0u);
+        // rank entry (flags bit 4; the parked words are then {mask, z, k + J | flags << 8 | thresholds at or below lane 0 << 16 | the
+        // split rotation's row of rank_tab, in bytes, << 20})
+        uint32_t w0 = (uint32_t)xp, w1 = (uint32_t)y, kw = (uint32_t)k;
+        if (kRank && (narrow || hi) && k >= KA && k <= kRankTop) {
+            uint32_t l[kRankSkip - 1] = {};                                      // the ROM words of rotations k .. k + J - 2 (k per lane)
+#pragma unroll
+            for (int kk = KA; kk <= kRankTop; ++kk)
+                if (k == kk) {
+#pragma unroll
+                    for (int m = 0; m + 1 < kRankSkip; ++m) l[m] = plan.lut[kk + m];
+                }
+            uint64_t mask = 0ull;
+            uint32_t below = 0u, above = 0u;
+            bool ok = true;
+            int32_t prev = INT32_MIN;
+            const int32_t round_up = (int32_t)((1u << s) - 1u) - zf;
+#pragma unroll
+            for (uint32_t p = 1; p < (1u << kRankSkip); ++p) {
+                const int32_t t = rank_threshold(p, l);
+                ok = ok && t > prev;                                             // in order (the ROM words nest)
+                prev = t;
+                const int32_t first = (t + round_up) >> s;                       // first lane with z_k >= t: ceil((t - zf) / 2^s)
+                if (first <= 0) ++below;
+                else if (first > 63) ++above;
+                else mask |= 1ull << (first - 1);
+            }
+            if (ok && (uint32_t)__builtin_popcountll(mask) + below + above == (1u << kRankSkip) - 1u) {   // no two thresholds at one lane
+                rank_candidates<0, 0>((uint32_t)xp, (uint32_t)y, (uint32_t)k, hi ? 1u << (NITER - 1 - k) : 0u, &cand_s[threadIdx.x * kRankCand]);
+                w0 = (uint32_t)mask;
+                w1 = (uint32_t)(mask >> 32);
+                kw = (uint32_t)(k + kRankSkip) | (below << 16) | ((uint32_t)(k - KA) << (20 + kRankSkip + 3));
+                flags |= 16u;
+            }
+        }
+        gst[threadIdx.x] = make_int4((int32_t)w0, (int32_t)w1, zf, (int32_t)(kw | (flags << 8)));
         ghi[threadIdx.x] = make_int2((int32_t)(xp >> 32), (int32_t)(y >> 32));
         BHW_STAMP(11);                                               // prefixes done
     }
@@ -594,7 +685,6 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(8, 8)))
     // the ROM words of the ten-rotation block, held in scalar registers across the groups: as kernel arguments the compiler fetched
     // twelve of them again for every group (two s_load and a wait).  Read from the LDS copy, so that they are not the values the
     // deferred chains below fetch as arguments, which would then be kept alive across the walk as well (in spilled registers).
-    constexpr int KA = KS - 10;
     static_assert(KA >= 5 && KA < kcap && KS - KA == 10, "ten-rotation block");
     uint32_t rom[10];
 #pragma unroll
@@ -608,6 +698,8 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(8, 8)))
         uint32_t u = ((group0 + wave) << 6) + lane;
         uint32_t st_off = wave * (uint32_t)sizeof(int4);
         asm volatile("" : "+v"(st_off));                            // (a vector register from the start: it is only ever an LDS address)
+        uint32_t cand_off = wave * (uint32_t)(kRankCand * sizeof(uint2));   // ... and the group's states in cand_s
+        asm volatile("" : "+v"(cand_off));
         uint32_t idx = idx_a + (group0 + wave) * idx_m;              // split layout (FMT 2): the entry's index, stepped like u
         uint32_t off1, pos1, off2, pos2;
         auto cells_of = [&]() {
@@ -637,8 +729,8 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(8, 8)))
             for (; gi < q_end; gi += kWaves) {
                 const int4 st = *reinterpret_cast<const int4 *>(reinterpret_cast<const char *>(gst) + st_off);
                 const uint32_t kf = __builtin_amdgcn_readfirstlane((uint32_t)st.w);
-                const int k0 = (int)(kf & 0xFFu);
-                const uint32_t gf = kf >> 8;
+                const int k0 = (int)(kf & 0xFFu);                            // (a rank group: the rotation it enters at, split rotation + J)
+                const uint32_t gf = (kf >> 8) & 0xFFu;
                 int32_t z = (int32_t)((uint32_t)st.z + zlane);
                 uint64_t zmask = 0ull;                                       // lanes whose z_k was exactly 0 at a rotation before KS
                 int32_t c1, s1, c2, s2;                                      // the entry and its image
@@ -649,7 +741,17 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(8, 8)))
                     // entry at the group's split rotation k0 (17 or 18 at 2^26 / 32 bits): rotations below KA = KS - 10 behind one scalar guard
                     // each (rare: a group that splits that early), the last ten as one block entered at k0 (a switch with fall-through is
                     // lowered to a flag machine that costs 10 us of the pass)
-                    if (k0 < KA) {
+                    if (kRank && (gf & 16u)) {
+                        // rank entry: the first J rotations from the group's candidate states
+                        // (the count and the row taken from the parked word's vector copy: two VOP3 instead of three scalar instructions)
+                        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)st.y, __builtin_amdgcn_mbcnt_lo((uint32_t)st.x, ((uint32_t)st.w >> 16) & 15u));
+                        const uint2 cs = *reinterpret_cast<const uint2 *>(reinterpret_cast<const char *>(cand_s) + cand_off + (rank << 3));
+                        const int2 rt = *reinterpret_cast<const int2 *>(reinterpret_cast<const char *>(rank_tab) + ((uint32_t)st.w >> 20) + (rank << 3));
+                        zacc = (uint32_t)z - (uint32_t)rt.y;                 // 0: z_k0 sits on the threshold, some z_(k0+i) was 0
+                        z -= rt.x;
+                        x = cs.x;
+                        y = cs.y;
+                    } else if (k0 < KA) {
                         // (the ROM words of rotations 1 .. 8 from the LDS copy: one group in a thousand splits that early, and as kernel
                         // arguments they occupied eight scalar registers for the whole walk)
 #define BHW_NARROW(K) if constexpr (K < KA) { if (K >= k0) rot_narrow<K, true>(x, y, z, zacc, K < 9 ? (uint32_t)__builtin_amdgcn_readfirstlane(lut_s[K]) : plan.lut[K]); }
@@ -752,6 +854,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(8, 8)))
                 }
                 u += (uint32_t)THREADS;
                 st_off += kWaves * (uint32_t)sizeof(int4);
+                cand_off += kWaves * (uint32_t)(kRankCand * sizeof(uint2));
                 idx += kWaves * idx_m;
                 if constexpr (kWholeCells) { off1 += cell_step; off2 -= cell_step; }
                 else cells_of();

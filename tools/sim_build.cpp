@@ -9,6 +9,11 @@
 //   (4) biased narrow state (round 4): a group whose x runs up to 2^NITER (1 + eps) -- the first third of a degree of the octant,
 //       where x alone does not fit the 32-bit word -- keeps x - 2^(NITER-1) in the word instead:  (x >> k) = ((x - B) >> k) + (B >> k)
 //       exactly, B = 2^(NITER-1) being a multiple of 2^k for every k < NITER, and the tail table gets a 65th row (x >> KS = 64).
+//   (5) rank entry: from its split rotation k0 the angle of a group's leaves is affine in the lane, z_k0(lane) = zf + (lane << z_shl),
+//       so the first J = 4 decisions of a leaf are its rank among the 2^J - 1 sign-change thresholds of the decision tree (partial
+//       sums +- lut[k0] +- lut[k0+1] +- lut[k0+2], in order).  The 2^J states a group can reach are computed once per group, the
+//       rank is a population count over a 64-bit mask of the lanes at which a threshold is crossed, and a zero event z_(k0+i) == 0
+//       is z_k0 == the threshold just below the rank.  Each leaf is also walked through the J rotations one by one and compared.
 // Every entry of the first-quadrant table is compared with the plain chain (the rotation loop of
 // hls/windows/win_function.cpp:110-125 | cpp/cordic_sincos.cpp:49-63 | src/cordic_dds.vhd:197-213).
 // Test infrastructure / design evidence only: nothing here is linked into the product.
@@ -109,6 +114,8 @@ int main(int argc, char **argv)
     const int64_t BX = (int64_t)1 << (N - 1);                                // bias of the biased narrow state
     uint64_t n_groups = E >> 7, wide_groups = 0, unsafe_waves = 0, unsafe_lanes = 0, zero_lanes = 0, zero_prefix = 0;
     const int64_t LIM = (int64_t)1 << N;
+    constexpr int J = 4;                                                     // rotations a rank group skips
+    uint64_t rank_groups = 0, rank_refused = 0, rank_bad = 0, zero_thr = 0, zero_rot = 0;
     // deferred images per workgroup of the kernel, for both of its shapes (64 and 256 own groups): what its worklist (kWorkMax = 8 x
     // groups per workgroup) has to hold
     std::vector<uint32_t> def64((n_groups + 63) / 64, 0u), def256((n_groups + 255) / 256, 0u);
@@ -144,11 +151,67 @@ int main(int argc, char **argv)
         wide_groups += !narrow;
         if (!narrow && getenv("SIM_VERBOSE")) fprintf(stderr, "wide g=%llu k0=%d X=%lld Y=%lld Dr=%lld\n", (unsigned long long)g, k0, (long long)X, (long long)Y, (long long)Dr);
         bool wave_unsafe = false;
+        // rank entry (per group, as one lane of the kernel's phase 1 has it): thresholds in order, the lane at which each is crossed,
+        // the 2^J candidate states
+        bool ranked = narrow && k0 >= KA && k0 + J <= KS;
+        int32_t Tb[1 << J], Cr[1 << J];                                      // threshold just below rank r; z offset of rank r
+        uint32_t cx[1 << J], cy[1 << J];
+        uint64_t M = 0;
+        int base = 0;
+        if (ranked) {
+            int32_t prev = INT32_MIN;
+            int n_hi = 0;
+            Tb[0] = INT32_MIN;
+            for (int p = 1; p < (1 << J); ++p) {                             // in-order position p: depth J - 1 - ctz(p), path p >> (ctz(p) + 1)
+                const int tz = __builtin_ctz(p), depth = J - 1 - tz, path = p >> (tz + 1);
+                int64_t T = 0;
+                for (int m = 0; m < depth; ++m) T += ((path >> (depth - 1 - m)) & 1) ? c.lut[k0 + m] : -c.lut[k0 + m];
+                if (T <= prev) ranked = false;                               // not in order: the ROM words do not nest
+                prev = (int32_t)T;
+                Tb[p] = (int32_t)T;
+                const int64_t num = T - zf + (((int64_t)1 << s) - 1);        // l = ceil((T - zf) / 2^s): first lane with z >= T
+                if (num != (int32_t)num) { fprintf(stderr, "threshold difference leaves 32 bits\n"); return 1; }
+                const int32_t l = (int32_t)num >> s;
+                if (l <= 0) ++base;
+                else if (l <= 63) M |= 1ull << (l - 1);
+                else ++n_hi;
+            }
+            if (__builtin_popcountll(M) + base + n_hi != (1 << J) - 1) ranked = false;   // two thresholds between the same two lanes
+            for (int r = 0; r < (1 << J); ++r) {
+                int64_t C = 0;
+                for (int m = 0; m < J; ++m) C += ((r >> (J - 1 - m)) & 1) ? c.lut[k0 + m] : -c.lut[k0 + m];
+                Cr[r] = (int32_t)C;
+            }
+            cx[0] = (uint32_t)(X - bias); cy[0] = (uint32_t)Y;
+            for (int m = 0; m < J; ++m)                                      // level m: 2^m states -> 2^(m+1), child 2r + 1 = forward (z >= 0)
+                for (int r = (1 << m) - 1; r >= 0; --r) {
+                    const uint32_t a = cy[r] >> (k0 + m), b = (cx[r] >> (k0 + m)) + (uint32_t)(bias >> (k0 + m));
+                    const uint32_t xr = cx[r], yr = cy[r];
+                    cx[2 * r] = xr + a; cy[2 * r] = yr - b;
+                    cx[2 * r + 1] = xr - a; cy[2 * r + 1] = yr + b;
+                }
+            rank_refused += !ranked;
+            rank_groups += ranked;
+        }
         struct Lane { int64_t x, y, z; bool zero; } L[64];
         for (int lane = 0; lane < 64; ++lane) {
             int64_t x = X, y = Y, z = zf + ((int64_t)lane << s);
             bool zero = false;
-            for (int k = k0; k < KS; ++k) {
+            int kfrom = k0;
+            if (ranked) {
+                // the J rotations one by one (what the rank entry replaces) ...
+                int64_t xr = X, yr = Y, zr = z;
+                bool zrot = false;
+                for (int k = k0; k < k0 + J; ++k) { zrot |= zr == 0; step(xr, yr, zr, k, c.lut[k]); }
+                // ... and the rank entry
+                const int rank = base + __builtin_popcountll(M & ((1ull << lane) - 1ull));
+                zero = (int32_t)z == Tb[rank];
+                x = (int64_t)cx[rank] + bias; y = cy[rank]; z = z - Cr[rank];
+                zero_thr += zero; zero_rot += zrot;
+                if (x != xr || y != yr || z != zr || zero != zrot) { if (rank_bad < 5) fprintf(stderr, "rank entry differs g=%llu lane=%d rank=%d\n", (unsigned long long)g, lane, rank); ++rank_bad; }
+                kfrom = k0 + J;
+            }
+            for (int k = kfrom; k < KS; ++k) {
                 zero |= z == 0;
                 if (narrow) {
                     if (x - bias < 0 || y < 0 || x - bias >= ((int64_t)1 << 32) || y >= LIM) { fprintf(stderr, "narrow range violated g=%llu lane=%d k=%d\n", (unsigned long long)g, lane, k); return 1; }
@@ -242,5 +305,9 @@ int main(int argc, char **argv)
            (unsigned long long)wide_groups, 100.0 * wide_groups / n_groups, (unsigned long long)unsafe_waves, (unsigned long long)unsafe_lanes,
            (unsigned long long)zero_lanes, (unsigned long long)zero_prefix, (unsigned long long)hi_groups, (unsigned long long)bad, def64_max, def256_max,
            dlog, (unsigned long long)nib_out, (unsigned long long)esc_all, esc_wg_max, wg_groups);
-    return bad ? 1 : 0;
+    // (a line of its own: the sweep's parsers read the line above as it always was)
+    printf("rank entry J %d: groups %llu of %llu, refused %llu, leaves that differ from the rotations %llu, zero events by threshold %llu | by rotation %llu\n", J,
+           (unsigned long long)rank_groups, (unsigned long long)n_groups, (unsigned long long)rank_refused, (unsigned long long)rank_bad,
+           (unsigned long long)zero_thr, (unsigned long long)zero_rot);
+    return bad || rank_bad || zero_thr != zero_rot ? 1 : 0;
 }
