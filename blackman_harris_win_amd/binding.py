@@ -60,6 +60,8 @@ ABI_SYMBOLS = (
     "bhw_welch_cmfft_workspace_bytes", "bhw_welch_cmfft_f32_device", "bhw_welch_cmfft_f32_from_table", "bhw_describe_welch_cmfft",
     "bhw_hold_cfft_workspace_bytes", "bhw_hold_cfft_f32_device", "bhw_hold_cfft_f32_from_table", "bhw_describe_hold_cfft",
     "bhw_hold_cmfft_workspace_bytes", "bhw_hold_cmfft_f32_device", "bhw_hold_cmfft_f32_from_table", "bhw_describe_hold_cmfft",
+    "bhw_hold_fft_workspace_bytes", "bhw_hold_fft_f32_device", "bhw_hold_fft_f32_from_table", "bhw_describe_hold_fft",
+    "bhw_hold_mfft_workspace_bytes", "bhw_hold_mfft_f32_device", "bhw_hold_mfft_f32_from_table", "bhw_describe_hold_mfft",
 )
 
 
@@ -378,6 +380,12 @@ def lib():
         getattr(L, f"bhw_hold_{fam}_workspace_bytes").argtypes = [S]
         getattr(L, f"bhw_hold_{fam}_f32_device").argtypes = [P, u64, ci, vp, S, u32, f64, f32p, f32p, f32p, u64, vp, u64]
         getattr(L, f"bhw_hold_{fam}_f32_from_table").argtypes = [T, P, u64, vp, S, u32, f64, f32p, f32p, f32p, u64, vp, u64]
+        getattr(L, f"bhw_describe_hold_{fam}").argtypes = [T, P, u64, S, u32, u32, ctypes.c_char_p, u64]
+    for fam in ("fft", "mfft"):                                  # real input: the Welch siblings' lists with two outputs for d_P
+        getattr(L, f"bhw_hold_{fam}_workspace_bytes").restype = u64
+        getattr(L, f"bhw_hold_{fam}_workspace_bytes").argtypes = [S]
+        getattr(L, f"bhw_hold_{fam}_f32_device").argtypes = [P, u64, ci, vp, S, u32, f64, u32, f32p, f32p, f32p, u64, vp, u64]
+        getattr(L, f"bhw_hold_{fam}_f32_from_table").argtypes = [T, P, u64, vp, S, u32, f64, u32, f32p, f32p, f32p, u64, vp, u64]
         getattr(L, f"bhw_describe_hold_{fam}").argtypes = [T, P, u64, S, u32, u32, ctypes.c_char_p, u64]
     PA = ctypes.POINTER(BhwAtan2Params)
     L.bhw_atan2_device.argtypes = [PA, ci, vp, u64, i32p, i32p, i32p]
@@ -776,6 +784,40 @@ def describe_hold_cmfft(params, length, stft, *, detrend=False, fftshift=False, 
     flags = (WELCH_DETREND_CONSTANT if detrend else 0) | (CFFT_SHIFT if fftshift else 0)
     check(lib().bhw_describe_hold_cmfft(table, ctypes.byref(params), int(length), ctypes.byref(stft), flags, hold_traces(traces), buf,
                                         len(buf)))
+    return buf.value.decode()
+
+
+def hold_fft_workspace_bytes(stft):
+    """The bytes of workspace a fused max-hold / min-hold call for real input of the descriptor `stft` (a BhwStft with channels 1,
+    y strides 0) needs: welch_fft_workspace_bytes(stft) -- a (max, min) pair of float32 words per chunk and block takes the 8 bytes
+    of a chunk sum (bhw_hold_fft_workspace_bytes)."""
+    return int(lib().bhw_hold_fft_workspace_bytes(ctypes.byref(stft)))
+
+
+def describe_hold_fft(params, length, stft, *, detrend=False, traces="both", table=None):
+    """One line: the fields of describe_welch_fft in the same words ("hold fft ...", with the hold kernels and their join), plus the
+    traces that are stored ("both" | "max" | "min"), for a fused max-hold / min-hold call for real input over the window of `length`
+    with the descriptor `stft` (bhw_describe_hold_fft).  `table` is a resident table handle or None for the library call.  Host
+    arithmetic only."""
+    buf = ctypes.create_string_buffer(1280)
+    flags = WELCH_DETREND_CONSTANT if detrend else 0
+    check(lib().bhw_describe_hold_fft(table, ctypes.byref(params), int(length), ctypes.byref(stft), flags, hold_traces(traces), buf,
+                                      len(buf)))
+    return buf.value.decode()
+
+
+def hold_mfft_workspace_bytes(stft):
+    """hold_fft_workspace_bytes() at a mixed-radix n_fft: welch_mfft_workspace_bytes(stft) (bhw_hold_mfft_workspace_bytes)."""
+    return int(lib().bhw_hold_mfft_workspace_bytes(ctypes.byref(stft)))
+
+
+def describe_hold_mfft(params, length, stft, *, detrend=False, traces="both", table=None):
+    """describe_hold_fft() at a mixed-radix n_fft: the fields of describe_welch_mfft in the same words ("hold mfft ..."), plus the
+    traces that are stored (bhw_describe_hold_mfft)."""
+    buf = ctypes.create_string_buffer(1280)
+    flags = WELCH_DETREND_CONSTANT if detrend else 0
+    check(lib().bhw_describe_hold_mfft(table, ctypes.byref(params), int(length), ctypes.byref(stft), flags, hold_traces(traces), buf,
+                                       len(buf)))
     return buf.value.decode()
 
 

@@ -1291,6 +1291,41 @@ int welch_mfft_run(bhw_table t, const bhw_params *p, uint64_t length, int device
     });
 }
 
+// The fused max-hold / min-hold traces for real input (t NULL: the direct CORDIC chains): the checks, then the reducing kernel and the
+// join.  A NULL output is a trace that is not stored.
+int hold_fft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *s, uint32_t flags,
+                 double scale, uint32_t psd_flags, const float *d_x, float *d_max, float *d_min, uint64_t p_stride, void *workspace,
+                 uint64_t workspace_bytes)
+{
+    int rc = bhwp_hold_fft_checks(p, length, s, flags, scale, psd_flags, p_stride, d_x, d_max, d_min, workspace, workspace_bytes);
+    if (!rc && t) rc = table_call_checks(t, p);
+    if (rc || !s->frames) return rc;
+    const uint32_t traces = (d_max ? BHW_HOLD_MAX : 0u) | (d_min ? BHW_HOLD_MIN : 0u);
+    const BhwHoldFftPlan pl = bhwp_hold_fft_plan(p, length, s, flags, p_stride, traces, t != nullptr);
+    const char *what = t ? "hold fft launch (resident table)" : "hold fft launch";
+    return run_source(t, p, length, device, stream, what, [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *tab,
+                                                              const BhwLenPhase *lp) {
+        return bhwk_hold_fft_f32(l, c, w, pl, s, scale, psd_flags, d_x, d_max, d_min, workspace, tab, *lp);
+    });
+}
+
+// The same at a mixed-radix n_fft.
+int hold_mfft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *s, uint32_t flags,
+                  double scale, uint32_t psd_flags, const float *d_x, float *d_max, float *d_min, uint64_t p_stride, void *workspace,
+                  uint64_t workspace_bytes)
+{
+    int rc = bhwp_hold_mfft_checks(p, length, s, flags, scale, psd_flags, p_stride, d_x, d_max, d_min, workspace, workspace_bytes);
+    if (!rc && t) rc = table_call_checks(t, p);
+    if (rc || !s->frames) return rc;
+    const uint32_t traces = (d_max ? BHW_HOLD_MAX : 0u) | (d_min ? BHW_HOLD_MIN : 0u);
+    const BhwHoldMfftPlan pl = bhwp_hold_mfft_plan(p, length, s, flags, p_stride, traces, t != nullptr);
+    const char *what = t ? "hold mfft launch (resident table)" : "hold mfft launch";
+    return run_source(t, p, length, device, stream, what, [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *tab,
+                                                              const BhwLenPhase *lp) {
+        return bhwk_hold_mfft_f32(l, c, w, pl, s, scale, psd_flags, d_x, d_max, d_min, workspace, tab, *lp);
+    });
+}
+
 // The mixed-radix fused window + FFT in its three output forms (t NULL: the direct CORDIC chains): the checks, then the one kernel.
 int stft_mfft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *s, uint32_t flags,
                   const bhw_fbank *fb, const float *d_x, float *d_out)
@@ -1798,6 +1833,70 @@ int bhw_describe_welch_mfft(bhw_table t, const bhw_params *p, uint64_t length, c
     int rc = bhwp_welch_mfft_checks(p, length, s, flags, 0.0, 0, 0, nullptr, nullptr, nullptr, 0, false);
     if (!rc && t) rc = table_call_checks(t, p);
     return rc ? rc : bhwp_describe_welch_mfft(p, t ? &t->c : nullptr, length, s, flags, buf, len);
+}
+
+// ---- fused max-hold / min-hold traces for real input (include/bhw.h: bhw_hold_fft_f32_device ..., bhw_hold_mfft_f32_device ...) ------------
+
+uint64_t bhw_hold_fft_workspace_bytes(const bhw_stft *s)
+{
+    return s && s->struct_size == sizeof(bhw_stft) ? bhwp_hold_fft_workspace_bytes(s) : 0;
+}
+
+int bhw_hold_fft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags, double scale,
+                            uint32_t psd_flags, const float *d_x, float *d_max, float *d_min, uint64_t p_stride, void *workspace, uint64_t workspace_bytes)
+{
+    return hold_fft_run(nullptr, p, length, device, hip_stream, s, flags, scale, psd_flags, d_x, d_max, d_min, p_stride, workspace,
+                        workspace_bytes);
+}
+
+int bhw_hold_fft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags, double scale,
+                                uint32_t psd_flags, const float *d_x, float *d_max, float *d_min, uint64_t p_stride, void *workspace, uint64_t workspace_bytes)
+{
+    const int rc = bhwp_hold_fft_checks(p, length, s, flags, scale, psd_flags, p_stride, d_x, d_max, d_min, workspace, workspace_bytes);
+    if (rc) return rc;
+    return t ? hold_fft_run(t, p, length, t->device, hip_stream, s, flags, scale, psd_flags, d_x, d_max, d_min, p_stride, workspace,
+                            workspace_bytes)
+             : fail(BHW_ERR_BADARG, "table is NULL");
+}
+
+int bhw_describe_hold_fft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, uint32_t traces, char *buf,
+                          uint64_t len)
+{
+    int rc = bhwp_hold_fft_checks(p, length, s, flags, 0.0, 0, 0, nullptr, nullptr, nullptr, nullptr, 0, false);
+    if (!rc) rc = bhwp_hold_traces_check(traces);
+    if (!rc && t) rc = table_call_checks(t, p);
+    return rc ? rc : bhwp_describe_hold_fft(p, t ? &t->c : nullptr, length, s, flags, traces, buf, len);
+}
+
+uint64_t bhw_hold_mfft_workspace_bytes(const bhw_stft *s)
+{
+    return s && s->struct_size == sizeof(bhw_stft) ? bhwp_hold_mfft_workspace_bytes(s) : 0;
+}
+
+int bhw_hold_mfft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags, double scale,
+                             uint32_t psd_flags, const float *d_x, float *d_max, float *d_min, uint64_t p_stride, void *workspace, uint64_t workspace_bytes)
+{
+    return hold_mfft_run(nullptr, p, length, device, hip_stream, s, flags, scale, psd_flags, d_x, d_max, d_min, p_stride, workspace,
+                         workspace_bytes);
+}
+
+int bhw_hold_mfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags, double scale,
+                                 uint32_t psd_flags, const float *d_x, float *d_max, float *d_min, uint64_t p_stride, void *workspace, uint64_t workspace_bytes)
+{
+    const int rc = bhwp_hold_mfft_checks(p, length, s, flags, scale, psd_flags, p_stride, d_x, d_max, d_min, workspace, workspace_bytes);
+    if (rc) return rc;
+    return t ? hold_mfft_run(t, p, length, t->device, hip_stream, s, flags, scale, psd_flags, d_x, d_max, d_min, p_stride, workspace,
+                             workspace_bytes)
+             : fail(BHW_ERR_BADARG, "table is NULL");
+}
+
+int bhw_describe_hold_mfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, uint32_t traces, char *buf,
+                           uint64_t len)
+{
+    int rc = bhwp_hold_mfft_checks(p, length, s, flags, 0.0, 0, 0, nullptr, nullptr, nullptr, nullptr, 0, false);
+    if (!rc) rc = bhwp_hold_traces_check(traces);
+    if (!rc && t) rc = table_call_checks(t, p);
+    return rc ? rc : bhwp_describe_hold_mfft(p, t ? &t->c : nullptr, length, s, flags, traces, buf, len);
 }
 
 // ---- mixed-radix fused window and real FFT (include/bhw.h: bhw_stft_mfft_f32_device ...) -----------------------------------------------

@@ -57,13 +57,15 @@ struct HoldJoin {
     const uint2 *in;           // the pairs to reduce: [(b * n_in + i) * bins + j]
     uint2 *out;                // stage 1 with several blocks: [(b * n_out + o) * bins + j]
     float *pmax, *pmin;        // either may be NULL: that trace is not written
-    uint64_t batch, bins, n_in, n_out, p_stride;
+    uint64_t batch, bins, n_fft, n_in, n_out, p_stride;
     double scale;
+    uint32_t flags, pad;       // bhw_psd's flags: the one-sided doubling of the real-input calls; 0 for I/Q
 };
 
 // Sixteen pairs of one (signal, column) per trip, all loads in flight; past the last one the last is loaded again, which changes
 // neither a maximum nor a minimum.  GROUPED: output o reduces the inputs 16 o .. 16 o + 15 (the chunks of a block); else every input
-// (the blocks of a signal).  FINAL: the traces are written; a maximum that is a NaN (its word lies above +inf's) is the minimum too.
+// (the blocks of a signal).  FINAL: the traces are written, scaled by k_welch_fft_join's very factor (`scale` alone under flags 0); a
+// maximum that is a NaN (its word lies above +inf's) is the minimum too.
 template <bool GROUPED, bool FINAL>
 __global__ __launch_bounds__(256) void k_hold_join(HoldJoin a)
 {
@@ -87,8 +89,9 @@ __global__ __launch_bounds__(256) void k_hold_join(HoldJoin a)
     }
     if constexpr (FINAL) {
         if (H > 0x7F800000u) L = H;                                     // some frame's power was a NaN: both traces are
-        if (a.pmax) a.pmax[b * a.p_stride + j] = (float)((double)__uint_as_float(H) * a.scale);
-        if (a.pmin) a.pmin[b * a.p_stride + j] = (float)((double)__uint_as_float(L) * a.scale);
+        const double sk = bhw_psd_doubled(a.flags, j, a.bins, a.n_fft) ? a.scale * 2.0 : a.scale;
+        if (a.pmax) a.pmax[b * a.p_stride + j] = (float)((double)__uint_as_float(H) * sk);
+        if (a.pmin) a.pmin[b * a.p_stride + j] = (float)((double)__uint_as_float(L) * sk);
     } else {
         a.out[(b * a.n_out + o) * a.bins + j] = make_uint2(H, L);
     }
@@ -150,12 +153,15 @@ int bhwk_hold_cfft_f32(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWi
     }
     const int e = finish(hipSuccess);
     if (e) return e;
-    return bhwk_hold_join(l, d_ws, d_max, d_min, s->batch, wp.bins, wp.chunks, wp.blocks, wp.blocks_grid, wp.join_grid, wp.p_stride, scale);
+    return bhwk_hold_join(l, d_ws, d_max, d_min, s->batch, wp.bins, s->n_fft, wp.chunks, wp.blocks, wp.blocks_grid, wp.join_grid, wp.p_stride,
+                          scale, 0u);
 }
 
-// The join of the chunk pairs at d_ws (the block pairs follow them), for this unit and bhw_hold_cmfft.hip: bhw_internal.h.
-int bhwk_hold_join(const BhwLaunch &l, void *d_ws, float *d_max, float *d_min, uint64_t batch, uint64_t bins, uint64_t chunks,
-                   uint64_t blocks, uint64_t blocks_grid, uint64_t join_grid, uint64_t p_stride, double scale)
+// The join of the chunk pairs at d_ws (the block pairs follow them), for this unit, bhw_hold_cmfft.hip, bhw_hold_fft.hip and
+// bhw_hold_mfft.hip: bhw_internal.h.
+int bhwk_hold_join(const BhwLaunch &l, void *d_ws, float *d_max, float *d_min, uint64_t batch, uint64_t bins, uint64_t n_fft,
+                   uint64_t chunks, uint64_t blocks, uint64_t blocks_grid, uint64_t join_grid, uint64_t p_stride, double scale,
+                   uint32_t psd_flags)
 {
     hipStream_t st = (hipStream_t)l.stream;
     HoldJoin j{};
@@ -165,10 +171,12 @@ int bhwk_hold_join(const BhwLaunch &l, void *d_ws, float *d_max, float *d_min, u
     j.pmin = d_min;
     j.batch = batch;
     j.bins = bins;
+    j.n_fft = n_fft;
     j.n_in = chunks;
     j.n_out = blocks;
     j.p_stride = p_stride;
     j.scale = scale;
+    j.flags = psd_flags;
     const dim3 g1((unsigned)blocks_grid), g2((unsigned)join_grid);
     if (blocks == 1) {
         launch(k_hold_join<true, true>, g1, dim3(256), st, j);

@@ -110,5 +110,6 @@ int bhwk_hold_cmfft_f32(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwW
     }
     const int e = finish(hipSuccess);
     if (e) return e;
-    return bhwk_hold_join(l, d_ws, d_max, d_min, s->batch, wp.bins, wp.chunks, wp.blocks, wp.blocks_grid, wp.join_grid, wp.p_stride, scale);
+    return bhwk_hold_join(l, d_ws, d_max, d_min, s->batch, wp.bins, s->n_fft, wp.chunks, wp.blocks, wp.blocks_grid, wp.join_grid, wp.p_stride,
+                          scale, 0u);
 }

@@ -1,0 +1,120 @@
+// bhw_hold_mfft.hip -- window, mixed-radix real FFT and the max-hold / min-hold traces over the frames in one kernel, for even n_fft =
+// 2^a 3^b 5^c that is no power of two (bhw_hold_mfft_f32_device / _from_table; contract: include/bhw.h, plan: BhwHoldMfftPlan in
+// bhw_plan.h, reasons and measurements: DESIGN.md section 34).
+//
+// The row function of bhw_stft_mfft.h, unedited, under the epilogue of bhw_hold_real.h, as bhw_hold_fft.hip is the power-of-two kernel
+// under it: the power of a bin is the float32 word bhw_stft_mfft_f32_* writes for it under BHW_MFFT_POWER (mfft_power's expression),
+// and the (B, F, K) powers never exist.  The kernels below are k_welch_mfft_direct / _table of bhw_welch_mfft.hip with that epilogue
+// in place of the binary64 sums; the join is bhwk_hold_join of bhw_hold_cfft.hip with the call's psd_flags.
+#include "bhw_stft_mfft.h"
+#include "bhw_hold_real.h"
+
+namespace {
+
+using HoldMfftAccumulate = HoldRealAccumulate<kHoldMfftMaxAcc, false>;
+
+// Without a hint the allocator ends at 129 VGPRs, one above the 128 that four waves of a SIMD share, as it does for the Welch sibling;
+// asked for four waves it finds 128 with no scratch and no spill in every instance (kernel_resources.json; tests/test_abi.py's
+// standing rule holds it there).
+#define BHW_HOLD_MFFT_WAVES __attribute__((amdgpu_waves_per_eu(4, 4)))
+
+// Coefficient by the direct CORDIC chains (FORM: direct_form, as k_stft_mfft_direct).
+template <int FORM>
+__global__ __launch_bounds__(kFftBlock) BHW_HOLD_MFFT_WAVES void k_hold_mfft_direct(BhwCordicCfg cfg, BhwWinCfg win, MfftIo a, BhwLenPhase lp, HoldAcc wa)
+{
+    using T = std::conditional_t<FORM == 0, int32_t, int64_t>;
+    using L = std::conditional_t<FORM == 2, uint32_t, T>;
+    __shared__ L lut_s[32];
+    if (threadIdx.x < 32) lut_s[threadIdx.x] = (L)cfg.lut[threadIdx.x];
+    __syncthreads();
+    float *vbuf = (float *)fft_lds;
+    for (uint32_t j = threadIdx.x; j < a.n_fft; j += kFftBlock) {
+        const uint32_t k = j - a.col0;                             // unsigned: k < L is the window test
+        float v = 0.0f;
+        if (k < a.len) {
+            int32_t w;
+            if constexpr (FORM == 2) w = direct_coeff_mad_ph(cfg, win, lut_s, len_theta_of(lp, k));
+            else                     w = direct_coeff_ph<T>(cfg, win, lut_s, len_theta_of(lp, k));
+            v = fft_coeff(w, a.shift);
+        }
+        vbuf[j] = v;
+    }
+    __syncthreads();
+    stft_mfft_rows(a, HoldMfftAccumulate(wa));
+}
+
+// Coefficient gathered from a resident table in format FMT (as k_stft_mfft_table).
+template <int FMT, int NT, int MODE>
+__global__ __launch_bounds__(kFftBlock) BHW_HOLD_MFFT_WAVES void k_hold_mfft_table(BhwCordicCfg cfg, BhwWinCfg win,
+                                                                                    const void *__restrict__ table, MfftIo a, BhwLenPhase lp,
+                                                                                    HoldAcc wa)
+{
+    float *vbuf = (float *)fft_lds;
+    for (uint32_t j0 = 0; j0 < a.n_fft; j0 += kFftBlock) {
+        const uint32_t j = j0 + threadIdx.x;
+        const uint32_t k = j - a.col0;
+        const bool in = j < a.n_fft && k < a.len;
+        const int32_t w = range_coeff_ph<FMT, NT, MODE>(cfg, win, table, len_theta_of(lp, in ? k : 0u));
+        if (j < a.n_fft) vbuf[j] = in ? fft_coeff(w, a.shift) : 0.0f;
+    }
+    __syncthreads();
+    stft_mfft_rows(a, HoldMfftAccumulate(wa));
+}
+
+} // namespace
+
+int bhwk_hold_mfft_f32(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinCfg &w, const BhwHoldMfftPlan &hp, const bhw_stft *s,
+                       double scale, uint32_t psd_flags, const float *d_x, float *d_max, float *d_min, void *d_ws, const int32_t *d_table,
+                       const BhwLenPhase &lp)
+{
+    const BhwWelchMfftPlan &wp = hp.welch;
+    const BhwStftMfftPlan &pl = wp.fft;
+    if (!pl.rows) return 0;
+    hipStream_t st = (hipStream_t)l.stream;
+    MfftIo a{};
+    a.x = d_x;
+    a.Y = nullptr;
+    a.rows = pl.rows;
+    a.frames = s->frames;
+    a.hop = s->hop;
+    a.samples = s->samples;
+    a.pad = s->pad;
+    a.x_stride = pl.x_stride;
+    a.y_stride = 0;
+    a.y_bstride = 0;
+    a.groups = pl.groups;
+    a.n_fft = (uint32_t)s->n_fft;
+    a.m = pl.m;
+    a.col0 = (uint32_t)s->col0;
+    a.len = (uint32_t)pl.len;
+    a.lpf = pl.lpf;
+    a.fy = pl.fy;
+    a.cpl = pl.cpl;
+    a.passes = pl.passes;
+    for (uint32_t p = 0; p < pl.passes; ++p) a.sched |= (uint32_t)pl.radix[p] << (4u * p);
+    a.shift = s->shift;
+    a.reflect = s->pad_mode == BHW_PAD_REFLECT ? 1u : 0u;
+    a.detrend = pl.detrend ? 1u : 0u;
+    a.form = BHWP_MFFT_SPECTRUM;                                        // not read: the epilogue is HoldMfftAccumulate
+    HoldAcc wa{};
+    wa.chunk_ws = (uint2 *)d_ws;
+    wa.fpad = wp.fpad;
+    wa.chunks = wp.chunks;
+    wa.gpr = wp.gpr;
+    const dim3 grid((unsigned)pl.grid), block(kFftBlock);
+    if (!d_table) {
+        with_int_or_last<2, 1, 0>(direct_form(c_in), [&](auto D) { launch_lds(k_hold_mfft_direct<D>, grid, block, pl.lds_bytes, st, c_in, w, a, lp, wa); });
+    } else {
+        const BhwCordicCfg c = table_layout(c_in);
+        int fmt, nt, mode;
+        if (!bhwp_range_form(c, w, &fmt, &nt, &mode)) return (int)hipErrorInvalidValue;
+        const void *tab = (const void *)d_table;
+        with_range_form(fmt, nt, mode, [&](auto F, auto NT, auto M) {
+            launch_lds(k_hold_mfft_table<F, NT, M>, grid, block, pl.lds_bytes, st, c, w, tab, a, lp, wa);
+        });
+    }
+    const int e = finish(hipSuccess);
+    if (e) return e;
+    return bhwk_hold_join(l, d_ws, d_max, d_min, s->batch, wp.bins, s->n_fft, wp.chunks, wp.blocks, wp.blocks_grid, wp.join_grid, wp.p_stride,
+                          scale, psd_flags);
+}

@@ -136,5 +136,8 @@ int bhwk_welch_join_blocks(const BhwLaunch &l, double *d_ws, uint64_t batch, uin
 // The join of the fused hold calls (bhw_hold_cfft.hip; also launched by bhw_hold_cmfft.hip): the chunk pairs (the words of the
 // maximum and of the minimum, 8 bytes) [(b * chunks + c) * bins + j] at d_ws, followed (blocks > 1) by the block pairs, reduced by
 // k_hold_join in one launch (one block) or two; the traces are scaled and written to d_max and d_min, either of which may be NULL.
-int bhwk_hold_join(const BhwLaunch &l, void *d_ws, float *d_max, float *d_min, uint64_t batch, uint64_t bins, uint64_t chunks,
-                   uint64_t blocks, uint64_t blocks_grid, uint64_t join_grid, uint64_t p_stride, double scale);
+// psd_flags and n_fft: bhwk_welch_join's, for the doubling of a one-sided row (bhw_hold_fft.hip, bhw_hold_mfft.hip); the I/Q calls
+// pass psd_flags 0, under which every column is scaled by `scale` alone.
+int bhwk_hold_join(const BhwLaunch &l, void *d_ws, float *d_max, float *d_min, uint64_t batch, uint64_t bins, uint64_t n_fft,
+                   uint64_t chunks, uint64_t blocks, uint64_t blocks_grid, uint64_t join_grid, uint64_t p_stride, double scale,
+                   uint32_t psd_flags);

@@ -1844,8 +1844,11 @@ BhwWelchFftPlan bhwp_welch_fft_plan(const bhw_params *p, uint64_t length, const 
     return pl;
 }
 
-int bhwp_describe_welch_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf,
-                            uint64_t len)
+// The describe line of the calls that put stft_fft_rows under an epilogue that owns runs: bhw_describe_welch_fft (what "welch", the
+// join k_welch_fft_join, no tail) and bhw_describe_hold_fft (what "hold", its kernels, its join and the traces as the tail).
+static int describe_fft_runs(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags,
+                             const char *what, const char *k_direct, const char *k_table, const char *join, const char *tail, char *buf,
+                             uint64_t len)
 {
     if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
     const char *route = ct ? "table" : "direct";
@@ -1854,24 +1857,30 @@ int bhwp_describe_welch_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64_
     const char *pad = s->pad_mode == BHW_PAD_REFLECT ? "reflect" : "constant";
     const char *det = pl.detrend ? "constant detrend" : "no detrending";
     if (!s->frames) {
-        snprintf(buf, len, "welch fft %s (L = %llu, n_fft %llu, %s): nothing (frames 0)", route, (unsigned long long)length,
-                 (unsigned long long)s->n_fft, det);
+        snprintf(buf, len, "%s fft %s (L = %llu, n_fft %llu, %s): nothing (frames 0)%s", what, route, (unsigned long long)length,
+                 (unsigned long long)s->n_fft, det, tail);
         return BHW_OK;
     }
     char kern[64], sched[48];
-    kernel_name(p, ct, "k_welch_fft_direct", "k_welch_fft_table", false, kern, sizeof kern);
+    kernel_name(p, ct, k_direct, k_table, false, kern, sizeof kern);
     bhwp_stft_fft_schedule(pl, sched, sizeof sched);
-    snprintf(buf, len, "welch fft %s (L = %llu, n_fft %llu, col0 %llu, pad %llu %s, %s): %s, %llu signals x %llu frames = %llu rows, "
+    snprintf(buf, len, "%s fft %s (L = %llu, n_fft %llu, col0 %llu, pad %llu %s, %s): %s, %llu signals x %llu frames = %llu rows, "
              "complex FFT of %u points in passes %s + split, %u lanes per row x %u rows per workgroup, %u columns per lane, %llu groups, "
              "grid %llu x %u lanes, %u bytes of LDS; chunk %u frames, %llu runs of %llu frames (%u group%s per run), %u accumulator%s "
-             "per lane, %llu chunks and %llu block%s per signal, then k_welch_fft_join %s, workspace %llu bytes",
-             route, (unsigned long long)length, (unsigned long long)s->n_fft, (unsigned long long)s->col0, (unsigned long long)s->pad, pad,
+             "per lane, %llu chunks and %llu block%s per signal, then %s %s, workspace %llu bytes%s",
+             what, route, (unsigned long long)length, (unsigned long long)s->n_fft, (unsigned long long)s->col0, (unsigned long long)s->pad, pad,
              det, kern, (unsigned long long)s->batch, (unsigned long long)s->frames, (unsigned long long)pl.rows, pl.m, sched, pl.lpf, pl.fy,
              pl.cpl, (unsigned long long)pl.groups, (unsigned long long)pl.grid, kFftBlock, pl.lds_bytes, BHW_WELCH_FFT_CHUNK,
              (unsigned long long)wp.runs, (unsigned long long)wp.run, wp.gpr, wp.gpr == 1 ? "" : "s", wp.acc, wp.acc == 1 ? "" : "s",
-             (unsigned long long)wp.chunks, (unsigned long long)wp.blocks, wp.blocks == 1 ? "" : "s",
-             wp.blocks == 1 ? "once (chunks)" : "twice (chunks, blocks)", (unsigned long long)wp.ws_bytes);
+             (unsigned long long)wp.chunks, (unsigned long long)wp.blocks, wp.blocks == 1 ? "" : "s", join,
+             wp.blocks == 1 ? "once (chunks)" : "twice (chunks, blocks)", (unsigned long long)wp.ws_bytes, tail);
     return BHW_OK;
+}
+
+int bhwp_describe_welch_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf,
+                            uint64_t len)
+{
+    return describe_fft_runs(p, ct, length, s, flags, "welch", "k_welch_fft_direct", "k_welch_fft_table", "k_welch_fft_join", "", buf, len);
 }
 
 // ---- fused Welch cross spectra ----------------------------------------------------------------------------------------------------------------
@@ -2657,11 +2666,12 @@ int bhwp_hold_traces_check(uint32_t traces)
 
 // The pointers of both hold calls, after the Welch sibling's check function passed everything else (the descriptor, the flags, the
 // y strides, scale, p_stride and the 2^34 bound: steps 1 to 4 of include/bhw.h): steps 5 to 7.  d_P's rules hold for each output
-// and between the two.
-static int hold_pointer_checks(const bhw_stft *s, uint64_t p_stride, const void *d_x, const void *d_max, const void *d_min,
-                               const void *workspace, uint64_t workspace_bytes)
+// and between the two.  bins: the columns of a trace row (n_fft for I/Q input, K for real input); xt: the floats of one signal (2 T
+// or T); need: the sibling's workspace bytes.
+static int hold_pointer_checks(const bhw_stft *s, uint64_t p_stride, uint64_t bins, uint64_t xt, uint64_t need, const void *d_x,
+                               const void *d_max, const void *d_min, const void *workspace, uint64_t workspace_bytes)
 {
-    const uint64_t T = s->samples, N = s->n_fft;
+    const uint64_t N = bins;
     if (!s->frames) return BHW_OK;
     // 5.
     if (!d_x) return bhwp_fail(BHW_ERR_BADARG, "d_x is NULL");
@@ -2670,15 +2680,14 @@ static int hold_pointer_checks(const bhw_stft *s, uint64_t p_stride, const void 
     if ((uintptr_t)d_min % 4) return bhwp_fail(BHW_ERR_BADARG, "d_min is not 4-byte aligned");
     if ((uintptr_t)d_x % 4) return bhwp_fail(BHW_ERR_BADARG, "d_x is not 4-byte aligned");
     // 6.
-    const uint64_t need = bhwp_welch_cfft_workspace_bytes(s);
     if (!workspace) return bhwp_fail(BHW_ERR_BADARG, "workspace is NULL: the chunk pairs need %llu bytes", (unsigned long long)need);
     if ((uintptr_t)workspace % 8) return bhwp_fail(BHW_ERR_BADARG, "workspace is not 8-byte aligned");
     if (workspace_bytes < need)
         return bhwp_fail(BHW_ERR_WORKSPACE, "workspace of %llu bytes, the chunk and block pairs need %llu", (unsigned long long)workspace_bytes,
                          (unsigned long long)need);
-    // 7. (x counts floats: 2 T of a signal)
-    const uint64_t xs = s->x_stride ? s->x_stride : 2 * T, ps = p_stride ? p_stride : N;
-    const unsigned __int128 xe = (unsigned __int128)(s->batch - 1) * xs + 2 * T, pe = (unsigned __int128)(s->batch - 1) * ps + N;
+    // 7. (x counts floats: xt of a signal)
+    const uint64_t xs = s->x_stride ? s->x_stride : xt, ps = p_stride ? p_stride : N;
+    const unsigned __int128 xe = (unsigned __int128)(s->batch - 1) * xs + xt, pe = (unsigned __int128)(s->batch - 1) * ps + N;
     if (xe > (1ull << 60) || pe > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "x or trace extent beyond 2^60 elements");
     const uint64_t xa = (uint64_t)(uintptr_t)d_x, wa = (uint64_t)(uintptr_t)workspace;
     const uint64_t xb = (uint64_t)xe * 4u, pb = (uint64_t)pe * 4u;
@@ -2701,7 +2710,8 @@ int bhwp_hold_cfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *
 {
     const int rc = bhwp_welch_cfft_checks(p, length, s, flags, scale, p_stride, nullptr, nullptr, nullptr, 0, false);
     if (rc || !pointers) return rc;
-    return hold_pointer_checks(s, p_stride, d_x, d_max, d_min, workspace, workspace_bytes);
+    return hold_pointer_checks(s, p_stride, s->n_fft, 2 * s->samples, bhwp_welch_cfft_workspace_bytes(s), d_x, d_max, d_min, workspace,
+                               workspace_bytes);
 }
 
 int bhwp_hold_cmfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, double scale, uint64_t p_stride,
@@ -2710,7 +2720,8 @@ int bhwp_hold_cmfft_checks(const bhw_params *p, uint64_t length, const bhw_stft 
 {
     const int rc = bhwp_welch_cmfft_checks(p, length, s, flags, scale, p_stride, nullptr, nullptr, nullptr, 0, false);
     if (rc || !pointers) return rc;
-    return hold_pointer_checks(s, p_stride, d_x, d_max, d_min, workspace, workspace_bytes);
+    return hold_pointer_checks(s, p_stride, s->n_fft, 2 * s->samples, bhwp_welch_cmfft_workspace_bytes(s), d_x, d_max, d_min, workspace,
+                               workspace_bytes);
 }
 
 BhwHoldCfftPlan bhwp_hold_cfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, uint64_t p_stride,
@@ -2833,8 +2844,10 @@ BhwWelchMfftPlan bhwp_welch_mfft_plan(const bhw_params *p, uint64_t length, cons
     return pl;
 }
 
-int bhwp_describe_welch_mfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf,
-                             uint64_t len)
+// describe_fft_runs for stft_mfft_rows: bhw_describe_welch_mfft and bhw_describe_hold_mfft.
+static int describe_mfft_runs(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags,
+                              const char *what, const char *k_direct, const char *k_table, const char *join, const char *tail, char *buf,
+                              uint64_t len)
 {
     if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
     const char *route = ct ? "table" : "direct";
@@ -2843,24 +2856,82 @@ int bhwp_describe_welch_mfft(const bhw_params *p, const BhwCordicCfg *ct, uint64
     const char *pad = s->pad_mode == BHW_PAD_REFLECT ? "reflect" : "constant";
     const char *det = pl.detrend ? "constant detrend" : "no detrending";
     if (!s->frames) {
-        snprintf(buf, len, "welch mfft %s (L = %llu, n_fft %llu, %s): nothing (frames 0)", route, (unsigned long long)length,
-                 (unsigned long long)s->n_fft, det);
+        snprintf(buf, len, "%s mfft %s (L = %llu, n_fft %llu, %s): nothing (frames 0)%s", what, route, (unsigned long long)length,
+                 (unsigned long long)s->n_fft, det, tail);
         return BHW_OK;
     }
     char kern[64], sched[48];
-    kernel_name(p, ct, "k_welch_mfft_direct", "k_welch_mfft_table", false, kern, sizeof kern);
+    kernel_name(p, ct, k_direct, k_table, false, kern, sizeof kern);
     bhwp_stft_mfft_schedule(pl, sched, sizeof sched);
-    snprintf(buf, len, "welch mfft %s (L = %llu, n_fft %llu, col0 %llu, pad %llu %s, %s): %s, %llu signals x %llu frames = %llu rows, "
+    snprintf(buf, len, "%s mfft %s (L = %llu, n_fft %llu, col0 %llu, pad %llu %s, %s): %s, %llu signals x %llu frames = %llu rows, "
              "complex FFT of %u points in passes %s + split, %u lanes per row x %u rows per workgroup, %u columns per lane, %llu groups, "
              "grid %llu x %u lanes, %u bytes of LDS; chunk %u frames, %llu runs of %llu frames (%u group%s per run), %u accumulator%s "
-             "per lane, %llu chunks and %llu block%s per signal, then k_welch_fft_join %s, workspace %llu bytes",
-             route, (unsigned long long)length, (unsigned long long)s->n_fft, (unsigned long long)s->col0, (unsigned long long)s->pad, pad,
+             "per lane, %llu chunks and %llu block%s per signal, then %s %s, workspace %llu bytes%s",
+             what, route, (unsigned long long)length, (unsigned long long)s->n_fft, (unsigned long long)s->col0, (unsigned long long)s->pad, pad,
              det, kern, (unsigned long long)s->batch, (unsigned long long)s->frames, (unsigned long long)pl.rows, pl.m, sched, pl.lpf, pl.fy,
              pl.cpl, (unsigned long long)pl.groups, (unsigned long long)pl.grid, kFftBlock, pl.lds_bytes, BHW_WELCH_FFT_CHUNK,
              (unsigned long long)wp.runs, (unsigned long long)wp.run, wp.gpr, wp.gpr == 1 ? "" : "s", wp.acc, wp.acc == 1 ? "" : "s",
-             (unsigned long long)wp.chunks, (unsigned long long)wp.blocks, wp.blocks == 1 ? "" : "s",
-             wp.blocks == 1 ? "once (chunks)" : "twice (chunks, blocks)", (unsigned long long)wp.ws_bytes);
+             (unsigned long long)wp.chunks, (unsigned long long)wp.blocks, wp.blocks == 1 ? "" : "s", join,
+             wp.blocks == 1 ? "once (chunks)" : "twice (chunks, blocks)", (unsigned long long)wp.ws_bytes, tail);
     return BHW_OK;
+}
+
+int bhwp_describe_welch_mfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf,
+                             uint64_t len)
+{
+    return describe_mfft_runs(p, ct, length, s, flags, "welch", "k_welch_mfft_direct", "k_welch_mfft_table", "k_welch_fft_join", "", buf,
+                              len);
+}
+
+// ---- fused max-hold / min-hold traces for real input -------------------------------------------------------------------------------------------
+
+uint64_t bhwp_hold_fft_workspace_bytes(const bhw_stft *s) { return bhwp_welch_fft_workspace_bytes(s); }
+uint64_t bhwp_hold_mfft_workspace_bytes(const bhw_stft *s) { return bhwp_welch_mfft_workspace_bytes(s); }
+
+int bhwp_hold_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, double scale, uint32_t psd_flags,
+                         uint64_t p_stride, const void *d_x, const void *d_max, const void *d_min, const void *workspace,
+                         uint64_t workspace_bytes, bool pointers)
+{
+    const int rc = bhwp_welch_fft_checks(p, length, s, flags, scale, psd_flags, p_stride, nullptr, nullptr, nullptr, 0, false);
+    if (rc || !pointers) return rc;
+    return hold_pointer_checks(s, p_stride, s->n_fft / 2 + 1, s->samples, bhwp_welch_fft_workspace_bytes(s), d_x, d_max, d_min, workspace,
+                               workspace_bytes);
+}
+
+int bhwp_hold_mfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, double scale, uint32_t psd_flags,
+                          uint64_t p_stride, const void *d_x, const void *d_max, const void *d_min, const void *workspace,
+                          uint64_t workspace_bytes, bool pointers)
+{
+    const int rc = bhwp_welch_mfft_checks(p, length, s, flags, scale, psd_flags, p_stride, nullptr, nullptr, nullptr, 0, false);
+    if (rc || !pointers) return rc;
+    return hold_pointer_checks(s, p_stride, s->n_fft / 2 + 1, s->samples, bhwp_welch_mfft_workspace_bytes(s), d_x, d_max, d_min, workspace,
+                               workspace_bytes);
+}
+
+BhwHoldFftPlan bhwp_hold_fft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, uint64_t p_stride,
+                                  uint32_t traces, bool from_table)
+{
+    return BhwHoldFftPlan{bhwp_welch_fft_plan(p, length, s, flags, p_stride, from_table), traces};
+}
+
+BhwHoldMfftPlan bhwp_hold_mfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, uint64_t p_stride,
+                                    uint32_t traces, bool from_table)
+{
+    return BhwHoldMfftPlan{bhwp_welch_mfft_plan(p, length, s, flags, p_stride, from_table), traces};
+}
+
+int bhwp_describe_hold_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags,
+                           uint32_t traces, char *buf, uint64_t len)
+{
+    return describe_fft_runs(p, ct, length, s, flags, "hold", "k_hold_fft_direct", "k_hold_fft_table", "k_hold_join",
+                             hold_traces_tail(traces), buf, len);
+}
+
+int bhwp_describe_hold_mfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags,
+                            uint32_t traces, char *buf, uint64_t len)
+{
+    return describe_mfft_runs(p, ct, length, s, flags, "hold", "k_hold_mfft_direct", "k_hold_mfft_table", "k_hold_join",
+                              hold_traces_tail(traces), buf, len);
 }
 
 // ---- fused inverse real FFT, window and overlap-add -----------------------------------------------------------------------------------------

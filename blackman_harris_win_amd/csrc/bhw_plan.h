@@ -823,6 +823,49 @@ int  bhwk_welch_mfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWin
                          double scale, uint32_t psd_flags, const float *d_x, float *d_P, double *d_ws, const int32_t *d_table,
                          const BhwLenPhase &lp);
 
+// ---- fused max-hold / min-hold traces for real input (bhw_hold_fft_f32_*, bhw_hold_mfft_f32_*; bhw_hold_fft.hip, bhw_hold_mfft.hip) --------
+// As BhwHoldCfftPlan: the plan of a hold call IS the plan of its Welch sibling (bins = K = n_fft / 2 + 1) plus the traces that are
+// stored, and a (max, min) pair of float32 words is the 8 bytes of a chunk sum.  welch.acc counts the PAIRS a lane carries over a run
+// (at most kHoldFftMaxAcc, the ninth being bin M on lane 0 at n_fft 4096; kHoldMfftMaxAcc).
+constexpr uint32_t kHoldFftMaxAcc = kWelchFftMaxAcc;  // 9
+constexpr uint32_t kHoldMfftMaxAcc = kWelchMfftMaxAcc; // 8
+struct BhwHoldFftPlan {
+    BhwWelchFftPlan welch;
+    uint32_t traces;      // BHW_HOLD_MAX | BHW_HOLD_MIN: what is stored (both are always computed)
+};
+struct BhwHoldMfftPlan {
+    BhwWelchMfftPlan welch;
+    uint32_t traces;
+};
+// Every check of the calls that needs no table handle, before any HIP call and in the order of include/bhw.h: the Welch sibling's
+// check function for everything but the pointers (bhwp_welch_fft_checks / bhwp_welch_mfft_checks, `pointers` false), then the two
+// outputs and the workspace (hold_pointer_checks, the I/Q hold calls' text with K bins and T floats of a signal).  frames 0 passes
+// with the pointers unchecked; `pointers` false: the describe call.
+int  bhwp_hold_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, double scale, uint32_t psd_flags,
+                          uint64_t p_stride, const void *d_x, const void *d_max, const void *d_min, const void *workspace,
+                          uint64_t workspace_bytes, bool pointers = true);
+int  bhwp_hold_mfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, double scale, uint32_t psd_flags,
+                           uint64_t p_stride, const void *d_x, const void *d_max, const void *d_min, const void *workspace,
+                           uint64_t workspace_bytes, bool pointers = true);
+// bhw_hold_(m)fft_workspace_bytes: the Welch sibling's figure
+uint64_t bhwp_hold_fft_workspace_bytes(const bhw_stft *s);
+uint64_t bhwp_hold_mfft_workspace_bytes(const bhw_stft *s);
+BhwHoldFftPlan  bhwp_hold_fft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, uint64_t p_stride,
+                                   uint32_t traces, bool from_table);
+BhwHoldMfftPlan bhwp_hold_mfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, uint64_t p_stride,
+                                    uint32_t traces, bool from_table);
+// traces: a non-empty subset of BHW_HOLD_MAX | BHW_HOLD_MIN (checked by the caller)
+int  bhwp_describe_hold_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags,
+                            uint32_t traces, char *buf, uint64_t len);
+int  bhwp_describe_hold_mfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags,
+                             uint32_t traces, char *buf, uint64_t len);
+int  bhwk_hold_fft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwHoldFftPlan &pl, const bhw_stft *s,
+                       double scale, uint32_t psd_flags, const float *d_x, float *d_max, float *d_min, void *d_ws, const int32_t *d_table,
+                       const BhwLenPhase &lp);
+int  bhwk_hold_mfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwHoldMfftPlan &pl, const bhw_stft *s,
+                        double scale, uint32_t psd_flags, const float *d_x, float *d_max, float *d_min, void *d_ws, const int32_t *d_table,
+                        const BhwLenPhase &lp);
+
 // ---- fused inverse real FFT, window and overlap-add (bhw_istft_fft_f32_*; bhw_istft_fft.hip) ------------------------------------------
 // The lane layout of the forward kernel (lpf lanes along a row, fy slots side by side, cpl columns per lane).  The window-start axis
 // w = t + pad - col0 of every signal (frame f covers w in [f * hop, f * hop + L)) is cut into spans of S * hop positions; the spans

@@ -1357,12 +1357,20 @@ def _welch_fft_call(torch, params, L, s, flags, xb, nb, K, scale, onesided, out,
 
 
 def _welch_fft_psd(torch, params, x, n_fft, hop, scale, win_length, center, pad_mode, detrend, onesided_doubling, shift, out, workspace,
-                   dev, table, family="fft"):
+                   dev, table, family="fft", hold=None):
+    """hold: None (the mean: welch_fft*), or (traces, out_max, out_min) for hold_fft*: the same front and descriptor, and _hold_call
+    in place of _welch_fft_call."""
     check = _fft_input if family == "fft" else _welch_mfft_input
+    if hold is not None:
+        B.hold_traces(hold[0])
+        check = _hold_fft_input if family == "fft" else _hold_mfft_input
     n_fft, L, xb, nb, T, frames, d = _stft_front(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, dev, check)
     shift = params.dat_width - 1 if shift is None else int(shift)
     s = B.make_stft(nb, T, frames, d["hop"], n_fft, col0=d["col0"], pad=d["pad"], pad_mode=d["pad_mode"], shift=shift,
                     x_stride=xb.stride(0) if nb > 1 else 0)
+    if hold is not None:
+        return _hold_call(torch, params, L, s, B.WELCH_DETREND_CONSTANT if detrend else 0, xb, nb, n_fft // 2 + 1, scale, hold, workspace,
+                          dev, table, x.dim() == 1, family, bool(onesided_doubling))
     return _welch_fft_call(torch, params, L, s, B.WELCH_DETREND_CONSTANT if detrend else 0, xb, nb, n_fft // 2 + 1, scale,
                            onesided_doubling, out, workspace, dev, table, x.dim() == 1, family)
 
@@ -1387,7 +1395,12 @@ def welch_fft(params, x, n_fft, hop, scale, *, win_length=None, center=False, pa
                           workspace, x.device.index, None)
 
 
-def _welch_fused(torch, params, x, fs, length, noverlap, nfft, detrend, scaling, shift, out, workspace, dev, table, cache, family="fft"):
+def _welch_fused(torch, params, x, fs, length, noverlap, nfft, detrend, scaling, shift, out, workspace, dev, table, cache, family="fft",
+                 hold=None):
+    """hold: None (the mean: welch_fused*), or (traces, out_max, out_min) for hold_fused*: the same checks, window sums and
+    frequency axis (the same cache keys), the scale of ONE frame's periodogram, and _hold_call in place of _welch_fft_call."""
+    if hold is not None:
+        B.hold_traces(hold[0])
     if detrend not in ("constant", False, None):
         raise ValueError(f"detrend must be 'constant' or False, got {detrend!r}")
     if scaling not in ("density", "spectrum"):
@@ -1398,7 +1411,10 @@ def _welch_fused(torch, params, x, fs, length, noverlap, nfft, detrend, scaling,
         raise ValueError("noverlap must be less than length")
     nfft = L if nfft is None else int(nfft)
     hop = L - noverlap
-    (_fft_input if family == "fft" else _welch_mfft_input)(torch, x, nfft, dev)
+    if hold is not None:
+        (_hold_fft_input if family == "fft" else _hold_mfft_input)(torch, x, nfft, dev)
+    else:
+        (_fft_input if family == "fft" else _welch_mfft_input)(torch, x, nfft, dev)
     if not 1 <= L <= 1 << params.phi_width:
         raise ValueError(f"length {L} outside 1..2^phi_width = {1 << params.phi_width}")
     if nfft < L:
@@ -1410,11 +1426,14 @@ def _welch_fused(torch, params, x, fs, length, noverlap, nfft, detrend, scaling,
     frames = 1 + (T - L) // hop
     xb = _stft_input(xb, (T,))
     sums = _window_sums(torch, params, L, True, shift, dev, table, cache)
-    scale = B.welch_scale(sums, frames, fs, scaling)
+    scale = B.welch_scale(sums, frames if hold is None else 1, fs, scaling)
     sh = params.dat_width - 1 if shift is None else int(shift)
     s = B.make_stft(nb, T, frames, hop, nfft, shift=sh, x_stride=xb.stride(0) if nb > 1 else 0)
     # before the launch: it refuses inside a capture when missing
     freqs = _freq_axis(torch, cache, nfft, fs, dev, "freqs" if family == "fft" else "freqs_mixed")
+    if hold is not None:
+        return (freqs,) + _hold_call(torch, params, L, s, B.WELCH_DETREND_CONSTANT if detrend == "constant" else 0, xb, nb,
+                                     nfft // 2 + 1, scale, hold, workspace, dev, table, x.dim() == 1, family, True)
     P = _welch_fft_call(torch, params, L, s, B.WELCH_DETREND_CONSTANT if detrend == "constant" else 0, xb, nb, nfft // 2 + 1, scale,
                         True, out, workspace, dev, table, x.dim() == 1, family)
     return freqs, P
@@ -1710,17 +1729,22 @@ def welch_fused_iq_mixed(params, x, fs=1.0, *, length, noverlap=None, nfft=None,
 
 # ---- fused max-hold / min-hold traces for I/Q input: window, complex FFT and the extrema over the frames in one kernel -------------------
 
-def _hold_call(torch, params, L, s, flags, xb, nb, n_fft, scale, hold, workspace, dev, table, one_d, family):
+def _hold_call(torch, params, L, s, flags, xb, nb, n_fft, scale, hold, workspace, dev, table, one_d, family, onesided=None):
     """The output and workspace rules of the fused hold calls and their launch: (pmax, pmin), each float32 (n_fft,) or (B, n_fft)
     or None for the trace not asked for.  The rules of each output are those of welch_fft_iq's `out`; both given share one row
-    stride (the C call has one p_stride)."""
+    stride (the C call has one p_stride).  For the real-input families "fft" and "mfft" n_fft counts the K columns of a row and
+    `onesided` is the doubling the C call takes as psd_flags behind the scale; the I/Q families have no such argument."""
     traces, out_max, out_min = hold
     mask = B.hold_traces(traces)
     lib = B.lib()
     if family == "cfft":
         ws_bytes, device_call, table_call = B.hold_cfft_workspace_bytes, lib.bhw_hold_cfft_f32_device, lib.bhw_hold_cfft_f32_from_table
-    else:
+    elif family == "cmfft":
         ws_bytes, device_call, table_call = B.hold_cmfft_workspace_bytes, lib.bhw_hold_cmfft_f32_device, lib.bhw_hold_cmfft_f32_from_table
+    elif family == "fft":
+        ws_bytes, device_call, table_call = B.hold_fft_workspace_bytes, lib.bhw_hold_fft_f32_device, lib.bhw_hold_fft_f32_from_table
+    else:
+        ws_bytes, device_call, table_call = B.hold_mfft_workspace_bytes, lib.bhw_hold_mfft_f32_device, lib.bhw_hold_mfft_f32_from_table
     shape = (n_fft,) if one_d else (nb, n_fft)
     outs = []
     for bit, name, out in ((B.HOLD_MAX, "out_max", out_max), (B.HOLD_MIN, "out_min", out_min)):
@@ -1743,7 +1767,8 @@ def _hold_call(torch, params, L, s, flags, xb, nb, n_fft, scale, hold, workspace
     else:
         _check_out(torch, workspace, need, "workspace", torch.float64)
     ptr = lambda o: ctypes.c_void_p(o.data_ptr()) if o is not None else None   # noqa: E731
-    tail = (ctypes.byref(s), flags, float(scale), ctypes.c_void_p(xb.data_ptr()), ptr(pmax), ptr(pmin),
+    psd = () if onesided is None else (B.PSD_ONESIDED if onesided else 0,)
+    tail = (ctypes.byref(s), flags, float(scale)) + psd + (ctypes.c_void_p(xb.data_ptr()), ptr(pmax), ptr(pmin),
             strides.pop() if strides else 0, ctypes.c_void_p(workspace.data_ptr()), workspace.numel() * 8)
     if table is None:
         B.check(device_call(ctypes.byref(params), L, dev, _stream_ptr(torch, dev), *tail))
@@ -1807,6 +1832,90 @@ def hold_fused_iq_mixed(params, x, fs=1.0, *, length, noverlap=None, nfft=None, 
     dev = x.device.index if isinstance(x, torch.Tensor) and x.is_cuda else None
     return _welch_fused_iq(torch, params, x, fs, length, noverlap, nfft, detrend, scaling, shift, fftshift, None, workspace, dev, None,
                            _SUMS_CACHE, "cmfft", (traces, out_max, out_min))
+
+
+# ---- fused max-hold / min-hold traces for real input: window, real FFT and the extrema over the frames in one kernel -----------------------
+
+def _hold_fft_input(torch, x, n_fft, dev):
+    """_fft_input for hold_fft / hold_fused: what this call does not take is refused in the name of the hold call that does."""
+    if isinstance(x, torch.Tensor) and x.is_complex():
+        raise ValueError(f"the fused hold traces for real input take real float32 input, got {x.dtype} (complex64 I/Q input: "
+                         "hold_fft_iq / hold_fused_iq)")
+    if B.mfft_supported(n_fft):
+        raise ValueError(f"n_fft {int(n_fft)} is mixed-radix: hold_fft_mixed / hold_fused_mixed transform it (one transform per n_fft)")
+    _fft_input(torch, x, n_fft, dev)
+
+
+def _hold_mfft_input(torch, x, n_fft, dev):
+    """_welch_mfft_input for hold_fft_mixed / hold_fused_mixed, with the refusals in the hold calls' names."""
+    if isinstance(x, torch.Tensor) and x.is_complex():
+        raise ValueError(f"the mixed-radix fused hold traces for real input take real float32 input, got {x.dtype} (complex64 I/Q "
+                         "input: hold_fft_iq_mixed / hold_fused_iq_mixed)")
+    n = int(n_fft)
+    if n > 0 and n & (n - 1) == 0:
+        raise ValueError(f"n_fft {n} is a power of two: hold_fft / hold_fused transform it (one transform per n_fft)")
+    _welch_mfft_input(torch, x, n_fft, dev)
+
+
+def hold_fft(params, x, n_fft, hop, scale=1.0, *, win_length=None, center=False, pad_mode="reflect", detrend=False,
+             onesided_doubling=True, shift=None, traces="both", out_max=None, out_min=None, workspace=None):
+    """The max-hold and min-hold traces of the rows of spectrogram() WITHOUT the powers ever reaching memory
+    (bhw_hold_fft_f32_device): x (T,) or (B, T), real float32, framed, windowed and transformed exactly as spectrogram(params, x,
+    n_fft, hop, win_length=..., center=..., pad_mode=..., detrend=...) does -- the float32 power of every bin is the same word -- and
+    reduced over the frames in the same kernel.  Returns (pmax, pmin), each float32 (K,) or (B, K), K = n_fft // 2 + 1:
+    pmax = (S.amax(-2).double() * sk).float() and pmin the same with amin, S that spectrogram and sk = scale * (2 for the doubled
+    bins under onesided_doubling: every bin but 0 and n_fft / 2), welch_fft()'s factor, BIT FOR BIT at every number of frames (a
+    maximum has no order of summation); a NaN in any frame of a bin makes both traces of it NaN as amax / amin do.  So the traces do
+    not depend on B or the plan.  traces: "both" | "max" | "min"; the trace not asked for is None and is not written.  n_fft: a power
+    of two in 16..4096; the arguments and their checks are welch_fft()'s, a mixed-radix n_fft raises ValueError (hold_fft_mixed
+    transforms it), complex x too (hold_fft_iq).  `out_max`, `out_min`: float32 of the returned shape, bins contiguous, rows apart by
+    the same stride (gaps are left alone); `workspace`: float64, B.hold_fft_workspace_bytes(...) // 8 elements (allocated when not
+    given).  With the outputs and the workspace given the call neither allocates nor synchronises and can be captured with no warm
+    call.  The mean of the same frames is welch_fft(); a median is not built."""
+    torch = _torch()
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise ValueError("x must be a float32 CUDA tensor")
+    return _welch_fft_psd(torch, params, x, n_fft, hop, scale, win_length, center, pad_mode, detrend, onesided_doubling, shift, None,
+                          workspace, x.device.index, None, "fft", (traces, out_max, out_min))
+
+
+def hold_fft_mixed(params, x, n_fft, hop, scale=1.0, *, win_length=None, center=False, pad_mode="reflect", detrend=False,
+                   onesided_doubling=True, shift=None, traces="both", out_max=None, out_min=None, workspace=None):
+    """hold_fft() at the n_fft of stft_mixed() (bhw_hold_mfft_f32_device): even, 2^a·3^b·5^c, in 16..4095 and not a power of two --
+    400, 480, 960, 1000, 4000.  The traces are those of spectrogram_mixed()'s rows, bit for bit.  The arguments and their checks are
+    welch_fft_mixed()'s: a power-of-two n_fft raises ValueError (hold_fft transforms it), complex x too (hold_fft_iq_mixed).
+    `workspace`: B.hold_mfft_workspace_bytes(...) // 8 float64 elements."""
+    torch = _torch()
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise ValueError("x must be a float32 CUDA tensor")
+    return _welch_fft_psd(torch, params, x, n_fft, hop, scale, win_length, center, pad_mode, detrend, onesided_doubling, shift, None,
+                          workspace, x.device.index, None, "mfft", (traces, out_max, out_min))
+
+
+def hold_fused(params, x, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", scaling="density", shift=None,
+               traces="both", out_max=None, out_min=None, workspace=None):
+    """The max-hold and min-hold traces beside welch_fused()'s mean (bhw_hold_fft_f32_device): scipy.signal.welch's segments, their
+    FFT, and the largest and the smallest periodogram value of every bin over the segments, in ONE kernel and a small join.  The
+    arguments, their checks, the window sums cache and the SHARED read-only `freqs` are welch_fused()'s (the same tensors under the
+    same keys); the scale is that of ONE segment's periodogram, so the traces are in the units of welch_fused()'s Pxx and bracket
+    it: pmin <= Pxx <= pmax.  Returns (freqs, pmax, pmin); traces, out_max, out_min and workspace as hold_fft(), whose traces at that
+    scale these are bit for bit.  After one warm call it can be captured (ResidentTable.hold_fused); a first call inside a capture
+    raises, as welch_fused does."""
+    torch = _torch()
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise ValueError("x must be a float32 CUDA tensor")
+    return _welch_fused(torch, params, x, fs, length, noverlap, nfft, detrend, scaling, shift, None, workspace, x.device.index, None,
+                        _SUMS_CACHE, "fft", (traces, out_max, out_min))
+
+
+def hold_fused_mixed(params, x, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", scaling="density", shift=None,
+                     traces="both", out_max=None, out_min=None, workspace=None):
+    """hold_fused() at a mixed-radix nfft (bhw_hold_mfft_f32_device): the checks, the caches and `freqs` are welch_fused_mixed()'s."""
+    torch = _torch()
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise ValueError("x must be a float32 CUDA tensor")
+    return _welch_fused(torch, params, x, fs, length, noverlap, nfft, detrend, scaling, shift, None, workspace, x.device.index, None,
+                        _SUMS_CACHE, "mfft", (traces, out_max, out_min))
 
 
 # ---- Welch cross spectra: the pass behind the FFT for two signals -------------------------------------------------------------------------
@@ -2525,6 +2634,34 @@ class ResidentTable:
         can be captured into a graph, a first call inside a capture raises."""
         return _welch_fused_iq(_torch(), params, x, fs, length, noverlap, nfft, detrend, scaling, shift, fftshift, None, workspace,
                                self.device, self._live(), self._sums, "cmfft", (traces, out_max, out_min))
+
+    def hold_fft(self, params, x, n_fft, hop, scale=1.0, *, win_length=None, center=False, pad_mode="reflect", detrend=False,
+                 onesided_doubling=True, shift=None, traces="both", out_max=None, out_min=None, workspace=None):
+        """hold_fft() with the coefficients gathered from this table (bhw_hold_fft_f32_from_table): no allocation by the library, no
+        synchronisation, capturable on its first call; the bits are those of the library form."""
+        return _welch_fft_psd(_torch(), params, x, n_fft, hop, scale, win_length, center, pad_mode, detrend, onesided_doubling, shift,
+                              None, workspace, self.device, self._live(), "fft", (traces, out_max, out_min))
+
+    def hold_fused(self, params, x, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", scaling="density", shift=None,
+                   traces="both", out_max=None, out_min=None, workspace=None):
+        """hold_fused() from this table.  The sums cache and the capture rule are welch()'s: after one warm call the call can be
+        captured into a graph, a first call inside a capture raises."""
+        return _welch_fused(_torch(), params, x, fs, length, noverlap, nfft, detrend, scaling, shift, None, workspace, self.device,
+                            self._live(), self._sums, "fft", (traces, out_max, out_min))
+
+    def hold_fft_mixed(self, params, x, n_fft, hop, scale=1.0, *, win_length=None, center=False, pad_mode="reflect", detrend=False,
+                       onesided_doubling=True, shift=None, traces="both", out_max=None, out_min=None, workspace=None):
+        """hold_fft_mixed() with the coefficients gathered from this table (bhw_hold_mfft_f32_from_table): no allocation by the
+        library, no synchronisation, capturable on its first call; the bits are those of the library form."""
+        return _welch_fft_psd(_torch(), params, x, n_fft, hop, scale, win_length, center, pad_mode, detrend, onesided_doubling, shift,
+                              None, workspace, self.device, self._live(), "mfft", (traces, out_max, out_min))
+
+    def hold_fused_mixed(self, params, x, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", scaling="density",
+                         shift=None, traces="both", out_max=None, out_min=None, workspace=None):
+        """hold_fused_mixed() from this table.  The sums cache and the capture rule are welch()'s: after one warm call the call can
+        be captured into a graph, a first call inside a capture raises."""
+        return _welch_fused(_torch(), params, x, fs, length, noverlap, nfft, detrend, scaling, shift, None, workspace, self.device,
+                            self._live(), self._sums, "mfft", (traces, out_max, out_min))
 
     def cross_spectra(self, params, x, y, fs=1.0, *, length, noverlap=None, nfft=None, detrend="constant", return_onesided=True,
                       scaling="density", shift=None, outputs=("pxy", "pxx", "pyy", "coherence", "h1"), fft="torch"):

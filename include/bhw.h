@@ -1112,6 +1112,7 @@ int bhw_describe_istft_cmfft(bhw_table t, const bhw_params *p, uint64_t length, 
  *   - Not built: max-hold or median averaging; a filter bank on the averaged powers.  (I/Q input and the mixed-radix n_fft have this
  *     epilogue, bhw_welch_cfft_f32_* and bhw_welch_mfft_f32_* below; cross spectra have it for two signals side by side,
  *     bhw_csd_fft_f32_* below.  Max-hold and min-hold traces exist for I/Q input: bhw_hold_cfft_f32_* and bhw_hold_cmfft_f32_* below.)
+ *     Max-hold and min-hold traces of these rows: bhw_hold_fft_f32_* below.
  *   - bhw_describe_welch_fft: bhw_describe_stft_fft's line in the same words, plus the chunk, the runs, the groups per run, the
  *     accumulators per lane and the workspace bytes.  t may be NULL (the library call).  Host arithmetic only. */
 /* Why 16: the frames of ONE signal are the only parallelism a long record has.  16 381 frames of one signal (2^24 samples, n_fft 4096,
@@ -1211,7 +1212,7 @@ int bhw_describe_welch_cfft(bhw_table t, const bhw_params *p, uint64_t length, c
  *     call.
  *   - Not built: odd n_fft and factors >= 7; cross spectra at these lengths in one kernel; max-hold or median traces.  (I/Q input
  *     at these lengths, odd ones included: bhw_welch_cmfft_f32_* below.  Max-hold and min-hold traces exist for I/Q input only:
- *     bhw_hold_cmfft_f32_* below.)
+ *     bhw_hold_cmfft_f32_* below.)  Max-hold and min-hold traces of these rows have since been built: bhw_hold_mfft_f32_* below.
  *   - bhw_describe_welch_mfft: bhw_describe_stft_mfft's line in the same words (without the output form), plus the fields
  *     bhw_describe_welch_fft adds.  t may be NULL (the library call).  Host arithmetic only. */
 uint64_t bhw_welch_mfft_workspace_bytes(const bhw_stft *s);
@@ -1317,7 +1318,8 @@ int bhw_describe_welch_cmfft(bhw_table t, const bhw_params *p, uint64_t length, 
  *   - Capture: as bhw_welch_cfft_f32_*.  The library form needs no bhw_prepare_device; the from-table form is capturable on its
  *     first call.
  *   - Not built: median or percentile traces; the mean in the same launch (call bhw_welch_cfft_f32_* beside this one); real input;
- *     n_fft >= 2048 for I/Q input (2048 itself is taken here, 4096 is not).
+ *     n_fft >= 2048 for I/Q input (2048 itself is taken here, 4096 is not).  Real input has calls of its own: bhw_hold_fft_f32_*
+ *     and bhw_hold_mfft_f32_* below.
  *   - bhw_describe_hold_cfft: bhw_describe_welch_cfft's line field for field ("hold cfft ...", its own kernels and k_hold_join),
  *     plus the traces asked for: traces is a non-empty subset of BHW_HOLD_MAX | BHW_HOLD_MIN.  t may be NULL (the library call).
  *     Host arithmetic only. */
@@ -1353,6 +1355,74 @@ int bhw_hold_cmfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t len
                                   void *workspace, uint64_t workspace_bytes);
 int bhw_describe_hold_cmfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, uint32_t traces,
                             char *buf, uint64_t len);
+
+/* Fused max-hold and min-hold traces for real input: window, real FFT and the maximum and the minimum of |Y|^2 over the frames by ONE
+ * kernel and the join of bhw_hold_cfft_f32_* -- the two analyser traces beside the average of bhw_welch_fft_f32_*, for audio, vibration
+ * and speech frames.  The rows of bhw_stft_fft_f32_* are formed and transformed by the same kernel body, and the powers are reduced over
+ * the frames where the transform ends, so the (B, F, K) powers that bhw_spectrogram_f32_* writes for an amax / amin to read back never
+ * exist.  The argument list is bhw_welch_fft_f32_*'s with the two outputs in d_P's place.
+ *   - Inputs: (p, length, s, flags, scale, psd_flags) exactly as bhw_welch_fft_f32_* takes them: channels 1, flags 0 or
+ *     BHW_WELCH_DETREND_CONSTANT, s->y_stride and s->y_batch_stride 0, a finite scale, psd_flags 0 or BHW_PSD_ONESIDED.
+ *   - Outputs: d_max and d_min are float32 (B, K), K = n_fft / 2 + 1, row b at b * p_stride floats (0 = K).  Either may be NULL: that
+ *     trace is not written.  Both NULL is BHW_ERR_BADARG.  Both traces are always computed; the pointers only select what is stored.
+ *     The alignment, p_stride and overlap rules are those of bhw_hold_cfft_f32_*, with K columns and T floats of a signal.
+ *   - Values: let h_f be the float32 word that bhw_spectrogram_f32_* stores for bin k of row (b, f): fl32((double) re * re +
+ *     (double) im * im) of the split bin, the binary64 sum of the two exact products rounded to float32, from the same row function
+ *     and the same split expression.  Then, over the live frames f < F only,
+ *        d_max[b * p_stride + k] = fl32((double) max_f h_f * s_k)           d_min[b * p_stride + k] = fl32((double) min_f h_f * s_k)
+ *        s_k = scale * 2.0 where bhw_welch_psd_f32's rule doubles bin k (psd_flags, k, K, n_fft), else scale
+ *     s_k is the very factor of bhw_welch_fft_f32_*, so the traces are in that call's units and bracket its P for the same scale
+ *     times F.
+ *   - NaN: if any h_f of a bin is a NaN, both traces of that bin are NaN, as an amax / amin over the frames gives; the words are
+ *     reduced as unsigned integers, as bhw_hold_cfft_f32_* explains.  Infinities behave as IEEE says.  A NaN or an infinity in x
+ *     reaches only the bins of its own signal.  Zeros in give +0.0 out (for a scale >= 0).
+ *   - Consequences: the bits of both traces depend on the window, n_fft, the flags, scale, psd_flags and the signal's samples only --
+ *     not on B, the grid, the order of the reduction (a maximum has none), or library versus table.  At EVERY F the result equals the
+ *     reduction of bhw_spectrogram_f32_*'s power rows bit for bit; there is no ulp clause.
+ *   - Workspace: caller-provided, 8-byte aligned, bhw_hold_fft_workspace_bytes(s) = bhw_welch_fft_workspace_bytes(s) bytes: a
+ *     (max, min) pair of words is the 8 bytes of a chunk sum.  The layout inside is not part of the contract.  Partial results are
+ *     stored plainly, once each: there are no float atomics.  A short workspace is BHW_ERR_WORKSPACE.  No call allocates.
+ *   - Supported: exactly the set of bhw_welch_fft_f32_* (channels 1, n_fft a power of two in 16..4096), with that call's codes and
+ *     words for every refusal on the input side: both calls run the same check function.
+ *   - Checks before any HIP call, in this order (BHW_ERR_BADARG unless noted): everything bhw_welch_fft_f32_* checks before its
+ *     pointers, in its words (frames 0 returns BHW_OK there with the pointers unchecked); then the steps 5. to 8. of
+ *     bhw_hold_cfft_f32_*.
+ *   - Capture: as bhw_welch_fft_f32_*.  The library form needs no bhw_prepare_device; the from-table form is capturable on its first
+ *     call.
+ *   - Not built: median or percentile traces; the mean in the same launch (call bhw_welch_fft_f32_* beside this one); a filter bank
+ *     on the traces; odd n_fft.
+ *   - bhw_describe_hold_fft: bhw_describe_welch_fft's line field for field ("hold fft ...", its own kernels and k_hold_join), plus
+ *     the traces asked for: traces is a non-empty subset of BHW_HOLD_MAX | BHW_HOLD_MIN.  t may be NULL (the library call).  Host
+ *     arithmetic only. */
+uint64_t bhw_hold_fft_workspace_bytes(const bhw_stft *s);
+int bhw_hold_fft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                            double scale, uint32_t psd_flags, const float *d_x, float *d_max, float *d_min, uint64_t p_stride,
+                            void *workspace, uint64_t workspace_bytes);
+int bhw_hold_fft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                double scale, uint32_t psd_flags, const float *d_x, float *d_max, float *d_min, uint64_t p_stride,
+                                void *workspace, uint64_t workspace_bytes);
+int bhw_describe_hold_fft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, uint32_t traces,
+                          char *buf, uint64_t len);
+
+/* The same traces at a mixed-radix n_fft (400, 1000, 1200, 1536): the rows of bhw_stft_mfft_f32_* under the same epilogue.  The argument
+ * list is bhw_hold_fft_f32_*'s, word for word, and so is the contract, with bhw_stft_mfft_f32_* and bhw_welch_mfft_f32_* read for
+ * bhw_stft_fft_f32_* and bhw_welch_fft_f32_*:
+ *   - Inputs, and every refusal on the input side, are bhw_welch_mfft_f32_*'s (the same check function): channels 1, the 95 even
+ *     n_fft = 2^a 3^b 5^c in 16..4095 that are no power of two, flags 0 or BHW_WELCH_DETREND_CONSTANT (BHW_MFFT_POWER is refused); a
+ *     power of two, I/Q input and every other n_fft are BHW_ERR_UNSUPPORTED in that call's words.
+ *   - Values: h_f is the float32 word bhw_stft_mfft_f32_* writes under BHW_MFFT_POWER; the traces, s_k, the NaN rule, the
+ *     consequences (bit for bit at every F) and the pointer checks are those above.
+ *   - Workspace: bhw_hold_mfft_workspace_bytes(s) = bhw_welch_mfft_workspace_bytes(s) bytes.
+ *   - Not built: as above; factors of 7 and above. */
+uint64_t bhw_hold_mfft_workspace_bytes(const bhw_stft *s);
+int bhw_hold_mfft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                             double scale, uint32_t psd_flags, const float *d_x, float *d_max, float *d_min, uint64_t p_stride,
+                             void *workspace, uint64_t workspace_bytes);
+int bhw_hold_mfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                 double scale, uint32_t psd_flags, const float *d_x, float *d_max, float *d_min, uint64_t p_stride,
+                                 void *workspace, uint64_t workspace_bytes);
+int bhw_describe_hold_mfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, uint32_t traces,
+                           char *buf, uint64_t len);
 
 /* Fused Welch cross spectra: window, real FFT of TWO signals and the four averages over the frames by ONE kernel and a small join.  The
  * rows of bhw_stft_fft_f32_* of x and of y are formed and transformed side by side by the same kernel body, and the terms of
