@@ -211,30 +211,7 @@ int bhwk_csd_fft_f32(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinC
     const BhwStftFftPlan &pl = cp.fft;
     if (!pl.rows) return 0;
     hipStream_t st = (hipStream_t)l.stream;
-    FftIo a;
-    a.x = d_x;
-    a.Y = nullptr;
-    a.rows = pl.rows;
-    a.frames = s->frames;
-    a.hop = s->hop;
-    a.samples = s->samples;
-    a.pad = s->pad;
-    a.x_stride = pl.x_stride;
-    a.y_stride = 0;
-    a.y_bstride = 0;
-    a.groups = pl.groups;
-    a.n_fft = (uint32_t)s->n_fft;
-    a.m = pl.m;
-    a.col0 = (uint32_t)s->col0;
-    a.len = (uint32_t)pl.len;
-    a.lpf = pl.lpf;
-    a.fy = pl.fy;
-    a.cpl = pl.cpl;
-    a.radix4 = pl.radix4;
-    a.radix2 = pl.radix2;
-    a.shift = s->shift;
-    a.reflect = s->pad_mode == BHW_PAD_REFLECT ? 1u : 0u;
-    a.detrend = pl.detrend ? 1u : 0u;
+    const FftIo a = fft_io(pl, s, d_x, nullptr);
     CsdFftAcc wa{};
     wa.y = d_y;
     wa.chunk_ws = d_ws;
@@ -243,18 +220,11 @@ int bhwk_csd_fft_f32(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinC
     wa.gpr = cp.gpr;
     wa.bcast = (cp.flags & BHW_CSD_BROADCAST_X) ? 1u : 0u;
     const dim3 grid((unsigned)pl.grid), block(kFftBlock);
-    if (!d_table) {
-        with_int_or_last<2, 1, 0>(direct_form(c_in), [&](auto D) { launch_lds(k_csd_fft_direct<D>, grid, block, pl.lds_bytes, st, c_in, w, a, lp, wa); });
-    } else {
-        const BhwCordicCfg c = table_layout(c_in);
-        int fmt, nt, mode;
-        if (!bhwp_range_form(c, w, &fmt, &nt, &mode)) return (int)hipErrorInvalidValue;
-        const void *tab = (const void *)d_table;
-        with_range_form(fmt, nt, mode, [&](auto F, auto NT, auto M) {
+    int e = with_window_source(
+        c_in, w, d_table, [&](auto D) { launch_lds(k_csd_fft_direct<D>, grid, block, pl.lds_bytes, st, c_in, w, a, lp, wa); },
+        [&](auto F, auto NT, auto M, const BhwCordicCfg &c, const void *tab) {
             launch_lds(k_csd_fft_table<F, NT, M>, grid, block, pl.lds_bytes, st, c, w, tab, a, lp, wa);
         });
-    }
-    int e = finish(hipSuccess);
     if (e) return e;
     const uint64_t row = kCsdFftChains * cp.bins;
     if (cp.blocks > 1) {

@@ -862,6 +862,9 @@ __device__ __forceinline__ int32_t range_coeff(const BhwCordicCfg &cfg, const Bh
     return range_coeff_ph<FMT, NT, MODE>(cfg, win, table, [&](uint32_t k) { return (k * n) & mask; });
 }
 
+// The window coefficient w as the float the fused forward FFT kernels multiply by: w * 2^-shift (exact).
+__device__ __forceinline__ float fft_coeff(int32_t w, uint32_t shift) { return ldexpf((float)w, -(int)shift); }
+
 inline unsigned grid_for(uint64_t count) { return (unsigned)((count + kBlock - 1) / kBlock); }
 
 // Launches go through hipLaunchKernel, which returns the launch status itself: the thread's hipGetLastError() state is
@@ -939,11 +942,36 @@ inline uint32_t pair_io(uint32_t channels, const void *a, const void *b, uint64_
     return channels == 1 ? 0u : (((((uintptr_t)a | (uintptr_t)b) % 8 == 0) && stride % 2 == 0) ? 2u : 1u);
 }
 
+// The `vec` of CfftIo and CmfftIo: one 8-byte load per complex sample where every sample of every signal is 8-byte aligned.
+inline uint32_t iq_vec(const void *d_x, uint64_t batch, uint64_t x_stride)
+{
+    return ((uintptr_t)d_x % 8 == 0 && (batch == 1 || x_stride % 2 == 0)) ? 1u : 0u;
+}
+
 inline int finish(hipError_t e)
 {
     if (e == hipSuccess) e = t_launch_err;
     t_launch_err = hipSuccess;
     return (int)e;
+}
+
+// Where the window of a fused forward FFT launch comes from: no table -- direct(FORM) for the configuration's direct_form, the
+// kernel taking c_in; a resident table -- table(FMT, NT, MODE, c, tab) for the form bhwp_range_form chose, c being the table's
+// layout and tab the table.  Returns the launch status (finish), or hipErrorInvalidValue with nothing launched for a table no range
+// form reads.
+template <typename FD, typename FT>
+inline int with_window_source(const BhwCordicCfg &c_in, const BhwWinCfg &w, const int32_t *d_table, FD &&direct, FT &&table)
+{
+    if (!d_table) {
+        with_int_or_last<2, 1, 0>(direct_form(c_in), direct);
+        return finish(hipSuccess);
+    }
+    const BhwCordicCfg c = table_layout(c_in);
+    int fmt, nt, mode;
+    if (!bhwp_range_form(c, w, &fmt, &nt, &mode)) return (int)hipErrorInvalidValue;
+    const void *tab = (const void *)d_table;
+    with_range_form(fmt, nt, mode, [&](auto F, auto NT, auto M) { table(F, NT, M, c, tab); });
+    return finish(hipSuccess);
 }
 
 

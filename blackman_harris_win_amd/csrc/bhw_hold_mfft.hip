@@ -71,49 +71,18 @@ int bhwk_hold_mfft_f32(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWi
     const BhwStftMfftPlan &pl = wp.fft;
     if (!pl.rows) return 0;
     hipStream_t st = (hipStream_t)l.stream;
-    MfftIo a{};
-    a.x = d_x;
-    a.Y = nullptr;
-    a.rows = pl.rows;
-    a.frames = s->frames;
-    a.hop = s->hop;
-    a.samples = s->samples;
-    a.pad = s->pad;
-    a.x_stride = pl.x_stride;
-    a.y_stride = 0;
-    a.y_bstride = 0;
-    a.groups = pl.groups;
-    a.n_fft = (uint32_t)s->n_fft;
-    a.m = pl.m;
-    a.col0 = (uint32_t)s->col0;
-    a.len = (uint32_t)pl.len;
-    a.lpf = pl.lpf;
-    a.fy = pl.fy;
-    a.cpl = pl.cpl;
-    a.passes = pl.passes;
-    for (uint32_t p = 0; p < pl.passes; ++p) a.sched |= (uint32_t)pl.radix[p] << (4u * p);
-    a.shift = s->shift;
-    a.reflect = s->pad_mode == BHW_PAD_REFLECT ? 1u : 0u;
-    a.detrend = pl.detrend ? 1u : 0u;
-    a.form = BHWP_MFFT_SPECTRUM;                                        // not read: the epilogue is HoldMfftAccumulate
+    const MfftIo a = mfft_io(pl, s, d_x, nullptr);
     HoldAcc wa{};
     wa.chunk_ws = (uint2 *)d_ws;
     wa.fpad = wp.fpad;
     wa.chunks = wp.chunks;
     wa.gpr = wp.gpr;
     const dim3 grid((unsigned)pl.grid), block(kFftBlock);
-    if (!d_table) {
-        with_int_or_last<2, 1, 0>(direct_form(c_in), [&](auto D) { launch_lds(k_hold_mfft_direct<D>, grid, block, pl.lds_bytes, st, c_in, w, a, lp, wa); });
-    } else {
-        const BhwCordicCfg c = table_layout(c_in);
-        int fmt, nt, mode;
-        if (!bhwp_range_form(c, w, &fmt, &nt, &mode)) return (int)hipErrorInvalidValue;
-        const void *tab = (const void *)d_table;
-        with_range_form(fmt, nt, mode, [&](auto F, auto NT, auto M) {
+    const int e = with_window_source(
+        c_in, w, d_table, [&](auto D) { launch_lds(k_hold_mfft_direct<D>, grid, block, pl.lds_bytes, st, c_in, w, a, lp, wa); },
+        [&](auto F, auto NT, auto M, const BhwCordicCfg &c, const void *tab) {
             launch_lds(k_hold_mfft_table<F, NT, M>, grid, block, pl.lds_bytes, st, c, w, tab, a, lp, wa);
         });
-    }
-    const int e = finish(hipSuccess);
     if (e) return e;
     return bhwk_hold_join(l, d_ws, d_max, d_min, s->batch, wp.bins, s->n_fft, wp.chunks, wp.blocks, wp.blocks_grid, wp.join_grid, wp.p_stride,
                           scale, psd_flags);

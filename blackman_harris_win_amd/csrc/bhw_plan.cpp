@@ -1537,6 +1537,17 @@ int bhwp_describe_csd(const bhw_csd *d, char *buf, uint64_t len)
 
 // ---- fused window and real FFT -------------------------------------------------------------------------------------------------------------
 
+// The descriptor with packed output strides, for a call whose y strides count other rows than the call it borrows its checks or its
+// plan from, or that writes no rows at all: t = *s with both y strides 0, and &t is returned.  A NULL or wrongly sized descriptor is
+// passed through for the borrowed checks to refuse (t is then not set).
+static const bhw_stft *packed_strides(const bhw_stft *s, bhw_stft &t)
+{
+    if (!s || s->struct_size != sizeof(bhw_stft)) return s;
+    t = *s;
+    t.y_stride = t.y_batch_stride = 0;
+    return &t;
+}
+
 int bhwp_stft_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const void *d_x, const void *d_Y,
                          bool pointers)
 {
@@ -1547,8 +1558,8 @@ int bhwp_stft_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s
     if (s->struct_size != sizeof(bhw_stft)) return bhwp_fail(BHW_ERR_BADARG, "bhw_stft.struct_size %u != %zu", s->struct_size, sizeof(bhw_stft));
     // what the frames or the segments call checks, for the same descriptor with packed rows (the output strides mean something else
     // here and are checked below)
-    bhw_stft t = *s;
-    t.y_stride = t.y_batch_stride = 0;
+    bhw_stft t;
+    packed_strides(s, t);
     const bool segments = (flags & BHW_WELCH_DETREND_CONSTANT) || (!s->pad && !s->col0 && !s->pad_mode);
     if (segments) rc = bhwp_welch_checks(p, length, &t, flags, nullptr, nullptr, nullptr, 0, false);
     else          rc = bhwp_stft_checks(p, length, &t, false, 0, nullptr, nullptr, false);
@@ -1648,12 +1659,8 @@ int bhwp_spectrogram_checks(const bhw_params *p, uint64_t length, const bhw_stft
                             const void *d_P, bool pointers)
 {
     // the input side: the forward call's checks for the descriptor with packed output strides (they count other rows here)
-    bhw_stft t{};
-    if (s && s->struct_size == sizeof(bhw_stft)) {
-        t = *s;
-        t.y_stride = t.y_batch_stride = 0;
-    }
-    int rc = bhwp_stft_fft_checks(p, length, s && s->struct_size == sizeof(bhw_stft) ? &t : s, flags, nullptr, nullptr, false);
+    bhw_stft t;
+    int rc = bhwp_stft_fft_checks(p, length, packed_strides(s, t), flags, nullptr, nullptr, false);
     if (rc) return rc;
     const uint64_t T = s->samples, F = s->frames, K = s->n_fft / 2 + 1;
     if (fb) {
@@ -1745,11 +1752,14 @@ int bhwp_describe_spectrogram(const bhw_params *p, const BhwCordicCfg *ct, uint6
 
 // ---- fused Welch PSD ------------------------------------------------------------------------------------------------------------------------
 
-BhwWelchRuns bhwp_welch_runs(uint64_t batch, uint64_t F, uint32_t fy, uint64_t bins)
+BhwWelchRuns bhwp_welch_runs(uint64_t batch, uint64_t F, uint32_t fy, uint64_t bins, uint64_t p_stride)
 {
     BhwWelchRuns r{};
+    r.bins = bins;
+    r.p_stride = p_stride ? p_stride : bins;
     r.run = fy > BHW_WELCH_FFT_CHUNK ? fy : BHW_WELCH_FFT_CHUNK;
     r.gpr = (uint32_t)(r.run / fy);
+    r.acc = fy >= BHW_WELCH_FFT_CHUNK ? 0u : (uint32_t)((bins + kFftBlock - 1) / kFftBlock);
     if (!F || !batch) return r;
     r.fpad = ((F - 1) / r.run + 1) * r.run;
     r.chunks = (F - 1) / BHW_WELCH_FFT_CHUNK + 1;
@@ -1764,49 +1774,39 @@ BhwWelchRuns bhwp_welch_runs(uint64_t batch, uint64_t F, uint32_t fy, uint64_t b
     return r;
 }
 
-uint64_t bhwp_welch_fft_workspace_bytes(const bhw_stft *s)
+// The output side of every fused Welch call, after the forward call's checks and the refusal of that call's power flag: the y strides,
+// psd_flags (the real-input calls; NULL for I/Q input), scale, p_stride, the 2^34 bound, the pointers, the workspace and the overlaps,
+// in the order of include/bhw.h.  bins: the columns of a row of P; xf: the floats of a sample of x (1 real, 2 I/Q); row, cap: the
+// words for `bins` in the p_stride and the 2^34 messages ("bins" and "K", or "n_fft" twice).  The hold calls pass `pointers` false and
+// check theirs in hold_pointer_checks.
+static int welch_output_checks(const bhw_stft *s, uint64_t bins, uint64_t xf, const char *row, const char *cap, double scale,
+                               const uint32_t *psd_flags, uint64_t p_stride, const void *d_x, const void *d_P, const void *workspace,
+                               uint64_t workspace_bytes, bool pointers)
 {
-    if (!s || !s->frames || !s->batch) return 0;
-    return bhwp_welch_runs(s->batch, s->frames, 1, s->n_fft / 2 + 1).ws_bytes;        // the bytes do not depend on fy
-}
-
-int bhwp_welch_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, double scale, uint32_t psd_flags,
-                          uint64_t p_stride, const void *d_x, const void *d_P, const void *workspace, uint64_t workspace_bytes,
-                          bool pointers)
-{
-    // the input side: the forward call's checks for the descriptor with packed output strides (no spectrum is written here)
-    bhw_stft t{};
-    const bool sized = s && s->struct_size == sizeof(bhw_stft);
-    if (sized) {
-        t = *s;
-        t.y_stride = t.y_batch_stride = 0;
-    }
-    int rc = bhwp_stft_fft_checks(p, length, sized ? &t : s, flags, nullptr, nullptr, false);
-    if (rc) return rc;
     if (s->y_stride || s->y_batch_stride)
         return bhwp_fail(BHW_ERR_BADARG, "y_stride %llu, y_batch_stride %llu: no spectrum is written, both must be 0",
                          (unsigned long long)s->y_stride, (unsigned long long)s->y_batch_stride);
-    if (psd_flags & ~BHW_PSD_ONESIDED) return bhwp_fail(BHW_ERR_BADARG, "psd_flags 0x%x (0 or BHW_PSD_ONESIDED)", psd_flags);
+    if (psd_flags && (*psd_flags & ~BHW_PSD_ONESIDED)) return bhwp_fail(BHW_ERR_BADARG, "psd_flags 0x%x (0 or BHW_PSD_ONESIDED)", *psd_flags);
     if (!(scale - scale == 0.0)) return bhwp_fail(BHW_ERR_BADARG, "scale is not finite");
-    const uint64_t T = s->samples, F = s->frames, K = s->n_fft / 2 + 1;
+    const uint64_t T = xf * s->samples, F = s->frames;                  // T: the floats of a signal
     if (!F) return BHW_OK;
-    if (p_stride && p_stride < K)
-        return bhwp_fail(BHW_ERR_BADARG, "p_stride %llu < bins %llu: rows overlap", (unsigned long long)p_stride, (unsigned long long)K);
+    if (p_stride && p_stride < bins)
+        return bhwp_fail(BHW_ERR_BADARG, "p_stride %llu < %s %llu: rows overlap", (unsigned long long)p_stride, row, (unsigned long long)bins);
     const uint64_t chunks = (F - 1) / BHW_WELCH_FFT_CHUNK + 1;
-    if ((unsigned __int128)s->batch * chunks * K > (1ull << 34))
-        return bhwp_fail(BHW_ERR_BADARG, "batch * ceil(frames / %u) * K above 2^34 per call", BHW_WELCH_FFT_CHUNK);
+    if ((unsigned __int128)s->batch * chunks * bins > (1ull << 34))
+        return bhwp_fail(BHW_ERR_BADARG, "batch * ceil(frames / %u) * %s above 2^34 per call", BHW_WELCH_FFT_CHUNK, cap);
     if (!pointers) return BHW_OK;
     if (!d_x || !d_P) return bhwp_fail(BHW_ERR_BADARG, "d_x / d_P is NULL");
     if ((uintptr_t)d_P % 4) return bhwp_fail(BHW_ERR_BADARG, "d_P is not 4-byte aligned");
     if ((uintptr_t)d_x % 4) return bhwp_fail(BHW_ERR_BADARG, "d_x is not 4-byte aligned");
-    const uint64_t need = bhwp_welch_fft_workspace_bytes(s);
+    const uint64_t need = bhwp_welch_runs(s->batch, F, 1, bins).ws_bytes;                 // the bytes do not depend on fy
     if (!workspace) return bhwp_fail(BHW_ERR_BADARG, "workspace is NULL: the chunk sums need %llu bytes", (unsigned long long)need);
     if ((uintptr_t)workspace % 8) return bhwp_fail(BHW_ERR_BADARG, "workspace is not 8-byte aligned");
     if (workspace_bytes < need)
         return bhwp_fail(BHW_ERR_WORKSPACE, "workspace of %llu bytes, the chunk and block sums need %llu", (unsigned long long)workspace_bytes,
                          (unsigned long long)need);
-    const uint64_t xs = s->x_stride ? s->x_stride : T, ps = p_stride ? p_stride : K;
-    const unsigned __int128 xe = (unsigned __int128)(s->batch - 1) * xs + T, pe = (unsigned __int128)(s->batch - 1) * ps + K;
+    const uint64_t xs = s->x_stride ? s->x_stride : T, ps = p_stride ? p_stride : bins;
+    const unsigned __int128 xe = (unsigned __int128)(s->batch - 1) * xs + T, pe = (unsigned __int128)(s->batch - 1) * ps + bins;
     if (xe > (1ull << 60) || pe > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "x or P extent beyond 2^60 elements");
     const uint64_t xa = (uint64_t)(uintptr_t)d_x, pa = (uint64_t)(uintptr_t)d_P, wa = (uint64_t)(uintptr_t)workspace;
     const uint64_t xb = (uint64_t)xe * 4u, pb = (uint64_t)pe * 4u;
@@ -1818,29 +1818,54 @@ int bhwp_welch_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *
     return BHW_OK;
 }
 
+// The run plan of a Welch plan whose forward plan is set -- the plan's BhwWelchRuns base --, with the groups and the grid of pl.fft
+// recounted from the runs and its y strides 0 (no spectrum is written).
+template <class Plan>
+static void welch_plan_runs(Plan &pl, const bhw_stft *s, uint64_t bins, uint64_t p_stride)
+{
+    pl.fft.y_stride = pl.fft.y_bstride = 0;
+    static_cast<BhwWelchRuns &>(pl) = bhwp_welch_runs(s->batch, s->frames, pl.fft.fy, bins, p_stride);
+    pl.fft.groups = pl.groups;
+    pl.fft.grid = pl.grid;
+}
+
+// The common end of the four describe_*_runs lines, appended to the head in buf: from "; chunk" to the tail.
+static void describe_runs_tail(char *buf, uint64_t len, const BhwWelchRuns &r, const char *join, const char *tail)
+{
+    const size_t at = strlen(buf);
+    snprintf(buf + at, len - at, "; chunk %u frames, %llu runs of %llu frames (%u group%s per run), %u accumulator%s per lane, %llu chunks "
+             "and %llu block%s per signal, then %s %s, workspace %llu bytes%s",
+             BHW_WELCH_FFT_CHUNK, (unsigned long long)r.runs, (unsigned long long)r.run, r.gpr, r.gpr == 1 ? "" : "s", r.acc,
+             r.acc == 1 ? "" : "s", (unsigned long long)r.chunks, (unsigned long long)r.blocks, r.blocks == 1 ? "" : "s", join,
+             r.blocks == 1 ? "once (chunks)" : "twice (chunks, blocks)", (unsigned long long)r.ws_bytes, tail);
+}
+
+uint64_t bhwp_welch_fft_workspace_bytes(const bhw_stft *s)
+{
+    if (!s || !s->frames || !s->batch) return 0;
+    return bhwp_welch_runs(s->batch, s->frames, 1, s->n_fft / 2 + 1).ws_bytes;        // the bytes do not depend on fy
+}
+
+int bhwp_welch_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, double scale, uint32_t psd_flags,
+                          uint64_t p_stride, const void *d_x, const void *d_P, const void *workspace, uint64_t workspace_bytes,
+                          bool pointers)
+{
+    // the input side: the forward call's checks for the descriptor with packed output strides (no spectrum is written here)
+    bhw_stft t;
+    const bhw_stft *packed = packed_strides(s, t);
+    int rc = bhwp_stft_fft_checks(p, length, packed, flags, nullptr, nullptr, false);
+    if (rc) return rc;
+    return welch_output_checks(s, s->n_fft / 2 + 1, 1, "bins", "K", scale, &psd_flags, p_stride, d_x, d_P, workspace, workspace_bytes, pointers);
+}
+
 BhwWelchFftPlan bhwp_welch_fft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, uint64_t p_stride,
                                     bool from_table)
 {
     BhwWelchFftPlan pl{};
-    bhw_stft t = *s;
-    t.y_stride = t.y_batch_stride = 0;
+    bhw_stft t;
+    packed_strides(s, t);
     pl.fft = bhwp_stft_fft_plan(p, length, &t, flags, from_table);
-    pl.fft.y_stride = pl.fft.y_bstride = 0;
-    pl.bins = s->n_fft / 2 + 1;
-    const BhwWelchRuns r = bhwp_welch_runs(s->batch, s->frames, pl.fft.fy, pl.bins);
-    pl.run = r.run;
-    pl.gpr = r.gpr;
-    pl.acc = pl.fft.fy >= BHW_WELCH_FFT_CHUNK ? 0u : (uint32_t)((pl.bins + kFftBlock - 1) / kFftBlock);
-    pl.p_stride = p_stride ? p_stride : pl.bins;
-    pl.fpad = r.fpad;
-    pl.chunks = r.chunks;
-    pl.blocks = r.blocks;
-    pl.runs = r.runs;
-    pl.fft.groups = r.groups;
-    pl.fft.grid = r.grid;
-    pl.blocks_grid = r.blocks_grid;
-    pl.join_grid = r.join_grid;
-    pl.ws_bytes = r.ws_bytes;
+    welch_plan_runs(pl, s, s->n_fft / 2 + 1, p_stride);
     return pl;
 }
 
@@ -1866,14 +1891,11 @@ static int describe_fft_runs(const bhw_params *p, const BhwCordicCfg *ct, uint64
     bhwp_stft_fft_schedule(pl, sched, sizeof sched);
     snprintf(buf, len, "%s fft %s (L = %llu, n_fft %llu, col0 %llu, pad %llu %s, %s): %s, %llu signals x %llu frames = %llu rows, "
              "complex FFT of %u points in passes %s + split, %u lanes per row x %u rows per workgroup, %u columns per lane, %llu groups, "
-             "grid %llu x %u lanes, %u bytes of LDS; chunk %u frames, %llu runs of %llu frames (%u group%s per run), %u accumulator%s "
-             "per lane, %llu chunks and %llu block%s per signal, then %s %s, workspace %llu bytes%s",
+             "grid %llu x %u lanes, %u bytes of LDS",
              what, route, (unsigned long long)length, (unsigned long long)s->n_fft, (unsigned long long)s->col0, (unsigned long long)s->pad, pad,
              det, kern, (unsigned long long)s->batch, (unsigned long long)s->frames, (unsigned long long)pl.rows, pl.m, sched, pl.lpf, pl.fy,
-             pl.cpl, (unsigned long long)pl.groups, (unsigned long long)pl.grid, kFftBlock, pl.lds_bytes, BHW_WELCH_FFT_CHUNK,
-             (unsigned long long)wp.runs, (unsigned long long)wp.run, wp.gpr, wp.gpr == 1 ? "" : "s", wp.acc, wp.acc == 1 ? "" : "s",
-             (unsigned long long)wp.chunks, (unsigned long long)wp.blocks, wp.blocks == 1 ? "" : "s", join,
-             wp.blocks == 1 ? "once (chunks)" : "twice (chunks, blocks)", (unsigned long long)wp.ws_bytes, tail);
+             pl.cpl, (unsigned long long)pl.groups, (unsigned long long)pl.grid, kFftBlock, pl.lds_bytes);
+    describe_runs_tail(buf, len, wp, join, tail);
     return BHW_OK;
 }
 
@@ -1896,16 +1918,13 @@ int bhwp_csd_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s,
                         uint64_t workspace_bytes, bool pointers)
 {
     // the descriptor: bhwp_welch_fft_checks' in its order, with the routes that take what this call refuses named
-    bhw_stft t{};
-    const bool sized = s && s->struct_size == sizeof(bhw_stft);
-    if (sized) {
-        t = *s;
-        t.y_stride = t.y_batch_stride = 0;
-    }
+    bhw_stft t;
+    const bhw_stft *packed = packed_strides(s, t);
     // the params first, as every fused call has them first: their refusals (the source, the model, phi_width) keep their words
     int rc = bhwp_f32_checks(p, length, 0);
     if (rc) return rc;
-    rc = bhwp_stft_fft_checks(p, length, sized ? &t : s, flags, nullptr, nullptr, false);
+    rc = bhwp_stft_fft_checks(p, length, packed, flags, nullptr, nullptr, false);
+    const bool sized = packed == &t;
     const bool pow2 = sized && s->n_fft && !(s->n_fft & (s->n_fft - 1)) && s->n_fft >= (1ull << kFftMinLog) && s->n_fft <= (1ull << kFftMaxLog);
     if (rc == BHW_ERR_UNSUPPORTED && sized && (s->channels != 1 || !pow2)) {           // the two refusals this call renames
         if (s->channels != 1)
@@ -1963,8 +1982,8 @@ BhwCsdFftPlan bhwp_csd_fft_plan(const bhw_params *p, uint64_t length, const bhw_
                                 uint64_t o_stride, bool from_table)
 {
     BhwCsdFftPlan pl{};
-    bhw_stft t = *s;
-    t.y_stride = t.y_batch_stride = 0;
+    bhw_stft t;
+    packed_strides(s, t);
     BhwStftFftPlan &f = pl.fft;
     f = bhwp_stft_fft_plan(p, length, &t, flags, from_table);
     f.y_stride = f.y_bstride = 0;
@@ -2057,8 +2076,8 @@ int bhwp_stft_mfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *
     if (fb && !(flags & BHW_MFFT_POWER)) return bhwp_fail(BHW_ERR_BADARG, "a filter bank folds powers: fb needs BHW_MFFT_POWER in flags");
     // what the frames or the segments call checks, for the same descriptor with packed rows (the output strides mean something else
     // here and are checked below)
-    bhw_stft t = *s;
-    t.y_stride = t.y_batch_stride = 0;
+    bhw_stft t;
+    packed_strides(s, t);
     const uint32_t det = flags & BHW_WELCH_DETREND_CONSTANT;
     const bool segments = det || (!s->pad && !s->col0 && !s->pad_mode);
     if (segments) rc = bhwp_welch_checks(p, length, &t, det, nullptr, nullptr, nullptr, 0, false);
@@ -2245,8 +2264,8 @@ static int iq_descriptor_checks(const bhw_params *p, uint64_t length, const bhw_
     if (s->struct_size != sizeof(bhw_stft)) return bhwp_fail(BHW_ERR_BADARG, "bhw_stft.struct_size %u != %zu", s->struct_size, sizeof(bhw_stft));
     // 1. what the frames or the segments call checks, for the same descriptor with packed rows (the output strides mean something
     //    else here and are checked below); this holds batch * frames * n_fft to 2^34 and the extents of x to 2^60 floats
-    bhw_stft t = *s;
-    t.y_stride = t.y_batch_stride = 0;
+    bhw_stft t;
+    packed_strides(s, t);
     const uint32_t detrend = flags & BHW_WELCH_DETREND_CONSTANT;
     const bool segments = detrend || (!s->pad && !s->col0 && !s->pad_mode);
     if (segments) rc = bhwp_welch_checks(p, length, &t, detrend, nullptr, nullptr, nullptr, 0, false);
@@ -2432,61 +2451,23 @@ uint64_t bhwp_welch_cfft_workspace_bytes(const bhw_stft *s)
 }
 
 // The output side of both fused I/Q Welch calls (bhw_welch_cfft_f32_*, bhw_welch_cmfft_f32_*), after the forward call's checks passed:
-// steps 2 to 7 of include/bhw.h.  The workspace is bhwp_welch_runs' with bins = n_fft in both.
+// steps 2 to 7 of include/bhw.h -- the refusal of BHW_CFFT_POWER, then welch_output_checks with bins = n_fft and two floats a sample.
 static int welch_iq_output_checks(const bhw_stft *s, uint32_t flags, double scale, uint64_t p_stride, const void *d_x, const void *d_P,
                                   const void *workspace, uint64_t workspace_bytes, bool pointers)
 {
     // 2.
     if (flags & BHW_CFFT_POWER)
         return bhwp_fail(BHW_ERR_BADARG, "flags 0x%x: BHW_CFFT_POWER has no meaning here (BHW_WELCH_DETREND_CONSTANT, BHW_CFFT_SHIFT)", flags);
-    if (s->y_stride || s->y_batch_stride)
-        return bhwp_fail(BHW_ERR_BADARG, "y_stride %llu, y_batch_stride %llu: no spectrum is written, both must be 0",
-                         (unsigned long long)s->y_stride, (unsigned long long)s->y_batch_stride);
-    if (!(scale - scale == 0.0)) return bhwp_fail(BHW_ERR_BADARG, "scale is not finite");
-    // 3., 4.
-    const uint64_t T = s->samples, F = s->frames, N = s->n_fft;
-    if (!F) return BHW_OK;
-    if (p_stride && p_stride < N)
-        return bhwp_fail(BHW_ERR_BADARG, "p_stride %llu < n_fft %llu: rows overlap", (unsigned long long)p_stride, (unsigned long long)N);
-    const uint64_t chunks = (F - 1) / BHW_WELCH_FFT_CHUNK + 1;
-    if ((unsigned __int128)s->batch * chunks * N > (1ull << 34))
-        return bhwp_fail(BHW_ERR_BADARG, "batch * ceil(frames / %u) * n_fft above 2^34 per call", BHW_WELCH_FFT_CHUNK);
-    if (!pointers) return BHW_OK;
-    // 5., 6.
-    if (!d_x || !d_P) return bhwp_fail(BHW_ERR_BADARG, "d_x / d_P is NULL");
-    if ((uintptr_t)d_P % 4) return bhwp_fail(BHW_ERR_BADARG, "d_P is not 4-byte aligned");
-    if ((uintptr_t)d_x % 4) return bhwp_fail(BHW_ERR_BADARG, "d_x is not 4-byte aligned");
-    const uint64_t need = bhwp_welch_cfft_workspace_bytes(s);
-    if (!workspace) return bhwp_fail(BHW_ERR_BADARG, "workspace is NULL: the chunk sums need %llu bytes", (unsigned long long)need);
-    if ((uintptr_t)workspace % 8) return bhwp_fail(BHW_ERR_BADARG, "workspace is not 8-byte aligned");
-    if (workspace_bytes < need)
-        return bhwp_fail(BHW_ERR_WORKSPACE, "workspace of %llu bytes, the chunk and block sums need %llu", (unsigned long long)workspace_bytes,
-                         (unsigned long long)need);
-    // 7. (x counts floats: 2 T of a signal)
-    const uint64_t xs = s->x_stride ? s->x_stride : 2 * T, ps = p_stride ? p_stride : N;
-    const unsigned __int128 xe = (unsigned __int128)(s->batch - 1) * xs + 2 * T, pe = (unsigned __int128)(s->batch - 1) * ps + N;
-    if (xe > (1ull << 60) || pe > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "x or P extent beyond 2^60 elements");
-    const uint64_t xa = (uint64_t)(uintptr_t)d_x, pa = (uint64_t)(uintptr_t)d_P, wa = (uint64_t)(uintptr_t)workspace;
-    const uint64_t xb = (uint64_t)xe * 4u, pb = (uint64_t)pe * 4u;
-    if (xa > UINT64_MAX - xb || pa > UINT64_MAX - pb || wa > UINT64_MAX - need)
-        return bhwp_fail(BHW_ERR_BADARG, "x, P or workspace range wraps the address space");
-    if (xa < pa + pb && pa < xa + xb) return bhwp_fail(BHW_ERR_BADARG, "d_x and d_P overlap");
-    if ((wa < xa + xb && xa < wa + need) || (wa < pa + pb && pa < wa + need))
-        return bhwp_fail(BHW_ERR_BADARG, "workspace overlaps d_x or d_P");
-    return BHW_OK;
+    return welch_output_checks(s, s->n_fft, 2, "n_fft", "n_fft", scale, nullptr, p_stride, d_x, d_P, workspace, workspace_bytes, pointers);
 }
 
 int bhwp_welch_cfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, double scale, uint64_t p_stride,
                            const void *d_x, const void *d_P, const void *workspace, uint64_t workspace_bytes, bool pointers)
 {
     // 1. the input side: the forward call's checks for the descriptor with packed output strides (no spectrum is written here)
-    bhw_stft t{};
-    const bool sized = s && s->struct_size == sizeof(bhw_stft);
-    if (sized) {
-        t = *s;
-        t.y_stride = t.y_batch_stride = 0;
-    }
-    const int rc = bhwp_stft_cfft_checks(p, length, sized ? &t : s, flags, nullptr, nullptr, false);
+    bhw_stft t;
+    const bhw_stft *packed = packed_strides(s, t);
+    const int rc = bhwp_stft_cfft_checks(p, length, packed, flags, nullptr, nullptr, false);
     if (rc) return rc;
     return welch_iq_output_checks(s, flags, scale, p_stride, d_x, d_P, workspace, workspace_bytes, pointers);
 }
@@ -2495,25 +2476,10 @@ BhwWelchCfftPlan bhwp_welch_cfft_plan(const bhw_params *p, uint64_t length, cons
                                       bool from_table)
 {
     BhwWelchCfftPlan pl{};
-    bhw_stft t = *s;
-    t.y_stride = t.y_batch_stride = 0;
+    bhw_stft t;
+    packed_strides(s, t);
     pl.fft = bhwp_stft_cfft_plan(p, length, &t, flags & kWelchCfftFlags, from_table);
-    pl.fft.y_stride = pl.fft.y_bstride = 0;
-    pl.bins = s->n_fft;
-    const BhwWelchRuns r = bhwp_welch_runs(s->batch, s->frames, pl.fft.fy, pl.bins);
-    pl.run = r.run;
-    pl.gpr = r.gpr;
-    pl.acc = pl.fft.fy >= BHW_WELCH_FFT_CHUNK ? 0u : (uint32_t)((pl.bins + kFftBlock - 1) / kFftBlock);
-    pl.p_stride = p_stride ? p_stride : pl.bins;
-    pl.fpad = r.fpad;
-    pl.chunks = r.chunks;
-    pl.blocks = r.blocks;
-    pl.runs = r.runs;
-    pl.fft.groups = r.groups;
-    pl.fft.grid = r.grid;
-    pl.blocks_grid = r.blocks_grid;
-    pl.join_grid = r.join_grid;
-    pl.ws_bytes = r.ws_bytes;
+    welch_plan_runs(pl, s, s->n_fft, p_stride);
     return pl;
 }
 
@@ -2543,14 +2509,11 @@ static int describe_cfft_runs(const bhw_params *p, const BhwCordicCfg *ct, uint6
     bhwp_stft_fft_schedule(f, sched, sizeof sched);
     snprintf(buf, len, "%s cfft %s (L = %llu, n_fft %llu, col0 %llu, pad %llu %s, %s), %s: %s, %llu signals x %llu frames = %llu rows, "
              "complex FFT of %u points in passes %s (no split), %u lanes per row x %u rows per workgroup, %u columns per lane, %llu groups, "
-             "grid %llu x %u lanes, %u bytes of LDS; chunk %u frames, %llu runs of %llu frames (%u group%s per run), %u accumulator%s "
-             "per lane, %llu chunks and %llu block%s per signal, then %s %s, workspace %llu bytes%s",
+             "grid %llu x %u lanes, %u bytes of LDS",
              what, route, (unsigned long long)length, (unsigned long long)s->n_fft, (unsigned long long)s->col0, (unsigned long long)s->pad, pad,
              det, bins, kern, (unsigned long long)s->batch, (unsigned long long)s->frames, (unsigned long long)pl.rows, pl.n, sched, pl.lpf,
-             pl.fy, pl.cpl, (unsigned long long)pl.groups, (unsigned long long)pl.grid, kFftBlock, pl.lds_bytes, BHW_WELCH_FFT_CHUNK,
-             (unsigned long long)wp.runs, (unsigned long long)wp.run, wp.gpr, wp.gpr == 1 ? "" : "s", wp.acc, wp.acc == 1 ? "" : "s",
-             (unsigned long long)wp.chunks, (unsigned long long)wp.blocks, wp.blocks == 1 ? "" : "s", join,
-             wp.blocks == 1 ? "once (chunks)" : "twice (chunks, blocks)", (unsigned long long)wp.ws_bytes, tail);
+             pl.fy, pl.cpl, (unsigned long long)pl.groups, (unsigned long long)pl.grid, kFftBlock, pl.lds_bytes);
+    describe_runs_tail(buf, len, wp, join, tail);
     return BHW_OK;
 }
 
@@ -2572,13 +2535,9 @@ int bhwp_welch_cmfft_checks(const bhw_params *p, uint64_t length, const bhw_stft
                             const void *d_x, const void *d_P, const void *workspace, uint64_t workspace_bytes, bool pointers)
 {
     // 1. the input side: the mixed-radix forward call's checks for the descriptor with packed output strides
-    bhw_stft t{};
-    const bool sized = s && s->struct_size == sizeof(bhw_stft);
-    if (sized) {
-        t = *s;
-        t.y_stride = t.y_batch_stride = 0;
-    }
-    const int rc = bhwp_stft_cmfft_checks(p, length, sized ? &t : s, flags, nullptr, nullptr, false);
+    bhw_stft t;
+    const bhw_stft *packed = packed_strides(s, t);
+    const int rc = bhwp_stft_cmfft_checks(p, length, packed, flags, nullptr, nullptr, false);
     if (rc) return rc;
     return welch_iq_output_checks(s, flags, scale, p_stride, d_x, d_P, workspace, workspace_bytes, pointers);
 }
@@ -2587,25 +2546,10 @@ BhwWelchCmfftPlan bhwp_welch_cmfft_plan(const bhw_params *p, uint64_t length, co
                                         bool from_table)
 {
     BhwWelchCmfftPlan pl{};
-    bhw_stft t = *s;
-    t.y_stride = t.y_batch_stride = 0;
+    bhw_stft t;
+    packed_strides(s, t);
     pl.fft = bhwp_stft_cmfft_plan(p, length, &t, flags & kWelchCfftFlags, from_table);
-    pl.fft.y_stride = pl.fft.y_bstride = 0;
-    pl.bins = s->n_fft;
-    const BhwWelchRuns r = bhwp_welch_runs(s->batch, s->frames, pl.fft.fy, pl.bins);
-    pl.run = r.run;
-    pl.gpr = r.gpr;
-    pl.acc = pl.fft.fy >= BHW_WELCH_FFT_CHUNK ? 0u : (uint32_t)((pl.bins + kFftBlock - 1) / kFftBlock);
-    pl.p_stride = p_stride ? p_stride : pl.bins;
-    pl.fpad = r.fpad;
-    pl.chunks = r.chunks;
-    pl.blocks = r.blocks;
-    pl.runs = r.runs;
-    pl.fft.groups = r.groups;
-    pl.fft.grid = r.grid;
-    pl.blocks_grid = r.blocks_grid;
-    pl.join_grid = r.join_grid;
-    pl.ws_bytes = r.ws_bytes;
+    welch_plan_runs(pl, s, s->n_fft, p_stride);
     return pl;
 }
 
@@ -2634,14 +2578,11 @@ static int describe_cmfft_runs(const bhw_params *p, const BhwCordicCfg *ct, uint
     bhwp_stft_mfft_schedule(f, sched, sizeof sched);
     snprintf(buf, len, "%s cmfft %s (L = %llu, n_fft %llu, col0 %llu, pad %llu %s, %s), %s: %s, %llu signals x %llu frames = %llu rows, "
              "complex FFT of %u points in passes %s (no split), %u lanes per row x %u rows per workgroup, %u columns per lane, %llu groups, "
-             "grid %llu x %u lanes, %u bytes of LDS, %u twiddles; chunk %u frames, %llu runs of %llu frames (%u group%s per run), "
-             "%u accumulator%s per lane, %llu chunks and %llu block%s per signal, then %s %s, workspace %llu bytes%s",
+             "grid %llu x %u lanes, %u bytes of LDS, %u twiddles",
              what, route, (unsigned long long)length, (unsigned long long)s->n_fft, (unsigned long long)s->col0, (unsigned long long)s->pad, pad,
              det, bins, kern, (unsigned long long)s->batch, (unsigned long long)s->frames, (unsigned long long)pl.rows, pl.n, sched, pl.lpf,
-             pl.fy, pl.cpl, (unsigned long long)pl.groups, (unsigned long long)pl.grid, kFftBlock, pl.lds_bytes, pl.fold,
-             BHW_WELCH_FFT_CHUNK, (unsigned long long)wp.runs, (unsigned long long)wp.run, wp.gpr, wp.gpr == 1 ? "" : "s", wp.acc,
-             wp.acc == 1 ? "" : "s", (unsigned long long)wp.chunks, (unsigned long long)wp.blocks, wp.blocks == 1 ? "" : "s", join,
-             wp.blocks == 1 ? "once (chunks)" : "twice (chunks, blocks)", (unsigned long long)wp.ws_bytes, tail);
+             pl.fy, pl.cpl, (unsigned long long)pl.groups, (unsigned long long)pl.grid, kFftBlock, pl.lds_bytes, pl.fold);
+    describe_runs_tail(buf, len, wp, join, tail);
     return BHW_OK;
 }
 
@@ -2769,78 +2710,24 @@ int bhwp_welch_mfft_checks(const bhw_params *p, uint64_t length, const bhw_stft 
 {
     // 1. the input side: the forward call's checks for the descriptor with packed output strides (no spectrum is written here) and no
     //    bank.  BHW_MFFT_POWER is a flag that call knows: it passes here and is refused below.
-    bhw_stft t{};
-    const bool sized = s && s->struct_size == sizeof(bhw_stft);
-    if (sized) {
-        t = *s;
-        t.y_stride = t.y_batch_stride = 0;
-    }
-    int rc = bhwp_stft_mfft_checks(p, length, sized ? &t : s, flags, nullptr, nullptr, nullptr, false);
+    bhw_stft t;
+    const bhw_stft *packed = packed_strides(s, t);
+    int rc = bhwp_stft_mfft_checks(p, length, packed, flags, nullptr, nullptr, nullptr, false);
     if (rc) return rc;
     // 2.
     if (flags & BHW_MFFT_POWER)
         return bhwp_fail(BHW_ERR_BADARG, "flags 0x%x: BHW_MFFT_POWER has no meaning here (BHW_WELCH_DETREND_CONSTANT)", flags);
-    if (s->y_stride || s->y_batch_stride)
-        return bhwp_fail(BHW_ERR_BADARG, "y_stride %llu, y_batch_stride %llu: no spectrum is written, both must be 0",
-                         (unsigned long long)s->y_stride, (unsigned long long)s->y_batch_stride);
-    if (psd_flags & ~BHW_PSD_ONESIDED) return bhwp_fail(BHW_ERR_BADARG, "psd_flags 0x%x (0 or BHW_PSD_ONESIDED)", psd_flags);
-    if (!(scale - scale == 0.0)) return bhwp_fail(BHW_ERR_BADARG, "scale is not finite");
-    // 3., 4., 5.
-    const uint64_t T = s->samples, F = s->frames, K = s->n_fft / 2 + 1;
-    if (!F) return BHW_OK;
-    if (p_stride && p_stride < K)
-        return bhwp_fail(BHW_ERR_BADARG, "p_stride %llu < bins %llu: rows overlap", (unsigned long long)p_stride, (unsigned long long)K);
-    const uint64_t chunks = (F - 1) / BHW_WELCH_FFT_CHUNK + 1;
-    if ((unsigned __int128)s->batch * chunks * K > (1ull << 34))
-        return bhwp_fail(BHW_ERR_BADARG, "batch * ceil(frames / %u) * K above 2^34 per call", BHW_WELCH_FFT_CHUNK);
-    if (!pointers) return BHW_OK;
-    // 6., 7.
-    if (!d_x || !d_P) return bhwp_fail(BHW_ERR_BADARG, "d_x / d_P is NULL");
-    if ((uintptr_t)d_P % 4) return bhwp_fail(BHW_ERR_BADARG, "d_P is not 4-byte aligned");
-    if ((uintptr_t)d_x % 4) return bhwp_fail(BHW_ERR_BADARG, "d_x is not 4-byte aligned");
-    const uint64_t need = bhwp_welch_mfft_workspace_bytes(s);
-    if (!workspace) return bhwp_fail(BHW_ERR_BADARG, "workspace is NULL: the chunk sums need %llu bytes", (unsigned long long)need);
-    if ((uintptr_t)workspace % 8) return bhwp_fail(BHW_ERR_BADARG, "workspace is not 8-byte aligned");
-    if (workspace_bytes < need)
-        return bhwp_fail(BHW_ERR_WORKSPACE, "workspace of %llu bytes, the chunk and block sums need %llu", (unsigned long long)workspace_bytes,
-                         (unsigned long long)need);
-    // 8.
-    const uint64_t xs = s->x_stride ? s->x_stride : T, ps = p_stride ? p_stride : K;
-    const unsigned __int128 xe = (unsigned __int128)(s->batch - 1) * xs + T, pe = (unsigned __int128)(s->batch - 1) * ps + K;
-    if (xe > (1ull << 60) || pe > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "x or P extent beyond 2^60 elements");
-    const uint64_t xa = (uint64_t)(uintptr_t)d_x, pa = (uint64_t)(uintptr_t)d_P, wa = (uint64_t)(uintptr_t)workspace;
-    const uint64_t xb = (uint64_t)xe * 4u, pb = (uint64_t)pe * 4u;
-    if (xa > UINT64_MAX - xb || pa > UINT64_MAX - pb || wa > UINT64_MAX - need)
-        return bhwp_fail(BHW_ERR_BADARG, "x, P or workspace range wraps the address space");
-    if (xa < pa + pb && pa < xa + xb) return bhwp_fail(BHW_ERR_BADARG, "d_x and d_P overlap");
-    if ((wa < xa + xb && xa < wa + need) || (wa < pa + pb && pa < wa + need))
-        return bhwp_fail(BHW_ERR_BADARG, "workspace overlaps d_x or d_P");
-    return BHW_OK;
+    return welch_output_checks(s, s->n_fft / 2 + 1, 1, "bins", "K", scale, &psd_flags, p_stride, d_x, d_P, workspace, workspace_bytes, pointers);
 }
 
 BhwWelchMfftPlan bhwp_welch_mfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, uint64_t p_stride,
                                       bool from_table)
 {
     BhwWelchMfftPlan pl{};
-    bhw_stft t = *s;
-    t.y_stride = t.y_batch_stride = 0;
+    bhw_stft t;
+    packed_strides(s, t);
     pl.fft = bhwp_stft_mfft_plan(p, length, &t, flags & BHW_WELCH_DETREND_CONSTANT, nullptr, from_table);
-    pl.fft.y_stride = pl.fft.y_bstride = 0;
-    pl.bins = s->n_fft / 2 + 1;
-    const BhwWelchRuns r = bhwp_welch_runs(s->batch, s->frames, pl.fft.fy, pl.bins);
-    pl.run = r.run;
-    pl.gpr = r.gpr;
-    pl.acc = pl.fft.fy >= BHW_WELCH_FFT_CHUNK ? 0u : (uint32_t)((pl.bins + kFftBlock - 1) / kFftBlock);
-    pl.p_stride = p_stride ? p_stride : pl.bins;
-    pl.fpad = r.fpad;
-    pl.chunks = r.chunks;
-    pl.blocks = r.blocks;
-    pl.runs = r.runs;
-    pl.fft.groups = r.groups;
-    pl.fft.grid = r.grid;
-    pl.blocks_grid = r.blocks_grid;
-    pl.join_grid = r.join_grid;
-    pl.ws_bytes = r.ws_bytes;
+    welch_plan_runs(pl, s, s->n_fft / 2 + 1, p_stride);
     return pl;
 }
 
@@ -2865,14 +2752,11 @@ static int describe_mfft_runs(const bhw_params *p, const BhwCordicCfg *ct, uint6
     bhwp_stft_mfft_schedule(pl, sched, sizeof sched);
     snprintf(buf, len, "%s mfft %s (L = %llu, n_fft %llu, col0 %llu, pad %llu %s, %s): %s, %llu signals x %llu frames = %llu rows, "
              "complex FFT of %u points in passes %s + split, %u lanes per row x %u rows per workgroup, %u columns per lane, %llu groups, "
-             "grid %llu x %u lanes, %u bytes of LDS; chunk %u frames, %llu runs of %llu frames (%u group%s per run), %u accumulator%s "
-             "per lane, %llu chunks and %llu block%s per signal, then %s %s, workspace %llu bytes%s",
+             "grid %llu x %u lanes, %u bytes of LDS",
              what, route, (unsigned long long)length, (unsigned long long)s->n_fft, (unsigned long long)s->col0, (unsigned long long)s->pad, pad,
              det, kern, (unsigned long long)s->batch, (unsigned long long)s->frames, (unsigned long long)pl.rows, pl.m, sched, pl.lpf, pl.fy,
-             pl.cpl, (unsigned long long)pl.groups, (unsigned long long)pl.grid, kFftBlock, pl.lds_bytes, BHW_WELCH_FFT_CHUNK,
-             (unsigned long long)wp.runs, (unsigned long long)wp.run, wp.gpr, wp.gpr == 1 ? "" : "s", wp.acc, wp.acc == 1 ? "" : "s",
-             (unsigned long long)wp.chunks, (unsigned long long)wp.blocks, wp.blocks == 1 ? "" : "s", join,
-             wp.blocks == 1 ? "once (chunks)" : "twice (chunks, blocks)", (unsigned long long)wp.ws_bytes, tail);
+             pl.cpl, (unsigned long long)pl.groups, (unsigned long long)pl.grid, kFftBlock, pl.lds_bytes);
+    describe_runs_tail(buf, len, wp, join, tail);
     return BHW_OK;
 }
 
@@ -2945,8 +2829,8 @@ int bhwp_istft_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *
     if (s->struct_size != sizeof(bhw_stft)) return bhwp_fail(BHW_ERR_BADARG, "bhw_stft.struct_size %u != %zu", s->struct_size, sizeof(bhw_stft));
     // what the overlap-add checks, for the same descriptor with packed rows (the input strides mean something else here and are
     // checked below)
-    bhw_stft t = *s;
-    t.y_stride = t.y_batch_stride = 0;
+    bhw_stft t;
+    packed_strides(s, t);
     rc = bhwp_stft_checks(p, length, &t, true, flags, nullptr, nullptr, false);
     if (rc) return rc;
     if (s->channels != 1) return bhwp_fail(BHW_ERR_UNSUPPORTED, "channels %u: the fused inverse FFT gives real output (1)", s->channels);
@@ -3084,8 +2968,8 @@ int bhwp_istft_mfft_checks(const bhw_params *p, uint64_t length, const bhw_stft 
     if (s->struct_size != sizeof(bhw_stft)) return bhwp_fail(BHW_ERR_BADARG, "bhw_stft.struct_size %u != %zu", s->struct_size, sizeof(bhw_stft));
     // what the overlap-add checks, for the same descriptor with packed rows (the input strides mean something else here and are
     // checked below)
-    bhw_stft t = *s;
-    t.y_stride = t.y_batch_stride = 0;
+    bhw_stft t;
+    packed_strides(s, t);
     rc = bhwp_stft_checks(p, length, &t, true, flags, nullptr, nullptr, false);
     if (rc) return rc;
     if (s->channels != 1)
@@ -3199,8 +3083,8 @@ static int iq_inverse_descriptor_checks(const bhw_params *p, uint64_t length, co
     if (rc) return rc;
     if (!s) return bhwp_fail(BHW_ERR_BADARG, "stft descriptor is NULL");
     if (s->struct_size != sizeof(bhw_stft)) return bhwp_fail(BHW_ERR_BADARG, "bhw_stft.struct_size %u != %zu", s->struct_size, sizeof(bhw_stft));
-    bhw_stft t = *s;
-    t.y_stride = t.y_batch_stride = 0;
+    bhw_stft t;
+    packed_strides(s, t);
     rc = bhwp_stft_checks(p, length, &t, true, ola_flags, nullptr, nullptr, false);
     if (rc) return rc;
     // 2.

@@ -481,11 +481,15 @@ int  bhwk_spectrogram_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWi
 // (fy < 16: ceil(K / kFftBlock), at most kWelchFftMaxAcc; fy >= 16: none is carried, a lane sums one (chunk, bin) at a time).
 // Workspace: B * chunks * K chunk sums, then (blocks > 1) B * blocks * K block sums.
 constexpr uint32_t kWelchFftMaxAcc = 9;               // ceil(2049 / 256)
-// The run arithmetic of both fused Welch plans (real and I/Q input), from the batch, the frames, the rows side by side and the bins
-// of an output row: one text for bhwp_welch_fft_plan and bhwp_welch_cfft_plan.  frames 0: everything but run and gpr is 0.
+// The run plan of every fused Welch and hold call (real and I/Q input, both radix families), from the batch, the frames, the rows side
+// by side, the bins of an output row and the caller's p_stride: one text for the four bhwp_welch_*_plan and, with `pairs` for fy,
+// bhwp_csd_fft_plan.  frames 0: everything but bins, p_stride, run, gpr and acc is 0.
 struct BhwWelchRuns {
+    uint64_t bins;        // columns of an output row: K = n_fft / 2 + 1 (real input, one-sided) or n_fft (I/Q, two-sided)
+    uint64_t p_stride;    // resolved (0 -> bins)
     uint64_t run;         // frames of a run: max(BHW_WELCH_FFT_CHUNK, fy)
     uint32_t gpr;         // groups per run: run / fy
+    uint32_t acc;         // accumulators a lane carries over a run: ceil(bins / kFftBlock); 0 for fy >= 16
     uint64_t fpad;        // frames of a signal padded to whole runs
     uint64_t chunks;      // ceil(F / BHW_WELCH_FFT_CHUNK) per signal
     uint64_t blocks;      // ceil(F / BHW_WELCH_BLOCK) per signal
@@ -496,21 +500,10 @@ struct BhwWelchRuns {
     uint64_t join_grid;   // workgroups of the launch that adds the blocks (0 for one block)
     uint64_t ws_bytes;    // 8 * B * bins * (chunks + (blocks > 1 ? blocks : 0)); 0 beyond 2^60
 };
-BhwWelchRuns bhwp_welch_runs(uint64_t batch, uint64_t frames, uint32_t fy, uint64_t bins);
-struct BhwWelchFftPlan {
-    BhwStftFftPlan fft;   // groups = B * fpad / fy, grid = min(runs, kFftMaxGrid); rows = B * frames; the y strides are 0
-    uint64_t bins;        // K = n_fft / 2 + 1
-    uint64_t run;         // frames of a run: max(BHW_WELCH_FFT_CHUNK, fy)
-    uint32_t gpr;         // groups per run: run / fy
-    uint32_t acc;         // accumulators a lane carries (0 for fy >= 16)
-    uint64_t fpad;        // frames of a signal padded to whole runs
-    uint64_t chunks;      // ceil(F / BHW_WELCH_FFT_CHUNK) per signal
-    uint64_t blocks;      // ceil(F / BHW_WELCH_BLOCK) per signal
-    uint64_t runs;        // B * fpad / run
-    uint64_t blocks_grid; // workgroups of the launch that adds the chunks of a block
-    uint64_t join_grid;   // workgroups of the launch that adds the blocks (0 for one block)
-    uint64_t p_stride;    // resolved
-    uint64_t ws_bytes;
+BhwWelchRuns bhwp_welch_runs(uint64_t batch, uint64_t frames, uint32_t fy, uint64_t bins, uint64_t p_stride = 0);
+// A Welch plan IS the run plan (its base: wp.chunks, wp.p_stride, ...) plus the family's forward plan.
+struct BhwWelchFftPlan : BhwWelchRuns {   // bins = K = n_fft / 2 + 1
+    BhwStftFftPlan fft;   // groups = B * fpad / fy and grid = min(runs, kFftMaxGrid) as in the base; rows = B * frames; the y strides are 0
 };
 // Every check of the two calls that needs no table handle, before any HIP call (include/bhw.h).  frames 0 passes with the pointers
 // unchecked; `pointers` false: the describe call.
@@ -692,15 +685,8 @@ int  bhwk_stft_cmfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWin
 // none).  Workspace: B * chunks * n_fft chunk sums, then (blocks > 1) B * blocks * n_fft block sums.
 constexpr uint32_t kWelchCfftMaxAcc = 8;              // 2048 / 256
 constexpr uint32_t kWelchCfftFlags = BHW_WELCH_DETREND_CONSTANT | BHW_CFFT_SHIFT;
-struct BhwWelchCfftPlan {
-    BhwStftCfftPlan fft;  // groups = B * fpad / fy, grid = min(runs, kFftMaxGrid); rows = B * frames; the y strides are 0; power false
-    uint64_t bins;        // n_fft: the estimate is two-sided
-    uint64_t run;
-    uint32_t gpr;
-    uint32_t acc;         // accumulators a lane carries (0 for fy >= 16)
-    uint64_t fpad, chunks, blocks, runs, blocks_grid, join_grid;   // bhwp_welch_runs'
-    uint64_t p_stride;    // resolved
-    uint64_t ws_bytes;
+struct BhwWelchCfftPlan : BhwWelchRuns {  // bins = n_fft: the estimate is two-sided
+    BhwStftCfftPlan fft;  // groups and grid as in the base; rows = B * frames; the y strides are 0; power false
 };
 // Every check of the two calls that needs no table handle, before any HIP call and in the order of include/bhw.h.  frames 0 passes
 // with the pointers unchecked; `pointers` false: the describe call.
@@ -723,15 +709,8 @@ int  bhwk_welch_cfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWin
 // kFftBlock), at most kWelchCmfftMaxAcc; fy >= 16: none).  Workspace: B * chunks * n_fft chunk sums, then (blocks > 1) B * blocks *
 // n_fft block sums.  The flags are kWelchCfftFlags.
 constexpr uint32_t kWelchCmfftMaxAcc = 8;             // ceil(2025 / 256)
-struct BhwWelchCmfftPlan {
-    BhwStftCmfftPlan fft; // groups = B * fpad / fy, grid = min(runs, kFftMaxGrid); rows = B * frames; the y strides are 0; power false
-    uint64_t bins;        // n_fft: the estimate is two-sided
-    uint64_t run;
-    uint32_t gpr;
-    uint32_t acc;         // accumulators a lane carries (0 for fy >= 16)
-    uint64_t fpad, chunks, blocks, runs, blocks_grid, join_grid;   // bhwp_welch_runs'
-    uint64_t p_stride;    // resolved
-    uint64_t ws_bytes;
+struct BhwWelchCmfftPlan : BhwWelchRuns { // bins = n_fft: the estimate is two-sided
+    BhwStftCmfftPlan fft; // groups and grid as in the base; rows = B * frames; the y strides are 0; power false
 };
 // Every check of the two calls that needs no table handle, before any HIP call and in the order of include/bhw.h: the checks of
 // bhwp_stft_cmfft_checks, then the output side of bhwp_welch_cfft_checks (one text for both).  frames 0 passes with the pointers
@@ -798,15 +777,8 @@ int  bhwk_hold_cmfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWin
 // (fy < 16: ceil(K / kFftBlock), at most kWelchMfftMaxAcc; fy >= 16: none).  Workspace: B * chunks * K chunk sums, then (blocks > 1)
 // B * blocks * K block sums.
 constexpr uint32_t kWelchMfftMaxAcc = 8;              // ceil(2026 / 256): n_fft 4050
-struct BhwWelchMfftPlan {
-    BhwStftMfftPlan fft;  // groups = B * fpad / fy, grid = min(runs, kFftMaxGrid); rows = B * frames; the y strides are 0
-    uint64_t bins;        // K = n_fft / 2 + 1: the estimate is one-sided
-    uint64_t run;
-    uint32_t gpr;
-    uint32_t acc;         // accumulators a lane carries (0 for fy >= 16)
-    uint64_t fpad, chunks, blocks, runs, blocks_grid, join_grid;   // bhwp_welch_runs'
-    uint64_t p_stride;    // resolved
-    uint64_t ws_bytes;
+struct BhwWelchMfftPlan : BhwWelchRuns {  // bins = K = n_fft / 2 + 1: the estimate is one-sided
+    BhwStftMfftPlan fft;  // groups and grid as in the base; rows = B * frames; the y strides are 0; form BHWP_MFFT_SPECTRUM
 };
 // Every check of the two calls that needs no table handle, before any HIP call and in the order of include/bhw.h.  frames 0 passes
 // with the pointers unchecked; `pointers` false: the describe call.

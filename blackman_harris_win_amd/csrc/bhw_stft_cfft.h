@@ -40,9 +40,39 @@ struct CfftIo {
     uint32_t power, binshift, vec;
 };
 
-extern __shared__ __attribute__((aligned(16))) unsigned char cfft_lds[];
+// The Io of a launch from the plan and the descriptor; the Welch and hold plans carry zero y strides and power false.
+inline CfftIo cfft_io(const BhwStftCfftPlan &pl, const bhw_stft *s, const float *d_x, float *d_Y)
+{
+    CfftIo a;
+    a.x = d_x;
+    a.Y = d_Y;
+    a.rows = pl.rows;
+    a.frames = s->frames;
+    a.hop = s->hop;
+    a.samples = s->samples;
+    a.pad = s->pad;
+    a.x_stride = pl.x_stride;
+    a.y_stride = pl.y_stride;
+    a.y_bstride = pl.y_bstride;
+    a.groups = pl.groups;
+    a.n = pl.n;
+    a.col0 = (uint32_t)s->col0;
+    a.len = (uint32_t)pl.len;
+    a.lpf = pl.lpf;
+    a.fy = pl.fy;
+    a.cpl = pl.cpl;
+    a.radix4 = pl.radix4;
+    a.radix2 = pl.radix2;
+    a.shift = s->shift;
+    a.reflect = s->pad_mode == BHW_PAD_REFLECT ? 1u : 0u;
+    a.detrend = pl.detrend ? 1u : 0u;
+    a.power = pl.power ? 1u : 0u;
+    a.binshift = pl.shifted ? 1u : 0u;
+    a.vec = iq_vec(d_x, s->batch, pl.x_stride);
+    return a;
+}
 
-__device__ __forceinline__ float cfft_coeff(int32_t w, uint32_t shift) { return ldexpf((float)w, -(int)shift); }
+extern __shared__ __attribute__((aligned(16))) unsigned char cfft_lds[];
 
 __device__ __forceinline__ cfft_v2f cmul(cfft_v2f a, cfft_v2f w) { return cfft_v2f{a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x}; }
 

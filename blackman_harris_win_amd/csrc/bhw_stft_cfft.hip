@@ -24,7 +24,7 @@ __global__ __launch_bounds__(kFftBlock) void k_stft_cfft_direct(BhwCordicCfg cfg
             int32_t w;
             if constexpr (FORM == 2) w = direct_coeff_mad_ph(cfg, win, lut_s, len_theta_of(lp, k));
             else                     w = direct_coeff_ph<T>(cfg, win, lut_s, len_theta_of(lp, k));
-            v = cfft_coeff(w, a.shift);
+            v = fft_coeff(w, a.shift);
         }
         vbuf[j] = v;
     }
@@ -44,7 +44,7 @@ __global__ __launch_bounds__(kFftBlock) void k_stft_cfft_table(BhwCordicCfg cfg,
         const uint32_t k = j - a.col0;
         const bool in = j < a.n && k < a.len;
         const int32_t w = range_coeff_ph<FMT, NT, MODE>(cfg, win, table, len_theta_of(lp, in ? k : 0u));
-        if (j < a.n) vbuf[j] = in ? cfft_coeff(w, a.shift) : 0.0f;
+        if (j < a.n) vbuf[j] = in ? fft_coeff(w, a.shift) : 0.0f;
     }
     __syncthreads();
     stft_cfft_rows(a, CfftStore{});
@@ -57,44 +57,11 @@ int bhwk_stft_cfft_f32(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWi
 {
     if (!pl.rows) return 0;
     hipStream_t st = (hipStream_t)l.stream;
-    CfftIo a;
-    a.x = d_x;
-    a.Y = d_Y;
-    a.rows = pl.rows;
-    a.frames = s->frames;
-    a.hop = s->hop;
-    a.samples = s->samples;
-    a.pad = s->pad;
-    a.x_stride = pl.x_stride;
-    a.y_stride = pl.y_stride;
-    a.y_bstride = pl.y_bstride;
-    a.groups = pl.groups;
-    a.n = pl.n;
-    a.col0 = (uint32_t)s->col0;
-    a.len = (uint32_t)pl.len;
-    a.lpf = pl.lpf;
-    a.fy = pl.fy;
-    a.cpl = pl.cpl;
-    a.radix4 = pl.radix4;
-    a.radix2 = pl.radix2;
-    a.shift = s->shift;
-    a.reflect = s->pad_mode == BHW_PAD_REFLECT ? 1u : 0u;
-    a.detrend = pl.detrend ? 1u : 0u;
-    a.power = pl.power ? 1u : 0u;
-    a.binshift = pl.shifted ? 1u : 0u;
-    // one 8-byte load per complex sample where every sample is 8-byte aligned, as the frames kernel's io 2
-    a.vec = ((uintptr_t)d_x % 8 == 0 && (s->batch == 1 || pl.x_stride % 2 == 0)) ? 1u : 0u;
+    const CfftIo a = cfft_io(pl, s, d_x, d_Y);
     const dim3 grid((unsigned)pl.grid), block(kFftBlock);
-    if (!d_table) {
-        with_int_or_last<2, 1, 0>(direct_form(c_in), [&](auto D) { launch_lds(k_stft_cfft_direct<D>, grid, block, pl.lds_bytes, st, c_in, w, a, lp); });
-        return finish(hipSuccess);
-    }
-    const BhwCordicCfg c = table_layout(c_in);
-    int fmt, nt, mode;
-    if (!bhwp_range_form(c, w, &fmt, &nt, &mode)) return (int)hipErrorInvalidValue;
-    const void *tab = (const void *)d_table;
-    with_range_form(fmt, nt, mode, [&](auto F, auto NT, auto M) {
-        launch_lds(k_stft_cfft_table<F, NT, M>, grid, block, pl.lds_bytes, st, c, w, tab, a, lp);
-    });
-    return finish(hipSuccess);
+    return with_window_source(
+        c_in, w, d_table, [&](auto D) { launch_lds(k_stft_cfft_direct<D>, grid, block, pl.lds_bytes, st, c_in, w, a, lp); },
+        [&](auto F, auto NT, auto M, const BhwCordicCfg &c, const void *tab) {
+            launch_lds(k_stft_cfft_table<F, NT, M>, grid, block, pl.lds_bytes, st, c, w, tab, a, lp);
+        });
 }

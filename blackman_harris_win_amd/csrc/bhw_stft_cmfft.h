@@ -38,6 +38,39 @@ struct CmfftIo {
     uint32_t power, binshift, vec;
 };
 
+// The Io of a launch from the plan and the descriptor; the Welch and hold plans carry zero y strides and power false.
+inline CmfftIo cmfft_io(const BhwStftCmfftPlan &pl, const bhw_stft *s, const float *d_x, float *d_Y)
+{
+    CmfftIo a{};
+    a.x = d_x;
+    a.Y = d_Y;
+    a.rows = pl.rows;
+    a.frames = s->frames;
+    a.hop = s->hop;
+    a.samples = s->samples;
+    a.pad = s->pad;
+    a.x_stride = pl.x_stride;
+    a.y_stride = pl.y_stride;
+    a.y_bstride = pl.y_bstride;
+    a.groups = pl.groups;
+    a.n = pl.n;
+    a.fold = pl.fold;
+    a.col0 = (uint32_t)s->col0;
+    a.len = (uint32_t)pl.len;
+    a.lpf = pl.lpf;
+    a.fy = pl.fy;
+    a.cpl = pl.cpl;
+    a.passes = pl.passes;
+    for (uint32_t p = 0; p < pl.passes; ++p) a.sched |= (uint32_t)pl.radix[p] << (4u * p);
+    a.shift = s->shift;
+    a.reflect = s->pad_mode == BHW_PAD_REFLECT ? 1u : 0u;
+    a.detrend = pl.detrend ? 1u : 0u;
+    a.power = pl.power ? 1u : 0u;
+    a.binshift = pl.shifted ? 1u : 0u;
+    a.vec = iq_vec(d_x, s->batch, pl.x_stride);
+    return a;
+}
+
 // What happens to a transformed row is the epilogue, a template parameter of the row function.  CmfftStore, the epilogue of
 // bhw_stft_cmfft_f32_*, is a tag: its text stands in the row function itself under `if constexpr`, as in both parents.
 //

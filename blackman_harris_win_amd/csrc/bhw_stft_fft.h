@@ -39,9 +39,37 @@ struct FftIo {
     uint32_t shift, reflect, detrend;
 };
 
-extern __shared__ __attribute__((aligned(16))) unsigned char fft_lds[];
+// The Io of a launch from the plan and the descriptor; the Welch, hold and csd plans carry zero y strides.
+inline FftIo fft_io(const BhwStftFftPlan &pl, const bhw_stft *s, const float *d_x, float *d_Y)
+{
+    FftIo a;
+    a.x = d_x;
+    a.Y = d_Y;
+    a.rows = pl.rows;
+    a.frames = s->frames;
+    a.hop = s->hop;
+    a.samples = s->samples;
+    a.pad = s->pad;
+    a.x_stride = pl.x_stride;
+    a.y_stride = pl.y_stride;
+    a.y_bstride = pl.y_bstride;
+    a.groups = pl.groups;
+    a.n_fft = (uint32_t)s->n_fft;
+    a.m = pl.m;
+    a.col0 = (uint32_t)s->col0;
+    a.len = (uint32_t)pl.len;
+    a.lpf = pl.lpf;
+    a.fy = pl.fy;
+    a.cpl = pl.cpl;
+    a.radix4 = pl.radix4;
+    a.radix2 = pl.radix2;
+    a.shift = s->shift;
+    a.reflect = s->pad_mode == BHW_PAD_REFLECT ? 1u : 0u;
+    a.detrend = pl.detrend ? 1u : 0u;
+    return a;
+}
 
-__device__ __forceinline__ float fft_coeff(int32_t w, uint32_t shift) { return ldexpf((float)w, -(int)shift); }
+extern __shared__ __attribute__((aligned(16))) unsigned char fft_lds[];
 
 __device__ __forceinline__ fft_v2f cmul(fft_v2f a, fft_v2f w) { return fft_v2f{a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x}; }
 

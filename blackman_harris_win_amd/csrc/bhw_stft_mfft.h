@@ -39,6 +39,38 @@ struct MfftIo {
     uint32_t filters, weights;
 };
 
+// The Io of a launch from the plan and the descriptor, without a bank (bhwk_stft_mfft_f32 adds it); the Welch and hold plans
+// carry zero y strides and form BHWP_MFFT_SPECTRUM.
+inline MfftIo mfft_io(const BhwStftMfftPlan &pl, const bhw_stft *s, const float *d_x, float *d_Y)
+{
+    MfftIo a{};
+    a.x = d_x;
+    a.Y = d_Y;
+    a.rows = pl.rows;
+    a.frames = s->frames;
+    a.hop = s->hop;
+    a.samples = s->samples;
+    a.pad = s->pad;
+    a.x_stride = pl.x_stride;
+    a.y_stride = pl.y_stride;
+    a.y_bstride = pl.y_bstride;
+    a.groups = pl.groups;
+    a.n_fft = (uint32_t)s->n_fft;
+    a.m = pl.m;
+    a.col0 = (uint32_t)s->col0;
+    a.len = (uint32_t)pl.len;
+    a.lpf = pl.lpf;
+    a.fy = pl.fy;
+    a.cpl = pl.cpl;
+    a.passes = pl.passes;
+    for (uint32_t p = 0; p < pl.passes; ++p) a.sched |= (uint32_t)pl.radix[p] << (4u * p);
+    a.shift = s->shift;
+    a.reflect = s->pad_mode == BHW_PAD_REFLECT ? 1u : 0u;
+    a.detrend = pl.detrend ? 1u : 0u;
+    a.form = pl.form;
+    return a;
+}
+
 // W at index idx < n_fft (table of M = n_fft / 2 entries, W[idx + M] = -W[idx]); M is no power of two: a compare, not a mask
 __device__ __forceinline__ fft_v2f mfft_twiddle(const fft_v2f *tw, uint32_t idx, uint32_t M)
 {

@@ -57,31 +57,7 @@ int bhwk_stft_mfft_f32(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWi
 {
     if (!pl.rows) return 0;
     hipStream_t st = (hipStream_t)l.stream;
-    MfftIo a{};
-    a.x = d_x;
-    a.Y = d_out;
-    a.rows = pl.rows;
-    a.frames = s->frames;
-    a.hop = s->hop;
-    a.samples = s->samples;
-    a.pad = s->pad;
-    a.x_stride = pl.x_stride;
-    a.y_stride = pl.y_stride;
-    a.y_bstride = pl.y_bstride;
-    a.groups = pl.groups;
-    a.n_fft = (uint32_t)s->n_fft;
-    a.m = pl.m;
-    a.col0 = (uint32_t)s->col0;
-    a.len = (uint32_t)pl.len;
-    a.lpf = pl.lpf;
-    a.fy = pl.fy;
-    a.cpl = pl.cpl;
-    a.passes = pl.passes;
-    for (uint32_t p = 0; p < pl.passes; ++p) a.sched |= (uint32_t)pl.radix[p] << (4u * p);
-    a.shift = s->shift;
-    a.reflect = s->pad_mode == BHW_PAD_REFLECT ? 1u : 0u;
-    a.detrend = pl.detrend ? 1u : 0u;
-    a.form = pl.form;
+    MfftIo a = mfft_io(pl, s, d_x, d_out);
     if (pl.form == BHWP_MFFT_BANK) {
         if (!bank) return (int)hipErrorInvalidValue;
         a.first = bank->d_first;
@@ -91,16 +67,9 @@ int bhwk_stft_mfft_f32(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWi
         a.weights = bank->weights;
     }
     const dim3 grid((unsigned)pl.grid), block(kFftBlock);
-    if (!d_table) {
-        with_int_or_last<2, 1, 0>(direct_form(c_in), [&](auto D) { launch_lds(k_stft_mfft_direct<D>, grid, block, pl.lds_bytes, st, c_in, w, a, lp); });
-        return finish(hipSuccess);
-    }
-    const BhwCordicCfg c = table_layout(c_in);
-    int fmt, nt, mode;
-    if (!bhwp_range_form(c, w, &fmt, &nt, &mode)) return (int)hipErrorInvalidValue;
-    const void *tab = (const void *)d_table;
-    with_range_form(fmt, nt, mode, [&](auto F, auto NT, auto M) {
-        launch_lds(k_stft_mfft_table<F, NT, M>, grid, block, pl.lds_bytes, st, c, w, tab, a, lp);
-    });
-    return finish(hipSuccess);
+    return with_window_source(
+        c_in, w, d_table, [&](auto D) { launch_lds(k_stft_mfft_direct<D>, grid, block, pl.lds_bytes, st, c_in, w, a, lp); },
+        [&](auto F, auto NT, auto M, const BhwCordicCfg &c, const void *tab) {
+            launch_lds(k_stft_mfft_table<F, NT, M>, grid, block, pl.lds_bytes, st, c, w, tab, a, lp);
+        });
 }
