@@ -11,6 +11,7 @@ import blackman_harris_win_amd as bhw
 from blackman_harris_win_amd import binding as B
 
 import oracle_lib as O
+from len_bit_model import combine, full_cos, model_window, thetas  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -38,63 +39,7 @@ def _valid(p):
     return B.lib().bhw_params_validate(ctypes.byref(p)) == 0
 
 
-# ---- the bit model, restated ----------------------------------------------------------------------------------------------------
-
-def thetas(L, P, n, K):
-    """theta_k(n) for k = 1..K-1 in Python integers: round(((k * (n mod L)) mod L) * 2^P / L) mod 2^P."""
-    m = np.asarray(n, dtype=np.uint64) % np.uint64(L)                  # L <= 2^30: every product below stays inside 64 bits
-    out = []
-    for k in range(1, K):
-        mk = (m * np.uint64(k)) % np.uint64(L)
-        q = ((mk << np.uint64(P + 1)) + np.uint64(L)) // np.uint64(2 * L)
-        out.append((q % np.uint64(1 << P)).astype(np.int64))
-    return out
-
-
-def _wrap(v, bits):
-    return ((v + (1 << (bits - 1))) % (1 << bits)) - (1 << (bits - 1))
-
-
-def combine(p, cos_k):
-    """The cosine-sum of the configured rule (HLS: truncating, VHDL: per-product and final rounding) over the cosines of harmonics
-    1..K-1, in int64 NumPy."""
-    W, K = p.dat_width, p.n_terms
-    acc = np.full(cos_k[0].shape, int(p.aa[0]), dtype=np.int64)
-    for k in range(1, K):
-        m = (int(p.aa[k]) * cos_k[k - 1].astype(np.int64)) >> (W - 2)
-        if p.combine == B.COMBINE_VHDL:
-            r = _wrap(m, W + 1)
-            m = _wrap((r >> 1) + (r & 1), W)
-        acc = acc - m if k & 1 else acc + m
-    if p.combine == B.COMBINE_VHDL:
-        if K == 2:
-            S = _wrap(acc, W + 1)
-            acc = (S >> 1) + (S & 1)
-        else:
-            S = _wrap(acc, W + 2)
-            acc = (S >> 2) + ((S >> 1) & 1)
-    return _wrap(acc, W).astype(np.int32)
-
-
-_cos_cache = {}
-
-
-def full_cos(p, source="oracle"):
-    """cos over the full circle of 2^phi_width angles: the oracle's model, or the reference's compiled cordic() (model CPP)."""
-    key = (source, p.model, p.phi_width, p.dat_width, p.precision)
-    if key not in _cos_cache:
-        if source == "oracle":
-            _cos_cache[key] = O.sincos(O.from_bhw(p), 0, 1 << p.phi_width)[1]
-        else:
-            lib = [f for P, W, f in O.ref_pairs() if P == p.phi_width and W == p.dat_width]
-            _cos_cache[key] = O.RefCordic(lib[0]).sweep(range(1 << p.phi_width))[1]
-    return _cos_cache[key]
-
-
-def model_window(p, L, n, source="oracle"):
-    c = full_cos(p, source)
-    return combine(p, [c[t] for t in thetas(L, p.phi_width, n, p.n_terms)])
-
+# ---- the bit model, restated: len_bit_model.py (shared with test_gpu_table_source.py) ------------------------------------------------------
 
 def _gen(p, L, n0, count):
     return bhw.generate(p, n0, count, length=L).cpu().numpy()
@@ -276,10 +221,12 @@ def test_overlap_add_is_the_transpose_of_frames(torch, L, hop):
 FORMATS = (B.TABLE_PLAIN, B.TABLE_DELTA16, B.TABLE_RESIDUAL, B.TABLE_NIBBLE, B.TABLE_NIBBLE_ESC)
 
 
-@pytest.mark.parametrize("P,model", [(16, B.MODEL_HLS), (16, B.MODEL_VHDL), (22, B.MODEL_CPP)])
-def test_from_table_equals_library_in_every_format(torch, P, model):
-    p = B.make_params(B.WIN_BH7, P, 32, model=model)
-    q = B.make_params(B.WIN_BH4, P, 32, model=model, combine=B.COMBINE_VHDL)
+@pytest.mark.parametrize("P,model,W", [(16, B.MODEL_HLS, 32), (16, B.MODEL_VHDL, 32), (22, B.MODEL_CPP, 32), (22, B.MODEL_CPP, 25)],
+                         ids=[f"16-{B.MODEL_HLS}", f"16-{B.MODEL_VHDL}", f"22-{B.MODEL_CPP}", f"22-{B.MODEL_CPP}-w25"])
+def test_from_table_equals_library_in_every_format(torch, P, model, W):
+    """W 32: the tables of these phase widths are plain under every limit.  cpp 22 / 25 takes the packed formats."""
+    p = B.make_params(B.WIN_BH7, P, W, model=model)
+    q = B.make_params(B.WIN_BH4, P, W, model=model, combine=B.COMBINE_VHDL)
     rng = np.random.default_rng(P)
     hop, frames = 160, 64
     xh = rng.integers(-2 ** 31, 2 ** 31, size=(frames - 1) * hop + 1000, dtype=np.int64).astype(np.int32)
@@ -289,6 +236,7 @@ def test_from_table_equals_library_in_every_format(torch, P, model):
     want = {(id(pp), L): bhw.generate(pp, 5, L + 300, length=L) for pp in (p, q) for L in lens}
     want_f = {id(pp): bhw.apply_frames(pp, x, hop, shift=31, length=1000) for pp in (p, q)}
     want_o = {id(pp): bhw.overlap_add(pp, y, hop, shift=31, length=1000) for pp in (p, q)}
+    seen = set()
     for fmt in FORMATS:
         with bhw.ResidentTable(p, table_format=fmt) as t:
             for pp in (p, q):
@@ -300,6 +248,9 @@ def test_from_table_equals_library_in_every_format(torch, P, model):
                 assert "split" in t.describe(p, 0, 1 << P) or "nibble" in t.describe(p, 0, 1 << P)
             d = B.describe_len(p, 1000, frames=B.make_frames(frames, hop), table=t.handle)
             assert d.startswith("any-length route") and "k_frames_table_len<" in d, d
+            seen.add(d.split("k_frames_table_len<")[1].split(",")[0])
+    if W < 32:
+        assert len(seen) >= 3, seen
 
 
 def test_from_table_calls_replay_from_a_graph(torch):

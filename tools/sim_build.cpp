@@ -20,12 +20,15 @@
 // Besides the comparison it prints what the rare paths of the kernel see in this configuration: the deferred images of the fullest
 // workgroup (the kernel's worklist bound) and the entries that leave the four-bit fields of the nibble formats (the format the
 // device settles on).
-//   usage: sim_build <model 0 hls | 1 cpp | 2 vhdl> <PW> <W> [precision [tail rotations 6 | 7]]     (exit code 0 = every entry identical)
+//   usage: sim_build [--escapes] <model 0 hls | 1 cpp | 2 vhdl> <PW> <W> [precision [tail rotations 6 | 7]]     (exit code 0 = every entry identical)
+// --escapes adds a last line "listed entries:" with the index u of every entry the nibble + escapes format lists, in ascending order
+// (tools/escape_lengths.py chooses from it the window lengths whose gathers reach such entries).
 #include <quadmath.h>
 
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 static int64_t T2[48], T4[48], G46, G47;
@@ -61,7 +64,14 @@ static void step(int64_t &x, int64_t &y, int64_t &z, int k, int64_t l)
 
 int main(int argc, char **argv)
 {
-    if (argc < 4) { fprintf(stderr, "usage: sim_build model PW W [precision]\n"); return 2; }
+    bool list_escapes = false;
+    for (int i = 1; i < argc; ++i)
+        if (!strcmp(argv[i], "--escapes")) {
+            list_escapes = true;
+            for (int j = i; j + 1 < argc; ++j) argv[j] = argv[j + 1];
+            --argc; --i;
+        }
+    if (argc < 4) { fprintf(stderr, "usage: sim_build [--escapes] model PW W [precision]\n"); return 2; }
     tables();
     const int model = atoi(argv[1]), PW = atoi(argv[2]), W = atoi(argv[3]), P = argc > 4 ? atoi(argv[4]) : 1;
     Cfg c{};
@@ -276,6 +286,7 @@ int main(int argc, char **argv)
     if (dlog < 7 || W + c.out_shr > 34) dlog = 0;                                // no residual cell: not a configuration of the packed formats
     uint64_t nib_out = 0, esc_all = 0;
     uint32_t esc_wg_max = 0;
+    std::vector<uint32_t> esc_u;                                                 // the listed entries (--escapes)
     const uint32_t wg_groups = E >= (1u << 24) ? 256u : 64u;
     if (dlog) {
         std::vector<uint32_t> esc_wg((n_groups + wg_groups - 1) / wg_groups, 0u);
@@ -291,6 +302,7 @@ int main(int argc, char **argv)
             if (ec - 1u > 14u || es > 15u) {
                 const uint32_t src = u < (E >> 1) ? u : u == (E >> 1) ? (E >> 1) - 1u : E - u;   // the own entry whose workgroup stores it
                 ++esc_all;
+                esc_u.push_back(u);
                 ++esc_wg[(src >> 6) / wg_groups];
             }
         }
@@ -309,5 +321,10 @@ int main(int argc, char **argv)
     printf("rank entry J %d: groups %llu of %llu, refused %llu, leaves that differ from the rotations %llu, zero events by threshold %llu | by rotation %llu\n", J,
            (unsigned long long)rank_groups, (unsigned long long)n_groups, (unsigned long long)rank_refused, (unsigned long long)rank_bad,
            (unsigned long long)zero_thr, (unsigned long long)zero_rot);
+    if (list_escapes) {
+        printf("listed entries:");
+        for (uint32_t u : esc_u) printf(" %u", u);
+        printf("\n");
+    }
     return bad || rank_bad || zero_thr != zero_rot ? 1 : 0;
 }
