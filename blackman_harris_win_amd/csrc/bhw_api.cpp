@@ -1339,57 +1339,48 @@ int stft_mfft_run(bhw_table t, const bhw_params *p, uint64_t length, int device,
                                                               const BhwLenPhase *lp) { return bhwk_stft_mfft_f32(l, c, w, pl, s, fb, d_x, d_out, tab, *lp); });
 }
 
-// The fused inverse FFT + overlap-add (t NULL: the direct CORDIC chains): the checks, then the one kernel.
+// The fused inverse FFT + overlap-add of a family (t NULL: the direct CORDIC chains): its checks, then its plan and its one kernel.
+template <auto Checks, auto Plan, auto Launch>
+int istft_run(const char *what, const char *what_table, bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream,
+              const bhw_stft *s, uint32_t flags, const float *d_Y, float *d_x)
+{
+    int rc = Checks(p, length, s, flags, d_Y, d_x, true);
+    if (!rc && t) rc = table_call_checks(t, p);
+    if (rc || !s->samples) return rc;
+    const auto pl = Plan(p, length, s, flags, t != nullptr);
+    return run_source(t, p, length, device, stream, t ? what_table : what,
+                      [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *tab, const BhwLenPhase *lp) {
+                          return Launch(l, c, w, pl, s, d_Y, d_x, tab, *lp);
+                      });
+}
+
+// Real output at a power of two and at a mixed-radix n_fft, I/Q output at a power of two and at a mixed-radix n_fft.
 int istft_fft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *s, uint32_t flags,
                   const float *d_Y, float *d_x)
 {
-    int rc = bhwp_istft_fft_checks(p, length, s, flags, d_Y, d_x);
-    if (!rc && t) rc = table_call_checks(t, p);
-    if (rc || !s->samples) return rc;
-    const BhwIstftFftPlan pl = bhwp_istft_fft_plan(p, length, s, flags, t != nullptr);
-    const char *what = t ? "istft fft launch (resident table)" : "istft fft launch";
-    return run_source(t, p, length, device, stream, what, [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *tab,
-                                                              const BhwLenPhase *lp) { return bhwk_istft_fft_f32(l, c, w, pl, s, d_Y, d_x, tab, *lp); });
+    return istft_run<bhwp_istft_fft_checks, bhwp_istft_fft_plan, bhwk_istft_fft_f32>(
+        "istft fft launch", "istft fft launch (resident table)", t, p, length, device, stream, s, flags, d_Y, d_x);
 }
 
-// The mixed-radix fused inverse FFT + overlap-add (t NULL: the direct CORDIC chains): the checks, then the one kernel.
 int istft_mfft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *s, uint32_t flags,
                    const float *d_Y, float *d_x)
 {
-    int rc = bhwp_istft_mfft_checks(p, length, s, flags, d_Y, d_x);
-    if (!rc && t) rc = table_call_checks(t, p);
-    if (rc || !s->samples) return rc;
-    const BhwIstftMfftPlan pl = bhwp_istft_mfft_plan(p, length, s, flags, t != nullptr);
-    const char *what = t ? "istft mfft launch (resident table)" : "istft mfft launch";
-    return run_source(t, p, length, device, stream, what, [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *tab,
-                                                              const BhwLenPhase *lp) { return bhwk_istft_mfft_f32(l, c, w, pl, s, d_Y, d_x, tab, *lp); });
+    return istft_run<bhwp_istft_mfft_checks, bhwp_istft_mfft_plan, bhwk_istft_mfft_f32>(
+        "istft mfft launch", "istft mfft launch (resident table)", t, p, length, device, stream, s, flags, d_Y, d_x);
 }
 
-// The fused inverse complex FFT + overlap-add for I/Q output (t NULL: the direct CORDIC chains): the checks, then the one kernel.
 int istft_cfft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *s, uint32_t flags,
                    const float *d_Y, float *d_x)
 {
-    int rc = bhwp_istft_cfft_checks(p, length, s, flags, d_Y, d_x);
-    if (!rc && t) rc = table_call_checks(t, p);
-    if (rc || !s->samples) return rc;
-    const BhwIstftCfftPlan pl = bhwp_istft_cfft_plan(p, length, s, flags, t != nullptr);
-    const char *what = t ? "istft cfft launch (resident table)" : "istft cfft launch";
-    return run_source(t, p, length, device, stream, what, [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *tab,
-                                                              const BhwLenPhase *lp) { return bhwk_istft_cfft_f32(l, c, w, pl, s, d_Y, d_x, tab, *lp); });
+    return istft_run<bhwp_istft_cfft_checks, bhwp_istft_cfft_plan, bhwk_istft_cfft_f32>(
+        "istft cfft launch", "istft cfft launch (resident table)", t, p, length, device, stream, s, flags, d_Y, d_x);
 }
 
-// The mixed-radix fused inverse complex FFT + overlap-add for I/Q output (t NULL: the direct CORDIC chains): the checks, then the one
-// kernel.
 int istft_cmfft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *s, uint32_t flags,
                     const float *d_Y, float *d_x)
 {
-    int rc = bhwp_istft_cmfft_checks(p, length, s, flags, d_Y, d_x);
-    if (!rc && t) rc = table_call_checks(t, p);
-    if (rc || !s->samples) return rc;
-    const BhwIstftCmfftPlan pl = bhwp_istft_cmfft_plan(p, length, s, flags, t != nullptr);
-    const char *what = t ? "istft cmfft launch (resident table)" : "istft cmfft launch";
-    return run_source(t, p, length, device, stream, what, [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *tab,
-                                                              const BhwLenPhase *lp) { return bhwk_istft_cmfft_f32(l, c, w, pl, s, d_Y, d_x, tab, *lp); });
+    return istft_run<bhwp_istft_cmfft_checks, bhwp_istft_cmfft_plan, bhwk_istft_cmfft_f32>(
+        "istft cmfft launch", "istft cmfft launch (resident table)", t, p, length, device, stream, s, flags, d_Y, d_x);
 }
 
 // The window sums (t NULL: the direct CORDIC chains): the checks, then the memset of the four words and the reduction.

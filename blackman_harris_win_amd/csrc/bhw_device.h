@@ -874,12 +874,19 @@ thread_local hipError_t t_launch_err = hipSuccess;
 
 template <typename T> struct same_type { using type = T; };
 
+// lds: the bytes of dynamic LDS (the fused FFT fronts: their plan's lds_bytes)
+template <typename... KArgs>
+inline void launch_lds(void (*kernel)(KArgs...), dim3 grid, dim3 block, uint32_t lds, hipStream_t st, typename same_type<KArgs>::type... args)
+{
+    void *ptrs[] = {(void *)&args...};
+    const hipError_t e = hipLaunchKernel(reinterpret_cast<const void *>(kernel), grid, block, ptrs, lds, st);
+    if (e != hipSuccess && t_launch_err == hipSuccess) t_launch_err = e;
+}
+
 template <typename... KArgs>
 inline void launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, hipStream_t st, typename same_type<KArgs>::type... args)
 {
-    void *ptrs[] = {(void *)&args...};
-    const hipError_t e = hipLaunchKernel(reinterpret_cast<const void *>(kernel), grid, block, ptrs, 0, st);
-    if (e != hipSuccess && t_launch_err == hipSuccess) t_launch_err = e;
+    launch_lds(kernel, grid, block, 0u, st, args...);
 }
 
 // The kernel of a front for its phase map: k at L = 2^phi_width or, with lp, k_len (the same parameters, the BhwLenPhase last).
@@ -942,7 +949,8 @@ inline uint32_t pair_io(uint32_t channels, const void *a, const void *b, uint64_
     return channels == 1 ? 0u : (((((uintptr_t)a | (uintptr_t)b) % 8 == 0) && stride % 2 == 0) ? 2u : 1u);
 }
 
-// The `vec` of CfftIo and CmfftIo: one 8-byte load per complex sample where every sample of every signal is 8-byte aligned.
+// The `vec` of CfftIo, CmfftIo, IcfftIo and IcmfftIo: one 8-byte load (the inverse fronts: store) per complex sample where every
+// sample of every signal is 8-byte aligned.
 inline uint32_t iq_vec(const void *d_x, uint64_t batch, uint64_t x_stride)
 {
     return ((uintptr_t)d_x % 8 == 0 && (batch == 1 || x_stride % 2 == 0)) ? 1u : 0u;
@@ -955,7 +963,7 @@ inline int finish(hipError_t e)
     return (int)e;
 }
 
-// Where the window of a fused forward FFT launch comes from: no table -- direct(FORM) for the configuration's direct_form, the
+// Where the window of a fused FFT or float front's launch comes from: no table -- direct(FORM) for the configuration's direct_form, the
 // kernel taking c_in; a resident table -- table(FMT, NT, MODE, c, tab) for the form bhwp_range_form chose, c being the table's
 // layout and tab the table.  Returns the launch status (finish), or hipErrorInvalidValue with nothing launched for a table no range
 // form reads.

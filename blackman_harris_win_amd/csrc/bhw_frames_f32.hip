@@ -86,18 +86,9 @@ int bhwk_frames_f32(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinCf
     a.shift = f->shift;
     a.io = pair_io(f->channels, d_x, d_y, pl.y_stride);
     const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y), block(kFramesBlock);
-    if (!d_table) {
-        with_int_or_last<2, 1, 0>(direct_form(c_in), [&](auto D) {
-            launch_phase(k_frames_f32_direct_len<D>, k_frames_f32_direct<D>, lp, grid, block, st, c_in, w, a);
+    return with_window_source(
+        c_in, w, d_table, [&](auto D) { launch_phase(k_frames_f32_direct_len<D>, k_frames_f32_direct<D>, lp, grid, block, st, c_in, w, a); },
+        [&](auto F, auto NT, auto M, const BhwCordicCfg &c, const void *tab) {
+            launch_phase(k_frames_f32_table_len<F, NT, M>, k_frames_f32_table<F, NT, M>, lp, grid, block, st, c, w, tab, a);
         });
-        return finish(hipSuccess);
-    }
-    const BhwCordicCfg c = table_layout(c_in);
-    int fmt, nt, mode;
-    if (!bhwp_range_form(c, w, &fmt, &nt, &mode)) return (int)hipErrorInvalidValue;
-    const void *tab = (const void *)d_table;
-    with_range_form(fmt, nt, mode, [&](auto F, auto NT, auto M) {
-        launch_phase(k_frames_f32_table_len<F, NT, M>, k_frames_f32_table<F, NT, M>, lp, grid, block, st, c, w, tab, a);
-    });
-    return finish(hipSuccess);
 }

@@ -21,15 +21,14 @@
 // idle once its frames are done.  A row's arithmetic does not depend on its slot, span or grid, and an output's sum takes its rows in
 // ascending f whatever the spans are: the bits of an output are a function of the window, the flags and the rows that reach it.
 //
-// Kept in step by hand: cmul, twiddle and launch_lds restate those of bhw_stft_cfft.hip and bhw_istft_fft.hip (those files and their
-// code objects stay the parent's), and tests/cpp/san_istft_cfft.cpp replays this file's index arithmetic -- the load's point index,
-// the pass indices, the ring's (q - base) mod n and the flush bound `end` -- from a copy of its own, since only bhwp_istft_span is
-// shared through bhw_plan.h.  An edit of any of these here is an edit of the replay too.
-#include "bhw_device.h"
+// Kept in step by hand: the span walk, the ring and the flush stand in all four inverse units (bhw_istft_fft.hip,
+// bhw_istft_mfft.hip, this one, bhw_istft_cmfft.hip), and tests/cpp/san_istft_cfft.cpp replays this file's index arithmetic -- the
+// load's point index, the pass indices, the ring's (q - base) mod n and the flush bound `end` -- from a copy of its own, since only
+// bhwp_istft_span is shared through bhw_plan.h.  An edit of any of these here is an edit of the siblings and of the replay too.
+// cmul, twiddle and the dynamic LDS array are bhw_stft_fft.h's, the Io fill, istft_out and istft_store bhw_istft.h's.
+#include "bhw_istft.h"
 
 namespace {
-
-typedef float icfft_v2f __attribute__((ext_vector_type(2)));
 
 struct IcfftIo {
     const float *Y;
@@ -42,56 +41,26 @@ struct IcfftIo {
     uint32_t shift, normalize, binshift, vec;
 };
 
-extern __shared__ __attribute__((aligned(16))) unsigned char icfft_lds[];
-
-__device__ __forceinline__ float icfft_coeff(int32_t w, uint32_t shift) { return ldexpf((float)w, -(int)shift); }
-
-__device__ __forceinline__ icfft_v2f cmul(icfft_v2f a, icfft_v2f w) { return icfft_v2f{a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x}; }
-
-// W at index idx < n (table of h = n / 2 entries, W[idx + h] = -W[idx])
-__device__ __forceinline__ icfft_v2f twiddle(const icfft_v2f *tw, uint32_t idx, uint32_t h)
-{
-    const icfft_v2f w = tw[idx & (h - 1u)];
-    return (idx & h) ? icfft_v2f{-w.x, -w.y} : w;
-}
-
-__device__ __forceinline__ float icfft_out(double s, double e, uint32_t normalize)
-{
-    if (!normalize) return (float)s;
-    return e > 0.0 ? (float)(s / e) : 0.0f;
-}
-
-// the complex sample at float offset 2 * t of a signal: one 8-byte store on the 8-byte grid, else two 4-byte ones
-__device__ __forceinline__ void icfft_store(float *xb, uint64_t t, icfft_v2f z, uint32_t vec)
-{
-    float *px = xb + 2 * t;
-    if (vec) *(icfft_v2f *)px = z;
-    else {
-        px[0] = z.x;
-        px[1] = z.y;
-    }
-}
-
 // Everything after the prologue's coefficients: vS (behind the twiddles) holds v[0..L).
 __device__ __forceinline__ void istft_cfft_spans(const IcfftIo &a)
 {
     const uint32_t n = a.n, H = n >> 1, Q = n >> 2, lpf = a.lpf, fy = a.fy, L = a.len;
-    icfft_v2f *bufA = (icfft_v2f *)icfft_lds;
-    icfft_v2f *bufB = bufA + (size_t)fy * n;
-    icfft_v2f *tw = bufB + (size_t)fy * n;
+    fft_v2f *bufA = (fft_v2f *)fft_lds;
+    fft_v2f *bufB = bufA + (size_t)fy * n;
+    fft_v2f *tw = bufB + (size_t)fy * n;
     const float *vS = (const float *)(tw + H);
     const uint32_t tid = threadIdx.x;
     const uint32_t slot = tid / lpf, l = tid - slot * lpf;
     for (uint32_t k = tid; k < H; k += kFftBlock) {
         double sn, cs;
         sincospi((double)k * 2.0 / (double)n, &sn, &cs);
-        tw[k] = icfft_v2f{(float)cs, (float)sn};
+        tw[k] = fft_v2f{(float)cs, (float)sn};
     }
     __syncthreads();
     const float scale = 1.0f / (float)n;                                 // a power of two: exact
     const uint64_t pool = a.batch * a.spans, hop = a.hop;
     const uint32_t turn = a.binshift ? H : 0u;
-    const icfft_v2f zero = icfft_v2f{0.0f, 0.0f};
+    const fft_v2f zero = fft_v2f{0.0f, 0.0f};
     double accr[kCfftMaxCpl], acci[kCfftMaxCpl], env[kCfftMaxCpl];
 #pragma unroll
     for (uint32_t c = 0; c < kCfftMaxCpl; ++c) accr[c] = acci[c] = env[c] = 0.0;
@@ -108,9 +77,9 @@ __device__ __forceinline__ void istft_cfft_spans(const IcfftIo &a)
             const uint64_t f = r.f_lo + it;
             const bool act = f < r.f_hi;
             // 1. the load, into the slot's row of buffer A
-            icfft_v2f *src = bufA + (size_t)slot * n, *dst = bufB + (size_t)slot * n;
+            fft_v2f *src = bufA + (size_t)slot * n, *dst = bufB + (size_t)slot * n;
             if (act) {
-                const icfft_v2f *yp = (const icfft_v2f *)(yb + f * a.y_stride);
+                const fft_v2f *yp = (const fft_v2f *)(yb + f * a.y_stride);
 #pragma unroll
                 for (uint32_t c = 0; c < kCfftMaxCpl; ++c) {
                     if (c < a.cpl) {
@@ -126,15 +95,15 @@ __device__ __forceinline__ void istft_cfft_spans(const IcfftIo &a)
                 const uint32_t ts = n / (4u * Ns);
                 for (uint32_t i = l; i < Q; i += lpf) {
                     const uint32_t k = i & (Ns - 1u);
-                    icfft_v2f a0 = src[i], a1 = src[i + Q], a2 = src[i + 2u * Q], a3 = src[i + 3u * Q];
+                    fft_v2f a0 = src[i], a1 = src[i + Q], a2 = src[i + 2u * Q], a3 = src[i + 3u * Q];
                     if (Ns > 1u) {
                         const uint32_t kt = k * ts;
                         a1 = cmul(a1, twiddle(tw, kt, H));
                         a2 = cmul(a2, twiddle(tw, 2u * kt, H));
                         a3 = cmul(a3, twiddle(tw, 3u * kt, H));
                     }
-                    const icfft_v2f t0 = a0 + a2, t1 = a0 - a2, t2 = a1 + a3;
-                    const icfft_v2f t3 = icfft_v2f{a3.y - a1.y, a1.x - a3.x};   // +i (a1 - a3)
+                    const fft_v2f t0 = a0 + a2, t1 = a0 - a2, t2 = a1 + a3;
+                    const fft_v2f t3 = fft_v2f{a3.y - a1.y, a1.x - a3.x};   // +i (a1 - a3)
                     const uint32_t o = ((i - k) << 2) + k;
                     dst[o] = t0 + t2;
                     dst[o + Ns] = t1 + t3;
@@ -142,28 +111,28 @@ __device__ __forceinline__ void istft_cfft_spans(const IcfftIo &a)
                     dst[o + 3u * Ns] = t1 - t3;
                 }
                 __syncthreads();
-                icfft_v2f *sw = src;
+                fft_v2f *sw = src;
                 src = dst;
                 dst = sw;
                 Ns <<= 2;
             }
             if (a.radix2) {                                              // Ns = n / 2: k = i, twiddle W[i]
                 for (uint32_t i = l; i < H; i += lpf) {
-                    const icfft_v2f a0 = src[i], a1 = cmul(src[i + H], tw[i]);
+                    const fft_v2f a0 = src[i], a1 = cmul(src[i + H], tw[i]);
                     dst[i] = a0 + a1;
                     dst[i + H] = a0 - a1;
                 }
                 __syncthreads();
-                icfft_v2f *sw = src;
+                fft_v2f *sw = src;
                 src = dst;
                 dst = sw;
             }
             // 3. and 4.: the ring
             if (act) {
-                const icfft_v2f *row = src + a.col0;
+                const fft_v2f *row = src + a.col0;
                 const uint64_t base = f * hop;
                 if (cur < base) {                                        // a gap no frame reaches (hop > L, or the span's start)
-                    for (uint64_t w = cur + l; w < base; w += lpf) icfft_store(xb, w - a.t0, zero, a.vec);
+                    for (uint64_t w = cur + l; w < base; w += lpf) istft_store(xb, w - a.t0, zero, a.vec);
                     cur = base;
                 }
                 uint64_t end = (f + 1 == r.f_hi || base + hop > r.whi) ? r.whi : base + hop;
@@ -176,13 +145,13 @@ __device__ __forceinline__ void istft_cfft_spans(const IcfftIo &a)
                         const uint64_t w = base + k;
                         if (k < L && w >= cur && w < r.whi) {
                             const double v = (double)vS[k];
-                            const icfft_v2f z = row[k];
+                            const fft_v2f z = row[k];
                             accr[c] += (double)(z.x * scale) * v;
                             acci[c] += (double)(z.y * scale) * v;
                             env[c] += v * v;
                             if (w < end) {
-                                icfft_store(xb, w - a.t0,
-                                            icfft_v2f{icfft_out(accr[c], env[c], a.normalize), icfft_out(acci[c], env[c], a.normalize)}, a.vec);
+                                istft_store(xb, w - a.t0,
+                                            fft_v2f{istft_out(accr[c], env[c], a.normalize), istft_out(acci[c], env[c], a.normalize)}, a.vec);
                                 accr[c] = acci[c] = env[c] = 0.0;
                             }
                         }
@@ -190,13 +159,13 @@ __device__ __forceinline__ void istft_cfft_spans(const IcfftIo &a)
                 }
                 const uint64_t reach = base + L;                         // the frame's extent: beyond it up to `end` nothing is summed
                 if (reach < end)
-                    for (uint64_t w = (reach > cur ? reach : cur) + l; w < end; w += lpf) icfft_store(xb, w - a.t0, zero, a.vec);
+                    for (uint64_t w = (reach > cur ? reach : cur) + l; w < end; w += lpf) istft_store(xb, w - a.t0, zero, a.vec);
                 cur = end;
             }
             __syncthreads();                                             // the next round overwrites both buffers
         }
         if (live)
-            for (uint64_t w = cur + l; w < r.whi; w += lpf) icfft_store(xb, w - a.t0, zero, a.vec);   // no frame, or past the last one
+            for (uint64_t w = cur + l; w < r.whi; w += lpf) istft_store(xb, w - a.t0, zero, a.vec);   // no frame, or past the last one
     }
 }
 
@@ -211,12 +180,12 @@ __global__ __launch_bounds__(kFftBlock) void k_istft_cfft_direct(BhwCordicCfg cf
     __shared__ L lut_s[32];
     if (threadIdx.x < 32) lut_s[threadIdx.x] = (L)cfg.lut[threadIdx.x];
     __syncthreads();
-    float *vS = (float *)(icfft_lds + ((size_t)2u * a.fy * a.n + a.n / 2u) * sizeof(icfft_v2f));
+    float *vS = (float *)(fft_lds + ((size_t)2u * a.fy * a.n + a.n / 2u) * sizeof(fft_v2f));
     for (uint32_t k = threadIdx.x; k < a.len; k += kFftBlock) {
         int32_t w;
         if constexpr (FORM == 2) w = direct_coeff_mad_ph(cfg, win, lut_s, len_theta_of(lp, k));
         else                     w = direct_coeff_ph<T>(cfg, win, lut_s, len_theta_of(lp, k));
-        vS[k] = icfft_coeff(w, a.shift);
+        vS[k] = fft_coeff(w, a.shift);
     }
     istft_cfft_spans(a);
 }
@@ -227,23 +196,14 @@ template <int FMT, int NT, int MODE>
 __global__ __launch_bounds__(kFftBlock) void k_istft_cfft_table(BhwCordicCfg cfg, BhwWinCfg win, const void *__restrict__ table, IcfftIo a,
                                                                  BhwLenPhase lp)
 {
-    float *vS = (float *)(icfft_lds + ((size_t)2u * a.fy * a.n + a.n / 2u) * sizeof(icfft_v2f));
+    float *vS = (float *)(fft_lds + ((size_t)2u * a.fy * a.n + a.n / 2u) * sizeof(fft_v2f));
     for (uint32_t k0 = 0; k0 < a.len; k0 += kFftBlock) {
         const uint32_t k = k0 + threadIdx.x;
         const bool in = k < a.len;
         const int32_t w = range_coeff_ph<FMT, NT, MODE>(cfg, win, table, len_theta_of(lp, in ? k : 0u));
-        if (in) vS[k] = icfft_coeff(w, a.shift);
+        if (in) vS[k] = fft_coeff(w, a.shift);
     }
     istft_cfft_spans(a);
-}
-
-// launch() of bhw_device.h with the plan's dynamic LDS
-template <typename... KArgs>
-inline void launch_lds(void (*kernel)(KArgs...), dim3 grid, dim3 block, uint32_t lds, hipStream_t st, typename same_type<KArgs>::type... args)
-{
-    void *ptrs[] = {(void *)&args...};
-    const hipError_t e = hipLaunchKernel(reinterpret_cast<const void *>(kernel), grid, block, ptrs, lds, st);
-    if (e != hipSuccess && t_launch_err == hipSuccess) t_launch_err = e;
 }
 
 } // namespace
@@ -253,45 +213,16 @@ int bhwk_istft_cfft_f32(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwW
 {
     if (!s->samples) return 0;
     hipStream_t st = (hipStream_t)l.stream;
-    IcfftIo a;
-    a.Y = d_Y;
-    a.x = d_x;
-    a.batch = s->batch;
-    a.frames = s->frames;
-    a.hop = pl.hop;
-    a.samples = s->samples;
-    a.t0 = pl.t0;
-    a.x_stride = pl.x_stride;
-    a.y_stride = pl.y_stride;
-    a.y_bstride = pl.y_bstride;
-    a.span = pl.span;
-    a.spans = pl.spans;
-    a.groups = pl.groups;
-    a.trips = pl.trips;
+    IcfftIo a = istft_io<IcfftIo>(pl, s, d_Y, d_x);
     a.n = pl.n;
-    a.col0 = (uint32_t)s->col0;
-    a.len = (uint32_t)pl.len;
-    a.lpf = pl.lpf;
-    a.fy = pl.fy;
-    a.cpl = pl.cpl;
     a.radix4 = pl.radix4;
     a.radix2 = pl.radix2;
-    a.shift = s->shift;
-    a.normalize = pl.normalize ? 1u : 0u;
     a.binshift = pl.shifted ? 1u : 0u;
-    // one 8-byte store per complex sample where every sample is 8-byte aligned, as the load of bhw_stft_cfft.hip
-    a.vec = ((uintptr_t)d_x % 8 == 0 && (s->batch == 1 || pl.x_stride % 2 == 0)) ? 1u : 0u;
+    a.vec = iq_vec(d_x, s->batch, pl.x_stride);    // one 8-byte store per complex sample, as the load of bhw_stft_cfft.hip
     const dim3 grid((unsigned)pl.grid), block(kFftBlock);
-    if (!d_table) {
-        with_int_or_last<2, 1, 0>(direct_form(c_in), [&](auto D) { launch_lds(k_istft_cfft_direct<D>, grid, block, pl.lds_bytes, st, c_in, w, a, lp); });
-        return finish(hipSuccess);
-    }
-    const BhwCordicCfg c = table_layout(c_in);
-    int fmt, nt, mode;
-    if (!bhwp_range_form(c, w, &fmt, &nt, &mode)) return (int)hipErrorInvalidValue;
-    const void *tab = (const void *)d_table;
-    with_range_form(fmt, nt, mode, [&](auto F, auto NT, auto M) {
-        launch_lds(k_istft_cfft_table<F, NT, M>, grid, block, pl.lds_bytes, st, c, w, tab, a, lp);
-    });
-    return finish(hipSuccess);
+    return with_window_source(
+        c_in, w, d_table, [&](auto D) { launch_lds(k_istft_cfft_direct<D>, grid, block, pl.lds_bytes, st, c_in, w, a, lp); },
+        [&](auto F, auto NT, auto M, const BhwCordicCfg &c, const void *tab) {
+            launch_lds(k_istft_cfft_table<F, NT, M>, grid, block, pl.lds_bytes, st, c, w, tab, a, lp);
+        });
 }

@@ -28,9 +28,11 @@
 // idle once its frames are done.  A row's arithmetic does not depend on its slot, span or grid, and an output's sum takes its rows in
 // ascending f whatever the spans are: the bits of an output are a function of the window, the flags and the rows that reach it.
 //
-// Kept in step by hand: the span walk, the ring and the flush restate bhw_istft_cfft.hip and bhw_istft_mfft.hip (those files and their
-// code objects stay the parent's); tests/cpp/san_istft_cmfft.cpp replays this file's index arithmetic -- the load's column, the pass
-// indices, the ring's stepped base mod n and the flush bound `end` -- from a copy of its own.
+// Kept in step by hand: the span walk, the ring and the flush stand in all four inverse units (bhw_istft_fft.hip,
+// bhw_istft_mfft.hip, bhw_istft_cfft.hip, this one); tests/cpp/san_istft_cmfft.cpp replays this file's index arithmetic -- the
+// load's column, the pass indices, the ring's stepped base mod n and the flush bound `end` -- from a copy of its own.  An edit of
+// any of these here is an edit of the siblings and of the replay too.  The Io fill, istft_out and istft_store are bhw_istft.h's.
+#include "bhw_istft.h"
 #include "bhw_stft_mfft.h"
 
 namespace {
@@ -46,23 +48,6 @@ struct IcmfftIo {
     uint32_t sched;                       // the radix of pass p in bits 4p .. 4p + 3
     uint32_t shift, normalize, binshift, vec;
 };
-
-__device__ __forceinline__ float icmfft_out(double s, double e, uint32_t normalize)
-{
-    if (!normalize) return (float)s;
-    return e > 0.0 ? (float)(s / e) : 0.0f;
-}
-
-// the complex sample at float offset 2 * t of a signal: one 8-byte store on the 8-byte grid, else two 4-byte ones
-__device__ __forceinline__ void icmfft_store(float *xb, uint64_t t, fft_v2f z, uint32_t vec)
-{
-    float *px = xb + 2 * t;
-    if (vec) *(fft_v2f *)px = z;
-    else {
-        px[0] = z.x;
-        px[1] = z.y;
-    }
-}
 
 // the float offset of the window coefficients in the dynamic LDS: behind the two buffers and the twiddles
 __device__ __forceinline__ size_t icmfft_window_offset(const IcmfftIo &a) { return ((size_t)2u * a.fy * a.n + a.fold) * sizeof(fft_v2f); }
@@ -154,7 +139,7 @@ __device__ __forceinline__ void istft_cmfft_spans(const IcmfftIo &a)
                 const fft_v2f *row = src + a.col0;
                 const uint64_t base = f * hop;
                 if (cur < base) {                                        // a gap no frame reaches (hop > L, or the span's start)
-                    for (uint64_t w = cur + l; w < base; w += lpf) icmfft_store(xb, w - a.t0, zero, a.vec);
+                    for (uint64_t w = cur + l; w < base; w += lpf) istft_store(xb, w - a.t0, zero, a.vec);
                     cur = base;
                 }
                 uint64_t end = (f + 1 == r.f_hi || base + hop > r.whi) ? r.whi : base + hop;
@@ -172,8 +157,8 @@ __device__ __forceinline__ void istft_cmfft_spans(const IcmfftIo &a)
                             acci[c] += (double)(z.x * scale) * v;
                             env[c] += v * v;
                             if (w < end) {
-                                icmfft_store(xb, w - a.t0,
-                                             fft_v2f{icmfft_out(accr[c], env[c], a.normalize), icmfft_out(acci[c], env[c], a.normalize)}, a.vec);
+                                istft_store(xb, w - a.t0,
+                                             fft_v2f{istft_out(accr[c], env[c], a.normalize), istft_out(acci[c], env[c], a.normalize)}, a.vec);
                                 accr[c] = acci[c] = env[c] = 0.0;
                             }
                         }
@@ -181,7 +166,7 @@ __device__ __forceinline__ void istft_cmfft_spans(const IcmfftIo &a)
                 }
                 const uint64_t reach = base + L;                         // the frame's extent: beyond it up to `end` nothing is summed
                 if (reach < end)
-                    for (uint64_t w = (reach > cur ? reach : cur) + l; w < end; w += lpf) icmfft_store(xb, w - a.t0, zero, a.vec);
+                    for (uint64_t w = (reach > cur ? reach : cur) + l; w < end; w += lpf) istft_store(xb, w - a.t0, zero, a.vec);
                 cur = end;
             }
             bm += hm;                                                    // ((f + 1) * hop) mod n: both terms are below n
@@ -189,7 +174,7 @@ __device__ __forceinline__ void istft_cmfft_spans(const IcmfftIo &a)
             __syncthreads();                                             // the next round overwrites both buffers
         }
         if (live)
-            for (uint64_t w = cur + l; w < r.whi; w += lpf) icmfft_store(xb, w - a.t0, zero, a.vec);   // no frame, or past the last one
+            for (uint64_t w = cur + l; w < r.whi; w += lpf) istft_store(xb, w - a.t0, zero, a.vec);   // no frame, or past the last one
     }
 }
 
@@ -237,46 +222,17 @@ int bhwk_istft_cmfft_f32(const BhwLaunch &l, const BhwCordicCfg &c_in, const Bhw
 {
     if (!s->samples) return 0;
     hipStream_t st = (hipStream_t)l.stream;
-    IcmfftIo a{};
-    a.Y = d_Y;
-    a.x = d_x;
-    a.batch = s->batch;
-    a.frames = s->frames;
-    a.hop = pl.hop;
-    a.samples = s->samples;
-    a.t0 = pl.t0;
-    a.x_stride = pl.x_stride;
-    a.y_stride = pl.y_stride;
-    a.y_bstride = pl.y_bstride;
-    a.span = pl.span;
-    a.spans = pl.spans;
-    a.groups = pl.groups;
-    a.trips = pl.trips;
+    IcmfftIo a = istft_io<IcmfftIo>(pl, s, d_Y, d_x);
     a.n = pl.n;
     a.fold = pl.fold;
-    a.col0 = (uint32_t)s->col0;
-    a.len = (uint32_t)pl.len;
-    a.lpf = pl.lpf;
-    a.fy = pl.fy;
-    a.cpl = pl.cpl;
     a.passes = pl.passes;
     for (uint32_t p = 0; p < pl.passes; ++p) a.sched |= (uint32_t)pl.radix[p] << (4u * p);
-    a.shift = s->shift;
-    a.normalize = pl.normalize ? 1u : 0u;
     a.binshift = pl.shifted ? 1u : 0u;
-    // one 8-byte store per complex sample where every sample is 8-byte aligned, as the power-of-two kernel's
-    a.vec = ((uintptr_t)d_x % 8 == 0 && (s->batch == 1 || pl.x_stride % 2 == 0)) ? 1u : 0u;
+    a.vec = iq_vec(d_x, s->batch, pl.x_stride);    // one 8-byte store per complex sample, as the power-of-two kernel's
     const dim3 grid((unsigned)pl.grid), block(kFftBlock);
-    if (!d_table) {
-        with_int_or_last<2, 1, 0>(direct_form(c_in), [&](auto D) { launch_lds(k_istft_cmfft_direct<D>, grid, block, pl.lds_bytes, st, c_in, w, a, lp); });
-        return finish(hipSuccess);
-    }
-    const BhwCordicCfg c = table_layout(c_in);
-    int fmt, nt, mode;
-    if (!bhwp_range_form(c, w, &fmt, &nt, &mode)) return (int)hipErrorInvalidValue;
-    const void *tab = (const void *)d_table;
-    with_range_form(fmt, nt, mode, [&](auto F, auto NT, auto M) {
-        launch_lds(k_istft_cmfft_table<F, NT, M>, grid, block, pl.lds_bytes, st, c, w, tab, a, lp);
-    });
-    return finish(hipSuccess);
+    return with_window_source(
+        c_in, w, d_table, [&](auto D) { launch_lds(k_istft_cmfft_direct<D>, grid, block, pl.lds_bytes, st, c_in, w, a, lp); },
+        [&](auto F, auto NT, auto M, const BhwCordicCfg &c, const void *tab) {
+            launch_lds(k_istft_cmfft_table<F, NT, M>, grid, block, pl.lds_bytes, st, c, w, tab, a, lp);
+        });
 }

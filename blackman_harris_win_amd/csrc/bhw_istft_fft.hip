@@ -22,15 +22,14 @@
 // idle once its frames are done.  A row's arithmetic does not depend on its slot, span or grid, and an output's sum takes its rows in
 // ascending f whatever the spans are: the bits of an output are a function of the window and the rows that reach it.
 //
-// Kept in step by hand: icmul, itwiddle and launch_lds restate cmul, twiddle and the launch helper of bhw_stft_fft.hip (that file
-// and its code objects stay the parent's), and tests/cpp/san_istft_fft.cpp replays this file's index arithmetic -- the pre-split
+// Kept in step by hand: the span walk, the ring and the flush stand in all four inverse units (this one, bhw_istft_mfft.hip,
+// bhw_istft_cfft.hip, bhw_istft_cmfft.hip), and tests/cpp/san_istft_fft.cpp replays this file's index arithmetic -- the pre-split
 // pairs, the pass indices, the ring's (q - base) mod n_fft and the flush bound `end` -- from a copy of its own, since only
-// bhwp_istft_span is shared through bhw_plan.h.  An edit of any of these here is an edit of the replay too.
-#include "bhw_device.h"
+// bhwp_istft_span is shared through bhw_plan.h.  An edit of any of these here is an edit of the siblings and of the replay too.
+// cmul, twiddle and the dynamic LDS array are bhw_stft_fft.h's, the Io fill and istft_out bhw_istft.h's.
+#include "bhw_istft.h"
 
 namespace {
-
-typedef float ifft_v2f __attribute__((ext_vector_type(2)));
 
 struct IfftIo {
     const float *Y;
@@ -43,39 +42,20 @@ struct IfftIo {
     uint32_t shift, normalize;
 };
 
-extern __shared__ __attribute__((aligned(16))) unsigned char ifft_lds[];
-
-__device__ __forceinline__ float ifft_coeff(int32_t w, uint32_t shift) { return ldexpf((float)w, -(int)shift); }
-
-__device__ __forceinline__ ifft_v2f icmul(ifft_v2f a, ifft_v2f w) { return ifft_v2f{a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x}; }
-
-// W at index idx < n_fft (table of n_fft / 2 entries, W[idx + n_fft / 2] = -W[idx])
-__device__ __forceinline__ ifft_v2f itwiddle(const ifft_v2f *tw, uint32_t idx, uint32_t m)
-{
-    const ifft_v2f w = tw[idx & (m - 1u)];
-    return (idx & m) ? ifft_v2f{-w.x, -w.y} : w;
-}
-
-__device__ __forceinline__ float ifft_out(double s, double e, uint32_t normalize)
-{
-    if (!normalize) return (float)s;
-    return e > 0.0 ? (float)(s / e) : 0.0f;
-}
-
 // Everything after the prologue's coefficients: vS (behind the twiddles) holds v[0..L).
 __device__ __forceinline__ void istft_fft_spans(const IfftIo &a)
 {
     const uint32_t M = a.m, n = a.n_fft, lpf = a.lpf, fy = a.fy, L = a.len;
-    ifft_v2f *bufA = (ifft_v2f *)ifft_lds;
-    ifft_v2f *bufB = bufA + (size_t)fy * M;
-    ifft_v2f *tw = bufB + (size_t)fy * M;
+    fft_v2f *bufA = (fft_v2f *)fft_lds;
+    fft_v2f *bufB = bufA + (size_t)fy * M;
+    fft_v2f *tw = bufB + (size_t)fy * M;
     const float *vS = (const float *)(tw + M);
     const uint32_t tid = threadIdx.x;
     const uint32_t slot = tid / lpf, l = tid - slot * lpf;
     for (uint32_t k = tid; k < M; k += kFftBlock) {
         double sn, cs;
         sincospi((double)k * 2.0 / (double)n, &sn, &cs);
-        tw[k] = ifft_v2f{(float)cs, (float)sn};
+        tw[k] = fft_v2f{(float)cs, (float)sn};
     }
     __syncthreads();
     const float scale = 1.0f / (float)n;                                 // a power of two: exact
@@ -97,22 +77,22 @@ __device__ __forceinline__ void istft_fft_spans(const IfftIo &a)
             const uint64_t f = r.f_lo + it;
             const bool act = f < r.f_hi;
             // 1. the pre-split, into the slot's half of buffer A
-            ifft_v2f *src = bufA + (size_t)slot * M, *dst = bufB + (size_t)slot * M;
+            fft_v2f *src = bufA + (size_t)slot * M, *dst = bufB + (size_t)slot * M;
             if (act) {
-                const ifft_v2f *yp = (const ifft_v2f *)(yb + f * a.y_stride);
+                const fft_v2f *yp = (const fft_v2f *)(yb + f * a.y_stride);
                 for (uint32_t k = l; k <= H; k += lpf) {
-                    const ifft_v2f A = yp[k], B = yp[M - k];
+                    const fft_v2f A = yp[k], B = yp[M - k];
                     if (k == 0u) {
-                        src[0] = ifft_v2f{A.x + B.x, A.x - B.x};
+                        src[0] = fft_v2f{A.x + B.x, A.x - B.x};
                     } else {
-                        const ifft_v2f w = tw[k];
-                        const ifft_v2f e0 = ifft_v2f{A.x + B.x, A.y - B.y}, d0 = ifft_v2f{A.x - B.x, A.y + B.y};
-                        const ifft_v2f o0 = icmul(d0, w);
-                        src[k] = ifft_v2f{e0.x - o0.y, e0.y + o0.x};
+                        const fft_v2f w = tw[k];
+                        const fft_v2f e0 = fft_v2f{A.x + B.x, A.y - B.y}, d0 = fft_v2f{A.x - B.x, A.y + B.y};
+                        const fft_v2f o0 = cmul(d0, w);
+                        src[k] = fft_v2f{e0.x - o0.y, e0.y + o0.x};
                         if (k != H) {                                    // the partner M - k: W[M - k] = -conj W[k]
-                            const ifft_v2f e1 = ifft_v2f{e0.x, -e0.y}, d1 = ifft_v2f{-d0.x, d0.y};
-                            const ifft_v2f o1 = icmul(d1, ifft_v2f{-w.x, w.y});
-                            src[M - k] = ifft_v2f{e1.x - o1.y, e1.y + o1.x};
+                            const fft_v2f e1 = fft_v2f{e0.x, -e0.y}, d1 = fft_v2f{-d0.x, d0.y};
+                            const fft_v2f o1 = cmul(d1, fft_v2f{-w.x, w.y});
+                            src[M - k] = fft_v2f{e1.x - o1.y, e1.y + o1.x};
                         }
                     }
                 }
@@ -124,15 +104,15 @@ __device__ __forceinline__ void istft_fft_spans(const IfftIo &a)
                 const uint32_t ts = M / (2u * Ns);                       // n_fft / (4 Ns)
                 for (uint32_t i = l; i < Q; i += lpf) {
                     const uint32_t k = i & (Ns - 1u);
-                    ifft_v2f a0 = src[i], a1 = src[i + Q], a2 = src[i + 2u * Q], a3 = src[i + 3u * Q];
+                    fft_v2f a0 = src[i], a1 = src[i + Q], a2 = src[i + 2u * Q], a3 = src[i + 3u * Q];
                     if (Ns > 1u) {
                         const uint32_t kt = k * ts;
-                        a1 = icmul(a1, itwiddle(tw, kt, M));
-                        a2 = icmul(a2, itwiddle(tw, 2u * kt, M));
-                        a3 = icmul(a3, itwiddle(tw, 3u * kt, M));
+                        a1 = cmul(a1, twiddle(tw, kt, M));
+                        a2 = cmul(a2, twiddle(tw, 2u * kt, M));
+                        a3 = cmul(a3, twiddle(tw, 3u * kt, M));
                     }
-                    const ifft_v2f t0 = a0 + a2, t1 = a0 - a2, t2 = a1 + a3;
-                    const ifft_v2f t3 = ifft_v2f{a3.y - a1.y, a1.x - a3.x};   // +i (a1 - a3)
+                    const fft_v2f t0 = a0 + a2, t1 = a0 - a2, t2 = a1 + a3;
+                    const fft_v2f t3 = fft_v2f{a3.y - a1.y, a1.x - a3.x};   // +i (a1 - a3)
                     const uint32_t o = ((i - k) << 2) + k;
                     dst[o] = t0 + t2;
                     dst[o + Ns] = t1 + t3;
@@ -140,19 +120,19 @@ __device__ __forceinline__ void istft_fft_spans(const IfftIo &a)
                     dst[o + 3u * Ns] = t1 - t3;
                 }
                 __syncthreads();
-                ifft_v2f *sw = src;
+                fft_v2f *sw = src;
                 src = dst;
                 dst = sw;
                 Ns <<= 2;
             }
             if (a.radix2) {                                              // Ns = M / 2: k = i, twiddle W[2 i]
                 for (uint32_t i = l; i < H; i += lpf) {
-                    const ifft_v2f a0 = src[i], a1 = icmul(src[i + H], tw[2u * i]);
+                    const fft_v2f a0 = src[i], a1 = cmul(src[i + H], tw[2u * i]);
                     dst[i] = a0 + a1;
                     dst[i + H] = a0 - a1;
                 }
                 __syncthreads();
-                ifft_v2f *sw = src;
+                fft_v2f *sw = src;
                 src = dst;
                 dst = sw;
             }
@@ -177,7 +157,7 @@ __device__ __forceinline__ void istft_fft_spans(const IfftIo &a)
                             acc[c] += (double)(row[k] * scale) * v;
                             env[c] += v * v;
                             if (w < end) {
-                                xb[w - a.t0] = ifft_out(acc[c], env[c], a.normalize);
+                                xb[w - a.t0] = istft_out(acc[c], env[c], a.normalize);
                                 acc[c] = env[c] = 0.0;
                             }
                         }
@@ -205,12 +185,12 @@ __global__ __launch_bounds__(kFftBlock, 4) void k_istft_fft_direct(BhwCordicCfg 
     __shared__ L lut_s[32];
     if (threadIdx.x < 32) lut_s[threadIdx.x] = (L)cfg.lut[threadIdx.x];
     __syncthreads();
-    float *vS = (float *)(ifft_lds + (size_t)(2u * a.fy + 1u) * a.m * sizeof(ifft_v2f));
+    float *vS = (float *)(fft_lds + (size_t)(2u * a.fy + 1u) * a.m * sizeof(fft_v2f));
     for (uint32_t k = threadIdx.x; k < a.len; k += kFftBlock) {
         int32_t w;
         if constexpr (FORM == 2) w = direct_coeff_mad_ph(cfg, win, lut_s, len_theta_of(lp, k));
         else                     w = direct_coeff_ph<T>(cfg, win, lut_s, len_theta_of(lp, k));
-        vS[k] = ifft_coeff(w, a.shift);
+        vS[k] = fft_coeff(w, a.shift);
     }
     istft_fft_spans(a);
 }
@@ -221,23 +201,14 @@ template <int FMT, int NT, int MODE>
 __global__ __launch_bounds__(kFftBlock, 4) void k_istft_fft_table(BhwCordicCfg cfg, BhwWinCfg win, const void *__restrict__ table, IfftIo a,
                                                                 BhwLenPhase lp)
 {
-    float *vS = (float *)(ifft_lds + (size_t)(2u * a.fy + 1u) * a.m * sizeof(ifft_v2f));
+    float *vS = (float *)(fft_lds + (size_t)(2u * a.fy + 1u) * a.m * sizeof(fft_v2f));
     for (uint32_t k0 = 0; k0 < a.len; k0 += kFftBlock) {
         const uint32_t k = k0 + threadIdx.x;
         const bool in = k < a.len;
         const int32_t w = range_coeff_ph<FMT, NT, MODE>(cfg, win, table, len_theta_of(lp, in ? k : 0u));
-        if (in) vS[k] = ifft_coeff(w, a.shift);
+        if (in) vS[k] = fft_coeff(w, a.shift);
     }
     istft_fft_spans(a);
-}
-
-// launch() of bhw_device.h with the plan's dynamic LDS
-template <typename... KArgs>
-inline void launch_lds(void (*kernel)(KArgs...), dim3 grid, dim3 block, uint32_t lds, hipStream_t st, typename same_type<KArgs>::type... args)
-{
-    void *ptrs[] = {(void *)&args...};
-    const hipError_t e = hipLaunchKernel(reinterpret_cast<const void *>(kernel), grid, block, ptrs, lds, st);
-    if (e != hipSuccess && t_launch_err == hipSuccess) t_launch_err = e;
 }
 
 } // namespace
@@ -247,43 +218,15 @@ int bhwk_istft_fft_f32(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWi
 {
     if (!s->samples) return 0;
     hipStream_t st = (hipStream_t)l.stream;
-    IfftIo a;
-    a.Y = d_Y;
-    a.x = d_x;
-    a.batch = s->batch;
-    a.frames = s->frames;
-    a.hop = pl.hop;
-    a.samples = s->samples;
-    a.t0 = pl.t0;
-    a.x_stride = pl.x_stride;
-    a.y_stride = pl.y_stride;
-    a.y_bstride = pl.y_bstride;
-    a.span = pl.span;
-    a.spans = pl.spans;
-    a.groups = pl.groups;
-    a.trips = pl.trips;
+    IfftIo a = istft_io<IfftIo>(pl, s, d_Y, d_x);
     a.n_fft = (uint32_t)s->n_fft;
     a.m = pl.m;
-    a.col0 = (uint32_t)s->col0;
-    a.len = (uint32_t)pl.len;
-    a.lpf = pl.lpf;
-    a.fy = pl.fy;
-    a.cpl = pl.cpl;
     a.radix4 = pl.radix4;
     a.radix2 = pl.radix2;
-    a.shift = s->shift;
-    a.normalize = pl.normalize ? 1u : 0u;
     const dim3 grid((unsigned)pl.grid), block(kFftBlock);
-    if (!d_table) {
-        with_int_or_last<2, 1, 0>(direct_form(c_in), [&](auto D) { launch_lds(k_istft_fft_direct<D>, grid, block, pl.lds_bytes, st, c_in, w, a, lp); });
-        return finish(hipSuccess);
-    }
-    const BhwCordicCfg c = table_layout(c_in);
-    int fmt, nt, mode;
-    if (!bhwp_range_form(c, w, &fmt, &nt, &mode)) return (int)hipErrorInvalidValue;
-    const void *tab = (const void *)d_table;
-    with_range_form(fmt, nt, mode, [&](auto F, auto NT, auto M) {
-        launch_lds(k_istft_fft_table<F, NT, M>, grid, block, pl.lds_bytes, st, c, w, tab, a, lp);
-    });
-    return finish(hipSuccess);
+    return with_window_source(
+        c_in, w, d_table, [&](auto D) { launch_lds(k_istft_fft_direct<D>, grid, block, pl.lds_bytes, st, c_in, w, a, lp); },
+        [&](auto F, auto NT, auto M, const BhwCordicCfg &c, const void *tab) {
+            launch_lds(k_istft_fft_table<F, NT, M>, grid, block, pl.lds_bytes, st, c, w, tab, a, lp);
+        });
 }

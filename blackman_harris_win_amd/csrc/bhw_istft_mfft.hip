@@ -29,16 +29,16 @@
 // idle once its frames are done.  A row's arithmetic does not depend on its slot, span or grid, and an output's sum takes its rows in
 // ascending f whatever the spans are: the bits of an output are a function of the window and the rows that reach it.
 //
-// Kept in step by hand: imf_cmul, imf_twiddle, the radix constants, imf_pass and launch_lds restate cmul, mfft_twiddle, the constants,
-// mfft_pass and the launch helper of bhw_stft_mfft.hip / bhw_stft_fft.h, and the span walk restates bhw_istft_fft.hip (those files
-// and their code objects stay the parent's); tests/cpp/san_istft_mfft.cpp replays this file's index arithmetic -- the pre-split pairs,
-// the pass indices and the float i mod Ns, the ring's stepped base mod n_fft and the flush bound `end` -- from a copy of its own,
-// since only bhwp_istft_span is shared through bhw_plan.h.  An edit of any of these here is an edit of the replay too.
-#include "bhw_device.h"
+// Kept in step by hand: imf_pass restates mfft_pass of bhw_stft_mfft.h around the conjugated butterfly, and the span walk, the ring
+// and the flush stand in all four inverse units (bhw_istft_fft.hip, this one, bhw_istft_cfft.hip, bhw_istft_cmfft.hip);
+// tests/cpp/san_istft_mfft.cpp replays this file's index arithmetic -- the pre-split pairs, the pass indices and the float i mod Ns,
+// the ring's stepped base mod n_fft and the flush bound `end` -- from a copy of its own, since only bhwp_istft_span is shared
+// through bhw_plan.h.  An edit of any of these here is an edit of the siblings and of the replay too.  cmul, mfft_twiddle, the radix
+// constants and the dynamic LDS array are bhw_stft_mfft.h's and bhw_stft_fft.h's, the Io fill and istft_out bhw_istft.h's.
+#include "bhw_istft.h"
+#include "bhw_stft_mfft.h"
 
 namespace {
-
-typedef float imf_v2f __attribute__((ext_vector_type(2)));
 
 struct ImfftIo {
     const float *Y;
@@ -52,75 +52,48 @@ struct ImfftIo {
     uint32_t shift, normalize;
 };
 
-extern __shared__ __attribute__((aligned(16))) unsigned char imf_lds[];
-
-__device__ __forceinline__ float imf_coeff(int32_t w, uint32_t shift) { return ldexpf((float)w, -(int)shift); }
-
-__device__ __forceinline__ imf_v2f imf_cmul(imf_v2f a, imf_v2f w) { return imf_v2f{a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x}; }
-
-// W at index idx < n_fft (table of M = n_fft / 2 entries, W[idx + M] = -W[idx]); M is no power of two: a compare, not a mask
-__device__ __forceinline__ imf_v2f imf_twiddle(const imf_v2f *tw, uint32_t idx, uint32_t M)
-{
-    const bool hi = idx >= M;
-    const imf_v2f w = tw[hi ? idx - M : idx];
-    return hi ? imf_v2f{-w.x, -w.y} : w;
-}
-
-__device__ __forceinline__ float imf_out(double s, double e, uint32_t normalize)
-{
-    if (!normalize) return (float)s;
-    return e > 0.0 ? (float)(s / e) : 0.0f;
-}
-
-// float32 roundings of binary64 values (bhw_stft_mfft.hip's)
-constexpr float kImfSin3 = (float)0.86602540378443864676;      // sin(2 pi / 3)
-constexpr float kImfCos5a = (float)0.30901699437494742410;     // cos(2 pi / 5)
-constexpr float kImfCos5b = (float)-0.80901699437494742410;    // cos(4 pi / 5)
-constexpr float kImfSin5a = (float)0.95105651629515357212;     // sin(2 pi / 5)
-constexpr float kImfSin5b = (float)0.58778525229247312917;     // sin(4 pi / 5)
-
 // X[q] = sum over j of a[j] exp(+2 pi i j q / R), in place: the forward's butterflies conjugated
 template <uint32_t R>
-__device__ __forceinline__ void imf_butterfly(imf_v2f (&a)[R])
+__device__ __forceinline__ void imf_butterfly(fft_v2f (&a)[R])
 {
     if constexpr (R == 2) {
-        const imf_v2f a0 = a[0], a1 = a[1];
+        const fft_v2f a0 = a[0], a1 = a[1];
         a[0] = a0 + a1;
         a[1] = a0 - a1;
     } else if constexpr (R == 3) {
-        const imf_v2f t1 = a[1] + a[2], d = a[1] - a[2];
-        const imf_v2f t2 = a[0] - 0.5f * t1, t3 = kImfSin3 * d;
+        const fft_v2f t1 = a[1] + a[2], d = a[1] - a[2];
+        const fft_v2f t2 = a[0] - 0.5f * t1, t3 = kSin3 * d;
         a[0] = a[0] + t1;
-        a[1] = imf_v2f{t2.x - t3.y, t2.y + t3.x};                  // t2 + i t3
-        a[2] = imf_v2f{t2.x + t3.y, t2.y - t3.x};                  // t2 - i t3
+        a[1] = fft_v2f{t2.x - t3.y, t2.y + t3.x};                  // t2 + i t3
+        a[2] = fft_v2f{t2.x + t3.y, t2.y - t3.x};                  // t2 - i t3
     } else if constexpr (R == 4) {
-        const imf_v2f t0 = a[0] + a[2], t1 = a[0] - a[2], t2 = a[1] + a[3];
-        const imf_v2f t3 = imf_v2f{a[3].y - a[1].y, a[1].x - a[3].x};   // +i (a1 - a3)
+        const fft_v2f t0 = a[0] + a[2], t1 = a[0] - a[2], t2 = a[1] + a[3];
+        const fft_v2f t3 = fft_v2f{a[3].y - a[1].y, a[1].x - a[3].x};   // +i (a1 - a3)
         a[0] = t0 + t2;
         a[1] = t1 + t3;
         a[2] = t0 - t2;
         a[3] = t1 - t3;
     } else {
         static_assert(R == 5, "radix");
-        const imf_v2f b1 = a[1] + a[4], b2 = a[2] + a[3], d1 = a[1] - a[4], d2 = a[2] - a[3];
-        const imf_v2f m1 = a[0] + kImfCos5a * b1 + kImfCos5b * b2, m2 = a[0] + kImfCos5b * b1 + kImfCos5a * b2;
-        const imf_v2f n1 = kImfSin5a * d1 + kImfSin5b * d2, n2 = kImfSin5b * d1 - kImfSin5a * d2;
+        const fft_v2f b1 = a[1] + a[4], b2 = a[2] + a[3], d1 = a[1] - a[4], d2 = a[2] - a[3];
+        const fft_v2f m1 = a[0] + kCos5a * b1 + kCos5b * b2, m2 = a[0] + kCos5b * b1 + kCos5a * b2;
+        const fft_v2f n1 = kSin5a * d1 + kSin5b * d2, n2 = kSin5b * d1 - kSin5a * d2;
         a[0] = a[0] + b1 + b2;
-        a[1] = imf_v2f{m1.x - n1.y, m1.y + n1.x};                  // m1 + i n1
-        a[4] = imf_v2f{m1.x + n1.y, m1.y - n1.x};
-        a[2] = imf_v2f{m2.x - n2.y, m2.y + n2.x};                  // m2 + i n2
-        a[3] = imf_v2f{m2.x + n2.y, m2.y - n2.x};
+        a[1] = fft_v2f{m1.x - n1.y, m1.y + n1.x};                  // m1 + i n1
+        a[4] = fft_v2f{m1.x + n1.y, m1.y - n1.x};
+        a[2] = fft_v2f{m2.x - n2.y, m2.y + n2.x};                  // m2 + i n2
+        a[3] = fft_v2f{m2.x + n2.y, m2.y - n2.x};
     }
 }
 
 // One Stockham pass of radix R over the slot's M points: Q = M / R butterflies, sub-transform length Ns, ts = n_fft / (R Ns).
 template <uint32_t R>
-__device__ __forceinline__ void imf_pass(const imf_v2f *src, imf_v2f *dst, const imf_v2f *tw, uint32_t M, uint32_t Q, uint32_t Ns, uint32_t ts,
+__device__ __forceinline__ void imf_pass(const fft_v2f *src, fft_v2f *dst, const fft_v2f *tw, uint32_t M, uint32_t Q, uint32_t Ns, uint32_t ts,
                                          uint32_t l, uint32_t lpf)
 {
     const float inv = __builtin_amdgcn_rcpf((float)Ns);
     for (uint32_t i = l; i < Q; i += lpf) {
-        imf_v2f a[R];
+        fft_v2f a[R];
 #pragma unroll
         for (uint32_t q = 0; q < R; ++q) a[q] = src[i + q * Q];
         uint32_t k = i;                                                 // the last pass: Ns = Q
@@ -128,7 +101,7 @@ __device__ __forceinline__ void imf_pass(const imf_v2f *src, imf_v2f *dst, const
         if (Ns > 1u) {
             const uint32_t kt = k * ts;
 #pragma unroll
-            for (uint32_t q = 1; q < R; ++q) a[q] = imf_cmul(a[q], imf_twiddle(tw, q * kt, M));
+            for (uint32_t q = 1; q < R; ++q) a[q] = cmul(a[q], mfft_twiddle(tw, q * kt, M));
         }
         imf_butterfly<R>(a);
         const uint32_t o = (i - k) * R + k;
@@ -141,16 +114,16 @@ __device__ __forceinline__ void imf_pass(const imf_v2f *src, imf_v2f *dst, const
 __device__ __forceinline__ void istft_mfft_spans(const ImfftIo &a)
 {
     const uint32_t M = a.m, n = a.n_fft, lpf = a.lpf, fy = a.fy, L = a.len;
-    imf_v2f *bufA = (imf_v2f *)imf_lds;
-    imf_v2f *bufB = bufA + (size_t)fy * M;
-    imf_v2f *tw = bufB + (size_t)fy * M;
+    fft_v2f *bufA = (fft_v2f *)fft_lds;
+    fft_v2f *bufB = bufA + (size_t)fy * M;
+    fft_v2f *tw = bufB + (size_t)fy * M;
     const float *vS = (const float *)(tw + M);
     const uint32_t tid = threadIdx.x;
     const uint32_t slot = tid / lpf, l = tid - slot * lpf;
     for (uint32_t k = tid; k < M; k += kFftBlock) {
         double sn, cs;
         sincospi((double)k * 2.0 / (double)n, &sn, &cs);
-        tw[k] = imf_v2f{(float)cs, (float)sn};
+        tw[k] = fft_v2f{(float)cs, (float)sn};
     }
     __syncthreads();
     const float scale = (float)(1.0 / (double)n);                        // not a power of two: the multiply rounds
@@ -179,22 +152,22 @@ __device__ __forceinline__ void istft_mfft_spans(const ImfftIo &a)
             const uint64_t f = r.f_lo + it;
             const bool act = f < r.f_hi;
             // 1. the pre-split, into the slot's half of buffer A
-            imf_v2f *src = bufA + (size_t)slot * M, *dst = bufB + (size_t)slot * M;
+            fft_v2f *src = bufA + (size_t)slot * M, *dst = bufB + (size_t)slot * M;
             if (act) {
-                const imf_v2f *yp = (const imf_v2f *)(yb + f * a.y_stride);
+                const fft_v2f *yp = (const fft_v2f *)(yb + f * a.y_stride);
                 for (uint32_t k = l; k <= H; k += lpf) {
-                    const imf_v2f A = yp[k], B = yp[M - k];
+                    const fft_v2f A = yp[k], B = yp[M - k];
                     if (k == 0u) {
-                        src[0] = imf_v2f{A.x + B.x, A.x - B.x};
+                        src[0] = fft_v2f{A.x + B.x, A.x - B.x};
                     } else {
-                        const imf_v2f w = tw[k];
-                        const imf_v2f e0 = imf_v2f{A.x + B.x, A.y - B.y}, d0 = imf_v2f{A.x - B.x, A.y + B.y};
-                        const imf_v2f o0 = imf_cmul(d0, w);
-                        src[k] = imf_v2f{e0.x - o0.y, e0.y + o0.x};
+                        const fft_v2f w = tw[k];
+                        const fft_v2f e0 = fft_v2f{A.x + B.x, A.y - B.y}, d0 = fft_v2f{A.x - B.x, A.y + B.y};
+                        const fft_v2f o0 = cmul(d0, w);
+                        src[k] = fft_v2f{e0.x - o0.y, e0.y + o0.x};
                         if (2u * k != M) {                               // the partner M - k: W[M - k] = -conj W[k]
-                            const imf_v2f e1 = imf_v2f{e0.x, -e0.y}, d1 = imf_v2f{-d0.x, d0.y};
-                            const imf_v2f o1 = imf_cmul(d1, imf_v2f{-w.x, w.y});
-                            src[M - k] = imf_v2f{e1.x - o1.y, e1.y + o1.x};
+                            const fft_v2f e1 = fft_v2f{e0.x, -e0.y}, d1 = fft_v2f{-d0.x, d0.y};
+                            const fft_v2f o1 = cmul(d1, fft_v2f{-w.x, w.y});
+                            src[M - k] = fft_v2f{e1.x - o1.y, e1.y + o1.x};
                         }
                     }
                 }
@@ -219,7 +192,7 @@ __device__ __forceinline__ void istft_mfft_spans(const ImfftIo &a)
                     imf_pass<2>(src, dst, tw, M, M >> 1, Ns, 2u * rest, l, lpf);
                 }
                 __syncthreads();
-                imf_v2f *sw = src;
+                fft_v2f *sw = src;
                 src = dst;
                 dst = sw;
                 Ns *= rdx;
@@ -245,7 +218,7 @@ __device__ __forceinline__ void istft_mfft_spans(const ImfftIo &a)
                             acc[c] += (double)(row[k] * scale) * v;
                             env[c] += v * v;
                             if (w < end) {
-                                xb[w - a.t0] = imf_out(acc[c], env[c], a.normalize);
+                                xb[w - a.t0] = istft_out(acc[c], env[c], a.normalize);
                                 acc[c] = env[c] = 0.0;
                             }
                         }
@@ -276,12 +249,12 @@ __global__ __launch_bounds__(kFftBlock) void k_istft_mfft_direct(BhwCordicCfg cf
     __shared__ L lut_s[32];
     if (threadIdx.x < 32) lut_s[threadIdx.x] = (L)cfg.lut[threadIdx.x];
     __syncthreads();
-    float *vS = (float *)(imf_lds + (size_t)(2u * a.fy + 1u) * a.m * sizeof(imf_v2f));
+    float *vS = (float *)(fft_lds + (size_t)(2u * a.fy + 1u) * a.m * sizeof(fft_v2f));
     for (uint32_t k = threadIdx.x; k < a.len; k += kFftBlock) {
         int32_t w;
         if constexpr (FORM == 2) w = direct_coeff_mad_ph(cfg, win, lut_s, len_theta_of(lp, k));
         else                     w = direct_coeff_ph<T>(cfg, win, lut_s, len_theta_of(lp, k));
-        vS[k] = imf_coeff(w, a.shift);
+        vS[k] = fft_coeff(w, a.shift);
     }
     istft_mfft_spans(a);
 }
@@ -292,23 +265,14 @@ template <int FMT, int NT, int MODE>
 __global__ __launch_bounds__(kFftBlock) void k_istft_mfft_table(BhwCordicCfg cfg, BhwWinCfg win, const void *__restrict__ table, ImfftIo a,
                                                                  BhwLenPhase lp)
 {
-    float *vS = (float *)(imf_lds + (size_t)(2u * a.fy + 1u) * a.m * sizeof(imf_v2f));
+    float *vS = (float *)(fft_lds + (size_t)(2u * a.fy + 1u) * a.m * sizeof(fft_v2f));
     for (uint32_t k0 = 0; k0 < a.len; k0 += kFftBlock) {
         const uint32_t k = k0 + threadIdx.x;
         const bool in = k < a.len;
         const int32_t w = range_coeff_ph<FMT, NT, MODE>(cfg, win, table, len_theta_of(lp, in ? k : 0u));
-        if (in) vS[k] = imf_coeff(w, a.shift);
+        if (in) vS[k] = fft_coeff(w, a.shift);
     }
     istft_mfft_spans(a);
-}
-
-// launch() of bhw_device.h with the plan's dynamic LDS
-template <typename... KArgs>
-inline void launch_lds(void (*kernel)(KArgs...), dim3 grid, dim3 block, uint32_t lds, hipStream_t st, typename same_type<KArgs>::type... args)
-{
-    void *ptrs[] = {(void *)&args...};
-    const hipError_t e = hipLaunchKernel(reinterpret_cast<const void *>(kernel), grid, block, ptrs, lds, st);
-    if (e != hipSuccess && t_launch_err == hipSuccess) t_launch_err = e;
 }
 
 } // namespace
@@ -318,43 +282,15 @@ int bhwk_istft_mfft_f32(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwW
 {
     if (!s->samples) return 0;
     hipStream_t st = (hipStream_t)l.stream;
-    ImfftIo a{};
-    a.Y = d_Y;
-    a.x = d_x;
-    a.batch = s->batch;
-    a.frames = s->frames;
-    a.hop = pl.hop;
-    a.samples = s->samples;
-    a.t0 = pl.t0;
-    a.x_stride = pl.x_stride;
-    a.y_stride = pl.y_stride;
-    a.y_bstride = pl.y_bstride;
-    a.span = pl.span;
-    a.spans = pl.spans;
-    a.groups = pl.groups;
-    a.trips = pl.trips;
+    ImfftIo a = istft_io<ImfftIo>(pl, s, d_Y, d_x);
     a.n_fft = (uint32_t)s->n_fft;
     a.m = pl.m;
-    a.col0 = (uint32_t)s->col0;
-    a.len = (uint32_t)pl.len;
-    a.lpf = pl.lpf;
-    a.fy = pl.fy;
-    a.cpl = pl.cpl;
     a.passes = pl.passes;
     for (uint32_t p = 0; p < pl.passes; ++p) a.sched |= (uint32_t)pl.radix[p] << (4u * p);
-    a.shift = s->shift;
-    a.normalize = pl.normalize ? 1u : 0u;
     const dim3 grid((unsigned)pl.grid), block(kFftBlock);
-    if (!d_table) {
-        with_int_or_last<2, 1, 0>(direct_form(c_in), [&](auto D) { launch_lds(k_istft_mfft_direct<D>, grid, block, pl.lds_bytes, st, c_in, w, a, lp); });
-        return finish(hipSuccess);
-    }
-    const BhwCordicCfg c = table_layout(c_in);
-    int fmt, nt, mode;
-    if (!bhwp_range_form(c, w, &fmt, &nt, &mode)) return (int)hipErrorInvalidValue;
-    const void *tab = (const void *)d_table;
-    with_range_form(fmt, nt, mode, [&](auto F, auto NT, auto M) {
-        launch_lds(k_istft_mfft_table<F, NT, M>, grid, block, pl.lds_bytes, st, c, w, tab, a, lp);
-    });
-    return finish(hipSuccess);
+    return with_window_source(
+        c_in, w, d_table, [&](auto D) { launch_lds(k_istft_mfft_direct<D>, grid, block, pl.lds_bytes, st, c_in, w, a, lp); },
+        [&](auto F, auto NT, auto M, const BhwCordicCfg &c, const void *tab) {
+            launch_lds(k_istft_mfft_table<F, NT, M>, grid, block, pl.lds_bytes, st, c, w, tab, a, lp);
+        });
 }

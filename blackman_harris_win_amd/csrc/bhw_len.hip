@@ -55,16 +55,9 @@ int bhwk_len_range(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinCfg
     hipStream_t st = (hipStream_t)l.stream;
     const uint64_t m0 = bhw_len_mod(n0, lp);
     const dim3 grid(grid_for(count)), block(kBlock);
-    if (!d_table) {
-        with_int_or_last<2, 1, 0>(direct_form(c_in), [&](auto D) { launch(k_direct_len<D>, grid, block, st, c_in, w, lp, m0, count, d_out); });
-        return finish(hipSuccess);
-    }
-    const BhwCordicCfg c = table_layout(c_in);
-    int fmt, nt, mode;
-    if (!bhwp_range_form(c, w, &fmt, &nt, &mode)) return (int)hipErrorInvalidValue;   // every format a resident table holds has instances
-    const void *tab = (const void *)d_table;
-    with_range_form(fmt, nt, mode, [&](auto F, auto NT, auto M) {
-        launch(k_range_len<F, NT, M>, grid, block, st, c, w, tab, lp, m0, count, d_out);
-    });
-    return finish(hipSuccess);
+    return with_window_source(
+        c_in, w, d_table, [&](auto D) { launch(k_direct_len<D>, grid, block, st, c_in, w, lp, m0, count, d_out); },
+        [&](auto F, auto NT, auto M, const BhwCordicCfg &c, const void *tab) {
+            launch(k_range_len<F, NT, M>, grid, block, st, c, w, tab, lp, m0, count, d_out);
+        });
 }

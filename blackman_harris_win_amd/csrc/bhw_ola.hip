@@ -173,20 +173,16 @@ int bhwk_ola(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinCfg &w, c
     OlaArgs a;
     ola_args(a, pl, o, d_y, d_x);
     const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y), block(kOlaBlock);
-    if (!d_table) {
-        with_int_or_last<0, 1, 2>(a.io, [&](auto IO) {
-            with_int_or_last<2, 1, 0>(direct_form(c_in), [&](auto D) {
+    return with_window_source(
+        c_in, w, d_table,
+        [&](auto D) {
+            with_int_or_last<0, 1, 2>(a.io, [&](auto IO) {
                 launch_phase(k_ola_direct_len<D, IO>, k_ola_direct<D, IO>, lp, grid, block, st, c_in, w, a);
             });
+        },
+        [&](auto F, auto NT, auto M, const BhwCordicCfg &c, const void *tab) {
+            with_int_or_last<0, 1, 2>(a.io, [&](auto IO) {
+                launch_phase(k_ola_table_len<F, NT, M, IO>, k_ola_table<F, NT, M, IO>, lp, grid, block, st, c, w, tab, a);
+            });
         });
-        return finish(hipSuccess);
-    }
-    const BhwCordicCfg c = table_layout(c_in);
-    int fmt, nt, mode;
-    if (!bhwp_range_form(c, w, &fmt, &nt, &mode)) return (int)hipErrorInvalidValue;   // every format a resident table holds has instances
-    const void *tab = (const void *)d_table;
-    with_range_form(fmt, nt, mode, [&](auto F, auto NT, auto M) {
-        with_int_or_last<0, 1, 2>(a.io, [&](auto IO) { launch_phase(k_ola_table_len<F, NT, M, IO>, k_ola_table<F, NT, M, IO>, lp, grid, block, st, c, w, tab, a); });
-    });
-    return finish(hipSuccess);
 }

@@ -189,30 +189,32 @@ int ola_f32_launch(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinCfg
     a.y_bstride = bt.y_bstride;
     a.x_bstride = bt.x_bstride;
     if (a.io == 2 && bt.batch > 1 && (bt.y_bstride % 2 || bt.x_bstride % 2)) a.io = 1;    // every signal start 8-byte aligned
-    const BhwCordicCfg c = d_table ? table_layout(c_in) : c_in;
-    int fmt = 0, nt = 0, mode = 0;
-    if (d_table && !bhwp_range_form(c, w, &fmt, &nt, &mode)) return (int)hipErrorInvalidValue;
-    const void *tab = (const void *)d_table;
-    for (uint64_t b0 = 0; b0 < bt.batch; b0 += kOlaMaxGridZ) {
-        const uint64_t nb = bt.batch - b0 < kOlaMaxGridZ ? bt.batch - b0 : kOlaMaxGridZ;
-        a.y = d_y + b0 * bt.y_bstride;
-        a.x = d_x + b0 * bt.x_bstride;
-        const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y, (unsigned)nb), block(kOlaBlock);
-        if (!d_table) {
+    // one launch per slab of kOlaMaxGridZ signals, inside the source's callback: the table's form is resolved once
+    const dim3 block(kOlaBlock);
+    const auto per_slab = [&](auto &&launch_slab) {
+        for (uint64_t b0 = 0; b0 < bt.batch; b0 += kOlaMaxGridZ) {
+            const uint64_t nb = bt.batch - b0 < kOlaMaxGridZ ? bt.batch - b0 : kOlaMaxGridZ;
+            a.y = d_y + b0 * bt.y_bstride;
+            a.x = d_x + b0 * bt.x_bstride;
+            launch_slab(dim3((unsigned)pl.grid_x, (unsigned)pl.grid_y, (unsigned)nb));
+        }
+    };
+    return with_window_source(
+        c_in, w, d_table,
+        [&](auto D) {
             with_int_or_last<0, 1, 2>(a.io, [&](auto IO) {
-                with_int_or_last<2, 1, 0>(direct_form(c_in), [&](auto D) {
+                per_slab([&](dim3 grid) {
                     launch_phase(k_ola_f32_direct_len<D, IO, NORM>, k_ola_f32_direct<D, IO, NORM>, lp, grid, block, st, c_in, w, a);
                 });
             });
-            continue;
-        }
-        with_range_form(fmt, nt, mode, [&](auto F, auto NT, auto M) {
+        },
+        [&](auto F, auto NT, auto M, const BhwCordicCfg &c, const void *tab) {
             with_int_or_last<0, 1, 2>(a.io, [&](auto IO) {
-                launch_phase(k_ola_f32_table_len<F, NT, M, IO, NORM>, k_ola_f32_table<F, NT, M, IO, NORM>, lp, grid, block, st, c, w, tab, a);
+                per_slab([&](dim3 grid) {
+                    launch_phase(k_ola_f32_table_len<F, NT, M, IO, NORM>, k_ola_f32_table<F, NT, M, IO, NORM>, lp, grid, block, st, c, w, tab, a);
+                });
             });
         });
-    }
-    return finish(hipSuccess);
 }
 
 } // namespace

@@ -2818,42 +2818,49 @@ int bhwp_describe_hold_mfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_
                               hold_traces_tail(traces), buf, len);
 }
 
-// ---- fused inverse real FFT, window and overlap-add -----------------------------------------------------------------------------------------
+// ---- the fused inverse fronts: inverse FFT, window and overlap-add (real and I/Q output, both radix families) ----------------------------
 
-int bhwp_istft_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const void *d_Y, const void *d_x,
-                          bool pointers)
+// The first and the last step of the four checks functions; each puts its channel and n_fft refusals between them.
+// The descriptor as the overlap-add checks it, for the same descriptor with packed rows (the input strides mean something else here
+// and are checked by istft_io_checks).  The real pair passes the caller's whole flags, so the overlap-add refuses a foreign bit; the
+// I/Q pair (iq) has the shift bit of its own: it passes the normalise bit alone and refuses foreign bits afterwards.
+static int istft_descriptor_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, bool iq)
 {
-    int rc = bhwp_f32_checks(p, length, flags);
+    const uint32_t ola_flags = iq ? flags & BHW_OLA_NORMALIZE : flags;
+    int rc = bhwp_f32_checks(p, length, ola_flags);
     if (rc) return rc;
     if (!s) return bhwp_fail(BHW_ERR_BADARG, "stft descriptor is NULL");
     if (s->struct_size != sizeof(bhw_stft)) return bhwp_fail(BHW_ERR_BADARG, "bhw_stft.struct_size %u != %zu", s->struct_size, sizeof(bhw_stft));
-    // what the overlap-add checks, for the same descriptor with packed rows (the input strides mean something else here and are
-    // checked below)
     bhw_stft t;
     packed_strides(s, t);
-    rc = bhwp_stft_checks(p, length, &t, true, flags, nullptr, nullptr, false);
+    rc = bhwp_stft_checks(p, length, &t, true, ola_flags, nullptr, nullptr, false);
     if (rc) return rc;
-    if (s->channels != 1) return bhwp_fail(BHW_ERR_UNSUPPORTED, "channels %u: the fused inverse FFT gives real output (1)", s->channels);
-    if ((s->n_fft & (s->n_fft - 1)) || s->n_fft < (1ull << kFftMinLog) || s->n_fft > (1ull << kFftMaxLog))
-        return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu: the fused inverse FFT takes a power of two in %u..%u", (unsigned long long)s->n_fft,
-                         1u << kFftMinLog, 1u << kFftMaxLog);
-    const uint64_t T = s->samples, F = s->frames, K2 = s->n_fft + 2;          // 2K floats of a spectrum row
-    if (!T) return BHW_OK;                                           // (batch * frames * K is below the overlap-add's cap on n_fft)
-    if (s->y_stride && (s->y_stride < K2 || s->y_stride % 2))
-        return bhwp_fail(BHW_ERR_BADARG, "y_stride %llu: at least 2 * K = %llu floats, and even", (unsigned long long)s->y_stride,
-                         (unsigned long long)K2);
-    const uint64_t ys = s->y_stride ? s->y_stride : K2;
-    const unsigned __int128 ysig = (unsigned __int128)(F - 1) * ys + K2;
+    if (iq && (flags & ~kIcfftFlags)) return bhwp_fail(BHW_ERR_BADARG, "flags 0x%x (BHW_OLA_NORMALIZE, BHW_CFFT_SHIFT)", flags);
+    return BHW_OK;
+}
+
+// samples 0, the stride rules of the spectrum rows, the pointers.  W: the floats of a spectrum row (2K = n_fft + 2, or 2 * n_fft),
+// `row` its name in two messages; xf: the floats of an output sample (1, or 2 for I/Q).  batch * frames * W is below the overlap-add's
+// cap on n_fft.
+static int istft_io_checks(const bhw_stft *s, uint64_t W, const char *row, uint64_t xf, const void *d_Y, const void *d_x, bool pointers)
+{
+    const uint64_t T = s->samples, F = s->frames;
+    if (!T) return BHW_OK;
+    if (s->y_stride && (s->y_stride < W || s->y_stride % 2))
+        return bhwp_fail(BHW_ERR_BADARG, "y_stride %llu: at least %s = %llu floats, and even", (unsigned long long)s->y_stride, row,
+                         (unsigned long long)W);
+    const uint64_t ys = s->y_stride ? s->y_stride : W;
+    const unsigned __int128 ysig = (unsigned __int128)(F - 1) * ys + W;
     if (ysig > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "Y extent beyond 2^60 elements");
     if (s->y_batch_stride && (s->y_batch_stride < (uint64_t)ysig || s->y_batch_stride % 2))
-        return bhwp_fail(BHW_ERR_BADARG, "y_batch_stride %llu: at least (frames - 1) * y_stride + 2 * K = %llu floats, and even",
-                         (unsigned long long)s->y_batch_stride, (unsigned long long)ysig);
+        return bhwp_fail(BHW_ERR_BADARG, "y_batch_stride %llu: at least (frames - 1) * y_stride + %s = %llu floats, and even",
+                         (unsigned long long)s->y_batch_stride, row, (unsigned long long)ysig);
     if (!pointers) return BHW_OK;
     if (!d_x || !d_Y) return bhwp_fail(BHW_ERR_BADARG, "d_Y / d_x is NULL");
     if ((uintptr_t)d_Y % 8) return bhwp_fail(BHW_ERR_BADARG, "d_Y is not 8-byte aligned");
     if ((uintptr_t)d_x % 4) return bhwp_fail(BHW_ERR_BADARG, "d_x is not 4-byte aligned");
-    const uint64_t xs = s->x_stride ? s->x_stride : T, ybs = s->y_batch_stride ? s->y_batch_stride : F * ys;
-    const unsigned __int128 xe = (unsigned __int128)(s->batch - 1) * xs + T, ye = (unsigned __int128)(s->batch - 1) * ybs + ysig;
+    const uint64_t xs = s->x_stride ? s->x_stride : xf * T, ybs = s->y_batch_stride ? s->y_batch_stride : F * ys;
+    const unsigned __int128 xe = (unsigned __int128)(s->batch - 1) * xs + xf * T, ye = (unsigned __int128)(s->batch - 1) * ybs + ysig;
     if (xe > (1ull << 60) || ye > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "x or Y extent beyond 2^60 elements");
     const uint64_t xa = (uint64_t)(uintptr_t)d_x, ya = (uint64_t)(uintptr_t)d_Y, xb = (uint64_t)xe * 4u, yb = (uint64_t)ye * 4u;
     if (xa > UINT64_MAX - xb || ya > UINT64_MAX - yb) return bhwp_fail(BHW_ERR_BADARG, "x or Y range wraps the address space");
@@ -2861,15 +2868,17 @@ int bhwp_istft_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *
     return BHW_OK;
 }
 
-// The spans of a fused inverse call with fy slots per workgroup (BhwIstftFftPlan's fields of the same names): one function for the
-// real and the I/Q front.
-struct IstftSpans {
-    uint64_t t0, hop, halo, span, spans, groups, grid, trips;
-    bool halo_bound;
-};
-static IstftSpans istft_spans(uint64_t length, const bhw_stft *s, uint32_t fy)
+// The span plan of a fused inverse call (BhwIstftRuns in bhw_plan.h) with fy slots per workgroup, W floats in a spectrum row and xf
+// floats in an output sample: one function for the four fronts.
+static BhwIstftRuns istft_runs(uint64_t length, const bhw_stft *s, uint32_t flags, uint32_t fy, int route, uint64_t W, uint64_t xf)
 {
-    IstftSpans pl{};
+    BhwIstftRuns pl{};
+    pl.route = route;
+    pl.normalize = (flags & BHW_OLA_NORMALIZE) != 0;
+    pl.len = length;
+    pl.x_stride = s->x_stride ? s->x_stride : xf * s->samples;
+    pl.y_stride = s->y_stride ? s->y_stride : W;
+    pl.y_bstride = s->y_batch_stride ? s->y_batch_stride : s->frames * pl.y_stride;
     pl.t0 = s->pad - s->col0;
     const uint64_t end = pl.t0 + s->samples;                         // <= 2^40 + 2^34
     pl.hop = s->hop < end ? s->hop : end;
@@ -2890,6 +2899,86 @@ static IstftSpans istft_spans(uint64_t length, const bhw_stft *s, uint32_t fy)
     return pl;
 }
 
+// What a describe line says of a family's lanes, beside the span plan.
+struct IstftLanes {
+    uint32_t points, lpf, fy, cpl, lds_bytes;
+    uint32_t twiddles;    // the entries of the twiddle table, for the family whose line says them (cmfft's fold); 0: not said
+    char sched[48];
+};
+
+// The describe line of the four fused inverse calls, next to describe_runs_tail for the forward ones.  The families differ in their
+// name, their kernels, the twiddle count and, between real and I/Q output (iq), in three places: the bins phrase, whether the
+// transform has a pre-split, and the library call the heavy-overlap tail names.  lanes_of(IstftLanes &) fills the lanes and returns
+// the family's plan; it is not called at samples 0, where no plan exists (the hop clamp would be 0).
+template <typename LanesOf>
+static int describe_istft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags, const char *family,
+                          const char *k_direct, const char *k_table, bool iq, char *buf, uint64_t len, LanesOf lanes_of)
+{
+    if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
+    const char *route = ct ? "table" : "direct";
+    const char *norm = (flags & BHW_OLA_NORMALIZE) ? "normalised by the window envelope" : "not normalised";
+    const char *bins = !iq ? "" : (flags & BHW_CFFT_SHIFT) ? ", bins shifted" : ", bins in order";
+    if (!s->samples) {
+        snprintf(buf, len, "istft %s %s (L = %llu, n_fft %llu), %s%s: nothing (samples 0)", family, route, (unsigned long long)length,
+                 (unsigned long long)s->n_fft, norm, bins);
+        return BHW_OK;
+    }
+    IstftLanes ln{};
+    const BhwIstftRuns pl = lanes_of(ln);
+    char kern[64], twiddles[32] = "", heavy[128] = "";
+    kernel_name(p, ct, k_direct, k_table, false, kern, sizeof kern);
+    if (ln.twiddles) snprintf(twiddles, sizeof twiddles, ", %u twiddles", ln.twiddles);
+    // the repeats: every span but a signal's first transforms up to `halo` frames that the span before it transforms too (span >= 1:
+    // the quotient needs no guard)
+    const uint64_t repeat = pl.spans > 1 ? 100 * pl.halo / (pl.span + pl.halo) : 0;
+    if (pl.halo_bound && pl.groups < kIfftTargetGroups / 4)
+        snprintf(heavy, sizeof heavy, "; heavy overlap: the halo sets S and few workgroups run (%s + istft overlap-add may be faster)",
+                 iq ? "ifft" : "irfft");
+    snprintf(buf, len, "istft %s %s (L = %llu, n_fft %llu, col0 %llu, pad %llu: t0 = %llu), %s%s: %s, %llu signals x %llu frames = %llu rows, "
+             "inverse complex FFT of %u points in %spasses %s%s, %u lanes per row x %u spans per workgroup, %u columns per lane, "
+             "spans of S = %llu frames + halo %llu (%llu spans per signal, up to %llu frames a span, %llu%% of the transforms repeated), "
+             "%llu groups, grid %llu x %u lanes, %u bytes of LDS%s%s", family, route, (unsigned long long)length,
+             (unsigned long long)s->n_fft, (unsigned long long)s->col0, (unsigned long long)s->pad, (unsigned long long)pl.t0, norm, bins, kern,
+             (unsigned long long)s->batch, (unsigned long long)s->frames, (unsigned long long)(s->batch * s->frames), ln.points,
+             iq ? "" : "pre-split + ", ln.sched, iq ? " (no split)" : "", ln.lpf, ln.fy, ln.cpl, (unsigned long long)pl.span,
+             (unsigned long long)pl.halo, (unsigned long long)pl.spans, (unsigned long long)pl.trips, (unsigned long long)repeat,
+             (unsigned long long)pl.groups, (unsigned long long)pl.grid, kFftBlock, ln.lds_bytes, twiddles, heavy);
+    return BHW_OK;
+}
+
+// the schedule text of a plan's radix fields (the forward plans' formatters)
+template <typename Plan>
+static void istft_fft_schedule(const Plan &pl, IstftLanes &ln)
+{
+    BhwStftFftPlan f{};
+    f.radix4 = pl.radix4;
+    f.radix2 = pl.radix2;
+    bhwp_stft_fft_schedule(f, ln.sched, sizeof ln.sched);
+}
+
+template <typename Plan>
+static void istft_mfft_schedule(const Plan &pl, IstftLanes &ln)
+{
+    BhwStftMfftPlan f{};
+    f.passes = pl.passes;
+    for (uint32_t i = 0; i < pl.passes; ++i) f.radix[i] = pl.radix[i];
+    bhwp_stft_mfft_schedule(f, ln.sched, sizeof ln.sched);
+}
+
+// ---- fused inverse real FFT, window and overlap-add -----------------------------------------------------------------------------------------
+
+int bhwp_istft_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const void *d_Y, const void *d_x,
+                          bool pointers)
+{
+    const int rc = istft_descriptor_checks(p, length, s, flags, false);
+    if (rc) return rc;
+    if (s->channels != 1) return bhwp_fail(BHW_ERR_UNSUPPORTED, "channels %u: the fused inverse FFT gives real output (1)", s->channels);
+    if ((s->n_fft & (s->n_fft - 1)) || s->n_fft < (1ull << kFftMinLog) || s->n_fft > (1ull << kFftMaxLog))
+        return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu: the fused inverse FFT takes a power of two in %u..%u", (unsigned long long)s->n_fft,
+                         1u << kFftMinLog, 1u << kFftMaxLog);
+    return istft_io_checks(s, s->n_fft + 2, "2 * K", 1, d_Y, d_x, pointers);
+}
+
 BhwIstftFftPlan bhwp_istft_fft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, bool from_table)
 {
     // the lane layout and the radix schedule are the forward's
@@ -2897,8 +2986,7 @@ BhwIstftFftPlan bhwp_istft_fft_plan(const bhw_params *p, uint64_t length, const 
     fw.frames = 0;
     const BhwStftFftPlan f = bhwp_stft_fft_plan(p, length, &fw, 0, from_table);
     BhwIstftFftPlan pl{};
-    pl.route = f.route;
-    pl.normalize = (flags & BHW_OLA_NORMALIZE) != 0;
+    static_cast<BhwIstftRuns &>(pl) = istft_runs(length, s, flags, f.fy, f.route, s->n_fft + 2, 1);
     pl.log2n = f.log2n;
     pl.m = f.m;
     pl.lpf = f.lpf;
@@ -2907,54 +2995,18 @@ BhwIstftFftPlan bhwp_istft_fft_plan(const bhw_params *p, uint64_t length, const 
     pl.radix4 = f.radix4;
     pl.radix2 = f.radix2;
     pl.lds_bytes = 2u * pl.fy * pl.m * 8u + pl.m * 8u + (uint32_t)s->n_fft * 4u;
-    pl.len = length;
-    pl.x_stride = s->x_stride ? s->x_stride : s->samples;
-    pl.y_stride = s->y_stride ? s->y_stride : s->n_fft + 2;
-    pl.y_bstride = s->y_batch_stride ? s->y_batch_stride : s->frames * pl.y_stride;
-    const IstftSpans sp = istft_spans(length, s, pl.fy);
-    pl.t0 = sp.t0;
-    pl.hop = sp.hop;
-    pl.halo = sp.halo;
-    pl.halo_bound = sp.halo_bound;
-    pl.span = sp.span;
-    pl.spans = sp.spans;
-    pl.groups = sp.groups;
-    pl.grid = sp.grid;
-    pl.trips = sp.trips;
     return pl;
 }
 
 int bhwp_describe_istft_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf,
                             uint64_t len)
 {
-    if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
-    const char *route = ct ? "table" : "direct";
-    const char *norm = (flags & BHW_OLA_NORMALIZE) ? "normalised by the window envelope" : "not normalised";
-    if (!s->samples) {
-        snprintf(buf, len, "istft fft %s (L = %llu, n_fft %llu), %s: nothing (samples 0)", route, (unsigned long long)length,
-                 (unsigned long long)s->n_fft, norm);
-        return BHW_OK;
-    }
-    const BhwIstftFftPlan pl = bhwp_istft_fft_plan(p, length, s, flags, ct != nullptr);
-    BhwStftFftPlan f{};
-    f.radix4 = pl.radix4;
-    f.radix2 = pl.radix2;
-    char kern[64], sched[48];
-    kernel_name(p, ct, "k_istft_fft_direct", "k_istft_fft_table", false, kern, sizeof kern);
-    bhwp_stft_fft_schedule(f, sched, sizeof sched);
-    // the repeats: every span but a signal's first transforms up to `halo` frames that the span before it transforms too
-    const uint64_t repeat = pl.spans > 1 ? (pl.halo < pl.span + pl.halo ? 100 * pl.halo / (pl.span + pl.halo) : 0) : 0;
-    const bool few = pl.halo_bound && pl.groups < kIfftTargetGroups / 4;
-    snprintf(buf, len, "istft fft %s (L = %llu, n_fft %llu, col0 %llu, pad %llu: t0 = %llu), %s: %s, %llu signals x %llu frames = %llu rows, "
-             "inverse complex FFT of %u points in pre-split + passes %s, %u lanes per row x %u spans per workgroup, %u columns per lane, "
-             "spans of S = %llu frames + halo %llu (%llu spans per signal, up to %llu frames a span, %llu%% of the transforms repeated), "
-             "%llu groups, grid %llu x %u lanes, %u bytes of LDS%s", route, (unsigned long long)length, (unsigned long long)s->n_fft,
-             (unsigned long long)s->col0, (unsigned long long)s->pad, (unsigned long long)pl.t0, norm, kern, (unsigned long long)s->batch,
-             (unsigned long long)s->frames, (unsigned long long)(s->batch * s->frames), pl.m, sched, pl.lpf, pl.fy, pl.cpl,
-             (unsigned long long)pl.span, (unsigned long long)pl.halo, (unsigned long long)pl.spans, (unsigned long long)pl.trips,
-             (unsigned long long)repeat, (unsigned long long)pl.groups, (unsigned long long)pl.grid, kFftBlock, pl.lds_bytes,
-             few ? "; heavy overlap: the halo sets S and few workgroups run (irfft + istft overlap-add may be faster)" : "");
-    return BHW_OK;
+    return describe_istft(p, ct, length, s, flags, "fft", "k_istft_fft_direct", "k_istft_fft_table", false, buf, len, [&](IstftLanes &ln) {
+        const BhwIstftFftPlan pl = bhwp_istft_fft_plan(p, length, s, flags, ct != nullptr);
+        ln.points = pl.m, ln.lpf = pl.lpf, ln.fy = pl.fy, ln.cpl = pl.cpl, ln.lds_bytes = pl.lds_bytes;
+        istft_fft_schedule(pl, ln);
+        return static_cast<const BhwIstftRuns &>(pl);
+    });
 }
 
 // ---- fused inverse mixed-radix FFT, window and overlap-add ----------------------------------------------------------------------------------
@@ -2962,15 +3014,7 @@ int bhwp_describe_istft_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64_
 int bhwp_istft_mfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const void *d_Y, const void *d_x,
                            bool pointers)
 {
-    int rc = bhwp_f32_checks(p, length, flags);
-    if (rc) return rc;
-    if (!s) return bhwp_fail(BHW_ERR_BADARG, "stft descriptor is NULL");
-    if (s->struct_size != sizeof(bhw_stft)) return bhwp_fail(BHW_ERR_BADARG, "bhw_stft.struct_size %u != %zu", s->struct_size, sizeof(bhw_stft));
-    // what the overlap-add checks, for the same descriptor with packed rows (the input strides mean something else here and are
-    // checked below)
-    bhw_stft t;
-    packed_strides(s, t);
-    rc = bhwp_stft_checks(p, length, &t, true, flags, nullptr, nullptr, false);
+    const int rc = istft_descriptor_checks(p, length, s, flags, false);
     if (rc) return rc;
     if (s->channels != 1)
         return bhwp_fail(BHW_ERR_UNSUPPORTED, "channels %u: the mixed-radix fused inverse FFT gives real output (1)", s->channels);
@@ -2980,28 +3024,7 @@ int bhwp_istft_mfft_checks(const bhw_params *p, uint64_t length, const bhw_stft 
     if (!bhwp_mfft_supported(s->n_fft))
         return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu: the mixed-radix fused inverse FFT takes an even 2^a 3^b 5^c in %u..%u",
                          (unsigned long long)s->n_fft, kMfftMinN, kMfftMaxN);
-    const uint64_t T = s->samples, F = s->frames, K2 = s->n_fft + 2;          // 2K floats of a spectrum row
-    if (!T) return BHW_OK;                                           // (batch * frames * K is below the overlap-add's cap on n_fft)
-    if (s->y_stride && (s->y_stride < K2 || s->y_stride % 2))
-        return bhwp_fail(BHW_ERR_BADARG, "y_stride %llu: at least 2 * K = %llu floats, and even", (unsigned long long)s->y_stride,
-                         (unsigned long long)K2);
-    const uint64_t ys = s->y_stride ? s->y_stride : K2;
-    const unsigned __int128 ysig = (unsigned __int128)(F - 1) * ys + K2;
-    if (ysig > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "Y extent beyond 2^60 elements");
-    if (s->y_batch_stride && (s->y_batch_stride < (uint64_t)ysig || s->y_batch_stride % 2))
-        return bhwp_fail(BHW_ERR_BADARG, "y_batch_stride %llu: at least (frames - 1) * y_stride + 2 * K = %llu floats, and even",
-                         (unsigned long long)s->y_batch_stride, (unsigned long long)ysig);
-    if (!pointers) return BHW_OK;
-    if (!d_x || !d_Y) return bhwp_fail(BHW_ERR_BADARG, "d_Y / d_x is NULL");
-    if ((uintptr_t)d_Y % 8) return bhwp_fail(BHW_ERR_BADARG, "d_Y is not 8-byte aligned");
-    if ((uintptr_t)d_x % 4) return bhwp_fail(BHW_ERR_BADARG, "d_x is not 4-byte aligned");
-    const uint64_t xs = s->x_stride ? s->x_stride : T, ybs = s->y_batch_stride ? s->y_batch_stride : F * ys;
-    const unsigned __int128 xe = (unsigned __int128)(s->batch - 1) * xs + T, ye = (unsigned __int128)(s->batch - 1) * ybs + ysig;
-    if (xe > (1ull << 60) || ye > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "x or Y extent beyond 2^60 elements");
-    const uint64_t xa = (uint64_t)(uintptr_t)d_x, ya = (uint64_t)(uintptr_t)d_Y, xb = (uint64_t)xe * 4u, yb = (uint64_t)ye * 4u;
-    if (xa > UINT64_MAX - xb || ya > UINT64_MAX - yb) return bhwp_fail(BHW_ERR_BADARG, "x or Y range wraps the address space");
-    if (xa < ya + yb && ya < xa + xb) return bhwp_fail(BHW_ERR_BADARG, "d_Y and d_x overlap");
-    return BHW_OK;
+    return istft_io_checks(s, s->n_fft + 2, "2 * K", 1, d_Y, d_x, pointers);
 }
 
 BhwIstftMfftPlan bhwp_istft_mfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, bool from_table)
@@ -3011,8 +3034,7 @@ BhwIstftMfftPlan bhwp_istft_mfft_plan(const bhw_params *p, uint64_t length, cons
     fw.frames = 0;
     const BhwStftMfftPlan f = bhwp_stft_mfft_plan(p, length, &fw, 0, nullptr, from_table);
     BhwIstftMfftPlan pl{};
-    pl.route = f.route;
-    pl.normalize = (flags & BHW_OLA_NORMALIZE) != 0;
+    static_cast<BhwIstftRuns &>(pl) = istft_runs(length, s, flags, f.fy, f.route, s->n_fft + 2, 1);
     pl.m = f.m;
     pl.lpf = f.lpf;
     pl.fy = f.fy;
@@ -3020,109 +3042,27 @@ BhwIstftMfftPlan bhwp_istft_mfft_plan(const bhw_params *p, uint64_t length, cons
     pl.passes = f.passes;
     for (uint32_t i = 0; i < f.passes; ++i) pl.radix[i] = f.radix[i];
     pl.lds_bytes = 2u * pl.fy * pl.m * 8u + pl.m * 8u + (uint32_t)s->n_fft * 4u;
-    pl.len = length;
-    pl.x_stride = s->x_stride ? s->x_stride : s->samples;
-    pl.y_stride = s->y_stride ? s->y_stride : s->n_fft + 2;
-    pl.y_bstride = s->y_batch_stride ? s->y_batch_stride : s->frames * pl.y_stride;
-    const IstftSpans sp = istft_spans(length, s, pl.fy);
-    pl.t0 = sp.t0;
-    pl.hop = sp.hop;
-    pl.halo = sp.halo;
-    pl.halo_bound = sp.halo_bound;
-    pl.span = sp.span;
-    pl.spans = sp.spans;
-    pl.groups = sp.groups;
-    pl.grid = sp.grid;
-    pl.trips = sp.trips;
     return pl;
 }
 
 int bhwp_describe_istft_mfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf,
                              uint64_t len)
 {
-    if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
-    const char *route = ct ? "table" : "direct";
-    const char *norm = (flags & BHW_OLA_NORMALIZE) ? "normalised by the window envelope" : "not normalised";
-    if (!s->samples) {
-        snprintf(buf, len, "istft mfft %s (L = %llu, n_fft %llu), %s: nothing (samples 0)", route, (unsigned long long)length,
-                 (unsigned long long)s->n_fft, norm);
-        return BHW_OK;
-    }
-    const BhwIstftMfftPlan pl = bhwp_istft_mfft_plan(p, length, s, flags, ct != nullptr);
-    BhwStftMfftPlan f{};
-    f.passes = pl.passes;
-    for (uint32_t i = 0; i < pl.passes; ++i) f.radix[i] = pl.radix[i];
-    char kern[64], sched[48];
-    kernel_name(p, ct, "k_istft_mfft_direct", "k_istft_mfft_table", false, kern, sizeof kern);
-    bhwp_stft_mfft_schedule(f, sched, sizeof sched);
-    // the repeats: every span but a signal's first transforms up to `halo` frames that the span before it transforms too
-    const uint64_t repeat = pl.spans > 1 ? (pl.halo < pl.span + pl.halo ? 100 * pl.halo / (pl.span + pl.halo) : 0) : 0;
-    const bool few = pl.halo_bound && pl.groups < kIfftTargetGroups / 4;
-    snprintf(buf, len, "istft mfft %s (L = %llu, n_fft %llu, col0 %llu, pad %llu: t0 = %llu), %s: %s, %llu signals x %llu frames = %llu rows, "
-             "inverse complex FFT of %u points in pre-split + passes %s, %u lanes per row x %u spans per workgroup, %u columns per lane, "
-             "spans of S = %llu frames + halo %llu (%llu spans per signal, up to %llu frames a span, %llu%% of the transforms repeated), "
-             "%llu groups, grid %llu x %u lanes, %u bytes of LDS%s", route, (unsigned long long)length, (unsigned long long)s->n_fft,
-             (unsigned long long)s->col0, (unsigned long long)s->pad, (unsigned long long)pl.t0, norm, kern, (unsigned long long)s->batch,
-             (unsigned long long)s->frames, (unsigned long long)(s->batch * s->frames), pl.m, sched, pl.lpf, pl.fy, pl.cpl,
-             (unsigned long long)pl.span, (unsigned long long)pl.halo, (unsigned long long)pl.spans, (unsigned long long)pl.trips,
-             (unsigned long long)repeat, (unsigned long long)pl.groups, (unsigned long long)pl.grid, kFftBlock, pl.lds_bytes,
-             few ? "; heavy overlap: the halo sets S and few workgroups run (irfft + istft overlap-add may be faster)" : "");
-    return BHW_OK;
+    return describe_istft(p, ct, length, s, flags, "mfft", "k_istft_mfft_direct", "k_istft_mfft_table", false, buf, len, [&](IstftLanes &ln) {
+        const BhwIstftMfftPlan pl = bhwp_istft_mfft_plan(p, length, s, flags, ct != nullptr);
+        ln.points = pl.m, ln.lpf = pl.lpf, ln.fy = pl.fy, ln.cpl = pl.cpl, ln.lds_bytes = pl.lds_bytes;
+        istft_mfft_schedule(pl, ln);
+        return static_cast<const BhwIstftRuns &>(pl);
+    });
 }
 
 // ---- fused inverse complex FFT, window and overlap-add for I/Q output ----------------------------------------------------------------------
 
-// Steps 1 and 2 of the I/Q inverse calls (bhw_istft_cfft_f32_*, bhw_istft_cmfft_f32_*): the descriptor as the overlap-add checks it,
-// then the flag bits.
-static int iq_inverse_descriptor_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags)
-{
-    // 1. what the overlap-add checks, for the same descriptor with packed rows (the input strides are checked below; the shift bit is
-    //    this call's own)
-    const uint32_t ola_flags = flags & BHW_OLA_NORMALIZE;
-    int rc = bhwp_f32_checks(p, length, ola_flags);
-    if (rc) return rc;
-    if (!s) return bhwp_fail(BHW_ERR_BADARG, "stft descriptor is NULL");
-    if (s->struct_size != sizeof(bhw_stft)) return bhwp_fail(BHW_ERR_BADARG, "bhw_stft.struct_size %u != %zu", s->struct_size, sizeof(bhw_stft));
-    bhw_stft t;
-    packed_strides(s, t);
-    rc = bhwp_stft_checks(p, length, &t, true, ola_flags, nullptr, nullptr, false);
-    if (rc) return rc;
-    // 2.
-    if (flags & ~kIcfftFlags) return bhwp_fail(BHW_ERR_BADARG, "flags 0x%x (BHW_OLA_NORMALIZE, BHW_CFFT_SHIFT)", flags);
-    return BHW_OK;
-}
-
-// Steps 4 and 5 of the same calls: samples 0, the stride rules of the spectrum rows, the pointers.
-static int iq_inverse_io_checks(const bhw_stft *s, const void *d_Y, const void *d_x, bool pointers)
-{
-    const uint64_t T = s->samples, F = s->frames, W = 2 * s->n_fft;           // floats of a spectrum row
-    if (!T) return BHW_OK;
-    if (s->y_stride && (s->y_stride < W || s->y_stride % 2))
-        return bhwp_fail(BHW_ERR_BADARG, "y_stride %llu: at least 2 * n_fft = %llu floats, and even", (unsigned long long)s->y_stride,
-                         (unsigned long long)W);
-    const uint64_t ys = s->y_stride ? s->y_stride : W;
-    const unsigned __int128 ysig = (unsigned __int128)(F - 1) * ys + W;
-    if (ysig > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "Y extent beyond 2^60 elements");
-    if (s->y_batch_stride && (s->y_batch_stride < (uint64_t)ysig || s->y_batch_stride % 2))
-        return bhwp_fail(BHW_ERR_BADARG, "y_batch_stride %llu: at least (frames - 1) * y_stride + 2 * n_fft = %llu floats, and even",
-                         (unsigned long long)s->y_batch_stride, (unsigned long long)ysig);
-    if (!pointers) return BHW_OK;
-    if (!d_x || !d_Y) return bhwp_fail(BHW_ERR_BADARG, "d_Y / d_x is NULL");
-    if ((uintptr_t)d_Y % 8) return bhwp_fail(BHW_ERR_BADARG, "d_Y is not 8-byte aligned");
-    if ((uintptr_t)d_x % 4) return bhwp_fail(BHW_ERR_BADARG, "d_x is not 4-byte aligned");
-    const uint64_t xs = s->x_stride ? s->x_stride : 2 * T, ybs = s->y_batch_stride ? s->y_batch_stride : F * ys;
-    const unsigned __int128 xe = (unsigned __int128)(s->batch - 1) * xs + 2 * T, ye = (unsigned __int128)(s->batch - 1) * ybs + ysig;
-    if (xe > (1ull << 60) || ye > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "x or Y extent beyond 2^60 elements");
-    const uint64_t xa = (uint64_t)(uintptr_t)d_x, ya = (uint64_t)(uintptr_t)d_Y, xb = (uint64_t)xe * 4u, yb = (uint64_t)ye * 4u;
-    if (xa > UINT64_MAX - xb || ya > UINT64_MAX - yb) return bhwp_fail(BHW_ERR_BADARG, "x or Y range wraps the address space");
-    if (xa < ya + yb && ya < xa + xb) return bhwp_fail(BHW_ERR_BADARG, "d_Y and d_x overlap");
-    return BHW_OK;
-}
-
 int bhwp_istft_cfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const void *d_Y, const void *d_x,
                            bool pointers)
 {
-    const int rc = iq_inverse_descriptor_checks(p, length, s, flags);
+    // 1., 2. (the steps of include/bhw.h)
+    const int rc = istft_descriptor_checks(p, length, s, flags, true);
     if (rc) return rc;
     // 3.
     if (s->channels != 2)
@@ -3132,7 +3072,7 @@ int bhwp_istft_cfft_checks(const bhw_params *p, uint64_t length, const bhw_stft 
         return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu: the fused inverse complex FFT takes a power of two in %u..%u",
                          (unsigned long long)s->n_fft, 1u << kCfftMinLog, 1u << kCfftMaxLog);
     // 4., 5.
-    return iq_inverse_io_checks(s, d_Y, d_x, pointers);
+    return istft_io_checks(s, 2 * s->n_fft, "2 * n_fft", 2, d_Y, d_x, pointers);
 }
 
 BhwIstftCfftPlan bhwp_istft_cfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, bool from_table)
@@ -3142,8 +3082,7 @@ BhwIstftCfftPlan bhwp_istft_cfft_plan(const bhw_params *p, uint64_t length, cons
     fw.frames = 0;
     const BhwStftCfftPlan f = bhwp_stft_cfft_plan(p, length, &fw, 0, from_table);
     BhwIstftCfftPlan pl{};
-    pl.route = f.route;
-    pl.normalize = (flags & BHW_OLA_NORMALIZE) != 0;
+    static_cast<BhwIstftRuns &>(pl) = istft_runs(length, s, flags, f.fy, f.route, 2 * s->n_fft, 2);
     pl.shifted = (flags & BHW_CFFT_SHIFT) != 0;
     pl.log2n = f.log2n;
     pl.n = f.n;
@@ -3153,55 +3092,18 @@ BhwIstftCfftPlan bhwp_istft_cfft_plan(const bhw_params *p, uint64_t length, cons
     pl.radix4 = f.radix4;
     pl.radix2 = f.radix2;
     pl.lds_bytes = 2u * pl.fy * pl.n * 8u + pl.n / 2u * 8u + pl.n * 4u;
-    pl.len = length;
-    pl.x_stride = s->x_stride ? s->x_stride : 2 * s->samples;
-    pl.y_stride = s->y_stride ? s->y_stride : 2 * s->n_fft;
-    pl.y_bstride = s->y_batch_stride ? s->y_batch_stride : s->frames * pl.y_stride;
-    const IstftSpans sp = istft_spans(length, s, pl.fy);
-    pl.t0 = sp.t0;
-    pl.hop = sp.hop;
-    pl.halo = sp.halo;
-    pl.halo_bound = sp.halo_bound;
-    pl.span = sp.span;
-    pl.spans = sp.spans;
-    pl.groups = sp.groups;
-    pl.grid = sp.grid;
-    pl.trips = sp.trips;
     return pl;
 }
 
 int bhwp_describe_istft_cfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf,
                              uint64_t len)
 {
-    if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
-    const char *route = ct ? "table" : "direct";
-    const char *norm = (flags & BHW_OLA_NORMALIZE) ? "normalised by the window envelope" : "not normalised";
-    const char *bins = (flags & BHW_CFFT_SHIFT) ? "bins shifted" : "bins in order";
-    if (!s->samples) {
-        snprintf(buf, len, "istft cfft %s (L = %llu, n_fft %llu), %s, %s: nothing (samples 0)", route, (unsigned long long)length,
-                 (unsigned long long)s->n_fft, norm, bins);
-        return BHW_OK;
-    }
-    const BhwIstftCfftPlan pl = bhwp_istft_cfft_plan(p, length, s, flags, ct != nullptr);
-    BhwStftFftPlan f{};
-    f.radix4 = pl.radix4;
-    f.radix2 = pl.radix2;
-    char kern[64], sched[48];
-    kernel_name(p, ct, "k_istft_cfft_direct", "k_istft_cfft_table", false, kern, sizeof kern);
-    bhwp_stft_fft_schedule(f, sched, sizeof sched);
-    // the repeats: every span but a signal's first transforms up to `halo` frames that the span before it transforms too
-    const uint64_t repeat = pl.spans > 1 ? 100 * pl.halo / (pl.span + pl.halo) : 0;
-    const bool few = pl.halo_bound && pl.groups < kIfftTargetGroups / 4;
-    snprintf(buf, len, "istft cfft %s (L = %llu, n_fft %llu, col0 %llu, pad %llu: t0 = %llu), %s, %s: %s, %llu signals x %llu frames = %llu rows, "
-             "inverse complex FFT of %u points in passes %s (no split), %u lanes per row x %u spans per workgroup, %u columns per lane, "
-             "spans of S = %llu frames + halo %llu (%llu spans per signal, up to %llu frames a span, %llu%% of the transforms repeated), "
-             "%llu groups, grid %llu x %u lanes, %u bytes of LDS%s", route, (unsigned long long)length, (unsigned long long)s->n_fft,
-             (unsigned long long)s->col0, (unsigned long long)s->pad, (unsigned long long)pl.t0, norm, bins, kern, (unsigned long long)s->batch,
-             (unsigned long long)s->frames, (unsigned long long)(s->batch * s->frames), pl.n, sched, pl.lpf, pl.fy, pl.cpl,
-             (unsigned long long)pl.span, (unsigned long long)pl.halo, (unsigned long long)pl.spans, (unsigned long long)pl.trips,
-             (unsigned long long)repeat, (unsigned long long)pl.groups, (unsigned long long)pl.grid, kFftBlock, pl.lds_bytes,
-             few ? "; heavy overlap: the halo sets S and few workgroups run (ifft + istft overlap-add may be faster)" : "");
-    return BHW_OK;
+    return describe_istft(p, ct, length, s, flags, "cfft", "k_istft_cfft_direct", "k_istft_cfft_table", true, buf, len, [&](IstftLanes &ln) {
+        const BhwIstftCfftPlan pl = bhwp_istft_cfft_plan(p, length, s, flags, ct != nullptr);
+        ln.points = pl.n, ln.lpf = pl.lpf, ln.fy = pl.fy, ln.cpl = pl.cpl, ln.lds_bytes = pl.lds_bytes;
+        istft_fft_schedule(pl, ln);
+        return static_cast<const BhwIstftRuns &>(pl);
+    });
 }
 
 // ---- fused inverse mixed-radix complex FFT, window and overlap-add for I/Q output ----------------------------------------------------------
@@ -3209,7 +3111,7 @@ int bhwp_describe_istft_cfft(const bhw_params *p, const BhwCordicCfg *ct, uint64
 int bhwp_istft_cmfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const void *d_Y, const void *d_x,
                             bool pointers)
 {
-    const int rc = iq_inverse_descriptor_checks(p, length, s, flags);
+    const int rc = istft_descriptor_checks(p, length, s, flags, true);
     if (rc) return rc;
     // 3.: each refusal names the route that takes the call
     if (s->channels != 2)
@@ -3222,7 +3124,7 @@ int bhwp_istft_cmfft_checks(const bhw_params *p, uint64_t length, const bhw_stft
         return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu: the mixed-radix fused inverse complex FFT takes 2^a 3^b 5^c in %u..%u",
                          (unsigned long long)s->n_fft, kCmfftMinN, kCmfftMaxN);
     // 4., 5.
-    return iq_inverse_io_checks(s, d_Y, d_x, pointers);
+    return istft_io_checks(s, 2 * s->n_fft, "2 * n_fft", 2, d_Y, d_x, pointers);
 }
 
 BhwIstftCmfftPlan bhwp_istft_cmfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, bool from_table)
@@ -3232,8 +3134,7 @@ BhwIstftCmfftPlan bhwp_istft_cmfft_plan(const bhw_params *p, uint64_t length, co
     fw.frames = 0;
     const BhwStftCmfftPlan f = bhwp_stft_cmfft_plan(p, length, &fw, 0, from_table);
     BhwIstftCmfftPlan pl{};
-    pl.route = f.route;
-    pl.normalize = (flags & BHW_OLA_NORMALIZE) != 0;
+    static_cast<BhwIstftRuns &>(pl) = istft_runs(length, s, flags, f.fy, f.route, 2 * s->n_fft, 2);
     pl.shifted = (flags & BHW_CFFT_SHIFT) != 0;
     pl.n = f.n;
     pl.fold = f.fold;
@@ -3243,55 +3144,18 @@ BhwIstftCmfftPlan bhwp_istft_cmfft_plan(const bhw_params *p, uint64_t length, co
     pl.passes = f.passes;
     for (uint32_t i = 0; i < f.passes; ++i) pl.radix[i] = f.radix[i];
     pl.lds_bytes = 2u * pl.fy * pl.n * 8u + pl.fold * 8u + pl.n * 4u;
-    pl.len = length;
-    pl.x_stride = s->x_stride ? s->x_stride : 2 * s->samples;
-    pl.y_stride = s->y_stride ? s->y_stride : 2 * s->n_fft;
-    pl.y_bstride = s->y_batch_stride ? s->y_batch_stride : s->frames * pl.y_stride;
-    const IstftSpans sp = istft_spans(length, s, pl.fy);
-    pl.t0 = sp.t0;
-    pl.hop = sp.hop;
-    pl.halo = sp.halo;
-    pl.halo_bound = sp.halo_bound;
-    pl.span = sp.span;
-    pl.spans = sp.spans;
-    pl.groups = sp.groups;
-    pl.grid = sp.grid;
-    pl.trips = sp.trips;
     return pl;
 }
 
 int bhwp_describe_istft_cmfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags, char *buf,
                               uint64_t len)
 {
-    if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
-    const char *route = ct ? "table" : "direct";
-    const char *norm = (flags & BHW_OLA_NORMALIZE) ? "normalised by the window envelope" : "not normalised";
-    const char *bins = (flags & BHW_CFFT_SHIFT) ? "bins shifted" : "bins in order";
-    if (!s->samples) {
-        snprintf(buf, len, "istft cmfft %s (L = %llu, n_fft %llu), %s, %s: nothing (samples 0)", route, (unsigned long long)length,
-                 (unsigned long long)s->n_fft, norm, bins);
-        return BHW_OK;
-    }
-    const BhwIstftCmfftPlan pl = bhwp_istft_cmfft_plan(p, length, s, flags, ct != nullptr);
-    BhwStftMfftPlan f{};
-    f.passes = pl.passes;
-    for (uint32_t i = 0; i < pl.passes; ++i) f.radix[i] = pl.radix[i];
-    char kern[64], sched[48];
-    kernel_name(p, ct, "k_istft_cmfft_direct", "k_istft_cmfft_table", false, kern, sizeof kern);
-    bhwp_stft_mfft_schedule(f, sched, sizeof sched);
-    // the repeats: every span but a signal's first transforms up to `halo` frames that the span before it transforms too
-    const uint64_t repeat = pl.spans > 1 ? 100 * pl.halo / (pl.span + pl.halo) : 0;
-    const bool few = pl.halo_bound && pl.groups < kIfftTargetGroups / 4;
-    snprintf(buf, len, "istft cmfft %s (L = %llu, n_fft %llu, col0 %llu, pad %llu: t0 = %llu), %s, %s: %s, %llu signals x %llu frames = %llu rows, "
-             "inverse complex FFT of %u points in passes %s (no split), %u lanes per row x %u spans per workgroup, %u columns per lane, "
-             "spans of S = %llu frames + halo %llu (%llu spans per signal, up to %llu frames a span, %llu%% of the transforms repeated), "
-             "%llu groups, grid %llu x %u lanes, %u bytes of LDS, %u twiddles%s", route, (unsigned long long)length,
-             (unsigned long long)s->n_fft, (unsigned long long)s->col0, (unsigned long long)s->pad, (unsigned long long)pl.t0, norm, bins, kern,
-             (unsigned long long)s->batch, (unsigned long long)s->frames, (unsigned long long)(s->batch * s->frames), pl.n, sched, pl.lpf, pl.fy,
-             pl.cpl, (unsigned long long)pl.span, (unsigned long long)pl.halo, (unsigned long long)pl.spans, (unsigned long long)pl.trips,
-             (unsigned long long)repeat, (unsigned long long)pl.groups, (unsigned long long)pl.grid, kFftBlock, pl.lds_bytes, pl.fold,
-             few ? "; heavy overlap: the halo sets S and few workgroups run (ifft + istft overlap-add may be faster)" : "");
-    return BHW_OK;
+    return describe_istft(p, ct, length, s, flags, "cmfft", "k_istft_cmfft_direct", "k_istft_cmfft_table", true, buf, len, [&](IstftLanes &ln) {
+        const BhwIstftCmfftPlan pl = bhwp_istft_cmfft_plan(p, length, s, flags, ct != nullptr);
+        ln.points = pl.n, ln.lpf = pl.lpf, ln.fy = pl.fy, ln.cpl = pl.cpl, ln.lds_bytes = pl.lds_bytes, ln.twiddles = pl.fold;
+        istft_mfft_schedule(pl, ln);
+        return static_cast<const BhwIstftRuns &>(pl);
+    });
 }
 
 // ---- the pure entry points of the C ABI (include/bhw.h) -------------------------------------------------------------------------------

@@ -851,11 +851,12 @@ int  bhwk_hold_mfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinC
 // twiddles and the n_fft floats of the window (a function of n_fft alone, 64 KiB at 4096).
 constexpr uint32_t kIfftTargetGroups = 1024;          // span groups the planner asks for before spans grow (four per CU)
 constexpr uint32_t kIfftHaloFactor = 4;               // S >= 4 * halo
-struct BhwIstftFftPlan {
+// The span plan of every fused inverse call (real and I/Q output, both radix families), from the descriptor, the flags, the fy slots
+// of the family's forward plan, the floats of a spectrum row and the floats of an output sample: one text (istft_runs in
+// bhw_plan.cpp) for the four bhwp_istft_*_plan.
+struct BhwIstftRuns {
     int route;            // BHWP_FRAMES_DIRECT or BHWP_FRAMES_TABLE
     bool normalize;
-    uint32_t log2n, m, lpf, fy, cpl, radix4, radix2;   // as BhwStftFftPlan
-    uint32_t lds_bytes;   // 2 * fy * M * 8 + M * 8 + n_fft * 4  (<= 64 KiB)
     uint64_t t0;          // pad - col0: output t is position w = t + t0
     uint64_t hop;         // min(hop, t0 + samples): a larger hop leaves frame 0 alone under the outputs either way
     uint64_t halo;        // ceil(L / hop) - 1
@@ -865,8 +866,13 @@ struct BhwIstftFftPlan {
     uint64_t grid;        // min(groups, kFftMaxGrid)
     uint64_t trips;       // frames one slot walks at most: min(S + halo, frames)
     bool halo_bound;      // S was set by the halo, not by the grid target: few workgroups under heavy overlap
-    uint64_t x_stride, y_stride, y_bstride;   // resolved (0 -> samples, 2K, frames * y_stride)
+    uint64_t x_stride, y_stride, y_bstride;   // resolved, in floats (0 -> samples, 2K, frames * y_stride; I/Q: 2 * samples, 2 * n_fft)
     uint64_t len;         // L
+};
+// An inverse plan IS the span plan (its base: pl.t0, pl.trips, ...) plus the lane and radix fields of the family's forward plan.
+struct BhwIstftFftPlan : BhwIstftRuns {
+    uint32_t log2n, m, lpf, fy, cpl, radix4, radix2;   // as BhwStftFftPlan
+    uint32_t lds_bytes;   // 2 * fy * M * 8 + M * 8 + n_fft * 4  (<= 64 KiB)
 };
 // Span s of a signal: its outputs [wlo, whi) on the w axis and the frames [f_lo, f_hi) that reach them (both may be empty).
 struct BhwIstftSpan {
@@ -902,19 +908,13 @@ int  bhwk_istft_fft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinC
 
 // ---- fused inverse mixed-radix FFT, window and overlap-add (bhw_istft_mfft_f32_*; bhw_istft_mfft.hip) ---------------------------------
 // The lane layout and the radix schedule of bhwp_stft_mfft_plan (lpf lanes along a row of M = n_fft / 2 complex points, fy slots side
-// by side, cpl = ceil(n_fft / lpf) ring positions per lane, the last of which need not exist) under the spans of bhwp_istft_fft_plan:
-// the same S, halo, trips, halo_bound, grid cap and hop clamp, from one function (istft_spans in bhw_plan.cpp), and bhwp_istft_span as
-// it is.  LDS is BhwIstftFftPlan's formula: 16 000 bytes at n_fft 400, 64 800 at 4050, the largest.
-struct BhwIstftMfftPlan {
-    int route;            // BHWP_FRAMES_DIRECT or BHWP_FRAMES_TABLE
-    bool normalize;
+// by side, cpl = ceil(n_fft / lpf) ring positions per lane, the last of which need not exist) under the span plan (BhwIstftRuns: the
+// same S, halo, trips, halo_bound, grid cap and hop clamp) and bhwp_istft_span as it is.  LDS is BhwIstftFftPlan's formula: 16 000
+// bytes at n_fft 400, 64 800 at 4050, the largest.
+struct BhwIstftMfftPlan : BhwIstftRuns {
     uint32_t m, lpf, fy, cpl, passes;                  // as BhwStftMfftPlan
     uint8_t radix[kMfftMaxPasses];
     uint32_t lds_bytes;   // 2 * fy * M * 8 + M * 8 + n_fft * 4  (<= 64 800)
-    uint64_t t0, hop, halo, span, spans, groups, grid, trips;   // as BhwIstftFftPlan
-    bool halo_bound;
-    uint64_t x_stride, y_stride, y_bstride;   // resolved (0 -> samples, 2K, frames * y_stride)
-    uint64_t len;         // L
 };
 // Every check of the two calls that needs no table handle, before any HIP call (include/bhw.h).  samples 0 passes with the pointers
 // unchecked; `pointers` false: the describe call.
@@ -929,20 +929,15 @@ int  bhwk_istft_mfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWin
 
 // ---- fused inverse complex FFT, window and overlap-add for I/Q output (bhw_istft_cfft_f32_*; bhw_istft_cfft.hip) ----------------------
 // The lane layout and the passes of bhwp_stft_cfft_plan (lpf lanes along a row of n = n_fft complex points, fy slots side by side,
-// cpl complex columns per lane) under the spans of bhwp_istft_fft_plan: the same S, halo, trips, halo_bound, grid cap and hop clamp,
-// from one function (istft_spans in bhw_plan.cpp), and bhwp_istft_span as it is.  A lane keeps cpl ring positions of two binary64
+// cpl complex columns per lane) under the span plan (BhwIstftRuns: the same S, halo, trips, halo_bound, grid cap and hop clamp, the
+// strides in floats of two per sample) and bhwp_istft_span as it is.  A lane keeps cpl ring positions of two binary64
 // sums (re, im) and one envelope sum.  LDS: the two Stockham buffers of fy * n complex64, the n / 2 conjugated twiddles and the n
 // floats of the window: 48 KiB at 2048, three workgroups on a CU.
 constexpr uint32_t kIcfftFlags = BHW_OLA_NORMALIZE | BHW_CFFT_SHIFT;
-struct BhwIstftCfftPlan {
-    int route;            // BHWP_FRAMES_DIRECT or BHWP_FRAMES_TABLE
-    bool normalize, shifted;
+struct BhwIstftCfftPlan : BhwIstftRuns {
+    bool shifted;
     uint32_t log2n, n, lpf, fy, cpl, radix4, radix2;   // as BhwStftCfftPlan
     uint32_t lds_bytes;   // 2 * fy * n * 8 + n / 2 * 8 + n * 4  (<= 48 KiB)
-    uint64_t t0, hop, halo, span, spans, groups, grid, trips;   // as BhwIstftFftPlan
-    bool halo_bound;
-    uint64_t x_stride, y_stride, y_bstride;   // resolved, in floats (0 -> 2 * samples, 2 * n_fft, frames * y_stride)
-    uint64_t len;         // L
 };
 // Every check of the two calls that needs no table handle, before any HIP call and in the order of include/bhw.h.  samples 0 passes
 // with the strides and the pointers unchecked; `pointers` false: the describe call.
@@ -959,20 +954,15 @@ int  bhwk_istft_cfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWin
 // The lane layout, the radix schedule and the twiddle-table form of bhwp_stft_cmfft_plan (lpf lanes along a row of n = n_fft complex
 // points, fy slots side by side, cpl = ceil(n / lpf) <= kCfftMaxCpl ring positions per lane, the last of which need not exist; fold
 // entries of the FORWARD table exp(-2 pi i k / n): the kernel swaps the parts of its input and of its result instead of conjugating
-// the transform) under the spans of bhwp_istft_fft_plan: the same S, halo, trips, halo_bound, grid cap and hop clamp, from one
-// function (istft_spans in bhw_plan.cpp), and bhwp_istft_span as it is.  A lane keeps cpl ring positions of two binary64 sums
+// the transform) under the span plan (BhwIstftRuns: the same S, halo, trips, halo_bound, grid cap and hop clamp, the strides in
+// floats of two per sample) and bhwp_istft_span as it is.  A lane keeps cpl ring positions of two binary64 sums
 // (re, im) and one envelope sum.  LDS: the two Stockham buffers of fy * n complex64, the fold twiddles and the n floats of the
 // window: 48 000 bytes at 2000, 56 700 at 2025, the largest.
-struct BhwIstftCmfftPlan {
-    int route;            // BHWP_FRAMES_DIRECT or BHWP_FRAMES_TABLE
-    bool normalize, shifted;
+struct BhwIstftCmfftPlan : BhwIstftRuns {
+    bool shifted;
     uint32_t n, fold, lpf, fy, cpl, passes;            // as BhwStftCmfftPlan
     uint8_t radix[kMfftMaxPasses];
     uint32_t lds_bytes;   // 2 * fy * n * 8 + fold * 8 + n * 4  (<= 56 700)
-    uint64_t t0, hop, halo, span, spans, groups, grid, trips;   // as BhwIstftFftPlan
-    bool halo_bound;
-    uint64_t x_stride, y_stride, y_bstride;   // resolved, in floats (0 -> 2 * samples, 2 * n_fft, frames * y_stride)
-    uint64_t len;         // L
 };
 // Every check of the two calls that needs no table handle, before any HIP call and in the order of bhwp_istft_cfft_checks.  samples 0
 // passes with the strides and the pointers unchecked; `pointers` false: the describe call.

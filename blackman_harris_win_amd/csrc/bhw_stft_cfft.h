@@ -293,13 +293,4 @@ __device__ __forceinline__ void stft_cfft_rows(const CfftIo &a, const Epilogue &
     }
 }
 
-// launch() of bhw_device.h with the plan's dynamic LDS
-template <typename... KArgs>
-inline void launch_lds(void (*kernel)(KArgs...), dim3 grid, dim3 block, uint32_t lds, hipStream_t st, typename same_type<KArgs>::type... args)
-{
-    void *ptrs[] = {(void *)&args...};
-    const hipError_t e = hipLaunchKernel(reinterpret_cast<const void *>(kernel), grid, block, ptrs, lds, st);
-    if (e != hipSuccess && t_launch_err == hipSuccess) t_launch_err = e;
-}
-
 } // namespace

@@ -83,14 +83,9 @@ int bhwk_stft_frames_f32(const BhwLaunch &l, const BhwCordicCfg &c_in, const Bhw
     a.io = pair_io(s->channels, d_x, d_y, pl.y_stride);
     if (a.io == 2 && (pl.x_stride % 2 || pl.y_bstride % 2)) a.io = 1;
     const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y), block(kFramesBlock);
-    if (!d_table) {
-        with_int_or_last<2, 1, 0>(direct_form(c_in), [&](auto D) { launch(k_stft_frames_direct<D>, grid, block, st, c_in, w, a, lp); });
-        return finish(hipSuccess);
-    }
-    const BhwCordicCfg c = table_layout(c_in);
-    int fmt, nt, mode;
-    if (!bhwp_range_form(c, w, &fmt, &nt, &mode)) return (int)hipErrorInvalidValue;
-    const void *tab = (const void *)d_table;
-    with_range_form(fmt, nt, mode, [&](auto F, auto NT, auto M) { launch(k_stft_frames_table<F, NT, M>, grid, block, st, c, w, tab, a, lp); });
-    return finish(hipSuccess);
+    return with_window_source(
+        c_in, w, d_table, [&](auto D) { launch(k_stft_frames_direct<D>, grid, block, st, c_in, w, a, lp); },
+        [&](auto F, auto NT, auto M, const BhwCordicCfg &c, const void *tab) {
+            launch(k_stft_frames_table<F, NT, M>, grid, block, st, c, w, tab, a, lp);
+        });
 }

@@ -168,16 +168,11 @@ int bhwk_welch_frames_f32(const BhwLaunch &l, const BhwCordicCfg &c_in, const Bh
     const int mode = s->channels == 1 ? 0 : m.vec ? 2 : 1;
     with_int_or_last<0, 1, 2>(mode, [&](auto M) { launch(k_welch_mean<M>, dim3((unsigned)wp.mean_grid), dim3(kWelchMeanBlock), st, m); });
     const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y), block(kFramesBlock);
-    if (!d_table) {
-        with_int_or_last<2, 1, 0>(direct_form(c_in), [&](auto D) { launch(k_welch_frames_direct<D>, grid, block, st, c_in, w, a, lp); });
-        return finish(hipSuccess);
-    }
-    const BhwCordicCfg c = table_layout(c_in);
-    int fmt, nt, mode_t;
-    if (!bhwp_range_form(c, w, &fmt, &nt, &mode_t)) return (int)hipErrorInvalidValue;
-    const void *tab = (const void *)d_table;
-    with_range_form(fmt, nt, mode_t, [&](auto F, auto NT, auto M) { launch(k_welch_frames_table<F, NT, M>, grid, block, st, c, w, tab, a, lp); });
-    return finish(hipSuccess);
+    return with_window_source(
+        c_in, w, d_table, [&](auto D) { launch(k_welch_frames_direct<D>, grid, block, st, c_in, w, a, lp); },
+        [&](auto F, auto NT, auto M, const BhwCordicCfg &c, const void *tab) {
+            launch(k_welch_frames_table<F, NT, M>, grid, block, st, c, w, tab, a, lp);
+        });
 }
 
 int bhwk_welch_psd_f32(const BhwLaunch &l, const BhwPsdPlan &pl, const bhw_psd *d, const float *d_Y, float *d_P, double *d_ws)

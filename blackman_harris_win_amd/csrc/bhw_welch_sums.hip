@@ -104,14 +104,9 @@ int bhwk_window_sums(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinC
     a.trips = pl.trips;
     a.f32 = (flags & BHW_SUMS_F32) ? 1u : 0u;
     const dim3 grid(pl.grid), block(kSumsBlock);
-    if (!d_table) {
-        with_int_or_last<2, 1, 0>(direct_form(c_in), [&](auto D) { launch(k_window_sums_direct<D>, grid, block, st, c_in, w, a, lp); });
-        return finish(hipSuccess);
-    }
-    const BhwCordicCfg c = table_layout(c_in);
-    int fmt, nt, mode;
-    if (!bhwp_range_form(c, w, &fmt, &nt, &mode)) return (int)hipErrorInvalidValue;
-    const void *tab = (const void *)d_table;
-    with_range_form(fmt, nt, mode, [&](auto F, auto NT, auto M) { launch(k_window_sums_table<F, NT, M>, grid, block, st, c, w, tab, a, lp); });
-    return finish(hipSuccess);
+    return with_window_source(
+        c_in, w, d_table, [&](auto D) { launch(k_window_sums_direct<D>, grid, block, st, c_in, w, a, lp); },
+        [&](auto F, auto NT, auto M, const BhwCordicCfg &c, const void *tab) {
+            launch(k_window_sums_table<F, NT, M>, grid, block, st, c, w, tab, a, lp);
+        });
 }
