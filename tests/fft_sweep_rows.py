@@ -107,9 +107,9 @@ def inverse_case(n, iq=False):
 
 # ---- forward signals ---------------------------------------------------------------------------------------------------------------
 
-def forward_signals(n):
-    """(6, T) float32, T = 4 n + 7: ROW_TYPES in order."""
-    T = 4 * n + 7
+def forward_signals(n, T=None):
+    """(6, T) float32, T = 4 n + 7 unless given: ROW_TYPES in order."""
+    T = 4 * n + 7 if T is None else int(T)
     t = np.arange(T, dtype=np.float64)
     rng = np.random.default_rng(1000 + n)
     x = np.zeros((NB, T))
@@ -121,9 +121,10 @@ def forward_signals(n):
     return x.astype(np.float32)
 
 
-def forward_signals_iq(n):
-    """(7, T) complex64: ROW_TYPES_IQ in order.  The tones at +k0 and -k0 land in the two halves fftshift swaps."""
-    T = 4 * n + 7
+def forward_signals_iq(n, T=None):
+    """(7, T) complex64, T = 4 n + 7 unless given: ROW_TYPES_IQ in order.  The tones at +k0 and -k0 land in the two halves fftshift
+    swaps."""
+    T = 4 * n + 7 if T is None else int(T)
     ti = np.arange(T)
     t = ti.astype(np.float64)
     rng = np.random.default_rng(2000 + n)

@@ -33,10 +33,10 @@ def forward_case(n):
     return c
 
 
-def forward_signals_iq(n):
-    """(7, T) complex64: ROW_TYPES_IQ in order (fft_sweep_rows.forward_signals_iq); at an odd n the last row is DC plus the exact-bin
-    tone at (n - 1) / 2."""
-    x = R.forward_signals_iq(n)
+def forward_signals_iq(n, T=None):
+    """(7, T) complex64, T = 4 n + 7 unless given: ROW_TYPES_IQ in order (fft_sweep_rows.forward_signals_iq); at an odd n the last
+    row is DC plus the exact-bin tone at (n - 1) / 2."""
+    x = R.forward_signals_iq(n, T)
     if n % 2:
         ti = np.arange(x.shape[1])
         k0 = (n - 1) // 2

@@ -11,6 +11,12 @@ radix sizes also the round trip istft_mixed(stft_mixed(x)) against torch.istft(t
 and row type, the worst fused / cap and the worst fused / yardstick and the size each occurred at.
 
     python tools/sweep_fft_sizes.py [--out FILE]
+
+--epilogues runs the other sweep instead: every size of the four forward families under the power, filter-bank, Welch and hold
+epilogues (tests/epilogue_sweep_rows.py, the figures tests/test_gpu_epilogue_size_sweep.py holds), written to
+profiles/r39_epilogue_size_sweep.json by default.
+
+    python tools/sweep_fft_sizes.py --epilogues [--out FILE]
 """
 import argparse
 import json
@@ -36,11 +42,55 @@ def worst(sizes, names, key):
     return out
 
 
+def epilogues(out):
+    """--epilogues: every size of the four families under every epilogue that is not the stored spectrum, by
+    tests/test_gpu_epilogue_size_sweep.epilogue_figures (the function its tests hold): per family and front the number of sizes, the
+    differing words against the exact contract (expected 0) and the worst ratio to the derived float64 bound, with the size and row
+    type it occurred at."""
+    import epilogue_sweep_rows as E
+    import test_gpu_epilogue_size_sweep as G
+    tables = S.Tables()
+    rec = {"device": torch.cuda.get_device_name(0), "torch": torch.__version__, "rows": "tests/epilogue_sweep_rows.py",
+           "bounds": {"power": "2 g + g^2 + 2^-23", "bank": "power x max |W|", "welch": "power + 2^-24", "hold": "power, of the loudest frame",
+                      "stored spectrum": "g = fft_sweep_rows.gate(n, row)"},
+           "families": {}}
+    for fam, sizes in E.FAMILIES.items():
+        names = E.row_types(fam)
+        fronts = {}
+        for n in sizes:
+            for e in G.epilogue_figures(torch, tables, fam, n):
+                f = fronts.setdefault(e["front"], {"sizes": set(), "calls": 0, "words": 0, "differing_words": 0, "worst_ratio": None})
+                f["sizes"].add(n)
+                f["calls"] += 1
+                if e["differ"] is not None:
+                    f["words"] += e["words"]
+                    f["differing_words"] += e["differ"]
+                if e["ratios"] is not None:
+                    b = max(range(len(names)), key=lambda i: e["ratios"][i])
+                    if f["worst_ratio"] is None or e["ratios"][b] > f["worst_ratio"]["value"]:
+                        f["worst_ratio"] = {"value": e["ratios"][b], "n_fft": n, "row": names[b], "form": e["form"]}
+        for name, f in fronts.items():
+            f["sizes"] = len(f["sizes"])
+            w = f["worst_ratio"]
+            print(f"{fam}, {name}: {f['sizes']} sizes, {f['differing_words']} differing words of {f['words']}"
+                  + (f", worst ratio to the bound {w['value']:.3f} at n_fft {w['n_fft']}, {w['row']}" if w else ""))
+        rec["families"][fam] = {"sizes": len(sizes), "row_types": list(names), "fronts": fronts}
+    torch.cuda.synchronize()
+    tables.close()
+    with open(out, "w") as f:
+        f.write(json.dumps(rec, indent=1) + "\n")
+    print("wrote", out)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r21_fft_size_sweep.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--epilogues", action="store_true", help="the epilogue size sweep (profiles/r39_epilogue_size_sweep.json)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
+    if a.epilogues:
+        return epilogues(a.out or os.path.join(ROOT, "profiles", "r39_epilogue_size_sweep.json"))
+    a.out = a.out or os.path.join(ROOT, "profiles", "r21_fft_size_sweep.json")
     tables = S.Tables()
     rec = {"device": torch.cuda.get_device_name(0), "torch": torch.__version__, "rows": "tests/fft_sweep_rows.py",
            "gates": {"noise": "fused <= 2 x yardstick and fused <= cap", "structured": "fused <= 2 x cap; the yardstick is not gated"},
