@@ -48,6 +48,8 @@ ABI_SYMBOLS = (
     "bhw_istft_fft_f32_device", "bhw_istft_fft_f32_from_table", "bhw_describe_istft_fft",
     "bhw_spectrogram_f32_device", "bhw_spectrogram_f32_from_table", "bhw_describe_spectrogram",
     "bhw_stft_mfft_f32_device", "bhw_stft_mfft_f32_from_table", "bhw_describe_stft_mfft",
+    "bhw_logspec_f32_device", "bhw_logspec_f32_from_table", "bhw_describe_logspec",
+    "bhw_logspec_mfft_f32_device", "bhw_logspec_mfft_f32_from_table", "bhw_describe_logspec_mfft",
     "bhw_istft_mfft_f32_device", "bhw_istft_mfft_f32_from_table", "bhw_describe_istft_mfft",
     "bhw_stft_cfft_f32_device", "bhw_stft_cfft_f32_from_table", "bhw_describe_stft_cfft",
     "bhw_istft_cfft_f32_device", "bhw_istft_cfft_f32_from_table", "bhw_describe_istft_cfft",
@@ -158,6 +160,26 @@ def make_fbank(filters, bins, weights, d_first, d_offset, d_weight):
     fb.filters, fb.bins, fb.weights = int(filters), int(bins), int(weights)
     fb.d_first, fb.d_offset, fb.d_weight = d_first, d_offset, d_weight
     return fb
+
+
+LOG_CLAMP, LOG_ADD = 0, 1                # BHW_LOG_CLAMP, BHW_LOG_ADD
+LOG_MAX_COEFFS, LOG_MAX_DCT = 4096, 1 << 24
+
+
+class BhwLogspec(ctypes.Structure):
+    """struct bhw_logspec of include/bhw.h (the log and DCT stages of the fused log spectrogram / MFCC)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("mode", ctypes.c_uint32), ("floor", ctypes.c_double), ("mult", ctypes.c_double),
+                ("coeffs", ctypes.c_uint32), ("dct_rows", ctypes.c_uint32), ("d_dct", ctypes.c_void_p), ("reserved", ctypes.c_uint64)]
+
+
+def make_logspec(floor, mult, *, add=False, coeffs=0, dct_rows=0, d_dct=None):
+    """A bhw_logspec: clamp at `floor` (or add it, add=True), mult * ln; coeffs > 0 with the (dct_rows, coeffs) float32 matrix at the
+    device address d_dct (an int) for the DCT stage."""
+    ls = BhwLogspec()
+    ls.struct_size = ctypes.sizeof(BhwLogspec)
+    ls.mode, ls.floor, ls.mult = (LOG_ADD if add else LOG_CLAMP), float(floor), float(mult)
+    ls.coeffs, ls.dct_rows, ls.d_dct = int(coeffs), int(dct_rows), d_dct
+    return ls
 
 
 class BhwPsd(ctypes.Structure):
@@ -334,6 +356,11 @@ def lib():
     L.bhw_stft_mfft_f32_device.argtypes = [P, u64, ci, vp, S, u32, FB, f32p, f32p]
     L.bhw_stft_mfft_f32_from_table.argtypes = [T, P, u64, vp, S, u32, FB, f32p, f32p]
     L.bhw_describe_stft_mfft.argtypes = [T, P, u64, S, u32, FB, ctypes.c_char_p, u64]
+    LS = ctypes.POINTER(BhwLogspec)
+    for stem in ("bhw_logspec", "bhw_logspec_mfft"):
+        getattr(L, stem + "_f32_device").argtypes = [P, u64, ci, vp, S, u32, FB, LS, f32p, f32p]
+        getattr(L, stem + "_f32_from_table").argtypes = [T, P, u64, vp, S, u32, FB, LS, f32p, f32p]
+        getattr(L, "bhw_describe_" + stem[4:]).argtypes = [T, P, u64, S, u32, FB, LS, ctypes.c_char_p, u64]
     L.bhw_istft_mfft_f32_device.argtypes = [P, u64, ci, vp, S, u32, f32p, f32p]
     L.bhw_istft_mfft_f32_from_table.argtypes = [T, P, u64, vp, S, u32, f32p, f32p]
     L.bhw_describe_istft_mfft.argtypes = [T, P, u64, S, u32, ctypes.c_char_p, u64]
@@ -606,6 +633,27 @@ def describe_stft_mfft(params, length, stft, *, detrend=False, power=False, fban
     check(lib().bhw_describe_stft_mfft(table, ctypes.byref(params), int(length), ctypes.byref(stft), flags,
                                        ctypes.byref(fbank) if fbank is not None else None, buf, len(buf)))
     return buf.value.decode()
+
+
+def _describe_logspec(fn, params, length, stft, logspec, detrend, fbank, table):
+    buf = ctypes.create_string_buffer(1280)
+    check(fn(table, ctypes.byref(params), int(length), ctypes.byref(stft), WELCH_DETREND_CONSTANT if detrend else 0,
+             ctypes.byref(fbank) if fbank is not None else None, ctypes.byref(logspec) if logspec is not None else None, buf, len(buf)))
+    return buf.value.decode()
+
+
+def describe_logspec(params, length, stft, logspec, *, detrend=False, fbank=None, table=None):
+    """One line: the plan fields of describe_spectrogram's line in the same words, plus the rows that are logged (power or bank), the
+    log stage (clamp or add, floor, mult), the DCT's shape and W, for a fused log-spectrogram / MFCC call over the window of `length`
+    with the descriptor `stft` (a BhwStft; its y strides count floats of output rows), `logspec` (a BhwLogspec, make_logspec) and
+    `fbank` (a BhwFbank or None) (bhw_describe_logspec).  `table` is a resident table handle or None.  Host arithmetic only."""
+    return _describe_logspec(lib().bhw_describe_logspec, params, length, stft, logspec, detrend, fbank, table)
+
+
+def describe_logspec_mfft(params, length, stft, logspec, *, detrend=False, fbank=None, table=None):
+    """describe_logspec for the mixed-radix n_fft of describe_stft_mfft (bhw_describe_logspec_mfft): the plan fields of that call's
+    line under power=True."""
+    return _describe_logspec(lib().bhw_describe_logspec_mfft, params, length, stft, logspec, detrend, fbank, table)
 
 
 def describe_istft_mfft(params, length, stft, *, normalize=False, table=None):

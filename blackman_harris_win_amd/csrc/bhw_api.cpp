@@ -1180,6 +1180,21 @@ int spectrogram_run(bhw_table t, const bhw_params *p, uint64_t length, int devic
                                                               const BhwLenPhase *lp) { return bhwk_spectrogram_f32(l, c, w, pl, s, fb, d_x, d_P, tab, *lp); });
 }
 
+// The fused log spectrogram / MFCC of either radix family (t NULL: the direct CORDIC chains): the checks, then the one kernel.
+int logspec_run(bool mixed, bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *s, uint32_t flags,
+                const bhw_fbank *fb, const bhw_logspec *ls, const float *d_x, float *d_out)
+{
+    int rc = bhwp_logspec_checks(mixed, p, length, s, flags, fb, ls, d_x, d_out);
+    if (!rc && t) rc = table_call_checks(t, p);
+    if (rc || !s->frames) return rc;
+    const char *what = t ? "logspec launch (resident table)" : "logspec launch";
+    return run_source(t, p, length, device, stream, what, [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *tab,
+                                                              const BhwLenPhase *lp) {
+        if (mixed) return bhwk_logspec_mfft_f32(l, c, w, bhwp_logspec_mfft_plan(p, length, s, flags, fb, ls, t != nullptr), s, fb, ls, d_x, d_out, tab, *lp);
+        return bhwk_logspec_f32(l, c, w, bhwp_logspec_plan(p, length, s, flags, fb, ls, t != nullptr), s, fb, ls, d_x, d_out, tab, *lp);
+    });
+}
+
 // The fused Welch PSD (t NULL: the direct CORDIC chains): the checks, then the accumulating kernel and its join.
 int welch_fft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *s, uint32_t flags,
                   double scale, uint32_t psd_flags, const float *d_x, float *d_P, uint64_t p_stride, void *workspace, uint64_t workspace_bytes)
@@ -1983,6 +1998,60 @@ int bhw_describe_istft_fft(bhw_table t, const bhw_params *p, uint64_t length, co
     int rc = bhwp_istft_fft_checks(p, length, s, flags, nullptr, nullptr, false);
     if (!rc && t) rc = table_call_checks(t, p);
     return rc ? rc : bhwp_describe_istft_fft(p, t ? &t->c : nullptr, length, s, flags, buf, len);
+}
+
+// ---- fused log spectrogram, log-mel and MFCC (include/bhw.h: bhw_logspec_f32_device ..., bhw_logspec_mfft_f32_device ...) -------------
+
+int bhw_logspec_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                           const bhw_fbank *fb, const bhw_logspec *ls, const float *d_x, float *d_out)
+{
+    return logspec_run(false, nullptr, p, length, device, hip_stream, s, flags, fb, ls, d_x, d_out);
+}
+
+int bhw_logspec_mfft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                const bhw_fbank *fb, const bhw_logspec *ls, const float *d_x, float *d_out)
+{
+    return logspec_run(true, nullptr, p, length, device, hip_stream, s, flags, fb, ls, d_x, d_out);
+}
+
+static int logspec_from_table(bool mixed, bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s,
+                              uint32_t flags, const bhw_fbank *fb, const bhw_logspec *ls, const float *d_x, float *d_out)
+{
+    const int rc = bhwp_logspec_checks(mixed, p, length, s, flags, fb, ls, d_x, d_out);
+    if (rc) return rc;
+    return t ? logspec_run(mixed, t, p, length, t->device, hip_stream, s, flags, fb, ls, d_x, d_out) : fail(BHW_ERR_BADARG, "table is NULL");
+}
+
+int bhw_logspec_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                               const bhw_fbank *fb, const bhw_logspec *ls, const float *d_x, float *d_out)
+{
+    return logspec_from_table(false, t, p, length, hip_stream, s, flags, fb, ls, d_x, d_out);
+}
+
+int bhw_logspec_mfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                    const bhw_fbank *fb, const bhw_logspec *ls, const float *d_x, float *d_out)
+{
+    return logspec_from_table(true, t, p, length, hip_stream, s, flags, fb, ls, d_x, d_out);
+}
+
+static int describe_logspec(bool mixed, bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags,
+                            const bhw_fbank *fb, const bhw_logspec *ls, char *buf, uint64_t len)
+{
+    int rc = bhwp_logspec_checks(mixed, p, length, s, flags, fb, ls, nullptr, nullptr, false);
+    if (!rc && t) rc = table_call_checks(t, p);
+    return rc ? rc : bhwp_describe_logspec(mixed, p, t ? &t->c : nullptr, length, s, flags, fb, ls, buf, len);
+}
+
+int bhw_describe_logspec(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const bhw_fbank *fb,
+                         const bhw_logspec *ls, char *buf, uint64_t len)
+{
+    return describe_logspec(false, t, p, length, s, flags, fb, ls, buf, len);
+}
+
+int bhw_describe_logspec_mfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const bhw_fbank *fb,
+                              const bhw_logspec *ls, char *buf, uint64_t len)
+{
+    return describe_logspec(true, t, p, length, s, flags, fb, ls, buf, len);
 }
 
 // ---- fused inverse mixed-radix FFT, window and overlap-add (include/bhw.h: bhw_istft_mfft_f32_device ...) ------------------------------

@@ -2221,6 +2221,166 @@ int bhwp_describe_stft_mfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_
     return BHW_OK;
 }
 
+// ---- fused log spectrogram, log-mel and MFCC ---------------------------------------------------------------------------------------------
+
+uint64_t bhwp_logspec_width(const bhw_stft *s, const bhw_fbank *fb, const bhw_logspec *ls)
+{
+    return ls->coeffs ? ls->coeffs : fb ? fb->filters : s->n_fft / 2 + 1;
+}
+
+int bhwp_logspec_checks(bool mixed, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const bhw_fbank *fb,
+                        const bhw_logspec *ls, const void *d_x, const void *d_out, bool pointers)
+{
+    if (flags & ~BHW_WELCH_DETREND_CONSTANT)
+        return bhwp_fail(BHW_ERR_BADARG, "flags 0x%x (0 or BHW_WELCH_DETREND_CONSTANT: the power is implied)", flags);
+    // the input side and the fields of fb: the parent's checks for the descriptor with packed output strides (they count other rows
+    // here and are checked below)
+    bhw_stft t;
+    const bhw_stft *ps = packed_strides(s, t);
+    int rc = mixed ? bhwp_stft_mfft_checks(p, length, ps, flags | BHW_MFFT_POWER, fb, nullptr, nullptr, false)
+                   : bhwp_spectrogram_checks(p, length, ps, flags, fb, nullptr, nullptr, false);
+    if (rc == BHW_ERR_UNSUPPORTED && ps == &t && s->channels == 1) {
+        // the other family's n_fft: name its call
+        const uint64_t n = s->n_fft;
+        if (mixed && n && !(n & (n - 1)))
+            return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu is a power of two: bhw_logspec_f32_* transforms it (one transform per n_fft)",
+                             (unsigned long long)n);
+        if (!mixed && bhwp_mfft_supported(n))
+            return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu is no power of two: bhw_logspec_mfft_f32_* transforms it (one transform per n_fft)",
+                             (unsigned long long)n);
+    }
+    if (rc) return rc;
+    if (!ls) return bhwp_fail(BHW_ERR_BADARG, "log descriptor is NULL");
+    if (ls->struct_size != sizeof(bhw_logspec))
+        return bhwp_fail(BHW_ERR_BADARG, "bhw_logspec.struct_size %u != %zu", ls->struct_size, sizeof(bhw_logspec));
+    if (ls->reserved) return bhwp_fail(BHW_ERR_BADARG, "bhw_logspec.reserved is not 0");
+    if (ls->mode != BHW_LOG_CLAMP && ls->mode != BHW_LOG_ADD)
+        return bhwp_fail(BHW_ERR_BADARG, "bhw_logspec.mode %u (BHW_LOG_CLAMP or BHW_LOG_ADD)", ls->mode);
+    if (!std::isfinite(ls->floor) || !(ls->floor > 0.0)) return bhwp_fail(BHW_ERR_BADARG, "bhw_logspec.floor %g: finite and > 0", ls->floor);
+    if (!std::isfinite(ls->mult) || ls->mult == 0.0) return bhwp_fail(BHW_ERR_BADARG, "bhw_logspec.mult %g: finite and not 0", ls->mult);
+    if (ls->coeffs > kLogMaxCoeffs) return bhwp_fail(BHW_ERR_BADARG, "bhw_logspec.coeffs %u above %u", ls->coeffs, kLogMaxCoeffs);
+    if (ls->coeffs) {
+        if (!fb) return bhwp_fail(BHW_ERR_BADARG, "bhw_logspec.coeffs %u without a filter bank: the DCT takes bank rows", ls->coeffs);
+        if (ls->dct_rows != fb->filters)
+            return bhwp_fail(BHW_ERR_BADARG, "bhw_logspec.dct_rows %u: the bank has %u filters", ls->dct_rows, fb->filters);
+        if (fb->filters > s->n_fft)
+            return bhwp_fail(BHW_ERR_BADARG, "bhw_fbank.filters %u above n_fft %llu: the log row of a DCT waits in n_fft floats of LDS",
+                             fb->filters, (unsigned long long)s->n_fft);
+        if ((uint64_t)ls->dct_rows * ls->coeffs > kLogMaxDct)
+            return bhwp_fail(BHW_ERR_BADARG, "bhw_logspec.dct_rows * coeffs = %llu above 2^24", (unsigned long long)ls->dct_rows * ls->coeffs);
+    }
+    const uint64_t T = s->samples, F = s->frames;
+    if (!F) return BHW_OK;
+    // the output rows: the parent's rules with W
+    const uint64_t W = bhwp_logspec_width(s, fb, ls);
+    if ((unsigned __int128)s->batch * F * W > (1ull << 34)) return bhwp_fail(BHW_ERR_BADARG, "batch * frames * W above 2^34 per call");
+    if (s->y_stride && s->y_stride < W)
+        return bhwp_fail(BHW_ERR_BADARG, "y_stride %llu: at least W = %llu floats", (unsigned long long)s->y_stride, (unsigned long long)W);
+    const uint64_t ys = s->y_stride ? s->y_stride : W;
+    const unsigned __int128 ysig = (unsigned __int128)(F - 1) * ys + W;
+    if (ysig > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "output extent beyond 2^60 elements");
+    if (s->y_batch_stride && s->y_batch_stride < (uint64_t)ysig)
+        return bhwp_fail(BHW_ERR_BADARG, "y_batch_stride %llu: at least (frames - 1) * y_stride + W = %llu floats",
+                         (unsigned long long)s->y_batch_stride, (unsigned long long)ysig);
+    if (!pointers) return BHW_OK;
+    if (!d_x || !d_out) return bhwp_fail(BHW_ERR_BADARG, "d_x / d_out is NULL");
+    if ((uintptr_t)d_out % 4) return bhwp_fail(BHW_ERR_BADARG, "d_out is not 4-byte aligned");
+    if ((uintptr_t)d_x % 4) return bhwp_fail(BHW_ERR_BADARG, "d_x is not 4-byte aligned");
+    const uint64_t xs = s->x_stride ? s->x_stride : T, ybs = s->y_batch_stride ? s->y_batch_stride : F * ys;
+    const unsigned __int128 xe = (unsigned __int128)(s->batch - 1) * xs + T, ye = (unsigned __int128)(s->batch - 1) * ybs + ysig;
+    if (xe > (1ull << 60) || ye > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "x or output extent beyond 2^60 elements");
+    const uint64_t xa = (uint64_t)(uintptr_t)d_x, ya = (uint64_t)(uintptr_t)d_out, xb = (uint64_t)xe * 4u, yb = (uint64_t)ye * 4u;
+    if (xa > UINT64_MAX - xb || ya > UINT64_MAX - yb) return bhwp_fail(BHW_ERR_BADARG, "x or output range wraps the address space");
+    if (xa < ya + yb && ya < xa + xb) return bhwp_fail(BHW_ERR_BADARG, "d_x and d_out overlap");
+    uint64_t ba[3] = {0, 0, 0}, bn[3] = {0, 0, 0};
+    static const char *const what[3] = {"d_first", "d_offset", "d_weight"};
+    if (fb) {
+        if (!fb->d_first || !fb->d_offset) return bhwp_fail(BHW_ERR_BADARG, "bhw_fbank.d_first / d_offset is NULL");
+        if (!fb->d_weight && fb->weights) return bhwp_fail(BHW_ERR_BADARG, "bhw_fbank.d_weight is NULL with %u weights", fb->weights);
+        const void *ptr[3] = {fb->d_first, fb->d_offset, fb->d_weight};
+        const uint64_t nb[3] = {(uint64_t)fb->filters * 4u, ((uint64_t)fb->filters + 1u) * 4u, (uint64_t)fb->weights * 4u};
+        for (int i = 0; i < 3; ++i) {
+            const uint64_t a = (uint64_t)(uintptr_t)ptr[i];
+            if (a % 4) return bhwp_fail(BHW_ERR_BADARG, "bhw_fbank.%s is not 4-byte aligned", what[i]);
+            if (a > UINT64_MAX - nb[i]) return bhwp_fail(BHW_ERR_BADARG, "bhw_fbank.%s range wraps the address space", what[i]);
+            if (nb[i] && a < ya + yb && ya < a + nb[i]) return bhwp_fail(BHW_ERR_BADARG, "bhw_fbank.%s and d_out overlap", what[i]);
+            ba[i] = a;
+            bn[i] = nb[i];
+        }
+    }
+    if (ls->coeffs) {
+        if (!ls->d_dct) return bhwp_fail(BHW_ERR_BADARG, "bhw_logspec.d_dct is NULL with %u coeffs", ls->coeffs);
+        const uint64_t a = (uint64_t)(uintptr_t)ls->d_dct, n = (uint64_t)ls->dct_rows * ls->coeffs * 4u;
+        if (a % 4) return bhwp_fail(BHW_ERR_BADARG, "bhw_logspec.d_dct is not 4-byte aligned");
+        if (a > UINT64_MAX - n) return bhwp_fail(BHW_ERR_BADARG, "bhw_logspec.d_dct range wraps the address space");
+        if (a < ya + yb && ya < a + n) return bhwp_fail(BHW_ERR_BADARG, "bhw_logspec.d_dct and d_out overlap");
+        for (int i = 0; i < 3; ++i)
+            if (bn[i] && a < ba[i] + bn[i] && ba[i] < a + n)
+                return bhwp_fail(BHW_ERR_BADARG, "bhw_logspec.d_dct and bhw_fbank.%s overlap", what[i]);
+    }
+    return BHW_OK;
+}
+
+// the parent's plan with the output strides resolved for W
+template <class Plan>
+static Plan logspec_strides(Plan pl, const bhw_stft *s, const bhw_fbank *fb, const bhw_logspec *ls)
+{
+    const uint64_t W = bhwp_logspec_width(s, fb, ls);
+    pl.y_stride = s->y_stride ? s->y_stride : W;
+    pl.y_bstride = s->y_batch_stride ? s->y_batch_stride : s->frames * pl.y_stride;
+    return pl;
+}
+
+BhwStftFftPlan bhwp_logspec_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const bhw_fbank *fb,
+                                 const bhw_logspec *ls, bool from_table)
+{
+    return logspec_strides(bhwp_spectrogram_plan(p, length, s, flags, fb, from_table), s, fb, ls);
+}
+
+BhwStftMfftPlan bhwp_logspec_mfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const bhw_fbank *fb,
+                                       const bhw_logspec *ls, bool from_table)
+{
+    return logspec_strides(bhwp_stft_mfft_plan(p, length, s, flags | BHW_MFFT_POWER, fb, from_table), s, fb, ls);
+}
+
+int bhwp_describe_logspec(bool mixed, const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags,
+                          const bhw_fbank *fb, const bhw_logspec *ls, char *buf, uint64_t len)
+{
+    if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
+    // the parent's line: its plan fields stand in it from the kernel's name on, and stay in the parent's words
+    char parent[1024];
+    const int rc = mixed ? bhwp_describe_stft_mfft(p, ct, length, s, flags | BHW_MFFT_POWER, fb, parent, sizeof parent)
+                         : bhwp_describe_spectrogram(p, ct, length, s, flags, fb, parent, sizeof parent);
+    if (rc) return rc;
+    const char *name = mixed ? "logspec mfft" : "logspec";
+    const char *route = ct ? "table" : "direct";
+    const char *det = (flags & BHW_WELCH_DETREND_CONSTANT) ? "constant detrend" : "no detrending";
+    char stage[224], form[96];
+    if (fb) snprintf(form, sizeof form, "bank rows (%u filters, %u weights)", fb->filters, fb->weights);
+    else    snprintf(form, sizeof form, "power rows");
+    const int at = snprintf(stage, sizeof stage, "%s, %s floor %g, mult %.17g", form, ls->mode == BHW_LOG_ADD ? "log add" : "log clamp",
+                            ls->floor, ls->mult);
+    if (ls->coeffs && at > 0 && (size_t)at < sizeof stage)
+        snprintf(stage + at, sizeof stage - at, ", DCT %u x %u", ls->dct_rows, ls->coeffs);
+    const uint64_t W = bhwp_logspec_width(s, fb, ls);
+    if (!s->frames) {
+        snprintf(buf, len, "%s %s (L = %llu, n_fft %llu, %s), %s, W = %llu: nothing (frames 0)", name, route, (unsigned long long)length,
+                 (unsigned long long)s->n_fft, det, stage, (unsigned long long)W);
+        return BHW_OK;
+    }
+    char kern[64];
+    kernel_name(p, ct, mixed ? "k_logspec_mfft_direct" : "k_logspec_direct", mixed ? "k_logspec_mfft_table" : "k_logspec_table", false, kern,
+                sizeof kern);
+    // the parent's plan fields: everything after its kernel name
+    const char *fields = strstr(parent, " signals x ");
+    while (fields && fields > parent && fields[-1] != ' ') --fields;
+    const char *pad = s->pad_mode == BHW_PAD_REFLECT ? "reflect" : "constant";
+    snprintf(buf, len, "%s %s (L = %llu, n_fft %llu, col0 %llu, pad %llu %s, %s), %s, W = %llu: %s, %s", name, route, (unsigned long long)length,
+             (unsigned long long)s->n_fft, (unsigned long long)s->col0, (unsigned long long)s->pad, pad, det, stage, (unsigned long long)W, kern,
+             fields ? fields : "");
+    return BHW_OK;
+}
+
 // ---- fused window and complex FFT for I/Q input ----------------------------------------------------------------------------------------------
 
 // Steps 4 and 5 of the I/Q forward calls (bhw_stft_cfft_f32_*, bhw_stft_cmfft_f32_*): frames 0, the stride rules of the output form,

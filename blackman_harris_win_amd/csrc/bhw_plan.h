@@ -602,6 +602,30 @@ int  bhwp_describe_stft_mfft(const bhw_params *p, const BhwCordicCfg *ct, uint64
 int  bhwk_stft_mfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwStftMfftPlan &pl, const bhw_stft *s,
                         const bhw_fbank *fb, const float *d_x, float *d_out, const int32_t *d_table, const BhwLenPhase &lp);
 
+// ---- fused log spectrogram, log-mel and MFCC (bhw_logspec_f32_*, bhw_logspec_mfft_f32_*; bhw_logspec.hip, bhw_logspec_mfft.hip) ----------
+// The two real-input forward kernels under one more epilogue (bhw_logspec.h): the parent's plan field for field -- grid, LDS bytes,
+// lanes, schedule -- with y_stride / y_bstride resolved in floats of output rows of W = coeffs (DCT), filters (bank) or K (power).
+// `mixed` false: the power-of-two family (parent bhw_spectrogram_f32_*); true: the mixed-radix one (bhw_stft_mfft_f32_* + BHW_MFFT_POWER).
+constexpr uint32_t kLogMaxCoeffs = 4096;
+constexpr uint64_t kLogMaxDct = 1ull << 24;
+// Every check of the calls that needs no table handle, before any HIP call and in the order of include/bhw.h: ONE function for both
+// families.  frames 0 passes with the pointers unchecked; `pointers` false: the describe call.
+int  bhwp_logspec_checks(bool mixed, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const bhw_fbank *fb,
+                         const bhw_logspec *ls, const void *d_x, const void *d_out, bool pointers = true);
+uint64_t bhwp_logspec_width(const bhw_stft *s, const bhw_fbank *fb, const bhw_logspec *ls);
+BhwStftFftPlan  bhwp_logspec_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const bhw_fbank *fb,
+                                  const bhw_logspec *ls, bool from_table);
+BhwStftMfftPlan bhwp_logspec_mfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const bhw_fbank *fb,
+                                       const bhw_logspec *ls, bool from_table);
+int  bhwp_describe_logspec(bool mixed, const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *s, uint32_t flags,
+                           const bhw_fbank *fb, const bhw_logspec *ls, char *buf, uint64_t len);
+int  bhwk_logspec_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwStftFftPlan &pl, const bhw_stft *s,
+                      const bhw_fbank *fb, const bhw_logspec *ls, const float *d_x, float *d_out, const int32_t *d_table,
+                      const BhwLenPhase &lp);
+int  bhwk_logspec_mfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwStftMfftPlan &pl, const bhw_stft *s,
+                           const bhw_fbank *fb, const bhw_logspec *ls, const float *d_x, float *d_out, const int32_t *d_table,
+                           const BhwLenPhase &lp);
+
 // ---- fused window and complex FFT for I/Q input (bhw_stft_cfft_f32_*; bhw_stft_cfft.hip) ----------------------------------------------
 // The lane layout of the real forward kernel for rows of n = n_fft COMPLEX points: lpf lanes work on a row (one radix-4 butterfly per
 // lane and pass up to n = 1024, two at 2048), fy = kFftBlock / lpf rows side by side, a lane holds cpl = n / lpf complex columns of its

@@ -163,10 +163,20 @@ __device__ __forceinline__ float mfft_power(fft_v2f y)
 // the group, its signal, the frame of slot 0, the transformed points of slot 0 (slot s at base + s * M) and the twiddle table.  Such
 // an epilogue may carry state from group to group in `mutable` members, on the terms bhw_stft_fft.h states: one object per lane
 // lives for the whole group loop, and the calls of a run's groups come in ascending order with nothing of another run between them.
+//
+// An epilogue with a member kRows (kStore and kRuns false) keeps the flat pool and takes each transformed row itself
+// (bhw_logspec_mfft.hip): it is called by every lane of the workgroup, live or not, after the last pass's barrier, as
+// epilogue(a, lpf, live, b, f, l, src, dst, tw): the slot's transformed points in src, its idle buffer dst.  It is stateless and may
+// hold barriers that every lane reaches.
 struct MfftStore {
     static constexpr bool kStore = true;
     static constexpr bool kRuns = false;
 };
+
+template <class E, class = void>
+struct mfft_takes_rows : std::false_type {};
+template <class E>
+struct mfft_takes_rows<E, std::void_t<decltype(E::kRows)>> : std::true_type {};
 
 template <class E>
 __device__ __forceinline__ uint64_t mfft_first_group(const E &e)
@@ -342,6 +352,8 @@ __device__ __forceinline__ void stft_mfft_rows(const MfftIo &a, const Epilogue &
                     }
                 }
             }
+        } else if constexpr (mfft_takes_rows<Epilogue>::value) {
+            epilogue(a, lpf, live, b, f, l, src, dst, tw);
         } else {
             epilogue(a, g, b, f0, src - (size_t)slot * M, tw);
         }

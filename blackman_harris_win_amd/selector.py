@@ -4,6 +4,7 @@ torch is plumbing here: it owns the output tensor, the current stream and (in be
 process group.  The arithmetic is in libbhw.so's HIP kernels.
 """
 import ctypes
+import math
 
 from . import binding as B
 
@@ -1101,6 +1102,212 @@ def spectrogram_mixed(params, x, n_fft, hop, *, win_length=None, center=True, pa
     if not isinstance(x, torch.Tensor) or not x.is_cuda:
         raise ValueError("x must be a float32 CUDA tensor")
     return _stft_mixed(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, True, fbank, shift, out, x.device.index, None)
+
+
+# ---- fused log spectrogram, log-mel spectrogram and MFCC ------------------------------------------------------------------------------------
+
+def dct_weights(n_coeffs, n_mels, norm="ortho"):
+    """The DCT-II matrix of torchaudio.functional.create_dct(n_mfcc, n_mels, norm), restated: a host numpy float32 array
+    (n_mels, n_coeffs) computed in float64 and rounded once.  Entry (m, j) is cos(pi / n_mels * (m + 0.5) * j), times 2 for norm
+    None; for norm "ortho" column 0 is scaled by 1 / sqrt(2) and everything by sqrt(2 / n_mels).  DctMatrix(dct_weights(13, 80),
+    device=...) is the DCT of mfcc()."""
+    import numpy as np
+    n_coeffs, n_mels = int(n_coeffs), int(n_mels)
+    if n_coeffs < 1 or n_mels < 1:
+        raise ValueError("n_coeffs and n_mels must be >= 1")
+    if norm not in (None, "ortho"):
+        raise ValueError(f"norm must be None or 'ortho', got {norm!r}")
+    m = np.arange(n_mels, dtype=np.float64)[:, None]
+    j = np.arange(n_coeffs, dtype=np.float64)[None, :]
+    d = np.cos(np.pi / n_mels * (m + 0.5) * j)
+    if norm is None:
+        d = d * 2.0
+    else:
+        d[:, 0] *= 1.0 / np.sqrt(2.0)
+        d = d * np.sqrt(2.0 / n_mels)
+    return np.ascontiguousarray(d, dtype=np.float32)
+
+
+class DctMatrix:
+    """A dense matrix for the DCT stage of mfcc() / log_spectrogram(dct=), built ONCE from a (filters, coeffs) float array or tensor --
+    the layout of torchaudio.functional.create_dct and of dct_weights() -- and kept on `device` row-major.  The contents are
+    validated here, and the upload (and its one synchronisation, when the matrix comes from a device tensor) happens here and never
+    in the call.  filters, coeffs: the shape; dense(): the (filters, coeffs) float32 numpy array."""
+
+    MAX_COEFFS, MAX_WORDS = B.LOG_MAX_COEFFS, B.LOG_MAX_DCT
+
+    def __init__(self, dense, device=None):
+        import numpy as np
+        torch = _torch()
+        if isinstance(dense, torch.Tensor):
+            if device is None and dense.is_cuda:
+                device = dense.device
+            dense = dense.detach().cpu().numpy()
+        d = np.asarray(dense)
+        if d.ndim != 2 or d.shape[0] < 1 or d.shape[1] < 1:
+            raise ValueError("a DCT matrix is a dense (filters, coeffs) array")
+        if d.dtype.kind not in "fiu":
+            raise ValueError(f"a DCT matrix holds real numbers, got {d.dtype}")
+        d = np.array(d, dtype=np.float32, order="C")                 # a copy: the caller's array may change or be read-only
+        if not np.isfinite(d).all():
+            raise ValueError("a DCT matrix's entries must be finite")
+        M, C = d.shape
+        if C > self.MAX_COEFFS:
+            raise ValueError(f"{C} coefficients: a DCT matrix holds 1..{self.MAX_COEFFS}")
+        if M * C > self.MAX_WORDS:
+            raise ValueError(f"{M * C} entries: a DCT matrix holds 2^24 at most")
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise ValueError("a DctMatrix lives on a CUDA device")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.device = dev
+        self.filters, self.coeffs = int(M), int(C)
+        self._host = d
+        self._dev = torch.from_numpy(d).to(dev)
+
+    def data_ptr(self):
+        return self._dev.data_ptr()
+
+    def dense(self):
+        return self._host.copy()
+
+    def __repr__(self):
+        return f"DctMatrix(filters={self.filters}, coeffs={self.coeffs}, device={self.device})"
+
+
+_LOG_MULT = {"ln": 1.0, "log10": 1.0 / math.log(10.0), "db": 10.0 / math.log(10.0)}
+
+
+def log_multiplier(log):
+    """The multiplier of the natural log that `log` names: "db" (10 / ln 10, the dB of a power), "ln" (1), "log10" (1 / ln 10), or a
+    finite non-zero float."""
+    if isinstance(log, str):
+        if log not in _LOG_MULT:
+            raise ValueError(f"log must be 'db', 'ln', 'log10' or a float multiplier of ln, got {log!r}")
+        return _LOG_MULT[log]
+    if isinstance(log, bool) or not isinstance(log, (int, float)) or not math.isfinite(log) or log == 0:
+        raise ValueError(f"log must be 'db', 'ln', 'log10' or a finite non-zero float multiplier of ln, got {log!r}")
+    return float(log)
+
+
+def _logspec_input(mixed):
+    """_fft_input / _mfft_input under the names of the log calls: complex x first, then the other family's n_fft by name."""
+    def check(torch, x, n_fft, dev):
+        if isinstance(x, torch.Tensor) and x.is_complex():
+            raise ValueError(f"the fused log spectrogram takes real input, got {x.dtype} (I/Q input is not built)")
+        n = int(n_fft)
+        if mixed and n > 0 and n & (n - 1) == 0:
+            raise ValueError(f"n_fft {n} is a power of two: bhw.log_spectrogram / bhw.mfcc transform it (one transform per n_fft)")
+        if not mixed and B.mfft_supported(n):
+            raise ValueError(f"n_fft {n} is no power of two: bhw.log_spectrogram_mixed / bhw.mfcc_mixed transform it "
+                             "(one transform per n_fft)")
+        (_mfft_input if mixed else _fft_input)(torch, x, n_fft, dev)
+    return check
+
+
+def _logspec(torch, mixed, params, x, n_fft, hop, fbank, log, floor, add, dct, win_length, center, pad_mode, detrend, shift, out, dev, table):
+    mult = log_multiplier(log)
+    floor = float(floor)
+    if not math.isfinite(floor) or floor <= 0:
+        raise ValueError(f"floor must be finite and > 0, got {floor!r}")
+    n_fft, L, xb, nb, T, frames, d = _stft_front(torch, params, x, n_fft, hop, win_length, center, pad_mode, detrend, dev,
+                                                 _logspec_input(mixed))
+    K = n_fft // 2 + 1
+    if fbank is not None:
+        if not isinstance(fbank, FilterBank):
+            raise ValueError("fbank must be a FilterBank (FilterBank(dense_weights, device=...)) or None")
+        if fbank.bins != K:
+            raise ValueError(f"the filter bank has {fbank.bins} bins, n_fft // 2 + 1 is {K}")
+        if fbank.device != x.device:
+            raise ValueError(f"the filter bank is on {fbank.device}, x on {x.device}")
+    W = K if fbank is None else fbank.filters
+    if dct is not None:
+        if not isinstance(dct, DctMatrix):
+            raise ValueError("dct must be a DctMatrix (DctMatrix(dense, device=...)) or None")
+        if fbank is None:
+            raise ValueError("a DCT takes the rows of a filter bank: pass fbank")
+        if dct.filters != fbank.filters:
+            raise ValueError(f"the DCT matrix has {dct.filters} rows, the filter bank {fbank.filters} filters")
+        if dct.device != x.device:
+            raise ValueError(f"the DCT matrix is on {dct.device}, x on {x.device}")
+        if fbank.filters > n_fft:
+            raise ValueError(f"{fbank.filters} filters above n_fft {n_fft}: the DCT stage holds the log row in n_fft floats")
+        W = dct.coeffs
+    out, ys, ybs = _fft_out(torch, out, (nb, frames, W) if x.dim() == 2 else (frames, W), x, torch.float32)
+    shift = params.dat_width - 1 if shift is None else int(shift)
+    s = B.make_stft(nb, T, frames, d["hop"], n_fft, col0=d["col0"], pad=d["pad"], pad_mode=d["pad_mode"], shift=shift,
+                    x_stride=xb.stride(0) if nb > 1 else 0, y_stride=ys, y_batch_stride=ybs)
+    ls = B.make_logspec(floor, mult, add=add) if dct is None else \
+        B.make_logspec(floor, mult, add=add, coeffs=dct.coeffs, dct_rows=dct.filters, d_dct=dct.data_ptr())
+    tail = (ctypes.byref(s), B.WELCH_DETREND_CONSTANT if detrend else 0, ctypes.byref(fbank.descriptor) if fbank is not None else None,
+            ctypes.byref(ls), ctypes.c_void_p(xb.data_ptr()), ctypes.c_void_p(out.data_ptr()))
+    L_ = B.lib()
+    device_call, table_call = (L_.bhw_logspec_mfft_f32_device, L_.bhw_logspec_mfft_f32_from_table) if mixed else \
+        (L_.bhw_logspec_f32_device, L_.bhw_logspec_f32_from_table)
+    if table is None:
+        B.check(device_call(ctypes.byref(params), L, dev, _stream_ptr(torch, dev), *tail))
+    else:
+        B.check(table_call(table, ctypes.byref(params), L, _stream_ptr(torch, dev), *tail))
+    return out
+
+
+def _logspec_front(mixed, params, x, n_fft, hop, fbank, log, floor, add, dct, win_length, center, pad_mode, detrend, shift, out, table):
+    """The library form (table None: the coefficients by direct CORDIC) or the form that gathers them from `table`, a ResidentTable
+    (bhw_logspec*_f32_from_table: no allocation by the library, no synchronisation, capturable into a graph on its first call)."""
+    torch = _torch()
+    if table is not None:
+        if not isinstance(table, ResidentTable):
+            raise ValueError("table must be a ResidentTable or None")
+        return _logspec(torch, mixed, params, x, n_fft, hop, fbank, log, floor, add, dct, win_length, center, pad_mode, detrend, shift,
+                        out, table.device, table._live())
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise ValueError("x must be a float32 CUDA tensor")
+    return _logspec(torch, mixed, params, x, n_fft, hop, fbank, log, floor, add, dct, win_length, center, pad_mode, detrend, shift, out,
+                    x.device.index, None)
+
+
+def _mfcc_args(fbank, dct):
+    if fbank is None or dct is None:
+        raise ValueError("mfcc takes fbank (a FilterBank) and dct (a DctMatrix)")
+
+
+def log_spectrogram(params, x, n_fft, hop, *, fbank=None, log="db", floor=1e-10, add=False, dct=None, win_length=None, center=True,
+                    pad_mode="reflect", detrend=False, shift=None, out=None, table=None):
+    """The dB / log spectrogram, the log-mel spectrogram or (with dct) the MFCCs of a batch in ONE launch (bhw_logspec_f32_device):
+    x, the framing, the window, the transform and the bank are spectrogram()'s, and each word q that call would have written leaves
+    the kernel as fl32(mult * ln(max(q, floor))) -- or ln(q + floor) with add=True -- taken in binary64.  log: "db" (10 log10), "ln",
+    "log10" or a float multiplier of ln.  With dct (a DctMatrix of fbank.filters rows; needs fbank, filters <= n_fft) the log row is
+    folded through it in binary64, in ascending filter order, rounded once: W = dct.coeffs columns.  Returns float32 (B, F, W) or
+    (F, W), W = n_fft // 2 + 1, fbank.filters or dct.coeffs.  The log words are within one float32 ulp of the binary64 formula; given
+    them the DCT is exact.  top_db, Whisper's max - 8 clamp, magnitude, liftering and deltas are not built: apply them to the small
+    result.  n_fft: a power of two in 16..4096 (a mixed-radix n_fft raises ValueError naming log_spectrogram_mixed; complex x too).
+    `out`: as spectrogram().  `table`: a ResidentTable of these params to gather the window coefficients from
+    (bhw_logspec_f32_from_table: no allocation by the library, no synchronisation, capturable on its first call), or None."""
+    return _logspec_front(False, params, x, n_fft, hop, fbank, log, floor, add, dct, win_length, center, pad_mode, detrend, shift, out, table)
+
+
+def log_spectrogram_mixed(params, x, n_fft, hop, *, fbank=None, log="db", floor=1e-10, add=False, dct=None, win_length=None, center=True,
+                          pad_mode="reflect", detrend=False, shift=None, out=None, table=None):
+    """log_spectrogram() at the n_fft of stft_mixed() (bhw_logspec_mfft_f32_device): the words of spectrogram_mixed() through the same
+    log and DCT stages.  log_spectrogram_mixed(p, x, 400, 160, fbank=FilterBank(mel_weights(400, 80, 16000)), log="log10") is
+    Whisper's log-mel front end before its clamp.  A power-of-two n_fft raises ValueError (bhw.log_spectrogram transforms it)."""
+    return _logspec_front(True, params, x, n_fft, hop, fbank, log, floor, add, dct, win_length, center, pad_mode, detrend, shift, out, table)
+
+
+def mfcc(params, x, n_fft, hop, *, fbank, dct, log="db", floor=1e-10, add=False, win_length=None, center=True, pad_mode="reflect",
+         detrend=False, shift=None, out=None, table=None):
+    """log_spectrogram() with fbank and dct required: the MFCCs of a batch in ONE launch, float32 (B, F, dct.coeffs)."""
+    _mfcc_args(fbank, dct)
+    return _logspec_front(False, params, x, n_fft, hop, fbank, log, floor, add, dct, win_length, center, pad_mode, detrend, shift, out, table)
+
+
+def mfcc_mixed(params, x, n_fft, hop, *, fbank, dct, log="db", floor=1e-10, add=False, win_length=None, center=True, pad_mode="reflect",
+               detrend=False, shift=None, out=None, table=None):
+    """mfcc() at the n_fft of stft_mixed().  mfcc_mixed(p, x, 400, 160, fbank=FilterBank(mel_weights(400, 80, 16000)),
+    dct=DctMatrix(dct_weights(13, 80)), log="ln", floor=1e-6, add=True) is torchaudio's MFCC(log_mels=True) in one launch."""
+    _mfcc_args(fbank, dct)
+    return _logspec_front(True, params, x, n_fft, hop, fbank, log, floor, add, dct, win_length, center, pad_mode, detrend, shift, out, table)
 
 
 def _welch_fft(torch, params, x, length, hop, nfft, detrend, shift, out, dev, table):

@@ -786,7 +786,7 @@ int bhw_describe_istft_fft(bhw_table t, const bhw_params *p, uint64_t length, co
  *     d_P; and (from a table) the key match.  frames 0 returns BHW_OK with the pointers unchecked.
  *   - Capture: as bhw_stft_fft_f32_*.  The library form makes no allocation, uses no scratch and is capturable with no
  *     bhw_prepare_device; the from-table form is capturable on its first call.
- *   - Not built: magnitude (power 1); log (the caller applies it to the small result); a complex output next to the power;
+ *   - Not built: magnitude (power 1); a complex output next to the power (the log of these rows is bhw_logspec_f32_* below);
  *     accumulating over frames in the kernel (Welch: bhw_welch_fft_f32_* is that call); complex input (bhw_stft_cfft_f32_* with
  *     BHW_CFFT_POWER is its power form).
  *     Other n_fft: bhw_stft_mfft_f32_* with BHW_MFFT_POWER writes these rows for an even n_fft = 2^a 3^b 5^c that is no power of two.
@@ -862,6 +862,63 @@ int bhw_stft_mfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t leng
                                  const bhw_fbank *fb, const float *d_x, float *d_out);
 int bhw_describe_stft_mfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const bhw_fbank *fb,
                            char *buf, uint64_t len);
+
+/* Fused log spectrogram, log-mel spectrogram and MFCC: the power or bank rows of bhw_spectrogram_f32_* (bhw_logspec_f32_*: n_fft a
+ * power of two in 16..4096) or of bhw_stft_mfft_f32_* under BHW_MFFT_POWER (bhw_logspec_mfft_f32_*: its even 2^a 3^b 5^c sizes) taken
+ * through a log and, optionally, a dense DCT matrix before they leave the kernel, by ONE launch.  Neither the powers nor the bank
+ * rows nor the log rows reach memory.  No existing call changes.
+ *   - Row, transform, power and bank: exactly those of the parent call for the same (p, length, s, flags, fb); flags is 0 or
+ *     BHW_WELCH_DETREND_CONSTANT (BHW_MFFT_POWER is not a flag here: power is implied).  Let q be the float32 word the parent writes
+ *     for column m of row (b, f): the power of bin m when fb is NULL, the bank value otherwise.
+ *   - Log stage.  BHW_LOG_CLAMP: t = (q < floor) ? floor : (double) q; a NaN passes through, as torch.clamp(min=) passes it.
+ *     BHW_LOG_ADD: t = (double) q + floor.  g_m = fl32(mult * log(t)): a binary64 natural log, one binary64 multiply, one rounding to
+ *     float32.  mult is 1 for ln, 1 / ln 10 for log10, 10 / ln 10 for the dB of a power.  With coeffs == 0 the output row is g,
+ *     W = K = n_fft / 2 + 1 or fb->filters.  The device's binary64 log is not correctly rounded, so the contract of this stage is
+ *     "within one float32 ulp of fl32(mult * log(t)) evaluated in IEEE binary64".
+ *   - DCT stage, coeffs > 0 (needs fb, dct_rows == fb->filters and filters <= n_fft: the log row waits in n_fft floats of LDS):
+ *         c_j = fl32(sum over m < filters of (double) g_m * (double) d_dct[m * coeffs + j])
+ *     a binary64 fma chain in ASCENDING m from +0.0, rounded once -- the arithmetic of the bank sum.  The output row is c,
+ *     W = coeffs.  Given the g that was produced, this stage is exact.
+ *   - Strides, determinism, IEEE and capture: as the parent, with this W.  d_out is 4-byte aligned; only the W floats of a row are
+ *     written.
+ *   - Memory safety: the kernel reads d_dct only at m < filters, j < coeffs, and its reads of the bank stay clamped as in
+ *     bhw_spectrogram_f32_*.  A wrong bank or matrix gives wrong numbers, never a stray access.
+ *   - Checks before any HIP call, in this order (BHW_ERR_BADARG unless noted): flag bits other than BHW_WELCH_DETREND_CONSTANT; everything
+ *     the parent checks on the input side and on the fields of fb, in the parent's words (channels 2 is BHW_ERR_UNSUPPORTED with the
+ *     words "real input"; an n_fft of the other family is BHW_ERR_UNSUPPORTED with a message that names the other family's call); ls
+ *     NULL, its struct_size, reserved != 0, an unknown mode; floor not finite or <= 0; mult not finite or 0; coeffs above 4096;
+ *     coeffs > 0 without fb; dct_rows != fb->filters; filters > n_fft with coeffs > 0; dct_rows * coeffs above 2^24.  frames 0
+ *     returns BHW_OK here with the pointers unchecked.  Then the parent's output-stride, extent and overlap rules with this W, the
+ *     pointers and the arrays of fb as the parent checks them, and d_dct: NULL, not 4-byte aligned, overlapping d_out or an array
+ *     of fb; and (from a table) the key match.
+ *   - Not built: top_db and Whisper's "max - 8" clamp (both need a per-signal maximum of the result: the caller applies it to the
+ *     small output); magnitude (power 1); liftering and deltas; complex input (I/Q); a DCT without a bank.
+ *   - bhw_describe_logspec / bhw_describe_logspec_mfft: the plan fields of the parent's line in the same words, plus the log stage
+ *     and W.  t may be NULL (the library call).  Host arithmetic only. */
+#define BHW_LOG_CLAMP 0u
+#define BHW_LOG_ADD 1u
+typedef struct bhw_logspec {
+    uint32_t struct_size;      /* sizeof(bhw_logspec) = 48                                                            */
+    uint32_t mode;             /* BHW_LOG_CLAMP or BHW_LOG_ADD                                                        */
+    double floor;              /* the clamp floor or the added epsilon: finite and > 0                                */
+    double mult;               /* finite and non-zero: the multiplier of the natural log                              */
+    uint32_t coeffs;           /* 0: the log rows; 1..4096: DCT rows of `coeffs` columns                              */
+    uint32_t dct_rows;         /* must equal fb->filters when coeffs > 0                                              */
+    const float *d_dct;        /* device, dct_rows * coeffs floats (<= 2^24), row-major [m * coeffs + j]; coeffs > 0 */
+    uint64_t reserved;         /* 0                                                                                   */
+} bhw_logspec;
+int bhw_logspec_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                           const bhw_fbank *fb, const bhw_logspec *ls, const float *d_x, float *d_out);
+int bhw_logspec_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                               const bhw_fbank *fb, const bhw_logspec *ls, const float *d_x, float *d_out);
+int bhw_describe_logspec(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const bhw_fbank *fb,
+                         const bhw_logspec *ls, char *buf, uint64_t len);
+int bhw_logspec_mfft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                const bhw_fbank *fb, const bhw_logspec *ls, const float *d_x, float *d_out);
+int bhw_logspec_mfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *s, uint32_t flags,
+                                    const bhw_fbank *fb, const bhw_logspec *ls, const float *d_x, float *d_out);
+int bhw_describe_logspec_mfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const bhw_fbank *fb,
+                              const bhw_logspec *ls, char *buf, uint64_t len);
 
 /* Fused inverse mixed-radix real FFT, window and overlap-add: bhw_istft_fft_f32_* for the row lengths of bhw_stft_mfft_f32_* --
  * torch.fft.irfft(Y, n=n_fft) in front of bhw_istft_ola_f32_*, by ONE launch, for n_fft 400, 480, 960, 1000, 1200, 1920, ...  The time
