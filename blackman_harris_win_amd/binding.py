@@ -64,6 +64,7 @@ ABI_SYMBOLS = (
     "bhw_hold_cmfft_workspace_bytes", "bhw_hold_cmfft_f32_device", "bhw_hold_cmfft_f32_from_table", "bhw_describe_hold_cmfft",
     "bhw_hold_fft_workspace_bytes", "bhw_hold_fft_f32_device", "bhw_hold_fft_f32_from_table", "bhw_describe_hold_fft",
     "bhw_hold_mfft_workspace_bytes", "bhw_hold_mfft_f32_device", "bhw_hold_mfft_f32_from_table", "bhw_describe_hold_mfft",
+    "bhw_mask_fft_f32_device", "bhw_mask_fft_f32_from_table", "bhw_describe_mask_fft",
 )
 
 
@@ -349,6 +350,9 @@ def lib():
     L.bhw_istft_fft_f32_device.argtypes = [P, u64, ci, vp, S, u32, f32p, f32p]
     L.bhw_istft_fft_f32_from_table.argtypes = [T, P, u64, vp, S, u32, f32p, f32p]
     L.bhw_describe_istft_fft.argtypes = [T, P, u64, S, u32, ctypes.c_char_p, u64]
+    L.bhw_mask_fft_f32_device.argtypes = [P, u64, ci, vp, S, S, u32, f32p, f32p, u64, u64, f32p]
+    L.bhw_mask_fft_f32_from_table.argtypes = [T, P, u64, vp, S, S, u32, f32p, f32p, u64, u64, f32p]
+    L.bhw_describe_mask_fft.argtypes = [T, P, u64, S, S, u32, u64, u64, ctypes.c_char_p, u64]
     FB = ctypes.POINTER(BhwFbank)
     L.bhw_spectrogram_f32_device.argtypes = [P, u64, ci, vp, S, u32, FB, f32p, f32p]
     L.bhw_spectrogram_f32_from_table.argtypes = [T, P, u64, vp, S, u32, FB, f32p, f32p]
@@ -553,6 +557,26 @@ def describe_istft_fft(params, length, stft, *, normalize=False, table=None):
     buf = ctypes.create_string_buffer(1024)
     check(lib().bhw_describe_istft_fft(table, ctypes.byref(params), int(length), ctypes.byref(stft),
                                        OLA_NORMALIZE if normalize else 0, buf, len(buf)))
+    return buf.value.decode()
+
+
+MASK_FFT_MAX_N = 2048
+
+
+def mask_fft_supported(n_fft):
+    """True for the n_fft the fused STFT + mask + inverse STFT kernel takes: a power of two in FFT_MIN_N..MASK_FFT_MAX_N."""
+    return fft_supported(n_fft) and int(n_fft) <= MASK_FFT_MAX_N
+
+
+def describe_mask_fft(params, length, analysis, synthesis, *, normalize=False, g_stride=0, g_batch_stride=0, table=None):
+    """One line: the route, the kernel and the plan of a fused STFT + mask + inverse STFT call over the window of `length`
+    (bhw_describe_mask_fft): the plan fields of describe_istft_fft for `synthesis` in the same words (only the LDS bytes differ),
+    "forward + inverse FFT", the padding of `analysis` and the gain strides (0: one gain row for every frame / every signal).  Both
+    descriptors are BhwStft (make_stft) with zero y strides.  `table` is a resident table handle or None for the library call.  Host
+    arithmetic only."""
+    buf = ctypes.create_string_buffer(1280)
+    check(lib().bhw_describe_mask_fft(table, ctypes.byref(params), int(length), ctypes.byref(analysis), ctypes.byref(synthesis),
+                                      OLA_NORMALIZE if normalize else 0, int(g_stride), int(g_batch_stride), buf, len(buf)))
     return buf.value.decode()
 
 

@@ -1398,6 +1398,21 @@ int istft_cmfft_run(bhw_table t, const bhw_params *p, uint64_t length, int devic
         "istft cmfft launch", "istft cmfft launch (resident table)", t, p, length, device, stream, s, flags, d_Y, d_x);
 }
 
+// The fused STFT, mask and inverse STFT (t NULL: the direct CORDIC chains): its checks, then the inverse plan and the one kernel.
+int mask_fft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *sa, const bhw_stft *ss,
+                 uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride, float *d_out)
+{
+    int rc = bhwp_mask_fft_checks(p, length, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out);
+    if (!rc && t) rc = table_call_checks(t, p);
+    if (rc || !ss->samples) return rc;
+    const BhwMaskFftPlan pl = bhwp_mask_fft_plan(p, length, sa, ss, flags, g_stride, g_batch_stride, t != nullptr);
+    const char *what = t ? "mask fft launch (resident table)" : "mask fft launch";
+    return run_source(t, p, length, device, stream, what, [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *tab,
+                                                              const BhwLenPhase *lp) {
+        return bhwk_mask_fft_f32(l, c, w, pl, sa, ss, d_x, d_g, d_out, tab, *lp);
+    });
+}
+
 // The window sums (t NULL: the direct CORDIC chains): the checks, then the memset of the four words and the reduction.
 int window_sums_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, uint32_t flags, uint64_t *d_sums)
 {
@@ -1998,6 +2013,32 @@ int bhw_describe_istft_fft(bhw_table t, const bhw_params *p, uint64_t length, co
     int rc = bhwp_istft_fft_checks(p, length, s, flags, nullptr, nullptr, false);
     if (!rc && t) rc = table_call_checks(t, p);
     return rc ? rc : bhwp_describe_istft_fft(p, t ? &t->c : nullptr, length, s, flags, buf, len);
+}
+
+// ---- fused STFT, spectral mask and inverse STFT (include/bhw.h: bhw_mask_fft_f32_device ...) --------------------------------------------
+
+int bhw_mask_fft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *sa, const bhw_stft *ss,
+                            uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride, float *d_out)
+{
+    return mask_fft_run(nullptr, p, length, device, hip_stream, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out);
+}
+
+int bhw_mask_fft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *sa, const bhw_stft *ss,
+                                uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride,
+                                float *d_out)
+{
+    const int rc = bhwp_mask_fft_checks(p, length, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out);
+    if (rc) return rc;
+    return t ? mask_fft_run(t, p, length, t->device, hip_stream, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out)
+             : fail(BHW_ERR_BADARG, "table is NULL");
+}
+
+int bhw_describe_mask_fft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
+                          uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len)
+{
+    int rc = bhwp_mask_fft_checks(p, length, sa, ss, flags, nullptr, nullptr, g_stride, g_batch_stride, nullptr, false);
+    if (!rc && t) rc = table_call_checks(t, p);
+    return rc ? rc : bhwp_describe_mask_fft(p, t ? &t->c : nullptr, length, sa, ss, flags, g_stride, g_batch_stride, buf, len);
 }
 
 // ---- fused log spectrogram, log-mel and MFCC (include/bhw.h: bhw_logspec_f32_device ..., bhw_logspec_mfft_f32_device ...) -------------

@@ -22,158 +22,19 @@
 // idle once its frames are done.  A row's arithmetic does not depend on its slot, span or grid, and an output's sum takes its rows in
 // ascending f whatever the spans are: the bits of an output are a function of the window and the rows that reach it.
 //
-// Kept in step by hand: the span walk, the ring and the flush stand in all four inverse units (this one, bhw_istft_mfft.hip,
-// bhw_istft_cfft.hip, bhw_istft_cmfft.hip), and tests/cpp/san_istft_fft.cpp replays this file's index arithmetic -- the pre-split
-// pairs, the pass indices, the ring's (q - base) mod n_fft and the flush bound `end` -- from a copy of its own, since only
-// bhwp_istft_span is shared through bhw_plan.h.  An edit of any of these here is an edit of the siblings and of the replay too.
-// cmul, twiddle and the dynamic LDS array are bhw_stft_fft.h's, the Io fill and istft_out bhw_istft.h's.
-#include "bhw_istft.h"
+// The text of all this -- IfftIo and istft_fft_spans -- stands in bhw_istft_fft.h, a template on the frame source, since
+// bhw_mask_fft.hip runs the same spans over frames it forms from a signal; this unit instantiates the source
+// that reads the bins from memory (IstftBins), and its kernels compiled to the same instruction streams as before the move.
+//
+// Kept in step by hand: the span walk, the ring and the flush stand in all four inverse families (bhw_istft_fft.h for this unit and
+// bhw_mask_fft.hip, bhw_istft_mfft.hip, bhw_istft_cfft.hip, bhw_istft_cmfft.hip), and tests/cpp/san_istft_fft.cpp replays this
+// family's index arithmetic -- the pre-split pairs, the pass indices, the ring's (q - base) mod n_fft and the flush bound `end` --
+// from a copy of its own (tests/cpp/san_mask_fft.cpp: the ring and the flush again, under the mask's frame source), since only
+// bhwp_istft_span is shared through bhw_plan.h.  An edit of any of these in bhw_istft_fft.h is an edit of the siblings and of the
+// replays too.  cmul, twiddle and the dynamic LDS array are bhw_stft_fft.h's, the Io fill and istft_out bhw_istft.h's.
+#include "bhw_istft_fft.h"
 
 namespace {
-
-struct IfftIo {
-    const float *Y;
-    float *x;
-    uint64_t batch, frames, hop, samples, t0;
-    uint64_t x_stride, y_stride, y_bstride;
-    uint64_t span, spans, groups, trips;
-    uint32_t n_fft, m, col0, len;
-    uint32_t lpf, fy, cpl, radix4, radix2;
-    uint32_t shift, normalize;
-};
-
-// Everything after the prologue's coefficients: vS (behind the twiddles) holds v[0..L).
-__device__ __forceinline__ void istft_fft_spans(const IfftIo &a)
-{
-    const uint32_t M = a.m, n = a.n_fft, lpf = a.lpf, fy = a.fy, L = a.len;
-    fft_v2f *bufA = (fft_v2f *)fft_lds;
-    fft_v2f *bufB = bufA + (size_t)fy * M;
-    fft_v2f *tw = bufB + (size_t)fy * M;
-    const float *vS = (const float *)(tw + M);
-    const uint32_t tid = threadIdx.x;
-    const uint32_t slot = tid / lpf, l = tid - slot * lpf;
-    for (uint32_t k = tid; k < M; k += kFftBlock) {
-        double sn, cs;
-        sincospi((double)k * 2.0 / (double)n, &sn, &cs);
-        tw[k] = fft_v2f{(float)cs, (float)sn};
-    }
-    __syncthreads();
-    const float scale = 1.0f / (float)n;                                 // a power of two: exact
-    const uint64_t pool = a.batch * a.spans, hop = a.hop;
-    const uint32_t H = M >> 1, Q = M >> 2;
-    double acc[kFftMaxCpl], env[kFftMaxCpl];
-#pragma unroll
-    for (uint32_t c = 0; c < kFftMaxCpl; ++c) acc[c] = env[c] = 0.0;
-    for (uint64_t g = blockIdx.x; g < a.groups; g += gridDim.x) {
-        const uint64_t sp = g * fy + slot;
-        const bool live = sp < pool;
-        const uint64_t b = live ? sp / a.spans : 0, s = live ? sp - b * a.spans : 0;
-        BhwIstftSpan r = bhwp_istft_span(s, a.span, hop, L, a.t0, a.samples, a.frames);
-        if (!live) r.wlo = r.whi = r.f_lo = r.f_hi = 0;
-        const float *yb = a.Y + b * a.y_bstride;
-        float *xb = a.x + b * a.x_stride;                                // output t = w - t0 (every w formed below is >= wlo >= t0)
-        uint64_t cur = r.wlo;                                            // the span's outputs below cur are stored
-        for (uint64_t it = 0; it < a.trips; ++it) {
-            const uint64_t f = r.f_lo + it;
-            const bool act = f < r.f_hi;
-            // 1. the pre-split, into the slot's half of buffer A
-            fft_v2f *src = bufA + (size_t)slot * M, *dst = bufB + (size_t)slot * M;
-            if (act) {
-                const fft_v2f *yp = (const fft_v2f *)(yb + f * a.y_stride);
-                for (uint32_t k = l; k <= H; k += lpf) {
-                    const fft_v2f A = yp[k], B = yp[M - k];
-                    if (k == 0u) {
-                        src[0] = fft_v2f{A.x + B.x, A.x - B.x};
-                    } else {
-                        const fft_v2f w = tw[k];
-                        const fft_v2f e0 = fft_v2f{A.x + B.x, A.y - B.y}, d0 = fft_v2f{A.x - B.x, A.y + B.y};
-                        const fft_v2f o0 = cmul(d0, w);
-                        src[k] = fft_v2f{e0.x - o0.y, e0.y + o0.x};
-                        if (k != H) {                                    // the partner M - k: W[M - k] = -conj W[k]
-                            const fft_v2f e1 = fft_v2f{e0.x, -e0.y}, d1 = fft_v2f{-d0.x, d0.y};
-                            const fft_v2f o1 = cmul(d1, fft_v2f{-w.x, w.y});
-                            src[M - k] = fft_v2f{e1.x - o1.y, e1.y + o1.x};
-                        }
-                    }
-                }
-            }
-            __syncthreads();
-            // 2. the passes (every slot, idle ones on stale data: their result is not read)
-            uint32_t Ns = 1;
-            for (uint32_t p = 0; p < a.radix4; ++p) {
-                const uint32_t ts = M / (2u * Ns);                       // n_fft / (4 Ns)
-                for (uint32_t i = l; i < Q; i += lpf) {
-                    const uint32_t k = i & (Ns - 1u);
-                    fft_v2f a0 = src[i], a1 = src[i + Q], a2 = src[i + 2u * Q], a3 = src[i + 3u * Q];
-                    if (Ns > 1u) {
-                        const uint32_t kt = k * ts;
-                        a1 = cmul(a1, twiddle(tw, kt, M));
-                        a2 = cmul(a2, twiddle(tw, 2u * kt, M));
-                        a3 = cmul(a3, twiddle(tw, 3u * kt, M));
-                    }
-                    const fft_v2f t0 = a0 + a2, t1 = a0 - a2, t2 = a1 + a3;
-                    const fft_v2f t3 = fft_v2f{a3.y - a1.y, a1.x - a3.x};   // +i (a1 - a3)
-                    const uint32_t o = ((i - k) << 2) + k;
-                    dst[o] = t0 + t2;
-                    dst[o + Ns] = t1 + t3;
-                    dst[o + 2u * Ns] = t0 - t2;
-                    dst[o + 3u * Ns] = t1 - t3;
-                }
-                __syncthreads();
-                fft_v2f *sw = src;
-                src = dst;
-                dst = sw;
-                Ns <<= 2;
-            }
-            if (a.radix2) {                                              // Ns = M / 2: k = i, twiddle W[2 i]
-                for (uint32_t i = l; i < H; i += lpf) {
-                    const fft_v2f a0 = src[i], a1 = cmul(src[i + H], tw[2u * i]);
-                    dst[i] = a0 + a1;
-                    dst[i + H] = a0 - a1;
-                }
-                __syncthreads();
-                fft_v2f *sw = src;
-                src = dst;
-                dst = sw;
-            }
-            // 3. and 4.: the ring
-            if (act) {
-                const float *row = (const float *)src + a.col0;
-                const uint64_t base = f * hop;
-                if (cur < base) {                                        // a gap no frame reaches (hop > L, or the span's start)
-                    for (uint64_t w = cur + l; w < base; w += lpf) xb[w - a.t0] = 0.0f;
-                    cur = base;
-                }
-                uint64_t end = (f + 1 == r.f_hi || base + hop > r.whi) ? r.whi : base + hop;
-                if (end < cur) end = cur;                                // a halo frame whose own hop lies before the span
-                const uint32_t bm = (uint32_t)(base & (uint64_t)(n - 1u));
-#pragma unroll
-                for (uint32_t c = 0; c < kFftMaxCpl; ++c) {
-                    if (c < a.cpl) {
-                        const uint32_t k = (c * lpf + l - bm) & (n - 1u);
-                        const uint64_t w = base + k;
-                        if (k < L && w >= cur && w < r.whi) {
-                            const double v = (double)vS[k];
-                            acc[c] += (double)(row[k] * scale) * v;
-                            env[c] += v * v;
-                            if (w < end) {
-                                xb[w - a.t0] = istft_out(acc[c], env[c], a.normalize);
-                                acc[c] = env[c] = 0.0;
-                            }
-                        }
-                    }
-                }
-                const uint64_t reach = base + L;                         // the frame's extent: beyond it up to `end` nothing is summed
-                if (reach < end)
-                    for (uint64_t w = (reach > cur ? reach : cur) + l; w < end; w += lpf) xb[w - a.t0] = 0.0f;
-                cur = end;
-            }
-            __syncthreads();                                             // the next round overwrites both buffers
-        }
-        if (live)
-            for (uint64_t w = cur + l; w < r.whi; w += lpf) xb[w - a.t0] = 0.0f;   // a span with no frame, or outputs past the last one
-    }
-}
 
 // Four workgroups per CU (128 registers a lane): the compiler's own choice is 129 and three.
 // Coefficient by the direct CORDIC chains (FORM: direct_form, as k_stft_fft_direct).
@@ -192,7 +53,7 @@ __global__ __launch_bounds__(kFftBlock, 4) void k_istft_fft_direct(BhwCordicCfg 
         else                     w = direct_coeff_ph<T>(cfg, win, lut_s, len_theta_of(lp, k));
         vS[k] = fft_coeff(w, a.shift);
     }
-    istft_fft_spans(a);
+    istft_fft_spans(a, IstftBins{});
 }
 
 // Coefficient gathered from a resident table in format FMT; every lane reaches the gather (at k = 0 past the window) for the escape
@@ -208,7 +69,7 @@ __global__ __launch_bounds__(kFftBlock, 4) void k_istft_fft_table(BhwCordicCfg c
         const int32_t w = range_coeff_ph<FMT, NT, MODE>(cfg, win, table, len_theta_of(lp, in ? k : 0u));
         if (in) vS[k] = fft_coeff(w, a.shift);
     }
-    istft_fft_spans(a);
+    istft_fft_spans(a, IstftBins{});
 }
 
 } // namespace

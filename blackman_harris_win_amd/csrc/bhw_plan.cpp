@@ -3169,6 +3169,131 @@ int bhwp_describe_istft_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64_
     });
 }
 
+// ---- fused STFT, spectral mask and inverse STFT ---------------------------------------------------------------------------------------------
+
+// a field the two descriptors must share
+static int mask_fft_agree(const char *field, uint64_t a, uint64_t s)
+{
+    if (a == s) return BHW_OK;
+    return bhwp_fail(BHW_ERR_BADARG, "%s: the analysis descriptor has %llu, the synthesis descriptor %llu (they must agree)", field,
+                     (unsigned long long)a, (unsigned long long)s);
+}
+
+int bhwp_mask_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const void *d_x,
+                         const void *d_g, uint64_t g_stride, uint64_t g_batch_stride, const void *d_out, bool pointers)
+{
+    int rc = bhwp_f32_checks(p, length, flags);
+    if (rc) return rc;
+    // the routes that take what this call does not: named before the parents refuse the same input in their own words
+    for (const bhw_stft *s : {sa, ss}) {
+        if (!s || s->struct_size != sizeof(bhw_stft)) continue;
+        const char *which = s == sa ? "analysis" : "synthesis";
+        if (s->channels == 2)
+            return bhwp_fail(BHW_ERR_UNSUPPORTED, "channels 2 (%s descriptor): the fused mask takes real input and gives real output; "
+                             "bhw_stft_cfft_f32_* + bhw_istft_cfft_f32_* take I/Q", which);
+        if (s->n_fft == (1ull << kFftMaxLog))
+            return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu (%s descriptor): the fused mask takes a power of two in %u..%u; "
+                             "bhw_stft_fft_f32_* + bhw_istft_fft_f32_* take %llu", (unsigned long long)s->n_fft, which, 1u << kFftMinLog,
+                             1u << kMaskFftMaxLog, (unsigned long long)s->n_fft);
+        if ((s->n_fft & (s->n_fft - 1)) && bhwp_mfft_supported(s->n_fft))
+            return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu (%s descriptor): the fused mask takes a power of two in %u..%u; "
+                             "bhw_stft_mfft_f32_* + bhw_istft_mfft_f32_* take the mixed-radix lengths", (unsigned long long)s->n_fft, which,
+                             1u << kFftMinLog, 1u << kMaskFftMaxLog);
+    }
+    // each descriptor by its parent's checks, with packed row strides (no spectrum rows exist here)
+    bhw_stft ta, ts;
+    rc = bhwp_stft_fft_checks(p, length, packed_strides(sa, ta), 0, nullptr, nullptr, false);
+    if (rc) return rc;
+    rc = bhwp_istft_fft_checks(p, length, packed_strides(ss, ts), flags, nullptr, nullptr, false);
+    if (rc) return rc;
+    if (sa->y_stride || sa->y_batch_stride || ss->y_stride || ss->y_batch_stride)
+        return bhwp_fail(BHW_ERR_BADARG, "y_stride / y_batch_stride of the %s descriptor is not 0: the fused mask has no spectrum rows",
+                         (sa->y_stride || sa->y_batch_stride) ? "analysis" : "synthesis");
+    if ((rc = mask_fft_agree("batch", sa->batch, ss->batch))) return rc;
+    if ((rc = mask_fft_agree("frames", sa->frames, ss->frames))) return rc;
+    if ((rc = mask_fft_agree("hop", sa->hop, ss->hop))) return rc;
+    if ((rc = mask_fft_agree("n_fft", sa->n_fft, ss->n_fft))) return rc;
+    if ((rc = mask_fft_agree("col0", sa->col0, ss->col0))) return rc;
+    if ((rc = mask_fft_agree("shift", sa->shift, ss->shift))) return rc;
+    if ((rc = mask_fft_agree("channels", sa->channels, ss->channels))) return rc;
+    if (!ss->samples) return BHW_OK;
+    // (samples > 0: the inverse checks have refused frames 0, and with frames > 0 the forward ones samples 0 of the analysis side)
+    const uint64_t K = ss->n_fft / 2 + 1, F = ss->frames, Bn = ss->batch;
+    if (g_stride && g_stride < K)
+        return bhwp_fail(BHW_ERR_BADARG, "g_stride %llu: 0 (one gain row for every frame) or at least K = %llu floats", (unsigned long long)g_stride,
+                         (unsigned long long)K);
+    const unsigned __int128 gsig = (unsigned __int128)(F - 1) * g_stride + K;                // the gain rows of one signal
+    if (gsig > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "g extent beyond 2^60 elements");
+    if (g_batch_stride && g_batch_stride < (uint64_t)gsig)
+        return bhwp_fail(BHW_ERR_BADARG, "g_batch_stride %llu: 0 (the same gains for every signal) or at least (frames - 1) * g_stride + K = "
+                         "%llu floats", (unsigned long long)g_batch_stride, (unsigned long long)(uint64_t)gsig);
+    if (!pointers) return BHW_OK;
+    if (!d_x || !d_g || !d_out) return bhwp_fail(BHW_ERR_BADARG, "d_x / d_g / d_out is NULL");
+    if ((uintptr_t)d_x % 4) return bhwp_fail(BHW_ERR_BADARG, "d_x is not 4-byte aligned");
+    if ((uintptr_t)d_g % 4) return bhwp_fail(BHW_ERR_BADARG, "d_g is not 4-byte aligned");
+    if ((uintptr_t)d_out % 4) return bhwp_fail(BHW_ERR_BADARG, "d_out is not 4-byte aligned");
+    const uint64_t xs = sa->x_stride ? sa->x_stride : sa->samples, os = ss->x_stride ? ss->x_stride : ss->samples;
+    const unsigned __int128 xe = (unsigned __int128)(Bn - 1) * xs + sa->samples, oe = (unsigned __int128)(Bn - 1) * os + ss->samples;
+    const unsigned __int128 ge = (unsigned __int128)(Bn - 1) * g_batch_stride + gsig;
+    if (xe > (1ull << 60) || ge > (1ull << 60) || oe > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "x, g or out extent beyond 2^60 elements");
+    const uint64_t xa = (uint64_t)(uintptr_t)d_x, ga = (uint64_t)(uintptr_t)d_g, oa = (uint64_t)(uintptr_t)d_out;
+    const uint64_t xb = (uint64_t)xe * 4u, gb = (uint64_t)ge * 4u, ob = (uint64_t)oe * 4u;
+    if (xa > UINT64_MAX - xb || ga > UINT64_MAX - gb || oa > UINT64_MAX - ob)
+        return bhwp_fail(BHW_ERR_BADARG, "x, g or out range wraps the address space");
+    // spans read the samples under their halo frames again: the call is not in place
+    if (oa < xa + xb && xa < oa + ob) return bhwp_fail(BHW_ERR_BADARG, "d_x and d_out overlap");
+    if (oa < ga + gb && ga < oa + ob) return bhwp_fail(BHW_ERR_BADARG, "d_g and d_out overlap");
+    return BHW_OK;
+}
+
+BhwMaskFftPlan bhwp_mask_fft_plan(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
+                                  uint64_t g_stride, uint64_t g_batch_stride, bool from_table)
+{
+    BhwMaskFftPlan pl{};
+    static_cast<BhwIstftFftPlan &>(pl) = bhwp_istft_fft_plan(p, length, ss, flags, from_table);
+    pl.lds_bytes = 2u * pl.fy * pl.m * 8u + 2u * pl.m * 8u + (uint32_t)ss->n_fft * 4u;     // the forward table beside the inverse one
+    pl.in_stride = sa->x_stride ? sa->x_stride : sa->samples;
+    pl.g_stride = g_stride;
+    pl.g_bstride = g_batch_stride;
+    return pl;
+}
+
+int bhwp_describe_mask_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *sa, const bhw_stft *ss,
+                           uint32_t flags, uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len)
+{
+    if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
+    const char *route = ct ? "table" : "direct";
+    const char *norm = (flags & BHW_OLA_NORMALIZE) ? "normalised by the window envelope" : "not normalised";
+    if (!ss->samples) {
+        snprintf(buf, len, "mask fft %s (L = %llu, n_fft %llu), %s: nothing (samples 0)", route, (unsigned long long)length,
+                 (unsigned long long)ss->n_fft, norm);
+        return BHW_OK;
+    }
+    // the parent's line: its plan fields stand in it from the kernel's name on, and stay in the parent's words, but for the LDS
+    char parent[1024];
+    const int rc = bhwp_describe_istft_fft(p, ct, length, ss, flags, parent, sizeof parent);
+    if (rc) return rc;
+    const BhwMaskFftPlan pl = bhwp_mask_fft_plan(p, length, sa, ss, flags, g_stride, g_batch_stride, ct != nullptr);
+    char kern[64], gains[160];
+    kernel_name(p, ct, "k_mask_fft_direct", "k_mask_fft_table", false, kern, sizeof kern);
+    if (!g_stride && !g_batch_stride) snprintf(gains, sizeof gains, "one gain row for every frame and every signal");
+    else if (!g_stride) snprintf(gains, sizeof gains, "one gain row for every frame, g_batch_stride %llu", (unsigned long long)g_batch_stride);
+    else if (!g_batch_stride) snprintf(gains, sizeof gains, "g_stride %llu, one set of gain rows for every signal", (unsigned long long)g_stride);
+    else snprintf(gains, sizeof gains, "g_stride %llu, g_batch_stride %llu", (unsigned long long)g_stride, (unsigned long long)g_batch_stride);
+    const char *fields = strstr(parent, " signals x ");
+    while (fields && fields > parent && fields[-1] != ' ') --fields;
+    const char *lds_end = fields ? strstr(fields, " bytes of LDS") : nullptr;
+    const char *lds = lds_end;
+    while (lds && lds > fields && lds[-1] != ' ') --lds;
+    if (!lds) return bhwp_fail(BHW_ERR_BADARG, "buf: the inverse describe line has no plan fields");
+    const char *pad = sa->pad_mode == BHW_PAD_REFLECT ? "reflect" : "constant";
+    snprintf(buf, len, "mask fft %s (L = %llu, n_fft %llu, col0 %llu, pad %llu: t0 = %llu; analysis of %llu samples, pad %llu %s), %s: %s, "
+             "forward + inverse FFT, gains: %s, %.*s%u%s", route, (unsigned long long)length, (unsigned long long)ss->n_fft,
+             (unsigned long long)ss->col0, (unsigned long long)ss->pad, (unsigned long long)pl.t0, (unsigned long long)sa->samples,
+             (unsigned long long)sa->pad, pad, norm, kern, gains, (int)(lds - fields), fields, pl.lds_bytes, lds_end);
+    return BHW_OK;
+}
+
 // ---- fused inverse mixed-radix FFT, window and overlap-add ----------------------------------------------------------------------------------
 
 int bhwp_istft_mfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, const void *d_Y, const void *d_x,

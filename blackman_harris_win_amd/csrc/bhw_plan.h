@@ -930,6 +930,28 @@ int  bhwp_describe_istft_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64
 int  bhwk_istft_fft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwIstftFftPlan &pl, const bhw_stft *s,
                         const float *d_Y, float *d_x, const int32_t *d_table, const BhwLenPhase &lp);
 
+// ---- fused STFT, spectral mask and inverse STFT (bhw_mask_fft_f32_*; bhw_mask_fft.hip) -------------------------------------------------
+// The inverse kernel with its frames formed from the signal: the plan IS bhwp_istft_fft_plan of the synthesis descriptor, field for
+// field, but for the LDS, which holds a second (forward) twiddle table: 40 960 bytes at 2048, the largest n_fft (at 4096 the inverse
+// alone fills the 64 KiB).  Beside it the resolved strides of what the frame source reads.
+constexpr uint32_t kMaskFftMaxLog = 11;               // n_fft <= 2048
+struct BhwMaskFftPlan : BhwIstftFftPlan {             // lds_bytes: 2 * fy * M * 8 + 2 * M * 8 + n_fft * 4  (<= 40 KiB)
+    uint64_t in_stride;   // floats between the input signals (0 -> the analysis descriptor's samples)
+    uint64_t g_stride, g_bstride;   // floats between the gain rows of a signal and between the signals' gains, as given (0: one row)
+};
+// Every check of the two calls that needs no table handle, before any HIP call and in the order of include/bhw.h: the params, the two
+// descriptors by the checks of bhw_stft_fft_f32_* and bhw_istft_fft_f32_* (in their words), the rules that tie them, the gain strides,
+// the pointers and the overlaps.  ss->samples 0 passes with the pointers unchecked; `pointers` false: the describe call.
+int  bhwp_mask_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const void *d_x,
+                          const void *d_g, uint64_t g_stride, uint64_t g_batch_stride, const void *d_out, bool pointers = true);
+// the plan of a call that passed the checks with ss->samples > 0
+BhwMaskFftPlan bhwp_mask_fft_plan(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
+                                  uint64_t g_stride, uint64_t g_batch_stride, bool from_table);
+int  bhwp_describe_mask_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *sa, const bhw_stft *ss,
+                            uint32_t flags, uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len);
+int  bhwk_mask_fft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwMaskFftPlan &pl, const bhw_stft *sa,
+                       const bhw_stft *ss, const float *d_x, const float *d_g, float *d_out, const int32_t *d_table, const BhwLenPhase &lp);
+
 // ---- fused inverse mixed-radix FFT, window and overlap-add (bhw_istft_mfft_f32_*; bhw_istft_mfft.hip) ---------------------------------
 // The lane layout and the radix schedule of bhwp_stft_mfft_plan (lpf lanes along a row of M = n_fft / 2 complex points, fy slots side
 // by side, cpl = ceil(n_fft / lpf) ring positions per lane, the last of which need not exist) under the span plan (BhwIstftRuns: the

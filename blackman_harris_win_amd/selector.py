@@ -858,6 +858,96 @@ def istft_iq_mixed(params, Y, n_fft, hop, *, win_length=None, center=True, lengt
 
 # ---- fused power and filter-bank spectrogram ---------------------------------------------------------------------------------------------
 
+# ---- fused STFT, spectral mask and inverse STFT: analysis, modify and synthesis in one launch ----------------------------------------------
+
+def _mask_fft_refusals(torch, x, mask, n_fft):
+    """What stft_mask_istft() does not take, refused naming the calls that do, before any check that needs a device."""
+    if isinstance(mask, torch.Tensor) and mask.is_complex():
+        raise ValueError("the fused mask takes real float32 gains; complex gains are not built: bhw.stft, a complex multiply and bhw.istft "
+                         "apply them")
+    if isinstance(x, torch.Tensor) and x.is_complex():
+        raise ValueError(f"the fused mask takes real float32 input, got {x.dtype} (I/Q input: bhw.stft_iq, a multiply and bhw.istft_iq)")
+    n = int(n_fft)
+    if n > 0 and n & (n - 1) and B.mfft_supported(n):
+        raise ValueError(f"the fused mask takes n_fft a power of two in {B.FFT_MIN_N}..{B.MASK_FFT_MAX_N}, got {n} (a mixed-radix n_fft: "
+                         f"bhw.stft_mixed, a multiply and bhw.istft_mixed)")
+    if B.fft_supported(n) and not B.mask_fft_supported(n):
+        raise ValueError(f"the fused mask takes n_fft a power of two in {B.FFT_MIN_N}..{B.MASK_FFT_MAX_N}, got {n} (bhw.stft, a multiply and "
+                         f"bhw.istft take it)")
+
+
+def _mask_gains(torch, mask, nb, frames, K, dev):
+    """The gains as the kernel reads them: (the tensor read, g_stride, g_batch_stride).  mask: real float32, (K,), (F, K) or
+    (1 | B, 1 | F, K), its last axis contiguous.  An axis of size 1 or of stride 0 (an expand() view) becomes a zero stride and is never
+    materialised; rows or signals that overlap in memory some other way are copied first."""
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.float32 or not mask.is_cuda or mask.device.index != dev:
+        raise ValueError("mask must be a real float32 CUDA tensor on the call's device")
+    if mask.dim() not in (1, 2, 3) or mask.shape[-1] != K:
+        raise ValueError(f"mask must be (K,), (F, K) or (1 | B, 1 | F, K) with K = n_fft // 2 + 1 = {K}, got {tuple(mask.shape)}")
+    m = mask.resolve_neg()
+    while m.dim() < 3:
+        m = m.unsqueeze(0)
+    if m.shape[0] not in (1, nb) or m.shape[1] not in (1, frames):
+        raise ValueError(f"mask {tuple(mask.shape)} does not broadcast to (B, F, K) = {(nb, frames, K)}")
+    if K > 1 and m.stride(2) != 1:
+        raise ValueError("mask must be contiguous along its last axis (the bins)")
+    gs = m.stride(1) if m.shape[1] > 1 else 0
+    gbs = m.stride(0) if m.shape[0] > 1 else 0
+    if (gs and gs < K) or (gbs and gbs < (frames - 1) * gs + K):
+        m = m.contiguous()
+        gs = m.stride(1) if m.shape[1] > 1 else 0
+        gbs = m.stride(0) if m.shape[0] > 1 else 0
+    return m, gs, gbs
+
+
+def stft_mask_istft(params, x, mask, n_fft, hop, *, win_length=None, center=True, pad_mode="reflect", length=None, normalize=True,
+                    shift=None, out=None, table=None):
+    """A time-frequency mask applied to a batch in ONE launch (bhw_mask_fft_f32_device): stft(), a real gain per bin and istft() with
+    neither spectrum in memory.  x (T,) or (B, T), float32; mask real float32, broadcastable to (B, F, K) by torch's rules -- (K,),
+    (F, K) or (1 | B, 1 | F, K), K = n_fft // 2 + 1, F the frames stft() gives, the last axis contiguous.  A broadcast axis, an
+    expand() view included, is never materialised.  Returns float32 (B, length), or (length,) for 1-D x; length defaults to T.  The
+    result equals
+
+        bhw.istft(params, bhw.stft(params, x, n_fft, hop, ...) * mask[..., None], n_fft, hop, ..., length=length, normalize=normalize)
+
+    BIT FOR BIT: the rows are stft()'s words, each part times its gain is rounded once, and the sum is istft()'s.  n_fft: a power of
+    two in 16..2048.  ValueError naming the calls that take it: a complex mask (stft + a complex multiply + istft), a mixed-radix n_fft
+    (stft_mixed + istft_mixed), complex x (stft_iq + istft_iq), 4096 (stft + istft).  `out`: a contiguous float32 tensor of the
+    returned shape; it may not share memory with x or mask.  `table`: a ResidentTable of these params to gather the window
+    coefficients from (bhw_mask_fft_f32_from_table: no allocation by the library, no synchronisation, capturable on its first call),
+    or None (the library form: capturable with no warm call)."""
+    torch = _torch()
+    _mask_fft_refusals(torch, x, mask, n_fft)
+    if table is not None:
+        if not isinstance(table, ResidentTable):
+            raise ValueError("table must be a ResidentTable or None")
+        dev, handle = table.device, table._live()
+    else:
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise ValueError("x must be a float32 CUDA tensor")
+        dev, handle = x.device.index, None
+    n_fft, L, xb, nb, T, frames, d = _stft_front(torch, params, x, n_fft, hop, win_length, center, pad_mode, False, dev)
+    if not center and L < n_fft:
+        raise ValueError("center=False with win_length < n_fft: the first outputs have no window under them")
+    K = n_fft // 2 + 1
+    g, gs, gbs = _mask_gains(torch, mask, nb, frames, K, dev)
+    length = T if length is None else int(length)
+    if length < 0:
+        raise ValueError(f"length {length} < 0")
+    out = _stft_out(torch, out, (nb, length) if x.dim() == 2 else (length,), x, "x")
+    shift = params.dat_width - 1 if shift is None else int(shift)
+    sa = B.make_stft(nb, T, frames, d["hop"], n_fft, col0=d["col0"], pad=d["pad"], pad_mode=d["pad_mode"], shift=shift,
+                     x_stride=xb.stride(0) if nb > 1 else 0)
+    ss = B.make_stft(nb, length, frames, d["hop"], n_fft, col0=d["col0"], pad=d["pad"], shift=shift)
+    tail = (ctypes.byref(sa), ctypes.byref(ss), B.OLA_NORMALIZE if normalize else 0, ctypes.c_void_p(xb.data_ptr()),
+            ctypes.c_void_p(g.data_ptr()), gs, gbs, ctypes.c_void_p(out.data_ptr()))
+    if handle is None:
+        B.check(B.lib().bhw_mask_fft_f32_device(ctypes.byref(params), L, dev, _stream_ptr(torch, dev), *tail))
+    else:
+        B.check(B.lib().bhw_mask_fft_f32_from_table(handle, ctypes.byref(params), L, _stream_ptr(torch, dev), *tail))
+    return out
+
+
 def fbank_bands(weights):
     """The sparse form of a dense (K, filters) bank, on the host: (first, offset, weight) as numpy uint32, uint32 and float32 arrays.
     Filter m's band runs from its first to its last nonzero weight (interior zeros are kept as weights) and owns

@@ -1533,6 +1533,52 @@ int bhw_csd_fft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length
 int bhw_describe_csd_fft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *s, uint32_t flags, uint32_t csd_flags,
                          char *buf, uint64_t len);
 
+/* Fused STFT, spectral mask and inverse STFT: bhw_stft_fft_f32_*, a real gain per bin, and bhw_istft_fft_f32_* by ONE launch -- the
+ * analysis - modify - synthesis chain of a time-frequency mask (speech enhancement, source separation, spectral gating, a per-bin
+ * equaliser).  The span kernel of bhw_istft_fft_f32_* forms every frame it needs in LDS from the signal: the window, the forward
+ * transform, the gains, the inverse transform, the window again and the overlap-add.  Neither spectrum reaches memory, so the call
+ * takes no workspace.
+ *   - sa, the analysis descriptor: exactly what bhw_stft_fft_f32_* takes for d_x -- samples = T, pad, pad_mode BHW_PAD_REFLECT or
+ *     BHW_PAD_CONSTANT, col0, x_stride (floats between input signals).  ss, the synthesis descriptor: exactly what bhw_istft_fft_f32_*
+ *     takes for d_out -- samples = the output length, pad (with col0: the first output), pad_mode 0, x_stride = floats between output
+ *     signals.  The y strides of both must be 0: there are no spectrum rows.  The two must agree on batch, frames, hop, n_fft, col0,
+ *     shift and channels (1); a disagreement is BHW_ERR_BADARG naming the field.  flags: 0 or BHW_OLA_NORMALIZE (no detrending).
+ *   - d_g: the real gain of bin k < K = n_fft / 2 + 1 of frame f of signal b is d_g[b * g_batch_stride + f * g_stride + k].  Either
+ *     stride may be 0: one row for every frame, the same gains for every signal.  A nonzero g_stride is at least K, a nonzero
+ *     g_batch_stride at least (frames - 1) * g_stride + K.  Floats between the rows are never read.
+ *   - The rows, in terms of the two contracts above.  Y[b, f, k] = (re, im) is the float32 pair bhw_stft_fft_f32_* writes for
+ *     (sa, d_x, flags 0); the masked bin is (fl32(re * g), fl32(im * g)), one float32 rounding per part; d_out is exactly what
+ *     bhw_istft_fft_f32_* writes for (ss, flags) from those masked rows.  The three-call route and this call agree WORD FOR WORD.
+ *   - Determinism: the bits of an output depend on the window, the descriptors' geometry, the flags, the samples and the gains under
+ *     its frames only -- not on the batch, the plan, the spans, the strides, or library versus table.
+ *   - IEEE: a NaN or an infinity in gain row (b, f), or in the samples of that frame, makes exactly the outputs under that frame's
+ *     window non-finite; every other output keeps its bits.
+ *   - Only the ss->samples floats of each output signal are written.  d_out may not overlap d_x or d_g: a span reads the samples under
+ *     its halo frames again, so the call is not in place.
+ *   - Supported: channels 1, n_fft a power of two in 16..2048 (the kernel keeps a forward and an inverse twiddle table in LDS, and at
+ *     4096 the inverse kernel alone fills 64 KiB).  BHW_ERR_UNSUPPORTED naming the route that takes the input: 4096 names
+ *     bhw_stft_fft_f32_* + bhw_istft_fft_f32_*, a mixed-radix n_fft bhw_stft_mfft_f32_* + bhw_istft_mfft_f32_*, channels 2
+ *     bhw_stft_cfft_f32_* + bhw_istft_cfft_f32_*.
+ *   - Checks before any HIP call, in this order (BHW_ERR_BADARG unless noted): the params and unknown flags; the three refusals above;
+ *     everything bhw_stft_fft_f32_* checks on sa and everything bhw_istft_fft_f32_* checks on ss, both with packed row strides and in
+ *     those calls' own words; nonzero y strides; the fields that must agree; ss->samples 0 returns BHW_OK here with the pointers
+ *     unchecked; the gain strides; NULL pointers, any not 4-byte aligned, an extent beyond 2^60 elements; d_out overlapping d_x or d_g;
+ *     and (from a table) the key match.
+ *   - No workspace, no allocation, no float atomics.  The library form computes the coefficients by direct CORDIC and both twiddle
+ *     tables in the kernel: capturable with no bhw_prepare_device.  The from-table form is capturable on its first call.
+ *   - Not built: complex gains; mixed-radix n_fft; I/Q input; 4096; a gain computed in the kernel; a second output with the masked
+ *     spectrum.
+ *   - bhw_describe_mask_fft: the plan fields of bhw_describe_istft_fft's line for ss in the same words (the plan IS that call's, but
+ *     for the LDS bytes), with the kernel, "forward + inverse FFT", the analysis padding and the gain strides.  It takes the gain
+ *     strides because its line and its checks need them.  t may be NULL (the library call).  Host arithmetic only. */
+int bhw_mask_fft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *sa, const bhw_stft *ss,
+                            uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride, float *d_out);
+int bhw_mask_fft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *sa, const bhw_stft *ss,
+                                uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride,
+                                float *d_out);
+int bhw_describe_mask_fft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
+                          uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len);
+
 /* Threading: every entry point may be called from any host thread.  Calls that use the library-owned scratch of one
  * (device, stream) are serialised against each other for the duration of their launches (the table is rebuilt per call);
  * callers that pass their own bhw_exec.workspace must not share one workspace between concurrent calls.  The calling
