@@ -65,6 +65,7 @@ ABI_SYMBOLS = (
     "bhw_hold_fft_workspace_bytes", "bhw_hold_fft_f32_device", "bhw_hold_fft_f32_from_table", "bhw_describe_hold_fft",
     "bhw_hold_mfft_workspace_bytes", "bhw_hold_mfft_f32_device", "bhw_hold_mfft_f32_from_table", "bhw_describe_hold_mfft",
     "bhw_mask_fft_f32_device", "bhw_mask_fft_f32_from_table", "bhw_describe_mask_fft",
+    "bhw_mask_mfft_f32_device", "bhw_mask_mfft_f32_from_table", "bhw_describe_mask_mfft",
 )
 
 
@@ -353,6 +354,9 @@ def lib():
     L.bhw_mask_fft_f32_device.argtypes = [P, u64, ci, vp, S, S, u32, f32p, f32p, u64, u64, f32p]
     L.bhw_mask_fft_f32_from_table.argtypes = [T, P, u64, vp, S, S, u32, f32p, f32p, u64, u64, f32p]
     L.bhw_describe_mask_fft.argtypes = [T, P, u64, S, S, u32, u64, u64, ctypes.c_char_p, u64]
+    L.bhw_mask_mfft_f32_device.argtypes = [P, u64, ci, vp, S, S, u32, f32p, f32p, u64, u64, f32p]
+    L.bhw_mask_mfft_f32_from_table.argtypes = [T, P, u64, vp, S, S, u32, f32p, f32p, u64, u64, f32p]
+    L.bhw_describe_mask_mfft.argtypes = [T, P, u64, S, S, u32, u64, u64, ctypes.c_char_p, u64]
     FB = ctypes.POINTER(BhwFbank)
     L.bhw_spectrogram_f32_device.argtypes = [P, u64, ci, vp, S, u32, FB, f32p, f32p]
     L.bhw_spectrogram_f32_from_table.argtypes = [T, P, u64, vp, S, u32, FB, f32p, f32p]
@@ -577,6 +581,25 @@ def describe_mask_fft(params, length, analysis, synthesis, *, normalize=False, g
     buf = ctypes.create_string_buffer(1280)
     check(lib().bhw_describe_mask_fft(table, ctypes.byref(params), int(length), ctypes.byref(analysis), ctypes.byref(synthesis),
                                       OLA_NORMALIZE if normalize else 0, int(g_stride), int(g_batch_stride), buf, len(buf)))
+    return buf.value.decode()
+
+
+MASK_MFFT_MAX_N = 2047
+
+
+def mask_mfft_supported(n_fft):
+    """True for the n_fft the mixed-radix fused STFT + mask + inverse STFT kernel takes: the mfft_supported() lengths below 2048 (an
+    even 2^a 3^b 5^c that is no power of two, 18..2000)."""
+    return mfft_supported(n_fft) and int(n_fft) <= MASK_MFFT_MAX_N
+
+
+def describe_mask_mfft(params, length, analysis, synthesis, *, normalize=False, g_stride=0, g_batch_stride=0, table=None):
+    """describe_mask_fft() for a mixed-radix n_fft (bhw_describe_mask_mfft): the plan fields of describe_istft_mfft for `synthesis` in
+    the same words (only the LDS bytes differ), "forward + inverse FFT", the padding of `analysis` and the gain strides.  Host
+    arithmetic only."""
+    buf = ctypes.create_string_buffer(1280)
+    check(lib().bhw_describe_mask_mfft(table, ctypes.byref(params), int(length), ctypes.byref(analysis), ctypes.byref(synthesis),
+                                       OLA_NORMALIZE if normalize else 0, int(g_stride), int(g_batch_stride), buf, len(buf)))
     return buf.value.decode()
 
 

@@ -1413,6 +1413,21 @@ int mask_fft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, 
     });
 }
 
+// The same at a mixed-radix n_fft: its checks, then the inverse mixed-radix plan and the one kernel.
+int mask_mfft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *sa, const bhw_stft *ss,
+                  uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride, float *d_out)
+{
+    int rc = bhwp_mask_mfft_checks(p, length, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out);
+    if (!rc && t) rc = table_call_checks(t, p);
+    if (rc || !ss->samples) return rc;
+    const BhwMaskMfftPlan pl = bhwp_mask_mfft_plan(p, length, sa, ss, flags, g_stride, g_batch_stride, t != nullptr);
+    const char *what = t ? "mask mfft launch (resident table)" : "mask mfft launch";
+    return run_source(t, p, length, device, stream, what, [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *tab,
+                                                              const BhwLenPhase *lp) {
+        return bhwk_mask_mfft_f32(l, c, w, pl, sa, ss, d_x, d_g, d_out, tab, *lp);
+    });
+}
+
 // The window sums (t NULL: the direct CORDIC chains): the checks, then the memset of the four words and the reduction.
 int window_sums_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, uint32_t flags, uint64_t *d_sums)
 {
@@ -2039,6 +2054,32 @@ int bhw_describe_mask_fft(bhw_table t, const bhw_params *p, uint64_t length, con
     int rc = bhwp_mask_fft_checks(p, length, sa, ss, flags, nullptr, nullptr, g_stride, g_batch_stride, nullptr, false);
     if (!rc && t) rc = table_call_checks(t, p);
     return rc ? rc : bhwp_describe_mask_fft(p, t ? &t->c : nullptr, length, sa, ss, flags, g_stride, g_batch_stride, buf, len);
+}
+
+// ---- fused STFT, spectral mask and inverse STFT at mixed-radix n_fft (include/bhw.h: bhw_mask_mfft_f32_device ...) -------------------------
+
+int bhw_mask_mfft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *sa, const bhw_stft *ss,
+                             uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride, float *d_out)
+{
+    return mask_mfft_run(nullptr, p, length, device, hip_stream, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out);
+}
+
+int bhw_mask_mfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *sa, const bhw_stft *ss,
+                                 uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride,
+                                 float *d_out)
+{
+    const int rc = bhwp_mask_mfft_checks(p, length, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out);
+    if (rc) return rc;
+    return t ? mask_mfft_run(t, p, length, t->device, hip_stream, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out)
+             : fail(BHW_ERR_BADARG, "table is NULL");
+}
+
+int bhw_describe_mask_mfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
+                           uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len)
+{
+    int rc = bhwp_mask_mfft_checks(p, length, sa, ss, flags, nullptr, nullptr, g_stride, g_batch_stride, nullptr, false);
+    if (!rc && t) rc = table_call_checks(t, p);
+    return rc ? rc : bhwp_describe_mask_mfft(p, t ? &t->c : nullptr, length, sa, ss, flags, g_stride, g_batch_stride, buf, len);
 }
 
 // ---- fused log spectrogram, log-mel and MFCC (include/bhw.h: bhw_logspec_f32_device ..., bhw_logspec_mfft_f32_device ...) -------------

@@ -1,0 +1,194 @@
+// bhw_mask_mfft.hip -- window, mixed-radix real FFT, a real gain per bin, inverse mixed-radix real FFT, window and overlap-add in one
+// kernel, for even n_fft = 2^a 3^b 5^c below 2048 that is no power of two (bhw_mask_mfft_f32_device / _from_table; contract:
+// include/bhw.h, plan: BhwMaskMfftPlan in bhw_plan.h, reasons: DESIGN.md section 42).
+//
+// The span / ring / flush kernel of bhw_istft_mfft.hip (istft_mfft_spans in bhw_istft_mfft.h) with another frame source: where that
+// kernel loads the bins Y[k], Y[M - k] of a frame from memory, this one forms them in LDS from the signal, as bhw_mask_fft.hip does
+// for the powers of two.  Prologue, once per workgroup: the window coefficients v[0..L) as the inverse kernels keep them, and TWO
+// twiddle tables of M = n_fft / 2 entries, the inverse one exp(+2 pi i k / n_fft) and behind it the forward one
+// exp(-2 pi i k / n_fft), both from the same binary64 sincospi.  Then, per frame f of a slot (MaskMfftSource::frame):
+//   a. lane l takes the columns j = l, l + lpf, ... of the row: sample t = f * hop + j - pad of the signal under the padding rule of
+//      bhw_stft_mfft.h (reflect, or +0.0 in place of the sample), times v[j - col0]; +0.0 outside the window and in a slot without a
+//      frame.  The float row goes to the slot's buffer A; one barrier;
+//   b. the forward passes in the plan's schedule: mfft_pass of bhw_stft_mfft.h, reading the forward table;
+//   c. the lane of k <= floor(M / 2) forms Y[k] and Y[M - k] by fft_split_bin, multiplies each by its gain (one float32 rounding per
+//      part, never contracted into the adds that follow), forms Z[k] and Z[M - k] by the pre-split of bhw_istft_mfft.h (M may be odd:
+//      the self-partner test is 2 k == M) and writes them to the slot's OTHER buffer: the split reads src[k], src[M - k] and src[0]
+//      of the transformed points, which no lane overwrites.
+// The inverse passes, the scale, the ring and the flush follow as they stand.  The bits of a masked row are those
+// bhw_stft_mfft_f32_* stores, times the gains; the bits of an output those bhw_istft_mfft_f32_* gives for these rows.
+//
+// tests/cpp/san_mask_mfft.cpp replays a., the pass indices of b., the gain reads and the pre-split points of c. and the buffer each
+// phase writes from a copy of its own; an edit of MaskMfftSource::frame is an edit of the replay too.
+#include "bhw_istft_mfft.h"
+
+namespace {
+
+// The pre-split of the bins A = Y[k], B = Y[M - k], 0 < k <= floor(M / 2), with w = W[k] of the inverse table: Z[k], and Z[M - k]
+// where 2 k != M, with the roundings k_istft_mfft_* were compiled with spelled out (istft_presplit of bhw_istft_fft.h is the model,
+// and the reason is there): of the two products of each part of o = d * w the one by d.x is rounded and the one by d.y is fused into
+// it; the adds of e are separate; the partner's o is o's with the sign of its imaginary part turned.
+__device__ __forceinline__ void imf_presplit(fft_v2f *z, uint32_t k, uint32_t M, fft_v2f A, fft_v2f B, fft_v2f w)
+{
+#pragma clang fp contract(off)
+    const float ex = A.x + B.x, ey = A.y - B.y, dx = A.x - B.x, dy = A.y + B.y;
+    const float ox = __builtin_fmaf(-dy, w.y, dx * w.x), oy = __builtin_fmaf(dy, w.x, dx * w.y);
+    z[k] = fft_v2f{ex - oy, ey + ox};
+    if (2u * k != M) z[M - k] = fft_v2f{ex + oy, ox - ey};           // the partner M - k: W[M - k] = -conj W[k]
+}
+
+struct MaskMfftSource {
+    static constexpr bool kBins = false;
+    static constexpr uint32_t kTables = 2;
+    static constexpr uint32_t kMaxCpl = 8;                            // n_fft < 2048: 16 columns per lane come with 2160 and above
+    const float *x, *g;
+    uint64_t samples, pad, hop, x_stride, g_stride, g_bstride;
+    uint32_t reflect;
+
+    __device__ __forceinline__ void tables(fft_v2f *twf, uint32_t k, double cs, double sn) const { twf[k] = fft_v2f{(float)cs, (float)-sn}; }
+
+    // the masked bin: one rounding per part, whatever is added to it afterwards
+    static __device__ __forceinline__ fft_v2f masked(fft_v2f y, float gain)
+    {
+#pragma clang fp contract(off)
+        return fft_v2f{y.x * gain, y.y * gain};
+    }
+
+    __device__ __forceinline__ void frame(const ImfftIo &a, bool act, uint64_t b, uint64_t f, uint32_t l, const fft_v2f *tw, const float *vS,
+                                          fft_v2f *&src, fft_v2f *&dst) const
+    {
+        const uint32_t M = a.m, n = a.n_fft, lpf = a.lpf, H = M >> 1;
+        const fft_v2f *twf = tw + M;
+        // a. the windowed row
+        {
+            float *row = (float *)src;
+            const float *xb = x + b * x_stride;
+            const uint64_t T = samples, t0 = f * hop - pad;              // the (wrapped) time of column 0
+            for (uint32_t j = l; j < n; j += lpf) {
+                const uint32_t k = j - a.col0;                           // unsigned: k < L is the window test
+                float r = 0.0f;
+                if (act && k < a.len) {
+                    uint64_t t = t0 + j;                                 // unsigned: t < T is the whole interior test
+                    bool zero = false;
+                    if (t >= T) {
+                        const int64_t ts = (int64_t)t;
+                        if (reflect) t = ts < 0 ? (uint64_t)(-ts) : 2 * (T - 1) - t;
+                        else {
+                            t = 0;
+                            zero = true;
+                        }
+                    }
+                    const float xv = xb[t];
+                    r = (zero ? 0.0f : xv) * vS[k];
+                }
+                row[j] = r;
+            }
+        }
+        __syncthreads();
+        // b. the forward passes: the schedule walk of stft_mfft_rows around mfft_pass
+        uint32_t Ns = 1, rest = M;
+        for (uint32_t p = 0; p < a.passes; ++p) {
+            const uint32_t rdx = (a.sched >> (4u * p)) & 15u;
+            if (rdx == 5u) {
+                rest /= 5u;
+                mfft_pass<5>(src, dst, twf, M, M / 5u, Ns, 2u * rest, l, lpf);
+            } else if (rdx == 3u) {
+                rest /= 3u;
+                mfft_pass<3>(src, dst, twf, M, M / 3u, Ns, 2u * rest, l, lpf);
+            } else if (rdx == 4u) {
+                rest >>= 2;
+                mfft_pass<4>(src, dst, twf, M, M >> 2, Ns, 2u * rest, l, lpf);
+            } else {
+                rest >>= 1;
+                mfft_pass<2>(src, dst, twf, M, M >> 1, Ns, 2u * rest, l, lpf);
+            }
+            __syncthreads();
+            fft_v2f *sw = src;
+            src = dst;
+            dst = sw;
+            Ns *= rdx;
+        }
+        // c. the split, the gains and the pre-split, into the other buffer
+        if (act) {
+            const float *gp = g + b * g_bstride + f * g_stride;
+            for (uint32_t k = l; k <= H; k += lpf) {
+#pragma clang fp contract(off)
+                const fft_v2f A = masked(fft_split_bin(src, twf, k, M), gp[k]);
+                const fft_v2f B = masked(fft_split_bin(src, twf, M - k, M), gp[M - k]);
+                if (k == 0u) dst[0] = fft_v2f{A.x + B.x, A.x - B.x};
+                else         imf_presplit(dst, k, M, A, B, tw[k]);
+            }
+        }
+        fft_v2f *sw = src;                                               // the inverse passes start from Z
+        src = dst;
+        dst = sw;
+    }
+};
+
+// Unhinted, as the parent is: the compiler's own choice is 123 registers a lane, no scratch and four workgroups per CU in all 48
+// instances (the parent, with 16 accumulator pairs per lane, has 156 and three).
+// Coefficient by the direct CORDIC chains (FORM: direct_form, as k_istft_mfft_direct).
+template <int FORM>
+__global__ __launch_bounds__(kFftBlock) void k_mask_mfft_direct(BhwCordicCfg cfg, BhwWinCfg win, ImfftIo a, MaskMfftSource m, BhwLenPhase lp)
+{
+    using T = std::conditional_t<FORM == 0, int32_t, int64_t>;
+    using L = std::conditional_t<FORM == 2, uint32_t, T>;
+    __shared__ L lut_s[32];
+    if (threadIdx.x < 32) lut_s[threadIdx.x] = (L)cfg.lut[threadIdx.x];
+    __syncthreads();
+    float *vS = (float *)(fft_lds + (size_t)(2u * a.fy + 2u) * a.m * sizeof(fft_v2f));
+    for (uint32_t k = threadIdx.x; k < a.len; k += kFftBlock) {
+        int32_t w;
+        if constexpr (FORM == 2) w = direct_coeff_mad_ph(cfg, win, lut_s, len_theta_of(lp, k));
+        else                     w = direct_coeff_ph<T>(cfg, win, lut_s, len_theta_of(lp, k));
+        vS[k] = fft_coeff(w, a.shift);
+    }
+    istft_mfft_spans(a, m);
+}
+
+// Coefficient gathered from a resident table in format FMT; every lane reaches the gather (at k = 0 past the window) for the escape
+// format's wave-wide fix.
+template <int FMT, int NT, int MODE>
+__global__ __launch_bounds__(kFftBlock) void k_mask_mfft_table(BhwCordicCfg cfg, BhwWinCfg win, const void *__restrict__ table, ImfftIo a,
+                                                                MaskMfftSource m, BhwLenPhase lp)
+{
+    float *vS = (float *)(fft_lds + (size_t)(2u * a.fy + 2u) * a.m * sizeof(fft_v2f));
+    for (uint32_t k0 = 0; k0 < a.len; k0 += kFftBlock) {
+        const uint32_t k = k0 + threadIdx.x;
+        const bool in = k < a.len;
+        const int32_t w = range_coeff_ph<FMT, NT, MODE>(cfg, win, table, len_theta_of(lp, in ? k : 0u));
+        if (in) vS[k] = fft_coeff(w, a.shift);
+    }
+    istft_mfft_spans(a, m);
+}
+
+} // namespace
+
+int bhwk_mask_mfft_f32(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinCfg &w, const BhwMaskMfftPlan &pl, const bhw_stft *sa,
+                       const bhw_stft *ss, const float *d_x, const float *d_g, float *d_out, const int32_t *d_table, const BhwLenPhase &lp)
+{
+    if (!ss->samples) return 0;
+    if (pl.cpl > MaskMfftSource::kMaxCpl) return (int)hipErrorInvalidValue;   // (the checks refuse 2048 and above)
+    hipStream_t st = (hipStream_t)l.stream;
+    ImfftIo a = istft_io<ImfftIo>(pl, ss, nullptr, d_out);
+    a.n_fft = (uint32_t)ss->n_fft;
+    a.m = pl.m;
+    a.passes = pl.passes;
+    for (uint32_t p = 0; p < pl.passes; ++p) a.sched |= (uint32_t)pl.radix[p] << (4u * p);
+    MaskMfftSource m;
+    m.x = d_x;
+    m.g = d_g;
+    m.samples = sa->samples;
+    m.pad = sa->pad;
+    m.hop = sa->hop;
+    m.x_stride = pl.in_stride;
+    m.g_stride = pl.g_stride;
+    m.g_bstride = pl.g_bstride;
+    m.reflect = sa->pad_mode == BHW_PAD_REFLECT ? 1u : 0u;
+    const dim3 grid((unsigned)pl.grid), block(kFftBlock);
+    return with_window_source(
+        c_in, w, d_table, [&](auto D) { launch_lds(k_mask_mfft_direct<D>, grid, block, pl.lds_bytes, st, c_in, w, a, m, lp); },
+        [&](auto F, auto NT, auto M, const BhwCordicCfg &c, const void *tab) {
+            launch_lds(k_mask_mfft_table<F, NT, M>, grid, block, pl.lds_bytes, st, c, w, tab, a, m, lp);
+        });
+}

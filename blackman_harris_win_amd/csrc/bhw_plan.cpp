@@ -3179,33 +3179,12 @@ static int mask_fft_agree(const char *field, uint64_t a, uint64_t s)
                      (unsigned long long)a, (unsigned long long)s);
 }
 
-int bhwp_mask_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const void *d_x,
-                         const void *d_g, uint64_t g_stride, uint64_t g_batch_stride, const void *d_out, bool pointers)
+// What both fused masks check once each descriptor has passed its parent's checks: nonzero y strides, the seven fields that must agree,
+// the gain strides, the pointers, their alignment, the extents, the wrap and the overlaps.
+static int mask_tail_checks(const bhw_stft *sa, const bhw_stft *ss, const void *d_x, const void *d_g, uint64_t g_stride, uint64_t g_batch_stride,
+                            const void *d_out, bool pointers)
 {
-    int rc = bhwp_f32_checks(p, length, flags);
-    if (rc) return rc;
-    // the routes that take what this call does not: named before the parents refuse the same input in their own words
-    for (const bhw_stft *s : {sa, ss}) {
-        if (!s || s->struct_size != sizeof(bhw_stft)) continue;
-        const char *which = s == sa ? "analysis" : "synthesis";
-        if (s->channels == 2)
-            return bhwp_fail(BHW_ERR_UNSUPPORTED, "channels 2 (%s descriptor): the fused mask takes real input and gives real output; "
-                             "bhw_stft_cfft_f32_* + bhw_istft_cfft_f32_* take I/Q", which);
-        if (s->n_fft == (1ull << kFftMaxLog))
-            return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu (%s descriptor): the fused mask takes a power of two in %u..%u; "
-                             "bhw_stft_fft_f32_* + bhw_istft_fft_f32_* take %llu", (unsigned long long)s->n_fft, which, 1u << kFftMinLog,
-                             1u << kMaskFftMaxLog, (unsigned long long)s->n_fft);
-        if ((s->n_fft & (s->n_fft - 1)) && bhwp_mfft_supported(s->n_fft))
-            return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu (%s descriptor): the fused mask takes a power of two in %u..%u; "
-                             "bhw_stft_mfft_f32_* + bhw_istft_mfft_f32_* take the mixed-radix lengths", (unsigned long long)s->n_fft, which,
-                             1u << kFftMinLog, 1u << kMaskFftMaxLog);
-    }
-    // each descriptor by its parent's checks, with packed row strides (no spectrum rows exist here)
-    bhw_stft ta, ts;
-    rc = bhwp_stft_fft_checks(p, length, packed_strides(sa, ta), 0, nullptr, nullptr, false);
-    if (rc) return rc;
-    rc = bhwp_istft_fft_checks(p, length, packed_strides(ss, ts), flags, nullptr, nullptr, false);
-    if (rc) return rc;
+    int rc;
     if (sa->y_stride || sa->y_batch_stride || ss->y_stride || ss->y_batch_stride)
         return bhwp_fail(BHW_ERR_BADARG, "y_stride / y_batch_stride of the %s descriptor is not 0: the fused mask has no spectrum rows",
                          (sa->y_stride || sa->y_batch_stride) ? "analysis" : "synthesis");
@@ -3246,6 +3225,36 @@ int bhwp_mask_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s
     return BHW_OK;
 }
 
+int bhwp_mask_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const void *d_x,
+                         const void *d_g, uint64_t g_stride, uint64_t g_batch_stride, const void *d_out, bool pointers)
+{
+    int rc = bhwp_f32_checks(p, length, flags);
+    if (rc) return rc;
+    // the routes that take what this call does not: named before the parents refuse the same input in their own words
+    for (const bhw_stft *s : {sa, ss}) {
+        if (!s || s->struct_size != sizeof(bhw_stft)) continue;
+        const char *which = s == sa ? "analysis" : "synthesis";
+        if (s->channels == 2)
+            return bhwp_fail(BHW_ERR_UNSUPPORTED, "channels 2 (%s descriptor): the fused mask takes real input and gives real output; "
+                             "bhw_stft_cfft_f32_* + bhw_istft_cfft_f32_* take I/Q", which);
+        if (s->n_fft == (1ull << kFftMaxLog))
+            return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu (%s descriptor): the fused mask takes a power of two in %u..%u; "
+                             "bhw_stft_fft_f32_* + bhw_istft_fft_f32_* take %llu", (unsigned long long)s->n_fft, which, 1u << kFftMinLog,
+                             1u << kMaskFftMaxLog, (unsigned long long)s->n_fft);
+        if ((s->n_fft & (s->n_fft - 1)) && bhwp_mfft_supported(s->n_fft))
+            return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu (%s descriptor): the fused mask takes a power of two in %u..%u; "
+                             "bhw_stft_mfft_f32_* + bhw_istft_mfft_f32_* take the mixed-radix lengths", (unsigned long long)s->n_fft, which,
+                             1u << kFftMinLog, 1u << kMaskFftMaxLog);
+    }
+    // each descriptor by its parent's checks, with packed row strides (no spectrum rows exist here)
+    bhw_stft ta, ts;
+    rc = bhwp_stft_fft_checks(p, length, packed_strides(sa, ta), 0, nullptr, nullptr, false);
+    if (rc) return rc;
+    rc = bhwp_istft_fft_checks(p, length, packed_strides(ss, ts), flags, nullptr, nullptr, false);
+    if (rc) return rc;
+    return mask_tail_checks(sa, ss, d_x, d_g, g_stride, g_batch_stride, d_out, pointers);
+}
+
 BhwMaskFftPlan bhwp_mask_fft_plan(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
                                   uint64_t g_stride, uint64_t g_batch_stride, bool from_table)
 {
@@ -3258,24 +3267,32 @@ BhwMaskFftPlan bhwp_mask_fft_plan(const bhw_params *p, uint64_t length, const bh
     return pl;
 }
 
-int bhwp_describe_mask_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *sa, const bhw_stft *ss,
-                           uint32_t flags, uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len)
+// The describe line of a fused mask of `family` ("fft", "mfft") from its parent's: parent_of(line, size) writes the inverse describe
+// line of ss and gives the mask plan's t0 and LDS bytes.  The parent's plan fields stand in its line from the row count on, and stay
+// in the parent's words, schedule text included, but for the LDS.
+struct MaskLine {
+    int rc;
+    uint64_t t0;
+    uint32_t lds_bytes;
+};
+template <typename ParentOf>
+static int describe_mask(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
+                         uint64_t g_stride, uint64_t g_batch_stride, const char *family, const char *k_direct, const char *k_table, char *buf,
+                         uint64_t len, ParentOf parent_of)
 {
     if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
     const char *route = ct ? "table" : "direct";
     const char *norm = (flags & BHW_OLA_NORMALIZE) ? "normalised by the window envelope" : "not normalised";
     if (!ss->samples) {
-        snprintf(buf, len, "mask fft %s (L = %llu, n_fft %llu), %s: nothing (samples 0)", route, (unsigned long long)length,
+        snprintf(buf, len, "mask %s %s (L = %llu, n_fft %llu), %s: nothing (samples 0)", family, route, (unsigned long long)length,
                  (unsigned long long)ss->n_fft, norm);
         return BHW_OK;
     }
-    // the parent's line: its plan fields stand in it from the kernel's name on, and stay in the parent's words, but for the LDS
     char parent[1024];
-    const int rc = bhwp_describe_istft_fft(p, ct, length, ss, flags, parent, sizeof parent);
-    if (rc) return rc;
-    const BhwMaskFftPlan pl = bhwp_mask_fft_plan(p, length, sa, ss, flags, g_stride, g_batch_stride, ct != nullptr);
+    const MaskLine ml = parent_of(parent, sizeof parent);
+    if (ml.rc) return ml.rc;
     char kern[64], gains[160];
-    kernel_name(p, ct, "k_mask_fft_direct", "k_mask_fft_table", false, kern, sizeof kern);
+    kernel_name(p, ct, k_direct, k_table, false, kern, sizeof kern);
     if (!g_stride && !g_batch_stride) snprintf(gains, sizeof gains, "one gain row for every frame and every signal");
     else if (!g_stride) snprintf(gains, sizeof gains, "one gain row for every frame, g_batch_stride %llu", (unsigned long long)g_batch_stride);
     else if (!g_batch_stride) snprintf(gains, sizeof gains, "g_stride %llu, one set of gain rows for every signal", (unsigned long long)g_stride);
@@ -3287,11 +3304,83 @@ int bhwp_describe_mask_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t
     while (lds && lds > fields && lds[-1] != ' ') --lds;
     if (!lds) return bhwp_fail(BHW_ERR_BADARG, "buf: the inverse describe line has no plan fields");
     const char *pad = sa->pad_mode == BHW_PAD_REFLECT ? "reflect" : "constant";
-    snprintf(buf, len, "mask fft %s (L = %llu, n_fft %llu, col0 %llu, pad %llu: t0 = %llu; analysis of %llu samples, pad %llu %s), %s: %s, "
-             "forward + inverse FFT, gains: %s, %.*s%u%s", route, (unsigned long long)length, (unsigned long long)ss->n_fft,
-             (unsigned long long)ss->col0, (unsigned long long)ss->pad, (unsigned long long)pl.t0, (unsigned long long)sa->samples,
-             (unsigned long long)sa->pad, pad, norm, kern, gains, (int)(lds - fields), fields, pl.lds_bytes, lds_end);
+    snprintf(buf, len, "mask %s %s (L = %llu, n_fft %llu, col0 %llu, pad %llu: t0 = %llu; analysis of %llu samples, pad %llu %s), %s: %s, "
+             "forward + inverse FFT, gains: %s, %.*s%u%s", family, route, (unsigned long long)length, (unsigned long long)ss->n_fft,
+             (unsigned long long)ss->col0, (unsigned long long)ss->pad, (unsigned long long)ml.t0, (unsigned long long)sa->samples,
+             (unsigned long long)sa->pad, pad, norm, kern, gains, (int)(lds - fields), fields, ml.lds_bytes, lds_end);
     return BHW_OK;
+}
+
+int bhwp_describe_mask_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *sa, const bhw_stft *ss,
+                           uint32_t flags, uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len)
+{
+    return describe_mask(p, ct, length, sa, ss, flags, g_stride, g_batch_stride, "fft", "k_mask_fft_direct", "k_mask_fft_table", buf, len,
+                         [&](char *parent, uint64_t size) {
+                             const int rc = bhwp_describe_istft_fft(p, ct, length, ss, flags, parent, size);
+                             if (rc) return MaskLine{rc, 0, 0};
+                             const BhwMaskFftPlan pl = bhwp_mask_fft_plan(p, length, sa, ss, flags, g_stride, g_batch_stride, ct != nullptr);
+                             return MaskLine{0, pl.t0, pl.lds_bytes};
+                         });
+}
+
+// ---- fused STFT, spectral mask and inverse STFT at mixed-radix n_fft ---------------------------------------------------------------------
+
+int bhwp_mask_mfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const void *d_x,
+                          const void *d_g, uint64_t g_stride, uint64_t g_batch_stride, const void *d_out, bool pointers)
+{
+    int rc = bhwp_f32_checks(p, length, flags);
+    if (rc) return rc;
+    // the routes that take what this call does not: named before the parents refuse the same input in their own words
+    for (const bhw_stft *s : {sa, ss}) {
+        if (!s || s->struct_size != sizeof(bhw_stft)) continue;
+        const char *which = s == sa ? "analysis" : "synthesis";
+        const bool pow2 = s->n_fft && !(s->n_fft & (s->n_fft - 1));
+        if (s->channels == 2)
+            return bhwp_fail(BHW_ERR_UNSUPPORTED, "channels 2 (%s descriptor): the mixed-radix fused mask takes real input and gives real "
+                             "output; bhw_stft_cmfft_f32_* + bhw_istft_cmfft_f32_* take I/Q", which);
+        if (pow2 && s->n_fft >= (1ull << kFftMinLog) && s->n_fft <= (1ull << kMaskFftMaxLog))
+            return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu (%s descriptor) is a power of two: bhw_mask_fft_f32_* takes it; the mixed-radix "
+                             "fused mask takes an even 2^a 3^b 5^c in %u..%u", (unsigned long long)s->n_fft, which, kMfftMinN, kMaskMfftMaxN);
+        if (s->n_fft == (1ull << kFftMaxLog))
+            return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu (%s descriptor) is a power of two: bhw_stft_fft_f32_* + bhw_istft_fft_f32_* "
+                             "take it; the mixed-radix fused mask takes an even 2^a 3^b 5^c in %u..%u", (unsigned long long)s->n_fft, which,
+                             kMfftMinN, kMaskMfftMaxN);
+        if (s->n_fft > kMaskMfftMaxN && bhwp_mfft_supported(s->n_fft))
+            return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu (%s descriptor): the mixed-radix fused mask takes an even 2^a 3^b 5^c in "
+                             "%u..%u; bhw_stft_mfft_f32_* + bhw_istft_mfft_f32_* take the larger ones", (unsigned long long)s->n_fft, which,
+                             kMfftMinN, kMaskMfftMaxN);
+    }
+    // each descriptor by its parent's checks, with packed row strides (no spectrum rows exist here)
+    bhw_stft ta, ts;
+    rc = bhwp_stft_mfft_checks(p, length, packed_strides(sa, ta), 0, nullptr, nullptr, nullptr, false);
+    if (rc) return rc;
+    rc = bhwp_istft_mfft_checks(p, length, packed_strides(ss, ts), flags, nullptr, nullptr, false);
+    if (rc) return rc;
+    return mask_tail_checks(sa, ss, d_x, d_g, g_stride, g_batch_stride, d_out, pointers);
+}
+
+BhwMaskMfftPlan bhwp_mask_mfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
+                                    uint64_t g_stride, uint64_t g_batch_stride, bool from_table)
+{
+    BhwMaskMfftPlan pl{};
+    static_cast<BhwIstftMfftPlan &>(pl) = bhwp_istft_mfft_plan(p, length, ss, flags, from_table);
+    pl.lds_bytes = 2u * pl.fy * pl.m * 8u + 2u * pl.m * 8u + (uint32_t)ss->n_fft * 4u;     // the forward table beside the inverse one
+    pl.in_stride = sa->x_stride ? sa->x_stride : sa->samples;
+    pl.g_stride = g_stride;
+    pl.g_bstride = g_batch_stride;
+    return pl;
+}
+
+int bhwp_describe_mask_mfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *sa, const bhw_stft *ss,
+                            uint32_t flags, uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len)
+{
+    return describe_mask(p, ct, length, sa, ss, flags, g_stride, g_batch_stride, "mfft", "k_mask_mfft_direct", "k_mask_mfft_table", buf, len,
+                         [&](char *parent, uint64_t size) {
+                             const int rc = bhwp_describe_istft_mfft(p, ct, length, ss, flags, parent, size);
+                             if (rc) return MaskLine{rc, 0, 0};
+                             const BhwMaskMfftPlan pl = bhwp_mask_mfft_plan(p, length, sa, ss, flags, g_stride, g_batch_stride, ct != nullptr);
+                             return MaskLine{0, pl.t0, pl.lds_bytes};
+                         });
 }
 
 // ---- fused inverse mixed-radix FFT, window and overlap-add ----------------------------------------------------------------------------------

@@ -973,6 +973,29 @@ int  bhwp_describe_istft_mfft(const bhw_params *p, const BhwCordicCfg *ct, uint6
 int  bhwk_istft_mfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwIstftMfftPlan &pl, const bhw_stft *s,
                          const float *d_Y, float *d_x, const int32_t *d_table, const BhwLenPhase &lp);
 
+// ---- fused STFT, spectral mask and inverse STFT at mixed-radix n_fft (bhw_mask_mfft_f32_*; bhw_mask_mfft.hip) ---------------------------
+// The inverse mixed-radix kernel with its frames formed from the signal, as BhwMaskFftPlan is the power-of-two one: the plan IS
+// bhwp_istft_mfft_plan of the synthesis descriptor, field for field, but for the LDS, which holds a second (forward) twiddle table:
+// 40 000 bytes at 2000, the largest n_fft.  Below 2048 the forward planner gives lpf >= n_fft / 8, so a lane keeps at most 8 ring
+// columns; the 22 sizes from 2160 to 4050 need 16 and up to 81 000 bytes, and are refused.
+constexpr uint32_t kMaskMfftMaxN = 2047;              // n_fft < 2048
+struct BhwMaskMfftPlan : BhwIstftMfftPlan {           // lds_bytes: 2 * fy * M * 8 + 2 * M * 8 + n_fft * 4  (<= 40 000)
+    uint64_t in_stride;   // floats between the input signals (0 -> the analysis descriptor's samples)
+    uint64_t g_stride, g_bstride;   // floats between the gain rows of a signal and between the signals' gains, as given (0: one row)
+};
+// Every check of the two calls that needs no table handle, before any HIP call and in the order of include/bhw.h: the params, the
+// refusals that name a route, the two descriptors by the checks of bhw_stft_mfft_f32_* and bhw_istft_mfft_f32_* (in their words), then
+// what bhwp_mask_fft_checks checks after its parents, from the same function.  `pointers` false: the describe call.
+int  bhwp_mask_mfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const void *d_x,
+                           const void *d_g, uint64_t g_stride, uint64_t g_batch_stride, const void *d_out, bool pointers = true);
+// the plan of a call that passed the checks with ss->samples > 0
+BhwMaskMfftPlan bhwp_mask_mfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
+                                    uint64_t g_stride, uint64_t g_batch_stride, bool from_table);
+int  bhwp_describe_mask_mfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *sa, const bhw_stft *ss,
+                             uint32_t flags, uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len);
+int  bhwk_mask_mfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwMaskMfftPlan &pl, const bhw_stft *sa,
+                        const bhw_stft *ss, const float *d_x, const float *d_g, float *d_out, const int32_t *d_table, const BhwLenPhase &lp);
+
 // ---- fused inverse complex FFT, window and overlap-add for I/Q output (bhw_istft_cfft_f32_*; bhw_istft_cfft.hip) ----------------------
 // The lane layout and the passes of bhwp_stft_cfft_plan (lpf lanes along a row of n = n_fft complex points, fy slots side by side,
 // cpl complex columns per lane) under the span plan (BhwIstftRuns: the same S, halo, trips, halo_bound, grid cap and hop clamp, the

@@ -915,9 +915,17 @@ def stft_mask_istft(params, x, mask, n_fft, hop, *, win_length=None, center=True
     (stft_mixed + istft_mixed), complex x (stft_iq + istft_iq), 4096 (stft + istft).  `out`: a contiguous float32 tensor of the
     returned shape; it may not share memory with x or mask.  `table`: a ResidentTable of these params to gather the window
     coefficients from (bhw_mask_fft_f32_from_table: no allocation by the library, no synchronisation, capturable on its first call),
-    or None (the library form: capturable with no warm call)."""
+    or None (the library form: capturable with no warm call).  stft_mask_istft_mixed() is this call at a mixed-radix n_fft."""
     torch = _torch()
     _mask_fft_refusals(torch, x, mask, n_fft)
+    return _stft_mask_istft(torch, params, x, mask, n_fft, hop, win_length, center, pad_mode, length, normalize, shift, out, table,
+                            _fft_input, "bhw_mask_fft_f32_device", "bhw_mask_fft_f32_from_table")
+
+
+def _stft_mask_istft(torch, params, x, mask, n_fft, hop, win_length, center, pad_mode, length, normalize, shift, out, table, check, device_call,
+                     table_call):
+    """What stft_mask_istft() and stft_mask_istft_mixed() share after their refusals: the input checks (check: _fft_input or
+    _mfft_input), the two descriptors, the gains and the one call."""
     if table is not None:
         if not isinstance(table, ResidentTable):
             raise ValueError("table must be a ResidentTable or None")
@@ -926,7 +934,7 @@ def stft_mask_istft(params, x, mask, n_fft, hop, *, win_length=None, center=True
         if not isinstance(x, torch.Tensor) or not x.is_cuda:
             raise ValueError("x must be a float32 CUDA tensor")
         dev, handle = x.device.index, None
-    n_fft, L, xb, nb, T, frames, d = _stft_front(torch, params, x, n_fft, hop, win_length, center, pad_mode, False, dev)
+    n_fft, L, xb, nb, T, frames, d = _stft_front(torch, params, x, n_fft, hop, win_length, center, pad_mode, False, dev, check)
     if not center and L < n_fft:
         raise ValueError("center=False with win_length < n_fft: the first outputs have no window under them")
     K = n_fft // 2 + 1
@@ -942,10 +950,49 @@ def stft_mask_istft(params, x, mask, n_fft, hop, *, win_length=None, center=True
     tail = (ctypes.byref(sa), ctypes.byref(ss), B.OLA_NORMALIZE if normalize else 0, ctypes.c_void_p(xb.data_ptr()),
             ctypes.c_void_p(g.data_ptr()), gs, gbs, ctypes.c_void_p(out.data_ptr()))
     if handle is None:
-        B.check(B.lib().bhw_mask_fft_f32_device(ctypes.byref(params), L, dev, _stream_ptr(torch, dev), *tail))
+        B.check(getattr(B.lib(), device_call)(ctypes.byref(params), L, dev, _stream_ptr(torch, dev), *tail))
     else:
-        B.check(B.lib().bhw_mask_fft_f32_from_table(handle, ctypes.byref(params), L, _stream_ptr(torch, dev), *tail))
+        B.check(getattr(B.lib(), table_call)(handle, ctypes.byref(params), L, _stream_ptr(torch, dev), *tail))
     return out
+
+
+def _mask_mfft_refusals(torch, x, mask, n_fft):
+    """What stft_mask_istft_mixed() does not take, refused naming the calls that do, before any check that needs a device."""
+    if isinstance(mask, torch.Tensor) and mask.is_complex():
+        raise ValueError("the mixed-radix fused mask takes real float32 gains; complex gains are not built: bhw.stft_mixed, a complex "
+                         "multiply and bhw.istft_mixed apply them")
+    if isinstance(x, torch.Tensor) and x.is_complex():
+        raise ValueError(f"the mixed-radix fused mask takes real float32 input, got {x.dtype} (I/Q input: bhw.stft_iq_mixed, a multiply "
+                         f"and bhw.istft_iq_mixed)")
+    n = int(n_fft)
+    if B.mask_fft_supported(n):
+        raise ValueError(f"n_fft {n} is a power of two: bhw.stft_mask_istft takes it (one transform per n_fft)")
+    if B.fft_supported(n):
+        raise ValueError(f"n_fft {n} is a power of two above {B.MASK_FFT_MAX_N}: bhw.stft, a multiply and bhw.istft take it")
+    if n > B.MASK_MFFT_MAX_N and B.mfft_supported(n):
+        raise ValueError(f"the mixed-radix fused mask takes n_fft even 2^a·3^b·5^c in {B.MFFT_MIN_N}..{B.MASK_MFFT_MAX_N}, got {n} "
+                         f"(bhw.stft_mixed, a multiply and bhw.istft_mixed take it)")
+
+
+def stft_mask_istft_mixed(params, x, mask, n_fft, hop, *, win_length=None, center=True, pad_mode="reflect", length=None, normalize=True,
+                          shift=None, out=None, table=None):
+    """stft_mask_istft() at the n_fft of stft_mixed() in ONE launch (bhw_mask_mfft_f32_device): n_fft even, 2^a·3^b·5^c, no power of two,
+    from 18 to 2000 -- 320, 400, 480, 960, 1000, 1200, 1920.  The arguments, the shapes, the `out` rules and the mask layouts are
+    stft_mask_istft()'s: x (T,) or (B, T), float32; mask real float32 (K,), (F, K) or (1 | B, 1 | F, K), K = n_fft // 2 + 1, a
+    broadcast axis (an expand() view included) never materialised.  The result equals
+
+        bhw.istft_mixed(params, bhw.stft_mixed(params, x, n_fft, hop, ...) * mask[..., None], n_fft, hop, ..., length=length,
+                        normalize=normalize)
+
+    BIT FOR BIT.  ValueError naming the calls that take it: a power of two (stft_mask_istft), an n_fft of 2048 or more (stft_mixed, a
+    multiply and istft_mixed), complex x (stft_iq_mixed + istft_iq_mixed), a complex mask (stft_mixed + a complex multiply +
+    istft_mixed).  `table`: a ResidentTable of these params (bhw_mask_mfft_f32_from_table: no allocation by the library, no
+    synchronisation, capturable on its first call), or None (the library form: capturable with no warm call)."""
+    import torch as host_torch                            # the refusals look at no device: they come before _torch() asks for one
+    _mask_mfft_refusals(host_torch, x, mask, n_fft)
+    torch = _torch()
+    return _stft_mask_istft(torch, params, x, mask, n_fft, hop, win_length, center, pad_mode, length, normalize, shift, out, table,
+                            _mfft_input, "bhw_mask_mfft_f32_device", "bhw_mask_mfft_f32_from_table")
 
 
 def fbank_bands(weights):

@@ -1566,8 +1566,8 @@ int bhw_describe_csd_fft(bhw_table t, const bhw_params *p, uint64_t length, cons
  *     and (from a table) the key match.
  *   - No workspace, no allocation, no float atomics.  The library form computes the coefficients by direct CORDIC and both twiddle
  *     tables in the kernel: capturable with no bhw_prepare_device.  The from-table form is capturable on its first call.
- *   - Not built: complex gains; mixed-radix n_fft; I/Q input; 4096; a gain computed in the kernel; a second output with the masked
- *     spectrum.
+ *   - Not built: complex gains; I/Q input; 4096; a gain computed in the kernel; a second output with the masked spectrum.  (A
+ *     mixed-radix n_fft from 18 to 2000 has calls of its own: bhw_mask_mfft_f32_* below.)
  *   - bhw_describe_mask_fft: the plan fields of bhw_describe_istft_fft's line for ss in the same words (the plan IS that call's, but
  *     for the LDS bytes), with the kernel, "forward + inverse FFT", the analysis padding and the gain strides.  It takes the gain
  *     strides because its line and its checks need them.  t may be NULL (the library call).  Host arithmetic only. */
@@ -1578,6 +1578,35 @@ int bhw_mask_fft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t lengt
                                 float *d_out);
 int bhw_describe_mask_fft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
                           uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len);
+
+/* Fused STFT, spectral mask and inverse STFT at a mixed-radix n_fft: bhw_stft_mfft_f32_*, a real gain per bin, and
+ * bhw_istft_mfft_f32_* by ONE launch -- bhw_mask_fft_f32_* for the frame sizes speech and audio callers use (320, 400, 480, 960, 1000,
+ * 1200, 1920).  The arguments are those of bhw_mask_fft_f32_device, _from_table and bhw_describe_mask_fft, word for word, and so is the
+ * contract, stated by the two mixed-radix parents:
+ *   - Y[b, f, k] = (re, im) is the float32 pair bhw_stft_mfft_f32_* writes for (sa, d_x, flags 0); the masked bin is
+ *     (fl32(re * g), fl32(im * g)), one float32 rounding per part; d_out is exactly what bhw_istft_mfft_f32_* writes for (ss, flags)
+ *     from those masked rows.  The three-call route and this call agree WORD FOR WORD.  K = n_fft / 2 + 1.
+ *   - The descriptors, the gain strides (0: one row for every frame / the same gains for every signal), ss->samples 0 -> BHW_OK, the
+ *     determinism and IEEE statements and the overlap rules are bhw_mask_fft_f32_*'s.
+ *   - Supported: channels 1, n_fft even, 2^a 3^b 5^c, no power of two, from 18 to 2000: 73 of the 95 lengths bhw_stft_mfft_f32_* takes
+ *     (a lane keeps at most 8 ring columns and the two twiddle tables fit 40 000 bytes of LDS; the 22 lengths from 2160 to 4050 need
+ *     16 columns and up to 81 000 bytes).  BHW_ERR_UNSUPPORTED naming the route that takes the input: channels 2 names
+ *     bhw_stft_cmfft_f32_* + bhw_istft_cmfft_f32_*, a power of two in 16..2048 bhw_mask_fft_f32_*, 4096 bhw_stft_fft_f32_* +
+ *     bhw_istft_fft_f32_*, a mixed-radix length above 2047 bhw_stft_mfft_f32_* + bhw_istft_mfft_f32_*.
+ *   - Checks before any HIP call, in this order (BHW_ERR_BADARG unless noted): the params and unknown flags; the four refusals above;
+ *     everything bhw_stft_mfft_f32_* checks on sa and everything bhw_istft_mfft_f32_* checks on ss, both with packed row strides and
+ *     in those calls' own words; then what bhw_mask_fft_f32_* checks after its parents, in its words and its order.
+ *   - No workspace, no allocation, no float atomics; both forms are capturable as bhw_mask_fft_f32_*'s are.
+ *   - Not built: complex gains; I/Q input; n_fft >= 2048; a gain computed in the kernel; a second output with the masked spectrum.
+ *   - bhw_describe_mask_mfft: the plan fields of bhw_describe_istft_mfft's line for ss in the same words (the plan IS that call's, but
+ *     for the LDS bytes), with the kernel, "forward + inverse FFT", the analysis padding and the gain strides. */
+int bhw_mask_mfft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *sa, const bhw_stft *ss,
+                             uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride, float *d_out);
+int bhw_mask_mfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *sa, const bhw_stft *ss,
+                                 uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride,
+                                 float *d_out);
+int bhw_describe_mask_mfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
+                           uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len);
 
 /* Threading: every entry point may be called from any host thread.  Calls that use the library-owned scratch of one
  * (device, stream) are serialised against each other for the duration of their launches (the table is rebuilt per call);
