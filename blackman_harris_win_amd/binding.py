@@ -66,6 +66,8 @@ ABI_SYMBOLS = (
     "bhw_hold_mfft_workspace_bytes", "bhw_hold_mfft_f32_device", "bhw_hold_mfft_f32_from_table", "bhw_describe_hold_mfft",
     "bhw_mask_fft_f32_device", "bhw_mask_fft_f32_from_table", "bhw_describe_mask_fft",
     "bhw_mask_mfft_f32_device", "bhw_mask_mfft_f32_from_table", "bhw_describe_mask_mfft",
+    "bhw_cmask_fft_f32_device", "bhw_cmask_fft_f32_from_table", "bhw_describe_cmask_fft",
+    "bhw_cmask_mfft_f32_device", "bhw_cmask_mfft_f32_from_table", "bhw_describe_cmask_mfft",
 )
 
 
@@ -357,6 +359,10 @@ def lib():
     L.bhw_mask_mfft_f32_device.argtypes = [P, u64, ci, vp, S, S, u32, f32p, f32p, u64, u64, f32p]
     L.bhw_mask_mfft_f32_from_table.argtypes = [T, P, u64, vp, S, S, u32, f32p, f32p, u64, u64, f32p]
     L.bhw_describe_mask_mfft.argtypes = [T, P, u64, S, S, u32, u64, u64, ctypes.c_char_p, u64]
+    for fam in ("fft", "mfft"):                          # d_g: interleaved float32 pairs, the strides in pairs
+        getattr(L, f"bhw_cmask_{fam}_f32_device").argtypes = [P, u64, ci, vp, S, S, u32, f32p, f32p, u64, u64, f32p]
+        getattr(L, f"bhw_cmask_{fam}_f32_from_table").argtypes = [T, P, u64, vp, S, S, u32, f32p, f32p, u64, u64, f32p]
+        getattr(L, f"bhw_describe_cmask_{fam}").argtypes = [T, P, u64, S, S, u32, u64, u64, ctypes.c_char_p, u64]
     FB = ctypes.POINTER(BhwFbank)
     L.bhw_spectrogram_f32_device.argtypes = [P, u64, ci, vp, S, u32, FB, f32p, f32p]
     L.bhw_spectrogram_f32_from_table.argtypes = [T, P, u64, vp, S, u32, FB, f32p, f32p]
@@ -600,6 +606,25 @@ def describe_mask_mfft(params, length, analysis, synthesis, *, normalize=False, 
     buf = ctypes.create_string_buffer(1280)
     check(lib().bhw_describe_mask_mfft(table, ctypes.byref(params), int(length), ctypes.byref(analysis), ctypes.byref(synthesis),
                                        OLA_NORMALIZE if normalize else 0, int(g_stride), int(g_batch_stride), buf, len(buf)))
+    return buf.value.decode()
+
+
+def describe_cmask_fft(params, length, analysis, synthesis, *, normalize=False, g_stride=0, g_batch_stride=0, table=None):
+    """describe_mask_fft() for the complex-gain call (bhw_describe_cmask_fft): the same plan fields -- the plan IS the real-gain
+    call's; the gains live in registers -- in a line that begins "cmask", names k_cmask_fft_direct / k_cmask_fft_table and says
+    "complex gains".  The gain strides count (gr, gi) pairs.  Host arithmetic only."""
+    buf = ctypes.create_string_buffer(1280)
+    check(lib().bhw_describe_cmask_fft(table, ctypes.byref(params), int(length), ctypes.byref(analysis), ctypes.byref(synthesis),
+                                       OLA_NORMALIZE if normalize else 0, int(g_stride), int(g_batch_stride), buf, len(buf)))
+    return buf.value.decode()
+
+
+def describe_cmask_mfft(params, length, analysis, synthesis, *, normalize=False, g_stride=0, g_batch_stride=0, table=None):
+    """describe_cmask_fft() for a mixed-radix n_fft (bhw_describe_cmask_mfft): describe_mask_mfft()'s plan fields, k_cmask_mfft_direct /
+    k_cmask_mfft_table and "complex gains", the strides in pairs.  Host arithmetic only."""
+    buf = ctypes.create_string_buffer(1280)
+    check(lib().bhw_describe_cmask_mfft(table, ctypes.byref(params), int(length), ctypes.byref(analysis), ctypes.byref(synthesis),
+                                        OLA_NORMALIZE if normalize else 0, int(g_stride), int(g_batch_stride), buf, len(buf)))
     return buf.value.decode()
 
 

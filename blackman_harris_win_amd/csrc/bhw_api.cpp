@@ -1398,34 +1398,51 @@ int istft_cmfft_run(bhw_table t, const bhw_params *p, uint64_t length, int devic
         "istft cmfft launch", "istft cmfft launch (resident table)", t, p, length, device, stream, s, flags, d_Y, d_x);
 }
 
-// The fused STFT, mask and inverse STFT (t NULL: the direct CORDIC chains): its checks, then the inverse plan and the one kernel.
-int mask_fft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *sa, const bhw_stft *ss,
-                 uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride, float *d_out)
+// The fused STFT, mask and inverse STFT (t NULL: the direct CORDIC chains): its checks, then the inverse plan and the one kernel.  One
+// text for the two families and the two gain types: Checks / Plan / Kernel are bhwp_[c]mask_[m]fft_checks, bhwp_mask_[m]fft_plan (the
+// complex-gain calls run the real-gain plan, their strides in pairs) and bhwk_[c]mask_[m]fft_f32.
+template <auto Checks, auto Plan, auto Kernel>
+int mask_run(const char *what, const char *what_table, bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream,
+             const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride,
+             uint64_t g_batch_stride, float *d_out)
 {
-    int rc = bhwp_mask_fft_checks(p, length, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out);
+    int rc = Checks(p, length, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out, true);
     if (!rc && t) rc = table_call_checks(t, p);
     if (rc || !ss->samples) return rc;
-    const BhwMaskFftPlan pl = bhwp_mask_fft_plan(p, length, sa, ss, flags, g_stride, g_batch_stride, t != nullptr);
-    const char *what = t ? "mask fft launch (resident table)" : "mask fft launch";
-    return run_source(t, p, length, device, stream, what, [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *tab,
-                                                              const BhwLenPhase *lp) {
-        return bhwk_mask_fft_f32(l, c, w, pl, sa, ss, d_x, d_g, d_out, tab, *lp);
+    const auto pl = Plan(p, length, sa, ss, flags, g_stride, g_batch_stride, t != nullptr);
+    return run_source(t, p, length, device, stream, t ? what_table : what, [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w,
+                                                                               const int32_t *tab, const BhwLenPhase *lp) {
+        return Kernel(l, c, w, pl, sa, ss, d_x, d_g, d_out, tab, *lp);
     });
 }
 
-// The same at a mixed-radix n_fft: its checks, then the inverse mixed-radix plan and the one kernel.
+int mask_fft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *sa, const bhw_stft *ss,
+                 uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride, float *d_out)
+{
+    return mask_run<bhwp_mask_fft_checks, bhwp_mask_fft_plan, bhwk_mask_fft_f32>(
+        "mask fft launch", "mask fft launch (resident table)", t, p, length, device, stream, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out);
+}
+
 int mask_mfft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *sa, const bhw_stft *ss,
                   uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride, float *d_out)
 {
-    int rc = bhwp_mask_mfft_checks(p, length, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out);
-    if (!rc && t) rc = table_call_checks(t, p);
-    if (rc || !ss->samples) return rc;
-    const BhwMaskMfftPlan pl = bhwp_mask_mfft_plan(p, length, sa, ss, flags, g_stride, g_batch_stride, t != nullptr);
-    const char *what = t ? "mask mfft launch (resident table)" : "mask mfft launch";
-    return run_source(t, p, length, device, stream, what, [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *tab,
-                                                              const BhwLenPhase *lp) {
-        return bhwk_mask_mfft_f32(l, c, w, pl, sa, ss, d_x, d_g, d_out, tab, *lp);
-    });
+    return mask_run<bhwp_mask_mfft_checks, bhwp_mask_mfft_plan, bhwk_mask_mfft_f32>(
+        "mask mfft launch", "mask mfft launch (resident table)", t, p, length, device, stream, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out);
+}
+
+// d_g: interleaved float32 pairs (gr, gi), the strides in pairs
+int cmask_fft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *sa, const bhw_stft *ss,
+                  uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride, float *d_out)
+{
+    return mask_run<bhwp_cmask_fft_checks, bhwp_mask_fft_plan, bhwk_cmask_fft_f32>(
+        "cmask fft launch", "cmask fft launch (resident table)", t, p, length, device, stream, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out);
+}
+
+int cmask_mfft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *sa, const bhw_stft *ss,
+                   uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride, float *d_out)
+{
+    return mask_run<bhwp_cmask_mfft_checks, bhwp_mask_mfft_plan, bhwk_cmask_mfft_f32>(
+        "cmask mfft launch", "cmask mfft launch (resident table)", t, p, length, device, stream, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out);
 }
 
 // The window sums (t NULL: the direct CORDIC chains): the checks, then the memset of the four words and the reduction.
@@ -2080,6 +2097,58 @@ int bhw_describe_mask_mfft(bhw_table t, const bhw_params *p, uint64_t length, co
     int rc = bhwp_mask_mfft_checks(p, length, sa, ss, flags, nullptr, nullptr, g_stride, g_batch_stride, nullptr, false);
     if (!rc && t) rc = table_call_checks(t, p);
     return rc ? rc : bhwp_describe_mask_mfft(p, t ? &t->c : nullptr, length, sa, ss, flags, g_stride, g_batch_stride, buf, len);
+}
+
+// ---- fused STFT, complex spectral gain and inverse STFT (include/bhw.h: bhw_cmask_fft_f32_device ...) ----------------------------------
+
+int bhw_cmask_fft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *sa, const bhw_stft *ss,
+                             uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride, float *d_out)
+{
+    return cmask_fft_run(nullptr, p, length, device, hip_stream, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out);
+}
+
+int bhw_cmask_fft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *sa, const bhw_stft *ss,
+                                 uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride,
+                                 float *d_out)
+{
+    const int rc = bhwp_cmask_fft_checks(p, length, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out);
+    if (rc) return rc;
+    return t ? cmask_fft_run(t, p, length, t->device, hip_stream, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out)
+             : fail(BHW_ERR_BADARG, "table is NULL");
+}
+
+int bhw_describe_cmask_fft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
+                           uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len)
+{
+    int rc = bhwp_cmask_fft_checks(p, length, sa, ss, flags, nullptr, nullptr, g_stride, g_batch_stride, nullptr, false);
+    if (!rc && t) rc = table_call_checks(t, p);
+    return rc ? rc : bhwp_describe_cmask_fft(p, t ? &t->c : nullptr, length, sa, ss, flags, g_stride, g_batch_stride, buf, len);
+}
+
+// ---- fused STFT, complex spectral gain and inverse STFT at mixed-radix n_fft (include/bhw.h: bhw_cmask_mfft_f32_device ...) ---------------
+
+int bhw_cmask_mfft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *sa, const bhw_stft *ss,
+                              uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride, float *d_out)
+{
+    return cmask_mfft_run(nullptr, p, length, device, hip_stream, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out);
+}
+
+int bhw_cmask_mfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *sa, const bhw_stft *ss,
+                                  uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride,
+                                  float *d_out)
+{
+    const int rc = bhwp_cmask_mfft_checks(p, length, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out);
+    if (rc) return rc;
+    return t ? cmask_mfft_run(t, p, length, t->device, hip_stream, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out)
+             : fail(BHW_ERR_BADARG, "table is NULL");
+}
+
+int bhw_describe_cmask_mfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
+                            uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len)
+{
+    int rc = bhwp_cmask_mfft_checks(p, length, sa, ss, flags, nullptr, nullptr, g_stride, g_batch_stride, nullptr, false);
+    if (!rc && t) rc = table_call_checks(t, p);
+    return rc ? rc : bhwp_describe_cmask_mfft(p, t ? &t->c : nullptr, length, sa, ss, flags, g_stride, g_batch_stride, buf, len);
 }
 
 // ---- fused log spectrogram, log-mel and MFCC (include/bhw.h: bhw_logspec_f32_device ..., bhw_logspec_mfft_f32_device ...) -------------

@@ -1,5 +1,6 @@
 // bhw_mask_fft.hip -- window, real FFT, a real gain per bin, inverse real FFT, window and overlap-add in one kernel
 // (bhw_mask_fft_f32_device / _from_table; contract: include/bhw.h, plan: BhwMaskFftPlan in bhw_plan.h, reasons: DESIGN.md section 41).
+// The same kernel with a complex gain per bin: bhw_cmask_fft_f32_device / _from_table, k_cmask_fft_* below.
 //
 // The span / ring / flush kernel of bhw_istft_fft.hip (istft_fft_spans in bhw_istft_fft.h) with another frame source: where that
 // kernel loads the bins Y[k], Y[M - k] of a frame from memory, this one forms them in LDS from the signal.  Prologue, once per
@@ -22,11 +23,16 @@
 
 namespace {
 
-struct MaskSource {
+// G, the gain of a bin: float (bhw_mask_fft_f32_*) or the pair fft_v2f (gr, gi) (bhw_cmask_fft_f32_*).  g points to G and the two gain
+// strides count G, so step c. loads gp[k] ascending and gp[M - k] descending as 4-byte words or as 8-byte pairs from the one text of
+// frame(); masked() is overloaded on G.  tests/cpp/san_cmask.cpp replays the pair reads.
+template <typename G>
+struct MaskSourceT {
     static constexpr bool kBins = false;
     static constexpr uint32_t kTables = 2;
     static constexpr uint32_t kMaxCpl = 8;                            // n_fft <= 2048: 16 columns per lane come with 4096 only
-    const float *x, *g;
+    const float *x;
+    const G *g;
     uint64_t samples, pad, hop, x_stride, g_stride, g_bstride;
     uint32_t reflect;
 
@@ -37,6 +43,13 @@ struct MaskSource {
     {
 #pragma clang fp contract(off)
         return fft_v2f{y.x * gain, y.y * gain};
+    }
+    // by a pair (gr, gi): four products, each rounded on its own, then one subtraction and one addition (include/bhw.h)
+    static __device__ __forceinline__ fft_v2f masked(fft_v2f y, fft_v2f gain)
+    {
+#pragma clang fp contract(off)
+        const float rr = y.x * gain.x, ii = y.y * gain.y, ri = y.x * gain.y, ir = y.y * gain.x;
+        return fft_v2f{rr - ii, ri + ir};
     }
 
     __device__ __forceinline__ void frame(const IfftIo &a, bool act, uint64_t b, uint64_t f, uint32_t l, const fft_v2f *tw, const float *vS,
@@ -110,7 +123,7 @@ struct MaskSource {
         }
         // c. the split, the gains and the pre-split, into the other buffer
         if (act) {
-            const float *gp = g + b * g_bstride + f * g_stride;
+            const G *gp = g + b * g_bstride + f * g_stride;
             for (uint32_t k = l; k <= H; k += lpf) {
 #pragma clang fp contract(off)
                 const fft_v2f A = masked(fft_split_bin(src, twf, k, M), gp[k]);
@@ -124,6 +137,8 @@ struct MaskSource {
         dst = sw;
     }
 };
+using MaskSource = MaskSourceT<float>;
+using CMaskSource = MaskSourceT<fft_v2f>;
 
 // Coefficient by the direct CORDIC chains (FORM: direct_form, as k_istft_fft_direct).
 template <int FORM>
@@ -160,10 +175,45 @@ __global__ __launch_bounds__(kFftBlock, 4) void k_mask_fft_table(BhwCordicCfg cf
     istft_fft_spans(a, m);
 }
 
+// The same two kernels under the pair-gain source (bhw_cmask_fft_f32_*): the prologues are the ones above, word for word.
+template <int FORM>
+__global__ __launch_bounds__(kFftBlock, 4) void k_cmask_fft_direct(BhwCordicCfg cfg, BhwWinCfg win, IfftIo a, CMaskSource m, BhwLenPhase lp)
+{
+    using T = std::conditional_t<FORM == 0, int32_t, int64_t>;
+    using L = std::conditional_t<FORM == 2, uint32_t, T>;
+    __shared__ L lut_s[32];
+    if (threadIdx.x < 32) lut_s[threadIdx.x] = (L)cfg.lut[threadIdx.x];
+    __syncthreads();
+    float *vS = (float *)(fft_lds + (size_t)(2u * a.fy + 2u) * a.m * sizeof(fft_v2f));
+    for (uint32_t k = threadIdx.x; k < a.len; k += kFftBlock) {
+        int32_t w;
+        if constexpr (FORM == 2) w = direct_coeff_mad_ph(cfg, win, lut_s, len_theta_of(lp, k));
+        else                     w = direct_coeff_ph<T>(cfg, win, lut_s, len_theta_of(lp, k));
+        vS[k] = fft_coeff(w, a.shift);
+    }
+    istft_fft_spans(a, m);
+}
+
+template <int FMT, int NT, int MODE>
+__global__ __launch_bounds__(kFftBlock, 4) void k_cmask_fft_table(BhwCordicCfg cfg, BhwWinCfg win, const void *__restrict__ table, IfftIo a,
+                                                                CMaskSource m, BhwLenPhase lp)
+{
+    float *vS = (float *)(fft_lds + (size_t)(2u * a.fy + 2u) * a.m * sizeof(fft_v2f));
+    for (uint32_t k0 = 0; k0 < a.len; k0 += kFftBlock) {
+        const uint32_t k = k0 + threadIdx.x;
+        const bool in = k < a.len;
+        const int32_t w = range_coeff_ph<FMT, NT, MODE>(cfg, win, table, len_theta_of(lp, in ? k : 0u));
+        if (in) vS[k] = fft_coeff(w, a.shift);
+    }
+    istft_fft_spans(a, m);
+}
+
 } // namespace
 
-int bhwk_mask_fft_f32(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinCfg &w, const BhwMaskFftPlan &pl, const bhw_stft *sa,
-                      const bhw_stft *ss, const float *d_x, const float *d_g, float *d_out, const int32_t *d_table, const BhwLenPhase &lp)
+// One launcher for both gain types: G float launches k_mask_fft_*, G fft_v2f (d_g: pairs, the strides in pairs) k_cmask_fft_*.
+template <typename G>
+static int mask_fft_launch(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinCfg &w, const BhwMaskFftPlan &pl, const bhw_stft *sa,
+                           const bhw_stft *ss, const float *d_x, const G *d_g, float *d_out, const int32_t *d_table, const BhwLenPhase &lp)
 {
     if (!ss->samples) return 0;
     if (pl.cpl > MaskSource::kMaxCpl) return (int)hipErrorInvalidValue;   // (the checks refuse 4096)
@@ -173,7 +223,7 @@ int bhwk_mask_fft_f32(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWin
     a.m = pl.m;
     a.radix4 = pl.radix4;
     a.radix2 = pl.radix2;
-    MaskSource m;
+    MaskSourceT<G> m;
     m.x = d_x;
     m.g = d_g;
     m.samples = sa->samples;
@@ -185,8 +235,24 @@ int bhwk_mask_fft_f32(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWin
     m.reflect = sa->pad_mode == BHW_PAD_REFLECT ? 1u : 0u;
     const dim3 grid((unsigned)pl.grid), block(kFftBlock);
     return with_window_source(
-        c_in, w, d_table, [&](auto D) { launch_lds(k_mask_fft_direct<D>, grid, block, pl.lds_bytes, st, c_in, w, a, m, lp); },
+        c_in, w, d_table, [&](auto D) {
+            if constexpr (std::is_same_v<G, float>) launch_lds(k_mask_fft_direct<D>, grid, block, pl.lds_bytes, st, c_in, w, a, m, lp);
+            else                                    launch_lds(k_cmask_fft_direct<D>, grid, block, pl.lds_bytes, st, c_in, w, a, m, lp);
+        },
         [&](auto F, auto NT, auto M, const BhwCordicCfg &c, const void *tab) {
-            launch_lds(k_mask_fft_table<F, NT, M>, grid, block, pl.lds_bytes, st, c, w, tab, a, m, lp);
+            if constexpr (std::is_same_v<G, float>) launch_lds(k_mask_fft_table<F, NT, M>, grid, block, pl.lds_bytes, st, c, w, tab, a, m, lp);
+            else                                    launch_lds(k_cmask_fft_table<F, NT, M>, grid, block, pl.lds_bytes, st, c, w, tab, a, m, lp);
         });
+}
+
+int bhwk_mask_fft_f32(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinCfg &w, const BhwMaskFftPlan &pl, const bhw_stft *sa,
+                      const bhw_stft *ss, const float *d_x, const float *d_g, float *d_out, const int32_t *d_table, const BhwLenPhase &lp)
+{
+    return mask_fft_launch<float>(l, c_in, w, pl, sa, ss, d_x, d_g, d_out, d_table, lp);
+}
+
+int bhwk_cmask_fft_f32(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinCfg &w, const BhwMaskFftPlan &pl, const bhw_stft *sa,
+                       const bhw_stft *ss, const float *d_x, const float *d_g, float *d_out, const int32_t *d_table, const BhwLenPhase &lp)
+{
+    return mask_fft_launch<fft_v2f>(l, c_in, w, pl, sa, ss, d_x, (const fft_v2f *)d_g, d_out, d_table, lp);
 }

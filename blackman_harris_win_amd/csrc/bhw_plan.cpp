@@ -3180,10 +3180,12 @@ static int mask_fft_agree(const char *field, uint64_t a, uint64_t s)
 }
 
 // What both fused masks check once each descriptor has passed its parent's checks: nonzero y strides, the seven fields that must agree,
-// the gain strides, the pointers, their alignment, the extents, the wrap and the overlaps.
+// the gain strides, the pointers, their alignment, the extents, the wrap and the overlaps.  g_elem: the bytes of a gain, 4 (a float) or
+// 8 (an interleaved float32 pair (gr, gi)); the gain strides and the gain extent count such elements.
 static int mask_tail_checks(const bhw_stft *sa, const bhw_stft *ss, const void *d_x, const void *d_g, uint64_t g_stride, uint64_t g_batch_stride,
-                            const void *d_out, bool pointers)
+                            const void *d_out, bool pointers, uint32_t g_elem)
 {
+    const char *unit = g_elem == 8u ? "pairs" : "floats";
     int rc;
     if (sa->y_stride || sa->y_batch_stride || ss->y_stride || ss->y_batch_stride)
         return bhwp_fail(BHW_ERR_BADARG, "y_stride / y_batch_stride of the %s descriptor is not 0: the fused mask has no spectrum rows",
@@ -3199,16 +3201,18 @@ static int mask_tail_checks(const bhw_stft *sa, const bhw_stft *ss, const void *
     // (samples > 0: the inverse checks have refused frames 0, and with frames > 0 the forward ones samples 0 of the analysis side)
     const uint64_t K = ss->n_fft / 2 + 1, F = ss->frames, Bn = ss->batch;
     if (g_stride && g_stride < K)
-        return bhwp_fail(BHW_ERR_BADARG, "g_stride %llu: 0 (one gain row for every frame) or at least K = %llu floats", (unsigned long long)g_stride,
-                         (unsigned long long)K);
+        return bhwp_fail(BHW_ERR_BADARG, "g_stride %llu: 0 (one gain row for every frame) or at least K = %llu %s", (unsigned long long)g_stride,
+                         (unsigned long long)K, unit);
     const unsigned __int128 gsig = (unsigned __int128)(F - 1) * g_stride + K;                // the gain rows of one signal
     if (gsig > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "g extent beyond 2^60 elements");
     if (g_batch_stride && g_batch_stride < (uint64_t)gsig)
         return bhwp_fail(BHW_ERR_BADARG, "g_batch_stride %llu: 0 (the same gains for every signal) or at least (frames - 1) * g_stride + K = "
-                         "%llu floats", (unsigned long long)g_batch_stride, (unsigned long long)(uint64_t)gsig);
+                         "%llu %s", (unsigned long long)g_batch_stride, (unsigned long long)(uint64_t)gsig, unit);
     if (!pointers) return BHW_OK;
     if (!d_x || !d_g || !d_out) return bhwp_fail(BHW_ERR_BADARG, "d_x / d_g / d_out is NULL");
     if ((uintptr_t)d_x % 4) return bhwp_fail(BHW_ERR_BADARG, "d_x is not 4-byte aligned");
+    if (g_elem == 8u && (uintptr_t)d_g % 8)
+        return bhwp_fail(BHW_ERR_BADARG, "d_g is not 8-byte aligned: the gains are interleaved float32 pairs (gr, gi), read as 8-byte words");
     if ((uintptr_t)d_g % 4) return bhwp_fail(BHW_ERR_BADARG, "d_g is not 4-byte aligned");
     if ((uintptr_t)d_out % 4) return bhwp_fail(BHW_ERR_BADARG, "d_out is not 4-byte aligned");
     const uint64_t xs = sa->x_stride ? sa->x_stride : sa->samples, os = ss->x_stride ? ss->x_stride : ss->samples;
@@ -3216,7 +3220,7 @@ static int mask_tail_checks(const bhw_stft *sa, const bhw_stft *ss, const void *
     const unsigned __int128 ge = (unsigned __int128)(Bn - 1) * g_batch_stride + gsig;
     if (xe > (1ull << 60) || ge > (1ull << 60) || oe > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "x, g or out extent beyond 2^60 elements");
     const uint64_t xa = (uint64_t)(uintptr_t)d_x, ga = (uint64_t)(uintptr_t)d_g, oa = (uint64_t)(uintptr_t)d_out;
-    const uint64_t xb = (uint64_t)xe * 4u, gb = (uint64_t)ge * 4u, ob = (uint64_t)oe * 4u;
+    const uint64_t xb = (uint64_t)xe * 4u, gb = (uint64_t)ge * g_elem, ob = (uint64_t)oe * 4u;
     if (xa > UINT64_MAX - xb || ga > UINT64_MAX - gb || oa > UINT64_MAX - ob)
         return bhwp_fail(BHW_ERR_BADARG, "x, g or out range wraps the address space");
     // spans read the samples under their halo frames again: the call is not in place
@@ -3225,25 +3229,33 @@ static int mask_tail_checks(const bhw_stft *sa, const bhw_stft *ss, const void *
     return BHW_OK;
 }
 
-int bhwp_mask_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const void *d_x,
-                         const void *d_g, uint64_t g_stride, uint64_t g_batch_stride, const void *d_out, bool pointers)
+// The checks of both gain types of the power-of-two family.  g_elem 4: bhw_mask_fft_f32_*, in the words they had; g_elem 8:
+// bhw_cmask_fft_f32_*, whose refusals are the same sentences about "the fused complex-gain mask" and name bhw_cmask_mfft_f32_* for the
+// mixed-radix lengths it takes.
+static int mask_fft_checks_of(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const void *d_x,
+                              const void *d_g, uint64_t g_stride, uint64_t g_batch_stride, const void *d_out, bool pointers, uint32_t g_elem)
 {
     int rc = bhwp_f32_checks(p, length, flags);
     if (rc) return rc;
+    const char *cg = g_elem == 8u ? "complex-gain " : "";
     // the routes that take what this call does not: named before the parents refuse the same input in their own words
     for (const bhw_stft *s : {sa, ss}) {
         if (!s || s->struct_size != sizeof(bhw_stft)) continue;
         const char *which = s == sa ? "analysis" : "synthesis";
         if (s->channels == 2)
-            return bhwp_fail(BHW_ERR_UNSUPPORTED, "channels 2 (%s descriptor): the fused mask takes real input and gives real output; "
-                             "bhw_stft_cfft_f32_* + bhw_istft_cfft_f32_* take I/Q", which);
+            return bhwp_fail(BHW_ERR_UNSUPPORTED, "channels 2 (%s descriptor): the fused %smask takes real input and gives real output; "
+                             "bhw_stft_cfft_f32_* + bhw_istft_cfft_f32_* take I/Q", which, cg);
         if (s->n_fft == (1ull << kFftMaxLog))
-            return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu (%s descriptor): the fused mask takes a power of two in %u..%u; "
-                             "bhw_stft_fft_f32_* + bhw_istft_fft_f32_* take %llu", (unsigned long long)s->n_fft, which, 1u << kFftMinLog,
+            return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu (%s descriptor): the fused %smask takes a power of two in %u..%u; "
+                             "bhw_stft_fft_f32_* + bhw_istft_fft_f32_* take %llu", (unsigned long long)s->n_fft, which, cg, 1u << kFftMinLog,
                              1u << kMaskFftMaxLog, (unsigned long long)s->n_fft);
+        if (g_elem == 8u && (s->n_fft & (s->n_fft - 1)) && s->n_fft <= kMaskMfftMaxN && bhwp_mfft_supported(s->n_fft))
+            return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu (%s descriptor): the fused %smask takes a power of two in %u..%u; "
+                             "bhw_cmask_mfft_f32_* takes the mixed-radix lengths up to %u", (unsigned long long)s->n_fft, which, cg,
+                             1u << kFftMinLog, 1u << kMaskFftMaxLog, kMaskMfftMaxN);
         if ((s->n_fft & (s->n_fft - 1)) && bhwp_mfft_supported(s->n_fft))
-            return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu (%s descriptor): the fused mask takes a power of two in %u..%u; "
-                             "bhw_stft_mfft_f32_* + bhw_istft_mfft_f32_* take the mixed-radix lengths", (unsigned long long)s->n_fft, which,
+            return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu (%s descriptor): the fused %smask takes a power of two in %u..%u; "
+                             "bhw_stft_mfft_f32_* + bhw_istft_mfft_f32_* take the mixed-radix lengths", (unsigned long long)s->n_fft, which, cg,
                              1u << kFftMinLog, 1u << kMaskFftMaxLog);
     }
     // each descriptor by its parent's checks, with packed row strides (no spectrum rows exist here)
@@ -3252,7 +3264,19 @@ int bhwp_mask_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *s
     if (rc) return rc;
     rc = bhwp_istft_fft_checks(p, length, packed_strides(ss, ts), flags, nullptr, nullptr, false);
     if (rc) return rc;
-    return mask_tail_checks(sa, ss, d_x, d_g, g_stride, g_batch_stride, d_out, pointers);
+    return mask_tail_checks(sa, ss, d_x, d_g, g_stride, g_batch_stride, d_out, pointers, g_elem);
+}
+
+int bhwp_mask_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const void *d_x,
+                         const void *d_g, uint64_t g_stride, uint64_t g_batch_stride, const void *d_out, bool pointers)
+{
+    return mask_fft_checks_of(p, length, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out, pointers, 4u);
+}
+
+int bhwp_cmask_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const void *d_x,
+                          const void *d_g, uint64_t g_stride, uint64_t g_batch_stride, const void *d_out, bool pointers)
+{
+    return mask_fft_checks_of(p, length, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out, pointers, 8u);
 }
 
 BhwMaskFftPlan bhwp_mask_fft_plan(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
@@ -3277,14 +3301,15 @@ struct MaskLine {
 };
 template <typename ParentOf>
 static int describe_mask(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
-                         uint64_t g_stride, uint64_t g_batch_stride, const char *family, const char *k_direct, const char *k_table, char *buf,
-                         uint64_t len, ParentOf parent_of)
+                         uint64_t g_stride, uint64_t g_batch_stride, bool pairs, const char *family, const char *k_direct, const char *k_table,
+                         char *buf, uint64_t len, ParentOf parent_of)
 {
+    const char *c = pairs ? "c" : "", *cg = pairs ? "complex " : "";      // "cmask ...", "complex gains: ..." (strides in pairs)
     if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
     const char *route = ct ? "table" : "direct";
     const char *norm = (flags & BHW_OLA_NORMALIZE) ? "normalised by the window envelope" : "not normalised";
     if (!ss->samples) {
-        snprintf(buf, len, "mask %s %s (L = %llu, n_fft %llu), %s: nothing (samples 0)", family, route, (unsigned long long)length,
+        snprintf(buf, len, "%smask %s %s (L = %llu, n_fft %llu), %s: nothing (samples 0)", c, family, route, (unsigned long long)length,
                  (unsigned long long)ss->n_fft, norm);
         return BHW_OK;
     }
@@ -3304,17 +3329,18 @@ static int describe_mask(const bhw_params *p, const BhwCordicCfg *ct, uint64_t l
     while (lds && lds > fields && lds[-1] != ' ') --lds;
     if (!lds) return bhwp_fail(BHW_ERR_BADARG, "buf: the inverse describe line has no plan fields");
     const char *pad = sa->pad_mode == BHW_PAD_REFLECT ? "reflect" : "constant";
-    snprintf(buf, len, "mask %s %s (L = %llu, n_fft %llu, col0 %llu, pad %llu: t0 = %llu; analysis of %llu samples, pad %llu %s), %s: %s, "
-             "forward + inverse FFT, gains: %s, %.*s%u%s", family, route, (unsigned long long)length, (unsigned long long)ss->n_fft,
+    snprintf(buf, len, "%smask %s %s (L = %llu, n_fft %llu, col0 %llu, pad %llu: t0 = %llu; analysis of %llu samples, pad %llu %s), %s: %s, "
+             "forward + inverse FFT, %sgains: %s, %.*s%u%s", c, family, route, (unsigned long long)length, (unsigned long long)ss->n_fft,
              (unsigned long long)ss->col0, (unsigned long long)ss->pad, (unsigned long long)ml.t0, (unsigned long long)sa->samples,
-             (unsigned long long)sa->pad, pad, norm, kern, gains, (int)(lds - fields), fields, ml.lds_bytes, lds_end);
+             (unsigned long long)sa->pad, pad, norm, kern, cg, gains, (int)(lds - fields), fields, ml.lds_bytes, lds_end);
     return BHW_OK;
 }
 
-int bhwp_describe_mask_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *sa, const bhw_stft *ss,
-                           uint32_t flags, uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len)
+static int describe_mask_fft_of(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *sa, const bhw_stft *ss,
+                               uint32_t flags, uint64_t g_stride, uint64_t g_batch_stride, bool pairs, char *buf, uint64_t len)
 {
-    return describe_mask(p, ct, length, sa, ss, flags, g_stride, g_batch_stride, "fft", "k_mask_fft_direct", "k_mask_fft_table", buf, len,
+    return describe_mask(p, ct, length, sa, ss, flags, g_stride, g_batch_stride, pairs, "fft", pairs ? "k_cmask_fft_direct" : "k_mask_fft_direct",
+                         pairs ? "k_cmask_fft_table" : "k_mask_fft_table", buf, len,
                          [&](char *parent, uint64_t size) {
                              const int rc = bhwp_describe_istft_fft(p, ct, length, ss, flags, parent, size);
                              if (rc) return MaskLine{rc, 0, 0};
@@ -3323,32 +3349,48 @@ int bhwp_describe_mask_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t
                          });
 }
 
+int bhwp_describe_mask_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *sa, const bhw_stft *ss,
+                           uint32_t flags, uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len)
+{
+    return describe_mask_fft_of(p, ct, length, sa, ss, flags, g_stride, g_batch_stride, false, buf, len);
+}
+
+int bhwp_describe_cmask_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *sa, const bhw_stft *ss,
+                            uint32_t flags, uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len)
+{
+    return describe_mask_fft_of(p, ct, length, sa, ss, flags, g_stride, g_batch_stride, true, buf, len);
+}
+
 // ---- fused STFT, spectral mask and inverse STFT at mixed-radix n_fft ---------------------------------------------------------------------
 
-int bhwp_mask_mfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const void *d_x,
-                          const void *d_g, uint64_t g_stride, uint64_t g_batch_stride, const void *d_out, bool pointers)
+// The checks of both gain types of the mixed-radix family, as mask_fft_checks_of is the power-of-two one: g_elem 8 names
+// bhw_cmask_fft_f32_* for a power of two.
+static int mask_mfft_checks_of(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const void *d_x,
+                               const void *d_g, uint64_t g_stride, uint64_t g_batch_stride, const void *d_out, bool pointers, uint32_t g_elem)
 {
     int rc = bhwp_f32_checks(p, length, flags);
     if (rc) return rc;
+    const char *cg = g_elem == 8u ? "complex-gain " : "", *pow2_call = g_elem == 8u ? "bhw_cmask_fft_f32_*" : "bhw_mask_fft_f32_*";
     // the routes that take what this call does not: named before the parents refuse the same input in their own words
     for (const bhw_stft *s : {sa, ss}) {
         if (!s || s->struct_size != sizeof(bhw_stft)) continue;
         const char *which = s == sa ? "analysis" : "synthesis";
         const bool pow2 = s->n_fft && !(s->n_fft & (s->n_fft - 1));
         if (s->channels == 2)
-            return bhwp_fail(BHW_ERR_UNSUPPORTED, "channels 2 (%s descriptor): the mixed-radix fused mask takes real input and gives real "
-                             "output; bhw_stft_cmfft_f32_* + bhw_istft_cmfft_f32_* take I/Q", which);
+            return bhwp_fail(BHW_ERR_UNSUPPORTED, "channels 2 (%s descriptor): the mixed-radix fused %smask takes real input and gives real "
+                             "output; bhw_stft_cmfft_f32_* + bhw_istft_cmfft_f32_* take I/Q", which, cg);
         if (pow2 && s->n_fft >= (1ull << kFftMinLog) && s->n_fft <= (1ull << kMaskFftMaxLog))
-            return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu (%s descriptor) is a power of two: bhw_mask_fft_f32_* takes it; the mixed-radix "
-                             "fused mask takes an even 2^a 3^b 5^c in %u..%u", (unsigned long long)s->n_fft, which, kMfftMinN, kMaskMfftMaxN);
+            return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu (%s descriptor) is a power of two: %s takes it; the mixed-radix "
+                             "fused %smask takes an even 2^a 3^b 5^c in %u..%u", (unsigned long long)s->n_fft, which, pow2_call, cg, kMfftMinN,
+                             kMaskMfftMaxN);
         if (s->n_fft == (1ull << kFftMaxLog))
             return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu (%s descriptor) is a power of two: bhw_stft_fft_f32_* + bhw_istft_fft_f32_* "
-                             "take it; the mixed-radix fused mask takes an even 2^a 3^b 5^c in %u..%u", (unsigned long long)s->n_fft, which,
-                             kMfftMinN, kMaskMfftMaxN);
+                             "take it; the mixed-radix fused %smask takes an even 2^a 3^b 5^c in %u..%u", (unsigned long long)s->n_fft, which,
+                             cg, kMfftMinN, kMaskMfftMaxN);
         if (s->n_fft > kMaskMfftMaxN && bhwp_mfft_supported(s->n_fft))
-            return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu (%s descriptor): the mixed-radix fused mask takes an even 2^a 3^b 5^c in "
+            return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu (%s descriptor): the mixed-radix fused %smask takes an even 2^a 3^b 5^c in "
                              "%u..%u; bhw_stft_mfft_f32_* + bhw_istft_mfft_f32_* take the larger ones", (unsigned long long)s->n_fft, which,
-                             kMfftMinN, kMaskMfftMaxN);
+                             cg, kMfftMinN, kMaskMfftMaxN);
     }
     // each descriptor by its parent's checks, with packed row strides (no spectrum rows exist here)
     bhw_stft ta, ts;
@@ -3356,7 +3398,19 @@ int bhwp_mask_mfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *
     if (rc) return rc;
     rc = bhwp_istft_mfft_checks(p, length, packed_strides(ss, ts), flags, nullptr, nullptr, false);
     if (rc) return rc;
-    return mask_tail_checks(sa, ss, d_x, d_g, g_stride, g_batch_stride, d_out, pointers);
+    return mask_tail_checks(sa, ss, d_x, d_g, g_stride, g_batch_stride, d_out, pointers, g_elem);
+}
+
+int bhwp_mask_mfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const void *d_x,
+                          const void *d_g, uint64_t g_stride, uint64_t g_batch_stride, const void *d_out, bool pointers)
+{
+    return mask_mfft_checks_of(p, length, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out, pointers, 4u);
+}
+
+int bhwp_cmask_mfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const void *d_x,
+                           const void *d_g, uint64_t g_stride, uint64_t g_batch_stride, const void *d_out, bool pointers)
+{
+    return mask_mfft_checks_of(p, length, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out, pointers, 8u);
 }
 
 BhwMaskMfftPlan bhwp_mask_mfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
@@ -3371,16 +3425,29 @@ BhwMaskMfftPlan bhwp_mask_mfft_plan(const bhw_params *p, uint64_t length, const 
     return pl;
 }
 
-int bhwp_describe_mask_mfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *sa, const bhw_stft *ss,
-                            uint32_t flags, uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len)
+static int describe_mask_mfft_of(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *sa, const bhw_stft *ss,
+                                uint32_t flags, uint64_t g_stride, uint64_t g_batch_stride, bool pairs, char *buf, uint64_t len)
 {
-    return describe_mask(p, ct, length, sa, ss, flags, g_stride, g_batch_stride, "mfft", "k_mask_mfft_direct", "k_mask_mfft_table", buf, len,
+    return describe_mask(p, ct, length, sa, ss, flags, g_stride, g_batch_stride, pairs, "mfft", pairs ? "k_cmask_mfft_direct" : "k_mask_mfft_direct",
+                         pairs ? "k_cmask_mfft_table" : "k_mask_mfft_table", buf, len,
                          [&](char *parent, uint64_t size) {
                              const int rc = bhwp_describe_istft_mfft(p, ct, length, ss, flags, parent, size);
                              if (rc) return MaskLine{rc, 0, 0};
                              const BhwMaskMfftPlan pl = bhwp_mask_mfft_plan(p, length, sa, ss, flags, g_stride, g_batch_stride, ct != nullptr);
                              return MaskLine{0, pl.t0, pl.lds_bytes};
                          });
+}
+
+int bhwp_describe_mask_mfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *sa, const bhw_stft *ss,
+                            uint32_t flags, uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len)
+{
+    return describe_mask_mfft_of(p, ct, length, sa, ss, flags, g_stride, g_batch_stride, false, buf, len);
+}
+
+int bhwp_describe_cmask_mfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *sa, const bhw_stft *ss,
+                             uint32_t flags, uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len)
+{
+    return describe_mask_mfft_of(p, ct, length, sa, ss, flags, g_stride, g_batch_stride, true, buf, len);
 }
 
 // ---- fused inverse mixed-radix FFT, window and overlap-add ----------------------------------------------------------------------------------

@@ -937,7 +937,7 @@ int  bhwk_istft_fft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinC
 constexpr uint32_t kMaskFftMaxLog = 11;               // n_fft <= 2048
 struct BhwMaskFftPlan : BhwIstftFftPlan {             // lds_bytes: 2 * fy * M * 8 + 2 * M * 8 + n_fft * 4  (<= 40 KiB)
     uint64_t in_stride;   // floats between the input signals (0 -> the analysis descriptor's samples)
-    uint64_t g_stride, g_bstride;   // floats between the gain rows of a signal and between the signals' gains, as given (0: one row)
+    uint64_t g_stride, g_bstride;   // gains (floats; pairs for bhw_cmask_*) between the gain rows of a signal and between the signals' gains, as given (0: one row)
 };
 // Every check of the two calls that needs no table handle, before any HIP call and in the order of include/bhw.h: the params, the two
 // descriptors by the checks of bhw_stft_fft_f32_* and bhw_istft_fft_f32_* (in their words), the rules that tie them, the gain strides,
@@ -951,6 +951,16 @@ int  bhwp_describe_mask_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64_
                             uint32_t flags, uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len);
 int  bhwk_mask_fft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwMaskFftPlan &pl, const bhw_stft *sa,
                        const bhw_stft *ss, const float *d_x, const float *d_g, float *d_out, const int32_t *d_table, const BhwLenPhase &lp);
+// The same call with a complex gain per bin (bhw_cmask_fft_f32_*; k_cmask_fft_* in bhw_mask_fft.hip): d_g holds interleaved float32 pairs
+// (gr, gi) and both gain strides count pairs.  The checks are bhwp_mask_fft_checks' with 8-byte gain elements (extents, overlaps, an
+// 8-byte aligned d_g) and refusals that name the complex-gain call of the other family; the plan IS bhwp_mask_fft_plan's, strides in
+// pairs: the gains live in registers, so lanes, spans, columns and LDS do not change.
+int  bhwp_cmask_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const void *d_x,
+                           const void *d_g, uint64_t g_stride, uint64_t g_batch_stride, const void *d_out, bool pointers = true);
+int  bhwp_describe_cmask_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *sa, const bhw_stft *ss,
+                             uint32_t flags, uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len);
+int  bhwk_cmask_fft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwMaskFftPlan &pl, const bhw_stft *sa,
+                        const bhw_stft *ss, const float *d_x, const float *d_g, float *d_out, const int32_t *d_table, const BhwLenPhase &lp);
 
 // ---- fused inverse mixed-radix FFT, window and overlap-add (bhw_istft_mfft_f32_*; bhw_istft_mfft.hip) ---------------------------------
 // The lane layout and the radix schedule of bhwp_stft_mfft_plan (lpf lanes along a row of M = n_fft / 2 complex points, fy slots side
@@ -981,7 +991,7 @@ int  bhwk_istft_mfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWin
 constexpr uint32_t kMaskMfftMaxN = 2047;              // n_fft < 2048
 struct BhwMaskMfftPlan : BhwIstftMfftPlan {           // lds_bytes: 2 * fy * M * 8 + 2 * M * 8 + n_fft * 4  (<= 40 000)
     uint64_t in_stride;   // floats between the input signals (0 -> the analysis descriptor's samples)
-    uint64_t g_stride, g_bstride;   // floats between the gain rows of a signal and between the signals' gains, as given (0: one row)
+    uint64_t g_stride, g_bstride;   // gains (floats; pairs for bhw_cmask_*) between the gain rows of a signal and between the signals' gains, as given (0: one row)
 };
 // Every check of the two calls that needs no table handle, before any HIP call and in the order of include/bhw.h: the params, the
 // refusals that name a route, the two descriptors by the checks of bhw_stft_mfft_f32_* and bhw_istft_mfft_f32_* (in their words), then
@@ -995,6 +1005,14 @@ int  bhwp_describe_mask_mfft(const bhw_params *p, const BhwCordicCfg *ct, uint64
                              uint32_t flags, uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len);
 int  bhwk_mask_mfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwMaskMfftPlan &pl, const bhw_stft *sa,
                         const bhw_stft *ss, const float *d_x, const float *d_g, float *d_out, const int32_t *d_table, const BhwLenPhase &lp);
+// The same call with a complex gain per bin (bhw_cmask_mfft_f32_*; k_cmask_mfft_* in bhw_mask_mfft.hip), as bhwp_cmask_fft_checks and
+// its siblings are the power-of-two one: pairs (gr, gi), strides in pairs, bhwp_mask_mfft_plan as it is.
+int  bhwp_cmask_mfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const void *d_x,
+                            const void *d_g, uint64_t g_stride, uint64_t g_batch_stride, const void *d_out, bool pointers = true);
+int  bhwp_describe_cmask_mfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *sa, const bhw_stft *ss,
+                              uint32_t flags, uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len);
+int  bhwk_cmask_mfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwMaskMfftPlan &pl, const bhw_stft *sa,
+                         const bhw_stft *ss, const float *d_x, const float *d_g, float *d_out, const int32_t *d_table, const BhwLenPhase &lp);
 
 // ---- fused inverse complex FFT, window and overlap-add for I/Q output (bhw_istft_cfft_f32_*; bhw_istft_cfft.hip) ----------------------
 // The lane layout and the passes of bhwp_stft_cfft_plan (lpf lanes along a row of n = n_fft complex points, fy slots side by side,

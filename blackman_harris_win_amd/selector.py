@@ -876,15 +876,18 @@ def _mask_fft_refusals(torch, x, mask, n_fft):
                          f"bhw.istft take it)")
 
 
-def _mask_gains(torch, mask, nb, frames, K, dev):
-    """The gains as the kernel reads them: (the tensor read, g_stride, g_batch_stride).  mask: real float32, (K,), (F, K) or
-    (1 | B, 1 | F, K), its last axis contiguous.  An axis of size 1 or of stride 0 (an expand() view) becomes a zero stride and is never
-    materialised; rows or signals that overlap in memory some other way are copied first."""
-    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.float32 or not mask.is_cuda or mask.device.index != dev:
-        raise ValueError("mask must be a real float32 CUDA tensor on the call's device")
+def _mask_gains(torch, mask, nb, frames, K, dev, complex_gains=False):
+    """The gains as the kernel reads them: (the tensor read, g_stride, g_batch_stride).  mask: real float32 -- complex64 with
+    complex_gains, the strides then counting (re, im) pairs, as torch counts them -- (K,), (F, K) or (1 | B, 1 | F, K), its last axis
+    contiguous.  An axis of size 1 or of stride 0 (an expand() view) becomes a zero stride and is never materialised; rows or signals
+    that overlap in memory some other way are copied first.  A lazy conjugate is resolved first."""
+    want = torch.complex64 if complex_gains else torch.float32
+    if not isinstance(mask, torch.Tensor) or mask.dtype != want or not mask.is_cuda or mask.device.index != dev:
+        raise ValueError("mask must be a complex64 CUDA tensor on the call's device" if complex_gains else
+                         "mask must be a real float32 CUDA tensor on the call's device")
     if mask.dim() not in (1, 2, 3) or mask.shape[-1] != K:
         raise ValueError(f"mask must be (K,), (F, K) or (1 | B, 1 | F, K) with K = n_fft // 2 + 1 = {K}, got {tuple(mask.shape)}")
-    m = mask.resolve_neg()
+    m = mask.resolve_conj().resolve_neg()
     while m.dim() < 3:
         m = m.unsqueeze(0)
     if m.shape[0] not in (1, nb) or m.shape[1] not in (1, frames):
@@ -915,7 +918,8 @@ def stft_mask_istft(params, x, mask, n_fft, hop, *, win_length=None, center=True
     (stft_mixed + istft_mixed), complex x (stft_iq + istft_iq), 4096 (stft + istft).  `out`: a contiguous float32 tensor of the
     returned shape; it may not share memory with x or mask.  `table`: a ResidentTable of these params to gather the window
     coefficients from (bhw_mask_fft_f32_from_table: no allocation by the library, no synchronisation, capturable on its first call),
-    or None (the library form: capturable with no warm call).  stft_mask_istft_mixed() is this call at a mixed-radix n_fft."""
+    or None (the library form: capturable with no warm call).  stft_mask_istft_mixed() is this call at a mixed-radix n_fft, and
+    stft_cmask_istft() this call with a complex gain per bin."""
     torch = _torch()
     _mask_fft_refusals(torch, x, mask, n_fft)
     return _stft_mask_istft(torch, params, x, mask, n_fft, hop, win_length, center, pad_mode, length, normalize, shift, out, table,
@@ -923,9 +927,9 @@ def stft_mask_istft(params, x, mask, n_fft, hop, *, win_length=None, center=True
 
 
 def _stft_mask_istft(torch, params, x, mask, n_fft, hop, win_length, center, pad_mode, length, normalize, shift, out, table, check, device_call,
-                     table_call):
-    """What stft_mask_istft() and stft_mask_istft_mixed() share after their refusals: the input checks (check: _fft_input or
-    _mfft_input), the two descriptors, the gains and the one call."""
+                     table_call, complex_gains=False):
+    """What stft_mask_istft(), stft_mask_istft_mixed() and their complex-gain siblings share after their refusals: the input checks
+    (check: _fft_input or _mfft_input), the two descriptors, the gains (complex_gains: complex64, strides in pairs) and the one call."""
     if table is not None:
         if not isinstance(table, ResidentTable):
             raise ValueError("table must be a ResidentTable or None")
@@ -938,7 +942,7 @@ def _stft_mask_istft(torch, params, x, mask, n_fft, hop, win_length, center, pad
     if not center and L < n_fft:
         raise ValueError("center=False with win_length < n_fft: the first outputs have no window under them")
     K = n_fft // 2 + 1
-    g, gs, gbs = _mask_gains(torch, mask, nb, frames, K, dev)
+    g, gs, gbs = _mask_gains(torch, mask, nb, frames, K, dev, complex_gains)
     length = T if length is None else int(length)
     if length < 0:
         raise ValueError(f"length {length} < 0")
@@ -987,12 +991,85 @@ def stft_mask_istft_mixed(params, x, mask, n_fft, hop, *, win_length=None, cente
     BIT FOR BIT.  ValueError naming the calls that take it: a power of two (stft_mask_istft), an n_fft of 2048 or more (stft_mixed, a
     multiply and istft_mixed), complex x (stft_iq_mixed + istft_iq_mixed), a complex mask (stft_mixed + a complex multiply +
     istft_mixed).  `table`: a ResidentTable of these params (bhw_mask_mfft_f32_from_table: no allocation by the library, no
-    synchronisation, capturable on its first call), or None (the library form: capturable with no warm call)."""
+    synchronisation, capturable on its first call), or None (the library form: capturable with no warm call).
+    stft_cmask_istft_mixed() is this call with a complex gain per bin."""
     import torch as host_torch                            # the refusals look at no device: they come before _torch() asks for one
     _mask_mfft_refusals(host_torch, x, mask, n_fft)
     torch = _torch()
     return _stft_mask_istft(torch, params, x, mask, n_fft, hop, win_length, center, pad_mode, length, normalize, shift, out, table,
                             _mfft_input, "bhw_mask_mfft_f32_device", "bhw_mask_mfft_f32_from_table")
+
+
+# ---- the same with a complex gain per bin ------------------------------------------------------------------------------------------------
+
+def _cmask_refusals(torch, x, mask, n_fft, mixed):
+    """What stft_cmask_istft() (mixed False) and stft_cmask_istft_mixed() (mixed True) do not take, refused naming the calls that do,
+    before any check that needs a device."""
+    what = "the mixed-radix fused complex-gain mask" if mixed else "the fused complex-gain mask"
+    tail = "_mixed" if mixed else ""
+    if isinstance(mask, torch.Tensor) and not mask.is_complex():
+        raise ValueError(f"{what} takes complex64 gains, got {mask.dtype}: bhw.stft_mask_istft{tail} takes real gains")
+    if isinstance(x, torch.Tensor) and x.is_complex():
+        raise ValueError(f"{what} takes real float32 input, got {x.dtype} (I/Q input: bhw.stft_iq{tail}, a complex multiply and "
+                         f"bhw.istft_iq{tail})")
+    n = int(n_fft)
+    if mixed:
+        if B.mask_fft_supported(n):
+            raise ValueError(f"n_fft {n} is a power of two: bhw.stft_cmask_istft takes it (one transform per n_fft)")
+        if B.fft_supported(n):
+            raise ValueError(f"n_fft {n} is a power of two above {B.MASK_FFT_MAX_N}: bhw.stft, a complex multiply and bhw.istft take it")
+        if n > B.MASK_MFFT_MAX_N and B.mfft_supported(n):
+            raise ValueError(f"{what} takes n_fft even 2^a·3^b·5^c in {B.MFFT_MIN_N}..{B.MASK_MFFT_MAX_N}, got {n} (bhw.stft_mixed, a "
+                             f"complex multiply and bhw.istft_mixed take it)")
+    else:
+        if B.mask_mfft_supported(n):
+            raise ValueError(f"{what} takes n_fft a power of two in {B.FFT_MIN_N}..{B.MASK_FFT_MAX_N}, got {n} (a mixed-radix n_fft: "
+                             f"bhw.stft_cmask_istft_mixed takes it)")
+        if n > 0 and n & (n - 1) and B.mfft_supported(n):
+            raise ValueError(f"{what} takes n_fft a power of two in {B.FFT_MIN_N}..{B.MASK_FFT_MAX_N}, got {n} (bhw.stft_mixed, a complex "
+                             f"multiply and bhw.istft_mixed take it)")
+        if B.fft_supported(n) and not B.mask_fft_supported(n):
+            raise ValueError(f"{what} takes n_fft a power of two in {B.FFT_MIN_N}..{B.MASK_FFT_MAX_N}, got {n} (bhw.stft, a complex multiply "
+                             f"and bhw.istft take it)")
+
+
+def stft_cmask_istft(params, x, mask, n_fft, hop, *, win_length=None, center=True, pad_mode="reflect", length=None, normalize=True,
+                     shift=None, out=None, table=None):
+    """stft_mask_istft() with a COMPLEX gain per bin in ONE launch (bhw_cmask_fft_f32_device): a complex ratio mask, a frequency
+    response H[k] as one (K,) row, a fractional delay exp(-2πi·k·d/n_fft), a beamforming weight per bin.  x (T,) or (B, T), float32;
+    mask complex64 with the layouts of stft_mask_istft(): (K,), (F, K) or (1 | B, 1 | F, K), K = n_fft // 2 + 1, the last axis
+    contiguous; an axis of size 1 or stride 0 (an expand() view) is never materialised, a conjugate view is resolved first.  With
+    Y = bhw.stft(params, x, n_fft, hop, ...) and G = mask, the masked spectrum is, in separate float32 operations,
+
+        Z.real = Y.real * G.real - Y.imag * G.imag        Z.imag = Y.real * G.imag + Y.imag * G.real
+
+    -- each of the four products rounded on its own -- and the result equals bhw.istft(params, Z, n_fft, hop, ..., length=length,
+    normalize=normalize) BIT FOR BIT.  That is what eager float32 torch operations on the two planes give; it is not promised to
+    equal Y * G of torch complex tensors bit for bit (a library's complex multiply may round differently), only to within that
+    multiply's rounding.  The imaginary parts of the gains at bins 0 and n_fft / 2 multiply stored zeros and are otherwise unused.
+    n_fft: a power of two in 16..2048.  ValueError naming the calls that take it: a real mask (stft_mask_istft), a mixed-radix n_fft
+    (stft_cmask_istft_mixed), complex x (stft_iq + istft_iq), 4096 (stft, a complex multiply and istft).  `out`, `table` and the
+    other keywords are stft_mask_istft()'s (bhw_cmask_fft_f32_from_table)."""
+    import torch as host_torch                            # the refusals look at no device: they come before _torch() asks for one
+    _cmask_refusals(host_torch, x, mask, n_fft, False)
+    torch = _torch()
+    return _stft_mask_istft(torch, params, x, mask, n_fft, hop, win_length, center, pad_mode, length, normalize, shift, out, table,
+                            _fft_input, "bhw_cmask_fft_f32_device", "bhw_cmask_fft_f32_from_table", True)
+
+
+def stft_cmask_istft_mixed(params, x, mask, n_fft, hop, *, win_length=None, center=True, pad_mode="reflect", length=None, normalize=True,
+                           shift=None, out=None, table=None):
+    """stft_cmask_istft() at the n_fft of stft_mixed() in ONE launch (bhw_cmask_mfft_f32_device): n_fft even, 2^a·3^b·5^c, no power of
+    two, from 18 to 2000 -- 320, 400, 480, 960, 1000, 1200, 1920.  The arguments, the complex64 mask layouts, the four-product formula
+    and the statement about torch's complex multiply are stft_cmask_istft()'s, with stft_mixed() and istft_mixed() as the two
+    transforms: the result equals istft_mixed() of the masked stft_mixed() rows BIT FOR BIT.  ValueError naming the calls that take
+    it: a real mask (stft_mask_istft_mixed), a power of two (stft_cmask_istft), an n_fft of 2048 or more (stft_mixed, a complex
+    multiply and istft_mixed), complex x (stft_iq_mixed + istft_iq_mixed).  `table`: bhw_cmask_mfft_f32_from_table."""
+    import torch as host_torch
+    _cmask_refusals(host_torch, x, mask, n_fft, True)
+    torch = _torch()
+    return _stft_mask_istft(torch, params, x, mask, n_fft, hop, win_length, center, pad_mode, length, normalize, shift, out, table,
+                            _mfft_input, "bhw_cmask_mfft_f32_device", "bhw_cmask_mfft_f32_from_table", True)
 
 
 def fbank_bands(weights):

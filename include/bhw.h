@@ -1566,8 +1566,8 @@ int bhw_describe_csd_fft(bhw_table t, const bhw_params *p, uint64_t length, cons
  *     and (from a table) the key match.
  *   - No workspace, no allocation, no float atomics.  The library form computes the coefficients by direct CORDIC and both twiddle
  *     tables in the kernel: capturable with no bhw_prepare_device.  The from-table form is capturable on its first call.
- *   - Not built: complex gains; I/Q input; 4096; a gain computed in the kernel; a second output with the masked spectrum.  (A
- *     mixed-radix n_fft from 18 to 2000 has calls of its own: bhw_mask_mfft_f32_* below.)
+ *   - Not built: complex gains (bhw_cmask_fft_f32_* below take them); I/Q input; 4096; a gain computed in the kernel; a second output
+ *     with the masked spectrum.  (A mixed-radix n_fft from 18 to 2000 has calls of its own: bhw_mask_mfft_f32_* below.)
  *   - bhw_describe_mask_fft: the plan fields of bhw_describe_istft_fft's line for ss in the same words (the plan IS that call's, but
  *     for the LDS bytes), with the kernel, "forward + inverse FFT", the analysis padding and the gain strides.  It takes the gain
  *     strides because its line and its checks need them.  t may be NULL (the library call).  Host arithmetic only. */
@@ -1597,7 +1597,8 @@ int bhw_describe_mask_fft(bhw_table t, const bhw_params *p, uint64_t length, con
  *     everything bhw_stft_mfft_f32_* checks on sa and everything bhw_istft_mfft_f32_* checks on ss, both with packed row strides and
  *     in those calls' own words; then what bhw_mask_fft_f32_* checks after its parents, in its words and its order.
  *   - No workspace, no allocation, no float atomics; both forms are capturable as bhw_mask_fft_f32_*'s are.
- *   - Not built: complex gains; I/Q input; n_fft >= 2048; a gain computed in the kernel; a second output with the masked spectrum.
+ *   - Not built: complex gains (bhw_cmask_mfft_f32_* below take them); I/Q input; n_fft >= 2048; a gain computed in the kernel; a second
+ *     output with the masked spectrum.
  *   - bhw_describe_mask_mfft: the plan fields of bhw_describe_istft_mfft's line for ss in the same words (the plan IS that call's, but
  *     for the LDS bytes), with the kernel, "forward + inverse FFT", the analysis padding and the gain strides. */
 int bhw_mask_mfft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *sa, const bhw_stft *ss,
@@ -1607,6 +1608,51 @@ int bhw_mask_mfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t leng
                                  float *d_out);
 int bhw_describe_mask_mfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
                            uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len);
+
+/* Fused STFT, COMPLEX spectral gain and inverse STFT: bhw_mask_fft_f32_* and bhw_mask_mfft_f32_* with a complex gain per bin -- a
+ * complex ratio mask (phase as well as magnitude), a frequency response H[k] as one (K,) row, a fractional delay
+ * exp(-2 pi i k d / n_fft), one channel's beamforming weight per bin.  Still ONE launch and no spectrum in memory.  The arguments are
+ * those of the real-gain calls of the same family, word for word, with one difference:
+ *   - d_g points to interleaved float32 pairs (gr, gi), and g_stride / g_batch_stride count PAIRS.  The gain of bin k < K =
+ *     n_fft / 2 + 1 of frame f of signal b is the pair at d_g + 2 * (b * g_batch_stride + f * g_stride + k).  Either stride may be 0; a
+ *     nonzero g_stride is at least K, a nonzero g_batch_stride at least (frames - 1) * g_stride + K.  Pairs between the rows are never
+ *     read.  d_g must be 8-byte aligned (a message of its own), and its extent, the 2^60 bound, the wrap and the overlap with d_out
+ *     are computed in 8-byte elements.
+ *   - The rows.  Y[b, f, k] = (re, im) is the float32 pair bhw_stft_fft_f32_* (bhw_stft_mfft_f32_*) writes for (sa, d_x, flags 0).
+ *     The masked bin is
+ *         re' = fl32( fl32(re * gr) - fl32(im * gi) )
+ *         im' = fl32( fl32(re * gi) + fl32(im * gr) )
+ *     -- each of the four products rounded on its own, none fused into the subtraction or the addition.  d_out is exactly what
+ *     bhw_istft_fft_f32_* (bhw_istft_mfft_f32_*) writes for (ss, flags) from those masked rows: WORD FOR WORD, with no tolerance.
+ *     This is what separate float32 operations on the real and imaginary planes give; it is NOT promised to equal a library's complex
+ *     multiply Y * G bit for bit (such a multiply may fuse a product into the sum), only to within that multiply's rounding.
+ *   - Bins 0 and n_fft / 2: the forward parents store im = 0 there and the inverse parents read only the real parts, so gi enters
+ *     through re' = fl32(re * gr) - fl32(0 * gi) alone: a finite gi changes nothing, a NaN or an infinity there is one in the row.
+ *   - The descriptors, ss->samples 0 -> BHW_OK, the determinism and IEEE statements (a non-finite part of a gain pair counts as a
+ *     non-finite gain), the rule that d_out overlaps neither d_x nor d_g, capture, workspace (none) and the order of the checks are
+ *     the real-gain calls'.
+ *   - Supported: what the real-gain call of the family takes -- bhw_cmask_fft_f32_*: a power of two in 16..2048;
+ *     bhw_cmask_mfft_f32_*: even 2^a 3^b 5^c in 18..2000, no power of two (73 sizes).  BHW_ERR_UNSUPPORTED in the real-gain calls'
+ *     sentences, about "the fused complex-gain mask": channels 2 names the I/Q transforms, 4096 and the mixed-radix lengths above 2047
+ *     the pairs of transforms, and the other family's sizes name bhw_cmask_mfft_f32_* / bhw_cmask_fft_f32_*.
+ *   - Not built: I/Q input; n_fft >= 2048 (mixed) / 4096; a gain computed in the kernel; a second output with the masked spectrum.
+ *   - bhw_describe_cmask_fft / _mfft: bhw_describe_mask_fft's / _mfft's line -- the plan IS that call's for the same arguments: lanes,
+ *     spans, columns per lane and LDS bytes; the gains live in registers -- beginning "cmask", naming k_cmask_*_direct / _table and
+ *     saying "complex gains" before the strides (in pairs). */
+int bhw_cmask_fft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *sa, const bhw_stft *ss,
+                             uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride, float *d_out);
+int bhw_cmask_fft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *sa, const bhw_stft *ss,
+                                 uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride,
+                                 float *d_out);
+int bhw_describe_cmask_fft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
+                           uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len);
+int bhw_cmask_mfft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *sa, const bhw_stft *ss,
+                              uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride, float *d_out);
+int bhw_cmask_mfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *sa, const bhw_stft *ss,
+                                  uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride,
+                                  float *d_out);
+int bhw_describe_cmask_mfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
+                            uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len);
 
 /* Threading: every entry point may be called from any host thread.  Calls that use the library-owned scratch of one
  * (device, stream) are serialised against each other for the duration of their launches (the table is rebuilt per call);
