@@ -63,8 +63,8 @@ def _write_stamp(target, digest):
         f.write(digest + "\n")
 
 
-KERNEL_UNITS = ("bhw_direct.hip", "bhw_build.hip", "bhw_combine.hip", "bhw_range.hip", "bhw_frames.hip", "bhw_ola.hip", "bhw_frames_f32.hip", "bhw_ola_f32.hip", "bhw_ola_f32_norm.hip", "bhw_stft_f32.hip", "bhw_stft_fft.hip", "bhw_spectrogram.hip", "bhw_welch_fft.hip", "bhw_csd_fft.hip", "bhw_welch_cfft.hip", "bhw_welch_mfft.hip", "bhw_welch_cmfft.hip", "bhw_hold_cfft.hip", "bhw_hold_cmfft.hip", "bhw_hold_fft.hip", "bhw_hold_mfft.hip", "bhw_stft_mfft.hip", "bhw_logspec.hip", "bhw_logspec_mfft.hip", "bhw_stft_cfft.hip", "bhw_stft_cmfft.hip", "bhw_istft_fft.hip", "bhw_mask_fft.hip", "bhw_istft_mfft.hip", "bhw_mask_mfft.hip", "bhw_istft_cfft.hip", "bhw_istft_cmfft.hip", "bhw_welch_f32.hip", "bhw_welch_sums.hip", "bhw_welch_csd.hip", "bhw_tile9.hip", "bhw_fused.hip", "bhw_taylor.hip", "bhw_variants.hip", "bhw_len.hip")
-HEADERS = ("bhw_internal.h", "bhw_plan.h", "bhw_len.h", "bhw_device.h", "bhw_frames.h", "bhw_ola.h", "bhw_ola_f32.h", "bhw_stft.h", "bhw_stft_fft.h", "bhw_csd_out.h", "bhw_stft_cfft.h", "bhw_stft_mfft.h", "bhw_logspec.h", "bhw_stft_cmfft.h", "bhw_istft.h", "bhw_istft_fft.h", "bhw_istft_mfft.h", "bhw_hold.h", "bhw_hold_real.h", "bhw_welch.h", "bhw_tables.inc")
+KERNEL_UNITS = ("bhw_direct.hip", "bhw_build.hip", "bhw_combine.hip", "bhw_range.hip", "bhw_frames.hip", "bhw_ola.hip", "bhw_frames_f32.hip", "bhw_ola_f32.hip", "bhw_ola_f32_norm.hip", "bhw_stft_f32.hip", "bhw_stft_fft.hip", "bhw_spectrogram.hip", "bhw_welch_fft.hip", "bhw_csd_fft.hip", "bhw_welch_cfft.hip", "bhw_welch_mfft.hip", "bhw_welch_cmfft.hip", "bhw_hold_cfft.hip", "bhw_hold_cmfft.hip", "bhw_hold_fft.hip", "bhw_hold_mfft.hip", "bhw_stft_mfft.hip", "bhw_logspec.hip", "bhw_logspec_mfft.hip", "bhw_stft_cfft.hip", "bhw_stft_cmfft.hip", "bhw_istft_fft.hip", "bhw_mask_fft.hip", "bhw_istft_mfft.hip", "bhw_mask_mfft.hip", "bhw_istft_cfft.hip", "bhw_istft_cmfft.hip", "bhw_mask_cfft.hip", "bhw_mask_cmfft.hip", "bhw_welch_f32.hip", "bhw_welch_sums.hip", "bhw_welch_csd.hip", "bhw_tile9.hip", "bhw_fused.hip", "bhw_taylor.hip", "bhw_variants.hip", "bhw_len.hip")
+HEADERS = ("bhw_internal.h", "bhw_plan.h", "bhw_len.h", "bhw_device.h", "bhw_frames.h", "bhw_ola.h", "bhw_ola_f32.h", "bhw_stft.h", "bhw_stft_fft.h", "bhw_csd_out.h", "bhw_stft_cfft.h", "bhw_stft_mfft.h", "bhw_logspec.h", "bhw_stft_cmfft.h", "bhw_istft.h", "bhw_istft_fft.h", "bhw_istft_mfft.h", "bhw_istft_cfft.h", "bhw_istft_cmfft.h", "bhw_hold.h", "bhw_hold_real.h", "bhw_welch.h", "bhw_tables.inc")
 
 
 def library_sources():

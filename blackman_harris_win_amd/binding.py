@@ -68,6 +68,10 @@ ABI_SYMBOLS = (
     "bhw_mask_mfft_f32_device", "bhw_mask_mfft_f32_from_table", "bhw_describe_mask_mfft",
     "bhw_cmask_fft_f32_device", "bhw_cmask_fft_f32_from_table", "bhw_describe_cmask_fft",
     "bhw_cmask_mfft_f32_device", "bhw_cmask_mfft_f32_from_table", "bhw_describe_cmask_mfft",
+    "bhw_mask_cfft_f32_device", "bhw_mask_cfft_f32_from_table", "bhw_describe_mask_cfft",
+    "bhw_cmask_cfft_f32_device", "bhw_cmask_cfft_f32_from_table", "bhw_describe_cmask_cfft",
+    "bhw_mask_cmfft_f32_device", "bhw_mask_cmfft_f32_from_table", "bhw_describe_mask_cmfft",
+    "bhw_cmask_cmfft_f32_device", "bhw_cmask_cmfft_f32_from_table", "bhw_describe_cmask_cmfft",
 )
 
 
@@ -363,6 +367,10 @@ def lib():
         getattr(L, f"bhw_cmask_{fam}_f32_device").argtypes = [P, u64, ci, vp, S, S, u32, f32p, f32p, u64, u64, f32p]
         getattr(L, f"bhw_cmask_{fam}_f32_from_table").argtypes = [T, P, u64, vp, S, S, u32, f32p, f32p, u64, u64, f32p]
         getattr(L, f"bhw_describe_cmask_{fam}").argtypes = [T, P, u64, S, S, u32, u64, u64, ctypes.c_char_p, u64]
+    for name in ("mask_cfft", "cmask_cfft", "mask_cmfft", "cmask_cmfft"):          # the same twelve for I/Q input
+        getattr(L, f"bhw_{name}_f32_device").argtypes = [P, u64, ci, vp, S, S, u32, f32p, f32p, u64, u64, f32p]
+        getattr(L, f"bhw_{name}_f32_from_table").argtypes = [T, P, u64, vp, S, S, u32, f32p, f32p, u64, u64, f32p]
+        getattr(L, f"bhw_describe_{name}").argtypes = [T, P, u64, S, S, u32, u64, u64, ctypes.c_char_p, u64]
     FB = ctypes.POINTER(BhwFbank)
     L.bhw_spectrogram_f32_device.argtypes = [P, u64, ci, vp, S, u32, FB, f32p, f32p]
     L.bhw_spectrogram_f32_from_table.argtypes = [T, P, u64, vp, S, u32, FB, f32p, f32p]
@@ -626,6 +634,36 @@ def describe_cmask_mfft(params, length, analysis, synthesis, *, normalize=False,
     check(lib().bhw_describe_cmask_mfft(table, ctypes.byref(params), int(length), ctypes.byref(analysis), ctypes.byref(synthesis),
                                         OLA_NORMALIZE if normalize else 0, int(g_stride), int(g_batch_stride), buf, len(buf)))
     return buf.value.decode()
+
+
+def _describe_mask_iq(name, params, length, analysis, synthesis, normalize, fftshift, g_stride, g_batch_stride, table):
+    buf = ctypes.create_string_buffer(1280)
+    flags = (OLA_NORMALIZE if normalize else 0) | (CFFT_SHIFT if fftshift else 0)
+    check(getattr(lib(), "bhw_describe_" + name)(table, ctypes.byref(params), int(length), ctypes.byref(analysis), ctypes.byref(synthesis),
+                                                 flags, int(g_stride), int(g_batch_stride), buf, len(buf)))
+    return buf.value.decode()
+
+
+def describe_mask_cfft(params, length, analysis, synthesis, *, normalize=False, fftshift=False, g_stride=0, g_batch_stride=0, table=None):
+    """One line: the route, the kernel and the plan of a fused STFT + gain + inverse STFT call for I/Q input (bhw_describe_mask_cfft):
+    the plan fields of describe_istft_cfft for `synthesis` in the same words (only the LDS bytes differ), with the kernel name,
+    "forward + inverse FFT", the analysis padding, the gain strides and whether the gain columns are shifted.  Host arithmetic only."""
+    return _describe_mask_iq("mask_cfft", params, length, analysis, synthesis, normalize, fftshift, g_stride, g_batch_stride, table)
+
+
+def describe_cmask_cfft(params, length, analysis, synthesis, *, normalize=False, fftshift=False, g_stride=0, g_batch_stride=0, table=None):
+    """describe_mask_cfft() for the complex-gain call (bhw_describe_cmask_cfft): "cmask", k_cmask_cfft_*, "complex gains", strides in pairs."""
+    return _describe_mask_iq("cmask_cfft", params, length, analysis, synthesis, normalize, fftshift, g_stride, g_batch_stride, table)
+
+
+def describe_mask_cmfft(params, length, analysis, synthesis, *, normalize=False, fftshift=False, g_stride=0, g_batch_stride=0, table=None):
+    """describe_mask_cfft() for a mixed-radix n_fft (bhw_describe_mask_cmfft): the plan fields of describe_istft_cmfft, LDS bytes included."""
+    return _describe_mask_iq("mask_cmfft", params, length, analysis, synthesis, normalize, fftshift, g_stride, g_batch_stride, table)
+
+
+def describe_cmask_cmfft(params, length, analysis, synthesis, *, normalize=False, fftshift=False, g_stride=0, g_batch_stride=0, table=None):
+    """describe_mask_cmfft() for the complex-gain call (bhw_describe_cmask_cmfft)."""
+    return _describe_mask_iq("cmask_cmfft", params, length, analysis, synthesis, normalize, fftshift, g_stride, g_batch_stride, table)
 
 
 def describe_spectrogram(params, length, stft, *, detrend=False, fbank=None, table=None):

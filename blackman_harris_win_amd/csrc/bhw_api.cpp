@@ -1445,6 +1445,35 @@ int cmask_mfft_run(bhw_table t, const bhw_params *p, uint64_t length, int device
         "cmask mfft launch", "cmask mfft launch (resident table)", t, p, length, device, stream, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out);
 }
 
+// The same for I/Q input (d_x, d_out: interleaved I/Q; K = n_fft gains a row), a real gain or a pair per bin
+int mask_cfft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *sa, const bhw_stft *ss,
+                  uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride, float *d_out)
+{
+    return mask_run<bhwp_mask_cfft_checks, bhwp_mask_cfft_plan, bhwk_mask_cfft_f32>(
+        "mask cfft launch", "mask cfft launch (resident table)", t, p, length, device, stream, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out);
+}
+
+int cmask_cfft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *sa, const bhw_stft *ss,
+                   uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride, float *d_out)
+{
+    return mask_run<bhwp_cmask_cfft_checks, bhwp_mask_cfft_plan, bhwk_cmask_cfft_f32>(
+        "cmask cfft launch", "cmask cfft launch (resident table)", t, p, length, device, stream, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out);
+}
+
+int mask_cmfft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *sa, const bhw_stft *ss,
+                   uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride, float *d_out)
+{
+    return mask_run<bhwp_mask_cmfft_checks, bhwp_mask_cmfft_plan, bhwk_mask_cmfft_f32>(
+        "mask cmfft launch", "mask cmfft launch (resident table)", t, p, length, device, stream, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out);
+}
+
+int cmask_cmfft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *sa, const bhw_stft *ss,
+                    uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride, float *d_out)
+{
+    return mask_run<bhwp_cmask_cmfft_checks, bhwp_mask_cmfft_plan, bhwk_cmask_cmfft_f32>(
+        "cmask cmfft launch", "cmask cmfft launch (resident table)", t, p, length, device, stream, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out);
+}
+
 // The window sums (t NULL: the direct CORDIC chains): the checks, then the memset of the four words and the reduction.
 int window_sums_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, uint32_t flags, uint64_t *d_sums)
 {
@@ -2150,6 +2179,37 @@ int bhw_describe_cmask_mfft(bhw_table t, const bhw_params *p, uint64_t length, c
     if (!rc && t) rc = table_call_checks(t, p);
     return rc ? rc : bhwp_describe_cmask_mfft(p, t ? &t->c : nullptr, length, sa, ss, flags, g_stride, g_batch_stride, buf, len);
 }
+
+// ---- fused STFT, real or complex gain per bin and inverse STFT for I/Q input (include/bhw.h: bhw_mask_cfft_f32_device ...) -------------
+// The three entry points of each of the four calls, in the shape of the ones above: NAME in {mask_cfft, cmask_cfft, mask_cmfft,
+// cmask_cmfft}.
+#define BHW_MASK_IQ_ENTRIES(NAME)                                                                                                               \
+    int bhw_##NAME##_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *sa, const bhw_stft *ss,      \
+                                uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride, float *d_out)    \
+    {                                                                                                                                           \
+        return NAME##_run(nullptr, p, length, device, hip_stream, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out);                    \
+    }                                                                                                                                           \
+    int bhw_##NAME##_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *sa,                     \
+                                    const bhw_stft *ss, uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride,                   \
+                                    uint64_t g_batch_stride, float *d_out)                                                                       \
+    {                                                                                                                                           \
+        const int rc = bhwp_##NAME##_checks(p, length, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out);                               \
+        if (rc) return rc;                                                                                                                      \
+        return t ? NAME##_run(t, p, length, t->device, hip_stream, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out)                    \
+                 : fail(BHW_ERR_BADARG, "table is NULL");                                                                                       \
+    }                                                                                                                                           \
+    int bhw_describe_##NAME(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,           \
+                            uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len)                                                 \
+    {                                                                                                                                           \
+        int rc = bhwp_##NAME##_checks(p, length, sa, ss, flags, nullptr, nullptr, g_stride, g_batch_stride, nullptr, false);                    \
+        if (!rc && t) rc = table_call_checks(t, p);                                                                                             \
+        return rc ? rc : bhwp_describe_##NAME(p, t ? &t->c : nullptr, length, sa, ss, flags, g_stride, g_batch_stride, buf, len);                \
+    }
+BHW_MASK_IQ_ENTRIES(mask_cfft)
+BHW_MASK_IQ_ENTRIES(cmask_cfft)
+BHW_MASK_IQ_ENTRIES(mask_cmfft)
+BHW_MASK_IQ_ENTRIES(cmask_cmfft)
+#undef BHW_MASK_IQ_ENTRIES
 
 // ---- fused log spectrogram, log-mel and MFCC (include/bhw.h: bhw_logspec_f32_device ..., bhw_logspec_mfft_f32_device ...) -------------
 

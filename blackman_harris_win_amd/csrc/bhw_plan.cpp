@@ -3181,9 +3181,10 @@ static int mask_fft_agree(const char *field, uint64_t a, uint64_t s)
 
 // What both fused masks check once each descriptor has passed its parent's checks: nonzero y strides, the seven fields that must agree,
 // the gain strides, the pointers, their alignment, the extents, the wrap and the overlaps.  g_elem: the bytes of a gain, 4 (a float) or
-// 8 (an interleaved float32 pair (gr, gi)); the gain strides and the gain extent count such elements.
+// 8 (an interleaved float32 pair (gr, gi)); the gain strides and the gain extent count such elements.  xf: the floats of a sample of d_x
+// and d_out, 1 or 2 (interleaved I/Q: K = n_fft gains a row, and the extents and overlaps of d_x and d_out count two floats a sample).
 static int mask_tail_checks(const bhw_stft *sa, const bhw_stft *ss, const void *d_x, const void *d_g, uint64_t g_stride, uint64_t g_batch_stride,
-                            const void *d_out, bool pointers, uint32_t g_elem)
+                            const void *d_out, bool pointers, uint32_t g_elem, uint64_t xf = 1)
 {
     const char *unit = g_elem == 8u ? "pairs" : "floats";
     int rc;
@@ -3199,7 +3200,7 @@ static int mask_tail_checks(const bhw_stft *sa, const bhw_stft *ss, const void *
     if ((rc = mask_fft_agree("channels", sa->channels, ss->channels))) return rc;
     if (!ss->samples) return BHW_OK;
     // (samples > 0: the inverse checks have refused frames 0, and with frames > 0 the forward ones samples 0 of the analysis side)
-    const uint64_t K = ss->n_fft / 2 + 1, F = ss->frames, Bn = ss->batch;
+    const uint64_t K = xf == 2 ? ss->n_fft : ss->n_fft / 2 + 1, F = ss->frames, Bn = ss->batch;
     if (g_stride && g_stride < K)
         return bhwp_fail(BHW_ERR_BADARG, "g_stride %llu: 0 (one gain row for every frame) or at least K = %llu %s", (unsigned long long)g_stride,
                          (unsigned long long)K, unit);
@@ -3215,8 +3216,8 @@ static int mask_tail_checks(const bhw_stft *sa, const bhw_stft *ss, const void *
         return bhwp_fail(BHW_ERR_BADARG, "d_g is not 8-byte aligned: the gains are interleaved float32 pairs (gr, gi), read as 8-byte words");
     if ((uintptr_t)d_g % 4) return bhwp_fail(BHW_ERR_BADARG, "d_g is not 4-byte aligned");
     if ((uintptr_t)d_out % 4) return bhwp_fail(BHW_ERR_BADARG, "d_out is not 4-byte aligned");
-    const uint64_t xs = sa->x_stride ? sa->x_stride : sa->samples, os = ss->x_stride ? ss->x_stride : ss->samples;
-    const unsigned __int128 xe = (unsigned __int128)(Bn - 1) * xs + sa->samples, oe = (unsigned __int128)(Bn - 1) * os + ss->samples;
+    const uint64_t xs = sa->x_stride ? sa->x_stride : xf * sa->samples, os = ss->x_stride ? ss->x_stride : xf * ss->samples;
+    const unsigned __int128 xe = (unsigned __int128)(Bn - 1) * xs + xf * sa->samples, oe = (unsigned __int128)(Bn - 1) * os + xf * ss->samples;
     const unsigned __int128 ge = (unsigned __int128)(Bn - 1) * g_batch_stride + gsig;
     if (xe > (1ull << 60) || ge > (1ull << 60) || oe > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "x, g or out extent beyond 2^60 elements");
     const uint64_t xa = (uint64_t)(uintptr_t)d_x, ga = (uint64_t)(uintptr_t)d_g, oa = (uint64_t)(uintptr_t)d_out;
@@ -3302,7 +3303,7 @@ struct MaskLine {
 template <typename ParentOf>
 static int describe_mask(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
                          uint64_t g_stride, uint64_t g_batch_stride, bool pairs, const char *family, const char *k_direct, const char *k_table,
-                         char *buf, uint64_t len, ParentOf parent_of)
+                         char *buf, uint64_t len, ParentOf parent_of, bool iq = false)
 {
     const char *c = pairs ? "c" : "", *cg = pairs ? "complex " : "";      // "cmask ...", "complex gains: ..." (strides in pairs)
     if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
@@ -3316,12 +3317,16 @@ static int describe_mask(const bhw_params *p, const BhwCordicCfg *ct, uint64_t l
     char parent[1024];
     const MaskLine ml = parent_of(parent, sizeof parent);
     if (ml.rc) return ml.rc;
-    char kern[64], gains[160];
+    char kern[64], gains[200];
     kernel_name(p, ct, k_direct, k_table, false, kern, sizeof kern);
     if (!g_stride && !g_batch_stride) snprintf(gains, sizeof gains, "one gain row for every frame and every signal");
     else if (!g_stride) snprintf(gains, sizeof gains, "one gain row for every frame, g_batch_stride %llu", (unsigned long long)g_batch_stride);
     else if (!g_batch_stride) snprintf(gains, sizeof gains, "g_stride %llu, one set of gain rows for every signal", (unsigned long long)g_stride);
     else snprintf(gains, sizeof gains, "g_stride %llu, g_batch_stride %llu", (unsigned long long)g_stride, (unsigned long long)g_batch_stride);
+    if (iq) {                                                              // the I/Q masks: which bin a gain column holds
+        const size_t at = strlen(gains);
+        snprintf(gains + at, sizeof gains - at, ", gain columns %s", (flags & BHW_CFFT_SHIFT) ? "shifted" : "in order");
+    }
     const char *fields = strstr(parent, " signals x ");
     while (fields && fields > parent && fields[-1] != ' ') --fields;
     const char *lds_end = fields ? strstr(fields, " bytes of LDS") : nullptr;
@@ -3597,6 +3602,166 @@ int bhwp_describe_istft_cmfft(const bhw_params *p, const BhwCordicCfg *ct, uint6
         istft_mfft_schedule(pl, ln);
         return static_cast<const BhwIstftRuns &>(pl);
     });
+}
+
+// ---- fused STFT, real or complex gain per bin and inverse STFT for I/Q input --------------------------------------------------------------
+
+// The checks of the four I/Q masks: one text per family, the gain element size an argument.  The refusals that name a route come before
+// the parents refuse the same input in their own words.
+static int mask_cfft_checks_of(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const void *d_x,
+                               const void *d_g, uint64_t g_stride, uint64_t g_batch_stride, const void *d_out, bool pointers, uint32_t g_elem)
+{
+    int rc = bhwp_f32_checks(p, length, flags & BHW_OLA_NORMALIZE);
+    if (rc) return rc;
+    const char *cg = g_elem == 8u ? "complex-gain " : "", *c = g_elem == 8u ? "c" : "";
+    for (const bhw_stft *s : {sa, ss}) {
+        if (!s || s->struct_size != sizeof(bhw_stft)) continue;
+        const char *which = s == sa ? "analysis" : "synthesis";
+        if (s->channels == 1)
+            return bhwp_fail(BHW_ERR_UNSUPPORTED, "channels 1 (%s descriptor): the fused I/Q %smask takes interleaved I/Q input and gives "
+                             "I/Q output (2); bhw_%smask_fft_f32_* takes a real signal", which, cg, c);
+        if (bhwp_cmfft_supported(s->n_fft))
+            return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu (%s descriptor): the fused I/Q %smask takes a power of two in %u..%u; "
+                             "bhw_%smask_cmfft_f32_* takes the mixed-radix lengths up to %u", (unsigned long long)s->n_fft, which, cg,
+                             1u << kCfftMinLog, 1u << kCfftMaxLog, c, kCmfftMaxN);
+        if (s->n_fft == (2ull << kCfftMaxLog))
+            return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu (%s descriptor): the fused I/Q %smask takes a power of two in %u..%u, the range of "
+                             "bhw_stft_cfft_f32_* + bhw_istft_cfft_f32_*", (unsigned long long)s->n_fft, which, cg, 1u << kCfftMinLog,
+                             1u << kCfftMaxLog);
+    }
+    // each descriptor by its parent's checks, with packed row strides (no spectrum rows exist here); the analysis side takes no flag
+    bhw_stft ta, ts;
+    rc = bhwp_stft_cfft_checks(p, length, packed_strides(sa, ta), 0, nullptr, nullptr, false);
+    if (rc) return rc;
+    rc = bhwp_istft_cfft_checks(p, length, packed_strides(ss, ts), flags, nullptr, nullptr, false);
+    if (rc) return rc;
+    return mask_tail_checks(sa, ss, d_x, d_g, g_stride, g_batch_stride, d_out, pointers, g_elem, 2);
+}
+
+static int mask_cmfft_checks_of(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const void *d_x,
+                                const void *d_g, uint64_t g_stride, uint64_t g_batch_stride, const void *d_out, bool pointers, uint32_t g_elem)
+{
+    int rc = bhwp_f32_checks(p, length, flags & BHW_OLA_NORMALIZE);
+    if (rc) return rc;
+    const char *cg = g_elem == 8u ? "complex-gain " : "", *c = g_elem == 8u ? "c" : "";
+    for (const bhw_stft *s : {sa, ss}) {
+        if (!s || s->struct_size != sizeof(bhw_stft)) continue;
+        const char *which = s == sa ? "analysis" : "synthesis";
+        const bool pow2 = s->n_fft && !(s->n_fft & (s->n_fft - 1));
+        if (s->channels == 1)
+            return bhwp_fail(BHW_ERR_UNSUPPORTED, "channels 1 (%s descriptor): the mixed-radix fused I/Q %smask takes interleaved I/Q input "
+                             "and gives I/Q output (2); bhw_%smask_mfft_f32_* takes a real signal", which, cg, c);
+        if (pow2 && s->n_fft >= (1ull << kCfftMinLog) && s->n_fft <= (1ull << kCfftMaxLog))
+            return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu (%s descriptor) is a power of two: bhw_%smask_cfft_f32_* takes it; the mixed-radix "
+                             "fused I/Q %smask takes 2^a 3^b 5^c in %u..%u", (unsigned long long)s->n_fft, which, c, cg, kCmfftMinN, kCmfftMaxN);
+        if (s->n_fft > kCmfftMaxN && s->n_fft <= 2u * kCmfftMaxN + 2u && (pow2 || bhwp_mfft_supported(s->n_fft)))
+            return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu (%s descriptor): the mixed-radix fused I/Q %smask takes 2^a 3^b 5^c in %u..%u, "
+                             "the range of bhw_stft_cmfft_f32_* + bhw_istft_cmfft_f32_*", (unsigned long long)s->n_fft, which, cg, kCmfftMinN,
+                             kCmfftMaxN);
+    }
+    bhw_stft ta, ts;
+    rc = bhwp_stft_cmfft_checks(p, length, packed_strides(sa, ta), 0, nullptr, nullptr, false);
+    if (rc) return rc;
+    rc = bhwp_istft_cmfft_checks(p, length, packed_strides(ss, ts), flags, nullptr, nullptr, false);
+    if (rc) return rc;
+    return mask_tail_checks(sa, ss, d_x, d_g, g_stride, g_batch_stride, d_out, pointers, g_elem, 2);
+}
+
+int bhwp_mask_cfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const void *d_x,
+                          const void *d_g, uint64_t g_stride, uint64_t g_batch_stride, const void *d_out, bool pointers)
+{
+    return mask_cfft_checks_of(p, length, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out, pointers, 4u);
+}
+
+int bhwp_cmask_cfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const void *d_x,
+                           const void *d_g, uint64_t g_stride, uint64_t g_batch_stride, const void *d_out, bool pointers)
+{
+    return mask_cfft_checks_of(p, length, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out, pointers, 8u);
+}
+
+int bhwp_mask_cmfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const void *d_x,
+                           const void *d_g, uint64_t g_stride, uint64_t g_batch_stride, const void *d_out, bool pointers)
+{
+    return mask_cmfft_checks_of(p, length, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out, pointers, 4u);
+}
+
+int bhwp_cmask_cmfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const void *d_x,
+                            const void *d_g, uint64_t g_stride, uint64_t g_batch_stride, const void *d_out, bool pointers)
+{
+    return mask_cmfft_checks_of(p, length, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out, pointers, 8u);
+}
+
+BhwMaskCfftPlan bhwp_mask_cfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
+                                    uint64_t g_stride, uint64_t g_batch_stride, bool from_table)
+{
+    BhwMaskCfftPlan pl{};
+    static_cast<BhwIstftCfftPlan &>(pl) = bhwp_istft_cfft_plan(p, length, ss, flags, from_table);
+    pl.lds_bytes = 2u * pl.fy * pl.n * 8u + 2u * (pl.n / 2u) * 8u + pl.n * 4u;              // the forward table beside the inverse one
+    pl.in_stride = sa->x_stride ? sa->x_stride : 2 * sa->samples;
+    pl.g_stride = g_stride;
+    pl.g_bstride = g_batch_stride;
+    return pl;
+}
+
+BhwMaskCmfftPlan bhwp_mask_cmfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
+                                      uint64_t g_stride, uint64_t g_batch_stride, bool from_table)
+{
+    BhwMaskCmfftPlan pl{};
+    static_cast<BhwIstftCmfftPlan &>(pl) = bhwp_istft_cmfft_plan(p, length, ss, flags, from_table);   // one table serves both directions
+    pl.in_stride = sa->x_stride ? sa->x_stride : 2 * sa->samples;
+    pl.g_stride = g_stride;
+    pl.g_bstride = g_batch_stride;
+    return pl;
+}
+
+static int describe_mask_cfft_of(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *sa, const bhw_stft *ss,
+                                uint32_t flags, uint64_t g_stride, uint64_t g_batch_stride, bool pairs, char *buf, uint64_t len)
+{
+    return describe_mask(p, ct, length, sa, ss, flags, g_stride, g_batch_stride, pairs, "cfft", pairs ? "k_cmask_cfft_direct" : "k_mask_cfft_direct",
+                         pairs ? "k_cmask_cfft_table" : "k_mask_cfft_table", buf, len,
+                         [&](char *parent, uint64_t size) {
+                             const int rc = bhwp_describe_istft_cfft(p, ct, length, ss, flags, parent, size);
+                             if (rc) return MaskLine{rc, 0, 0};
+                             const BhwMaskCfftPlan pl = bhwp_mask_cfft_plan(p, length, sa, ss, flags, g_stride, g_batch_stride, ct != nullptr);
+                             return MaskLine{0, pl.t0, pl.lds_bytes};
+                         }, true);
+}
+
+static int describe_mask_cmfft_of(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *sa, const bhw_stft *ss,
+                                 uint32_t flags, uint64_t g_stride, uint64_t g_batch_stride, bool pairs, char *buf, uint64_t len)
+{
+    return describe_mask(p, ct, length, sa, ss, flags, g_stride, g_batch_stride, pairs, "cmfft",
+                         pairs ? "k_cmask_cmfft_direct" : "k_mask_cmfft_direct", pairs ? "k_cmask_cmfft_table" : "k_mask_cmfft_table", buf, len,
+                         [&](char *parent, uint64_t size) {
+                             const int rc = bhwp_describe_istft_cmfft(p, ct, length, ss, flags, parent, size);
+                             if (rc) return MaskLine{rc, 0, 0};
+                             const BhwMaskCmfftPlan pl = bhwp_mask_cmfft_plan(p, length, sa, ss, flags, g_stride, g_batch_stride, ct != nullptr);
+                             return MaskLine{0, pl.t0, pl.lds_bytes};
+                         }, true);
+}
+
+int bhwp_describe_mask_cfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *sa, const bhw_stft *ss,
+                            uint32_t flags, uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len)
+{
+    return describe_mask_cfft_of(p, ct, length, sa, ss, flags, g_stride, g_batch_stride, false, buf, len);
+}
+
+int bhwp_describe_cmask_cfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *sa, const bhw_stft *ss,
+                             uint32_t flags, uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len)
+{
+    return describe_mask_cfft_of(p, ct, length, sa, ss, flags, g_stride, g_batch_stride, true, buf, len);
+}
+
+int bhwp_describe_mask_cmfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *sa, const bhw_stft *ss,
+                             uint32_t flags, uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len)
+{
+    return describe_mask_cmfft_of(p, ct, length, sa, ss, flags, g_stride, g_batch_stride, false, buf, len);
+}
+
+int bhwp_describe_cmask_cmfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *sa, const bhw_stft *ss,
+                              uint32_t flags, uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len)
+{
+    return describe_mask_cmfft_of(p, ct, length, sa, ss, flags, g_stride, g_batch_stride, true, buf, len);
 }
 
 // ---- the pure entry points of the C ABI (include/bhw.h) -------------------------------------------------------------------------------

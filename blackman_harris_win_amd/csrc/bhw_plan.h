@@ -1062,6 +1062,55 @@ int  bhwp_describe_istft_cmfft(const bhw_params *p, const BhwCordicCfg *ct, uint
 int  bhwk_istft_cmfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwIstftCmfftPlan &pl, const bhw_stft *s,
                           const float *d_Y, float *d_x, const int32_t *d_table, const BhwLenPhase &lp);
 
+// ---- fused STFT, real or complex gain per bin and inverse STFT for I/Q input (bhw_[c]mask_cfft_f32_*, bhw_[c]mask_cmfft_f32_*;
+// ---- bhw_mask_cfft.hip, bhw_mask_cmfft.hip) ----------------------------------------------------------------------
+// The inverse I/Q kernels with their frames formed from the signal, as BhwMaskFftPlan is the real-signal one: each plan IS
+// bhwp_istft_cfft_plan / bhwp_istft_cmfft_plan of the synthesis descriptor, field for field, but for the LDS of the power-of-two
+// family, which holds a second (forward) twiddle table of n / 2 entries: 56 KiB at 2048 where the parent has 48, two workgroups on a
+// CU by LDS where the parent has three.  The mixed-radix parent already runs the forward passes over the forward table, so its LDS
+// bytes stand.  `shifted` (BHW_CFFT_SHIFT in flags) is of the gain columns here: the gain of bin k is in column (k + n_fft / 2) mod
+// n_fft, where the parents keep bin k under the same flag.  K = n_fft gains a row; in_stride counts floats, two per sample.
+struct BhwMaskCfftPlan : BhwIstftCfftPlan {           // lds_bytes: 2 * fy * n * 8 + 2 * (n / 2) * 8 + n * 4  (<= 56 KiB)
+    uint64_t in_stride;   // floats between the input signals (0 -> 2 * the analysis descriptor's samples)
+    uint64_t g_stride, g_bstride;   // gains (floats; pairs for bhw_cmask_*) between the gain rows of a signal and between the signals' gains, as given (0: one row)
+};
+struct BhwMaskCmfftPlan : BhwIstftCmfftPlan {         // lds_bytes: the parent's
+    uint64_t in_stride;
+    uint64_t g_stride, g_bstride;
+};
+// Every check of the calls that needs no table handle, before any HIP call: the params, the refusals that name a route, the two
+// descriptors by the checks of bhw_stft_c[m]fft_f32_* (flags 0: detrending is refused with the flag bits) and bhw_istft_c[m]fft_f32_*
+// (in their words, packed row strides), then mask_tail_checks with K = n_fft and two floats a sample.  bhwp_cmask_*: 8-byte gains.
+int  bhwp_mask_cfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const void *d_x,
+                           const void *d_g, uint64_t g_stride, uint64_t g_batch_stride, const void *d_out, bool pointers = true);
+int  bhwp_cmask_cfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const void *d_x,
+                            const void *d_g, uint64_t g_stride, uint64_t g_batch_stride, const void *d_out, bool pointers = true);
+int  bhwp_mask_cmfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const void *d_x,
+                            const void *d_g, uint64_t g_stride, uint64_t g_batch_stride, const void *d_out, bool pointers = true);
+int  bhwp_cmask_cmfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const void *d_x,
+                             const void *d_g, uint64_t g_stride, uint64_t g_batch_stride, const void *d_out, bool pointers = true);
+// the plans of a call that passed the checks with ss->samples > 0 (one per family: the pair-gain calls run it with strides in pairs)
+BhwMaskCfftPlan  bhwp_mask_cfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
+                                     uint64_t g_stride, uint64_t g_batch_stride, bool from_table);
+BhwMaskCmfftPlan bhwp_mask_cmfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
+                                      uint64_t g_stride, uint64_t g_batch_stride, bool from_table);
+int  bhwp_describe_mask_cfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *sa, const bhw_stft *ss,
+                             uint32_t flags, uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len);
+int  bhwp_describe_cmask_cfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *sa, const bhw_stft *ss,
+                              uint32_t flags, uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len);
+int  bhwp_describe_mask_cmfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *sa, const bhw_stft *ss,
+                              uint32_t flags, uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len);
+int  bhwp_describe_cmask_cmfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *sa, const bhw_stft *ss,
+                               uint32_t flags, uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len);
+int  bhwk_mask_cfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwMaskCfftPlan &pl, const bhw_stft *sa,
+                        const bhw_stft *ss, const float *d_x, const float *d_g, float *d_out, const int32_t *d_table, const BhwLenPhase &lp);
+int  bhwk_cmask_cfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwMaskCfftPlan &pl, const bhw_stft *sa,
+                         const bhw_stft *ss, const float *d_x, const float *d_g, float *d_out, const int32_t *d_table, const BhwLenPhase &lp);
+int  bhwk_mask_cmfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwMaskCmfftPlan &pl, const bhw_stft *sa,
+                         const bhw_stft *ss, const float *d_x, const float *d_g, float *d_out, const int32_t *d_table, const BhwLenPhase &lp);
+int  bhwk_cmask_cmfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwMaskCmfftPlan &pl, const bhw_stft *sa,
+                          const bhw_stft *ss, const float *d_x, const float *d_g, float *d_out, const int32_t *d_table, const BhwLenPhase &lp);
+
 // the generate kernel of a window of any length (bhw_len.hip): d_table NULL = k_direct_len, else k_range_len over the resident table of c
 int  bhwk_len_range(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const int32_t *d_table, const BhwLenPhase &lp,
                     uint64_t n0, uint64_t count, int32_t *d_out);

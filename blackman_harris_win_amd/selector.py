@@ -876,15 +876,19 @@ def _mask_fft_refusals(torch, x, mask, n_fft):
                          f"bhw.istft take it)")
 
 
-def _mask_gains(torch, mask, nb, frames, K, dev, complex_gains=False):
+def _mask_gains(torch, mask, nb, frames, K, dev, complex_gains=False, iq=False):
     """The gains as the kernel reads them: (the tensor read, g_stride, g_batch_stride).  mask: real float32 -- complex64 with
     complex_gains, the strides then counting (re, im) pairs, as torch counts them -- (K,), (F, K) or (1 | B, 1 | F, K), its last axis
     contiguous.  An axis of size 1 or of stride 0 (an expand() view) becomes a zero stride and is never materialised; rows or signals
-    that overlap in memory some other way are copied first.  A lazy conjugate is resolved first."""
+    that overlap in memory some other way are copied first.  A lazy conjugate is resolved first.  iq: the I/Q calls, whose rows hold
+    K = n_fft gains and say so."""
     want = torch.complex64 if complex_gains else torch.float32
     if not isinstance(mask, torch.Tensor) or mask.dtype != want or not mask.is_cuda or mask.device.index != dev:
         raise ValueError("mask must be a complex64 CUDA tensor on the call's device" if complex_gains else
                          "mask must be a real float32 CUDA tensor on the call's device")
+    if iq and (mask.dim() not in (1, 2, 3) or mask.shape[-1] != K):
+        raise ValueError(f"mask must be (K,), (F, K) or (1 | B, 1 | F, K) with K = n_fft = {K} (I/Q input: every bin takes a gain), got "
+                         f"{tuple(mask.shape)}")
     if mask.dim() not in (1, 2, 3) or mask.shape[-1] != K:
         raise ValueError(f"mask must be (K,), (F, K) or (1 | B, 1 | F, K) with K = n_fft // 2 + 1 = {K}, got {tuple(mask.shape)}")
     m = mask.resolve_conj().resolve_neg()
@@ -918,8 +922,8 @@ def stft_mask_istft(params, x, mask, n_fft, hop, *, win_length=None, center=True
     (stft_mixed + istft_mixed), complex x (stft_iq + istft_iq), 4096 (stft + istft).  `out`: a contiguous float32 tensor of the
     returned shape; it may not share memory with x or mask.  `table`: a ResidentTable of these params to gather the window
     coefficients from (bhw_mask_fft_f32_from_table: no allocation by the library, no synchronisation, capturable on its first call),
-    or None (the library form: capturable with no warm call).  stft_mask_istft_mixed() is this call at a mixed-radix n_fft, and
-    stft_cmask_istft() this call with a complex gain per bin."""
+    or None (the library form: capturable with no warm call).  stft_mask_istft_mixed() is this call at a mixed-radix n_fft,
+    stft_cmask_istft() this call with a complex gain per bin, and stft_mask_istft_iq() this call for complex (I/Q) x in one launch."""
     torch = _torch()
     _mask_fft_refusals(torch, x, mask, n_fft)
     return _stft_mask_istft(torch, params, x, mask, n_fft, hop, win_length, center, pad_mode, length, normalize, shift, out, table,
@@ -927,31 +931,37 @@ def stft_mask_istft(params, x, mask, n_fft, hop, *, win_length=None, center=True
 
 
 def _stft_mask_istft(torch, params, x, mask, n_fft, hop, win_length, center, pad_mode, length, normalize, shift, out, table, check, device_call,
-                     table_call, complex_gains=False):
-    """What stft_mask_istft(), stft_mask_istft_mixed() and their complex-gain siblings share after their refusals: the input checks
-    (check: _fft_input or _mfft_input), the two descriptors, the gains (complex_gains: complex64, strides in pairs) and the one call."""
+                     table_call, complex_gains=False, iq=False, fftshift=False):
+    """What stft_mask_istft(), stft_mask_istft_mixed(), their complex-gain siblings and the four I/Q calls share after their refusals:
+    the input checks (check: _fft_input or _mfft_input; _cfft_input or _cmfft_input with iq), the two descriptors, the gains
+    (complex_gains: complex64, strides in pairs; iq: K = n_fft of them a row, fftshift: their columns on a centred axis) and the one
+    call."""
     if table is not None:
         if not isinstance(table, ResidentTable):
             raise ValueError("table must be a ResidentTable or None")
         dev, handle = table.device, table._live()
     else:
         if not isinstance(x, torch.Tensor) or not x.is_cuda:
-            raise ValueError("x must be a float32 CUDA tensor")
+            raise ValueError("x must be a complex64 CUDA tensor" if iq else "x must be a float32 CUDA tensor")
         dev, handle = x.device.index, None
     n_fft, L, xb, nb, T, frames, d = _stft_front(torch, params, x, n_fft, hop, win_length, center, pad_mode, False, dev, check)
     if not center and L < n_fft:
         raise ValueError("center=False with win_length < n_fft: the first outputs have no window under them")
-    K = n_fft // 2 + 1
-    g, gs, gbs = _mask_gains(torch, mask, nb, frames, K, dev, complex_gains)
+    if iq and (not x.is_cuda or x.device.index != dev):
+        raise ValueError("x must be a complex64 CUDA tensor on the call's device")
+    K = n_fft if iq else n_fft // 2 + 1
+    C = 2 if iq else 1
+    g, gs, gbs = _mask_gains(torch, mask, nb, frames, K, dev, complex_gains, iq)
     length = T if length is None else int(length)
     if length < 0:
         raise ValueError(f"length {length} < 0")
     out = _stft_out(torch, out, (nb, length) if x.dim() == 2 else (length,), x, "x")
     shift = params.dat_width - 1 if shift is None else int(shift)
-    sa = B.make_stft(nb, T, frames, d["hop"], n_fft, col0=d["col0"], pad=d["pad"], pad_mode=d["pad_mode"], shift=shift,
-                     x_stride=xb.stride(0) if nb > 1 else 0)
-    ss = B.make_stft(nb, length, frames, d["hop"], n_fft, col0=d["col0"], pad=d["pad"], shift=shift)
-    tail = (ctypes.byref(sa), ctypes.byref(ss), B.OLA_NORMALIZE if normalize else 0, ctypes.c_void_p(xb.data_ptr()),
+    sa = B.make_stft(nb, T, frames, d["hop"], n_fft, col0=d["col0"], pad=d["pad"], pad_mode=d["pad_mode"], shift=shift, channels=C,
+                     x_stride=xb.stride(0) * C if nb > 1 else 0)
+    ss = B.make_stft(nb, length, frames, d["hop"], n_fft, col0=d["col0"], pad=d["pad"], shift=shift, channels=C)
+    flags = (B.OLA_NORMALIZE if normalize else 0) | (B.CFFT_SHIFT if fftshift else 0)
+    tail = (ctypes.byref(sa), ctypes.byref(ss), flags, ctypes.c_void_p(xb.data_ptr()),
             ctypes.c_void_p(g.data_ptr()), gs, gbs, ctypes.c_void_p(out.data_ptr()))
     if handle is None:
         B.check(getattr(B.lib(), device_call)(ctypes.byref(params), L, dev, _stream_ptr(torch, dev), *tail))
@@ -992,7 +1002,7 @@ def stft_mask_istft_mixed(params, x, mask, n_fft, hop, *, win_length=None, cente
     multiply and istft_mixed), complex x (stft_iq_mixed + istft_iq_mixed), a complex mask (stft_mixed + a complex multiply +
     istft_mixed).  `table`: a ResidentTable of these params (bhw_mask_mfft_f32_from_table: no allocation by the library, no
     synchronisation, capturable on its first call), or None (the library form: capturable with no warm call).
-    stft_cmask_istft_mixed() is this call with a complex gain per bin."""
+    stft_cmask_istft_mixed() is this call with a complex gain per bin, stft_mask_istft_iq_mixed() this call for complex (I/Q) x."""
     import torch as host_torch                            # the refusals look at no device: they come before _torch() asks for one
     _mask_mfft_refusals(host_torch, x, mask, n_fft)
     torch = _torch()
@@ -1049,7 +1059,8 @@ def stft_cmask_istft(params, x, mask, n_fft, hop, *, win_length=None, center=Tru
     multiply's rounding.  The imaginary parts of the gains at bins 0 and n_fft / 2 multiply stored zeros and are otherwise unused.
     n_fft: a power of two in 16..2048.  ValueError naming the calls that take it: a real mask (stft_mask_istft), a mixed-radix n_fft
     (stft_cmask_istft_mixed), complex x (stft_iq + istft_iq), 4096 (stft, a complex multiply and istft).  `out`, `table` and the
-    other keywords are stft_mask_istft()'s (bhw_cmask_fft_f32_from_table)."""
+    other keywords are stft_mask_istft()'s (bhw_cmask_fft_f32_from_table).  stft_cmask_istft_iq() is this call for complex (I/Q) x in
+    one launch."""
     import torch as host_torch                            # the refusals look at no device: they come before _torch() asks for one
     _cmask_refusals(host_torch, x, mask, n_fft, False)
     torch = _torch()
@@ -1064,12 +1075,101 @@ def stft_cmask_istft_mixed(params, x, mask, n_fft, hop, *, win_length=None, cent
     and the statement about torch's complex multiply are stft_cmask_istft()'s, with stft_mixed() and istft_mixed() as the two
     transforms: the result equals istft_mixed() of the masked stft_mixed() rows BIT FOR BIT.  ValueError naming the calls that take
     it: a real mask (stft_mask_istft_mixed), a power of two (stft_cmask_istft), an n_fft of 2048 or more (stft_mixed, a complex
-    multiply and istft_mixed), complex x (stft_iq_mixed + istft_iq_mixed).  `table`: bhw_cmask_mfft_f32_from_table."""
+    multiply and istft_mixed), complex x (stft_iq_mixed + istft_iq_mixed).  `table`: bhw_cmask_mfft_f32_from_table.
+    stft_cmask_istft_iq_mixed() is this call for complex (I/Q) x in one launch."""
     import torch as host_torch
     _cmask_refusals(host_torch, x, mask, n_fft, True)
     torch = _torch()
     return _stft_mask_istft(torch, params, x, mask, n_fft, hop, win_length, center, pad_mode, length, normalize, shift, out, table,
                             _mfft_input, "bhw_cmask_mfft_f32_device", "bhw_cmask_mfft_f32_from_table", True)
+
+
+# ---- the same for I/Q input: a real or complex gain on every one of the n_fft bins ---------------------------------------------------------
+
+def _mask_iq_refusals(torch, x, mask, n_fft, complex_gains, mixed):
+    """What the four I/Q mask calls do not take, refused naming the call that does, before any check that needs a device."""
+    c, tail = ("c" if complex_gains else ""), ("_mixed" if mixed else "")
+    name = f"bhw.stft_{c}mask_istft_iq{tail}"
+    if isinstance(x, torch.Tensor) and not x.is_complex():
+        raise ValueError(f"{name} takes complex64 (I/Q) input, got {x.dtype}: bhw.stft_{c}mask_istft{tail} takes a real signal")
+    if isinstance(mask, torch.Tensor) and mask.is_complex() != complex_gains:
+        other = f"bhw.stft_{'' if complex_gains else 'c'}mask_istft_iq{tail}"
+        raise ValueError(f"{name} takes {'complex64' if complex_gains else 'real float32'} gains, got {mask.dtype}: {other} takes "
+                         f"{'real' if complex_gains else 'complex'} gains")
+    n = int(n_fft)
+    if mixed and B.cfft_supported(n):
+        raise ValueError(f"n_fft {n} is a power of two: bhw.stft_{c}mask_istft_iq takes it (one transform per n_fft)")
+    if not mixed and B.cmfft_supported(n):
+        raise ValueError(f"{name} takes n_fft a power of two in {B.CFFT_MIN_N}..{B.CFFT_MAX_N}, got {n} (a mixed-radix n_fft: "
+                         f"bhw.stft_{c}mask_istft_iq_mixed takes it)")
+    if n > B.CFFT_MAX_N and (B.fft_supported(n) or B.mfft_supported(n)):
+        raise ValueError(f"{name} takes n_fft up to {B.CFFT_MAX_N if not mixed else B.CMFFT_MAX_N}, got {n}: no fused I/Q transform takes it "
+                         f"(the three-call route there is stft_frames, torch.fft.fft, a multiply, torch.fft.ifft and istft_overlap_add)")
+
+
+def _stft_mask_istft_iq(params, iq, gains, n_fft, hop, win_length, center, pad_mode, length, normalize, shift, fftshift, out, table,
+                        complex_gains, mixed):
+    """The four I/Q calls: their refusals, then _stft_mask_istft with the I/Q input check, K = n_fft and the shift of the gain columns."""
+    import torch as host_torch                            # the refusals look at no device: they come before _torch() asks for one
+    _mask_iq_refusals(host_torch, iq, gains, n_fft, complex_gains, mixed)
+    torch = _torch()
+    name = f"bhw_{'c' if complex_gains else ''}mask_{'cmfft' if mixed else 'cfft'}_f32"
+    return _stft_mask_istft(torch, params, iq, gains, n_fft, hop, win_length, center, pad_mode, length, normalize, shift, out, table,
+                            _cmfft_input if mixed else _cfft_input, name + "_device", name + "_from_table", complex_gains, True, fftshift)
+
+
+def stft_mask_istft_iq(params, x, mask, n_fft, hop, *, win_length=None, center=True, pad_mode="reflect", length=None, normalize=True,
+                       shift=None, fftshift=False, out=None, table=None):
+    """stft_mask_istft() for complex baseband in ONE launch (bhw_mask_cfft_f32_device): stft_iq(), a real gain on every bin and
+    istft_iq() with neither spectrum in memory -- interference excision, notch and blanking masks.  x (T,) or (B, T), complex64; mask
+    real float32 (K,), (F, K) or (1 | B, 1 | F, K) with K = n_fft (all bins, not n_fft // 2 + 1), the last axis contiguous; an axis
+    of size 1 or stride 0 (an expand() view) is never materialised.  fftshift=True: the gain of bin k is mask column
+    (k + n_fft // 2) % n_fft, the column stft_iq(fftshift=True) writes bin k to -- the mask is torch.fft.fftshift(g, dim=-1) of the
+    gains g in natural order, so a mask designed on a centred frequency axis is passed as it is; x and the result are not touched by
+    it.  Returns complex64 (B, length), or (length,) for 1-D x; length defaults to T.  With Y = bhw.stft_iq(params, x, n_fft, hop, ...)
+    in natural bin order and g the gains in that order, the result equals
+
+        bhw.istft_iq(params, torch.complex(Y.real * g, Y.imag * g), n_fft, hop, ..., length=length, normalize=normalize)
+
+    BIT FOR BIT.  n_fft: a power of two in 16..2048.  ValueError naming the call that takes the input: a real x (stft_mask_istft), a
+    complex mask (stft_cmask_istft_iq), a mixed-radix n_fft (stft_mask_istft_iq_mixed).  center=False with win_length < n_fft is
+    refused, and there is no detrending (it has no inverse).  `out`: a contiguous complex64 tensor of the returned shape that shares
+    no memory with x or mask.  `table`: a ResidentTable of these params (bhw_mask_cfft_f32_from_table), or None."""
+    return _stft_mask_istft_iq(params, x, mask, n_fft, hop, win_length, center, pad_mode, length, normalize, shift, fftshift, out, table,
+                               False, False)
+
+
+def stft_cmask_istft_iq(params, x, mask, n_fft, hop, *, win_length=None, center=True, pad_mode="reflect", length=None, normalize=True,
+                        shift=None, fftshift=False, out=None, table=None):
+    """stft_mask_istft_iq() with a COMPLEX gain per bin (bhw_cmask_cfft_f32_device): an equaliser or channeliser response H[k] as one
+    (K,) row, a fractional delay, per-channel beamforming weights (B, 1, K).  mask complex64, K = n_fft; a conjugate view is resolved
+    first.  With Y = bhw.stft_iq(...) and G the gains in natural bin order the masked spectrum is, in separate float32 operations,
+
+        Z.real = Y.real * G.real - Y.imag * G.imag        Z.imag = Y.real * G.imag + Y.imag * G.real
+
+    and the result equals bhw.istft_iq(params, Z, ...) BIT FOR BIT; equality with torch's complex Y * G is not promised.  No bin is
+    special: bins 0 and n_fft / 2 of a complex signal carry an imaginary part and G.imag acts on them like on any other bin.
+    ValueError: a real mask names stft_mask_istft_iq, a real x stft_cmask_istft, a mixed-radix n_fft stft_cmask_istft_iq_mixed."""
+    return _stft_mask_istft_iq(params, x, mask, n_fft, hop, win_length, center, pad_mode, length, normalize, shift, fftshift, out, table,
+                               True, False)
+
+
+def stft_mask_istft_iq_mixed(params, x, mask, n_fft, hop, *, win_length=None, center=True, pad_mode="reflect", length=None, normalize=True,
+                             shift=None, fftshift=False, out=None, table=None):
+    """stft_mask_istft_iq() at the n_fft of stft_iq_mixed() (bhw_mask_cmfft_f32_device): the 91 sizes 2^a·3^b·5^c in 18..2025 that are
+    no power of two, odd ones included.  The result equals istft_iq_mixed() of the gained stft_iq_mixed() rows BIT FOR BIT;
+    fftshift=True uses integer division at an odd n_fft too.  A power of two names stft_mask_istft_iq."""
+    return _stft_mask_istft_iq(params, x, mask, n_fft, hop, win_length, center, pad_mode, length, normalize, shift, fftshift, out, table,
+                               False, True)
+
+
+def stft_cmask_istft_iq_mixed(params, x, mask, n_fft, hop, *, win_length=None, center=True, pad_mode="reflect", length=None, normalize=True,
+                              shift=None, fftshift=False, out=None, table=None):
+    """stft_cmask_istft_iq() at the n_fft of stft_iq_mixed() (bhw_cmask_cmfft_f32_device); the formula, the layouts and the errors are
+    stft_cmask_istft_iq()'s with stft_iq_mixed() and istft_iq_mixed() as the two transforms: the result equals istft_iq_mixed() of the
+    masked stft_iq_mixed() rows BIT FOR BIT.  A power of two names stft_cmask_istft_iq."""
+    return _stft_mask_istft_iq(params, x, mask, n_fft, hop, win_length, center, pad_mode, length, normalize, shift, fftshift, out, table,
+                               True, True)
 
 
 def fbank_bands(weights):

@@ -1566,7 +1566,7 @@ int bhw_describe_csd_fft(bhw_table t, const bhw_params *p, uint64_t length, cons
  *     and (from a table) the key match.
  *   - No workspace, no allocation, no float atomics.  The library form computes the coefficients by direct CORDIC and both twiddle
  *     tables in the kernel: capturable with no bhw_prepare_device.  The from-table form is capturable on its first call.
- *   - Not built: complex gains (bhw_cmask_fft_f32_* below take them); I/Q input; 4096; a gain computed in the kernel; a second output
+ *   - Not built: complex gains (bhw_cmask_fft_f32_* below take them); I/Q input (bhw_mask_cfft_f32_* below takes it); 4096; a gain computed in the kernel; a second output
  *     with the masked spectrum.  (A mixed-radix n_fft from 18 to 2000 has calls of its own: bhw_mask_mfft_f32_* below.)
  *   - bhw_describe_mask_fft: the plan fields of bhw_describe_istft_fft's line for ss in the same words (the plan IS that call's, but
  *     for the LDS bytes), with the kernel, "forward + inverse FFT", the analysis padding and the gain strides.  It takes the gain
@@ -1597,7 +1597,7 @@ int bhw_describe_mask_fft(bhw_table t, const bhw_params *p, uint64_t length, con
  *     everything bhw_stft_mfft_f32_* checks on sa and everything bhw_istft_mfft_f32_* checks on ss, both with packed row strides and
  *     in those calls' own words; then what bhw_mask_fft_f32_* checks after its parents, in its words and its order.
  *   - No workspace, no allocation, no float atomics; both forms are capturable as bhw_mask_fft_f32_*'s are.
- *   - Not built: complex gains (bhw_cmask_mfft_f32_* below take them); I/Q input; n_fft >= 2048; a gain computed in the kernel; a second
+ *   - Not built: complex gains (bhw_cmask_mfft_f32_* below take them); I/Q input (bhw_mask_cmfft_f32_* below takes it); n_fft >= 2048; a gain computed in the kernel; a second
  *     output with the masked spectrum.
  *   - bhw_describe_mask_mfft: the plan fields of bhw_describe_istft_mfft's line for ss in the same words (the plan IS that call's, but
  *     for the LDS bytes), with the kernel, "forward + inverse FFT", the analysis padding and the gain strides. */
@@ -1635,7 +1635,8 @@ int bhw_describe_mask_mfft(bhw_table t, const bhw_params *p, uint64_t length, co
  *     bhw_cmask_mfft_f32_*: even 2^a 3^b 5^c in 18..2000, no power of two (73 sizes).  BHW_ERR_UNSUPPORTED in the real-gain calls'
  *     sentences, about "the fused complex-gain mask": channels 2 names the I/Q transforms, 4096 and the mixed-radix lengths above 2047
  *     the pairs of transforms, and the other family's sizes name bhw_cmask_mfft_f32_* / bhw_cmask_fft_f32_*.
- *   - Not built: I/Q input; n_fft >= 2048 (mixed) / 4096; a gain computed in the kernel; a second output with the masked spectrum.
+ *   - Not built: n_fft >= 2048 (mixed) / 4096; a gain computed in the kernel; a second output with the masked spectrum.  (I/Q input:
+ *     bhw_cmask_cfft_f32_* and bhw_cmask_cmfft_f32_* below.)
  *   - bhw_describe_cmask_fft / _mfft: bhw_describe_mask_fft's / _mfft's line -- the plan IS that call's for the same arguments: lanes,
  *     spans, columns per lane and LDS bytes; the gains live in registers -- beginning "cmask", naming k_cmask_*_direct / _table and
  *     saying "complex gains" before the strides (in pairs). */
@@ -1653,6 +1654,70 @@ int bhw_cmask_mfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t len
                                   float *d_out);
 int bhw_describe_cmask_mfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
                             uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len);
+
+/* Fused STFT, a REAL OR COMPLEX gain per bin and inverse STFT for I/Q INPUT: the four calls above for complex baseband -- excision
+ * and blanking masks, an equaliser or channeliser response H[k] as one (K,) row, a fractional delay, per-channel beamforming weights.
+ * ONE launch, no spectrum in memory, no workspace.  bhw_mask_cfft_f32_* / bhw_cmask_cfft_f32_*: n_fft a power of two in 16..2048;
+ * bhw_mask_cmfft_f32_* / bhw_cmask_cmfft_f32_*: the 91 sizes 2^a 3^b 5^c in 18..2025 that are no power of two, odd ones included.
+ * The arguments are those of bhw_mask_fft_f32_device / _from_table / bhw_describe_mask_fft, word for word, with these differences:
+ *   - d_x and d_out hold interleaved I/Q (two floats a sample; x_stride counts floats, 0 = 2 * samples) and both descriptors carry
+ *     channels = 2.  sa is checked exactly as bhw_stft_cfft_f32_* (bhw_stft_cmfft_f32_*) checks it with flags 0 and ss as
+ *     bhw_istft_cfft_f32_* (bhw_istft_cmfft_f32_*) checks it with `flags`, in those calls' words and with packed row strides.
+ *   - K = n_fft: every bin takes a gain, at an odd n_fft too.  bhw_mask_*: d_g holds floats; bhw_cmask_*: interleaved pairs (gr, gi),
+ *     8-byte aligned, the strides in pairs.  The gain of column j of frame f of signal b is at b * g_batch_stride + f * g_stride + j;
+ *     either stride may be 0, a nonzero g_stride is at least K, a nonzero g_batch_stride at least (frames - 1) * g_stride + K.
+ *   - flags: BHW_OLA_NORMALIZE and BHW_CFFT_SHIFT.  With BHW_CFFT_SHIFT the gain of bin k is read from column (k + n_fft / 2) mod
+ *     n_fft (integer division at an odd n_fft too) -- the column bhw_stft_c[m]fft_f32_* writes bin k to and bhw_istft_c[m]fft_f32_*
+ *     reads it from under the same flag, torch.fft.fftshift along the bins: a mask designed on a centred frequency axis is passed as
+ *     it is.  (At an even n_fft column j then holds the gain of bin (j + n_fft / 2) mod n_fft; at an odd one of bin
+ *     (j + n_fft / 2 + 1) mod n_fft.)  The shift is a load index in the kernel, never a pass over the data, and it does not touch d_x
+ *     or d_out.  Detrending has no inverse and is refused with the other unknown flag bits.
+ *   - NO BIN IS SPECIAL (unlike bhw_cmask_fft_f32_* above): bins 0 and n_fft / 2 of a complex signal carry an imaginary part, and gi
+ *     acts on them as on every other bin.
+ *   - The rows, exact and without tolerance.  Y[b, f, k] = (re, im) is the pair bhw_stft_cfft_f32_* (bhw_stft_cmfft_f32_*) writes for
+ *     (sa, d_x, flags 0).  The masked bin under a real gain g is (fl32(re * g), fl32(im * g)); under a pair
+ *         re' = fl32( fl32(re * gr) - fl32(im * gi) )
+ *         im' = fl32( fl32(re * gi) + fl32(im * gr) )
+ *     with nothing contracted.  d_out is what bhw_istft_cfft_f32_* (bhw_istft_cmfft_f32_*) writes for (ss, flags & BHW_OLA_NORMALIZE)
+ *     from those rows, WORD FOR WORD.  Equality with a library's complex multiply is not promised.
+ *   - Determinism: an output's bits depend only on the window, the geometry, the flags, the samples and the gains under its frames.
+ *     IEEE: a NaN or infinity in one gain (or one part of it), or in either part of one sample, reaches exactly the outputs under
+ *     those frames' windows.  ss->samples 0 -> BHW_OK.  d_out overlaps neither d_x nor d_g (extents in floats of two per sample, and
+ *     in gain elements).  No workspace, no allocation, no float atomics; both forms can be captured in a HIP graph.
+ *   - BHW_ERR_UNSUPPORTED names the route that takes the input: channels 1 the real-signal mask call of the same gain type and
+ *     family; a size of the other family the sibling among these four; 4096 and the mixed-radix lengths above 2047, which no fused
+ *     I/Q transform takes either, the pair of I/Q transforms whose range this call shares.
+ *   - bhw_describe_[c]mask_c[m]fft: the line of bhw_describe_istft_c[m]fft for (ss, flags) with the kernel name, "forward + inverse
+ *     FFT", the analysis padding, the gain strides ("complex gains:" for pairs), "gain columns shifted" / "in order" and the LDS
+ *     bytes of this call. */
+int bhw_mask_cfft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *sa, const bhw_stft *ss,
+                             uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride, float *d_out);
+int bhw_mask_cfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *sa, const bhw_stft *ss,
+                                 uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride,
+                                 float *d_out);
+int bhw_describe_mask_cfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
+                           uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len);
+int bhw_cmask_cfft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *sa, const bhw_stft *ss,
+                              uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride, float *d_out);
+int bhw_cmask_cfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *sa, const bhw_stft *ss,
+                                  uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride,
+                                  float *d_out);
+int bhw_describe_cmask_cfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
+                            uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len);
+int bhw_mask_cmfft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *sa, const bhw_stft *ss,
+                              uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride, float *d_out);
+int bhw_mask_cmfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *sa, const bhw_stft *ss,
+                                  uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride,
+                                  float *d_out);
+int bhw_describe_mask_cmfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
+                            uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len);
+int bhw_cmask_cmfft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *sa, const bhw_stft *ss,
+                               uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride, float *d_out);
+int bhw_cmask_cmfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *sa, const bhw_stft *ss,
+                                   uint32_t flags, const float *d_x, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride,
+                                   float *d_out);
+int bhw_describe_cmask_cmfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
+                             uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len);
 
 /* Threading: every entry point may be called from any host thread.  Calls that use the library-owned scratch of one
  * (device, stream) are serialised against each other for the duration of their launches (the table is rebuilt per call);
