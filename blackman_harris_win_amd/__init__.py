@@ -20,10 +20,10 @@ from .binding import (  # noqa: F401
     MODEL_CPP, MODEL_DDS48, MODEL_HLS, MODEL_SCALED, MODEL_VHDL,
     SIN_CORDIC, SIN_TAYLOR, SIN_TAYLOR_ALL,
     WIN_BH3, WIN_BH4, WIN_BH5, WIN_BH7, WIN_HAMMING, WIN_HANN,
-    BhwAtan2Params, BhwError, BhwFrames, BhwOla, BhwParams, BhwPsd, BhwCsd, BhwStft, WELCH_BLOCK, WELCH_FFT_CHUNK, describe_welch_fft, welch_fft_workspace_bytes, describe_csd_fft, csd_fft_workspace_bytes, describe_stft_cmfft, describe_mask_fft, describe_mask_mfft, describe_cmask_fft, describe_cmask_mfft, describe_mask_cfft, describe_cmask_cfft, describe_mask_cmfft, describe_cmask_cmfft, describe_welch_cfft, welch_cfft_workspace_bytes, describe_welch_mfft, welch_mfft_workspace_bytes, describe_welch_cmfft, welch_cmfft_workspace_bytes, describe_hold_cfft, hold_cfft_workspace_bytes, describe_hold_cmfft, hold_cmfft_workspace_bytes, describe_hold_fft, hold_fft_workspace_bytes, describe_hold_mfft, hold_mfft_workspace_bytes, describe_welch, describe_csd, PAD_CONSTANT, PAD_REFLECT, coeffs_from_float, describe_f32, describe_frames, describe_len, describe_ola, describe_stft, describe_stft_fft, describe_istft_fft, describe_spectrogram, describe_stft_mfft, describe_istft_mfft, mfft_supported, MFFT_POWER, describe_stft_cfft, describe_istft_cfft, describe_istft_cmfft, make_fbank, BhwFbank, BhwLogspec, make_logspec, describe_logspec, describe_logspec_mfft, LOG_CLAMP, LOG_ADD, constant_tables, describe_table, lib, lib_path, make_params, part_segments,
+    BhwAtan2Params, BhwError, BhwFrames, BhwOla, BhwParams, BhwPsd, BhwCsd, BhwStft, WELCH_BLOCK, WELCH_FFT_CHUNK, describe_welch_fft, welch_fft_workspace_bytes, describe_csd_fft, csd_fft_workspace_bytes, describe_stft_cmfft, describe_mask_fft, describe_mask_mfft, describe_cmask_fft, describe_cmask_mfft, describe_mask_cfft, describe_cmask_cfft, describe_mask_cmfft, describe_cmask_cmfft, describe_beam_fft, describe_beam_mfft, BEAM_MAX_CH, describe_welch_cfft, welch_cfft_workspace_bytes, describe_welch_mfft, welch_mfft_workspace_bytes, describe_welch_cmfft, welch_cmfft_workspace_bytes, describe_hold_cfft, hold_cfft_workspace_bytes, describe_hold_cmfft, hold_cmfft_workspace_bytes, describe_hold_fft, hold_fft_workspace_bytes, describe_hold_mfft, hold_mfft_workspace_bytes, describe_welch, describe_csd, PAD_CONSTANT, PAD_REFLECT, coeffs_from_float, describe_f32, describe_frames, describe_len, describe_ola, describe_stft, describe_stft_fft, describe_istft_fft, describe_spectrogram, describe_stft_mfft, describe_istft_mfft, mfft_supported, MFFT_POWER, describe_stft_cfft, describe_istft_cfft, describe_istft_cmfft, make_fbank, BhwFbank, BhwLogspec, make_logspec, describe_logspec, describe_logspec_mfft, LOG_CLAMP, LOG_ADD, constant_tables, describe_table, lib, lib_path, make_params, part_segments,
 )
 from .selector import (  # noqa: F401
-    ResidentTable, WinSelector, apply, apply_frames, atan2, istft_overlap_add, stft, istft, spectrogram, stft_mixed, spectrogram_mixed, istft_mixed, stft_iq, spectrogram_iq, stft_iq_mixed, spectrogram_iq_mixed, istft_iq, istft_iq_mixed, stft_mask_istft, stft_mask_istft_mixed, stft_cmask_istft, stft_cmask_istft_mixed, stft_mask_istft_iq, stft_cmask_istft_iq, stft_mask_istft_iq_mixed, stft_cmask_istft_iq_mixed, FilterBank, mel_weights, DctMatrix, dct_weights, log_spectrogram, log_spectrogram_mixed, mfcc, mfcc_mixed, stft_frames, welch, welch_fft, welch_fused, welch_fft_iq, welch_fused_iq, welch_fft_mixed, welch_fused_mixed, welch_fft_iq_mixed, welch_fused_iq_mixed, hold_fft_iq, hold_fused_iq, hold_fft_iq_mixed, hold_fused_iq_mixed, hold_fft, hold_fused, hold_fft_mixed, hold_fused_mixed, welch_frames, welch_psd, welch_csd, csd, coherence, transfer_function, cross_spectra, csd_fft, cross_spectra_fused, csd_fused, coherence_fused, transfer_function_fused, window_sums, overlap_add, cordic, gather_parts, generate, generate_batched, generate_part, prepare, shard_range, win_function, window,
+    ResidentTable, WinSelector, apply, apply_frames, atan2, istft_overlap_add, stft, istft, spectrogram, stft_mixed, spectrogram_mixed, istft_mixed, stft_iq, spectrogram_iq, stft_iq_mixed, spectrogram_iq_mixed, istft_iq, istft_iq_mixed, stft_mask_istft, stft_mask_istft_mixed, stft_cmask_istft, stft_cmask_istft_mixed, stft_mask_istft_iq, stft_cmask_istft_iq, stft_mask_istft_iq_mixed, stft_cmask_istft_iq_mixed, stft_beamform_istft, stft_beamform_istft_mixed, FilterBank, mel_weights, DctMatrix, dct_weights, log_spectrogram, log_spectrogram_mixed, mfcc, mfcc_mixed, stft_frames, welch, welch_fft, welch_fused, welch_fft_iq, welch_fused_iq, welch_fft_mixed, welch_fused_mixed, welch_fft_iq_mixed, welch_fused_iq_mixed, hold_fft_iq, hold_fused_iq, hold_fft_iq_mixed, hold_fused_iq_mixed, hold_fft, hold_fused, hold_fft_mixed, hold_fused_mixed, welch_frames, welch_psd, welch_csd, csd, coherence, transfer_function, cross_spectra, csd_fft, cross_spectra_fused, csd_fused, coherence_fused, transfer_function_fused, window_sums, overlap_add, cordic, gather_parts, generate, generate_batched, generate_part, prepare, shard_range, win_function, window,
 )
 
 __all__ = [
@@ -41,6 +41,7 @@ __all__ = [
     "stft_cmask_istft", "describe_cmask_fft", "stft_cmask_istft_mixed", "describe_cmask_mfft",
     "stft_mask_istft_iq", "describe_mask_cfft", "stft_cmask_istft_iq", "describe_cmask_cfft",
     "stft_mask_istft_iq_mixed", "describe_mask_cmfft", "stft_cmask_istft_iq_mixed", "describe_cmask_cmfft",
+    "stft_beamform_istft", "describe_beam_fft", "stft_beamform_istft_mixed", "describe_beam_mfft", "BEAM_MAX_CH",
     "window_sums", "welch_frames", "welch_psd", "welch", "describe_welch",
     "welch_fft", "welch_fused", "describe_welch_fft", "welch_fft_workspace_bytes", "WELCH_FFT_CHUNK",
     "welch_fft_iq", "welch_fused_iq", "describe_welch_cfft", "welch_cfft_workspace_bytes",

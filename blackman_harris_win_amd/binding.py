@@ -72,6 +72,8 @@ ABI_SYMBOLS = (
     "bhw_cmask_cfft_f32_device", "bhw_cmask_cfft_f32_from_table", "bhw_describe_cmask_cfft",
     "bhw_mask_cmfft_f32_device", "bhw_mask_cmfft_f32_from_table", "bhw_describe_mask_cmfft",
     "bhw_cmask_cmfft_f32_device", "bhw_cmask_cmfft_f32_from_table", "bhw_describe_cmask_cmfft",
+    "bhw_beam_fft_f32_device", "bhw_beam_fft_f32_from_table", "bhw_describe_beam_fft",
+    "bhw_beam_mfft_f32_device", "bhw_beam_mfft_f32_from_table", "bhw_describe_beam_mfft",
 )
 
 
@@ -367,6 +369,10 @@ def lib():
         getattr(L, f"bhw_cmask_{fam}_f32_device").argtypes = [P, u64, ci, vp, S, S, u32, f32p, f32p, u64, u64, f32p]
         getattr(L, f"bhw_cmask_{fam}_f32_from_table").argtypes = [T, P, u64, vp, S, S, u32, f32p, f32p, u64, u64, f32p]
         getattr(L, f"bhw_describe_cmask_{fam}").argtypes = [T, P, u64, S, S, u32, u64, u64, ctypes.c_char_p, u64]
+    for fam in ("fft", "mfft"):                          # filter-and-sum: n_ch and x_ch_stride behind d_x, g_ch_stride between the gain strides
+        getattr(L, f"bhw_beam_{fam}_f32_device").argtypes = [P, u64, ci, vp, S, S, u32, f32p, u32, u64, f32p, u64, u64, u64, f32p]
+        getattr(L, f"bhw_beam_{fam}_f32_from_table").argtypes = [T, P, u64, vp, S, S, u32, f32p, u32, u64, f32p, u64, u64, u64, f32p]
+        getattr(L, f"bhw_describe_beam_{fam}").argtypes = [T, P, u64, S, S, u32, u32, u64, u64, u64, u64, ctypes.c_char_p, u64]
     for name in ("mask_cfft", "cmask_cfft", "mask_cmfft", "cmask_cmfft"):          # the same twelve for I/Q input
         getattr(L, f"bhw_{name}_f32_device").argtypes = [P, u64, ci, vp, S, S, u32, f32p, f32p, u64, u64, f32p]
         getattr(L, f"bhw_{name}_f32_from_table").argtypes = [T, P, u64, vp, S, S, u32, f32p, f32p, u64, u64, f32p]
@@ -664,6 +670,32 @@ def describe_mask_cmfft(params, length, analysis, synthesis, *, normalize=False,
 def describe_cmask_cmfft(params, length, analysis, synthesis, *, normalize=False, fftshift=False, g_stride=0, g_batch_stride=0, table=None):
     """describe_mask_cmfft() for the complex-gain call (bhw_describe_cmask_cmfft)."""
     return _describe_mask_iq("cmask_cmfft", params, length, analysis, synthesis, normalize, fftshift, g_stride, g_batch_stride, table)
+
+
+BEAM_MAX_CH = 64   # BHW_BEAM_MAX_CH
+
+
+def _describe_beam(fam, params, length, analysis, synthesis, n_ch, normalize, x_ch_stride, g_stride, g_ch_stride, g_batch_stride, table):
+    buf = ctypes.create_string_buffer(1280)
+    check(getattr(lib(), "bhw_describe_beam_" + fam)(table, ctypes.byref(params), int(length), ctypes.byref(analysis), ctypes.byref(synthesis),
+                                                     OLA_NORMALIZE if normalize else 0, int(n_ch), int(x_ch_stride), int(g_stride),
+                                                     int(g_ch_stride), int(g_batch_stride), buf, len(buf)))
+    return buf.value.decode()
+
+
+def describe_beam_fft(params, length, analysis, synthesis, n_ch, *, normalize=False, x_ch_stride=0, g_stride=0, g_ch_stride=0,
+                      g_batch_stride=0, table=None):
+    """describe_cmask_fft() for the filter-and-sum call over n_ch channels (bhw_describe_beam_fft): the same plan fields for the B
+    output signals -- the channel sums live in registers -- in a line that begins "beam", names k_beam_fft_direct / k_beam_fft_table
+    and says "channels C" and the three gain strides (in pairs).  Host arithmetic only."""
+    return _describe_beam("fft", params, length, analysis, synthesis, n_ch, normalize, x_ch_stride, g_stride, g_ch_stride, g_batch_stride, table)
+
+
+def describe_beam_mfft(params, length, analysis, synthesis, n_ch, *, normalize=False, x_ch_stride=0, g_stride=0, g_ch_stride=0,
+                       g_batch_stride=0, table=None):
+    """describe_beam_fft() for a mixed-radix n_fft (bhw_describe_beam_mfft): describe_cmask_mfft()'s plan fields, k_beam_mfft_direct /
+    k_beam_mfft_table.  Host arithmetic only."""
+    return _describe_beam("mfft", params, length, analysis, synthesis, n_ch, normalize, x_ch_stride, g_stride, g_ch_stride, g_batch_stride, table)
 
 
 def describe_spectrogram(params, length, stft, *, detrend=False, fbank=None, table=None):

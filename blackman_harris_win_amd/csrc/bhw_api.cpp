@@ -1474,6 +1474,41 @@ int cmask_cmfft_run(bhw_table t, const bhw_params *p, uint64_t length, int devic
         "cmask cmfft launch", "cmask cmfft launch (resident table)", t, p, length, device, stream, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out);
 }
 
+// The fused filter-and-sum over ch.n_ch channels: mask_run with the channel axis (Checks / Plan / Kernel: bhwp_beam_[m]fft_checks,
+// bhwp_beam_[m]fft_plan, bhwk_beam_[m]fft_f32).
+template <auto Checks, auto Plan, auto Kernel>
+int beam_run(const char *what, const char *what_table, bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream,
+             const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const float *d_x, const BhwBeamAxis &ch, const float *d_g,
+             uint64_t g_stride, uint64_t g_batch_stride, float *d_out)
+{
+    int rc = Checks(p, length, sa, ss, flags, d_x, ch, d_g, g_stride, g_batch_stride, d_out, true);
+    if (!rc && t) rc = table_call_checks(t, p);
+    if (rc || !ss->samples) return rc;
+    const auto pl = Plan(p, length, sa, ss, flags, ch, g_stride, g_batch_stride, t != nullptr);
+    return run_source(t, p, length, device, stream, t ? what_table : what, [&](const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w,
+                                                                               const int32_t *tab, const BhwLenPhase *lp) {
+        return Kernel(l, c, w, pl, sa, ss, d_x, d_g, d_out, tab, *lp);
+    });
+}
+
+int beam_fft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *sa, const bhw_stft *ss,
+                 uint32_t flags, const float *d_x, const BhwBeamAxis &ch, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride,
+                 float *d_out)
+{
+    return beam_run<bhwp_beam_fft_checks, bhwp_beam_fft_plan, bhwk_beam_fft_f32>(
+        "beam fft launch", "beam fft launch (resident table)", t, p, length, device, stream, sa, ss, flags, d_x, ch, d_g, g_stride, g_batch_stride,
+        d_out);
+}
+
+int beam_mfft_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, const bhw_stft *sa, const bhw_stft *ss,
+                  uint32_t flags, const float *d_x, const BhwBeamAxis &ch, const float *d_g, uint64_t g_stride, uint64_t g_batch_stride,
+                  float *d_out)
+{
+    return beam_run<bhwp_beam_mfft_checks, bhwp_beam_mfft_plan, bhwk_beam_mfft_f32>(
+        "beam mfft launch", "beam mfft launch (resident table)", t, p, length, device, stream, sa, ss, flags, d_x, ch, d_g, g_stride,
+        g_batch_stride, d_out);
+}
+
 // The window sums (t NULL: the direct CORDIC chains): the checks, then the memset of the four words and the reduction.
 int window_sums_run(bhw_table t, const bhw_params *p, uint64_t length, int device, void *stream, uint32_t flags, uint64_t *d_sums)
 {
@@ -2210,6 +2245,39 @@ BHW_MASK_IQ_ENTRIES(cmask_cfft)
 BHW_MASK_IQ_ENTRIES(mask_cmfft)
 BHW_MASK_IQ_ENTRIES(cmask_cmfft)
 #undef BHW_MASK_IQ_ENTRIES
+
+// ---- fused multichannel filter-and-sum (include/bhw.h: bhw_beam_fft_f32_device ..., bhw_beam_mfft_f32_device ...) -------------------------
+// The three entry points of each family, in the shape of the ones above: NAME in {beam_fft, beam_mfft}.
+#define BHW_BEAM_ENTRIES(NAME)                                                                                                                  \
+    int bhw_##NAME##_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *sa, const bhw_stft *ss,      \
+                                uint32_t flags, const float *d_x, uint32_t n_ch, uint64_t x_ch_stride, const float *d_g, uint64_t g_stride,     \
+                                uint64_t g_ch_stride, uint64_t g_batch_stride, float *d_out)                                                     \
+    {                                                                                                                                           \
+        const BhwBeamAxis ch{n_ch, x_ch_stride, g_ch_stride};                                                                                   \
+        return NAME##_run(nullptr, p, length, device, hip_stream, sa, ss, flags, d_x, ch, d_g, g_stride, g_batch_stride, d_out);                \
+    }                                                                                                                                           \
+    int bhw_##NAME##_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *sa,                     \
+                                    const bhw_stft *ss, uint32_t flags, const float *d_x, uint32_t n_ch, uint64_t x_ch_stride,                   \
+                                    const float *d_g, uint64_t g_stride, uint64_t g_ch_stride, uint64_t g_batch_stride, float *d_out)            \
+    {                                                                                                                                           \
+        const BhwBeamAxis ch{n_ch, x_ch_stride, g_ch_stride};                                                                                   \
+        const int rc = bhwp_##NAME##_checks(p, length, sa, ss, flags, d_x, ch, d_g, g_stride, g_batch_stride, d_out);                           \
+        if (rc) return rc;                                                                                                                      \
+        return t ? NAME##_run(t, p, length, t->device, hip_stream, sa, ss, flags, d_x, ch, d_g, g_stride, g_batch_stride, d_out)                \
+                 : fail(BHW_ERR_BADARG, "table is NULL");                                                                                       \
+    }                                                                                                                                           \
+    int bhw_describe_##NAME(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,           \
+                            uint32_t n_ch, uint64_t x_ch_stride, uint64_t g_stride, uint64_t g_ch_stride, uint64_t g_batch_stride, char *buf,    \
+                            uint64_t len)                                                                                                       \
+    {                                                                                                                                           \
+        const BhwBeamAxis ch{n_ch, x_ch_stride, g_ch_stride};                                                                                   \
+        int rc = bhwp_##NAME##_checks(p, length, sa, ss, flags, nullptr, ch, nullptr, g_stride, g_batch_stride, nullptr, false);                \
+        if (!rc && t) rc = table_call_checks(t, p);                                                                                             \
+        return rc ? rc : bhwp_describe_##NAME(p, t ? &t->c : nullptr, length, sa, ss, flags, ch, g_stride, g_batch_stride, buf, len);            \
+    }
+BHW_BEAM_ENTRIES(beam_fft)
+BHW_BEAM_ENTRIES(beam_mfft)
+#undef BHW_BEAM_ENTRIES
 
 // ---- fused log spectrogram, log-mel and MFCC (include/bhw.h: bhw_logspec_f32_device ..., bhw_logspec_mfft_f32_device ...) -------------
 

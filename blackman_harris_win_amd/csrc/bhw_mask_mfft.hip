@@ -2,6 +2,7 @@
 // kernel, for even n_fft = 2^a 3^b 5^c below 2048 that is no power of two (bhw_mask_mfft_f32_device / _from_table; contract:
 // include/bhw.h, plan: BhwMaskMfftPlan in bhw_plan.h, reasons: DESIGN.md section 42).
 // The same kernel with a complex gain per bin: bhw_cmask_mfft_f32_device / _from_table, k_cmask_mfft_* below.
+// The same kernel over n_ch channels summed behind their gains: bhw_beam_mfft_f32_device / _from_table, k_beam_mfft_* (section 45).
 //
 // The span / ring / flush kernel of bhw_istft_mfft.hip (istft_mfft_spans in bhw_istft_mfft.h) with another frame source: where that
 // kernel loads the bins Y[k], Y[M - k] of a frame from memory, this one forms them in LDS from the signal, as bhw_mask_fft.hip does
@@ -38,6 +39,62 @@ __device__ __forceinline__ void imf_presplit(fft_v2f *z, uint32_t k, uint32_t M,
     if (2u * k != M) z[M - k] = fft_v2f{ex + oy, ox - ey};           // the partner M - k: W[M - k] = -conj W[k]
 }
 
+// Steps a. and b. of a frame source, one text for MaskMfftSourceT and BeamMfftSource below.
+// a. the windowed row of frame f of the signal at xb, into `row` (the caller's barrier follows)
+__device__ __forceinline__ void mask_mfft_row(const ImfftIo &a, bool act, const float *xb, uint64_t samples, uint64_t pad, uint64_t hop,
+                                              uint32_t reflect, uint64_t f, uint32_t l, const float *vS, float *row)
+{
+    const uint32_t n = a.n_fft, lpf = a.lpf;
+    const uint64_t T = samples, t0 = f * hop - pad;              // the (wrapped) time of column 0
+    for (uint32_t j = l; j < n; j += lpf) {
+        const uint32_t k = j - a.col0;                           // unsigned: k < L is the window test
+        float r = 0.0f;
+        if (act && k < a.len) {
+            uint64_t t = t0 + j;                                 // unsigned: t < T is the whole interior test
+            bool zero = false;
+            if (t >= T) {
+                const int64_t ts = (int64_t)t;
+                if (reflect) t = ts < 0 ? (uint64_t)(-ts) : 2 * (T - 1) - t;
+                else {
+                    t = 0;
+                    zero = true;
+                }
+            }
+            const float xv = xb[t];
+            r = (zero ? 0.0f : xv) * vS[k];
+        }
+        row[j] = r;
+    }
+}
+
+// b. the forward passes in the plan's schedule, the walk of stft_mfft_rows around mfft_pass: the transformed points end in src
+__device__ __forceinline__ void mask_mfft_forward(const ImfftIo &a, uint32_t l, const fft_v2f *twf, fft_v2f *&src, fft_v2f *&dst)
+{
+    const uint32_t M = a.m, lpf = a.lpf;
+    uint32_t Ns = 1, rest = M;
+    for (uint32_t p = 0; p < a.passes; ++p) {
+        const uint32_t rdx = (a.sched >> (4u * p)) & 15u;
+        if (rdx == 5u) {
+            rest /= 5u;
+            mfft_pass<5>(src, dst, twf, M, M / 5u, Ns, 2u * rest, l, lpf);
+        } else if (rdx == 3u) {
+            rest /= 3u;
+            mfft_pass<3>(src, dst, twf, M, M / 3u, Ns, 2u * rest, l, lpf);
+        } else if (rdx == 4u) {
+            rest >>= 2;
+            mfft_pass<4>(src, dst, twf, M, M >> 2, Ns, 2u * rest, l, lpf);
+        } else {
+            rest >>= 1;
+            mfft_pass<2>(src, dst, twf, M, M >> 1, Ns, 2u * rest, l, lpf);
+        }
+        __syncthreads();
+        fft_v2f *sw = src;
+        src = dst;
+        dst = sw;
+        Ns *= rdx;
+    }
+}
+
 // G, the gain of a bin: float (bhw_mask_mfft_f32_*) or the pair fft_v2f (gr, gi) (bhw_cmask_mfft_f32_*).  g points to G and the two gain
 // strides count G, so step c. loads gp[k] ascending and gp[M - k] descending as 4-byte words or as 8-byte pairs from the one text of
 // frame(); masked() is overloaded on G.  tests/cpp/san_cmask.cpp replays the pair reads.
@@ -70,57 +127,11 @@ struct MaskMfftSourceT {
     __device__ __forceinline__ void frame(const ImfftIo &a, bool act, uint64_t b, uint64_t f, uint32_t l, const fft_v2f *tw, const float *vS,
                                           fft_v2f *&src, fft_v2f *&dst) const
     {
-        const uint32_t M = a.m, n = a.n_fft, lpf = a.lpf, H = M >> 1;
+        const uint32_t M = a.m, lpf = a.lpf, H = M >> 1;
         const fft_v2f *twf = tw + M;
-        // a. the windowed row
-        {
-            float *row = (float *)src;
-            const float *xb = x + b * x_stride;
-            const uint64_t T = samples, t0 = f * hop - pad;              // the (wrapped) time of column 0
-            for (uint32_t j = l; j < n; j += lpf) {
-                const uint32_t k = j - a.col0;                           // unsigned: k < L is the window test
-                float r = 0.0f;
-                if (act && k < a.len) {
-                    uint64_t t = t0 + j;                                 // unsigned: t < T is the whole interior test
-                    bool zero = false;
-                    if (t >= T) {
-                        const int64_t ts = (int64_t)t;
-                        if (reflect) t = ts < 0 ? (uint64_t)(-ts) : 2 * (T - 1) - t;
-                        else {
-                            t = 0;
-                            zero = true;
-                        }
-                    }
-                    const float xv = xb[t];
-                    r = (zero ? 0.0f : xv) * vS[k];
-                }
-                row[j] = r;
-            }
-        }
+        mask_mfft_row(a, act, x + b * x_stride, samples, pad, hop, reflect, f, l, vS, (float *)src);  // a.
         __syncthreads();
-        // b. the forward passes: the schedule walk of stft_mfft_rows around mfft_pass
-        uint32_t Ns = 1, rest = M;
-        for (uint32_t p = 0; p < a.passes; ++p) {
-            const uint32_t rdx = (a.sched >> (4u * p)) & 15u;
-            if (rdx == 5u) {
-                rest /= 5u;
-                mfft_pass<5>(src, dst, twf, M, M / 5u, Ns, 2u * rest, l, lpf);
-            } else if (rdx == 3u) {
-                rest /= 3u;
-                mfft_pass<3>(src, dst, twf, M, M / 3u, Ns, 2u * rest, l, lpf);
-            } else if (rdx == 4u) {
-                rest >>= 2;
-                mfft_pass<4>(src, dst, twf, M, M >> 2, Ns, 2u * rest, l, lpf);
-            } else {
-                rest >>= 1;
-                mfft_pass<2>(src, dst, twf, M, M >> 1, Ns, 2u * rest, l, lpf);
-            }
-            __syncthreads();
-            fft_v2f *sw = src;
-            src = dst;
-            dst = sw;
-            Ns *= rdx;
-        }
+        mask_mfft_forward(a, l, twf, src, dst);                                                         // b.
         // c. the split, the gains and the pre-split, into the other buffer
         if (act) {
             const G *gp = g + b * g_bstride + f * g_stride;
@@ -139,6 +150,76 @@ struct MaskMfftSourceT {
 };
 using MaskMfftSource = MaskMfftSourceT<float>;
 using CMaskMfftSource = MaskMfftSourceT<fft_v2f>;
+
+// The filter-and-sum source (bhw_beam_mfft_f32_*), BeamSource of bhw_mask_fft.hip for these sizes: n_ch
+// channels of signal b, each with its own pair-gain rows.  frame() runs a. and b. per channel, always from the slot's first buffer, and in c. adds the masked bins of the lane's own k into a
+// running sum in registers (channel 0 sets it: +0 + -0 would lose a sign), in ascending channel order and one float32 add per part.
+// After the last channel the pre-split of the sums goes to the buffer the transformed points are not in, as MaskMfftSourceT's does.
+//   Between channels: step c. reads src[k], src[M - k] and src[0] of the transformed points of OTHER lanes' passes.  With an even
+// pass count they lie in the first buffer, which the next channel's row overwrites: a barrier that every lane reaches, active or
+// not, stands between.  With an odd count they lie in the second buffer; the next row goes to the first, which no lane reads after
+// the last pass's barrier, and the barrier behind that row stands before the first pass writes the second buffer.
+//   A lane owns k = l, l + lpf, ... <= floor(M / 2): at most floor(M / 2) / lpf + 1 <= cpl / 4 + 1 = kMaxK values (the launcher checks it).
+struct BeamMfftSource {
+    static constexpr bool kBins = false;
+    static constexpr uint32_t kTables = 2;
+    static constexpr uint32_t kMaxCpl = CMaskMfftSource::kMaxCpl;
+    static constexpr uint32_t kMaxK = kMaxCpl / 4u + 1u;
+    const float *x;
+    const fft_v2f *g;
+    uint64_t samples, pad, hop, x_stride, x_cstride, g_stride, g_cstride, g_bstride;
+    uint32_t reflect, n_ch;
+
+    __device__ __forceinline__ void tables(fft_v2f *twf, uint32_t k, double cs, double sn) const { twf[k] = fft_v2f{(float)cs, (float)-sn}; }
+
+    __device__ __forceinline__ void frame(const ImfftIo &a, bool act, uint64_t b, uint64_t f, uint32_t l, const fft_v2f *tw, const float *vS,
+                                          fft_v2f *&src, fft_v2f *&dst) const
+    {
+        const uint32_t M = a.m, lpf = a.lpf, H = M >> 1;
+        const fft_v2f *twf = tw + M;
+        fft_v2f *const first = src, *const second = dst;
+        const bool even = (a.passes & 1u) == 0u;
+        fft_v2f sA[kMaxK], sB[kMaxK];                                    // the sums of the masked Y[k] and Y[M - k]
+#pragma unroll
+        for (uint32_t i = 0; i < kMaxK; ++i) sA[i] = sB[i] = fft_v2f{0.0f, 0.0f};
+        for (uint32_t c = 0; c < n_ch; ++c) {
+            src = first;                                                 // every channel ends in the same buffer
+            dst = second;
+            mask_mfft_row(a, act, x + b * x_stride + c * x_cstride, samples, pad, hop, reflect, f, l, vS, (float *)src);   // a.
+            __syncthreads();
+            mask_mfft_forward(a, l, twf, src, dst);                                                                      // b.
+            if (act) {                                                   // c. the split, the gains and the sum
+                const fft_v2f *gp = g + b * g_bstride + c * g_cstride + f * g_stride;
+#pragma unroll
+                for (uint32_t i = 0; i < kMaxK; ++i) {
+#pragma clang fp contract(off)
+                    const uint32_t k = l + i * lpf;
+                    if (k <= H) {
+                        const fft_v2f A = CMaskMfftSource::masked(fft_split_bin(src, twf, k, M), gp[k]);
+                        const fft_v2f B = CMaskMfftSource::masked(fft_split_bin(src, twf, M - k, M), gp[M - k]);
+                        sA[i] = c ? fft_v2f{sA[i].x + A.x, sA[i].y + A.y} : A;
+                        sB[i] = c ? fft_v2f{sB[i].x + B.x, sB[i].y + B.y} : B;
+                    }
+                }
+            }
+            if (even && c + 1u < n_ch) __syncthreads();                  // the next row overwrites the points c. reads
+        }
+        if (act) {                                                       // the pre-split of the sums, into the other buffer
+#pragma unroll
+            for (uint32_t i = 0; i < kMaxK; ++i) {
+#pragma clang fp contract(off)
+                const uint32_t k = l + i * lpf;
+                if (k <= H) {
+                    if (k == 0u) dst[0] = fft_v2f{sA[i].x + sB[i].x, sA[i].x - sB[i].x};
+                    else         imf_presplit(dst, k, M, sA[i], sB[i], tw[k]);
+                }
+            }
+        }
+        fft_v2f *sw = src;                                               // the inverse passes start from Z
+        src = dst;
+        dst = sw;
+    }
+};
 
 // Unhinted, as the parent is: the compiler's own choice is 123 registers a lane, no scratch and four workgroups per CU in all 48
 // instances (the parent, with 16 accumulator pairs per lane, has 156 and three).
@@ -210,6 +291,39 @@ __global__ __launch_bounds__(kFftBlock) void k_cmask_mfft_table(BhwCordicCfg cfg
     istft_mfft_spans(a, m);
 }
 
+// The same two kernels under the filter-and-sum source (bhw_beam_mfft_f32_*): the prologues are the ones above, word for word.
+template <int FORM>
+__global__ __launch_bounds__(kFftBlock) void k_beam_mfft_direct(BhwCordicCfg cfg, BhwWinCfg win, ImfftIo a, BeamMfftSource m, BhwLenPhase lp)
+{
+    using T = std::conditional_t<FORM == 0, int32_t, int64_t>;
+    using L = std::conditional_t<FORM == 2, uint32_t, T>;
+    __shared__ L lut_s[32];
+    if (threadIdx.x < 32) lut_s[threadIdx.x] = (L)cfg.lut[threadIdx.x];
+    __syncthreads();
+    float *vS = (float *)(fft_lds + (size_t)(2u * a.fy + 2u) * a.m * sizeof(fft_v2f));
+    for (uint32_t k = threadIdx.x; k < a.len; k += kFftBlock) {
+        int32_t w;
+        if constexpr (FORM == 2) w = direct_coeff_mad_ph(cfg, win, lut_s, len_theta_of(lp, k));
+        else                     w = direct_coeff_ph<T>(cfg, win, lut_s, len_theta_of(lp, k));
+        vS[k] = fft_coeff(w, a.shift);
+    }
+    istft_mfft_spans(a, m);
+}
+
+template <int FMT, int NT, int MODE>
+__global__ __launch_bounds__(kFftBlock) void k_beam_mfft_table(BhwCordicCfg cfg, BhwWinCfg win, const void *__restrict__ table, ImfftIo a,
+                                                               BeamMfftSource m, BhwLenPhase lp)
+{
+    float *vS = (float *)(fft_lds + (size_t)(2u * a.fy + 2u) * a.m * sizeof(fft_v2f));
+    for (uint32_t k0 = 0; k0 < a.len; k0 += kFftBlock) {
+        const uint32_t k = k0 + threadIdx.x;
+        const bool in = k < a.len;
+        const int32_t w = range_coeff_ph<FMT, NT, MODE>(cfg, win, table, len_theta_of(lp, in ? k : 0u));
+        if (in) vS[k] = fft_coeff(w, a.shift);
+    }
+    istft_mfft_spans(a, m);
+}
+
 } // namespace
 
 // One launcher for both gain types: G float launches k_mask_mfft_*, G fft_v2f (d_g: pairs, the strides in pairs) k_cmask_mfft_*.
@@ -257,4 +371,36 @@ int bhwk_cmask_mfft_f32(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwW
                         const bhw_stft *ss, const float *d_x, const float *d_g, float *d_out, const int32_t *d_table, const BhwLenPhase &lp)
 {
     return mask_mfft_launch<fft_v2f>(l, c_in, w, pl, sa, ss, d_x, (const fft_v2f *)d_g, d_out, d_table, lp);
+}
+
+int bhwk_beam_mfft_f32(const BhwLaunch &l, const BhwCordicCfg &c_in, const BhwWinCfg &w, const BhwBeamMfftPlan &pl, const bhw_stft *sa,
+                       const bhw_stft *ss, const float *d_x, const float *d_g, float *d_out, const int32_t *d_table, const BhwLenPhase &lp)
+{
+    if (!ss->samples) return 0;
+    if (pl.cpl > BeamMfftSource::kMaxCpl || (pl.m >> 1) / pl.lpf + 1u > BeamMfftSource::kMaxK) return (int)hipErrorInvalidValue;   // (no plan has either)
+    hipStream_t st = (hipStream_t)l.stream;
+    ImfftIo a = istft_io<ImfftIo>(pl, ss, nullptr, d_out);
+    a.n_fft = (uint32_t)ss->n_fft;
+    a.m = pl.m;
+    a.passes = pl.passes;
+    for (uint32_t p = 0; p < pl.passes; ++p) a.sched |= (uint32_t)pl.radix[p] << (4u * p);
+    BeamMfftSource m;
+    m.x = d_x;
+    m.g = (const fft_v2f *)d_g;
+    m.samples = sa->samples;
+    m.pad = sa->pad;
+    m.hop = sa->hop;
+    m.x_stride = pl.in_stride;
+    m.x_cstride = pl.x_cstride;
+    m.g_stride = pl.g_stride;
+    m.g_cstride = pl.g_cstride;
+    m.g_bstride = pl.g_bstride;
+    m.reflect = sa->pad_mode == BHW_PAD_REFLECT ? 1u : 0u;
+    m.n_ch = pl.n_ch;
+    const dim3 grid((unsigned)pl.grid), block(kFftBlock);
+    return with_window_source(
+        c_in, w, d_table, [&](auto D) { launch_lds(k_beam_mfft_direct<D>, grid, block, pl.lds_bytes, st, c_in, w, a, m, lp); },
+        [&](auto F, auto NT, auto M, const BhwCordicCfg &c, const void *tab) {
+            launch_lds(k_beam_mfft_table<F, NT, M>, grid, block, pl.lds_bytes, st, c, w, tab, a, m, lp);
+        });
 }

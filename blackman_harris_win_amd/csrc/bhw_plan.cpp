@@ -3183,8 +3183,10 @@ static int mask_fft_agree(const char *field, uint64_t a, uint64_t s)
 // the gain strides, the pointers, their alignment, the extents, the wrap and the overlaps.  g_elem: the bytes of a gain, 4 (a float) or
 // 8 (an interleaved float32 pair (gr, gi)); the gain strides and the gain extent count such elements.  xf: the floats of a sample of d_x
 // and d_out, 1 or 2 (interleaved I/Q: K = n_fft gains a row, and the extents and overlaps of d_x and d_out count two floats a sample).
+// ch: the channel axis of the filter-and-sum calls (bhw_beam_*), nullptr elsewhere: n_ch channels of d_x and of d_g stand inside one
+// signal's stride, the extents of both count them, and d_out holds one signal per group of channels.
 static int mask_tail_checks(const bhw_stft *sa, const bhw_stft *ss, const void *d_x, const void *d_g, uint64_t g_stride, uint64_t g_batch_stride,
-                            const void *d_out, bool pointers, uint32_t g_elem, uint64_t xf = 1)
+                            const void *d_out, bool pointers, uint32_t g_elem, uint64_t xf = 1, const BhwBeamAxis *ch = nullptr)
 {
     const char *unit = g_elem == 8u ? "pairs" : "floats";
     int rc;
@@ -3198,6 +3200,8 @@ static int mask_tail_checks(const bhw_stft *sa, const bhw_stft *ss, const void *
     if ((rc = mask_fft_agree("col0", sa->col0, ss->col0))) return rc;
     if ((rc = mask_fft_agree("shift", sa->shift, ss->shift))) return rc;
     if ((rc = mask_fft_agree("channels", sa->channels, ss->channels))) return rc;
+    if (ch && (ch->n_ch < 1u || ch->n_ch > BHW_BEAM_MAX_CH))
+        return bhwp_fail(BHW_ERR_BADARG, "n_ch %u: 1..%u channels a signal", ch->n_ch, (unsigned)BHW_BEAM_MAX_CH);
     if (!ss->samples) return BHW_OK;
     // (samples > 0: the inverse checks have refused frames 0, and with frames > 0 the forward ones samples 0 of the analysis side)
     const uint64_t K = xf == 2 ? ss->n_fft : ss->n_fft / 2 + 1, F = ss->frames, Bn = ss->batch;
@@ -3206,9 +3210,30 @@ static int mask_tail_checks(const bhw_stft *sa, const bhw_stft *ss, const void *
                          (unsigned long long)K, unit);
     const unsigned __int128 gsig = (unsigned __int128)(F - 1) * g_stride + K;                // the gain rows of one signal
     if (gsig > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "g extent beyond 2^60 elements");
-    if (g_batch_stride && g_batch_stride < (uint64_t)gsig)
-        return bhwp_fail(BHW_ERR_BADARG, "g_batch_stride %llu: 0 (the same gains for every signal) or at least (frames - 1) * g_stride + K = "
-                         "%llu %s", (unsigned long long)g_batch_stride, (unsigned long long)(uint64_t)gsig, unit);
+    const uint64_t C1 = ch ? ch->n_ch - 1u : 0, xcs = ch ? (ch->x_ch_stride ? ch->x_ch_stride : sa->samples) : 0, gcs = ch ? ch->g_ch_stride : 0;
+    unsigned __int128 gall = gsig;                                                          // the gain rows of one signal, every channel
+    if (ch) {
+        if (ch->x_ch_stride && ch->x_ch_stride < sa->samples)
+            return bhwp_fail(BHW_ERR_BADARG, "x_ch_stride %llu: 0 (packed channels) or at least the analysis samples %llu",
+                             (unsigned long long)ch->x_ch_stride, (unsigned long long)sa->samples);
+        const unsigned __int128 xall = (unsigned __int128)C1 * xcs + sa->samples;           // the channels of one signal
+        if (xall > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "x extent beyond 2^60 elements");
+        if (sa->x_stride && sa->x_stride < (uint64_t)xall)
+            return bhwp_fail(BHW_ERR_BADARG, "x_stride %llu of the analysis descriptor: 0 (n_ch channel strides) or at least (n_ch - 1) * "
+                             "x_ch_stride + samples = %llu", (unsigned long long)sa->x_stride, (unsigned long long)(uint64_t)xall);
+        if (C1 && !gcs)
+            return bhwp_fail(BHW_ERR_BADARG, "g_ch_stride 0 with n_ch %u: the same weights on every channel are a sum of the channels of x "
+                             "before bhw_cmask_*; the fused beamformer takes a gain row per channel", ch->n_ch);
+        if (gcs && gcs < (uint64_t)gsig)
+            return bhwp_fail(BHW_ERR_BADARG, "g_ch_stride %llu: at least (frames - 1) * g_stride + K = %llu %s", (unsigned long long)gcs,
+                             (unsigned long long)(uint64_t)gsig, unit);
+        gall = (unsigned __int128)C1 * gcs + gsig;
+        if (gall > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "g extent beyond 2^60 elements");
+    }
+    if (g_batch_stride && g_batch_stride < (uint64_t)gall)
+        return bhwp_fail(BHW_ERR_BADARG, "g_batch_stride %llu: 0 (the same gains for every signal) or at least %s(frames - 1) * g_stride + K = "
+                         "%llu %s", (unsigned long long)g_batch_stride, ch ? "(n_ch - 1) * g_ch_stride + " : "",
+                         (unsigned long long)(uint64_t)gall, unit);
     if (!pointers) return BHW_OK;
     if (!d_x || !d_g || !d_out) return bhwp_fail(BHW_ERR_BADARG, "d_x / d_g / d_out is NULL");
     if ((uintptr_t)d_x % 4) return bhwp_fail(BHW_ERR_BADARG, "d_x is not 4-byte aligned");
@@ -3216,9 +3241,10 @@ static int mask_tail_checks(const bhw_stft *sa, const bhw_stft *ss, const void *
         return bhwp_fail(BHW_ERR_BADARG, "d_g is not 8-byte aligned: the gains are interleaved float32 pairs (gr, gi), read as 8-byte words");
     if ((uintptr_t)d_g % 4) return bhwp_fail(BHW_ERR_BADARG, "d_g is not 4-byte aligned");
     if ((uintptr_t)d_out % 4) return bhwp_fail(BHW_ERR_BADARG, "d_out is not 4-byte aligned");
-    const uint64_t xs = sa->x_stride ? sa->x_stride : xf * sa->samples, os = ss->x_stride ? ss->x_stride : xf * ss->samples;
-    const unsigned __int128 xe = (unsigned __int128)(Bn - 1) * xs + xf * sa->samples, oe = (unsigned __int128)(Bn - 1) * os + xf * ss->samples;
-    const unsigned __int128 ge = (unsigned __int128)(Bn - 1) * g_batch_stride + gsig;
+    const uint64_t xs = sa->x_stride ? sa->x_stride : ch ? ch->n_ch * xcs : xf * sa->samples, os = ss->x_stride ? ss->x_stride : xf * ss->samples;
+    const unsigned __int128 xe = (unsigned __int128)(Bn - 1) * xs + (unsigned __int128)C1 * xcs + xf * sa->samples;
+    const unsigned __int128 oe = (unsigned __int128)(Bn - 1) * os + xf * ss->samples;
+    const unsigned __int128 ge = (unsigned __int128)(Bn - 1) * g_batch_stride + gall;
     if (xe > (1ull << 60) || ge > (1ull << 60) || oe > (1ull << 60)) return bhwp_fail(BHW_ERR_BADARG, "x, g or out extent beyond 2^60 elements");
     const uint64_t xa = (uint64_t)(uintptr_t)d_x, ga = (uint64_t)(uintptr_t)d_g, oa = (uint64_t)(uintptr_t)d_out;
     const uint64_t xb = (uint64_t)xe * 4u, gb = (uint64_t)ge * g_elem, ob = (uint64_t)oe * 4u;
@@ -3233,29 +3259,32 @@ static int mask_tail_checks(const bhw_stft *sa, const bhw_stft *ss, const void *
 // The checks of both gain types of the power-of-two family.  g_elem 4: bhw_mask_fft_f32_*, in the words they had; g_elem 8:
 // bhw_cmask_fft_f32_*, whose refusals are the same sentences about "the fused complex-gain mask" and name bhw_cmask_mfft_f32_* for the
 // mixed-radix lengths it takes.
+// ch: bhw_beam_fft_f32_* (g_elem 8), about "the fused beamformer" and naming bhw_beam_mfft_f32_*.
 static int mask_fft_checks_of(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const void *d_x,
-                              const void *d_g, uint64_t g_stride, uint64_t g_batch_stride, const void *d_out, bool pointers, uint32_t g_elem)
+                              const void *d_g, uint64_t g_stride, uint64_t g_batch_stride, const void *d_out, bool pointers, uint32_t g_elem,
+                              const BhwBeamAxis *ch = nullptr)
 {
     int rc = bhwp_f32_checks(p, length, flags);
     if (rc) return rc;
-    const char *cg = g_elem == 8u ? "complex-gain " : "";
+    const char *cg = ch ? "beamformer" : g_elem == 8u ? "complex-gain mask" : "mask";
+    const char *mixed_call = ch ? "bhw_beam_mfft_f32_*" : "bhw_cmask_mfft_f32_*";
     // the routes that take what this call does not: named before the parents refuse the same input in their own words
     for (const bhw_stft *s : {sa, ss}) {
         if (!s || s->struct_size != sizeof(bhw_stft)) continue;
         const char *which = s == sa ? "analysis" : "synthesis";
         if (s->channels == 2)
-            return bhwp_fail(BHW_ERR_UNSUPPORTED, "channels 2 (%s descriptor): the fused %smask takes real input and gives real output; "
+            return bhwp_fail(BHW_ERR_UNSUPPORTED, "channels 2 (%s descriptor): the fused %s takes real input and gives real output; "
                              "bhw_stft_cfft_f32_* + bhw_istft_cfft_f32_* take I/Q", which, cg);
         if (s->n_fft == (1ull << kFftMaxLog))
-            return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu (%s descriptor): the fused %smask takes a power of two in %u..%u; "
+            return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu (%s descriptor): the fused %s takes a power of two in %u..%u; "
                              "bhw_stft_fft_f32_* + bhw_istft_fft_f32_* take %llu", (unsigned long long)s->n_fft, which, cg, 1u << kFftMinLog,
                              1u << kMaskFftMaxLog, (unsigned long long)s->n_fft);
         if (g_elem == 8u && (s->n_fft & (s->n_fft - 1)) && s->n_fft <= kMaskMfftMaxN && bhwp_mfft_supported(s->n_fft))
-            return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu (%s descriptor): the fused %smask takes a power of two in %u..%u; "
-                             "bhw_cmask_mfft_f32_* takes the mixed-radix lengths up to %u", (unsigned long long)s->n_fft, which, cg,
-                             1u << kFftMinLog, 1u << kMaskFftMaxLog, kMaskMfftMaxN);
+            return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu (%s descriptor): the fused %s takes a power of two in %u..%u; "
+                             "%s takes the mixed-radix lengths up to %u", (unsigned long long)s->n_fft, which, cg, 1u << kFftMinLog,
+                             1u << kMaskFftMaxLog, mixed_call, kMaskMfftMaxN);
         if ((s->n_fft & (s->n_fft - 1)) && bhwp_mfft_supported(s->n_fft))
-            return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu (%s descriptor): the fused %smask takes a power of two in %u..%u; "
+            return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu (%s descriptor): the fused %s takes a power of two in %u..%u; "
                              "bhw_stft_mfft_f32_* + bhw_istft_mfft_f32_* take the mixed-radix lengths", (unsigned long long)s->n_fft, which, cg,
                              1u << kFftMinLog, 1u << kMaskFftMaxLog);
     }
@@ -3265,7 +3294,7 @@ static int mask_fft_checks_of(const bhw_params *p, uint64_t length, const bhw_st
     if (rc) return rc;
     rc = bhwp_istft_fft_checks(p, length, packed_strides(ss, ts), flags, nullptr, nullptr, false);
     if (rc) return rc;
-    return mask_tail_checks(sa, ss, d_x, d_g, g_stride, g_batch_stride, d_out, pointers, g_elem);
+    return mask_tail_checks(sa, ss, d_x, d_g, g_stride, g_batch_stride, d_out, pointers, g_elem, 1, ch);
 }
 
 int bhwp_mask_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const void *d_x,
@@ -3303,14 +3332,15 @@ struct MaskLine {
 template <typename ParentOf>
 static int describe_mask(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
                          uint64_t g_stride, uint64_t g_batch_stride, bool pairs, const char *family, const char *k_direct, const char *k_table,
-                         char *buf, uint64_t len, ParentOf parent_of, bool iq = false)
+                         char *buf, uint64_t len, ParentOf parent_of, bool iq = false, const BhwBeamAxis *ch = nullptr)
 {
-    const char *c = pairs ? "c" : "", *cg = pairs ? "complex " : "";      // "cmask ...", "complex gains: ..." (strides in pairs)
+    // "cmask ...", "complex gains: ..." (strides in pairs); with a channel axis "beam ..." and the three gain strides behind "channels C"
+    const char *c = ch ? "beam" : pairs ? "cmask" : "mask", *cg = pairs ? "complex " : "";
     if (!buf || !len) return bhwp_fail(BHW_ERR_BADARG, "buf is NULL or empty");
     const char *route = ct ? "table" : "direct";
     const char *norm = (flags & BHW_OLA_NORMALIZE) ? "normalised by the window envelope" : "not normalised";
     if (!ss->samples) {
-        snprintf(buf, len, "%smask %s %s (L = %llu, n_fft %llu), %s: nothing (samples 0)", c, family, route, (unsigned long long)length,
+        snprintf(buf, len, "%s %s %s (L = %llu, n_fft %llu), %s: nothing (samples 0)", c, family, route, (unsigned long long)length,
                  (unsigned long long)ss->n_fft, norm);
         return BHW_OK;
     }
@@ -3319,7 +3349,10 @@ static int describe_mask(const bhw_params *p, const BhwCordicCfg *ct, uint64_t l
     if (ml.rc) return ml.rc;
     char kern[64], gains[200];
     kernel_name(p, ct, k_direct, k_table, false, kern, sizeof kern);
-    if (!g_stride && !g_batch_stride) snprintf(gains, sizeof gains, "one gain row for every frame and every signal");
+    if (ch)
+        snprintf(gains, sizeof gains, "channels %u, g_stride %llu, g_ch_stride %llu, g_batch_stride %llu", ch->n_ch, (unsigned long long)g_stride,
+                 (unsigned long long)ch->g_ch_stride, (unsigned long long)g_batch_stride);
+    else if (!g_stride && !g_batch_stride) snprintf(gains, sizeof gains, "one gain row for every frame and every signal");
     else if (!g_stride) snprintf(gains, sizeof gains, "one gain row for every frame, g_batch_stride %llu", (unsigned long long)g_batch_stride);
     else if (!g_batch_stride) snprintf(gains, sizeof gains, "g_stride %llu, one set of gain rows for every signal", (unsigned long long)g_stride);
     else snprintf(gains, sizeof gains, "g_stride %llu, g_batch_stride %llu", (unsigned long long)g_stride, (unsigned long long)g_batch_stride);
@@ -3334,7 +3367,7 @@ static int describe_mask(const bhw_params *p, const BhwCordicCfg *ct, uint64_t l
     while (lds && lds > fields && lds[-1] != ' ') --lds;
     if (!lds) return bhwp_fail(BHW_ERR_BADARG, "buf: the inverse describe line has no plan fields");
     const char *pad = sa->pad_mode == BHW_PAD_REFLECT ? "reflect" : "constant";
-    snprintf(buf, len, "%smask %s %s (L = %llu, n_fft %llu, col0 %llu, pad %llu: t0 = %llu; analysis of %llu samples, pad %llu %s), %s: %s, "
+    snprintf(buf, len, "%s %s %s (L = %llu, n_fft %llu, col0 %llu, pad %llu: t0 = %llu; analysis of %llu samples, pad %llu %s), %s: %s, "
              "forward + inverse FFT, %sgains: %s, %.*s%u%s", c, family, route, (unsigned long long)length, (unsigned long long)ss->n_fft,
              (unsigned long long)ss->col0, (unsigned long long)ss->pad, (unsigned long long)ml.t0, (unsigned long long)sa->samples,
              (unsigned long long)sa->pad, pad, norm, kern, cg, gains, (int)(lds - fields), fields, ml.lds_bytes, lds_end);
@@ -3370,30 +3403,33 @@ int bhwp_describe_cmask_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64_
 
 // The checks of both gain types of the mixed-radix family, as mask_fft_checks_of is the power-of-two one: g_elem 8 names
 // bhw_cmask_fft_f32_* for a power of two.
+// ch: bhw_beam_mfft_f32_* (g_elem 8), about "the mixed-radix fused beamformer" and naming bhw_beam_fft_f32_*.
 static int mask_mfft_checks_of(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const void *d_x,
-                               const void *d_g, uint64_t g_stride, uint64_t g_batch_stride, const void *d_out, bool pointers, uint32_t g_elem)
+                               const void *d_g, uint64_t g_stride, uint64_t g_batch_stride, const void *d_out, bool pointers, uint32_t g_elem,
+                               const BhwBeamAxis *ch = nullptr)
 {
     int rc = bhwp_f32_checks(p, length, flags);
     if (rc) return rc;
-    const char *cg = g_elem == 8u ? "complex-gain " : "", *pow2_call = g_elem == 8u ? "bhw_cmask_fft_f32_*" : "bhw_mask_fft_f32_*";
+    const char *cg = ch ? "beamformer" : g_elem == 8u ? "complex-gain mask" : "mask";
+    const char *pow2_call = ch ? "bhw_beam_fft_f32_*" : g_elem == 8u ? "bhw_cmask_fft_f32_*" : "bhw_mask_fft_f32_*";
     // the routes that take what this call does not: named before the parents refuse the same input in their own words
     for (const bhw_stft *s : {sa, ss}) {
         if (!s || s->struct_size != sizeof(bhw_stft)) continue;
         const char *which = s == sa ? "analysis" : "synthesis";
         const bool pow2 = s->n_fft && !(s->n_fft & (s->n_fft - 1));
         if (s->channels == 2)
-            return bhwp_fail(BHW_ERR_UNSUPPORTED, "channels 2 (%s descriptor): the mixed-radix fused %smask takes real input and gives real "
+            return bhwp_fail(BHW_ERR_UNSUPPORTED, "channels 2 (%s descriptor): the mixed-radix fused %s takes real input and gives real "
                              "output; bhw_stft_cmfft_f32_* + bhw_istft_cmfft_f32_* take I/Q", which, cg);
         if (pow2 && s->n_fft >= (1ull << kFftMinLog) && s->n_fft <= (1ull << kMaskFftMaxLog))
             return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu (%s descriptor) is a power of two: %s takes it; the mixed-radix "
-                             "fused %smask takes an even 2^a 3^b 5^c in %u..%u", (unsigned long long)s->n_fft, which, pow2_call, cg, kMfftMinN,
+                             "fused %s takes an even 2^a 3^b 5^c in %u..%u", (unsigned long long)s->n_fft, which, pow2_call, cg, kMfftMinN,
                              kMaskMfftMaxN);
         if (s->n_fft == (1ull << kFftMaxLog))
             return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu (%s descriptor) is a power of two: bhw_stft_fft_f32_* + bhw_istft_fft_f32_* "
-                             "take it; the mixed-radix fused %smask takes an even 2^a 3^b 5^c in %u..%u", (unsigned long long)s->n_fft, which,
+                             "take it; the mixed-radix fused %s takes an even 2^a 3^b 5^c in %u..%u", (unsigned long long)s->n_fft, which,
                              cg, kMfftMinN, kMaskMfftMaxN);
         if (s->n_fft > kMaskMfftMaxN && bhwp_mfft_supported(s->n_fft))
-            return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu (%s descriptor): the mixed-radix fused %smask takes an even 2^a 3^b 5^c in "
+            return bhwp_fail(BHW_ERR_UNSUPPORTED, "n_fft %llu (%s descriptor): the mixed-radix fused %s takes an even 2^a 3^b 5^c in "
                              "%u..%u; bhw_stft_mfft_f32_* + bhw_istft_mfft_f32_* take the larger ones", (unsigned long long)s->n_fft, which,
                              cg, kMfftMinN, kMaskMfftMaxN);
     }
@@ -3403,7 +3439,7 @@ static int mask_mfft_checks_of(const bhw_params *p, uint64_t length, const bhw_s
     if (rc) return rc;
     rc = bhwp_istft_mfft_checks(p, length, packed_strides(ss, ts), flags, nullptr, nullptr, false);
     if (rc) return rc;
-    return mask_tail_checks(sa, ss, d_x, d_g, g_stride, g_batch_stride, d_out, pointers, g_elem);
+    return mask_tail_checks(sa, ss, d_x, d_g, g_stride, g_batch_stride, d_out, pointers, g_elem, 1, ch);
 }
 
 int bhwp_mask_mfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const void *d_x,
@@ -3453,6 +3489,68 @@ int bhwp_describe_cmask_mfft(const bhw_params *p, const BhwCordicCfg *ct, uint64
                              uint32_t flags, uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len)
 {
     return describe_mask_mfft_of(p, ct, length, sa, ss, flags, g_stride, g_batch_stride, true, buf, len);
+}
+
+// ---- fused multichannel filter-and-sum: the complex-gain mask's checks, plan and line with the channel axis --------------------------------
+
+int bhwp_beam_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const void *d_x,
+                         const BhwBeamAxis &ch, const void *d_g, uint64_t g_stride, uint64_t g_batch_stride, const void *d_out, bool pointers)
+{
+    return mask_fft_checks_of(p, length, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out, pointers, 8u, &ch);
+}
+
+BhwBeamFftPlan bhwp_beam_fft_plan(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
+                                  const BhwBeamAxis &ch, uint64_t g_stride, uint64_t g_batch_stride, bool from_table)
+{
+    BhwBeamFftPlan pl{};
+    static_cast<BhwMaskFftPlan &>(pl) = bhwp_mask_fft_plan(p, length, sa, ss, flags, g_stride, g_batch_stride, from_table);
+    pl.n_ch = ch.n_ch;
+    pl.x_cstride = ch.x_ch_stride ? ch.x_ch_stride : sa->samples;
+    pl.g_cstride = ch.g_ch_stride;
+    pl.in_stride = sa->x_stride ? sa->x_stride : ch.n_ch * pl.x_cstride;
+    return pl;
+}
+
+int bhwp_describe_beam_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *sa, const bhw_stft *ss,
+                           uint32_t flags, const BhwBeamAxis &ch, uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len)
+{
+    return describe_mask(p, ct, length, sa, ss, flags, g_stride, g_batch_stride, true, "fft", "k_beam_fft_direct", "k_beam_fft_table", buf, len,
+                         [&](char *parent, uint64_t size) {
+                             const int rc = bhwp_describe_istft_fft(p, ct, length, ss, flags, parent, size);
+                             if (rc) return MaskLine{rc, 0, 0};
+                             const BhwBeamFftPlan pl = bhwp_beam_fft_plan(p, length, sa, ss, flags, ch, g_stride, g_batch_stride, ct != nullptr);
+                             return MaskLine{0, pl.t0, pl.lds_bytes};
+                         }, false, &ch);
+}
+
+int bhwp_beam_mfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const void *d_x,
+                         const BhwBeamAxis &ch, const void *d_g, uint64_t g_stride, uint64_t g_batch_stride, const void *d_out, bool pointers)
+{
+    return mask_mfft_checks_of(p, length, sa, ss, flags, d_x, d_g, g_stride, g_batch_stride, d_out, pointers, 8u, &ch);
+}
+
+BhwBeamMfftPlan bhwp_beam_mfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
+                                  const BhwBeamAxis &ch, uint64_t g_stride, uint64_t g_batch_stride, bool from_table)
+{
+    BhwBeamMfftPlan pl{};
+    static_cast<BhwMaskMfftPlan &>(pl) = bhwp_mask_mfft_plan(p, length, sa, ss, flags, g_stride, g_batch_stride, from_table);
+    pl.n_ch = ch.n_ch;
+    pl.x_cstride = ch.x_ch_stride ? ch.x_ch_stride : sa->samples;
+    pl.g_cstride = ch.g_ch_stride;
+    pl.in_stride = sa->x_stride ? sa->x_stride : ch.n_ch * pl.x_cstride;
+    return pl;
+}
+
+int bhwp_describe_beam_mfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *sa, const bhw_stft *ss,
+                           uint32_t flags, const BhwBeamAxis &ch, uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len)
+{
+    return describe_mask(p, ct, length, sa, ss, flags, g_stride, g_batch_stride, true, "mfft", "k_beam_mfft_direct", "k_beam_mfft_table", buf, len,
+                         [&](char *parent, uint64_t size) {
+                             const int rc = bhwp_describe_istft_mfft(p, ct, length, ss, flags, parent, size);
+                             if (rc) return MaskLine{rc, 0, 0};
+                             const BhwBeamMfftPlan pl = bhwp_beam_mfft_plan(p, length, sa, ss, flags, ch, g_stride, g_batch_stride, ct != nullptr);
+                             return MaskLine{0, pl.t0, pl.lds_bytes};
+                         }, false, &ch);
 }
 
 // ---- fused inverse mixed-radix FFT, window and overlap-add ----------------------------------------------------------------------------------

@@ -1014,6 +1014,46 @@ int  bhwp_describe_cmask_mfft(const bhw_params *p, const BhwCordicCfg *ct, uint6
 int  bhwk_cmask_mfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwMaskMfftPlan &pl, const bhw_stft *sa,
                          const bhw_stft *ss, const float *d_x, const float *d_g, float *d_out, const int32_t *d_table, const BhwLenPhase &lp);
 
+// ---- fused multichannel filter-and-sum (bhw_beam_fft_f32_*, bhw_beam_mfft_f32_*; k_beam_* in bhw_mask_fft.hip / bhw_mask_mfft.hip;
+// ---- DESIGN.md section 45) --------------------------------------------------------------------------------------------------------------
+// The complex-gain mask over n_ch channels of each signal, summed per bin before the one inverse transform.  The channel axis of a
+// call: the channel count and the strides between the channels of one signal, of d_x in floats (0: the analysis samples) and of d_g
+// in pairs.
+struct BhwBeamAxis {
+    uint32_t n_ch;
+    uint64_t x_ch_stride, g_ch_stride;
+};
+// The plans ARE bhwp_mask_fft_plan's / bhwp_mask_mfft_plan's for the B output signals, field for field (the sums live in registers:
+// lanes, spans, columns per lane and LDS do not change), beside the channel axis resolved; in_stride 0 resolves to n_ch channel strides.
+struct BhwBeamFftPlan : BhwMaskFftPlan {
+    uint32_t n_ch;
+    uint64_t x_cstride, g_cstride;
+};
+struct BhwBeamMfftPlan : BhwMaskMfftPlan {
+    uint32_t n_ch;
+    uint64_t x_cstride, g_cstride;
+};
+// The checks of bhwp_cmask_[m]fft_checks in their order, about "the fused beamformer", with the channel axis: n_ch and the channel
+// strides behind the fields that must agree, extents with the channel axis, d_out against every channel of d_x and against d_g.
+int  bhwp_beam_fft_checks(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const void *d_x,
+                          const BhwBeamAxis &ch, const void *d_g, uint64_t g_stride, uint64_t g_batch_stride, const void *d_out,
+                          bool pointers = true);
+int  bhwp_beam_mfft_checks(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags, const void *d_x,
+                           const BhwBeamAxis &ch, const void *d_g, uint64_t g_stride, uint64_t g_batch_stride, const void *d_out,
+                           bool pointers = true);
+BhwBeamFftPlan  bhwp_beam_fft_plan(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
+                                   const BhwBeamAxis &ch, uint64_t g_stride, uint64_t g_batch_stride, bool from_table);
+BhwBeamMfftPlan bhwp_beam_mfft_plan(const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
+                                    const BhwBeamAxis &ch, uint64_t g_stride, uint64_t g_batch_stride, bool from_table);
+int  bhwp_describe_beam_fft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *sa, const bhw_stft *ss,
+                            uint32_t flags, const BhwBeamAxis &ch, uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len);
+int  bhwp_describe_beam_mfft(const bhw_params *p, const BhwCordicCfg *ct, uint64_t length, const bhw_stft *sa, const bhw_stft *ss,
+                             uint32_t flags, const BhwBeamAxis &ch, uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len);
+int  bhwk_beam_fft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwBeamFftPlan &pl, const bhw_stft *sa,
+                       const bhw_stft *ss, const float *d_x, const float *d_g, float *d_out, const int32_t *d_table, const BhwLenPhase &lp);
+int  bhwk_beam_mfft_f32(const BhwLaunch &l, const BhwCordicCfg &c, const BhwWinCfg &w, const BhwBeamMfftPlan &pl, const bhw_stft *sa,
+                        const bhw_stft *ss, const float *d_x, const float *d_g, float *d_out, const int32_t *d_table, const BhwLenPhase &lp);
+
 // ---- fused inverse complex FFT, window and overlap-add for I/Q output (bhw_istft_cfft_f32_*; bhw_istft_cfft.hip) ----------------------
 // The lane layout and the passes of bhwp_stft_cfft_plan (lpf lanes along a row of n = n_fft complex points, fy slots side by side,
 // cpl complex columns per lane) under the span plan (BhwIstftRuns: the same S, halo, trips, halo_bound, grid cap and hop clamp, the

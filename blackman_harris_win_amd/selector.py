@@ -1084,6 +1084,168 @@ def stft_cmask_istft_mixed(params, x, mask, n_fft, hop, *, win_length=None, cent
                             _mfft_input, "bhw_cmask_mfft_f32_device", "bhw_cmask_mfft_f32_from_table", True)
 
 
+# ---- multichannel filter-and-sum: an STFT per channel, a complex weight per channel and bin, one inverse STFT ------------------------------
+
+def _beam_refusals(torch, x, weights, n_fft, mixed):
+    """What stft_beamform_istft() (mixed False) and stft_beamform_istft_mixed() (mixed True) do not take, refused naming what does,
+    before any check that needs a device."""
+    what = "the mixed-radix fused beamformer" if mixed else "the fused beamformer"
+    tail = "_mixed" if mixed else ""
+    if isinstance(weights, torch.Tensor) and not weights.is_complex():
+        raise ValueError(f"{what} takes complex64 weights, got {weights.dtype}: real gains per channel are not built (weights.to(torch.complex64) "
+                         f"applies them; bhw.stft_mask_istft{tail} takes real gains on one channel)")
+    if isinstance(x, torch.Tensor) and x.is_complex():
+        raise ValueError(f"{what} takes real float32 input, got {x.dtype}: the I/Q beamformer is not built (bhw.stft_cmask_istft_iq{tail} per "
+                         f"channel and a sum over the channels take it)")
+    n = int(n_fft)
+    if mixed:
+        if B.mask_fft_supported(n):
+            raise ValueError(f"n_fft {n} is a power of two: bhw.stft_beamform_istft takes it (one transform per n_fft)")
+        if B.fft_supported(n):
+            raise ValueError(f"n_fft {n} is a power of two above {B.MASK_FFT_MAX_N}: bhw.stft, the weights and a sum over the channels, and "
+                             f"bhw.istft take it")
+        if n > B.MASK_MFFT_MAX_N and B.mfft_supported(n):
+            raise ValueError(f"{what} takes n_fft even 2^a·3^b·5^c in {B.MFFT_MIN_N}..{B.MASK_MFFT_MAX_N}, got {n} (bhw.stft_mixed, the "
+                             f"weights and a sum over the channels, and bhw.istft_mixed take it)")
+    else:
+        if B.mask_mfft_supported(n):
+            raise ValueError(f"{what} takes n_fft a power of two in {B.FFT_MIN_N}..{B.MASK_FFT_MAX_N}, got {n} (a mixed-radix n_fft: "
+                             f"bhw.stft_beamform_istft_mixed takes it)")
+        if n > 0 and n & (n - 1) and B.mfft_supported(n):
+            raise ValueError(f"{what} takes n_fft a power of two in {B.FFT_MIN_N}..{B.MASK_FFT_MAX_N}, got {n} (bhw.stft_mixed, the weights "
+                             f"and a sum over the channels, and bhw.istft_mixed take it)")
+        if B.fft_supported(n) and not B.mask_fft_supported(n):
+            raise ValueError(f"{what} takes n_fft a power of two in {B.FFT_MIN_N}..{B.MASK_FFT_MAX_N}, got {n} (bhw.stft, the weights and a "
+                             f"sum over the channels, and bhw.istft take it)")
+    if isinstance(x, torch.Tensor) and x.dim() not in (2, 3):
+        raise ValueError(f"x must be (C, T) or (B, C, T), got {tuple(x.shape)}")
+    if isinstance(x, torch.Tensor) and not 1 <= x.shape[-2] <= B.BEAM_MAX_CH:
+        raise ValueError(f"x has {x.shape[-2]} channels: the fused beamformer takes 1..{B.BEAM_MAX_CH}")
+    if isinstance(x, torch.Tensor) and isinstance(weights, torch.Tensor):
+        C = x.shape[-2]
+        if weights.dim() not in (2, 3, 4):
+            raise ValueError(f"weights must be (C, K), (C, F, K) or (1 | B, C, 1 | F, K), got {tuple(weights.shape)}")
+        ch = weights.dim() - (2 if weights.dim() == 2 else 3)
+        if C > 1 and (weights.shape[ch] == 1 or (weights.shape[ch] == C and weights.stride(ch) == 0)):
+            raise ValueError("weights are broadcast along the channels: the same weights on every channel are x.sum over the channels "
+                             f"and bhw.stft_cmask_istft{tail}; the fused beamformer takes a row per channel")
+        if weights.shape[ch] != C:
+            raise ValueError(f"weights {tuple(weights.shape)} have {weights.shape[ch]} channels, x has {C}")
+
+
+def _beam_gains(torch, weights, nb, C, frames, K, dev):
+    """The weights as the kernel reads them: (the tensor read, g_stride, g_ch_stride, g_batch_stride), the strides in (re, im) pairs
+    as torch counts them.  weights: complex64 (C, K), (C, F, K) or (1 | B, C, 1 | F, K), the last axis contiguous.  A batch or frame
+    axis of size 1 or of stride 0 (an expand() view) becomes a zero stride and is never materialised; rows that overlap in memory some
+    other way are copied first.  A lazy conjugate is resolved first."""
+    if not isinstance(weights, torch.Tensor) or weights.dtype != torch.complex64 or not weights.is_cuda or weights.device.index != dev:
+        raise ValueError("weights must be a complex64 CUDA tensor on the call's device")
+    m = weights.resolve_conj().resolve_neg()
+    if m.dim() == 2:
+        m = m.unsqueeze(1)
+    if m.dim() == 3:
+        m = m.unsqueeze(0)
+    if m.shape[0] not in (1, nb) or m.shape[1] != C or m.shape[2] not in (1, frames) or m.shape[3] != K:
+        raise ValueError(f"weights {tuple(weights.shape)} do not broadcast to (B, C, F, K) = {(nb, C, frames, K)} (K = n_fft // 2 + 1)")
+    if K > 1 and m.stride(3) != 1:
+        raise ValueError("weights must be contiguous along their last axis (the bins)")
+
+    def strides(t):
+        return t.stride(2) if t.shape[2] > 1 else 0, t.stride(1) if C > 1 else 0, t.stride(0) if t.shape[0] > 1 else 0
+    gs, gcs, gbs = strides(m)
+    rows = (frames - 1) * gs + K
+    if (gs and gs < K) or (C > 1 and gcs < rows) or (gbs and gbs < (C - 1) * gcs + rows):
+        m = m.contiguous()
+        gs, gcs, gbs = strides(m)
+    return m, gs, gcs, gbs
+
+
+def _stft_beamform_istft(torch, params, x, weights, n_fft, hop, win_length, center, pad_mode, length, normalize, shift, out, table, check,
+                         device_call, table_call):
+    """What the two beamformer calls share after their refusals: the input checks on one signal's channels (check: _fft_input or
+    _mfft_input), the channel axis of x and of the weights, the two descriptors and the one call."""
+    if table is not None:
+        if not isinstance(table, ResidentTable):
+            raise ValueError("table must be a ResidentTable or None")
+        dev, handle = table.device, table._live()
+    else:
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise ValueError("x must be a float32 CUDA tensor")
+        dev, handle = x.device.index, None
+    if not isinstance(x, torch.Tensor) or x.dim() not in (2, 3):
+        raise ValueError("x must be (C, T) or (B, C, T)")
+    x3 = x if x.dim() == 3 else x.unsqueeze(0)
+    if x3.shape[0] < 1:
+        raise ValueError("zero signals")
+    n_fft, L, _, C, T, frames, d = _stft_front(torch, params, x3[0], n_fft, hop, win_length, center, pad_mode, False, dev, check)
+    if not center and L < n_fft:
+        raise ValueError("center=False with win_length < n_fft: the first outputs have no window under them")
+    nb = x3.shape[0]
+    xcs = x3.stride(1) if C > 1 else T
+    if (T > 1 and x3.stride(2) != 1) or (C > 1 and xcs < T) or (nb > 1 and x3.stride(0) < (C - 1) * xcs + T):
+        x3 = x3.contiguous()
+        xcs = T
+    K = n_fft // 2 + 1
+    g, gs, gcs, gbs = _beam_gains(torch, weights, nb, C, frames, K, dev)
+    length = T if length is None else int(length)
+    if length < 0:
+        raise ValueError(f"length {length} < 0")
+    out = _stft_out(torch, out, (nb, length) if x.dim() == 3 else (length,), x, "x")
+    shift = params.dat_width - 1 if shift is None else int(shift)
+    sa = B.make_stft(nb, T, frames, d["hop"], n_fft, col0=d["col0"], pad=d["pad"], pad_mode=d["pad_mode"], shift=shift,
+                     x_stride=x3.stride(0) if nb > 1 else 0)
+    ss = B.make_stft(nb, length, frames, d["hop"], n_fft, col0=d["col0"], pad=d["pad"], shift=shift)
+    tail = (ctypes.byref(sa), ctypes.byref(ss), B.OLA_NORMALIZE if normalize else 0, ctypes.c_void_p(x3.data_ptr()), C, xcs,
+            ctypes.c_void_p(g.data_ptr()), gs, gcs, gbs, ctypes.c_void_p(out.data_ptr()))
+    if handle is None:
+        B.check(getattr(B.lib(), device_call)(ctypes.byref(params), L, dev, _stream_ptr(torch, dev), *tail))
+    else:
+        B.check(getattr(B.lib(), table_call)(handle, ctypes.byref(params), L, _stream_ptr(torch, dev), *tail))
+    return out
+
+
+def stft_beamform_istft(params, x, weights, n_fft, hop, *, win_length=None, center=True, pad_mode="reflect", length=None, normalize=True,
+                        shift=None, out=None, table=None):
+    """A filter-and-sum beamformer (delay-and-sum, MVDR, GEV, ...) over C channels in ONE launch (bhw_beam_fft_f32_device): stft() of
+    every channel, a complex weight per channel and bin, the sum over the channels in the frequency domain and ONE istft() -- C forward
+    transforms and one inverse per output frame, no spectrum in memory.  x (C, T) or (B, C, T), float32, 1 <= C <= 64; weights
+    complex64 (C, K), (C, F, K) or (1 | B, C, 1 | F, K), K = n_fft // 2 + 1, F the frames stft() gives, the last axis contiguous.  A
+    batch or frame axis of size 1 or stride 0 (an expand() view) is never materialised; a conjugate view is resolved first; a
+    broadcast CHANNEL axis raises (the same weights on every channel are x.sum(-2) and stft_cmask_istft).  Returns float32
+    (B, length), or (length,) for 2-D x; length defaults to T.  With Y_c = bhw.stft(params, x[..., c, :], n_fft, hop, ...) and
+    G_c = weights[..., c, :, :], in separate float32 operations,
+
+        P_c.real = Y_c.real * G_c.real - Y_c.imag * G_c.imag        P_c.imag = Y_c.real * G_c.imag + Y_c.imag * G_c.real
+
+    -- stft_cmask_istft()'s formula -- and Z = P_0, then Z = Z + P_c for c = 1 .. C - 1 per part, in that order.  The result equals
+    bhw.istft(params, Z, n_fft, hop, ..., length=length, normalize=normalize) BIT FOR BIT: what eager float32 torch operations on the
+    two planes give in a Python loop over the channels.  The weights are applied as given: for w^H x pass w.conj().  Bins 0 and
+    n_fft / 2 behave per channel as in stft_cmask_istft(); with C = 1 the call equals stft_cmask_istft() bit for bit.  n_fft: a power
+    of two in 16..2048.  ValueError naming what takes it, before any device is asked for: real weights, complex x (the I/Q beamformer
+    is not built: stft_cmask_istft_iq per channel and a sum), a mixed-radix n_fft (stft_beamform_istft_mixed), 4096 (stft, the weights
+    and a sum, istft).  `out`, `table` and the other keywords are stft_cmask_istft()'s (bhw_beam_fft_f32_from_table)."""
+    import torch as host_torch                            # the refusals look at no device: they come before _torch() asks for one
+    _beam_refusals(host_torch, x, weights, n_fft, False)
+    torch = _torch()
+    return _stft_beamform_istft(torch, params, x, weights, n_fft, hop, win_length, center, pad_mode, length, normalize, shift, out, table,
+                                _fft_input, "bhw_beam_fft_f32_device", "bhw_beam_fft_f32_from_table")
+
+
+def stft_beamform_istft_mixed(params, x, weights, n_fft, hop, *, win_length=None, center=True, pad_mode="reflect", length=None,
+                              normalize=True, shift=None, out=None, table=None):
+    """stft_beamform_istft() at the n_fft of stft_mixed() in ONE launch (bhw_beam_mfft_f32_device): n_fft even, 2^a·3^b·5^c, no power
+    of two, from 18 to 2000 -- 320, 400, 480, 960, 1000, 1200, 1920.  The arguments, the layouts of x and of the weights, the formula
+    and the order of the sum are stft_beamform_istft()'s, with stft_mixed() and istft_mixed() as the transforms: the result equals
+    istft_mixed() of the summed rows BIT FOR BIT, and stft_cmask_istft_mixed() at C = 1.  ValueError naming what takes it: real
+    weights, complex x (stft_cmask_istft_iq_mixed per channel and a sum), a power of two (stft_beamform_istft), an n_fft of 2048 or
+    more (stft_mixed, the weights and a sum, istft_mixed).  `table`: bhw_beam_mfft_f32_from_table."""
+    import torch as host_torch
+    _beam_refusals(host_torch, x, weights, n_fft, True)
+    torch = _torch()
+    return _stft_beamform_istft(torch, params, x, weights, n_fft, hop, win_length, center, pad_mode, length, normalize, shift, out, table,
+                                _mfft_input, "bhw_beam_mfft_f32_device", "bhw_beam_mfft_f32_from_table")
+
+
 # ---- the same for I/Q input: a real or complex gain on every one of the n_fft bins ---------------------------------------------------------
 
 def _mask_iq_refusals(torch, x, mask, n_fft, complex_gains, mixed):

@@ -1719,6 +1719,65 @@ int bhw_cmask_cmfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t le
 int bhw_describe_cmask_cmfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
                              uint64_t g_stride, uint64_t g_batch_stride, char *buf, uint64_t len);
 
+/* Fused multichannel FILTER-AND-SUM: STFT of every channel, a complex weight per channel and bin, the sum over the channels in the
+ * frequency domain and ONE inverse STFT -- a delay-and-sum, MVDR, GEV or any other filter-and-sum beamformer over n_ch microphone
+ * channels, in one launch.  Per output frame: n_ch forward transforms and one inverse; no spectrum reaches memory and there is no
+ * workspace.  bhw_beam_fft_f32_*: n_fft a power of two in 16..2048; bhw_beam_mfft_f32_*: even 2^a 3^b 5^c in 18..2000, no power of
+ * two (73 sizes).  The arguments are those of bhw_cmask_fft_f32_* (bhw_cmask_mfft_f32_*), word for word, with these additions:
+ *   - n_ch: the channels of one signal, 1..BHW_BEAM_MAX_CH.  sa->batch == ss->batch == B counts OUTPUT signals: d_out is (B, T_out),
+ *     one signal per group of n_ch channels.
+ *   - x_ch_stride: floats between the channels of one signal; 0 = sa->samples, otherwise at least that.  Channel c of signal b starts
+ *     at d_x + b * sa->x_stride + c * x_ch_stride.  sa->x_stride 0 = n_ch channel strides, otherwise at least
+ *     (n_ch - 1) * x_ch_stride + samples.  Floats between the channels and between the signals are never read.
+ *   - g_ch_stride: PAIRS between the gain rows of the channels, as g_stride and g_batch_stride count pairs.  The gain row of frame f
+ *     of channel c of signal b starts at d_g + 2 * (b * g_batch_stride + c * g_ch_stride + f * g_stride).  g_stride and
+ *     g_batch_stride may be 0 (one row for every frame; the same weights for every signal).  g_ch_stride is at least
+ *     (frames - 1) * g_stride + K and may not be 0 when n_ch > 1: equal weights on every channel are a sum of the channels of x in
+ *     front of bhw_cmask_*, and the refusal says so.  A nonzero g_batch_stride is at least (n_ch - 1) * g_ch_stride +
+ *     (frames - 1) * g_stride + K.  Pairs between the rows are never read.
+ *   - The rows, exact and without tolerance.  With Y_c[b, f, k] = (re, im) the pair bhw_stft_fft_f32_* (bhw_stft_mfft_f32_*) writes
+ *     for channel c of signal b under (sa, flags 0) and (gr, gi) that channel's gain of the bin,
+ *         P_c.re = fl32( fl32(re * gr) - fl32(im * gi) )
+ *         P_c.im = fl32( fl32(re * gi) + fl32(im * gr) )
+ *     as in bhw_cmask_*, and the sum runs per part in float32 in ascending channel order: Z = P_0, then Z = fl32(Z + P_c) for
+ *     c = 1 .. n_ch - 1.  Nothing is contracted.  d_out is exactly what bhw_istft_fft_f32_* (bhw_istft_mfft_f32_*) writes for
+ *     (ss, flags) from the rows Z: WORD FOR WORD.  This is what eager float32 operations on the two planes give in a loop over the
+ *     channels.  The weights are applied as given: a caller with w^H x passes conj(w).
+ *   - Bins 0 and n_fft / 2 behave per channel as in bhw_cmask_*: the forward parents store im = 0 there and the inverse parents read
+ *     only the real part of the sum.  With n_ch == 1 the call equals bhw_cmask_fft_f32_* (bhw_cmask_mfft_f32_*) bit for bit.
+ *   - Determinism: an output's bits depend only on the window, the geometry, the flags, the samples of the channels and the gains
+ *     under its frames, never on the batch, the grid, or library versus table.  IEEE: a NaN or infinity in one sample of one channel,
+ *     or in one part of one gain pair, reaches exactly the outputs under the frames concerned.  ss->samples 0 -> BHW_OK.  d_out
+ *     overlaps neither any channel of d_x nor d_g.  No workspace, no allocation, no float atomics; both forms can be captured in a
+ *     HIP graph.  The checks go in the order of bhw_cmask_*: n_ch behind the fields the descriptors share, the channel strides with
+ *     the gain strides, the extents (up to 2^60 elements, the channel axis included) and the overlaps last.
+ *   - BHW_ERR_UNSUPPORTED in the sentences of bhw_cmask_*, about "the fused beamformer": channels 2 names the I/Q transforms, 4096
+ *     and the mixed-radix lengths above 2047 the pairs of transforms, the other family's sizes bhw_beam_mfft_f32_* /
+ *     bhw_beam_fft_f32_*.
+ *   - Not built: I/Q input (bhw_cmask_cfft_f32_* per channel and a sum take it); real gains; more than one output beam a launch;
+ *     weights computed in the kernel.
+ *   - bhw_describe_beam_fft / _mfft: bhw_describe_cmask_fft's / _mfft's line -- the plan IS that call's for B signals: the sums live
+ *     in registers -- beginning "beam", naming k_beam_*_direct / _table and saying "channels C" and the three gain strides. */
+#define BHW_BEAM_MAX_CH 64u
+int bhw_beam_fft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *sa, const bhw_stft *ss,
+                            uint32_t flags, const float *d_x, uint32_t n_ch, uint64_t x_ch_stride, const float *d_g, uint64_t g_stride,
+                            uint64_t g_ch_stride, uint64_t g_batch_stride, float *d_out);
+int bhw_beam_fft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *sa, const bhw_stft *ss,
+                                uint32_t flags, const float *d_x, uint32_t n_ch, uint64_t x_ch_stride, const float *d_g, uint64_t g_stride,
+                                uint64_t g_ch_stride, uint64_t g_batch_stride, float *d_out);
+int bhw_describe_beam_fft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
+                          uint32_t n_ch, uint64_t x_ch_stride, uint64_t g_stride, uint64_t g_ch_stride, uint64_t g_batch_stride, char *buf,
+                          uint64_t len);
+int bhw_beam_mfft_f32_device(const bhw_params *p, uint64_t length, int device, void *hip_stream, const bhw_stft *sa, const bhw_stft *ss,
+                             uint32_t flags, const float *d_x, uint32_t n_ch, uint64_t x_ch_stride, const float *d_g, uint64_t g_stride,
+                             uint64_t g_ch_stride, uint64_t g_batch_stride, float *d_out);
+int bhw_beam_mfft_f32_from_table(bhw_table t, const bhw_params *p, uint64_t length, void *hip_stream, const bhw_stft *sa, const bhw_stft *ss,
+                                 uint32_t flags, const float *d_x, uint32_t n_ch, uint64_t x_ch_stride, const float *d_g, uint64_t g_stride,
+                                 uint64_t g_ch_stride, uint64_t g_batch_stride, float *d_out);
+int bhw_describe_beam_mfft(bhw_table t, const bhw_params *p, uint64_t length, const bhw_stft *sa, const bhw_stft *ss, uint32_t flags,
+                           uint32_t n_ch, uint64_t x_ch_stride, uint64_t g_stride, uint64_t g_ch_stride, uint64_t g_batch_stride, char *buf,
+                           uint64_t len);
+
 /* Threading: every entry point may be called from any host thread.  Calls that use the library-owned scratch of one
  * (device, stream) are serialised against each other for the duration of their launches (the table is rebuilt per call);
  * callers that pass their own bhw_exec.workspace must not share one workspace between concurrent calls.  The calling
